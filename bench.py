@@ -1,12 +1,20 @@
 #!/usr/bin/env python3
 """Headline benchmark: audio frames/s of the wake-word hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--model crnn|wavenet] [--clips 256]
+    python bench.py --gpus N --steps K --warmup W [--model crnn|wavenet] [--clips 256] [--dump-outputs DIR] [--full]
 
 One step = one pass of the whole hot path over one batch of synthetic 16 kHz clips that is
 already resident in HBM: int16 PCM [clips, 24000] -> log-mel -> one zero-padded window per
 clip -> encode + detect -> posteriors [clips, n_out]   (BASELINE.json configs[1] for CRNN,
 configs[2] for Wavenet; 1 audio frame = one 10 ms hop = 160 samples, 150 per 1.5 s clip).
+
+A plain run does what the headline needs and nothing else: set up, W warm-up steps, ONE timed
+region of exactly K steps (`ms_per_step` = that region / K), the result line.  --full adds
+everything below: repeated regions, roofline, single stream, the other precisions and models,
+streaming, evaluation and the CPU baseline.  --dump-outputs DIR writes what the timed path
+returned in its last timed step (step K-1: the posteriors, float32, as DIR/posteriors.npy; with
+N > 1 every rank's in rank order, as the gather delivers them).  The inputs are seeded: the same
+arguments give the same inputs run after run.
 
 N > 1.  Either something else started the ranks (torch.distributed.run sets WORLD_SIZE), or this
 process does it itself: with --gpus N and no WORLD_SIZE in the environment the parent - which
@@ -17,14 +25,15 @@ shard of clips (weak scaling, no data-path collective); the only exchange is the
 gather (all_gather of the K*clips*n_out floats each rank produced, RCCL over xGMI), done once
 at the end of every timed region, as the offline evaluator does after its shard is finished.
 
-Timing.  W untimed warm-up steps (at least one per pipelined context), then the region of
-EXACTLY K steps - barrier + synchronize on both sides, MAX over ranks - is repeated --repeats
-times; `value` / `ms_per_step` are those of the MEDIAN region and `timed_regions` holds
-min / median / max, so that a short K is not a single sample.  The input rotates over
+Timing.  W untimed warm-up steps (at least one per pipelined context; more, until 0.25 s of
+work has run, so that clocks are in steady state), then the region of
+EXACTLY K steps - barrier + synchronize on both sides, MAX over ranks.  With --full (or an
+explicit --repeats) it is repeated; `value` / `ms_per_step` are those of the MEDIAN region and
+`timed_regions` holds min / median / max, so that a short K is not a single sample.  The input rotates over
 --rotate (24) distinct resident batches whatever K is: 24 x 12.3 MB = 295 MB > the 256 MiB
 Infinity Cache, so a step's PCM comes from HBM.
 
-Rank 0 prints ONE JSON line (schema in the task contract) that also carries
+Rank 0 prints ONE JSON line with the headline fields; with --full it also carries
   roofline      - dominant kernel, HIP events around every launch (ww_profile_enable) in a
                   separate pass of the same steps, priced per DESIGN.md section 4
   cpu_baseline  - the C restatement in oracle/ (NOT TFLite) on this box's host cores, bounded
@@ -56,6 +65,7 @@ PEAK_HBM = 8.0e12
 PEAK_BF16_MFMA = 2.5e15   # dense bf16, MI355X_MICROARCH.md
 PEAK_F64_VALU = 78.6e12   # fp64 vector FMA peak
 N_SIMD = 1024             # 256 CUs x 4
+WARM_SECONDS = 0.25       # the headline's warm-up runs at least this long (Job.warm)
 VALU_CYCLES_PER_INST = 3.7  # measured: tools/pmc_calib.hip (v_fma_f32, >= 2 waves per SIMD); fp64 ops issue at the same rate (tools/valu_probe.hip)
 
 
@@ -246,10 +256,17 @@ class Job:
             self.dist.barrier()
         self.torch.cuda.synchronize()
 
-    def warm(self, n, fp):
-        for k in range(n):
-            self.step(k, fp)
-        self.sync()
+    def warm(self, n, fp, min_seconds=0.0):
+        """n steps, then rounds of 64 more until min_seconds of synchronised work have passed: a region timed after a
+        millisecond of warm-up ran ~2.5 % slower than one timed after 0.1 s (clocks not yet in steady state)."""
+        k, t0 = 0, time.perf_counter()
+        while True:
+            for _ in range(n if k == 0 else 64):
+                self.step(k, fp)
+                k += 1
+            self.sync()
+            if time.perf_counter() - t0 >= min_seconds:
+                break
         if self.dist is not None:  # the communicator too, outside the timed regions - and the gather alone, timed
             import numpy as np
             ts = []
@@ -294,6 +311,17 @@ class Job:
             self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
             el = float(t.item())
         return el, own
+
+    def last_outputs(self):
+        """What a caller of the timed path holds after the last region's last step (K-1): its posteriors [clips, n_out]; with a
+        process group, every rank's in rank order as the region's gather delivered them [world * clips, n_out]."""
+        if self.dist is None:
+            return self.d_all[self.K - 1].cpu().numpy()
+        if self.comm_dev == "cuda":
+            last = self.gathered[:, self.K - 1]
+        else:
+            last = self.torch.stack([t[self.K - 1] for t in self.gathered])
+        return last.reshape(-1, self.n_out).cpu().numpy()
 
     def regions(self, n, fp, only0=False):
         import numpy as np
@@ -825,8 +853,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions of K steps each (median reported); 0 = auto: "
-                    "enough regions for >= 1 s of timed work, between 5 and 2001")
+    ap.add_argument("--repeats", type=int, default=0, help="timed regions of K steps each (median reported); 0 = one region, "
+                    "or with --full enough regions for >= 1 s of timed work, between 5 and 2001")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: repeated regions, "
+                    "roofline, single stream, the other precisions and models, streaming, evaluation, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the posteriors of the last timed step to DIR/posteriors.npy")
     ap.add_argument("--model", choices=["crnn", "wavenet"], default="crnn")
     ap.add_argument("--clips", type=int, default=256)
     ap.add_argument("--rotate", type=int, default=24, help="distinct resident input batches to rotate over")
@@ -837,6 +868,7 @@ def main():
     ap.add_argument("--precision", choices=["auto", "fp32", "bf16x3"], default="auto",
                     help="model contractions: fp32 MFMA, or (Wavenet only) three bf16 MFMAs on split operands with "
                          "fp32 accumulate; auto = fp32 for CRNN (BASELINE cfg 2), bf16x3 for Wavenet (cfg 3)")
+    # (the options below shape the --full legs)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="headline job only: skip the wavenet / streaming / eval legs")
     ap.add_argument("--stream-ticks", type=int, default=10000)
@@ -906,18 +938,21 @@ def main():
         d_pcm.append(torch.roll(d_pcm[0], shifts=37 * r, dims=1) * (1 if r % 2 == 0 else -1))
     torch.cuda.synchronize()
 
-    def run_model(model, precision, want_profile):
+    def run_model(model, precision, want_profile, want_last=False):
         engs = [Engine(os.path.join(assets, "CRNN" if model == "crnn" else "Wavenet"), device=local_rank, ctx=c,
                        precision=precision) for c in ctxs]
         job = Job(torch, engs, ctxs, d_pcm, args.clips, K, dist, comm_dev, world)
-        job.warm(W, fp)
+        job.warm(W, fp, WARM_SECONDS)
         n_rep = args.repeats
+        if n_rep <= 0 and not args.full:
+            n_rep = 1  # the plain run: exactly K timed steps
         if n_rep <= 0:
             probe = sorted(job.region(fp)[0] for _ in range(3))[1]  # (the median of three: one slow probe region must not halve the count)
             # >= 1 s of timed headline work (round 5 timed 41 regions of 1 ms under the driver's --steps 20: 39 ms in all)
             n_rep = int(min(2001, max(5, 1.1 / max(probe, 1e-6)))) | 1
         stats, med = job.regions(n_rep, fp)
         res = {"engs": engs, "job": job, "stats": stats, "median_s": med}
+        res["last"] = job.last_outputs() if want_last else None
         res["posts"] = job.d_all[:min(K, R)].cpu().numpy()
         if want_profile:
             job.warm(1, fp)
@@ -932,13 +967,13 @@ def main():
     precision = args.precision if args.precision != "auto" else ("fp32" if args.model == "crnn" else "bf16x3")
     if args.model == "crnn":
         precision = "fp32"
-    head = run_model(args.model, precision, True)
+    head = run_model(args.model, precision, args.full, want_last=bool(args.dump_outputs))
     eng = head["engs"][0]
 
     # ---- same regions with the fp32-FFT front end (precise=0), reported as a side figure:
     # posteriors stay within 5e-6 of the fp64-FFT path (tools/f32_error.py), log-mel within 1.4e-4
     alt = None
-    if not args.fast_frontend:
+    if args.full and not args.fast_frontend:
         fp_fast = frontend_params(32767.0, True, 0.0, 160, False)
         head["job"].warm(P, fp_fast)
         s, m = head["job"].regions(max(3, head["stats"]["n"] // 2) | 1, fp_fast)
@@ -948,7 +983,7 @@ def main():
     # ---- CRNN only: the same regions with conv + projection on split-bf16 MFMA (ww_model_set_precision(BF16X3)); fp32 stays
     # the headline (BASELINE configs[1] is an fp32 configuration), this is what the bf16 matrix pipe buys at <= 3e-5 on posteriors
     alt_bf16 = fast_profile = None
-    if args.model == "crnn" and precision == "fp32" and not args.fast_frontend:
+    if args.full and args.model == "crnn" and precision == "fp32" and not args.fast_frontend:
         for e in head["engs"]:
             e.set_precision("bf16x3")
         head["job"].warm(P, fp)
@@ -982,7 +1017,7 @@ def main():
             e.close()
 
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         # ---- BASELINE configs[2] (or configs[1] when the headline is the Wavenet): the other model, same regions
         if args.model == "crnn":
             wv = run_model("wavenet", "bf16x3", True)
@@ -1011,7 +1046,9 @@ def main():
 
     if rank == 0:
         med = head["median_s"]
-        roof = roofline_of(eng, head["prof"], args.clips, args.fast_frontend, step_s=med / K)
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "posteriors.npy"), np.ascontiguousarray(head["last"], dtype=np.float32))
         line = {
             "metric": "audio frames/sec (16 kHz, 40-mel, 10 ms hop) + FRR@0.5 FA/h",
             "value": throughput(world, K, args.clips, med),
@@ -1041,23 +1078,21 @@ def main():
             "timed_regions": dict(head["stats"], note="each region = exactly `steps` steps; barrier+synchronize in front, the clock "
                                   "stops when the posterior gather (N > 1) has completed on the rank, MAX over ranks; value and "
                                   "ms_per_step are the median region's; collective_ms = the gather alone (warm-up, median of 4)"),
-            "roofline": roof,
             "posterior_checksum": float(np.sum(head["posts"][0], dtype=np.float64)),
-            "single_stream": head["single"],
-            "alt_fp32_fft_frontend": alt,
-            "alt_crnn_split_bf16": alt_bf16,
-            "fast_profile": fast_profile,
         }
         if world > 1 and backend != "nccl":
             line["config"]["rehearsal"] = f"{backend} backend, ranks share {n_dev} physical GPU(s): not a scaling measurement"
-        line.update(extra)
-        if extra.get("eval_testset"):
-            line["frr_at_0.5_fa_per_hour"] = extra["eval_testset"]["frr_at_0.5_fa_per_hour"]
-        if not args.no_cpu_baseline and world == 1:
-            line["cpu_baseline"] = cpu_baseline(eng, pcm0, float(os.environ.get("WW_BENCH_CPU_SECONDS", "10")))
-        elif not args.no_cpu_baseline:
-            line["cpu_baseline"] = None
-        line["summary"] = summary_of(line)  # LAST key: the driver's record keeps the last 8 KB of this line
+        if args.full:
+            line["roofline"] = roofline_of(eng, head["prof"], args.clips, args.fast_frontend, step_s=med / K)
+            line.update(single_stream=head["single"], alt_fp32_fft_frontend=alt, alt_crnn_split_bf16=alt_bf16, fast_profile=fast_profile)
+            line.update(extra)
+            if extra.get("eval_testset"):
+                line["frr_at_0.5_fa_per_hour"] = extra["eval_testset"]["frr_at_0.5_fa_per_hour"]
+            if not args.no_cpu_baseline and world == 1:
+                line["cpu_baseline"] = cpu_baseline(eng, pcm0, float(os.environ.get("WW_BENCH_CPU_SECONDS", "10")))
+            elif not args.no_cpu_baseline:
+                line["cpu_baseline"] = None
+            line["summary"] = summary_of(line)  # LAST key: a reader that keeps only the line's tail still finds every figure
         print(json.dumps(line), flush=True)
     close(head)
     if dist is not None:

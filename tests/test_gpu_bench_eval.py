@@ -26,9 +26,9 @@ def _bench(args, env=None, timeout=900):
 
 
 def test_bench_line_honours_the_contract():
-    """`python bench.py --steps K --warmup W` prints ONE JSON line with the driver's fields, the roofline of the
+    """`python bench.py --full --steps K --warmup W` prints ONE JSON line with the headline fields, the roofline of the
     dominant kernel, the CPU baseline, and the legs for BASELINE configs[0], [2], [3]-as-1-rank and [4]."""
-    d = _bench(["--steps", "40", "--warmup", "4", "--stream-ticks", "300", "--eval-clips", "256"])
+    d = _bench(["--full", "--steps", "40", "--warmup", "4", "--stream-ticks", "300", "--eval-clips", "256"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "timed_regions", "single_stream",
                 "wavenet", "streaming", "eval_testset", "frr_at_0.5_fa_per_hour"):
@@ -92,11 +92,40 @@ def test_bench_line_honours_the_contract():
     assert all(v is not None for v in sm["cfg4"].values()) and sm["frr_at_0.5_fa_per_hour"] == sm["frr_oracle"]
 
 
+def test_plain_bench_times_exactly_the_steps_and_dumps_the_last_one(tmp_path, assets):
+    """`python bench.py --steps K --warmup W` without --full: ONE region of exactly K steps, the headline fields and none of the
+    legs; --dump-outputs writes the posteriors of step K-1, which reads resident batch (K-1) mod 24 - here batch 1, the seeded
+    synthetic PCM rolled by 37 samples and negated - and they equal the oracle's on that input."""
+    import bench
+    from oracle.cpu import CpuOracle
+    from wwhip.engine import Engine
+    K, out = 26, tmp_path / "out"
+    d = _bench(["--steps", str(K), "--warmup", "4", "--dump-outputs", str(out)])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "timed_regions"):
+        assert key in d, key
+    assert d["steps"] == K and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert not {"roofline", "single_stream", "wavenet", "streaming", "eval_testset", "cpu_baseline", "summary"} & set(d)
+    tr = d["timed_regions"]
+    assert tr["n"] == 1 and abs(tr["median_ms"] - d["ms_per_step"] * K) < 1e-6 * tr["median_ms"] + 1e-9
+    assert abs(d["value"] - K * 256 * 150 / (d["ms_per_step"] * K * 1e-3)) / d["value"] < 1e-6
+    got = np.load(out / "posteriors.npy")
+    eng = Engine(os.path.join(assets, "CRNN"))
+    assert got.dtype == np.float32 and got.shape == (256, eng.n_out)
+    pcm = -np.roll(bench.synth_pcm(np.random.default_rng(1000), 256), 37, axis=1)
+    ora = CpuOracle(eng.blob)
+    wins = np.zeros((32, eng.window, 40), np.float32)
+    for i, c in enumerate(pcm[::8]):
+        mel = ora.logmel(c)
+        wins[i, :min(len(mel), eng.window)] = mel[:eng.window]
+    assert np.abs(got[::8] - ora.forward(wins)).max() < TOL
+    eng.close()
+
+
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no WORLD_SIZE: the parent (no torch, no GPU) starts two child ranks and relays
     rank 0's line.  One-GPU box: gloo rehearsal, both ranks on GPU 0 - the line says so."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "12", "--warmup", "4",
                         "--stream-ticks", "100", "--eval-clips", "128", "--eval-scale", "40"], capture_output=True, text=True, timeout=900,
                        env=dict(env, WW_BENCH_BACKEND="gloo", WW_BENCH_CPU_SECONDS="1"))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -113,14 +142,15 @@ def test_bench_starts_its_own_ranks():
     assert d["config"]["cpus_per_rank"] >= 1
 
 
-def test_bench_under_torch_distributed_run():
+def test_bench_under_torch_distributed_run(tmp_path):
     """The driver's launch form for N > 1: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port P bench.py --gpus N --steps K --warmup W` - the ranks come from the launcher (RANK / WORLD_SIZE in the environment),
     bench.py must not start its own.  One-GPU box: gloo rehearsal.  The evaluation leg's numbers equal the one-rank line's."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                        "127.0.0.1", "--master-port", "29668", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12",
-                        "--warmup", "4", "--stream-ticks", "100", "--eval-clips", "256", "--eval-scale", "60"], capture_output=True, text=True, timeout=900,
+                        "127.0.0.1", "--master-port", "29668", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "12",
+                        "--warmup", "4", "--stream-ticks", "100", "--eval-clips", "256", "--eval-scale", "60", "--dump-outputs", str(tmp_path / "two")],
+                       capture_output=True, text=True, timeout=900,
                        env=dict(env, WW_BENCH_BACKEND="gloo", WW_BENCH_CPU_SECONDS="1"))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -129,7 +159,13 @@ def test_bench_under_torch_distributed_run():
     assert d["n_gpus"] == 2 and d["steps"] == 12 and d["eval_testset"]["world_size"] == 2 and d["cpu_baseline"] is None
     tr = d["timed_regions"]
     assert tr["collective_ms"] > 0 and 0 < tr["per_rank_median_ms"]["min"] <= tr["per_rank_median_ms"]["max"]
-    one = _bench(["--steps", "12", "--warmup", "4", "--stream-ticks", "100", "--eval-clips", "256", "--eval-scale", "60", "--no-cpu-baseline"])
+    one = _bench(["--full", "--steps", "12", "--warmup", "4", "--stream-ticks", "100", "--eval-clips", "256", "--eval-scale", "60", "--no-cpu-baseline",
+                  "--dump-outputs", str(tmp_path / "one")])
+    # the last step's posteriors as the gather delivers them: rank 0's rows (its PCM is the one-rank run's) first, then rank 1's
+    two_post, one_post = np.load(tmp_path / "two" / "posteriors.npy"), np.load(tmp_path / "one" / "posteriors.npy")
+    assert two_post.shape == (2 * 256, 1) and one_post.shape == (256, 1)
+    np.testing.assert_array_equal(two_post[:256], one_post)
+    assert not np.array_equal(two_post[256:], one_post)
     for k in ("frr_at_0.5_fa_per_hour", "fa_count_at_threshold_0.5", "posterior_checksum", "windows", "negative_hours"):
         assert d["eval_testset"][k] == one["eval_testset"][k], k
     a2, a1 = d["eval_testset"]["at_scale"], one["eval_testset"]["at_scale"]    # the at-scale leg (reduced here): 2 ranks = 1 rank
@@ -385,16 +421,18 @@ def test_fp32_fft_front_end_leaves_far_frr_untouched(testset_one_rank, reference
     assert fast_ref["frr_at_0.5_fa_per_hour"] == ref["frr_at_0.5_fa_per_hour"]
 
 
-def test_bench_rccl_path_at_world_size_one():
+def test_bench_rccl_path_at_world_size_one(tmp_path):
     """The multi-GPU runs use the `nccl` (= RCCL) backend with device tensors in the posterior gather and the timing
     reductions; a one-GPU box can at least run that code at world size 1 (WW_BENCH_FORCE_DIST=1)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "4", "--no-extra",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "12", "--warmup", "4", "--no-extra",
+                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600,
                        env=dict(env, WW_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["timed_regions"]["n"] >= 5
+    post = np.load(tmp_path / "posteriors.npy")  # the last step as the RCCL gather delivered it
+    assert post.shape == (256, 1) and post.dtype == np.float32 and ((post >= 0) & (post <= 1)).all()
 
 
 def test_posterior_gather_over_rccl(tmp_path):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Development: the few numbers of a bench.py line one looks at first.  usage: bench_summary.py line.json"""
+"""Development: the few numbers of a `bench.py --full` line one looks at first.  usage: bench_summary.py line.json"""
 import json, sys
 d = json.load(open(sys.argv[1]))
 print("value %.4g frames/s, %.2f us/step; single stream %.2f us/step; regions %s" % (
