@@ -275,6 +275,11 @@ int ww_stream_destroy(ww_streams *st);
 int ww_stream_step(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post);
 /* WakewordTrigger.reset (tflite.py:241-246) for the listed streams (ids NULL -> all). */
 int ww_stream_reset(ww_streams *st, const int32_t *ids, int32_t n);
+/* Read-out for tests and tools: stream `stream`'s newest mel window - the T x n_mel block the model reads, the T rows that end at
+ * the last row written (all-zero rows in front of a stream's first rows and after a reset) - copied to host memory `out`
+ * (T * n_mel floats, row-major) after the context's stream has been synchronised.  Touches no state of the bank.  WW_EINVAL for
+ * a stream id out of range. */
+int ww_stream_window(ww_streams *st, int32_t stream, float *out);
 /* ---- the pipeline's host stages for S streams in lock step (BASELINE config 5 at the plugin surface) --------------------------
  * The reference drives three stage objects per stream and 20 ms frame (spokestack/pipeline.py:25-28, stage list of demo.py:29-36),
  * each a few comparisons on the shared SpeechContext.  For S streams each stage is ONE pass over plain arrays the caller owns

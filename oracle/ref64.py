@@ -34,6 +34,8 @@ class Ref64:
         self.m = ModelDir(model_dir, dtype=np.float64)
         self.is_crnn = self.m.is_crnn
         self.name = os.path.basename(os.path.normpath(model_dir))
+        self.model_dir = model_dir
+        self._fe = None
 
     def _x(self, window: np.ndarray) -> np.ndarray:
         w = np.asarray(window, np.float64)
@@ -56,6 +58,21 @@ class Ref64:
     def filter(self, mag: np.ndarray) -> np.ndarray:
         """``[n, 257]`` STFT magnitudes -> ``[n, 40]`` log-mel (filter.tflite alone)."""
         return np.asarray(self.m.filter(np.asarray(mag, np.float64))[0], np.float64)
+
+    @property
+    def frontend(self) -> "FrontEnd64":
+        if self._fe is None:
+            self._fe = FrontEnd64(self.model_dir)
+        return self._fe
+
+    def logmel(self, pcm: np.ndarray, divisor: float = 32767.0, clip: bool = True, preemph: float = 0.0,
+               hop: int = 160) -> "LogMel64":
+        """int16 utterance -> float64 log-mel rows with their error scales (``FrontEnd64.logmel``)."""
+        return self.frontend.logmel(pcm, divisor, clip, preemph, hop)
+
+    def logmel_f32(self, x: np.ndarray, preemph: float = 0.0, hop: int = 160) -> "LogMel64":
+        """float32 utterance (no divisor, no clip) -> float64 log-mel rows (``FrontEnd64.logmel_f32``)."""
+        return self.frontend.logmel_f32(x, preemph, hop)
 
 
 def logit(p: np.ndarray) -> np.ndarray:
@@ -266,3 +283,238 @@ def stream_windows(mel: np.ndarray, T: int) -> np.ndarray:
     frame; one window per row of ``mel``."""
     hist = np.concatenate([np.zeros((T, mel.shape[1]), np.float32), np.asarray(mel, np.float32)])
     return np.lib.stride_tricks.sliding_window_view(hist, (T, mel.shape[1]))[1:, 0]
+
+
+# ---------------------------------------------------------------------------------------------------------------- front end
+# The log-mel front end in float64 from the reference's input quantisation on: int16 -> float32 / divisor, clip, pre-emphasis
+# x - float32(pre) * prev in float32 with prev = 0 at the start of an utterance (oracle/numpy_ref.RefFilter), all part of the
+# specification; then np.hanning(512), np.fft.rfft, |X| and the filter graph's weights in float64.
+#
+# check_logmel's bound follows where an fp32 front end's error comes from.  A band's energy e = W|X| + b is summed in fp32 from
+# |X| rounded to fp32 (relative to A = |W||X| + |b|: tau_rel), and every |X| carries the transform's error, which scales with
+# the frame's 2-norm and not with the bin (N = ||hann x||_2 sum|W|: tau_fft).  Both reach y = scale (ln max(e, floor) + off) as a
+# relative error in max(e, floor), so a band next to the floor in a loud frame is held to the frame's 2-norm, not to its own
+# tiny energy.  On top: a few fp32 ulps of the log and of the log plus its offset (the irreducible rounding of logf and of the
+# sum) - -11.5 at the floor, where fp32's spacing is 9.5e-7.
+
+WIN = 512
+HANN64 = np.hanning(WIN)
+
+
+class LogMel64:
+    """Float64 log-mel rows and what bounds a kernel's error on them, per element ``[rows, n_mel]``: ``y`` the log-mel value,
+    ``e`` the mel energy ``W|X| + b``, ``A = |W||X| + |b|``, ``N = ||hann x||_2 sum|W|``; ``floor`` and ``scale`` of the
+    filter; ``mag`` the rows' ``|X|`` ``[rows, 257]`` and ``norm`` their ``||hann x||_2``."""
+
+    def __init__(self, y, e, A, N, floor, scale, mag, norm):
+        self.y, self.e, self.A, self.N, self.floor, self.scale, self.mag, self.norm = y, e, A, N, floor, scale, mag, norm
+
+    def __len__(self):
+        return len(self.y)
+
+    def __getitem__(self, i):
+        return LogMel64(self.y[i], self.e[i], self.A[i], self.N[i], self.floor, self.scale, self.mag[i], self.norm[i])
+
+    @staticmethod
+    def concat(parts):
+        parts = list(parts)
+        cat = [np.concatenate([getattr(p, k) for p in parts]) for k in ("y", "e", "A", "N")]
+        return LogMel64(*cat, parts[0].floor, parts[0].scale, np.concatenate([p.mag for p in parts]),
+                        np.concatenate([p.norm for p in parts]))
+
+
+def quantise(pcm: np.ndarray, divisor: float = 32767.0, clip: bool = True) -> np.ndarray:
+    """int16 -> float32 / divisor, clipped to [-1, 1] if asked (wakeword/tflite.py:150-151 with the divisor a parameter)."""
+    x = np.asarray(pcm, np.int16).astype(np.float32) / np.float32(divisor)
+    return np.clip(x, np.float32(-1.0), np.float32(1.0)) if clip else x
+
+
+def preemphasise(x: np.ndarray, preemph: float) -> np.ndarray:
+    """``x - float32(pre) * prev`` in float32, ``prev`` = the previous input sample, 0 before the first."""
+    x = np.asarray(x, np.float32)
+    if preemph == 0.0:
+        return x.copy()
+    prev = np.concatenate([np.zeros(1, np.float32), x[:-1]])
+    return x - np.float32(preemph) * prev
+
+
+def frames_of(x: np.ndarray, hop: int) -> np.ndarray:
+    """The 512-sample frames at offsets 0, hop, 2 hop ... that lie wholly inside ``x`` (``[n, 512]``, a view)."""
+    x = np.asarray(x)
+    nf = (len(x) - WIN) // hop + 1 if len(x) >= WIN else 0
+    if nf == 0:
+        return np.zeros((0, WIN), x.dtype)
+    return np.lib.stride_tricks.sliding_window_view(x, WIN)[::hop][:nf]
+
+
+def stft64(frames: np.ndarray) -> np.ndarray:
+    """``[n, 512]`` frames (any float type, taken as they are) -> the complex float64 ``rfft(hann * frame)`` ``[n, 257]``."""
+    return np.fft.rfft(np.asarray(frames, np.float64).reshape(-1, WIN) * HANN64, axis=1)
+
+
+def frame_norms(X: np.ndarray) -> np.ndarray:
+    """``||hann x||_2`` of each frame, from its rfft (Parseval)."""
+    p = np.abs(np.asarray(X)) ** 2
+    return np.sqrt((p[:, 0] + p[:, -1] + 2.0 * p[:, 1:-1].sum(axis=1)) / WIN)
+
+
+def _filter_params(model_dir: str):
+    from wwhip import weights as W   # (tests put the package on the path)
+    return W.load_model_dir(model_dir).filt
+
+
+def mel64(filt, mag: np.ndarray, norm: np.ndarray) -> LogMel64:
+    """float64 ``|X|`` rows (and their frames' ``||hann x||_2``) through the filter graph in float64."""
+    w = np.asarray(filt.weight, np.float64)
+    b = np.asarray(filt.bias, np.float64)
+    mag = np.asarray(mag, np.float64).reshape(-1, w.shape[1])
+    e = mag @ w.T + b
+    A = mag @ np.abs(w).T + np.abs(b)
+    N = np.asarray(norm, np.float64).reshape(-1, 1) * np.abs(w).sum(axis=1)
+    y = (np.log(np.maximum(e, filt.floor)) + filt.log_offset) * filt.scale
+    return LogMel64(y, e, A, N, float(filt.floor), float(filt.scale), mag, np.asarray(norm, np.float64).ravel())
+
+
+def logmel64_samples(filt, x: np.ndarray, hop: int = 160) -> LogMel64:
+    """Normalised (and pre-emphasised) float32 samples -> float64 log-mel rows."""
+    X = stft64(frames_of(np.asarray(x, np.float32), hop))
+    return mel64(filt, np.abs(X), frame_norms(X))
+
+
+class FrontEnd64:
+    """The filter of a model directory (``wwhip.weights.load_model_dir(dir).filt``) behind the float64 front end."""
+
+    def __init__(self, model_dir: str) -> None:
+        self.filt = _filter_params(model_dir)
+
+    def logmel(self, pcm: np.ndarray, divisor: float = 32767.0, clip: bool = True, preemph: float = 0.0,
+               hop: int = 160) -> LogMel64:
+        """int16 utterance -> float64 log-mel rows (as ``Engine.logmel`` / ``CpuOracle.logmel`` frame it)."""
+        return logmel64_samples(self.filt, preemphasise(quantise(pcm, divisor, clip), preemph), hop)
+
+    def logmel_f32(self, x: np.ndarray, preemph: float = 0.0, hop: int = 160) -> LogMel64:
+        """float32 utterance (taken as it is: no divisor, no clip) -> float64 log-mel rows (``ww_logmel_f32``)."""
+        return logmel64_samples(self.filt, preemphasise(np.asarray(x, np.float32), preemph), hop)
+
+    def frame(self, frame512: np.ndarray) -> LogMel64:
+        """One already normalised and pre-emphasised 512-sample frame -> its float64 log-mel row."""
+        return logmel64_samples(self.filt, np.asarray(frame512, np.float32).reshape(WIN), WIN)
+
+
+def _ulp32(v: np.ndarray) -> np.ndarray:
+    return np.spacing(np.abs(np.asarray(v, np.float64)).astype(np.float32)).astype(np.float64)
+
+
+def _logmel_terms(got, ref: LogMel64, ulps: float):
+    g = np.asarray(got, np.float64).reshape(ref.y.shape)
+    d = np.maximum(ref.e, ref.floor)
+    ln = np.log(d)
+    u = ref.scale * ulps * np.maximum(_ulp32(ln), _ulp32(ref.y / ref.scale))
+    return np.abs(g - ref.y), u, ref.scale * ref.A / d, ref.scale * ref.N / d
+
+
+def logmel_ratios(got, ref: LogMel64, tau_rel: float, tau_fft: float, ulps: float = 2) -> np.ndarray:
+    """Per element: ``|y - y64| / bound`` (see check_logmel)."""
+    err, u, cA, cN = _logmel_terms(got, ref, ulps)
+    return err / (tau_rel * cA + tau_fft * cN + u)
+
+
+def needed_taus(got, ref: LogMel64, tau_rel: float = 0.0, tau_fft: float = 0.0, ulps: float = 2):
+    """``(tau_rel, tau_fft)``: the smallest tau_rel with which check_logmel accepts ``got`` at the given tau_fft, and the
+    smallest tau_fft at the given tau_rel (what a test measures and quotes).  Elements the term does not reach (an all-zero
+    frame: A = N = 0) are left out; check_logmel holds them to the ulps term."""
+    err, u, cA, cN = _logmel_terms(got, ref, ulps)
+    out = []
+    for fixed, coef in ((tau_fft * cN, cA), (tau_rel * cA, cN)):
+        excess = np.maximum(err - u - fixed, 0.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = np.where((excess > 0) & (coef > 0), excess / coef, 0.0)
+        out.append(float(t.max()) if t.size else 0.0)
+    return tuple(out)
+
+
+def check_logmel(got, ref: LogMel64, tau_rel: float, tau_fft: float, ulps: float = 2) -> float:
+    """Every element: ``|y - y64| <= scale (tau_rel A + tau_fft N) / max(e64, floor) + scale ulps ulp32(ln max(e64, floor))``
+    (ulp32 also taken at the log plus its offset, ``y64 / scale``).  Returns the worst ratio of error to bound (<= 1); raises
+    AssertionError naming the worst element otherwise."""
+    r = logmel_ratios(got, ref, tau_rel, tau_fft, ulps)
+    worst = float(r.max()) if r.size else 0.0
+    if not worst <= 1.0:
+        i, j = np.unravel_index(int(np.argmax(r)), r.shape)
+        g = np.asarray(got, np.float64).reshape(ref.y.shape)
+        need = needed_taus(got, ref, tau_rel, tau_fft, ulps)
+        raise AssertionError(f"log-mel row {i} band {j}: got {g[i, j]!r} want {ref.y[i, j]!r} (e64 {ref.e[i, j]:.3g}, "
+                             f"floor {ref.floor:.3g}, row max e64 {ref.e[i].max():.3g}): {worst:.3g} x the bound at "
+                             f"tau_rel={tau_rel:g}, tau_fft={tau_fft:g} (needs tau_rel {need[0]:.3g} or tau_fft {need[1]:.3g}); "
+                             f"{int((r > 1).sum())} of {r.size} elements fail")
+    return worst
+
+
+def stft_ratios(got, X64: np.ndarray, tau_rel: float, tau_fft: float) -> np.ndarray:
+    m = np.abs(np.asarray(X64))
+    g = np.asarray(got, np.float64).reshape(m.shape)
+    bound = tau_rel * m + tau_fft * frame_norms(X64)[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(g == m, 0.0, np.abs(g - m) / bound)
+
+
+def check_stft(got, X64: np.ndarray, tau_rel: float, tau_fft: float) -> float:
+    """Every bin: ``| m - |X64| | <= tau_rel |X64| + tau_fft ||hann x||_2``.  Returns the worst ratio (<= 1)."""
+    r = stft_ratios(got, X64, tau_rel, tau_fft)
+    worst = float(r.max()) if r.size else 0.0
+    if not worst <= 1.0:
+        i, k = np.unravel_index(int(np.argmax(r)), r.shape)
+        raise AssertionError(f"|X| frame {i} bin {k}: got {np.asarray(got).reshape(r.shape)[i, k]!r} want "
+                             f"{abs(X64[i, k])!r}: {worst:.3g} x the bound at tau_rel={tau_rel:g}, tau_fft={tau_fft:g}; "
+                             f"{int((r > 1).sum())} of {r.size} bins fail")
+    return worst
+
+
+def frontend_signals(seed: int = 0):
+    """Named int16 clips that cover where a front end goes wrong (an ordered dict): silence; +-1 and +-3 LSB dither (rows at the
+    floor); a DC offset (bin 0); alternating +-A (bin 256); fs/4 (bin 128, the untangle's self-partner); bin-centred tones at
+    k = 1, 2, 127, 129, 255 at full scale and at -40 dB; a loud tone plus +-1 LSB dither (more than 1e5 between the bands of a
+    row); single impulses at frame positions 0, 1, 255, 256, 510 and 511 of the hop-160 grid's fourth frame; a full-scale square
+    wave that reaches -32768 (clipped with divisor 32767, not with 32768); a chirp from 50 Hz to 8 kHz; white noise at 10, 100,
+    1,000 and 10,000 LSB; 1/f noise with formant tones.  Lengths are ragged (not multiples of the hop)."""
+    rng = np.random.default_rng(seed)
+    out = {}
+
+    def put(name, x):
+        out[name] = np.clip(np.rint(x), -32768, 32767).astype(np.int16)
+
+    n = np.arange(8000)
+    put("silence", np.zeros(3001))
+    put("dither1", rng.integers(-1, 2, 6007))
+    put("dither3", rng.integers(-3, 4, 4013))
+    put("dc", np.full(3203, 12000.0))
+    put("nyquist", 20000.0 * (-1.0) ** n[:3211])
+    put("fs4", 25000.0 * np.sin(0.5 * np.pi * n[:3227] + 0.3))
+    for k in (1, 2, 127, 129, 255):
+        for db, amp in (("full", 32000.0), ("m40", 320.0)):
+            put(f"tone{k}_{db}", amp * np.cos(2.0 * np.pi * k * n[:2731] / WIN + 0.7))
+    t = n[:8009] / 16000.0
+    put("tone_dither", 29000.0 * np.sin(2.0 * np.pi * 1000.0 * t) + rng.integers(-1, 2, len(t)))
+    for p in (0, 1, 255, 256, 510, 511):
+        x = np.zeros(WIN + 6 * 160 + 17)
+        x[3 * 160 + p] = 30000.0
+        put(f"impulse{p}", x)
+    sq = np.where((n[:3331] // 37) % 2 == 0, 32767.0, -32768.0)
+    put("square", sq)
+    t = np.arange(16003) / 16000.0
+    f0, f1, T = 50.0, 8000.0, len(t) / 16000.0
+    put("chirp", 16000.0 * np.sin(2.0 * np.pi * (f0 * t + 0.5 * (f1 - f0) / T * t * t)))
+    for lsb in (10, 100, 1000, 10000):
+        put(f"noise{lsb}", rng.normal(0.0, lsb, 4099))
+    m = 9011
+    spec = np.fft.rfft(rng.normal(size=m))
+    f = np.fft.rfftfreq(m, 1.0 / 16000.0)
+    spec[1:] /= np.sqrt(f[1:] / f[1])
+    spec[0] = 0.0
+    pink = np.fft.irfft(spec, m)
+    pink *= 800.0 / pink.std()
+    tt = np.arange(m) / 16000.0
+    formants = sum(a * np.sin(2.0 * np.pi * fr * tt + ph) for a, fr, ph in ((3000.0, 520.0, 0.1), (1500.0, 1480.0, 1.3),
+                                                                          (600.0, 2500.0, 2.2)))
+    put("pink_formants", pink + formants)
+    return out

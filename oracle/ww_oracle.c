@@ -185,6 +185,15 @@ static void mel_log(const float *mag, const float *W, const float *b, int n_mel,
  * `prefix` (may be NULL) holds n_prefix float samples that precede pcm[0] in the stream
  * (quirk C2: the reference never resets the Filter between files).
  */
+/* The reference's pre-emphasis is two float32 operations, each rounded (frame -= pre_emphasis * previous, NumPy float32).
+ * gcc contracts a * b - c into one fused multiply-add by default (-ffp-contract=fast), which rounds once: one ulp off a
+ * sample, up to 4e-4 in the log-mel of a row whose bands sit far below its frame's 2-norm (pre-emphasised DC).  The volatile
+ * store keeps the product a rounded float32. */
+static inline float rn_mul(float a, float b) {
+  volatile float p = a * b;
+  return p;
+}
+
 int wwo_logmel(const void *blob, size_t blob_len, const int16_t *pcm, int64_t n, float divisor, int do_clip,
                float preemph, int hop, const float *prefix, int n_prefix, float *mel, int64_t *n_frames_out) {
   blob_t b;
@@ -206,7 +215,7 @@ int wwo_logmel(const void *blob, size_t blob_len, const int16_t *pcm, int64_t n,
     float v = (float)pcm[i] / divisor;
     if (do_clip) v = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
     float cur = v;
-    v = v - preemph * carry;
+    v = v - rn_mul(preemph, carry);
     carry = cur;
     x[n_prefix + i] = v;
   }
@@ -241,7 +250,7 @@ int wwo_logmel_f32(const void *blob, size_t blob_len, const float *xin, int64_t 
   float carry = 0.f;
   for (int64_t i = 0; i < n; ++i) {
     float cur = xin[i];
-    x[i] = cur - preemph * carry;
+    x[i] = cur - rn_mul(preemph, carry);
     carry = cur;
   }
   int64_t nf = wwo_num_frames(n, hop);

@@ -307,6 +307,15 @@ int ww_k_far_frr(ww_ctx *ctx, const float *d_pos, int64_t n_pos, const float *d_
 // argument comes out of an MFMA.  On the bit pattern a signed-integer max does the same job (negative floats, -0
 // included, are negative integers).  Not inline asm: the compiler does not see an MFMA -> VALU read hazard through it
 // and omits the wait states.
+// Pre-emphasis x - a * b as the reference computes it: two fp32 operations, the product rounded before the subtraction
+// (NumPy float32).  __fmul_rn / __fsub_rn are plain * and - in these headers, which the compiler contracts into one FMA (one
+// rounding: an ulp off a sample, up to 5e-4 in the log-mel of bands far below their frame's 2-norm).
+__device__ __forceinline__ float ww_preemph_rn(float x, float a, float b) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return x - p;
+}
+
 __device__ __forceinline__ float relu1(float x) {
   const int b = __float_as_int(x);
   return __int_as_float(b > 0 ? b : 0);

@@ -1009,7 +1009,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
         p = __fdiv_rn((float)fxs[i - 1], fe.divisor);
         if (fe.clip) p = fminf(fmaxf(p, -1.0f), 1.0f);
       }
-      fx[fill + i] = (fe.preemph != 0.0f) ? __fsub_rn(v, __fmul_rn(fe.preemph, p)) : v;
+      fx[fill + i] = (fe.preemph != 0.0f) ? ww_preemph_rn(v, fe.preemph, p) : v;
     }
     __syncthreads();
     CT_STAMP(3)

@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256, sizeof(R) == 8 ? 4 : 5) void logmel_kernel(log
         // except that sample s_begin itself must see a zero carry (v[0] above / guard here).
         const bool at_start = (g + e == s_begin);
         const float prev = at_start ? 0.0f : v[e];
-        o[e] = (alpha != 0.0f) ? __fsub_rn(v[1 + e], __fmul_rn(alpha, prev)) : v[1 + e];
+        o[e] = (alpha != 0.0f) ? ww_preemph_rn(v[1 + e], alpha, prev) : v[1 + e];
       }
       float4 *dst = (float4 *)(tile + (size_t)q * VEC);
       dst[0] = make_float4(o[0], o[1], o[2], o[3]);
@@ -720,7 +720,7 @@ __device__ __forceinline__ void lw_stage_generic(const logmel_args &a, float *ds
     for (int e = 0; e < VEC; ++e) {
       // reference: frame -= pre_emphasis * previous  (separate fp32 multiply and subtract); sample s_begin sees a zero carry
       const float prev = (g + e == s_begin) ? 0.0f : v[e];
-      o[e] = (alpha != 0.0f) ? __fsub_rn(v[1 + e], __fmul_rn(alpha, prev)) : v[1 + e];
+      o[e] = (alpha != 0.0f) ? ww_preemph_rn(v[1 + e], alpha, prev) : v[1 + e];
     }
     float4 *d4 = (float4 *)(dst + (size_t)q * VEC);
     d4[0] = make_float4(o[0], o[1], o[2], o[3]);

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(128) void stream_frontend_kernel(stream_fe_args a) 
       p = __fdiv_rn((float)xs[i - 1], a.divisor);
       if (a.clip) p = fminf(fmaxf(p, -1.0f), 1.0f);
     }
-    x[fill + i] = (a.preemph != 0.0f) ? __fsub_rn(v, __fmul_rn(a.preemph, p)) : v;
+    x[fill + i] = (a.preemph != 0.0f) ? ww_preemph_rn(v, a.preemph, p) : v;
   }
   __syncthreads();
   if (tid == 0) {
@@ -375,6 +375,24 @@ int ww_stream_reset(ww_streams *st, const int32_t *ids, int32_t n) {
     st->pos[s] = 0;
     st->rowq[s] = 0;
   }
+  return WW_OK;
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+int ww_stream_window(ww_streams *st, int32_t stream, float *out) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  ww_ctx *ctx = st->ctx;
+  if (!out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (stream < 0 || stream >= st->S) return ww_fail(ctx, WW_EINVAL, "stream id %d out of range", stream);
+  WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
+  // the T rows that end at the last row written (pos - 1) start at slot (pos - 1 + 2) % R of the mirrored ring.  Copied behind
+  // everything enqueued so far (a polled tick returns once its posteriors are in, while workgroups that owe none may still be
+  // writing rows), then waited for
+  const int R = st->T + 1;
+  const float *src = st->hist + ((size_t)stream * st->HR + (st->pos[stream] + 1) % R) * st->F;
+  WW_HIP(ctx, hipMemcpyAsync(out, src, (size_t)st->T * st->F * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return WW_OK;
   WW_GUARD_END(st ? st->ctx : nullptr)
 }

@@ -412,7 +412,7 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
         p = __fdiv_rn((float)fxs[i - 1], fe.divisor);
         if (fe.clip) p = fminf(fmaxf(p, -1.0f), 1.0f);
       }
-      fx[fill + i] = (fe.preemph != 0.0f) ? __fsub_rn(v, __fmul_rn(fe.preemph, p)) : v;
+      fx[fill + i] = (fe.preemph != 0.0f) ? ww_preemph_rn(v, fe.preemph, p) : v;
     }
     if (window) {  // (the zero fill is complete: the old rows go in beside the normalisation)
 #pragma unroll

@@ -362,6 +362,13 @@ class StreamBank:
             a = np.ascontiguousarray(ids, dtype=np.int32)
             _lib.raise_for(self._lib.ww_stream_reset(self._h, _lib.ptr(a), a.size), self.engine.ctx.handle)
 
+    def window(self, stream: int) -> np.ndarray:
+        """Stream ``stream``'s newest ``[window, n_mel]`` mel window, the block the model reads (``ww_stream_window``: a
+        read-out; the bank's state is left as it is)."""
+        out = np.empty((self.engine.window, self.engine.n_mel), np.float32)
+        _lib.raise_for(self._lib.ww_stream_window(self._h, int(stream), _lib.ptr(out)), self.engine.ctx.handle)
+        return out
+
     def close(self) -> None:
         if self._h and not _lib.is_shutdown():
             self._lib.ww_stream_destroy(self._h)
