@@ -253,6 +253,8 @@ def test_crnn_large_batch_path(engines, oracles, name):
         e.set_option("crnn_tail_mfma", 1)
     with pytest.raises(ValueError):
         e.set_option("no_such_option", 1)
+    from wwhip import _lib
+    assert _lib.load().ww_model_set_option(e.handle, _lib.OPT_CRNN_TAIL_MFMA, 3) == _lib.WW_EINVAL  # 0, 1 and 2 only
 
 
 def test_retired_precision_mode_is_refused(engines):

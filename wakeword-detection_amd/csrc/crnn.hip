@@ -380,7 +380,7 @@ struct fused_args {
   float *enc;         // optional [Nw][64]
   float *out;         // [Nw][NOUT]
   int T, NOUT, HEAD;
-  long long *stamps;  // development: [blocks][4 waves][10] s_memtime at the phase boundaries (nullptr = off)
+  long long *stamps;  // crnn_fused_kernel<front>'s phase stamps: [blocks][4 waves][10] s_memtime (nullptr = off; no launch sets it)
   float *gx_out;      // FRONT_ONLY: [Nw][OT][192] layer-1 input projections incl. b_x
   const unsigned short *cwb;   // bf16x3: conv weights, A-operand order [plane 2][k-step 4][m-tile 2][lane 64][8]
   const unsigned short *wx1b;  // bf16x3: W_x1, B-operand order [plane 2][k-step 20][n-tile 12][lane 64][8]
@@ -440,18 +440,6 @@ __device__ __forceinline__ float cf_recurrence(const gru_w &g, const float *gxs,
   rem[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(rv_.e_, b_[1].e_, rem[1], 0, 0, 0);                     \
   rem[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(rv_.e_, b_[2].e_, rem[2], 0, 0, 0);
 
-// development: s_memtime at the phase boundaries (fused_args::stamps; nullptr = off)
-#ifdef CF_STAMP_PHASE_A  // development build: slots 6..9 hold the inside of phase A instead of phases D..G
-#define CF_STAMP(i_)                                                                                          \
-  if ((i_) < 6 && a.stamps && lane == 0) a.stamps[((size_t)blockIdx.x * 4 + wave) * 10 + (i_)] = __builtin_amdgcn_s_memtime();
-#define CF_STAMP_A(i_)                                                                                        \
-  if (a.stamps && lane == 0) a.stamps[((size_t)blockIdx.x * 4 + wave) * 10 + (i_)] = __builtin_amdgcn_s_memtime();
-#else
-#define CF_STAMP(i_)                                                                                          \
-  if (a.stamps && lane == 0) a.stamps[((size_t)blockIdx.x * 4 + wave) * 10 + (i_)] = __builtin_amdgcn_s_memtime();
-#define CF_STAMP_A(i_)
-#endif
-
 // Phases D..G of the fused kernels (fp32 and split-bf16 front halves share them): gx1 is in LDS, g holds this wave's
 // recurrent weights (waves 0, 1: layer 1; waves 2, 3: layer 2).
 __device__ __forceinline__ void cf_phases_d_to_g(const fused_args &a, float *img, float *feat, const gru_w &g, int w) {
@@ -474,7 +462,6 @@ __device__ __forceinline__ void cf_phases_d_to_g(const fused_args &a, float *img
     __builtin_amdgcn_s_setprio(0);
   }
   __syncthreads();
-  CF_STAMP(6)
 
   // ---- E: layer-2 input projection gx2[t][n] = seq1[t][:] . Wx2[n][:] + bx2[n]  (19 rows, K = 64, N = 192): rows 0..15 as one
   //      MFMA tile, rows 16..18 as a second one (rows 19..31 of seq1 are zeros), 3 n-tiles per wave; every row is the same
@@ -508,7 +495,6 @@ __device__ __forceinline__ void cf_phases_d_to_g(const fused_args &a, float *img
     }
   }
   __syncthreads();
-  CF_STAMP(7)
 
   // ---- F: layer-2 recurrence (waves 2, 3): only the last state of each direction is kept | waves 0, 1: head -> LDS
   float *w1s = feat;  // [64][GR_W1_LD]
@@ -525,7 +511,6 @@ __device__ __forceinline__ void cf_phases_d_to_g(const fused_args &a, float *img
     for (int i = tid; i < a.NOUT * 64; i += 128) w2s[i] = a.w2[i];
   }
   __syncthreads();
-  CF_STAMP(8)
 
   // ---- G: detect head: Dense(64, relu) -> Dense(NOUT) -> sigmoid | softmax   (wave 0)
   if (wave == 0) {
@@ -558,9 +543,12 @@ __device__ __forceinline__ void cf_phases_d_to_g(const fused_args &a, float *img
       a.out[(size_t)w * a.NOUT + lane] = p;
     }
   }
-  CF_STAMP(9)
 }
 
+// crnn_fused_kernel<front> alone keeps its stamp sites: without them its compiled form ran ~1 % slower at 16,384 windows
+// per launch (the other forms lost theirs at no cost; profiles/EXPERIMENTS.md 9.5)
+#define CF_STAMP(i_) \
+  if (FRONT_ONLY && a.stamps && lane == 0) a.stamps[((size_t)blockIdx.x * 4 + wave) * 10 + (i_)] = __builtin_amdgcn_s_memtime();
 template <bool FRONT_ONLY>
 __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a) {
   extern __shared__ __align__(16) float cf_smem[];
@@ -601,9 +589,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a)
           stage[q] = ld_mel4<AL>(src + (i < n ? i : n - 4), true);
         }
       });
-    CF_STAMP_A(6)
     for (int i = tid; i < CF_IMG_FLOATS / 4; i += CF_THREADS) ((float4 *)img)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    CF_STAMP_A(7)
     // while the window is on its way: LDS offsets of this lane's conv operands and results for its six m-tiles
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -626,7 +612,6 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a)
       }
     }
     __syncthreads();
-    CF_STAMP_A(8)
 #pragma unroll
     for (int q = 0; q < MAXV; ++q) {
       const int i = (q * CF_THREADS + tid) * 4;
@@ -640,7 +625,6 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a)
       }
     }
   }
-  CF_STAMP_A(9)
   __syncthreads();
   CF_STAMP(1)
   // (raw buffer loads with a scalar k-step offset would take the 64-bit pointer adds off the vector ALU, but this compiler
@@ -817,10 +801,7 @@ struct stream_args {
   int n_mel;
   float floor_v, log_off, scale;
   const double *hann, *tw256, *tw512;
-  long long *tstamps;  // development (WWHIP_CF_STAMPS): [workgroups][4 waves][6] s_memtime inside the tick prologue
 };
-#define CT_STAMP(i_) \
-  if (sa.tstamps && lane == 0) sa.tstamps[((size_t)blockIdx.x * 4 + wave) * 6 + (i_)] = __builtin_amdgcn_s_memtime();
 
 // Mel-side LDS of the one-launch tick form, in the part of the feat region the three conv rows leave free (floats from `feat`)
 #define CT_X (3 * CF_FLD)                 // [WW_ST_RING] ring | the tick's new samples
@@ -851,7 +832,6 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kk = lane >> 4;
   const int w = blockIdx.x;
-  CF_STAMP(0)
   float4 wreg[CV_KB][2];
   float cb0, cb1;
   float4 crow0, crow1, crow2;
@@ -958,7 +938,6 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
     // ---- what this workgroup is (uniform over it)
     const int fill = cw.x, nf = cw.y, flags = cw.z, pos = cw.w & 0xffff, rowq = cw.w >> 16;
     const int par = (flags >> 2) & 1;
-    CT_STAMP(0)  // the control words are here
     const int np = (flags & 1) ? nf : 0;  // frames are analysed only while the VAD says speech (tflite.py:166)
     if ((flags & 2) || k >= (np > 1 ? np : 1)) return;  // an active stream is not sampled at all (tflite.py:139-140) | no second window
     const bool window = k < np, writer = k + 1 >= np;
@@ -995,9 +974,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
       for (int i = tid; i < CF_IMG_FLOATS / 4; i += CF_THREADS) ((float4 *)img)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       tile_offsets();
     }
-    CT_STAMP(1)
     __syncthreads();
-    CT_STAMP(2)
     // ---- [ring | new samples]: normalise, clip, pre-emphasise (the arithmetic of stream_frontend_kernel, streams.hip)
     for (int i = tid; i < WW_CHUNK; i += CF_THREADS) {
       float v = __fdiv_rn((float)fxs[i], fe.divisor);
@@ -1012,7 +989,6 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
       fx[fill + i] = (fe.preemph != 0.0f) ? ww_preemph_rn(v, fe.preemph, p) : v;
     }
     __syncthreads();
-    CT_STAMP(3)
     if (writer && tid == 0) {
       float v = __fdiv_rn((float)fxs[WW_CHUNK - 1], fe.divisor);
       if (fe.clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
@@ -1042,13 +1018,10 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
       float *ring = fe.ring + ((size_t)(par ^ 1) * fe.S + s) * WW_ST_RING;
       for (int i = tid; i < keep; i += CF_THREADS) ring[i] = fx[nf * fe.hop + i];
     }
-    CT_STAMP(4)  // (waves 0, 1: the new frames are in the image)
     if (!window) return;  // the tick has no window for this stream: its ring has advanced, that is all
     scatter(stage, sidx);
-    CT_STAMP(5)
   }
   __syncthreads();
-  CF_STAMP(1)
   // ---- B: conv of the 60 rows -> feat[p][f * 32 + channel]
   {
     float4 av[CV_KB];
@@ -1089,9 +1062,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
   for (int s2 = 0; s2 < CS_DEPTH - 1; ++s2)
 #pragma unroll
     for (int n = 0; n < 3; ++n) bq[s2][n] = w_ld(s2, n);
-  CF_STAMP(2)
   __syncthreads();  // feat complete; the image is dead from here on
-  CF_STAMP(3)
   float *gxs = img + CF_GX, *seq1 = img + CF_SEQ, *hb = img + CF_HB;
   for (int i = tid; i < 32 * GR_SEQ_LD; i += CF_THREADS) seq1[i] = 0.f;
   if (tid < 2 * 2 * 2 * H) hb[tid] = 0.f;
@@ -1151,9 +1122,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
       }
     }
   }
-  CF_STAMP(4)
   __syncthreads();  // gx complete; nobody reads feat any more
-  CF_STAMP(5)
   cf_phases_d_to_g(a, img, feat, g, w);
 }
 
@@ -1392,7 +1361,6 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_bf16_kernel(fused_ar
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kk = lane >> 4;
   const int w = blockIdx.x;
-  CF_STAMP(0)
   int64_t row;
   int valid;
   window_span(a.wa, w, a.T, row, valid);
@@ -1456,7 +1424,6 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_bf16_kernel(fused_ar
     }
   }
   __syncthreads();
-  CF_STAMP(1)
 
   // ---- B: conv (transposed) -> feat planes
   {
@@ -1515,9 +1482,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_bf16_kernel(fused_ar
     for (int p = 0; p < 2; ++p)
 #pragma unroll
       for (int n = 0; n < 3; ++n) bq[s2][p][n] = w_ld(p, s2, n);
-  CF_STAMP(2)
   __syncthreads();  // feat complete; the image is dead from here on
-  CF_STAMP(3)
   float *gxs = img + CF_GX, *seq1 = img + CF_SEQ, *hb = img + CF_HB;
   for (int i = tid; i < 32 * GR_SEQ_LD; i += CF_THREADS) seq1[i] = 0.f;
   if (tid < 2 * 2 * 2 * H) hb[tid] = 0.f;
@@ -1572,9 +1537,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_bf16_kernel(fused_ar
         }
     }
   }
-  CF_STAMP(4)
   __syncthreads();
-  CF_STAMP(5)
   if (FRONT_ONLY) {
     float4 *dst = (float4 *)(a.gx_out + (size_t)w * OT * 6 * H);
     for (int q = tid; q < OT * 6 * H / 4; q += CF_THREADS) {
@@ -1756,7 +1719,6 @@ __global__ __launch_bounds__(128, 2) void gru_tail16_kernel(tail16_args aa) {
   // LDS: the h exchange (9.2 KB) + each wave's recurrent weights as B-operand pages [tile 6][half 2][lane 64] x 16 bytes
   // (24.6 KB: every lane reads back only what it wrote - 48 registers' worth that the four chains per tile need elsewhere);
   // the head's enc / hid rows move into the dead pages at the end.  33.8 KB: four workgroups per CU, as the registers allow
-  // (dynamic: the launch asks for MORE than GT16_SMEM_BYTES when its grid does not fill the chip four workgroups deep - launch_tail)
   extern __shared__ __align__(16) float sm16[];
   float (*hs)[2][16 * GT16_LD] = (float (*)[2][16 * GT16_LD])sm16;
   float *encs = sm16 + 2 * 2 * 16 * GT16_LD, *hid = encs + 16 * GT16_ELD;
@@ -2021,267 +1983,6 @@ __global__ __launch_bounds__(128, 2) void gru_tail16_kernel(tail16_args aa) {
 }
 
 
-#ifndef WW_TAIL16H
-#define WW_TAIL16H 0
-#endif
-#if WW_TAIL16H
-// ------------------------------------------------------------------------------------------
-// gru_tail16h_kernel (round 6): gru_tail16_kernel's work for TWO groups of sixteen windows per four-wave workgroup, with the
-// layer-2 input projection HOISTED out of the 19-step recurrence into a phase of its own:
-//   * the recurrent weight pages (24.6 KB of LDS) are shared by the two groups - 43 KB per workgroup instead of 2 x 33.8:
-//     three workgroups = twelve waves per CU, THREE waves per SIMD where gru_tail16_kernel has two;
-//   * W_x2 (96 registers) is alive only while the projection phase runs: gx2[t] of all 19 steps - the same MFMA chains, bias
-//     last - goes to memory in the layout layer 1 reads its projected inputs in (over the group's own rows of gx1 when the
-//     launch has them to itself, else into aa.gx2), and the layer-2 recurrence IS the layer-1 loop on those rows;
-//   * every sum is associated as before, so a posterior has the same bits whichever tail served it.
-// MEASURED AND NOT ADOPTED (profiles/r06/tail16_probes.txt): bit-identical to gru_tail16_kernel, but 16-20 % slower per window at
-// three waves per SIMD than that kernel at two (690.9 vs 596.9 us per 49,152 windows, 364.4 vs 360.5 per 24,576): the
-// projection's MFMAs no longer cover the h round trip of the recurrence and 29 KB per window take a trip through memory.
-// Kept as a development build (-DWW_TAIL16H=1: WW_OPT_CRNN_TAIL_MFMA = 3 selects it for launches that own their gx1 rows; the
-// prologue and the head spill ~25 registers at the 168 the occupancy allows - outside the loops, but it is not a shipped kernel).
-// ------------------------------------------------------------------------------------------
-#define GT16H_HS (2 * 2 * 2 * 16 * GT16_LD)  // floats: h exchange [group 2][direction 2][buffer 2][16 x GT16_LD]
-#define GT16H_SMEM_BYTES ((GT16H_HS + 2 * 6 * 2 * 64 * 4) * 4)
-struct tail16h_args {
-  tail_args t;
-  float *seq;   // [group][OT][16][64] layer-1 outputs
-  float *gx2;   // [nw][OT][192] projected layer-2 inputs, or nullptr: written over the group's own rows of t.gx1
-  int nw;
-};
-
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void gru_tail16h_kernel(tail16h_args aa) {
-  constexpr int H = GR_H, OT = CV_OT;
-  const tail_args &a = aa.t;
-  extern __shared__ __align__(16) float sm16[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = wave >> 1, dir = wave & 1;
-  const int c = lane & 15, g = lane >> 4;
-  float (*hs)[2][16 * GT16_LD] = (float (*)[2][16 * GT16_LD])(sm16 + grp * 2 * 2 * 16 * GT16_LD);  // this group's exchange
-  float *pages = sm16 + GT16H_HS;
-  float *encs = pages + grp * 2 * 16 * GT16_ELD, *hid = encs + 16 * GT16_ELD;
-  static_assert(2 * 2 * 16 * GT16_ELD <= 2 * 6 * 2 * 64 * 4, "enc / hid rows of two groups do not fit the weight pages");
-  float4 *whl = (float4 *)pages + (size_t)dir * 6 * 2 * 64 + lane;  // this lane's slot of page 0 (both groups read the same pages)
-  const int gi = blockIdx.x * 2 + grp;  // group number in the launch
-  const int w0 = gi * 16;
-  float *seq = aa.seq + (size_t)gi * OT * 16 * 2 * H;
-
-  // This form serves launches that own their projected inputs t.gx1 [window][t][192] (the rows of a window are nobody else's:
-  // front + tail over explicit windows): a lane's four windows (rows of its accumulator tiles, 4 g + r; clamped in a partial
-  // group: computed twice, stored once) as 32-bit element offsets - the index arithmetic of the three gx sources that
-  // gru_tail16_kernel carries through its loops costs registers this kernel does not have.
-  int ro[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) ro[r] = min(w0 + 4 * g + r, aa.nw - 1) * (OT * 6 * H) + dir * 3 * H + c;
-  const float *const g1base = a.gx1;
-  // where layer 2's projected inputs go: the same layout, over the group's own rows of gx1 (or aa.gx2 when the caller gave one)
-  float *const g2base = aa.gx2 ? aa.gx2 : const_cast<float *>(a.gx1);
-  auto gx_row = [&](int r, int t) -> const float * { return g1base + ro[r] + t * (6 * H); };
-  auto gx2_row = [&](int r, int t) -> float * { return g2base + ro[r] + t * (6 * H); };
-  // (GT16_POS, GT16_PRE_ALL, GT16_PRE_FIRST: gru_tail16_kernel's, still defined)
-  float bh[6];
-  auto load_wh = [&](const float *whp, const float *bhp) {  // group 0 writes the pages, everybody takes the biases
-#pragma unroll
-    for (int nt = 0; nt < 6; ++nt) {
-      const int row = (nt >> 1) * H + (nt & 1) * 16 + c;
-      if (grp == 0) {
-        const float *p = whp + ((size_t)dir * 3 * H + row) * H + 2 * g;
-        float wv[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wv[i] = p[16 * (i >> 2) + 8 * ((i >> 1) & 1) + (i & 1)];
-        whl[(2 * nt) * 64] = make_float4(wv[0], wv[1], wv[2], wv[3]);
-        whl[(2 * nt + 1) * 64] = make_float4(wv[4], wv[5], wv[6], wv[7]);
-      }
-      bh[nt] = bhp[dir * 3 * H + row];
-    }
-  };
-  const int pos0 = GT16_POS(c), pos1 = GT16_POS(16 + c);
-  float h_own[4][2];
-  float gxn[4][6];
-  // One layer's recurrence over projected inputs in the [window][t][192] layout (LAYER 1: gx_row, from the kernels in front; LAYER
-  // 2: gx2_row, from this kernel's projection phase): the loop of gru_tail16_kernel's layer 1, statement for statement.
-#define GT16H_RECUR(ROW_, STORE_SEQ_)                                                                         \
-  {                                                                                                           \
-    _Pragma("unroll") for (int r = 0; r < 4; ++r) h_own[r][0] = h_own[r][1] = 0.f;                             \
-    {                                                                                                         \
-      const int t = dir ? OT - 1 : 0;                                                                         \
-      _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                         \
-        const float *row = ROW_(r, t);                                                      \
-        _Pragma("unroll") for (int nt = 0; nt < 6; ++nt) gxn[r][nt] = row[(nt >> 1) * H + (nt & 1) * 16];      \
-      }                                                                                                       \
-    }                                                                                                         \
-    __syncthreads();                                                                                          \
-    _Pragma("unroll 1") for (int s = 0; s < OT; ++s) {                                                        \
-      const int t = dir ? OT - 1 - s : s, cur = s & 1;                                                        \
-      f32x4 x0[4];                                                                                            \
-      _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) x0[nt] = (f32x4){gxn[0][nt], gxn[1][nt], gxn[2][nt], gxn[3][nt]}; \
-      float gxc[4][2];                                                                                        \
-      _Pragma("unroll") for (int r = 0; r < 4; ++r) { gxc[r][0] = gxn[r][4]; gxc[r][1] = gxn[r][5]; }          \
-      if (s + 1 < OT) {                                                                                       \
-        const int tn = dir ? t - 1 : t + 1;                                                                   \
-        _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                       \
-          const float *row = ROW_(r, tn);                                                   \
-          _Pragma("unroll") for (int nt = 0; nt < 6; ++nt) gxn[r][nt] = row[(nt >> 1) * H + (nt & 1) * 16];    \
-        }                                                                                                     \
-      }                                                                                                       \
-      const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};                                                               \
-      float ha[8];                                                                                            \
-      if (s > 0) {                                                                                            \
-        const float4 *hp = (const float4 *)(&hs[dir][cur][c * GT16_LD + 8 * g]);                              \
-        const float4 a0 = hp[0], a1 = hp[1];                                                                  \
-        ha[0] = a0.x; ha[1] = a0.y; ha[2] = a0.z; ha[3] = a0.w; ha[4] = a1.x; ha[5] = a1.y; ha[6] = a1.z; ha[7] = a1.w; \
-      }                                                                                                       \
-      /* the six tiles in the order z, r, c of unit half 0, then of unit half 1: a half's gates are evaluated as soon as its  \
-         three tiles are in (12 pre-activation registers alive instead of 24); a tile's sums are gru_tail16_kernel's */     \
-      float4 wb[2][2];                                                                                        \
-      if (s > 0) { wb[0][0] = whl[0]; wb[0][1] = whl[64]; }                                                   \
-      _Pragma("unroll") for (int uh = 0; uh < 2; ++uh) {                                                      \
-        f32x4 pre3[3];                                                                                        \
-        _Pragma("unroll") for (int gt = 0; gt < 3; ++gt) {                                                    \
-          const int nt = 2 * gt + uh, q = 3 * uh + gt;                /* q: position in the visiting order */ \
-          const f32x4 xin = gt < 2 ? x0[nt < 4 ? nt : 0] : zero4;                                             \
-          const f32x4 o0i = {bh[nt], bh[nt], bh[nt], bh[nt]};                                                 \
-          if (s > 0) {                                                                                        \
-            if (q + 1 < 6) {                                                                                  \
-              const int ntn = 2 * ((q + 1) % 3) + (q + 1) / 3;                                                \
-              wb[(q + 1) & 1][0] = whl[(2 * ntn) * 64];                                                       \
-              wb[(q + 1) & 1][1] = whl[(2 * ntn + 1) * 64];                                                   \
-            }                                                                                                 \
-            __builtin_amdgcn_sched_barrier(0);                                                                \
-            const float4 b0 = wb[q & 1][0], b1 = wb[q & 1][1];                                                \
-            f32x4 e0 = xin, o0 = o0i;                                                                         \
-            e0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ha[0], b0.x, e0, 0, 0, 0);                              \
-            o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ha[1], b0.y, o0, 0, 0, 0);                              \
-            e0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ha[2], b0.z, e0, 0, 0, 0);                              \
-            o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ha[3], b0.w, o0, 0, 0, 0);                              \
-            f32x4 e1 = zero4, o1 = zero4;                                                                     \
-            e1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ha[4], b1.x, e1, 0, 0, 0);                              \
-            o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ha[5], b1.y, o1, 0, 0, 0);                              \
-            e1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ha[6], b1.z, e1, 0, 0, 0);                              \
-            o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ha[7], b1.w, o1, 0, 0, 0);                              \
-            pre3[gt] = (e0 + o0) + (e1 + o1);                                                                 \
-            __builtin_amdgcn_sched_barrier(0);                                                                \
-          } else {                                                                                            \
-            pre3[gt] = (xin + o0i) + (zero4 + zero4);   /* h = 0: the chains are their initial values */      \
-          }                                                                                                   \
-        }                                                                                                     \
-        _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                       \
-          const float z = fast_sigmoid(pre3[0][r]);                                                           \
-          const float rr = fast_sigmoid(pre3[1][r]);                                                          \
-          const float hn = gru_blend(z, h_own[r][uh], gru_candidate(rr, pre3[2][r], gxc[r][uh]));             \
-          h_own[r][uh] = hn;                                                                                  \
-          hs[dir][cur ^ 1][(4 * g + r) * GT16_LD + (uh ? pos1 : pos0)] = hn;                                  \
-          if (STORE_SEQ_) seq[((size_t)t * 16 + 4 * g + r) * 2 * H + dir * H + uh * 16 + c] = hn;             \
-        }                                                                                                     \
-      }                                                                                                       \
-      wsync_h();                                                                                              \
-    }                                                                                                         \
-  }
-
-  // ---- layer 1 ------------------------------------------------------------------------------
-  load_wh(a.wh1, a.bh1);
-  for (int i = tid; i < GT16H_HS; i += 256) sm16[i] = 0.f;
-  GT16H_RECUR(gx_row, true)
-  __syncthreads();  // seq1 of both directions is in memory; every wave is done with the layer-1 pages and with its rows of gx1
-
-  // ---- layer 2, projection phase: gx2[t] for all t, one fmaf chain per value over k = 16 kb + 4 kk + e in the order kb, e, kk,
-  //      the bias added last (phase E of crnn_fused_kernel); A = seq1[t] of the sixteen windows, B = this direction's 96 rows of W_x2
-  load_wh(a.wh2, a.bh2);
-  // Three of the six n-tiles at a time (48 registers of W_x2 instead of 96: the phase fits three waves per SIMD without a spill);
-  // seq1[t] is read once per half - 2 KB per wave and step out of L2.  Every value is still ONE chain in k order, bias last.
-#define GT16H_PROJ_HALF(NT0_)                                                                                   \
-  {                                                                                                             \
-    float wx[3][16];                                                                                            \
-    float bx[3];                                                                                                \
-    _Pragma("unroll") for (int i = 0; i < 3; ++i) {                                                             \
-      const int nt = (NT0_) + i;                                                                                \
-      const int row = dir * 3 * H + (nt >> 1) * H + (nt & 1) * 16 + c;                                          \
-      const float4 *p = (const float4 *)(a.wx2 + (size_t)row * 2 * H + 4 * g);                                  \
-      _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                           \
-        const float4 v = p[4 * q];                                                                              \
-        wx[i][4 * q] = v.x; wx[i][4 * q + 1] = v.y; wx[i][4 * q + 2] = v.z; wx[i][4 * q + 3] = v.w;             \
-      }                                                                                                         \
-      bx[i] = a.bx2[row];                                                                                       \
-    }                                                                                                           \
-    _Pragma("unroll 1") for (int t = 0; t < OT; ++t) {                                                          \
-      const float4 *sp = (const float4 *)(seq + ((size_t)t * 16 + c) * 2 * H + 4 * g);                          \
-      const float4 q0 = sp[0], q1 = sp[4], q2 = sp[8], q3 = sp[12];                                             \
-      f32x4 gx2[3];                                                                                             \
-      _Pragma("unroll") for (int i = 0; i < 3; ++i) gx2[i] = (f32x4){0.f, 0.f, 0.f, 0.f};                       \
-      GT16H_PROJ(q0, 0)                                                                                         \
-      GT16H_PROJ(q1, 1)                                                                                         \
-      GT16H_PROJ(q2, 2)                                                                                         \
-      GT16H_PROJ(q3, 3)                                                                                         \
-      _Pragma("unroll") for (int i = 0; i < 3; ++i) gx2[i] += (f32x4){bx[i], bx[i], bx[i], bx[i]};              \
-      _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                           \
-        float *row = gx2_row(r, t);                                                           \
-        _Pragma("unroll") for (int i = 0; i < 3; ++i) row[(((NT0_) + i) >> 1) * H + (((NT0_) + i) & 1) * 16] = gx2[i][r]; \
-      }                                                                                                         \
-    }                                                                                                           \
-  }
-#define GT16H_PROJ(q_, kb_)                                                                          \
-  _Pragma("unroll") for (int i = 0; i < 3; ++i) gx2[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(q_.x, wx[i][4 * kb_ + 0], gx2[i], 0, 0, 0); \
-  _Pragma("unroll") for (int i = 0; i < 3; ++i) gx2[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(q_.y, wx[i][4 * kb_ + 1], gx2[i], 0, 0, 0); \
-  _Pragma("unroll") for (int i = 0; i < 3; ++i) gx2[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(q_.z, wx[i][4 * kb_ + 2], gx2[i], 0, 0, 0); \
-  _Pragma("unroll") for (int i = 0; i < 3; ++i) gx2[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(q_.w, wx[i][4 * kb_ + 3], gx2[i], 0, 0, 0);
-  GT16H_PROJ_HALF(0)
-  GT16H_PROJ_HALF(3)
-#undef GT16H_PROJ
-#undef GT16H_PROJ_HALF
-  for (int i = tid; i < GT16H_HS; i += 256) sm16[i] = 0.f;
-  __threadfence_block();  // (a lane reads back what it - or its clamped twin with the same values - wrote: program order suffices)
-  // ---- layer 2, recurrence: the layer-1 loop on the rows written above
-  GT16H_RECUR(gx2_row, false)
-  __syncthreads();  // every wave is done with the weight pages: enc / hid take their place
-#pragma unroll
-  for (int uh = 0; uh < 2; ++uh)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      encs[(4 * g + r) * GT16_ELD + dir * H + uh * 16 + c] = h_own[r][uh];
-      if (a.enc && w0 + 4 * g + r < aa.nw) a.enc[(size_t)(w0 + 4 * g + r) * 2 * H + dir * H + uh * 16 + c] = h_own[r][uh];
-    }
-  __syncthreads();
-  // ---- detect head per group: wave `dir` takes windows 8 dir .. 8 dir + 7; lane = hidden unit, its w1 row in registers
-  {
-    float4 w1r[16];
-    const float4 *wr = (const float4 *)(a.w1 + (size_t)lane * 2 * H);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) w1r[q] = wr[q];
-    const float b1v = a.b1[lane];
-#pragma unroll 1
-    for (int wq = dir * 8; wq < dir * 8 + 8; ++wq) {
-      float acc = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const float4 ev = *(const float4 *)(&encs[wq * GT16_ELD + q * 4]);
-        acc = fmaf(w1r[q].x, ev.x, acc); acc = fmaf(w1r[q].y, ev.y, acc);
-        acc = fmaf(w1r[q].z, ev.z, acc); acc = fmaf(w1r[q].w, ev.w, acc);
-      }
-      hid[wq * GT16_ELD + lane] = fmaxf(acc + b1v, 0.f);
-    }
-  }
-  __syncthreads();
-  {
-    const int tg = tid & 127, wq = tg >> 3, o = tg & 7;  // per group: 16 windows x up to 8 outputs
-    float y = 0.f;
-    if (o < a.NOUT) {
-      for (int k = 0; k < 2 * H; ++k) y = fmaf(a.w2[o * 64 + k], hid[wq * GT16_ELD + k], y);
-      y += a.b2[o];
-    }
-    const bool live = o < a.NOUT && w0 + wq < aa.nw;
-    if (a.HEAD == 0) {
-      if (live) a.out[(size_t)(w0 + wq) * a.NOUT + o] = sigmoid_f(y);
-    } else {
-      float mx = (o < a.NOUT) ? y : -INFINITY;
-      for (int d = 1; d < 8; d <<= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-      const float e = (o < a.NOUT) ? expf(y - mx) : 0.f;
-      float sum = e;
-      for (int d = 1; d < 8; d <<= 1) sum += __shfl_xor(sum, d);
-      if (live) a.out[(size_t)(w0 + wq) * a.NOUT + o] = e / sum;
-    }
-  }
-}
-#undef GT16H_RECUR
-#endif  // WW_TAIL16H
-
 #undef CF_ROUND
 #undef CF_ROUND_L2
 #undef GT16_PRE_ALL
@@ -2467,11 +2168,6 @@ static int crnn_forward_generic(ww_ctx *ctx, const ww_model *m, const win_addr &
 // (ww_model_set_option(WW_OPT_CRNN_SPLIT_AT): 0 = always fused.)
 static int crnn_split_threshold(const ww_model *m) { return m->opt_split_at; }
 
-// More than half a CU's LDS: a workgroup that asks for this much has the CU's LDS to itself (development probes only: asked for
-// on crnn_fused_kernel / crnn_stream_kernel<tick> launches of <= 256 workgroups it changed nothing - 33.92 vs 33.90 us, tick
-// p50 37.3 vs 37.0 us: those grids already sit one workgroup per CU; profiles/r06/tail16_probes.txt).
-#define WW_LDS_ONE_PER_CU (82 * 1024)
-
 // Every CRNN kernel that asks for more than the default 64 KB of dynamic LDS.  The attribute is per device, so it is set
 // for the device of every new context (ww_ctx_create, under its device scope) instead of once per process.
 int ww_k_crnn_init_device(ww_ctx *ctx) {
@@ -2479,12 +2175,26 @@ int ww_k_crnn_init_device(ww_ctx *ctx) {
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
-  WW_HIP(ctx, hipFuncSetAttribute((const void *)gru_tail16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WW_LDS_ONE_PER_CU));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_FUSED_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_FUSED_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CFB_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, CFB_SMEM_BYTES));
   return WW_OK;
+}
+
+// The arguments of the fused and streaming kernels: the model's weights, the launch's mel source, windows and outputs;
+// gx_out and tag are left empty for the caller.
+static fused_args crnn_fused_args(const ww_crnn_dev &c, const float *mel, const win_addr &wa, float *enc, float *out) {
+  fused_args a = {};
+  a.mel = mel; a.wa = wa;
+  a.w4 = c.conv_w; a.cbias = c.conv_b;
+  a.wx1s = c.wx1s; a.bx1 = c.bx1; a.wh1 = c.wh1; a.bh1 = c.bh1;
+  a.wx2s = c.wx2s; a.bx2 = c.bx2; a.wh2 = c.wh2; a.bh2 = c.bh2;
+  a.w1 = c.w1; a.b1 = c.b1; a.w2 = c.w2; a.b2 = c.b2;
+  a.enc = enc; a.out = out;
+  a.T = c.T; a.NOUT = c.NOUT; a.HEAD = c.HEAD;
+  a.cwb = c.cwb; a.wx1b = c.wx1b;
+  return a;
 }
 
 // streaming form (crnn_stream_kernel): standard geometry, fp32 contractions
@@ -2498,48 +2208,20 @@ int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int pre
     return ww_fail(ctx, WW_EINVAL, "one-launch streaming tick: standard conv geometry, 40 mel bands and hop 160 only");
   if (!tag.slots || fe.S <= 0) return ww_fail(ctx, WW_EINVAL, "one-launch streaming tick: no tag slots / no streams");
   stream_args sa = {};
-  sa.f = {fe.hist, {nullptr, nullptr, 0, 0, 0, (int64_t)fe.S * fe.HR}, c.conv_w, c.conv_b, c.wx1s, c.bx1, c.wh1, c.bh1, c.wx2s, c.bx2, c.wh2, c.bh2,
-          c.w1, c.b1, c.w2, c.b2, nullptr, nullptr, c.T, c.NOUT, c.HEAD, nullptr, nullptr, c.cwb, c.wx1b};
+  sa.f = crnn_fused_args(c, fe.hist, {nullptr, nullptr, 0, 0, 0, (int64_t)fe.S * fe.HR}, nullptr, nullptr);
   sa.f.tag = tag;
   sa.gxc = d_gxc;
   sa.fe = fe;
   sa.start = f.start; sa.wpad = f.wpad; sa.bias = f.bias; sa.n_mel = f.n_mel;
   sa.floor_v = f.floor_v; sa.log_off = f.log_off; sa.scale = f.scale;
   sa.hann = f.hann; sa.tw256 = f.tw256; sa.tw512 = f.tw512;
-  static const bool want_stamps = getenv("WWHIP_CF_STAMPS") != nullptr;  // development: phase timeline (the call then waits for its kernel)
   const int nwg = 2 * fe.S;
-  if (want_stamps) {
-    WW_HIP(ctx, hipMalloc((void **)&sa.f.stamps, (size_t)nwg * 64 * sizeof(long long)));
-    WW_HIP(ctx, hipMemsetAsync(sa.f.stamps, 0, (size_t)nwg * 64 * sizeof(long long), ctx->stream));
-    sa.tstamps = sa.f.stamps + (size_t)nwg * 40;
-  }
   {
     ww_launch_scope scope(ctx, "crnn_stream_kernel<tick>");
     if (precise) hipLaunchKernelGGL(crnn_stream_kernel<2>, dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa);
     else hipLaunchKernelGGL(crnn_stream_kernel<1>, dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa);
   }
   WW_HIP(ctx, hipGetLastError());
-  if (want_stamps) {
-    std::vector<long long> h((size_t)nwg * 64);
-    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    WW_HIP(ctx, hipMemcpy(h.data(), sa.f.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-    WW_HIP(ctx, hipFree(sa.f.stamps));
-    for (int wv : {0, 3}) {  // wave 0 transforms a frame, wave 3 only stages: mean cycles since the workgroup's entry
-      double sum[16] = {0};
-      int cnt = 0;
-      for (int b = 0; b < nwg; ++b) {
-        const long long *c = &h[((size_t)b * 4 + wv) * 10], *t = &h[(size_t)nwg * 40 + ((size_t)b * 4 + wv) * 6];
-        if (!c[0] || !c[9]) continue;  // (a workgroup without a window)
-        for (int i = 0; i < 6; ++i) sum[i] += (double)(t[i] - c[0]);
-        for (int i = 1; i < 10; ++i) sum[5 + i] += (double)(c[i] - c[0]);
-        ++cnt;
-      }
-      fprintf(stderr, "crnn_stream_kernel<tick>, %d window workgroups, wave %d, mean cycles since entry: ctl | pre-barrier barrier normalised "
-              "frames staged | image conv conv-barrier proj proj-barrier D E F G:", cnt, wv);
-      for (int i = 0; i < 15; ++i) fprintf(stderr, "%s %.0f", i == 1 || i == 6 ? " |" : "", cnt ? sum[i] / cnt : 0.0);
-      fprintf(stderr, "\n");
-    }
-  }
   return WW_OK;
 }
 
@@ -2551,33 +2233,15 @@ int ww_k_crnn_stream_forward(ww_ctx *ctx, const ww_model *m, const float *d_hist
   if (c.generic) return ww_fail(ctx, WW_EINVAL, "streaming CRNN kernel: standard conv geometry only");
   if (!d_win_row || !d_win_valid || !d_win_aux) return ww_fail(ctx, WW_EINVAL, "streaming CRNN kernel: NULL window table");
   stream_args sa = {};
-  sa.f = {d_hist, {d_win_row, d_win_valid, 0, 0, 0, hist_rows}, c.conv_w, c.conv_b, c.wx1s, c.bx1, c.wh1, c.bh1, c.wx2s, c.bx2, c.wh2, c.bh2,
-          c.w1, c.b1, c.w2, c.b2, nullptr, d_out, c.T, c.NOUT, c.HEAD, nullptr, nullptr, c.cwb, c.wx1b};
+  sa.f = crnn_fused_args(c, d_hist, {d_win_row, d_win_valid, 0, 0, 0, hist_rows}, nullptr, d_out);
   sa.aux = d_win_aux;
   sa.gxc = d_gxc;
   if (tag) sa.f.tag = *tag;
-  static const bool want_stamps = getenv("WWHIP_CF_STAMPS") != nullptr;  // development: phase timeline (as ww_k_crnn_forward)
-  if (want_stamps) {
-    WW_HIP(ctx, hipMalloc((void **)&sa.f.stamps, (size_t)nw * 40 * sizeof(long long)));
-    WW_HIP(ctx, hipMemsetAsync(sa.f.stamps, 0, (size_t)nw * 40 * sizeof(long long), ctx->stream));
-  }
   {
     ww_launch_scope scope(ctx, "crnn_stream_kernel");
     hipLaunchKernelGGL(crnn_stream_kernel<0>, dim3(nw), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa);
   }
   WW_HIP(ctx, hipGetLastError());
-  if (want_stamps) {
-    std::vector<long long> h((size_t)nw * 40);
-    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    WW_HIP(ctx, hipMemcpy(h.data(), sa.f.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-    WW_HIP(ctx, hipFree(sa.f.stamps));
-    double sum[10] = {0};
-    for (int b = 0; b < nw; ++b)
-      for (int i = 0; i < 10; ++i) sum[i] += (double)(h[((size_t)b * 4 + 0) * 10 + i] - h[((size_t)b * 4 + 0) * 10]);
-    fprintf(stderr, "crnn_stream_kernel, %d windows, wave 0, mean cycles since entry:", nw);
-    for (int i = 0; i < 10; ++i) fprintf(stderr, " %.0f", sum[i] / nw);
-    fprintf(stderr, "\n");
-  }
   return WW_OK;
 }
 
@@ -2587,26 +2251,13 @@ int ww_k_crnn_stream_forward(ww_ctx *ctx, const ww_model *m, const float *d_hist
 // front + tail per launch 743 vs 745 us at 9,216 windows, 1,204 vs 1,309 at 16,384, but 226 vs 188 at 2,048), so
 // WW_OPT_CRNN_TAIL_MFMA = 1 (default) takes it from WW_TAIL16_MIN windows per launch on; 2 = always, 0 = never.
 #define WW_TAIL16_MIN 9216
-static size_t tail_seq_bytes(int nw) { return ww_bump::need((size_t)((((nw + 15) / 16) + 1) & ~1) * CV_OT * 16 * 2 * GR_H, 4); }  // (an even number of groups: gru_tail16h_kernel takes two per workgroup)
+static size_t tail_seq_bytes(int nw) { return ww_bump::need((size_t)((nw + 15) / 16) * CV_OT * 16 * 2 * GR_H, 4); }
 static void launch_tail(ww_ctx *ctx, const ww_model *m, tail_args t, int nw, float *seq) {
   t.wx2 = m->crnn.wx2;
-#if WW_TAIL16H
-  if (m->opt_tail_mfma == 3 && t.gx1) {  // (round 6 probe) hoisted projection, two groups per workgroup: launches that own their gx1 rows
-    tail16h_args ah = {t, seq, nullptr, nw};
-    ww_launch_scope scope(ctx, "gru_tail16h_kernel");
-    hipLaunchKernelGGL(gru_tail16h_kernel, dim3((unsigned)((nw + 31) / 32)), dim3(256), GT16H_SMEM_BYTES, ctx->stream, ah);
-    return;
-  }
-#endif
   if (m->opt_tail_mfma >= 2 || (m->opt_tail_mfma == 1 && nw >= WW_TAIL16_MIN)) {
     tail16_args a16 = {t, seq, nw};
     ww_launch_scope scope(ctx, "gru_tail16_kernel");
-    // Development (round 6 occupancy probe, tools/tail16_occ.py -> profiles/r06/tail16_probes.txt): WWHIP_TAIL16_DEEP = n asks
-    // for so much LDS that only n workgroups fit on a CU - the shipped instruction stream at 1 / 2 / 3 / 4 workgroups per CU.
-    const int n_wg = (nw + 15) / 16;
-    static const int deep = getenv("WWHIP_TAIL16_DEEP") ? atoi(getenv("WWHIP_TAIL16_DEEP")) : 4;
-    const size_t lds = deep >= 4 ? (size_t)GT16_SMEM_BYTES : deep == 3 ? (size_t)44 * 1024 : deep == 2 ? (size_t)56 * 1024 : (size_t)WW_LDS_ONE_PER_CU;
-    hipLaunchKernelGGL(gru_tail16_kernel, dim3((unsigned)n_wg), dim3(128), lds, ctx->stream, a16);
+    hipLaunchKernelGGL(gru_tail16_kernel, dim3((unsigned)((nw + 15) / 16)), dim3(128), GT16_SMEM_BYTES, ctx->stream, a16);
   } else {
     ww_launch_scope scope(ctx, "gru_tail_kernel");
     hipLaunchKernelGGL(gru_tail_kernel, dim3((unsigned)nw), dim3(128), 0, ctx->stream, t);
@@ -2748,8 +2399,7 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
   }
   if (c.generic && tag && tag->slots) return ww_fail(ctx, WW_EINVAL, "tick tags: the generic CRNN path does not write them");
   if (c.generic) return crnn_forward_generic(ctx, m, wa, d_mel, nw, ws, d_out, d_enc);
-  fused_args a = {d_mel, wa, c.conv_w, c.conv_b, c.wx1s, c.bx1, c.wh1, c.bh1, c.wx2s, c.bx2, c.wh2, c.bh2,
-                  c.w1, c.b1, c.w2, c.b2, d_enc, d_out, c.T, c.NOUT, c.HEAD, nullptr, nullptr, c.cwb, c.wx1b};
+  fused_args a = crnn_fused_args(c, d_mel, wa, d_enc, d_out);
   const bool bf16 = m->precision == WW_PRECISION_BF16X3;
   // (also in split-bf16 mode: the mode permits bf16 products, and computing a seventh of them in fp32 is both faster and closer)
   if (slide_form) {
@@ -2797,31 +2447,11 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
     WW_HIP(ctx, hipGetLastError());
     return WW_OK;
   }
-  // development: WWHIP_CF_STAMPS=1 prints the s_memtime stamps of the phase boundaries (first, middle and last workgroup)
-  static const bool want_stamps = getenv("WWHIP_CF_STAMPS") != nullptr;
-  if (want_stamps) {
-    WW_HIP(ctx, hipMalloc((void **)&a.stamps, (size_t)nw * 40 * sizeof(long long)));
-    WW_HIP(ctx, hipMemsetAsync(a.stamps, 0, (size_t)nw * 40 * sizeof(long long), ctx->stream));
-  }
   {
     ww_launch_scope scope(ctx, bf16 ? "crnn_fused_kernel<bf16x3>" : "crnn_fused_kernel");
     if (bf16) hipLaunchKernelGGL(crnn_fused_bf16_kernel<false>, dim3(nw), dim3(CF_THREADS), CFB_SMEM_BYTES, ctx->stream, a);
     else hipLaunchKernelGGL(crnn_fused_kernel<false>, dim3(nw), dim3(CF_THREADS), CF_FUSED_SMEM_BYTES, ctx->stream, a);
   }
   WW_HIP(ctx, hipGetLastError());
-  if (want_stamps) {
-    std::vector<long long> h((size_t)nw * 40);
-    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    WW_HIP(ctx, hipMemcpy(h.data(), a.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-    WW_HIP(ctx, hipFree(a.stamps));
-    for (int b : {0, nw / 2, nw - 1}) {
-      for (int wv = 0; wv < 4; ++wv) {
-        const long long *t = &h[((size_t)b * 4 + wv) * 10];
-        fprintf(stderr, "block %d wave %d:", b, wv);
-        for (int i = 0; i < 10; ++i) fprintf(stderr, " %lld", t[i] - t[0]);  // clocks of different XCDs are not comparable
-        fprintf(stderr, "\n");
-      }
-    }
-  }
   return WW_OK;
 }

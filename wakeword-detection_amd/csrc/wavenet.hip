@@ -33,7 +33,6 @@
 #undef WIN
 
 #include <type_traits>
-#include <vector>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -43,13 +42,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define WV_PAD 16     // causal zero rows in front of u
 #define WV_INLD 48    // staged input row stride (40 mel + zero pad to 3 k-blocks)
 // wavefronts per workgroup = template parameter NW of the kernel: the 12 row tiles of 16 frames are dealt 12 / NW per wave.
-// Both modes run 12 waves x 1 tile (3 waves per SIMD).  The split-bf16 loop is written over the tiles of a wave, so
-// -DWV_BF16_NW=6 or 4 builds the 2- and 3-tile forms (independent MFMAs / gate evaluations back to back in one wave, a third of
-// the operand reads): measured 45.2 and 44.6 us against 38.9 us for 12 x 1 - a wave's LDS and MFMA -> VALU latencies are
-// covered better by two more waves on the SIMD than by two more tiles in the wave.
-#ifndef WV_BF16_NW
-#define WV_BF16_NW 12
-#endif
+// Both modes run 12 waves x 1 tile (3 waves per SIMD).  The split-bf16 loop is written over the tiles of a wave; its 6- and
+// 4-wave forms (2 and 3 tiles per wave: independent MFMAs / gate evaluations back to back in one wave, a third of the operand
+// reads) measured 45.2 and 44.6 us against 38.9 us for 12 x 1 - a wave's LDS and MFMA -> VALU latencies are covered better
+// by two more waves on the SIMD than by two more tiles in the wave.
 #ifndef WV_F32_WIDE_FROM
 #define WV_F32_WIDE_FROM 256   // the fp32 transposed loop likewise (round 5)
 #endif
@@ -90,7 +86,6 @@ struct wave_args {
   float *enc;           // optional [Nw][T][32]
   const float *enc_in;  // HEAD_ONLY: encoder output to run the detect graph on
   const uint4 *wpk;     // split-bf16 mode: parameter pages [NB][WV_PAGE_U4] (A operands of v_mfma_f32_16x16x32_bf16, then the vectors)
-  long long *stamps;    // development (-DWV_STAMPS=1): [windows][12 waves][WV_STAMP_NB blocks][12] s_memtime inside the split-bf16 loop
   ww_tick_tag tag;      // streaming ticks: the posterior as a {value, tick number} pair instead of the row of `out`
   // TICK != 0 - ONE launch per tick (round 5): the streaming front end's side (common.h) and the model's filterbank
   ww_tick_fe fe;
@@ -108,37 +103,6 @@ struct wave_args {
 #define WT_BUF (WT_MAG + 2 * 260 + 8)  // [2][FFT_LD] complex (16-byte aligned)
 #define WT_END (WT_BUF + 2 * FFT_LD * 4)
 static_assert(WT_BUF % 4 == 0 && WW_MEL_TAPS * 64 <= 768 * 4, "tick front end: LDS layout");
-
-#ifndef WV_STAMPS
-#define WV_STAMPS 0
-#endif
-// probes of round 6 (profiles/r06/wavenet_bf16x3_probes.txt): development builds only (tools/build_variant.sh)
-#ifndef WV_PROBE_NOBAR
-#define WV_PROBE_NOBAR 0
-#endif
-#ifndef WV_PROBE_ACC2
-#define WV_PROBE_ACC2 0
-#endif
-#ifndef WV_PROBE_RCP1
-#define WV_PROBE_RCP1 0
-#endif
-#define WV_STAMP_NB 24
-#if WV_STAMPS
-// Stamp i_ of every block (round 6: all blocks, so that the table can separate the dilations); stamp 11 = the top of the NEXT
-// block, written into this block's row.  Reading s_memtime waits for the wave's outstanding LDS operations as well (one
-// counter): a stamped build runs the same instructions with every counted wait turned into a full one - the table's total per
-// block stands beside the unstamped kernel's so that the price of looking is on record.
-#define WV_STAMP(i_)                                                                                                   \
-  {                                                                                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                                                 \
-    if (a.stamps && lane == 0 && blk - ((i_) == 11 ? 1 : 0) >= 0 && blk < WV_STAMP_NB + ((i_) == 11 ? 1 : 0))          \
-      a.stamps[(((size_t)blockIdx.x * 12 + wave) * WV_STAMP_NB + blk - ((i_) == 11 ? 1 : 0)) * 12 + (i_)] =           \
-          __builtin_amdgcn_s_memtime();                                                                                \
-    __builtin_amdgcn_sched_barrier(0);                                                                                 \
-  }
-#else
-#define WV_STAMP(i_)
-#endif
 
 __device__ __forceinline__ float sigmoid_w(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -754,7 +718,6 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
     const s16x4 one2 = {one, one, 0, 0};                                          // k-slots 4, 5 of lane group 0 = 1.0: the bias slots (hi, lo)
     int pbuf = 0;  // blk % 3
     for (int blk = 0; blk < a.NB; ++blk) {
-      WV_STAMP(0) WV_STAMP(11)
       const int bo = (blk & 1) * U_BUF_B;
       const int d = (int)(((blk < 16 ? dil_lo : dil_hi) >> (4 * (blk & 15))) & 15);
       const int nblk = blk + 2 < a.NB ? blk + 2 : a.NB - 1;                      // unconditional prefetch target
@@ -766,7 +729,6 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
       __builtin_amdgcn_sched_barrier(0);  // keep the loads HERE (the scheduler would sink them to their use)
       const uint4 *pg = pages + pbuf * WV_PAGE_U4;
       const bf16x8 *wsl = (const bf16x8 *)pg + lane;                             // slot q: wsl[q * 64]
-      WV_STAMP(1)
       const float4 bn_s = bnall[blk * 8 + kk], bn_t = bnall[blk * 8 + 4 + kk];
       // BatchNorm affine (wavenet_model.py:57): a tile's u = the undelayed tap's B operand
       s16x4 u2h[WV_MPW], u2l[WV_MPW];
@@ -776,7 +738,6 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
         const float uv[4] = {x[mi][0] * bn_s.x + bn_t.x, x[mi][1] * bn_s.y + bn_t.y, x[mi][2] * bn_s.z + bn_t.z, x[mi][3] * bn_s.w + bn_t.w};
         split4(uv, u2h[mi], u2l[mi]);
       }
-      WV_STAMP(2)
       // hi and lo planes straight from the operand register pairs (immediate offsets: tile, plane)
 #define WV_WR(mi_)                                                                                                   \
   if ((mi_) < WV_MPW)                                                                                                \
@@ -787,7 +748,6 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
       // this block's gate operands (the page was published one barrier ago)
       const bf16x8 w0 = wsl[0 * 64], w1 = wsl[1 * 64], w2 = wsl[2 * 64], w3 = wsl[3 * 64];
       const bf16x8 w4 = wsl[4 * 64], w5 = wsl[5 * 64], w6 = wsl[6 * 64], w7 = wsl[7 * 64];
-      WV_STAMP(3)
       // k-step 0 = tap 2, operands in registers - these MFMAs run while the other waves arrive.  The 8 k-slots of a lane
       // group hold TWO 4-channel groups: (w_hi | w_hi) x (u_hi | u_lo) is hi*hi + hi*lo in one MFMA, (w_lo | bias) x (u_hi | 1, 1)
       // the lo*hi product plus the bias (hi and lo halves in k-slots 4, 5 of lane group 0): api.hip, load_wavenet
@@ -800,15 +760,9 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
         MFMA_BF(as[mi], w0, xua); MFMA_BF(at[mi], w2, xua);
         MFMA_BF(as[mi], w1, xub); MFMA_BF(at[mi], w3, xub);
       }
-      WV_STAMP(4)
       // u complete (all rows, all waves).  At most the 8 operand reads above are younger than the u writes, so "at most 8
       // LDS operations outstanding" means the writes have landed; the operands keep streaming across the barrier.
-#if WV_PROBE_NOBAR  // ablation (wrong results, right instruction stream): what the twelve-wave barrier itself costs
-      asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-#else
       asm volatile("s_waitcnt lgkmcnt(8)\n\ts_barrier" ::: "memory");
-#endif
-      WV_STAMP(5)
       // k-step 1 = (tap 0 | tap 1) = rows t - 2d and t - d (rows < 0 hit the zero pad, d <= 8)
       s16x4 u0h[WV_MPW], u1h[WV_MPW], u0l[WV_MPW], u1l[WV_MPW];
       {
@@ -843,19 +797,6 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
 #pragma unroll
       for (int mi = 0; mi < WV_MPW; ++mi)
         asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(u0h[mi]), "+v"(u1h[mi]), "+v"(u0l[mi]), "+v"(u1l[mi]) : : "memory");
-      WV_STAMP(6)
-#if WV_PROBE_ACC2  // probe (round 6): the delayed taps into accumulators of their own - two MFMA chains of depth 2 and 3 per gate
-                   // instead of one of depth 5, joined by one v_add per row (other bits, still <= 2e-5)
-#pragma unroll
-      for (int mi = 0; mi < WV_MPW; ++mi) {
-        const bf16x8 xdh = cat8(u0h[mi], u1h[mi]), xdl = cat8(u0l[mi], u1l[mi]);
-        f32x4 as2 = {0.f, 0.f, 0.f, 0.f}, at2 = {0.f, 0.f, 0.f, 0.f};
-        MFMA_BF(as2, w4, xdh); MFMA_BF(at2, w6, xdh);
-        MFMA_BF(as2, w5, xdh); MFMA_BF(at2, w7, xdh);
-        MFMA_BF(as2, w4, xdl); MFMA_BF(at2, w6, xdl);
-        as[mi] += as2; at[mi] += at2;
-      }
-#else
 #pragma unroll
       for (int mi = 0; mi < WV_MPW; ++mi) {
         const bf16x8 xdh = cat8(u0h[mi], u1h[mi]), xdl = cat8(u0l[mi], u1l[mi]);
@@ -863,8 +804,6 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
         MFMA_BF(as[mi], w5, xdh); MFMA_BF(at[mi], w7, xdh);
         MFMA_BF(as[mi], w4, xdl); MFMA_BF(at[mi], w6, xdl);
       }
-#endif
-      WV_STAMP(7)
       // gate: tanh(t) * sigmoid(s); biases AND the exp2 scale factors (-log2 e, 2 log2 e) are inside the accumulators
       f32x4 ar[WV_MPW], s0[WV_MPW], s1[WV_MPW];
 #pragma unroll
@@ -872,17 +811,10 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
         float gv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-#if WV_PROBE_RCP1  // probe (round 6): tanh(t) sigmoid(s) = (et - 1) / ((1 + et)(1 + es)) - ONE reciprocal; et clamped so that inf / inf cannot occur
-          const float et = __builtin_amdgcn_exp2f(__builtin_fminf(at[mi][r], 60.0f));
-          const float es = __builtin_amdgcn_exp2f(as[mi][r]);
-          gv[r] = (et - 1.0f) * __builtin_amdgcn_rcpf((1.0f + et) * (1.0f + es));
-#else
           const float et = __builtin_amdgcn_exp2f(at[mi][r]);    // exp(2 t): inf -> tanh 1, 0 -> -1
           const float es = __builtin_amdgcn_exp2f(as[mi][r]);    // exp(-s)
           gv[r] = (1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + et)) * __builtin_amdgcn_rcpf(1.0f + es);
-#endif
         }
-        WV_STAMP(8)
         s16x4 g_h, g_l;
         split4(gv, g_h, g_l);  // the gate product is the res / skip conv's B operand as it stands
         ar[mi] = (f32x4){0.f, 0.f, 0.f, 0.f}; s0[mi] = ar[mi]; s1[mi] = ar[mi];
@@ -890,7 +822,6 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
         MFMA_BF(ar[mi], r0, ga8); MFMA_BF(s0[mi], r2, ga8); MFMA_BF(s1[mi], r4, ga8);
         MFMA_BF(ar[mi], r1, gb8); MFMA_BF(s0[mi], r3, gb8); MFMA_BF(s1[mi], r5, gb8);
       }
-      WV_STAMP(9)
       // residual / skip update; biases ride in the MFMA, and a block without a residual conv has zero
       // res weights and bias (relu(0) = 0), so no special case
 #pragma unroll
@@ -901,7 +832,6 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
           skip[mi][0][r] = skip[mi][0][r] + relu1(s0[mi][r]);
           skip[mi][1][r] = skip[mi][1][r] + relu1(s1[mi][r]);
         }
-      WV_STAMP(10)
       // park page blk+2 (loaded a whole block ago) in the buffer that held page blk-1: every wave is past its
       // reads of that one (they precede the barrier of block blk, which everyone here has passed)
       const int nbuf = pbuf == 0 ? 2 : pbuf - 1;  // (blk + 2) % 3
@@ -1018,16 +948,10 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
 
 size_t ww_wave_workspace(const ww_model *, int) { return 256; }
 
-int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
-                      const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int nw, void *, size_t, float *d_out,
-                      float *d_enc, const ww_tick_tag *tag) {
-  if (nw <= 0) return WW_OK;
-  const ww_wave_dev &v = m->wave;
-  wave_args a = {};
-  a.mel = d_mel;
-  a.wa = {d_win_row, d_win_valid, row0, hop, valid_const, mel_rows};
-  a.T = v.T; a.n_mel = v.n_mel; a.NB = v.NB; a.NOUT = v.NOUT;
+// The model's side of wave_args for the forward and tick launches: sizes, weights, dilations and the residual mask
+static int wave_model_args(ww_ctx *ctx, const ww_wave_dev &v, wave_args &a) {
   if (v.NB > 32) return ww_fail(ctx, WW_EINVAL, "Wavenet with %d blocks: kernel limit 32", v.NB);
+  a.T = v.T; a.n_mel = v.n_mel; a.NB = v.NB; a.NOUT = v.NOUT;
   for (int b = 0; b < v.NB; ++b) {
     if (v.dil[b] < 1 || v.dil[b] > 8) return ww_fail(ctx, WW_EINVAL, "dilation %d of block %d outside 1..8", v.dil[b], b);
     a.dil4[b >> 4] |= (unsigned long long)v.dil[b] << (4 * (b & 15));
@@ -1036,64 +960,32 @@ int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
   a.w_in4 = v.w_in; a.b_in = v.b_in; a.bn_s = v.bn_s; a.bn_t = v.bn_t;
   a.w_gate4 = v.w_gate; a.b_gate = v.b_gate; a.w_rs4 = v.w_rs; a.b_rs = v.b_rs;
   a.d_w1_4 = v.d_w1; a.d_b1 = v.d_b1; a.d_w2_4 = v.d_w2; a.d_b2 = v.d_b2;
+  a.wpk = (const uint4 *)v.wpk;
+  return WW_OK;
+}
+
+int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                      const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int nw, void *, size_t, float *d_out,
+                      float *d_enc, const ww_tick_tag *tag) {
+  if (nw <= 0) return WW_OK;
+  const ww_wave_dev &v = m->wave;
+  wave_args a = {};
+  a.mel = d_mel;
+  a.wa = {d_win_row, d_win_valid, row0, hop, valid_const, mel_rows};
+  if (int rc = wave_model_args(ctx, v, a)) return rc;
   a.out = d_out; a.enc = d_enc;
   if (tag) a.tag = *tag;
   ww_launch_scope scope(ctx, m->precision == WW_PRECISION_BF16X3 ? "wavenet_kernel<bf16x3>" : "wavenet_kernel");
-  a.wpk = (const uint4 *)v.wpk;
-#if WV_STAMPS
-  // development build: WWHIP_WV_STAMPS=1 prints, per block, the mean cycles since the block's top at each stamp (over all windows
-  // and waves), the mean wait at the barrier (stamp 5 - stamp 4) and the spread of the twelve waves' arrivals at it
-  // (max - min of stamp 4 within a window): tools/wv_stamps.py turns the lines into profiles/r06/wavenet_bf16x3_phase_stamps.txt
-  struct stamp_dump {
-    ww_ctx *ctx; long long *d; int n;
-    ~stamp_dump() {
-      if (!d) return;
-      const size_t per_wave = (size_t)WV_STAMP_NB * 12;
-      std::vector<long long> h((size_t)n * 12 * per_wave);
-      hipStreamSynchronize(ctx->stream);
-      hipMemcpy(h.data(), d, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
-      hipFree(d);
-      for (int b = 0; b < WV_STAMP_NB; ++b) {
-        double sum[12] = {0}, wait = 0, spread = 0;
-        long long cnt = 0, wins = 0;
-        for (int w = 0; w < n; ++w) {
-          long long lo = 0, hi = 0;
-          bool any = false;
-          for (int v = 0; v < 12; ++v) {
-            const long long *t = &h[((size_t)w * 12 + v) * per_wave + (size_t)b * 12];
-            if (!t[0] || !t[10]) continue;
-            for (int i = 0; i < 12; ++i) sum[i] += t[i] ? (double)(t[i] - t[0]) : 0.0;
-            wait += (double)(t[5] - t[4]);
-            lo = any ? (t[4] < lo ? t[4] : lo) : t[4];
-            hi = any ? (t[4] > hi ? t[4] : hi) : t[4];
-            any = true;
-            ++cnt;
-          }
-          if (any) { spread += (double)(hi - lo); ++wins; }
-        }
-        fprintf(stderr, "wavenet stamps: block %d waves %lld cycles:", b, cnt);
-        for (int i = 0; i < 12; ++i) fprintf(stderr, " %.0f", sum[i] / (cnt ? cnt : 1));
-        fprintf(stderr, " barrier_wait %.0f arrival_spread %.0f\n", wait / (cnt ? cnt : 1), spread / (wins ? wins : 1));
-      }
-    }
-  } dump{ctx, nullptr, nw};
-  if (getenv("WWHIP_WV_STAMPS") && m->precision == WW_PRECISION_BF16X3 && nw <= WV_BF16_WIDE_FROM) {
-    const size_t bytes = (size_t)nw * 12 * WV_STAMP_NB * 12 * sizeof(long long);
-    WW_HIP(ctx, hipMalloc((void **)&a.stamps, bytes));
-    WW_HIP(ctx, hipMemsetAsync(a.stamps, 0, bytes, ctx->stream));
-    dump.d = a.stamps;
-  }
-#endif
   // split-bf16: twelve waves x one 16-row tile while every window has a CU of its own (the 24 blocks of a window are a serial
   // chain: more waves per window cover its latencies best, 39.1 vs 45.7 us per 256 windows); from the 257th window of a launch
   // on FOUR waves x three tiles (173 registers, 74 KB: TWO workgroups per CU, each wave issuing three tiles' independent MFMAs
   // and gate evaluations back to back): 1,656 vs 1,957 us per 16,384 windows, 69.8 vs 74.5 at 512.  Same arithmetic per
   // tile in both forms: a posterior does not depend on the launch size (tests/test_gpu_parity.py).  (Six waves x two tiles -
   // also two workgroups per CU - lose at every size: 2,393 us.)
-  if (m->precision == WW_PRECISION_BF16X3 && WV_BF16_NW == 12 && nw > WV_BF16_WIDE_FROM)
+  if (m->precision == WW_PRECISION_BF16X3 && nw > WV_BF16_WIDE_FROM)
     hipLaunchKernelGGL((wavenet_kernel<false, true, 4>), dim3(nw), dim3(4 * 64), 0, ctx->stream, a);
   else if (m->precision == WW_PRECISION_BF16X3)
-    hipLaunchKernelGGL((wavenet_kernel<false, true, WV_BF16_NW>), dim3(nw), dim3(WV_BF16_NW * 64), 0, ctx->stream, a);
+    hipLaunchKernelGGL((wavenet_kernel<false, true, 12>), dim3(nw), dim3(12 * 64), 0, ctx->stream, a);
   else if (m->opt_wave_rowmajor)
     hipLaunchKernelGGL((wavenet_kernel<false, false, 12>), dim3(nw), dim3(12 * 64), 0, ctx->stream, a);
   else if (nw > WV_F32_WIDE_FROM)  // (round 5) fp32: the same two forms as the split-bf16 loop, the same bits in both
@@ -1123,17 +1015,7 @@ int ww_k_wave_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int pre
   wave_args a = {};
   a.mel = fe.hist;
   a.wa = {nullptr, nullptr, 0, 0, 0, (int64_t)fe.S * fe.HR};
-  a.T = v.T; a.n_mel = v.n_mel; a.NB = v.NB; a.NOUT = v.NOUT;
-  if (v.NB > 32) return ww_fail(ctx, WW_EINVAL, "Wavenet with %d blocks: kernel limit 32", v.NB);
-  for (int b = 0; b < v.NB; ++b) {
-    if (v.dil[b] < 1 || v.dil[b] > 8) return ww_fail(ctx, WW_EINVAL, "dilation %d of block %d outside 1..8", v.dil[b], b);
-    a.dil4[b >> 4] |= (unsigned long long)v.dil[b] << (4 * (b & 15));
-    if (v.has_res[b]) a.has_res_mask |= 1u << b;
-  }
-  a.w_in4 = v.w_in; a.b_in = v.b_in; a.bn_s = v.bn_s; a.bn_t = v.bn_t;
-  a.w_gate4 = v.w_gate; a.b_gate = v.b_gate; a.w_rs4 = v.w_rs; a.b_rs = v.b_rs;
-  a.d_w1_4 = v.d_w1; a.d_b1 = v.d_b1; a.d_w2_4 = v.d_w2; a.d_b2 = v.d_b2;
-  a.wpk = (const uint4 *)v.wpk;
+  if (int rc = wave_model_args(ctx, v, a)) return rc;
   a.tag = tag;
   a.fe = fe;
   a.mel_start = f.start; a.mel_wpad = f.wpad; a.mel_bias = f.bias;

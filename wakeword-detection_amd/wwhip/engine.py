@@ -65,7 +65,7 @@ class Engine:
         this many windows take front + tail kernels (0 = always one fused kernel); ``"crnn_slide_min"`` - regular
         sliding windows take the once-per-sequence form from this many windows on (0 = never); ``"crnn_tail_mfma"`` - the recurrences
         of those two forms for sixteen windows per workgroup on the matrix pipe: 1 (default) from 9,216 windows per launch on,
-        2 always, 0 never (one window per workgroup on the vector ALU); ``"wavenet_rowmajor"`` - 1: the fp32 Wavenet's row-major block loop of rounds 1-2 instead of the
+        2 always, 0 never (one window per workgroup on the vector ALU), any other value is refused; ``"wavenet_rowmajor"`` - 1: the fp32 Wavenet's row-major block loop of rounds 1-2 instead of the
         transposed one."""
         keys = {"crnn_split_at": _lib.OPT_CRNN_SPLIT_AT, "crnn_slide_min": _lib.OPT_CRNN_SLIDE_MIN,
                 "crnn_tail_mfma": _lib.OPT_CRNN_TAIL_MFMA, "wavenet_rowmajor": _lib.OPT_WAVENET_ROWMAJOR}
