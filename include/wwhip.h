@@ -175,6 +175,9 @@ int ww_model_set_precision(ww_model *model, int precision);
 #define WW_OPT_CRNN_SLIDE_MIN 2
 #define WW_OPT_CRNN_TAIL_MFMA 3
 #define WW_OPT_WAVENET_ROWMAJOR 4
+/*   WW_OPT_WAVE_SEQ_SEGMENT rows per independently computed segment of the Wavenet's sequence form (ww_wave_sequence); 0 (default) = the
+ *                          library's choice.  Every value gives the same bits: it exists so that a test can move the cuts. */
+#define WW_OPT_WAVE_SEQ_SEGMENT 5
 int ww_model_set_option(ww_model *model, int key, int64_t value);
 
 /* ---- front end: PCM -> log-mel ---------------------------------------------------------
@@ -243,6 +246,31 @@ int ww_forward_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_me
 int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
                             const int32_t *seg_nw, int32_t n_seg, int32_t hop, float *d_out);
 
+/* ---- Wavenet on whole sequences (fp32) ----------------------------------------------------
+ * The reference Wavenet is causal and fully convolutional: its trainer builds it with timesteps=None "for variable length"
+ * (wwdetect/wavenet/train_wavenet.py:75, wavenet_model.py:165-172) and only the TFLite export freezes 182 rows.  This is that
+ * reading - NOT the TFLite window form of ww_forward / ww_slide_forward, whose every window zero-pads its own left edge.
+ * For a mel sequence x[0..L), any L >= 1:
+ *   enc[t]     [32]     the skip sum of row t, and
+ *   logits[t]  [n_out]  the head's value BEFORE the max over time, of the model evaluated on the whole sequence: causal taps
+ *                       read zeros in front of row 0 and nothing else is padded;
+ *   post       [n_out]  softmax(max over t of logits[t]): what model(X) returns with timesteps=None;
+ *   post_frames[t]      softmax(m[t]), m[t][c] = max of logits[s][c] over max(0, t - pool_rows + 1) <= s <= t; pool_rows = 0:
+ *                       from row 0.  With pool_rows = the model's window (182) this is the pool of the window form, with true
+ *                       left context in place of the window's padding.
+ * Row t depends on rows t - RF + 1 .. t only (RF = 1 + 2 * sum of the dilations = 181): enc[t], t >= window - 1, carries the bits
+ * of row window - 1 of ww_forward_enc on the window that ends at t, and for L = window the call IS the window form.
+ * Sequence s occupies rows [row_offs[s], row_offs[s + 1]) of the mel buffer (row_offs: n_seq + 1 ascending HOST entries within
+ * [0, total_rows]; rows between or around the sequences are neither read nor written).  The per-row outputs are indexed by
+ * mel row; post by sequence (an empty sequence's row is left as it is).  Every output may be NULL.  No limit on L: a long
+ * sequence is cut into segments that run in parallel (WW_OPT_WAVE_SEQ_SEGMENT), with the same bits wherever the cuts fall.
+ * WW_EINVAL for a CRNN, for a model in WW_PRECISION_BF16X3, n_seq < 0, pool_rows < 0 or descending offsets; n_seq = 0 and empty
+ * sequences are no-ops.  The device form enqueues on the context's stream (row_offs is consumed before it returns). */
+int ww_wave_sequence_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t total_rows, const int64_t *row_offs,
+                         int32_t n_seq, int32_t pool_rows, float *d_enc, float *d_logits, float *d_post_frames, float *d_post);
+int ww_wave_sequence(ww_ctx *ctx, const ww_model *model, const float *mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
+                     int32_t pool_rows, float *enc, float *logits, float *post_frames, float *post);
+
 /* Whole hot path for a batch of equal-length clips resident in HBM (BASELINE configs 2/3):
  * PCM [n_clips][samples_per_clip] -> log-mel -> one zero-padded window per clip ->
  * encode + detect -> d_out [n_clips][n_out].  d_mel_scratch may be NULL (ctx workspace). */
@@ -270,6 +298,15 @@ int ww_clips_forward_dev(ww_ctx *ctx, const ww_model *model, const int16_t *d_pc
  * the forms the tests compare against. */
 #define WW_STREAM_TWO_LAUNCH 2u
 #define WW_STREAM_SYNC_WAIT 4u
+/* WW_STREAM_CAUSAL (fp32 Wavenet only, else WW_EINVAL; not together with WW_STREAM_FULL_RECOMPUTE): the bank advances the
+ * sequence form of ww_wave_sequence one mel row at a time from cached activations instead of recomputing a window per row.  Per
+ * stream it keeps the blocks' last 16 rows of BatchNorm output (24 KB), a ring of the last `window` logit rows and a row count.
+ * EVERY sampled mel row advances that state, whatever bit 0 of is_speech says (the history must not have holes); posteriors are
+ * emitted under the usual rule - for rows that arrive while bit 0 is set - and are post_frames[t][posterior column] of
+ * ww_wave_sequence with pool_rows = window over the stream's rows since its last reset, bit for bit.  Bit 1 freezes the stream
+ * as always; ww_stream_reset zeroes the causal state: the next row is row 0 of a new sequence.  A tick is the front-end kernel
+ * and one model kernel, with either wait.  Without the flag nothing changes. */
+#define WW_STREAM_CAUSAL 8u
 int ww_stream_create(ww_ctx *ctx, const ww_model *model, int32_t n_streams, const ww_frontend_params *fp, uint32_t flags,
                      ww_streams **out);
 int ww_stream_destroy(ww_streams *st);

@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""The fp32 Wavenet's sequence form, measured (profiles/EXPERIMENTS.md).
+
+  throughput  the hey-snips-size stand-in of tools/eval_at_scale.py joined into one stream, mel resident on the device: the
+              sequence form (ww_wave_sequence_dev: post_frames of every row) against the window form at hop 2
+              (ww_forward_segments_dev), alternated in one process; time per 10 ms frame of audio and the sequence kernel's
+              achieved FLOP/s at 113.5 kFLOP per row.  --once: one untimed call of the sequence form (for a kernel trace).
+  latency     StreamBank.step p50 / p99 at S streams: the causal bank against the window bank, alternated in blocks of ticks.
+  distance    on the clips of tools/eval_testset.py: how far post_frames lies from the window form's posterior at the same end
+              row, in logit units (the two readings differ by their left context; this is a description, not a check).
+
+usage: wave_sequence.py throughput [--model Wavenet] [--reps 5] [--once] | latency [--streams 128] [--ticks 4000] |
+       distance [--clips 256]"""
+import argparse, json, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "wakeword-detection_amd")]
+import numpy as np
+
+FLOP_PER_ROW = 20.66e6 / 182  # the network's work per frame: one window's 20.66 MFLOP over its 182 rows
+
+
+def _engine(model):
+    from wwhip.engine import Engine
+    return Engine(os.path.join(ROOT, "wakeword-detection_amd/assets/tf_lite_models", model))
+
+
+def _spread(v):
+    v = np.asarray(v, float)
+    return {"median": float(np.median(v)), "min": float(v.min()), "max": float(v.max()), "n": int(v.size)}
+
+
+def throughput(args):
+    import torch
+    from wwhip.evaluate import synth_testset_scaled
+    eng = _engine(args.model)
+    clips, _ = synth_testset_scaled(args.wake, args.wake)
+    pcm = np.concatenate(clips)
+    hours = len(pcm) / 16000 / 3600
+    mel = eng.logmel([pcm])[0]
+    rows, T, NO = len(mel), eng.window, eng.n_out
+    d_mel = torch.from_numpy(mel).cuda()
+    nw = (rows - T) // 2 + 1
+    d_pf = torch.empty((rows, NO), dtype=torch.float32, device="cuda")
+    d_win = torch.empty((nw, NO), dtype=torch.float32, device="cuda")
+    offs = np.array([0, rows], np.int64)
+    seq = lambda: eng.wave_sequence_dev(d_mel.data_ptr(), rows, offs, d_post_frames_ptr=d_pf.data_ptr())
+    win = lambda: eng.forward_segments_dev(d_mel.data_ptr(), rows, np.array([0], np.int64), np.array([nw], np.int32), 2, d_win.data_ptr())
+    torch.cuda.synchronize()
+    if args.once:
+        seq(); eng.ctx.synchronize()
+        print(json.dumps({"rows": rows, "once": True}))
+        return
+
+    def timed(f):
+        eng.ctx.synchronize()
+        t0 = time.perf_counter(); f(); eng.ctx.synchronize()
+        return time.perf_counter() - t0
+    for f in (seq, win, seq, win):  # warm-up: code objects, the context's workspace at its final size
+        timed(f)
+    t_seq, t_win = [], []
+    for _ in range(args.reps):      # the two sides alternated
+        t_seq.append(timed(seq)); t_win.append(timed(win))
+    eng.ctx.profile(True); seq(); prof = eng.ctx.profile_read(); eng.ctx.profile(False)
+    k_ms = prof["wavenet_seq_kernel"]["total_ms"]
+    # the same end rows: window w ends at row 2 w + T - 1
+    pf, pw = d_pf.cpu().numpy(), d_win.cpu().numpy()
+    frames = len(pcm) / 160
+    out = {"model": args.model, "audio_hours": round(hours, 3), "mel_rows": rows, "windows_hop2": nw,
+           "sequence_s": _spread(t_seq), "window_hop2_s": _spread(t_win),
+           "sequence_ns_per_10ms_frame": float(np.median(t_seq)) / frames * 1e9, "window_hop2_ns_per_10ms_frame": float(np.median(t_win)) / frames * 1e9,
+           "speedup_median": float(np.median(t_win) / np.median(t_seq)),
+           "kernels_ms_one_call": {k: round(v["total_ms"], 3) for k, v in prof.items()},
+           "wavenet_seq_kernel_TFLOPs": rows * FLOP_PER_ROW / (k_ms * 1e-3) / 1e12,
+           "max_abs_dp_same_end_row": float(np.abs(pf[T - 1::2][:nw] - pw).max()),
+           "checksum_sequence": float(pf.sum(dtype=np.float64)), "checksum_window": float(pw.sum(dtype=np.float64))}
+    print(json.dumps(out))
+
+
+def latency(args):
+    from wwhip.engine import StreamBank
+    eng = _engine(args.model)
+    S = args.streams
+    rng = np.random.default_rng(0)
+    frames = np.clip(rng.normal(0, 2500, (64, S, 320)), -32768, 32767).astype(np.int16)
+    speech = np.ones(S, np.uint8)
+    banks = {"causal": StreamBank(eng, S, causal=True), "window": StreamBank(eng, S)}
+    lat = {k: [] for k in banks}
+    for k, b in banks.items():
+        for t in range(300):
+            b.step(frames[t % 64], speech)
+    block = 500
+    for t0 in range(0, args.ticks, block):  # alternated in blocks of ticks
+        for k, b in banks.items():
+            for t in range(t0, min(t0 + block, args.ticks)):
+                a = time.perf_counter(); b.step(frames[t % 64], speech); lat[k].append(time.perf_counter() - a)
+    out = {"model": args.model, "streams": S, "ticks": args.ticks}
+    for k in banks:
+        v = np.array(lat[k]) * 1e6
+        halves = [float(np.percentile(h, 50)) for h in np.array_split(v, 4)]
+        out[k] = {"p50_us": float(np.percentile(v, 50)), "p99_us": float(np.percentile(v, 99)), "mean_us": float(v.mean()),
+                  "p50_us_by_quarter": halves}
+        banks[k].close()
+    print(json.dumps(out))
+
+
+def distance(args):
+    from wwhip.evaluate import synth_testset
+    eng = _engine(args.model)
+    clips, _ = synth_testset(args.clips)
+    mels = [m for m in eng.logmel(clips) if len(m) >= eng.window]
+    T, c = eng.window, eng.posterior_index
+    pf = eng.sequence_forward(mels, want=("post_frames",))["post_frames"]
+    d = []
+    lg = lambda p: np.log(np.clip(p, 1e-30, None)) - np.log(np.clip(1 - p, 1e-30, None))
+    for m, f in zip(mels, pf):
+        w = eng.slide_forward(m, 1)
+        d.append(np.abs(lg(f[T - 1:, c].astype(np.float64)) - lg(w[:, c].astype(np.float64))))
+    d = np.concatenate(d)
+    first = np.array([abs(lg(float(f[T - 1, c])) - lg(float(eng.slide_forward(m[:T], 1)[0, c]))) for m, f in zip(mels[:8], pf[:8])])
+    print(json.dumps({"model": args.model, "clips": len(mels), "end_rows": int(d.size), "logit_distance_median": float(np.median(d)),
+                      "logit_distance_p99": float(np.percentile(d, 99)), "logit_distance_max": float(d.max()),
+                      "at_row_T_minus_1_max": float(first.max())}))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", choices=["throughput", "latency", "distance"])
+    ap.add_argument("--model", default="Wavenet")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--wake", type=int, default=2529)
+    ap.add_argument("--once", action="store_true")
+    ap.add_argument("--streams", type=int, default=128)
+    ap.add_argument("--ticks", type=int, default=4000)
+    ap.add_argument("--clips", type=int, default=256)
+    a = ap.parse_args()
+    {"throughput": throughput, "latency": latency, "distance": distance}[a.what](a)

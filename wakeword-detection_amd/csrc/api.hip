@@ -785,6 +785,7 @@ int ww_model_set_option(ww_model *m, int key, int64_t value) {
       m->opt_tail_mfma = (int)value;
       return WW_OK;
     case WW_OPT_WAVENET_ROWMAJOR: m->opt_wave_rowmajor = value != 0; return WW_OK;
+    case WW_OPT_WAVE_SEQ_SEGMENT: m->opt_wave_seq_segment = (int)value; return WW_OK;
     default: return ww_fail(m->ctx, WW_EINVAL, "unknown model option %d", key);
   }
   WW_GUARD_END(m ? m->ctx : nullptr)
@@ -1179,6 +1180,134 @@ int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, 
     rc = model_forward(ctx, m, d_mel, mel_rows, d_rows + w0, d_valid + w0, 0, 0, 0, n, ws, d_out + (size_t)w0 * NO, nullptr);
     if (rc) return rc;
   }
+  return WW_OK;
+  WW_GUARD_END(ctx)
+}
+
+// ---- the Wavenet's sequence form (wavenet.hip: wavenet_seq_kernel) -----------------------------------------------------------
+// Device scratch of one call: the segment table, the device copy of row_offs, logits where the caller wants none, and the two
+// buffers of the pooled maximum
+struct wave_seq_plan {
+  std::vector<wv_seg> segs;
+  int64_t max_len = 0;
+  size_t b_segs = 0, b_offs = 0, b_z = 0, b_pool = 0;
+  size_t bytes() const { return b_segs + b_offs + b_z + 2 * b_pool; }
+};
+
+static int wave_seq_validate(ww_ctx *ctx, const ww_model *m, int64_t total_rows, const int64_t *row_offs, int32_t n_seq, int32_t pool_rows) {
+  if (m->kind != WW_KIND_WAVENET)
+    return ww_fail(ctx, WW_EINVAL, "ww_wave_sequence: Wavenet models only (a CRNN's bidirectional GRUs have no causal reading)");
+  if (m->precision != WW_PRECISION_FP32) return ww_fail(ctx, WW_EINVAL, "ww_wave_sequence: fp32 only; this model is in split-bf16 mode");
+  if (n_seq < 0) return ww_fail(ctx, WW_EINVAL, "negative sequence count");
+  if (pool_rows < 0) return ww_fail(ctx, WW_EINVAL, "negative pool length");
+  if (total_rows < 0) return ww_fail(ctx, WW_EINVAL, "negative row count");
+  if (n_seq == 0) return WW_OK;
+  if (!row_offs) return ww_fail(ctx, WW_EINVAL, "row_offs is NULL");
+  if (row_offs[0] < 0 || row_offs[n_seq] > total_rows) return ww_fail(ctx, WW_EINVAL, "row_offs leave the mel buffer");
+  for (int s = 0; s < n_seq; ++s)
+    if (row_offs[s + 1] < row_offs[s]) return ww_fail(ctx, WW_EINVAL, "row_offs descend at sequence %d", s);
+  return WW_OK;
+}
+
+// Cuts: a sequence is computed in segments of G rows; every segment but a sequence's first starts RF - 1 rows early and drops them.
+// The library's G makes a segment's warm-up + rows a whole number of 192-row chunks, and about two segments per CU once there is
+// enough work (warm-up: a tenth of the rows at most).
+static void wave_seq_make_plan(const ww_model *m, int64_t total_rows, const int64_t *row_offs, int n_seq, bool need_z, bool need_pool,
+                               wave_seq_plan &pl) {
+  const int rf = ww_wave_receptive_field(m), NO = m->info.n_out;
+  int64_t span = 0;
+  for (int s = 0; s < n_seq; ++s) {
+    span += row_offs[s + 1] - row_offs[s];
+    pl.max_len = std::max<int64_t>(pl.max_len, row_offs[s + 1] - row_offs[s]);
+  }
+  int64_t G = m->opt_wave_seq_segment;
+  if (G <= 0) {
+    int64_t chunks = (span + 2 * WW_NUM_CUS * 192 - 1) / (2 * WW_NUM_CUS * 192);
+    chunks = std::min<int64_t>(std::max<int64_t>(chunks, 10), 64);
+    G = chunks * 192 - (rf - 1);
+    if (G < 192) G = 192;
+  }
+  for (int s = 0; s < n_seq; ++s) {
+    const int64_t o = row_offs[s], len = row_offs[s + 1] - o;
+    for (int64_t s0 = 0; s0 < len; s0 += G) {
+      const int64_t warm = std::min<int64_t>(s0, rf - 1), rows = std::min<int64_t>(G, len - s0);
+      pl.segs.push_back({o + s0 - warm, (int32_t)(warm + rows), (int32_t)warm});
+    }
+  }
+  pl.b_segs = ww_bump::need(pl.segs.size(), sizeof(wv_seg));
+  pl.b_offs = ww_bump::need((size_t)n_seq + 1, 8);
+  pl.b_z = need_z ? ww_bump::need((size_t)total_rows * NO, 4) : 0;
+  pl.b_pool = need_pool ? ww_bump::need((size_t)total_rows * NO, 4) : 0;
+}
+
+static int wave_seq_run(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t total_rows, const int64_t *row_offs, int n_seq,
+                        int pool_rows, float *d_enc, float *d_logits, float *d_pf, float *d_post, const wave_seq_plan &pl, ww_bump &bump) {
+  if (pl.segs.empty()) return WW_OK;
+  if (pl.segs.size() > 0x7fffffffu) return ww_fail(ctx, WW_EINVAL, "too many segments in one call");
+  const int NO = m->info.n_out;
+  wv_seg *d_segs = bump.take<wv_seg>(pl.segs.size());
+  int64_t *d_offs = bump.take<int64_t>((size_t)n_seq + 1);
+  float *d_z = d_logits;
+  if (!d_z && (d_pf || d_post)) d_z = bump.take<float>((size_t)total_rows * NO);
+  float *d_a = d_pf ? bump.take<float>((size_t)total_rows * NO) : nullptr, *d_b = d_pf ? bump.take<float>((size_t)total_rows * NO) : nullptr;
+  WW_HIP(ctx, hipMemcpyAsync(d_segs, pl.segs.data(), pl.segs.size() * sizeof(wv_seg), hipMemcpyHostToDevice, ctx->stream));
+  WW_HIP(ctx, hipMemcpyAsync(d_offs, row_offs, ((size_t)n_seq + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host tables are the caller's / go out of scope
+  int rc = ww_k_wave_sequence(ctx, m, d_mel, d_segs, (int)pl.segs.size(), d_enc, d_z);
+  if (rc) return rc;
+  if (d_pf || d_post) rc = ww_k_wave_pool(ctx, d_z, row_offs[n_seq] - row_offs[0], row_offs[n_seq], NO, d_offs, n_seq, pool_rows, pl.max_len, d_a, d_b, d_pf, d_post);
+  return rc;
+}
+
+int ww_wave_sequence_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
+                         int32_t pool_rows, float *d_enc, float *d_logits, float *d_post_frames, float *d_post) {
+  WW_GUARD_BEGIN
+  if (!ctx || !m) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (int rc = wave_seq_validate(ctx, m, total_rows, row_offs, n_seq, pool_rows)) return rc;
+  if (n_seq == 0 || row_offs[n_seq] == row_offs[0]) return WW_OK;
+  if (!d_mel) return ww_fail(ctx, WW_EINVAL, "NULL mel buffer");
+  if (!d_enc && !d_logits && !d_post_frames && !d_post) return WW_OK;
+  WW_ON_DEVICE(ctx, dev);
+  wave_seq_plan pl;
+  wave_seq_make_plan(m, total_rows, row_offs, n_seq, !d_logits && (d_post_frames || d_post), d_post_frames != nullptr, pl);
+  if (int rc = ww_ensure(ctx, ctx->dev, pl.bytes() + 1024, false)) return rc;
+  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
+  return wave_seq_run(ctx, m, d_mel, total_rows, row_offs, n_seq, pool_rows, d_enc, d_logits, d_post_frames, d_post, pl, bump);
+  WW_GUARD_END(ctx)
+}
+
+int ww_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
+                     int32_t pool_rows, float *enc, float *logits, float *post_frames, float *post) {
+  WW_GUARD_BEGIN
+  if (!ctx || !m) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (int rc = wave_seq_validate(ctx, m, total_rows, row_offs, n_seq, pool_rows)) return rc;
+  if (n_seq == 0 || row_offs[n_seq] == row_offs[0]) return WW_OK;
+  if (!mel) return ww_fail(ctx, WW_EINVAL, "NULL mel buffer");
+  if (!enc && !logits && !post_frames && !post) return WW_OK;
+  WW_ON_DEVICE(ctx, dev);
+  const int F = m->info.n_mel, NO = m->info.n_out, S = m->info.enc_width;
+  wave_seq_plan pl;
+  wave_seq_make_plan(m, total_rows, row_offs, n_seq, !logits && (post_frames || post), post_frames != nullptr, pl);
+  const size_t b_mel = ww_bump::need((size_t)total_rows * F, 4), b_enc = enc ? ww_bump::need((size_t)total_rows * S, 4) : 0;
+  const size_t b_rows = ww_bump::need((size_t)total_rows * NO, 4), b_post = ww_bump::need((size_t)n_seq * NO, 4);
+  if (int rc = ww_ensure(ctx, ctx->dev, b_mel + b_enc + 2 * b_rows + b_post + pl.bytes() + 1024, false)) return rc;
+  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
+  float *d_mel = bump.take<float>((size_t)total_rows * F);
+  float *d_enc = enc ? bump.take<float>((size_t)total_rows * S) : nullptr;
+  float *d_z = logits ? bump.take<float>((size_t)total_rows * NO) : nullptr;
+  float *d_pf = post_frames ? bump.take<float>((size_t)total_rows * NO) : nullptr;
+  float *d_post = post ? bump.take<float>((size_t)n_seq * NO) : nullptr;
+  // rows of the mel buffer outside every sequence are never read; rows of the outputs outside every sequence are never written:
+  // the caller's bytes there stay as they are
+  const int64_t r0 = row_offs[0], r1 = row_offs[n_seq];
+  WW_HIP(ctx, hipMemcpyAsync(d_mel + r0 * F, mel + r0 * F, (size_t)(r1 - r0) * F * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (d_post) WW_HIP(ctx, hipMemcpyAsync(d_post, post, (size_t)n_seq * NO * 4, hipMemcpyHostToDevice, ctx->stream));  // (empty sequences keep theirs)
+  if (int rc = wave_seq_run(ctx, m, d_mel, total_rows, row_offs, n_seq, pool_rows, d_enc, d_z, d_pf, d_post, pl, bump)) return rc;
+  if (enc) WW_HIP(ctx, hipMemcpyAsync(enc + r0 * S, d_enc + r0 * S, (size_t)(r1 - r0) * S * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (logits) WW_HIP(ctx, hipMemcpyAsync(logits + r0 * NO, d_z + r0 * NO, (size_t)(r1 - r0) * NO * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (post_frames) WW_HIP(ctx, hipMemcpyAsync(post_frames + r0 * NO, d_pf + r0 * NO, (size_t)(r1 - r0) * NO * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (post) WW_HIP(ctx, hipMemcpyAsync(post, d_post, (size_t)n_seq * NO * 4, hipMemcpyDeviceToHost, ctx->stream));
+  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return WW_OK;
   WW_GUARD_END(ctx)
 }

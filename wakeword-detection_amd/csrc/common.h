@@ -125,6 +125,7 @@ struct ww_model {
   int opt_slide_min = 64;   // WW_OPT_CRNN_SLIDE_MIN
   int opt_tail_mfma = 1;    // WW_OPT_CRNN_TAIL_MFMA
   int opt_wave_rowmajor = 0;  // WW_OPT_WAVENET_ROWMAJOR
+  int opt_wave_seq_segment = 0;  // WW_OPT_WAVE_SEQ_SEGMENT (0 = the library's choice)
   std::vector<void *> allocs;
 };
 
@@ -294,6 +295,22 @@ int ww_k_posterior_pick(ww_ctx *ctx, const float *d_rows, int64_t n, int n_out, 
                         float *d_out);
 bool ww_wave_tick_capable(const ww_model *m, int n_streams);
 int ww_k_wave_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, const ww_tick_tag &tag);
+// The fp32 Wavenet's sequence form (wavenet.hip: wavenet_seq_kernel).  A segment = rows [row0, row0 + n) of the mel buffer, all of
+// one sequence; outputs of its first `skip` rows (the warm-up of a segment that does not start at its sequence's row 0) are
+// discarded.
+struct wv_seg {
+  int64_t row0;
+  int32_t n, skip;
+};
+int ww_wave_receptive_field(const ww_model *m);  // 1 + 2 * sum of the dilations
+int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const wv_seg *d_segs, int n_segs, float *d_enc, float *d_logits);
+// rows = offs[n_seq] - offs[0] (the rows that belong to a sequence), row_end = offs[n_seq]
+int ww_k_wave_pool(ww_ctx *ctx, const float *d_z, int64_t rows, int64_t row_end, int n_out, const int64_t *d_offs, int n_seq, int64_t pool_rows,
+                   int64_t max_len, float *d_a, float *d_b, float *d_pf, float *d_post);
+#define WW_WAVE_STATE_BLOCK 256  // floats of carried state per block and stream: [4 channel groups][16 rows][4]
+int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, const int64_t *d_win_row, const int32_t *d_win_valid,
+                          const int32_t *d_win_aux, int nw, float *d_state, float *d_zring, int32_t *d_zpos, float *d_out,
+                          const ww_tick_tag *tag);
 int ww_k_far_frr(ww_ctx *ctx, const float *d_pos, int64_t n_pos, const float *d_neg, int64_t n_neg, int win,
                  const double *d_thr, int n_thr, double *d_smoothed, unsigned long long *d_pos_cnt,
                  unsigned long long *d_fa_cnt);

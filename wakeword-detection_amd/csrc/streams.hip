@@ -79,6 +79,11 @@ struct ww_streams {
   int32_t *h_win_aux = nullptr, *d_win_aux = nullptr;
   std::vector<int> rowq;
   bool incremental = false;
+  // WW_STREAM_CAUSAL (fp32 Wavenet): the sequence form advanced row by row (wavenet.hip: wavenet_seq_kernel<1, stream>) - per stream
+  // the blocks' last 16 rows of BatchNorm output, a ring of the last T logit rows, and {next ring slot, rows held}
+  bool causal = false;
+  float *wstate = nullptr, *zring = nullptr;  // [S][NB][WW_WAVE_STATE_BLOCK], [S][T][16]
+  int32_t *zpos = nullptr;                    // [S][2]
   // host timeline of ww_stream_step (ww_stream_timeline): nanoseconds per phase summed over the ticks since the last reset
   uint64_t tl_ns[WW_STREAM_TL_PHASES] = {0};
   int64_t tl_ticks = 0;
@@ -221,6 +226,15 @@ __global__ __launch_bounds__(128) void stream_frontend_kernel(stream_fe_args a) 
   for (int i = tid; i < keep; i += 128) ring[i] = x[n_frames * a.hop + i];
 }
 
+// a causal bank's reset: the next row is row 0 of a new sequence (zero history, empty ring; the ring's rows need no clearing)
+__global__ void stream_causal_reset_kernel(float *wstate, int32_t *zpos, const int32_t *ids, int S, int state_floats) {
+  const int b = blockIdx.x;
+  const int s = ids ? ids[b] : b;
+  if (s < 0 || s >= S) return;
+  for (int i = threadIdx.x; i < state_floats; i += blockDim.x) wstate[(size_t)s * state_floats + i] = 0.f;
+  if (threadIdx.x < 2) zpos[2 * s + threadIdx.x] = 0;
+}
+
 __global__ void stream_reset_kernel(float *hist, const int32_t *ids, int S, int HR, int F, float *gxc, const float *gx_zero) {
   const int b = blockIdx.x;
   const int s = ids ? ids[b] : b;
@@ -239,7 +253,7 @@ int ww_stream_destroy(ww_streams *st) {
   if (!st) return WW_OK;
   ww_device_scope dev_scope(st->ctx->device);
   hipStreamSynchronize(st->ctx->stream);
-  void *dev[] = {st->ring, st->hist, st->prev, st->d_pack, st->ws, st->gxc, st->gx_zero};
+  void *dev[] = {st->ring, st->hist, st->prev, st->d_pack, st->ws, st->gxc, st->gx_zero, st->wstate, st->zring, st->zpos};
   for (void *p : dev)
     if (p) hipFree(p);
   void *host[] = {st->h_pack, st->h_out, st->h_tag};
@@ -255,8 +269,13 @@ int ww_stream_create(ww_ctx *ctx, const ww_model *model, int32_t S, const ww_fro
   WW_GUARD_BEGIN
   if (!ctx || !model || !fp || !out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
   *out = nullptr;
-  if (flags & ~(uint32_t)(WW_STREAM_FULL_RECOMPUTE | WW_STREAM_TWO_LAUNCH | WW_STREAM_SYNC_WAIT))
+  if (flags & ~(uint32_t)(WW_STREAM_FULL_RECOMPUTE | WW_STREAM_TWO_LAUNCH | WW_STREAM_SYNC_WAIT | WW_STREAM_CAUSAL))
     return ww_fail(ctx, WW_EINVAL, "unknown stream flags 0x%x", flags);
+  const bool causal = (flags & WW_STREAM_CAUSAL) != 0;
+  if (causal && (flags & WW_STREAM_FULL_RECOMPUTE))
+    return ww_fail(ctx, WW_EINVAL, "WW_STREAM_CAUSAL advances cached activations: it cannot be combined with WW_STREAM_FULL_RECOMPUTE");
+  if (causal && (model->kind != WW_KIND_WAVENET || model->precision != WW_PRECISION_FP32))
+    return ww_fail(ctx, WW_EINVAL, "WW_STREAM_CAUSAL is the fp32 Wavenet's sequence form: not for a CRNN or a model in split-bf16 mode");
   if (S <= 0 || S > 65535) return ww_fail(ctx, WW_EINVAL, "stream count %d out of range (1..65535)", S);
   if (fp->hop != 160) return ww_fail(ctx, WW_EINVAL, "streaming mode supports hop 160 (10 ms @ 16 kHz) only, got %d", fp->hop);
   if (!(fp->pcm_divisor > 0.f)) return ww_fail(ctx, WW_EINVAL, "pcm_divisor must be positive");
@@ -272,7 +291,8 @@ int ww_stream_create(ww_ctx *ctx, const ww_model *model, int32_t S, const ww_fro
   st->incremental = ww_crnn_stream_capable(model) && !(flags & WW_STREAM_FULL_RECOMPUTE);
   // ONE launch per tick: the incremental CRNN at any size (tools/stream_forms.py: 7 % faster from 128 to 1,024 streams), the
   // Wavenet while a tick's windows stay within its twelve-wave form (ww_wave_tick_capable: up to 128 streams)
-  st->one_launch = !(flags & WW_STREAM_TWO_LAUNCH) &&
+  st->causal = causal;  // (always the front-end kernel + one model kernel)
+  st->one_launch = !causal && !(flags & WW_STREAM_TWO_LAUNCH) &&
                    ((st->incremental && model->filt.n_mel == 40) || ww_wave_tick_capable(model, S));
   // a borrowed stream is the caller's: when the call returns everything enqueued on it has completed, as before
   st->poll = ctx->own_stream && !(flags & WW_STREAM_SYNC_WAIT);
@@ -340,6 +360,16 @@ int ww_stream_create(ww_ctx *ctx, const ww_model *model, int32_t S, const ww_fro
       return ww_fail(ctx, WW_EHIP, "streaming CRNN set-up failed");
     }
   }
+  if (causal) {
+    const size_t b_state = (size_t)S * (int)model->wave.dil.size() * WW_WAVE_STATE_BLOCK * 4, b_ring = (size_t)S * st->T * 16 * 4;
+    if (hipMalloc((void **)&st->wstate, b_state) != hipSuccess || hipMalloc((void **)&st->zring, b_ring) != hipSuccess ||
+        hipMalloc((void **)&st->zpos, (size_t)S * 2 * 4) != hipSuccess)
+      return ww_fail(ctx, WW_ENOMEM, "cannot allocate the causal state of %d streams", S);
+    hipMemsetAsync(st->wstate, 0, b_state, ctx->stream);
+    hipMemsetAsync(st->zring, 0, b_ring, ctx->stream);
+    hipMemsetAsync(st->zpos, 0, (size_t)S * 2 * 4, ctx->stream);
+    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
   *out = own.release();
   return WW_OK;
   WW_GUARD_END(ctx)
@@ -365,6 +395,9 @@ int ww_stream_reset(ww_streams *st, const int32_t *ids, int32_t n) {
   }
   hipLaunchKernelGGL(stream_reset_kernel, dim3(count), dim3(256), 0, ctx->stream, st->hist, (const int32_t *)d_ids, st->S, st->HR, st->F,
                      st->gxc, (const float *)st->gx_zero);
+  if (st->causal)
+    hipLaunchKernelGGL(stream_causal_reset_kernel, dim3(count), dim3(256), 0, ctx->stream, st->wstate, st->zpos, (const int32_t *)d_ids, st->S,
+                       (int)st->model->wave.dil.size() * WW_WAVE_STATE_BLOCK);
   WW_HIP(ctx, hipGetLastError());
   WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // WakewordTrigger.reset (tflite.py:241-246): sample window emptied, frame window zeroed;
@@ -454,7 +487,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   int16_t *h_frames = (int16_t *)((char *)st->h_frames + cp);
   int32_t *h_ctl = (int32_t *)((char *)st->h_ctl + cp);
   st->expect.clear();
-  int nw = 0;
+  int nw = 0, nw_c = 0;  // windows of the tick | causal: streams with new rows
   for (int s = 0; s < S; ++s) {
     const int flags = is_speech[s] & 3;
     int nf = 0;
@@ -472,6 +505,18 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
       h_ctl[s * 4 + 3] = st->pos[s] | (st->rowq[s] << 16);
       for (int k = 0; k < np; ++k) st->expect.push_back(2 * s + k);
       if (!(flags & 2)) st->par[s] ^= 1;
+    } else if (st->causal) {
+      // every sampled row is analysed and advances the stream's state; bit 0 only decides whether its posterior is emitted.  One
+      // descriptor per stream with new rows: they are rows pos, pos + 1 of its mirrored ring (contiguous: pos + 1 <= R)
+      h_ctl[s * 4 + 2] = flags | 1;
+      h_ctl[s * 4 + 3] = st->pos[s];
+      if (nf) {
+        st->h_win_row[nw_c] = (int64_t)s * st->HR + st->pos[s];
+        st->h_win_valid[nw_c] = nf;
+        st->h_win_aux[nw_c] = s | ((np ? 1 : 0) << 16);
+        ++nw_c;
+      }
+      for (int k = 0; k < np; ++k) st->expect.push_back(2 * s + k);
     } else {
       h_ctl[s * 4 + 2] = flags;
       h_ctl[s * 4 + 3] = st->pos[s];
@@ -485,7 +530,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     }
     nw += np;
     if (!(flags & 2)) st->fill[s] = st->fill[s] + WW_CHUNK - nf * hop;
-    st->pos[s] = (st->pos[s] + np) % R;
+    st->pos[s] = (st->pos[s] + (st->causal ? nf : np)) % R;
     st->rowq[s] = (st->rowq[s] + np) % WW_STREAM_GXC;
   }
   tl[1] = st_now_ns();
@@ -517,7 +562,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     a.h_row = (const int64_t *)(st->h_pack_dev + ((char *)st->h_win_row - st->h_pack));
     a.h_valid = (const int32_t *)(st->h_pack_dev + ((char *)st->h_win_valid - st->h_pack));
     a.h_aux = (const int32_t *)(st->h_pack_dev + ((char *)st->h_win_aux - st->h_pack));
-    a.d_row = st->d_win_row; a.d_valid = st->d_win_valid; a.d_aux = st->d_win_aux; a.nw = nw; a.S = S;
+    a.d_row = st->d_win_row; a.d_valid = st->d_win_valid; a.d_aux = st->d_win_aux; a.nw = st->causal ? nw_c : nw; a.S = S;
     a.ring = st->ring;
     a.hist = st->hist; a.prev = st->prev;
     a.T = st->T; a.F = st->F; a.HR = st->HR;
@@ -537,7 +582,15 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     }
     WW_HIP(ctx, hipGetLastError());
     tl[3] = st_now_ns();
-    if (nw && !st->incremental) {
+    if (st->causal) {
+      // the model kernel of a causal tick: one workgroup per stream with new rows; posteriors land in slot 2 s + k.  Polled only
+      // when the tick owes a posterior (a tick that owes none still has to see its front end through before the next one
+      // rewrites the page-locked block)
+      tagged = st->poll && !st->expect.empty();
+      int rc = ww_k_wave_stream_tick(ctx, m, st->hist, st->d_win_row, st->d_win_valid, st->d_win_aux, nw_c, st->wstate, st->zring, st->zpos,
+                                     st->h_out_dev, tagged ? &tag : nullptr);
+      if (rc) return rc;
+    } else if (nw && !st->incremental) {
       // the per-window kernels' scratch under the model's options of THIS tick (ww_model_set_option may have lowered the
       // front/tail threshold since the bank was created: the split form then wants nw x 19 x 192 floats)
       const size_t need = m->kind == WW_KIND_CRNN ? ww_crnn_workspace(m, nw, false) : ww_wave_workspace(m, nw);
@@ -551,7 +604,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
         st->ws_bytes = want > need ? want : need;
       }
     }
-    if (nw) {
+    if (nw && !st->causal) {
       // the heads store a tick's few posteriors straight into pinned host memory - as {value, tick number} pairs where the
       // launch form writes them (every one-kernel form), else as rows of h_out: no device-to-host copy (a DMA operation of
       // its own) between the last kernel and the host's wake-up
@@ -580,10 +633,10 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     post[s * 2 + 1] = 0.f;
     for (int k = 0; k < n_post[s]; ++k, ++w) {
       if (tagged) {
-        const unsigned bits = (unsigned)st->h_tag[st->one_launch ? 2 * s + k : w];
+        const unsigned bits = (unsigned)st->h_tag[st->one_launch || st->causal ? 2 * s + k : w];
         memcpy(&post[s * 2 + k], &bits, 4);
       } else {
-        post[s * 2 + k] = st->h_out[(size_t)w * st->NO + pidx];
+        post[s * 2 + k] = st->h_out[(size_t)(st->causal ? 2 * s + k : w) * st->NO + pidx];
       }
     }
   }

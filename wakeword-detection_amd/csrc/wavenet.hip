@@ -27,6 +27,10 @@
 // v_mfma_f32_16x16x32_bf16, operands straight from registers, parameters through LDS pages.
 //
 // The detect head (ReLU, 1x1 32->32 ReLU, 1x1 32->2, max over time, softmax) runs in the same launch.
+//
+// wavenet_seq_kernel (fp32): the same block loop over a mel sequence of ANY length - the model as its trainer builds it with
+// timesteps=None, causal zeros in front of row 0 only - walked in chunks with each block's last 16 rows of u carried from chunk
+// to chunk; whole sequences (ww_wave_sequence) and, one wave per stream, a causal bank's tick (WW_STREAM_CAUSAL).  See there.
 #include "common.h"
 #include "fft_device.h"
 #undef NB   // (fft_device.h: bins of the transform; here NB is the model's block count)
@@ -209,6 +213,166 @@ __device__ __forceinline__ bf16x8 cat8(s16x4 first, s16x4 second) {
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define WV_SLOTS 14  // A-operand slots per block: gate (2 k-steps x {sig,tanh} x 2) = 8, res | skip (3 m-tiles x 2) = 6
 #define WV_PAGE_U4 (WV_SLOTS * 64)  // one block's parameter page in 16-byte units (the conv biases sit in padded k-slots)
+
+// ---- the fp32 transposed block body, the detect head of one 16-row tile and the 16-lane softmax: ONE definition each, used by
+//      wavenet_kernel (a window per workgroup) and wavenet_seq_kernel (a sequence walked in chunks, below).  DESIGN.md 4.3: one
+//      association of every sum, whatever the dispatch - a time step's chains do not depend on the tile or chunk it sits in.
+struct wv_wblk { float4 wg[3][2], wrs[3]; };
+struct wv_vblk { float4 bns, bnt, bsig, btanh; };
+__device__ __forceinline__ f32x4 wv_f4(const float4 &v) { return (f32x4){v.x, v.y, v.z, v.w}; }
+__device__ __forceinline__ void wv_wload(const wave_args &a, int blk, int j, int kk, wv_wblk &p) {
+  const float *wg = a.w_gate4 + (size_t)blk * 3 * 4 * 32 * 4, *wrs = a.w_rs4 + (size_t)blk * 4 * 48 * 4;
+  const unsigned og = (unsigned)(kk * 32 + j) * 4, ors = (unsigned)(kk * 48 + j) * 4;
+#pragma unroll
+  for (int kb = 0; kb < 3; ++kb)
+#pragma unroll
+    for (int n = 0; n < 2; ++n) p.wg[kb][n] = *(const float4 *)(wg + og + kb * 4 * 32 * 4 + n * 16 * 4);
+#pragma unroll
+  for (int n = 0; n < 3; ++n) p.wrs[n] = *(const float4 *)(wrs + ors + n * 16 * 4);
+}
+// a block's seven small vectors (this lane's channel group): read from the table one block AHEAD, behind the barrier, so
+// that no LDS round trip sits in front of the u write, the accumulators' initial values or the res | skip products
+// (the BatchNorm pair and the gate biases, which a block needs at once; the res | skip biases are requested at the top of their
+// own block and used ~1,500 cycles later: prefetching all seven costs 56 registers and spills)
+__device__ __forceinline__ void wv_vload(const float *vtab, int blk, int kk, wv_vblk &v) {
+  const float4 *vt = (const float4 *)(vtab + blk * 112) + kk;  // vector q: vt[4 q]
+  v.bns = vt[0]; v.bnt = vt[4]; v.bsig = vt[8]; v.btanh = vt[12];
+}
+// Written over a wave's MPW tiles (round 5: launches of more than 256 windows run FOUR waves x three tiles, two
+// workgroups per CU - the form that gave the split-bf16 loop 14 % at scale; up to 256 windows - one per CU - twelve waves x
+// one tile): the tiles' MFMAs and gate evaluations are independent instructions back to back, the per-tile arithmetic is
+// the same source in both forms, so a posterior does not depend on the launch size.
+// UPL: floats per channel-group plane of a u buffer ((rows + WV_PAD) * 4); tl: this lane's time column in the wave's first tile.
+// HIST (the sequence form): the WV_PAD rows in front of u are not zeros but the block's last WV_PAD rows of u from the chunk
+// before - hist[blk][kk][row][4], parked in the pad rows in front of the barrier by the wave with hist_wave set, and replaced
+// behind it by rows [valid, valid + WV_PAD) of [pad | u], i.e. the last WV_PAD rows up to the chunk's last valid row.  One
+// wave does both and a wave's LDS operations complete in issue order, so the history needs no barrier of its own.
+template <int MPW, int UPL, bool HIST>
+__device__ __forceinline__ void wv_block_t(const wave_args &a, int blk, float *ubuf, const float *vtab, int j, int kk, int tl,
+                                           f32x4 (&x)[MPW], f32x4 (&skip)[MPW][2], const wv_wblk &P, wv_wblk &Pnext,
+                                           const wv_vblk &V, wv_vblk &Vnext, float *hist = nullptr, int valid = 0,
+                                           bool hist_wave = false) {
+  float *u = ubuf + (blk & 1) * 4 * UPL + kk * UPL + WV_PAD * 4;          // row 0 of this lane's channel-group plane
+  const int d = (int)((a.dil4[blk >> 4] >> (4 * (blk & 15))) & 15);
+  const float4 *vt = (const float4 *)(vtab + blk * 112) + kk;
+  const float4 bres = vt[16], bsk0 = vt[20], bsk1 = vt[24];
+  f32x4 uv[MPW], as[MPW], at[MPW];
+  f32x4 hv = {0.f, 0.f, 0.f, 0.f};
+  if (HIST && hist_wave) hv = *(const f32x4 *)(hist + blk * (4 * WV_PAD * 4) + (kk * WV_PAD + j) * 4);
+#pragma unroll
+  for (int mi = 0; mi < MPW; ++mi) {
+    uv[mi] = (f32x4){x[mi][0] * V.bns.x + V.bnt.x, x[mi][1] * V.bns.y + V.bnt.y, x[mi][2] * V.bns.z + V.bnt.z,
+                     x[mi][3] * V.bns.w + V.bnt.w};
+    *(f32x4 *)(u + (tl + 16 * mi) * 4) = uv[mi];
+  }
+  const int nb = blk + 1 < a.NB ? blk + 1 : blk;
+  wv_wload(a, nb, j, kk, Pnext);  // unconditional (clamped) prefetch, as the row-major loop
+#pragma unroll
+  for (int mi = 0; mi < MPW; ++mi) {
+    as[mi] = wv_f4(V.bsig);
+    at[mi] = wv_f4(V.btanh);
+    MFMA4(as[mi], P.wg[2][0], uv[mi]);             // tap 2 = this row: runs while the other waves arrive
+    MFMA4(at[mi], P.wg[2][1], uv[mi]);
+  }
+  if (HIST && hist_wave) *(f32x4 *)(u + (j - WV_PAD) * 4) = hv;
+  __syncthreads();  // u complete (all rows, all waves)
+  f32x4 t0v[MPW], t1v[MPW];
+#pragma unroll
+  for (int mi = 0; mi < MPW; ++mi) {            // rows < 0 hit the pad (d <= 8)
+    t0v[mi] = *(const f32x4 *)(u + (tl + 16 * mi - 2 * d) * 4);
+    t1v[mi] = *(const f32x4 *)(u + (tl + 16 * mi - d) * 4);
+  }
+  wv_vload(vtab, nb, kk, Vnext);
+  if (HIST && hist_wave) hv = *(const f32x4 *)(u + (valid - WV_PAD + j) * 4);
+  __builtin_amdgcn_sched_barrier(0);  // the tap reads (and the table reads behind them) are in flight before the first wait
+  const int has_res = (a.has_res_mask >> blk) & 1;
+#pragma unroll
+  for (int mi = 0; mi < MPW; ++mi) {
+    MFMA4(as[mi], P.wg[0][0], t0v[mi]);
+    MFMA4(at[mi], P.wg[0][1], t0v[mi]);
+    MFMA4(as[mi], P.wg[1][0], t1v[mi]);
+    MFMA4(at[mi], P.wg[1][1], t1v[mi]);
+  }
+  if (HIST && hist_wave) *(f32x4 *)(hist + blk * (4 * WV_PAD * 4) + (kk * WV_PAD + j) * 4) = hv;
+#pragma unroll
+  for (int mi = 0; mi < MPW; ++mi) {
+    const f32x4 gv = {fast_tanh_w(at[mi][0]) * fast_sigmoid_w(as[mi][0]), fast_tanh_w(at[mi][1]) * fast_sigmoid_w(as[mi][1]),
+                      fast_tanh_w(at[mi][2]) * fast_sigmoid_w(as[mi][2]), fast_tanh_w(at[mi][3]) * fast_sigmoid_w(as[mi][3])};
+    f32x4 ar = wv_f4(bres), s0 = wv_f4(bsk0), s1 = wv_f4(bsk1);
+    // (hand-interleaving the k-steps of the accumulators - dependent MFMAs issue after 40 cycles, independent ones after 32 - was
+    //  1 % SLOWER: with three waves per SIMD the other waves fill those 8 cycles, and the compiler's own order keeps fewer values live)
+    if (has_res) { MFMA4(ar, P.wrs[0], gv); }
+    MFMA4(s0, P.wrs[1], gv);
+    MFMA4(s1, P.wrs[2], gv);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (has_res) x[mi][r] = relu1(ar[r]) + x[mi][r];
+      skip[mi][0][r] = skip[mi][0][r] + relu1(s0[r]);
+      skip[mi][1][r] = skip[mi][1][r] + relu1(s1[r]);
+    }
+  }
+}
+
+// The detect head's two 1x1 convs on one 16-row tile: ReLU(skip sums) -> 32 -> ReLU -> NOUT (padded to 16), through the wave-private
+// tile ht [16][32].  Returns the logits WITHOUT the last bias: register r of a lane = row 4 kk + r of the tile, column j.
+struct wv_head_w { float4 w1[2][2], w2[2]; float b1a, b1b, b2; };
+__device__ __forceinline__ void wv_head_load(const wave_args &a, int j, int kk, wv_head_w &h) {
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+    for (int n = 0; n < 2; ++n) h.w1[kb][n] = *(const float4 *)(a.d_w1_4 + (unsigned)((kb * 4 + kk) * 32 + n * 16 + j) * 4);
+    h.w2[kb] = *(const float4 *)(a.d_w2_4 + (unsigned)((kb * 4 + kk) * 16 + j) * 4);
+  }
+  const unsigned uj = (unsigned)j;  // (uniform base + one 32-bit per-lane offset, as wave_blk_load)
+  h.b1a = a.d_b1[uj]; h.b1b = a.d_b1[uj + 16]; h.b2 = a.d_b2[uj];
+}
+template <bool TRANSPOSED>
+__device__ __forceinline__ f32x4 wv_head_tile(const f32x4 (&sk)[2], float *ht, const wv_head_w &h, int j, int kk) {
+  if (TRANSPOSED) {
+    *(float4 *)(ht + j * WV_S + kk * 4) = make_float4(fmaxf(sk[0][0], 0.f), fmaxf(sk[0][1], 0.f), fmaxf(sk[0][2], 0.f), fmaxf(sk[0][3], 0.f));
+    *(float4 *)(ht + j * WV_S + 16 + kk * 4) = make_float4(fmaxf(sk[1][0], 0.f), fmaxf(sk[1][1], 0.f), fmaxf(sk[1][2], 0.f), fmaxf(sk[1][3], 0.f));
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      ht[(kk * 4 + r) * WV_S + j] = fmaxf(sk[0][r], 0.f);
+      ht[(kk * 4 + r) * WV_S + 16 + j] = fmaxf(sk[1][r], 0.f);
+    }
+  }
+  wsync();
+  f32x4 h0 = {0.f, 0.f, 0.f, 0.f}, h1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb) {
+    const float4 av = *(const float4 *)(ht + j * WV_S + kb * 16 + kk * 4);
+    MFMA4(h0, av, h.w1[kb][0]);
+    MFMA4(h1, av, h.w1[kb][1]);
+  }
+  wsync();
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    ht[(kk * 4 + r) * WV_S + j] = fmaxf(h0[r] + h.b1a, 0.f);
+    ht[(kk * 4 + r) * WV_S + 16 + j] = fmaxf(h1[r] + h.b1b, 0.f);
+  }
+  wsync();
+  f32x4 y = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb) {
+    const float4 av = *(const float4 *)(ht + j * WV_S + kb * 16 + kk * 4);
+    MFMA4(y, av, h.w2[kb]);
+  }
+  wsync();
+  return y;
+}
+
+// softmax over the NOUT <= 16 pooled logits held by lanes 0..15 of a wave (lane c = column c; call it from those lanes): the
+// value of this lane's column
+__device__ __forceinline__ float wv_softmax16(float v, int c, int NOUT) {
+  float mx = (c < NOUT) ? v : -INFINITY;
+  for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  float e = (c < NOUT) ? expf(v - mx) : 0.f;
+  float sum = e;
+  for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o);
+  return e / sum;
+}
 
 // FP32T: the fp32 block loop in the TRANSPOSED form of the split-bf16 loop (channels x time; round 3) - see its comment below.
 // TICK = 1 / 2 (fp32 / fp64 transform) - ONE launch per streaming tick (round 5; crnn.hip's crnn_stream_kernel<FE> has the full
@@ -507,96 +671,15 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
       const int b = i / (4 * WV_PAD * 4), k = (i / (WV_PAD * 4)) & 3, o = i % (WV_PAD * 4);
       ubuf[b * 4 * UPL + k * UPL + o] = 0.f;
     }
-    struct wblk_t { float4 wg[3][2], wrs[3]; };
-    auto wload = [&](int blk, wblk_t &p) {
-      const float *wg = a.w_gate4 + (size_t)blk * 3 * 4 * 32 * 4, *wrs = a.w_rs4 + (size_t)blk * 4 * 48 * 4;
-      const unsigned og = (unsigned)(kk * 32 + j) * 4, ors = (unsigned)(kk * 48 + j) * 4;
-#pragma unroll
-      for (int kb = 0; kb < 3; ++kb)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) p.wg[kb][n] = *(const float4 *)(wg + og + kb * 4 * 32 * 4 + n * 16 * 4);
-#pragma unroll
-      for (int n = 0; n < 3; ++n) p.wrs[n] = *(const float4 *)(wrs + ors + n * 16 * 4);
-    };
-    wblk_t pw[2];
-    wload(0, pw[0]);
+    wv_wblk pw[2];
+    wv_wload(a, 0, j, kk, pw[0]);
     const int tl = wave * WV_MPW * 16 + j;  // this lane's time column in the wave's first tile (tile mi: + 16 mi)
     __syncthreads();               // table + zero rows
-    // a block's seven small vectors (this lane's channel group): read from the table one block AHEAD, behind the barrier, so
-    // that no LDS round trip sits in front of the u write, the accumulators' initial values or the res | skip products
-    // (the BatchNorm pair and the gate biases, which a block needs at once; the res | skip biases are requested at the top of their
-    // own block and used ~1,500 cycles later: prefetching all seven costs 56 registers and spills)
-    struct vblk_t { float4 bns, bnt, bsig, btanh; };
-    auto vload = [&](int blk, vblk_t &v) {
-      const float4 *vt = (const float4 *)(vtab + blk * 112) + kk;  // vector q: vt[4 q]
-      v.bns = vt[0]; v.bnt = vt[4]; v.bsig = vt[8]; v.btanh = vt[12];
-    };
-    vblk_t pv[2];
-    vload(0, pv[0]);
-    auto f4 = [](const float4 &v) { return (f32x4){v.x, v.y, v.z, v.w}; };
-    // Written over a wave's WV_MPW tiles (round 5: launches of more than 256 windows run FOUR waves x three tiles, two
-    // workgroups per CU - the form that gave the split-bf16 loop 14 % at scale; up to 256 windows - one per CU - twelve waves x
-    // one tile): the tiles' MFMAs and gate evaluations are independent instructions back to back, the per-tile arithmetic is
-    // the same source in both forms, so a posterior does not depend on the launch size.
-    auto run_block_t = [&](int blk, const wblk_t &P, wblk_t &Pnext, const vblk_t &V, vblk_t &Vnext) {
-      float *u = ubuf + (blk & 1) * 4 * UPL + kk * UPL + WV_PAD * 4;          // row 0 of this lane's channel-group plane
-      const int d = (int)((a.dil4[blk >> 4] >> (4 * (blk & 15))) & 15);
-      const float4 *vt = (const float4 *)(vtab + blk * 112) + kk;
-      const float4 bres = vt[16], bsk0 = vt[20], bsk1 = vt[24];
-      f32x4 uv[WV_MPW], as[WV_MPW], at[WV_MPW];
-#pragma unroll
-      for (int mi = 0; mi < WV_MPW; ++mi) {
-        uv[mi] = (f32x4){x[mi][0] * V.bns.x + V.bnt.x, x[mi][1] * V.bns.y + V.bnt.y, x[mi][2] * V.bns.z + V.bnt.z,
-                         x[mi][3] * V.bns.w + V.bnt.w};
-        *(f32x4 *)(u + (tl + 16 * mi) * 4) = uv[mi];
-      }
-      const int nb = blk + 1 < a.NB ? blk + 1 : blk;
-      wload(nb, Pnext);  // unconditional (clamped) prefetch, as the row-major loop
-#pragma unroll
-      for (int mi = 0; mi < WV_MPW; ++mi) {
-        as[mi] = f4(V.bsig);
-        at[mi] = f4(V.btanh);
-        MFMA4(as[mi], P.wg[2][0], uv[mi]);             // tap 2 = this row: runs while the other waves arrive
-        MFMA4(at[mi], P.wg[2][1], uv[mi]);
-      }
-      __syncthreads();  // u complete (all rows, all waves)
-      f32x4 t0v[WV_MPW], t1v[WV_MPW];
-#pragma unroll
-      for (int mi = 0; mi < WV_MPW; ++mi) {            // rows < 0 hit the zero pad (d <= 8)
-        t0v[mi] = *(const f32x4 *)(u + (tl + 16 * mi - 2 * d) * 4);
-        t1v[mi] = *(const f32x4 *)(u + (tl + 16 * mi - d) * 4);
-      }
-      vload(nb, Vnext);
-      __builtin_amdgcn_sched_barrier(0);  // the tap reads (and the table reads behind them) are in flight before the first wait
-      const int has_res = (a.has_res_mask >> blk) & 1;
-#pragma unroll
-      for (int mi = 0; mi < WV_MPW; ++mi) {
-        MFMA4(as[mi], P.wg[0][0], t0v[mi]);
-        MFMA4(at[mi], P.wg[0][1], t0v[mi]);
-        MFMA4(as[mi], P.wg[1][0], t1v[mi]);
-        MFMA4(at[mi], P.wg[1][1], t1v[mi]);
-      }
-#pragma unroll
-      for (int mi = 0; mi < WV_MPW; ++mi) {
-        const f32x4 gv = {fast_tanh_w(at[mi][0]) * fast_sigmoid_w(as[mi][0]), fast_tanh_w(at[mi][1]) * fast_sigmoid_w(as[mi][1]),
-                          fast_tanh_w(at[mi][2]) * fast_sigmoid_w(as[mi][2]), fast_tanh_w(at[mi][3]) * fast_sigmoid_w(as[mi][3])};
-        f32x4 ar = f4(bres), s0 = f4(bsk0), s1 = f4(bsk1);
-        // (hand-interleaving the k-steps of the accumulators - dependent MFMAs issue after 40 cycles, independent ones after 32 - was
-        //  1 % SLOWER: with three waves per SIMD the other waves fill those 8 cycles, and the compiler's own order keeps fewer values live)
-        if (has_res) { MFMA4(ar, P.wrs[0], gv); }
-        MFMA4(s0, P.wrs[1], gv);
-        MFMA4(s1, P.wrs[2], gv);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (has_res) x[mi][r] = relu1(ar[r]) + x[mi][r];
-          skip[mi][0][r] = skip[mi][0][r] + relu1(s0[r]);
-          skip[mi][1][r] = skip[mi][1][r] + relu1(s1[r]);
-        }
-      }
-    };
+    wv_vblk pv[2];
+    wv_vload(vtab, 0, kk, pv[0]);
     for (int blk = 0; blk < a.NB; blk += 2) {
-      run_block_t(blk, pw[0], pw[1], pv[0], pv[1]);
-      if (blk + 1 < a.NB) run_block_t(blk + 1, pw[1], pw[0], pv[1], pv[0]);
+      wv_block_t<WV_MPW, UPL, false>(a, blk, ubuf, vtab, j, kk, tl, x, skip, pw[0], pw[1], pv[0], pv[1]);
+      if (blk + 1 < a.NB) wv_block_t<WV_MPW, UPL, false>(a, blk + 1, ubuf, vtab, j, kk, tl, x, skip, pw[1], pw[0], pv[1], pv[0]);
     }
     __syncthreads();
   } else if (!SPLIT_BF16) {
@@ -868,57 +951,17 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
       }
     }
   }
-  float4 w1[2][2], w2[2];
-#pragma unroll
-  for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-    for (int n = 0; n < 2; ++n) w1[kb][n] = *(const float4 *)(a.d_w1_4 + ((size_t)(kb * 4 + kk) * 32 + n * 16 + j) * 4);
-    w2[kb] = *(const float4 *)(a.d_w2_4 + ((size_t)(kb * 4 + kk) * 16 + j) * 4);
-  }
-  const float b1a = a.d_b1[j], b1b = a.d_b1[16 + j], b2 = a.d_b2[j];
+  wv_head_w hw;
+  wv_head_load(a, j, kk, hw);
   float best = -INFINITY;
 #pragma unroll
   for (int mi = 0; mi < WV_MPW; ++mi) {
     const int t0 = (wave * WV_MPW + mi) * 16;
-    float *ht = hbuf + t0 * WV_S;  // [16][32] tile, wave-private
-    if (TRANSPOSED) {
-      *(float4 *)(ht + j * WV_S + kk * 4) = make_float4(fmaxf(skip[mi][0][0], 0.f), fmaxf(skip[mi][0][1], 0.f),
-                                                        fmaxf(skip[mi][0][2], 0.f), fmaxf(skip[mi][0][3], 0.f));
-      *(float4 *)(ht + j * WV_S + 16 + kk * 4) = make_float4(fmaxf(skip[mi][1][0], 0.f), fmaxf(skip[mi][1][1], 0.f),
-                                                             fmaxf(skip[mi][1][2], 0.f), fmaxf(skip[mi][1][3], 0.f));
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        ht[(kk * 4 + r) * WV_S + j] = fmaxf(skip[mi][0][r], 0.f);
-        ht[(kk * 4 + r) * WV_S + 16 + j] = fmaxf(skip[mi][1][r], 0.f);
-      }
-    }
-    wsync();
-    f32x4 h0 = {0.f, 0.f, 0.f, 0.f}, h1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      const float4 av = *(const float4 *)(ht + j * WV_S + kb * 16 + kk * 4);
-      MFMA4(h0, av, w1[kb][0]);
-      MFMA4(h1, av, w1[kb][1]);
-    }
-    wsync();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      ht[(kk * 4 + r) * WV_S + j] = fmaxf(h0[r] + b1a, 0.f);
-      ht[(kk * 4 + r) * WV_S + 16 + j] = fmaxf(h1[r] + b1b, 0.f);
-    }
-    wsync();
-    f32x4 y = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      const float4 av = *(const float4 *)(ht + j * WV_S + kb * 16 + kk * 4);
-      MFMA4(y, av, w2[kb]);
-    }
-    wsync();
+    const f32x4 y = wv_head_tile<TRANSPOSED>(skip[mi], hbuf + t0 * WV_S, hw, j, kk);  // [16][32] tile, wave-private
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int t = t0 + kk * 4 + r;
-      if (t < T) best = fmaxf(best, y[r] + b2);
+      if (t < T) best = fmaxf(best, y[r] + hw.b2);
     }
   }
   // GlobalMaxPooling1D over time: reduce over kk (lanes j, j+16, j+32, j+48), then over waves
@@ -930,19 +973,262 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
     float v = red[0][tid];
 #pragma unroll
     for (int q = 1; q < WV_NW; ++q) v = fmaxf(v, red[q][tid]);
-    float mx = (tid < a.NOUT) ? v : -INFINITY;
-    for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    float e = (tid < a.NOUT) ? expf(v - mx) : 0.f;
-    float sum = e;
-    for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o);
+    const float p = wv_softmax16(v, tid, a.NOUT);
     if (a.tag.slots) {  // a streaming tick: the posterior as ONE 8-byte {value, tick number} store the host polls (common.h)
       if (tid == a.tag.pidx) {
-        const unsigned long long word = (unsigned long long)__float_as_uint(e / sum) | ((unsigned long long)a.tag.seq << 32);
+        const unsigned long long word = (unsigned long long)__float_as_uint(p) | ((unsigned long long)a.tag.seq << 32);
         __hip_atomic_store(a.tag.slots + w, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     } else if (tid < a.NOUT) {
-      a.out[(size_t)w * a.NOUT + tid] = e / sum;
+      a.out[(size_t)w * a.NOUT + tid] = p;
     }
+  }
+}
+
+// ---- the sequence form (fp32): a mel sequence of ANY length, evaluated as the reference's Keras model evaluates it with
+//      timesteps=None - causal taps read zeros in front of row 0 and nothing else is padded - instead of as 182-row windows that
+//      each pad their own left edge.  One workgroup walks one SEGMENT (wv_seg: rows [row0, row0 + n) of one sequence) in chunks of
+//      NW x 16 rows through the block body of wavenet_kernel (wv_block_t: the same instructions, so row t carries the bits of
+//      position T - 1 of the window that ends at t).  What a window form cannot have is carried from chunk to chunk in LDS: per
+//      block the last WV_PAD = 16 rows of u (2 d <= 16), 1 KB x NB = 24 KB - they take the place of the causal zero rows, so no row
+//      is computed twice.  A long sequence is cut into segments that run in parallel; a segment that does not start at row 0 of its
+//      sequence starts RF - 1 rows early (RF = 1 + 2 sum d, the receptive field) from an all-zero history and discards those rows
+//      (`skip`): row t depends on rows t - RF + 1 .. t only, so what it keeps are the bits of the uncut evaluation.
+//      Outputs per kept row: the skip sum (enc) and the head's logits BEFORE the max over time; the pooled maxima and the
+//      softmax are wave_pool_*_kernel's (sequences) or the tail of this kernel (STREAM).
+//      STREAM (NW = 1): one workgroup = one stream's tick of 1..2 new rows.  The history comes from and returns to the stream's
+//      state in memory; the new logit rows go into the stream's ring of the last P rows, and each new row's posterior -
+//      softmax(max over the ring's rows up to it) - leaves as a tag or a row of `out` when the segment's emit bit is set.
+struct wave_seq_args {
+  const wv_seg *segs;
+  float *enc, *logits;          // [mel rows][32], [mel rows][NOUT]: a segment's kept rows, by mel row; either may be NULL
+  // STREAM
+  const int64_t *win_row;       // [nw] first new mel row (in `mel` = the bank's mirrored rings)
+  const int32_t *win_valid;     // [nw] new rows (1..2)
+  const int32_t *win_aux;       // [nw] stream | emit << 16
+  float *state;                 // [S][NB][4 kk][WV_PAD][4]
+  float *zring;                 // [S][P][16]
+  int32_t *zpos;                // [S][2]: the ring slot of the next row, rows held (<= P)
+  float *out;                   // [2 S][NOUT] (no tags)
+  int P;
+};
+
+template <int NW, bool STREAM>
+__global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(wave_args a, wave_seq_args q) {
+  constexpr int CH = NW * 16, THREADS = NW * 64, UPL = (CH + WV_PAD) * 4;
+  constexpr int U_F = 2 * 4 * UPL, H_F = CH * WV_S, IN_F = CH * WV_INLD, V_F = 32 * 7 * 16, HB = 4 * WV_PAD * 4;
+  static_assert(UPL % 64 == 0, "u planes must start on the same bank");
+  static_assert(IN_F <= U_F + H_F, "the staged input lies under the u buffers and the head tile");
+  static_assert(!STREAM || NW == 1, "a stream's tick is one tile");
+  // [ u[2][4][UPL] | head tile [CH][32] ] (the staged input [CH][48] under both) | vector table [32][7][16] | history [32][HB]
+  __shared__ __align__(16) float lds[U_F + H_F + V_F + 32 * HB];
+  float *ubuf = lds, *hbuf = lds + U_F, *vtab = hbuf + H_F, *hist = vtab + V_F, *in_lds = lds;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 15, kk = lane >> 4;
+  const int w = blockIdx.x;
+  int64_t row0;
+  int n, skipn, sid = 0, emit = 0;
+  if (STREAM) {
+    row0 = q.win_row[w];
+    n = q.win_valid[w];
+    n = n < CH ? n : CH;
+    skipn = 0;
+    const int aux = q.win_aux[w];
+    sid = aux & 0xffff;
+    emit = aux >> 16;
+  } else {
+    const wv_seg sg = q.segs[w];
+    row0 = sg.row0; n = sg.n; skipn = sg.skip;
+  }
+  for (int i = tid; i < a.NB * 7 * 16; i += THREADS) {  // all blocks' small vectors: [NB][7][16] = bn_s, bn_t, b_sig, b_tanh, b_res, b_skip0, b_skip1
+    const int b = i / 112, v = (i / 16) % 7, c = i & 15;
+    const float *p = v == 0 ? a.bn_s + b * WV_C + c : v == 1 ? a.bn_t + b * WV_C + c : v < 4 ? a.b_gate + b * 32 + (v - 2) * 16 + c
+                                                                                           : a.b_rs + b * 48 + (v - 4) * 16 + c;
+    vtab[i] = *p;
+  }
+  {
+    const f32x4 *sp = (const f32x4 *)(q.state + (size_t)sid * a.NB * HB);
+    for (int i = tid; i < a.NB * HB / 4; i += THREADS) ((f32x4 *)hist)[i] = STREAM ? sp[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  const bool vec_in = (a.n_mel & 3) == 0 && ((((uintptr_t)a.mel) & 15) == 0);
+  f32x4 y = {0.f, 0.f, 0.f, 0.f};
+  float b2 = 0.f;
+  for (int c0 = 0; c0 < n; c0 += CH) {
+    const int valid = n - c0 < CH ? n - c0 : CH;
+    // (the thread's coordinates as values the compiler cannot move out of the chunk loop: the per-lane addresses of the staging,
+    //  the input conv and - formed again behind the block loop - the head would otherwise be held, i.e. spilled, across the block
+    //  loop, which runs at the register limit of three waves per SIMD)
+    int tc = tid;
+    asm volatile("" : "+v"(tc));
+    const int wc = tc >> 6, jc = tc & 15, kc = (tc >> 4) & 3;
+    const int tl = wc * 16 + jc;  // this lane's time column in the chunk
+    // the input conv's operands: requested now, used behind the staging (per chunk: they are not held across the block loop)
+    float4 bw[3];
+#pragma unroll
+    for (int kb = 0; kb < 3; ++kb) bw[kb] = *(const float4 *)(a.w_in4 + (unsigned)((kb * 4 + kc) * 16 + jc) * 4);
+    __syncthreads();  // the chunk before is through with the head tile (and, the first time, the tables are in place)
+    // ---- stage the chunk: in_lds[t][0..47], zero outside [0, valid) x [0, n_mel)
+    const float *src = a.mel + (row0 + c0) * a.n_mel;
+    if (vec_in) {
+      for (int i = tc; i < CH * (WV_INLD / 4); i += THREADS) {
+        const int t = i / (WV_INLD / 4), c = (i - t * (WV_INLD / 4)) * 4;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (t < valid && c < a.n_mel) v = *(const f32x4 *)(src + (size_t)t * a.n_mel + c);
+        *(f32x4 *)(in_lds + t * WV_INLD + c) = v;
+      }
+    } else {
+      for (int i = tc; i < CH * WV_INLD; i += THREADS) {
+        const int t = i / WV_INLD, c = i - t * WV_INLD;
+        in_lds[i] = (t < valid && c < a.n_mel) ? src[(size_t)t * a.n_mel + c] : 0.f;
+      }
+    }
+    __syncthreads();
+    // ---- input 1x1 conv + ReLU -> x, transposed (lane = time column, registers = channels 4 kk + r): wavenet_kernel's
+    f32x4 x[1], skip[1][2];
+    {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kb = 0; kb < 3; ++kb) {
+        const float4 av = *(const float4 *)(in_lds + tl * WV_INLD + kb * 16 + kc * 4);
+        MFMA4(acc, bw[kb], av);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) x[0][r] = fmaxf(acc[r] + a.b_in[(unsigned)(kc * 4 + r)], 0.f);
+      skip[0][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      skip[0][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    wv_wblk pw[2];
+    wv_wload(a, 0, jc, kc, pw[0]);
+    __syncthreads();  // in_lds is dead from here on
+    wv_vblk pv[2];
+    wv_vload(vtab, 0, kc, pv[0]);
+    for (int blk = 0; blk < a.NB; blk += 2) {
+      wv_block_t<1, UPL, true>(a, blk, ubuf, vtab, jc, kc, tl, x, skip, pw[0], pw[1], pv[0], pv[1], hist, valid, wc == 0);
+      if (blk + 1 < a.NB) wv_block_t<1, UPL, true>(a, blk + 1, ubuf, vtab, jc, kc, tl, x, skip, pw[1], pw[0], pv[1], pv[0], hist, valid, wc == 0);
+    }
+    // ---- a kept row's skip sum and logits
+    int td = tid;
+    asm volatile("" : "+v"(td));
+    const int wd = td >> 6, jd = td & 15, kd = (td >> 4) & 3;
+    const int ts = c0 + wd * 16 + jd;  // this lane's time column, in rows of the segment
+    if (q.enc && ts >= skipn && ts < n) {
+      float *e = q.enc + (size_t)(row0 + ts) * WV_S;
+      *(float4 *)(e + kd * 4) = make_float4(skip[0][0][0], skip[0][0][1], skip[0][0][2], skip[0][0][3]);
+      *(float4 *)(e + 16 + kd * 4) = make_float4(skip[0][1][0], skip[0][1][1], skip[0][1][2], skip[0][1][3]);
+    }
+    wv_head_w hw;
+    wv_head_load(a, jd, kd, hw);
+    y = wv_head_tile<true>(skip[0], hbuf + wd * 16 * WV_S, hw, jd, kd);  // (wave-private tile: no barrier)
+    b2 = hw.b2;
+    if (!STREAM && q.logits && jd < a.NOUT) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int t = c0 + wd * 16 + kd * 4 + r;
+        if (t >= skipn && t < n) q.logits[(size_t)(row0 + t) * a.NOUT + jd] = y[r] + b2;
+      }
+    }
+  }
+  if (STREAM) {
+    // ---- the tick's n <= 2 new logit rows (rows 0, 1 of the tile: registers 0, 1 of lanes 0..15), the pooled maximum over the
+    //      ring's rows up to each, the softmax, the ring
+    float *zl = hbuf;  // [2][16]
+    if (kk == 0) {
+      zl[j] = y[0] + b2;
+      zl[16 + j] = y[1] + b2;
+    }
+    wsync();
+    const int P = q.P, pos = q.zpos[2 * sid], held = q.zpos[2 * sid + 1];
+    float *ring = q.zring + (size_t)sid * P * 16;
+    for (int k = 0; k < n; ++k) {
+      const int cnt = held + k + 1 < P ? held + k + 1 : P;  // rows of the pool that ends at new row k
+      float m = -INFINITY;
+      for (int i = kk; i < cnt; i += 4) {                   // i rows back from it: a new row, or the ring's
+        const float v = i <= k ? zl[(k - i) * 16 + j] : ring[(size_t)((pos + k - i + P) % P) * 16 + j];
+        m = fmaxf(m, v);
+      }
+      m = fmaxf(m, __shfl_xor(m, 16));
+      m = fmaxf(m, __shfl_xor(m, 32));
+      if (lane < 16) {
+        const float p = wv_softmax16(m, lane, a.NOUT);
+        if (emit) {
+          if (a.tag.slots) {
+            if (lane == a.tag.pidx) {
+              const unsigned long long word = (unsigned long long)__float_as_uint(p) | ((unsigned long long)a.tag.seq << 32);
+              __hip_atomic_store(a.tag.slots + 2 * sid + k, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+          } else if (lane < a.NOUT) {
+            q.out[(size_t)(2 * sid + k) * a.NOUT + lane] = p;
+          }
+        }
+      }
+    }
+    wsync();  // the ring is read before it is written: new row 1 takes the slot of the oldest row of new row 0's pool
+    if (lane < 16)
+      for (int k = 0; k < n; ++k) ring[(size_t)((pos + k) % P) * 16 + lane] = zl[k * 16 + lane];
+    if (lane == 0) {
+      q.zpos[2 * sid] = (pos + n) % P;
+      q.zpos[2 * sid + 1] = held + n < P ? held + n : P;
+    }
+    __syncthreads();
+    f32x4 *sp = (f32x4 *)(q.state + (size_t)sid * a.NB * HB);
+    for (int i = tid; i < a.NB * HB / 4; i += THREADS) sp[i] = ((const f32x4 *)hist)[i];
+  }
+}
+
+// ---- pooled maxima of the sequence form.  m[t] = max of z over the last P rows up to t (of t's own sequence), P = 0: from row 0.
+//      By doubling: M_0 = z, M_{i+1}[t] = max(M_i[t], M_i[t - 2^i]) is the maximum over the last 2^(i+1) rows; with 2^k <= P < 2^(k+1)
+//      m[t] = max(M_k[t], M_k[t - (P - 2^k)]).  A maximum is exact in any order, so neither the cuts of the main kernel nor the
+//      order here can show in the result.  k + 1 passes over [rows][NOUT] floats: for 2.4 h of audio, 8 x 7 MB.
+__device__ __forceinline__ int64_t wv_row_in_seq(const int64_t *offs, int n_seq, int64_t row) {
+  int lo = 0, hi = n_seq;  // the sequence s with offs[s] <= row < offs[s + 1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (offs[mid] <= row) lo = mid; else hi = mid;
+  }
+  return row - offs[lo];
+}
+
+__global__ __launch_bounds__(256) void wave_pool_step_kernel(const float *in, float *out, int64_t rows, int NOUT, const int64_t *offs, int n_seq,
+                                                             int64_t step) {
+  // (rows = [offs[0], offs[n_seq]): rows of the buffers in front of or behind the sequences are neither read nor written)
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * NOUT) return;
+  i += offs[0] * NOUT;
+  const int64_t row = i / NOUT;
+  float v = in[i];
+  if (wv_row_in_seq(offs, n_seq, row) >= step) v = fmaxf(v, in[i - step * NOUT]);
+  out[i] = v;
+}
+
+// sixteen lanes per row (lane c = column c): the last step of the pooled maximum and wavenet_kernel's softmax
+__global__ __launch_bounds__(256) void wave_pool_final_kernel(const float *M, int64_t rows, int NOUT, const int64_t *offs, int n_seq, int64_t back,
+                                                              float *pf) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = offs[0] + (g >> 4), rc = row < rows ? row : rows - 1;
+  const int c = (int)(g & 15);
+  float v = c < NOUT ? M[rc * NOUT + c] : -INFINITY;
+  if (back > 0 && c < NOUT && wv_row_in_seq(offs, n_seq, rc) >= back) v = fmaxf(v, M[(rc - back) * NOUT + c]);
+  const float p = wv_softmax16(v, c, NOUT);
+  if (row < rows && c < NOUT) pf[row * NOUT + c] = p;
+}
+
+// one workgroup per sequence: softmax(max over all its rows) - what model(X) returns with timesteps=None
+__global__ __launch_bounds__(256) void wave_seq_post_kernel(const float *z, const int64_t *offs, int NOUT, float *post) {
+  __shared__ float red[16][16];
+  const int s = blockIdx.x, tid = threadIdx.x, c = tid & 15, g = tid >> 4;
+  const int64_t r0 = offs[s], r1 = offs[s + 1];
+  if (r1 <= r0) return;  // an empty sequence has no posterior: its row of `post` is left as it is
+  float m = -INFINITY;
+  if (c < NOUT)
+    for (int64_t r = r0 + g; r < r1; r += 16) m = fmaxf(m, z[r * NOUT + c]);
+  red[g][c] = m;
+  __syncthreads();
+  if (tid < 16) {
+    float v = red[0][tid];
+#pragma unroll
+    for (int k = 1; k < 16; ++k) v = fmaxf(v, red[k][tid]);
+    const float p = wv_softmax16(v, tid, NOUT);
+    if (tid < NOUT) post[(size_t)s * NOUT + tid] = p;
   }
 }
 
@@ -992,6 +1278,78 @@ int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
     hipLaunchKernelGGL((wavenet_kernel<false, false, 4, true>), dim3(nw), dim3(4 * 64), 0, ctx->stream, a);
   else
     hipLaunchKernelGGL((wavenet_kernel<false, false, 12, true>), dim3(nw), dim3(12 * 64), 0, ctx->stream, a);
+  WW_HIP(ctx, hipGetLastError());
+  return WW_OK;
+}
+
+// The sequence form's reach: the fp32 transposed block loop only
+static int wave_seq_check(ww_ctx *ctx, const ww_model *m, const char *what) {
+  if (m->kind != WW_KIND_WAVENET) return ww_fail(ctx, WW_EINVAL, "%s: the sequence form exists for Wavenet models only (a CRNN's bidirectional GRUs have no causal reading)", what);
+  if (m->precision != WW_PRECISION_FP32) return ww_fail(ctx, WW_EINVAL, "%s: the sequence form is fp32 only; this model is in split-bf16 mode", what);
+  return WW_OK;
+}
+
+int ww_wave_receptive_field(const ww_model *m) {
+  int rf = 1;
+  for (int d : m->wave.dil) rf += 2 * d;
+  return rf;
+}
+
+int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const wv_seg *d_segs, int n_segs, float *d_enc, float *d_logits) {
+  if (n_segs <= 0) return WW_OK;
+  if (int rc = wave_seq_check(ctx, m, "ww_wave_sequence")) return rc;
+  wave_args a = {};
+  a.mel = d_mel;
+  if (int rc = wave_model_args(ctx, m->wave, a)) return rc;
+  wave_seq_args q = {};
+  q.segs = d_segs; q.enc = d_enc; q.logits = d_logits;
+  ww_launch_scope scope(ctx, "wavenet_seq_kernel");
+  hipLaunchKernelGGL((wavenet_seq_kernel<12, false>), dim3(n_segs), dim3(12 * 64), 0, ctx->stream, a, q);
+  WW_HIP(ctx, hipGetLastError());
+  return WW_OK;
+}
+
+// pool_rows: 0 = from row 0 of each sequence.  max_len: the longest sequence.  d_a / d_b: [rows][NOUT] floats of scratch each.
+int ww_k_wave_pool(ww_ctx *ctx, const float *d_z, int64_t rows, int64_t row_end, int NOUT, const int64_t *d_offs, int n_seq, int64_t pool_rows,
+                   int64_t max_len, float *d_a, float *d_b, float *d_pf, float *d_post) {
+  if (rows <= 0 || n_seq <= 0) return WW_OK;  // rows: offs[n_seq] - offs[0], the rows that belong to a sequence
+  if (d_post) {
+    ww_launch_scope scope(ctx, "wave_seq_post_kernel");
+    hipLaunchKernelGGL(wave_seq_post_kernel, dim3(n_seq), dim3(256), 0, ctx->stream, d_z, d_offs, NOUT, d_post);
+    WW_HIP(ctx, hipGetLastError());
+  }
+  if (!d_pf) return WW_OK;
+  const int64_t P = pool_rows == 0 || pool_rows > max_len ? max_len : pool_rows;  // (a pool longer than every sequence is "from row 0")
+  ww_launch_scope scope(ctx, "wave_pool_kernels");
+  const float *cur = d_z;
+  int64_t span = 1;  // cur[t] = max over the last `span` rows
+  const unsigned g1 = (unsigned)((rows * NOUT + 255) / 256);
+  while (span * 2 <= P) {
+    float *nxt = cur == d_a ? d_b : d_a;
+    hipLaunchKernelGGL(wave_pool_step_kernel, dim3(g1), dim3(256), 0, ctx->stream, cur, nxt, rows, NOUT, d_offs, n_seq, span);
+    cur = nxt;
+    span *= 2;
+  }
+  hipLaunchKernelGGL(wave_pool_final_kernel, dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, ctx->stream, cur, row_end, NOUT, d_offs, n_seq, P - span, d_pf);
+  WW_HIP(ctx, hipGetLastError());
+  return WW_OK;
+}
+
+// A causal bank's tick (streams.hip): workgroup w advances stream win_aux[w] & 0xffff by its win_valid[w] new mel rows
+int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, const int64_t *d_win_row, const int32_t *d_win_valid,
+                          const int32_t *d_win_aux, int nw, float *d_state, float *d_zring, int32_t *d_zpos, float *d_out,
+                          const ww_tick_tag *tag) {
+  if (nw <= 0) return WW_OK;
+  if (int rc = wave_seq_check(ctx, m, "causal streaming tick")) return rc;
+  wave_args a = {};
+  a.mel = d_hist;
+  if (int rc = wave_model_args(ctx, m->wave, a)) return rc;
+  if (tag) a.tag = *tag;
+  wave_seq_args q = {};
+  q.win_row = d_win_row; q.win_valid = d_win_valid; q.win_aux = d_win_aux;
+  q.state = d_state; q.zring = d_zring; q.zpos = d_zpos; q.out = d_out; q.P = m->wave.T;
+  ww_launch_scope scope(ctx, "wavenet_seq_kernel<stream>");
+  hipLaunchKernelGGL((wavenet_seq_kernel<1, true>), dim3(nw), dim3(64), 0, ctx->stream, a, q);
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
 }

@@ -22,8 +22,8 @@ LIB_PATH = os.environ.get("WWHIP_LIB") or os.path.join(_PKG, "libwwhip.so")
 WW_OK, WW_EINVAL, WW_EBLOB, WW_EHIP, WW_ENOMEM, WW_ESTATE, WW_ENODEVICE, WW_EINTERNAL = 0, -1, -2, -3, -4, -5, -6, -7
 KIND_CRNN, KIND_WAVENET = 1, 2
 PRECISION_FP32, PRECISION_BF16X3 = 0, 1
-OPT_CRNN_SPLIT_AT, OPT_CRNN_SLIDE_MIN, OPT_CRNN_TAIL_MFMA, OPT_WAVENET_ROWMAJOR = 1, 2, 3, 4
-STREAM_FULL_RECOMPUTE, STREAM_TWO_LAUNCH, STREAM_SYNC_WAIT = 1, 2, 4
+OPT_CRNN_SPLIT_AT, OPT_CRNN_SLIDE_MIN, OPT_CRNN_TAIL_MFMA, OPT_WAVENET_ROWMAJOR, OPT_WAVE_SEQ_SEGMENT = 1, 2, 3, 4, 5
+STREAM_FULL_RECOMPUTE, STREAM_TWO_LAUNCH, STREAM_SYNC_WAIT, STREAM_CAUSAL = 1, 2, 4, 8
 ABI = 4  # include/wwhip.h: WW_ABI - the signatures this binding was written against
 
 
@@ -83,6 +83,8 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_slide_forward": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _P(_i64)]),
     "ww_forward_windows_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
     "ww_forward_segments_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
+    "ww_wave_sequence_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ww_wave_sequence": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ww_clips_forward_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _P(FrontendParams), _vp]),
     "ww_stream_create": (C.c_int, [_vp, _vp, _i32, _P(FrontendParams), C.c_uint32, _P(_vp)]),
     "ww_stream_destroy": (C.c_int, [_vp]),

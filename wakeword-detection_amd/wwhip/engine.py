@@ -46,7 +46,7 @@ class Engine:
         self.enc_shape = (info.enc_rows, info.enc_width)
         self.model_dir = model_dir
         _lib.register("models", self)
-        self._options = {"crnn_split_at": 1024, "crnn_slide_min": 64, "crnn_tail_mfma": 1, "wavenet_rowmajor": 0}  # the library's defaults
+        self._options = {"crnn_split_at": 1024, "crnn_slide_min": 64, "crnn_tail_mfma": 1, "wavenet_rowmajor": 0, "wave_seq_segment": 0}  # the library's defaults
         self.precision = "fp32"
         if precision != "fp32":
             self.set_precision(precision)
@@ -66,9 +66,11 @@ class Engine:
         sliding windows take the once-per-sequence form from this many windows on (0 = never); ``"crnn_tail_mfma"`` - the recurrences
         of those two forms for sixteen windows per workgroup on the matrix pipe: 1 (default) from 9,216 windows per launch on,
         2 always, 0 never (one window per workgroup on the vector ALU), any other value is refused; ``"wavenet_rowmajor"`` - 1: the fp32 Wavenet's row-major block loop of rounds 1-2 instead of the
-        transposed one."""
+        transposed one; ``"wave_seq_segment"`` - rows per independently computed segment of :meth:`sequence_forward` (0 = the
+        library's choice; the same bits for every value)."""
         keys = {"crnn_split_at": _lib.OPT_CRNN_SPLIT_AT, "crnn_slide_min": _lib.OPT_CRNN_SLIDE_MIN,
-                "crnn_tail_mfma": _lib.OPT_CRNN_TAIL_MFMA, "wavenet_rowmajor": _lib.OPT_WAVENET_ROWMAJOR}
+                "crnn_tail_mfma": _lib.OPT_CRNN_TAIL_MFMA, "wavenet_rowmajor": _lib.OPT_WAVENET_ROWMAJOR,
+                "wave_seq_segment": _lib.OPT_WAVE_SEQ_SEGMENT}
         if key not in keys:
             raise ValueError(f"option must be one of {sorted(keys)}")
         self._chk(self._lib.ww_model_set_option(self._model, keys[key], int(value)))
@@ -215,6 +217,60 @@ class Engine:
         assert got.value == nw
         return out
 
+    SEQUENCE_OUTPUTS = ("enc", "logits", "post_frames", "post")
+
+    def sequence_forward(self, mels, pool: Optional[int] = None, want: Sequence[str] = ("post",)) -> dict:
+        """The fp32 Wavenet on whole mel sequences of any length (``ww_wave_sequence``): the reference's model with
+        ``timesteps=None`` - causal taps read zeros in front of row 0, nothing else is padded.  This is NOT the TFLite window form
+        of :meth:`forward` / :meth:`slide_forward`, whose windows each pad their own left edge; for a sequence of exactly
+        ``window`` rows the two coincide, bit for bit.
+
+        ``mels``: a list of ``[L_i, n_mel]`` arrays (or one such array).  ``want``: any of ``"enc"`` (``[L_i, 32]`` skip sums),
+        ``"logits"`` (``[L_i, n_out]``, the head before the max over time), ``"post_frames"`` (``[L_i, n_out]``: softmax of the
+        maximum over the last ``pool`` rows; ``pool=None``: the model's window, ``0``: from row 0) and ``"post"`` (``[n_out]``:
+        softmax of the maximum over the whole sequence).  Returns ``{name: list of arrays, one per sequence}``; an empty
+        sequence's ``post`` is NaN."""
+        if isinstance(mels, np.ndarray) and mels.ndim == 2:
+            mels = [mels]
+        want = tuple(want)
+        bad = [k for k in want if k not in self.SEQUENCE_OUTPUTS]
+        if bad:
+            raise ValueError(f"want must be drawn from {self.SEQUENCE_OUTPUTS}, got {bad}")
+        seqs = [np.ascontiguousarray(m, dtype=np.float32).reshape(-1, self.n_mel) if np.size(m) == 0 else np.ascontiguousarray(m, dtype=np.float32)
+                for m in mels]
+        for m in seqs:
+            if m.ndim != 2 or m.shape[1] != self.n_mel:
+                raise ValueError(f"every sequence must be [rows, {self.n_mel}]")
+        offs = np.zeros(len(seqs) + 1, np.int64)
+        np.cumsum([m.shape[0] for m in seqs], out=offs[1:])
+        total = int(offs[-1])
+        mel = np.concatenate(seqs) if seqs else np.zeros((0, self.n_mel), np.float32)
+        pool = self.window if pool is None else int(pool)
+        bufs = {"enc": np.empty((total, 32), np.float32) if "enc" in want else None,
+                "logits": np.empty((total, self.n_out), np.float32) if "logits" in want else None,
+                "post_frames": np.empty((total, self.n_out), np.float32) if "post_frames" in want else None,
+                "post": np.full((len(seqs), self.n_out), np.nan, np.float32) if "post" in want else None}
+        self._chk(self._lib.ww_wave_sequence(self.ctx.handle, self._model, _lib.ptr(mel), total, _lib.ptr(offs), len(seqs), pool,
+                                             _lib.ptr(bufs["enc"]), _lib.ptr(bufs["logits"]), _lib.ptr(bufs["post_frames"]),
+                                             _lib.ptr(bufs["post"])))
+        out = {}
+        for k in want:
+            out[k] = [bufs[k][i] for i in range(len(seqs))] if k == "post" else [bufs[k][offs[i]:offs[i + 1]] for i in range(len(seqs))]
+        return out
+
+    def wave_sequence_dev(self, d_mel_ptr: int, total_rows: int, row_offs: np.ndarray, pool: Optional[int] = None, d_enc_ptr: int = 0,
+                          d_logits_ptr: int = 0, d_post_frames_ptr: int = 0, d_post_ptr: int = 0) -> None:
+        """:meth:`sequence_forward` on device buffers (``ww_wave_sequence_dev``): sequence ``s`` is rows ``[row_offs[s],
+        row_offs[s + 1])`` of the mel buffer (``row_offs``: a host array); the per-row outputs are indexed by mel row, ``post`` by
+        sequence; a pointer of 0 leaves that output out.  Enqueued on the context's stream, not waited for."""
+        offs = np.ascontiguousarray(row_offs, dtype=np.int64)
+        if offs.ndim != 1 or offs.size < 1:
+            raise ValueError("row_offs must be a 1-D array of n_seq + 1 offsets")
+        vp = lambda p: C.c_void_p(p) if p else None
+        self._chk(self._lib.ww_wave_sequence_dev(self.ctx.handle, self._model, vp(d_mel_ptr), int(total_rows), _lib.ptr(offs), int(offs.size - 1),
+                                                 self.window if pool is None else int(pool), vp(d_enc_ptr), vp(d_logits_ptr),
+                                                 vp(d_post_frames_ptr), vp(d_post_ptr)))
+
     # ------------------------------------------------------------------ evaluator
     def far_frr(self, pos: np.ndarray, neg: np.ndarray, thresholds: np.ndarray, num_wakewords: float, hours: float,
                 window: int = 30, want_smoothed: bool = False):
@@ -284,18 +340,22 @@ class StreamBank:
     """S device-resident streams advanced 20 ms per :meth:`step` (``ww_stream_*``)."""
 
     def __init__(self, engine: Engine, n_streams: int, fp: Optional[_lib.FrontendParams] = None,
-                 full_recompute: bool = False, two_launch: bool = False, sync_wait: bool = False) -> None:
+                 full_recompute: bool = False, two_launch: bool = False, sync_wait: bool = False, causal: bool = False) -> None:
         """``full_recompute``: every streaming CRNN window recomputed from its mel rows (``WW_STREAM_FULL_RECOMPUTE``)
         instead of the incremental kernel.  ``two_launch``: the incremental CRNN's tick as a front-end kernel + a model kernel
         (``WW_STREAM_TWO_LAUNCH``; default: ONE launch per tick).  ``sync_wait``: wait for a tick with ``hipStreamSynchronize``
-        instead of polling its posteriors in page-locked memory (``WW_STREAM_SYNC_WAIT``).  Same bits in every form."""
+        instead of polling its posteriors in page-locked memory (``WW_STREAM_SYNC_WAIT``).  Same bits in every form.
+        ``causal`` (fp32 Wavenet only, ``WW_STREAM_CAUSAL``): another model reading, not another form - the bank advances
+        :meth:`Engine.sequence_forward` row by row from cached activations; a posterior is ``post_frames`` of the stream's rows
+        since its last reset (every sampled row advances the state; rows that arrive while ``is_speech`` is set emit)."""
         self.engine = engine
         self.S = int(n_streams)
         self._lib = _lib.load()
         fp = fp or frontend_params()
         h = C.c_void_p()
         flags = ((_lib.STREAM_FULL_RECOMPUTE if full_recompute else 0) | (_lib.STREAM_TWO_LAUNCH if two_launch else 0)
-                 | (_lib.STREAM_SYNC_WAIT if sync_wait else 0))
+                 | (_lib.STREAM_SYNC_WAIT if sync_wait else 0) | (_lib.STREAM_CAUSAL if causal else 0))
+        self.causal = bool(causal)
         _lib.raise_for(self._lib.ww_stream_create(engine.ctx.handle, engine.handle, self.S, C.byref(fp), flags, C.byref(h)),
                        engine.ctx.handle)
         self._h = h

@@ -25,7 +25,9 @@ class WakewordTrigger:
     def __init__(self, pre_emphasis: float = 0.0, sample_rate: int = 16000, fft_window_type: str = "hann",
                  fft_hop_length: int = 10, model_dir: str = "", model_type: str = "",
                  posterior_threshold: float = 0.5, on_wake: Optional[Callable[[], None]] = None, device: int = 0,
-                 superframe_len: int = 0, **kwargs) -> None:
+                 superframe_len: int = 0, causal: bool = False, **kwargs) -> None:
+        # causal (fp32 Wavenet only): the posteriors come from the sequence form advanced row by row (StreamBank(causal=True))
+        # instead of from a window recomputed per row; the trigger logic below is the same
         self.pre_emphasis = pre_emphasis
         self.hop_length = int(fft_hop_length * sample_rate / 1000)
         if fft_window_type != "hann":
@@ -42,7 +44,7 @@ class WakewordTrigger:
         self.mel_length = self._engine.window
         self.mel_width = self._engine.n_mel
         self.encode_length, self.encode_width = self._engine.enc_shape
-        self._bank = StreamBank(self._engine, 1, frontend_params(32767.0, True, pre_emphasis, self.hop_length, True))
+        self._bank = StreamBank(self._engine, 1, frontend_params(32767.0, True, pre_emphasis, self.hop_length, True), causal=causal)
         self._posterior_threshold = posterior_threshold
         self._posterior_max = 0.0
         self._is_speech = False
@@ -101,14 +103,15 @@ class WakewordBank:
     ``SpeechContext`` objects (their flags are gathered and written back one by one: the slow form)."""
 
     def __init__(self, n_streams: int, model_dir: str = "", posterior_threshold: float = 0.5, pre_emphasis: float = 0.0,
-                 device: int = 0, on_wake: Optional[Callable[[np.ndarray], None]] = None, bank=None) -> None:
+                 device: int = 0, on_wake: Optional[Callable[[np.ndarray], None]] = None, bank=None, causal: bool = False) -> None:
+        # causal: the bank this stage builds is StreamBank(causal=True) (fp32 Wavenet only); a bank= of the caller's is taken as it is
         from . import _lib
         self.S = int(n_streams)
         if bank is None:
             if not model_dir:
                 raise ValueError("WakewordBank needs model_dir (or bank=: a StreamBank built on an Engine of the caller's)")
             self._engine = engine_for(model_dir, device)
-            bank = StreamBank(self._engine, self.S, frontend_params(32767.0, True, pre_emphasis, 160, True))
+            bank = StreamBank(self._engine, self.S, frontend_params(32767.0, True, pre_emphasis, 160, True), causal=causal)
         self._bank = bank  # (anything with StreamBank's step_trigger / reset / close: the host-only tests pass a stub)
         self.threshold = float(posterior_threshold)
         self._on_wake = on_wake  # called with the ids of the streams that woke up this tick
