@@ -318,6 +318,27 @@ int ww_stream_reset(ww_streams *st, const int32_t *ids, int32_t n);
  * (T * n_mel floats, row-major) after the context's stream has been synchronised.  Touches no state of the bank.  WW_EINVAL for
  * a stream id out of range. */
 int ww_stream_window(ww_streams *st, int32_t stream, float *out);
+/* ww_stream_feed - a WW_STREAM_CAUSAL bank advanced by ANY subset of its streams and ANY number of samples for each (packets of
+ * 10 .. 100 ms, a backlog of minutes): stream ids[i] receives samples [sample_offs[i], sample_offs[i + 1]) of pcm, any count >= 0.
+ * Framing is the tick's rule for k samples: a stream holds fill <= 511 pending samples; tot = fill + k,
+ * rows = tot >= 512 ? (tot - 512) / 160 + 1 : 0, fill' = tot - 160 rows.  Every new mel row advances the causal state and yields
+ * one posterior - post_frames[t][posterior column] of ww_wave_sequence with pool_rows = window over the stream's rows since its
+ * last reset, the tick's definition.  However a stream's samples are cut into packets, calls and ww_stream_step ticks, the mel
+ * rows, the posteriors and the state left behind are the same bits; ww_stream_step / _reset / _window work on a fed bank as before.
+ *   row_offs [n + 1]            written: stream ids[i]'s new rows are [row_offs[i], row_offs[i + 1]) of post and mel
+ *   post [row_offs[n]]          one posterior (the posterior column, as ww_stream_step's) per new mel row, stream by stream
+ *   mel  [row_offs[n]][n_mel]   the new mel rows themselves; may be NULL
+ *   cap_rows                    rows `post` (and `mel`) have room for
+ * There is no is_speech: a stream that must stand still is not named.  WW_EINVAL - before any state changes - for a bank without
+ * WW_STREAM_CAUSAL, NULL arguments, n < 0, an id out of range or named twice, descending sample_offs, cap_rows smaller than the
+ * rows of the call; WW_ESTATE for a bank marked broken; WW_ENOMEM when the call's scratch (samples, rows, logits; it grows on
+ * demand) cannot be had.  n = 0, empty packets and packets that leave a stream below 512 samples are no-ops for the model (the
+ * samples are kept).  A failure after the host's mirrors advanced marks the bank broken, as a tick's does.  The call ends in
+ * hipStreamSynchronize on the context's stream (a ragged result has no tag slots); it works on a borrowed stream.
+ * ww_stream_feed_rows writes the row_offs the same call would produce and touches no state: what to size post / mel by. */
+int ww_stream_feed_rows(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs);
+int ww_stream_feed(ww_streams *st, const int32_t *ids, int32_t n, const int16_t *pcm, const int64_t *sample_offs, int64_t cap_rows,
+                   int64_t *row_offs, float *post, float *mel);
 /* ---- the pipeline's host stages for S streams in lock step (BASELINE config 5 at the plugin surface) --------------------------
  * The reference drives three stage objects per stream and 20 ms frame (spokestack/pipeline.py:25-28, stage list of demo.py:29-36),
  * each a few comparisons on the shared SpeechContext.  For S streams each stage is ONE pass over plain arrays the caller owns

@@ -9,7 +9,13 @@
   distance    on the clips of tools/eval_testset.py: how far post_frames lies from the window form's posterior at the same end
               row, in logit units (the two readings differ by their left context; this is a description, not a check).
 
-usage: wave_sequence.py throughput [--model Wavenet] [--reps 5] [--once] | latency [--streams 128] [--ticks 4000] |
+  feed        StreamBank.feed measured: catch-up (S streams x N seconds in ONE feed against the tick loop over the same audio on a
+              twin bank, alternated), lock step (a feed of 320 samples per stream against step, polled and sync_wait, p50 / p99,
+              alternated in blocks) and one stream's hour in one packet against Engine.logmel + sequence_forward, with the library's
+              per-kernel times.  --part catchup | lockstep | hour | once (one untimed 1 h feed, for a kernel trace) | all.
+
+usage: wave_sequence.py feed [--part all] [--streams 128] [--seconds 10] [--reps 5] [--ticks 4000] |
+       wave_sequence.py throughput [--model Wavenet] [--reps 5] [--once] | latency [--streams 128] [--ticks 4000] |
        distance [--clips 256]"""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -103,6 +109,85 @@ def latency(args):
     print(json.dumps(out))
 
 
+def feed(args):
+    from wwhip.engine import StreamBank
+    eng = _engine(args.model)
+    rng = np.random.default_rng(0)
+    out = {"model": args.model}
+    noise = lambda *shape: np.clip(rng.normal(0, 2500, shape), -32768, 32767).astype(np.int16)
+
+    def clock(f):
+        a = time.perf_counter(); f(); return time.perf_counter() - a   # (step and feed both return after a synchronise / their posteriors)
+
+    if args.part in ("catchup", "all"):
+        for S, seconds in ((args.streams, args.seconds), (1024, 1)):
+            ticks = seconds * 50
+            pcm = noise(S, ticks * 320)
+            ids, speech = list(range(S)), np.ones(S, np.uint8)
+            fed, ticked = StreamBank(eng, S, causal=True), StreamBank(eng, S, causal=True)
+            packets = [pcm[s] for s in range(S)]
+
+            def tick_loop():
+                for t in range(ticks):
+                    ticked.step(pcm[:, t * 320:(t + 1) * 320], speech)
+            t_feed, t_tick = [], []
+            for r in range(args.reps + 1):   # alternated; the first pair is the warm-up (code objects, the call's scratch at its size)
+                a, b = clock(lambda: fed.feed(ids, packets)), clock(tick_loop)
+                if r:
+                    t_feed.append(a); t_tick.append(b)
+            eng.ctx.profile(True); fed.feed(ids, packets); prof = eng.ctx.profile_read(); eng.ctx.profile(False)
+            out[f"catchup_{S}x{seconds}s"] = {"feed_ms": _spread(np.array(t_feed) * 1e3), "tick_loop_ms": _spread(np.array(t_tick) * 1e3), "ticks": ticks,
+                                             "speedup_median": float(np.median(t_tick) / np.median(t_feed)),
+                                             "spreads_overlap": bool(max(t_feed) >= min(t_tick)),
+                                             "feed_kernels_ms_one_call": {k: round(v["total_ms"], 3) for k, v in prof.items()}}
+            fed.close(); ticked.close()
+    if args.part in ("lockstep", "all"):
+        S = args.streams
+        frames = noise(64, S, 320)
+        ids, speech = list(range(S)), np.ones(S, np.uint8)
+        banks = {"feed": StreamBank(eng, S, causal=True), "step_polled": StreamBank(eng, S, causal=True), "step_sync_wait": StreamBank(eng, S, causal=True, sync_wait=True)}
+        call = {k: ((lambda f, b=b: b.feed(ids, list(f))) if k == "feed" else (lambda f, b=b: b.step(f, speech))) for k, b in banks.items()}
+        lat = {k: [] for k in banks}
+        for k in banks:
+            for t in range(300):
+                call[k](frames[t % 64])
+        block = 500
+        for t0 in range(0, args.ticks, block):
+            for k in banks:
+                for t in range(t0, min(t0 + block, args.ticks)):
+                    f = frames[t % 64]
+                    a = time.perf_counter(); call[k](f); lat[k].append(time.perf_counter() - a)
+        ls = {"streams": S, "calls": args.ticks}
+        for k, b in banks.items():
+            v = np.array(lat[k]) * 1e6
+            ls[k] = {"p50_us": float(np.percentile(v, 50)), "p99_us": float(np.percentile(v, 99)), "mean_us": float(v.mean()),
+                     "p50_us_by_quarter": [float(np.percentile(h, 50)) for h in np.array_split(v, 4)]}
+            b.close()
+        out["lockstep"] = ls
+    if args.part in ("hour", "once", "all"):
+        pcm = noise(3600 * 16000)
+        bank = StreamBank(eng, 1, causal=True)
+        if args.part == "once":
+            bank.feed([0], [pcm]); bank.close()
+            print(json.dumps({"once": True, "samples": len(pcm)}))
+            return
+        two = lambda: eng.sequence_forward(eng.logmel([pcm]), pool=eng.window, want=("post_frames",))
+        one = lambda: (bank.reset(), bank.feed([0], [pcm]))
+        t_one, t_two = [], []
+        for r in range(args.reps + 1):
+            a, b = clock(one), clock(two)
+            if r:
+                t_one.append(a); t_two.append(b)
+        bank.reset()
+        eng.ctx.profile(True); p, _ = bank.feed([0], [pcm]); prof = eng.ctx.profile_read(); eng.ctx.profile(False)
+        eng.ctx.profile(True); two(); prof2 = eng.ctx.profile_read(); eng.ctx.profile(False)
+        out["hour"] = {"rows": int(len(p[0])), "feed_ms": _spread(np.array(t_one) * 1e3), "logmel_plus_sequence_ms": _spread(np.array(t_two) * 1e3),
+                       "feed_kernels_ms": {k: round(v["total_ms"], 3) for k, v in prof.items()},
+                       "logmel_plus_sequence_kernels_ms": {k: round(v["total_ms"], 3) for k, v in prof2.items()}}
+        bank.close()
+    print(json.dumps(out))
+
+
 def distance(args):
     from wwhip.evaluate import synth_testset
     eng = _engine(args.model)
@@ -124,7 +209,7 @@ def distance(args):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["throughput", "latency", "distance"])
+    ap.add_argument("what", choices=["throughput", "latency", "distance", "feed"])
     ap.add_argument("--model", default="Wavenet")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--wake", type=int, default=2529)
@@ -132,5 +217,7 @@ if __name__ == "__main__":
     ap.add_argument("--streams", type=int, default=128)
     ap.add_argument("--ticks", type=int, default=4000)
     ap.add_argument("--clips", type=int, default=256)
+    ap.add_argument("--seconds", type=int, default=10)
+    ap.add_argument("--part", default="all", choices=["all", "catchup", "lockstep", "hour", "once"])
     a = ap.parse_args()
-    {"throughput": throughput, "latency": latency, "distance": distance}[a.what](a)
+    {"throughput": throughput, "latency": latency, "distance": distance, "feed": feed}[a.what](a)

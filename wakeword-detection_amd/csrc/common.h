@@ -308,6 +308,26 @@ int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const
 int ww_k_wave_pool(ww_ctx *ctx, const float *d_z, int64_t rows, int64_t row_end, int n_out, const int64_t *d_offs, int n_seq, int64_t pool_rows,
                    int64_t max_len, float *d_a, float *d_b, float *d_pf, float *d_post);
 #define WW_WAVE_STATE_BLOCK 256  // floats of carried state per block and stream: [4 channel groups][16 rows][4]
+// A causal bank's feed (streams.hip: ww_stream_feed): the sequence form over the rows a call brought, stream by stream.  A segment
+// is rows [row0, row0 + n) of the call's row buffer, all of one stream; bit 0 of flags: its history comes from the stream's state
+// (the stream's first segment; the others start RF - 1 rows early from zeros and drop `skip` rows), bit 1: its history goes back
+// there (the stream's last segment).
+struct wv_feed_seg {
+  int64_t row0;
+  int32_t n, skip, sid, flags;
+};
+// the pooled maxima of a stream that brought more rows than one tile: rows [k0, k0 + 256) of its n new rows, which start at row0
+struct wv_feed_pool {
+  int64_t row0;
+  int32_t n, sid, k0, pad;
+};
+#define WW_FEED_TILE_ROWS 16   // up to here a stream's new rows are one tile of the one-wave form, tail included
+#define WW_FEED_POOL_ROWS 256  // rows per workgroup of wave_feed_pool_kernel
+// segs[0, n_small): one-wave form (posteriors, ring and state inside the kernel); segs[n_small, n_segs): twelve-wave form, logits to
+// d_z, then pool[n_pool] -> d_post and ring[n_ring] (one entry per such stream) -> the logit rings
+int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv_feed_seg *d_segs, int n_small, int n_segs,
+                   const wv_feed_pool *d_pool, int n_pool, const wv_feed_pool *d_ring, int n_ring, float *d_z, float *d_state,
+                   float *d_zring, int32_t *d_zpos, int pidx, float *d_post);
 int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, const int64_t *d_win_row, const int32_t *d_win_valid,
                           const int32_t *d_win_aux, int nw, float *d_state, float *d_zring, int32_t *d_zpos, float *d_out,
                           const ww_tick_tag *tag);

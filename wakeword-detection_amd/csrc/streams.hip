@@ -21,13 +21,17 @@
 //   every tick (round 1's ping-pong shift).  The one spare slot is what lets BOTH windows of a two-frame tick be evaluated
 //   after both rows are in place: the window that ends at row k leaves out exactly the slot of row k + 1.
 //   then the regular CRNN / Wavenet kernels run on the compacted list of new windows.
+//   stream_feed_frontend_kernel  a causal bank fed any number of samples per stream (ww_stream_feed, further down): one workgroup
+//                           per 16 new frames of a stream, the same conversion and the same per-frame functions as above.
 #include "common.h"
 #include "fft_device.h"
 
+#include <algorithm>
 #include <sched.h>
 #include <time.h>
 
 #define ST_RING WW_ST_RING  // 511 + 320 rounded up
+#define WV_FEED_HIST_ROWS 16  // rows of BatchNorm output a block carries (wavenet.hip: WV_PAD)
 #define ST_WL_BYTES (((WW_MEL_TAPS * 64 * 4 + 2047) / 2048) * 2048)  // the mel weights in LDS, padded to whole rounds of 128 x 16 bytes
 
 struct ww_streams {
@@ -224,6 +228,122 @@ __global__ __launch_bounds__(128) void stream_frontend_kernel(stream_fe_args a) 
   // ---- keep the ring tail
   const int keep = fill + WW_CHUNK - n_frames * a.hop;
   for (int i = tid; i < keep; i += 128) ring[i] = x[n_frames * a.hop + i];
+}
+
+// ---- a causal bank's feed (ww_stream_feed): the front end of any number of new samples per stream ---------------------------------
+// One workgroup (4 waves) per group of up to FEED_GROUP new frames of one stream.  Frame f of a call covers samples
+// [160 f, 160 f + 512) of [the stream's pending samples | the packet]; the group stages what its frames cover in LDS - the pending
+// samples as they are, the packet's through the conversion of stream_frontend_kernel (same operations on the same values) - and
+// each wave runs the tick's frame_fft_mag + mel_band on its frames: a fed row is the tick's row bit for bit.
+// The stream's state (pending samples, carry) is written by the stream's FIRST group (the only one when the packet completes no
+// frame): pending samples are fewer than 512, so only frames 0..3 - the first group's - reach into them, and the carry belongs to
+// the packet's first sample, which frame 0 covers.  The one reader being the one writer, the groups of a stream need no order.
+#define FEED_GROUP 16
+#define FEED_WAVES 4
+#define FEED_X (512 + (FEED_GROUP - 1) * 160)
+struct feed_str {       // a stream of the call
+  int64_t s_off;        // its packet's first sample in the call's sample buffer
+  int64_t k;            // samples in the packet
+  int64_t r_off;        // its first new row in the call's row buffer
+  int32_t sid, fill, rows, pos;
+};
+struct feed_grp {
+  int32_t i, f0, nf, pad;  // stream of the call, first frame, frames (0: the stream's state only)
+};
+struct feed_fe_args {
+  const int16_t *pcm;
+  const feed_str *str;
+  const feed_grp *grp;
+  float *rows;          // [rows of the call][F]
+  float *ring, *hist, *prev;
+  int T, F, HR;
+  float divisor;
+  int clip;
+  float preemph;
+  const int *start;
+  const float *wpad, *bias;
+  int n_mel;
+  float floor_v, log_off, scale;
+  const double *hann, *tw256, *tw512;
+};
+
+template <typename R>
+__global__ __launch_bounds__(FEED_WAVES * 64) void stream_feed_frontend_kernel(feed_fe_args a) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const feed_grp g = a.grp[blockIdx.x];
+  const feed_str d = a.str[g.i];
+  const int s = d.sid, fill = d.fill;
+  const bool first = g.f0 == 0;
+
+  size_t off = 0;
+  cplx<R> *fbuf = (cplx<R> *)(smem + off); off += FEED_WAVES * FFT_LD * sizeof(cplx<R>);
+  float *mag = (float *)(smem + off); off += FEED_WAVES * 260 * sizeof(float);
+  float *wl = (float *)(smem + off); off += WW_MEL_TAPS * 64 * 4;
+  float *x = (float *)(smem + off); off += FEED_X * sizeof(float);
+  float *pend = (float *)(smem + off);  // [512] the stream's new pending samples (first group)
+
+  for (int i = tid; i < WW_MEL_TAPS * 64 / 4; i += FEED_WAVES * 64) ((float4 *)wl)[i] = ((const float4 *)a.wpad)[i];
+  const int mel_st = lane < a.n_mel ? a.start[lane] : 0;
+  const float mel_bias = lane < a.n_mel ? a.bias[lane] : 0.0f;
+  float *ring = a.ring + (size_t)s * ST_RING;
+  const int16_t *pk = a.pcm + d.s_off;
+  const float carry = first ? a.prev[s] : 0.0f;  // (only the packet's first sample needs it, and only the first group covers that)
+  fft_consts<R> fc;
+  fft_load_consts<R>(fc, lane, a.hann, a.tw256, a.tw512);
+  // sample v of [pending | packet]: stream_frontend_kernel's conversion loop, x[fill + i] = ...
+  auto sample = [&](int64_t v) -> float {
+    if (v < fill) return ring[v];
+    const int64_t i = v - fill;
+    float sv = __fdiv_rn((float)pk[i], a.divisor);
+    if (a.clip) sv = fminf(fmaxf(sv, -1.0f), 1.0f);
+    float p;
+    if (i == 0) {
+      p = carry;
+    } else {
+      p = __fdiv_rn((float)pk[i - 1], a.divisor);
+      if (a.clip) p = fminf(fmaxf(p, -1.0f), 1.0f);
+    }
+    return (a.preemph != 0.0f) ? ww_preemph_rn(sv, a.preemph, p) : sv;
+  };
+  const int64_t base = (int64_t)g.f0 * 160;
+  const int len = g.nf > 0 ? (g.nf - 1) * 160 + 512 : 0;
+  for (int i = tid; i < len; i += FEED_WAVES * 64) x[i] = sample(base + i);
+  const int64_t tot = (int64_t)fill + d.k;
+  const int keep = (int)(tot - (int64_t)d.rows * 160);  // < 512
+  if (first)
+    for (int i = tid; i < keep; i += FEED_WAVES * 64) pend[i] = sample((int64_t)d.rows * 160 + i);
+  __syncthreads();  // x and pend complete; the ring and the carry have been read
+  if (first) {
+    for (int i = tid; i < keep; i += FEED_WAVES * 64) ring[i] = pend[i];
+    if (tid == 0 && d.k > 0) {
+      float v = __fdiv_rn((float)pk[d.k - 1], a.divisor);
+      if (a.clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
+      a.prev[s] = v;  // the un-emphasised last sample; an empty packet leaves the carry
+    }
+  }
+  // ---- the group's frames, wave k frames k, k + 4, ...: to the call's row buffer, the stream's last T + 1 rows also into its
+  //      mirrored ring (row r of the call at slot (pos + r) % (T + 1), as the ticks would have left them)
+  const int slots = a.T + 1;
+  const int ring_from = d.rows > slots ? d.rows - slots : 0;
+  for (int fl = wave; fl < g.nf; fl += FEED_WAVES) {
+    const float *src = x + fl * 160;
+    auto x2 = [&](int n) -> float2 { return make_float2(src[2 * n], src[2 * n + 1]); };
+    float *mg = mag + wave * 260;
+    frame_fft_mag<R>(x2, fc, fbuf + wave * FFT_LD, mg, lane);
+    const float mv = mel_band(mg, wl, mel_st, mel_bias, a.floor_v, a.log_off, a.scale, lane);
+    const int r = g.f0 + fl;
+    if (lane < a.n_mel) {
+      a.rows[(size_t)(d.r_off + r) * a.F + lane] = mv;
+      if (r >= ring_from) {
+        const int p = (int)(((int64_t)d.pos + r) % slots);
+        float *h = a.hist + ((size_t)s * a.HR + p) * a.F + lane;
+        h[0] = mv;
+        h[(size_t)slots * a.F] = mv;
+      }
+    }
+    wave_sync();  // the wave is through with its magnitudes before the next frame's transform writes them
+  }
 }
 
 // a causal bank's reset: the next row is row 0 of a new sequence (zero history, empty ring; the ring's rows need no clearing)
@@ -654,6 +774,179 @@ int ww_stream_step(ww_streams *st, const int16_t *frames, const uint8_t *is_spee
   if (st->broken) return ww_fail(st->ctx, WW_ESTATE, "this stream bank failed in an earlier tick: destroy it and create a new one");
   bool mutated = false;
   const int rc = stream_step_impl(st, frames, is_speech, post, n_post, &mutated);
+  if (rc != WW_OK && mutated) st->broken = true;
+  return rc;
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+// ---- ww_stream_feed: a causal bank advanced by any subset of its streams and any number of samples for each --------------------
+// The framing is the tick's rule for k samples instead of 320: tot = fill + k, rows = tot >= 512 ? (tot - 512) / 160 + 1 : 0,
+// fill' = tot - 160 rows.  Everything a refusal can depend on is looked at here, before any state moves.
+static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs, const char *what) {
+  ww_ctx *ctx = st->ctx;
+  if (!st->causal) return ww_fail(ctx, WW_EINVAL, "%s: only a bank created with WW_STREAM_CAUSAL can be fed (a window bank recomputes a window per row)", what);
+  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
+  if (n < 0) return ww_fail(ctx, WW_EINVAL, "%s: negative stream count", what);
+  if (!sample_offs || !row_offs || (n > 0 && !ids)) return ww_fail(ctx, WW_EINVAL, "%s: NULL argument", what);
+  std::vector<uint8_t> seen((size_t)st->S, 0);
+  int64_t rows = 0;
+  row_offs[0] = 0;
+  for (int i = 0; i < n; ++i) {
+    const int s = ids[i];
+    if (s < 0 || s >= st->S) return ww_fail(ctx, WW_EINVAL, "%s: stream id %d out of range", what, s);
+    if (seen[s]) return ww_fail(ctx, WW_EINVAL, "%s: stream %d is named twice", what, s);
+    seen[s] = 1;
+    const int64_t k = sample_offs[i + 1] - sample_offs[i];
+    if (k < 0) return ww_fail(ctx, WW_EINVAL, "%s: sample_offs descend at entry %d", what, i);
+    const int64_t tot = st->fill[s] + k;
+    const int64_t r = tot >= WW_FFT_WINDOW ? (tot - WW_FFT_WINDOW) / st->fp.hop + 1 : 0;
+    if (r > 0x3fffffff || rows + r > 0x3fffffff) return ww_fail(ctx, WW_EINVAL, "%s: more than 2^30 rows in one call", what);
+    rows += r;
+    row_offs[i + 1] = rows;
+  }
+  return WW_OK;
+}
+
+int ww_stream_feed_rows(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  return feed_check(st, ids, n, sample_offs, row_offs, "ww_stream_feed_rows");
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+// The cuts of a stream that brought more rows than one tile.  Segments of G rows as ww_wave_sequence cuts them,
+// with two differences: a segment that is not the stream's first needs its whole warm-up inside the call's row buffer (the rows in
+// front of the call's first row are gone), hence G >= RF - 1; and the stream's history is taken from its last segment, whose 16
+// rows per block are the uncut evaluation's only after RF - 1 + 16 rows from zeros: a last segment that keeps fewer than 16 rows
+// is merged into the one before it.
+static void feed_cut(std::vector<wv_feed_seg> &segs, int64_t r_off, int64_t rows, int sid, int64_t G, int rf) {
+  for (int64_t s0 = 0; s0 < rows; s0 += G) {
+    int64_t len = std::min<int64_t>(G, rows - s0);
+    if (rows - (s0 + len) < WV_FEED_HIST_ROWS && rows - (s0 + len) > 0) len = rows - s0;  // (the next one would be too short to carry the history)
+    const int64_t warm = s0 ? rf - 1 : 0;
+    segs.push_back({r_off + s0 - warm, (int32_t)(warm + len), (int32_t)warm, sid, s0 ? 0 : 1});
+    if (s0 + len >= rows) break;
+  }
+  segs.back().flags |= 2;
+}
+
+static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const int16_t *pcm, const int64_t *sample_offs, int64_t cap_rows,
+                            int64_t *row_offs, float *post, float *mel, bool *mutated) {
+  ww_ctx *ctx = st->ctx;
+  if (int rc = feed_check(st, ids, n, sample_offs, row_offs, "ww_stream_feed")) return rc;
+  const int64_t rows = row_offs[n], samples = n > 0 ? sample_offs[n] - sample_offs[0] : 0;
+  if (cap_rows < rows) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: the call produces %lld rows, the buffers hold %lld", (long long)rows, (long long)cap_rows);
+  if (samples > 0 && !pcm) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: NULL sample buffer");
+  if (rows > 0 && !post) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: NULL posterior buffer");
+  if (samples == 0) return WW_OK;  // nothing arrived: no stream moves
+  const ww_model *m = st->model;
+  const int T = st->T, F = st->F, NO = st->NO, R = T + 1, hop = st->fp.hop, rf = ww_wave_receptive_field(m);
+  if ((size_t)(WW_FEED_POOL_ROWS + T - 1) * 64 > 64 * 1024) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: windows of up to %d rows only", 1024 - WW_FEED_POOL_ROWS + 1);
+  WW_ON_DEVICE(ctx, dev_scope);
+  // ---- the plan: streams, front-end groups, model segments (one-wave form first), the twelve-wave form's tail
+  std::vector<feed_str> str((size_t)n);
+  std::vector<feed_grp> grp;
+  std::vector<wv_feed_seg> small, large;
+  std::vector<wv_feed_pool> pool, ringt;
+  int64_t large_rows = 0;
+  for (int i = 0; i < n; ++i) {
+    const int64_t r = row_offs[i + 1] - row_offs[i];
+    if (r > WW_FEED_TILE_ROWS || r > T) large_rows += r;
+  }
+  int64_t G = m->opt_wave_seq_segment;
+  if (G <= 0) {  // the library's choice, as ww_wave_sequence's: whole chunks, about two segments per CU once there is enough work
+    int64_t chunks = (large_rows + 2 * WW_NUM_CUS * 192 - 1) / (2 * WW_NUM_CUS * 192);
+    chunks = std::min<int64_t>(std::max<int64_t>(chunks, 10), 64);
+    G = chunks * 192 - (rf - 1);
+  }
+  G = std::min<int64_t>(std::max<int64_t>(G, std::max(rf - 1, 1)), 1 << 30);
+  for (int i = 0; i < n; ++i) {
+    const int s = ids[i];
+    const int64_t k = sample_offs[i + 1] - sample_offs[i], r = row_offs[i + 1] - row_offs[i];
+    str[i] = {sample_offs[i] - sample_offs[0], k, row_offs[i], s, st->fill[s], (int32_t)r, st->pos[s]};
+    if (k == 0) continue;  // an empty packet: the stream stands still
+    if (r == 0) grp.push_back({i, 0, 0, 0});
+    for (int64_t f0 = 0; f0 < r; f0 += FEED_GROUP) grp.push_back({i, (int32_t)f0, (int32_t)std::min<int64_t>(FEED_GROUP, r - f0), 0});
+    if (r == 0) continue;
+    if (r <= WW_FEED_TILE_ROWS && r <= T) {
+      small.push_back({row_offs[i], (int32_t)r, 0, s, 3});
+    } else {
+      feed_cut(large, row_offs[i], r, s, G, rf);
+      for (int64_t k0 = 0; k0 < r; k0 += WW_FEED_POOL_ROWS) pool.push_back({row_offs[i], (int32_t)r, s, (int32_t)k0, 0});
+      ringt.push_back({row_offs[i], (int32_t)r, s, 0, 0});
+    }
+  }
+  if (grp.size() > 0x7fffffffu || small.size() + large.size() > 0x7fffffffu) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: too much work for one call");
+  // ---- the call's scratch: [tables | samples | mel rows | logits | posteriors] in the context's workspace, the tables' host copy
+  //      in its page-locked arena
+  const size_t b_str = ww_bump::need(str.size(), sizeof(feed_str)), b_grp = ww_bump::need(grp.size(), sizeof(feed_grp)),
+               b_seg = ww_bump::need(small.size() + large.size(), sizeof(wv_feed_seg)), b_pool = ww_bump::need(pool.size(), sizeof(wv_feed_pool)),
+               b_ring = ww_bump::need(ringt.size(), sizeof(wv_feed_pool));
+  const size_t b_tab = b_str + b_grp + b_seg + b_pool + b_ring;
+  const size_t b_pcm = ww_bump::need((size_t)samples, 2), b_rows = ww_bump::need((size_t)rows * F, 4), b_z = ww_bump::need((size_t)rows * NO, 4),
+               b_post = ww_bump::need((size_t)rows, 4);
+  if (int rc = ww_ensure(ctx, ctx->pinned, b_tab + 1024, true)) return rc;
+  if (int rc = ww_ensure(ctx, ctx->dev, b_tab + b_pcm + b_rows + (large.empty() ? 0 : b_z) + b_post + 1024, false)) return rc;
+  ww_bump hb(ctx->pinned.ptr, ctx->pinned.cap), db(ctx->dev.ptr, ctx->dev.cap);
+  feed_str *h_str = hb.take<feed_str>(str.size()), *d_str = db.take<feed_str>(str.size());
+  feed_grp *h_grp = hb.take<feed_grp>(grp.size()), *d_grp = db.take<feed_grp>(grp.size());
+  wv_feed_seg *h_seg = hb.take<wv_feed_seg>(small.size() + large.size()), *d_seg = db.take<wv_feed_seg>(small.size() + large.size());
+  wv_feed_pool *h_pool = hb.take<wv_feed_pool>(pool.size()), *d_pool = db.take<wv_feed_pool>(pool.size());
+  wv_feed_pool *h_ringt = hb.take<wv_feed_pool>(ringt.size()), *d_ringt = db.take<wv_feed_pool>(ringt.size());
+  int16_t *d_pcm = db.take<int16_t>((size_t)samples);
+  float *d_rows = db.take<float>((size_t)rows * F);
+  float *d_z = large.empty() ? nullptr : db.take<float>((size_t)rows * NO);
+  float *d_post = db.take<float>((size_t)rows);
+  if (!str.empty()) memcpy(h_str, str.data(), str.size() * sizeof(feed_str));
+  if (!grp.empty()) memcpy(h_grp, grp.data(), grp.size() * sizeof(feed_grp));
+  if (!small.empty()) memcpy(h_seg, small.data(), small.size() * sizeof(wv_feed_seg));
+  if (!large.empty()) memcpy(h_seg + small.size(), large.data(), large.size() * sizeof(wv_feed_seg));
+  if (!pool.empty()) memcpy(h_pool, pool.data(), pool.size() * sizeof(wv_feed_pool));
+  if (!ringt.empty()) memcpy(h_ringt, ringt.data(), ringt.size() * sizeof(wv_feed_pool));
+  // ---- from here on the host's mirrors of the streams' state advance
+  *mutated = true;
+  for (int i = 0; i < n; ++i) {
+    const int s = ids[i];
+    const int64_t k = sample_offs[i + 1] - sample_offs[i], r = row_offs[i + 1] - row_offs[i];
+    st->fill[s] = (int)(st->fill[s] + k - r * hop);
+    st->pos[s] = (int)((st->pos[s] + r) % R);
+  }
+  WW_HIP(ctx, hipMemcpyAsync(d_str, h_str, b_tab, hipMemcpyHostToDevice, ctx->stream));  // (the tables are one block on both sides)
+  WW_HIP(ctx, hipMemcpyAsync(d_pcm, pcm + sample_offs[0], (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
+  const ww_filter_dev &f = m->filt;
+  feed_fe_args a = {};
+  a.pcm = d_pcm; a.str = d_str; a.grp = d_grp; a.rows = d_rows;
+  a.ring = st->ring; a.hist = st->hist; a.prev = st->prev;
+  a.T = T; a.F = F; a.HR = st->HR;
+  a.divisor = st->fp.pcm_divisor; a.clip = st->fp.clip; a.preemph = st->fp.pre_emphasis;
+  a.start = f.start; a.wpad = f.wpad; a.bias = f.bias;
+  a.n_mel = f.n_mel; a.floor_v = f.floor_v; a.log_off = f.log_off; a.scale = f.scale;
+  a.hann = f.hann; a.tw256 = f.tw256; a.tw512 = f.tw512;
+  if (!grp.empty()) {
+    ww_launch_scope scope(ctx, "stream_feed_frontend_kernel");
+    const size_t sm_rest = FEED_WAVES * 260 * 4 + WW_MEL_TAPS * 64 * 4 + FEED_X * 4 + 512 * 4;
+    if (st->fp.precise)
+      hipLaunchKernelGGL((stream_feed_frontend_kernel<double>), dim3((unsigned)grp.size()), dim3(FEED_WAVES * 64), FEED_WAVES * FFT_LD * 16 + sm_rest, ctx->stream, a);
+    else
+      hipLaunchKernelGGL((stream_feed_frontend_kernel<float>), dim3((unsigned)grp.size()), dim3(FEED_WAVES * 64), FEED_WAVES * FFT_LD * 8 + sm_rest, ctx->stream, a);
+    WW_HIP(ctx, hipGetLastError());
+  }
+  const int pidx = NO == 1 ? 0 : 1;  // posterior element, as a tick's
+  if (int rc = ww_k_wave_feed(ctx, m, d_rows, d_seg, (int)small.size(), (int)(small.size() + large.size()), d_pool, (int)pool.size(), d_ringt,
+                              (int)ringt.size(), d_z, st->wstate, st->zring, st->zpos, pidx, d_post))
+    return rc;
+  if (rows > 0) WW_HIP(ctx, hipMemcpyAsync(post, d_post, (size_t)rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (rows > 0 && mel) WW_HIP(ctx, hipMemcpyAsync(mel, d_rows, (size_t)rows * F * 4, hipMemcpyDeviceToHost, ctx->stream));
+  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return WW_OK;
+}
+
+int ww_stream_feed(ww_streams *st, const int32_t *ids, int32_t n, const int16_t *pcm, const int64_t *sample_offs, int64_t cap_rows,
+                   int64_t *row_offs, float *post, float *mel) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  bool mutated = false;
+  const int rc = stream_feed_impl(st, ids, n, pcm, sample_offs, cap_rows, row_offs, post, mel, &mutated);
   if (rc != WW_OK && mutated) st->broken = true;
   return rc;
   WW_GUARD_END(st ? st->ctx : nullptr)

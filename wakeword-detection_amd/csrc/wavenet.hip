@@ -999,6 +999,11 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
 //      STREAM (NW = 1): one workgroup = one stream's tick of 1..2 new rows.  The history comes from and returns to the stream's
 //      state in memory; the new logit rows go into the stream's ring of the last P rows, and each new row's posterior -
 //      softmax(max over the ring's rows up to it) - leaves as a tag or a row of `out` when the segment's emit bit is set.
+//      FEED (ww_stream_feed): a segment of the rows a call brought for one stream (wv_feed_seg).  `mel` is the call's row buffer.
+//      The stream's first segment takes its history from the stream's state, its last one returns it there.  NW = 1: a stream
+//      that brought up to 16 rows - the tick's tail for rows 0 .. n - 1 of the tile (register r of lane group kk is row 4 kk + r),
+//      every row's posterior to `post`.  NW = 12: more rows, logits to `logits`; wave_feed_pool_kernel / wave_feed_ring_kernel
+//      are its tail.
 struct wave_seq_args {
   const wv_seg *segs;
   float *enc, *logits;          // [mel rows][32], [mel rows][NOUT]: a segment's kept rows, by mel row; either may be NULL
@@ -1011,10 +1016,14 @@ struct wave_seq_args {
   int32_t *zpos;                // [S][2]: the ring slot of the next row, rows held (<= P)
   float *out;                   // [2 S][NOUT] (no tags)
   int P;
+  // FEED
+  const wv_feed_seg *fsegs;     // [workgroups]
+  float *post;                  // [rows of the call]: the posterior column of every new row (the one-wave form's tail)
 };
 
-template <int NW, bool STREAM>
+template <int NW, bool STREAM, bool FEED = false>
 __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(wave_args a, wave_seq_args q) {
+  static_assert(!(STREAM && FEED) && (!FEED || NW == 1 || NW == 12), "a feed is not a tick; its forms are one wave and twelve");
   constexpr int CH = NW * 16, THREADS = NW * 64, UPL = (CH + WV_PAD) * 4;
   constexpr int U_F = 2 * 4 * UPL, H_F = CH * WV_S, IN_F = CH * WV_INLD, V_F = 32 * 7 * 16, HB = 4 * WV_PAD * 4;
   static_assert(UPL % 64 == 0, "u planes must start on the same bank");
@@ -1027,8 +1036,11 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(
   const int j = lane & 15, kk = lane >> 4;
   const int w = blockIdx.x;
   int64_t row0;
-  int n, skipn, sid = 0, emit = 0;
-  if (STREAM) {
+  int n, skipn, sid = 0, emit = 0, fflags = 0;
+  if (FEED) {
+    const wv_feed_seg sg = q.fsegs[w];
+    row0 = sg.row0; n = sg.n; skipn = sg.skip; sid = sg.sid; fflags = sg.flags;
+  } else if (STREAM) {
     row0 = q.win_row[w];
     n = q.win_valid[w];
     n = n < CH ? n : CH;
@@ -1048,7 +1060,7 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(
   }
   {
     const f32x4 *sp = (const f32x4 *)(q.state + (size_t)sid * a.NB * HB);
-    for (int i = tid; i < a.NB * HB / 4; i += THREADS) ((f32x4 *)hist)[i] = STREAM ? sp[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int i = tid; i < a.NB * HB / 4; i += THREADS) ((f32x4 *)hist)[i] = (STREAM || (FEED && (fflags & 1))) ? sp[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
   }
   const bool vec_in = (a.n_mel & 3) == 0 && ((((uintptr_t)a.mel) & 15) == 0);
   f32x4 y = {0.f, 0.f, 0.f, 0.f};
@@ -1172,6 +1184,93 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(
     __syncthreads();
     f32x4 *sp = (f32x4 *)(q.state + (size_t)sid * a.NB * HB);
     for (int i = tid; i < a.NB * HB / 4; i += THREADS) sp[i] = ((const f32x4 *)hist)[i];
+  }
+  if (FEED) {
+    if (NW == 1) {
+      // ---- the tick's tail for the n <= 16 new logit rows of the tile: the pooled maximum over the ring's rows up to each, the
+      //      softmax, the ring.  Every row's posterior leaves.
+      float *zl = hbuf;  // [16][16]
+#pragma unroll
+      for (int r = 0; r < 4; ++r) zl[(kk * 4 + r) * 16 + j] = y[r] + b2;
+      wsync();
+      const int P = q.P, pos = q.zpos[2 * sid], held = q.zpos[2 * sid + 1];
+      float *ring = q.zring + (size_t)sid * P * 16;
+      for (int k = 0; k < n; ++k) {
+        const int cnt = held + k + 1 < P ? held + k + 1 : P;
+        float m = -INFINITY;
+        for (int i = kk; i < cnt; i += 4) {
+          const float v = i <= k ? zl[(k - i) * 16 + j] : ring[(size_t)((pos + k - i + P) % P) * 16 + j];
+          m = fmaxf(m, v);
+        }
+        m = fmaxf(m, __shfl_xor(m, 16));
+        m = fmaxf(m, __shfl_xor(m, 32));
+        if (lane < 16) {
+          const float p = wv_softmax16(m, lane, a.NOUT);
+          if (lane == a.tag.pidx) q.post[row0 + k] = p;
+        }
+      }
+      wsync();  // the ring is read before it is written (n <= 16 < P: a new row never takes the slot of another new row)
+      if (lane < 16)
+        for (int k = 0; k < n; ++k) ring[(size_t)((pos + k) % P) * 16 + lane] = zl[k * 16 + lane];
+      if (lane == 0) {
+        q.zpos[2 * sid] = (pos + n) % P;
+        q.zpos[2 * sid + 1] = held + n < P ? held + n : P;
+      }
+    }
+    if (fflags & 2) {
+      __syncthreads();
+      f32x4 *sp = (f32x4 *)(q.state + (size_t)sid * a.NB * HB);
+      for (int i = tid; i < a.NB * HB / 4; i += THREADS) sp[i] = ((const f32x4 *)hist)[i];
+    }
+  }
+}
+
+// ---- the tail of a feed's twelve-wave form.  The pool of new row k of a stream ends at k and covers the last P rows of
+//      [the ring's held rows | the new rows].  One workgroup per 256 new rows: the rows and the P - 1 in front of them in LDS
+//      (-inf where the stream has no row yet), sixteen lanes per row (lane c = column c), the maximum - exact in any order - and
+//      the tick's softmax.  The ring is only read here: wave_feed_ring_kernel writes it, behind this kernel.
+__global__ __launch_bounds__(256) void wave_feed_pool_kernel(const float *z, const wv_feed_pool *tab, int NOUT, int P, int pidx,
+                                                             const float *zring, const int32_t *zpos, float *post) {
+  extern __shared__ __align__(16) float pool_tile[];  // [WW_FEED_POOL_ROWS + P - 1][16]
+  const wv_feed_pool d = tab[blockIdx.x];
+  const int tid = threadIdx.x, c = tid & 15, g = tid >> 4;
+  const int pos = zpos[2 * d.sid], held = zpos[2 * d.sid + 1];
+  const float *ring = zring + (size_t)d.sid * P * 16;
+  const int here = d.n - d.k0 < WW_FEED_POOL_ROWS ? d.n - d.k0 : WW_FEED_POOL_ROWS;
+  for (int i = g; i < here + P - 1; i += 16) {
+    const int64_t v = (int64_t)d.k0 - (P - 1) + i;  // the row, counted from the stream's first new row
+    float x = -INFINITY;
+    if (c < NOUT) {
+      if (v >= 0) x = z[(d.row0 + v) * NOUT + c];
+      else if (v >= -held) x = ring[(size_t)((pos + (int)v + P) % P) * 16 + c];
+    }
+    pool_tile[i * 16 + c] = x;
+  }
+  __syncthreads();
+  for (int r = g; r < here; r += 16) {
+    float m = -INFINITY;
+    for (int i = 0; i < P; ++i) m = fmaxf(m, pool_tile[(r + i) * 16 + c]);
+    const float p = wv_softmax16(m, c, NOUT);
+    if (c == pidx) post[d.row0 + d.k0 + r] = p;
+  }
+}
+
+// one workgroup per stream of the twelve-wave form: its last min(n, P) new logit rows into the ring, the ring's position and count
+__global__ __launch_bounds__(256) void wave_feed_ring_kernel(const float *z, const wv_feed_pool *tab, int NOUT, int P, float *zring,
+                                                             int32_t *zpos) {
+  const wv_feed_pool d = tab[blockIdx.x];
+  const int tid = threadIdx.x;
+  const int pos = zpos[2 * d.sid], held = zpos[2 * d.sid + 1];
+  float *ring = zring + (size_t)d.sid * P * 16;
+  const int m = d.n < P ? d.n : P;
+  for (int i = tid; i < m * 16; i += 256) {
+    const int k = d.n - m + (i >> 4), c = i & 15;
+    ring[(size_t)((pos + k) % P) * 16 + c] = c < NOUT ? z[(d.row0 + k) * NOUT + c] : 0.f;
+  }
+  __syncthreads();  // (every thread has read the position)
+  if (tid == 0) {
+    zpos[2 * d.sid] = (pos + d.n) % P;
+    zpos[2 * d.sid + 1] = held + d.n < P ? held + d.n : P;
   }
 }
 
@@ -1351,6 +1450,44 @@ int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, c
   ww_launch_scope scope(ctx, "wavenet_seq_kernel<stream>");
   hipLaunchKernelGGL((wavenet_seq_kernel<1, true>), dim3(nw), dim3(64), 0, ctx->stream, a, q);
   WW_HIP(ctx, hipGetLastError());
+  return WW_OK;
+}
+
+// A causal bank's feed (streams.hip: ww_stream_feed).  The forms by the rows a stream brought: up to WW_FEED_TILE_ROWS the one-wave
+// form, above the twelve-wave form with its tail as two small kernels; a call may launch both.
+int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv_feed_seg *d_segs, int n_small, int n_segs,
+                   const wv_feed_pool *d_pool, int n_pool, const wv_feed_pool *d_ring, int n_ring, float *d_z, float *d_state,
+                   float *d_zring, int32_t *d_zpos, int pidx, float *d_post) {
+  if (n_segs <= 0) return WW_OK;
+  if (int rc = wave_seq_check(ctx, m, "ww_stream_feed")) return rc;
+  wave_args a = {};
+  a.mel = d_rows;
+  if (int rc = wave_model_args(ctx, m->wave, a)) return rc;
+  a.tag = {nullptr, 0, pidx};
+  wave_seq_args q = {};
+  q.state = d_state; q.zring = d_zring; q.zpos = d_zpos; q.P = m->wave.T; q.post = d_post;
+  if (n_small > 0) {
+    q.fsegs = d_segs;
+    ww_launch_scope scope(ctx, "wavenet_seq_kernel<feed,1>");
+    hipLaunchKernelGGL((wavenet_seq_kernel<1, false, true>), dim3(n_small), dim3(64), 0, ctx->stream, a, q);
+    WW_HIP(ctx, hipGetLastError());
+  }
+  if (n_segs > n_small) {
+    q.fsegs = d_segs + n_small;
+    q.logits = d_z;
+    {
+      ww_launch_scope scope(ctx, "wavenet_seq_kernel<feed,12>");
+      hipLaunchKernelGGL((wavenet_seq_kernel<12, false, true>), dim3(n_segs - n_small), dim3(12 * 64), 0, ctx->stream, a, q);
+      WW_HIP(ctx, hipGetLastError());
+    }
+    ww_launch_scope scope(ctx, "wave_feed_pool_kernels");
+    const size_t sm = (size_t)(WW_FEED_POOL_ROWS + q.P - 1) * 16 * sizeof(float);
+    if (sm > 64 * 1024) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: a window of %d rows is beyond the pool kernel's tile", q.P);
+    hipLaunchKernelGGL(wave_feed_pool_kernel, dim3(n_pool), dim3(256), sm, ctx->stream, (const float *)d_z, d_pool, a.NOUT, q.P, pidx,
+                       (const float *)d_zring, (const int32_t *)d_zpos, d_post);
+    hipLaunchKernelGGL(wave_feed_ring_kernel, dim3(n_ring), dim3(256), 0, ctx->stream, (const float *)d_z, d_ring, a.NOUT, q.P, d_zring, d_zpos);
+    WW_HIP(ctx, hipGetLastError());
+  }
   return WW_OK;
 }
 

@@ -429,6 +429,31 @@ class StreamBank:
         _lib.raise_for(self._lib.ww_stream_window(self._h, int(stream), _lib.ptr(out)), self.engine.ctx.handle)
         return out
 
+    def feed(self, ids: Sequence[int], packets: Sequence[np.ndarray], want_mel: bool = False):
+        """A causal bank advanced by any subset of its streams and any number of samples for each (``ww_stream_feed``):
+        stream ``ids[i]`` receives the int16 samples ``packets[i]``.  Returns ``(posts, mels)``: per listed stream the posteriors
+        of its new mel rows ``[rows]`` and, with ``want_mel``, the rows themselves ``[rows, n_mel]`` (``mels`` is ``None``
+        otherwise).  However the samples are cut into packets, calls and :meth:`step` ticks, the results are the same bits."""
+        a_ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        n = int(a_ids.size)
+        if len(packets) != n:
+            raise ValueError("one packet per listed stream")
+        pk = [np.ascontiguousarray(p, dtype=np.int16).ravel() for p in packets]
+        offs = np.zeros(n + 1, np.int64)
+        np.cumsum([p.size for p in pk], out=offs[1:])
+        pcm = np.concatenate(pk) if n and offs[n] else np.zeros(1, np.int16)
+        row_offs = np.zeros(n + 1, np.int64)
+        h = self.engine.ctx.handle
+        _lib.raise_for(self._lib.ww_stream_feed_rows(self._h, _lib.ptr(a_ids), n, _lib.ptr(offs), _lib.ptr(row_offs)), h)
+        rows = int(row_offs[n])
+        post = np.empty(max(rows, 1), np.float32)
+        mel = np.empty((max(rows, 1), self.engine.n_mel), np.float32) if want_mel else None
+        _lib.raise_for(self._lib.ww_stream_feed(self._h, _lib.ptr(a_ids), n, _lib.ptr(pcm), _lib.ptr(offs), rows, _lib.ptr(row_offs),
+                                                _lib.ptr(post), _lib.ptr(mel) if want_mel else None), h)
+        posts = [post[row_offs[i]:row_offs[i + 1]].copy() for i in range(n)]
+        mels = [mel[row_offs[i]:row_offs[i + 1]].copy() for i in range(n)] if want_mel else None
+        return posts, mels
+
     def close(self) -> None:
         if self._h and not _lib.is_shutdown():
             self._lib.ww_stream_destroy(self._h)
