@@ -5,7 +5,8 @@ mel rows, the posteriors and the state left behind are those of the tick loop; a
 ``Engine.sequence_forward`` over the rows it returned since the stream's reset; neither the cuts of a long packet
 (``wave_seq_segment``), nor a packet's neighbours in a call, nor the order of ``ids`` show.  AGAINST FLOAT64 with the bounds the
 tick's forms already hold (tests/test_gpu_frontend64.py, tests/test_gpu_wave_sequence.py).  And the refusals of the contract,
-each leaving the bank as a twin that never saw the refused call.
+each leaving the bank as a twin that never saw the refused call.  One test runs every streaming form (CRNN and Wavenet ticks
+in one and two launches, the causal tick, the feed) on samples that clip, with the clip off and with another divisor.
 
 Inputs: seeded synthetic PCM (noise + chirp), one silent stream; both Wavenet model directories.
 """
@@ -167,6 +168,75 @@ def test_any_split_gives_the_ticks_bits(engines, model, sync_wait, precise):
     finally:
         A.close()
         B.close()
+
+
+# ---------------------------------------------------------- 1b. clip off, another divisor, samples that clip: one conversion
+@pytest.mark.parametrize("divisor,clip", [(32768, False), (16384, True)], ids=["div32768-noclip", "div16384-clip"])
+def test_every_form_converts_the_samples_alike(engines, assets, divisor, clip):
+    """The int16 -> sample conversion (division, optional clip, pre-emphasis 0.97 against the carried sample) under parameters no
+    other streaming test uses: 3 streams x 12 ticks of noise with sigma 9,000 (about 7 % of the samples clip under divisor 16,384)
+    and -32768 / 32767 in the first and last sample of several ticks, where the carry is taken and used.  Through the default CRNN
+    bank, the CRNN bank with ``two_launch``, the default Wavenet bank, the causal bank by ``step`` and the causal bank by ``feed``
+    (7 + 633 + 3,200 samples): the streams' final mel windows are the same bits in every form, the fed rows are the causal tick's,
+    and stream 0's rows pass ``check_logmel`` against the float64 front end with TAU_REL (precise), as ``test_against_float64``."""
+    from wwhip.engine import Engine, StreamBank, frontend_params
+    S, ticks = 3, 12
+    rng = np.random.default_rng(71)
+    pcm = np.clip(np.rint(rng.normal(0, 9000, (S, ticks * 320))), -32768, 32767).astype(np.int16)
+    for t, (first, last) in {0: (-32768, 32767), 3: (32767, -32768), 4: (-32768, -32768), 7: (32767, 32767), 11: (-32768, 32767)}.items():
+        pcm[:, t * 320] = first
+        pcm[:, t * 320 + 319] = last
+    if clip:
+        assert 0.05 < np.mean(np.abs(pcm.astype(np.int32)) > divisor) < 0.09
+    fp = frontend_params(divisor, clip, 0.97, 160, True)
+    wave = engines["Wavenet"]
+    crnn = Engine(os.path.join(assets, "CRNN"))
+    ones = np.ones(S, np.uint8)
+    windows = {}
+
+    def ticked(name, bank):
+        try:
+            for t in range(ticks):
+                bank.step(pcm[:, t * 320:(t + 1) * 320], ones)
+            windows[name] = [bank.window(s) for s in range(S)]
+        finally:
+            bank.close()
+
+    try:
+        ticked("crnn", StreamBank(crnn, S, fp))
+        ticked("crnn two_launch", StreamBank(crnn, S, fp, two_launch=True))
+        ticked("wavenet", StreamBank(wave, S, fp))
+        A, B = _bank(wave, S, fp), _bank(wave, S, fp)
+        try:
+            rows_tick, _ = _tick_all(A, wave, pcm)
+            rows_feed = [[] for _ in range(S)]
+            at = 0
+            for k in (7, 633, 3200):
+                _, m = B.feed(list(range(S)), [pcm[s, at:at + k] for s in range(S)], want_mel=True)
+                for s in range(S):
+                    rows_feed[s].append(m[s])
+                at += k
+            assert at == pcm.shape[1]
+            windows["causal step"] = [A.window(s) for s in range(S)]
+            windows["causal feed"] = [B.window(s) for s in range(S)]
+        finally:
+            A.close()
+            B.close()
+    finally:
+        crnn.close()
+    _same_streams(rows_tick, rows_feed, "fed rows against the causal tick's")
+    n_rows = _rows_of(0, pcm.shape[1])[0]
+    tail = min(min(w[0].shape[0] for w in windows.values()), n_rows)  # (a CRNN window and a Wavenet window differ in length)
+    assert tail >= 20
+    for name, w in windows.items():
+        for s in range(S):
+            np.testing.assert_array_equal(w[s][-tail:], windows["causal step"][s][-tail:], err_msg=f"{name}: window of stream {s}")
+            np.testing.assert_array_equal(w[s][-tail:], np.concatenate(rows_tick[s])[-tail:], err_msg=f"{name}: window of stream {s} against its rows")
+    want = R.Ref64(os.path.join(assets, "Wavenet")).logmel(pcm[0], float(divisor), clip, 0.97, 160)
+    got = np.asarray(np.concatenate(rows_tick[0]), np.float64)
+    assert got.shape == want.y.shape == (n_rows, 40)
+    print(f"\nCONVERT divisor {divisor} clip {clip}: {n_rows} rows, mel needs tau_rel {R.needed_taus(got, want, 0.0, 0.0)[0]:.2e} (tau_rel {TAU_REL:g})", end="")
+    R.check_logmel(got, want, TAU_REL, 0.0)
 
 
 # ------------------------------------------------------------------ 2. a feed emits the frame posteriors of the rows it returns

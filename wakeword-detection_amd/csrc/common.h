@@ -240,21 +240,7 @@ struct ww_tick_tag {
   int pidx;                   // the head's output element that is the posterior
 };
 
-// The streaming front end's side of crnn_stream_kernel<FE != 0> - ONE launch per tick (crnn.hip).  Workgroup 2 s + k is window k of
-// stream s's tick; it reads the stream's control words and samples over the bus itself.
-#define WW_ST_RING 832  // 511 + 320 rounded up
-struct ww_tick_fe {
-  const int16_t *frames;  // page-locked host memory [S][WW_CHUNK]
-  const int32_t *ctl;     // page-locked host memory [S][4]: fill, n_frames, flags (1 speech, 2 active, 4 state parity), pos | rowq << 16
-  float *ring;            // [2][S][WW_ST_RING]: a stream's sample ring, ping-pong by its state parity (read [par], written [par ^ 1])
-  float *prev;            // [2][S] pre-emphasis carry, likewise
-  float *hist;            // [S][HR][F] mirrored mel rings (the model's `mel`)
-  int S, HR;
-  float divisor;
-  int clip;
-  float preemph;
-  int hop;
-};
+struct ww_tick_fe;  // the streaming front end's side of a one-launch tick (stream_fe.h)
 
 // ---- kernel-side entry points implemented in the .hip files ------------------------------
 int ww_k_logmel(ww_ctx *ctx, const ww_model *m, const int16_t *d_pcm, const float *d_f32, const int64_t *d_sample_offs,

@@ -13,8 +13,7 @@
 //                      crnn_detect_kernel.
 // Round 1's three-kernel chain (conv5x20_kernel -> gemm_nt_kernel -> gru_head_kernel, 52 us per 256 windows against
 // 34 us fused) and its bf16x6 projection GEMM are gone; their measurements are in DESIGN.md 7.1.
-#include "common.h"
-#include "fft_device.h"
+#include "stream_fe.h"
 #include <type_traits>
 
 #include <cstdlib>
@@ -794,23 +793,14 @@ struct stream_args {
   fused_args f;
   const int32_t *aux;  // [nw] stream * WW_STREAM_GXC + (stream rows incl. this window's newest) % WW_STREAM_GXC
   float *gxc;          // [S][WW_STREAM_GXC][192]
-  // FE != 0 - ONE launch per tick: the streaming front end's side (common.h) and the model's filterbank
+  // FE != 0 - ONE launch per tick: the streaming front end's side and the model's filterbank (stream_fe.h)
   ww_tick_fe fe;
-  const int *start;
-  const float *wpad, *bias;
-  int n_mel;
-  float floor_v, log_off, scale;
-  const double *hann, *tw256, *tw512;
+  ww_fe_filt fb;
 };
 
-// Mel-side LDS of the one-launch tick form, in the part of the feat region the three conv rows leave free (floats from `feat`)
-#define CT_X (3 * CF_FLD)                 // [WW_ST_RING] ring | the tick's new samples
-#define CT_XS (CT_X + WW_ST_RING)         // [WW_CHUNK] int16: the raw samples
-#define CT_WL (CT_XS + WW_CHUNK / 2)      // [3 rounds x 256 x 4] the mel weights [WW_MEL_TAPS][64], padded to whole store rounds
-#define CT_MAG (CT_WL + 3 * 256 * 4)      // [2][260] magnitudes of the (at most) two new frames
-#define CT_BUF (CT_MAG + 2 * 260 + 8)     // [2][FFT_LD] complex: the transforms' exchange buffers (16-byte aligned)
-static_assert(CT_BUF % 4 == 0 && CT_BUF + 2 * FFT_LD * 4 <= CF_FEAT_FLOATS, "tick front end does not fit beside the conv rows");
-static_assert(WW_MEL_TAPS * 64 <= 3 * 256 * 4 && WW_CHUNK * 2 == 40 * 16, "tick front end: store rounds");
+// Mel-side LDS of the one-launch tick form (stream_fe.h: fe_tick_lds), in the part of the feat region the three conv rows leave free
+#define CT_BASE (3 * CF_FLD)  // floats from `feat`; the weights go in in three store rounds of 256 x 16 bytes
+static_assert(CT_BASE % 4 == 0 && CT_BASE + FE_TL_FLOATS <= CF_FEAT_FLOATS, "tick front end does not fit beside the conv rows");
 
 // FE = 0: the windows of a tick come as descriptor tables behind a front-end kernel of its own (stream_frontend_kernel: two
 // launches per tick).  FE = 1 / 2 (fp32 / fp64 transform) - ONE launch per tick (round 5): workgroup 2 s + k is window k of stream
@@ -926,99 +916,66 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
       const int i = tid + q * CF_THREADS;
-      wlq[q] = ((const f32x4 *)sa.wpad)[i < WW_MEL_TAPS * 64 / 4 ? i : 0];
+      wlq[q] = ((const f32x4 *)sa.fb.wpad)[i < WW_MEL_TAPS * 64 / 4 ? i : 0];
     }
-    const int mel_st = lane < sa.n_mel ? sa.start[lane] : 0;
-    const float mel_bias = lane < sa.n_mel ? sa.bias[lane] : 0.0f;
+    const int mel_st = lane < sa.fb.n_mel ? sa.fb.start[lane] : 0;
+    const float mel_bias = lane < sa.fb.n_mel ? sa.fb.bias[lane] : 0.0f;
     const float4 ringq = ((const float4 *)(fe.ring + ((size_t)(tid >> 7) * fe.S + s) * WW_ST_RING))[tid & 127];
     const float carry0 = fe.prev[s], carry1 = fe.prev[fe.S + s];
     fft_consts<R> fc;
-    if (wave < 2) fft_load_consts<R>(fc, lane, sa.hann, sa.tw256, sa.tw512);
+    if (wave < 2) fft_load_consts<R>(fc, lane, sa.fb.hann, sa.fb.tw256, sa.fb.tw512);
     load_conv_w();
     // ---- what this workgroup is (uniform over it)
-    const int fill = cw.x, nf = cw.y, flags = cw.z, pos = cw.w & 0xffff, rowq = cw.w >> 16;
-    const int par = (flags >> 2) & 1;
-    const int np = (flags & 1) ? nf : 0;  // frames are analysed only while the VAD says speech (tflite.py:166)
-    if ((flags & 2) || k >= (np > 1 ? np : 1)) return;  // an active stream is not sampled at all (tflite.py:139-140) | no second window
-    const bool window = k < np, writer = k + 1 >= np;
-    const int nfk = window ? k + 1 : 0;  // window k ends at new frame k: it needs frames 0..k
     const int slots = a.T + 1;
+    const fe_tick_ctl c = fe_tick_decode(cw, k, slots);
+    if (c.idle) return;
     float4 stage[2];
     int sidx[2] = {-1, -1};
-    if (window) {
-      // the T rows that end at new row k are the contiguous block that starts at slot (pos + k + 2) % (T + 1) of the mirrored ring
-      int b = pos + k + 2;
-      b = b >= slots ? b - slots : b;
-      q0 = rowq + k + 1;  // rows since the reset incl. this window's newest, mod the cache ring
+    if (c.window) {
+      q0 = c.rowq + k + 1;  // rows since the reset incl. this window's newest, mod the cache ring
       q0 = q0 >= RA ? q0 - RA : q0;
       cache = sa.gxc + (size_t)s * RA * (6 * H);
       crow0 = cached(0); crow1 = cached(1); crow2 = cached(2);
-      const float *src = a.mel + ((size_t)s * fe.HR + b) * CV_NMEL;
+      const float *src = a.mel + ((size_t)s * fe.HR + c.b) * CV_NMEL;
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int i = tid + q * CF_THREADS;            // 140 + 210 float4
         const int f4 = i < 140 ? i : 1300 + (i - 140);  // float4 index inside the [151][40] window
-        const bool in = i < 350 && f4 / 10 < a.T - nfk;  // (the rows of this tick come from waves 0, 1)
+        const bool in = i < 350 && f4 / 10 < a.T - c.nfk;  // (the rows of this tick come from waves 0, 1)
         sidx[q] = in ? f4 : -1;
         stage[q] = in ? *(const float4 *)(src + (size_t)f4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
-    float *fx = feat + CT_X, *fwl = feat + CT_WL, *fmag = feat + CT_MAG;
-    short *fxs = (short *)(feat + CT_XS);
-    cplx<R> *fbuf = (cplx<R> *)(feat + CT_BUF);
+    const fe_tick_lds<R> l = FE_TICK_LDS(R, feat + CT_BASE);
 #pragma unroll
-    for (int q = 0; q < 3; ++q) ((f32x4 *)fwl)[tid + q * CF_THREADS] = wlq[q];
-    if ((tid >> 7) == par) ((float4 *)fx)[tid & 127] = ringq;
-    if (tid < 40) ((uint4 *)fxs)[tid] = raw;
-    if (window) {
+    for (int q = 0; q < 3; ++q) ((f32x4 *)l.wl)[tid + q * CF_THREADS] = wlq[q];
+    if ((tid >> 7) == c.par) ((float4 *)l.x)[tid & 127] = ringq;
+    if (tid < 40) ((uint4 *)l.xs)[tid] = raw;
+    if (c.window) {
       for (int i = tid; i < CF_IMG_FLOATS / 4; i += CF_THREADS) ((float4 *)img)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       tile_offsets();
     }
     __syncthreads();
-    // ---- [ring | new samples]: normalise, clip, pre-emphasise (the arithmetic of stream_frontend_kernel, streams.hip)
-    for (int i = tid; i < WW_CHUNK; i += CF_THREADS) {
-      float v = __fdiv_rn((float)fxs[i], fe.divisor);
-      if (fe.clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
-      float p;
-      if (i == 0) {
-        p = par ? carry1 : carry0;
-      } else {
-        p = __fdiv_rn((float)fxs[i - 1], fe.divisor);
-        if (fe.clip) p = fminf(fmaxf(p, -1.0f), 1.0f);
-      }
-      fx[fill + i] = (fe.preemph != 0.0f) ? ww_preemph_rn(v, fe.preemph, p) : v;
-    }
+    // ---- [ring | new samples]: normalise, clip, pre-emphasise
+    for (int i = tid; i < WW_CHUNK; i += CF_THREADS) l.x[c.fill + i] = fe_sample(l.xs, i, c.par ? carry1 : carry0, fe.cv);
     __syncthreads();
-    if (writer && tid == 0) {
-      float v = __fdiv_rn((float)fxs[WW_CHUNK - 1], fe.divisor);
-      if (fe.clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
-      fe.prev[(size_t)(par ^ 1) * fe.S + s] = v;  // tflite.py:156-158: the carry is the un-emphasised last sample
-    }
+    // tflite.py:156-158: the carry is the un-emphasised last sample
+    if (c.writer && tid == 0) fe.prev[(size_t)(c.par ^ 1) * fe.S + s] = fe_norm(l.xs[WW_CHUNK - 1], fe.cv);
     // ---- new frames: wave f transforms frame f, its mel row goes straight into the window image (time T - nfk + f) and,
     // from the writer, into the stream's mirrored ring
-    if (wave < nfk) {
-      const float *srcx = fx + wave * fe.hop;
-      auto x2 = [&](int n) -> float2 { return make_float2(srcx[2 * n], srcx[2 * n + 1]); };
-      float *mg = fmag + wave * 260;
-      frame_fft_mag<R>(x2, fc, fbuf + wave * FFT_LD, mg, lane);
-      const float mv = mel_band(mg, fwl, mel_st, mel_bias, sa.floor_v, sa.log_off, sa.scale, lane);
+    if (wave < c.nfk) {
+      const float mv = fe_frame_mel<R>(l.x + wave * fe.hop, fc, l.buf, l.mag, wave, l.wl, mel_st, mel_bias, sa.fb, lane);
       if (lane < CV_NMEL) {
-        img[(lane + CV_PF) * CV_LDT + (a.T - nfk + wave) + CV_PT] = mv;
-        if (writer) {
-          int p = pos + wave;  // mirrored ring: the row goes to p % slots and p % slots + slots
-          p = p >= slots ? p - slots : p;
-          float *h = fe.hist + ((size_t)s * fe.HR + p) * CV_NMEL + lane;
-          h[0] = mv;
-          h[(size_t)slots * CV_NMEL] = mv;
-        }
+        img[(lane + CV_PF) * CV_LDT + (a.T - c.nfk + wave) + CV_PT] = mv;
+        if (c.writer) fe_ring_store(fe.hist, (size_t)s * fe.HR, c.pos + wave, slots, CV_NMEL, lane, mv);
       }
     }
-    if (writer) {  // keep the ring tail (for the next tick: the other copy)
-      const int keep = fill + WW_CHUNK - nf * fe.hop;
-      float *ring = fe.ring + ((size_t)(par ^ 1) * fe.S + s) * WW_ST_RING;
-      for (int i = tid; i < keep; i += CF_THREADS) ring[i] = fx[nf * fe.hop + i];
+    if (c.writer) {  // keep the ring tail (for the next tick: the other copy)
+      const int keep = c.fill + WW_CHUNK - c.nf * fe.hop;
+      float *ring = fe.ring + ((size_t)(c.par ^ 1) * fe.S + s) * WW_ST_RING;
+      for (int i = tid; i < keep; i += CF_THREADS) ring[i] = l.x[c.nf * fe.hop + i];
     }
-    if (!window) return;  // the tick has no window for this stream: its ring has advanced, that is all
+    if (!c.window) return;  // the tick has no window for this stream: its ring has advanced, that is all
     scatter(stage, sidx);
   }
   __syncthreads();
@@ -2212,9 +2169,7 @@ int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int pre
   sa.f.tag = tag;
   sa.gxc = d_gxc;
   sa.fe = fe;
-  sa.start = f.start; sa.wpad = f.wpad; sa.bias = f.bias; sa.n_mel = f.n_mel;
-  sa.floor_v = f.floor_v; sa.log_off = f.log_off; sa.scale = f.scale;
-  sa.hann = f.hann; sa.tw256 = f.tw256; sa.tw512 = f.tw512;
+  sa.fb = ww_fe_filt_of(f);
   const int nwg = 2 * fe.S;
   {
     ww_launch_scope scope(ctx, "crnn_stream_kernel<tick>");

@@ -11,6 +11,8 @@
 // knows the number of posteriors a tick will produce and can size the launch exactly; all
 // sample and mel data stay in HBM.
 //
+// The front end's arithmetic and the mirrored ring's row store are stream_fe.h's, shared with the one-launch ticks of crnn.hip and
+// wavenet.hip; the kernels here are
 //   stream_frontend_kernel  one workgroup (2 waves) per stream: read the tick's samples and control words from
 //                           pinned host memory, normalise + pre-emphasise the 320 new
 //                           samples, FFT + mel for each new frame (one wave per frame) when
@@ -23,8 +25,7 @@
 //   then the regular CRNN / Wavenet kernels run on the compacted list of new windows.
 //   stream_feed_frontend_kernel  a causal bank fed any number of samples per stream (ww_stream_feed, further down): one workgroup
 //                           per 16 new frames of a stream, the same conversion and the same per-frame functions as above.
-#include "common.h"
-#include "fft_device.h"
+#include "stream_fe.h"
 
 #include <algorithm>
 #include <sched.h>
@@ -113,15 +114,19 @@ struct stream_fe_args {
   float *hist;
   float *prev;
   int T, F, HR;
-  float divisor;
-  int clip;
-  float preemph;
+  ww_fe_pcm cv;
   int hop;
-  const int *start;
-  const float *wpad, *bias;
-  int n_mel;
-  float floor_v, log_off, scale;
-  const double *hann, *tw256, *tw512;
+  ww_fe_filt fb;
+};
+// the kernel's dynamic LDS (bytes)
+template <typename R>
+struct stream_fe_lds {
+  static constexpr size_t buf = 0;                                     // [2][FFT_LD] complex
+  static constexpr size_t mag = buf + 2 * FFT_LD * sizeof(cplx<R>);    // [2][FE_MAG_LD]
+  static constexpr size_t wl = mag + 2 * FE_MAG_LD * sizeof(float);    // the mel weights (rounded up to whole 128-thread store rounds)
+  static constexpr size_t x = wl + ST_WL_BYTES;                        // [ST_RING] ring | new samples
+  static constexpr size_t xs = x + ST_RING * sizeof(float);            // [WW_CHUNK] raw samples of the tick
+  static constexpr size_t bytes = xs + WW_CHUNK * sizeof(short);
 };
 
 template <typename R>
@@ -131,19 +136,16 @@ __global__ __launch_bounds__(128) void stream_frontend_kernel(stream_fe_args a) 
   const int s = blockIdx.x;
   // the tick's 320 samples (40 x 16 bytes) are requested from pinned host memory BEFORE the control words are looked at:
   // one trip over the bus instead of two in a row (control words -> branch -> samples)
-  static_assert(WW_CHUNK * 2 == 40 * 16, "a tick is 40 sixteen-byte pieces");
   uint4 raw = make_uint4(0u, 0u, 0u, 0u);
   if (tid < 40) raw = ((const uint4 *)(a.frames + (size_t)s * WW_CHUNK))[tid];
   const int4 cw = ((const int4 *)a.ctl)[s];
   const int fill = cw.x, n_frames = cw.y, flags = cw.z, pos = cw.w;
   const bool speech = flags & 1, skip = flags & 2;
 
-  size_t off = 0;
-  cplx<R> *fbuf = (cplx<R> *)(smem + off); off += 2 * FFT_LD * sizeof(cplx<R>);
-  float *mag = (float *)(smem + off); off += 2 * 260 * sizeof(float);
-  float *wl = (float *)(smem + off); off += ST_WL_BYTES;  // (rounded up to whole 128-thread store rounds)
-  float *x = (float *)(smem + off); off += ST_RING * sizeof(float);  // [ST_RING]
-  short *xs = (short *)(smem + off);  // [WW_CHUNK] raw samples of the tick
+  typedef stream_fe_lds<R> L;
+  cplx<R> *fbuf = (cplx<R> *)(smem + L::buf);
+  float *mag = (float *)(smem + L::mag), *wl = (float *)(smem + L::wl), *x = (float *)(smem + L::x);
+  short *xs = (short *)(smem + L::xs);
 
   // ---- this tick's window descriptors: host-pinned -> device arrays (read by the model kernels that follow).  A tick has at
   // most two windows per stream, i.e. one descriptor per thread of the first workgroups: requested here with everything else
@@ -161,15 +163,15 @@ __global__ __launch_bounds__(128) void stream_frontend_kernel(stream_fe_args a) 
 #pragma unroll
   for (int q = 0; q < WLQ; ++q) {
     const int i = tid + q * 128;
-    wlq[q] = ((const f32x4 *)a.wpad)[i < WW_MEL_TAPS * 64 / 4 ? i : 0];
+    wlq[q] = ((const f32x4 *)a.fb.wpad)[i < WW_MEL_TAPS * 64 / 4 ? i : 0];
   }
-  const int mel_st = lane < a.n_mel ? a.start[lane] : 0;      // (the mel stage's two per-band scalars: asked for here, not
-  const float mel_bias = lane < a.n_mel ? a.bias[lane] : 0.0f;  // behind the transform where they are used)
+  const int mel_st = lane < a.fb.n_mel ? a.fb.start[lane] : 0;      // (the mel stage's two per-band scalars: asked for here, not
+  const float mel_bias = lane < a.fb.n_mel ? a.fb.bias[lane] : 0.0f;  // behind the transform where they are used)
   float *ring = a.ring + (size_t)s * ST_RING;
   const float4 ringq = ((const float4 *)ring)[tid];  // samples 4 tid .. 4 tid + 3 (128 threads x 4 = 512 >= fill)
   const float carry = a.prev[s];
   fft_consts<R> fc;
-  fft_load_consts<R>(fc, lane, a.hann, a.tw256, a.tw512);
+  fft_load_consts<R>(fc, lane, a.fb.hann, a.fb.tw256, a.fb.tw512);
   // parked in LDS unconditionally and BEFORE the branch on the control words: behind it, and under a per-piece condition, the
   // compiler moved each load down to its store - five round trips to L2 in a row (the wl region is padded to whole rounds)
 #pragma unroll
@@ -190,39 +192,13 @@ __global__ __launch_bounds__(128) void stream_frontend_kernel(stream_fe_args a) 
   ((float4 *)x)[tid] = ringq;
   if (tid < 40) ((uint4 *)xs)[tid] = raw;
   __syncthreads();
-  for (int i = tid; i < WW_CHUNK; i += 128) {
-    float v = __fdiv_rn((float)xs[i], a.divisor);
-    if (a.clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
-    float p;
-    if (i == 0) {
-      p = carry;
-    } else {
-      p = __fdiv_rn((float)xs[i - 1], a.divisor);
-      if (a.clip) p = fminf(fmaxf(p, -1.0f), 1.0f);
-    }
-    x[fill + i] = (a.preemph != 0.0f) ? ww_preemph_rn(v, a.preemph, p) : v;
-  }
+  for (int i = tid; i < WW_CHUNK; i += 128) x[fill + i] = fe_sample(xs, i, carry, a.cv);
   __syncthreads();
-  if (tid == 0) {
-    float v = __fdiv_rn((float)xs[WW_CHUNK - 1], a.divisor);
-    if (a.clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
-    a.prev[s] = v;  // tflite.py:156-158: carry is the un-emphasised last sample
-  }
+  if (tid == 0) a.prev[s] = fe_norm(xs[WW_CHUNK - 1], a.cv);  // tflite.py:156-158: carry is the un-emphasised last sample
   // ---- new frames (wave k handles frame k); only analysed while is_speech (tflite.py:166)
   if (speech && wave < n_frames) {
-    const float *src = x + wave * a.hop;
-    auto x2 = [&](int n) -> float2 { return make_float2(src[2 * n], src[2 * n + 1]); };
-    float *mg = mag + wave * 260;
-    frame_fft_mag<R>(x2, fc, fbuf + wave * FFT_LD, mg, lane);
-    const float mv = mel_band(mg, wl, mel_st, mel_bias, a.floor_v, a.log_off, a.scale, lane);
-    if (lane < a.n_mel) {
-      const int slots = a.T + 1;
-      int p = pos + wave;  // mirrored ring: the row goes to p % slots and p % slots + slots
-      p = p >= slots ? p - slots : p;
-      float *h = a.hist + ((size_t)s * a.HR + p) * a.F + lane;
-      h[0] = mv;
-      h[(size_t)slots * a.F] = mv;
-    }
+    const float mv = fe_frame_mel<R>(x + wave * a.hop, fc, fbuf, mag, wave, wl, mel_st, mel_bias, a.fb, lane);
+    if (lane < a.fb.n_mel) fe_ring_store(a.hist, (size_t)s * a.HR, pos + wave, a.T + 1, a.F, lane, mv);
   }
   __syncthreads();
   // ---- keep the ring tail
@@ -233,8 +209,8 @@ __global__ __launch_bounds__(128) void stream_frontend_kernel(stream_fe_args a) 
 // ---- a causal bank's feed (ww_stream_feed): the front end of any number of new samples per stream ---------------------------------
 // One workgroup (4 waves) per group of up to FEED_GROUP new frames of one stream.  Frame f of a call covers samples
 // [160 f, 160 f + 512) of [the stream's pending samples | the packet]; the group stages what its frames cover in LDS - the pending
-// samples as they are, the packet's through the conversion of stream_frontend_kernel (same operations on the same values) - and
-// each wave runs the tick's frame_fft_mag + mel_band on its frames: a fed row is the tick's row bit for bit.
+// samples as they are, the packet's through the tick's conversion (fe_sample) - and each wave runs the tick's fe_frame_mel on its
+// frames: a fed row is the tick's row bit for bit.
 // The stream's state (pending samples, carry) is written by the stream's FIRST group (the only one when the packet completes no
 // frame): pending samples are fewer than 512, so only frames 0..3 - the first group's - reach into them, and the carry belongs to
 // the packet's first sample, which frame 0 covers.  The one reader being the one writer, the groups of a stream need no order.
@@ -257,14 +233,18 @@ struct feed_fe_args {
   float *rows;          // [rows of the call][F]
   float *ring, *hist, *prev;
   int T, F, HR;
-  float divisor;
-  int clip;
-  float preemph;
-  const int *start;
-  const float *wpad, *bias;
-  int n_mel;
-  float floor_v, log_off, scale;
-  const double *hann, *tw256, *tw512;
+  ww_fe_pcm cv;
+  ww_fe_filt fb;
+};
+// the kernel's dynamic LDS (bytes)
+template <typename R>
+struct feed_fe_lds {
+  static constexpr size_t buf = 0;                                              // [FEED_WAVES][FFT_LD] complex
+  static constexpr size_t mag = buf + FEED_WAVES * FFT_LD * sizeof(cplx<R>);    // [FEED_WAVES][FE_MAG_LD]
+  static constexpr size_t wl = mag + FEED_WAVES * FE_MAG_LD * sizeof(float);    // [WW_MEL_TAPS][64] the mel weights
+  static constexpr size_t x = wl + WW_MEL_TAPS * 64 * sizeof(float);            // [FEED_X] what the group's frames cover
+  static constexpr size_t pend = x + FEED_X * sizeof(float);                    // [512] the stream's new pending samples (first group)
+  static constexpr size_t bytes = pend + 512 * sizeof(float);
 };
 
 template <typename R>
@@ -276,36 +256,20 @@ __global__ __launch_bounds__(FEED_WAVES * 64) void stream_feed_frontend_kernel(f
   const int s = d.sid, fill = d.fill;
   const bool first = g.f0 == 0;
 
-  size_t off = 0;
-  cplx<R> *fbuf = (cplx<R> *)(smem + off); off += FEED_WAVES * FFT_LD * sizeof(cplx<R>);
-  float *mag = (float *)(smem + off); off += FEED_WAVES * 260 * sizeof(float);
-  float *wl = (float *)(smem + off); off += WW_MEL_TAPS * 64 * 4;
-  float *x = (float *)(smem + off); off += FEED_X * sizeof(float);
-  float *pend = (float *)(smem + off);  // [512] the stream's new pending samples (first group)
+  typedef feed_fe_lds<R> L;
+  cplx<R> *fbuf = (cplx<R> *)(smem + L::buf);
+  float *mag = (float *)(smem + L::mag), *wl = (float *)(smem + L::wl), *x = (float *)(smem + L::x), *pend = (float *)(smem + L::pend);
 
-  for (int i = tid; i < WW_MEL_TAPS * 64 / 4; i += FEED_WAVES * 64) ((float4 *)wl)[i] = ((const float4 *)a.wpad)[i];
-  const int mel_st = lane < a.n_mel ? a.start[lane] : 0;
-  const float mel_bias = lane < a.n_mel ? a.bias[lane] : 0.0f;
+  for (int i = tid; i < WW_MEL_TAPS * 64 / 4; i += FEED_WAVES * 64) ((float4 *)wl)[i] = ((const float4 *)a.fb.wpad)[i];
+  const int mel_st = lane < a.fb.n_mel ? a.fb.start[lane] : 0;
+  const float mel_bias = lane < a.fb.n_mel ? a.fb.bias[lane] : 0.0f;
   float *ring = a.ring + (size_t)s * ST_RING;
   const int16_t *pk = a.pcm + d.s_off;
   const float carry = first ? a.prev[s] : 0.0f;  // (only the packet's first sample needs it, and only the first group covers that)
   fft_consts<R> fc;
-  fft_load_consts<R>(fc, lane, a.hann, a.tw256, a.tw512);
-  // sample v of [pending | packet]: stream_frontend_kernel's conversion loop, x[fill + i] = ...
-  auto sample = [&](int64_t v) -> float {
-    if (v < fill) return ring[v];
-    const int64_t i = v - fill;
-    float sv = __fdiv_rn((float)pk[i], a.divisor);
-    if (a.clip) sv = fminf(fmaxf(sv, -1.0f), 1.0f);
-    float p;
-    if (i == 0) {
-      p = carry;
-    } else {
-      p = __fdiv_rn((float)pk[i - 1], a.divisor);
-      if (a.clip) p = fminf(fmaxf(p, -1.0f), 1.0f);
-    }
-    return (a.preemph != 0.0f) ? ww_preemph_rn(sv, a.preemph, p) : sv;
-  };
+  fft_load_consts<R>(fc, lane, a.fb.hann, a.fb.tw256, a.fb.tw512);
+  // sample v of [pending | packet]
+  auto sample = [&](int64_t v) -> float { return v < fill ? ring[v] : fe_sample(pk, v - fill, carry, a.cv); };
   const int64_t base = (int64_t)g.f0 * 160;
   const int len = g.nf > 0 ? (g.nf - 1) * 160 + 512 : 0;
   for (int i = tid; i < len; i += FEED_WAVES * 64) x[i] = sample(base + i);
@@ -316,31 +280,19 @@ __global__ __launch_bounds__(FEED_WAVES * 64) void stream_feed_frontend_kernel(f
   __syncthreads();  // x and pend complete; the ring and the carry have been read
   if (first) {
     for (int i = tid; i < keep; i += FEED_WAVES * 64) ring[i] = pend[i];
-    if (tid == 0 && d.k > 0) {
-      float v = __fdiv_rn((float)pk[d.k - 1], a.divisor);
-      if (a.clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
-      a.prev[s] = v;  // the un-emphasised last sample; an empty packet leaves the carry
-    }
+    if (tid == 0 && d.k > 0) a.prev[s] = fe_norm(pk[d.k - 1], a.cv);  // the un-emphasised last sample; an empty packet leaves the carry
   }
   // ---- the group's frames, wave k frames k, k + 4, ...: to the call's row buffer, the stream's last T + 1 rows also into its
   //      mirrored ring (row r of the call at slot (pos + r) % (T + 1), as the ticks would have left them)
   const int slots = a.T + 1;
   const int ring_from = d.rows > slots ? d.rows - slots : 0;
   for (int fl = wave; fl < g.nf; fl += FEED_WAVES) {
-    const float *src = x + fl * 160;
-    auto x2 = [&](int n) -> float2 { return make_float2(src[2 * n], src[2 * n + 1]); };
-    float *mg = mag + wave * 260;
-    frame_fft_mag<R>(x2, fc, fbuf + wave * FFT_LD, mg, lane);
-    const float mv = mel_band(mg, wl, mel_st, mel_bias, a.floor_v, a.log_off, a.scale, lane);
+    const float mv = fe_frame_mel<R>(x + fl * 160, fc, fbuf, mag, wave, wl, mel_st, mel_bias, a.fb, lane);
     const int r = g.f0 + fl;
-    if (lane < a.n_mel) {
+    if (lane < a.fb.n_mel) {
       a.rows[(size_t)(d.r_off + r) * a.F + lane] = mv;
-      if (r >= ring_from) {
-        const int p = (int)(((int64_t)d.pos + r) % slots);
-        float *h = a.hist + ((size_t)s * a.HR + p) * a.F + lane;
-        h[0] = mv;
-        h[(size_t)slots * a.F] = mv;
-      }
+      // (a call can bring more rows than the ring has slots: reduced below `slots` here)
+      if (r >= ring_from) fe_ring_store(a.hist, (size_t)s * a.HR, (int)(((int64_t)d.pos + r) % slots), slots, a.F, lane, mv);
     }
     wave_sync();  // the wave is through with its magnitudes before the next frame's transform writes them
   }
@@ -612,8 +564,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     const int flags = is_speech[s] & 3;
     int nf = 0;
     if (!(flags & 2)) {
-      const int tot = st->fill[s] + WW_CHUNK;
-      nf = tot >= WW_FFT_WINDOW ? (tot - WW_FFT_WINDOW) / hop + 1 : 0;
+      nf = (int)ww_fe_frames(st->fill[s] + WW_CHUNK, hop);
     }
     const int np = (flags & 1) && !(flags & 2) ? nf : 0;
     n_post[s] = np;
@@ -657,7 +608,6 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   memcpy(h_frames, frames, (size_t)S * WW_CHUNK * 2);
   tl[2] = st_now_ns();
   const ww_model *m = st->model;
-  const ww_filter_dev &f = m->filt;
   // posterior element: width-1 head -> [0]; width-2 head -> [1]  
   const int pidx = st->NO == 1 ? 0 : 1;
   ww_tick_tag tag = {st->h_tag_dev, st->seq, pidx};
@@ -669,7 +619,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     fe.ctl = (const int32_t *)(st->h_pack_dev + ((char *)h_ctl - st->h_pack));
     fe.ring = st->ring; fe.prev = st->prev; fe.hist = st->hist;
     fe.S = S; fe.HR = st->HR;
-    fe.divisor = st->fp.pcm_divisor; fe.clip = st->fp.clip; fe.preemph = st->fp.pre_emphasis; fe.hop = hop;
+    fe.cv = ww_fe_pcm_of(st->fp); fe.hop = hop;
     int rc = m->kind == WW_KIND_CRNN ? ww_k_crnn_tick(ctx, m, fe, st->fp.precise, st->gxc, tag) : ww_k_wave_tick(ctx, m, fe, st->fp.precise, tag);
     if (rc) return rc;
     tagged = true;
@@ -686,19 +636,14 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     a.ring = st->ring;
     a.hist = st->hist; a.prev = st->prev;
     a.T = st->T; a.F = st->F; a.HR = st->HR;
-    a.divisor = st->fp.pcm_divisor; a.clip = st->fp.clip; a.preemph = st->fp.pre_emphasis; a.hop = hop;
-    a.start = f.start; a.wpad = f.wpad; a.bias = f.bias;
-    a.n_mel = f.n_mel; a.floor_v = f.floor_v; a.log_off = f.log_off; a.scale = f.scale;
-    a.hann = f.hann; a.tw256 = f.tw256; a.tw512 = f.tw512;
+    a.cv = ww_fe_pcm_of(st->fp); a.hop = hop;
+    a.fb = ww_fe_filt_of(m->filt);
     {
       ww_launch_scope scope(ctx, "stream_frontend_kernel");
-      if (st->fp.precise) {
-        size_t sm = 2 * FFT_LD * 16 + 2 * 260 * 4 + ST_WL_BYTES + ST_RING * 4 + WW_CHUNK * 2;
-        hipLaunchKernelGGL((stream_frontend_kernel<double>), dim3(S), dim3(128), sm, ctx->stream, a);
-      } else {
-        size_t sm = 2 * FFT_LD * 8 + 2 * 260 * 4 + ST_WL_BYTES + ST_RING * 4 + WW_CHUNK * 2;
-        hipLaunchKernelGGL((stream_frontend_kernel<float>), dim3(S), dim3(128), sm, ctx->stream, a);
-      }
+      if (st->fp.precise)
+        hipLaunchKernelGGL((stream_frontend_kernel<double>), dim3(S), dim3(128), stream_fe_lds<double>::bytes, ctx->stream, a);
+      else
+        hipLaunchKernelGGL((stream_frontend_kernel<float>), dim3(S), dim3(128), stream_fe_lds<float>::bytes, ctx->stream, a);
     }
     WW_HIP(ctx, hipGetLastError());
     tl[3] = st_now_ns();
@@ -798,8 +743,7 @@ static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64
     seen[s] = 1;
     const int64_t k = sample_offs[i + 1] - sample_offs[i];
     if (k < 0) return ww_fail(ctx, WW_EINVAL, "%s: sample_offs descend at entry %d", what, i);
-    const int64_t tot = st->fill[s] + k;
-    const int64_t r = tot >= WW_FFT_WINDOW ? (tot - WW_FFT_WINDOW) / st->fp.hop + 1 : 0;
+    const int64_t r = ww_fe_frames(st->fill[s] + k, st->fp.hop);
     if (r > 0x3fffffff || rows + r > 0x3fffffff) return ww_fail(ctx, WW_EINVAL, "%s: more than 2^30 rows in one call", what);
     rows += r;
     row_offs[i + 1] = rows;
@@ -913,22 +857,18 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
   }
   WW_HIP(ctx, hipMemcpyAsync(d_str, h_str, b_tab, hipMemcpyHostToDevice, ctx->stream));  // (the tables are one block on both sides)
   WW_HIP(ctx, hipMemcpyAsync(d_pcm, pcm + sample_offs[0], (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
-  const ww_filter_dev &f = m->filt;
   feed_fe_args a = {};
   a.pcm = d_pcm; a.str = d_str; a.grp = d_grp; a.rows = d_rows;
   a.ring = st->ring; a.hist = st->hist; a.prev = st->prev;
   a.T = T; a.F = F; a.HR = st->HR;
-  a.divisor = st->fp.pcm_divisor; a.clip = st->fp.clip; a.preemph = st->fp.pre_emphasis;
-  a.start = f.start; a.wpad = f.wpad; a.bias = f.bias;
-  a.n_mel = f.n_mel; a.floor_v = f.floor_v; a.log_off = f.log_off; a.scale = f.scale;
-  a.hann = f.hann; a.tw256 = f.tw256; a.tw512 = f.tw512;
+  a.cv = ww_fe_pcm_of(st->fp);
+  a.fb = ww_fe_filt_of(m->filt);
   if (!grp.empty()) {
     ww_launch_scope scope(ctx, "stream_feed_frontend_kernel");
-    const size_t sm_rest = FEED_WAVES * 260 * 4 + WW_MEL_TAPS * 64 * 4 + FEED_X * 4 + 512 * 4;
     if (st->fp.precise)
-      hipLaunchKernelGGL((stream_feed_frontend_kernel<double>), dim3((unsigned)grp.size()), dim3(FEED_WAVES * 64), FEED_WAVES * FFT_LD * 16 + sm_rest, ctx->stream, a);
+      hipLaunchKernelGGL((stream_feed_frontend_kernel<double>), dim3((unsigned)grp.size()), dim3(FEED_WAVES * 64), feed_fe_lds<double>::bytes, ctx->stream, a);
     else
-      hipLaunchKernelGGL((stream_feed_frontend_kernel<float>), dim3((unsigned)grp.size()), dim3(FEED_WAVES * 64), FEED_WAVES * FFT_LD * 8 + sm_rest, ctx->stream, a);
+      hipLaunchKernelGGL((stream_feed_frontend_kernel<float>), dim3((unsigned)grp.size()), dim3(FEED_WAVES * 64), feed_fe_lds<float>::bytes, ctx->stream, a);
     WW_HIP(ctx, hipGetLastError());
   }
   const int pidx = NO == 1 ? 0 : 1;  // posterior element, as a tick's

@@ -31,8 +31,7 @@
 // wavenet_seq_kernel (fp32): the same block loop over a mel sequence of ANY length - the model as its trainer builds it with
 // timesteps=None, causal zeros in front of row 0 only - walked in chunks with each block's last 16 rows of u carried from chunk
 // to chunk; whole sequences (ww_wave_sequence) and, one wave per stream, a causal bank's tick (WW_STREAM_CAUSAL).  See there.
-#include "common.h"
-#include "fft_device.h"
+#include "stream_fe.h"
 #undef NB   // (fft_device.h: bins of the transform; here NB is the model's block count)
 #undef WIN
 
@@ -91,22 +90,15 @@ struct wave_args {
   const float *enc_in;  // HEAD_ONLY: encoder output to run the detect graph on
   const uint4 *wpk;     // split-bf16 mode: parameter pages [NB][WV_PAGE_U4] (A operands of v_mfma_f32_16x16x32_bf16, then the vectors)
   ww_tick_tag tag;      // streaming ticks: the posterior as a {value, tick number} pair instead of the row of `out`
-  // TICK != 0 - ONE launch per tick (round 5): the streaming front end's side (common.h) and the model's filterbank
+  // TICK != 0 - ONE launch per tick (round 5): the streaming front end's side and the model's filterbank (stream_fe.h)
   ww_tick_fe fe;
-  const int *mel_start;
-  const float *mel_wpad, *mel_bias;
-  float floor_v, log_off, scale;
-  const double *hann, *tw256, *tw512;
+  ww_fe_filt fb;
 };
 
-// Mel-side LDS of the one-launch tick form, behind the staged input [WV_T][WV_INLD] (floats from `lds`); dead before the block loop
-#define WT_X (WV_T * WV_INLD)          // [WW_ST_RING] ring | the tick's new samples
-#define WT_XS (WT_X + WW_ST_RING)      // [WW_CHUNK] int16: the raw samples
-#define WT_WL (WT_XS + WW_CHUNK / 2)   // [768 x 4] the mel weights [WW_MEL_TAPS][64], padded to one store round of 12 waves
-#define WT_MAG (WT_WL + 768 * 4)       // [2][260] magnitudes of the (at most) two new frames
-#define WT_BUF (WT_MAG + 2 * 260 + 8)  // [2][FFT_LD] complex (16-byte aligned)
-#define WT_END (WT_BUF + 2 * FFT_LD * 4)
-static_assert(WT_BUF % 4 == 0 && WW_MEL_TAPS * 64 <= 768 * 4, "tick front end: LDS layout");
+// Mel-side LDS of the one-launch tick form (stream_fe.h: fe_tick_lds), behind the staged input [WV_T][WV_INLD]; dead before the block loop
+#define WT_BASE (WV_T * WV_INLD)  // floats from `lds`; the weights go in in one store round of 12 waves x 16 bytes
+#define WT_END (WT_BASE + FE_TL_FLOATS)
+static_assert(WT_BASE % 4 == 0, "tick front end: LDS layout");
 
 __device__ __forceinline__ float sigmoid_w(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -489,60 +481,41 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
     const ww_tick_fe &fe = a.fe;
     const int s = w >> 1, k = w & 1;
     // device-side inputs of the front end that do not depend on the control words: requested while those cross the bus
-    const f32x4 wlq = ((const f32x4 *)a.mel_wpad)[tid < WW_MEL_TAPS * 64 / 4 ? tid : 0];
-    const int mel_st = lane < a.n_mel ? a.mel_start[lane] : 0;
-    const float mel_bias = lane < a.n_mel ? a.mel_bias[lane] : 0.0f;
+    const f32x4 wlq = ((const f32x4 *)a.fb.wpad)[tid < WW_MEL_TAPS * 64 / 4 ? tid : 0];
+    const int mel_st = lane < a.n_mel ? a.fb.start[lane] : 0;
+    const float mel_bias = lane < a.n_mel ? a.fb.bias[lane] : 0.0f;
     // the sample ring: threads 0..127 ask for the copy of parity 0, threads 128..255 for parity 1 (128 x 4 = 512 > fill)
     const f32x4 ringq = ((const f32x4 *)(fe.ring + ((size_t)((tid >> 7) & 1) * fe.S + s) * WW_ST_RING))[tid & 127];
     const float carry0 = fe.prev[s], carry1 = fe.prev[fe.S + s];
     fft_consts<RT> fc;
-    if (wave < 2) fft_load_consts<RT>(fc, lane, a.hann, a.tw256, a.tw512);
-    // ---- what this workgroup is (uniform over it; as crnn_stream_kernel<FE>)
-    const int fill = t_cw.x, nf = t_cw.y, flags = t_cw.z, pos = t_cw.w & 0xffff;
-    const int par = (flags >> 2) & 1;
-    const int np = (flags & 1) ? nf : 0;  // frames are analysed only while the VAD says speech (tflite.py:166)
-    if ((flags & 2) || k >= (np > 1 ? np : 1)) return;  // an active stream is not sampled at all (tflite.py:139-140) | no second window
-    const bool window = k < np, writer = k + 1 >= np;
-    const int nfk = window ? k + 1 : 0;  // window k ends at new frame k: it needs frames 0..k
+    if (wave < 2) fft_load_consts<RT>(fc, lane, a.fb.hann, a.fb.tw256, a.fb.tw512);
+    // ---- what this workgroup is (uniform over it)
     const int slots = T + 1;
+    const fe_tick_ctl c = fe_tick_decode(t_cw, k, slots);
+    if (c.idle) return;
     // the rows that were there before: the block [(pos + k + 2) % (T + 1), + T - nfk) of the stream's mirrored ring
     constexpr int SQ = (WV_T * WV_INLD / 4 + WV_THREADS - 1) / WV_THREADS;
     f32x4 st[SQ];
     int n4 = 0;
-    if (window) {
-      int b = pos + k + 2;
-      b = b >= slots ? b - slots : b;
-      const float *src = a.mel + ((size_t)s * fe.HR + b) * a.n_mel;  // (160-byte rows of a hipMalloc'ed history: 16-byte aligned)
-      n4 = ((T - nfk) * a.n_mel) >> 2;
+    if (c.window) {
+      const float *src = a.mel + ((size_t)s * fe.HR + c.b) * a.n_mel;  // (160-byte rows of a hipMalloc'ed history: 16-byte aligned)
+      n4 = ((T - c.nfk) * a.n_mel) >> 2;
 #pragma unroll
       for (int q = 0; q < SQ; ++q) {
         const int i = tid + q * WV_THREADS;
         st[q] = *(const f32x4 *)(src + 4 * (i < n4 ? i : n4 - 1));
       }
     }
-    float *fx = lds + WT_X, *fwl = lds + WT_WL, *fmag = lds + WT_MAG;
-    short *fxs = (short *)(lds + WT_XS);
-    cplx<RT> *fbuf = (cplx<RT> *)(lds + WT_BUF);
-    ((f32x4 *)fwl)[tid] = wlq;
-    if (tid < 256 && (tid >> 7) == par) ((f32x4 *)fx)[tid & 127] = ringq;
-    if (tid < 40) ((uint4 *)fxs)[tid] = t_raw;
-    if (window)
+    const fe_tick_lds<RT> l = FE_TICK_LDS(RT, lds + WT_BASE);
+    ((f32x4 *)l.wl)[tid] = wlq;
+    if (tid < 256 && (tid >> 7) == c.par) ((f32x4 *)l.x)[tid & 127] = ringq;
+    if (tid < 40) ((uint4 *)l.xs)[tid] = t_raw;
+    if (c.window)
       for (int i = tid; i < WV_T * WV_INLD / 4; i += WV_THREADS) ((float4 *)in_lds)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
-    // ---- [ring | new samples]: normalise, clip, pre-emphasise (the arithmetic of stream_frontend_kernel, streams.hip)
-    for (int i = tid; i < WW_CHUNK; i += WV_THREADS) {
-      float v = __fdiv_rn((float)fxs[i], fe.divisor);
-      if (fe.clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
-      float p;
-      if (i == 0) {
-        p = par ? carry1 : carry0;
-      } else {
-        p = __fdiv_rn((float)fxs[i - 1], fe.divisor);
-        if (fe.clip) p = fminf(fmaxf(p, -1.0f), 1.0f);
-      }
-      fx[fill + i] = (fe.preemph != 0.0f) ? ww_preemph_rn(v, fe.preemph, p) : v;
-    }
-    if (window) {  // (the zero fill is complete: the old rows go in beside the normalisation)
+    // ---- [ring | new samples]: normalise, clip, pre-emphasise
+    for (int i = tid; i < WW_CHUNK; i += WV_THREADS) l.x[c.fill + i] = fe_sample(l.xs, i, c.par ? carry1 : carry0, fe.cv);
+    if (c.window) {  // (the zero fill is complete: the old rows go in beside the normalisation)
 #pragma unroll
       for (int q = 0; q < SQ; ++q) {
         const int i = tid + q * WV_THREADS;
@@ -553,36 +526,23 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
       }
     }
     __syncthreads();
-    if (writer && tid == 0) {
-      float v = __fdiv_rn((float)fxs[WW_CHUNK - 1], fe.divisor);
-      if (fe.clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
-      fe.prev[(size_t)(par ^ 1) * fe.S + s] = v;  // tflite.py:156-158: the carry is the un-emphasised last sample
-    }
+    // tflite.py:156-158: the carry is the un-emphasised last sample
+    if (c.writer && tid == 0) fe.prev[(size_t)(c.par ^ 1) * fe.S + s] = fe_norm(l.xs[WW_CHUNK - 1], fe.cv);
     // ---- new frames: wave f transforms frame f; its mel row goes straight into the staged input (row T - nfk + f) and, from
     // the writer, into the stream's mirrored ring
-    if (wave < nfk) {
-      const float *srcx = fx + wave * fe.hop;
-      auto x2 = [&](int n) -> float2 { return make_float2(srcx[2 * n], srcx[2 * n + 1]); };
-      float *mg = fmag + wave * 260;
-      frame_fft_mag<RT>(x2, fc, fbuf + wave * FFT_LD, mg, lane);
-      const float mv = mel_band(mg, fwl, mel_st, mel_bias, a.floor_v, a.log_off, a.scale, lane);
+    if (wave < c.nfk) {
+      const float mv = fe_frame_mel<RT>(l.x + wave * fe.hop, fc, l.buf, l.mag, wave, l.wl, mel_st, mel_bias, a.fb, lane);
       if (lane < a.n_mel) {
-        in_lds[(T - nfk + wave) * WV_INLD + lane] = mv;
-        if (writer) {
-          int p = pos + wave;  // mirrored ring: the row goes to p % slots and p % slots + slots
-          p = p >= slots ? p - slots : p;
-          float *h = fe.hist + ((size_t)s * fe.HR + p) * a.n_mel + lane;
-          h[0] = mv;
-          h[(size_t)slots * a.n_mel] = mv;
-        }
+        in_lds[(T - c.nfk + wave) * WV_INLD + lane] = mv;
+        if (c.writer) fe_ring_store(fe.hist, (size_t)s * fe.HR, c.pos + wave, slots, a.n_mel, lane, mv);
       }
     }
-    if (writer) {  // keep the ring tail (for the next tick: the other copy)
-      const int keep = fill + WW_CHUNK - nf * fe.hop;
-      float *ring = fe.ring + ((size_t)(par ^ 1) * fe.S + s) * WW_ST_RING;
-      for (int i = tid; i < keep; i += WV_THREADS) ring[i] = fx[nf * fe.hop + i];
+    if (c.writer) {  // keep the ring tail (for the next tick: the other copy)
+      const int keep = c.fill + WW_CHUNK - c.nf * fe.hop;
+      float *ring = fe.ring + ((size_t)(c.par ^ 1) * fe.S + s) * WW_ST_RING;
+      for (int i = tid; i < keep; i += WV_THREADS) ring[i] = l.x[c.nf * fe.hop + i];
     }
-    if (!window) return;  // the tick has no window for this stream: its ring has advanced, that is all
+    if (!c.window) return;  // the tick has no window for this stream: its ring has advanced, that is all
   } else {
     const float *src = a.mel + row * a.n_mel;
     const int n = valid * a.n_mel;
@@ -1513,9 +1473,7 @@ int ww_k_wave_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int pre
   if (int rc = wave_model_args(ctx, v, a)) return rc;
   a.tag = tag;
   a.fe = fe;
-  a.mel_start = f.start; a.mel_wpad = f.wpad; a.mel_bias = f.bias;
-  a.floor_v = f.floor_v; a.log_off = f.log_off; a.scale = f.scale;
-  a.hann = f.hann; a.tw256 = f.tw256; a.tw512 = f.tw512;
+  a.fb = ww_fe_filt_of(f);
   const dim3 grid(2 * fe.S), block(12 * 64);
   ww_launch_scope scope(ctx, m->precision == WW_PRECISION_BF16X3 ? "wavenet_kernel<bf16x3,tick>" : "wavenet_kernel<tick>");
   if (m->precision == WW_PRECISION_BF16X3) {
