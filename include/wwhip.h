@@ -209,6 +209,53 @@ int ww_logmel_dev(ww_ctx *ctx, const ww_model *model, const int16_t *d_pcm, cons
                   const int64_t *d_frame_offs, int32_t n_utt, int64_t total_frames, int64_t max_frames_per_utt,
                   const ww_frontend_params *fp, float *d_mel);
 
+/* ---- sample-rate conversion: audio at any rate -> the models' 16 kHz --------------------------
+ * Stands where the reference's entry points call librosa.load(path, sr=16000) (utils/evaluate_models.py:46,
+ * utils/filter_dataset_to_h5.py:70).  NOT librosa's bits: librosa's filters (soxr_hq, kaiser_best) are third-party code; the
+ * transform here is the float64 statement below (wwhip/resample.py: design), evaluated in fp32.
+ *   g = gcd(rate_in, rate_out), up = rate_out / g, down = rate_in / g, L = rate_in * up
+ *   f2 = rolloff * min(rate_in, rate_out) / L, half = ceil(zeros / f2)
+ *   h[i] = up * f2 * sinc(f2 * i) * kaiser(2 * half + 1, beta)[i + half], i = -half .. half  (np.sinc, np.kaiser, float64)
+ *   y[m] = sum over k with |m * down - k * up| <= half of h[m * down - k * up] * x[k],  m = 0 .. ceil(n * up / down) - 1
+ * which is scipy.signal.resample_poly(x, up, down, window=h / up).  x reads as zero outside its signal; int16 input is scaled
+ * by exactly 1 / 32768.  taps per output = ceil((2 * half + 1) / up).  rate_in == rate_out: no filter, y = x bit for bit.
+ * Arithmetic: y[m] is ONE fp32 fmaf chain from 0 over its input samples in ascending k, taps rounded once from float64 - its
+ * bits depend on m, the filter and the samples of its span only, not on tiles, batch neighbours or how a stream was cut.
+ * params == NULL: zeros 32, rolloff 0.945, beta 14.769656459379492. */
+typedef struct ww_resampler ww_resampler;
+typedef struct ww_resampler_params {
+  double rolloff, beta;
+  int32_t zeros, reserved;
+} ww_resampler_params;
+typedef struct ww_resample_info {
+  int64_t up, down, half, taps_per_output, table_bytes; /* table_bytes: the fp32 tap table on the device */
+} ww_resample_info;
+/* A filter whose table (up * taps per output) exceeds WW_RESAMPLE_MAX_TAPS, or whose tile (2 * down + taps per output + 2
+ * staged samples) exceeds WW_RESAMPLE_MAX_SPAN, is refused with WW_EINVAL: every pair of the standard rates 8, 11.025, 16,
+ * 22.05, 24, 32, 44.1, 48, 88.2, 96, 176.4, 192 kHz passes (largest: 192 kHz <-> 11.025 kHz, 174,080 taps), 44101 -> 16000
+ * (2.99 M taps) does not.  Rates <= 0: WW_EINVAL. */
+#define WW_RESAMPLE_MAX_TAPS (1 << 20)
+#define WW_RESAMPLE_MAX_SPAN 12288
+#define WW_SAMPLE_I16 0
+#define WW_SAMPLE_F32 1
+int ww_resampler_create(ww_ctx *ctx, int32_t rate_in, int32_t rate_out, const ww_resampler_params *params, ww_resampler **out);
+int ww_resampler_destroy(ww_resampler *r);
+int ww_resampler_info(const ww_resampler *r, ww_resample_info *out);
+/* Output ranges of n_seg segments in one launch.  Segment u holds samples [sample_offs[u], sample_offs[u + 1]) of `in`
+ * (WW_SAMPLE_I16 or WW_SAMPLE_F32), which are samples in_first[u] .. of its own signal; outputs out_first[u] .. of that signal,
+ * out_offs[u + 1] - out_offs[u] of them, go to out[out_offs[u] .. out_offs[u + 1]) as WW_SAMPLE_F32, or as WW_SAMPLE_I16 =
+ * clip(rint(y * 32768), -32768, 32767).  Samples outside a segment read as zero.  in_first / out_first == NULL: all zero (a
+ * one-shot clip: count = ceil(n * up / down)).  A long signal in pieces, or a stream in packets: give each piece
+ * ceil(half / up) samples of history in front of the first sample its outputs need - the pieces are the one-shot's bits.
+ * All offset arrays are HOST arrays, consumed before the call returns.  WW_EINVAL (nothing is written): n_seg < 0, NULL where
+ * data is needed, an unknown format, negative or descending offsets, an output range beyond ceil((in_first + n) * up / down).
+ * n_seg = 0 and empty segments are WW_OK and write nothing.  ww_resample takes host pointers and returns with the result in
+ * `out`; ww_resample_dev takes device pointers, enqueues on the context's stream and does not synchronise. */
+int ww_resample(ww_resampler *r, const void *in, int32_t in_format, const int64_t *sample_offs, const int64_t *in_first,
+                const int64_t *out_first, const int64_t *out_offs, int32_t n_seg, void *out, int32_t out_format);
+int ww_resample_dev(ww_resampler *r, const void *d_in, int32_t in_format, const int64_t *sample_offs, const int64_t *in_first,
+                    const int64_t *out_first, const int64_t *out_offs, int32_t n_seg, void *d_out, int32_t out_format);
+
 /* ---- encode + detect -------------------------------------------------------------------
  * Replaces encode_model(x) followed by detect_model(x) (two TFLiteModel.__call__,
  * spokestack/wakeword/tflite.py:193-231; utils/evaluate_models.py:76-86;

@@ -36,6 +36,8 @@ def parse_args():
     p.add_argument("--sample_rate", type=int, default=16000, help="Sample rate for audio (Hz)")
     p.add_argument("--frame_width", type=int, default=20, help="Frame width for audio in (ms)")
     p.add_argument("--examine_audio", default=False, action="store_true", help="Flag to examine problematic audio clips")
+    p.add_argument("--resample", default=False, action="store_true",
+                   help="convert wavs at another rate to --sample_rate on the GPU (wwhip.resample) instead of refusing them")
     p.add_argument("--plot", default=False, action="store_true", help="draw the three curves with matplotlib")
     args = p.parse_args()
     assert Path(args.models_dir).exists(), "Directory for TF-Lite models and results is not found!"
@@ -60,13 +62,18 @@ def main(args) -> int:
     num_wakewords = len(wakeword_paths)
     if rank == 0 and not FAR_path.exists():
         os.makedirs(args.eval_dir, exist_ok=True)
-        E.concatenate_FA(not_wakeword_paths, num_wakewords, str(FAR_path), args.sample_rate)
+        E.concatenate_FA(not_wakeword_paths, num_wakewords, str(FAR_path), args.sample_rate, resample=args.resample)
     if dist is not None:
         dist.barrier()
     total_duration_hrs = E.duration_test(str(FAR_path), args.sample_rate) / 3600
+    loader, lengths = None, None
+    if args.resample:  # the reference's librosa.load(path, sr=16000): any rate in, 16 kHz out (lengths from the headers)
+        from wwhip import resample as R
+        loader = lambda p: R.load(p, sr=args.sample_rate, device=dev)  # noqa: E731
+        lengths = [E.wav_length(str(f), args.sample_rate, resample=True) for f in wakeword_paths]
     pos = E.load_posteriors(args.models_dir, args.model_type, args.frame_width, args.sample_rate, "false_negatives",
                             wakeword_paths, Path(os.path.join(args.models_dir, args.model_type + "_all_wakeword.pkl")),
-                            args.examine_audio, rank, world, comm_dev, dev)
+                            args.examine_audio, rank, world, comm_dev, dev, loader=loader, lengths=lengths)
     neg = E.load_posteriors(args.models_dir, args.model_type, args.frame_width, args.sample_rate, "false_accepts",
                             [str(FAR_path)], Path(os.path.join(args.models_dir, args.model_type + "_no_wakeword.pkl")),
                             args.examine_audio, rank, world, comm_dev, dev)

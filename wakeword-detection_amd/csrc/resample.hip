@@ -1,0 +1,473 @@
+// Rational-ratio polyphase windowed-sinc resampler (include/wwhip.h: ww_resample*): audio at any rate -> the models' 16 kHz.
+//
+//   y[m] = sum_k h[m * down - k * up] * x[k],  |m * down - k * up| <= half
+//
+// Arithmetic rule (as for the models): an output is ONE fmaf chain from +0 over its input samples in ascending k,
+// every tap rounded once from float64.  Taps outside the filter are stored as +0 and samples outside the segment are staged as
+// +0: fmaf(0, x, acc) and fmaf(h, 0, acc) leave acc as it is, so padding a chain changes no bit, and neither does the choice of
+// kernel form, tile, launch or packet cut.
+//
+// Two forms, both with a tile's input span staged once in LDS as fp32 (int16 converted there):
+//   up == 1 (48, 32, 96 kHz -> 16 kHz: every output has the same taps): a lane owns RS_R1 consecutive outputs and walks its input
+//     window once - each staged sample is read from LDS once and feeds all RS_R1 chains; the RS_R1 taps that go with window
+//     position u are one row of a host-built table [n_u][8], a wave-uniform address (scalar loads).
+//   any up (44.1, 22.05, 11.025, 8 kHz ...): outputs are grouped by phase.  Item e = A * up + p owns the R outputs
+//     m = (A * R + r) * up + q(p), r < R, which share phase p = m * down mod up: one tap load feeds R chains.  Lanes are
+//     consecutive in p, and the table is tap-major [tpp][up], so a wave's tap load is one coalesced row segment.  R = 8 for long
+//     output ranges, R = 1 for short ones (a stream's packets), where R * up outputs per item would mostly be idle.
+#include "common.h"
+
+#include <algorithm>
+#include <cmath>
+
+#define RS_THREADS 256
+#define RS_XCAP WW_RESAMPLE_MAX_SPAN  // floats of staged input per tile (48 KB: three workgroups per CU)
+#define RS_R 8                        // outputs per item, phase form
+#define RS_R1 7                       // outputs per lane, up == 1 form: odd, so that the lane stride RS_R1 * down keeps odd `down` conflict-free
+#define RS_UNROLL1 4                  // window positions per unrolled step of the up == 1 form (the table is padded to it)
+#define RS_COPY 4096                  // outputs per tile of the identity form
+
+struct rs_tile {
+  int64_t in_off;     // index in the input buffer of the segment's first sample
+  int64_t in_first;   // absolute index of that sample in its signal
+  int64_t n_in;       // samples of the segment
+  int64_t out_off;    // index in the output buffer of output out_first
+  int64_t out_first;  // absolute index of the segment's first output
+  int64_t out_end;    // one past its last
+  int64_t k_lo;       // absolute index of staged sample 0
+  int64_t first;      // phase form: first item; up == 1 and identity forms: first output
+  int32_t n_x;        // staged samples (<= RS_XCAP)
+  int32_t n;          // phase form: items; up == 1 form: lanes; identity form: outputs
+};
+
+struct ww_resampler {
+  ww_ctx *ctx = nullptr;
+  int32_t rate_in = 0, rate_out = 0;
+  int64_t up = 1, down = 1, half = 0, tpp = 0, dinv = 0;
+  bool identity = false;
+  float *d_taps = nullptr;  // [tpp][up] tap-major
+  float *d_h2 = nullptr;    // up == 1: [n_u][8], row u = the taps of outputs r = 0 .. RS_R1 - 1 at window position u
+  int32_t n_u = 0;          // rows of d_h2 (a multiple of RS_UNROLL1)
+  int32_t lanes1 = 0;       // up == 1 form: lanes per tile (0: the form does not fit, the phase form runs)
+  int32_t ne8 = 0, ne1 = 0; // phase form: items per tile for R = 8 (0: does not fit) and R = 1
+  size_t table_bytes = 0;
+};
+
+__device__ __forceinline__ float rs_load(int16_t v) { return (float)v * (1.0f / 32768.0f); }  // exact: a power of two
+__device__ __forceinline__ float rs_load(float v) { return v; }
+__device__ __forceinline__ void rs_store(float *p, float v) { *p = v; }
+__device__ __forceinline__ void rs_store(int16_t *p, float v) {
+  v = rintf(v * 32768.0f);
+  v = fminf(fmaxf(v, -32768.0f), 32767.0f);
+  *p = (int16_t)(int)v;
+}
+
+template <typename TIn>
+__device__ __forceinline__ void rs_stage(float *xs, const TIn *__restrict__ in, const rs_tile &t) {
+  const TIn *seg = in + t.in_off;
+  const int64_t d = t.k_lo - t.in_first;  // segment index of staged sample 0
+  for (int i = threadIdx.x; i < t.n_x; i += RS_THREADS) {
+    const int64_t j = d + i;
+    float v = 0.0f;
+    if (j >= 0 && j < t.n_in) v = rs_load(seg[j]);
+    xs[i] = v;
+  }
+}
+
+template <typename TIn, typename TOut>
+__global__ __launch_bounds__(RS_THREADS) void resample_copy_kernel(const TIn *__restrict__ in, TOut *__restrict__ out,
+                                                                   const rs_tile *__restrict__ tiles) {
+  const rs_tile t = tiles[blockIdx.x];
+  for (int i = threadIdx.x; i < t.n; i += RS_THREADS) {
+    const int64_t m = t.first + i, j = m - t.in_first;
+    float v = 0.0f;
+    if (j >= 0 && j < t.n_in) v = rs_load(in[t.in_off + j]);
+    rs_store(out + t.out_off + (m - t.out_first), v);
+  }
+}
+
+template <typename TIn, typename TOut>
+__global__ __launch_bounds__(RS_THREADS) void resample_decim_kernel(const TIn *__restrict__ in, TOut *__restrict__ out,
+                                                                    const rs_tile *__restrict__ tiles, const float *__restrict__ h2,
+                                                                    int down, int n_u) {
+  __shared__ float xs[RS_XCAP];
+  const rs_tile t = tiles[blockIdx.x];
+  rs_stage(xs, in, t);
+  __syncthreads();
+  if ((int)threadIdx.x >= t.n) return;
+  const float *x0 = xs + (int)threadIdx.x * RS_R1 * down;  // t.k_lo = t.first * down - half: this lane's window position 0
+  float acc[RS_R1];
+#pragma unroll
+  for (int r = 0; r < RS_R1; ++r) acc[r] = 0.0f;
+  for (int u = 0; u < n_u; u += RS_UNROLL1) {
+#pragma unroll
+    for (int v = 0; v < RS_UNROLL1; ++v) {
+      const float xv = x0[u + v];
+      const float *hh = h2 + (size_t)(u + v) * 8;  // the same address in every lane
+#pragma unroll
+      for (int r = 0; r < RS_R1; ++r) acc[r] = fmaf(hh[r], xv, acc[r]);
+    }
+  }
+  const int64_t m0 = t.first + (int64_t)threadIdx.x * RS_R1;
+#pragma unroll
+  for (int r = 0; r < RS_R1; ++r)
+    if (m0 + r < t.out_end) rs_store(out + t.out_off + (m0 + r - t.out_first), acc[r]);
+}
+
+template <int R, typename TIn, typename TOut>
+__global__ __launch_bounds__(RS_THREADS) void resample_phase_kernel(const TIn *__restrict__ in, TOut *__restrict__ out,
+                                                                    const rs_tile *__restrict__ tiles, const float *__restrict__ taps,
+                                                                    int up, int down, int half, int tpp, int dinv) {
+  __shared__ float xs[RS_XCAP];
+  const rs_tile t = tiles[blockIdx.x];
+  rs_stage(xs, in, t);
+  __syncthreads();
+  if ((int)threadIdx.x >= t.n) return;
+  const int64_t e = t.first + threadIdx.x;
+  const int64_t A = e / up;
+  const int p = (int)(e - A * up);                     // phase: m * down mod up of every output of this item
+  const int q = (int)(((int64_t)p * dinv) % up);       // m mod up
+  const int cq = (int)(((int64_t)q * down) / up);      // floor(m * down / up) = (m / up) * down + cq
+  const int jmax = (half - p) / up;                    // tap 0 is h[p + jmax * up], the largest index <= half of the phase
+  const float *x0 = xs + (int)(A * R * down + cq - jmax - t.k_lo);  // sample of tap 0 of output r = 0
+  const float *tp = taps + p;
+  float acc[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r] = 0.0f;
+#pragma unroll 8
+  for (int tt = 0; tt < tpp; ++tt) {
+    const float h = tp[(size_t)tt * up];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = fmaf(h, x0[r * down + tt], acc[r]);
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int64_t m = (A * R + r) * up + q;
+    if (m >= t.out_first && m < t.out_end) rs_store(out + t.out_off + (m - t.out_first), acc[r]);
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+static double rs_i0(double x) {  // modified Bessel function I0 by its power series (every term positive: no cancellation)
+  const double q = 0.25 * x * x;
+  double term = 1.0, sum = 1.0;
+  for (int k = 1; k < 500; ++k) {
+    term *= q / ((double)k * (double)k);
+    sum += term;
+    if (term < sum * 1e-18) break;
+  }
+  return sum;
+}
+
+static int64_t rs_gcd(int64_t a, int64_t b) {
+  while (b) {
+    const int64_t t = a % b;
+    a = b;
+    b = t;
+  }
+  return a;
+}
+
+static int64_t rs_inverse(int64_t a, int64_t n) {  // a^-1 mod n, gcd(a, n) = 1
+  int64_t t = 0, nt = 1, r = n, nr = a % n;
+  while (nr) {
+    const int64_t qq = r / nr, t2 = t - qq * nt, r2 = r - qq * nr;
+    t = nt; nt = t2; r = nr; nr = r2;
+  }
+  return t < 0 ? t + n : t;
+}
+
+static int64_t rs_out_len(const ww_resampler *r, int64_t n) {  // ceil(n * up / down)
+  return (int64_t)(((__int128)n * r->up + r->down - 1) / r->down);
+}
+
+// worst-case staged samples of a phase-form tile of ne items
+static int64_t rs_phase_span(const ww_resampler *r, int R, int64_t ne) {
+  const int64_t nA = (ne - 1) / r->up + 2;
+  return nA * R * r->down + r->tpp + 2;
+}
+
+template <typename K, typename... Args>
+static void rs_launch(ww_ctx *ctx, const char *name, K kernel, size_t n_tiles, Args... args) {
+  ww_launch_scope scope(ctx, name);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_tiles), dim3(RS_THREADS), 0, ctx->stream, args...);
+}
+
+struct rs_plan {
+  std::vector<rs_tile> copy, decim, ph8, ph1;
+  size_t count() const { return copy.size() + decim.size() + ph8.size() + ph1.size(); }
+};
+
+static void rs_plan_phase(const ww_resampler *r, int R, int64_t ne, rs_tile base, std::vector<rs_tile> &dst) {
+  const int64_t up = r->up, down = r->down, J = r->half / up, Jmin = (r->half - up + 1) / up;
+  const int64_t e_lo = ((base.out_first / up) / R) * up, e_hi = (((base.out_end - 1) / up) / R + 1) * up;
+  for (int64_t e0 = e_lo; e0 < e_hi; e0 += ne) {
+    const int64_t n = std::min(ne, e_hi - e0), A0 = e0 / up, A1 = (e0 + n - 1) / up;
+    rs_tile t = base;
+    t.first = e0;
+    t.n = (int32_t)n;
+    t.k_lo = A0 * R * down - J;
+    t.n_x = (int32_t)((A1 * R + R - 1) * down + (down - 1) - Jmin + r->tpp - t.k_lo);
+    dst.push_back(t);
+  }
+}
+
+static int rs_make_plan(const ww_resampler *r, const int64_t *so, const int64_t *in_first, const int64_t *out_first, const int64_t *oo,
+                        int n_seg, rs_plan &pl) {
+  for (int u = 0; u < n_seg; ++u) {
+    const int64_t cnt = oo[u + 1] - oo[u];
+    if (cnt <= 0) continue;
+    rs_tile b = {};
+    b.in_off = so[u];
+    b.in_first = in_first ? in_first[u] : 0;
+    b.n_in = so[u + 1] - so[u];
+    b.out_off = oo[u];
+    b.out_first = out_first ? out_first[u] : 0;
+    b.out_end = b.out_first + cnt;
+    if (r->identity) {
+      for (int64_t m = b.out_first; m < b.out_end; m += RS_COPY) {
+        rs_tile t = b;
+        t.first = m;
+        t.n = (int32_t)std::min<int64_t>(RS_COPY, b.out_end - m);
+        pl.copy.push_back(t);
+      }
+    } else if (r->up == 1 && r->lanes1 > 0) {
+      const int64_t per = (int64_t)r->lanes1 * RS_R1;
+      for (int64_t m = b.out_first; m < b.out_end; m += per) {
+        rs_tile t = b;
+        t.first = m;
+        t.n = (int32_t)std::min<int64_t>(r->lanes1, (b.out_end - m + RS_R1 - 1) / RS_R1);
+        t.k_lo = m * r->down - r->half;
+        t.n_x = (int32_t)((int64_t)(t.n - 1) * RS_R1 * r->down + r->n_u);
+        pl.decim.push_back(t);
+      }
+    } else if (r->ne8 > 0 && cnt >= 2 * RS_R * r->up) {
+      rs_plan_phase(r, RS_R, r->ne8, b, pl.ph8);
+    } else {
+      rs_plan_phase(r, 1, r->ne1, b, pl.ph1);
+    }
+  }
+  return WW_OK;
+}
+
+static int rs_validate(const ww_resampler *r, const void *in, int in_fmt, const int64_t *so, const int64_t *in_first, const int64_t *out_first,
+                       const int64_t *oo, int n_seg, const void *out, int out_fmt, int64_t *n_out_total) {
+  ww_ctx *ctx = r->ctx;
+  *n_out_total = 0;
+  if (n_seg < 0) return ww_fail(ctx, WW_EINVAL, "ww_resample: n_seg = %d", n_seg);
+  if ((in_fmt != WW_SAMPLE_I16 && in_fmt != WW_SAMPLE_F32) || (out_fmt != WW_SAMPLE_I16 && out_fmt != WW_SAMPLE_F32))
+    return ww_fail(ctx, WW_EINVAL, "ww_resample: sample formats are WW_SAMPLE_I16 and WW_SAMPLE_F32");
+  if (n_seg == 0) return WW_OK;
+  if (!so || !oo) return ww_fail(ctx, WW_EINVAL, "ww_resample: NULL offset table");
+  if (so[0] < 0 || oo[0] < 0) return ww_fail(ctx, WW_EINVAL, "ww_resample: negative offset");
+  for (int u = 0; u < n_seg; ++u) {
+    if (so[u + 1] < so[u] || oo[u + 1] < oo[u]) return ww_fail(ctx, WW_EINVAL, "ww_resample: descending offsets at segment %d", u);
+    const int64_t i0 = in_first ? in_first[u] : 0, o0 = out_first ? out_first[u] : 0;
+    if (i0 < 0 || o0 < 0) return ww_fail(ctx, WW_EINVAL, "ww_resample: negative in_first / out_first at segment %d", u);
+    const int64_t cnt = oo[u + 1] - oo[u], lim = rs_out_len(r, i0 + (so[u + 1] - so[u]));
+    if (cnt > 0 && o0 + cnt > lim)
+      return ww_fail(ctx, WW_EINVAL, "ww_resample: segment %d asks for outputs [%lld, %lld) of a signal that has %lld", u, (long long)o0,
+                     (long long)(o0 + cnt), (long long)lim);
+  }
+  *n_out_total = oo[n_seg] - oo[0];
+  if (*n_out_total > 0 && !out) return ww_fail(ctx, WW_EINVAL, "ww_resample: NULL output buffer");
+  if (*n_out_total > 0 && so[n_seg] > so[0] && !in) return ww_fail(ctx, WW_EINVAL, "ww_resample: NULL input buffer");
+  return WW_OK;
+}
+
+template <typename TIn, typename TOut>
+static void rs_launch_all(const ww_resampler *r, const rs_plan &pl, const rs_tile *d_tiles, const TIn *d_in, TOut *d_out) {
+  ww_ctx *ctx = r->ctx;
+  const rs_tile *d = d_tiles;
+  if (!pl.copy.empty()) rs_launch(ctx, "resample_copy_kernel", resample_copy_kernel<TIn, TOut>, pl.copy.size(), d_in, d_out, d);
+  d += pl.copy.size();
+  if (!pl.decim.empty())
+    rs_launch(ctx, "resample_decim_kernel", resample_decim_kernel<TIn, TOut>, pl.decim.size(), d_in, d_out, d, (const float *)r->d_h2, (int)r->down,
+              (int)r->n_u);
+  d += pl.decim.size();
+  if (!pl.ph8.empty())
+    rs_launch(ctx, "resample_phase_kernel<8>", resample_phase_kernel<RS_R, TIn, TOut>, pl.ph8.size(), d_in, d_out, d, (const float *)r->d_taps,
+              (int)r->up, (int)r->down, (int)r->half, (int)r->tpp, (int)r->dinv);
+  d += pl.ph8.size();
+  if (!pl.ph1.empty())
+    rs_launch(ctx, "resample_phase_kernel<1>", resample_phase_kernel<1, TIn, TOut>, pl.ph1.size(), d_in, d_out, d, (const float *)r->d_taps,
+              (int)r->up, (int)r->down, (int)r->half, (int)r->tpp, (int)r->dinv);
+}
+
+// the tile table leaves through one of the context's two page-locked descriptor buffers (as ww_k_crnn_segments_forward's): the
+// copy is asynchronous and the call returns while its kernels run
+static int rs_run(const ww_resampler *r, const rs_plan &pl, rs_tile *d_tiles, const void *d_in, int in_fmt, void *d_out, int out_fmt) {
+  ww_ctx *ctx = r->ctx;
+  const int slot = (int)(ctx->desc_k++ & 1);
+  if (!ctx->desc_ev[slot]) WW_HIP(ctx, hipEventCreateWithFlags(&ctx->desc_ev[slot], hipEventDisableTiming));
+  if (ctx->desc_busy[slot]) {
+    WW_HIP(ctx, hipEventSynchronize(ctx->desc_ev[slot]));
+    ctx->desc_busy[slot] = false;
+  }
+  const size_t bytes = pl.count() * sizeof(rs_tile);
+  if (int rc = ww_ensure(ctx, ctx->desc_pin[slot], bytes, true)) return rc;
+  char *hp = (char *)ctx->desc_pin[slot].ptr;
+  size_t off = 0;
+  for (const std::vector<rs_tile> *v : {&pl.copy, &pl.decim, &pl.ph8, &pl.ph1}) {
+    if (!v->empty()) memcpy(hp + off, v->data(), v->size() * sizeof(rs_tile));
+    off += v->size() * sizeof(rs_tile);
+  }
+  WW_HIP(ctx, hipMemcpyAsync(d_tiles, hp, bytes, hipMemcpyHostToDevice, ctx->stream));
+  WW_HIP(ctx, hipEventRecord(ctx->desc_ev[slot], ctx->stream));
+  ctx->desc_busy[slot] = true;
+  if (in_fmt == WW_SAMPLE_I16 && out_fmt == WW_SAMPLE_F32) rs_launch_all(r, pl, d_tiles, (const int16_t *)d_in, (float *)d_out);
+  else if (in_fmt == WW_SAMPLE_F32 && out_fmt == WW_SAMPLE_F32) rs_launch_all(r, pl, d_tiles, (const float *)d_in, (float *)d_out);
+  else if (in_fmt == WW_SAMPLE_I16) rs_launch_all(r, pl, d_tiles, (const int16_t *)d_in, (int16_t *)d_out);
+  else rs_launch_all(r, pl, d_tiles, (const float *)d_in, (int16_t *)d_out);
+  WW_HIP(ctx, hipGetLastError());
+  return WW_OK;
+}
+
+extern "C" {
+
+int ww_resampler_destroy(ww_resampler *r) {
+  WW_GUARD_BEGIN
+  if (!r) return WW_OK;
+  ww_device_scope dev_scope(r->ctx->device);
+  hipStreamSynchronize(r->ctx->stream);
+  if (r->d_taps) hipFree(r->d_taps);
+  if (r->d_h2) hipFree(r->d_h2);
+  delete r;
+  return WW_OK;
+  WW_GUARD_END(nullptr)
+}
+
+int ww_resampler_create(ww_ctx *ctx, int32_t rate_in, int32_t rate_out, const ww_resampler_params *params, ww_resampler **out) {
+  WW_GUARD_BEGIN
+  if (!ctx || !out) return ww_fail(ctx, WW_EINVAL, "ww_resampler_create: NULL argument");
+  *out = nullptr;
+  if (rate_in <= 0 || rate_out <= 0) return ww_fail(ctx, WW_EINVAL, "ww_resampler_create: rates must be positive (%d -> %d)", rate_in, rate_out);
+  const double rolloff = params ? params->rolloff : 0.945, beta = params ? params->beta : 14.769656459379492;
+  const int zeros = params ? params->zeros : 32;
+  if (zeros < 1 || !(rolloff > 0.0 && rolloff <= 1.0) || !(beta >= 0.0) || !(beta < 100.0))
+    return ww_fail(ctx, WW_EINVAL, "ww_resampler_create: zeros >= 1, 0 < rolloff <= 1 and 0 <= beta < 100 are needed");
+  WW_ON_DEVICE(ctx, dev);
+  ww_resampler *r = new ww_resampler();
+  ww_scoped<ww_resampler, ww_resampler_destroy> own(r);
+  r->ctx = ctx;
+  r->rate_in = rate_in;
+  r->rate_out = rate_out;
+  const int64_t g = rs_gcd(rate_in, rate_out);
+  const int64_t up = r->up = rate_out / g, down = r->down = rate_in / g;
+  if (up == 1 && down == 1) {
+    r->identity = true;
+    *out = own.release();
+    return WW_OK;
+  }
+  const double L = (double)((int64_t)rate_in * up);
+  const double f2 = rolloff * (double)std::min(rate_in, rate_out) / L;
+  const double halfd = std::ceil((double)zeros / f2);
+  const double tapsd = std::ceil((2.0 * halfd + 1.0) / (double)up) * (double)up;
+  if (!(tapsd <= (double)WW_RESAMPLE_MAX_TAPS))
+    return ww_fail(ctx, WW_EINVAL, "ww_resampler_create: %d -> %d needs a table of %.0f taps; WW_RESAMPLE_MAX_TAPS is %d", rate_in, rate_out, tapsd,
+                   WW_RESAMPLE_MAX_TAPS);
+  const int64_t half = r->half = (int64_t)halfd, tpp = r->tpp = (2 * half + 1 + up - 1) / up;
+  if (2 * down + tpp + 2 > RS_XCAP)
+    return ww_fail(ctx, WW_EINVAL, "ww_resampler_create: %d -> %d needs a tile of %lld staged samples; WW_RESAMPLE_MAX_SPAN is %d", rate_in, rate_out,
+                   (long long)(2 * down + tpp + 2), RS_XCAP);
+  std::vector<double> h((size_t)(2 * half + 1));
+  const double i0b = rs_i0(beta), pi = 3.14159265358979323846;
+  for (int64_t i = -half; i <= half; ++i) {
+    const double a = (double)i / (double)half, w = rs_i0(beta * std::sqrt(std::max(0.0, 1.0 - a * a))) / i0b;
+    const double y = pi * (f2 * (double)i), s = i == 0 ? 1.0 : std::sin(y) / y;
+    h[(size_t)(i + half)] = (double)up * f2 * s * w;
+  }
+  std::vector<float> tab((size_t)(tpp * up));
+  for (int64_t p = 0; p < up; ++p) {
+    const int64_t jmax = (half - p) / up;
+    for (int64_t tt = 0; tt < tpp; ++tt) {
+      const int64_t idx = half + p + (jmax - tt) * up;
+      tab[(size_t)(tt * up + p)] = idx >= 0 ? (float)h[(size_t)idx] : 0.0f;
+    }
+  }
+  WW_HIP(ctx, hipMalloc((void **)&r->d_taps, tab.size() * 4));
+  WW_HIP(ctx, hipMemcpy(r->d_taps, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  r->table_bytes = tab.size() * 4;
+  r->dinv = up > 1 ? rs_inverse(down % up, up) : 0;
+  for (int64_t ne = RS_THREADS; ne >= 64 && !r->ne8; ne /= 2)
+    if (rs_phase_span(r, RS_R, ne) <= RS_XCAP) r->ne8 = (int32_t)ne;
+  for (int64_t ne = RS_THREADS; ne >= 1 && !r->ne1; ne /= 2)
+    if (rs_phase_span(r, 1, ne) <= RS_XCAP) r->ne1 = (int32_t)ne;
+  if (up == 1) {
+    const int64_t n_u = (RS_R1 - 1) * down + 2 * half + 1, n_u_pad = (n_u + RS_UNROLL1 - 1) / RS_UNROLL1 * RS_UNROLL1;
+    const int64_t lanes = std::min<int64_t>(RS_THREADS, (RS_XCAP - n_u_pad) / (RS_R1 * down) + 1);
+    if (n_u_pad <= RS_XCAP && lanes >= 1) {
+      std::vector<float> h2((size_t)n_u_pad * 8, 0.0f);
+      for (int64_t u = 0; u < n_u; ++u)
+        for (int64_t rr = 0; rr < RS_R1; ++rr) {
+          const int64_t idx = rr * down + 2 * half - u;
+          if (idx >= 0 && idx <= 2 * half) h2[(size_t)(u * 8 + rr)] = (float)h[(size_t)idx];
+        }
+      WW_HIP(ctx, hipMalloc((void **)&r->d_h2, h2.size() * 4));
+      WW_HIP(ctx, hipMemcpy(r->d_h2, h2.data(), h2.size() * 4, hipMemcpyHostToDevice));
+      r->n_u = (int32_t)n_u_pad;
+      r->lanes1 = (int32_t)lanes;
+    }
+  }
+  *out = own.release();
+  return WW_OK;
+  WW_GUARD_END(ctx)
+}
+
+int ww_resampler_info(const ww_resampler *r, ww_resample_info *out) {
+  WW_GUARD_BEGIN
+  if (!r || !out) return ww_fail(r ? r->ctx : nullptr, WW_EINVAL, "ww_resampler_info: NULL argument");
+  out->up = r->up;
+  out->down = r->down;
+  out->half = r->half;
+  out->taps_per_output = r->tpp;
+  out->table_bytes = (int64_t)r->table_bytes;
+  return WW_OK;
+  WW_GUARD_END(r ? r->ctx : nullptr)
+}
+
+int ww_resample_dev(ww_resampler *r, const void *d_in, int32_t in_format, const int64_t *sample_offs, const int64_t *in_first,
+                    const int64_t *out_first, const int64_t *out_offs, int32_t n_seg, void *d_out, int32_t out_format) {
+  WW_GUARD_BEGIN
+  if (!r) return ww_fail(nullptr, WW_EINVAL, "ww_resample_dev: NULL resampler");
+  ww_ctx *ctx = r->ctx;
+  int64_t n_out = 0;
+  if (int rc = rs_validate(r, d_in, in_format, sample_offs, in_first, out_first, out_offs, n_seg, d_out, out_format, &n_out)) return rc;
+  if (n_out == 0) return WW_OK;
+  WW_ON_DEVICE(ctx, dev);
+  rs_plan pl;
+  rs_make_plan(r, sample_offs, in_first, out_first, out_offs, n_seg, pl);
+  if (int rc = ww_ensure(ctx, ctx->dev, pl.count() * sizeof(rs_tile) + 1024, false)) return rc;
+  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
+  return rs_run(r, pl, bump.take<rs_tile>(pl.count()), d_in, in_format, d_out, out_format);
+  WW_GUARD_END(r ? r->ctx : nullptr)
+}
+
+int ww_resample(ww_resampler *r, const void *in, int32_t in_format, const int64_t *sample_offs, const int64_t *in_first,
+                const int64_t *out_first, const int64_t *out_offs, int32_t n_seg, void *out, int32_t out_format) {
+  WW_GUARD_BEGIN
+  if (!r) return ww_fail(nullptr, WW_EINVAL, "ww_resample: NULL resampler");
+  ww_ctx *ctx = r->ctx;
+  int64_t n_out = 0;
+  if (int rc = rs_validate(r, in, in_format, sample_offs, in_first, out_first, out_offs, n_seg, out, out_format, &n_out)) return rc;
+  if (n_out == 0) return WW_OK;
+  WW_ON_DEVICE(ctx, dev);
+  rs_plan pl;
+  rs_make_plan(r, sample_offs, in_first, out_first, out_offs, n_seg, pl);
+  const size_t ie = in_format == WW_SAMPLE_I16 ? 2 : 4, oe = out_format == WW_SAMPLE_I16 ? 2 : 4;
+  const int64_t s0 = sample_offs[0], n_in = sample_offs[n_seg] - s0, o0 = out_offs[0];
+  if (int rc = ww_ensure(ctx, ctx->dev, ww_bump::need((size_t)n_in, ie) + ww_bump::need((size_t)n_out, oe) + ww_bump::need(pl.count(), sizeof(rs_tile)) + 1024, false))
+    return rc;
+  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
+  char *d_in = bump.take<char>((size_t)n_in * ie), *d_out = bump.take<char>((size_t)n_out * oe);
+  rs_tile *d_tiles = bump.take<rs_tile>(pl.count());
+  if (n_in > 0) WW_HIP(ctx, hipMemcpyAsync(d_in, (const char *)in + s0 * ie, (size_t)n_in * ie, hipMemcpyHostToDevice, ctx->stream));
+  // the kernels index the buffers by the caller's offsets: shift the bases instead of the tables
+  if (int rc = rs_run(r, pl, d_tiles, d_in - s0 * (int64_t)ie, in_format, d_out - o0 * (int64_t)oe, out_format)) return rc;
+  WW_HIP(ctx, hipMemcpyAsync((char *)out + o0 * oe, d_out, (size_t)n_out * oe, hipMemcpyDeviceToHost, ctx->stream));
+  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return WW_OK;
+  WW_GUARD_END(r ? r->ctx : nullptr)
+}
+
+}  // extern "C"

@@ -24,6 +24,7 @@ KIND_CRNN, KIND_WAVENET = 1, 2
 PRECISION_FP32, PRECISION_BF16X3 = 0, 1
 OPT_CRNN_SPLIT_AT, OPT_CRNN_SLIDE_MIN, OPT_CRNN_TAIL_MFMA, OPT_WAVENET_ROWMAJOR, OPT_WAVE_SEQ_SEGMENT = 1, 2, 3, 4, 5
 STREAM_FULL_RECOMPUTE, STREAM_TWO_LAUNCH, STREAM_SYNC_WAIT, STREAM_CAUSAL = 1, 2, 4, 8
+SAMPLE_I16, SAMPLE_F32 = 0, 1
 ABI = 4  # include/wwhip.h: WW_ABI - the signatures this binding was written against
 
 
@@ -38,6 +39,14 @@ class PipelineState(C.Structure):
                                            "n_post", "timeout_was_speech", "active_frames", "fired_ids", "fall_ids", "deact_ids")]
                 + [(n, C.c_double) for n in ("threshold", "min_frames", "max_frames")]
                 + [(n, C.c_int32) for n in ("rise_frames", "fall_frames", "n_vad_changed", "n_fired", "n_fall", "n_deact")])
+
+
+class ResamplerParams(C.Structure):
+    _fields_ = [("rolloff", C.c_double), ("beta", C.c_double), ("zeros", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ResampleInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("up", "down", "half", "taps_per_output", "table_bytes")]
 
 
 class FrontendParams(C.Structure):
@@ -78,6 +87,11 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_filter_apply": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "ww_detect": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
     "ww_logmel_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _P(FrontendParams), _vp]),
+    "ww_resampler_create": (C.c_int, [_vp, _i32, _i32, _vp, _P(_vp)]),
+    "ww_resampler_destroy": (C.c_int, [_vp]),
+    "ww_resampler_info": (C.c_int, [_vp, _vp]),
+    "ww_resample": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32]),
+    "ww_resample_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32]),
     "ww_forward": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
     "ww_forward_enc": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp]),
     "ww_slide_forward": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _P(_i64)]),
@@ -114,7 +128,7 @@ _lock = threading.Lock()
 import atexit
 import weakref
 
-_live = {"uploaders": weakref.WeakSet(), "streams": weakref.WeakSet(), "models": weakref.WeakSet(), "contexts": weakref.WeakSet()}
+_live = {"uploaders": weakref.WeakSet(), "resamplers": weakref.WeakSet(), "streams": weakref.WeakSet(), "models": weakref.WeakSet(), "contexts": weakref.WeakSet()}
 _shutdown = False
 
 
@@ -128,7 +142,7 @@ def is_shutdown() -> bool:
 
 def _close_all() -> None:
     global _shutdown
-    for kind in ("uploaders", "streams", "models", "contexts"):
+    for kind in ("uploaders", "resamplers", "streams", "models", "contexts"):
         for obj in list(_live[kind]):
             try:
                 obj.close()

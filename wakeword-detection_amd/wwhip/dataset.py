@@ -79,7 +79,7 @@ class DatasetFilter:
 
     def __init__(self, dataset: str, models_dir: str, data_dir: str, out_dir: str, sample_rate: int = 16000,
                  frame_width: int = 20, hop_width: int = 10, vad: Optional[Callable[[bytes, int], bool]] = None,
-                 loader: Optional[Callable[[str], np.ndarray]] = None, device: int = 0, **kwargs: Any) -> None:
+                 loader: Optional[Callable[[str], np.ndarray]] = None, device: int = 0, resample: bool = False, **kwargs: Any) -> None:
         self.dataset = dataset
         with open(dataset, "r") as f:
             self.audio_metadata = json.load(f)
@@ -93,7 +93,7 @@ class DatasetFilter:
         os.makedirs(out_dir, exist_ok=True)
         self.dataset_file = os.path.join(out_dir, os.path.basename(dataset).replace(".json", ".h5"))
         self.vad = vad
-        self.load = loader or (lambda p: read_wav(p, self.sr))
+        self.load = loader or (lambda p: read_wav(p, self.sr, resample))  # resample: files at another rate are converted (wwhip.resample)
 
     def map_speakers(self) -> Dict[Any, int]:
         speakers = []

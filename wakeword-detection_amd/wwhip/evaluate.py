@@ -56,12 +56,16 @@ class _Phases:
         return scope()
 
 
-def read_wav(path: str, sample_rate: int = 16000) -> np.ndarray:
+def read_wav(path: str, sample_rate: int = 16000, resample: bool = False) -> np.ndarray:
     """PCM16 mono wav -> float32 in [-1, 1) exactly as ``librosa.load(path, sr=sample_rate)``
-    returns it when no resampling is needed (int16 / 32768)."""
+    returns it when no resampling is needed (int16 / 32768).  ``resample=True``: a file at another rate is converted on the
+    GPU (:func:`wwhip.resample.load` - this project's filter, not librosa's) instead of refused."""
     with wave.open(path, "rb") as w:
         if w.getsampwidth() != 2:
             raise ValueError(f"{path}: only 16-bit PCM is supported")
+        if w.getframerate() != sample_rate and resample:
+            from .resample import load
+            return load(path, sr=sample_rate)
         if w.getframerate() != sample_rate:
             raise ValueError(f"{path}: sample rate {w.getframerate()} != {sample_rate} (no resampler here)")
         raw = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16)
@@ -141,20 +145,24 @@ def get_posterior(models_dir, model_type, eval_type, test_files, frame_width, sa
 # The same flow, sharded over ranks: utterance-sharded for the positives, ONE long
 # negative stream cut into contiguous posterior ranges for the false accepts.
 # ----------------------------------------------------------------------------------------------
-def wav_length(path: str, sample_rate: int = 16000) -> int:
-    """Samples ``read_wav(path)`` would return, from the header alone."""
+def wav_length(path: str, sample_rate: int = 16000, resample: bool = False) -> int:
+    """Samples ``read_wav(path)`` would return, from the header alone (``resample=True``: ``ceil(n * up / down)`` for a file
+    at another rate)."""
     with wave.open(path, "rb") as w:
+        if w.getframerate() != sample_rate and resample:
+            from .resample import out_len, ratio
+            return out_len(w.getnframes(), *ratio(w.getframerate(), sample_rate))
         if w.getframerate() != sample_rate:
             raise ValueError(f"{path}: sample rate {w.getframerate()} != {sample_rate} (no resampler here)")
         return w.getnframes()
 
 
-def read_wav_pcm(path: str, sample_rate: int = 16000) -> np.ndarray:
+def read_wav_pcm(path: str, sample_rate: int = 16000, resample: bool = False) -> np.ndarray:
     """Mono PCM16 wav as int16 (``librosa.load`` = these / 32768); anything else as :func:`read_wav`'s float32."""
     with wave.open(path, "rb") as w:
         if w.getsampwidth() == 2 and w.getnchannels() == 1 and w.getframerate() == sample_rate:
             return np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16)
-    return read_wav(path, sample_rate)
+    return read_wav(path, sample_rate, resample)
 
 
 class StreamPlan:
@@ -1286,16 +1294,21 @@ def testset_files(base_path: str):
     return wake, other
 
 
-def concatenate_FA(wav_paths: Sequence[str], num_files: int, FAR_path: str, sample_rate: int = 16000) -> None:
+def concatenate_FA(wav_paths: Sequence[str], num_files: int, FAR_path: str, sample_rate: int = 16000, resample: bool = False) -> None:
     """One long negative wav: the first ``num_files`` clips joined by 100 ms of silence (``:150-160``;
-    the reference uses pydub, here the PCM16 payloads are concatenated directly)."""
+    the reference uses pydub, here the PCM16 payloads are concatenated directly).  ``resample=True``: mono clips at another
+    rate are converted to ``sample_rate`` (int16 output of :class:`wwhip.resample.Resampler`) before they are joined."""
     gap = np.zeros(sample_rate // 10, np.int16)
     parts: List[np.ndarray] = []
     for i, path in enumerate(wav_paths[:max(num_files, 1)]):
         with wave.open(path, "rb") as w:
-            if w.getsampwidth() != 2 or w.getnchannels() != 1 or w.getframerate() != sample_rate:
+            rate = w.getframerate()
+            if w.getsampwidth() != 2 or w.getnchannels() != 1 or (rate != sample_rate and not resample):
                 raise ValueError(f"{path}: expected mono PCM16 at {sample_rate} Hz")
             pcm = np.frombuffer(w.readframes(w.getnframes()), np.int16)
+        if rate != sample_rate:
+            from .resample import _cached
+            pcm = _cached(rate, sample_rate)(pcm, np.int16)
         if i:
             parts.append(gap)
         parts.append(pcm)
@@ -1312,7 +1325,8 @@ def duration_test(FAR_path: str, sample_rate: int) -> float:
 
 
 def load_posteriors(models_dir, model_type, frame_width, sample_rate, eval_type, input_path, out_path, examine_audio=False,
-                    rank: int = 0, world: int = 1, comm_device: Optional[str] = None, device: int = 0):
+                    rank: int = 0, world: int = 1, comm_device: Optional[str] = None, device: int = 0,
+                    loader: Optional[Callable[[str], np.ndarray]] = None, lengths: Optional[Sequence[int]] = None):
     """Pickle-cached posteriors (``:163-175``), computed by :func:`get_posterior_sharded` (``world`` = 1: one GPU, the
     same windows as :func:`get_posterior`); with ``world > 1`` every rank computes its share and rank 0 writes the cache."""
     import os
@@ -1322,7 +1336,7 @@ def load_posteriors(models_dir, model_type, frame_width, sample_rate, eval_type,
             posteriors = pickle.load(f)
     else:
         posteriors = get_posterior_sharded(models_dir, model_type, eval_type, input_path, frame_width, sample_rate, rank,
-                                           world, comm_device, device=device)
+                                           world, comm_device, loader=loader, lengths=lengths, device=device)
         if rank == 0:
             with open(str(out_path), "wb") as f:
                 pickle.dump(posteriors, f)

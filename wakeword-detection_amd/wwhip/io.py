@@ -1,6 +1,7 @@
 """Audio input stages with the surface of ``spokestack/io/pyaudio.py`` (``read() -> int16 frame``, ``start``,
 ``stop``, ``close``).  PyAudio and a microphone are not part of the hot path; :class:`WavInput` feeds a pipeline
-from a 16 kHz mono PCM16 wav file (or an array) and stops it at the end of the data."""
+from a 16 kHz mono PCM16 wav file (or an array) and stops it at the end of the data.  With ``resample=True`` a file at another
+rate is converted once, when it is opened (:class:`wwhip.resample.Resampler`, int16 output)."""
 from __future__ import annotations
 
 import wave
@@ -10,12 +11,18 @@ import numpy as np
 
 
 class WavInput:
-    def __init__(self, source: Union[str, np.ndarray], sample_rate: int = 16000, frame_width: int = 20) -> None:
+    def __init__(self, source: Union[str, np.ndarray], sample_rate: int = 16000, frame_width: int = 20, resample: bool = False) -> None:
         if isinstance(source, str):
             with wave.open(source, "rb") as w:
-                if w.getframerate() != sample_rate or w.getsampwidth() != 2 or w.getnchannels() != 1:
+                rate = w.getframerate()
+                if (rate != sample_rate and not resample) or w.getsampwidth() != 2 or w.getnchannels() != 1:
                     raise ValueError(f"{source}: expected mono PCM16 at {sample_rate} Hz")
                 self._pcm = np.frombuffer(w.readframes(w.getnframes()), np.int16)
+            if rate != sample_rate:
+                from .resample import Resampler
+                rs = Resampler(rate, sample_rate)
+                self._pcm = rs(self._pcm, np.int16)
+                rs.close()
         else:
             self._pcm = np.ascontiguousarray(source, dtype=np.int16)
         self._n = sample_rate // 1000 * frame_width
