@@ -1093,6 +1093,79 @@ def test_forward_segments_dev_matches_explicit_windows(engines, oracles, name):
         e.forward_segments_dev(d_mel.data_ptr(), len(mel), np.array([len(mel) - 10], np.int64), np.array([3], np.int32), 2, d_out.data_ptr())
 
 
+def test_crnn_unaligned_mel_pointer_gives_the_same_bits(assets, engines, oracles):
+    """ww_forward_windows_dev and ww_forward_segments_dev take ANY device pointer as the mel buffer.  The CRNN kernels stage the
+    window through stage_loads, which loads 16 bytes at a time from a 16-byte aligned first row and 4 x 4 bytes otherwise: the
+    same mel at float offsets 1 and 2 of a buffer (4 and 8 bytes off) gives the bits of the aligned copy (offset 4) - explicit
+    windows of full, partial, one-row and no validity, one ending on the buffer's last row, through crnn_fused_kernel (fp32 and
+    bf16x3, one-kernel and front + tail form); sequences by descriptors through crnn_rows_kernel.  The aligned fp32 result is
+    anchored to the oracle on the same windows zero-padded on the host."""
+    import torch
+    from wwhip.engine import Engine
+    e = engines["CRNN"]
+    T, rows, nw = e.window, 400, 40
+    rng = np.random.default_rng(211)
+    mel = rng.uniform(0, 6.5, (rows, 40)).astype(np.float32)
+    win_row = rng.integers(0, rows - T + 1, nw).astype(np.int64)
+    win_valid = np.full(nw, T, np.int32)
+    win_valid[1], win_valid[2], win_valid[3] = 100, 1, 0
+    win_valid[9:20] = rng.integers(1, T, 11)
+    win_row[4] = rows - T        # a full window that ends on the buffer's last row
+    win_row[5], win_valid[5] = rows - 100, 100  # and a partial one
+    assert win_valid[0] == T and (win_row + win_valid <= rows).all()
+    buf = torch.zeros(rows * 40 + 4, dtype=torch.float32, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    d_row, d_valid = torch.from_numpy(win_row).cuda(), torch.from_numpy(win_valid).cuda()
+
+    def place(off):
+        buf.zero_()
+        buf[off:off + rows * 40] = torch.from_numpy(mel.ravel()).cuda()
+        torch.cuda.synchronize()
+        return buf.data_ptr() + 4 * off
+
+    def windows(eng, off):
+        d_out = torch.zeros((nw, eng.n_out), dtype=torch.float32, device="cuda")
+        d_mel = place(off)
+        eng.forward_windows_dev(d_mel, rows, d_row.data_ptr(), d_valid.data_ptr(), nw, d_out.data_ptr())
+        eng.ctx.synchronize()
+        return d_out.cpu().numpy()
+
+    def segments(eng, off, hop):
+        seg_nw = np.array([17, 1, 40], np.int32)
+        seg_row0 = np.array([3, 200, rows - (39 * hop + T)], np.int64)  # (the sequences may overlap; the last ends on the last row)
+        d_out = torch.zeros((int(seg_nw.sum()), eng.n_out), dtype=torch.float32, device="cuda")
+        d_mel = place(off)
+        eng.forward_segments_dev(d_mel, rows, seg_row0, seg_nw, hop, d_out.data_ptr())
+        eng.ctx.synchronize()
+        return d_out.cpu().numpy()
+
+    bf = Engine(os.path.join(assets, "CRNN"), precision="bf16x3")
+    try:
+        for eng in (e, bf):
+            for split_at in (None, 16):   # default: crnn_fused_kernel<false>; 40 > 16 windows: crnn_fused_kernel<true> + tail
+                def run(off):
+                    if split_at is None:
+                        return windows(eng, off)
+                    with eng.options(crnn_split_at=split_at):
+                        return windows(eng, off)
+                aligned = run(4)
+                if eng is e and split_at is None:
+                    wins = np.zeros((nw, T, 40), np.float32)
+                    for k in range(nw):
+                        wins[k, :win_valid[k]] = mel[win_row[k]:win_row[k] + win_valid[k]]
+                    err = float(np.abs(aligned - oracles["CRNN"].forward(wins)).max())
+                    print(f"aligned fp32 explicit windows: max|gpu-oracle| = {err:.3e}")
+                    assert err < TOL_POST
+                for off in (1, 2):
+                    np.testing.assert_array_equal(run(off), aligned, err_msg=f"precision {eng is bf and 'bf16x3' or 'fp32'} split_at {split_at} offset {off}")
+        for hop in (2, 3):
+            aligned = segments(e, 4, hop)
+            for off in (1, 2):
+                np.testing.assert_array_equal(segments(e, off, hop), aligned, err_msg=f"segments hop {hop} offset {off}")
+    finally:
+        bf.close()
+
+
 def test_two_host_threads_through_the_c_abi(assets, oracles):
     """include/wwhip.h: "one ww_ctx per host thread".  Two Python threads (ctypes releases the GIL inside every call, so
     the library really runs concurrently), each with its OWN context, model and stream bank - one CRNN, one Wavenet -

@@ -14,6 +14,7 @@
 // Round 1's three-kernel chain (conv5x20_kernel -> gemm_nt_kernel -> gru_head_kernel, 52 us per 256 windows against
 // 34 us fused) and its bf16x6 projection GEMM are gone; their measurements are in DESIGN.md 7.1.
 #include "stream_fe.h"
+#include <algorithm>
 #include <type_traits>
 
 #include <cstdlib>
@@ -45,6 +46,25 @@ __device__ __forceinline__ void window_span(const win_addr &wa, int w, int T, in
 }
 
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// The detect head's activation for output o of a window: sigmoid (HEAD == 0), or softmax over the NOUT <= 8 outputs, which sit in
+// eight adjacent lanes (o = lane % 8; lanes with o >= NOUT take part in the exchanges and return nothing of use).  Every lane of
+// the wave calls it.
+__device__ __forceinline__ float head_activation(float y, int o, int NOUT, int HEAD) {
+  if (HEAD == 0) return sigmoid_f(y);
+  float mx = (o < NOUT) ? y : -INFINITY;
+  for (int d = 1; d < 8; d <<= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
+  const float e = (o < NOUT) ? expf(y - mx) : 0.f;
+  float sum = e;
+  for (int d = 1; d < 8; d <<= 1) sum += __shfl_xor(sum, d);
+  return e / sum;
+}
+
+// LDS clear by a workgroup of threads_ (thread tid): n4_ x 16 bytes from p_ (the window image).  This and CLEAR_SEQ_H are
+// macros because as functions the unrolled loops came out with other exit branches in every kernel that uses them
+// (profiles/EXPERIMENTS.md 13).
+#define LDS_CLEAR16(p_, n4_, threads_) \
+  for (int i = tid; i < (n4_); i += (threads_)) ((float4 *)(p_))[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 
 // Four mel features at p (zeros unless `in`).  Whether the window's first row is 16-byte aligned is uniform over a workgroup,
 // so the staging loops branch on it ONCE, outside (stage_loads below): with the 16-byte and the 4 x 4-byte form behind one
@@ -307,6 +327,131 @@ __device__ __forceinline__ void wsync_g() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// In front of the recurrences: `rows` rows of seq1 (the layer-2 projection reads zeros past row 18) and the states
+// h[layer 2][dir 2][ping-pong 2][32] start from zero
+#define CLEAR_SEQ_H(seq1_, rows_, hb_, threads_)                                      \
+  for (int i = tid; i < (rows_) * GR_SEQ_LD; i += (threads_)) (seq1_)[i] = 0.f;       \
+  for (int i = tid; i < 2 * 2 * 2 * GR_H; i += (threads_)) (hb_)[i] = 0.f;
+
+// ------------------------------------------------------------------------------------------
+// The fp32 conv as crnn_fused_kernel, crnn_stream_kernel and crnn_rows_kernel run it: an implicit GEMM on v_mfma_f32_16x16x4_f32,
+// m-tiles of 16 (position, frequency) rows x 32 channels, K = 100 taps padded to 7 k-blocks of 16.  One definition of each piece;
+// lane (j, kk) = (lane & 15, lane >> 4) are names of the kernel.  The loads are macros, not functions: as __forceinline__
+// functions that take the pointer as a parameter they lost their scalar base (global_load_dwordx4 v, v, s[2:3] became
+// v_lshl_add_u64 + a load from a 64-bit vector address: profiles/EXPERIMENTS.md 13).
+// ------------------------------------------------------------------------------------------
+// this lane's conv weights (B operand: [112/4][32][4]) and the biases of its two channels
+#define CV_LOAD_W(wreg_, cb0_, cb1_, w4_, cbias_)                                                    \
+  _Pragma("unroll") for (int kb = 0; kb < CV_KB; ++kb)                                               \
+    _Pragma("unroll") for (int n = 0; n < 2; ++n)                                                    \
+      wreg_[kb][n] = *(const float4 *)((w4_) + ((size_t)(kb * 4 + kk) * 32 + n * 16 + j) * 4);       \
+  cb0_ = (cbias_)[j];                                                                                \
+  cb1_ = (cbias_)[16 + j];
+// the A operands of one m-tile: abase_ = this lane's row (position, frequency) in the transposed image
+#define CV_LOAD_A(av_, abase_)                                                                       \
+  _Pragma("unroll") for (int kb = 0; kb < CV_KB; ++kb) {                                             \
+    const int k4 = kb * 16 + kk * 4;                                                                 \
+    const int kf = k4 / CV_KT, kt = k4 - kf * CV_KT;                                                 \
+    av_[kb] = *(const float4 *)((abase_) + kf * CV_LDT + kt);                                        \
+  }
+// one k-block: 16 taps x 32 channels onto acc0 (channels 0..15) and acc1 (16..31)
+#define CV_MFMA_KB(av_, kb_)                                                                         \
+  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].x, wreg[kb_][0].x, acc0, 0, 0, 0);             \
+  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].x, wreg[kb_][1].x, acc1, 0, 0, 0);             \
+  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].y, wreg[kb_][0].y, acc0, 0, 0, 0);             \
+  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].y, wreg[kb_][1].y, acc1, 0, 0, 0);             \
+  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].z, wreg[kb_][0].z, acc0, 0, 0, 0);             \
+  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].z, wreg[kb_][1].z, acc1, 0, 0, 0);             \
+  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].w, wreg[kb_][0].w, acc0, 0, 0, 0);             \
+  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].w, wreg[kb_][1].w, acc1, 0, 0, 0);
+// NT_ m-tiles per wave, software-pipelined by hand: the next tile's A operands are read while this tile's MFMAs run, and what
+// the caller does with the previous tile's sums prev0 / prev1 (the statements after NT_: ReLU + store, or keep them) sits in the
+// middle of them.  Vector instructions between fp32 MFMAs cost matrix time, so the loop holds none it can avoid: operand and
+// store offsets are the caller's, computed during the staging, the bias is the accumulators' initial value.  The caller has
+// load_a(av, i), wreg, cb0, cb1 and f32x4 prev0, prev1, which are the last tile's sums afterwards.  (As a function template
+// with the middle as a callable, crnn_rows_kernel kept its instructions and crnn_fused_kernel did not: EXPERIMENTS 13.)
+#define CV_TILE_LOOP(NT_, ...)                                                                       \
+  {                                                                                                  \
+    float4 av[2][CV_KB];                                                                             \
+    load_a(av[0], 0);                                                                                \
+    _Pragma("unroll") for (int i = 0; i < NT_; ++i) {                                                \
+      if (i + 1 < NT_) load_a(av[(i + 1) & 1], i + 1);                                               \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+      f32x4 acc0 = {cb0, cb0, cb0, cb0}, acc1 = {cb1, cb1, cb1, cb1};                                \
+      CV_MFMA_KB(av[i & 1], 0) CV_MFMA_KB(av[i & 1], 1) CV_MFMA_KB(av[i & 1], 2)                     \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+      __VA_ARGS__                                                                                    \
+      __builtin_amdgcn_sched_barrier(0);                                                             \
+      CV_MFMA_KB(av[i & 1], 3) CV_MFMA_KB(av[i & 1], 4) CV_MFMA_KB(av[i & 1], 5) CV_MFMA_KB(av[i & 1], 6) \
+      prev0 = acc0;                                                                                  \
+      prev1 = acc1;                                                                                  \
+    }                                                                                                \
+  }
+
+// ------------------------------------------------------------------------------------------
+// The layer-1 input projection gx1 = feat x W_x1^T (K = 640 = 40 k-steps of 16, N = 192: three n-tiles of 16 columns per wave)
+// as the same three kernels run it.  W_x1 streams from L2 straight into registers in B-operand order ([k/4][192][4], one
+// contiguous KB per wave load) through a ring bq[DEPTH][3] that is DEPTH - 1 k-steps ahead of its use; the A operands come from
+// LDS one k-step ahead (avq: the 16-row tile on v_mfma_f32_16x16x4_f32, rvq: the 3-row tile on v_mfma_f32_4x4x1_16b_f32).
+// ------------------------------------------------------------------------------------------
+// this lane's W_x1 operand of k-step 0, n-tile 0, and the one of k-step ks, n-tile n from there
+// (raw buffer loads with a scalar k-step offset would take the 64-bit pointer adds off the vector ALU, but this compiler
+//  lowers __builtin_amdgcn_raw_buffer_load_b128 to a one-dword load on gfx950: not used)
+__device__ __forceinline__ const float *pj_w_base(const float *wx1s, int kk, int wave, int j) {
+  return wx1s + ((size_t)kk * 192 + wave * 48 + j) * 4;
+}
+__device__ __forceinline__ float4 pj_w_ld(const float *wb, int ks, int n) {
+  constexpr size_t KS_STRIDE = (size_t)4 * 192 * 4;
+  return *(const float4 *)(wb + ks * KS_STRIDE + n * 64);
+}
+// the ring's first DEPTH_ - 1 k-steps: requested in front of the barrier that completes feat (it does not wait for them)
+#define PJ_RING_PROLOGUE(DEPTH_)                                                                     \
+  _Pragma("unroll") for (int s2 = 0; s2 < DEPTH_ - 1; ++s2)                                          \
+    _Pragma("unroll") for (int n = 0; n < 3; ++n) bq[s2][n] = pj_w_ld(wb, s2, n);
+// the biases of this lane's three columns: requested in front of the k-loop, added when the products are complete
+#define PJ_LOAD_BIAS(bv1_, bx1_)                                                                     \
+  _Pragma("unroll") for (int n = 0; n < 3; ++n) bv1_[n] = (bx1_)[wave * 48 + n * 16 + j];
+// one operand element e_ of a k-step on the row groups a kernel has; consecutive MFMAs go to different accumulators
+// (dependent-accumulator latency 40 > issue 32).  The order of the MFMAs in a round and of the k-steps is the association of
+// every sum of gx1.
+#define PJ_ROWS16(e_)                                                                                \
+  acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(avq[ks & 1].e_, b[0].e_, acc[0], 0, 0, 0);            \
+  acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(avq[ks & 1].e_, b[1].e_, acc[1], 0, 0, 0);            \
+  acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(avq[ks & 1].e_, b[2].e_, acc[2], 0, 0, 0);
+#define PJ_ROWS3(e_)                                                                                 \
+  rem[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(rvq[ks & 1].e_, b[0].e_, rem[0], 0, 0, 0);              \
+  rem[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(rvq[ks & 1].e_, b[1].e_, rem[1], 0, 0, 0);              \
+  rem[2] = __builtin_amdgcn_mfma_f32_4x4x1f32(rvq[ks & 1].e_, b[2].e_, rem[2], 0, 0, 0);
+#define PJ_NO_ROWS(e_)
+// The k-loop, fully unrolled so that the ring slots are plain registers (a rotating copy would have to wait for the load it
+// copies).  G16_ / G3_: PJ_ROWS16 / PJ_ROWS3 or PJ_NO_ROWS; the statements behind them load the next k-step's A operands
+// (avq / rvq[(ks + 1) & 1]).  The prefetches stay in front of the sched_barrier: sunk to just before their use, the LDS reads
+// cost ~130 cycles per k-step.
+#define PJ_KLOOP(DEPTH_, G16_, G3_, ...)                                                             \
+  _Pragma("unroll") for (int ks = 0; ks < 40; ++ks) {                                                \
+    if (ks + DEPTH_ - 1 < 40) {                                                                      \
+      _Pragma("unroll") for (int n = 0; n < 3; ++n) bq[(ks + DEPTH_ - 1) % DEPTH_][n] = pj_w_ld(wb, ks + DEPTH_ - 1, n); \
+    }                                                                                                \
+    if (ks + 1 < 40) { __VA_ARGS__ }                                                                 \
+    __builtin_amdgcn_sched_barrier(0);                                                               \
+    const float4 *b = bq[ks % DEPTH_];                                                               \
+    G16_(x) G3_(x) G16_(y) G3_(y) G16_(z) G3_(z) G16_(w) G3_(w)                                      \
+    __builtin_amdgcn_sched_barrier(0);                                                               \
+  }
+// The 3-row tile's epilogue for one column: the four k sub-steps of a column sit in lanes col, col + 16, col + 32, col + 48 and
+// meet in two cross-lane adds; in lane group kk == 0 the statements behind bv_ store row i's value v (bias added).  (As a
+// function template with the stores as a callable it moved crnn_stream_kernel's epilogue: EXPERIMENTS 13.)
+#define PJ_REM_ROWS(rem_, bv_, ...)                                                                  \
+  _Pragma("unroll") for (int i = 0; i < 3; ++i) {                                                    \
+    float s3 = rem_[i];                                                                              \
+    s3 += __shfl_xor(s3, 16);                                                                        \
+    s3 += __shfl_xor(s3, 32);                                                                        \
+    if (kk == 0) {                                                                                   \
+      const float v = s3 + bv_;                                                                      \
+      __VA_ARGS__                                                                                    \
+    }                                                                                                \
+  }
+
 // ------------------------------------------------------------------------------------------
 // crnn_fused_kernel: the whole CRNN for one window in one 4-wave workgroup - the conv output (feat, 48.6 KB per
 // window) and the layer-1 input projections (gx1, 14.6 KB) never leave the CU.
@@ -419,18 +564,9 @@ __device__ __forceinline__ float cf_recurrence(const gru_w &g, const float *gxs,
   return h_own;
 }
 
-// one operand quad of the 16 + 3 row product: 3 n-tiles x (16x16x4 on rows 0..15, 4x4x1 on rows 16..18); consecutive
-// MFMAs go to different accumulators (dependent-accumulator latency 40 > issue 32)
-#define CF_ROUND(av_, rv_, b_, e_)                                                                     \
-  acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.e_, b_[0].e_, acc[0], 0, 0, 0);                     \
-  acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.e_, b_[1].e_, acc[1], 0, 0, 0);                     \
-  acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.e_, b_[2].e_, acc[2], 0, 0, 0);                     \
-  rem[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(rv_.e_, b_[0].e_, rem[0], 0, 0, 0);                       \
-  rem[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(rv_.e_, b_[1].e_, rem[1], 0, 0, 0);                       \
-  rem[2] = __builtin_amdgcn_mfma_f32_4x4x1f32(rv_.e_, b_[2].e_, rem[2], 0, 0, 0);
-
-// the layer-2 projection's form of it: rows 16..18 on a second 16x16x4 tile (its other thirteen rows read zeros), so that ALL
-// nineteen rows are one fmaf chain in the same k order - the association gru_tail16_kernel reproduces step by step
+// one operand quad of the layer-2 projection: 3 n-tiles x (rows 0..15, rows 16..18), both on 16x16x4 tiles - unlike layer 1's
+// PJ_ROWS3, rows 16..18 are a second full tile (its other thirteen rows read zeros), so that ALL nineteen rows are one fmaf
+// chain in the same k order - the association gru_tail16_kernel reproduces step by step
 #define CF_ROUND_L2(av_, rv_, b_, e_)                                                                  \
   acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.e_, b_[0].e_, acc[0], 0, 0, 0);                     \
   acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.e_, b_[1].e_, acc[1], 0, 0, 0);                     \
@@ -438,6 +574,44 @@ __device__ __forceinline__ float cf_recurrence(const gru_w &g, const float *gxs,
   rem[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(rv_.e_, b_[0].e_, rem[0], 0, 0, 0);                     \
   rem[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(rv_.e_, b_[1].e_, rem[1], 0, 0, 0);                     \
   rem[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(rv_.e_, b_[2].e_, rem[2], 0, 0, 0);
+
+// Phase E, the layer-2 input projection gx2[t][n] = seq1[t][:] . Wx2[n][:] + bx2[n]  (19 rows, K = 64, N = 192), for the three
+// n-tiles nt0 .. nt0 + 2 of a wave: rows 0..15 as one MFMA tile, rows 16..18 as a second one whose lane j reads row rrow of
+// seq1 - the caller's choice of a row that is 16 + j for j < 3 and all zeros otherwise.  Every row is the same fmaf chain from
+// zero: k = 16 kb + 4 kk + e in the order kb, e, kk, the bias added last.  cf_phases_d_to_g (4 waves x 3 n-tiles, operands
+// requested before the recurrence) and gru_tail_kernel (2 waves x 2 passes x 3 n-tiles) run it.
+// (Macros: as functions they moved instructions in six kernels, profiles/EXPERIMENTS.md 13.  seq1, gxs, j and kk are the
+// kernel's names.)
+// W_x2 in B-operand order [64/4][192][4]: 12 x 16 bytes per lane, L2
+#define L2_LOAD_W(bq_, wx2s_, nt0_)                                                                  \
+  _Pragma("unroll") for (int kb = 0; kb < 4; ++kb)                                                   \
+    _Pragma("unroll") for (int n = 0; n < 3; ++n)                                                    \
+      bq_[kb][n] = *(const float4 *)((wx2s_) + ((size_t)(kb * 4 + kk) * 192 + ((nt0_) + n) * 16 + j) * 4);
+// the biases: requested in front of the products they are added to (asked for where they are used, each of the three was a
+// round trip to L2 of its own at the end of the phase)
+#define L2_LOAD_BIAS(bb_, bx2_, nt0_) \
+  _Pragma("unroll") for (int n = 0; n < 3; ++n) bb_[n] = (bx2_)[((nt0_) + n) * 16 + j];
+// the products; the statements behind nt0_ (gru_tail_kernel's barrier: gx2 takes gx1's place); the stores of the 19 rows
+#define L2_PROJECT(bq_, bb_, rrow_, nt0_, ...)                                                       \
+  {                                                                                                  \
+    f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};               \
+    f32x4 rem[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};               \
+    _Pragma("unroll") for (int kb = 0; kb < 4; ++kb) {                                               \
+      const float4 av = *(const float4 *)(&seq1[j * GR_SEQ_LD + kb * 16 + kk * 4]);                  \
+      const float4 rv = *(const float4 *)(&seq1[(rrow_) * GR_SEQ_LD + kb * 16 + kk * 4]);            \
+      const float4 *b = bq_[kb];                                                                     \
+      CF_ROUND_L2(av, rv, b, x) CF_ROUND_L2(av, rv, b, y) CF_ROUND_L2(av, rv, b, z) CF_ROUND_L2(av, rv, b, w) \
+    }                                                                                                \
+    __VA_ARGS__                                                                                      \
+    _Pragma("unroll") for (int n = 0; n < 3; ++n) {                                                  \
+      const int col = ((nt0_) + n) * 16 + j;                                                         \
+      const float bb = bb_[n];                                                                       \
+      _Pragma("unroll") for (int r = 0; r < 4; ++r) gxs[(kk * 4 + r) * GR_GX_LD + col] = acc[n][r] + bb; \
+      if (kk == 0) {                                                                                 \
+        _Pragma("unroll") for (int r = 0; r < 3; ++r) gxs[(16 + r) * GR_GX_LD + col] = rem[n][r] + bb; \
+      }                                                                                              \
+    }                                                                                                \
+  }
 
 // Phases D..G of the fused kernels (fp32 and split-bf16 front halves share them): gx1 is in LDS, g holds this wave's
 // recurrent weights (waves 0, 1: layer 1; waves 2, 3: layer 2).
@@ -451,10 +625,7 @@ __device__ __forceinline__ void cf_phases_d_to_g(const fused_args &a, float *img
   //      B-operand order, 12 x 16 bytes per lane, L2): they arrive during the recurrence, and phase E reads nothing but
   //      its A operand from LDS (W_x2 used to be staged through the feat space by waves 2, 3; phase E 4.3 k -> 4.0 k cycles for 1.9 k of MFMAs)
   float4 bq2[4][3];
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int n = 0; n < 3; ++n) bq2[kb][n] = *(const float4 *)(a.wx2s + ((size_t)(kb * 4 + kk) * 192 + (wave * 3 + n) * 16 + j) * 4);
+  L2_LOAD_W(bq2, a.wx2s, wave * 3)
   if (wave < 2) {
     __builtin_amdgcn_s_setprio(3);  // the serial chain issues ahead of a co-resident workgroup's MFMA stream (+1.5 % at scale)
     cf_recurrence<true>(g, gxs, hb + dir * 2 * H, seq1, dir, unit, half);
@@ -462,36 +633,12 @@ __device__ __forceinline__ void cf_phases_d_to_g(const fused_args &a, float *img
   }
   __syncthreads();
 
-  // ---- E: layer-2 input projection gx2[t][n] = seq1[t][:] . Wx2[n][:] + bx2[n]  (19 rows, K = 64, N = 192): rows 0..15 as one
-  //      MFMA tile, rows 16..18 as a second one (rows 19..31 of seq1 are zeros), 3 n-tiles per wave; every row is the same
-  //      fmaf chain from zero: k = 16 kb + 4 kk + e in the order kb, e, kk, the bias added last
+  // ---- E: layer-2 input projection (L2_PROJECT), 3 n-tiles per wave; rows 19..31 of seq1 are zeros
   {
-    f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    f32x4 rem[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    // the biases: requested in front of the products they are added to (asked for where they are used, each of the three
-    // was a round trip to L2 of its own at the end of the phase)
     float bb2[3];
-#pragma unroll
-    for (int n = 0; n < 3; ++n) bb2[n] = a.bx2[(wave * 3 + n) * 16 + j];
+    L2_LOAD_BIAS(bb2, a.bx2, wave * 3)
     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-      const float4 av = *(const float4 *)(&seq1[j * GR_SEQ_LD + kb * 16 + kk * 4]);
-      const float4 rv = *(const float4 *)(&seq1[(16 + j) * GR_SEQ_LD + kb * 16 + kk * 4]);
-      const float4 *b = bq2[kb];
-      CF_ROUND_L2(av, rv, b, x) CF_ROUND_L2(av, rv, b, y) CF_ROUND_L2(av, rv, b, z) CF_ROUND_L2(av, rv, b, w)
-    }
-#pragma unroll
-    for (int n = 0; n < 3; ++n) {
-      const int col = (wave * 3 + n) * 16 + j;
-      const float bb = bb2[n];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) gxs[(kk * 4 + r) * GR_GX_LD + col] = acc[n][r] + bb;
-      if (kk == 0) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r) gxs[(16 + r) * GR_GX_LD + col] = rem[n][r] + bb;
-      }
-    }
+    L2_PROJECT(bq2, bb2, 16 + j, wave * 3, )
   }
   __syncthreads();
 
@@ -525,17 +672,7 @@ __device__ __forceinline__ void cf_phases_d_to_g(const fused_args &a, float *img
       for (int k = 0; k < 2 * H; ++k) y = fmaf(w2s[lane * 64 + k], hid[k], y);
       y += b2v;
     }
-    float p;
-    if (a.HEAD == 0) {
-      p = sigmoid_f(y);
-    } else {
-      float mx = (lane < a.NOUT) ? y : -INFINITY;
-      for (int o = 1; o < 8; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-      float e = (lane < a.NOUT) ? expf(y - mx) : 0.f;
-      float sum = e;
-      for (int o = 1; o < 8; o <<= 1) sum += __shfl_xor(sum, o);
-      p = e / sum;
-    }
+    const float p = head_activation(y, lane, a.NOUT, a.HEAD);
     if (a.tag.slots) {
       if (lane == a.tag.pidx) tick_tag_store(a.tag, w, p);
     } else if (lane < a.NOUT) {
@@ -563,11 +700,8 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a)
 
   // conv weights for this lane (B operand of mfma 16x16x4: lane (j, kk)); issued first, used after the staging
   float4 wreg[CV_KB][2];
-#pragma unroll
-  for (int kb = 0; kb < CV_KB; ++kb)
-#pragma unroll
-    for (int n = 0; n < 2; ++n) wreg[kb][n] = *(const float4 *)(a.w4 + ((size_t)(kb * 4 + kk) * 32 + n * 16 + j) * 4);
-  const float cb0 = a.cbias[j], cb1 = a.cbias[16 + j];
+  float cb0, cb1;
+  CV_LOAD_W(wreg, cb0, cb1, a.w4, a.cbias)
 
   // ---- A: stage the window (loads first, then zero the image, then the transposed scatter)
   int a_off[6], o_off[6][4];
@@ -588,7 +722,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a)
           stage[q] = ld_mel4<AL>(src + (i < n ? i : n - 4), true);
         }
       });
-    for (int i = tid; i < CF_IMG_FLOATS / 4; i += CF_THREADS) ((float4 *)img)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    LDS_CLEAR16(img, CF_IMG_FLOATS / 4, CF_THREADS)
     // while the window is on its way: LDS offsets of this lane's conv operands and results for its six m-tiles
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -626,26 +760,11 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a)
   }
   __syncthreads();
   CF_STAMP(1)
-  // (raw buffer loads with a scalar k-step offset would take the 64-bit pointer adds off the vector ALU, but this compiler
-  //  lowers __builtin_amdgcn_raw_buffer_load_b128 to a one-dword load on gfx950: not used)
-  const float *wb = a.wx1s + ((size_t)kk * 192 + wave * 48 + j) * 4;
-  constexpr size_t KS_STRIDE = (size_t)4 * 192 * 4;
-  auto w_ld = [&](int ks, int n) { return *(const float4 *)(wb + ks * KS_STRIDE + n * 64); };
+  const float *wb = pj_w_base(a.wx1s, kk, wave, j);
   float4 bq[4][3];
-  // ---- B: conv -> feat (LDS).  Six m-tiles per wave, software-pipelined by hand: the next tile's A operands are read while
-  //      this tile's MFMAs run, and the previous tile's ReLU + store sit in the middle of them.  Vector instructions between
-  //      fp32 MFMAs cost matrix time, so the loop holds none it can avoid: operand and store offsets were computed during the
-  //      staging (a_off, o_off), the bias is the accumulators' initial value.
+  // ---- B: conv -> feat (LDS).  Six m-tiles per wave (CV_TILE_LOOP), operand and store offsets from the staging (a_off, o_off)
   {
-    auto load_a = [&](float4(&av)[CV_KB], int i) {
-      const float *abase = img + a_off[i];
-#pragma unroll
-      for (int kb = 0; kb < CV_KB; ++kb) {
-        const int k4 = kb * 16 + kk * 4;
-        const int kf = k4 / CV_KT, kt = k4 - kf * CV_KT;
-        av[kb] = *(const float4 *)(abase + kf * CV_LDT + kt);
-      }
-    };
+    auto load_a = [&](float4(&av)[CV_KB], int i) { CV_LOAD_A(av, img + a_off[i]) };
     auto store_tile = [&](int i, const f32x4 &r0, const f32x4 &r1) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -658,49 +777,21 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a)
         }
       }
     };
-#define CF_CONV_KB(kb_)                                                                              \
-  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].x, wreg[kb_][0].x, acc0, 0, 0, 0);       \
-  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].x, wreg[kb_][1].x, acc1, 0, 0, 0);       \
-  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].y, wreg[kb_][0].y, acc0, 0, 0, 0);       \
-  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].y, wreg[kb_][1].y, acc1, 0, 0, 0);       \
-  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].z, wreg[kb_][0].z, acc0, 0, 0, 0);       \
-  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].z, wreg[kb_][1].z, acc1, 0, 0, 0);       \
-  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].w, wreg[kb_][0].w, acc0, 0, 0, 0);       \
-  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].w, wreg[kb_][1].w, acc1, 0, 0, 0);
-    float4 av[2][CV_KB];
     f32x4 prev0 = {0.f, 0.f, 0.f, 0.f}, prev1 = {0.f, 0.f, 0.f, 0.f}, t4_0 = prev0, t4_1 = prev0;
-    load_a(av[0], 0);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      if (i + 1 < 6) load_a(av[(i + 1) & 1], i + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      f32x4 acc0 = {cb0, cb0, cb0, cb0}, acc1 = {cb1, cb1, cb1, cb1};
-      CF_CONV_KB(0) CF_CONV_KB(1) CF_CONV_KB(2)
-      __builtin_amdgcn_sched_barrier(0);
-      if (i > 0 && i < 5) store_tile(i - 1, prev0, prev1);  // tiles 4 and 5 hold the rows that go into the image: kept until it is dead
-      if (i == 5) { t4_0 = prev0; t4_1 = prev1; }
-      __builtin_amdgcn_sched_barrier(0);
-      CF_CONV_KB(3) CF_CONV_KB(4) CF_CONV_KB(5) CF_CONV_KB(6)
-      prev0 = acc0;
-      prev1 = acc1;
-    }
+    // tiles 4 and 5 hold the rows that go into the image: kept until it is dead
+    CV_TILE_LOOP(6, if (i > 0 && i < 5) store_tile(i - 1, prev0, prev1); if (i == 5) { t4_0 = prev0; t4_1 = prev1; })
     // the projection's first W operands: requested here, in front of the two barriers (they do not wait for global loads)
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-      for (int n = 0; n < 3; ++n) bq[s][n] = w_ld(s, n);
+    PJ_RING_PROLOGUE(4)
     __builtin_amdgcn_sched_barrier(0);
     lds_barrier();  // every wave has read its last image operand: rows 13..18 of feat may take the image's place
     store_tile(4, t4_0, t4_1);
     store_tile(5, prev0, prev1);
-#undef CF_CONV_KB
   }
   CF_STAMP(2)
   lds_barrier();  // feat complete (rows 0..12 in the feat region, rows 13..18 in the image, which holds nothing else any more)
   CF_STAMP(3)
   float *gxs = img + CF_GX, *seq1 = img + CF_SEQ, *hb = img + CF_HB;
-  for (int i = tid; i < 32 * GR_SEQ_LD; i += CF_THREADS) seq1[i] = 0.f;  // (behind gx: clear of the aliased rows)
-  if (tid < 2 * 2 * 2 * H) hb[tid] = 0.f;
+  CLEAR_SEQ_H(seq1, 32, hb, CF_THREADS)  // (behind gx: clear of the aliased rows)
 
   // ---- C: layer-1 input projection
   const int unit = lane >> 1, half = lane & 1, dir = wave & 1;
@@ -711,48 +802,26 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a)
     const float *a1p = img + CF_ALIAS_REM + 16 * r1 + kk * 4;  // the remainder block: k-step ks is its row ks / 2, columns 48 (ks % 2) ..
     f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     f32x4 rem[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    // operand ring, fully unrolled so that the slots are plain registers (a rotating copy would have to wait for the
-    // load it copies): W three k-steps ahead (L2), feat one step ahead (LDS)
+    // operand ring: W three k-steps ahead (L2), feat one step ahead (LDS)
     float4 avq[2], rvq[2];
     avq[0] = *(const float4 *)(a0p);
     rvq[0] = *(const float4 *)(a1p);
-    float bv1[3];  // the biases of this lane's three columns: requested now, added 40 k-steps later
-#pragma unroll
-    for (int n = 0; n < 3; ++n) bv1[n] = a.bx1[wave * 48 + n * 16 + j];
+    float bv1[3];
+    PJ_LOAD_BIAS(bv1, a.bx1)
     // recurrent weights: requested here too (48 registers the projection does not need), used a barrier (waves 0, 1) or a whole
     // recurrence (waves 2, 3) later - requested behind the projection they arrived in the first ~800 cycles of phase D
     if (!FRONT_ONLY) gru_load_w(g, wave < 2 ? a.wh1 : a.wh2, wave < 2 ? a.bh1 : a.bh2, dir, unit, half);
-#pragma unroll
-    for (int ks = 0; ks < 40; ++ks) {
-      if (ks + 3 < 40) {
-#pragma unroll
-        for (int n = 0; n < 3; ++n) bq[(ks + 3) & 3][n] = w_ld(ks + 3, n);
-      }
-      if (ks + 1 < 40) {
-        avq[(ks + 1) & 1] = *(const float4 *)(a0p + (ks + 1) * 16);
-        rvq[(ks + 1) & 1] = *(const float4 *)(a1p + ((ks + 1) >> 1) * 96 + ((ks + 1) & 1) * 48);
-      }
-      __builtin_amdgcn_sched_barrier(0);  // the prefetches stay HERE: sunk to just before their use, the LDS reads cost ~130 cycles per k-step
-      const float4 av = avq[ks & 1], rv = rvq[ks & 1];
-      const float4 *b = bq[ks & 3];
-      CF_ROUND(av, rv, b, x) CF_ROUND(av, rv, b, y) CF_ROUND(av, rv, b, z) CF_ROUND(av, rv, b, w)
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    PJ_KLOOP(4, PJ_ROWS16, PJ_ROWS3,
+             avq[(ks + 1) & 1] = *(const float4 *)(a0p + (ks + 1) * 16);
+             rvq[(ks + 1) & 1] = *(const float4 *)(a1p + ((ks + 1) >> 1) * 96 + ((ks + 1) & 1) * 48);)
     lds_barrier();  // gx takes the aliased block's place: every wave must have read its last remainder operand out of it
-    // the four k sub-steps of a column sit in lanes col, col+16, col+32, col+48
 #pragma unroll
     for (int n = 0; n < 3; ++n) {
       const int col = wave * 48 + n * 16 + j;
       const float bv = bv1[n];
 #pragma unroll
       for (int r = 0; r < 4; ++r) gxs[(kk * 4 + r) * GR_GX_LD + col] = acc[n][r] + bv;
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        float v = rem[n][i];
-        v += __shfl_xor(v, 16);
-        v += __shfl_xor(v, 32);
-        if (kk == 0) gxs[(16 + i) * GR_GX_LD + col] = v + bv;
-      }
+      PJ_REM_ROWS(rem[n], bv, gxs[(16 + i) * GR_GX_LD + col] = v;)
     }
   }
   CF_STAMP(4)
@@ -828,14 +897,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
   int a_off, o_off[4];
   int q0;
   float *cache;
-  auto load_conv_w = [&]() {
-#pragma unroll
-    for (int kb = 0; kb < CV_KB; ++kb)
-#pragma unroll
-      for (int n = 0; n < 2; ++n) wreg[kb][n] = *(const float4 *)(a.w4 + ((size_t)(kb * 4 + kk) * 32 + n * 16 + j) * 4);
-    cb0 = a.cbias[j];
-    cb1 = a.cbias[16 + j];
-  };
+  auto load_conv_w = [&]() { CV_LOAD_W(wreg, cb0, cb1, a.w4, a.cbias) };
   // ---- the sixteen cached rows (positions 1..16): requested first, parked in LDS once the image is dead
   // (three named registers: as an array they stayed in scratch memory)
   auto cached = [&](int q) {
@@ -897,7 +959,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
       sidx[q] = in ? f4 : -1;
       stage[q] = in ? *(const float4 *)(src + (size_t)f4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    for (int i = tid; i < CF_IMG_FLOATS / 4; i += CF_THREADS) ((float4 *)img)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    LDS_CLEAR16(img, CF_IMG_FLOATS / 4, CF_THREADS)
     tile_offsets();
     __syncthreads();
     scatter(stage, sidx);
@@ -952,7 +1014,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
     if ((tid >> 7) == c.par) ((float4 *)l.x)[tid & 127] = ringq;
     if (tid < 40) ((uint4 *)l.xs)[tid] = raw;
     if (c.window) {
-      for (int i = tid; i < CF_IMG_FLOATS / 4; i += CF_THREADS) ((float4 *)img)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      LDS_CLEAR16(img, CF_IMG_FLOATS / 4, CF_THREADS)
       tile_offsets();
     }
     __syncthreads();
@@ -982,25 +1044,10 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
   // ---- B: conv of the 60 rows -> feat[p][f * 32 + channel]
   {
     float4 av[CV_KB];
-    const float *abase = img + a_off;
-#pragma unroll
-    for (int kb = 0; kb < CV_KB; ++kb) {
-      const int k4 = kb * 16 + kk * 4;
-      const int kf = k4 / CV_KT, kt = k4 - kf * CV_KT;
-      av[kb] = *(const float4 *)(abase + kf * CV_LDT + kt);
-    }
+    CV_LOAD_A(av, img + a_off)
     f32x4 acc0 = {cb0, cb0, cb0, cb0}, acc1 = {cb1, cb1, cb1, cb1};
 #pragma unroll
-    for (int kb = 0; kb < CV_KB; ++kb) {
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kb].x, wreg[kb][0].x, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kb].x, wreg[kb][1].x, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kb].y, wreg[kb][0].y, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kb].y, wreg[kb][1].y, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kb].z, wreg[kb][0].z, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kb].z, wreg[kb][1].z, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kb].w, wreg[kb][0].w, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kb].w, wreg[kb][1].w, acc1, 0, 0, 0);
-    }
+    for (int kb = 0; kb < CV_KB; ++kb) { CV_MFMA_KB(av, kb) }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if (o_off[r] >= 0) {
@@ -1009,20 +1056,14 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
       }
     }
   }
-  const float *wb = a.wx1s + ((size_t)kk * 192 + wave * 48 + j) * 4;
-  constexpr size_t KS_STRIDE = (size_t)4 * 192 * 4;
-  auto w_ld = [&](int ks, int n) { return *(const float4 *)(wb + ks * KS_STRIDE + n * 64); };
+  const float *wb = pj_w_base(a.wx1s, kk, wave, j);
   // W_x1 ring: with three rows the projection is bound by how many bytes of W are in flight, not by the matrix pipe
   // (3.8 k cycles of MFMAs against 491 KB per workgroup): CS_DEPTH - 1 k-steps ahead instead of the batch kernel's three
   float4 bq[CS_DEPTH][3];
-#pragma unroll
-  for (int s2 = 0; s2 < CS_DEPTH - 1; ++s2)
-#pragma unroll
-    for (int n = 0; n < 3; ++n) bq[s2][n] = w_ld(s2, n);
+  PJ_RING_PROLOGUE(CS_DEPTH)
   __syncthreads();  // feat complete; the image is dead from here on
   float *gxs = img + CF_GX, *seq1 = img + CF_SEQ, *hb = img + CF_HB;
-  for (int i = tid; i < 32 * GR_SEQ_LD; i += CF_THREADS) seq1[i] = 0.f;
-  if (tid < 2 * 2 * 2 * H) hb[tid] = 0.f;
+  CLEAR_SEQ_H(seq1, 32, hb, CF_THREADS)
   auto park = [&](int q, const float4 v) {
     const int i = tid + q * CF_THREADS, tr = i / 48, c4 = i - tr * 48;
     *(float4 *)(&gxs[(tr + 1) * GR_GX_LD + c4 * 4]) = v;
@@ -1038,28 +1079,10 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
     f32x4 rem[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     float4 rvq[2];
     rvq[0] = *(const float4 *)(a1p);
-    float bv1[3];  // the biases of this lane's three columns: requested now, added when the products are complete
-#pragma unroll
-    for (int n = 0; n < 3; ++n) bv1[n] = a.bx1[wave * 48 + n * 16 + j];
+    float bv1[3];
+    PJ_LOAD_BIAS(bv1, a.bx1)
     gru_load_w(g, wave < 2 ? a.wh1 : a.wh2, wave < 2 ? a.bh1 : a.bh2, dir, unit, half);  // (as crnn_fused_kernel: in front of the projection)
-#pragma unroll
-    for (int ks = 0; ks < 40; ++ks) {
-      if (ks + CS_DEPTH - 1 < 40) {
-#pragma unroll
-        for (int n = 0; n < 3; ++n) bq[(ks + CS_DEPTH - 1) % CS_DEPTH][n] = w_ld(ks + CS_DEPTH - 1, n);
-      }
-      if (ks + 1 < 40) rvq[(ks + 1) & 1] = *(const float4 *)(a1p + (ks + 1) * 16);
-      __builtin_amdgcn_sched_barrier(0);
-      const float4 rv = rvq[ks & 1];
-      const float4 *b = bq[ks % CS_DEPTH];
-#define CS_ROUND(e_)                                                                 \
-  rem[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(rv.e_, b[0].e_, rem[0], 0, 0, 0);     \
-  rem[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(rv.e_, b[1].e_, rem[1], 0, 0, 0);     \
-  rem[2] = __builtin_amdgcn_mfma_f32_4x4x1f32(rv.e_, b[2].e_, rem[2], 0, 0, 0);
-      CS_ROUND(x) CS_ROUND(y) CS_ROUND(z) CS_ROUND(w)
-#undef CS_ROUND
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    PJ_KLOOP(CS_DEPTH, PJ_NO_ROWS, PJ_ROWS3, rvq[(ks + 1) & 1] = *(const float4 *)(a1p + (ks + 1) * 16);)
     int nslot = q0 + 128;
     nslot = nslot >= RA ? nslot - RA : nslot;
     float *crow_new = cache + (size_t)nslot * (6 * H);
@@ -1067,16 +1090,8 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
     for (int n = 0; n < 3; ++n) {
       const int col = wave * 48 + n * 16 + j;
       const float bv = bv1[n];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        float v = rem[n][i];
-        v += __shfl_xor(v, 16);
-        v += __shfl_xor(v, 32);
-        if (kk == 0) {
-          gxs[(i ? 16 + i : 0) * GR_GX_LD + col] = v + bv;
-          if (i == 1) crow_new[col] = v + bv;  // position 17: position 16 of the window 8 rows on, ... position 1 of the one 128 on
-        }
-      }
+      // rows 0, 17, 18; position 17 is position 16 of the window 8 rows on, ... position 1 of the one 128 on: into the cache too
+      PJ_REM_ROWS(rem[n], bv, gxs[(i ? 16 + i : 0) * GR_GX_LD + col] = v; if (i == 1) crow_new[col] = v;)
     }
   }
   __syncthreads();  // gx complete; nobody reads feat any more
@@ -1134,11 +1149,8 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
   const float *w4 = a.w4[kind];
 
   float4 wreg[CV_KB][2];
-#pragma unroll
-  for (int kb = 0; kb < CV_KB; ++kb)
-#pragma unroll
-    for (int n = 0; n < 2; ++n) wreg[kb][n] = *(const float4 *)(w4 + ((size_t)(kb * 4 + kk) * 32 + n * 16 + j) * 4);
-  const float cb0 = a.cbias[j], cb1 = a.cbias[16 + j];
+  float cb0, cb1;
+  CV_LOAD_W(wreg, cb0, cb1, w4, a.cbias)
 
   // ---- stage the union of the 16 fields: image[(mel + PF)][row - field0]
   int a_off[5], o_off[5][4];
@@ -1156,7 +1168,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
         stage[q] = ld_mel4_sel<AL>(a.mel + rc * CV_NMEL + (f4 - it * 10) * 4, it < ncols && r >= 0 && r < a.mel_rows);
       }
     });
-    for (int i = tid; i < CF_IMG_FLOATS / 4; i += CF_THREADS) ((float4 *)img)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    LDS_CLEAR16(img, CF_IMG_FLOATS / 4, CF_THREADS)
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
       const int mt = wave + 4 * i, m = mt * 16 + j;   // 20 m-tiles: (position, frequency) rows
@@ -1180,17 +1192,9 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
     }
   }
   __syncthreads();
-  // ---- conv: five m-tiles per wave, pipelined as in crnn_fused_kernel
+  // ---- conv: five m-tiles per wave (CV_TILE_LOOP)
   {
-    auto load_a = [&](float4(&av)[CV_KB], int i) {
-      const float *abase = img + a_off[i];
-#pragma unroll
-      for (int kb = 0; kb < CV_KB; ++kb) {
-        const int k4 = kb * 16 + kk * 4;
-        const int kf = k4 / CV_KT, kt = k4 - kf * CV_KT;
-        av[kb] = *(const float4 *)(abase + kf * CV_LDT + kt);
-      }
-    };
+    auto load_a = [&](float4(&av)[CV_KB], int i) { CV_LOAD_A(av, img + a_off[i]) };
     auto store_tile = [&](int i, const f32x4 &r0, const f32x4 &r1) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -1198,42 +1202,13 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
         feat[o_off[i][r] + 16] = relu1(r1[r]);
       }
     };
-#define CR_CONV_KB(kb_)                                                                              \
-  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].x, wreg[kb_][0].x, acc0, 0, 0, 0);       \
-  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].x, wreg[kb_][1].x, acc1, 0, 0, 0);       \
-  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].y, wreg[kb_][0].y, acc0, 0, 0, 0);       \
-  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].y, wreg[kb_][1].y, acc1, 0, 0, 0);       \
-  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].z, wreg[kb_][0].z, acc0, 0, 0, 0);       \
-  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].z, wreg[kb_][1].z, acc1, 0, 0, 0);       \
-  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].w, wreg[kb_][0].w, acc0, 0, 0, 0);       \
-  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i & 1][kb_].w, wreg[kb_][1].w, acc1, 0, 0, 0);
-    float4 av[2][CV_KB];
     f32x4 prev0 = {0.f, 0.f, 0.f, 0.f}, prev1 = {0.f, 0.f, 0.f, 0.f};
-    load_a(av[0], 0);
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      if (i + 1 < 5) load_a(av[(i + 1) & 1], i + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      f32x4 acc0 = {cb0, cb0, cb0, cb0}, acc1 = {cb1, cb1, cb1, cb1};
-      CR_CONV_KB(0) CR_CONV_KB(1) CR_CONV_KB(2)
-      __builtin_amdgcn_sched_barrier(0);
-      if (i > 0) store_tile(i - 1, prev0, prev1);
-      __builtin_amdgcn_sched_barrier(0);
-      CR_CONV_KB(3) CR_CONV_KB(4) CR_CONV_KB(5) CR_CONV_KB(6)
-      prev0 = acc0;
-      prev1 = acc1;
-    }
+    CV_TILE_LOOP(5, if (i > 0) store_tile(i - 1, prev0, prev1);)
     store_tile(4, prev0, prev1);
-#undef CR_CONV_KB
   }
-  const float *wb = a.wx1s + ((size_t)kk * 192 + wave * 48 + j) * 4;
-  constexpr size_t KS_STRIDE = (size_t)4 * 192 * 4;
-  auto w_ld = [&](int ks, int n) { return *(const float4 *)(wb + ks * KS_STRIDE + n * 64); };
+  const float *wb = pj_w_base(a.wx1s, kk, wave, j);
   float4 bq[4][3];
-#pragma unroll
-  for (int s2 = 0; s2 < 3; ++s2)
-#pragma unroll
-    for (int n = 0; n < 3; ++n) bq[s2][n] = w_ld(s2, n);
+  PJ_RING_PROLOGUE(4)
   __syncthreads();  // feat complete
   // ---- projection: 16 rows = one MFMA tile per n-tile, 3 n-tiles per wave
   {
@@ -1241,27 +1216,9 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
     f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     float4 avq[2];
     avq[0] = *(const float4 *)(a0p);
-    float bv1[3];  // the biases of this lane's three columns: requested now, added when the products are complete
-#pragma unroll
-    for (int n = 0; n < 3; ++n) bv1[n] = a.bx1[wave * 48 + n * 16 + j];
-#pragma unroll
-    for (int ks = 0; ks < 40; ++ks) {
-      if (ks + 3 < 40) {
-#pragma unroll
-        for (int n = 0; n < 3; ++n) bq[(ks + 3) & 3][n] = w_ld(ks + 3, n);
-      }
-      if (ks + 1 < 40) avq[(ks + 1) & 1] = *(const float4 *)(a0p + (ks + 1) * 16);
-      __builtin_amdgcn_sched_barrier(0);
-      const float4 av = avq[ks & 1];
-      const float4 *b = bq[ks & 3];
-#define CR_ROUND(e_)                                                                  \
-  acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.e_, b[0].e_, acc[0], 0, 0, 0);    \
-  acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.e_, b[1].e_, acc[1], 0, 0, 0);    \
-  acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.e_, b[2].e_, acc[2], 0, 0, 0);
-      CR_ROUND(x) CR_ROUND(y) CR_ROUND(z) CR_ROUND(w)
-#undef CR_ROUND
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    float bv1[3];
+    PJ_LOAD_BIAS(bv1, a.bx1)
+    PJ_KLOOP(4, PJ_ROWS16, PJ_NO_ROWS, avq[(ks + 1) & 1] = *(const float4 *)(a0p + (ks + 1) * 16);)
     float *out = a.out[kind] + (size_t)out_row * 192;
 #pragma unroll
     for (int n = 0; n < 3; ++n) {
@@ -1564,8 +1521,7 @@ __global__ __launch_bounds__(128, 4) void gru_tail_kernel(tail_args a) {
       if (q < NQ) *(f32x4 *)(&gxs[t * GR_GX_LD + c4 * 4]) = st[s];
     }
   }
-  for (int i = tid; i < 20 * GR_SEQ_LD; i += 128) seq1[i] = 0.f;
-  for (int i = tid; i < 2 * 2 * 2 * H; i += 128) hb[i] = 0.f;
+  CLEAR_SEQ_H(seq1, 20, hb, 128)
   __syncthreads();
   cf_recurrence<true>(g, gxs, hb + dir * 2 * H, seq1, dir, unit, half);
   __syncthreads();
@@ -1573,35 +1529,12 @@ __global__ __launch_bounds__(128, 4) void gru_tail_kernel(tail_args a) {
 #pragma unroll 1
   for (int pass = 0; pass < 2; ++pass) {
     const int nt0 = dir * 6 + pass * 3;
-    f32x4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    f32x4 rem[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     float4 bq[4][3];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int n = 0; n < 3; ++n) bq[kb][n] = *(const float4 *)(a.wx2s + ((size_t)(kb * 4 + kk) * 192 + (nt0 + n) * 16 + j) * 4);
-    float bb2[3];  // the biases with the weights (asked for where they are added, each was a round trip of its own)
-#pragma unroll
-    for (int n = 0; n < 3; ++n) bb2[n] = a.bx2[(nt0 + n) * 16 + j];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-      const float4 av = *(const float4 *)(&seq1[j * GR_SEQ_LD + kb * 16 + kk * 4]);
-      const float4 rv = *(const float4 *)(&seq1[(j < 3 ? 16 + j : 19) * GR_SEQ_LD + kb * 16 + kk * 4]);  // row 19 is zero
-      const float4 *b = bq[kb];
-      CF_ROUND_L2(av, rv, b, x) CF_ROUND_L2(av, rv, b, y) CF_ROUND_L2(av, rv, b, z) CF_ROUND_L2(av, rv, b, w)
-    }
-    __syncthreads();  // pass 0: both waves are done reading gx1 before anybody overwrites it (gx2 takes its place)
-#pragma unroll
-    for (int n = 0; n < 3; ++n) {
-      const int col = (nt0 + n) * 16 + j;
-      const float bb = bb2[n];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) gxs[(kk * 4 + r) * GR_GX_LD + col] = acc[n][r] + bb;
-      if (kk == 0) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r) gxs[(16 + r) * GR_GX_LD + col] = rem[n][r] + bb;
-      }
-    }
+    L2_LOAD_W(bq, a.wx2s, nt0)
+    float bb2[3];  // the biases with the weights
+    L2_LOAD_BIAS(bb2, a.bx2, nt0)
+    // between products and stores, pass 0: both waves are done reading gx1 before anybody overwrites it (gx2 takes its place)
+    L2_PROJECT(bq, bb2, j < 3 ? 16 + j : 19 /* row 19 is zero */, nt0, __syncthreads();)
   }
   // layer-2 recurrent weights: requested only now, when the projection's operands are dead - the kernel fits 128 registers
   // (four waves per SIMD instead of three); one L2 latency per window, partly behind the barrier
@@ -1632,16 +1565,8 @@ __global__ __launch_bounds__(128, 4) void gru_tail_kernel(tail_args a) {
       for (int k = 0; k < 2 * H; ++k) y = fmaf(a.w2[lane * 64 + k], hid[k], y);
       y += b2v;
     }
-    if (a.HEAD == 0) {
-      if (lane < a.NOUT) a.out[(size_t)w * a.NOUT + lane] = sigmoid_f(y);
-    } else {
-      float mx = (lane < a.NOUT) ? y : -INFINITY;
-      for (int o = 1; o < 8; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-      float e = (lane < a.NOUT) ? expf(y - mx) : 0.f;
-      float sum = e;
-      for (int o = 1; o < 8; o <<= 1) sum += __shfl_xor(sum, o);
-      if (lane < a.NOUT) a.out[(size_t)w * a.NOUT + lane] = e / sum;
-    }
+    const float p = head_activation(y, lane, a.NOUT, a.HEAD);
+    if (lane < a.NOUT) a.out[(size_t)w * a.NOUT + lane] = p;
   }
 }
 
@@ -1925,23 +1850,20 @@ __global__ __launch_bounds__(128, 2) void gru_tail16_kernel(tail16_args aa) {
       for (int k = 0; k < 2 * H; ++k) y = fmaf(a.w2[o * 64 + k], hid[wq * GT16_ELD + k], y);
       y += a.b2[o];
     }
-    const bool live = o < a.NOUT && w0 + wq < aa.nw;
-    if (a.HEAD == 0) {
-      if (live) a.out[(size_t)(w0 + wq) * a.NOUT + o] = sigmoid_f(y);
-    } else {
-      float mx = (o < a.NOUT) ? y : -INFINITY;
-      for (int d = 1; d < 8; d <<= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-      const float e = (o < a.NOUT) ? expf(y - mx) : 0.f;
-      float sum = e;
-      for (int d = 1; d < 8; d <<= 1) sum += __shfl_xor(sum, d);
-      if (live) a.out[(size_t)(w0 + wq) * a.NOUT + o] = e / sum;
-    }
+    const float p = head_activation(y, o, a.NOUT, a.HEAD);
+    if (o < a.NOUT && w0 + wq < aa.nw) a.out[(size_t)(w0 + wq) * a.NOUT + o] = p;
   }
 }
 
 
-#undef CF_ROUND
 #undef CF_ROUND_L2
+#undef L2_PROJECT
+#undef PJ_KLOOP
+#undef PJ_ROWS16
+#undef PJ_ROWS3
+#undef PJ_NO_ROWS
+#undef CV_TILE_LOOP
+#undef CV_MFMA_KB
 #undef GT16_PRE_ALL
 #undef GT16_PRE_FIRST
 #undef GT16_POS
@@ -1962,16 +1884,8 @@ __global__ __launch_bounds__(64) void crnn_detect_kernel(const float *enc, const
     for (int k = 0; k < 64; ++k) y = fmaf(w2[lane * 64 + k], hid[k], y);
     y += b2[lane];
   }
-  if (HEAD == 0) {
-    if (lane < NOUT) out[(size_t)w * NOUT + lane] = sigmoid_f(y);
-  } else {
-    float mx = (lane < NOUT) ? y : -INFINITY;
-    for (int o = 1; o < 8; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    float ex = (lane < NOUT) ? expf(y - mx) : 0.f;
-    float sum = ex;
-    for (int o = 1; o < 8; o <<= 1) sum += __shfl_xor(sum, o);
-    if (lane < NOUT) out[(size_t)w * NOUT + lane] = ex / sum;
-  }
+  const float p = head_activation(y, lane, NOUT, HEAD);
+  if (lane < NOUT) out[(size_t)w * NOUT + lane] = p;
 }
 
 int ww_k_crnn_detect(ww_ctx *ctx, const ww_model *m, const float *d_enc, int nw, float *d_out) {
@@ -2207,8 +2121,17 @@ int ww_k_crnn_stream_forward(ww_ctx *ctx, const ww_model *m, const float *d_hist
 // WW_OPT_CRNN_TAIL_MFMA = 1 (default) takes it from WW_TAIL16_MIN windows per launch on; 2 = always, 0 = never.
 #define WW_TAIL16_MIN 9216
 static size_t tail_seq_bytes(int nw) { return ww_bump::need((size_t)((nw + 15) / 16) * CV_OT * 16 * 2 * GR_H, 4); }
-static void launch_tail(ww_ctx *ctx, const ww_model *m, tail_args t, int nw, float *seq) {
-  t.wx2 = m->crnn.wx2;
+// The tail kernels' arguments: the model's weights; the caller names its source of projected rows (gx1, or gxI / gxL / gxR with
+// hop_g, eight_g and, for several sequences, iI0) and its outputs (enc, out).
+static tail_args crnn_tail_args(const ww_crnn_dev &c) {
+  tail_args t = {};
+  t.wh1 = c.wh1; t.bh1 = c.bh1;
+  t.wx2s = c.wx2s; t.wx2 = c.wx2; t.bx2 = c.bx2; t.wh2 = c.wh2; t.bh2 = c.bh2;
+  t.w1 = c.w1; t.b1 = c.b1; t.w2 = c.w2; t.b2 = c.b2;
+  t.NOUT = c.NOUT; t.HEAD = c.HEAD;
+  return t;
+}
+static void launch_tail(ww_ctx *ctx, const ww_model *m, const tail_args &t, int nw, float *seq) {
   if (m->opt_tail_mfma >= 2 || (m->opt_tail_mfma == 1 && nw >= WW_TAIL16_MIN)) {
     tail16_args a16 = {t, seq, nw};
     ww_launch_scope scope(ctx, "gru_tail16_kernel");
@@ -2223,6 +2146,25 @@ static void launch_tail(ww_ctx *ctx, const ww_model *m, tail_args t, int nw, flo
 // this many windows on (ww_model_set_option(WW_OPT_CRNN_SLIDE_MIN): 0 = never).
 static int crnn_slide_min(const ww_model *m) { return m->opt_slide_min > 0 ? m->opt_slide_min : 0x7fffffff; }
 static int gcd8(int hop) { return hop % 8 == 0 ? 8 : hop % 4 == 0 ? 4 : hop % 2 == 0 ? 2 : 1; }
+
+// crnn_rows_kernel's arguments but for its position lists (start / stride / count / tiles, or desc): the three output lists are
+// interior fields, left edges, right edges
+static rows_args rows_args_of(const ww_crnn_dev &c, const float *mel, int64_t mel_rows, float *gI, float *gL, float *gR) {
+  rows_args r = {};
+  r.mel = mel; r.mel_rows = mel_rows;
+  r.w4[0] = c.conv_w; r.w4[1] = c.conv_wL; r.w4[2] = c.conv_wR;
+  r.cbias = c.conv_b; r.wx1s = c.wx1s; r.bx1 = c.bx1;
+  r.out[0] = gI; r.out[1] = gL; r.out[2] = gR;
+  return r;
+}
+
+// Scratch of a launch of nw windows, for sizing a buffer (ww_crnn_workspace) and for checking the one handed in
+// (ww_k_crnn_forward).  Sliding form: (fields + 2 edge rows per window) x 192 floats; fields <= 7 nw + 130 (hop 7), i.e. never
+// more than the 19 rows per window of the front + tail form.
+static size_t crnn_slide_scratch(int nw) { return ww_bump::need(((size_t)9 * nw + 160) * 6 * GR_H, 4) + tail_seq_bytes(nw) + 2048; }
+static size_t crnn_split_scratch(const ww_crnn_dev &c, int nw) {
+  return ww_bump::need((size_t)nw * c.OT * 6 * c.H, 4) + tail_seq_bytes(nw) + 2048;
+}
 
 // Several mel sequences in one buffer (the clips of a test set, wwhip/evaluate.py), each slid over with the same hop:
 // crnn_rows_kernel by tile descriptors (no tile straddles two sequences), gru_tail_kernel with each window's first
@@ -2292,18 +2234,16 @@ int ww_k_crnn_segments_forward(ww_ctx *ctx, const ww_model *m, const float *d_me
       WW_HIP(ctx, hipMemcpyAsync(d_i0, hp + o_i, n_i, hipMemcpyHostToDevice, ctx->stream));
       WW_HIP(ctx, hipEventRecord(ctx->desc_ev[slot], ctx->stream));
       ctx->desc_busy[slot] = true;
-      rows_args r = {};
-      r.mel = d_mel; r.mel_rows = mel_rows;
-      r.w4[0] = c.conv_w; r.w4[1] = c.conv_wL; r.w4[2] = c.conv_wR;
-      r.cbias = c.conv_b; r.wx1s = c.wx1s; r.bx1 = c.bx1;
-      r.out[0] = gI; r.out[1] = gL; r.out[2] = gR;
+      rows_args r = rows_args_of(c, d_mel, mel_rows, gI, gL, gR);
       r.desc = d_tiles;
       {
         ww_launch_scope scope(ctx, "crnn_rows_kernel");
         hipLaunchKernelGGL(crnn_rows_kernel, dim3((unsigned)tiles.size()), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r);
       }
-      tail_args t = {nullptr, c.wh1, c.bh1, c.wx2s, c.bx2, c.wh2, c.bh2, c.w1, c.b1, c.w2, c.b2, nullptr,
-                     d_out + (size_t)w_done * c.NOUT, c.NOUT, c.HEAD, gI, gL, gR, hop / g, 8 / g, d_i0, nullptr};
+      tail_args t = crnn_tail_args(c);
+      t.gxI = gI; t.gxL = gL; t.gxR = gR;
+      t.hop_g = hop / g; t.eight_g = 8 / g; t.iI0 = d_i0;
+      t.out = d_out + (size_t)w_done * c.NOUT;
       launch_tail(ctx, m, t, (int)nW, seq);
       WW_HIP(ctx, hipGetLastError());
       w_done += nW;
@@ -2317,14 +2257,9 @@ size_t ww_crnn_workspace(const ww_model *m, int nw, bool sliding) {
   const ww_crnn_dev &c = m->crnn;
   if (c.generic) return crnn_generic_workspace(c, nw);
   const int thr = crnn_split_threshold(m);
-  // sliding form: (fields + 2 edge rows per window) x 192 floats; fields <= 7 nw + 130 (hop 7), i.e. never more than the
-  // 19 rows per window of the front/tail form
   size_t need = 1024;  // crnn_fused_kernel keeps every intermediate in LDS
-  if (sliding && nw >= crnn_slide_min(m)) need = ww_bump::need(((size_t)9 * nw + 160) * 6 * c.H, 4) + tail_seq_bytes(nw) + 2048;
-  if (thr > 0 && nw > thr) {
-    const size_t split = ww_bump::need((size_t)nw * c.OT * 6 * c.H, 4) + tail_seq_bytes(nw) + 2048;
-    need = split > need ? split : need;
-  }
+  if (sliding && nw >= crnn_slide_min(m)) need = crnn_slide_scratch(nw);
+  if (thr > 0 && nw > thr) need = std::max(need, crnn_split_scratch(c, nw));
   return need;
 }
 
@@ -2346,8 +2281,8 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
   {
     size_t need = 0;
     if (c.generic) need = crnn_generic_workspace(c, nw);
-    else if (slide_form) need = ww_bump::need(((size_t)9 * nw + 160) * 6 * c.H, 4) + tail_seq_bytes(nw) + 2048;
-    else if (crnn_split_threshold(m) > 0 && nw > crnn_split_threshold(m)) need = ww_bump::need((size_t)nw * c.OT * 6 * c.H, 4) + tail_seq_bytes(nw) + 2048;
+    else if (slide_form) need = crnn_slide_scratch(nw);
+    else if (crnn_split_threshold(m) > 0 && nw > crnn_split_threshold(m)) need = crnn_split_scratch(c, nw);
     if (need > ws_bytes)
       return ww_fail(ctx, WW_EINVAL, "CRNN launch of %d windows needs %zu bytes of scratch, the caller reserved %zu (options changed "
                      "after the buffer was sized?)", nw, need, ws_bytes);
@@ -2364,11 +2299,7 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
     ww_bump b(ws, ws_bytes);
     float *gI = b.take<float>((size_t)n_int * 6 * c.H), *gL = b.take<float>((size_t)nw * 6 * c.H), *gR = b.take<float>((size_t)nw * 6 * c.H);
     float *seq = (float *)b.take<char>(tail_seq_bytes(nw));
-    rows_args r = {};
-    r.mel = d_mel; r.mel_rows = mel_rows;
-    r.w4[0] = c.conv_w; r.w4[1] = c.conv_wL; r.w4[2] = c.conv_wR;
-    r.cbias = c.conv_b; r.wx1s = c.wx1s; r.bx1 = c.bx1;
-    r.out[0] = gI; r.out[1] = gL; r.out[2] = gR;
+    rows_args r = rows_args_of(c, d_mel, mel_rows, gI, gL, gR);
     r.start[0] = row0 + 2; r.start[1] = row0 - c.PT; r.start[2] = row0 + (int64_t)(c.OT - 1) * c.ST - c.PT;
     r.stride[0] = g; r.stride[1] = hop; r.stride[2] = hop;
     r.count[0] = (int)n_int; r.count[1] = nw; r.count[2] = nw;
@@ -2377,8 +2308,10 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
       ww_launch_scope scope(ctx, "crnn_rows_kernel");
       hipLaunchKernelGGL(crnn_rows_kernel, dim3(r.tiles[0] + r.tiles[1] + r.tiles[2]), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r);
     }
-    tail_args t = {nullptr, c.wh1, c.bh1, c.wx2s, c.bx2, c.wh2, c.bh2, c.w1, c.b1, c.w2, c.b2, d_enc, d_out, c.NOUT, c.HEAD,
-                   gI, gL, gR, hop / g, 8 / g, nullptr, nullptr};
+    tail_args t = crnn_tail_args(c);
+    t.gxI = gI; t.gxL = gL; t.gxR = gR;
+    t.hop_g = hop / g; t.eight_g = 8 / g;
+    t.enc = d_enc; t.out = d_out;
     launch_tail(ctx, m, t, nw, seq);
     WW_HIP(ctx, hipGetLastError());
     return WW_OK;
@@ -2397,7 +2330,9 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
       if (bf16) hipLaunchKernelGGL(crnn_fused_bf16_kernel<true>, dim3(nw), dim3(CF_THREADS), CFB_SMEM_BYTES, ctx->stream, a);
       else hipLaunchKernelGGL(crnn_fused_kernel<true>, dim3(nw), dim3(CF_THREADS), CF_FUSED_SMEM_BYTES, ctx->stream, a);
     }
-    tail_args t = {a.gx_out, c.wh1, c.bh1, c.wx2s, c.bx2, c.wh2, c.bh2, c.w1, c.b1, c.w2, c.b2, d_enc, d_out, c.NOUT, c.HEAD, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr};
+    tail_args t = crnn_tail_args(c);
+    t.gx1 = a.gx_out;
+    t.enc = d_enc; t.out = d_out;
     launch_tail(ctx, m, t, nw, seq);
     WW_HIP(ctx, hipGetLastError());
     return WW_OK;
