@@ -1166,6 +1166,92 @@ def test_crnn_unaligned_mel_pointer_gives_the_same_bits(assets, engines, oracles
         bf.close()
 
 
+def test_wavenet_unaligned_mel_pointer_gives_the_same_bits(assets, engines, oracles):
+    """The Wavenet kernels stage their input 16 bytes at a time from a 16-byte aligned mel buffer and 4 bytes at a time from any
+    other: the same mel at float offsets 1 and 2 of a buffer (4 and 8 bytes off) gives the bits of the aligned copy (offset 4).
+    ww_forward_windows_dev - explicit windows of full, partial, one-row and no validity, a full and a partial one ending on the
+    buffer's last row - through wavenet_kernel's twelve-wave form (40 windows) and its four-wave form (260 > 256 windows) in fp32
+    and bf16x3, and through the row-major loop; ww_wave_sequence_dev - sequences of 1, 200 and 450 rows (one, two and three
+    chunks of 192) through wavenet_seq_kernel: encoder output, logits and both posteriors.  The aligned fp32 result is anchored
+    to the oracle on the same windows zero-padded on the host."""
+    import torch
+    from wwhip.engine import Engine
+    e = engines["Wavenet"]
+    T, rows = e.window, 400
+    rng = np.random.default_rng(212)
+    mel = rng.uniform(0, 6.5, (rows, 40)).astype(np.float32)
+    seq_offs = np.array([0, 1, 201, 651], np.int64)
+    seq_mel = rng.uniform(0, 6.5, (int(seq_offs[-1]), 40)).astype(np.float32)
+    buf = torch.zeros(max(rows, len(seq_mel)) * 40 + 4, dtype=torch.float32, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+
+    def place(m, off):
+        buf.zero_()
+        buf[off:off + m.size] = torch.from_numpy(m.ravel()).cuda()
+        torch.cuda.synchronize()
+        return buf.data_ptr() + 4 * off
+
+    def window_list(nw):
+        win_row = rng.integers(0, rows - T + 1, nw).astype(np.int64)
+        win_valid = np.full(nw, T, np.int32)
+        win_valid[1], win_valid[2], win_valid[3] = 100, 1, 0
+        win_valid[9:20] = rng.integers(1, T, 11)
+        win_row[4] = rows - T                       # a full window that ends on the buffer's last row
+        win_row[5], win_valid[5] = rows - 100, 100  # and a partial one
+        assert win_valid[0] == T and (win_row + win_valid <= rows).all()
+        return win_row, win_valid
+
+    def windows(eng, win_row, win_valid, off):
+        nw = len(win_row)
+        d_row, d_valid = torch.from_numpy(win_row).cuda(), torch.from_numpy(win_valid).cuda()
+        d_out = torch.zeros((nw, eng.n_out), dtype=torch.float32, device="cuda")
+        d_mel = place(mel, off)
+        eng.forward_windows_dev(d_mel, rows, d_row.data_ptr(), d_valid.data_ptr(), nw, d_out.data_ptr())
+        eng.ctx.synchronize()
+        return d_out.cpu().numpy()
+
+    def sequences(off):
+        n, ns = len(seq_mel), len(seq_offs) - 1
+        outs = {"enc": torch.zeros((n, 32), dtype=torch.float32, device="cuda"),
+                "logits": torch.zeros((n, e.n_out), dtype=torch.float32, device="cuda"),
+                "post_frames": torch.zeros((n, e.n_out), dtype=torch.float32, device="cuda"),
+                "post": torch.zeros((ns, e.n_out), dtype=torch.float32, device="cuda")}
+        d_mel = place(seq_mel, off)
+        e.wave_sequence_dev(d_mel, n, seq_offs, None, outs["enc"].data_ptr(), outs["logits"].data_ptr(),
+                            outs["post_frames"].data_ptr(), outs["post"].data_ptr())
+        e.ctx.synchronize()
+        return {k: v.cpu().numpy() for k, v in outs.items()}
+
+    lists = {nw: window_list(nw) for nw in (40, 260)}
+    bf = Engine(os.path.join(assets, "Wavenet"), precision="bf16x3")
+    try:
+        for eng, nw, rowmajor in ((e, 40, 0), (e, 260, 0), (bf, 40, 0), (bf, 260, 0), (e, 40, 1)):
+            win_row, win_valid = lists[nw]
+
+            def run(off):
+                with eng.options(wavenet_rowmajor=rowmajor):
+                    return windows(eng, win_row, win_valid, off)
+            aligned = run(4)
+            if eng is e and nw == 40 and not rowmajor:
+                wins = np.zeros((nw, T, 40), np.float32)
+                for k in range(nw):
+                    wins[k, :win_valid[k]] = mel[win_row[k]:win_row[k] + win_valid[k]]
+                err = float(np.abs(aligned - oracles["Wavenet"].forward(wins)).max())
+                print(f"aligned fp32 explicit windows: max|gpu-oracle| = {err:.3e}")
+                assert err < TOL_POST
+            for off in (1, 2):
+                np.testing.assert_array_equal(run(off), aligned, err_msg=f"precision {eng is bf and 'bf16x3' or 'fp32'} windows {nw} "
+                                                                         f"rowmajor {rowmajor} offset {off}")
+        aligned = sequences(4)
+        assert np.isfinite(aligned["post"]).all() and np.abs(aligned["enc"]).max() > 0
+        for off in (1, 2):
+            got = sequences(off)
+            for k in aligned:
+                np.testing.assert_array_equal(got[k], aligned[k], err_msg=f"sequences {k} offset {off}")
+    finally:
+        bf.close()
+
+
 def test_two_host_threads_through_the_c_abi(assets, oracles):
     """include/wwhip.h: "one ww_ctx per host thread".  Two Python threads (ctypes releases the GIL inside every call, so
     the library really runs concurrently), each with its OWN context, model and stream bank - one CRNN, one Wavenet -

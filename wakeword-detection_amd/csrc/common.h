@@ -239,6 +239,15 @@ struct ww_tick_tag {
   unsigned seq;
   int pidx;                   // the head's output element that is the posterior
 };
+#ifdef __HIPCC__
+// One 8-byte store straight to page-locked host memory (system scope: not parked in L2): the host sees value and tick number
+// together or not at all.
+__device__ __forceinline__ void tick_tag_store(const ww_tick_tag &t, int w, float v, int k = 0) {
+  // slot w + k (two indices: a kernel whose slot is base + row keeps the two pointer additions it had)
+  const unsigned long long word = (unsigned long long)__float_as_uint(v) | ((unsigned long long)t.seq << 32);
+  __hip_atomic_store(t.slots + w + k, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+#endif
 
 struct ww_tick_fe;  // the streaming front end's side of a one-launch tick (stream_fe.h)
 

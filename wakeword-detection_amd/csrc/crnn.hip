@@ -531,13 +531,6 @@ struct fused_args {
   ww_tick_tag tag;             // streaming ticks: the posterior as a {value, tick number} pair instead of the row of `out` (common.h)
 };
 
-// One 8-byte store straight to page-locked host memory (system scope: not parked in L2): the host sees value and tick number
-// together or not at all.
-__device__ __forceinline__ void tick_tag_store(const ww_tick_tag &t, int w, float v) {
-  const unsigned long long word = (unsigned long long)__float_as_uint(v) | ((unsigned long long)t.seq << 32);
-  __hip_atomic_store(t.slots + w, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // one direction of one GRU layer over the OT steps held in LDS (gx rows incl. b_x), h ping-pong in hd
 template <bool SEQ>
 __device__ __forceinline__ float cf_recurrence(const gru_w &g, const float *gxs, float *hd, float *seq1, int dir, int unit, int half) {

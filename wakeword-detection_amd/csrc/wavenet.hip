@@ -127,20 +127,17 @@ __device__ __forceinline__ float fast_tanh_w(float x) {
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
-struct wave_blk {
-  float4 wg[3][2], wrs[3];
-  float bn_s, bn_t, bsig, btanh, bres, bsk0, bsk1;
-};
-
 #define MFMA4(acc, av, bv)                                              \
   acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, bv.x, acc, 0, 0, 0); \
   acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, bv.y, acc, 0, 0, 0); \
   acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, bv.z, acc, 0, 0, 0); \
   acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, bv.w, acc, 0, 0, 0);
 
+// A block's weights as this lane's MFMA operands: gate [3 taps][sig | tanh], res | skip [3 column tiles]
 // (block-uniform base pointers + one 32-bit per-lane offset each: the loads take SGPR base + VGPR offset + immediate, no
 //  64-bit address arithmetic on the vector ALU - in the fp32 kernel every vector instruction costs matrix time)
-__device__ __forceinline__ void wave_blk_load(const wave_args &a, int blk, int j, int kk, wave_blk &p) {
+struct wv_wblk { float4 wg[3][2], wrs[3]; };
+__device__ __forceinline__ void wv_wload(const wave_args &a, int blk, int j, int kk, wv_wblk &p) {
   const float *wg = a.w_gate4 + (size_t)blk * 3 * 4 * 32 * 4, *wrs = a.w_rs4 + (size_t)blk * 4 * 48 * 4;
   const unsigned og = (unsigned)(kk * 32 + j) * 4, ors = (unsigned)(kk * 48 + j) * 4;
 #pragma unroll
@@ -149,6 +146,14 @@ __device__ __forceinline__ void wave_blk_load(const wave_args &a, int blk, int j
     for (int n = 0; n < 2; ++n) p.wg[kb][n] = *(const float4 *)(wg + og + kb * 4 * 32 * 4 + n * 16 * 4);
 #pragma unroll
   for (int n = 0; n < 3; ++n) p.wrs[n] = *(const float4 *)(wrs + ors + n * 16 * 4);
+}
+
+// the row-major loop's block: the weights and this lane's column of the seven small vectors
+struct wave_blk : wv_wblk {
+  float bn_s, bn_t, bsig, btanh, bres, bsk0, bsk1;
+};
+__device__ __forceinline__ void wave_blk_load(const wave_args &a, int blk, int j, int kk, wave_blk &p) {
+  wv_wload(a, blk, j, kk, p);
   const float *bn_s = a.bn_s + blk * WV_C, *bn_t = a.bn_t + blk * WV_C, *bg = a.b_gate + blk * 32, *brs = a.b_rs + blk * 48;
   const unsigned uj = (unsigned)j;
   p.bn_s = bn_s[uj];
@@ -209,26 +214,32 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // ---- the fp32 transposed block body, the detect head of one 16-row tile and the 16-lane softmax: ONE definition each, used by
 //      wavenet_kernel (a window per workgroup) and wavenet_seq_kernel (a sequence walked in chunks, below).  DESIGN.md 4.3: one
 //      association of every sum, whatever the dispatch - a time step's chains do not depend on the tile or chunk it sits in.
-struct wv_wblk { float4 wg[3][2], wrs[3]; };
 struct wv_vblk { float4 bns, bnt, bsig, btanh; };
 __device__ __forceinline__ f32x4 wv_f4(const float4 &v) { return (f32x4){v.x, v.y, v.z, v.w}; }
-__device__ __forceinline__ void wv_wload(const wave_args &a, int blk, int j, int kk, wv_wblk &p) {
-  const float *wg = a.w_gate4 + (size_t)blk * 3 * 4 * 32 * 4, *wrs = a.w_rs4 + (size_t)blk * 4 * 48 * 4;
-  const unsigned og = (unsigned)(kk * 32 + j) * 4, ors = (unsigned)(kk * 48 + j) * 4;
-#pragma unroll
-  for (int kb = 0; kb < 3; ++kb)
-#pragma unroll
-    for (int n = 0; n < 2; ++n) p.wg[kb][n] = *(const float4 *)(wg + og + kb * 4 * 32 * 4 + n * 16 * 4);
-#pragma unroll
-  for (int n = 0; n < 3; ++n) p.wrs[n] = *(const float4 *)(wrs + ors + n * 16 * 4);
-}
+// All blocks' small vectors in one LDS table [NB][WV_VT_N][16] (the transposed fp32 loop): ONE definition of its layout.  A lane
+// reads its channel group of vector q of block b as the float4 wv_vt(vtab, b, kk)[4 q].
+enum { WV_VT_BNS, WV_VT_BNT, WV_VT_BSIG, WV_VT_BTANH, WV_VT_BRES, WV_VT_BSK0, WV_VT_BSK1, WV_VT_N };
+#define WV_VT_BLK (WV_VT_N * 16)   // floats per block
+#define WV_VT_F (32 * WV_VT_BLK)   // floats of the whole table (NB <= 32)
+__device__ __forceinline__ const float4 *wv_vt(const float *vtab, int blk, int kk) { return (const float4 *)(vtab + blk * WV_VT_BLK) + kk; }
+// dst_ = entry i_ of the table, fetched from where it lives in the model's arrays (a macro: as a function the address selection
+// moved instructions in eight kernels, EXPERIMENTS 14)
+#define WV_VT_FETCH(dst_, a_, i_)                                                                                       \
+  do {                                                                                                                  \
+    const int vb_ = (i_) / WV_VT_BLK, vq_ = ((i_) / 16) % WV_VT_N, vc_ = (i_) & 15;                                      \
+    const float *vp_ = vq_ == WV_VT_BNS ? (a_).bn_s + vb_ * WV_C + vc_                                                   \
+                       : vq_ == WV_VT_BNT ? (a_).bn_t + vb_ * WV_C + vc_                                                 \
+                       : vq_ < WV_VT_BRES ? (a_).b_gate + vb_ * 32 + (vq_ - WV_VT_BSIG) * 16 + vc_                       \
+                                          : (a_).b_rs + vb_ * 48 + (vq_ - WV_VT_BRES) * 16 + vc_;                        \
+    dst_ = *vp_;                                                                                                        \
+  } while (0)
 // a block's seven small vectors (this lane's channel group): read from the table one block AHEAD, behind the barrier, so
 // that no LDS round trip sits in front of the u write, the accumulators' initial values or the res | skip products
 // (the BatchNorm pair and the gate biases, which a block needs at once; the res | skip biases are requested at the top of their
 // own block and used ~1,500 cycles later: prefetching all seven costs 56 registers and spills)
 __device__ __forceinline__ void wv_vload(const float *vtab, int blk, int kk, wv_vblk &v) {
-  const float4 *vt = (const float4 *)(vtab + blk * 112) + kk;  // vector q: vt[4 q]
-  v.bns = vt[0]; v.bnt = vt[4]; v.bsig = vt[8]; v.btanh = vt[12];
+  const float4 *vt = wv_vt(vtab, blk, kk);
+  v.bns = vt[4 * WV_VT_BNS]; v.bnt = vt[4 * WV_VT_BNT]; v.bsig = vt[4 * WV_VT_BSIG]; v.btanh = vt[4 * WV_VT_BTANH];
 }
 // Written over a wave's MPW tiles (round 5: launches of more than 256 windows run FOUR waves x three tiles, two
 // workgroups per CU - the form that gave the split-bf16 loop 14 % at scale; up to 256 windows - one per CU - twelve waves x
@@ -246,8 +257,8 @@ __device__ __forceinline__ void wv_block_t(const wave_args &a, int blk, float *u
                                            bool hist_wave = false) {
   float *u = ubuf + (blk & 1) * 4 * UPL + kk * UPL + WV_PAD * 4;          // row 0 of this lane's channel-group plane
   const int d = (int)((a.dil4[blk >> 4] >> (4 * (blk & 15))) & 15);
-  const float4 *vt = (const float4 *)(vtab + blk * 112) + kk;
-  const float4 bres = vt[16], bsk0 = vt[20], bsk1 = vt[24];
+  const float4 *vt = wv_vt(vtab, blk, kk);
+  const float4 bres = vt[4 * WV_VT_BRES], bsk0 = vt[4 * WV_VT_BSK0], bsk1 = vt[4 * WV_VT_BSK1];
   f32x4 uv[MPW], as[MPW], at[MPW];
   f32x4 hv = {0.f, 0.f, 0.f, 0.f};
   if (HIST && hist_wave) hv = *(const f32x4 *)(hist + blk * (4 * WV_PAD * 4) + (kk * WV_PAD + j) * 4);
@@ -366,6 +377,103 @@ __device__ __forceinline__ float wv_softmax16(float v, int c, int NOUT) {
   return e / sum;
 }
 
+// LDS of wavenet_kernel, in floats (NB <= 32): ONE set of offsets; the kernel's array is sized from them.
+//   fp32:       [ u[2][WV_T + WV_PAD][16] | g [WV_T][16], later the head tile [WV_T][32] ] | vector table (transposed loop only)
+//   split-bf16: [ u planes (the fp32 u buffers' bytes) | three parameter pages (the head tile over them) | BatchNorm table ]
+//   under both, in the prologue only: the staged input [WV_T][WV_INLD] and, one-launch tick, the front end's mel side behind it
+constexpr int WV_U_F = 2 * (WV_T + WV_PAD) * WV_C;  // the two u buffers, causal pad rows included
+constexpr int WV_H_F = WV_T * WV_S;                 // the head tile (its first half: the row-major loop's g tiles)
+constexpr int WV_IN_F = WV_T * WV_INLD;             // the staged input
+constexpr int WV_PG_F = 3 * WV_PAGE_U4 * 4;         // three parameter pages
+constexpr int WV_BN_F = 32 * 8 * 4;                 // BatchNorm table [NB][2][4] float4
+static_assert(WV_H_F <= WV_PG_F, "the head tile lies over the parameter pages");
+#define WV_NVT(threads_) ((WV_VT_F + (threads_) - 1) / (threads_))        // vector-table entries per thread
+#define WV_NPL(threads_) ((WV_PAGE_U4 + (threads_) - 1) / (threads_))    // pieces of a parameter page per thread (the last one partial)
+
+// All NB blocks through wv_block_t<MPW_, UPL_, HIST_>: the parameters one block ahead in two register sets, the loop unrolled by
+// two.  pw_[0]: block 0's weights, requested in front of the barrier that publishes the vector table; the trailing arguments are
+// wv_block_t's hist, valid, hist_wave.  (A macro: as a function template the twelve-wave sequence kernels spilled 12 bytes,
+// EXPERIMENTS 14.)
+#define WV_BLOCKS_T(MPW_, UPL_, HIST_, a_, ubuf_, vtab_, j_, kk_, tl_, x_, skip_, pw_, ...)                                        \
+  do {                                                                                                                             \
+    wv_vblk pv[2];                                                                                                                 \
+    wv_vload(vtab_, 0, kk_, pv[0]);                                                                                                \
+    for (int blk = 0; blk < (a_).NB; blk += 2) {                                                                                   \
+      wv_block_t<MPW_, UPL_, HIST_>(a_, blk, ubuf_, vtab_, j_, kk_, tl_, x_, skip_, pw_[0], pw_[1], pv[0], pv[1], ##__VA_ARGS__);  \
+      if (blk + 1 < (a_).NB)                                                                                                       \
+        wv_block_t<MPW_, UPL_, HIST_>(a_, blk + 1, ubuf_, vtab_, j_, kk_, tl_, x_, skip_, pw_[1], pw_[0], pv[1], pv[0], ##__VA_ARGS__); \
+    }                                                                                                                              \
+  } while (0)
+
+// Where a posterior goes (lane c_ holds column c_ of launch row w_ + k_): a streaming tick's as ONE 8-byte {value, tick number} store
+// the host polls (common.h), anything else as its row of `out`.  (A macro: as a function it moved instructions in the four fp32
+// one-launch tick kernels, EXPERIMENTS 14.)
+#define WV_POST_STORE(tag_, out_, NOUT_, w_, k_, c_, p_)                       \
+  do {                                                                        \
+    if ((tag_).slots) {                                                       \
+      if ((c_) == (tag_).pidx) tick_tag_store(tag_, w_, p_, k_);              \
+    } else if ((c_) < (NOUT_)) {                                              \
+      (out_)[(size_t)((w_) + (k_)) * (NOUT_) + (c_)] = (p_);                  \
+    }                                                                         \
+  } while (0)
+
+// Input 1x1 conv + ReLU of one 16-row tile of the staged input -> x_ in accumulator layout, and the tile's skip sums start at zero.
+// row_: this lane's row j of the tile, in rows of in_lds_.  TR_: the operands swapped - lane = time column, registers = channels
+// 4 kk + r, bias b_in_[4 kk + r]; otherwise lane = column j (bias_: its b_in), registers = rows 4 kk + r.  (A macro: as a function
+// template it moved instructions in eight window and sequence kernels, EXPERIMENTS 14.)
+#define WV_INPUT_TILE(TR_, in_lds_, row_, kk_, bw_, b_in_, bias_, x_, skip_)                          \
+  do {                                                                                                \
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};                                                                 \
+    _Pragma("unroll") for (int kb = 0; kb < 3; ++kb) {                                                \
+      const float4 av = *(const float4 *)((in_lds_) + (row_) * WV_INLD + kb * 16 + (kk_) * 4);        \
+      if (TR_) {                                                                                      \
+        MFMA4(acc, bw_[kb], av);                                                                      \
+      } else {                                                                                        \
+        MFMA4(acc, av, bw_[kb]);                                                                      \
+      }                                                                                               \
+    }                                                                                                 \
+    _Pragma("unroll") for (int r = 0; r < 4; ++r)                                                     \
+      x_[r] = fmaxf(acc[r] + ((TR_) ? (b_in_)[(unsigned)((kk_) * 4 + r)] : (bias_)), 0.f);            \
+    skip_[0] = (f32x4){0.f, 0.f, 0.f, 0.f};                                                           \
+    skip_[1] = (f32x4){0.f, 0.f, 0.f, 0.f};                                                           \
+  } while (0)
+
+// a time step's skip sum (the encoder's output row e [32]) out of the transposed state: lane = time column, four consecutive
+// channels per register quad
+__device__ __forceinline__ void wv_enc_store_t(float *e, int kk, const f32x4 (&sk)[2]) {
+  *(float4 *)(e + kk * 4) = make_float4(sk[0][0], sk[0][1], sk[0][2], sk[0][3]);
+  *(float4 *)(e + 16 + kk * 4) = make_float4(sk[1][0], sk[1][1], sk[1][2], sk[1][3]);
+}
+
+// Staging a window of wavenet_kernel, in_lds[t][0..47] = the window's n4_ float4s (a contiguous [rows][n_mel] block, n_mel % 4 == 0,
+// 16-byte aligned) and zeros elsewhere, in three steps.  All of a thread's 16-byte loads are issued first (unconditional, from clamped
+// addresses: nothing for the next load to wait for), the zero fill runs while they are in flight, then - behind a barrier - the
+// 16-byte LDS stores.  tid_ / threads_: the thread and the workgroup's size.  (Macros: as functions over a small struct they moved
+// instructions in all eleven window kernels, EXPERIMENTS 14.)
+#define WV_STAGE_SQ(threads_) ((WV_T * WV_INLD / 4 + (threads_) - 1) / (threads_))  // float4s per thread
+#define WV_STAGE_REQUEST(st_, src_, n4_, tid_, threads_)                          \
+  do {                                                                            \
+    _Pragma("unroll") for (int sq_ = 0; sq_ < WV_STAGE_SQ(threads_); ++sq_) {     \
+      const int si_ = (tid_) + sq_ * (threads_);                                  \
+      st_[sq_] = *(const f32x4 *)((src_) + 4 * (si_ < (n4_) ? si_ : (n4_) - 1));  \
+    }                                                                             \
+  } while (0)
+#define WV_STAGE_ZERO(in_lds_, tid_, threads_)                                    \
+  do {                                                                            \
+    for (int si_ = (tid_); si_ < WV_T * WV_INLD / 4; si_ += (threads_))           \
+      ((float4 *)(in_lds_))[si_] = make_float4(0.f, 0.f, 0.f, 0.f);               \
+  } while (0)
+#define WV_STAGE_STORE(st_, in_lds_, n4_, n_mel_, tid_, threads_)                 \
+  do {                                                                            \
+    _Pragma("unroll") for (int sq_ = 0; sq_ < WV_STAGE_SQ(threads_); ++sq_) {     \
+      const int si_ = (tid_) + sq_ * (threads_);                                  \
+      if (si_ < (n4_)) {                                                          \
+        const int se_ = si_ * 4, st0_ = se_ / (n_mel_), sc_ = se_ - st0_ * (n_mel_); \
+        *(f32x4 *)((in_lds_) + st0_ * WV_INLD + sc_) = st_[sq_];                  \
+      }                                                                           \
+    }                                                                             \
+  } while (0)
+
 // FP32T: the fp32 block loop in the TRANSPOSED form of the split-bf16 loop (channels x time; round 3) - see its comment below.
 // TICK = 1 / 2 (fp32 / fp64 transform) - ONE launch per streaming tick (round 5; crnn.hip's crnn_stream_kernel<FE> has the full
 // story): workgroup 2 s + k is window k of stream s's tick; it reads the stream's control words and samples over the bus, waves
@@ -379,15 +487,9 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
   constexpr bool TRANSPOSED = SPLIT_BF16 || FP32T;  // state layout: lane = time column, four consecutive channels per register quad
   static_assert(!(SPLIT_BF16 && FP32T), "one arithmetic mode");
   static_assert(WV_MPW * WV_NW == 12, "12 row tiles");
-  // LDS: region A = staged input [192][48] (prologue only), later u[2][208][16] + g[192][16]
-  // split-bf16: u planes (same bytes as the fp32 u buffers) + two parameter pages (next to / under the head's tile)
-  constexpr int LDS_FP32 = WV_T * WV_INLD > (2 * (WV_T + WV_PAD) * WV_C + WV_T * WV_S) ? WV_T * WV_INLD
-                                                                                       : (2 * (WV_T + WV_PAD) * WV_C + WV_T * WV_S);
-  constexpr int LDS_BF16 = 2 * (WV_T + WV_PAD) * WV_C + 3 * WV_PAGE_U4 * 4 + 32 * 8 * 4;  // u planes + 3 pages + BatchNorm table (NB <= 32)
-  constexpr int LDS_F32T = 2 * (WV_T + WV_PAD) * WV_C + WV_T * WV_S + 32 * 7 * 16;        // u buffers + head tile + per-block vectors (NB <= 32)
-  constexpr int LDS_A = SPLIT_BF16 && LDS_BF16 > LDS_FP32 ? LDS_BF16 : LDS_FP32;
-  constexpr int LDS_B = FP32T && LDS_F32T > LDS_A ? LDS_F32T : LDS_A;
-  __shared__ __align__(16) float lds[TICK && WT_END > LDS_B ? WT_END : LDS_B];
+  constexpr int BLOCKS_F = SPLIT_BF16 ? WV_U_F + WV_PG_F + WV_BN_F : FP32T ? WV_U_F + WV_H_F + WV_VT_F : WV_U_F + WV_H_F;
+  constexpr int STAGE_F = TICK ? WT_END : WV_IN_F;
+  __shared__ __align__(16) float lds[BLOCKS_F > STAGE_F ? BLOCKS_F : STAGE_F];
   __shared__ float red[WV_NW][16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kk = lane >> 4;
@@ -396,7 +498,7 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
 
   f32x4 x[WV_MPW], skip[WV_MPW][2];
   float *ubuf = lds;                                    // [2][WV_T + WV_PAD][16]
-  float *gbuf = lds + 2 * (WV_T + WV_PAD) * WV_C;       // [WV_T][16] (wave-private tiles)
+  float *gbuf = lds + WV_U_F;                             // [WV_T][16] (wave-private tiles)
   float *hbuf = gbuf;                                   // detect head reuses it as [WV_T][32]
   if (HEAD_ONLY) {
     // detect.tflite alone (reference detect_model(x), wakeword/tflite.py:231): skip sums come from memory
@@ -445,9 +547,9 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
   // ... and what the block loop's LDS tables are filled from (split-bf16: parameter pages 0 and 1 and the BatchNorm table; fp32
   // transposed: the per-block vector table): requested here, parked in LDS once the staged input is dead - as loops of
   // "load, store" behind the input conv they were three to four round trips to L2 in a row on every window's critical path
-  constexpr int NPL = (WV_PAGE_U4 + WV_THREADS - 1) / WV_THREADS;                 // page pieces per thread (the last one partial)
+  constexpr int NPL = WV_NPL(WV_THREADS);
   static_assert(NPL >= 2 && NPL <= 4, "page pieces per thread");
-  constexpr int NVT = (32 * 7 * 16 + WV_THREADS - 1) / WV_THREADS;                // fp32 vector-table entries per thread (NB <= 32)
+  constexpr int NVT = WV_NVT(WV_THREADS);
   // (clang ext-vector elements: arrays of HIP's struct vector types stayed in scratch memory)
   u32x4 pg0[NPL], pg1[NPL];
   f32x4 bnv = {0.f, 0.f, 0.f, 0.f};
@@ -467,11 +569,8 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
 #pragma unroll
     for (int q = 0; q < NVT; ++q) {
       int i = tid + q * WV_THREADS;
-      i = i < a.NB * 7 * 16 ? i : 0;
-      const int b = i / 112, v = (i / 16) % 7, c = i & 15;
-      const float *p = v == 0 ? a.bn_s + b * WV_C + c : v == 1 ? a.bn_t + b * WV_C + c : v < 4 ? a.b_gate + b * 32 + (v - 2) * 16 + c
-                                                                                             : a.b_rs + b * 48 + (v - 4) * 16 + c;
-      vte[q] = *p;
+      i = i < a.NB * WV_VT_BLK ? i : 0;
+      WV_VT_FETCH(vte[q], a, i);
     }
   }
 
@@ -494,37 +593,22 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
     const fe_tick_ctl c = fe_tick_decode(t_cw, k, slots);
     if (c.idle) return;
     // the rows that were there before: the block [(pos + k + 2) % (T + 1), + T - nfk) of the stream's mirrored ring
-    constexpr int SQ = (WV_T * WV_INLD / 4 + WV_THREADS - 1) / WV_THREADS;
-    f32x4 st[SQ];
+    f32x4 st[WV_STAGE_SQ(WV_THREADS)];
     int n4 = 0;
     if (c.window) {
       const float *src = a.mel + ((size_t)s * fe.HR + c.b) * a.n_mel;  // (160-byte rows of a hipMalloc'ed history: 16-byte aligned)
       n4 = ((T - c.nfk) * a.n_mel) >> 2;
-#pragma unroll
-      for (int q = 0; q < SQ; ++q) {
-        const int i = tid + q * WV_THREADS;
-        st[q] = *(const f32x4 *)(src + 4 * (i < n4 ? i : n4 - 1));
-      }
+      WV_STAGE_REQUEST(st, src, n4, tid, WV_THREADS);
     }
     const fe_tick_lds<RT> l = FE_TICK_LDS(RT, lds + WT_BASE);
     ((f32x4 *)l.wl)[tid] = wlq;
     if (tid < 256 && (tid >> 7) == c.par) ((f32x4 *)l.x)[tid & 127] = ringq;
     if (tid < 40) ((uint4 *)l.xs)[tid] = t_raw;
-    if (c.window)
-      for (int i = tid; i < WV_T * WV_INLD / 4; i += WV_THREADS) ((float4 *)in_lds)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c.window) WV_STAGE_ZERO(in_lds, tid, WV_THREADS);
     __syncthreads();
     // ---- [ring | new samples]: normalise, clip, pre-emphasise
     for (int i = tid; i < WW_CHUNK; i += WV_THREADS) l.x[c.fill + i] = fe_sample(l.xs, i, c.par ? carry1 : carry0, fe.cv);
-    if (c.window) {  // (the zero fill is complete: the old rows go in beside the normalisation)
-#pragma unroll
-      for (int q = 0; q < SQ; ++q) {
-        const int i = tid + q * WV_THREADS;
-        if (i < n4) {
-          const int e = i * 4, t = e / a.n_mel, c = e - t * a.n_mel;
-          *(f32x4 *)(in_lds + t * WV_INLD + c) = st[q];
-        }
-      }
-    }
+    if (c.window) WV_STAGE_STORE(st, in_lds, n4, a.n_mel, tid, WV_THREADS);  // (the zero fill is complete: the old rows go in beside the normalisation)
     __syncthreads();
     // tflite.py:156-158: the carry is the un-emphasised last sample
     if (c.writer && tid == 0) fe.prev[(size_t)(c.par ^ 1) * fe.S + s] = fe_norm(l.xs[WW_CHUNK - 1], fe.cv);
@@ -547,33 +631,17 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
     const float *src = a.mel + row * a.n_mel;
     const int n = valid * a.n_mel;
     if ((a.n_mel & 3) == 0 && ((((uintptr_t)src) & 15) == 0)) {
-      // the window is one contiguous [valid][n_mel] block and a row is a whole number of float4s.  All of a thread's
-      // 16-byte loads are issued first (unconditional, from clamped addresses: nothing for the next load to wait for), the
-      // zero fill runs while they are in flight, then the 16-byte LDS stores
-      constexpr int SQ = (WV_T * WV_INLD / 4 + WV_THREADS - 1) / WV_THREADS;
+      // the window is one contiguous [valid][n_mel] block and a row is a whole number of float4s
       const int n4 = n >> 2;
-      f32x4 st[SQ];
+      f32x4 st[WV_STAGE_SQ(WV_THREADS)];
 #pragma unroll
-      for (int q = 0; q < SQ; ++q) st[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (n4 > 0) {
-#pragma unroll
-        for (int q = 0; q < SQ; ++q) {
-          const int i = tid + q * WV_THREADS;
-          st[q] = *(const f32x4 *)(src + 4 * (i < n4 ? i : n4 - 1));
-        }
-      }
-      for (int i = tid; i < WV_T * WV_INLD / 4; i += WV_THREADS) ((float4 *)in_lds)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int q = 0; q < WV_STAGE_SQ(WV_THREADS); ++q) st[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (n4 > 0) WV_STAGE_REQUEST(st, src, n4, tid, WV_THREADS);
+      WV_STAGE_ZERO(in_lds, tid, WV_THREADS);
       __syncthreads();
-#pragma unroll
-      for (int q = 0; q < SQ; ++q) {
-        const int i = tid + q * WV_THREADS;
-        if (i < n4) {
-          const int e = i * 4, t = e / a.n_mel, c = e - t * a.n_mel;
-          *(f32x4 *)(in_lds + t * WV_INLD + c) = st[q];
-        }
-      }
-    } else {
-      for (int i = tid; i < WV_T * WV_INLD / 4; i += WV_THREADS) ((float4 *)in_lds)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      WV_STAGE_STORE(st, in_lds, n4, a.n_mel, tid, WV_THREADS);
+    } else {  // any other pointer or row length: four bytes at a time
+      WV_STAGE_ZERO(in_lds, tid, WV_THREADS);
       __syncthreads();
       for (int i = tid; i < n; i += WV_THREADS) {
         int t = i / a.n_mel, c = i - t * a.n_mel;
@@ -585,26 +653,8 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
 
   // ---- input 1x1 conv + ReLU -> x in accumulator layout.  m-tile mi of this wave covers rows
   // (wave*3 + mi)*16 .. +15; lane holds rows kk*4 + r, column j.
-  {
 #pragma unroll
-    for (int mi = 0; mi < WV_MPW; ++mi) {
-      const int t0 = (wave * WV_MPW + mi) * 16;
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kb = 0; kb < 3; ++kb) {
-        const float4 av = *(const float4 *)(in_lds + (t0 + j) * WV_INLD + kb * 16 + kk * 4);
-        if (TRANSPOSED) {  // operands swapped: the transposed tile (channels x time)
-          MFMA4(acc, bw[kb], av);
-        } else {
-          MFMA4(acc, av, bw[kb]);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) x[mi][r] = fmaxf(acc[r] + (TRANSPOSED ? a.b_in[kk * 4 + r] : bias), 0.f);
-      skip[mi][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      skip[mi][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-  }
+  for (int mi = 0; mi < WV_MPW; ++mi) WV_INPUT_TILE(TRANSPOSED, in_lds, (wave * WV_MPW + mi) * 16 + j, kk, bw, a.b_in, bias, x[mi], skip[mi]);
   __syncthreads();  // in_lds is dead from here on
 
   if (FP32T) {
@@ -619,11 +669,11 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
     //      consecutive 16 bytes and the lane groups of ds_read_b128 / ds_write_b128 (MI355X_MICROARCH.md, LDS) cover all 64 banks
     //      once (row-major [row][16] put the 8 lanes of a write group on 2 bank quads: 5.3 M conflict cycles per 256 windows).  The conv biases are the
     //      accumulators' initial values (per-lane float4 by channel group); all blocks' small vectors sit in one LDS table.
-    float *vtab = lds + 2 * (WV_T + WV_PAD) * WV_C + WV_T * WV_S;  // [NB][7][16]: bn_s, bn_t, b_sig, b_tanh, b_res, b_skip0, b_skip1
+    float *vtab = hbuf + WV_H_F;
 #pragma unroll
     for (int q = 0; q < NVT; ++q) {
       const int i = tid + q * WV_THREADS;
-      if (i < a.NB * 7 * 16) vtab[i] = vte[q];
+      if (i < a.NB * WV_VT_BLK) vtab[i] = vte[q];
     }
     constexpr int UPL = (WV_T + WV_PAD) * 4;  // floats per channel-group plane
     static_assert(UPL % 64 == 0, "u planes must start on the same bank");
@@ -635,12 +685,7 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
     wv_wload(a, 0, j, kk, pw[0]);
     const int tl = wave * WV_MPW * 16 + j;  // this lane's time column in the wave's first tile (tile mi: + 16 mi)
     __syncthreads();               // table + zero rows
-    wv_vblk pv[2];
-    wv_vload(vtab, 0, kk, pv[0]);
-    for (int blk = 0; blk < a.NB; blk += 2) {
-      wv_block_t<WV_MPW, UPL, false>(a, blk, ubuf, vtab, j, kk, tl, x, skip, pw[0], pw[1], pv[0], pv[1]);
-      if (blk + 1 < a.NB) wv_block_t<WV_MPW, UPL, false>(a, blk + 1, ubuf, vtab, j, kk, tl, x, skip, pw[1], pw[0], pv[1], pv[0]);
-    }
+    WV_BLOCKS_T(WV_MPW, UPL, false, a, ubuf, vtab, j, kk, tl, x, skip, pw);
     __syncthreads();
   } else if (!SPLIT_BF16) {
   // causal zero rows of both u buffers
@@ -739,7 +784,7 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
     // block b+1 publishes it, so in block b+2 every wave may read its operands BEFORE that block's barrier.
     // (Per-wave register prefetch cost 1 us per block: the loads can only be issued once the registers are free, i.e. late;
     // double-buffered pages read after the barrier left ~1000 cycles of operand reads on the critical path.)
-    uint4 *pages = (uint4 *)(lds + 2 * (WV_T + WV_PAD) * WV_C);                  // [3][WV_PAGE_U4]
+    uint4 *pages = (uint4 *)(lds + WV_U_F);                                         // [3][WV_PAGE_U4]
     const uint4 *gpage = a.wpk;
     auto pclamp = [&](int q) { return tid + q * WV_THREADS < WV_PAGE_U4 ? tid + q * WV_THREADS : WV_PAGE_U4 - 1; };
     const int pidx0 = pclamp(0), pidx1 = pclamp(1), pidx2 = pclamp(2), pidx3 = pclamp(3);
@@ -753,7 +798,7 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
     }
     // The BatchNorm vectors are needed BEFORE a block's barrier (they produce u), i.e. before that block's
     // page is published: all blocks' copies live in their own small table, filled once.
-    float4 *bnall = (float4 *)(pages + 3 * WV_PAGE_U4);                           // [NB][2][4] float4 = scale, shift
+    float4 *bnall = (float4 *)(lds + WV_U_F + WV_PG_F);                                // [NB][2][4] float4 = scale, shift
     if (tid < a.NB * 8) *(f32x4 *)(bnall + tid) = bnv;
     __syncthreads();
     const unsigned long long dil_lo = a.dil4[0], dil_hi = a.dil4[1];             // kernel-argument SGPRs: no load inside the loop
@@ -895,10 +940,7 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
     for (int mi = 0; mi < WV_MPW; ++mi) {
       if (TRANSPOSED) {  // transposed state: lane = time column, four consecutive channels per register quad
         const int t = (wave * WV_MPW + mi) * 16 + j;
-        if (t < T) {
-          *(float4 *)(e + (size_t)t * WV_S + kk * 4) = make_float4(skip[mi][0][0], skip[mi][0][1], skip[mi][0][2], skip[mi][0][3]);
-          *(float4 *)(e + (size_t)t * WV_S + 16 + kk * 4) = make_float4(skip[mi][1][0], skip[mi][1][1], skip[mi][1][2], skip[mi][1][3]);
-        }
+        if (t < T) wv_enc_store_t(e + (size_t)t * WV_S, kk, skip[mi]);
         continue;
       }
 #pragma unroll
@@ -934,14 +976,7 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
 #pragma unroll
     for (int q = 1; q < WV_NW; ++q) v = fmaxf(v, red[q][tid]);
     const float p = wv_softmax16(v, tid, a.NOUT);
-    if (a.tag.slots) {  // a streaming tick: the posterior as ONE 8-byte {value, tick number} store the host polls (common.h)
-      if (tid == a.tag.pidx) {
-        const unsigned long long word = (unsigned long long)__float_as_uint(p) | ((unsigned long long)a.tag.seq << 32);
-        __hip_atomic_store(a.tag.slots + w, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    } else if (tid < a.NOUT) {
-      a.out[(size_t)w * a.NOUT + tid] = p;
-    }
+    WV_POST_STORE(a.tag, a.out, a.NOUT, w, 0, tid, p);
   }
 }
 
@@ -981,15 +1016,62 @@ struct wave_seq_args {
   float *post;                  // [rows of the call]: the posterior column of every new row (the one-wave form's tail)
 };
 
+// A stream's ring of its last P logit rows [P][16] and zpos = {the slot of the next row, rows held (<= P)}: the slot of the row
+// `off` rows from the next one (off >= -P), and the advance by n rows
+__device__ __forceinline__ int wv_ring_slot(int pos, int off, int P) { return (pos + off + P) % P; }
+__device__ __forceinline__ void wv_zpos_advance(int32_t *zpos, int sid, int pos, int held, int n, int P) {
+  zpos[2 * sid] = (pos + n) % P;
+  zpos[2 * sid + 1] = held + n < P ? held + n : P;
+}
+
+// The tail of the one-wave forms (ROWS_: 2, a tick, or 16, a feed).  The tile's first n_ <= ROWS_ rows are a stream's new logit rows (y_: register r of lane group kk_
+// is row 4 kk_ + r, without the last bias b2_): the pooled maximum over the ring's rows up to each new row, the softmax - SINK_, a
+// statement, gets new row k's posterior p in lanes 0..15, lane c = column c - then the ring and its position.  zl_: [ROWS_][16]
+// floats of LDS.  (A macro: as a function template taking the sink as a callable it moved instructions in both kernels.)
+#define WV_RING_TAIL(ROWS_, q_, sid_, n_, y_, b2_, zl_, lane_, j_, kk_, NOUT_, SINK_)                                            \
+  do {                                                                                                                           \
+    if ((ROWS_) == 2) { /* (written out: as the r-loop below under `4 kk + r < 2` the tick's kernel was scheduled otherwise) */  \
+      if ((kk_) == 0) {                                                                                                          \
+        (zl_)[(j_)] = (y_)[0] + (b2_);                                                                                           \
+        (zl_)[16 + (j_)] = (y_)[1] + (b2_);                                                                                      \
+      }                                                                                                                          \
+    } else {                                                                                                                     \
+      _Pragma("unroll") for (int r = 0; r < 4; ++r) (zl_)[((kk_) * 4 + r) * 16 + (j_)] = (y_)[r] + (b2_);                        \
+    }                                                                                                                            \
+    wsync();                                                                                                                     \
+    const int P = (q_).P, pos = (q_).zpos[2 * (sid_)], held = (q_).zpos[2 * (sid_) + 1];                                         \
+    float *ring = (q_).zring + (size_t)(sid_) * P * 16;                                                                          \
+    for (int k = 0; k < (n_); ++k) {                                                                                             \
+      const int cnt = held + k + 1 < P ? held + k + 1 : P; /* rows of the pool that ends at new row k */                         \
+      float m = -INFINITY;                                                                                                       \
+      for (int i = (kk_); i < cnt; i += 4) { /* i rows back from it: a new row, or the ring's */                                 \
+        const float v = i <= k ? (zl_)[(k - i) * 16 + (j_)] : ring[(size_t)wv_ring_slot(pos, k - i, P) * 16 + (j_)];             \
+        m = fmaxf(m, v);                                                                                                         \
+      }                                                                                                                          \
+      m = fmaxf(m, __shfl_xor(m, 16));                                                                                           \
+      m = fmaxf(m, __shfl_xor(m, 32));                                                                                           \
+      if ((lane_) < 16) {                                                                                                        \
+        const float p = wv_softmax16(m, lane_, NOUT_);                                                                           \
+        SINK_;                                                                                                                   \
+      }                                                                                                                          \
+    }                                                                                                                            \
+    /* the ring is read before it is written: a tick's new row 1 takes the slot of the oldest row of new row 0's pool (a feed's */ \
+    /* n <= 16 < P: a new row never takes the slot of another new row) */                                                        \
+    wsync();                                                                                                                     \
+    if ((lane_) < 16)                                                                                                            \
+      for (int k = 0; k < (n_); ++k) ring[(size_t)((pos + k) % P) * 16 + (lane_)] = (zl_)[k * 16 + (lane_)];                     \
+    if ((lane_) == 0) wv_zpos_advance((q_).zpos, sid_, pos, held, n_, P);                                                        \
+  } while (0)
+
 template <int NW, bool STREAM, bool FEED = false>
 __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(wave_args a, wave_seq_args q) {
   static_assert(!(STREAM && FEED) && (!FEED || NW == 1 || NW == 12), "a feed is not a tick; its forms are one wave and twelve");
   constexpr int CH = NW * 16, THREADS = NW * 64, UPL = (CH + WV_PAD) * 4;
-  constexpr int U_F = 2 * 4 * UPL, H_F = CH * WV_S, IN_F = CH * WV_INLD, V_F = 32 * 7 * 16, HB = 4 * WV_PAD * 4;
+  constexpr int U_F = 2 * 4 * UPL, H_F = CH * WV_S, IN_F = CH * WV_INLD, V_F = WV_VT_F, HB = 4 * WV_PAD * 4;
   static_assert(UPL % 64 == 0, "u planes must start on the same bank");
   static_assert(IN_F <= U_F + H_F, "the staged input lies under the u buffers and the head tile");
   static_assert(!STREAM || NW == 1, "a stream's tick is one tile");
-  // [ u[2][4][UPL] | head tile [CH][32] ] (the staged input [CH][48] under both) | vector table [32][7][16] | history [32][HB]
+  // [ u[2][4][UPL] | head tile [CH][32] ] (the staged input [CH][48] under both) | vector table (WV_VT_F) | history [32][HB]
   __shared__ __align__(16) float lds[U_F + H_F + V_F + 32 * HB];
   float *ubuf = lds, *hbuf = lds + U_F, *vtab = hbuf + H_F, *hist = vtab + V_F, *in_lds = lds;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1012,11 +1094,8 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(
     const wv_seg sg = q.segs[w];
     row0 = sg.row0; n = sg.n; skipn = sg.skip;
   }
-  for (int i = tid; i < a.NB * 7 * 16; i += THREADS) {  // all blocks' small vectors: [NB][7][16] = bn_s, bn_t, b_sig, b_tanh, b_res, b_skip0, b_skip1
-    const int b = i / 112, v = (i / 16) % 7, c = i & 15;
-    const float *p = v == 0 ? a.bn_s + b * WV_C + c : v == 1 ? a.bn_t + b * WV_C + c : v < 4 ? a.b_gate + b * 32 + (v - 2) * 16 + c
-                                                                                           : a.b_rs + b * 48 + (v - 4) * 16 + c;
-    vtab[i] = *p;
+  for (int i = tid; i < a.NB * WV_VT_BLK; i += THREADS) {  // all blocks' small vectors
+    WV_VT_FETCH(vtab[i], a, i);
   }
   {
     const f32x4 *sp = (const f32x4 *)(q.state + (size_t)sid * a.NB * HB);
@@ -1057,37 +1136,17 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(
     __syncthreads();
     // ---- input 1x1 conv + ReLU -> x, transposed (lane = time column, registers = channels 4 kk + r): wavenet_kernel's
     f32x4 x[1], skip[1][2];
-    {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kb = 0; kb < 3; ++kb) {
-        const float4 av = *(const float4 *)(in_lds + tl * WV_INLD + kb * 16 + kc * 4);
-        MFMA4(acc, bw[kb], av);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) x[0][r] = fmaxf(acc[r] + a.b_in[(unsigned)(kc * 4 + r)], 0.f);
-      skip[0][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      skip[0][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
+    WV_INPUT_TILE(true, in_lds, tl, kc, bw, a.b_in, 0.f, x[0], skip[0]);
     wv_wblk pw[2];
     wv_wload(a, 0, jc, kc, pw[0]);
     __syncthreads();  // in_lds is dead from here on
-    wv_vblk pv[2];
-    wv_vload(vtab, 0, kc, pv[0]);
-    for (int blk = 0; blk < a.NB; blk += 2) {
-      wv_block_t<1, UPL, true>(a, blk, ubuf, vtab, jc, kc, tl, x, skip, pw[0], pw[1], pv[0], pv[1], hist, valid, wc == 0);
-      if (blk + 1 < a.NB) wv_block_t<1, UPL, true>(a, blk + 1, ubuf, vtab, jc, kc, tl, x, skip, pw[1], pw[0], pv[1], pv[0], hist, valid, wc == 0);
-    }
+    WV_BLOCKS_T(1, UPL, true, a, ubuf, vtab, jc, kc, tl, x, skip, pw, hist, valid, wc == 0);
     // ---- a kept row's skip sum and logits
     int td = tid;
     asm volatile("" : "+v"(td));
     const int wd = td >> 6, jd = td & 15, kd = (td >> 4) & 3;
     const int ts = c0 + wd * 16 + jd;  // this lane's time column, in rows of the segment
-    if (q.enc && ts >= skipn && ts < n) {
-      float *e = q.enc + (size_t)(row0 + ts) * WV_S;
-      *(float4 *)(e + kd * 4) = make_float4(skip[0][0][0], skip[0][0][1], skip[0][0][2], skip[0][0][3]);
-      *(float4 *)(e + 16 + kd * 4) = make_float4(skip[0][1][0], skip[0][1][1], skip[0][1][2], skip[0][1][3]);
-    }
+    if (q.enc && ts >= skipn && ts < n) wv_enc_store_t(q.enc + (size_t)(row0 + ts) * WV_S, kd, skip[0]);
     wv_head_w hw;
     wv_head_load(a, jd, kd, hw);
     y = wv_head_tile<true>(skip[0], hbuf + wd * 16 * WV_S, hw, jd, kd);  // (wave-private tile: no barrier)
@@ -1100,88 +1159,16 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(
       }
     }
   }
-  if (STREAM) {
-    // ---- the tick's n <= 2 new logit rows (rows 0, 1 of the tile: registers 0, 1 of lanes 0..15), the pooled maximum over the
-    //      ring's rows up to each, the softmax, the ring
-    float *zl = hbuf;  // [2][16]
-    if (kk == 0) {
-      zl[j] = y[0] + b2;
-      zl[16 + j] = y[1] + b2;
-    }
-    wsync();
-    const int P = q.P, pos = q.zpos[2 * sid], held = q.zpos[2 * sid + 1];
-    float *ring = q.zring + (size_t)sid * P * 16;
-    for (int k = 0; k < n; ++k) {
-      const int cnt = held + k + 1 < P ? held + k + 1 : P;  // rows of the pool that ends at new row k
-      float m = -INFINITY;
-      for (int i = kk; i < cnt; i += 4) {                   // i rows back from it: a new row, or the ring's
-        const float v = i <= k ? zl[(k - i) * 16 + j] : ring[(size_t)((pos + k - i + P) % P) * 16 + j];
-        m = fmaxf(m, v);
-      }
-      m = fmaxf(m, __shfl_xor(m, 16));
-      m = fmaxf(m, __shfl_xor(m, 32));
-      if (lane < 16) {
-        const float p = wv_softmax16(m, lane, a.NOUT);
-        if (emit) {
-          if (a.tag.slots) {
-            if (lane == a.tag.pidx) {
-              const unsigned long long word = (unsigned long long)__float_as_uint(p) | ((unsigned long long)a.tag.seq << 32);
-              __hip_atomic_store(a.tag.slots + 2 * sid + k, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-          } else if (lane < a.NOUT) {
-            q.out[(size_t)(2 * sid + k) * a.NOUT + lane] = p;
-          }
-        }
-      }
-    }
-    wsync();  // the ring is read before it is written: new row 1 takes the slot of the oldest row of new row 0's pool
-    if (lane < 16)
-      for (int k = 0; k < n; ++k) ring[(size_t)((pos + k) % P) * 16 + lane] = zl[k * 16 + lane];
-    if (lane == 0) {
-      q.zpos[2 * sid] = (pos + n) % P;
-      q.zpos[2 * sid + 1] = held + n < P ? held + n : P;
-    }
+  if (STREAM) {  // the tick's n <= 2 new rows; a posterior leaves, as a tag or a row of `out`, when the segment's emit bit is set
+    WV_RING_TAIL(2, q, sid, n, y, b2, hbuf, lane, j, kk, a.NOUT, if (emit) WV_POST_STORE(a.tag, q.out, a.NOUT, 2 * sid, k, lane, p));
+  }
+  if (FEED && NW == 1) {  // the n <= 16 new rows of the tile; every row's posterior leaves
+    WV_RING_TAIL(16, q, sid, n, y, b2, hbuf, lane, j, kk, a.NOUT, if (lane == a.tag.pidx) q.post[row0 + k] = p);
+  }
+  if (STREAM || (FEED && (fflags & 2))) {  // the history returns to the stream's state (a feed: from the stream's last segment)
     __syncthreads();
     f32x4 *sp = (f32x4 *)(q.state + (size_t)sid * a.NB * HB);
     for (int i = tid; i < a.NB * HB / 4; i += THREADS) sp[i] = ((const f32x4 *)hist)[i];
-  }
-  if (FEED) {
-    if (NW == 1) {
-      // ---- the tick's tail for the n <= 16 new logit rows of the tile: the pooled maximum over the ring's rows up to each, the
-      //      softmax, the ring.  Every row's posterior leaves.
-      float *zl = hbuf;  // [16][16]
-#pragma unroll
-      for (int r = 0; r < 4; ++r) zl[(kk * 4 + r) * 16 + j] = y[r] + b2;
-      wsync();
-      const int P = q.P, pos = q.zpos[2 * sid], held = q.zpos[2 * sid + 1];
-      float *ring = q.zring + (size_t)sid * P * 16;
-      for (int k = 0; k < n; ++k) {
-        const int cnt = held + k + 1 < P ? held + k + 1 : P;
-        float m = -INFINITY;
-        for (int i = kk; i < cnt; i += 4) {
-          const float v = i <= k ? zl[(k - i) * 16 + j] : ring[(size_t)((pos + k - i + P) % P) * 16 + j];
-          m = fmaxf(m, v);
-        }
-        m = fmaxf(m, __shfl_xor(m, 16));
-        m = fmaxf(m, __shfl_xor(m, 32));
-        if (lane < 16) {
-          const float p = wv_softmax16(m, lane, a.NOUT);
-          if (lane == a.tag.pidx) q.post[row0 + k] = p;
-        }
-      }
-      wsync();  // the ring is read before it is written (n <= 16 < P: a new row never takes the slot of another new row)
-      if (lane < 16)
-        for (int k = 0; k < n; ++k) ring[(size_t)((pos + k) % P) * 16 + lane] = zl[k * 16 + lane];
-      if (lane == 0) {
-        q.zpos[2 * sid] = (pos + n) % P;
-        q.zpos[2 * sid + 1] = held + n < P ? held + n : P;
-      }
-    }
-    if (fflags & 2) {
-      __syncthreads();
-      f32x4 *sp = (f32x4 *)(q.state + (size_t)sid * a.NB * HB);
-      for (int i = tid; i < a.NB * HB / 4; i += THREADS) sp[i] = ((const f32x4 *)hist)[i];
-    }
   }
 }
 
@@ -1202,7 +1189,7 @@ __global__ __launch_bounds__(256) void wave_feed_pool_kernel(const float *z, con
     float x = -INFINITY;
     if (c < NOUT) {
       if (v >= 0) x = z[(d.row0 + v) * NOUT + c];
-      else if (v >= -held) x = ring[(size_t)((pos + (int)v + P) % P) * 16 + c];
+      else if (v >= -held) x = ring[(size_t)wv_ring_slot(pos, (int)v, P) * 16 + c];
     }
     pool_tile[i * 16 + c] = x;
   }
@@ -1228,10 +1215,7 @@ __global__ __launch_bounds__(256) void wave_feed_ring_kernel(const float *z, con
     ring[(size_t)((pos + k) % P) * 16 + c] = c < NOUT ? z[(d.row0 + k) * NOUT + c] : 0.f;
   }
   __syncthreads();  // (every thread has read the position)
-  if (tid == 0) {
-    zpos[2 * d.sid] = (pos + d.n) % P;
-    zpos[2 * d.sid + 1] = held + d.n < P ? held + d.n : P;
-  }
+  if (tid == 0) wv_zpos_advance(zpos, d.sid, pos, held, d.n, P);
 }
 
 // ---- pooled maxima of the sequence form.  m[t] = max of z over the last P rows up to t (of t's own sequence), P = 0: from row 0.
@@ -1293,10 +1277,19 @@ __global__ __launch_bounds__(256) void wave_seq_post_kernel(const float *z, cons
 
 size_t ww_wave_workspace(const ww_model *, int) { return 256; }
 
-// The model's side of wave_args for the forward and tick launches: sizes, weights, dilations and the residual mask
-static int wave_model_args(ww_ctx *ctx, const ww_wave_dev &v, wave_args &a) {
-  if (v.NB > 32) return ww_fail(ctx, WW_EINVAL, "Wavenet with %d blocks: kernel limit 32", v.NB);
+// The model's side of wave_args, from zero.  wave_head_args: the sizes and the detect head - all ww_k_wave_detect needs, and nothing
+// is refused; wave_model_args: with the encoder of every other launch - the mel buffer, weights, dilations and the residual mask.
+// wave_model_args OVERWRITES `a` as a whole: a launcher calls it first and sets its own fields (wa, out, enc, tag, fe, fb) after it.
+static wave_args wave_head_args(const ww_wave_dev &v) {
+  wave_args a = {};
   a.T = v.T; a.n_mel = v.n_mel; a.NB = v.NB; a.NOUT = v.NOUT;
+  a.d_w1_4 = v.d_w1; a.d_b1 = v.d_b1; a.d_w2_4 = v.d_w2; a.d_b2 = v.d_b2;
+  return a;
+}
+static int wave_model_args(ww_ctx *ctx, const ww_wave_dev &v, const float *d_mel, wave_args &a) {
+  if (v.NB > 32) return ww_fail(ctx, WW_EINVAL, "Wavenet with %d blocks: kernel limit 32", v.NB);
+  a = wave_head_args(v);
+  a.mel = d_mel;
   for (int b = 0; b < v.NB; ++b) {
     if (v.dil[b] < 1 || v.dil[b] > 8) return ww_fail(ctx, WW_EINVAL, "dilation %d of block %d outside 1..8", v.dil[b], b);
     a.dil4[b >> 4] |= (unsigned long long)v.dil[b] << (4 * (b & 15));
@@ -1304,20 +1297,39 @@ static int wave_model_args(ww_ctx *ctx, const ww_wave_dev &v, wave_args &a) {
   }
   a.w_in4 = v.w_in; a.b_in = v.b_in; a.bn_s = v.bn_s; a.bn_t = v.bn_t;
   a.w_gate4 = v.w_gate; a.b_gate = v.b_gate; a.w_rs4 = v.w_rs; a.b_rs = v.b_rs;
-  a.d_w1_4 = v.d_w1; a.d_b1 = v.d_b1; a.d_w2_4 = v.d_w2; a.d_b2 = v.d_b2;
   a.wpk = (const uint4 *)v.wpk;
   return WW_OK;
+}
+
+// The arithmetic form of a model's window kernel - split-bf16, fp32 row-major (WW_OPT_WAVENET_ROWMAJOR), fp32 transposed - decided
+// ONCE, and its launch.  The transposed forms run twelve waves x one tile up to wave_wide_from(m) windows per launch and four waves x
+// three tiles above; the row-major loop and the one-launch tick (TICK = 1 / 2: fp32 / fp64 transform) have the twelve-wave form only.
+static int wave_wide_from(const ww_model *m) { return m->precision == WW_PRECISION_BF16X3 ? WV_BF16_WIDE_FROM : WV_F32_WIDE_FROM; }
+template <bool SPLIT_BF16, bool FP32T, int TICK>
+static void wave_launch_form(ww_ctx *ctx, int nw, bool wide, const wave_args &a) {
+  if constexpr (TICK == 0 && (SPLIT_BF16 || FP32T)) {
+    if (wide) {
+      hipLaunchKernelGGL((wavenet_kernel<false, SPLIT_BF16, 4, FP32T>), dim3(nw), dim3(4 * 64), 0, ctx->stream, a);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((wavenet_kernel<false, SPLIT_BF16, 12, FP32T, TICK>), dim3(nw), dim3(12 * 64), 0, ctx->stream, a);
+}
+template <int TICK>
+static void wave_launch(ww_ctx *ctx, const ww_model *m, int nw, const wave_args &a) {
+  const bool wide = nw > wave_wide_from(m);
+  if (m->precision == WW_PRECISION_BF16X3) wave_launch_form<true, false, TICK>(ctx, nw, wide, a);
+  else if (m->opt_wave_rowmajor) wave_launch_form<false, false, TICK>(ctx, nw, wide, a);
+  else wave_launch_form<false, true, TICK>(ctx, nw, wide, a);
 }
 
 int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
                       const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int nw, void *, size_t, float *d_out,
                       float *d_enc, const ww_tick_tag *tag) {
   if (nw <= 0) return WW_OK;
-  const ww_wave_dev &v = m->wave;
-  wave_args a = {};
-  a.mel = d_mel;
+  wave_args a;
+  if (int rc = wave_model_args(ctx, m->wave, d_mel, a)) return rc;
   a.wa = {d_win_row, d_win_valid, row0, hop, valid_const, mel_rows};
-  if (int rc = wave_model_args(ctx, v, a)) return rc;
   a.out = d_out; a.enc = d_enc;
   if (tag) a.tag = *tag;
   ww_launch_scope scope(ctx, m->precision == WW_PRECISION_BF16X3 ? "wavenet_kernel<bf16x3>" : "wavenet_kernel");
@@ -1327,16 +1339,8 @@ int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
   // and gate evaluations back to back): 1,656 vs 1,957 us per 16,384 windows, 69.8 vs 74.5 at 512.  Same arithmetic per
   // tile in both forms: a posterior does not depend on the launch size (tests/test_gpu_parity.py).  (Six waves x two tiles -
   // also two workgroups per CU - lose at every size: 2,393 us.)
-  if (m->precision == WW_PRECISION_BF16X3 && nw > WV_BF16_WIDE_FROM)
-    hipLaunchKernelGGL((wavenet_kernel<false, true, 4>), dim3(nw), dim3(4 * 64), 0, ctx->stream, a);
-  else if (m->precision == WW_PRECISION_BF16X3)
-    hipLaunchKernelGGL((wavenet_kernel<false, true, 12>), dim3(nw), dim3(12 * 64), 0, ctx->stream, a);
-  else if (m->opt_wave_rowmajor)
-    hipLaunchKernelGGL((wavenet_kernel<false, false, 12>), dim3(nw), dim3(12 * 64), 0, ctx->stream, a);
-  else if (nw > WV_F32_WIDE_FROM)  // (round 5) fp32: the same two forms as the split-bf16 loop, the same bits in both
-    hipLaunchKernelGGL((wavenet_kernel<false, false, 4, true>), dim3(nw), dim3(4 * 64), 0, ctx->stream, a);
-  else
-    hipLaunchKernelGGL((wavenet_kernel<false, false, 12, true>), dim3(nw), dim3(12 * 64), 0, ctx->stream, a);
+  // (round 5) fp32: the same two forms as the split-bf16 loop, the same bits in both
+  wave_launch<0>(ctx, m, nw, a);
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
 }
@@ -1357,9 +1361,8 @@ int ww_wave_receptive_field(const ww_model *m) {
 int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const wv_seg *d_segs, int n_segs, float *d_enc, float *d_logits) {
   if (n_segs <= 0) return WW_OK;
   if (int rc = wave_seq_check(ctx, m, "ww_wave_sequence")) return rc;
-  wave_args a = {};
-  a.mel = d_mel;
-  if (int rc = wave_model_args(ctx, m->wave, a)) return rc;
+  wave_args a;
+  if (int rc = wave_model_args(ctx, m->wave, d_mel, a)) return rc;
   wave_seq_args q = {};
   q.segs = d_segs; q.enc = d_enc; q.logits = d_logits;
   ww_launch_scope scope(ctx, "wavenet_seq_kernel");
@@ -1400,9 +1403,8 @@ int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, c
                           const ww_tick_tag *tag) {
   if (nw <= 0) return WW_OK;
   if (int rc = wave_seq_check(ctx, m, "causal streaming tick")) return rc;
-  wave_args a = {};
-  a.mel = d_hist;
-  if (int rc = wave_model_args(ctx, m->wave, a)) return rc;
+  wave_args a;
+  if (int rc = wave_model_args(ctx, m->wave, d_hist, a)) return rc;
   if (tag) a.tag = *tag;
   wave_seq_args q = {};
   q.win_row = d_win_row; q.win_valid = d_win_valid; q.win_aux = d_win_aux;
@@ -1420,9 +1422,8 @@ int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv
                    float *d_zring, int32_t *d_zpos, int pidx, float *d_post) {
   if (n_segs <= 0) return WW_OK;
   if (int rc = wave_seq_check(ctx, m, "ww_stream_feed")) return rc;
-  wave_args a = {};
-  a.mel = d_rows;
-  if (int rc = wave_model_args(ctx, m->wave, a)) return rc;
+  wave_args a;
+  if (int rc = wave_model_args(ctx, m->wave, d_rows, a)) return rc;
   a.tag = {nullptr, 0, pidx};
   wave_seq_args q = {};
   q.state = d_state; q.zring = d_zring; q.zpos = d_zpos; q.P = m->wave.T; q.post = d_post;
@@ -1456,8 +1457,7 @@ int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv
 // more than the launch it costs (tools/stream_forms.py, split-bf16 p50: 128 streams 49.3 vs 54.5 us, 192: 84.9 vs 82.6, 512: 158.7 vs
 // 149.2, 1,024: 306.2 vs 273.1; fp32 alike)
 bool ww_wave_tick_capable(const ww_model *m, int S) {
-  const int wide_from = m->precision == WW_PRECISION_BF16X3 ? WV_BF16_WIDE_FROM : WV_F32_WIDE_FROM;
-  return m->kind == WW_KIND_WAVENET && m->filt.n_mel == 40 && m->wave.n_mel == 40 && m->wave.T + 10 <= WV_T && 2 * S <= wide_from;
+  return m->kind == WW_KIND_WAVENET && m->filt.n_mel == 40 && m->wave.n_mel == 40 && m->wave.T + 10 <= WV_T && 2 * S <= wave_wide_from(m);
 }
 
 // ONE launch per tick (wavenet_kernel<..., TICK>): 2 S workgroups of twelve waves, the posteriors as tags only
@@ -1467,36 +1467,23 @@ int ww_k_wave_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int pre
   if (f.n_mel != 40 || v.n_mel != 40 || fe.hop != 160 || v.T + 10 > WV_T)
     return ww_fail(ctx, WW_EINVAL, "one-launch streaming tick: 40 mel bands, hop 160 and a window of at most %d rows only", WV_T - 10);
   if (!tag.slots || fe.S <= 0) return ww_fail(ctx, WW_EINVAL, "one-launch streaming tick: no tag slots / no streams");
-  wave_args a = {};
-  a.mel = fe.hist;
+  wave_args a;
+  if (int rc = wave_model_args(ctx, v, fe.hist, a)) return rc;
   a.wa = {nullptr, nullptr, 0, 0, 0, (int64_t)fe.S * fe.HR};
-  if (int rc = wave_model_args(ctx, v, a)) return rc;
   a.tag = tag;
   a.fe = fe;
   a.fb = ww_fe_filt_of(f);
-  const dim3 grid(2 * fe.S), block(12 * 64);
   ww_launch_scope scope(ctx, m->precision == WW_PRECISION_BF16X3 ? "wavenet_kernel<bf16x3,tick>" : "wavenet_kernel<tick>");
-  if (m->precision == WW_PRECISION_BF16X3) {
-    if (precise) hipLaunchKernelGGL((wavenet_kernel<false, true, 12, false, 2>), grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL((wavenet_kernel<false, true, 12, false, 1>), grid, block, 0, ctx->stream, a);
-  } else if (m->opt_wave_rowmajor) {
-    if (precise) hipLaunchKernelGGL((wavenet_kernel<false, false, 12, false, 2>), grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL((wavenet_kernel<false, false, 12, false, 1>), grid, block, 0, ctx->stream, a);
-  } else {
-    if (precise) hipLaunchKernelGGL((wavenet_kernel<false, false, 12, true, 2>), grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL((wavenet_kernel<false, false, 12, true, 1>), grid, block, 0, ctx->stream, a);
-  }
+  if (precise) wave_launch<2>(ctx, m, 2 * fe.S, a);
+  else wave_launch<1>(ctx, m, 2 * fe.S, a);
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
 }
 
 int ww_k_wave_detect(ww_ctx *ctx, const ww_model *m, const float *d_enc, int nw, float *d_out) {
   if (nw <= 0) return WW_OK;
-  const ww_wave_dev &v = m->wave;
-  wave_args a = {};
-  a.T = v.T; a.n_mel = v.n_mel; a.NB = v.NB; a.NOUT = v.NOUT;
-  a.d_w1_4 = v.d_w1; a.d_b1 = v.d_b1; a.d_w2_4 = v.d_w2; a.d_b2 = v.d_b2;
-  a.out = d_out; a.enc = nullptr; a.enc_in = d_enc;
+  wave_args a = wave_head_args(m->wave);
+  a.out = d_out; a.enc_in = d_enc;
   ww_launch_scope scope(ctx, "wavenet_detect_kernel");
   hipLaunchKernelGGL((wavenet_kernel<true, false, 12>), dim3(nw), dim3(12 * 64), 0, ctx->stream, a);
   WW_HIP(ctx, hipGetLastError());
