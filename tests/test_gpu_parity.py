@@ -51,6 +51,26 @@ def test_stft_magnitude_vs_numpy(engines):
     assert np.abs(fast - want).max() < 2e-4 * max(1.0, float(want.max()))
 
 
+def test_stft_magnitude_either_side_of_the_staging_switch(engines):
+    """ww_stft_mag stages frames (2,048 bytes each) and magnitudes (1,028 bytes each, both rounded up to 256) in pinned
+    memory up to 256 KB and in the device arena above: 85 frames (261,632 bytes) and 86 (264,704), against the reference
+    and at the bounds of test_stft_magnitude_vs_numpy."""
+    def staged(n):
+        return ((n * 512 * 4 + 255) & ~255) + ((n * 257 * 4 + 255) & ~255)
+    n_pin = max(n for n in range(1, 200) if staged(n) <= 256 << 10)
+    assert n_pin == 85
+    rng = np.random.default_rng(5)
+    frames = rng.normal(0, 0.2, (n_pin + 1, 512)).astype(np.float32)
+    frames[0] = 0.0
+    frames[1] = 0.5 * np.sin(2 * np.pi * 1000 * np.arange(512) / 16000)
+    want = np.abs(np.fft.rfft(frames.astype(np.float64) * np.hanning(512), n=512)).astype(np.float32)
+    for n in (n_pin, n_pin + 1):
+        got = engines["CRNN"].stft_mag(frames[:n], precise=True)
+        np.testing.assert_allclose(got, want[:n], rtol=2e-6, atol=1e-9)
+        fast = engines["CRNN"].stft_mag(frames[:n], precise=False)
+        assert np.abs(fast - want[:n]).max() < 2e-4 * max(1.0, float(want[:n].max()))
+
+
 @pytest.mark.parametrize("div,clip,pre", [(32767.0, True, 0.0), (32768.0, False, 0.97)])
 def test_logmel_golden(engines, golden, div, clip, pre):
     from wwhip.engine import frontend_params

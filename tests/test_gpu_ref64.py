@@ -255,6 +255,50 @@ def test_filter_alone(engines, ref, name):
         assert err < TOL_FILTER, (n, err)
 
 
+SMALL_IO_BYTES = 256 << 10  # WW_SMALL_IO_BYTES (csrc/api.hip): up to here a host-pointer call stages in pinned memory
+
+
+def _need(n_bytes):
+    """ww_bump::need: what a staged buffer takes, a multiple of 256 bytes."""
+    return (n_bytes + 255) & ~255
+
+
+@pytest.mark.parametrize("name", ["CRNN", "Wavenet"])
+def test_forward_with_enc_either_side_of_the_staging_switch(engines, ref, name):
+    """Engine.forward(want_enc=True) (ww_forward_enc) at the largest window count whose mel, posteriors and encoder rows
+    stage in pinned memory and at the next one, which goes through the device arena: 10 and 11 windows of 151 x 40 (CRNN),
+    4 and 5 of 182 x 40 (Wavenet)."""
+    e = engines[name]
+    _, wins, out64, enc64 = ref(name)
+
+    def staged(n):
+        return _need(n * e.window * e.n_mel * 4) + _need(n * e.n_out * 4) + _need(n * e.enc_shape[0] * e.enc_shape[1] * 4)
+    n_pin = max(n for n in range(1, 65) if staged(n) <= SMALL_IO_BYTES)
+    assert n_pin == {"CRNN": 10, "Wavenet": 4}[name]
+    rng = np.random.default_rng(89)
+    for n in (n_pin, n_pin + 1):
+        idx = _tiled(len(wins), n, rng)
+        got, enc = e.forward(wins[idx], want_enc=True)
+        _post(f"{name} forward with enc, {n} windows", got, out64[idx], TAU)
+        _enc(f"{name} forward with enc, {n} windows", enc, enc64[idx], TAU_E)
+
+
+@pytest.mark.parametrize("name", ["CRNN", "Wavenet"])
+def test_slide_forward_hop_1_at_64_and_65_windows(engines, ref, name):
+    """Engine.slide_forward at hop 1 over 64 and 65 windows: bytes far below SMALL_IO_BYTES, which stage in pinned memory up
+    to 64 windows and in the device arena above (the CRNN also changes kernel form at 64 windows, crnn_slide_min) - every slid window against
+    Ref64."""
+    e = engines[name]
+    r, wins, _, _ = ref(name)
+    T = e.window
+    seq = _slide_seqs(wins, T)[0][:T + 64]
+    sw = np.lib.stride_tricks.sliding_window_view(seq, (T, 40))[:, 0]
+    assert len(sw) == 65
+    want = r.forward(sw)[0]
+    for nw in (64, 65):
+        _post(f"{name} slide_forward hop 1, {nw} windows", e.slide_forward(seq[:T + nw - 1], 1), want[:nw], TAU)
+
+
 # ---------------------------------------------------------------- g. streaming
 @pytest.mark.parametrize("name", ["CRNN", "Wavenet"])
 def test_stream_bank_vs_float64(engines, oracles, ref, name):

@@ -39,31 +39,73 @@ int ww_ensure(ww_ctx *ctx, ww_arena &a, size_t bytes, bool pinned) {
 }
 
 
-// Small host-pointer calls are latency-bound, and a copy-engine operation (hipMemcpyAsync) costs more than a few KB
-// are worth: their inputs are staged in the context's pinned arena, which the kernels read over the bus themselves,
-// and their outputs are stored into it by the kernels.  ww_small_io carves that arena and translates addresses.
+// Staging of a host-pointer call: the buffers its kernels read and write, carved in call order from one arena, and the bytes'
+// way in and out.  A call of more than WW_SMALL_IO_BYTES stages in the device arena (hipMemcpyAsync in, hipMemcpyAsync out, one
+// synchronise).  A smaller one is latency-bound, and a copy-engine operation costs more than a few KB are worth: it stages in the
+// context's pinned arena, which the kernels read and write over the bus themselves (memcpy in, one synchronise, memcpy out).
+// Every address handed out is the one the kernels use; the entry point is the same code in both modes.
 #define WW_SMALL_IO_BYTES (256u << 10)
-struct ww_small_io {
+struct ww_staged_io {
   ww_ctx *ctx;
-  char *host = nullptr, *dev = nullptr;
+  bool pinned = false, synced = false;
+  char *base = nullptr;  // the arena as the kernels address it
+  char *host = nullptr;  // pinned mode: the same bytes as the host addresses them
   size_t off = 0;
-  explicit ww_small_io(ww_ctx *c) : ctx(c) {}
-  int init(size_t bytes) {
-    int rc = ww_ensure(ctx, ctx->pinned, bytes + 1024, true);
-    if (rc) return rc;
+  int rc = WW_OK;        // the first in() that failed: checked once, before the launch
+  explicit ww_staged_io(ww_ctx *c) : ctx(c) {}
+  // bytes: the sum of the call's carves (ww_bump::need each); dev_extra: device scratch behind them (scratch())
+  int init(size_t bytes, size_t dev_extra = 0, bool may_pin = true) {
+    pinned = may_pin && bytes <= WW_SMALL_IO_BYTES;
+    if (!pinned) {
+      if (int r = ww_ensure(ctx, ctx->dev, bytes + dev_extra, false)) return r;
+      base = (char *)ctx->dev.ptr;
+      return WW_OK;
+    }
+    if (int r = ww_ensure(ctx, ctx->pinned, bytes + 1024, true)) return r;
     host = (char *)ctx->pinned.ptr;
-    if (hipHostGetDevicePointer((void **)&dev, host, 0) != hipSuccess)
+    if (hipHostGetDevicePointer((void **)&base, host, 0) != hipSuccess)
       return ww_fail(ctx, WW_EHIP, "pinned arena is not visible to the device");
-    return WW_OK;
+    return dev_extra ? ww_ensure(ctx, ctx->dev, dev_extra, false) : WW_OK;
   }
   template <typename T>
-  T *take(size_t n) {
-    T *r = (T *)(host + off);
+  T *out(size_t n) {  // a buffer the kernels write
+    T *r = (T *)(base + off);
     off += ww_bump::need(n, sizeof(T));
     return r;
   }
   template <typename T>
-  T *dv(T *h) const { return (T *)(dev + ((char *)h - host)); }
+  T *host_of(T *p) const { return (T *)(host + ((char *)p - base)); }  // pinned mode only
+  // a buffer of `room` (n if 0) elements that holds the caller's n; src stays the caller's until finish()
+  template <typename T>
+  T *in(const T *src, size_t n, size_t room = 0) {
+    T *d = out<T>(room ? room : n);
+    if (pinned) memcpy(host_of(d), src, n * sizeof(T));
+    else if (rc == WW_OK) rc = h2d(d, src, n * sizeof(T));
+    return d;
+  }
+  // the model's scratch stays in device memory: behind the carves there, at the device arena's start in pinned mode
+  void *scratch(size_t bytes) { return pinned ? ctx->dev.ptr : out<char>(bytes); }
+  int fetch(void *dst, const void *buf, size_t bytes) {  // dst is valid after finish()
+    if (!pinned) {
+      WW_HIP(ctx, hipMemcpyAsync(dst, buf, bytes, hipMemcpyDeviceToHost, ctx->stream));
+      return WW_OK;
+    }
+    if (int r = finish()) return r;
+    memcpy(dst, host_of((const char *)buf), bytes);
+    return WW_OK;
+  }
+  int finish() {  // pinned mode synchronises once: it takes calls that launch once
+    if (synced) return WW_OK;
+    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    synced = pinned;
+    return WW_OK;
+  }
+
+ private:
+  int h2d(void *d, const void *s, size_t bytes) {
+    WW_HIP(ctx, hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return WW_OK;
+  }
 };
 
 extern "C" {
@@ -410,6 +452,32 @@ static int load_filter(ww_ctx *ctx, ww_model *m, const blob_view &bv) {
   return WW_OK;
 }
 
+// split-bf16 mode (WW_PRECISION_BF16X3): x = hi + lo, both bf16 round-to-nearest-even
+static uint16_t bf16_rne(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+static float bf16_f(uint16_t h) {
+  uint32_t u = (uint32_t)h << 16;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+static void bf16_split(float x, uint16_t &hi, uint16_t &lo) {
+  hi = bf16_rne(x);
+  lo = bf16_rne(x - bf16_f(hi));
+}
+
+// a row-major [n_rows][k] matrix in MFMA B-operand order [k/4][n_rows][4]
+static std::vector<float> pack_k4(const std::vector<float> &src, size_t n_rows, size_t k) {
+  std::vector<float> dst(src.size());
+  for (size_t n = 0; n < n_rows; ++n)
+    for (size_t kk = 0; kk < k; ++kk) dst[((kk / 4) * n_rows + n) * 4 + (kk % 4)] = src[n * k + kk];
+  return dst;
+}
+
 static int load_crnn(ww_ctx *ctx, ww_model *m, const blob_view &bv) {
   uint32_t cnt = 0;
   const int32_t *meta = (const int32_t *)bv.find("crnn.meta", &cnt);
@@ -468,27 +536,7 @@ static int load_crnn(ww_ctx *ctx, ww_model *m, const blob_view &bv) {
   const size_t in1 = (size_t)c.OF * c.C, in2 = 2 * (size_t)c.H;
   if ((rc = cat2("crnn.g1f.wx", "crnn.g1b.wx", G * in1, v))) return rc; c.wx1 = upload(m, v);
   if (!c.generic) {
-    std::vector<float> ws(v.size());
-    for (size_t n = 0; n < (size_t)2 * G; ++n)
-      for (size_t k = 0; k < in1; ++k) ws[((k / 4) * 2 * G + n) * 4 + (k % 4)] = v[n * in1 + k];
-    c.wx1s = upload(m, ws);
-    // split-bf16 mode (WW_PRECISION_BF16X3): x = hi + lo, both bf16 round-to-nearest-even
-    auto rne = [](float f) -> uint16_t {
-      uint32_t u;
-      memcpy(&u, &f, 4);
-      u += 0x7FFFu + ((u >> 16) & 1u);
-      return (uint16_t)(u >> 16);
-    };
-    auto tof = [](uint16_t h) -> float {
-      uint32_t u = (uint32_t)h << 16;
-      float f;
-      memcpy(&f, &u, 4);
-      return f;
-    };
-    auto split = [&](float x, uint16_t &h, uint16_t &l) {
-      h = rne(x);
-      l = rne(x - tof(h));
-    };
+    c.wx1s = upload(m, pack_k4(v, 2 * G, in1));
     {  // W_x1 [192][640] -> [plane][k-step 20][n-tile 12][lane = g*16 + j][8]: element e is W[nt*16 + j][ks*32 + 8 g + e]
       std::vector<unsigned short> wb((size_t)2 * 20 * 12 * 64 * 8);
       for (int ks = 0; ks < 20; ++ks)
@@ -497,7 +545,7 @@ static int load_crnn(ww_ctx *ctx, ww_model *m, const blob_view &bv) {
             for (int e = 0; e < 8; ++e) {
               const int gq = ln >> 4, jj = ln & 15;
               uint16_t h, l;
-              split(v[(size_t)(nt * 16 + jj) * in1 + ks * 32 + 8 * gq + e], h, l);
+              bf16_split(v[(size_t)(nt * 16 + jj) * in1 + ks * 32 + 8 * gq + e], h, l);
               const size_t o = (((size_t)ks * 12 + nt) * 64 + ln) * 8 + e;
               wb[o] = h;
               wb[(size_t)20 * 12 * 64 * 8 + o] = l;
@@ -516,7 +564,7 @@ static int load_crnn(ww_ctx *ctx, ww_model *m, const blob_view &bv) {
               float x = 0.f;
               if (Gq < 15 && kt >= 0 && kt < c.KT) x = cw[(size_t)(mt * 16 + ii) * K + kf * c.KT + kt];
               uint16_t h, l;
-              split(x, h, l);
+              bf16_split(x, h, l);
               const size_t o = (((size_t)ks * 2 + mt) * 64 + ln) * 8 + e;
               wb[o] = h;
               wb[(size_t)4 * 2 * 64 * 8 + o] = l;
@@ -535,13 +583,8 @@ static int load_crnn(ww_ctx *ctx, ww_model *m, const blob_view &bv) {
   if ((rc = cat2("crnn.g1f.wh", "crnn.g1b.wh", (size_t)G * c.H, v))) return rc; c.wh1 = upload(m, v);
   if ((rc = cat2("crnn.g1f.bh", "crnn.g1b.bh", G, v))) return rc; c.bh1 = upload(m, v);
   if ((rc = cat2("crnn.g2f.wx", "crnn.g2b.wx", G * in2, v))) return rc; c.wx2 = upload(m, v);
-  {
-    std::vector<float> ws(v.size());
-    for (size_t n = 0; n < (size_t)2 * G; ++n)
-      for (size_t k = 0; k < in2; ++k) ws[((k / 4) * 2 * G + n) * 4 + (k % 4)] = v[n * in2 + k];
-    c.wx2s = upload(m, ws);
-    if (!c.wx2s) return ww_fail(ctx, WW_ENOMEM, "CRNN upload failed");
-  }
+  c.wx2s = upload(m, pack_k4(v, 2 * G, in2));
+  if (!c.wx2s) return ww_fail(ctx, WW_ENOMEM, "CRNN upload failed");
   if ((rc = cat2("crnn.g2f.bx", "crnn.g2b.bx", G, v))) return rc; c.bx2 = upload(m, v);
   if ((rc = cat2("crnn.g2f.wh", "crnn.g2b.wh", (size_t)G * c.H, v))) return rc; c.wh2 = upload(m, v);
   if ((rc = cat2("crnn.g2f.bh", "crnn.g2b.bh", G, v))) return rc; c.bh2 = upload(m, v);
@@ -634,23 +677,7 @@ static int load_wave(ww_ctx *ctx, ww_model *m, const blob_view &bv) {
   // hand the second group carries the hi x lo product instead of zeros: 5 MFMAs per gate and 2 per res | skip m-tile give
   // all three split products plus the bias (16 MFMAs per block and tile, not 21).
   {
-    auto bf16_rne = [](float f) -> uint16_t {
-      uint32_t u;
-      memcpy(&u, &f, 4);
-      u += 0x7FFFu + ((u >> 16) & 1u);
-      return (uint16_t)(u >> 16);
-    };
-    auto bf16_f = [](uint16_t h) -> float {
-      uint32_t u = (uint32_t)h << 16;
-      float f;
-      memcpy(&f, &u, 4);
-      return f;
-    };
     std::vector<uint16_t> pk((size_t)NB * 14 * 64 * 8, 0);
-    auto split = [&](float wv, uint16_t &hi, uint16_t &lo) {
-      hi = bf16_rne(wv);
-      lo = bf16_rne(wv - bf16_f(hi));
-    };
     auto put = [&](int b, int slot, int lane, int q, uint16_t val) { pk[((((size_t)b * 14 + slot) * 64) + lane) * 8 + q] = val; };
     for (int b = 0; b < NB; ++b) {
       for (int lane = 0; lane < 64; ++lane) {
@@ -666,17 +693,17 @@ static int load_wave(ww_ctx *ctx, ww_model *m, const blob_view &bv) {
             uint16_t hi, lo;
             // k-step 0, slot "hh": (hi of tap 2 | hi of tap 2) against B = (u_hi | u_lo);
             //           slot "lb": (lo of tap 2 | bias hi, bias lo in k-slots 4, 5 of lane group 0) against B = (u_hi | 1, 1, 0, 0)
-            split(wt(2), hi, lo);
+            bf16_split(wt(2), hi, lo);
             put(b, (0 * 2 + mt) * 2 + 0, lane, q, hi);
             if (q < 4) {
               put(b, (0 * 2 + mt) * 2 + 1, lane, q, lo);
             } else if (kg == 0 && q < 6) {
               uint16_t bh, bl;
-              split((mt == 0 ? b_sig : b_tanh)[(size_t)b * C + i] * sc, bh, bl);
+              bf16_split((mt == 0 ? b_sig : b_tanh)[(size_t)b * C + i] * sc, bh, bl);
               put(b, (0 * 2 + mt) * 2 + 1, lane, q, q == 4 ? bh : bl);
             }
             // k-step 1: (tap 0 | tap 1), hi and lo slots, against B = the two delayed rows (hi plane, then lo plane)
-            split(wt(q < 4 ? 0 : 1), hi, lo);
+            bf16_split(wt(q < 4 ? 0 : 1), hi, lo);
             put(b, (1 * 2 + mt) * 2 + 0, lane, q, hi);
             put(b, (1 * 2 + mt) * 2 + 1, lane, q, lo);
           }
@@ -684,13 +711,13 @@ static int load_wave(ww_ctx *ctx, ww_model *m, const blob_view &bv) {
             // res | skip: slot "hh" = (hi | hi) against B = (g_hi | g_lo), slot "lb" = (lo | bias hi, bias lo) against (g_hi | 1, 1, 0, 0)
             const float wv = mt == 0 ? (has_res[b] ? w_res[((size_t)b * C + ch) * C + i] : 0.f) : w_skip[((size_t)b * C + ch) * S + (mt - 1) * 16 + i];
             uint16_t hi, lo;
-            split(wv, hi, lo);
+            bf16_split(wv, hi, lo);
             put(b, 8 + mt * 2 + 0, lane, q, hi);
             if (q < 4) {
               put(b, 8 + mt * 2 + 1, lane, q, lo);
             } else if (kg == 0 && q < 6) {
               uint16_t bh, bl;
-              split(mt == 0 ? (has_res[b] ? b_res[(size_t)b * C + i] : 0.f) : b_skip[(size_t)b * S + (mt - 1) * 16 + i], bh, bl);
+              bf16_split(mt == 0 ? (has_res[b] ? b_res[(size_t)b * C + i] : 0.f) : b_skip[(size_t)b * S + (mt - 1) * 16 + i], bh, bl);
               put(b, 8 + mt * 2 + 1, lane, q, q == 4 ? bh : bl);
             }
           }
@@ -830,39 +857,30 @@ static int logmel_host(ww_ctx *ctx, const ww_model *m, const void *samples, size
   const int64_t base = sample_offs[0], total_s = sample_offs[n_utt] - base;
   const size_t b_s = ww_bump::need((size_t)total_s + 16, elt), b_o = ww_bump::need((size_t)n_utt + 1, 8);
   const size_t b_m = ww_bump::need((size_t)total_f * m->filt.n_mel, 4);
-  if (b_s + 2 * b_o + b_m <= WW_SMALL_IO_BYTES) {
-    ww_small_io io(ctx);
-    if ((rc = io.init(b_s + 2 * b_o + b_m))) return rc;
-    char *h_s = io.take<char>(b_s);
-    int64_t *h_so = io.take<int64_t>(n_utt + 1), *h_fo = io.take<int64_t>(n_utt + 1);
-    float *h_mel = io.take<float>((size_t)total_f * m->filt.n_mel);
-    memcpy(h_s, (const char *)samples + (size_t)base * elt, (size_t)total_s * elt);
-    memset(h_s + (size_t)total_s * elt, 0, 16 * elt);
+  ww_staged_io io(ctx);
+  if ((rc = io.init(b_s + 2 * b_o + b_m))) return rc;
+  // the samples, with room for 16 elements of zero padding behind them (zeroed where that is a host memset)
+  char *d_s = io.in((const char *)samples + (size_t)base * elt, (size_t)total_s * elt, ((size_t)total_s + 16) * elt);
+  if (io.pinned) memset(io.host_of(d_s) + (size_t)total_s * elt, 0, 16 * elt);
+  // sample_offs rebased to the first sample staged: written in place in pinned mode, copied from `so` (alive until finish()) otherwise
+  std::vector<int64_t> so;
+  int64_t *d_so;
+  if (io.pinned) {
+    int64_t *h_so = io.host_of(d_so = io.out<int64_t>(n_utt + 1));
     for (int u = 0; u <= n_utt; ++u) h_so[u] = sample_offs[u] - base;
-    memcpy(h_fo, frame_offs, sizeof(int64_t) * (n_utt + 1));
-    rc = ww_k_logmel(ctx, m, elt == 2 ? (const int16_t *)io.dv(h_s) : nullptr, elt == 4 ? (const float *)io.dv(h_s) : nullptr,
-                     io.dv(h_so), io.dv(h_fo), n_utt, total_f, max_f, fp, io.dv(h_mel), 0, total_s);
-    if (rc) return rc;
-    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(mel, h_mel, (size_t)total_f * m->filt.n_mel * 4);
-    return WW_OK;
+  } else {
+    so.resize(n_utt + 1);
+    for (int u = 0; u <= n_utt; ++u) so[u] = sample_offs[u] - base;
+    d_so = io.in(so.data(), n_utt + 1);
   }
-  if ((rc = ww_ensure(ctx, ctx->dev, b_s + 2 * b_o + b_m, false))) return rc;
-  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
-  char *d_s = bump.take<char>(b_s);
-  int64_t *d_so = bump.take<int64_t>(n_utt + 1), *d_fo = bump.take<int64_t>(n_utt + 1);
-  float *d_mel = bump.take<float>((size_t)total_f * m->filt.n_mel);
-  std::vector<int64_t> so(n_utt + 1);
-  for (int u = 0; u <= n_utt; ++u) so[u] = sample_offs[u] - base;
-  WW_HIP(ctx, hipMemcpyAsync(d_s, (const char *)samples + (size_t)base * elt, (size_t)total_s * elt, hipMemcpyHostToDevice, ctx->stream));
-  WW_HIP(ctx, hipMemcpyAsync(d_so, so.data(), sizeof(int64_t) * (n_utt + 1), hipMemcpyHostToDevice, ctx->stream));
-  WW_HIP(ctx, hipMemcpyAsync(d_fo, frame_offs, sizeof(int64_t) * (n_utt + 1), hipMemcpyHostToDevice, ctx->stream));
+  int64_t *d_fo = io.in(frame_offs, n_utt + 1);
+  float *d_mel = io.out<float>((size_t)total_f * m->filt.n_mel);
+  if (io.rc) return io.rc;
   rc = ww_k_logmel(ctx, m, elt == 2 ? (const int16_t *)d_s : nullptr, elt == 4 ? (const float *)d_s : nullptr, d_so, d_fo,
                    n_utt, total_f, max_f, fp, d_mel, 0, total_s);
   if (rc) return rc;
-  WW_HIP(ctx, hipMemcpyAsync(mel, d_mel, (size_t)total_f * m->filt.n_mel * 4, hipMemcpyDeviceToHost, ctx->stream));
-  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return WW_OK;
+  if ((rc = io.fetch(mel, d_mel, (size_t)total_f * m->filt.n_mel * 4))) return rc;
+  return io.finish();
 }
 
 extern "C" {
@@ -902,26 +920,15 @@ int ww_stft_mag(ww_ctx *ctx, const ww_model *m, const float *frames, int64_t n, 
   if (!frames || !mag) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
   WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
   const size_t b_f = ww_bump::need((size_t)n * WW_FFT_WINDOW, 4), b_m = ww_bump::need((size_t)n * WW_FFT_BINS, 4);
-  int rc;
-  if (b_f + b_m <= WW_SMALL_IO_BYTES) {
-    ww_small_io io(ctx);
-    if ((rc = io.init(b_f + b_m))) return rc;
-    float *h_f = io.take<float>((size_t)n * WW_FFT_WINDOW), *h_m = io.take<float>((size_t)n * WW_FFT_BINS);
-    memcpy(h_f, frames, (size_t)n * WW_FFT_WINDOW * 4);
-    if ((rc = ww_k_stft_mag(ctx, m, io.dv(h_f), n, precise, io.dv(h_m)))) return rc;
-    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(mag, h_m, (size_t)n * WW_FFT_BINS * 4);
-    return WW_OK;
-  }
-  rc = ww_ensure(ctx, ctx->dev, b_f + b_m, false);
+  ww_staged_io io(ctx);
+  int rc = io.init(b_f + b_m);
   if (rc) return rc;
-  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
-  float *d_f = bump.take<float>((size_t)n * WW_FFT_WINDOW), *d_m = bump.take<float>((size_t)n * WW_FFT_BINS);
-  WW_HIP(ctx, hipMemcpyAsync(d_f, frames, (size_t)n * WW_FFT_WINDOW * 4, hipMemcpyHostToDevice, ctx->stream));
+  const float *d_f = io.in(frames, (size_t)n * WW_FFT_WINDOW);
+  float *d_m = io.out<float>((size_t)n * WW_FFT_BINS);
+  if (io.rc) return io.rc;
   if ((rc = ww_k_stft_mag(ctx, m, d_f, n, precise, d_m))) return rc;
-  WW_HIP(ctx, hipMemcpyAsync(mag, d_m, (size_t)n * WW_FFT_BINS * 4, hipMemcpyDeviceToHost, ctx->stream));
-  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return WW_OK;
+  if ((rc = io.fetch(mag, d_m, (size_t)n * WW_FFT_BINS * 4))) return rc;
+  return io.finish();
   WW_GUARD_END(ctx)
 }
 
@@ -938,26 +945,15 @@ int ww_filter_apply(ww_ctx *ctx, const ww_model *m, const float *mag, int64_t n,
   WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
   const int NBN = m->filt.n_bins, F = m->filt.n_mel;
   const size_t b_a = ww_bump::need((size_t)n * NBN, 4), b_b = ww_bump::need((size_t)n * F, 4);
-  int rc;
-  if (b_a + b_b <= WW_SMALL_IO_BYTES) {
-    ww_small_io io(ctx);
-    if ((rc = io.init(b_a + b_b))) return rc;
-    float *h_a = io.take<float>((size_t)n * NBN), *h_b = io.take<float>((size_t)n * F);
-    memcpy(h_a, mag, (size_t)n * NBN * 4);
-    if ((rc = ww_k_mel_only(ctx, m, io.dv(h_a), n, io.dv(h_b)))) return rc;
-    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(mel, h_b, (size_t)n * F * 4);
-    return WW_OK;
-  }
-  rc = ww_ensure(ctx, ctx->dev, b_a + b_b, false);
+  ww_staged_io io(ctx);
+  int rc = io.init(b_a + b_b);
   if (rc) return rc;
-  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
-  float *d_a = bump.take<float>((size_t)n * NBN), *d_b = bump.take<float>((size_t)n * F);
-  WW_HIP(ctx, hipMemcpyAsync(d_a, mag, (size_t)n * NBN * 4, hipMemcpyHostToDevice, ctx->stream));
+  const float *d_a = io.in(mag, (size_t)n * NBN);
+  float *d_b = io.out<float>((size_t)n * F);
+  if (io.rc) return io.rc;
   if ((rc = ww_k_mel_only(ctx, m, d_a, n, d_b))) return rc;
-  WW_HIP(ctx, hipMemcpyAsync(mel, d_b, (size_t)n * F * 4, hipMemcpyDeviceToHost, ctx->stream));
-  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return WW_OK;
+  if ((rc = io.fetch(mel, d_b, (size_t)n * F * 4))) return rc;
+  return io.finish();
   WW_GUARD_END(ctx)
 }
 
@@ -970,28 +966,16 @@ int ww_detect(ww_ctx *ctx, const ww_model *m, const float *enc, int32_t n, float
   WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
   const size_t per = (size_t)m->info.enc_rows * m->info.enc_width;
   const size_t b_a = ww_bump::need((size_t)n * per, 4), b_b = ww_bump::need((size_t)n * m->info.n_out, 4);
-  int rc;
-  if (b_a + b_b <= WW_SMALL_IO_BYTES) {
-    ww_small_io io(ctx);
-    if ((rc = io.init(b_a + b_b))) return rc;
-    float *h_a = io.take<float>((size_t)n * per), *h_b = io.take<float>((size_t)n * m->info.n_out);
-    memcpy(h_a, enc, (size_t)n * per * 4);
-    rc = m->kind == WW_KIND_CRNN ? ww_k_crnn_detect(ctx, m, io.dv(h_a), n, io.dv(h_b)) : ww_k_wave_detect(ctx, m, io.dv(h_a), n, io.dv(h_b));
-    if (rc) return rc;
-    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(out, h_b, (size_t)n * m->info.n_out * 4);
-    return WW_OK;
-  }
-  rc = ww_ensure(ctx, ctx->dev, b_a + b_b, false);
+  ww_staged_io io(ctx);
+  int rc = io.init(b_a + b_b);
   if (rc) return rc;
-  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
-  float *d_a = bump.take<float>((size_t)n * per), *d_b = bump.take<float>((size_t)n * m->info.n_out);
-  WW_HIP(ctx, hipMemcpyAsync(d_a, enc, (size_t)n * per * 4, hipMemcpyHostToDevice, ctx->stream));
+  const float *d_a = io.in(enc, (size_t)n * per);
+  float *d_b = io.out<float>((size_t)n * m->info.n_out);
+  if (io.rc) return io.rc;
   rc = m->kind == WW_KIND_CRNN ? ww_k_crnn_detect(ctx, m, d_a, n, d_b) : ww_k_wave_detect(ctx, m, d_a, n, d_b);
   if (rc) return rc;
-  WW_HIP(ctx, hipMemcpyAsync(out, d_b, (size_t)n * m->info.n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return WW_OK;
+  if ((rc = io.fetch(out, d_b, (size_t)n * m->info.n_out * 4))) return rc;
+  return io.finish();
   WW_GUARD_END(ctx)
 }
 
@@ -1021,60 +1005,52 @@ static int model_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int
 #define WW_MAX_CHUNK 16384
 #endif
 
+static int chunk_of(int64_t nw) { return nw < WW_MAX_CHUNK ? (int)nw : WW_MAX_CHUNK; }
+
+// model_forward over nw windows, chunk_of(nw) at a time, ws sized for one chunk.  The windows slide over the mel rows (d_row ==
+// nullptr: window w starts at row w * hop and has valid_const rows) or are an explicit list (d_row, d_valid).  d_out moves on with
+// the windows; d_enc holds one chunk's encoder rows, which after_chunk(w0, n) takes away before the next chunk overwrites them.
+template <typename AfterChunk>
+static int forward_chunks(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_row,
+                          const int32_t *d_valid, int hop, int valid_const, int64_t nw, void *ws, float *d_out, float *d_enc,
+                          AfterChunk after_chunk) {
+  const int chunk = chunk_of(nw), NO = m->info.n_out;
+  for (int64_t w0 = 0; w0 < nw; w0 += chunk) {
+    const int n = (int)((nw - w0) < chunk ? (nw - w0) : chunk);
+    int rc = model_forward(ctx, m, d_mel, mel_rows, d_row ? d_row + w0 : nullptr, d_row ? d_valid + w0 : nullptr, d_row ? 0 : w0 * hop,
+                           hop, valid_const, n, ws, d_out + (size_t)w0 * NO, d_enc);
+    if (rc || (rc = after_chunk(w0, n))) return rc;
+  }
+  return WW_OK;
+}
+static int no_enc(int64_t, int) { return WW_OK; }  // the after_chunk of a caller that asks for no encoder rows
+
+// The reference's per-frame use (one window in, one posterior out, utils/time_tf_models.py) is the staging's pinned mode: no
+// host-to-device or device-to-host copy on its path.  Pinned mode synchronises once, so it is for calls of one chunk.
 static int forward_host(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t rows, int hop, int64_t nw, float *out,
                         float *enc) {
-  const int T = m->info.window, F = m->info.n_mel, NO = m->info.n_out;
+  const int T = m->info.window, F = m->info.n_mel, NO = m->info.n_out, chunk = chunk_of(nw);
   const size_t enc_per = (size_t)m->info.enc_rows * m->info.enc_width;
   WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
-  // Small calls (the reference's per-frame use: one window in, one posterior out, utils/time_tf_models.py) are
-  // latency-bound, and a copy-engine operation costs more than the few KB are worth: the window is staged in pinned
-  // host memory and the kernels read it over the bus themselves; the posteriors (and the encoder output) are stored
-  // into pinned host memory by the kernels.  No host-to-device or device-to-host copy on the path.
-  {
-    const size_t p_mel = ww_bump::need((size_t)rows * F, 4), p_out = ww_bump::need((size_t)nw * NO, 4);
-    const size_t p_enc = enc ? ww_bump::need((size_t)nw * enc_per, 4) : 0;
-    if (p_mel + p_out + p_enc <= WW_SMALL_IO_BYTES && nw <= 64) {
-      ww_small_io io(ctx);
-      int rc = io.init(p_mel + p_out + p_enc);
-      if (rc) return rc;
-      if ((rc = ww_ensure(ctx, ctx->dev, model_ws(m, (int)nw) + 1024, false))) return rc;
-      float *h_mel = io.take<float>((size_t)rows * F), *h_out = io.take<float>((size_t)nw * NO);
-      float *h_enc = enc ? io.take<float>((size_t)nw * enc_per) : nullptr;
-      memcpy(h_mel, mel, (size_t)rows * F * 4);
-      ww_bump db(ctx->dev.ptr, ctx->dev.cap);
-      void *ws = db.take<char>(model_ws(m, (int)nw));
-      rc = model_forward(ctx, m, io.dv(h_mel), rows, nullptr, nullptr, 0, hop, T, (int)nw, ws, io.dv(h_out), enc ? io.dv(h_enc) : nullptr);
-      if (rc) return rc;
-      WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      memcpy(out, h_out, (size_t)nw * NO * 4);
-      if (enc) memcpy(enc, h_enc, (size_t)nw * enc_per * 4);
-      return WW_OK;
-    }
-  }
-  const int chunk = nw < WW_MAX_CHUNK ? (int)nw : WW_MAX_CHUNK;
   const size_t b_mel = ww_bump::need((size_t)rows * F, 4), b_out = ww_bump::need((size_t)nw * NO, 4);
   const size_t b_enc = enc ? ww_bump::need((size_t)chunk * enc_per, 4) : 0;
   const size_t b_ws = model_ws(m, chunk);
-  int rc = ww_ensure(ctx, ctx->dev, b_mel + b_out + b_enc + b_ws + 1024, false);
+  ww_staged_io io(ctx);
+  int rc = io.init(b_mel + b_out + b_enc, b_ws + 1024, nw <= 64 && nw <= WW_MAX_CHUNK);
   if (rc) return rc;
-  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
-  float *d_mel = bump.take<float>((size_t)rows * F);
-  float *d_out = bump.take<float>((size_t)nw * NO);
-  float *d_enc = enc ? bump.take<float>((size_t)chunk * enc_per) : nullptr;
-  void *ws = bump.take<char>(b_ws);
-  WW_HIP(ctx, hipMemcpyAsync(d_mel, mel, (size_t)rows * F * 4, hipMemcpyHostToDevice, ctx->stream));
-  for (int64_t w0 = 0; w0 < nw; w0 += chunk) {
-    const int n = (int)((nw - w0) < chunk ? (nw - w0) : chunk);
-    rc = model_forward(ctx, m, d_mel, rows, nullptr, nullptr, w0 * hop, hop, T, n, ws, d_out + (size_t)w0 * NO, d_enc);
-    if (rc) return rc;
-    if (enc) {
-      WW_HIP(ctx, hipMemcpyAsync(enc + (size_t)w0 * enc_per, d_enc, (size_t)n * enc_per * 4, hipMemcpyDeviceToHost, ctx->stream));
-      WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-  }
-  WW_HIP(ctx, hipMemcpyAsync(out, d_out, (size_t)nw * NO * 4, hipMemcpyDeviceToHost, ctx->stream));
-  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return WW_OK;
+  const float *d_mel = io.in(mel, (size_t)rows * F);
+  float *d_out = io.out<float>((size_t)nw * NO);
+  float *d_enc = enc ? io.out<float>((size_t)chunk * enc_per) : nullptr;
+  void *ws = io.scratch(b_ws);
+  if (io.rc) return io.rc;
+  rc = forward_chunks(ctx, m, d_mel, rows, nullptr, nullptr, hop, T, nw, ws, d_out, d_enc, [&](int64_t w0, int n) -> int {
+    if (!enc) return WW_OK;
+    if (int r = io.fetch(enc + (size_t)w0 * enc_per, d_enc, (size_t)n * enc_per * 4)) return r;
+    return io.finish();
+  });
+  if (rc) return rc;
+  if ((rc = io.fetch(out, d_out, (size_t)nw * NO * 4))) return rc;
+  return io.finish();
 }
 
 __global__ void iota_offs_kernel(int64_t *sample_offs, int64_t *frame_offs, int n, int64_t samples, int64_t frames) {
@@ -1127,17 +1103,9 @@ int ww_forward_windows_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, i
   if (nw == 0) return WW_OK;
   if (!d_win_row || !d_win_valid) return ww_fail(ctx, WW_EINVAL, "window descriptors are NULL");
   WW_ON_DEVICE(ctx, dev);
-  const int NO = m->info.n_out;
-  const int chunk = nw < WW_MAX_CHUNK ? nw : WW_MAX_CHUNK;
-  int rc = ww_ensure(ctx, ctx->dev, model_ws(m, chunk) + 1024, false);
+  int rc = ww_ensure(ctx, ctx->dev, model_ws(m, chunk_of(nw)) + 1024, false);
   if (rc) return rc;
-  for (int w0 = 0; w0 < nw; w0 += chunk) {
-    const int n = (nw - w0) < chunk ? (nw - w0) : chunk;
-    rc = model_forward(ctx, m, d_mel, mel_rows, d_win_row + w0, d_win_valid + w0, 0, 0, 0, n, ctx->dev.ptr,
-                       d_out + (size_t)w0 * NO, nullptr);
-    if (rc) return rc;
-  }
-  return WW_OK;
+  return forward_chunks(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, nw, ctx->dev.ptr, d_out, nullptr, no_enc);
   WW_GUARD_END(ctx)
 }
 
@@ -1152,7 +1120,7 @@ int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, 
   WW_ON_DEVICE(ctx, dev);
   if (ww_crnn_segments_capable(m, hop)) return ww_k_crnn_segments_forward(ctx, m, d_mel, mel_rows, seg_row0, seg_nw, n_seg, hop, d_out);
   // every other model / mode: the same windows as an explicit list through the per-window kernels
-  const int T = m->info.window, NO = m->info.n_out;
+  const int T = m->info.window;
   std::vector<int64_t> rows;
   for (int s = 0; s < n_seg; ++s) {
     if (seg_nw[s] < 0) return ww_fail(ctx, WW_EINVAL, "negative window count in sequence %d", s);
@@ -1164,8 +1132,7 @@ int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, 
   if (nw == 0) return WW_OK;
   if (nw > 0x7fffffff) return ww_fail(ctx, WW_EINVAL, "too many windows in one call");
   std::vector<int32_t> valid((size_t)nw, T);
-  const int chunk = nw < WW_MAX_CHUNK ? (int)nw : WW_MAX_CHUNK;
-  const size_t b_rows = ww_bump::need((size_t)nw, 8), b_valid = ww_bump::need((size_t)nw, 4), b_ws = model_ws(m, chunk);
+  const size_t b_rows = ww_bump::need((size_t)nw, 8), b_valid = ww_bump::need((size_t)nw, 4), b_ws = model_ws(m, chunk_of(nw));
   int rc = ww_ensure(ctx, ctx->dev, b_rows + b_valid + b_ws + 1024, false);
   if (rc) return rc;
   ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
@@ -1175,12 +1142,7 @@ int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, 
   WW_HIP(ctx, hipMemcpyAsync(d_rows, rows.data(), (size_t)nw * 8, hipMemcpyHostToDevice, ctx->stream));
   WW_HIP(ctx, hipMemcpyAsync(d_valid, valid.data(), (size_t)nw * 4, hipMemcpyHostToDevice, ctx->stream));
   WW_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host vectors go out of scope
-  for (int64_t w0 = 0; w0 < nw; w0 += chunk) {
-    const int n = (int)((nw - w0) < chunk ? (nw - w0) : chunk);
-    rc = model_forward(ctx, m, d_mel, mel_rows, d_rows + w0, d_valid + w0, 0, 0, 0, n, ws, d_out + (size_t)w0 * NO, nullptr);
-    if (rc) return rc;
-  }
-  return WW_OK;
+  return forward_chunks(ctx, m, d_mel, mel_rows, d_rows, d_valid, 0, 0, nw, ws, d_out, nullptr, no_enc);
   WW_GUARD_END(ctx)
 }
 
@@ -1210,8 +1172,7 @@ static int wave_seq_validate(ww_ctx *ctx, const ww_model *m, int64_t total_rows,
 }
 
 // Cuts: a sequence is computed in segments of G rows; every segment but a sequence's first starts RF - 1 rows early and drops them.
-// The library's G makes a segment's warm-up + rows a whole number of 192-row chunks, and about two segments per CU once there is
-// enough work (warm-up: a tenth of the rows at most).
+// The library's G is ww_wave_segment_rows' (common.h), at least one chunk.
 static void wave_seq_make_plan(const ww_model *m, int64_t total_rows, const int64_t *row_offs, int n_seq, bool need_z, bool need_pool,
                                wave_seq_plan &pl) {
   const int rf = ww_wave_receptive_field(m), NO = m->info.n_out;
@@ -1221,12 +1182,7 @@ static void wave_seq_make_plan(const ww_model *m, int64_t total_rows, const int6
     pl.max_len = std::max<int64_t>(pl.max_len, row_offs[s + 1] - row_offs[s]);
   }
   int64_t G = m->opt_wave_seq_segment;
-  if (G <= 0) {
-    int64_t chunks = (span + 2 * WW_NUM_CUS * 192 - 1) / (2 * WW_NUM_CUS * 192);
-    chunks = std::min<int64_t>(std::max<int64_t>(chunks, 10), 64);
-    G = chunks * 192 - (rf - 1);
-    if (G < 192) G = 192;
-  }
+  if (G <= 0) G = std::max<int64_t>(ww_wave_segment_rows(span, rf), 192);
   for (int s = 0; s < n_seq; ++s) {
     const int64_t o = row_offs[s], len = row_offs[s + 1] - o;
     for (int64_t s0 = 0; s0 < len; s0 += G) {
@@ -1355,19 +1311,16 @@ int ww_clips_forward_dev(ww_ctx *ctx, const ww_model *m, const int16_t *d_pcm, i
   const size_t b_mel = ww_bump::need((size_t)n_clips * (nf > 0 ? nf : 1) * F, 4);
   const size_t b_ws = model_ws(m, n_clips);
   if ((rc = ww_ensure(ctx, ctx->dev, b_mel + b_ws + 1024, false))) return rc;
-  auto enqueue = [&]() -> int {
-    ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
-    float *d_mel = bump.take<float>((size_t)n_clips * (nf > 0 ? nf : 1) * F);
-    void *ws = bump.take<char>(b_ws);
-    int r = ww_k_logmel(ctx, m, d_pcm, nullptr, d_so, d_fo, n_clips, (int64_t)n_clips * nf, nf, fp, d_mel, samples, (int64_t)n_clips * samples);
-    if (r) return r;
-    // one window per clip: rows [c*nf, c*nf + min(nf, T)), zero padded to T
-    return model_forward(ctx, m, d_mel, (int64_t)n_clips * nf, nullptr, nullptr, 0, (int)nf, (int)(nf < T ? nf : T),
-                         n_clips, ws, d_out, nullptr);
-  };
+  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
+  float *d_mel = bump.take<float>((size_t)n_clips * (nf > 0 ? nf : 1) * F);
+  void *ws = bump.take<char>(b_ws);
   // Plain stream launches: measured on MI355X (round 1) the chain replays slower as a hipGraph (93 vs 88 us: the queue stays
-  // full, so launch latency is hidden, while a graph replay has a 10-16 us floor); the capture path was removed in round 3.
-  return enqueue();
+  // full, so launch latency is hidden, while a graph replay has a 10-16 us floor).
+  if ((rc = ww_k_logmel(ctx, m, d_pcm, nullptr, d_so, d_fo, n_clips, (int64_t)n_clips * nf, nf, fp, d_mel, samples, (int64_t)n_clips * samples)))
+    return rc;
+  // one window per clip: rows [c*nf, c*nf + min(nf, T)), zero padded to T
+  return model_forward(ctx, m, d_mel, (int64_t)n_clips * nf, nullptr, nullptr, 0, (int)nf, (int)(nf < T ? nf : T), n_clips, ws, d_out,
+                       nullptr);
   WW_GUARD_END(ctx)
 }
 

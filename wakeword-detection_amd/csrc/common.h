@@ -298,6 +298,14 @@ struct wv_seg {
   int32_t n, skip;
 };
 int ww_wave_receptive_field(const ww_model *m);  // 1 + 2 * sum of the dilations
+// The library's segment length for `rows` rows of work (WW_OPT_WAVE_SEQ_SEGMENT = 0), for ww_wave_sequence and the stream feed
+// alike; each clamps it to what its cuts need.  A segment's warm-up (rf - 1 rows) + its rows are a whole number of 192-row chunks:
+// about two segments per CU once there is enough work, 10 chunks at least (warm-up: a tenth of the rows at most) and 64 at most.
+static inline int64_t ww_wave_segment_rows(int64_t rows, int rf) {
+  int64_t chunks = (rows + 2 * WW_NUM_CUS * 192 - 1) / (2 * WW_NUM_CUS * 192);
+  chunks = chunks < 10 ? 10 : chunks > 64 ? 64 : chunks;
+  return chunks * 192 - (rf - 1);
+}
 int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const wv_seg *d_segs, int n_segs, float *d_enc, float *d_logits);
 // rows = offs[n_seq] - offs[0] (the rows that belong to a sequence), row_end = offs[n_seq]
 int ww_k_wave_pool(ww_ctx *ctx, const float *d_z, int64_t rows, int64_t row_end, int n_out, const int64_t *d_offs, int n_seq, int64_t pool_rows,

@@ -798,11 +798,7 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
     if (r > WW_FEED_TILE_ROWS || r > T) large_rows += r;
   }
   int64_t G = m->opt_wave_seq_segment;
-  if (G <= 0) {  // the library's choice, as ww_wave_sequence's: whole chunks, about two segments per CU once there is enough work
-    int64_t chunks = (large_rows + 2 * WW_NUM_CUS * 192 - 1) / (2 * WW_NUM_CUS * 192);
-    chunks = std::min<int64_t>(std::max<int64_t>(chunks, 10), 64);
-    G = chunks * 192 - (rf - 1);
-  }
+  if (G <= 0) G = ww_wave_segment_rows(large_rows, rf);
   G = std::min<int64_t>(std::max<int64_t>(G, std::max(rf - 1, 1)), 1 << 30);
   for (int i = 0; i < n; ++i) {
     const int s = ids[i];
