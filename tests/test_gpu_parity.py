@@ -132,6 +132,31 @@ def test_logmel_rows_across_clip_boundaries(engines, oracles, pre, hop, as_float
                 assert np.abs(got - oracles["CRNN"].logmel(p, 32768.0, False, pre)).max() < TOL_MEL
 
 
+@pytest.mark.parametrize("pre,hop,as_float", [(0.0, 160, False), (0.97, 160, False), (0.0, 100, True), (0.0, 512, False), (0.0, 7, False)])
+def test_logmel_tile_kernel_batch_equals_clips_alone(engines, pre, hop, as_float):
+    """logmel_kernel (precise=False) tiles every clip by itself, 16 frames to a workgroup, and stages a tile from the first
+    aligned vector at or below its first sample: a clip inside a batch starts at another sample offset than the clip alone
+    (other shifts, other vectors, the ragged end of the buffer somewhere else), and each frame's arithmetic depends on its
+    own samples only, so the batch must give, bit for bit, what its clips give one at a time.  The parameters take the
+    straight-line staging, the generic staging (pre-emphasis; a tile of more than two vectors per thread at hop 512), float
+    input, and the scalar Hann product with odd shifts (hop 7); the lengths give last tiles of 1-15 frames and clips
+    without a frame."""
+    from wwhip.engine import frontend_params
+    rng = np.random.default_rng(79)
+    W = 512
+    lens = [W + 146 * hop, W, W + hop, 0, W + 2 * hop + 1, 37, W + 5 * hop + 3, W + 3 * hop, W - 1, W + 11 * hop + hop // 2, W + 4 * hop]
+    pcm = [np.clip(rng.normal(0, 4000, n), -32768, 32767).astype(np.int16) for n in lens]
+    if as_float:
+        pcm = [p.astype(np.float32) / np.float32(32768.0) for p in pcm]
+    fp = frontend_params(32768.0, False, pre, hop, False)
+    eng = engines["CRNN"]
+    batch = eng.logmel(pcm, fp)
+    for n, p, got in zip(lens, pcm, batch):
+        nf = (n - W) // hop + 1 if n >= W else 0
+        assert got.shape == (nf, 40)
+        np.testing.assert_array_equal(got, eng.logmel([p], fp)[0])
+
+
 def test_logmel_equal_clips_arithmetic_lookup_equals_offset_tables(engines):
     """ww_clips_forward_dev tells the front end that its clips are equal and back to back (row -> clip by arithmetic);
     ww_logmel on the same clips walks the offset tables: the same posteriors, bit for bit, for a clip length whose frame count

@@ -18,6 +18,10 @@
 // log/affine tail, and the wave's 4x40 tile leaves through LDS as one contiguous store.  Wave 3 uses the sample
 // tile as its transpose buffer: the tile is dead once every wave has formed its Hann products (the second barrier).
 // (This kernel's fp64 form, the default front end of rounds 1-3, is recorded in profiles/EXPERIMENTS.md.)
+// logmel_kernel and logmel_rows_kernel are built from one set of pieces, defined once in front of them: LM_STAGE_GENERIC,
+// pcm_quot_clip2 and LM_STAGE_SIMPLE_LOAD / LM_STAGE_SIMPLE_STORE (staging), hann_pair, hann_mul_pair and hann_mul_at (Hann
+// product), LM_PARTNERS, LM_UNTANGLE_K2 and untangle_tail (real-FFT untangling), LM_MEL_TILE (mel filter and the park of the
+// output tile); logmel_lds is logmel_kernel's LDS layout, logmel_instance the host's choice of instantiation.
 // (stft_mag_kernel and the streaming kernel keep the earlier one-wave-per-frame radix-4 Stockham
 // FFT of fft_device.h: they are not on the batched path.)
 //
@@ -186,6 +190,258 @@ __device__ __forceinline__ H2 hann_pair(const H2 *tb, int n1, int j) {
 #define TR_LD 17    // padded row of the 16x16 transpose
 #define LM_WBUF (4 * MAG_LD * 4)  // logmel_kernel's per-wave scratch: 16x16 fp32 transposes of 4 frames, later their magnitudes
 
+// ---- pieces shared by logmel_kernel (256 threads on a 16-frame tile) and logmel_rows_kernel (one wave on four frames) ---------
+// Functions where both kernels keep their instruction stream, single-statement macros where a function moved it
+// (profiles/EXPERIMENTS.md, section 16); a macro's own names end in an underscore, thread index and stride are arguments.
+
+// Generic staging: dst[q * VEC + e] = normalised (and pre-emphasised) sample ga + q * VEC + e for q < n_vec, dealt to STRIDE
+// threads; ga is a multiple of VEC, so every full vector is one aligned 16-byte load
+#define LM_STAGE_GENERIC(F32IN_, STRIDE_, a_, dst_, ga_, n_vec_, s_begin_, total_, tid_)                                   \
+  do {                                                                                                                 \
+    constexpr int VEC_ = (F32IN_) ? 4 : 8;                                                                             \
+    const float alpha_ = (a_).preemph;                                                                                 \
+    for (int q_ = (tid_); q_ < (n_vec_); q_ += (STRIDE_)) {                                                            \
+      const int64_t g_ = (ga_) + (int64_t)q_ * VEC_;                                                                   \
+      float v_[VEC_ + 1];                                                                                              \
+      /* v_[0] = sample g-1 (pre-emphasis carry; 0 at the start of the utterance) */                                   \
+      v_[0] = (alpha_ != 0.0f && g_ - 1 >= (s_begin_)) ? norm_sample<F32IN_>(a_, g_ - 1) : 0.0f;                       \
+      if (g_ + VEC_ <= (total_)) {                                                                                     \
+        if (F32IN_) {                                                                                                  \
+          const float4 raw_ = *(const float4 *)((a_).f32 + g_);                                                        \
+          v_[1] = raw_.x; v_[2] = raw_.y; v_[3] = raw_.z; v_[4] = raw_.w;                                              \
+        } else {                                                                                                       \
+          const uint4 raw_ = *(const uint4 *)((a_).pcm + g_);                                                          \
+          const unsigned int w32_[4] = {raw_.x, raw_.y, raw_.z, raw_.w};                                               \
+          _Pragma("unroll") for (int e_ = 0; e_ < 8; ++e_) {                                                           \
+            const int16_t s16_ = (int16_t)((w32_[e_ >> 1] >> ((e_ & 1) * 16)) & 0xffffu);                              \
+            float f_ = pcm_quot((float)s16_, a_);                                                                      \
+            if ((a_).clip) f_ = fminf(fmaxf(f_, -1.0f), 1.0f);                                                         \
+            v_[1 + e_] = f_;                                                                                           \
+          }                                                                                                            \
+        }                                                                                                              \
+      } else { /* ragged end of the whole buffer */                                                                    \
+        _Pragma("unroll") for (int e_ = 0; e_ < VEC_; ++e_)                                                            \
+          v_[1 + e_] = (g_ + e_ < (total_)) ? norm_sample<F32IN_>(a_, g_ + e_) : 0.0f;                                 \
+      }                                                                                                                \
+      float o_[VEC_];                                                                                                  \
+      _Pragma("unroll") for (int e_ = 0; e_ < VEC_; ++e_) {                                                            \
+        /* reference: frame -= pre_emphasis * previous  (separate fp32 multiply and subtract).  Slots in front of the  \
+           utterance start are never read by a frame of this utterance, except that sample s_begin itself must see a   \
+           zero carry (v_[0] above / guard here). */                                                                   \
+        const float prev_ = (g_ + e_ == (s_begin_)) ? 0.0f : v_[e_];                                                   \
+        o_[e_] = (alpha_ != 0.0f) ? ww_preemph_rn(v_[1 + e_], alpha_, prev_) : v_[1 + e_];                             \
+      }                                                                                                                \
+      float4 *d4_ = (float4 *)((dst_) + (size_t)q_ * VEC_);                                                            \
+      d4_[0] = make_float4(o_[0], o_[1], o_[2], o_[3]);                                                                \
+      if (VEC_ == 8) d4_[1] = make_float4(o_[4], o_[5], o_[6], o_[7]);                                                 \
+    }                                                                                                                  \
+  } while (0)
+// logmel_rows_kernel stages from two places: one wave's instance of the above
+template <bool F32IN>
+__device__ __forceinline__ void stage_generic_wave(const logmel_args &a, float *dst, int64_t ga, int n_vec, int64_t s_begin,
+                                                   int64_t total, int lane) {
+  LM_STAGE_GENERIC(F32IN, 64, a, dst, ga, n_vec, s_begin, total, lane);
+}
+
+// The exact quotient (see pcm_quot) and the clip on the two int16 samples of one 32-bit word: v_pk_mul_f32 / v_pk_fma_f32, two
+// samples per issue; lim = 1 or +inf
+__device__ __forceinline__ void pcm_quot_clip2(const logmel_args &a, unsigned int w32, float lim, float &o0, float &o1) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const f32x2 r2 = {a.rdiv, a.rdiv}, nb2 = {-a.divisor, -a.divisor};
+  const f32x2 x = {(float)(int)(short)(w32 & 0xffffu), (float)((int)w32 >> 16)};
+  const f32x2 q0 = x * r2;
+  const f32x2 er = __builtin_elementwise_fma(nb2, q0, x);
+  const f32x2 q = __builtin_elementwise_fma(er, r2, q0);
+  o0 = __builtin_amdgcn_fmed3f(q.x, -lim, lim);
+  o1 = __builtin_amdgcn_fmed3f(q.y, -lim, lim);
+}
+
+// Straight-line staging (no pre-emphasis, divisor 32767/32768: the host checks), NV 16-byte vectors per thread of STRIDE threads,
+// indices of type idx_t: LM_STAGE_SIMPLE_LOAD requests all NV vectors before anything waits for one - the caller may put loads of
+// its own behind them - and LM_STAGE_SIMPLE_STORE normalises / clips them into tile[q * VEC ..], q = tid + STRIDE h < n_vec.
+// A load index is clamped: always a full vector inside the buffer, and never past this tile's last vector (threads beyond
+// it would otherwise pull the NEXT tile's lines through this XCD's L2: +40 % fabric traffic).
+#define LM_STAGE_SIMPLE_LOAD(F32IN_, NV_, STRIDE_, idx_t_, a_, ga_, n_vec_, total_, tid_, gq_, raw_)                        \
+  do {                                                                                                                 \
+    constexpr int VEC_ = (F32IN_) ? 4 : 8;                                                                             \
+    const idx_t_ last_ = ((total_) - VEC_) & ~(idx_t_)(VEC_ - 1); /* last full aligned vector (total >= WIN here) */   \
+    const idx_t_ tile_last_ = (ga_) + (idx_t_)((n_vec_) - 1) * VEC_;                                                   \
+    _Pragma("unroll") for (int h_ = 0; h_ < (NV_); ++h_) {                                                             \
+      (gq_)[h_] = (ga_) + (idx_t_)((tid_) + (STRIDE_) * h_) * VEC_;                                                    \
+      idx_t_ gl_ = (gq_)[h_] < tile_last_ ? (gq_)[h_] : tile_last_;                                                    \
+      gl_ = gl_ < last_ ? gl_ : last_;                                                                                 \
+      (raw_)[h_] = (F32IN_) ? *(const uint4 *)((a_).f32 + gl_) : *(const uint4 *)((a_).pcm + gl_);                     \
+    }                                                                                                                  \
+  } while (0)
+#define LM_STAGE_SIMPLE_STORE(F32IN_, NV_, STRIDE_, idx_t_, a_, tile_, n_vec_, total_, tid_, gq_, raw_)                     \
+  do {                                                                                                                 \
+    constexpr int VEC_ = (F32IN_) ? 4 : 8;                                                                             \
+    const idx_t_ last_ = ((total_) - VEC_) & ~(idx_t_)(VEC_ - 1);                                                      \
+    const float lim_ = (a_).clip ? 1.0f : __builtin_inff();                                                            \
+    _Pragma("unroll") for (int h_ = 0; h_ < (NV_); ++h_) {                                                             \
+      const int q_ = (tid_) + (STRIDE_) * h_;                                                                          \
+      if (q_ < (n_vec_)) {                                                                                             \
+        float o_[VEC_];                                                                                                \
+        if ((gq_)[h_] <= last_) {                                                                                      \
+          const unsigned int w32_[4] = {(raw_)[h_].x, (raw_)[h_].y, (raw_)[h_].z, (raw_)[h_].w};                       \
+          if (F32IN_) {                                                                                                \
+            _Pragma("unroll") for (int e_ = 0; e_ < VEC_; ++e_) o_[e_] = __uint_as_float(w32_[e_]);                    \
+          } else {                                                                                                     \
+            _Pragma("unroll") for (int e_ = 0; e_ < VEC_; e_ += 2) pcm_quot_clip2(a_, w32_[e_ >> 1], lim_, o_[e_], o_[e_ + 1]); \
+          }                                                                                                            \
+        } else { /* ragged end of the whole buffer: element-wise, zero beyond it */                                    \
+          _Pragma("unroll") for (int e_ = 0; e_ < VEC_; ++e_)                                                          \
+            o_[e_] = ((gq_)[h_] + e_ < (total_)) ? norm_sample<F32IN_>(a_, (int64_t)(gq_)[h_] + e_) : 0.0f;            \
+        }                                                                                                              \
+        float4 *d4_ = (float4 *)((tile_) + (size_t)q_ * VEC_);                                                         \
+        d4_[0] = make_float4(o_[0], o_[1], o_[2], o_[3]);                                                              \
+        if (VEC_ == 8) d4_[1] = make_float4(o_[4], o_[5], o_[6], o_[7]);                                               \
+      }                                                                                                                \
+    }                                                                                                                  \
+  } while (0)
+
+// Hann product of one n1 (pass 1: lane j holds z[16 n1 + j] = (x[2n] h[2n], x[2n+1] h[2n+1]), n = 16 n1 + j) from the sample pair
+// an 8-byte LDS read delivered, and from two scalar reads (odd shift or hop).  fp32: tflite.py:175 forms the product in fp64.
+template <typename R, typename H2>
+__device__ __forceinline__ cplx<R> hann_mul_pair(double xs, const H2 h) {
+  return {(R)((R)__int_as_float(__double2loint(xs)) * h.x), (R)((R)__int_as_float(__double2hiint(xs)) * h.y)};
+}
+template <typename R, typename H2>
+__device__ __forceinline__ cplx<R> hann_mul_at(const float *src, int n, const H2 h) {
+  return {(R)((R)src[2 * n] * h.x), (R)((R)src[2 * n + 1] * h.y)};
+}
+
+// Real-FFT untangling.  With a = Z[k], b = conj Z[256-k]:  2E = a+b, 2O = (a-b)/i, 2T = W512^k 2O and
+//   2X[k] = 2E + 2T,   2X[256-k] = conj(2E - 2T)   ->  two magnitudes per evaluation, k < 128 only;
+//   the factor 2 leaves as an exact 0.5 after the fp32 square root.
+// After the second DFT pass lane j register k2 holds k = j + 16 k2; its partner Z[256-k] lives in lane (16-j)%16 at
+// k2' = 15-k2 (j > 0) or in the same lane at k2' = (16-k2)%16 (j = 0).  LM_PARTNERS brings the eight partners of k2 = 0..7
+// into pz_[8] through the (dead) transpose buffer trs_ of this frame: rows 8..15 <- registers k2' = 8..15, row 7 <- k2' = 0
+// (only lane 0 reads that one), so lane j reads row 15-k2 (+1 for j = 0; row 7 for k2 = 0); real parts, then imaginary parts.
+#define LM_PARTNERS(R_, w_, trs_, j_, pz_)                                                          \
+  do {                                                                                              \
+    const int pj_ = (16 - (j_)) & 15;                                                               \
+    const R_ *prow0_ = (trs_) + ((j_) == 0 ? 7 : 15) * TR_LD + pj_;                                 \
+    const R_ *prow_ = (trs_) + ((j_) == 0 ? 16 : 15) * TR_LD + pj_;                                 \
+    (trs_)[7 * TR_LD + (j_)] = (w_)[pos_of(0)].re;                                                  \
+    _Pragma("unroll") for (int r_ = 8; r_ < 16; ++r_) (trs_)[r_ * TR_LD + (j_)] = (w_)[pos_of(r_)].re; \
+    lds_fence();                                                                                    \
+    (pz_)[0].re = prow0_[0];                                                                        \
+    _Pragma("unroll") for (int k2_ = 1; k2_ < 8; ++k2_) (pz_)[k2_].re = prow_[-k2_ * TR_LD];        \
+    lds_fence();                                                                                    \
+    (trs_)[7 * TR_LD + (j_)] = (w_)[pos_of(0)].im;                                                  \
+    _Pragma("unroll") for (int r_ = 8; r_ < 16; ++r_) (trs_)[r_ * TR_LD + (j_)] = (w_)[pos_of(r_)].im; \
+    lds_fence();                                                                                    \
+    (pz_)[0].im = prow0_[0];                                                                        \
+    _Pragma("unroll") for (int k2_ = 1; k2_ < 8; ++k2_) (pz_)[k2_].im = prow_[-k2_ * TR_LD];        \
+    lds_fence();                                                                                    \
+  } while (0)
+
+// One k = j + 16 k2 < 128 from own = Z[k], its partner p = Z[256 - k] and un = W512^k: magnitudes 2|X[k]| and 2|X[256 - k]|
+// into the frame's row (the mel weights carry the 0.5)
+#define LM_UNTANGLE_K2(R_, own_, p_, un_, mrow_, k_)                                                        \
+  do {                                                                                                   \
+    const cplx<R_> o_ = (own_), u_ = (un_);                                                              \
+    const R_ er_ = o_.re + (p_).re, ei_ = o_.im - (p_).im;                                               \
+    const R_ or_ = o_.im + (p_).im, oi_ = (p_).re - o_.re;                                               \
+    const R_ tr_ = or_ * u_.re - oi_ * u_.im, ti_ = or_ * u_.im + oi_ * u_.re;                           \
+    const R_ pr_ = er_ + tr_, pi_ = ei_ + ti_, qr_ = er_ - tr_, qi_ = ei_ - ti_;                         \
+    (mrow_)[(k_)] = __builtin_amdgcn_sqrtf((float)(pr_ * pr_ + pi_ * pi_));                              \
+    (mrow_)[256 - (k_)] = __builtin_amdgcn_sqrtf((float)(qr_ * qr_ + qi_ * qi_)); /* k = 0 -> bin 256 */ \
+  } while (0)
+// k = 128 pairs with itself: X[128] = conj(Z[128]) (lane 0, k2 = 8: z); bins 257..271 are zero padding
+template <typename R>
+__device__ __forceinline__ void untangle_tail(const cplx<R> z, float *mrow, int j) {
+  if (j == 0) mrow[128] = 2.0f * __builtin_amdgcn_sqrtf((float)(z.re * z.re + z.im * z.im));
+  else mrow[256 + j] = 0.0f;
+}
+
+// Mel filterbank on the vector ALU, per wave, on the wave's four rows of magnitudes mg_[4][MAG_LD], and the park of its
+// 4 x n_mel tile at mg_ for one contiguous store.  Lane 4 s + q owns frame q and slot s of each of the three
+//   band groups (load_filter, api.hip): 36 + 16 + 12 padded taps, one fused multiply-add per tap with the
+//   magnitudes read 16 bytes at a time from this wave's LDS rows.  Frame in the low lane bits: the four
+//   16-lane groups a ds_read_b128 is served in then hold four slots x four frames each, the rows of the four
+//   frames sit 4 sixteen-byte bank slots apart, and load_filter deals the bands so that the four slots of such
+//   a group start on different slots mod 4 - conflict-free.  (The fp32 MFMA form of this contraction kept
+//   the SIMD's vector ALU idle for 32 cycles per instruction - fp32 MFMA and VALU share a datapath on gfx950
+//   - and needed three workgroup barriers for the partial sums; this form needs none.)
+// Each group's weight chunks are fetched when its turn comes (the 64 weight registers must not be live across the FFT, and one
+// group's magnitudes and weights are in flight at a time); without melv_aligned the magnitudes are read a float at a time.
+// Empty slots write to a spare word each so that the code stays straight-line.
+#define LM_MEL_LOGTAIL(a_, acc_, bias_) ((logf(fmaxf((acc_) + (bias_), (a_).floor_v)) + (a_).log_off) * (a_).scale)
+#define LM_MEL_TILE(a_, mg_, lane_)                                                                                    \
+  do {                                                                                                                 \
+    const int j_ = (lane_) >> 2, sub_ = (lane_) & 3; /* (slot, frame) of this lane */                                  \
+    constexpr int CAPQ_[3] = {9, 4, 3}, C0_[3] = {0, 9, 13};                                                           \
+    const float4 *wv_ = (const float4 *)(a_).melV + j_;                                                                \
+    const float *mrow_ = (mg_) + sub_ * MAG_LD;                                                                        \
+    __builtin_amdgcn_sched_barrier(0);                                                                                 \
+    int meta_[3];                                                                                                      \
+    _Pragma("unroll") for (int g_ = 0; g_ < 3; ++g_) meta_[g_] = (a_).melVmeta[g_ * 16 + j_];                          \
+    float4 wq_[WW_MELV_CHUNKS];                                                                                        \
+    int band_[3];                                                                                                      \
+    float bias_[3];                                                                                                    \
+    _Pragma("unroll") for (int g_ = 0; g_ < 3; ++g_) {                                                                 \
+      band_[g_] = (int)((unsigned)meta_[g_] >> 16); /* 0xffff: empty slot */                                           \
+      bias_[g_] = (a_).bias[band_[g_] < (a_).n_mel ? band_[g_] : 0];                                                   \
+    }                                                                                                                  \
+    float res_[3];                                                                                                     \
+    if ((a_).melv_aligned) {                                                                                           \
+      _Pragma("unroll") for (int g_ = 0; g_ < 3; ++g_) {                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                                             \
+        _Pragma("unroll") for (int c_ = 0; c_ < CAPQ_[g_]; ++c_) wq_[C0_[g_] + c_] = wv_[(C0_[g_] + c_) * 16];         \
+        lds_cfloat4 *mb_ = (lds_cfloat4 *)lds_opaque(mrow_ + (meta_[g_] & 0xffff));                                    \
+        float acc_ = 0.f, acc1_ = 0.f; /* two chains: a dependent fp32 FMA does not issue back to back */              \
+        _Pragma("unroll") for (int c_ = 0; c_ < CAPQ_[g_]; ++c_) {                                                     \
+          const float4 w4_ = wq_[C0_[g_] + c_];                                                                        \
+          const f32x4 m4_ = mb_[c_];                                                                                   \
+          acc_ = fmaf(m4_[0], w4_.x, acc_);                                                                            \
+          acc1_ = fmaf(m4_[1], w4_.y, acc1_);                                                                          \
+          acc_ = fmaf(m4_[2], w4_.z, acc_);                                                                            \
+          acc1_ = fmaf(m4_[3], w4_.w, acc1_);                                                                          \
+        }                                                                                                              \
+        acc_ += acc1_;                                                                                                 \
+        res_[g_] = LM_MEL_LOGTAIL(a_, acc_, bias_[g_]);                                                                \
+      }                                                                                                                \
+    } else {                                                                                                           \
+      _Pragma("unroll") for (int g_ = 0; g_ < 3; ++g_) {                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                                             \
+        _Pragma("unroll") for (int c_ = 0; c_ < CAPQ_[g_]; ++c_) wq_[C0_[g_] + c_] = wv_[(C0_[g_] + c_) * 16];         \
+        lds_cfloat *mb_ = lds_opaque(mrow_ + (meta_[g_] & 0xffff));                                                    \
+        float acc_ = 0.f;                                                                                              \
+        _Pragma("unroll") for (int c_ = 0; c_ < CAPQ_[g_]; ++c_) {                                                     \
+          const float4 w4_ = wq_[C0_[g_] + c_];                                                                        \
+          acc_ = fmaf(mb_[4 * c_ + 0], w4_.x, acc_);                                                                   \
+          acc_ = fmaf(mb_[4 * c_ + 1], w4_.y, acc_);                                                                   \
+          acc_ = fmaf(mb_[4 * c_ + 2], w4_.z, acc_);                                                                   \
+          acc_ = fmaf(mb_[4 * c_ + 3], w4_.w, acc_);                                                                   \
+        }                                                                                                              \
+        res_[g_] = LM_MEL_LOGTAIL(a_, acc_, bias_[g_]);                                                                \
+      }                                                                                                                \
+    }                                                                                                                  \
+    lds_fence(); /* the magnitudes are dead */                                                                         \
+    _Pragma("unroll") for (int g_ = 0; g_ < 3; ++g_)                                                                   \
+      (mg_)[band_[g_] < (a_).n_mel ? sub_ * (a_).n_mel + band_[g_] : 4 * (a_).n_mel + (lane_)] = res_[g_];             \
+    lds_fence();                                                                                                       \
+  } while (0)
+
+// logmel_kernel's dynamic LDS, byte offsets: what the kernel forms its pointers from and the launcher its size
+struct logmel_lds {
+  // Hann table: np.hanning is symmetric (h[n] = h[511 - n]), so the first 256 values serve as 128 pairs (float2, in the slots
+  // of the fp64 form's double2); twiddle tables [k1][j] = W256^(j k1) and W512^k; one buffer per wave but the last, which uses the
+  // sample tile: that is dead once every wave has formed its Hann products (the second barrier)
+  static constexpr size_t hann = 0;
+  static constexpr size_t tw = hann + 128 * sizeof(double2);
+  static constexpr size_t un = tw + 256 * sizeof(cplx<float>);
+  static constexpr size_t wbuf = un + 256 * sizeof(cplx<float>);
+  static constexpr size_t tile = wbuf + (WAVES - 1) * LM_WBUF;  // fp32 samples, [WIN + (FPB-1)*hop + 16]
+  static size_t bytes(int hop) {
+    size_t tile_b = (size_t)(WIN + (FPB - 1) * hop + 16) * 4;
+    if (tile_b < (size_t)LM_WBUF) tile_b = LM_WBUF;  // the last wave's buffer
+    return (tile + tile_b + 15) & ~size_t(15);
+  }
+};
+
 template <bool F32IN, bool SIMPLE>
 __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -205,18 +461,13 @@ __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
   if (f0 >= nf) return;
   const int nfb = (int)((nf - f0) < FPB ? (nf - f0) : FPB);
 
-  // ---- LDS carve-up (logmel_smem)
-  size_t off = 0;
-  // Hann table: np.hanning is symmetric (h[n] = h[511 - n]), so the first 256 values serve as 128 pairs
+  // ---- LDS carve-up
   typedef float2 H2;
-  H2 *tb_hann = (H2 *)(smem + off); off += 128 * sizeof(double2);
-  // twiddle tables; three per-wave buffers: wave 3 uses the sample tile, which is dead once every wave has formed its
-  // Hann products (the second barrier)
-  cplx<R> *tb_tw = (cplx<R> *)(smem + off); off += 256 * sizeof(cplx<R>);   // [k1][j] = W256^(j k1)
-  cplx<R> *tb_un = (cplx<R> *)(smem + off); off += 256 * sizeof(cplx<R>);   // W512^k
-  constexpr int NWB = WAVES - 1;
-  unsigned char *wbuf = smem + off; off += NWB * LM_WBUF;
-  float *tile = (float *)(smem + off);  // fp32 samples, [WIN + (FPB-1)*hop + 16]
+  H2 *tb_hann = (H2 *)(smem + logmel_lds::hann);
+  cplx<R> *tb_tw = (cplx<R> *)(smem + logmel_lds::tw);
+  cplx<R> *tb_un = (cplx<R> *)(smem + logmel_lds::un);
+  unsigned char *wbuf = smem + logmel_lds::wbuf;
+  float *tile = (float *)(smem + logmel_lds::tile);
 
   // ---- stage the sample tile: aligned 16-byte global loads; tile[i + shift] = x[g_first + i]
   constexpr int VEC = F32IN ? 4 : 8;                      // elements per 16-byte load
@@ -240,100 +491,19 @@ __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
     const int64_t ga = g_first - shift;                   // multiple of VEC, >= 0
     const int n_vec = (shift + n_need + VEC - 1) / VEC;
     const int64_t total = a.sample_offs[a.n_utt];
-    const int64_t last = (total - VEC) & ~(int64_t)(VEC - 1);  // last full aligned vector (total >= WIN here)
-    const int64_t tile_last = ga + (int64_t)(n_vec - 1) * VEC;
     int64_t gq[2];
     uint4 raw[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      gq[h] = ga + (int64_t)(tid + 256 * h) * VEC;
-      // clamped: always a full vector inside the buffer, and never past this block's last vector (threads
-      // beyond it would otherwise pull the NEXT tile's lines through this XCD's L2: +40 % fabric traffic)
-      int64_t gl = gq[h] < tile_last ? gq[h] : tile_last;
-      gl = gl < last ? gl : last;
-      raw[h] = F32IN ? *(const uint4 *)(a.f32 + gl) : *(const uint4 *)(a.pcm + gl);
-    }
+    LM_STAGE_SIMPLE_LOAD(F32IN, 2, 256, int64_t, a, ga, n_vec, total, tid, gq, raw);
     const double2 hv = *(const double2 *)(a.hann + 2 * (tid & 127));
     const double2 twv = *(const double2 *)(a.tw16 + 2 * tid);
-    const float lim = a.clip ? 1.0f : __builtin_inff();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int q = tid + 256 * h;
-      if (q < n_vec) {
-        float o[VEC];
-        if (gq[h] <= last) {
-          const unsigned int w32[4] = {raw[h].x, raw[h].y, raw[h].z, raw[h].w};
-          if (F32IN) {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) o[e] = __uint_as_float(w32[e]);
-          } else {
-            // the exact quotient (see pcm_quot) on sample pairs: v_pk_mul_f32 / v_pk_fma_f32, two samples per issue
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            const f32x2 r2 = {a.rdiv, a.rdiv}, nb2 = {-a.divisor, -a.divisor};
-#pragma unroll
-            for (int e = 0; e < VEC; e += 2) {
-              const f32x2 x = {(float)(int)(short)(w32[e >> 1] & 0xffffu), (float)((int)w32[e >> 1] >> 16)};
-              const f32x2 q0 = x * r2;
-              const f32x2 er = __builtin_elementwise_fma(nb2, q0, x);
-              const f32x2 q = __builtin_elementwise_fma(er, r2, q0);
-              o[e] = __builtin_amdgcn_fmed3f(q.x, -lim, lim);
-              o[e + 1] = __builtin_amdgcn_fmed3f(q.y, -lim, lim);
-            }
-          }
-        } else {  // ragged end of the whole buffer: element-wise, zero beyond it
-#pragma unroll
-          for (int e = 0; e < VEC; ++e) o[e] = (gq[h] + e < total) ? norm_sample<F32IN>(a, gq[h] + e) : 0.0f;
-        }
-        float4 *dst = (float4 *)(tile + (size_t)q * VEC);
-        dst[0] = make_float4(o[0], o[1], o[2], o[3]);
-        if (VEC == 8) dst[1] = make_float4(o[4], o[5], o[6], o[7]);
-      }
-    }
+    LM_STAGE_SIMPLE_STORE(F32IN, 2, 256, int64_t, a, tile, n_vec, total, tid, gq, raw);
     fill_tables(hv, twv);
   } else {
     fill_tables(*(const double2 *)(a.hann + 2 * (tid & 127)), *(const double2 *)(a.tw16 + 2 * tid));
     const int64_t ga = g_first - shift;                   // multiple of VEC, >= 0
     const int n_vec = (shift + n_need + VEC - 1) / VEC;
     const int64_t total = a.sample_offs[a.n_utt];
-    const float alpha = a.preemph;
-    for (int q = tid; q < n_vec; q += 256) {
-      const int64_t g = ga + (int64_t)q * VEC;
-      float v[VEC + 1];
-      // v[0] = sample g-1 (pre-emphasis carry; 0 at the start of the utterance)
-      v[0] = (alpha != 0.0f && g - 1 >= s_begin) ? norm_sample<F32IN>(a, g - 1) : 0.0f;
-      if (g + VEC <= total) {
-        if (F32IN) {
-          const float4 raw = *(const float4 *)(a.f32 + g);
-          v[1] = raw.x; v[2] = raw.y; v[3] = raw.z; v[4] = raw.w;
-        } else {
-          const uint4 raw = *(const uint4 *)(a.pcm + g);
-          const unsigned int w32[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const int16_t s16 = (int16_t)((w32[e >> 1] >> ((e & 1) * 16)) & 0xffffu);
-            float f = pcm_quot((float)s16, a);
-            if (a.clip) f = fminf(fmaxf(f, -1.0f), 1.0f);
-            v[1 + e] = f;
-          }
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) v[1 + e] = (g + e < total) ? norm_sample<F32IN>(a, g + e) : 0.0f;
-      }
-      float o[VEC];
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        // reference: frame -= pre_emphasis * previous  (separate fp32 multiply and subtract).
-        // Slots in front of the utterance start are never read by a frame of this utterance,
-        // except that sample s_begin itself must see a zero carry (v[0] above / guard here).
-        const bool at_start = (g + e == s_begin);
-        const float prev = at_start ? 0.0f : v[e];
-        o[e] = (alpha != 0.0f) ? ww_preemph_rn(v[1 + e], alpha, prev) : v[1 + e];
-      }
-      float4 *dst = (float4 *)(tile + (size_t)q * VEC);
-      dst[0] = make_float4(o[0], o[1], o[2], o[3]);
-      if (VEC == 8) dst[1] = make_float4(o[4], o[5], o[6], o[7]);
-    }
+    LM_STAGE_GENERIC(F32IN, 256, a, tile, ga, n_vec, s_begin, total, tid);
   }
   __syncthreads();
 
@@ -359,17 +529,12 @@ __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
       for (int n1 = 0; n1 < 16; ++n1) h[n1] = hann_pair(tb_hann, n1, j);
       lds_wait_all(xs);
 #pragma unroll
-      for (int n1 = 0; n1 < 16; ++n1) {
-        v[n1].re = (R)((R)__int_as_float(__double2loint(xs[n1])) * h[n1].x);
-        v[n1].im = (R)((R)__int_as_float(__double2hiint(xs[n1])) * h[n1].y);
-      }
+      for (int n1 = 0; n1 < 16; ++n1) v[n1] = hann_mul_pair<R>(xs[n1], h[n1]);
     } else {
 #pragma unroll
       for (int n1 = 0; n1 < 16; ++n1) {
-        const int n = 16 * n1 + j;
         const H2 h = hann_pair(tb_hann, n1, j);
-        v[n1].re = (R)((R)src[2 * n] * h.x);
-        v[n1].im = (R)((R)src[2 * n + 1] * h.y);
+        v[n1] = hann_mul_at<R>(src, 16 * n1 + j, h);
       }
     }
   }
@@ -397,134 +562,25 @@ __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
     lds_fence();
     // pass 2: lane j = k1 holds Y[n2][k1]; output w[pos] = Z[k1 + 16 k_of(pos)]
     dft16<R>(w);
-    // untangle: with a = Z[k], b = conj Z[256-k]:  2E = a+b, 2O = (a-b)/i, 2T = W512^k 2O and
-    //   2X[k] = 2E + 2T,   2X[256-k] = conj(2E - 2T)   ->  two magnitudes per evaluation, k < 128 only;
-    //   the factor 2 leaves as an exact 0.5 after the fp32 square root.
-    // Lane j register k2 holds k = j + 16 k2; its partner Z[256-k] lives in lane (16-j)%16 at
-    // k2' = 15-k2 (j > 0) or in the same lane at k2' = (16-k2)%16 (j = 0).  The partners travel
-    // through the (dead) transpose buffer: rows 8..15 <- registers k2' = 8..15, row 7 <- k2' = 0
-    // (only lane 0 reads that one), so lane j reads row 15-k2 (+1 for j = 0; row 7 for k2 = 0).
-    const int pj = (16 - j) & 15;
-    const R *prow0 = trs + (j == 0 ? 7 : 15) * TR_LD + pj;
-    const R *prow = trs + (j == 0 ? 16 : 15) * TR_LD + pj;
+    // untangle: the partners Z[256 - k] arrive through the (dead) transpose buffer, W512^k from the LDS table
     cplx<R> pz[8];
-    trs[7 * TR_LD + j] = w[pos_of(0)].re;
-#pragma unroll
-    for (int r = 8; r < 16; ++r) trs[r * TR_LD + j] = w[pos_of(r)].re;
-    lds_fence();
-    pz[0].re = prow0[0];
-#pragma unroll
-    for (int k2 = 1; k2 < 8; ++k2) pz[k2].re = prow[-k2 * TR_LD];
-    lds_fence();
-    trs[7 * TR_LD + j] = w[pos_of(0)].im;
-#pragma unroll
-    for (int r = 8; r < 16; ++r) trs[r * TR_LD + j] = w[pos_of(r)].im;
-    lds_fence();
-    pz[0].im = prow0[0];
-#pragma unroll
-    for (int k2 = 1; k2 < 8; ++k2) pz[k2].im = prow[-k2 * TR_LD];
-    lds_fence();
+    LM_PARTNERS(R, w, trs, j, pz);
     float *mrow = mg + sub * MAG_LD;
 #pragma unroll
-    for (int k2 = 0; k2 < 8; ++k2) {
-      const cplx<R> own = w[pos_of(k2)];
-      const cplx<R> un = tb_un[j + 16 * k2];  // W512^(j + 16 k2)
-      const R er = own.re + pz[k2].re, ei = own.im - pz[k2].im;
-      const R orr = own.im + pz[k2].im, oi = pz[k2].re - own.re;
-      const R tr_ = orr * un.re - oi * un.im, ti_ = orr * un.im + oi * un.re;
-      const R pr = er + tr_, pi = ei + ti_, qr = er - tr_, qi = ei - ti_;
-      const int k = j + 16 * k2;
-      mrow[k] = __builtin_amdgcn_sqrtf((float)(pr * pr + pi * pi));  // 2|X[k]|: the mel weights carry the 0.5
-      mrow[256 - k] = __builtin_amdgcn_sqrtf((float)(qr * qr + qi * qi));  // k = 0 -> bin 256
-    }
-    {
-      // k = 128 pairs with itself: X[128] = conj(Z[128]) (lane 0, k2 = 8); bins 257..271 are zero padding
-      const cplx<R> z = w[pos_of(8)];
-      if (j == 0) mrow[128] = 2.0f * __builtin_amdgcn_sqrtf((float)(z.re * z.re + z.im * z.im));
-      else mrow[256 + j] = 0.0f;
-    }
+    for (int k2 = 0; k2 < 8; ++k2) LM_UNTANGLE_K2(R, w[pos_of(k2)], pz[k2], tb_un[j + 16 * k2], mrow, j + 16 * k2);
+    untangle_tail<R>(w[pos_of(8)], mrow, j);
   }
 
-  // ---- mel filterbank on the vector ALU, per wave: lane 4 s + q owns frame q and slot s of each of the three
-  //   band groups (load_filter, api.hip): 36 + 16 + 12 padded taps, one fused multiply-add per tap with the
-  //   magnitudes read 16 bytes at a time from this wave's LDS rows.  Frame in the low lane bits: the four
-  //   16-lane groups a ds_read_b128 is served in then hold four slots x four frames each, the rows of the four
-  //   frames sit 4 sixteen-byte bank slots apart, and load_filter deals the bands so that the four slots of such
-  //   a group start on different slots mod 4 - conflict-free.  (The fp32 MFMA form of this contraction kept
-  //   the SIMD's vector ALU idle for 32 cycles per instruction - fp32 MFMA and VALU share a datapath on gfx950
-  //   - and needed three workgroup barriers for the partial sums; this form needs none.)
+  // ---- mel filterbank and the park of the wave's 4 x n_mel tile, which leaves as one contiguous store
   lds_fence();
   {
-    const int j = lane >> 2, sub = lane & 3;  // mel phase only: (slot, frame) of this lane
-    constexpr int CAPQ[3] = {9, 4, 3}, C0[3] = {0, 9, 13};
-    const float4 *wv = (const float4 *)a.melV + j;
-    const float *mrow = mg + sub * MAG_LD;
-    __builtin_amdgcn_sched_barrier(0);  // the 64 weight registers must not be live across the FFT
-    int meta[3];
-#pragma unroll
-    for (int g = 0; g < 3; ++g) meta[g] = a.melVmeta[g * 16 + j];
-    // each group's weight chunks are fetched when its turn comes (96 registers at 5 workgroups per CU)
-    float4 wq[WW_MELV_CHUNKS];
-    int band[3];
-    float bias[3];
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-      band[g] = (int)((unsigned)meta[g] >> 16);  // 0xffff: empty slot
-      bias[g] = a.bias[band[g] < a.n_mel ? band[g] : 0];
-    }
-    float res[3];
-    if (a.melv_aligned) {
-#pragma unroll
-      for (int g = 0; g < 3; ++g) {
-        __builtin_amdgcn_sched_barrier(0);  // one group's magnitudes in flight at a time
-#pragma unroll
-        for (int c = 0; c < CAPQ[g]; ++c) wq[C0[g] + c] = wv[(C0[g] + c) * 16];
-        lds_cfloat4 *mb = (lds_cfloat4 *)lds_opaque(mrow + (meta[g] & 0xffff));
-        float acc = 0.f, acc1 = 0.f;  // two chains: a dependent fp32 FMA does not issue back to back
-#pragma unroll
-        for (int c = 0; c < CAPQ[g]; ++c) {
-          const float4 w4 = wq[C0[g] + c];
-          const f32x4 m4 = mb[c];
-          acc = fmaf(m4[0], w4.x, acc);
-          acc1 = fmaf(m4[1], w4.y, acc1);
-          acc = fmaf(m4[2], w4.z, acc);
-          acc1 = fmaf(m4[3], w4.w, acc1);
-        }
-        acc += acc1;
-        res[g] = (logf(fmaxf(acc + bias[g], a.floor_v)) + a.log_off) * a.scale;
-      }
-    } else {
-#pragma unroll
-      for (int g = 0; g < 3; ++g) {
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int c = 0; c < CAPQ[g]; ++c) wq[C0[g] + c] = wv[(C0[g] + c) * 16];
-        lds_cfloat *mb = lds_opaque(mrow + (meta[g] & 0xffff));
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < CAPQ[g]; ++c) {
-          const float4 w4 = wq[C0[g] + c];
-          acc = fmaf(mb[4 * c + 0], w4.x, acc);
-          acc = fmaf(mb[4 * c + 1], w4.y, acc);
-          acc = fmaf(mb[4 * c + 2], w4.z, acc);
-          acc = fmaf(mb[4 * c + 3], w4.w, acc);
-        }
-        res[g] = (logf(fmaxf(acc + bias[g], a.floor_v)) + a.log_off) * a.scale;
-      }
-    }
-    // park the wave's 4 x n_mel tile in LDS (its magnitudes are dead) for one contiguous store; empty slots
-    // write to a spare word each so that the code stays straight-line
-    lds_fence();
-    float *mt = mg;
-#pragma unroll
-    for (int g = 0; g < 3; ++g) mt[band[g] < a.n_mel ? sub * a.n_mel + band[g] : 4 * a.n_mel + lane] = res[g];
-    lds_fence();
+    LM_MEL_TILE(a, mg, lane);
     const int nv = (nfb - fb) < 4 ? (nfb - fb) : 4;
     float *dstf = a.mel + (a.frame_offs[u] + f0 + fb) * (int64_t)a.n_mel;
     if ((((uintptr_t)dstf) & 15) == 0 && (a.n_mel & 3) == 0) {
-      for (int i = lane; i < nv * a.n_mel / 4; i += 64) ((float4 *)dstf)[i] = ((const float4 *)mt)[i];
+      for (int i = lane; i < nv * a.n_mel / 4; i += 64) ((float4 *)dstf)[i] = ((const float4 *)mg)[i];
     } else {
-      for (int i = lane; i < nv * a.n_mel; i += 64) dstf[i] = mt[i];
+      for (int i = lane; i < nv * a.n_mel; i += 64) dstf[i] = mg[i];
     }
   }
 }
@@ -550,6 +606,11 @@ __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
 // A wave whose four frames do not lie in one clip within 3 hops of each other (a clip boundary) stages them frame by frame
 // (generic path, <= 1 wave in 37 for 1.5 s clips).  The arithmetic is that of the fp64 tile kernel it replaced, instruction for
 // instruction, with bit-identical results (profiles/EXPERIMENTS.md, round 4).
+// What it has in common with logmel_kernel is the shared pieces above, instantiated for one wave and R = double: staging
+// (LM_STAGE_SIMPLE_LOAD / LM_STAGE_SIMPLE_STORE with NV vectors per lane and idx_t indices; stage_generic_wave = LM_STAGE_GENERIC at
+// stride 64), hann_pair on the global double2 table with hann_mul_pair / hann_mul_at per chunk of LW_HC, LM_PARTNERS,
+// LM_UNTANGLE_K2 on a register chunk of W512^k, untangle_tail and LM_MEL_TILE.  Its own: the row -> clip lookup, the chunked
+// table fetches, the fp64 transposes (lds_read16_b64) and the final store, whose rows are global (vm) instead of per clip.
 // ---------------------------------------------------------------------------------------------------------------------
 #ifndef LW_WPB
 #define LW_WPB 2  // waves per workgroup (they share nothing).  Same box, rocprofv3, 256 / 4,096 clips: 4 waves 27.96 / 353.5 us,
@@ -567,49 +628,6 @@ __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
 #define LW_WBUF (4 * 16 * TR_LD * 8)  // 8,704 B per wave: 16x16 fp64 transposes of 4 frames; before that the sample tile
 #define LW_ROWF 528                   // generic path: floats per staged frame (512 + up to 7 of shift, 16-byte multiple)
 static_assert(4 * LW_ROWF * 4 <= LW_WBUF && (WIN + 3 * 512 + 16) * 4 <= LW_WBUF && 4 * MAG_LD * 4 <= LW_WBUF, "per-wave buffer too small");
-
-// dst[q * VEC + e] = normalised (and pre-emphasised) sample ga + q * VEC + e, q < n_vec; ga is a multiple of VEC
-template <bool F32IN>
-__device__ __forceinline__ void lw_stage_generic(const logmel_args &a, float *dst, int64_t ga, int n_vec, int64_t s_begin,
-                                                 int64_t total, int lane) {
-  constexpr int VEC = F32IN ? 4 : 8;
-  const float alpha = a.preemph;
-  for (int q = lane; q < n_vec; q += 64) {
-    const int64_t g = ga + (int64_t)q * VEC;
-    float v[VEC + 1];
-    // v[0] = sample g-1 (pre-emphasis carry; 0 at the start of the utterance)
-    v[0] = (alpha != 0.0f && g - 1 >= s_begin) ? norm_sample<F32IN>(a, g - 1) : 0.0f;
-    if (g + VEC <= total) {
-      if (F32IN) {
-        const float4 raw = *(const float4 *)(a.f32 + g);
-        v[1] = raw.x; v[2] = raw.y; v[3] = raw.z; v[4] = raw.w;
-      } else {
-        const uint4 raw = *(const uint4 *)(a.pcm + g);
-        const unsigned int w32[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int16_t s16 = (int16_t)((w32[e >> 1] >> ((e & 1) * 16)) & 0xffffu);
-          float f = pcm_quot((float)s16, a);
-          if (a.clip) f = fminf(fmaxf(f, -1.0f), 1.0f);
-          v[1 + e] = f;
-        }
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) v[1 + e] = (g + e < total) ? norm_sample<F32IN>(a, g + e) : 0.0f;
-    }
-    float o[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      // reference: frame -= pre_emphasis * previous  (separate fp32 multiply and subtract); sample s_begin sees a zero carry
-      const float prev = (g + e == s_begin) ? 0.0f : v[e];
-      o[e] = (alpha != 0.0f) ? ww_preemph_rn(v[1 + e], alpha, prev) : v[1 + e];
-    }
-    float4 *d4 = (float4 *)(dst + (size_t)q * VEC);
-    d4[0] = make_float4(o[0], o[1], o[2], o[3]);
-    if (VEC == 8) d4[1] = make_float4(o[4], o[5], o[6], o[7]);
-  }
-}
 
 // The lane number, recomputed where it is needed (two instructions) instead of kept in a register across the transform:
 // volatile, so the compiler cannot merge it with an earlier copy and carry that one through the register-tight phases.
@@ -705,53 +723,12 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
       // No pre-emphasis, divisor 32767/32768, hop <= 168 (host checks): NV vectors per lane, straight-line: all loads in
       // flight together
       constexpr int NV = F32IN ? 4 : 2;
-      const idx_t last = (total - VEC) & ~(idx_t)(VEC - 1);  // last full aligned vector (total >= WIN here)
-      const idx_t tile_last = ga + (idx_t)(n_vec - 1) * VEC;
       idx_t gq[NV];
       uint4 raw[NV];
-#pragma unroll
-      for (int h = 0; h < NV; ++h) {
-        gq[h] = ga + (idx_t)(lane + 64 * h) * VEC;
-        idx_t gl = gq[h] < tile_last ? gq[h] : tile_last;  // never past this wave's last vector
-        gl = gl < last ? gl : last;
-        raw[h] = F32IN ? *(const uint4 *)(a.f32 + gl) : *(const uint4 *)(a.pcm + gl);
-      }
-      const float lim = a.clip ? 1.0f : __builtin_inff();
-#pragma unroll
-      for (int h = 0; h < NV; ++h) {
-        const int q = lane + 64 * h;
-        if (q < n_vec) {
-          float o[VEC];
-          if (gq[h] <= last) {
-            const unsigned int w32[4] = {raw[h].x, raw[h].y, raw[h].z, raw[h].w};
-            if (F32IN) {
-#pragma unroll
-              for (int e = 0; e < VEC; ++e) o[e] = __uint_as_float(w32[e]);
-            } else {
-              // the exact quotient (see pcm_quot) on sample pairs: v_pk_mul_f32 / v_pk_fma_f32, two samples per issue
-              typedef float f32x2 __attribute__((ext_vector_type(2)));
-              const f32x2 r2 = {a.rdiv, a.rdiv}, nb2 = {-a.divisor, -a.divisor};
-#pragma unroll
-              for (int e = 0; e < VEC; e += 2) {
-                const f32x2 x = {(float)(int)(short)(w32[e >> 1] & 0xffffu), (float)((int)w32[e >> 1] >> 16)};
-                const f32x2 q0 = x * r2;
-                const f32x2 er = __builtin_elementwise_fma(nb2, q0, x);
-                const f32x2 qq = __builtin_elementwise_fma(er, r2, q0);
-                o[e] = __builtin_amdgcn_fmed3f(qq.x, -lim, lim);
-                o[e + 1] = __builtin_amdgcn_fmed3f(qq.y, -lim, lim);
-              }
-            }
-          } else {  // ragged end of the whole buffer: element-wise, zero beyond it
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) o[e] = (gq[h] + e < total) ? norm_sample<F32IN>(a, (int64_t)gq[h] + e) : 0.0f;
-          }
-          float4 *d4 = (float4 *)(tile + (size_t)q * VEC);
-          d4[0] = make_float4(o[0], o[1], o[2], o[3]);
-          if (VEC == 8) d4[1] = make_float4(o[4], o[5], o[6], o[7]);
-        }
-      }
+      LM_STAGE_SIMPLE_LOAD(F32IN, NV, 64, idx_t, a, ga, n_vec, total, lane, gq, raw);
+      LM_STAGE_SIMPLE_STORE(F32IN, NV, 64, idx_t, a, tile, n_vec, total, lane, gq, raw);
     } else {
-      lw_stage_generic<F32IN>(a, tile, (int64_t)ga, n_vec, (int64_t)s0, (int64_t)total, lane);
+      stage_generic_wave<F32IN>(a, tile, (int64_t)ga, n_vec, (int64_t)s0, (int64_t)total, lane);
     }
     src = tile + shift + (int)(b - b0);
   } else {
@@ -760,7 +737,7 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
       if (!((vm >> (16 * r)) & 1)) continue;
       const int64_t br = lw_readlane64(b, 16 * r), sr = lw_readlane64(s_begin, 16 * r);
       const int sh = (int)(br % VEC);
-      lw_stage_generic<F32IN>(a, tile + r * LW_ROWF, br - sh, (sh + WIN + VEC - 1) / VEC, sr, (int64_t)total, lane);
+      stage_generic_wave<F32IN>(a, tile + r * LW_ROWF, br - sh, (sh + WIN + VEC - 1) / VEC, sr, (int64_t)total, lane);
     }
     src = tile + (rv ? sub : r_first) * LW_ROWF + (int)(b % VEC);
   }
@@ -777,15 +754,10 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
     // n = 16 n1 + j, from the half table of 128 pairs (h[m] = h[511 - m]) through the vector L1, four n1 at a time and one
     // chunk ahead: 16 + 16 registers instead of the 64 of the whole set
     const double2 *hb = (const double2 *)a.hann;
-    auto hload = [&](int n1) -> double2 {
-      if (n1 < 8) return hb[16 * n1 + j];
-      const double2 m = hb[16 * (15 - n1) + 15 - j];
-      return make_double2(m.y, m.x);
-    };
     constexpr int HC = LW_HC, NHC = 16 / HC;  // Hann pairs per chunk; one chunk in flight ahead of the one being used
     double2 h[2][HC];
 #pragma unroll
-    for (int i = 0; i < HC; ++i) h[0][i] = hload(i);
+    for (int i = 0; i < HC; ++i) h[0][i] = hann_pair(hb, i, j);
     const bool pairs = __all((((int)(src - tile)) & 1) == 0);
     if (pairs) {
       // 8-byte aligned pairs: ds_read_b64 (with hop = 160 the four frames of a wave sit 32 banks apart: conflict-free)
@@ -795,16 +767,12 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
       for (int c = 0; c < NHC; ++c) {
         if (c + 1 < NHC) {
 #pragma unroll
-          for (int i = 0; i < HC; ++i) h[(c + 1) & 1][i] = hload(HC * (c + 1) + i);
+          for (int i = 0; i < HC; ++i) h[(c + 1) & 1][i] = hann_pair(hb, HC * (c + 1) + i, j);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (c == 0) lds_wait_all(xs);
 #pragma unroll
-        for (int i = 0; i < HC; ++i) {
-          const int n1 = HC * c + i;
-          v[n1].re = (R)__int_as_float(__double2loint(xs[n1])) * h[c & 1][i].x;
-          v[n1].im = (R)__int_as_float(__double2hiint(xs[n1])) * h[c & 1][i].y;
-        }
+        for (int i = 0; i < HC; ++i) v[HC * c + i] = hann_mul_pair<R>(xs[HC * c + i], h[c & 1][i]);
         __builtin_amdgcn_sched_barrier(0);
       }
     } else {
@@ -812,14 +780,10 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
       for (int c = 0; c < NHC; ++c) {
         if (c + 1 < NHC) {
 #pragma unroll
-          for (int i = 0; i < HC; ++i) h[(c + 1) & 1][i] = hload(HC * (c + 1) + i);
+          for (int i = 0; i < HC; ++i) h[(c + 1) & 1][i] = hann_pair(hb, HC * (c + 1) + i, j);
         }
 #pragma unroll
-        for (int i = 0; i < HC; ++i) {
-          const int n = 16 * (HC * c + i) + j;
-          v[HC * c + i].re = (R)src[2 * n] * h[c & 1][i].x;
-          v[HC * c + i].im = (R)src[2 * n + 1] * h[c & 1][i].y;
-        }
+        for (int i = 0; i < HC; ++i) v[HC * c + i] = hann_mul_at<R>(src, 16 * (HC * c + i) + j, h[c & 1][i]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -870,31 +834,14 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
     }
     // pass 2: lane j = k1 holds Y[n2][k1]; output w[pos] = Z[k1 + 16 k_of(pos)]
     dft16<R>(w);
-    // untangle (see logmel_kernel): partners Z[256 - k] travel through the dead transpose buffer
+    // untangle: the partners Z[256 - k] arrive through the (dead) transpose buffer, W512^k from the L1-resident table two k2 at a
+    // time and one chunk ahead
     const double2 *unp = (const double2 *)a.tw512 + j;  // W512^(j + 16 k2) at [16 k2]
     double2 uq[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) uq[0][i] = unp[16 * i];
-    const int pj = (16 - j) & 15;
-    const R *prow0 = trs + (j == 0 ? 7 : 15) * TR_LD + pj;
-    const R *prow = trs + (j == 0 ? 16 : 15) * TR_LD + pj;
     cplx<R> pz[8];
-    trs[7 * TR_LD + j] = w[pos_of(0)].re;
-#pragma unroll
-    for (int r = 8; r < 16; ++r) trs[r * TR_LD + j] = w[pos_of(r)].re;
-    lds_fence();
-    pz[0].re = prow0[0];
-#pragma unroll
-    for (int k2 = 1; k2 < 8; ++k2) pz[k2].re = prow[-k2 * TR_LD];
-    lds_fence();
-    trs[7 * TR_LD + j] = w[pos_of(0)].im;
-#pragma unroll
-    for (int r = 8; r < 16; ++r) trs[r * TR_LD + j] = w[pos_of(r)].im;
-    lds_fence();
-    pz[0].im = prow0[0];
-#pragma unroll
-    for (int k2 = 1; k2 < 8; ++k2) pz[k2].im = prow[-k2 * TR_LD];
-    lds_fence();
+    LM_PARTNERS(R, w, trs, j, pz);
     float *mrow = mg + sub * MAG_LD;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -906,106 +853,38 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int k2 = 2 * c + i;
-        const cplx<R> own = w[pos_of(k2)];
-        const cplx<R> un = {uq[c & 1][i].x, uq[c & 1][i].y};
-        const R er = own.re + pz[k2].re, ei = own.im - pz[k2].im;
-        const R orr = own.im + pz[k2].im, oi = pz[k2].re - own.re;
-        const R tr_ = orr * un.re - oi * un.im, ti_ = orr * un.im + oi * un.re;
-        const R pr = er + tr_, pi = ei + ti_, qr = er - tr_, qi = ei - ti_;
-        const int k = j + 16 * k2;
-        mrow[k] = __builtin_amdgcn_sqrtf((float)(pr * pr + pi * pi));  // 2|X[k]|: the mel weights carry the 0.5
-        mrow[256 - k] = __builtin_amdgcn_sqrtf((float)(qr * qr + qi * qi));  // k = 0 -> bin 256
+        LM_UNTANGLE_K2(R, w[pos_of(k2)], pz[k2], (cplx<R>{uq[c & 1][i].x, uq[c & 1][i].y}), mrow, j + 16 * k2);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    {
-      // k = 128 pairs with itself: X[128] = conj(Z[128]) (lane 0, k2 = 8); bins 257..271 are zero padding
-      const cplx<R> z = w[pos_of(8)];
-      if (j == 0) mrow[128] = 2.0f * __builtin_amdgcn_sqrtf((float)(z.re * z.re + z.im * z.im));
-      else mrow[256 + j] = 0.0f;
-    }
+    untangle_tail<R>(w[pos_of(8)], mrow, j);
   }
 
-  // ---- mel filterbank on the vector ALU (see logmel_kernel): lane 4 s + q owns frame q and slot s of each band group;
-  //      every group's weight chunks are fetched when its turn comes
+  // ---- mel filterbank and the park of the wave's 4 x n_mel tile.  Mel rows are global frame numbers: the four rows leave as
+  //      one contiguous store when all four are valid (16-byte aligned whenever n_mel is a multiple of 4: g0 is a multiple of 4)
   lds_fence();
   {
     const int lane = lw_lane();
-    const int j = lane >> 2, sub = lane & 3;  // mel phase only: (slot, frame) of this lane
-    constexpr int CAPQ[3] = {9, 4, 3}, C0[3] = {0, 9, 13};
-    const float4 *wv = (const float4 *)a.melV + j;
-    const float *mrow = mg + sub * MAG_LD;
-    __builtin_amdgcn_sched_barrier(0);
-    int meta[3];
-#pragma unroll
-    for (int g = 0; g < 3; ++g) meta[g] = a.melVmeta[g * 16 + j];
-    float4 wq[WW_MELV_CHUNKS];
-    int band[3];
-    float bias[3];
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-      band[g] = (int)((unsigned)meta[g] >> 16);  // 0xffff: empty slot
-      bias[g] = a.bias[band[g] < a.n_mel ? band[g] : 0];
-    }
-    float res[3];
-    if (a.melv_aligned) {
-#pragma unroll
-      for (int g = 0; g < 3; ++g) {
-        __builtin_amdgcn_sched_barrier(0);  // one group's magnitudes and weights in flight at a time
-#pragma unroll
-        for (int c = 0; c < CAPQ[g]; ++c) wq[C0[g] + c] = wv[(C0[g] + c) * 16];
-        lds_cfloat4 *mb = (lds_cfloat4 *)lds_opaque(mrow + (meta[g] & 0xffff));
-        float acc = 0.f, acc1 = 0.f;  // two chains: a dependent fp32 FMA does not issue back to back
-#pragma unroll
-        for (int c = 0; c < CAPQ[g]; ++c) {
-          const float4 w4 = wq[C0[g] + c];
-          const f32x4 m4 = mb[c];
-          acc = fmaf(m4[0], w4.x, acc);
-          acc1 = fmaf(m4[1], w4.y, acc1);
-          acc = fmaf(m4[2], w4.z, acc);
-          acc1 = fmaf(m4[3], w4.w, acc1);
-        }
-        acc += acc1;
-        res[g] = (logf(fmaxf(acc + bias[g], a.floor_v)) + a.log_off) * a.scale;
-      }
-    } else {
-#pragma unroll
-      for (int g = 0; g < 3; ++g) {
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int c = 0; c < CAPQ[g]; ++c) wq[C0[g] + c] = wv[(C0[g] + c) * 16];
-        lds_cfloat *mb = lds_opaque(mrow + (meta[g] & 0xffff));
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < CAPQ[g]; ++c) {
-          const float4 w4 = wq[C0[g] + c];
-          acc = fmaf(mb[4 * c + 0], w4.x, acc);
-          acc = fmaf(mb[4 * c + 1], w4.y, acc);
-          acc = fmaf(mb[4 * c + 2], w4.z, acc);
-          acc = fmaf(mb[4 * c + 3], w4.w, acc);
-        }
-        res[g] = (logf(fmaxf(acc + bias[g], a.floor_v)) + a.log_off) * a.scale;
-      }
-    }
-    // park the wave's 4 x n_mel tile in LDS (its magnitudes are dead); empty slots write to a spare word each so that
-    // the code stays straight-line.  Mel rows are global frame numbers: the four rows leave as one contiguous store
-    // when all four are valid (16-byte aligned whenever n_mel is a multiple of 4: g0 is a multiple of 4)
-    lds_fence();
-    float *mt = mg;
-#pragma unroll
-    for (int g = 0; g < 3; ++g) mt[band[g] < a.n_mel ? sub * a.n_mel + band[g] : 4 * a.n_mel + lane] = res[g];
-    lds_fence();
+    LM_MEL_TILE(a, mg, lane);
     float *dstf = a.mel + g0 * (int64_t)a.n_mel;
     const bool prefix = (vm & (vm + 1)) == 0;  // valid rows are 0 .. r_last
     if (prefix && (((uintptr_t)dstf) & 15) == 0 && (a.n_mel & 3) == 0) {
       const int nv = r_last + 1;
-      for (int i = lane; i < nv * a.n_mel / 4; i += 64) ((float4 *)dstf)[i] = ((const float4 *)mt)[i];
+      for (int i = lane; i < nv * a.n_mel / 4; i += 64) ((float4 *)dstf)[i] = ((const float4 *)mg)[i];
     } else {
       for (int i = lane; i < 4 * a.n_mel; i += 64)
-        if ((vm >> (16 * (i / a.n_mel))) & 1) dstf[i] = mt[i];
+        if ((vm >> (16 * (i / a.n_mel))) & 1) dstf[i] = mg[i];
     }
   }
 }
+
+#define STFT_MAG_LD 260  // floats per frame of magnitudes outside the log-mel kernels: 257, padded to a 16-byte multiple
+// stft_mag_kernel's dynamic LDS: per wave the FFT buffer, then the magnitudes
+template <typename R>
+struct stft_mag_lds {
+  static constexpr size_t mag = WAVES * FFT_LD * sizeof(cplx<R>);
+  static constexpr size_t bytes = mag + WAVES * STFT_MAG_LD * sizeof(float);
+};
 
 // STFT magnitude of explicit frames [n][512] -> [n][257]; one wave per frame.
 template <typename R>
@@ -1013,29 +892,17 @@ __global__ __launch_bounds__(256) void stft_mag_kernel(logmel_args a) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   cplx<R> *fbuf = (cplx<R> *)smem;
-  float *mag = (float *)(smem + WAVES * FFT_LD * sizeof(cplx<R>));
+  float *mag = (float *)(smem + stft_mag_lds<R>::mag);
   fft_consts<R> fc;
   fft_load_consts<R>(fc, lane, a.hann, a.tw256, a.tw512);
   const int64_t f = (int64_t)blockIdx.x * WAVES + wave;
   if (f >= a.n_frames_direct) return;
   const float *src = a.frames + f * WIN;
   auto x2 = [&](int n) -> float2 { return *(const float2 *)(src + 2 * n); };
-  float *mg = mag + wave * 260;
+  float *mg = mag + wave * STFT_MAG_LD;
   frame_fft_mag<R>(x2, fc, fbuf + wave * FFT_LD, mg, lane);
   float *dst = a.mag_out + f * NB;
   for (int k = lane; k < NB; k += 64) dst[k] = mg[k];
-}
-
-// logmel_kernel's LDS: Hann table, twiddle tables, three per-wave buffers, the sample tile (wave 3's buffer)
-static size_t logmel_smem(int hop) {
-  size_t off = 0;
-  off += 128 * sizeof(double2);
-  off += 2 * 256 * sizeof(cplx<float>);
-  off += (WAVES - 1) * LM_WBUF;
-  size_t tile_b = (size_t)(WIN + (FPB - 1) * hop + 16) * 4;
-  if (tile_b < (size_t)LM_WBUF) tile_b = LM_WBUF;  // wave 3's buffer moves into the tile
-  off += tile_b;
-  return (off + 15) & ~size_t(15);
 }
 
 static void fill_filter_args(logmel_args &a, const ww_model *m) {
@@ -1045,6 +912,18 @@ static void fill_filter_args(logmel_args &a, const ww_model *m) {
   a.floor_v = f.floor_v; a.log_off = f.log_off; a.scale = f.scale;
   a.hann = f.hann; a.tw256 = f.tw256; a.tw512 = f.tw512; a.tw16 = f.tw16;
   a.melV = f.melV; a.melVmeta = f.melVmeta; a.melv_aligned = f.melv_aligned;
+}
+
+// The instantiation for an input type and a staging form: straight-line staging (`simple`) when nothing exotic is asked for,
+// for logmel_rows_kernel also with 32-bit sample indices (`small_idx`, which implies `simple`)
+typedef void (*logmel_fn)(logmel_args);
+static logmel_fn logmel_instance(bool rows, bool f32in, bool simple, bool small_idx) {
+  static const logmel_fn tile[2][2] = {{logmel_kernel<false, false>, logmel_kernel<true, false>},
+                                       {logmel_kernel<false, true>, logmel_kernel<true, true>}};
+  static const logmel_fn wave[3][2] = {{logmel_rows_kernel<false, false>, logmel_rows_kernel<true, false>},
+                                       {logmel_rows_kernel<false, true>, logmel_rows_kernel<true, true>},
+                                       {logmel_rows_kernel<false, true, true>, logmel_rows_kernel<true, true, true>}};
+  return rows ? wave[simple + (simple && small_idx)][f32in] : tile[simple][f32in];
 }
 
 int ww_k_logmel(ww_ctx *ctx, const ww_model *m, const int16_t *d_pcm, const float *d_f32, const int64_t *d_sample_offs,
@@ -1060,8 +939,10 @@ int ww_k_logmel(ww_ctx *ctx, const ww_model *m, const int16_t *d_pcm, const floa
   a.mel = d_mel;
   fill_filter_args(a, m);
   const bool f32in = d_f32 != nullptr;
-  // straight-line staging (two vectors per thread) when nothing exotic is asked for
-  const bool simple = fp->pre_emphasis == 0.0f && (f32in || a.fast_div) && WIN + (FPB - 1) * fp->hop + 16 <= 512 * (f32in ? 4 : 8);
+  // straight-line staging when nothing exotic is asked for and the tile fits the kernel's vectors per thread: two for each of
+  // logmel_kernel's 256 threads, NV for each of logmel_rows_kernel's 64 lanes (hop <= 168)
+  const bool plain = fp->pre_emphasis == 0.0f && (f32in || a.fast_div);
+  const bool simple = plain && WIN + (FPB - 1) * fp->hop + 16 <= 512 * (f32in ? 4 : 8);
   if (fp->precise) {
     // fp64: waves own four consecutive global mel rows each (logmel_rows_kernel)
     a.total_frames = total_frames;
@@ -1069,7 +950,7 @@ int ww_k_logmel(ww_ctx *ctx, const ww_model *m, const int16_t *d_pcm, const floa
       a.uniform_nf = (int)max_frames_per_utt;
       a.uniform_ns = uniform_samples;
     }
-    const bool simple_w = fp->pre_emphasis == 0.0f && (f32in || a.fast_div) && fp->hop <= 168;
+    const bool simple_w = plain && fp->hop <= 168;
     // 32-bit sample indices when the caller could tell that every index of the launch fits 31 bits; with equal clips of >= 4
     // frames the row -> clip division becomes one multiply: M = ceil(2^(31 + l) / nf), l = ceil(log2 nf), is exact for
     // every row < 2^31 (M nf - 2^(31 + l) < nf <= 2^l)
@@ -1086,16 +967,7 @@ int ww_k_logmel(ww_ctx *ctx, const ww_model *m, const int16_t *d_pcm, const floa
     const dim3 grid_w((unsigned)n_wg), block_w(64 * LW_WPB);
     const size_t sm = (size_t)LW_WPB * LW_WBUF;
     ww_launch_scope scope(ctx, "logmel_rows_kernel");
-    if (small_w) {
-      if (f32in) hipLaunchKernelGGL((logmel_rows_kernel<true, true, true>), grid_w, block_w, sm, ctx->stream, a);
-      else hipLaunchKernelGGL((logmel_rows_kernel<false, true, true>), grid_w, block_w, sm, ctx->stream, a);
-    } else if (simple_w) {
-      if (f32in) hipLaunchKernelGGL((logmel_rows_kernel<true, true>), grid_w, block_w, sm, ctx->stream, a);
-      else hipLaunchKernelGGL((logmel_rows_kernel<false, true>), grid_w, block_w, sm, ctx->stream, a);
-    } else {
-      if (f32in) hipLaunchKernelGGL((logmel_rows_kernel<true, false>), grid_w, block_w, sm, ctx->stream, a);
-      else hipLaunchKernelGGL((logmel_rows_kernel<false, false>), grid_w, block_w, sm, ctx->stream, a);
-    }
+    hipLaunchKernelGGL(logmel_instance(true, f32in, simple_w, small_w), grid_w, block_w, sm, ctx->stream, a);
     WW_HIP(ctx, hipGetLastError());
     return WW_OK;
   }
@@ -1105,14 +977,7 @@ int ww_k_logmel(ww_ctx *ctx, const ww_model *m, const int16_t *d_pcm, const floa
   a.tiles_per_utt = (int)tiles;
   dim3 grid((unsigned)n_ids);
   ww_launch_scope scope(ctx, "logmel_kernel<f32>");
-  const size_t sm = logmel_smem(fp->hop);
-  if (simple) {
-    if (f32in) hipLaunchKernelGGL((logmel_kernel<true, true>), grid, dim3(256), sm, ctx->stream, a);
-    else hipLaunchKernelGGL((logmel_kernel<false, true>), grid, dim3(256), sm, ctx->stream, a);
-  } else {
-    if (f32in) hipLaunchKernelGGL((logmel_kernel<true, false>), grid, dim3(256), sm, ctx->stream, a);
-    else hipLaunchKernelGGL((logmel_kernel<false, false>), grid, dim3(256), sm, ctx->stream, a);
-  }
+  hipLaunchKernelGGL(logmel_instance(false, f32in, simple, false), grid, dim3(256), logmel_lds::bytes(fp->hop), ctx->stream, a);
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
 }
@@ -1120,7 +985,7 @@ int ww_k_logmel(ww_ctx *ctx, const ww_model *m, const int16_t *d_pcm, const floa
 // filter.tflite alone (reference filter_model(frame), wakeword/tflite.py:183-184): mag [n][257] -> mel [n][40]
 __global__ __launch_bounds__(64) void mel_only_kernel(const float *mag, int64_t n, const float *w, const float *bias, int n_mel,
                                                       int n_bins, float floor_v, float log_off, float scale, float *mel) {
-  __shared__ float m[260];
+  __shared__ float m[STFT_MAG_LD];
   const int lane = threadIdx.x;
   const int64_t f = blockIdx.x;
   for (int k = lane; k < n_bins; k += 64) m[k] = mag[f * n_bins + k];
@@ -1150,13 +1015,8 @@ int ww_k_stft_mag(ww_ctx *ctx, const ww_model *m, const float *d_frames, int64_t
   a.frames = d_frames; a.mag_out = d_mag; a.n_frames_direct = n;
   dim3 grid((unsigned)((n + WAVES - 1) / WAVES));
   ww_launch_scope scope(ctx, "stft_mag_kernel");
-  if (precise) {
-    size_t sm = WAVES * FFT_LD * sizeof(cplx<double>) + WAVES * 260 * sizeof(float);
-    hipLaunchKernelGGL((stft_mag_kernel<double>), grid, dim3(256), sm, ctx->stream, a);
-  } else {
-    size_t sm = WAVES * FFT_LD * sizeof(cplx<float>) + WAVES * 260 * sizeof(float);
-    hipLaunchKernelGGL((stft_mag_kernel<float>), grid, dim3(256), sm, ctx->stream, a);
-  }
+  if (precise) hipLaunchKernelGGL((stft_mag_kernel<double>), grid, dim3(256), stft_mag_lds<double>::bytes, ctx->stream, a);
+  else hipLaunchKernelGGL((stft_mag_kernel<float>), grid, dim3(256), stft_mag_lds<float>::bytes, ctx->stream, a);
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
 }
