@@ -97,7 +97,8 @@ __device__ __forceinline__ void stage_loads(bool al16, F &&body) {
 // ------------------------------------------------------------------------------------------
 #define CV_ROWS 44   // mel index + PF, 0..43
 #define CV_LDT 164   // time index + PT, 0..163 (multiple of 4; 164 % 32 == 4)
-#define CV_KB 7      // K = 5*20 = 100 padded to 112 = 7 * 16
+#define CV_KB 6      // K = 5*20 = 100 = 6 k-blocks of 16 and one last quad (k = 96..99): 25 MFMA k-steps, none on padding
+#define CV_QL 24     // the last quad
 #define CV_THREADS 512
 // Geometry of every CRNN the reference ships (wwdetect/CRNN/train.py:27-49; checked against the
 // blob at model load): compile-time constants turn the index divisions into shifts/multiplies.
@@ -335,44 +336,61 @@ __device__ __forceinline__ void wsync_g() {
 
 // ------------------------------------------------------------------------------------------
 // The fp32 conv as crnn_fused_kernel, crnn_stream_kernel and crnn_rows_kernel run it: an implicit GEMM on v_mfma_f32_16x16x4_f32,
-// m-tiles of 16 (position, frequency) rows x 32 channels, K = 100 taps padded to 7 k-blocks of 16.  One definition of each piece;
+// m-tiles of 16 (position, frequency) rows x 32 channels, K = 100 taps = 6 k-blocks of 16 and one quad.  One definition of each piece;
 // lane (j, kk) = (lane & 15, lane >> 4) are names of the kernel.  The loads are macros, not functions: as __forceinline__
 // functions that take the pointer as a parameter they lost their scalar base (global_load_dwordx4 v, v, s[2:3] became
 // v_lshl_add_u64 + a load from a 64-bit vector address: profiles/EXPERIMENTS.md 13).
 // ------------------------------------------------------------------------------------------
-// this lane's conv weights (B operand: [112/4][32][4]) and the biases of its two channels
-#define CV_LOAD_W(wreg_, cb0_, cb1_, w4_, cbias_)                                                    \
+// this lane's conv weights (B operand: [112/4][32][4]; the last quad's k = 96 + kk is element kk of it) and the biases of its
+// two channels
+#define CV_LOAD_W(wreg_, wlast_, cb0_, cb1_, w4_, cbias_)                                            \
   _Pragma("unroll") for (int kb = 0; kb < CV_KB; ++kb)                                               \
     _Pragma("unroll") for (int n = 0; n < 2; ++n)                                                    \
       wreg_[kb][n] = *(const float4 *)((w4_) + ((size_t)(kb * 4 + kk) * 32 + n * 16 + j) * 4);       \
+  _Pragma("unroll") for (int n = 0; n < 2; ++n)                                                      \
+    wlast_[n] = (w4_)[((size_t)CV_QL * 32 + n * 16 + j) * 4 + kk];                                   \
   cb0_ = (cbias_)[j];                                                                                \
   cb1_ = (cbias_)[16 + j];
-// the A operands of one m-tile: abase_ = this lane's row (position, frequency) in the transposed image
+// the A operands of one m-tile: abase_ = this lane's row (position, frequency) in the transposed image.  Six k-blocks as
+// 16-byte reads (lane group kk: quad 4 kb + kk) and the last quad one float per lane group
+struct cv_a {
+  float4 q[CV_KB];
+  float last;
+};
 #define CV_LOAD_A(av_, abase_)                                                                       \
   _Pragma("unroll") for (int kb = 0; kb < CV_KB; ++kb) {                                             \
     const int k4 = kb * 16 + kk * 4;                                                                 \
     const int kf = k4 / CV_KT, kt = k4 - kf * CV_KT;                                                 \
-    av_[kb] = *(const float4 *)((abase_) + kf * CV_LDT + kt);                                        \
-  }
+    av_.q[kb] = *(const float4 *)((abase_) + kf * CV_LDT + kt);                                      \
+  }                                                                                                  \
+  av_.last = (abase_)[(CV_QL * 4 / CV_KT) * CV_LDT + CV_QL * 4 % CV_KT + kk];
 // one k-block: 16 taps x 32 channels onto acc0 (channels 0..15) and acc1 (16..31)
 #define CV_MFMA_KB(av_, kb_)                                                                         \
-  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].x, wreg[kb_][0].x, acc0, 0, 0, 0);             \
-  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].x, wreg[kb_][1].x, acc1, 0, 0, 0);             \
-  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].y, wreg[kb_][0].y, acc0, 0, 0, 0);             \
-  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].y, wreg[kb_][1].y, acc1, 0, 0, 0);             \
-  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].z, wreg[kb_][0].z, acc0, 0, 0, 0);             \
-  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].z, wreg[kb_][1].z, acc1, 0, 0, 0);             \
-  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].w, wreg[kb_][0].w, acc0, 0, 0, 0);             \
-  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[kb_].w, wreg[kb_][1].w, acc1, 0, 0, 0);
+  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.q[kb_].x, wreg[kb_][0].x, acc0, 0, 0, 0);           \
+  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.q[kb_].x, wreg[kb_][1].x, acc1, 0, 0, 0);           \
+  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.q[kb_].y, wreg[kb_][0].y, acc0, 0, 0, 0);           \
+  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.q[kb_].y, wreg[kb_][1].y, acc1, 0, 0, 0);           \
+  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.q[kb_].z, wreg[kb_][0].z, acc0, 0, 0, 0);           \
+  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.q[kb_].z, wreg[kb_][1].z, acc1, 0, 0, 0);           \
+  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.q[kb_].w, wreg[kb_][0].w, acc0, 0, 0, 0);           \
+  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.q[kb_].w, wreg[kb_][1].w, acc1, 0, 0, 0);
+// the last quad: the k-lanes carry k = 96, 97, 98, 99.  The instruction adds its four products to the accumulator as an fmaf
+// chain in k-lane order, which is the order four instructions on the elements of a 16-byte operand - one
+// live k-lane each, three on the zero padding of K = 112 - added them in: the same bits for every finite input (the padding's
+// zero products are gone with it: they could only turn an accumulator of -0 into +0, which needs a bias of -0, or make a NaN out
+// of a non-finite mel value one row further down the image)
+#define CV_MFMA_LAST(av_)                                                                            \
+  acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.last, wlast[0], acc0, 0, 0, 0);                     \
+  acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av_.last, wlast[1], acc1, 0, 0, 0);
 // NT_ m-tiles per wave, software-pipelined by hand: the next tile's A operands are read while this tile's MFMAs run, and what
 // the caller does with the previous tile's sums prev0 / prev1 (the statements after NT_: ReLU + store, or keep them) sits in the
 // middle of them.  Vector instructions between fp32 MFMAs cost matrix time, so the loop holds none it can avoid: operand and
 // store offsets are the caller's, computed during the staging, the bias is the accumulators' initial value.  The caller has
-// load_a(av, i), wreg, cb0, cb1 and f32x4 prev0, prev1, which are the last tile's sums afterwards.  (As a function template
+// load_a(av, i), wreg, wlast, cb0, cb1 and f32x4 prev0, prev1, which are the last tile's sums afterwards.  (As a function template
 // with the middle as a callable, crnn_rows_kernel kept its instructions and crnn_fused_kernel did not: EXPERIMENTS 13.)
 #define CV_TILE_LOOP(NT_, ...)                                                                       \
   {                                                                                                  \
-    float4 av[2][CV_KB];                                                                             \
+    cv_a av[2];                                                                                      \
     load_a(av[0], 0);                                                                                \
     _Pragma("unroll") for (int i = 0; i < NT_; ++i) {                                                \
       if (i + 1 < NT_) load_a(av[(i + 1) & 1], i + 1);                                               \
@@ -382,7 +400,7 @@ __device__ __forceinline__ void wsync_g() {
       __builtin_amdgcn_sched_barrier(0);                                                             \
       __VA_ARGS__                                                                                    \
       __builtin_amdgcn_sched_barrier(0);                                                             \
-      CV_MFMA_KB(av[i & 1], 3) CV_MFMA_KB(av[i & 1], 4) CV_MFMA_KB(av[i & 1], 5) CV_MFMA_KB(av[i & 1], 6) \
+      CV_MFMA_KB(av[i & 1], 3) CV_MFMA_KB(av[i & 1], 4) CV_MFMA_KB(av[i & 1], 5) CV_MFMA_LAST(av[i & 1]) \
       prev0 = acc0;                                                                                  \
       prev1 = acc1;                                                                                  \
     }                                                                                                \
@@ -693,8 +711,8 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a)
 
   // conv weights for this lane (B operand of mfma 16x16x4: lane (j, kk)); issued first, used after the staging
   float4 wreg[CV_KB][2];
-  float cb0, cb1;
-  CV_LOAD_W(wreg, cb0, cb1, a.w4, a.cbias)
+  float wlast[2], cb0, cb1;
+  CV_LOAD_W(wreg, wlast, cb0, cb1, a.w4, a.cbias)
 
   // ---- A: stage the window (loads first, then zero the image, then the transposed scatter)
   int a_off[6], o_off[6][4];
@@ -757,7 +775,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a)
   float4 bq[4][3];
   // ---- B: conv -> feat (LDS).  Six m-tiles per wave (CV_TILE_LOOP), operand and store offsets from the staging (a_off, o_off)
   {
-    auto load_a = [&](float4(&av)[CV_KB], int i) { CV_LOAD_A(av, img + a_off[i]) };
+    auto load_a = [&](cv_a &av, int i) { CV_LOAD_A(av, img + a_off[i]) };
     auto store_tile = [&](int i, const f32x4 &r0, const f32x4 &r1) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -885,12 +903,12 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
   const int j = lane & 15, kk = lane >> 4;
   const int w = blockIdx.x;
   float4 wreg[CV_KB][2];
-  float cb0, cb1;
+  float wlast[2], cb0, cb1;
   float4 crow0, crow1, crow2;
   int a_off, o_off[4];
   int q0;
   float *cache;
-  auto load_conv_w = [&]() { CV_LOAD_W(wreg, cb0, cb1, a.w4, a.cbias) };
+  auto load_conv_w = [&]() { CV_LOAD_W(wreg, wlast, cb0, cb1, a.w4, a.cbias) };
   // ---- the sixteen cached rows (positions 1..16): requested first, parked in LDS once the image is dead
   // (three named registers: as an array they stayed in scratch memory)
   auto cached = [&](int q) {
@@ -1036,11 +1054,12 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
   __syncthreads();
   // ---- B: conv of the 60 rows -> feat[p][f * 32 + channel]
   {
-    float4 av[CV_KB];
+    cv_a av;
     CV_LOAD_A(av, img + a_off)
     f32x4 acc0 = {cb0, cb0, cb0, cb0}, acc1 = {cb1, cb1, cb1, cb1};
 #pragma unroll
     for (int kb = 0; kb < CV_KB; ++kb) { CV_MFMA_KB(av, kb) }
+    CV_MFMA_LAST(av)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if (o_off[r] >= 0) {
@@ -1142,8 +1161,8 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
   const float *w4 = a.w4[kind];
 
   float4 wreg[CV_KB][2];
-  float cb0, cb1;
-  CV_LOAD_W(wreg, cb0, cb1, w4, a.cbias)
+  float wlast[2], cb0, cb1;
+  CV_LOAD_W(wreg, wlast, cb0, cb1, w4, a.cbias)
 
   // ---- stage the union of the 16 fields: image[(mel + PF)][row - field0]
   int a_off[5], o_off[5][4];
@@ -1187,7 +1206,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
   __syncthreads();
   // ---- conv: five m-tiles per wave (CV_TILE_LOOP)
   {
-    auto load_a = [&](float4(&av)[CV_KB], int i) { CV_LOAD_A(av, img + a_off[i]) };
+    auto load_a = [&](cv_a &av, int i) { CV_LOAD_A(av, img + a_off[i]) };
     auto store_tile = [&](int i, const f32x4 &r0, const f32x4 &r1) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -1857,6 +1876,7 @@ __global__ __launch_bounds__(128, 2) void gru_tail16_kernel(tail16_args aa) {
 #undef PJ_NO_ROWS
 #undef CV_TILE_LOOP
 #undef CV_MFMA_KB
+#undef CV_MFMA_LAST
 #undef GT16_PRE_ALL
 #undef GT16_PRE_FIRST
 #undef GT16_POS
