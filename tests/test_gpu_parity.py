@@ -204,6 +204,36 @@ def test_forward_vs_oracle_batch(engines, oracles, name):
     assert np.abs(got - want).max() < TOL_POST
 
 
+@pytest.mark.parametrize("name", ["CRNN", "Wavenet"])
+def test_refused_load_then_load_free_and_reload_on_one_context(assets, engines, oracles, name):
+    """ww_model_load packs on the host and uploads ONE device block.  On one context: a blob cut to half its length is refused
+    (WW_EBLOB: ValueError) and hands out no model; the whole blob then loads and three windows agree with the oracle in fp32 and
+    in bf16x3 (smoke()'s 1e-4); after ww_model_free the same load and run once more: a refused load leaves nothing behind, and the
+    single block is freed and allocated again."""
+    import ctypes as C
+    from wwhip import _lib
+    from wwhip.engine import Engine
+    ctx, lib = _lib.Context(0), _lib.load()
+    blob = engines[name].blob
+    half = np.frombuffer(blob[:len(blob) // 2], np.uint8)
+    h = C.c_void_p()
+    with pytest.raises(ValueError, match="blob section"):
+        _lib.raise_for(lib.ww_model_load(ctx.handle, _lib.ptr(half), half.size, C.byref(h)), ctx.handle)
+    assert not h.value
+    wins = np.random.default_rng(23).uniform(0, 6.5, (3, engines[name].window, 40)).astype(np.float32)
+    want = oracles[name].forward(wins)
+    for _ in range(2):
+        e = Engine(os.path.join(assets, name), ctx=ctx)
+        for precision in ("fp32", "bf16x3"):
+            e.set_precision(precision)
+            got = e.forward(wins)
+            err = float(np.abs(got - want).max())
+            print(f"{name} {precision}: max|gpu - oracle| = {err:.3e}")
+            assert got.shape == want.shape and err < 1e-4, (precision, err)
+        e.close()
+    ctx.close()
+
+
 @pytest.mark.parametrize("name", ["CRNN", "Wavenet", "CRNN_old"])
 def test_slide_forward_vs_oracle(engines, oracles, name):
     rng = np.random.default_rng(22)
@@ -708,7 +738,7 @@ def _engine_with_filter(assets, monkeypatch, weight):
 
 
 def test_logmel_with_other_filterbanks(assets, monkeypatch):
-    """The lane form of the mel filter (api.hip load_filter) on filterbanks other than the shipped one: a bank
+    """The lane form of the mel filter (model_pack.h pack_filter) on filterbanks other than the shipped one: a bank
     whose widest band cannot be moved to a 16-byte boundary (scalar-read path), bands without any weight, bands of
     one tap, bands at the very top of the spectrum - and a band wider than the form takes (load error)."""
     from oracle.cpu import CpuOracle

@@ -1,6 +1,6 @@
 // C ABI of libwwhip.so: context, model upload, host/device entry points (see include/wwhip.h).
 #include "common.h"
-
+#include "model_pack.h"
 
 #include <algorithm>
 #include <cmath>
@@ -260,485 +260,26 @@ int ww_timer_stop(ww_ctx *ctx, float *ms) {
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------
-// blob parsing + upload
+// model load: parsed and packed on the host (model_pack.h), then one device block, one copy
 // ------------------------------------------------------------------------------------------
-struct blob_view {
-  const uint8_t *base;
-  size_t len;
-  uint32_t n, kind;
-  const void *find(const char *name, uint32_t *count) const {
-    for (uint32_t i = 0; i < n; ++i) {
-      const uint8_t *e = base + 16 + 32 * (size_t)i;
-      if (strncmp((const char *)e, name, 24) == 0) {
-        uint32_t off, cnt;
-        memcpy(&off, e + 24, 4);
-        memcpy(&cnt, e + 28, 4);
-        if ((size_t)off + (size_t)cnt * 4 > len) return nullptr;
-        if (count) *count = cnt;
-        return base + off;
-      }
-    }
-    return nullptr;
-  }
+// Where the device address of each packed array goes: the packer's name of an array is "<struct>.<member>" of ww_model.
+struct model_slot {
+  const char *name;
+  void (*set)(ww_model &, void *);
 };
-
-template <typename T>
-static T *upload(ww_model *m, const std::vector<T> &v) {
-  void *d = nullptr;
-  size_t bytes = (v.size() ? v.size() : 1) * sizeof(T);
-  if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
-  m->allocs.push_back(d);
-  if (v.size() && hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-  return (T *)d;
-}
-
-#define NEED_F(var, name, cnt_expect)                                                                       \
-  uint32_t var##_n = 0;                                                                                     \
-  const float *var = (const float *)bv.find(name, &var##_n);                                                \
-  if (!var || (size_t)var##_n != (size_t)(cnt_expect))                                                      \
-    return ww_fail(ctx, WW_EBLOB, "blob section %s missing or has %u elements (expected %zu)", name, var##_n, \
-                   (size_t)(cnt_expect));
-
-static int load_filter(ww_ctx *ctx, ww_model *m, const blob_view &bv) {
-  uint32_t cnt = 0;
-  const int32_t *meta = (const int32_t *)bv.find("filter.meta", &cnt);
-  if (!meta || cnt != 2) return ww_fail(ctx, WW_EBLOB, "blob lacks filter.meta");
-  const int n_mel = meta[0], n_bins = meta[1];
-  if (n_mel < 1 || n_mel > 40 || n_bins != WW_FFT_BINS)
-    return ww_fail(ctx, WW_EBLOB, "unsupported filter geometry %d x %d (need <= 40 x 257)", n_mel, n_bins);
-  NEED_F(cst, "filter.consts", 3);
-  NEED_F(w, "filter.w", (size_t)n_mel * n_bins);
-  NEED_F(b, "filter.b", n_mel);
-  ww_filter_dev &f = m->filt;
-  f.n_mel = n_mel; f.n_bins = n_bins; f.floor_v = cst[0]; f.log_off = cst[1]; f.scale = cst[2];
-  std::vector<int> start(n_mel), len(n_mel), woff(n_mel);
-  std::vector<float> taps;
-  for (int i = 0; i < n_mel; ++i) {
-    int lo = -1, hi = -1;
-    for (int k = 0; k < n_bins; ++k)
-      if (w[(size_t)i * n_bins + k] != 0.0f) {
-        if (lo < 0) lo = k;
-        hi = k;
-      }
-    start[i] = lo < 0 ? 0 : lo;
-    len[i] = lo < 0 ? 0 : hi - lo + 1;
-    woff[i] = (int)taps.size();
-    for (int k = 0; k < len[i]; ++k) taps.push_back(w[(size_t)i * n_bins + start[i] + k]);
-    if (len[i] > f.max_len) f.max_len = len[i];
-  }
-  f.total_taps = (int)taps.size();
-  const int MEL_TAPS = 36;  // WW_MEL_TAPS in fft_device.h
-  if (f.max_len > MEL_TAPS)
-    return ww_fail(ctx, WW_EBLOB, "mel band of %d taps exceeds the kernel limit of %d", f.max_len, MEL_TAPS);
-  std::vector<float> wpad((size_t)MEL_TAPS * 64, 0.f);
-  for (int i = 0; i < n_mel; ++i)
-    for (int k = 0; k < len[i]; ++k) wpad[(size_t)k * 64 + i] = taps[woff[i] + k];
-  std::vector<float> bias(b, b + n_mel);
-  std::vector<double> hann(WW_FFT_WINDOW), tw256(512), tw512(512);
-  // np.hanning(M) as NumPy evaluates it: 0.5 + 0.5 cos(pi n / (M-1)), n = 1-M, 3-M, ..., M-1 (exactly symmetric)
-  for (int n = 0; n < WW_FFT_WINDOW; ++n)
-    hann[n] = 0.5 + 0.5 * cos(M_PI * (double)(2 * n - (WW_FFT_WINDOW - 1)) / (double)(WW_FFT_WINDOW - 1));
-  for (int k = 0; k < 256; ++k) {
-    tw256[2 * k] = cos(-2.0 * M_PI * k / 256.0);
-    tw256[2 * k + 1] = sin(-2.0 * M_PI * k / 256.0);
-    tw512[2 * k] = cos(-2.0 * M_PI * k / 512.0);
-    tw512[2 * k + 1] = sin(-2.0 * M_PI * k / 512.0);
-  }
-  std::vector<double> tw16(512);
-  for (int k1 = 0; k1 < 16; ++k1)
-    for (int jj = 0; jj < 16; ++jj) {
-      tw16[2 * (k1 * 16 + jj)] = cos(-2.0 * M_PI * (double)(jj * k1) / 256.0);
-      tw16[2 * (k1 * 16 + jj) + 1] = sin(-2.0 * M_PI * (double)(jj * k1) / 256.0);
-    }
-  f.tw16 = upload(m, tw16);
-  // mel filter in lane form (frontend.hip, logmel_kernel): bands sorted by width, widest first, dealt to
-  // groups of 16 slots with 36 / 16 / 12 padded taps.  Weights carry the 0.5 of the real-FFT untangling
-  // (exact), and a band's first bin is pulled back so that its padded taps stay inside the zero-padded
-  // row of 272 magnitudes.
-  {
-    static const int cap[3] = {36, 16, 12}, chunk0[3] = {0, 9, 13};
-    if (n_mel > 48) return ww_fail(ctx, WW_EBLOB, "mel filterbank has %d bands; the lane form holds 48", n_mel);
-    std::vector<int> order(n_mel);
-    for (int i = 0; i < n_mel; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return len[x] > len[y]; });
-    // First bins are rounded down to a multiple of 4 when every band still fits its group's taps: the kernel
-    // then reads the magnitudes 16 bytes at a time.  A ds_read_b128 is served in four groups of 16 lanes
-    // ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same + 32); with lane = 4 slot + frame those hold the
-    // slots {0,3,5,6}, {1,2,4,7}, {8,11,13,14}, {9,10,12,15}, and the four frames' rows lie 4 sixteen-byte bank
-    // slots apart.  So the four bands of such a quad should start on different bank slots mod 4: where the
-    // taps leave room a band's first bin is pulled back further to get there.
-    static const int quad[4][4] = {{0, 3, 5, 6}, {1, 2, 4, 7}, {8, 11, 13, 14}, {9, 10, 12, 15}};
-    bool aligned = true;
-    for (int r = 0; r < n_mel; ++r) {
-      const int g = r / 16, band = order[r];
-      if (len[band] > cap[g])
-        return ww_fail(ctx, WW_EBLOB, "mel band %d spans %d bins; the lane form takes %d for the %d widest, %d for the next 16, %d for the rest",
-                       band, len[band], cap[0], 16, cap[1], cap[2]);
-      int s0 = start[band] < 272 - cap[g] ? start[band] : 272 - cap[g];
-      if (start[band] - (s0 & ~3) + len[band] > cap[g]) aligned = false;
-    }
-    std::vector<float> melV((size_t)WW_MELV_CHUNKS * 16 * 4, 0.f);
-    std::vector<int> meta(3 * 16, 0xffff << 16);
-    for (int g = 0; g < 3; ++g) {
-      const int nb = n_mel - 16 * g < 0 ? 0 : (n_mel - 16 * g > 16 ? 16 : n_mel - 16 * g);
-      int s0v[16], slotv[16], cls_n[4] = {0, 0, 0, 0};
-      // least flexible bands choose their residue class first
-      std::vector<int> idx(nb);
-      for (int i = 0; i < nb; ++i) idx[i] = i;
-      auto room = [&](int i) {  // how many steps of 4 bins band i can be pulled back beyond the plain rounding
-        const int band = order[16 * g + i];
-        int s0 = start[band] < 272 - cap[g] ? start[band] : 272 - cap[g];
-        if (!aligned) return 0;
-        s0 &= ~3;
-        int n = 0;
-        while (s0 - 4 * (n + 1) >= 0 && start[band] - (s0 - 4 * (n + 1)) + len[band] <= cap[g]) ++n;
-        return n;
-      };
-      std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return room(x) < room(y); });
-      for (int i : idx) {
-        const int band = order[16 * g + i];
-        int s0 = start[band] < 272 - cap[g] ? start[band] : 272 - cap[g];
-        if (aligned) s0 &= ~3;
-        int best = 0, best_n = 1 << 30;
-        for (int n = 0; n <= room(i) && n < 4; ++n) {
-          const int cls = ((s0 - 4 * n) / 4) & 3;
-          if (cls_n[cls] < best_n) { best_n = cls_n[cls]; best = n; }
-        }
-        s0 -= 4 * best;
-        s0v[i] = s0;
-        const int cls = (s0 / 4) & 3;
-        // class member number q goes to quad q (a fifth member of a class takes any free slot below)
-        slotv[i] = cls_n[cls] < 4 ? quad[cls_n[cls]][cls] : -1;
-        ++cls_n[cls];
-      }
-      bool used[16] = {false};
-      for (int i = 0; i < nb; ++i)
-        if (slotv[i] >= 0) {
-          if (used[slotv[i]]) slotv[i] = -1; else used[slotv[i]] = true;
-        }
-      for (int i = 0; i < nb; ++i)
-        if (slotv[i] < 0)
-          for (int sl = 0; sl < 16; ++sl)
-            if (!used[sl]) { slotv[i] = sl; used[sl] = true; break; }
-      for (int i = 0; i < nb; ++i) {
-        const int band = order[16 * g + i], slot = slotv[i], s0 = s0v[i];
-        for (int k = 0; k < len[band]; ++k) {
-          const int t = start[band] - s0 + k;
-          melV[((size_t)(chunk0[g] + t / 4) * 16 + slot) * 4 + t % 4] = 0.5f * w[(size_t)band * n_bins + start[band] + k];
-        }
-        meta[g * 16 + slot] = s0 | (band << 16);
-      }
-      // empty slots read (zero-weighted) magnitudes too: park each on the bank slot its quad still lacks
-      for (int q = 0; q < 4; ++q) {
-        bool have[4] = {false, false, false, false};
-        for (int c = 0; c < 4; ++c)
-          if (used[quad[q][c]]) have[((meta[g * 16 + quad[q][c]] & 0xffff) / 4) & 3] = true;
-        for (int c = 0; c < 4; ++c)
-          if (!used[quad[q][c]])
-            for (int cls = 0; cls < 4; ++cls)
-              if (!have[cls]) { have[cls] = true; meta[g * 16 + quad[q][c]] = (4 * cls) | (0xffff << 16); break; }
-      }
-    }
-    f.melv_aligned = aligned ? 1 : 0;
-    f.melV = upload(m, melV);
-    f.melVmeta = upload(m, meta);
-  }
-  f.start = upload(m, start); f.len = upload(m, len); f.woff = upload(m, woff);
-  f.w = upload(m, taps); f.bias = upload(m, bias); f.wpad = upload(m, wpad);
-  f.wdense = upload(m, std::vector<float>(w, w + (size_t)n_mel * n_bins));
-  f.hann = upload(m, hann); f.tw256 = upload(m, tw256); f.tw512 = upload(m, tw512);
-  if (!f.wdense || !f.tw16 || !f.melV || !f.melVmeta || !f.start || !f.len || !f.woff || !f.w || !f.bias || !f.wpad || !f.hann || !f.tw256 || !f.tw512)
-    return ww_fail(ctx, WW_ENOMEM, "filter upload failed");
-  return WW_OK;
-}
-
-// split-bf16 mode (WW_PRECISION_BF16X3): x = hi + lo, both bf16 round-to-nearest-even
-static uint16_t bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-static float bf16_f(uint16_t h) {
-  uint32_t u = (uint32_t)h << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-static void bf16_split(float x, uint16_t &hi, uint16_t &lo) {
-  hi = bf16_rne(x);
-  lo = bf16_rne(x - bf16_f(hi));
-}
-
-// a row-major [n_rows][k] matrix in MFMA B-operand order [k/4][n_rows][4]
-static std::vector<float> pack_k4(const std::vector<float> &src, size_t n_rows, size_t k) {
-  std::vector<float> dst(src.size());
-  for (size_t n = 0; n < n_rows; ++n)
-    for (size_t kk = 0; kk < k; ++kk) dst[((kk / 4) * n_rows + n) * 4 + (kk % 4)] = src[n * k + kk];
-  return dst;
-}
-
-static int load_crnn(ww_ctx *ctx, ww_model *m, const blob_view &bv) {
-  uint32_t cnt = 0;
-  const int32_t *meta = (const int32_t *)bv.find("crnn.meta", &cnt);
-  if (!meta || cnt != 14) return ww_fail(ctx, WW_EBLOB, "blob lacks crnn.meta");
-  ww_crnn_dev &c = m->crnn;
-  c.n_mel = meta[0]; c.T = meta[1]; c.C = meta[2]; c.KF = meta[3]; c.KT = meta[4]; c.SF = meta[5]; c.ST = meta[6];
-  c.PF = meta[7]; c.PT = meta[8]; c.OF = meta[9]; c.OT = meta[10]; c.H = meta[11]; c.NOUT = meta[12]; c.HEAD = meta[13];
-  const int K = c.KF * c.KT, KP = 112;
-  if (c.H != 32 || c.C < 1 || c.C > 64 || c.NOUT < 1 || c.NOUT > 8 || c.OT < 1 || c.OF < 1 || K < 1 || c.n_mel != m->filt.n_mel ||
-      c.T * c.n_mel > 16384)
-    return ww_fail(ctx, WW_EBLOB, "unsupported CRNN geometry (C=%d H=%d K=%dx%d stride %dx%d)", c.C, c.H, c.KF, c.KT, c.SF, c.ST);
-  // the geometry of wwdetect/CRNN/train.py:27-49 (every current export) runs on the kernels built for it
-  c.generic = !(c.C == 32 && c.n_mel == 40 && c.T == 151 && c.KF == 5 && c.KT == 20 && c.SF == 2 && c.ST == 8 && c.PF == 1 &&
-                c.PT == 6 && c.OF == 20 && c.OT == 19);
-  c.FEATP = (c.OF * c.C + 63) / 64 * 64;
-  NEED_F(cw, "crnn.conv_w", (size_t)c.C * K);
-  NEED_F(cb, "crnn.conv_b", c.C);
-  if (!c.generic) {
-    std::vector<float> w4((size_t)KP / 4 * 32 * 4, 0.f);
-    for (int ch = 0; ch < c.C; ++ch)
-      for (int k = 0; k < K; ++k) w4[((size_t)(k / 4) * 32 + ch) * 4 + (k % 4)] = cw[(size_t)ch * K + k];
-    c.conv_w = upload(m, w4);
-    // the positions at a window's edges see its zero padding: the same conv with the taps over the padding cleared
-    // (left: frames kt < PT; right: kt >= KT - (KT - PT - 1) = PT + 7), applied to the stream's real rows (crnn_rows_kernel)
-    std::vector<float> wl(w4), wr(w4);
-    for (int k = 0; k < K; ++k) {
-      const int kt = k % c.KT;
-      for (int ch = 0; ch < c.C; ++ch) {
-        const size_t o = ((size_t)(k / 4) * 32 + ch) * 4 + (k % 4);
-        if (kt < c.PT) wl[o] = 0.f;
-        if (kt >= c.T - (c.OT - 1) * c.ST + c.PT) wr[o] = 0.f;   // frames past the window's last row: kt >= 151 - 144 + 6 = 13
-      }
-    }
-    c.conv_wL = upload(m, wl);
-    c.conv_wR = upload(m, wr);
-    if (!c.conv_wL || !c.conv_wR) return ww_fail(ctx, WW_ENOMEM, "CRNN upload failed");
-  } else {
-    std::vector<float> wt((size_t)K * c.C);
-    for (int ch = 0; ch < c.C; ++ch)
-      for (int k = 0; k < K; ++k) wt[(size_t)k * c.C + ch] = cw[(size_t)ch * K + k];
-    c.conv_wt = upload(m, wt);
-    c.conv_w = c.conv_wt;
-  }
-  c.conv_b = upload(m, std::vector<float>(cb, cb + c.C));
-  const int G = 3 * c.H;
-  auto cat2 = [&](const char *a, const char *b, size_t each, std::vector<float> &out) -> int {
-    uint32_t na = 0, nb = 0;
-    const float *pa = (const float *)bv.find(a, &na), *pb = (const float *)bv.find(b, &nb);
-    if (!pa || !pb || na != each || nb != each) return ww_fail(ctx, WW_EBLOB, "blob sections %s/%s missing or mis-sized", a, b);
-    out.assign(pa, pa + each);
-    out.insert(out.end(), pb, pb + each);
-    return WW_OK;
-  };
-  std::vector<float> v;
-  int rc;
-  const size_t in1 = (size_t)c.OF * c.C, in2 = 2 * (size_t)c.H;
-  if ((rc = cat2("crnn.g1f.wx", "crnn.g1b.wx", G * in1, v))) return rc; c.wx1 = upload(m, v);
-  if (!c.generic) {
-    c.wx1s = upload(m, pack_k4(v, 2 * G, in1));
-    {  // W_x1 [192][640] -> [plane][k-step 20][n-tile 12][lane = g*16 + j][8]: element e is W[nt*16 + j][ks*32 + 8 g + e]
-      std::vector<unsigned short> wb((size_t)2 * 20 * 12 * 64 * 8);
-      for (int ks = 0; ks < 20; ++ks)
-        for (int nt = 0; nt < 12; ++nt)
-          for (int ln = 0; ln < 64; ++ln)
-            for (int e = 0; e < 8; ++e) {
-              const int gq = ln >> 4, jj = ln & 15;
-              uint16_t h, l;
-              bf16_split(v[(size_t)(nt * 16 + jj) * in1 + ks * 32 + 8 * gq + e], h, l);
-              const size_t o = (((size_t)ks * 12 + nt) * 64 + ln) * 8 + e;
-              wb[o] = h;
-              wb[(size_t)20 * 12 * 64 * 8 + o] = l;
-            }
-      c.wx1b = upload(m, wb);
-    }
-    {  // conv weights [32][5][20] -> [plane][k-step 4][m-tile 2][lane = g*16 + i][8]: group G = ks*4 + g = kf*3 + h holds
-       // kt'' = 8 h + e with kt = kt'' - 2 (zero outside 0..19); G = 15 is all zero
-      std::vector<unsigned short> wb((size_t)2 * 4 * 2 * 64 * 8, 0);
-      for (int ks = 0; ks < 4; ++ks)
-        for (int mt = 0; mt < 2; ++mt)
-          for (int ln = 0; ln < 64; ++ln)
-            for (int e = 0; e < 8; ++e) {
-              const int gq = ln >> 4, ii = ln & 15, Gq = ks * 4 + gq;
-              const int kf = Gq / 3, kt = (Gq % 3) * 8 + e - 2;
-              float x = 0.f;
-              if (Gq < 15 && kt >= 0 && kt < c.KT) x = cw[(size_t)(mt * 16 + ii) * K + kf * c.KT + kt];
-              uint16_t h, l;
-              bf16_split(x, h, l);
-              const size_t o = (((size_t)ks * 2 + mt) * 64 + ln) * 8 + e;
-              wb[o] = h;
-              wb[(size_t)4 * 2 * 64 * 8 + o] = l;
-            }
-      c.cwb = upload(m, wb);
-    }
-    if (!c.wx1s || !c.wx1b || !c.cwb) return ww_fail(ctx, WW_ENOMEM, "CRNN upload failed");
-  }
-  if (c.generic) {
-    std::vector<float> wp((size_t)2 * G * c.FEATP, 0.f);
-    for (int r = 0; r < 2 * G; ++r) memcpy(&wp[(size_t)r * c.FEATP], &v[(size_t)r * in1], in1 * sizeof(float));
-    c.wx1p = upload(m, wp);
-    if (!c.wx1p) return ww_fail(ctx, WW_ENOMEM, "CRNN upload failed");
-  }
-  if ((rc = cat2("crnn.g1f.bx", "crnn.g1b.bx", G, v))) return rc; c.bx1 = upload(m, v);
-  if ((rc = cat2("crnn.g1f.wh", "crnn.g1b.wh", (size_t)G * c.H, v))) return rc; c.wh1 = upload(m, v);
-  if ((rc = cat2("crnn.g1f.bh", "crnn.g1b.bh", G, v))) return rc; c.bh1 = upload(m, v);
-  if ((rc = cat2("crnn.g2f.wx", "crnn.g2b.wx", G * in2, v))) return rc; c.wx2 = upload(m, v);
-  c.wx2s = upload(m, pack_k4(v, 2 * G, in2));
-  if (!c.wx2s) return ww_fail(ctx, WW_ENOMEM, "CRNN upload failed");
-  if ((rc = cat2("crnn.g2f.bx", "crnn.g2b.bx", G, v))) return rc; c.bx2 = upload(m, v);
-  if ((rc = cat2("crnn.g2f.wh", "crnn.g2b.wh", (size_t)G * c.H, v))) return rc; c.wh2 = upload(m, v);
-  if ((rc = cat2("crnn.g2f.bh", "crnn.g2b.bh", G, v))) return rc; c.bh2 = upload(m, v);
-  NEED_F(w1, "crnn.head_w1", in2 * in2);
-  NEED_F(b1, "crnn.head_b1", in2);
-  NEED_F(w2, "crnn.head_w2", (size_t)c.NOUT * in2);
-  NEED_F(b2, "crnn.head_b2", c.NOUT);
-  c.w1 = upload(m, std::vector<float>(w1, w1 + in2 * in2));
-  c.b1 = upload(m, std::vector<float>(b1, b1 + in2));
-  c.w2 = upload(m, std::vector<float>(w2, w2 + c.NOUT * in2));
-  c.b2 = upload(m, std::vector<float>(b2, b2 + c.NOUT));
-  if (!c.conv_w || !c.conv_b || !c.wx1 || !c.bx1 || !c.wh1 || !c.bh1 || !c.wx2 || !c.bx2 || !c.wh2 || !c.bh2 || !c.w1 ||
-      !c.b1 || !c.w2 || !c.b2)
-    return ww_fail(ctx, WW_ENOMEM, "CRNN upload failed");
-  m->info.window = c.T; m->info.n_out = c.NOUT; m->info.enc_rows = 1; m->info.enc_width = 2 * c.H;
-  return WW_OK;
-}
-
-static int load_wave(ww_ctx *ctx, ww_model *m, const blob_view &bv) {
-  uint32_t cnt = 0;
-  const int32_t *meta = (const int32_t *)bv.find("wave.meta", &cnt);
-  if (!meta || cnt != 6) return ww_fail(ctx, WW_EBLOB, "blob lacks wave.meta");
-  ww_wave_dev &v = m->wave;
-  v.T = meta[0]; v.n_mel = meta[1]; v.C = meta[2]; v.S = meta[3]; v.NB = meta[4]; v.NOUT = meta[5];
-  if (v.C != 16 || v.S != 32 || v.T > 192 || v.T < 1 || v.n_mel > 48 || v.NOUT < 1 || v.NOUT > 16 || v.NB < 1 ||
-      v.n_mel != m->filt.n_mel)
-    return ww_fail(ctx, WW_EBLOB, "unsupported Wavenet geometry (T=%d C=%d S=%d)", v.T, v.C, v.S);
-  const int NB = v.NB, C = v.C, S = v.S;
-  const int32_t *dil = (const int32_t *)bv.find("wave.dilations", &cnt);
-  if (!dil || (int)cnt != NB) return ww_fail(ctx, WW_EBLOB, "blob lacks wave.dilations");
-  const int32_t *order = (const int32_t *)bv.find("wave.skip_order", &cnt);
-  if (!order || (int)cnt != NB) return ww_fail(ctx, WW_EBLOB, "blob lacks wave.skip_order");
-  const int32_t *has_res = (const int32_t *)bv.find("wave.has_res", &cnt);
-  if (!has_res || (int)cnt != NB) return ww_fail(ctx, WW_EBLOB, "blob lacks wave.has_res");
-  for (int b = 0; b < NB; ++b) {
-    if (dil[b] < 1 || 2 * dil[b] > 16) return ww_fail(ctx, WW_EBLOB, "dilation %d unsupported (max 8)", dil[b]);
-    if (order[b] != b) return ww_fail(ctx, WW_EBLOB, "skip connections are not summed in block order");
-  }
-  v.dil.assign(dil, dil + NB); v.order.assign(order, order + NB); v.has_res.assign(has_res, has_res + NB);
-  NEED_F(w_in, "wave.w_in", (size_t)v.n_mel * C);
-  NEED_F(b_in, "wave.b_in", C);
-  NEED_F(bn_s, "wave.bn_scale", (size_t)NB * C);
-  NEED_F(bn_t, "wave.bn_shift", (size_t)NB * C);
-  NEED_F(w_sig, "wave.w_sig", (size_t)NB * 3 * C * C);
-  NEED_F(b_sig, "wave.b_sig", (size_t)NB * C);
-  NEED_F(w_tanh, "wave.w_tanh", (size_t)NB * 3 * C * C);
-  NEED_F(b_tanh, "wave.b_tanh", (size_t)NB * C);
-  NEED_F(w_res, "wave.w_res", (size_t)NB * C * C);
-  NEED_F(b_res, "wave.b_res", (size_t)NB * C);
-  NEED_F(w_skip, "wave.w_skip", (size_t)NB * C * S);
-  NEED_F(b_skip, "wave.b_skip", (size_t)NB * S);
-  NEED_F(dw1, "wave.det_w1", (size_t)S * S);
-  NEED_F(db1, "wave.det_b1", S);
-  NEED_F(dw2, "wave.det_w2", (size_t)S * v.NOUT);
-  NEED_F(db2, "wave.det_b2", v.NOUT);
-  // MFMA B-operand order: [k-block][kk][col][q], k = kb*16 + kk*4 + q
-  std::vector<float> in4(3 * 4 * 16 * 4, 0.f);
-  for (int k = 0; k < v.n_mel; ++k)
-    for (int col = 0; col < C; ++col) in4[(((k / 16) * 4 + (k % 16) / 4) * 16 + col) * 4 + (k % 4)] = w_in[(size_t)k * C + col];
-  std::vector<float> g4((size_t)NB * 3 * 4 * 32 * 4), bg((size_t)NB * 32), rs4((size_t)NB * 4 * 48 * 4), brs((size_t)NB * 48);
-  for (int b = 0; b < NB; ++b) {
-    for (int tap = 0; tap < 3; ++tap)
-      for (int ch = 0; ch < C; ++ch)
-        for (int col = 0; col < 32; ++col) {
-          float val = col < 16 ? w_sig[(((size_t)b * 3 + tap) * C + ch) * C + col]
-                               : w_tanh[(((size_t)b * 3 + tap) * C + ch) * C + col - 16];
-          g4[((((size_t)b * 3 + tap) * 4 + ch / 4) * 32 + col) * 4 + (ch % 4)] = val;
-        }
-    for (int col = 0; col < 16; ++col) {
-      bg[(size_t)b * 32 + col] = b_sig[(size_t)b * C + col];
-      bg[(size_t)b * 32 + 16 + col] = b_tanh[(size_t)b * C + col];
-    }
-    for (int ch = 0; ch < C; ++ch)
-      for (int col = 0; col < 48; ++col) {
-        float val = col < 16 ? w_res[((size_t)b * C + ch) * C + col] : w_skip[((size_t)b * C + ch) * S + col - 16];
-        rs4[(((size_t)b * 4 + ch / 4) * 48 + col) * 4 + (ch % 4)] = val;
-      }
-    for (int col = 0; col < 48; ++col) brs[(size_t)b * 48 + col] = col < 16 ? b_res[(size_t)b * C + col] : b_skip[(size_t)b * S + col - 16];
-  }
-  std::vector<float> d1((size_t)2 * 4 * 32 * 4), d2((size_t)2 * 4 * 16 * 4, 0.f), d2b(16, 0.f);
-  for (int k = 0; k < S; ++k) {
-    for (int col = 0; col < S; ++col) d1[(((size_t)(k / 16) * 4 + (k % 16) / 4) * 32 + col) * 4 + (k % 4)] = dw1[(size_t)k * S + col];
-    for (int col = 0; col < v.NOUT; ++col) d2[(((size_t)(k / 16) * 4 + (k % 16) / 4) * 16 + col) * 4 + (k % 4)] = dw2[(size_t)k * v.NOUT + col];
-  }
-  for (int col = 0; col < v.NOUT; ++col) d2b[col] = db2[col];
-  // split-bf16 A operands (wavenet.hip, SPLIT_BF16; transposed formulation: rows = output channels).
-  // slot = (kstep*2 + {sig,tanh})*2 + {0,1} for the gate conv (k-step 0 = tap 2, k-step 1 = tap 0 | tap 1: the two
-  // delayed taps), 8 + mtile*2 + {0,1} for res | skip.  Lane (i = lane & 15, kg = lane >> 4) holds 8 k-slots = two
-  // groups of the 4 channels 4 kg .. 4 kg + 3 for output row 16 mtile + i.  Where only one tap (or the gate product) is at
-  // hand the second group carries the hi x lo product instead of zeros: 5 MFMAs per gate and 2 per res | skip m-tile give
-  // all three split products plus the bias (16 MFMAs per block and tile, not 21).
-  {
-    std::vector<uint16_t> pk((size_t)NB * 14 * 64 * 8, 0);
-    auto put = [&](int b, int slot, int lane, int q, uint16_t val) { pk[((((size_t)b * 14 + slot) * 64) + lane) * 8 + q] = val; };
-    for (int b = 0; b < NB; ++b) {
-      for (int lane = 0; lane < 64; ++lane) {
-        const int i = lane & 15, kg = lane >> 4;
-        for (int q = 0; q < 8; ++q) {
-          const int ch = 4 * kg + (q & 3);
-          for (int mt = 0; mt < 2; ++mt) {
-            // the gates are evaluated with v_exp_f32 (= exp2): sigmoid(s) = 1 / (1 + exp2(-log2e s)),
-            // tanh(t) = 1 - 2 / (1 + exp2(2 log2e t)) - the factors ride in the weights and biases
-            const float sc = mt == 0 ? -1.4426950408889634f : 2.8853900817779268f;
-            const float *wsrc = mt == 0 ? w_sig : w_tanh;
-            auto wt = [&](int tap) { return wsrc[(((size_t)b * 3 + tap) * C + ch) * C + i] * sc; };
-            uint16_t hi, lo;
-            // k-step 0, slot "hh": (hi of tap 2 | hi of tap 2) against B = (u_hi | u_lo);
-            //           slot "lb": (lo of tap 2 | bias hi, bias lo in k-slots 4, 5 of lane group 0) against B = (u_hi | 1, 1, 0, 0)
-            bf16_split(wt(2), hi, lo);
-            put(b, (0 * 2 + mt) * 2 + 0, lane, q, hi);
-            if (q < 4) {
-              put(b, (0 * 2 + mt) * 2 + 1, lane, q, lo);
-            } else if (kg == 0 && q < 6) {
-              uint16_t bh, bl;
-              bf16_split((mt == 0 ? b_sig : b_tanh)[(size_t)b * C + i] * sc, bh, bl);
-              put(b, (0 * 2 + mt) * 2 + 1, lane, q, q == 4 ? bh : bl);
-            }
-            // k-step 1: (tap 0 | tap 1), hi and lo slots, against B = the two delayed rows (hi plane, then lo plane)
-            bf16_split(wt(q < 4 ? 0 : 1), hi, lo);
-            put(b, (1 * 2 + mt) * 2 + 0, lane, q, hi);
-            put(b, (1 * 2 + mt) * 2 + 1, lane, q, lo);
-          }
-          for (int mt = 0; mt < 3; ++mt) {
-            // res | skip: slot "hh" = (hi | hi) against B = (g_hi | g_lo), slot "lb" = (lo | bias hi, bias lo) against (g_hi | 1, 1, 0, 0)
-            const float wv = mt == 0 ? (has_res[b] ? w_res[((size_t)b * C + ch) * C + i] : 0.f) : w_skip[((size_t)b * C + ch) * S + (mt - 1) * 16 + i];
-            uint16_t hi, lo;
-            bf16_split(wv, hi, lo);
-            put(b, 8 + mt * 2 + 0, lane, q, hi);
-            if (q < 4) {
-              put(b, 8 + mt * 2 + 1, lane, q, lo);
-            } else if (kg == 0 && q < 6) {
-              uint16_t bh, bl;
-              bf16_split(mt == 0 ? (has_res[b] ? b_res[(size_t)b * C + i] : 0.f) : b_skip[(size_t)b * S + (mt - 1) * 16 + i], bh, bl);
-              put(b, 8 + mt * 2 + 1, lane, q, q == 4 ? bh : bl);
-            }
-          }
-        }
-      }
-    }
-    v.wpk = upload(m, pk);  // one page per block (wavenet.hip: WV_PAGE_U4 16-byte units)
-    if (!v.wpk) return ww_fail(ctx, WW_ENOMEM, "Wavenet upload failed");
-  }
-  v.w_in = upload(m, in4); v.b_in = upload(m, std::vector<float>(b_in, b_in + C));
-  v.bn_s = upload(m, std::vector<float>(bn_s, bn_s + (size_t)NB * C));
-  v.bn_t = upload(m, std::vector<float>(bn_t, bn_t + (size_t)NB * C));
-  v.w_gate = upload(m, g4); v.b_gate = upload(m, bg); v.w_rs = upload(m, rs4); v.b_rs = upload(m, brs);
-  v.d_w1 = upload(m, d1); v.d_b1 = upload(m, std::vector<float>(db1, db1 + S));
-  v.d_w2 = upload(m, d2); v.d_b2 = upload(m, d2b);
-  if (!v.w_in || !v.b_in || !v.bn_s || !v.bn_t || !v.w_gate || !v.b_gate || !v.w_rs ||
-      !v.b_rs || !v.d_w1 || !v.d_b1 || !v.d_w2 || !v.d_b2)
-    return ww_fail(ctx, WW_ENOMEM, "Wavenet upload failed");
-  m->info.window = v.T; m->info.n_out = v.NOUT; m->info.enc_rows = v.T; m->info.enc_width = S;
-  return WW_OK;
-}
+#define WW_SLOT(s_, member_) {#s_ "." #member_, [](ww_model &m, void *p) { m.s_.member_ = (decltype(m.s_.member_))p; }}
+static const model_slot MODEL_SLOTS[] = {
+    WW_SLOT(filt, tw16), WW_SLOT(filt, melV), WW_SLOT(filt, melVmeta), WW_SLOT(filt, start), WW_SLOT(filt, bias), WW_SLOT(filt, wpad),
+    WW_SLOT(filt, wdense), WW_SLOT(filt, hann), WW_SLOT(filt, tw256), WW_SLOT(filt, tw512),
+    WW_SLOT(crnn, conv_w), WW_SLOT(crnn, conv_wL), WW_SLOT(crnn, conv_wR), WW_SLOT(crnn, conv_wt), WW_SLOT(crnn, conv_b),
+    WW_SLOT(crnn, wx1s), WW_SLOT(crnn, wx1b), WW_SLOT(crnn, cwb), WW_SLOT(crnn, wx1p), WW_SLOT(crnn, bx1), WW_SLOT(crnn, wh1),
+    WW_SLOT(crnn, bh1), WW_SLOT(crnn, wx2), WW_SLOT(crnn, wx2s), WW_SLOT(crnn, bx2), WW_SLOT(crnn, wh2), WW_SLOT(crnn, bh2),
+    WW_SLOT(crnn, w1), WW_SLOT(crnn, b1), WW_SLOT(crnn, w2), WW_SLOT(crnn, b2),
+    WW_SLOT(wave, wpk), WW_SLOT(wave, w_in), WW_SLOT(wave, b_in), WW_SLOT(wave, bn_s), WW_SLOT(wave, bn_t), WW_SLOT(wave, w_gate),
+    WW_SLOT(wave, b_gate), WW_SLOT(wave, w_rs), WW_SLOT(wave, b_rs), WW_SLOT(wave, d_w1), WW_SLOT(wave, d_b1), WW_SLOT(wave, d_w2),
+    WW_SLOT(wave, d_b2),
+};
+#undef WW_SLOT
 
 extern "C" {
 
@@ -746,24 +287,27 @@ int ww_model_load(ww_ctx *ctx, const void *blob, size_t len, ww_model **out) {
   WW_GUARD_BEGIN
   if (!ctx || !blob || !out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
   *out = nullptr;
-  if (len < 16) return ww_fail(ctx, WW_EBLOB, "blob too short");
-  uint32_t h[4];
-  memcpy(h, blob, sizeof h);  // the caller's buffer need not be 4-byte aligned
-  if (h[0] != 0x42485757u || h[1] != 1u) return ww_fail(ctx, WW_EBLOB, "bad blob magic/version");
-  blob_view bv = {(const uint8_t *)blob, len, h[3], h[2]};
-  if (16 + 32 * (size_t)bv.n > len) return ww_fail(ctx, WW_EBLOB, "section table exceeds blob");
-  if (bv.kind != WW_KIND_CRNN && bv.kind != WW_KIND_WAVENET) return ww_fail(ctx, WW_EBLOB, "unknown model kind %u", bv.kind);
+  ww_packed_model pm;
+  const int rc = ww_pack_model(pm, blob, len);  // (reads the blob through memcpy: the caller's buffer need not be 4-byte aligned)
+  if (rc != WW_OK) return ww_fail(ctx, rc, "%s", pm.err);
   WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
   ww_model *m = new ww_model();
   ww_scoped<ww_model, ww_model_free> own(m);
   m->ctx = ctx;
-  m->kind = (int)bv.kind;
-  int rc = load_filter(ctx, m, bv);
-  if (rc == WW_OK) rc = bv.kind == WW_KIND_CRNN ? load_crnn(ctx, m, bv) : load_wave(ctx, m, bv);
-  if (rc != WW_OK) return rc;  // (`own` frees what was uploaded so far)
-  m->info.kind = m->kind;
-  m->info.n_mel = m->filt.n_mel;
-  m->info.n_bins = m->filt.n_bins;
+  m->kind = pm.kind;
+  m->info = pm.info;
+  static_cast<ww_filter_geom &>(m->filt) = pm.filt;
+  static_cast<ww_crnn_geom &>(m->crnn) = pm.crnn;
+  static_cast<ww_wave_geom &>(m->wave) = pm.wave;
+  if (hipMalloc(&m->block, pm.bytes.size()) != hipSuccess ||
+      hipMemcpy(m->block, pm.bytes.data(), pm.bytes.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return ww_fail(ctx, WW_ENOMEM, "model upload failed (%zu bytes)", pm.bytes.size());  // (`own` frees the block)
+  for (const ww_pack_entry &e : pm.table) {
+    const model_slot *slot = std::find_if(std::begin(MODEL_SLOTS), std::end(MODEL_SLOTS), [&](const model_slot &s) { return strcmp(s.name, e.name) == 0; });
+    if (slot == std::end(MODEL_SLOTS)) return ww_fail(ctx, WW_EINTERNAL, "packed array %s has no place in ww_model", e.name);
+    slot->set(*m, (char *)m->block + e.off);
+  }
+  if (m->kind == WW_KIND_CRNN && m->crnn.generic) m->crnn.conv_w = m->crnn.conv_wt;  // one array, the generic kernels' name for it
   *out = own.release();
   return WW_OK;
   WW_GUARD_END(ctx)
@@ -776,7 +320,7 @@ int ww_model_free(ww_model *m) {
     ww_device_scope dev_scope(m->ctx->device);
     hipStreamSynchronize(m->ctx->stream);
   }
-  for (void *p : m->allocs) hipFree(p);
+  if (m->block) hipFree(m->block);
   delete m;
   return WW_OK;
   WW_GUARD_END(nullptr)

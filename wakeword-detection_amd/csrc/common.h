@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/wwhip.h"
+#include "model_layout.h"
 
 #define WW_WAVE 64
 
@@ -53,34 +54,27 @@ struct ww_ctx {
   unsigned desc_k = 0;
 };
 
-// Device-resident mel filterbank in banded form: band m covers bins [start[m], start[m]+len[m])
-// with weights w[woff[m] .. woff[m]+len[m]).
-#define WW_MELV_CHUNKS 16  // 9 + 4 + 3 float4 chunks: groups of 36, 16 and 12 taps
-struct ww_filter_dev {
-  int n_mel = 0, n_bins = 0;
-  float floor_v = 0, log_off = 0, scale = 0;
-  int *start = nullptr, *len = nullptr, *woff = nullptr;
-  float *w = nullptr, *bias = nullptr;
+// A loaded model's arrays all lie in ONE device block (ww_model::block), each from a 256-byte boundary, packed on the host by
+// model_pack.h; the structs below are model_layout.h's scalar geometry plus the pointers into that block (api.hip: ww_model_load).
+struct ww_filter_dev : ww_filter_geom {
+  int *start = nullptr;      // [n_mel] first bin of band m
+  float *bias = nullptr;
   float *wdense = nullptr;   // [n_mel][n_bins] dense weights (filter.tflite layout)
-  float *wpad = nullptr;     // [WW_MEL_TAPS][64] tap-major zero-padded weights (kernel form)
-  int total_taps = 0, max_len = 0;
+  float *wpad = nullptr;     // [WW_MEL_TAPS][64] tap-major zero-padded weights of the bands from their first bins (kernel form)
   double *hann = nullptr;    // [512] np.hanning(512) in fp64
   double *tw256 = nullptr;   // [256][2] e^{-2 pi i k / 256}
   double *tw512 = nullptr;   // [256][2] e^{-2 pi i k / 512}
   double *tw16 = nullptr;    // [16 k1][16 j][2] e^{-2 pi i j k1 / 256}
   // Mel filter in lane form for the batched front end (frontend.hip): the bands, sorted by width, are dealt
-  // to three groups of 16 "slots"; slot s of group g accumulates one band over WW_MELV_CAP[g] padded taps.
+  // to three groups of 16 "slots"; slot s of group g accumulates one band over 4 * WW_MELV_CAPQ[g] padded taps.
   float *melV = nullptr;     // [WW_MELV_CHUNKS][16 slots] float4: 0.5 * weight of taps 4c..4c+3 (chunks of group 0, 1, 2)
   int *melVmeta = nullptr;   // [3][16]: first bin | band << 16 (band 0xffff: empty slot)
-  int melv_aligned = 0;      // every first bin is a multiple of 4
 };
 
-struct ww_crnn_dev {
-  int n_mel, T, C, KF, KT, SF, ST, PF, PT, OF, OT, H, NOUT, HEAD;
-  float *conv_w = nullptr;   // [KF*KT][C]  (k-major for the implicit GEMM)
+struct ww_crnn_dev : ww_crnn_geom {
+  float *conv_w = nullptr;   // [CV_KPAD/4][32][4] (MFMA B-operand order); generic: conv_wt
   float *conv_b = nullptr;   // [C]
-  float *wx1 = nullptr;      // [2*3H][OF*C]  rows: fwd z,r,h then bwd z,r,h
-  float *wx1s = nullptr;     // the same matrix in MFMA B-operand order [OF*C/4][2*3H][4] (crnn_fused_kernel)
+  float *wx1s = nullptr;     // W_x1 [2*3H][OF*C] (rows: fwd z,r,h then bwd z,r,h) in MFMA B-operand order [OF*C/4][2*3H][4] (crnn_fused_kernel)
   float *bx1 = nullptr;      // [2*3H]
   float *wh1 = nullptr;      // [2][3H][H]
   float *bh1 = nullptr;      // [2][3H]
@@ -92,25 +86,19 @@ struct ww_crnn_dev {
   float *wh2 = nullptr;
   float *bh2 = nullptr;
   float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;
-  // Any other conv geometry (utils/CRNN_files/*_old.tflite: 20x5 kernel, stride 8x2, VALID, 74 steps of 96 features)
-  // takes the generic kernels of crnn.hip: direct conv, the same MFMA GEMM on K padded to FEATP, step-wise GRUs.
-  bool generic = false;
-  int FEATP = 0;               // OF*C rounded up to the GEMM's K tile (64)
-  float *conv_wt = nullptr;    // [KF*KT][C]
+  // generic geometry (ww_crnn_geom::generic)
+  float *conv_wt = nullptr;    // [KF*KT][C]  (k-major for the implicit GEMM)
   float *conv_wL = nullptr, *conv_wR = nullptr;  // conv_w with the taps that meet a window's zero padding cleared (first 6 / last 7 frames): crnn_rows_kernel
   float *wx1p = nullptr;       // [2*3H][FEATP], zero padded
 };
 
-struct ww_wave_dev {
-  int T, n_mel, C, S, NB, NOUT;
-  std::vector<int> dil, order, has_res;
+struct ww_wave_dev : ww_wave_geom {
   float *w_in = nullptr, *b_in = nullptr;          // [n_mel][C], [C]
   float *bn_s = nullptr, *bn_t = nullptr;          // [NB][C]
   float *w_gate = nullptr, *b_gate = nullptr;      // [NB][3*C][2C] (cols: sig 0..C-1, tanh C..2C-1), [NB][2C]
   float *w_rs = nullptr, *b_rs = nullptr;          // [NB][C][C+S] (cols: res 0..C-1, skip C..), [NB][C+S]
   float *d_w1 = nullptr, *d_b1 = nullptr, *d_w2 = nullptr, *d_b2 = nullptr;
-  uint16_t *wpk = nullptr;                         // split-bf16 parameter pages [NB]{[14][64][8] bf16 A operands, [7][16] f32 vectors}
-  bool order_is_natural = true;
+  uint16_t *wpk = nullptr;                         // split-bf16 parameter pages [NB]{[WV_SLOTS][64][8] bf16 A operands, [7][16] f32 vectors}
 };
 
 struct ww_model {
@@ -126,7 +114,7 @@ struct ww_model {
   int opt_tail_mfma = 1;    // WW_OPT_CRNN_TAIL_MFMA
   int opt_wave_rowmajor = 0;  // WW_OPT_WAVENET_ROWMAJOR
   int opt_wave_seq_segment = 0;  // WW_OPT_WAVE_SEQ_SEGMENT (0 = the library's choice)
-  std::vector<void *> allocs;
+  void *block = nullptr;  // the one device allocation behind every pointer of filt, crnn and wave
 };
 
 int ww_fail(ww_ctx *ctx, int code, const char *fmt, ...);

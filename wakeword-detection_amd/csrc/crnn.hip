@@ -341,7 +341,7 @@ __device__ __forceinline__ void wsync_g() {
 // functions that take the pointer as a parameter they lost their scalar base (global_load_dwordx4 v, v, s[2:3] became
 // v_lshl_add_u64 + a load from a 64-bit vector address: profiles/EXPERIMENTS.md 13).
 // ------------------------------------------------------------------------------------------
-// this lane's conv weights (B operand: [112/4][32][4]; the last quad's k = 96 + kk is element kk of it) and the biases of its
+// this lane's conv weights (B operand: [CV_KPAD/4][32][4]; the last quad's k = 96 + kk is element kk of it) and the biases of its
 // two channels
 #define CV_LOAD_W(wreg_, wlast_, cb0_, cb1_, w4_, cbias_)                                            \
   _Pragma("unroll") for (int kb = 0; kb < CV_KB; ++kb)                                               \
@@ -532,7 +532,7 @@ static_assert(64 * GR_W1_LD <= CF_FUSED_FEAT_ROWS * CF_FLD, "fused kernel's feat
 struct fused_args {
   const float *mel;
   win_addr wa;
-  const float *w4;    // conv weights [112/4][32][4]
+  const float *w4;    // conv weights [CV_KPAD/4][32][4]
   const float *cbias; // [32]
   const float *wx1s;  // W_x1 in B-operand order [640/4][192][4]
   const float *bx1;   // [192]
@@ -1292,13 +1292,13 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_bf16_kernel(fused_ar
   window_span(a.wa, w, a.T, row, valid);
 
   // conv weights, A operand (rows = channels): [plane][k-step 4][m-tile 2][lane][8 bf16]
-  uint4 wq[2][4][2];
+  uint4 wq[2][CWB_KS][CWB_MT];
 #pragma unroll
   for (int p = 0; p < 2; ++p)
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
+    for (int ks = 0; ks < CWB_KS; ++ks)
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) wq[p][ks][mt] = ((const uint4 *)a.cwb)[((p * 4 + ks) * 2 + mt) * 64 + lane];
+      for (int mt = 0; mt < CWB_MT; ++mt) wq[p][ks][mt] = ((const uint4 *)a.cwb)[((p * CWB_KS + ks) * CWB_MT + mt) * 64 + lane];
   float cb[2][4];  // bias of this lane's channels mt*16 + kk*4 + r
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
@@ -1400,7 +1400,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_bf16_kernel(fused_ar
     store_pos(5, prev);
   }
   // W_x1 planes, B operand: [plane][k-step 20][n-tile 12][lane][8 bf16]; this wave's n-tiles are 3 wave .. 3 wave + 2
-  auto w_ld = [&](int p, int ks, int n) { return ((const uint4 *)a.wx1b)[((size_t)(p * 20 + ks) * 12 + wave * 3 + n) * 64 + lane]; };
+  auto w_ld = [&](int p, int ks, int n) { return ((const uint4 *)a.wx1b)[((size_t)(p * WX1B_KS + ks) * WX1B_NT + wave * 3 + n) * 64 + lane]; };
   uint4 bq[3][2][3];  // [ring slot][plane][n]
 #pragma unroll
   for (int s2 = 0; s2 < 2; ++s2)

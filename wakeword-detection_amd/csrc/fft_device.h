@@ -10,9 +10,10 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "model_layout.h"  // WW_MEL_TAPS
+
 #define WIN 512
 #define NB 257
-#define WW_MEL_TAPS 36  // longest band of the shipped filterbank (checked at model load)
 #define FFT_LD 288  // per-wave complex buffer: 256 points + 1 pad slot per 8 (bank spreading)
 
 template <typename R>

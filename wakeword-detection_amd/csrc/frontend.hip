@@ -14,7 +14,7 @@
 // frame - and the real-FFT untangling, for which lane j fetches its partner Z[256-k] (lane (16-j)%16) through
 // the dead transpose buffer; two magnitudes per evaluation land in LDS.  The mel filter runs on the vector ALU
 // with the lanes re-dealt as (band slot, frame): 64 fused multiply-adds per lane on magnitudes read 16 bytes
-// at a time (bands dealt so that these reads are bank-conflict-free: load_filter in api.hip), then the
+// at a time (bands dealt so that these reads are bank-conflict-free: pack_filter in model_pack.h), then the
 // log/affine tail, and the wave's 4x40 tile leaves through LDS as one contiguous store.  Wave 3 uses the sample
 // tile as its transpose buffer: the tile is dead once every wave has formed its Hann products (the second barrier).
 // (This kernel's fp64 form, the default front end of rounds 1-3, is recorded in profiles/EXPERIMENTS.md.)
@@ -59,7 +59,7 @@ struct logmel_args {
   int n_mel;
   float floor_v, log_off, scale;
   const double *hann, *tw256, *tw512, *tw16;
-  const float *melV;           // mel filter in lane form: [WW_MELV_CHUNKS][16 slots] float4 (api.hip, load_filter)
+  const float *melV;           // mel filter in lane form: [WW_MELV_CHUNKS][16 slots] float4 (model_pack.h, pack_filter)
   const int *melVmeta;         // [3 groups][16 slots]: first bin | band << 16
   int melv_aligned;            // first bins are multiples of 4: 16-byte magnitude reads
   float *mel;
@@ -185,8 +185,8 @@ __device__ __forceinline__ H2 hann_pair(const H2 *tb, int n1, int j) {
   return r;
 }
 
-#define MAG_LD 272  // floats per frame of magnitudes: 257 + zero pad to 17*16; 16 mod 32, so the two frames a
-                    // 32-lane write group touches use disjoint banks
+// MAG_LD (model_layout.h) = 272 floats per frame of magnitudes: 257 + zero pad to 17*16; 16 mod 32, so the two frames a
+// 32-lane write group touches use disjoint banks
 #define TR_LD 17    // padded row of the 16x16 transpose
 #define LM_WBUF (4 * MAG_LD * 4)  // logmel_kernel's per-wave scratch: 16x16 fp32 transposes of 4 frames, later their magnitudes
 
@@ -358,10 +358,10 @@ __device__ __forceinline__ void untangle_tail(const cplx<R> z, float *mrow, int 
 
 // Mel filterbank on the vector ALU, per wave, on the wave's four rows of magnitudes mg_[4][MAG_LD], and the park of its
 // 4 x n_mel tile at mg_ for one contiguous store.  Lane 4 s + q owns frame q and slot s of each of the three
-//   band groups (load_filter, api.hip): 36 + 16 + 12 padded taps, one fused multiply-add per tap with the
+//   band groups (pack_filter, model_pack.h): 36 + 16 + 12 padded taps, one fused multiply-add per tap with the
 //   magnitudes read 16 bytes at a time from this wave's LDS rows.  Frame in the low lane bits: the four
 //   16-lane groups a ds_read_b128 is served in then hold four slots x four frames each, the rows of the four
-//   frames sit 4 sixteen-byte bank slots apart, and load_filter deals the bands so that the four slots of such
+//   frames sit 4 sixteen-byte bank slots apart, and pack_filter deals the bands so that the four slots of such
 //   a group start on different slots mod 4 - conflict-free.  (The fp32 MFMA form of this contraction kept
 //   the SIMD's vector ALU idle for 32 cycles per instruction - fp32 MFMA and VALU share a datapath on gfx950
 //   - and needed three workgroup barriers for the partial sums; this form needs none.)
@@ -372,7 +372,7 @@ __device__ __forceinline__ void untangle_tail(const cplx<R> z, float *mrow, int 
 #define LM_MEL_TILE(a_, mg_, lane_)                                                                                    \
   do {                                                                                                                 \
     const int j_ = (lane_) >> 2, sub_ = (lane_) & 3; /* (slot, frame) of this lane */                                  \
-    constexpr int CAPQ_[3] = {9, 4, 3}, C0_[3] = {0, 9, 13};                                                           \
+    constexpr int CAPQ_[WW_MELV_GROUPS] = WW_MELV_CAPQ, C0_[WW_MELV_GROUPS] = WW_MELV_CHUNK0;                          \
     const float4 *wv_ = (const float4 *)(a_).melV + j_;                                                                \
     const float *mrow_ = (mg_) + sub_ * MAG_LD;                                                                        \
     __builtin_amdgcn_sched_barrier(0);                                                                                 \

@@ -208,8 +208,7 @@ __device__ __forceinline__ bf16x8 cat8(s16x4 first, s16x4 second) {
 }
 #define MFMA_BF(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc, 0, 0, 0)
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#define WV_SLOTS 14  // A-operand slots per block: gate (2 k-steps x {sig,tanh} x 2) = 8, res | skip (3 m-tiles x 2) = 6
-#define WV_PAGE_U4 (WV_SLOTS * 64)  // one block's parameter page in 16-byte units (the conv biases sit in padded k-slots)
+// WV_SLOTS A-operand slots per block and its parameter page of WV_PAGE_U4 16-byte units: model_layout.h
 
 // ---- the fp32 transposed block body, the detect head of one 16-row tile and the 16-lane softmax: ONE definition each, used by
 //      wavenet_kernel (a window per workgroup) and wavenet_seq_kernel (a sequence walked in chunks, below).  DESIGN.md 4.3: one
@@ -838,7 +837,7 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
       const bf16x8 w4 = wsl[4 * 64], w5 = wsl[5 * 64], w6 = wsl[6 * 64], w7 = wsl[7 * 64];
       // k-step 0 = tap 2, operands in registers - these MFMAs run while the other waves arrive.  The 8 k-slots of a lane
       // group hold TWO 4-channel groups: (w_hi | w_hi) x (u_hi | u_lo) is hi*hi + hi*lo in one MFMA, (w_lo | bias) x (u_hi | 1, 1)
-      // the lo*hi product plus the bias (hi and lo halves in k-slots 4, 5 of lane group 0): api.hip, load_wavenet
+      // the lo*hi product plus the bias (hi and lo halves in k-slots 4, 5 of lane group 0): model_pack.h, pack_wave
       f32x4 as[WV_MPW], at[WV_MPW];
 #pragma unroll
       for (int mi = 0; mi < WV_MPW; ++mi) {
