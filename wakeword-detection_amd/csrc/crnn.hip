@@ -412,20 +412,41 @@ struct cv_a {
 // contiguous KB per wave load) through a ring bq[DEPTH][3] that is DEPTH - 1 k-steps ahead of its use; the A operands come from
 // LDS one k-step ahead (avq: the 16-row tile on v_mfma_f32_16x16x4_f32, rvq: the 3-row tile on v_mfma_f32_4x4x1_16b_f32).
 // ------------------------------------------------------------------------------------------
-// this lane's W_x1 operand of k-step 0, n-tile 0, and the one of k-step ks, n-tile n from there
-// (raw buffer loads with a scalar k-step offset would take the 64-bit pointer adds off the vector ALU, but this compiler
-//  lowers __builtin_amdgcn_raw_buffer_load_b128 to a one-dword load on gfx950: not used)
-__device__ __forceinline__ const float *pj_w_base(const float *wx1s, int kk, int wave, int j) {
-  return wx1s + ((size_t)kk * 192 + wave * 48 + j) * 4;
+// this lane's W_x1 operand of k-step ks, n-tile n: [ks][kk][192][4] floats, so its address is
+//     (wx1s + ks * PJ_KS_BYTES)  +  (kk * 192 + wave * 48 + j) * 16  +  n * 256
+//      uniform: a scalar pair,       32 bits, computed once            the load's immediate offset
+// i.e. global_load_dwordx4 v, v_lane, s[base:base+1] offset:256 n, the base advanced by s_add_u32 / s_addc_u32.  Left to
+// itself the compiler folds the lane part into a 64-bit vector pointer and advances THAT per k-step (the stride is past the
+// immediate's range): a v_add_co_u32 / v_addc_co_u32 pair and an s_nop between the MFMAs of 36 k-steps, at matrix-time prices
+// (profiles/EXPERIMENTS.md 19).  Two empty asm statements per k-step keep the parts apart - "+s" pins the base in scalar
+// registers, "+v" makes the lane offset a value of the k-step's own basic block, where instruction selection can see that it
+// is 32 bits wide - and the pointer says "global memory" outright, because behind the asm the compiler no longer knows where
+// it came from and would fall back to flat loads.  The loads themselves stay plain C++ (the compiler counts them in vmcnt).
+// (__builtin_amdgcn_raw_buffer_load_b128 would do the same with a scalar offset, but this compiler lowers it to a one-dword
+//  load on gfx950: not used)
+// PJ_W_LANE declares the kernel's two names (wb_0, wb_lane; kk, wave and j are the kernel's), PJ_W_KSTEP the base of one
+// k-step, PJ_W_LD is the load of one n-tile from it.
+#define PJ_KS_BYTES (4 * 192 * 16)
+typedef const __attribute__((address_space(1))) char *pj_gptr;
+typedef const __attribute__((address_space(1))) f32x4 *pj_gptr4;
+__device__ __forceinline__ float4 pj_w_ld(pj_gptr4 p) {
+  const f32x4 v = *p;
+  return make_float4(v.x, v.y, v.z, v.w);
 }
-__device__ __forceinline__ float4 pj_w_ld(const float *wb, int ks, int n) {
-  constexpr size_t KS_STRIDE = (size_t)4 * 192 * 4;
-  return *(const float4 *)(wb + ks * KS_STRIDE + n * 64);
-}
+#define PJ_W_LANE(wx1s_)                                                                             \
+  const pj_gptr wb_0 = (pj_gptr)(wx1s_);                                                             \
+  unsigned wb_lane = (unsigned)((kk * 192 + wave * 48 + j) * 16);
+#define PJ_W_KSTEP(wk_, ks_)                                                                         \
+  pj_gptr wk_ = wb_0 + (size_t)(ks_) * PJ_KS_BYTES;                                                  \
+  asm("" : "+s"(wk_));                                                                               \
+  asm("" : "+v"(wb_lane));
+#define PJ_W_LD(wk_, n_) pj_w_ld((pj_gptr4)(wk_ + wb_lane + (n_) * 256))
 // the ring's first DEPTH_ - 1 k-steps: requested in front of the barrier that completes feat (it does not wait for them)
 #define PJ_RING_PROLOGUE(DEPTH_)                                                                     \
-  _Pragma("unroll") for (int s2 = 0; s2 < DEPTH_ - 1; ++s2)                                          \
-    _Pragma("unroll") for (int n = 0; n < 3; ++n) bq[s2][n] = pj_w_ld(wb, s2, n);
+  _Pragma("unroll") for (int s2 = 0; s2 < DEPTH_ - 1; ++s2) {                                        \
+    PJ_W_KSTEP(wk, s2)                                                                               \
+    _Pragma("unroll") for (int n = 0; n < 3; ++n) bq[s2][n] = PJ_W_LD(wk, n);                        \
+  }
 // the biases of this lane's three columns: requested in front of the k-loop, added when the products are complete
 #define PJ_LOAD_BIAS(bv1_, bx1_)                                                                     \
   _Pragma("unroll") for (int n = 0; n < 3; ++n) bv1_[n] = (bx1_)[wave * 48 + n * 16 + j];
@@ -448,7 +469,8 @@ __device__ __forceinline__ float4 pj_w_ld(const float *wb, int ks, int n) {
 #define PJ_KLOOP(DEPTH_, G16_, G3_, ...)                                                             \
   _Pragma("unroll") for (int ks = 0; ks < 40; ++ks) {                                                \
     if (ks + DEPTH_ - 1 < 40) {                                                                      \
-      _Pragma("unroll") for (int n = 0; n < 3; ++n) bq[(ks + DEPTH_ - 1) % DEPTH_][n] = pj_w_ld(wb, ks + DEPTH_ - 1, n); \
+      PJ_W_KSTEP(wk, ks + DEPTH_ - 1)                                                                \
+      _Pragma("unroll") for (int n = 0; n < 3; ++n) bq[(ks + DEPTH_ - 1) % DEPTH_][n] = PJ_W_LD(wk, n); \
     }                                                                                                \
     if (ks + 1 < 40) { __VA_ARGS__ }                                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                               \
@@ -482,7 +504,9 @@ __device__ __forceinline__ float4 pj_w_ld(const float *wb, int ks, int n) {
 //      (lane = kk*16 + col), the A operand is feat[16 + lane%4][k + 4 kk ..], and the four kk partial sums of a
 //      column meet in two cross-lane adds at the very end - 20 rows of matrix time for 19 instead of 32.
 //      Each wave owns 3 of the 12 n-tiles over the whole K.  W_x1 (491 KB) streams from L2 straight into registers
-//      in B-operand order ([k/4][192][4], one contiguous KB per wave load), three k-steps ahead of its use.
+//      in B-operand order ([k/4][192][4], one contiguous KB per wave load), three k-steps ahead of its use, addressed as a
+//      scalar k-step base + one 32-bit lane offset + the n-tile as the load's immediate (PJ_W_KSTEP): between the projection's
+//      960 MFMAs a wave issues its loads and LDS reads and no vector ALU instruction.
 //   D  layer-1 recurrence (wave 0 forward, wave 1 backward); every wave's W_x2 operands (B-operand order) on their way
 //      from L2 into registers
 //   E  layer-2 input projection, the same 16 + 3 row split, A operand out of LDS
@@ -771,7 +795,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a)
   }
   __syncthreads();
   CF_STAMP(1)
-  const float *wb = pj_w_base(a.wx1s, kk, wave, j);
+  PJ_W_LANE(a.wx1s)
   float4 bq[4][3];
   // ---- B: conv -> feat (LDS).  Six m-tiles per wave (CV_TILE_LOOP), operand and store offsets from the staging (a_off, o_off)
   {
@@ -1068,7 +1092,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
       }
     }
   }
-  const float *wb = pj_w_base(a.wx1s, kk, wave, j);
+  PJ_W_LANE(a.wx1s)
   // W_x1 ring: with three rows the projection is bound by how many bytes of W are in flight, not by the matrix pipe
   // (3.8 k cycles of MFMAs against 491 KB per workgroup): CS_DEPTH - 1 k-steps ahead instead of the batch kernel's three
   float4 bq[CS_DEPTH][3];
@@ -1218,7 +1242,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
     CV_TILE_LOOP(5, if (i > 0) store_tile(i - 1, prev0, prev1);)
     store_tile(4, prev0, prev1);
   }
-  const float *wb = pj_w_base(a.wx1s, kk, wave, j);
+  PJ_W_LANE(a.wx1s)
   float4 bq[4][3];
   PJ_RING_PROLOGUE(4)
   __syncthreads();  // feat complete
