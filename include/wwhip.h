@@ -287,9 +287,10 @@ int ww_forward_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_me
  * sequence s has seg_nw[s] complete windows, window k of it covers rows [seg_row0[s] + k*hop, + window).
  * seg_row0 / seg_nw are HOST arrays; d_out receives the detect rows sequence by sequence.  This is the window loop of
  * utils/evaluate_models.py:66-88 over many files at once; for the CRNN the conv and the layer-1 projection of a time
- * position are computed once per sequence instead of once per window that contains it.  The host arrays are consumed before
- * the call returns; the kernels are enqueued like every _dev entry point's (the CRNN's launch descriptors travel through two
- * page-locked buffers of the context, so a caller can stage its next batch while this one computes). */
+ * position are computed once per sequence instead of once per window that contains it.  The host arrays are read before the
+ * call returns, for every model: the caller may free or overwrite them at once.  The kernels are enqueued like every _dev entry
+ * point's and the call waits for none of them unless a buffer of the context has to grow for it (its launch tables travel
+ * through two page-locked buffers of the context, so a caller can stage its next batch while this one computes). */
 int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
                             const int32_t *seg_nw, int32_t n_seg, int32_t hop, float *d_out);
 
@@ -312,7 +313,9 @@ int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *model, const float *d_m
  * mel row; post by sequence (an empty sequence's row is left as it is).  Every output may be NULL.  No limit on L: a long
  * sequence is cut into segments that run in parallel (WW_OPT_WAVE_SEQ_SEGMENT), with the same bits wherever the cuts fall.
  * WW_EINVAL for a CRNN, for a model in WW_PRECISION_BF16X3, n_seq < 0, pool_rows < 0 or descending offsets; n_seq = 0 and empty
- * sequences are no-ops.  The device form enqueues on the context's stream (row_offs is consumed before it returns). */
+ * sequences are no-ops.  The device form enqueues on the context's stream and does not synchronise it (but where one of the
+ * context's buffers has to grow for a call larger than any before): row_offs is read before the call returns, and the caller
+ * may free or overwrite it at once. */
 int ww_wave_sequence_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t total_rows, const int64_t *row_offs,
                          int32_t n_seq, int32_t pool_rows, float *d_enc, float *d_logits, float *d_post_frames, float *d_post);
 int ww_wave_sequence(ww_ctx *ctx, const ww_model *model, const float *mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,

@@ -38,6 +38,22 @@ int ww_ensure(ww_ctx *ctx, ww_arena &a, size_t bytes, bool pinned) {
   return WW_OK;
 }
 
+int ww_tables::send(ww_ctx *ctx, void *d_block) const {
+  if (bytes() == 0) return WW_OK;
+  const int slot = (int)(ctx->desc_k++ & 1);
+  if (!ctx->desc_ev[slot]) WW_HIP(ctx, hipEventCreateWithFlags(&ctx->desc_ev[slot], hipEventDisableTiming));
+  if (ctx->desc_busy[slot]) {
+    WW_HIP(ctx, hipEventSynchronize(ctx->desc_ev[slot]));
+    ctx->desc_busy[slot] = false;
+  }
+  if (int rc = ww_ensure(ctx, ctx->desc_pin[slot], bytes(), true)) return rc;
+  pack(ctx->desc_pin[slot].ptr);
+  WW_HIP(ctx, hipMemcpyAsync(d_block, ctx->desc_pin[slot].ptr, bytes(), hipMemcpyHostToDevice, ctx->stream));
+  WW_HIP(ctx, hipEventRecord(ctx->desc_ev[slot], ctx->stream));
+  ctx->desc_busy[slot] = true;
+  return WW_OK;
+}
+
 
 // Staging of a host-pointer call: the buffers its kernels read and write, carved in call order from one arena, and the bytes'
 // way in and out.  A call of more than WW_SMALL_IO_BYTES stages in the device arena (hipMemcpyAsync in, hipMemcpyAsync out, one
@@ -676,30 +692,21 @@ int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, 
   if (nw == 0) return WW_OK;
   if (nw > 0x7fffffff) return ww_fail(ctx, WW_EINVAL, "too many windows in one call");
   std::vector<int32_t> valid((size_t)nw, T);
-  const size_t b_rows = ww_bump::need((size_t)nw, 8), b_valid = ww_bump::need((size_t)nw, 4), b_ws = model_ws(m, chunk_of(nw));
-  int rc = ww_ensure(ctx, ctx->dev, b_rows + b_valid + b_ws + 1024, false);
+  ww_tables tb;
+  const size_t o_rows = tb.add(rows), o_valid = tb.add(valid), b_ws = model_ws(m, chunk_of(nw));
+  int rc = ww_ensure(ctx, ctx->dev, tb.bytes() + b_ws + 1024, false);
   if (rc) return rc;
   ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
-  int64_t *d_rows = bump.take<int64_t>((size_t)nw);
-  int32_t *d_valid = bump.take<int32_t>((size_t)nw);
+  char *d_tab = bump.take<char>(tb.bytes());
+  int64_t *d_rows = (int64_t *)(d_tab + o_rows);
+  int32_t *d_valid = (int32_t *)(d_tab + o_valid);
   void *ws = bump.take<char>(b_ws);
-  WW_HIP(ctx, hipMemcpyAsync(d_rows, rows.data(), (size_t)nw * 8, hipMemcpyHostToDevice, ctx->stream));
-  WW_HIP(ctx, hipMemcpyAsync(d_valid, valid.data(), (size_t)nw * 4, hipMemcpyHostToDevice, ctx->stream));
-  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host vectors go out of scope
+  if ((rc = tb.send(ctx, d_tab))) return rc;
   return forward_chunks(ctx, m, d_mel, mel_rows, d_rows, d_valid, 0, 0, nw, ws, d_out, nullptr, no_enc);
   WW_GUARD_END(ctx)
 }
 
 // ---- the Wavenet's sequence form (wavenet.hip: wavenet_seq_kernel) -----------------------------------------------------------
-// Device scratch of one call: the segment table, the device copy of row_offs, logits where the caller wants none, and the two
-// buffers of the pooled maximum
-struct wave_seq_plan {
-  std::vector<wv_seg> segs;
-  int64_t max_len = 0;
-  size_t b_segs = 0, b_offs = 0, b_z = 0, b_pool = 0;
-  size_t bytes() const { return b_segs + b_offs + b_z + 2 * b_pool; }
-};
-
 static int wave_seq_validate(ww_ctx *ctx, const ww_model *m, int64_t total_rows, const int64_t *row_offs, int32_t n_seq, int32_t pool_rows) {
   if (m->kind != WW_KIND_WAVENET)
     return ww_fail(ctx, WW_EINVAL, "ww_wave_sequence: Wavenet models only (a CRNN's bidirectional GRUs have no causal reading)");
@@ -715,44 +722,21 @@ static int wave_seq_validate(ww_ctx *ctx, const ww_model *m, int64_t total_rows,
   return WW_OK;
 }
 
-// Cuts: a sequence is computed in segments of G rows; every segment but a sequence's first starts RF - 1 rows early and drops them.
-// The library's G is ww_wave_segment_rows' (common.h), at least one chunk.
-static void wave_seq_make_plan(const ww_model *m, int64_t total_rows, const int64_t *row_offs, int n_seq, bool need_z, bool need_pool,
-                               wave_seq_plan &pl) {
-  const int rf = ww_wave_receptive_field(m), NO = m->info.n_out;
-  int64_t span = 0;
-  for (int s = 0; s < n_seq; ++s) {
-    span += row_offs[s + 1] - row_offs[s];
-    pl.max_len = std::max<int64_t>(pl.max_len, row_offs[s + 1] - row_offs[s]);
-  }
-  int64_t G = m->opt_wave_seq_segment;
-  if (G <= 0) G = std::max<int64_t>(ww_wave_segment_rows(span, rf), 192);
-  for (int s = 0; s < n_seq; ++s) {
-    const int64_t o = row_offs[s], len = row_offs[s + 1] - o;
-    for (int64_t s0 = 0; s0 < len; s0 += G) {
-      const int64_t warm = std::min<int64_t>(s0, rf - 1), rows = std::min<int64_t>(G, len - s0);
-      pl.segs.push_back({o + s0 - warm, (int32_t)(warm + rows), (int32_t)warm});
-    }
-  }
-  pl.b_segs = ww_bump::need(pl.segs.size(), sizeof(wv_seg));
-  pl.b_offs = ww_bump::need((size_t)n_seq + 1, 8);
-  pl.b_z = need_z ? ww_bump::need((size_t)total_rows * NO, 4) : 0;
-  pl.b_pool = need_pool ? ww_bump::need((size_t)total_rows * NO, 4) : 0;
-}
-
 static int wave_seq_run(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t total_rows, const int64_t *row_offs, int n_seq,
                         int pool_rows, float *d_enc, float *d_logits, float *d_pf, float *d_post, const wave_seq_plan &pl, ww_bump &bump) {
   if (pl.segs.empty()) return WW_OK;
   if (pl.segs.size() > 0x7fffffffu) return ww_fail(ctx, WW_EINVAL, "too many segments in one call");
   const int NO = m->info.n_out;
-  wv_seg *d_segs = bump.take<wv_seg>(pl.segs.size());
-  int64_t *d_offs = bump.take<int64_t>((size_t)n_seq + 1);
+  ww_tables tb;
+  const size_t o_segs = tb.add(pl.segs), o_offs = tb.add(row_offs, (size_t)n_seq + 1);
+  if (tb.bytes() != pl.b_segs + pl.b_offs) return ww_fail(ctx, WW_EINTERNAL, "wave_seq_run: the tables are not the size the plan reserved");
+  char *d_tab = bump.take<char>(tb.bytes());
+  const wv_seg *d_segs = (const wv_seg *)(d_tab + o_segs);
+  const int64_t *d_offs = (const int64_t *)(d_tab + o_offs);
   float *d_z = d_logits;
   if (!d_z && (d_pf || d_post)) d_z = bump.take<float>((size_t)total_rows * NO);
   float *d_a = d_pf ? bump.take<float>((size_t)total_rows * NO) : nullptr, *d_b = d_pf ? bump.take<float>((size_t)total_rows * NO) : nullptr;
-  WW_HIP(ctx, hipMemcpyAsync(d_segs, pl.segs.data(), pl.segs.size() * sizeof(wv_seg), hipMemcpyHostToDevice, ctx->stream));
-  WW_HIP(ctx, hipMemcpyAsync(d_offs, row_offs, ((size_t)n_seq + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host tables are the caller's / go out of scope
+  if (int rc = tb.send(ctx, d_tab)) return rc;
   int rc = ww_k_wave_sequence(ctx, m, d_mel, d_segs, (int)pl.segs.size(), d_enc, d_z);
   if (rc) return rc;
   if (d_pf || d_post) rc = ww_k_wave_pool(ctx, d_z, row_offs[n_seq] - row_offs[0], row_offs[n_seq], NO, d_offs, n_seq, pool_rows, pl.max_len, d_a, d_b, d_pf, d_post);
@@ -769,7 +753,8 @@ int ww_wave_sequence_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, int
   if (!d_enc && !d_logits && !d_post_frames && !d_post) return WW_OK;
   WW_ON_DEVICE(ctx, dev);
   wave_seq_plan pl;
-  wave_seq_make_plan(m, total_rows, row_offs, n_seq, !d_logits && (d_post_frames || d_post), d_post_frames != nullptr, pl);
+  wave_seq_make_plan(ww_wave_receptive_field(m), m->info.n_out, m->opt_wave_seq_segment, total_rows, row_offs, n_seq,
+                     !d_logits && (d_post_frames || d_post), d_post_frames != nullptr, pl);
   if (int rc = ww_ensure(ctx, ctx->dev, pl.bytes() + 1024, false)) return rc;
   ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
   return wave_seq_run(ctx, m, d_mel, total_rows, row_offs, n_seq, pool_rows, d_enc, d_logits, d_post_frames, d_post, pl, bump);
@@ -787,7 +772,8 @@ int ww_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t t
   WW_ON_DEVICE(ctx, dev);
   const int F = m->info.n_mel, NO = m->info.n_out, S = m->info.enc_width;
   wave_seq_plan pl;
-  wave_seq_make_plan(m, total_rows, row_offs, n_seq, !logits && (post_frames || post), post_frames != nullptr, pl);
+  wave_seq_make_plan(ww_wave_receptive_field(m), m->info.n_out, m->opt_wave_seq_segment, total_rows, row_offs, n_seq,
+                     !logits && (post_frames || post), post_frames != nullptr, pl);
   const size_t b_mel = ww_bump::need((size_t)total_rows * F, 4), b_enc = enc ? ww_bump::need((size_t)total_rows * S, 4) : 0;
   const size_t b_rows = ww_bump::need((size_t)total_rows * NO, 4), b_post = ww_bump::need((size_t)n_seq * NO, 4);
   if (int rc = ww_ensure(ctx, ctx->dev, b_mel + b_enc + 2 * b_rows + b_post + pl.bytes() + 1024, false)) return rc;

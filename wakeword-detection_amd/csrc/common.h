@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/wwhip.h"
+#include "launch_plan.h"
 #include "model_layout.h"
 
 #define WW_WAVE 64
@@ -46,8 +47,8 @@ struct ww_ctx {
     int64_t *d_so = nullptr, *d_fo = nullptr;
   };
   std::vector<clip_offs_t> clip_offs;
-  // host-built launch descriptors on their way to the device (ww_k_crnn_segments_forward): two page-locked buffers used
-  // alternately, each free again once the event behind its copies has passed - the call never waits for its kernels
+  // launch tables on their way to the device (ww_tables::send, the only code that touches these): two page-locked slots used
+  // alternately, each free again once the event behind its copy has passed
   ww_arena desc_pin[2];
   hipEvent_t desc_ev[2] = {nullptr, nullptr};
   bool desc_busy[2] = {false, false};
@@ -119,8 +120,6 @@ struct ww_model {
 
 int ww_fail(ww_ctx *ctx, int code, const char *fmt, ...);
 int ww_ensure(ww_ctx *ctx, ww_arena &a, size_t bytes, bool pinned);
-
-#define WW_NUM_CUS 256  // MI355X (gfx950): 8 XCDs x 32 CUs
 
 // No exception crosses the C ABI (every entry point returns a status, never throws): the body of every exported
 // function sits between WW_GUARD_BEGIN and WW_GUARD_END(ctx) - std::bad_alloc from a container or `new` becomes WW_ENOMEM,
@@ -204,19 +203,13 @@ struct ww_launch_scope {
   }
 };
 
-// bump allocator over the ctx workspace
-struct ww_bump {
-  char *base;
-  size_t off = 0, cap;
-  ww_bump(void *p, size_t c) : base((char *)p), cap(c) {}
-  template <typename T>
-  T *take(size_t n) {
-    size_t bytes = (n * sizeof(T) + 255) & ~size_t(255);
-    T *r = (T *)(base + off);
-    off += bytes;
-    return r;
-  }
-  static size_t need(size_t n, size_t elem) { return (n * elem + 255) & ~size_t(255); }
+// A call's launch tables (launch_plan.h: ww_table_block; ww_bump is there too) and their way to the device.  send() takes the
+// next of the context's two page-locked slots - waiting for the slot's event if its last copy is still in flight, growing it on
+// demand -, packs the block there, enqueues ONE copy to d_block (bytes() bytes of device memory) on the context's stream and
+// records the slot's event.  When it returns every registered array may be freed or overwritten, and the call has waited for no
+// kernel (but where the slot has to grow: ww_ensure): a _dev entry point never synchronises for its tables.
+struct ww_tables : ww_table_block {
+  int send(ww_ctx *ctx, void *d_block) const;  // api.hip
 };
 
 // A tick's posteriors as {value, tick number} pairs in page-locked host memory, each written with ONE 8-byte store by the head
@@ -278,42 +271,14 @@ int ww_k_posterior_pick(ww_ctx *ctx, const float *d_rows, int64_t n, int n_out, 
                         float *d_out);
 bool ww_wave_tick_capable(const ww_model *m, int n_streams);
 int ww_k_wave_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, const ww_tick_tag &tag);
-// The fp32 Wavenet's sequence form (wavenet.hip: wavenet_seq_kernel).  A segment = rows [row0, row0 + n) of the mel buffer, all of
-// one sequence; outputs of its first `skip` rows (the warm-up of a segment that does not start at its sequence's row 0) are
-// discarded.
-struct wv_seg {
-  int64_t row0;
-  int32_t n, skip;
-};
+// The fp32 Wavenet's sequence form (wavenet.hip: wavenet_seq_kernel) over launch_plan.h's segments (wv_seg).
 int ww_wave_receptive_field(const ww_model *m);  // 1 + 2 * sum of the dilations
-// The library's segment length for `rows` rows of work (WW_OPT_WAVE_SEQ_SEGMENT = 0), for ww_wave_sequence and the stream feed
-// alike; each clamps it to what its cuts need.  A segment's warm-up (rf - 1 rows) + its rows are a whole number of 192-row chunks:
-// about two segments per CU once there is enough work, 10 chunks at least (warm-up: a tenth of the rows at most) and 64 at most.
-static inline int64_t ww_wave_segment_rows(int64_t rows, int rf) {
-  int64_t chunks = (rows + 2 * WW_NUM_CUS * 192 - 1) / (2 * WW_NUM_CUS * 192);
-  chunks = chunks < 10 ? 10 : chunks > 64 ? 64 : chunks;
-  return chunks * 192 - (rf - 1);
-}
 int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const wv_seg *d_segs, int n_segs, float *d_enc, float *d_logits);
 // rows = offs[n_seq] - offs[0] (the rows that belong to a sequence), row_end = offs[n_seq]
 int ww_k_wave_pool(ww_ctx *ctx, const float *d_z, int64_t rows, int64_t row_end, int n_out, const int64_t *d_offs, int n_seq, int64_t pool_rows,
                    int64_t max_len, float *d_a, float *d_b, float *d_pf, float *d_post);
 #define WW_WAVE_STATE_BLOCK 256  // floats of carried state per block and stream: [4 channel groups][16 rows][4]
-// A causal bank's feed (streams.hip: ww_stream_feed): the sequence form over the rows a call brought, stream by stream.  A segment
-// is rows [row0, row0 + n) of the call's row buffer, all of one stream; bit 0 of flags: its history comes from the stream's state
-// (the stream's first segment; the others start RF - 1 rows early from zeros and drop `skip` rows), bit 1: its history goes back
-// there (the stream's last segment).
-struct wv_feed_seg {
-  int64_t row0;
-  int32_t n, skip, sid, flags;
-};
-// the pooled maxima of a stream that brought more rows than one tile: rows [k0, k0 + 256) of its n new rows, which start at row0
-struct wv_feed_pool {
-  int64_t row0;
-  int32_t n, sid, k0, pad;
-};
-#define WW_FEED_TILE_ROWS 16   // up to here a stream's new rows are one tile of the one-wave form, tail included
-#define WW_FEED_POOL_ROWS 256  // rows per workgroup of wave_feed_pool_kernel
+// A causal bank's feed (streams.hip: ww_stream_feed) over launch_plan.h's tables (wv_feed_seg, wv_feed_pool):
 // segs[0, n_small): one-wave form (posteriors, ring and state inside the kernel); segs[n_small, n_segs): twelve-wave form, logits to
 // d_z, then pool[n_pool] -> d_post and ring[n_ring] (one entry per such stream) -> the logit rings
 int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv_feed_seg *d_segs, int n_small, int n_segs,

@@ -1154,12 +1154,7 @@ struct rows_args {
   float *out[3];       // [count][192] per kind (b_x included)
   int64_t start[3];    // mel row of position 0's field (may lie outside the sequence: rows outside read as zeros)
   int stride[3], count[3], tiles[3];
-  const struct rows_tile *desc;  // or: one descriptor per workgroup (several sequences in one buffer: ww_k_crnn_segments_forward)
-};
-struct rows_tile {
-  int64_t start;    // mel row of the tile's first field
-  int64_t out_row;  // row of out[kind] its first position goes to
-  int32_t stride, count, kind, pad;
+  const rows_tile *desc;  // or: one descriptor per workgroup (launch_plan.h; several sequences in one buffer: ww_k_crnn_segments_forward)
 };
 
 __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
@@ -2182,7 +2177,6 @@ static void launch_tail(ww_ctx *ctx, const ww_model *m, const tail_args &t, int 
 // Regular sliding windows (hop <= 8 over one mel sequence, every window complete) take crnn_rows_kernel + gru_tail_kernel from
 // this many windows on (ww_model_set_option(WW_OPT_CRNN_SLIDE_MIN): 0 = never).
 static int crnn_slide_min(const ww_model *m) { return m->opt_slide_min > 0 ? m->opt_slide_min : 0x7fffffff; }
-static int gcd8(int hop) { return hop % 8 == 0 ? 8 : hop % 4 == 0 ? 4 : hop % 2 == 0 ? 2 : 1; }
 
 // crnn_rows_kernel's arguments but for its position lists (start / stride / count / tiles, or desc): the three output lists are
 // interior fields, left edges, right edges
@@ -2214,68 +2208,31 @@ bool ww_crnn_segments_capable(const ww_model *m, int hop) {
 int ww_k_crnn_segments_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
                                const int32_t *seg_nw, int n_seg, int hop, float *d_out) {
   const ww_crnn_dev &c = m->crnn;
-  const int g = gcd8(hop);
-  // groups of whole sequences of at most ~WW_SEG_GROUP windows bound the workspace
-  constexpr int64_t WW_SEG_GROUP = 32768;
-  std::vector<rows_tile> tiles;
-  std::vector<int64_t> i0;
+  const int g = crnn_gcd8(hop);
+  crnn_seg_group gp;  // launch_plan.h: groups of whole sequences of at most ~WW_SEG_GROUP windows bound the workspace
   int64_t w_done = 0;
-  for (int s0 = 0; s0 < n_seg;) {
-    tiles.clear();
-    i0.clear();
-    int64_t nI = 0, nW = 0;
-    int s1 = s0;
-    for (; s1 < n_seg && (s1 == s0 || nW + seg_nw[s1] <= WW_SEG_GROUP); ++s1) {
-      const int nw = seg_nw[s1];
-      if (nw < 0) return ww_fail(ctx, WW_EINVAL, "negative window count in sequence %d", s1);
-      if (nw == 0) continue;
-      const int64_t r0 = seg_row0[s1];
-      if (r0 < 0 || r0 + (int64_t)(nw - 1) * hop + c.T > mel_rows)
-        return ww_fail(ctx, WW_EINVAL, "sequence %d: windows leave the mel buffer", s1);
-      const int64_t n_int = ((int64_t)(nw - 1) * hop + 128) / g + 1;
-      for (int64_t p0 = 0; p0 < n_int; p0 += 16)
-        tiles.push_back({r0 + 2 + (int64_t)g * p0, nI + p0, g, (int32_t)(n_int - p0 < 16 ? n_int - p0 : 16), 0, 0});
-      for (int p0 = 0; p0 < nw; p0 += 16) {
-        const int32_t cnt = nw - p0 < 16 ? nw - p0 : 16;
-        tiles.push_back({r0 - c.PT + (int64_t)hop * p0, nW + p0, hop, cnt, 1, 0});
-        tiles.push_back({r0 + (int64_t)(c.OT - 1) * c.ST - c.PT + (int64_t)hop * p0, nW + p0, hop, cnt, 2, 0});
-      }
-      for (int k = 0; k < nw; ++k) i0.push_back(nI + (int64_t)k * hop / g);
-      nI += n_int;
-      nW += nw;
-    }
+  for (int s0 = 0; s0 < n_seg; s0 = gp.next) {
+    if (int rc = crnn_plan_group(seg_row0, seg_nw, n_seg, hop, c.T, c.PT, c.OT, c.ST, mel_rows, s0, gp)) return ww_fail(ctx, rc, "%s", gp.err);
+    const int64_t nI = gp.nI, nW = gp.nW;
     if (nW > 0) {
-      const size_t b_tiles = ww_bump::need(tiles.size() * sizeof(rows_tile), 1), b_i0 = ww_bump::need(i0.size() * 8, 1);
+      ww_tables tb;
+      const size_t o_tiles = tb.add(gp.tiles), o_i0 = tb.add(gp.i0);
       const size_t b_rows = ww_bump::need((size_t)(nI + 2 * nW) * 6 * c.H, 4);
-      int rc = ww_ensure(ctx, ctx->dev, b_tiles + b_i0 + b_rows + tail_seq_bytes((int)nW) + 8192, false);
+      int rc = ww_ensure(ctx, ctx->dev, tb.bytes() + b_rows + tail_seq_bytes((int)nW) + 8192, false);
       if (rc) return rc;
       ww_bump b(ctx->dev.ptr, ctx->dev.cap);
-      rows_tile *d_tiles = (rows_tile *)b.take<char>(tiles.size() * sizeof(rows_tile));
-      int64_t *d_i0 = b.take<int64_t>(i0.size());
+      char *d_tab = b.take<char>(tb.bytes());
+      const rows_tile *d_tiles = (const rows_tile *)(d_tab + o_tiles);
+      const int64_t *d_i0 = (const int64_t *)(d_tab + o_i0);
       float *gI = b.take<float>((size_t)nI * 6 * c.H), *gL = b.take<float>((size_t)nW * 6 * c.H), *gR = b.take<float>((size_t)nW * 6 * c.H);
       float *seq = (float *)b.take<char>(tail_seq_bytes((int)nW));
-      // the descriptors leave through one of the context's two page-locked buffers: the copies are asynchronous and the call
-      // goes on to build the next group (or returns) while this group's kernels run
-      const int slot = (int)(ctx->desc_k++ & 1);
-      if (!ctx->desc_ev[slot]) WW_HIP(ctx, hipEventCreateWithFlags(&ctx->desc_ev[slot], hipEventDisableTiming));
-      if (ctx->desc_busy[slot]) {
-        WW_HIP(ctx, hipEventSynchronize(ctx->desc_ev[slot]));
-        ctx->desc_busy[slot] = false;
-      }
-      const size_t n_t = tiles.size() * sizeof(rows_tile), n_i = i0.size() * 8, o_i = (n_t + 63) & ~(size_t)63;
-      if ((rc = ww_ensure(ctx, ctx->desc_pin[slot], o_i + n_i, true))) return rc;
-      char *hp = (char *)ctx->desc_pin[slot].ptr;
-      memcpy(hp, tiles.data(), n_t);
-      memcpy(hp + o_i, i0.data(), n_i);
-      WW_HIP(ctx, hipMemcpyAsync(d_tiles, hp, n_t, hipMemcpyHostToDevice, ctx->stream));
-      WW_HIP(ctx, hipMemcpyAsync(d_i0, hp + o_i, n_i, hipMemcpyHostToDevice, ctx->stream));
-      WW_HIP(ctx, hipEventRecord(ctx->desc_ev[slot], ctx->stream));
-      ctx->desc_busy[slot] = true;
+      // the call goes on to build the next group (or returns) while this group's kernels run
+      if ((rc = tb.send(ctx, d_tab))) return rc;
       rows_args r = rows_args_of(c, d_mel, mel_rows, gI, gL, gR);
       r.desc = d_tiles;
       {
         ww_launch_scope scope(ctx, "crnn_rows_kernel");
-        hipLaunchKernelGGL(crnn_rows_kernel, dim3((unsigned)tiles.size()), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r);
+        hipLaunchKernelGGL(crnn_rows_kernel, dim3((unsigned)gp.tiles.size()), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r);
       }
       tail_args t = crnn_tail_args(c);
       t.gxI = gI; t.gxL = gL; t.gxR = gR;
@@ -2285,7 +2242,6 @@ int ww_k_crnn_segments_forward(ww_ctx *ctx, const ww_model *m, const float *d_me
       WW_HIP(ctx, hipGetLastError());
       w_done += nW;
     }
-    s0 = s1;
   }
   return WW_OK;
 }
@@ -2331,8 +2287,8 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
   // (also in split-bf16 mode: the mode permits bf16 products, and computing a seventh of them in fp32 is both faster and closer)
   if (slide_form) {
     // windows sliding over one sequence: 1 + 2 positions per window instead of 19 (crnn_rows_kernel)
-    const int g = gcd8(hop);
-    const int64_t n_int = ((int64_t)(nw - 1) * hop + 128) / g + 1;
+    const int g = crnn_gcd8(hop);
+    const int64_t n_int = crnn_n_int(nw, hop);
     ww_bump b(ws, ws_bytes);
     float *gI = b.take<float>((size_t)n_int * 6 * c.H), *gL = b.take<float>((size_t)nw * 6 * c.H), *gR = b.take<float>((size_t)nw * 6 * c.H);
     float *seq = (float *)b.take<char>(tail_seq_bytes(nw));

@@ -21,35 +21,15 @@
 #include <cmath>
 
 #define RS_THREADS 256
-#define RS_XCAP WW_RESAMPLE_MAX_SPAN  // floats of staged input per tile (48 KB: three workgroups per CU)
-#define RS_R 8                        // outputs per item, phase form
-#define RS_R1 7                       // outputs per lane, up == 1 form: odd, so that the lane stride RS_R1 * down keeps odd `down` conflict-free
 #define RS_UNROLL1 4                  // window positions per unrolled step of the up == 1 form (the table is padded to it)
-#define RS_COPY 4096                  // outputs per tile of the identity form
+// (tile descriptor rs_tile, RS_XCAP / RS_R / RS_R1 / RS_COPY and the tile plans: launch_plan.h)
 
-struct rs_tile {
-  int64_t in_off;     // index in the input buffer of the segment's first sample
-  int64_t in_first;   // absolute index of that sample in its signal
-  int64_t n_in;       // samples of the segment
-  int64_t out_off;    // index in the output buffer of output out_first
-  int64_t out_first;  // absolute index of the segment's first output
-  int64_t out_end;    // one past its last
-  int64_t k_lo;       // absolute index of staged sample 0
-  int64_t first;      // phase form: first item; up == 1 and identity forms: first output
-  int32_t n_x;        // staged samples (<= RS_XCAP)
-  int32_t n;          // phase form: items; up == 1 form: lanes; identity form: outputs
-};
-
-struct ww_resampler {
+struct ww_resampler : rs_geom {
   ww_ctx *ctx = nullptr;
   int32_t rate_in = 0, rate_out = 0;
-  int64_t up = 1, down = 1, half = 0, tpp = 0, dinv = 0;
-  bool identity = false;
+  int64_t dinv = 0;
   float *d_taps = nullptr;  // [tpp][up] tap-major
   float *d_h2 = nullptr;    // up == 1: [n_u][8], row u = the taps of outputs r = 0 .. RS_R1 - 1 at window position u
-  int32_t n_u = 0;          // rows of d_h2 (a multiple of RS_UNROLL1)
-  int32_t lanes1 = 0;       // up == 1 form: lanes per tile (0: the form does not fit, the phase form runs)
-  int32_t ne8 = 0, ne1 = 0; // phase form: items per tile for R = 8 (0: does not fit) and R = 1
   size_t table_bytes = 0;
 };
 
@@ -177,77 +157,10 @@ static int64_t rs_inverse(int64_t a, int64_t n) {  // a^-1 mod n, gcd(a, n) = 1
   return t < 0 ? t + n : t;
 }
 
-static int64_t rs_out_len(const ww_resampler *r, int64_t n) {  // ceil(n * up / down)
-  return (int64_t)(((__int128)n * r->up + r->down - 1) / r->down);
-}
-
-// worst-case staged samples of a phase-form tile of ne items
-static int64_t rs_phase_span(const ww_resampler *r, int R, int64_t ne) {
-  const int64_t nA = (ne - 1) / r->up + 2;
-  return nA * R * r->down + r->tpp + 2;
-}
-
 template <typename K, typename... Args>
 static void rs_launch(ww_ctx *ctx, const char *name, K kernel, size_t n_tiles, Args... args) {
   ww_launch_scope scope(ctx, name);
   hipLaunchKernelGGL(kernel, dim3((unsigned)n_tiles), dim3(RS_THREADS), 0, ctx->stream, args...);
-}
-
-struct rs_plan {
-  std::vector<rs_tile> copy, decim, ph8, ph1;
-  size_t count() const { return copy.size() + decim.size() + ph8.size() + ph1.size(); }
-};
-
-static void rs_plan_phase(const ww_resampler *r, int R, int64_t ne, rs_tile base, std::vector<rs_tile> &dst) {
-  const int64_t up = r->up, down = r->down, J = r->half / up, Jmin = (r->half - up + 1) / up;
-  const int64_t e_lo = ((base.out_first / up) / R) * up, e_hi = (((base.out_end - 1) / up) / R + 1) * up;
-  for (int64_t e0 = e_lo; e0 < e_hi; e0 += ne) {
-    const int64_t n = std::min(ne, e_hi - e0), A0 = e0 / up, A1 = (e0 + n - 1) / up;
-    rs_tile t = base;
-    t.first = e0;
-    t.n = (int32_t)n;
-    t.k_lo = A0 * R * down - J;
-    t.n_x = (int32_t)((A1 * R + R - 1) * down + (down - 1) - Jmin + r->tpp - t.k_lo);
-    dst.push_back(t);
-  }
-}
-
-static int rs_make_plan(const ww_resampler *r, const int64_t *so, const int64_t *in_first, const int64_t *out_first, const int64_t *oo,
-                        int n_seg, rs_plan &pl) {
-  for (int u = 0; u < n_seg; ++u) {
-    const int64_t cnt = oo[u + 1] - oo[u];
-    if (cnt <= 0) continue;
-    rs_tile b = {};
-    b.in_off = so[u];
-    b.in_first = in_first ? in_first[u] : 0;
-    b.n_in = so[u + 1] - so[u];
-    b.out_off = oo[u];
-    b.out_first = out_first ? out_first[u] : 0;
-    b.out_end = b.out_first + cnt;
-    if (r->identity) {
-      for (int64_t m = b.out_first; m < b.out_end; m += RS_COPY) {
-        rs_tile t = b;
-        t.first = m;
-        t.n = (int32_t)std::min<int64_t>(RS_COPY, b.out_end - m);
-        pl.copy.push_back(t);
-      }
-    } else if (r->up == 1 && r->lanes1 > 0) {
-      const int64_t per = (int64_t)r->lanes1 * RS_R1;
-      for (int64_t m = b.out_first; m < b.out_end; m += per) {
-        rs_tile t = b;
-        t.first = m;
-        t.n = (int32_t)std::min<int64_t>(r->lanes1, (b.out_end - m + RS_R1 - 1) / RS_R1);
-        t.k_lo = m * r->down - r->half;
-        t.n_x = (int32_t)((int64_t)(t.n - 1) * RS_R1 * r->down + r->n_u);
-        pl.decim.push_back(t);
-      }
-    } else if (r->ne8 > 0 && cnt >= 2 * RS_R * r->up) {
-      rs_plan_phase(r, RS_R, r->ne8, b, pl.ph8);
-    } else {
-      rs_plan_phase(r, 1, r->ne1, b, pl.ph1);
-    }
-  }
-  return WW_OK;
 }
 
 static int rs_validate(const ww_resampler *r, const void *in, int in_fmt, const int64_t *so, const int64_t *in_first, const int64_t *out_first,
@@ -294,27 +207,15 @@ static void rs_launch_all(const ww_resampler *r, const rs_plan &pl, const rs_til
               (int)r->up, (int)r->down, (int)r->half, (int)r->tpp, (int)r->dinv);
 }
 
-// the tile table leaves through one of the context's two page-locked descriptor buffers (as ww_k_crnn_segments_forward's): the
-// copy is asynchronous and the call returns while its kernels run
+// the four tile lists are one table, in rs_launch_all's order
 static int rs_run(const ww_resampler *r, const rs_plan &pl, rs_tile *d_tiles, const void *d_in, int in_fmt, void *d_out, int out_fmt) {
   ww_ctx *ctx = r->ctx;
-  const int slot = (int)(ctx->desc_k++ & 1);
-  if (!ctx->desc_ev[slot]) WW_HIP(ctx, hipEventCreateWithFlags(&ctx->desc_ev[slot], hipEventDisableTiming));
-  if (ctx->desc_busy[slot]) {
-    WW_HIP(ctx, hipEventSynchronize(ctx->desc_ev[slot]));
-    ctx->desc_busy[slot] = false;
-  }
-  const size_t bytes = pl.count() * sizeof(rs_tile);
-  if (int rc = ww_ensure(ctx, ctx->desc_pin[slot], bytes, true)) return rc;
-  char *hp = (char *)ctx->desc_pin[slot].ptr;
-  size_t off = 0;
-  for (const std::vector<rs_tile> *v : {&pl.copy, &pl.decim, &pl.ph8, &pl.ph1}) {
-    if (!v->empty()) memcpy(hp + off, v->data(), v->size() * sizeof(rs_tile));
-    off += v->size() * sizeof(rs_tile);
-  }
-  WW_HIP(ctx, hipMemcpyAsync(d_tiles, hp, bytes, hipMemcpyHostToDevice, ctx->stream));
-  WW_HIP(ctx, hipEventRecord(ctx->desc_ev[slot], ctx->stream));
-  ctx->desc_busy[slot] = true;
+  ww_tables tb;
+  tb.add(pl.copy);
+  tb.join(pl.decim);
+  tb.join(pl.ph8);
+  tb.join(pl.ph1);
+  if (int rc = tb.send(ctx, d_tiles)) return rc;
   if (in_fmt == WW_SAMPLE_I16 && out_fmt == WW_SAMPLE_F32) rs_launch_all(r, pl, d_tiles, (const int16_t *)d_in, (float *)d_out);
   else if (in_fmt == WW_SAMPLE_F32 && out_fmt == WW_SAMPLE_F32) rs_launch_all(r, pl, d_tiles, (const float *)d_in, (float *)d_out);
   else if (in_fmt == WW_SAMPLE_I16) rs_launch_all(r, pl, d_tiles, (const int16_t *)d_in, (int16_t *)d_out);
@@ -437,7 +338,7 @@ int ww_resample_dev(ww_resampler *r, const void *d_in, int32_t in_format, const 
   WW_ON_DEVICE(ctx, dev);
   rs_plan pl;
   rs_make_plan(r, sample_offs, in_first, out_first, out_offs, n_seg, pl);
-  if (int rc = ww_ensure(ctx, ctx->dev, pl.count() * sizeof(rs_tile) + 1024, false)) return rc;
+  if (int rc = ww_ensure(ctx, ctx->dev, ww_bump::need(pl.count(), sizeof(rs_tile)) + 1024, false)) return rc;
   ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
   return rs_run(r, pl, bump.take<rs_tile>(pl.count()), d_in, in_format, d_out, out_format);
   WW_GUARD_END(r ? r->ctx : nullptr)

@@ -32,7 +32,6 @@
 #include <time.h>
 
 #define ST_RING WW_ST_RING  // 511 + 320 rounded up
-#define WV_FEED_HIST_ROWS 16  // rows of BatchNorm output a block carries (wavenet.hip: WV_PAD)
 #define ST_WL_BYTES (((WW_MEL_TAPS * 64 * 4 + 2047) / 2048) * 2048)  // the mel weights in LDS, padded to whole rounds of 128 x 16 bytes
 
 struct ww_streams {
@@ -214,18 +213,9 @@ __global__ __launch_bounds__(128) void stream_frontend_kernel(stream_fe_args a) 
 // The stream's state (pending samples, carry) is written by the stream's FIRST group (the only one when the packet completes no
 // frame): pending samples are fewer than 512, so only frames 0..3 - the first group's - reach into them, and the carry belongs to
 // the packet's first sample, which frame 0 covers.  The one reader being the one writer, the groups of a stream need no order.
-#define FEED_GROUP 16
 #define FEED_WAVES 4
 #define FEED_X (512 + (FEED_GROUP - 1) * 160)
-struct feed_str {       // a stream of the call
-  int64_t s_off;        // its packet's first sample in the call's sample buffer
-  int64_t k;            // samples in the packet
-  int64_t r_off;        // its first new row in the call's row buffer
-  int32_t sid, fill, rows, pos;
-};
-struct feed_grp {
-  int32_t i, f0, nf, pad;  // stream of the call, first frame, frames (0: the stream's state only)
-};
+// (FEED_GROUP and the tables feed_str - a stream of the call - and feed_grp: launch_plan.h)
 struct feed_fe_args {
   const int16_t *pcm;
   const feed_str *str;
@@ -758,22 +748,6 @@ int ww_stream_feed_rows(ww_streams *st, const int32_t *ids, int32_t n, const int
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
-// The cuts of a stream that brought more rows than one tile.  Segments of G rows as ww_wave_sequence cuts them,
-// with two differences: a segment that is not the stream's first needs its whole warm-up inside the call's row buffer (the rows in
-// front of the call's first row are gone), hence G >= RF - 1; and the stream's history is taken from its last segment, whose 16
-// rows per block are the uncut evaluation's only after RF - 1 + 16 rows from zeros: a last segment that keeps fewer than 16 rows
-// is merged into the one before it.
-static void feed_cut(std::vector<wv_feed_seg> &segs, int64_t r_off, int64_t rows, int sid, int64_t G, int rf) {
-  for (int64_t s0 = 0; s0 < rows; s0 += G) {
-    int64_t len = std::min<int64_t>(G, rows - s0);
-    if (rows - (s0 + len) < WV_FEED_HIST_ROWS && rows - (s0 + len) > 0) len = rows - s0;  // (the next one would be too short to carry the history)
-    const int64_t warm = s0 ? rf - 1 : 0;
-    segs.push_back({r_off + s0 - warm, (int32_t)(warm + len), (int32_t)warm, sid, s0 ? 0 : 1});
-    if (s0 + len >= rows) break;
-  }
-  segs.back().flags |= 2;
-}
-
 static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const int16_t *pcm, const int64_t *sample_offs, int64_t cap_rows,
                             int64_t *row_offs, float *post, float *mel, bool *mutated) {
   ww_ctx *ctx = st->ctx;
@@ -787,62 +761,30 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
   const int T = st->T, F = st->F, NO = st->NO, R = T + 1, hop = st->fp.hop, rf = ww_wave_receptive_field(m);
   if ((size_t)(WW_FEED_POOL_ROWS + T - 1) * 64 > 64 * 1024) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: windows of up to %d rows only", 1024 - WW_FEED_POOL_ROWS + 1);
   WW_ON_DEVICE(ctx, dev_scope);
-  // ---- the plan: streams, front-end groups, model segments (one-wave form first), the twelve-wave form's tail
-  std::vector<feed_str> str((size_t)n);
-  std::vector<feed_grp> grp;
-  std::vector<wv_feed_seg> small, large;
-  std::vector<wv_feed_pool> pool, ringt;
-  int64_t large_rows = 0;
-  for (int i = 0; i < n; ++i) {
-    const int64_t r = row_offs[i + 1] - row_offs[i];
-    if (r > WW_FEED_TILE_ROWS || r > T) large_rows += r;
-  }
-  int64_t G = m->opt_wave_seq_segment;
-  if (G <= 0) G = ww_wave_segment_rows(large_rows, rf);
-  G = std::min<int64_t>(std::max<int64_t>(G, std::max(rf - 1, 1)), 1 << 30);
-  for (int i = 0; i < n; ++i) {
-    const int s = ids[i];
-    const int64_t k = sample_offs[i + 1] - sample_offs[i], r = row_offs[i + 1] - row_offs[i];
-    str[i] = {sample_offs[i] - sample_offs[0], k, row_offs[i], s, st->fill[s], (int32_t)r, st->pos[s]};
-    if (k == 0) continue;  // an empty packet: the stream stands still
-    if (r == 0) grp.push_back({i, 0, 0, 0});
-    for (int64_t f0 = 0; f0 < r; f0 += FEED_GROUP) grp.push_back({i, (int32_t)f0, (int32_t)std::min<int64_t>(FEED_GROUP, r - f0), 0});
-    if (r == 0) continue;
-    if (r <= WW_FEED_TILE_ROWS && r <= T) {
-      small.push_back({row_offs[i], (int32_t)r, 0, s, 3});
-    } else {
-      feed_cut(large, row_offs[i], r, s, G, rf);
-      for (int64_t k0 = 0; k0 < r; k0 += WW_FEED_POOL_ROWS) pool.push_back({row_offs[i], (int32_t)r, s, (int32_t)k0, 0});
-      ringt.push_back({row_offs[i], (int32_t)r, s, 0, 0});
-    }
-  }
+  feed_plan pl;  // launch_plan.h
+  feed_make_plan(ids, n, sample_offs, row_offs, st->fill.data(), st->pos.data(), T, rf, m->opt_wave_seq_segment, pl);
+  const std::vector<feed_grp> &grp = pl.grp;
+  const std::vector<wv_feed_seg> &small = pl.small, &large = pl.large;
   if (grp.size() > 0x7fffffffu || small.size() + large.size() > 0x7fffffffu) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: too much work for one call");
-  // ---- the call's scratch: [tables | samples | mel rows | logits | posteriors] in the context's workspace, the tables' host copy
-  //      in its page-locked arena
-  const size_t b_str = ww_bump::need(str.size(), sizeof(feed_str)), b_grp = ww_bump::need(grp.size(), sizeof(feed_grp)),
-               b_seg = ww_bump::need(small.size() + large.size(), sizeof(wv_feed_seg)), b_pool = ww_bump::need(pool.size(), sizeof(wv_feed_pool)),
-               b_ring = ww_bump::need(ringt.size(), sizeof(wv_feed_pool));
-  const size_t b_tab = b_str + b_grp + b_seg + b_pool + b_ring;
+  // ---- the call's scratch: [tables | samples | mel rows | logits | posteriors] in the context's workspace
+  ww_tables tb;
+  const size_t o_str = tb.add(pl.str), o_grp = tb.add(grp), o_seg = tb.add(small);
+  tb.join(large);  // one table: the one-wave form's segments, then the twelve-wave form's
+  const size_t o_pool = tb.add(pl.pool), o_ring = tb.add(pl.ringt);
   const size_t b_pcm = ww_bump::need((size_t)samples, 2), b_rows = ww_bump::need((size_t)rows * F, 4), b_z = ww_bump::need((size_t)rows * NO, 4),
                b_post = ww_bump::need((size_t)rows, 4);
-  if (int rc = ww_ensure(ctx, ctx->pinned, b_tab + 1024, true)) return rc;
-  if (int rc = ww_ensure(ctx, ctx->dev, b_tab + b_pcm + b_rows + (large.empty() ? 0 : b_z) + b_post + 1024, false)) return rc;
-  ww_bump hb(ctx->pinned.ptr, ctx->pinned.cap), db(ctx->dev.ptr, ctx->dev.cap);
-  feed_str *h_str = hb.take<feed_str>(str.size()), *d_str = db.take<feed_str>(str.size());
-  feed_grp *h_grp = hb.take<feed_grp>(grp.size()), *d_grp = db.take<feed_grp>(grp.size());
-  wv_feed_seg *h_seg = hb.take<wv_feed_seg>(small.size() + large.size()), *d_seg = db.take<wv_feed_seg>(small.size() + large.size());
-  wv_feed_pool *h_pool = hb.take<wv_feed_pool>(pool.size()), *d_pool = db.take<wv_feed_pool>(pool.size());
-  wv_feed_pool *h_ringt = hb.take<wv_feed_pool>(ringt.size()), *d_ringt = db.take<wv_feed_pool>(ringt.size());
+  if (int rc = ww_ensure(ctx, ctx->dev, tb.bytes() + b_pcm + b_rows + (large.empty() ? 0 : b_z) + b_post + 1024, false)) return rc;
+  ww_bump db(ctx->dev.ptr, ctx->dev.cap);
+  char *d_tab = db.take<char>(tb.bytes());
+  const feed_str *d_str = (const feed_str *)(d_tab + o_str);
+  const feed_grp *d_grp = (const feed_grp *)(d_tab + o_grp);
+  const wv_feed_seg *d_seg = (const wv_feed_seg *)(d_tab + o_seg);
+  const wv_feed_pool *d_pool = (const wv_feed_pool *)(d_tab + o_pool), *d_ringt = (const wv_feed_pool *)(d_tab + o_ring);
   int16_t *d_pcm = db.take<int16_t>((size_t)samples);
   float *d_rows = db.take<float>((size_t)rows * F);
   float *d_z = large.empty() ? nullptr : db.take<float>((size_t)rows * NO);
   float *d_post = db.take<float>((size_t)rows);
-  if (!str.empty()) memcpy(h_str, str.data(), str.size() * sizeof(feed_str));
-  if (!grp.empty()) memcpy(h_grp, grp.data(), grp.size() * sizeof(feed_grp));
-  if (!small.empty()) memcpy(h_seg, small.data(), small.size() * sizeof(wv_feed_seg));
-  if (!large.empty()) memcpy(h_seg + small.size(), large.data(), large.size() * sizeof(wv_feed_seg));
-  if (!pool.empty()) memcpy(h_pool, pool.data(), pool.size() * sizeof(wv_feed_pool));
-  if (!ringt.empty()) memcpy(h_ringt, ringt.data(), ringt.size() * sizeof(wv_feed_pool));
+  if (int rc = tb.send(ctx, d_tab)) return rc;
   // ---- from here on the host's mirrors of the streams' state advance
   *mutated = true;
   for (int i = 0; i < n; ++i) {
@@ -851,7 +793,6 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
     st->fill[s] = (int)(st->fill[s] + k - r * hop);
     st->pos[s] = (int)((st->pos[s] + r) % R);
   }
-  WW_HIP(ctx, hipMemcpyAsync(d_str, h_str, b_tab, hipMemcpyHostToDevice, ctx->stream));  // (the tables are one block on both sides)
   WW_HIP(ctx, hipMemcpyAsync(d_pcm, pcm + sample_offs[0], (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
   feed_fe_args a = {};
   a.pcm = d_pcm; a.str = d_str; a.grp = d_grp; a.rows = d_rows;
@@ -868,8 +809,8 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
     WW_HIP(ctx, hipGetLastError());
   }
   const int pidx = NO == 1 ? 0 : 1;  // posterior element, as a tick's
-  if (int rc = ww_k_wave_feed(ctx, m, d_rows, d_seg, (int)small.size(), (int)(small.size() + large.size()), d_pool, (int)pool.size(), d_ringt,
-                              (int)ringt.size(), d_z, st->wstate, st->zring, st->zpos, pidx, d_post))
+  if (int rc = ww_k_wave_feed(ctx, m, d_rows, d_seg, (int)small.size(), (int)(small.size() + large.size()), d_pool, (int)pl.pool.size(), d_ringt,
+                              (int)pl.ringt.size(), d_z, st->wstate, st->zring, st->zpos, pidx, d_post))
     return rc;
   if (rows > 0) WW_HIP(ctx, hipMemcpyAsync(post, d_post, (size_t)rows * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (rows > 0 && mel) WW_HIP(ctx, hipMemcpyAsync(mel, d_rows, (size_t)rows * F * 4, hipMemcpyDeviceToHost, ctx->stream));
