@@ -180,6 +180,25 @@ int ww_model_set_precision(ww_model *model, int precision);
 #define WW_OPT_WAVE_SEQ_SEGMENT 5
 int ww_model_set_option(ww_model *model, int key, int64_t value);
 
+/* ---- model sets: several models of ONE geometry behind one launch and one stream bank -----------
+ * The reference evaluates lists of checkpoints over the same audio (wwdetect/wavenet/evaluate_wavenet.py: eval_models; utils/
+ * plot_eval_models.py) one TFLite interpreter at a time, and a service holds one wake word per tenant.  A loaded model is one
+ * device block whose layout depends on its geometry alone, so K models of one geometry are K blocks at a fixed stride:
+ * ww_model_set_create copies the members' blocks, device to device on the context's stream, into ONE allocation of n_models x stride
+ * (stride = the block size rounded up to 256 bytes), and the kernels add member x stride to their weight pointers, once per
+ * workgroup.  The members may be freed afterwards; the set must outlive the banks created from it.  Member k evaluated through a set
+ * gives the bits member k gives on its own.  ONE front end serves the set.
+ * WW_EINVAL (ww_last_error says which member and why): n_models outside 1..WW_SET_MAX_MODELS or NULL arguments; a member of another
+ * context; members of different kind, or whose ww_model_info differs in any field; members whose geometry differs (a Wavenet's
+ * dilations, block order and residual convs included) or is a CRNN's generic conv geometry; members whose block sizes differ; a
+ * member in WW_PRECISION_BF16X3 (sets are fp32 only); members whose filters (filter.tflite: geometry and every array) are not
+ * byte-identical.  ww_model_set_info: the members' common info and their number (either may be NULL). */
+typedef struct ww_model_set ww_model_set;
+#define WW_SET_MAX_MODELS 64
+int ww_model_set_create(ww_ctx *ctx, const ww_model *const *models, int32_t n_models, ww_model_set **out);
+int ww_model_set_destroy(ww_model_set *set);
+int ww_model_set_info(const ww_model_set *set, ww_model_info *info, int32_t *n_models);
+
 /* ---- front end: PCM -> log-mel ---------------------------------------------------------
  * Replaces the per-sample RingBuffer loop + np.fft.rfft + filter.tflite invoke of
  * Filter.filter_frame / WakewordTrigger._sample/_analyze/_filter
@@ -283,6 +302,16 @@ int ww_slide_forward(ww_ctx *ctx, const ww_model *model, const float *mel, int64
 int ww_forward_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows,
                            const int64_t *d_win_row, const int32_t *d_win_valid, int32_t n_windows, float *d_out);
 
+/* ww_forward_windows_dev over a model set: window w is evaluated by member win_model[w], all windows in ONE launch (K checkpoints
+ * over the same mel - the loop over eval_models of wwdetect/wavenet/evaluate_wavenet.py - are K x n windows that name the same rows).
+ * win_model is a HOST array: read and checked before the call returns (an id outside [0, n_models): WW_EINVAL, nothing is launched),
+ * sent to the device with the call's other tables.  d_enc (may be NULL) receives the encoder rows [n_windows][enc_rows][enc_width].
+ * CRNN: one crnn_fused_kernel launch whatever n_windows is (no front + tail split); Wavenet: the fp32 transposed form, twelve waves
+ * up to 256 windows and four above, as for one model.  Row w carries the bits of ww_forward_windows_dev with member win_model[w] on
+ * the same launch size.  n_windows = 0: WW_OK, nothing written. */
+int ww_set_forward_windows_dev(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                               const int32_t *d_win_valid, const int32_t *win_model, int32_t n_windows, float *d_out, float *d_enc);
+
 /* Several mel sequences in one device buffer (the padded clips of a test set), each slid over with the same hop:
  * sequence s has seg_nw[s] complete windows, window k of it covers rows [seg_row0[s] + k*hop, + window).
  * seg_row0 / seg_nw are HOST arrays; d_out receives the detect rows sequence by sequence.  This is the window loop of
@@ -359,6 +388,19 @@ int ww_clips_forward_dev(ww_ctx *ctx, const ww_model *model, const int16_t *d_pc
 #define WW_STREAM_CAUSAL 8u
 int ww_stream_create(ww_ctx *ctx, const ww_model *model, int32_t n_streams, const ww_frontend_params *fp, uint32_t flags,
                      ww_streams **out);
+/* A bank whose streams each have a model of a set (one wake word per tenant: one bank, one front end, one tick).  stream_model[s] is
+ * the member that serves stream s - a HOST array, checked here (an id outside [0, n_models): WW_EINVAL), NULL = all 0 - and the bank
+ * keeps it as a device table.  Every ww_stream_* call and ww_pipeline_bank_step work on such a bank unchanged; stream s yields the
+ * bits it yields in a bank of member stream_model[s] alone.  Forms: the incremental CRNN bank (one launch, WW_STREAM_TWO_LAUNCH, both
+ * waits), the Wavenet window bank (one launch and WW_STREAM_TWO_LAUNCH), WW_STREAM_CAUSAL by tick and by ww_stream_feed.
+ * WW_STREAM_FULL_RECOMPUTE on a set: WW_EINVAL.  The set must outlive the bank.
+ * ww_stream_set_model moves the listed streams (ids NULL -> all) to member `model` AND resets them as ww_stream_reset does - a
+ * stream's cached activations belong to the model that made them -, in stream order with the ticks.  WW_EINVAL: a bank that was not
+ * created from a set, an id or a model out of range.  A failure after the bank's table has changed marks the bank broken (WW_ESTATE
+ * from then on), as a failed tick does. */
+int ww_stream_create_set(ww_ctx *ctx, const ww_model_set *set, int32_t n_streams, const int32_t *stream_model,
+                         const ww_frontend_params *fp, uint32_t flags, ww_streams **out);
+int ww_stream_set_model(ww_streams *st, const int32_t *ids, int32_t n, int32_t model);
 int ww_stream_destroy(ww_streams *st);
 int ww_stream_step(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post);
 /* WakewordTrigger.reset (tflite.py:241-246) for the listed streams (ids NULL -> all). */

@@ -1,6 +1,7 @@
 // C ABI of libwwhip.so: context, model upload, host/device entry points (see include/wwhip.h).
 #include "common.h"
 #include "model_pack.h"
+#include "model_set.h"
 
 #include <algorithm>
 #include <cmath>
@@ -127,7 +128,7 @@ struct ww_staged_io {
 extern "C" {
 
 static_assert(WW_ABI == 4, "ww_version's text carries the ABI number");
-const char *ww_version(void) WW_NOTHROW { return "wwhip 0.5 (gfx950; ABI 4: ww_stream_create takes flags, ww_host_stage_i16, ww_uploader_*, ww_stream_timeline)"; }
+const char *ww_version(void) WW_NOTHROW { return "wwhip 0.5 (gfx950; ABI 4: ww_stream_create takes flags, ww_host_stage_i16, ww_uploader_*, ww_stream_timeline, ww_model_set_*)"; }
 
 int ww_runtime_info(int32_t *built_hip_version, int32_t *runtime_version, int32_t *driver_version) {
   WW_GUARD_BEGIN
@@ -324,6 +325,8 @@ int ww_model_load(ww_ctx *ctx, const void *blob, size_t len, ww_model **out) {
     slot->set(*m, (char *)m->block + e.off);
   }
   if (m->kind == WW_KIND_CRNN && m->crnn.generic) m->crnn.conv_w = m->crnn.conv_wt;  // one array, the generic kernels' name for it
+  m->block_bytes = pm.bytes.size();
+  m->filt_image = ww_set_filter_image(pm.table, pm.bytes.data());  // (what ww_model_set_create compares)
   *out = own.release();
   return WW_OK;
   WW_GUARD_END(ctx)
@@ -376,6 +379,76 @@ int ww_model_set_option(ww_model *m, int key, int64_t value) {
     default: return ww_fail(m->ctx, WW_EINVAL, "unknown model option %d", key);
   }
   WW_GUARD_END(m ? m->ctx : nullptr)
+}
+
+// ---- model sets (the host half - what may be one set, the stride, the pointer translation - is model_set.h) ----------------------
+int ww_model_set_destroy(ww_model_set *set) {
+  WW_GUARD_BEGIN
+  if (!set) return WW_OK;
+  if (set->ctx) {
+    ww_device_scope dev_scope(set->ctx->device);
+    hipStreamSynchronize(set->ctx->stream);
+    if (set->block) hipFree(set->block);
+  }
+  delete set;
+  return WW_OK;
+  WW_GUARD_END(nullptr)
+}
+
+int ww_model_set_create(ww_ctx *ctx, const ww_model *const *models, int32_t n_models, ww_model_set **out) {
+  WW_GUARD_BEGIN
+  if (!ctx || !models || !out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (n_models < 1 || n_models > WW_SET_MAX_MODELS)
+    return ww_fail(ctx, WW_EINVAL, "a model set has 1..%d members, not %d", WW_SET_MAX_MODELS, (int)n_models);
+  std::vector<ww_set_member> mem((size_t)n_models);
+  for (int k = 0; k < n_models; ++k) {
+    const ww_model *m = models[k];
+    if (!m) return ww_fail(ctx, WW_EINVAL, "member %d is NULL", k);
+    mem[k].ctx = m->ctx; mem[k].kind = m->kind; mem[k].precision = m->precision; mem[k].info = m->info;
+    mem[k].filt = &m->filt; mem[k].crnn = &m->crnn; mem[k].wave = &m->wave;
+    mem[k].block_bytes = m->block_bytes; mem[k].filt_image = &m->filt_image;
+  }
+  char why[384];
+  if (int rc = ww_set_check(mem.data(), n_models, ctx, why, sizeof why)) return ww_fail(ctx, rc, "ww_model_set_create: %s", why);
+  WW_ON_DEVICE(ctx, dev_scope);
+  ww_model_set *set = new ww_model_set();
+  ww_scoped<ww_model_set, ww_model_set_destroy> own(set);
+  set->ctx = ctx;
+  set->n = n_models;
+  const size_t bytes = models[0]->block_bytes;
+  set->stride = ww_set_stride(bytes);
+  if (hipMalloc(&set->block, set->stride * (size_t)n_models) != hipSuccess)
+    return ww_fail(ctx, WW_ENOMEM, "cannot allocate a set of %d models (%zu bytes)", (int)n_models, set->stride * (size_t)n_models);
+  for (int k = 0; k < n_models; ++k)
+    WW_HIP(ctx, hipMemcpyAsync((char *)set->block + (size_t)k * set->stride, models[k]->block, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the members may be freed as soon as the call returns
+  // member 0 as the launchers see it: its geometry, its pointers inside the set's block; the dispatch options are the library's
+  // defaults, whatever member 0's are (a set has no ww_model_set_option)
+  set->view = *models[0];
+  set->view.block = set->block;
+  {
+    const ww_model defaults;
+    set->view.opt_split_at = defaults.opt_split_at; set->view.opt_slide_min = defaults.opt_slide_min;
+    set->view.opt_tail_mfma = defaults.opt_tail_mfma; set->view.opt_wave_rowmajor = defaults.opt_wave_rowmajor;
+    set->view.opt_wave_seq_segment = defaults.opt_wave_seq_segment;
+  }
+  set->view.filt_image.clear();  // (compared above; the view needs no copy of it)
+  set->view.filt_image.shrink_to_fit();
+  if (!ww_set_translate_model(set->view.filt, set->view.crnn, set->view.wave, models[0]->block, bytes, set->block))
+    return ww_fail(ctx, WW_EINTERNAL, "ww_model_set_create: a pointer of member 0 lies outside its block");
+  *out = own.release();
+  return WW_OK;
+  WW_GUARD_END(ctx)
+}
+
+int ww_model_set_info(const ww_model_set *set, ww_model_info *info, int32_t *n_models) {
+  WW_GUARD_BEGIN
+  if (!set) return WW_EINVAL;
+  if (info) *info = set->view.info;
+  if (n_models) *n_models = set->n;
+  return WW_OK;
+  WW_GUARD_END(set ? set->ctx : nullptr)
 }
 
 int64_t ww_num_frames(int64_t n, int32_t hop) WW_NOTHROW {
@@ -666,6 +739,34 @@ int ww_forward_windows_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, i
   int rc = ww_ensure(ctx, ctx->dev, model_ws(m, chunk_of(nw)) + 1024, false);
   if (rc) return rc;
   return forward_chunks(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, nw, ctx->dev.ptr, d_out, nullptr, no_enc);
+  WW_GUARD_END(ctx)
+}
+
+int ww_set_forward_windows_dev(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                               const int32_t *d_win_valid, const int32_t *win_model, int32_t nw, float *d_out, float *d_enc) {
+  WW_GUARD_BEGIN
+  if (!ctx || !set) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (set->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "the model set belongs to another context");
+  if (nw < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
+  if (nw == 0) return WW_OK;
+  if (!d_mel || !d_out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (!d_win_row || !d_win_valid || !win_model) return ww_fail(ctx, WW_EINVAL, "window descriptors are NULL");
+  char why[160];
+  if (int rc = ww_set_check_ids(win_model, nw, set->n, "win_model", why, sizeof why)) return ww_fail(ctx, rc, "ww_set_forward_windows_dev: %s", why);
+  WW_ON_DEVICE(ctx, dev);
+  const ww_model *m = &set->view;
+  ww_tables tb;
+  const size_t o_ids = tb.add(win_model, (size_t)nw), b_ws = model_ws(m, 1);
+  if (int rc = ww_ensure(ctx, ctx->dev, tb.bytes() + b_ws + 1024, false)) return rc;
+  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
+  char *d_tab = bump.take<char>(tb.bytes());
+  void *ws = bump.take<char>(b_ws);
+  if (int rc = tb.send(ctx, d_tab)) return rc;
+  ww_set_ref ref;
+  ref.ids = (const int32_t *)(d_tab + o_ids);
+  ref.stride = (long long)set->stride;
+  if (m->kind == WW_KIND_CRNN) return ww_k_crnn_set_forward(ctx, m, ref, d_mel, mel_rows, d_win_row, d_win_valid, nw, d_out, d_enc);
+  return ww_k_wave_forward(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, 0, nw, ws, b_ws, d_out, d_enc, nullptr, &ref);
   WW_GUARD_END(ctx)
 }
 

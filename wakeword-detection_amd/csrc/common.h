@@ -55,53 +55,8 @@ struct ww_ctx {
   unsigned desc_k = 0;
 };
 
-// A loaded model's arrays all lie in ONE device block (ww_model::block), each from a 256-byte boundary, packed on the host by
-// model_pack.h; the structs below are model_layout.h's scalar geometry plus the pointers into that block (api.hip: ww_model_load).
-struct ww_filter_dev : ww_filter_geom {
-  int *start = nullptr;      // [n_mel] first bin of band m
-  float *bias = nullptr;
-  float *wdense = nullptr;   // [n_mel][n_bins] dense weights (filter.tflite layout)
-  float *wpad = nullptr;     // [WW_MEL_TAPS][64] tap-major zero-padded weights of the bands from their first bins (kernel form)
-  double *hann = nullptr;    // [512] np.hanning(512) in fp64
-  double *tw256 = nullptr;   // [256][2] e^{-2 pi i k / 256}
-  double *tw512 = nullptr;   // [256][2] e^{-2 pi i k / 512}
-  double *tw16 = nullptr;    // [16 k1][16 j][2] e^{-2 pi i j k1 / 256}
-  // Mel filter in lane form for the batched front end (frontend.hip): the bands, sorted by width, are dealt
-  // to three groups of 16 "slots"; slot s of group g accumulates one band over 4 * WW_MELV_CAPQ[g] padded taps.
-  float *melV = nullptr;     // [WW_MELV_CHUNKS][16 slots] float4: 0.5 * weight of taps 4c..4c+3 (chunks of group 0, 1, 2)
-  int *melVmeta = nullptr;   // [3][16]: first bin | band << 16 (band 0xffff: empty slot)
-};
-
-struct ww_crnn_dev : ww_crnn_geom {
-  float *conv_w = nullptr;   // [CV_KPAD/4][32][4] (MFMA B-operand order); generic: conv_wt
-  float *conv_b = nullptr;   // [C]
-  float *wx1s = nullptr;     // W_x1 [2*3H][OF*C] (rows: fwd z,r,h then bwd z,r,h) in MFMA B-operand order [OF*C/4][2*3H][4] (crnn_fused_kernel)
-  float *bx1 = nullptr;      // [2*3H]
-  float *wh1 = nullptr;      // [2][3H][H]
-  float *bh1 = nullptr;      // [2][3H]
-  float *wx2 = nullptr;      // [2*3H][2H]
-  float *wx2s = nullptr;     // the same in MFMA B-operand order [2H/4][2*3H][4]
-  unsigned short *cwb = nullptr;   // split-bf16 mode: conv weights hi/lo planes in A-operand order (crnn_fused_bf16_kernel)
-  unsigned short *wx1b = nullptr;  // split-bf16 mode: W_x1 hi/lo planes in B-operand order
-  float *bx2 = nullptr;
-  float *wh2 = nullptr;
-  float *bh2 = nullptr;
-  float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;
-  // generic geometry (ww_crnn_geom::generic)
-  float *conv_wt = nullptr;    // [KF*KT][C]  (k-major for the implicit GEMM)
-  float *conv_wL = nullptr, *conv_wR = nullptr;  // conv_w with the taps that meet a window's zero padding cleared (first 6 / last 7 frames): crnn_rows_kernel
-  float *wx1p = nullptr;       // [2*3H][FEATP], zero padded
-};
-
-struct ww_wave_dev : ww_wave_geom {
-  float *w_in = nullptr, *b_in = nullptr;          // [n_mel][C], [C]
-  float *bn_s = nullptr, *bn_t = nullptr;          // [NB][C]
-  float *w_gate = nullptr, *b_gate = nullptr;      // [NB][3*C][2C] (cols: sig 0..C-1, tanh C..2C-1), [NB][2C]
-  float *w_rs = nullptr, *b_rs = nullptr;          // [NB][C][C+S] (cols: res 0..C-1, skip C..), [NB][C+S]
-  float *d_w1 = nullptr, *d_b1 = nullptr, *d_w2 = nullptr, *d_b2 = nullptr;
-  uint16_t *wpk = nullptr;                         // split-bf16 parameter pages [NB]{[WV_SLOTS][64][8] bf16 A operands, [7][16] f32 vectors}
-};
-
+// (ww_filter_dev, ww_crnn_dev, ww_wave_dev - model_layout.h's scalar geometry plus the pointers into a model's device block - are
+// model_layout.h's too: model_set.h translates them on the host)
 struct ww_model {
   ww_ctx *ctx = nullptr;
   int kind = 0;
@@ -116,6 +71,31 @@ struct ww_model {
   int opt_wave_rowmajor = 0;  // WW_OPT_WAVENET_ROWMAJOR
   int opt_wave_seq_segment = 0;  // WW_OPT_WAVE_SEQ_SEGMENT (0 = the library's choice)
   void *block = nullptr;  // the one device allocation behind every pointer of filt, crnn and wave
+  size_t block_bytes = 0;           // its size: a function of the geometry alone (model_pack.h)
+  std::vector<uint8_t> filt_image;  // the filter's arrays as the packer made them (model_set.h: ww_set_filter_image): what two
+                                    // members of a set must share
+};
+
+// K models of one geometry behind one launch (include/wwhip.h: ww_model_set_create; the host half is model_set.h).  The members'
+// blocks lie at block + k * stride; `view` is member 0 with every pointer translated into that allocation - what the launchers
+// build their kernel arguments from - and owns nothing.
+struct ww_model_set {
+  ww_ctx *ctx = nullptr;
+  int n = 0;
+  size_t stride = 0;
+  void *block = nullptr;
+  ww_model view;
+};
+
+// A SET kernel's extra argument (crnn_fused_kernel, crnn_stream_kernel, wavenet_kernel, wavenet_seq_kernel with SET = true): the
+// workgroup's member is ids[i], i by the launch form - a batch: the workgroup's window; a one-launch tick: its stream; a
+// table-driven tick: the stream in its window's aux word (aux != nullptr: a Wavenet window bank's kernel has no other use for that
+// table); a feed: its segment's stream - and every weight pointer of the kernel's arguments moves on by member * stride bytes.
+// The SET = false instantiations take the same (empty) argument and never look at it.
+struct ww_set_ref {
+  const int32_t *ids = nullptr;
+  const int32_t *aux = nullptr;
+  long long stride = 0;
 };
 
 int ww_fail(ww_ctx *ctx, int code, const char *fmt, ...);
@@ -252,25 +232,29 @@ int ww_k_crnn_init_device(ww_ctx *ctx);  // per-device kernel attributes (dynami
 int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
                       const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int n_windows, void *ws, size_t ws_bytes,
                       float *d_out, float *d_enc, const ww_tick_tag *tag = nullptr);
+// a set's explicit windows, window w by member set->ids[w]: ONE crnn_fused_kernel launch whatever nw is (m: the set's view)
+int ww_k_crnn_set_forward(ww_ctx *ctx, const ww_model *m, const ww_set_ref &set, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                          const int32_t *d_win_valid, int nw, float *d_out, float *d_enc);
 bool ww_crnn_segments_capable(const ww_model *m, int hop);
 int ww_k_crnn_segments_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
                                const int32_t *seg_nw, int n_seg, int hop, float *d_out);
 bool ww_crnn_stream_capable(const ww_model *m);
 int ww_k_crnn_stream_forward(ww_ctx *ctx, const ww_model *m, const float *d_hist, int64_t hist_rows, const int64_t *d_win_row,
                              const int32_t *d_win_valid, const int32_t *d_win_aux, float *d_gxc, int n_windows, float *d_out,
-                             const ww_tick_tag *tag = nullptr);
+                             const ww_tick_tag *tag = nullptr, const ww_set_ref *set = nullptr);
 // one launch per tick: front end + incremental CRNN of all S streams (2 S workgroups); posteriors as tags only
-int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, float *d_gxc, const ww_tick_tag &tag);
+int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, float *d_gxc, const ww_tick_tag &tag,
+                   const ww_set_ref *set = nullptr);
 // does a ww_k_crnn_forward launch of n explicit windows write the tags (the one-kernel forms do)?
 bool ww_crnn_forward_tags(const ww_model *m, int n_windows);
 size_t ww_wave_workspace(const ww_model *m, int n_windows);
 int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
                       const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int n_windows, void *ws, size_t ws_bytes,
-                      float *d_out, float *d_enc, const ww_tick_tag *tag = nullptr);
+                      float *d_out, float *d_enc, const ww_tick_tag *tag = nullptr, const ww_set_ref *set = nullptr);
 int ww_k_posterior_pick(ww_ctx *ctx, const float *d_rows, int64_t n, int n_out, int pidx, const int64_t *d_seg_offs, int64_t n_seg,
                         float *d_out);
 bool ww_wave_tick_capable(const ww_model *m, int n_streams);
-int ww_k_wave_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, const ww_tick_tag &tag);
+int ww_k_wave_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, const ww_tick_tag &tag, const ww_set_ref *set = nullptr);
 // The fp32 Wavenet's sequence form (wavenet.hip: wavenet_seq_kernel) over launch_plan.h's segments (wv_seg).
 int ww_wave_receptive_field(const ww_model *m);  // 1 + 2 * sum of the dilations
 int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const wv_seg *d_segs, int n_segs, float *d_enc, float *d_logits);
@@ -283,10 +267,10 @@ int ww_k_wave_pool(ww_ctx *ctx, const float *d_z, int64_t rows, int64_t row_end,
 // d_z, then pool[n_pool] -> d_post and ring[n_ring] (one entry per such stream) -> the logit rings
 int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv_feed_seg *d_segs, int n_small, int n_segs,
                    const wv_feed_pool *d_pool, int n_pool, const wv_feed_pool *d_ring, int n_ring, float *d_z, float *d_state,
-                   float *d_zring, int32_t *d_zpos, int pidx, float *d_post);
+                   float *d_zring, int32_t *d_zpos, int pidx, float *d_post, const ww_set_ref *set = nullptr);
 int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, const int64_t *d_win_row, const int32_t *d_win_valid,
                           const int32_t *d_win_aux, int nw, float *d_state, float *d_zring, int32_t *d_zpos, float *d_out,
-                          const ww_tick_tag *tag);
+                          const ww_tick_tag *tag, const ww_set_ref *set = nullptr);
 int ww_k_far_frr(ww_ctx *ctx, const float *d_pos, int64_t n_pos, const float *d_neg, int64_t n_neg, int win,
                  const double *d_thr, int n_thr, double *d_smoothed, unsigned long long *d_pos_cnt,
                  unsigned long long *d_fa_cnt);
@@ -296,6 +280,16 @@ int ww_k_far_frr(ww_ctx *ctx, const float *d_pos, int64_t n_pos, const float *d_
 #define WW_STREAM_GXC 144
 
 #ifdef __HIPCC__
+// A SET kernel's first steps: the member id as a scalar (the index is uniform over the workgroup; readfirstlane says so where the
+// compiler cannot see it), and a weight pointer moved on to that member's block - scalar arithmetic, once per workgroup.
+__device__ __forceinline__ long long ww_set_offset(const ww_set_ref &set, int i) {
+  return (long long)__builtin_amdgcn_readfirstlane(set.ids[i]) * set.stride;
+}
+template <typename T>
+__device__ __forceinline__ void ww_set_move(const T *&p, long long off) {
+  p = (const T *)((const char *)p + off);
+}
+
 // max(x, 0) as ONE instruction: fmaxf compiles to a canonicalising v_max (x, x) in front of the v_max (0, x) when its
 // argument comes out of an MFMA.  On the bit pattern a signed-integer max does the same job (negative floats, -0
 // included, are negative integers).  Not inline asm: the compiler does not see an MFMA -> VALU read hazard through it

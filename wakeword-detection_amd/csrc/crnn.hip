@@ -720,8 +720,18 @@ __device__ __forceinline__ void cf_phases_d_to_g(const fused_args &a, float *img
 // per launch (the other forms lost theirs at no cost; profiles/EXPERIMENTS.md 9.5)
 #define CF_STAMP(i_) \
   if (FRONT_ONLY && a.stamps && lane == 0) a.stamps[((size_t)blockIdx.x * 4 + wave) * 10 + (i_)] = __builtin_amdgcn_s_memtime();
-template <bool FRONT_ONLY>
-__global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a) {
+// SET (a model set's batch, ww_k_crnn_set_forward): window blockIdx.x is evaluated by member set.ids[blockIdx.x] - the weight
+// pointers move on to that member's block before anything is read through them, and from there on the kernel is the
+// single-model kernel, instruction for instruction.
+__device__ __forceinline__ void cf_set_move(fused_args &a, long long off) {
+  ww_set_move(a.w4, off); ww_set_move(a.cbias, off); ww_set_move(a.wx1s, off); ww_set_move(a.bx1, off);
+  ww_set_move(a.wh1, off); ww_set_move(a.bh1, off); ww_set_move(a.wx2s, off); ww_set_move(a.bx2, off);
+  ww_set_move(a.wh2, off); ww_set_move(a.bh2, off); ww_set_move(a.w1, off); ww_set_move(a.b1, off);
+  ww_set_move(a.w2, off); ww_set_move(a.b2, off); ww_set_move(a.cwb, off); ww_set_move(a.wx1b, off);
+}
+template <bool FRONT_ONLY, bool SET = false>
+__global__ __launch_bounds__(CF_THREADS, 2) void crnn_fused_kernel(fused_args a, ww_set_ref set) {
+  if constexpr (SET) cf_set_move(a, ww_set_offset(set, blockIdx.x));
   extern __shared__ __align__(16) float cf_smem[];
   float *img = cf_smem, *feat = cf_smem + CF_IMG_FLOATS;
   constexpr int H = GR_H, OT = CV_OT;
@@ -917,8 +927,11 @@ static_assert(CT_BASE % 4 == 0 && CT_BASE + FE_TL_FLOATS <= CF_FEAT_FLOATS, "tic
 // the carry are kept twice and ping-pong by the stream's state parity.  The sibling transforms frame 0 a second time (same
 // instructions, same bits) rather than wait for it.  No kernel boundary, no second launch, no descriptor tables; the
 // posteriors go out as {value, tick number} pairs (ww_tick_tag) that the host polls.
-template <int FE>
-__global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args sa) {
+// SET (a bank created from a model set): the workgroup's member is set.ids[its stream] - FE != 0: stream blockIdx.x / 2; FE = 0: the
+// stream in the window's aux word.
+template <int FE, bool SET = false>
+__global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args sa, ww_set_ref set) {
+  if constexpr (SET && FE != 0) cf_set_move(sa.f, ww_set_offset(set, blockIdx.x >> 1));
   const fused_args &a = sa.f;
   extern __shared__ __align__(16) float cf_smem[];
   float *img = cf_smem, *feat = cf_smem + CF_IMG_FLOATS;
@@ -980,6 +993,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
     if (valid < 0) valid = 0;
     q0 = aux % RA;
     cache = sa.gxc + (size_t)(aux - q0) * (6 * H);
+    if constexpr (SET) cf_set_move(sa.f, ww_set_offset(set, aux / RA));
     load_conv_w();
     crow0 = cached(0); crow1 = cached(1); crow2 = cached(2);
     // ---- A: mel rows 0..13 (position 0) and 130..150 (positions 17, 18) of the window -> the transposed image
@@ -2080,6 +2094,10 @@ int ww_k_crnn_init_device(ww_ctx *ctx) {
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_FUSED_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_FUSED_SMEM_BYTES));
+  WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_FUSED_SMEM_BYTES));
+  WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
+  WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
+  WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CFB_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, CFB_SMEM_BYTES));
   return WW_OK;
@@ -2104,7 +2122,8 @@ static fused_args crnn_fused_args(const ww_crnn_dev &c, const float *mel, const 
 bool ww_crnn_stream_capable(const ww_model *m) { return m->kind == WW_KIND_CRNN && !m->crnn.generic; }
 
 // ONE launch per tick (crnn_stream_kernel<1 | 2>): 2 S workgroups, the posteriors as tags only
-int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, float *d_gxc, const ww_tick_tag &tag) {
+int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, float *d_gxc, const ww_tick_tag &tag,
+                   const ww_set_ref *set) {
   const ww_crnn_dev &c = m->crnn;
   const ww_filter_dev &f = m->filt;
   if (c.generic || f.n_mel != CV_NMEL || fe.hop != 160)
@@ -2119,8 +2138,10 @@ int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int pre
   const int nwg = 2 * fe.S;
   {
     ww_launch_scope scope(ctx, "crnn_stream_kernel<tick>");
-    if (precise) hipLaunchKernelGGL(crnn_stream_kernel<2>, dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa);
-    else hipLaunchKernelGGL(crnn_stream_kernel<1>, dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa);
+    if (set && precise) hipLaunchKernelGGL((crnn_stream_kernel<2, true>), dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, *set);
+    else if (set) hipLaunchKernelGGL((crnn_stream_kernel<1, true>), dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, *set);
+    else if (precise) hipLaunchKernelGGL(crnn_stream_kernel<2>, dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, ww_set_ref{});
+    else hipLaunchKernelGGL(crnn_stream_kernel<1>, dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, ww_set_ref{});
   }
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
@@ -2128,7 +2149,7 @@ int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int pre
 
 int ww_k_crnn_stream_forward(ww_ctx *ctx, const ww_model *m, const float *d_hist, int64_t hist_rows, const int64_t *d_win_row,
                              const int32_t *d_win_valid, const int32_t *d_win_aux, float *d_gxc, int nw, float *d_out,
-                             const ww_tick_tag *tag) {
+                             const ww_tick_tag *tag, const ww_set_ref *set) {
   if (nw <= 0) return WW_OK;
   const ww_crnn_dev &c = m->crnn;
   if (c.generic) return ww_fail(ctx, WW_EINVAL, "streaming CRNN kernel: standard conv geometry only");
@@ -2140,7 +2161,8 @@ int ww_k_crnn_stream_forward(ww_ctx *ctx, const ww_model *m, const float *d_hist
   if (tag) sa.f.tag = *tag;
   {
     ww_launch_scope scope(ctx, "crnn_stream_kernel");
-    hipLaunchKernelGGL(crnn_stream_kernel<0>, dim3(nw), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa);
+    if (set) hipLaunchKernelGGL((crnn_stream_kernel<0, true>), dim3(nw), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, *set);
+    else hipLaunchKernelGGL(crnn_stream_kernel<0>, dim3(nw), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, ww_set_ref{});
   }
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
@@ -2321,7 +2343,7 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
     {
       ww_launch_scope scope(ctx, bf16 ? "crnn_fused_kernel<front,bf16x3>" : "crnn_fused_kernel<front>");
       if (bf16) hipLaunchKernelGGL(crnn_fused_bf16_kernel<true>, dim3(nw), dim3(CF_THREADS), CFB_SMEM_BYTES, ctx->stream, a);
-      else hipLaunchKernelGGL(crnn_fused_kernel<true>, dim3(nw), dim3(CF_THREADS), CF_FUSED_SMEM_BYTES, ctx->stream, a);
+      else hipLaunchKernelGGL(crnn_fused_kernel<true>, dim3(nw), dim3(CF_THREADS), CF_FUSED_SMEM_BYTES, ctx->stream, a, ww_set_ref{});
     }
     tail_args t = crnn_tail_args(c);
     t.gx1 = a.gx_out;
@@ -2333,7 +2355,23 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
   {
     ww_launch_scope scope(ctx, bf16 ? "crnn_fused_kernel<bf16x3>" : "crnn_fused_kernel");
     if (bf16) hipLaunchKernelGGL(crnn_fused_bf16_kernel<false>, dim3(nw), dim3(CF_THREADS), CFB_SMEM_BYTES, ctx->stream, a);
-    else hipLaunchKernelGGL(crnn_fused_kernel<false>, dim3(nw), dim3(CF_THREADS), CF_FUSED_SMEM_BYTES, ctx->stream, a);
+    else hipLaunchKernelGGL(crnn_fused_kernel<false>, dim3(nw), dim3(CF_THREADS), CF_FUSED_SMEM_BYTES, ctx->stream, a, ww_set_ref{});
+  }
+  WW_HIP(ctx, hipGetLastError());
+  return WW_OK;
+}
+
+// A model set's explicit windows (ww_set_forward_windows_dev): crnn_fused_kernel<false, SET> in ONE launch whatever nw is - no
+// front + tail split, no scratch.  m is the set's view: member 0's arguments, which each workgroup moves on to its own member.
+int ww_k_crnn_set_forward(ww_ctx *ctx, const ww_model *m, const ww_set_ref &set, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                          const int32_t *d_win_valid, int nw, float *d_out, float *d_enc) {
+  if (nw <= 0) return WW_OK;
+  const ww_crnn_dev &c = m->crnn;
+  if (c.generic) return ww_fail(ctx, WW_EINVAL, "model set: standard conv geometry only");
+  const fused_args a = crnn_fused_args(c, d_mel, {d_win_row, d_win_valid, 0, 0, 0, mel_rows}, d_enc, d_out);
+  {
+    ww_launch_scope scope(ctx, "crnn_fused_kernel<set>");
+    hipLaunchKernelGGL((crnn_fused_kernel<false, true>), dim3(nw), dim3(CF_THREADS), CF_FUSED_SMEM_BYTES, ctx->stream, a, set);
   }
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;

@@ -3,6 +3,7 @@
 // Plain C++: no HIP header, no HIP call.
 #pragma once
 
+#include <cstdint>
 #include <vector>
 
 // ---- mel filter (fft_device.h, stream_fe.h, frontend.hip) --------------------------------------------------------------------
@@ -47,4 +48,52 @@ struct ww_wave_geom {
   int T = 0, n_mel = 0, C = 0, S = 0, NB = 0, NOUT = 0;
   std::vector<int> dil, order, has_res;
   bool order_is_natural = true;
+};
+
+// ---- the geometry plus the device addresses of the arrays: plain pointers, so that host-only code (model_set.h) can translate them
+// A loaded model's arrays all lie in ONE device block (ww_model::block), each from a 256-byte boundary, packed on the host by
+// model_pack.h; the structs below are model_layout.h's scalar geometry plus the pointers into that block (api.hip: ww_model_load).
+struct ww_filter_dev : ww_filter_geom {
+  int *start = nullptr;      // [n_mel] first bin of band m
+  float *bias = nullptr;
+  float *wdense = nullptr;   // [n_mel][n_bins] dense weights (filter.tflite layout)
+  float *wpad = nullptr;     // [WW_MEL_TAPS][64] tap-major zero-padded weights of the bands from their first bins (kernel form)
+  double *hann = nullptr;    // [512] np.hanning(512) in fp64
+  double *tw256 = nullptr;   // [256][2] e^{-2 pi i k / 256}
+  double *tw512 = nullptr;   // [256][2] e^{-2 pi i k / 512}
+  double *tw16 = nullptr;    // [16 k1][16 j][2] e^{-2 pi i j k1 / 256}
+  // Mel filter in lane form for the batched front end (frontend.hip): the bands, sorted by width, are dealt
+  // to three groups of 16 "slots"; slot s of group g accumulates one band over 4 * WW_MELV_CAPQ[g] padded taps.
+  float *melV = nullptr;     // [WW_MELV_CHUNKS][16 slots] float4: 0.5 * weight of taps 4c..4c+3 (chunks of group 0, 1, 2)
+  int *melVmeta = nullptr;   // [3][16]: first bin | band << 16 (band 0xffff: empty slot)
+};
+
+struct ww_crnn_dev : ww_crnn_geom {
+  float *conv_w = nullptr;   // [CV_KPAD/4][32][4] (MFMA B-operand order); generic: conv_wt
+  float *conv_b = nullptr;   // [C]
+  float *wx1s = nullptr;     // W_x1 [2*3H][OF*C] (rows: fwd z,r,h then bwd z,r,h) in MFMA B-operand order [OF*C/4][2*3H][4] (crnn_fused_kernel)
+  float *bx1 = nullptr;      // [2*3H]
+  float *wh1 = nullptr;      // [2][3H][H]
+  float *bh1 = nullptr;      // [2][3H]
+  float *wx2 = nullptr;      // [2*3H][2H]
+  float *wx2s = nullptr;     // the same in MFMA B-operand order [2H/4][2*3H][4]
+  unsigned short *cwb = nullptr;   // split-bf16 mode: conv weights hi/lo planes in A-operand order (crnn_fused_bf16_kernel)
+  unsigned short *wx1b = nullptr;  // split-bf16 mode: W_x1 hi/lo planes in B-operand order
+  float *bx2 = nullptr;
+  float *wh2 = nullptr;
+  float *bh2 = nullptr;
+  float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;
+  // generic geometry (ww_crnn_geom::generic)
+  float *conv_wt = nullptr;    // [KF*KT][C]  (k-major for the implicit GEMM)
+  float *conv_wL = nullptr, *conv_wR = nullptr;  // conv_w with the taps that meet a window's zero padding cleared (first 6 / last 7 frames): crnn_rows_kernel
+  float *wx1p = nullptr;       // [2*3H][FEATP], zero padded
+};
+
+struct ww_wave_dev : ww_wave_geom {
+  float *w_in = nullptr, *b_in = nullptr;          // [n_mel][C], [C]
+  float *bn_s = nullptr, *bn_t = nullptr;          // [NB][C]
+  float *w_gate = nullptr, *b_gate = nullptr;      // [NB][3*C][2C] (cols: sig 0..C-1, tanh C..2C-1), [NB][2C]
+  float *w_rs = nullptr, *b_rs = nullptr;          // [NB][C][C+S] (cols: res 0..C-1, skip C..), [NB][C+S]
+  float *d_w1 = nullptr, *d_b1 = nullptr, *d_w2 = nullptr, *d_b2 = nullptr;
+  uint16_t *wpk = nullptr;                         // split-bf16 parameter pages [NB]{[WV_SLOTS][64][8] bf16 A operands, [7][16] f32 vectors}
 };

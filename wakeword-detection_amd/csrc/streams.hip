@@ -25,6 +25,7 @@
 //   then the regular CRNN / Wavenet kernels run on the compacted list of new windows.
 //   stream_feed_frontend_kernel  a causal bank fed any number of samples per stream (ww_stream_feed, further down): one workgroup
 //                           per 16 new frames of a stream, the same conversion and the same per-frame functions as above.
+#include "model_set.h"  // (in front of fft_device.h's macros)
 #include "stream_fe.h"
 
 #include <algorithm>
@@ -92,6 +93,19 @@ struct ww_streams {
   uint64_t tl_ns[WW_STREAM_TL_PHASES] = {0};
   int64_t tl_ticks = 0;
   std::vector<uint8_t> stage_flags;  // ww_stream_step_trigger: bit 0 = is_speech, bit 1 = is_active per stream
+  // a bank created from a model set (ww_stream_create_set): `model` is the set's view, stream s is served by member stream_model[s]
+  // - the host's copy and the device table the SET kernels read -, and gx_zero holds one row per member
+  const ww_model_set *set = nullptr;
+  std::vector<int32_t> stream_model;
+  int32_t *d_stream_model = nullptr;  // [S]
+  ww_set_ref set_ref;                 // {d_stream_model, nullptr, the set's stride}
+  // the kernels' extra argument: nullptr for a bank of one model
+  const ww_set_ref *ref() const { return set ? &set_ref : nullptr; }
+  int send_stream_model() {  // the host's copy -> the device table, in stream order (ww_tables::send, the one upload path)
+    ww_tables tb;
+    tb.add(stream_model);
+    return tb.send(ctx, d_stream_model);
+  }
 };
 
 static inline uint64_t st_now_ns() {
@@ -297,14 +311,17 @@ __global__ void stream_causal_reset_kernel(float *wstate, int32_t *zpos, const i
   if (threadIdx.x < 2) zpos[2 * s + threadIdx.x] = 0;
 }
 
-__global__ void stream_reset_kernel(float *hist, const int32_t *ids, int S, int HR, int F, float *gxc, const float *gx_zero) {
+// gx_zero: [192], or with stream_model (a bank of a model set) [members][192]: the row of the stream's current member
+__global__ void stream_reset_kernel(float *hist, const int32_t *ids, int S, int HR, int F, float *gxc, const float *gx_zero,
+                                    const int32_t *stream_model) {
   const int b = blockIdx.x;
   const int s = ids ? ids[b] : b;
   if (s < 0 || s >= S) return;
   for (int i = threadIdx.x; i < HR * F; i += blockDim.x) hist[(size_t)s * HR * F + i] = 0.f;
   if (gxc) {  // every cached row = the row of an all-zero field (what lies in front of the stream's first mel rows)
     float *c = gxc + (size_t)s * WW_STREAM_GXC * 192;
-    for (int i = threadIdx.x; i < WW_STREAM_GXC * 192; i += blockDim.x) c[i] = gx_zero[i % 192];
+    const float *z = gx_zero + (stream_model ? (size_t)stream_model[s] * 192 : 0);
+    for (int i = threadIdx.x; i < WW_STREAM_GXC * 192; i += blockDim.x) c[i] = z[i % 192];
   }
 }
 
@@ -315,7 +332,7 @@ int ww_stream_destroy(ww_streams *st) {
   if (!st) return WW_OK;
   ww_device_scope dev_scope(st->ctx->device);
   hipStreamSynchronize(st->ctx->stream);
-  void *dev[] = {st->ring, st->hist, st->prev, st->d_pack, st->ws, st->gxc, st->gx_zero, st->wstate, st->zring, st->zpos};
+  void *dev[] = {st->ring, st->hist, st->prev, st->d_pack, st->ws, st->gxc, st->gx_zero, st->wstate, st->zring, st->zpos, st->d_stream_model};
   for (void *p : dev)
     if (p) hipFree(p);
   void *host[] = {st->h_pack, st->h_out, st->h_tag};
@@ -326,11 +343,11 @@ int ww_stream_destroy(ww_streams *st) {
   WW_GUARD_END(nullptr)
 }
 
-int ww_stream_create(ww_ctx *ctx, const ww_model *model, int32_t S, const ww_frontend_params *fp, uint32_t flags,
-                     ww_streams **out) {
-  WW_GUARD_BEGIN
-  if (!ctx || !model || !fp || !out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
-  *out = nullptr;
+}  // extern "C"
+
+// ww_stream_create (set == nullptr) and ww_stream_create_set (model = the set's view; stream_model: checked by the caller, or nullptr)
+static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model_set *set, const int32_t *stream_model, int32_t S,
+                              const ww_frontend_params *fp, uint32_t flags, ww_streams **out) {
   if (flags & ~(uint32_t)(WW_STREAM_FULL_RECOMPUTE | WW_STREAM_TWO_LAUNCH | WW_STREAM_SYNC_WAIT | WW_STREAM_CAUSAL))
     return ww_fail(ctx, WW_EINVAL, "unknown stream flags 0x%x", flags);
   const bool causal = (flags & WW_STREAM_CAUSAL) != 0;
@@ -345,6 +362,15 @@ int ww_stream_create(ww_ctx *ctx, const ww_model *model, int32_t S, const ww_fro
   ww_streams *st = new ww_streams();
   ww_scoped<ww_streams, ww_stream_destroy> own(st);  // (freed on every early return below)
   st->ctx = ctx; st->model = model; st->S = S; st->fp = *fp;
+  if (set) {
+    st->set = set;
+    if (stream_model) st->stream_model.assign(stream_model, stream_model + S);
+    else st->stream_model.assign((size_t)S, 0);
+    if (hipMalloc((void **)&st->d_stream_model, ww_bump::need((size_t)S, 4)) != hipSuccess)
+      return ww_fail(ctx, WW_ENOMEM, "cannot allocate the model table of %d streams", S);
+    st->set_ref.ids = st->d_stream_model;
+    st->set_ref.stride = (long long)set->stride;
+  }
   st->T = model->info.window; st->F = model->info.n_mel; st->NO = model->info.n_out; st->HR = 2 * (st->T + 1);
   const size_t hist_elems = (size_t)S * st->HR * st->F;
   // CRNN, standard geometry: three positions per new window instead of nineteen (crnn_stream_kernel, fp32 contractions - also
@@ -403,21 +429,34 @@ int ww_stream_create(ww_ctx *ctx, const ww_model *model, int32_t S, const ww_fro
   st->par.assign(S, 0);
   st->expect.reserve((size_t)2 * S);
   if (st->incremental) {
+    const int K = set ? set->n : 1;  // gx_zero is a function of the weights: one row per member
     if (hipMalloc((void **)&st->gxc, (size_t)S * WW_STREAM_GXC * 192 * 4) != hipSuccess ||
-        hipMalloc((void **)&st->gx_zero, 192 * 4) != hipSuccess) {
+        hipMalloc((void **)&st->gx_zero, (size_t)K * 192 * 4) != hipSuccess) {
       return ww_fail(ctx, WW_ENOMEM, "cannot allocate the projected-row cache of %d streams", S);
     }
     // the row of an all-zero field: position 17 of one window over the (all-zero) history of stream 0, which the kernel
-    // stores into slot (0 + 128) % ring of stream 0's cache
-    hipMemsetAsync(st->gxc, 0, (size_t)WW_STREAM_GXC * 192 * 4, ctx->stream);
-    int rc = ww_k_crnn_stream_forward(ctx, model, st->hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, st->d_win_aux,
-                                      st->gxc, 1, st->h_out_dev);  // d_pack is zeroed: window row 0, aux 0 (valid 0 = all-zero window)
-    if (rc) {
-      return rc;
+    // stores into slot (0 + 128) % ring of stream 0's cache.  A set: once per member, stream 0 lent to each in turn
+    std::vector<int32_t> real;
+    if (set) real.swap(st->stream_model);
+    for (int k = 0; k < K; ++k) {
+      if (set) {
+        st->stream_model.assign((size_t)S, k);
+        if (int rc = st->send_stream_model()) return rc;
+      }
+      hipMemsetAsync(st->gxc, 0, (size_t)WW_STREAM_GXC * 192 * 4, ctx->stream);
+      int rc = ww_k_crnn_stream_forward(ctx, model, st->hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, st->d_win_aux,
+                                        st->gxc, 1, st->h_out_dev, nullptr, st->ref());  // d_pack is zeroed: window row 0, aux 0 (valid 0 = all-zero window)
+      if (rc) {
+        return rc;
+      }
+      hipMemcpyAsync(st->gx_zero + (size_t)k * 192, st->gxc + (size_t)(128 % WW_STREAM_GXC) * 192, 192 * 4, hipMemcpyDeviceToDevice, ctx->stream);
     }
-    hipMemcpyAsync(st->gx_zero, st->gxc + (size_t)(128 % WW_STREAM_GXC) * 192, 192 * 4, hipMemcpyDeviceToDevice, ctx->stream);
+    if (set) {
+      st->stream_model.swap(real);
+      if (int rc = st->send_stream_model()) return rc;
+    }
     hipLaunchKernelGGL(stream_reset_kernel, dim3(S), dim3(256), 0, ctx->stream, st->hist, (const int32_t *)nullptr, S, st->HR, st->F,
-                       st->gxc, (const float *)st->gx_zero);
+                       st->gxc, (const float *)st->gx_zero, (const int32_t *)st->d_stream_model);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
       return ww_fail(ctx, WW_EHIP, "streaming CRNN set-up failed");
     }
@@ -432,9 +471,72 @@ int ww_stream_create(ww_ctx *ctx, const ww_model *model, int32_t S, const ww_fro
     hipMemsetAsync(st->zpos, 0, (size_t)S * 2 * 4, ctx->stream);
     WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
+  if (set && !st->incremental) {  // (the incremental bank sent it above, behind its members' turns)
+    if (int rc = st->send_stream_model()) return rc;
+    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
   *out = own.release();
   return WW_OK;
+}
+
+extern "C" {
+
+int ww_stream_create(ww_ctx *ctx, const ww_model *model, int32_t S, const ww_frontend_params *fp, uint32_t flags,
+                     ww_streams **out) {
+  WW_GUARD_BEGIN
+  if (!ctx || !model || !fp || !out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  *out = nullptr;
+  return stream_create_impl(ctx, model, nullptr, nullptr, S, fp, flags, out);
   WW_GUARD_END(ctx)
+}
+
+int ww_stream_create_set(ww_ctx *ctx, const ww_model_set *set, int32_t S, const int32_t *stream_model, const ww_frontend_params *fp,
+                         uint32_t flags, ww_streams **out) {
+  WW_GUARD_BEGIN
+  if (!ctx || !set || !fp || !out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (set->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "the model set belongs to another context");
+  if (flags & WW_STREAM_FULL_RECOMPUTE)
+    return ww_fail(ctx, WW_EINVAL, "WW_STREAM_FULL_RECOMPUTE runs the per-window batch kernels: not offered on a model set");
+  if (set->view.kind == WW_KIND_CRNN && !ww_crnn_stream_capable(&set->view))
+    return ww_fail(ctx, WW_EINVAL, "a CRNN set streams through the incremental kernel: standard conv geometry only");
+  if (S > 0) {
+    char why[160];
+    if (int rc = ww_set_check_ids(stream_model, S, set->n, "stream_model", why, sizeof why)) return ww_fail(ctx, rc, "ww_stream_create_set: %s", why);
+  }
+  return stream_create_impl(ctx, &set->view, set, stream_model, S, fp, flags, out);
+  WW_GUARD_END(ctx)
+}
+
+// The listed streams move to another member of the bank's set and start afresh: the table first, then ww_stream_reset's kernels
+// behind it on the stream (they read the new member's gx_zero row).
+int ww_stream_set_model(ww_streams *st, const int32_t *ids, int32_t n, int32_t model) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  ww_ctx *ctx = st->ctx;
+  if (!st->set) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_model: this bank was not created from a model set");
+  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
+  if (model < 0 || model >= st->set->n) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_model: model %d: the set has members 0..%d", (int)model, st->set->n - 1);
+  if (ids && n < 0) return ww_fail(ctx, WW_EINVAL, "negative id count");
+  if (ids && n > 2 * st->S) return ww_fail(ctx, WW_EINVAL, "more ids than streams");
+  const int count = ids ? n : st->S;
+  for (int i = 0; ids && i < n; ++i)
+    if (ids[i] < 0 || ids[i] >= st->S) return ww_fail(ctx, WW_EINVAL, "stream id %d out of range", ids[i]);
+  if (count == 0) return WW_OK;
+  WW_ON_DEVICE(ctx, dev_scope);
+  // the host's table is what the device's was last sent: it changes only with an upload that was enqueued, and a failure behind
+  // that point (the reset's kernels) leaves streams on their new member with their old caches: no further ticks
+  const std::vector<int32_t> before = st->stream_model;
+  for (int i = 0; i < count; ++i) st->stream_model[ids ? ids[i] : i] = model;
+  if (int rc = st->send_stream_model()) {
+    st->stream_model = before;
+    st->broken = true;  // (the copy may or may not have been enqueued: which table the device holds is not known)
+    return rc;
+  }
+  const int rc = ww_stream_reset(st, ids, n);
+  if (rc != WW_OK) st->broken = true;
+  return rc;
+  WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
 int ww_stream_reset(ww_streams *st, const int32_t *ids, int32_t n) {
@@ -456,7 +558,7 @@ int ww_stream_reset(ww_streams *st, const int32_t *ids, int32_t n) {
     d_ids = st->d_win_valid;
   }
   hipLaunchKernelGGL(stream_reset_kernel, dim3(count), dim3(256), 0, ctx->stream, st->hist, (const int32_t *)d_ids, st->S, st->HR, st->F,
-                     st->gxc, (const float *)st->gx_zero);
+                     st->gxc, (const float *)st->gx_zero, (const int32_t *)st->d_stream_model);
   if (st->causal)
     hipLaunchKernelGGL(stream_causal_reset_kernel, dim3(count), dim3(256), 0, ctx->stream, st->wstate, st->zpos, (const int32_t *)d_ids, st->S,
                        (int)st->model->wave.dil.size() * WW_WAVE_STATE_BLOCK);
@@ -610,7 +712,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     fe.ring = st->ring; fe.prev = st->prev; fe.hist = st->hist;
     fe.S = S; fe.HR = st->HR;
     fe.cv = ww_fe_pcm_of(st->fp); fe.hop = hop;
-    int rc = m->kind == WW_KIND_CRNN ? ww_k_crnn_tick(ctx, m, fe, st->fp.precise, st->gxc, tag) : ww_k_wave_tick(ctx, m, fe, st->fp.precise, tag);
+    int rc = m->kind == WW_KIND_CRNN ? ww_k_crnn_tick(ctx, m, fe, st->fp.precise, st->gxc, tag, st->ref()) : ww_k_wave_tick(ctx, m, fe, st->fp.precise, tag, st->ref());
     if (rc) return rc;
     tagged = true;
     tl[3] = st_now_ns();
@@ -643,7 +745,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
       // rewrites the page-locked block)
       tagged = st->poll && !st->expect.empty();
       int rc = ww_k_wave_stream_tick(ctx, m, st->hist, st->d_win_row, st->d_win_valid, st->d_win_aux, nw_c, st->wstate, st->zring, st->zpos,
-                                     st->h_out_dev, tagged ? &tag : nullptr);
+                                     st->h_out_dev, tagged ? &tag : nullptr, st->ref());
       if (rc) return rc;
     } else if (nw && !st->incremental) {
       // the per-window kernels' scratch under the model's options of THIS tick (ww_model_set_option may have lowered the
@@ -666,11 +768,15 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
       tagged = st->poll && (st->incremental || m->kind == WW_KIND_WAVENET || ww_crnn_forward_tags(m, nw));
       const ww_tick_tag *tg = tagged ? &tag : nullptr;
       const float *d_hist = st->hist;
+      // (a set's two-launch Wavenet tick: the kernel finds its stream in the window's aux word, which it has no other use for)
+      ww_set_ref wref = st->set_ref;
+      wref.aux = st->d_win_aux;
+      const ww_set_ref *wset = st->set ? &wref : nullptr;
       int rc = st->incremental
-                   ? ww_k_crnn_stream_forward(ctx, m, d_hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, st->d_win_aux, st->gxc, nw, st->h_out_dev, tg)
+                   ? ww_k_crnn_stream_forward(ctx, m, d_hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, st->d_win_aux, st->gxc, nw, st->h_out_dev, tg, st->ref())
                : m->kind == WW_KIND_CRNN
                    ? ww_k_crnn_forward(ctx, m, d_hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, 0, 0, 0, nw, st->ws, st->ws_bytes, st->h_out_dev, nullptr, tg)
-                   : ww_k_wave_forward(ctx, m, d_hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, 0, 0, 0, nw, st->ws, st->ws_bytes, st->h_out_dev, nullptr, tg);
+                   : ww_k_wave_forward(ctx, m, d_hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, 0, 0, 0, nw, st->ws, st->ws_bytes, st->h_out_dev, nullptr, tg, wset);
       if (rc) return rc;
     }
   }
@@ -810,7 +916,7 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
   }
   const int pidx = NO == 1 ? 0 : 1;  // posterior element, as a tick's
   if (int rc = ww_k_wave_feed(ctx, m, d_rows, d_seg, (int)small.size(), (int)(small.size() + large.size()), d_pool, (int)pl.pool.size(), d_ringt,
-                              (int)pl.ringt.size(), d_z, st->wstate, st->zring, st->zpos, pidx, d_post))
+                              (int)pl.ringt.size(), d_z, st->wstate, st->zring, st->zpos, pidx, d_post, st->ref()))
     return rc;
   if (rows > 0) WW_HIP(ctx, hipMemcpyAsync(post, d_post, (size_t)rows * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (rows > 0 && mel) WW_HIP(ctx, hipMemcpyAsync(mel, d_rows, (size_t)rows * F * 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -249,13 +249,21 @@ __device__ __forceinline__ void wv_vload(const float *vtab, int blk, int kk, wv_
 // before - hist[blk][kk][row][4], parked in the pad rows in front of the barrier by the wave with hist_wave set, and replaced
 // behind it by rows [valid, valid + WV_PAD) of [pad | u], i.e. the last WV_PAD rows up to the chunk's last valid row.  One
 // wave does both and a wave's LDS operations complete in issue order, so the history needs no barrier of its own.
-template <int MPW, int UPL, bool HIST>
+// (DIL - where a SET kernel, whose `a` is a moved COPY of its arguments, reads the dilations: an index into a local copy would keep
+//  it in scratch memory.  0: a.dil4[blk / 16], the arguments themselves.  1 - wavenet_seq_kernel<SET>, which has moved its arguments
+//  in place and has only the copy: the word is picked by a comparison.  2 - wavenet_kernel<SET>: from geo, the kernel's arguments as
+//  they came; with the comparison its one-launch tick forms held every argument in scalar registers from the top, 106 of them, and
+//  spilled four)
+template <int MPW, int UPL, bool HIST, int DIL = 0>
 __device__ __forceinline__ void wv_block_t(const wave_args &a, int blk, float *ubuf, const float *vtab, int j, int kk, int tl,
                                            f32x4 (&x)[MPW], f32x4 (&skip)[MPW][2], const wv_wblk &P, wv_wblk &Pnext,
                                            const wv_vblk &V, wv_vblk &Vnext, float *hist = nullptr, int valid = 0,
-                                           bool hist_wave = false) {
+                                           bool hist_wave = false, const wave_args *geo = nullptr) {
   float *u = ubuf + (blk & 1) * 4 * UPL + kk * UPL + WV_PAD * 4;          // row 0 of this lane's channel-group plane
-  const int d = (int)((a.dil4[blk >> 4] >> (4 * (blk & 15))) & 15);
+  int d;
+  if constexpr (DIL == 1) d = (int)(((blk < 16 ? a.dil4[0] : a.dil4[1]) >> (4 * (blk & 15))) & 15);
+  else if constexpr (DIL == 2) d = (int)((geo->dil4[blk >> 4] >> (4 * (blk & 15))) & 15);
+  else d = (int)((a.dil4[blk >> 4] >> (4 * (blk & 15))) & 15);
   const float4 *vt = wv_vt(vtab, blk, kk);
   const float4 bres = vt[4 * WV_VT_BRES], bsk0 = vt[4 * WV_VT_BSK0], bsk1 = vt[4 * WV_VT_BSK1];
   f32x4 uv[MPW], as[MPW], at[MPW];
@@ -391,16 +399,16 @@ static_assert(WV_H_F <= WV_PG_F, "the head tile lies over the parameter pages");
 
 // All NB blocks through wv_block_t<MPW_, UPL_, HIST_>: the parameters one block ahead in two register sets, the loop unrolled by
 // two.  pw_[0]: block 0's weights, requested in front of the barrier that publishes the vector table; the trailing arguments are
-// wv_block_t's hist, valid, hist_wave.  (A macro: as a function template the twelve-wave sequence kernels spilled 12 bytes,
+// wv_block_t's hist, valid, hist_wave; SET is the kernel's template parameter.  (A macro: as a function template the twelve-wave sequence kernels spilled 12 bytes,
 // EXPERIMENTS 14.)
-#define WV_BLOCKS_T(MPW_, UPL_, HIST_, a_, ubuf_, vtab_, j_, kk_, tl_, x_, skip_, pw_, ...)                                        \
+#define WV_BLOCKS_T(MPW_, UPL_, HIST_, DIL_, a_, ubuf_, vtab_, j_, kk_, tl_, x_, skip_, pw_, ...)                                        \
   do {                                                                                                                             \
     wv_vblk pv[2];                                                                                                                 \
     wv_vload(vtab_, 0, kk_, pv[0]);                                                                                                \
     for (int blk = 0; blk < (a_).NB; blk += 2) {                                                                                   \
-      wv_block_t<MPW_, UPL_, HIST_>(a_, blk, ubuf_, vtab_, j_, kk_, tl_, x_, skip_, pw_[0], pw_[1], pv[0], pv[1], ##__VA_ARGS__);  \
+      wv_block_t<MPW_, UPL_, HIST_, DIL_>(a_, blk, ubuf_, vtab_, j_, kk_, tl_, x_, skip_, pw_[0], pw_[1], pv[0], pv[1], ##__VA_ARGS__);  \
       if (blk + 1 < (a_).NB)                                                                                                       \
-        wv_block_t<MPW_, UPL_, HIST_>(a_, blk + 1, ubuf_, vtab_, j_, kk_, tl_, x_, skip_, pw_[1], pw_[0], pv[1], pv[0], ##__VA_ARGS__); \
+        wv_block_t<MPW_, UPL_, HIST_, DIL_>(a_, blk + 1, ubuf_, vtab_, j_, kk_, tl_, x_, skip_, pw_[1], pw_[0], pv[1], pv[0], ##__VA_ARGS__); \
     }                                                                                                                              \
   } while (0)
 
@@ -479,8 +487,43 @@ __device__ __forceinline__ void wv_enc_store_t(float *e, int kk, const f32x4 (&s
 // 0 and 1 transform the new frames (one each) straight into the staged input while the others stage the rows that were
 // there before; the workgroup of the tick's newest window alone writes the stream's state (mel rows, sample ring and carry -
 // the latter two ping-pong by the stream's parity, so its sibling still reads last tick's).  Twelve waves x one tile only.
-template <bool HEAD_ONLY, bool SPLIT_BF16, int WV_NW, bool FP32T = false, int TICK = 0>
-__global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC : 3) : 2) void wavenet_kernel(wave_args a) {
+// SET (a model set: ww_set_forward_windows_dev, or a bank created from one): the workgroup's member is set.ids[i] - a batch: its
+// window; a one-launch tick: its stream, blockIdx.x / 2; a two-launch tick: the stream in its window's aux word (stream *
+// WW_STREAM_GXC + ...) -, and the weight pointers move on to that member's block before anything is read through them.  fp32
+// transposed forms only.
+// (three parts.  wavenet_kernel leaves its arguments where they are and reads the weights of each phase through a copy made where
+//  the phase begins, WV_SET_VIEW; wavenet_seq_kernel moves all of them at its top)
+__device__ __forceinline__ void wv_set_move_front(wave_args &a, long long off) {  // the input conv and the per-block vectors
+  ww_set_move(a.w_in4, off); ww_set_move(a.b_in, off); ww_set_move(a.bn_s, off); ww_set_move(a.bn_t, off);
+  ww_set_move(a.b_gate, off); ww_set_move(a.b_rs, off); ww_set_move(a.wpk, off);
+}
+__device__ __forceinline__ void wv_set_move_blocks(wave_args &a, long long off) {
+  ww_set_move(a.w_gate4, off); ww_set_move(a.w_rs4, off);
+}
+__device__ __forceinline__ void wv_set_move_head(wave_args &a, long long off) {
+  ww_set_move(a.d_w1_4, off); ww_set_move(a.d_b1, off); ww_set_move(a.d_w2_4, off); ww_set_move(a.d_b2, off);
+}
+// name_: `a` itself (SET = false), or a copy of it - the whole struct, so that a field added later cannot be missing from it - whose
+// pointers mover_ has moved on by set_off.  The copy is made where the phase that reads it begins (the empty asm makes the moved
+// pointers values of THAT place: formed at the top they were held from there), and nothing indexes into it: the dilations, the one
+// array of wave_args, are read from `a` itself (wv_block_t's DIL = 2) - an index into a local copy would keep it in scratch memory.
+#define WV_SET_VIEW(name_, mover_)                                          \
+  wave_args name_##_m;                                                      \
+  if constexpr (SET) {                                                      \
+    name_##_m = a;                                                          \
+    long long off_ = set_off;                                               \
+    asm volatile("" : "+s"(off_));                                          \
+    mover_(name_##_m, off_);                                                \
+  }                                                                         \
+  const wave_args &name_ = SET ? name_##_m : a;
+template <bool HEAD_ONLY, bool SPLIT_BF16, int WV_NW, bool FP32T = false, int TICK = 0, bool SET = false>
+__global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC : 3) : 2) void wavenet_kernel(wave_args a, ww_set_ref set) {
+  static_assert(!SET || (FP32T && !HEAD_ONLY), "model sets run the fp32 transposed forms");
+  [[maybe_unused]] long long set_off = 0;
+  if constexpr (SET) {
+    const int wg = blockIdx.x;
+    set_off = ww_set_offset(set, TICK ? wg >> 1 : set.aux ? set.aux[wg] / WW_STREAM_GXC : wg);
+  }
   constexpr int WV_MPW = 12 / WV_NW, WV_THREADS = WV_NW * 64;
   static_assert(!TICK || (WV_NW == 12 && !HEAD_ONLY), "the one-launch tick runs twelve waves x one tile");
   constexpr bool TRANSPOSED = SPLIT_BF16 || FP32T;  // state layout: lane = time column, four consecutive channels per register quad
@@ -539,10 +582,11 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
   }
 
   // the input conv's operands: requested now, used behind the staging
+  WV_SET_VIEW(af, wv_set_move_front)
   float4 bw[3];
 #pragma unroll
-  for (int kb = 0; kb < 3; ++kb) bw[kb] = *(const float4 *)(a.w_in4 + ((size_t)(kb * 4 + kk) * 16 + j) * 4);
-  const float bias = a.b_in[j];
+  for (int kb = 0; kb < 3; ++kb) bw[kb] = *(const float4 *)(af.w_in4 + ((size_t)(kb * 4 + kk) * 16 + j) * 4);
+  const float bias = af.b_in[j];
   // ... and what the block loop's LDS tables are filled from (split-bf16: parameter pages 0 and 1 and the BatchNorm table; fp32
   // transposed: the per-block vector table): requested here, parked in LDS once the staged input is dead - as loops of
   // "load, store" behind the input conv they were three to four round trips to L2 in a row on every window's critical path
@@ -569,7 +613,7 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
     for (int q = 0; q < NVT; ++q) {
       int i = tid + q * WV_THREADS;
       i = i < a.NB * WV_VT_BLK ? i : 0;
-      WV_VT_FETCH(vte[q], a, i);
+      WV_VT_FETCH(vte[q], af, i);
     }
   }
 
@@ -653,7 +697,7 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
   // ---- input 1x1 conv + ReLU -> x in accumulator layout.  m-tile mi of this wave covers rows
   // (wave*3 + mi)*16 .. +15; lane holds rows kk*4 + r, column j.
 #pragma unroll
-  for (int mi = 0; mi < WV_MPW; ++mi) WV_INPUT_TILE(TRANSPOSED, in_lds, (wave * WV_MPW + mi) * 16 + j, kk, bw, a.b_in, bias, x[mi], skip[mi]);
+  for (int mi = 0; mi < WV_MPW; ++mi) WV_INPUT_TILE(TRANSPOSED, in_lds, (wave * WV_MPW + mi) * 16 + j, kk, bw, af.b_in, bias, x[mi], skip[mi]);
   __syncthreads();  // in_lds is dead from here on
 
   if (FP32T) {
@@ -681,10 +725,12 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
       ubuf[b * 4 * UPL + k * UPL + o] = 0.f;
     }
     wv_wblk pw[2];
-    wv_wload(a, 0, j, kk, pw[0]);
+    WV_SET_VIEW(ab, wv_set_move_blocks)
+    wv_wload(ab, 0, j, kk, pw[0]);
     const int tl = wave * WV_MPW * 16 + j;  // this lane's time column in the wave's first tile (tile mi: + 16 mi)
     __syncthreads();               // table + zero rows
-    WV_BLOCKS_T(WV_MPW, UPL, false, a, ubuf, vtab, j, kk, tl, x, skip, pw);
+    if constexpr (SET) WV_BLOCKS_T(WV_MPW, UPL, false, 2, ab, ubuf, vtab, j, kk, tl, x, skip, pw, (float *)nullptr, 0, false, &a);
+    else WV_BLOCKS_T(WV_MPW, UPL, false, 0, a, ubuf, vtab, j, kk, tl, x, skip, pw);
     __syncthreads();
   } else if (!SPLIT_BF16) {
   // causal zero rows of both u buffers
@@ -953,7 +999,8 @@ __global__ __launch_bounds__(WV_NW * 64, WV_NW == 12 ? (SPLIT_BF16 ? WV_BF16_OCC
     }
   }
   wv_head_w hw;
-  wv_head_load(a, j, kk, hw);
+  WV_SET_VIEW(ah, wv_set_move_head)
+  wv_head_load(ah, j, kk, hw);
   float best = -INFINITY;
 #pragma unroll
   for (int mi = 0; mi < WV_MPW; ++mi) {
@@ -1062,8 +1109,16 @@ __device__ __forceinline__ void wv_zpos_advance(int32_t *zpos, int sid, int pos,
     if ((lane_) == 0) wv_zpos_advance((q_).zpos, sid_, pos, held, n_, P);                                                        \
   } while (0)
 
-template <int NW, bool STREAM, bool FEED = false>
-__global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(wave_args a, wave_seq_args q) {
+// SET (a causal bank created from a model set): the member of the workgroup's stream, set.ids[sid].
+template <int NW, bool STREAM, bool FEED = false, bool SET = false>
+__global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(wave_args a, wave_seq_args q, ww_set_ref set) {
+  static_assert(!SET || STREAM || FEED, "the batch sequence form takes one model");
+  if constexpr (SET) {
+    const long long off = ww_set_offset(set, FEED ? q.fsegs[blockIdx.x].sid : q.win_aux[blockIdx.x] & 0xffff);
+    wv_set_move_front(a, off);
+    wv_set_move_blocks(a, off);
+    wv_set_move_head(a, off);
+  }
   static_assert(!(STREAM && FEED) && (!FEED || NW == 1 || NW == 12), "a feed is not a tick; its forms are one wave and twelve");
   constexpr int CH = NW * 16, THREADS = NW * 64, UPL = (CH + WV_PAD) * 4;
   constexpr int U_F = 2 * 4 * UPL, H_F = CH * WV_S, IN_F = CH * WV_INLD, V_F = WV_VT_F, HB = 4 * WV_PAD * 4;
@@ -1093,6 +1148,20 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(
     const wv_seg sg = q.segs[w];
     row0 = sg.row0; n = sg.n; skipn = sg.skip;
   }
+  // (SET: the twelve-wave feed form, at the register limit of three waves per SIMD, came out one register over it with tid held
+  //  across the block loop.  Its later readers form tid again instead: the wave's first thread, kept as a scalar, plus the lane
+  //  number from mbcnt - through an empty asm, so that each reader's copy is a value of its own and not one hoisted to the top)
+  [[maybe_unused]] int s_wave0 = 0;
+  if constexpr (SET) s_wave0 = __builtin_amdgcn_readfirstlane(tid & ~63);
+  auto tid_again = [&]() -> int {
+    if constexpr (SET) {
+      int base = s_wave0;
+      asm volatile("" : "+s"(base));
+      return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)base));
+    } else {
+      return tid;
+    }
+  };
   for (int i = tid; i < a.NB * WV_VT_BLK; i += THREADS) {  // all blocks' small vectors
     WV_VT_FETCH(vtab[i], a, i);
   }
@@ -1108,7 +1177,7 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(
     // (the thread's coordinates as values the compiler cannot move out of the chunk loop: the per-lane addresses of the staging,
     //  the input conv and - formed again behind the block loop - the head would otherwise be held, i.e. spilled, across the block
     //  loop, which runs at the register limit of three waves per SIMD)
-    int tc = tid;
+    int tc = tid_again();
     asm volatile("" : "+v"(tc));
     const int wc = tc >> 6, jc = tc & 15, kc = (tc >> 4) & 3;
     const int tl = wc * 16 + jc;  // this lane's time column in the chunk
@@ -1139,9 +1208,9 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(
     wv_wblk pw[2];
     wv_wload(a, 0, jc, kc, pw[0]);
     __syncthreads();  // in_lds is dead from here on
-    WV_BLOCKS_T(1, UPL, true, a, ubuf, vtab, jc, kc, tl, x, skip, pw, hist, valid, wc == 0);
+    WV_BLOCKS_T(1, UPL, true, (SET ? 1 : 0), a, ubuf, vtab, jc, kc, tl, x, skip, pw, hist, valid, wc == 0);
     // ---- a kept row's skip sum and logits
-    int td = tid;
+    int td = tid_again();
     asm volatile("" : "+v"(td));
     const int wd = td >> 6, jd = td & 15, kd = (td >> 4) & 3;
     const int ts = c0 + wd * 16 + jd;  // this lane's time column, in rows of the segment
@@ -1167,7 +1236,7 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(
   if (STREAM || (FEED && (fflags & 2))) {  // the history returns to the stream's state (a feed: from the stream's last segment)
     __syncthreads();
     f32x4 *sp = (f32x4 *)(q.state + (size_t)sid * a.NB * HB);
-    for (int i = tid; i < a.NB * HB / 4; i += THREADS) sp[i] = ((const f32x4 *)hist)[i];
+    for (int i = tid_again(); i < a.NB * HB / 4; i += THREADS) sp[i] = ((const f32x4 *)hist)[i];
   }
 }
 
@@ -1304,19 +1373,20 @@ static int wave_model_args(ww_ctx *ctx, const ww_wave_dev &v, const float *d_mel
 // ONCE, and its launch.  The transposed forms run twelve waves x one tile up to wave_wide_from(m) windows per launch and four waves x
 // three tiles above; the row-major loop and the one-launch tick (TICK = 1 / 2: fp32 / fp64 transform) have the twelve-wave form only.
 static int wave_wide_from(const ww_model *m) { return m->precision == WW_PRECISION_BF16X3 ? WV_BF16_WIDE_FROM : WV_F32_WIDE_FROM; }
-template <bool SPLIT_BF16, bool FP32T, int TICK>
-static void wave_launch_form(ww_ctx *ctx, int nw, bool wide, const wave_args &a) {
+template <bool SPLIT_BF16, bool FP32T, int TICK, bool SET = false>
+static void wave_launch_form(ww_ctx *ctx, int nw, bool wide, const wave_args &a, const ww_set_ref &set = ww_set_ref{}) {
   if constexpr (TICK == 0 && (SPLIT_BF16 || FP32T)) {
     if (wide) {
-      hipLaunchKernelGGL((wavenet_kernel<false, SPLIT_BF16, 4, FP32T>), dim3(nw), dim3(4 * 64), 0, ctx->stream, a);
+      hipLaunchKernelGGL((wavenet_kernel<false, SPLIT_BF16, 4, FP32T, 0, SET>), dim3(nw), dim3(4 * 64), 0, ctx->stream, a, set);
       return;
     }
   }
-  hipLaunchKernelGGL((wavenet_kernel<false, SPLIT_BF16, 12, FP32T, TICK>), dim3(nw), dim3(12 * 64), 0, ctx->stream, a);
+  hipLaunchKernelGGL((wavenet_kernel<false, SPLIT_BF16, 12, FP32T, TICK, SET>), dim3(nw), dim3(12 * 64), 0, ctx->stream, a, set);
 }
 template <int TICK>
-static void wave_launch(ww_ctx *ctx, const ww_model *m, int nw, const wave_args &a) {
+static void wave_launch(ww_ctx *ctx, const ww_model *m, int nw, const wave_args &a, const ww_set_ref *set = nullptr) {
   const bool wide = nw > wave_wide_from(m);
+  if (set) return wave_launch_form<false, true, TICK, true>(ctx, nw, wide, a, *set);  // (a set's view: fp32, transposed)
   if (m->precision == WW_PRECISION_BF16X3) wave_launch_form<true, false, TICK>(ctx, nw, wide, a);
   else if (m->opt_wave_rowmajor) wave_launch_form<false, false, TICK>(ctx, nw, wide, a);
   else wave_launch_form<false, true, TICK>(ctx, nw, wide, a);
@@ -1324,7 +1394,7 @@ static void wave_launch(ww_ctx *ctx, const ww_model *m, int nw, const wave_args 
 
 int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
                       const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int nw, void *, size_t, float *d_out,
-                      float *d_enc, const ww_tick_tag *tag) {
+                      float *d_enc, const ww_tick_tag *tag, const ww_set_ref *set) {
   if (nw <= 0) return WW_OK;
   wave_args a;
   if (int rc = wave_model_args(ctx, m->wave, d_mel, a)) return rc;
@@ -1339,7 +1409,7 @@ int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
   // tile in both forms: a posterior does not depend on the launch size (tests/test_gpu_parity.py).  (Six waves x two tiles -
   // also two workgroups per CU - lose at every size: 2,393 us.)
   // (round 5) fp32: the same two forms as the split-bf16 loop, the same bits in both
-  wave_launch<0>(ctx, m, nw, a);
+  wave_launch<0>(ctx, m, nw, a, set);
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
 }
@@ -1365,7 +1435,7 @@ int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const
   wave_seq_args q = {};
   q.segs = d_segs; q.enc = d_enc; q.logits = d_logits;
   ww_launch_scope scope(ctx, "wavenet_seq_kernel");
-  hipLaunchKernelGGL((wavenet_seq_kernel<12, false>), dim3(n_segs), dim3(12 * 64), 0, ctx->stream, a, q);
+  hipLaunchKernelGGL((wavenet_seq_kernel<12, false>), dim3(n_segs), dim3(12 * 64), 0, ctx->stream, a, q, ww_set_ref{});
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
 }
@@ -1399,7 +1469,7 @@ int ww_k_wave_pool(ww_ctx *ctx, const float *d_z, int64_t rows, int64_t row_end,
 // A causal bank's tick (streams.hip): workgroup w advances stream win_aux[w] & 0xffff by its win_valid[w] new mel rows
 int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, const int64_t *d_win_row, const int32_t *d_win_valid,
                           const int32_t *d_win_aux, int nw, float *d_state, float *d_zring, int32_t *d_zpos, float *d_out,
-                          const ww_tick_tag *tag) {
+                          const ww_tick_tag *tag, const ww_set_ref *set) {
   if (nw <= 0) return WW_OK;
   if (int rc = wave_seq_check(ctx, m, "causal streaming tick")) return rc;
   wave_args a;
@@ -1409,7 +1479,8 @@ int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, c
   q.win_row = d_win_row; q.win_valid = d_win_valid; q.win_aux = d_win_aux;
   q.state = d_state; q.zring = d_zring; q.zpos = d_zpos; q.out = d_out; q.P = m->wave.T;
   ww_launch_scope scope(ctx, "wavenet_seq_kernel<stream>");
-  hipLaunchKernelGGL((wavenet_seq_kernel<1, true>), dim3(nw), dim3(64), 0, ctx->stream, a, q);
+  if (set) hipLaunchKernelGGL((wavenet_seq_kernel<1, true, false, true>), dim3(nw), dim3(64), 0, ctx->stream, a, q, *set);
+  else hipLaunchKernelGGL((wavenet_seq_kernel<1, true>), dim3(nw), dim3(64), 0, ctx->stream, a, q, ww_set_ref{});
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
 }
@@ -1418,7 +1489,7 @@ int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, c
 // form, above the twelve-wave form with its tail as two small kernels; a call may launch both.
 int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv_feed_seg *d_segs, int n_small, int n_segs,
                    const wv_feed_pool *d_pool, int n_pool, const wv_feed_pool *d_ring, int n_ring, float *d_z, float *d_state,
-                   float *d_zring, int32_t *d_zpos, int pidx, float *d_post) {
+                   float *d_zring, int32_t *d_zpos, int pidx, float *d_post, const ww_set_ref *set) {
   if (n_segs <= 0) return WW_OK;
   if (int rc = wave_seq_check(ctx, m, "ww_stream_feed")) return rc;
   wave_args a;
@@ -1429,7 +1500,8 @@ int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv
   if (n_small > 0) {
     q.fsegs = d_segs;
     ww_launch_scope scope(ctx, "wavenet_seq_kernel<feed,1>");
-    hipLaunchKernelGGL((wavenet_seq_kernel<1, false, true>), dim3(n_small), dim3(64), 0, ctx->stream, a, q);
+    if (set) hipLaunchKernelGGL((wavenet_seq_kernel<1, false, true, true>), dim3(n_small), dim3(64), 0, ctx->stream, a, q, *set);
+    else hipLaunchKernelGGL((wavenet_seq_kernel<1, false, true>), dim3(n_small), dim3(64), 0, ctx->stream, a, q, ww_set_ref{});
     WW_HIP(ctx, hipGetLastError());
   }
   if (n_segs > n_small) {
@@ -1437,7 +1509,8 @@ int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv
     q.logits = d_z;
     {
       ww_launch_scope scope(ctx, "wavenet_seq_kernel<feed,12>");
-      hipLaunchKernelGGL((wavenet_seq_kernel<12, false, true>), dim3(n_segs - n_small), dim3(12 * 64), 0, ctx->stream, a, q);
+      if (set) hipLaunchKernelGGL((wavenet_seq_kernel<12, false, true, true>), dim3(n_segs - n_small), dim3(12 * 64), 0, ctx->stream, a, q, *set);
+      else hipLaunchKernelGGL((wavenet_seq_kernel<12, false, true>), dim3(n_segs - n_small), dim3(12 * 64), 0, ctx->stream, a, q, ww_set_ref{});
       WW_HIP(ctx, hipGetLastError());
     }
     ww_launch_scope scope(ctx, "wave_feed_pool_kernels");
@@ -1460,7 +1533,7 @@ bool ww_wave_tick_capable(const ww_model *m, int S) {
 }
 
 // ONE launch per tick (wavenet_kernel<..., TICK>): 2 S workgroups of twelve waves, the posteriors as tags only
-int ww_k_wave_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, const ww_tick_tag &tag) {
+int ww_k_wave_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, const ww_tick_tag &tag, const ww_set_ref *set) {
   const ww_wave_dev &v = m->wave;
   const ww_filter_dev &f = m->filt;
   if (f.n_mel != 40 || v.n_mel != 40 || fe.hop != 160 || v.T + 10 > WV_T)
@@ -1473,8 +1546,8 @@ int ww_k_wave_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int pre
   a.fe = fe;
   a.fb = ww_fe_filt_of(f);
   ww_launch_scope scope(ctx, m->precision == WW_PRECISION_BF16X3 ? "wavenet_kernel<bf16x3,tick>" : "wavenet_kernel<tick>");
-  if (precise) wave_launch<2>(ctx, m, 2 * fe.S, a);
-  else wave_launch<1>(ctx, m, 2 * fe.S, a);
+  if (precise) wave_launch<2>(ctx, m, 2 * fe.S, a, set);
+  else wave_launch<1>(ctx, m, 2 * fe.S, a, set);
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
 }
@@ -1484,7 +1557,7 @@ int ww_k_wave_detect(ww_ctx *ctx, const ww_model *m, const float *d_enc, int nw,
   wave_args a = wave_head_args(m->wave);
   a.out = d_out; a.enc_in = d_enc;
   ww_launch_scope scope(ctx, "wavenet_detect_kernel");
-  hipLaunchKernelGGL((wavenet_kernel<true, false, 12>), dim3(nw), dim3(12 * 64), 0, ctx->stream, a);
+  hipLaunchKernelGGL((wavenet_kernel<true, false, 12>), dim3(nw), dim3(12 * 64), 0, ctx->stream, a, ww_set_ref{});
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
 }

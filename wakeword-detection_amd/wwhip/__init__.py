@@ -4,7 +4,7 @@ Importing this package touches no GPU and loads no native code; the HIP library 
 first use and there is no CPU fallback for the hot path.
 """
 __all__ = ["RingBuffer", "SpeechContext", "SpeechPipeline", "ActivationTimeout", "TFLiteModel", "Filter",
-           "WakewordTrigger", "WakewordBank", "Engine", "StreamBank", "get_posterior", "far_frr",
+           "WakewordTrigger", "WakewordBank", "Engine", "ModelSet", "StreamBank", "get_posterior", "far_frr",
            "ContextBank", "SpeechPipelineBank", "VadBank", "ActivationTimeoutBank"]
 
 
@@ -13,7 +13,7 @@ def __getattr__(name):
     table = {
         "RingBuffer": "ring_buffer", "SpeechContext": "context", "SpeechPipeline": "pipeline",
         "ActivationTimeout": "activation_timeout", "TFLiteModel": "models", "Filter": "filter",
-        "WakewordTrigger": "wakeword", "WakewordBank": "wakeword", "Engine": "engine", "StreamBank": "engine",
+        "WakewordTrigger": "wakeword", "WakewordBank": "wakeword", "Engine": "engine", "ModelSet": "engine", "StreamBank": "engine",
         "get_posterior": "evaluate", "far_frr": "evaluate",
         "ContextBank": "context", "SpeechPipelineBank": "pipeline", "VadBank": "vad", "ActivationTimeoutBank": "activation_timeout",
     }

@@ -25,6 +25,7 @@ PRECISION_FP32, PRECISION_BF16X3 = 0, 1
 OPT_CRNN_SPLIT_AT, OPT_CRNN_SLIDE_MIN, OPT_CRNN_TAIL_MFMA, OPT_WAVENET_ROWMAJOR, OPT_WAVE_SEQ_SEGMENT = 1, 2, 3, 4, 5
 STREAM_FULL_RECOMPUTE, STREAM_TWO_LAUNCH, STREAM_SYNC_WAIT, STREAM_CAUSAL = 1, 2, 4, 8
 SAMPLE_I16, SAMPLE_F32 = 0, 1
+SET_MAX_MODELS = 64  # include/wwhip.h: WW_SET_MAX_MODELS
 ABI = 4  # include/wwhip.h: WW_ABI - the signatures this binding was written against
 
 
@@ -80,6 +81,9 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_model_get_info": (C.c_int, [_vp, _P(ModelInfo)]),
     "ww_model_set_precision": (C.c_int, [_vp, C.c_int]),
     "ww_model_set_option": (C.c_int, [_vp, C.c_int, _i64]),
+    "ww_model_set_create": (C.c_int, [_vp, _P(_vp), _i32, _P(_vp)]),
+    "ww_model_set_destroy": (C.c_int, [_vp]),
+    "ww_model_set_info": (C.c_int, [_vp, _P(ModelInfo), _P(_i32)]),
     "ww_num_frames": (_i64, [_i64, _i32]),
     "ww_logmel": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _P(FrontendParams), _vp, _vp]),
     "ww_logmel_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _P(FrontendParams), _vp, _vp]),
@@ -96,11 +100,14 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_forward_enc": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp]),
     "ww_slide_forward": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _P(_i64)]),
     "ww_forward_windows_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "ww_set_forward_windows_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp]),
     "ww_forward_segments_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
     "ww_wave_sequence_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ww_wave_sequence": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ww_clips_forward_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _P(FrontendParams), _vp]),
     "ww_stream_create": (C.c_int, [_vp, _vp, _i32, _P(FrontendParams), C.c_uint32, _P(_vp)]),
+    "ww_stream_create_set": (C.c_int, [_vp, _vp, _i32, _vp, _P(FrontendParams), C.c_uint32, _P(_vp)]),
+    "ww_stream_set_model": (C.c_int, [_vp, _vp, _i32, _i32]),
     "ww_stream_destroy": (C.c_int, [_vp]),
     "ww_stream_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ww_stream_reset": (C.c_int, [_vp, _vp, _i32]),
@@ -128,7 +135,8 @@ _lock = threading.Lock()
 import atexit
 import weakref
 
-_live = {"uploaders": weakref.WeakSet(), "resamplers": weakref.WeakSet(), "streams": weakref.WeakSet(), "models": weakref.WeakSet(), "contexts": weakref.WeakSet()}
+_live = {"uploaders": weakref.WeakSet(), "resamplers": weakref.WeakSet(), "streams": weakref.WeakSet(), "sets": weakref.WeakSet(), "models": weakref.WeakSet(),
+         "contexts": weakref.WeakSet()}
 _shutdown = False
 
 
@@ -142,7 +150,7 @@ def is_shutdown() -> bool:
 
 def _close_all() -> None:
     global _shutdown
-    for kind in ("uploaders", "resamplers", "streams", "models", "contexts"):
+    for kind in ("uploaders", "resamplers", "streams", "sets", "models", "contexts"):
         for obj in list(_live[kind]):
             try:
                 obj.close()

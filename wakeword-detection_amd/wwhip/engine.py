@@ -7,6 +7,7 @@ argument marshalling.  The reference-shaped classes (``Filter``, ``TFLiteModel``
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -336,28 +337,179 @@ class Engine:
                                                     _lib.ptr(r0), _lib.ptr(nw), int(r0.size), int(hop), C.c_void_p(d_out_ptr)))
 
 
+def _member_ids(ids, n: int, n_models: int, what: str) -> np.ndarray:
+    """``ids`` as the int32 table the library takes: ``n`` entries, each a member of a set of ``n_models`` (``ValueError`` otherwise:
+    the library would refuse them too - ``WW_EINVAL`` - but a list of the wrong length it cannot see)."""
+    a = np.asarray(ids)
+    if a.ndim != 1 or a.size != n:
+        raise ValueError(f"{what} must have one entry per {'stream' if what == 'models' else 'window'} ({n}), got shape {a.shape}")
+    if a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() >= n_models):
+        raise ValueError(f"{what} must be integers in [0, {n_models}): the set's members")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+class ModelSet:
+    """Several model directories of ONE geometry resident as one ``ww_model_set``: every launch and every :class:`StreamBank` built
+    on it serves all of them - window ``w`` by member ``model_ids[w]``, stream ``s`` by member ``models[s]`` - behind one front
+    end.  Member ``k`` through the set gives the bits ``Engine(member k)`` gives.  fp32 only; what may be one set:
+    ``ww_model_set_create`` in include/wwhip.h (same kind, info, geometry and filter; ``ValueError`` otherwise).
+
+    ``model_dirs``: directories, or :class:`Engine` objects of the caller's (left open by :meth:`close`)."""
+
+    def __init__(self, model_dirs: Sequence, device: int = 0, ctx: Optional[_lib.Context] = None) -> None:
+        members = list(model_dirs)
+        if not 1 <= len(members) <= _lib.SET_MAX_MODELS:
+            raise ValueError(f"a model set has 1..{_lib.SET_MAX_MODELS} members, not {len(members)}")
+        self._own: List[Engine] = []
+        self.engines: List[Engine] = []
+        self._set = None
+        try:
+            for m in members:
+                if isinstance(m, Engine):
+                    self.engines.append(m)
+                else:
+                    ctx = ctx if ctx is not None else (self.engines[0].ctx if self.engines else _lib.default_context(device))
+                    e = Engine(m, device=device, ctx=ctx)
+                    self._own.append(e)
+                    self.engines.append(e)
+            self.ctx = self.engines[0].ctx
+            self._lib = _lib.load()
+            arr = (C.c_void_p * len(self.engines))(*[e.handle.value for e in self.engines])
+            h = C.c_void_p()
+            _lib.raise_for(self._lib.ww_model_set_create(self.ctx.handle, arr, len(self.engines), C.byref(h)), self.ctx.handle)
+            self._set = h
+        except Exception:
+            for e in self._own:
+                e.close()
+            raise
+        info, n = _lib.ModelInfo(), C.c_int32(0)
+        _lib.raise_for(self._lib.ww_model_set_info(h, C.byref(info), C.byref(n)), self.ctx.handle)
+        self.n_models = int(n.value)
+        self.kind, self.window, self.n_mel, self.n_bins, self.n_out = info.kind, info.window, info.n_mel, info.n_bins, info.n_out
+        self.enc_shape = (info.enc_rows, info.enc_width)
+        self.names = [os.path.basename(os.path.normpath(e.model_dir)) for e in self.engines]
+        _lib.register("sets", self)
+
+    @property
+    def handle(self):
+        return self._set
+
+    @property
+    def posterior_index(self) -> int:
+        return self.engines[0].posterior_index
+
+    @property
+    def is_crnn(self) -> bool:
+        return self.kind == _lib.KIND_CRNN
+
+    def __len__(self) -> int:
+        return self.n_models
+
+    def logmel(self, pcm: Sequence[np.ndarray], fp: Optional[_lib.FrontendParams] = None) -> List[np.ndarray]:
+        """The set's one front end (member 0's; every member's filter is the same bytes)."""
+        return self.engines[0].logmel(pcm, fp)
+
+    def forward_windows_dev(self, d_mel_ptr: int, mel_rows: int, d_win_row_ptr: int, d_win_valid_ptr: int, model_ids, n_windows: int,
+                            d_out_ptr: int, d_enc_ptr: int = 0) -> None:
+        """``ww_set_forward_windows_dev``: :meth:`Engine.forward_windows_dev` with window ``w`` evaluated by member
+        ``model_ids[w]`` (a host array).  Enqueued on the context's stream, not waited for."""
+        ids = _member_ids(model_ids, int(n_windows), self.n_models, "model_ids")
+        _lib.raise_for(self._lib.ww_set_forward_windows_dev(self.ctx.handle, self._set, C.c_void_p(d_mel_ptr), int(mel_rows),
+                                                            C.c_void_p(d_win_row_ptr), C.c_void_p(d_win_valid_ptr), _lib.ptr(ids), int(n_windows),
+                                                            C.c_void_p(d_out_ptr), C.c_void_p(d_enc_ptr) if d_enc_ptr else None), self.ctx.handle)
+
+    def _windows(self, windows: np.ndarray) -> np.ndarray:
+        w = np.ascontiguousarray(windows, dtype=np.float32)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.shape[1] != self.window or w.shape[2] != self.n_mel:
+            raise ValueError(f"Cannot set tensor: Dimension mismatch. Got {tuple(w.shape[1:])} but expected "
+                             f"{(self.window, self.n_mel)} per window")
+        return w
+
+    def _launch(self, w: np.ndarray, win: np.ndarray, ids: np.ndarray, want_enc: bool):
+        """One upload of the mel, one launch over the windows ``win`` (indices into ``w``), window ``i`` by member ``ids[i]``."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        n = int(win.size)
+        out = torch.empty((n, self.n_out), dtype=torch.float32, device=dev)
+        enc = torch.empty((n,) + self.enc_shape, dtype=torch.float32, device=dev) if want_enc else None
+        if n:
+            d_mel = torch.from_numpy(w.reshape(-1, self.n_mel)).to(dev)
+            d_row = torch.from_numpy(win.astype(np.int64) * self.window).to(dev)
+            d_valid = torch.full((n,), self.window, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)  # (torch's stream is not the context's)
+            self.forward_windows_dev(d_mel.data_ptr(), w.shape[0] * self.window, d_row.data_ptr(), d_valid.data_ptr(), ids, n,
+                                     out.data_ptr(), enc.data_ptr() if want_enc else 0)
+            self.ctx.synchronize()
+        return (out.cpu().numpy(), enc.cpu().numpy()) if want_enc else out.cpu().numpy()
+
+    def forward(self, windows: np.ndarray, model_ids, want_enc: bool = False):
+        """``[B, window, 40]`` -> detect rows ``[B, n_out]`` (and encoder output), window ``b`` by member ``model_ids[b]``."""
+        w = self._windows(windows)
+        ids = _member_ids(model_ids, w.shape[0], self.n_models, "model_ids")
+        return self._launch(w, np.arange(w.shape[0]), ids, want_enc)
+
+    def forward_all(self, windows: np.ndarray, want_enc: bool = False):
+        """``[B, window, 40]`` -> ``[K, B, n_out]``: every window by every member - the table built on the host, ONE launch of
+        ``K * B`` windows over ONE upload of the mel (K :meth:`Engine.forward` calls upload it K times and launch K times)."""
+        w = self._windows(windows)
+        B, K = w.shape[0], self.n_models
+        got = self._launch(w, np.tile(np.arange(B), K), np.repeat(np.arange(K, dtype=np.int32), B), want_enc)
+        if want_enc:
+            return got[0].reshape(K, B, self.n_out), got[1].reshape((K, B) + self.enc_shape)
+        return got.reshape(K, B, self.n_out)
+
+    def close(self) -> None:
+        if self._set and not _lib.is_shutdown():
+            self._lib.ww_model_set_destroy(self._set)
+        self._set = None
+        for e in self._own:
+            e.close()
+        self._own = []
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class StreamBank:
     """S device-resident streams advanced 20 ms per :meth:`step` (``ww_stream_*``)."""
 
-    def __init__(self, engine: Engine, n_streams: int, fp: Optional[_lib.FrontendParams] = None,
-                 full_recompute: bool = False, two_launch: bool = False, sync_wait: bool = False, causal: bool = False) -> None:
+    def __init__(self, engine, n_streams: int, fp: Optional[_lib.FrontendParams] = None,
+                 full_recompute: bool = False, two_launch: bool = False, sync_wait: bool = False, causal: bool = False,
+                 models: Optional[Sequence[int]] = None) -> None:
         """``full_recompute``: every streaming CRNN window recomputed from its mel rows (``WW_STREAM_FULL_RECOMPUTE``)
         instead of the incremental kernel.  ``two_launch``: the incremental CRNN's tick as a front-end kernel + a model kernel
         (``WW_STREAM_TWO_LAUNCH``; default: ONE launch per tick).  ``sync_wait``: wait for a tick with ``hipStreamSynchronize``
         instead of polling its posteriors in page-locked memory (``WW_STREAM_SYNC_WAIT``).  Same bits in every form.
         ``causal`` (fp32 Wavenet only, ``WW_STREAM_CAUSAL``): another model reading, not another form - the bank advances
         :meth:`Engine.sequence_forward` row by row from cached activations; a posterior is ``post_frames`` of the stream's rows
-        since its last reset (every sampled row advances the state; rows that arrive while ``is_speech`` is set emit)."""
+        since its last reset (every sampled row advances the state; rows that arrive while ``is_speech`` is set emit).
+        ``engine`` may be a :class:`ModelSet`: stream ``s`` is then served by member ``models[s]`` (default: all by member 0;
+        ``ww_stream_create_set``) and :meth:`set_model` moves streams between members; ``full_recompute`` is refused."""
         self.engine = engine
         self.S = int(n_streams)
+        is_set = isinstance(engine, ModelSet)
+        if models is not None and not is_set:
+            raise ValueError("models= names the members of a ModelSet: this bank is built on one Engine")
+        if is_set and full_recompute:
+            raise ValueError("full_recompute is not offered on a ModelSet")
+        ids = _member_ids(models, self.S, engine.n_models, "models") if models is not None else None
         self._lib = _lib.load()
         fp = fp or frontend_params()
         h = C.c_void_p()
         flags = ((_lib.STREAM_FULL_RECOMPUTE if full_recompute else 0) | (_lib.STREAM_TWO_LAUNCH if two_launch else 0)
                  | (_lib.STREAM_SYNC_WAIT if sync_wait else 0) | (_lib.STREAM_CAUSAL if causal else 0))
         self.causal = bool(causal)
-        _lib.raise_for(self._lib.ww_stream_create(engine.ctx.handle, engine.handle, self.S, C.byref(fp), flags, C.byref(h)),
-                       engine.ctx.handle)
+        if is_set:
+            _lib.raise_for(self._lib.ww_stream_create_set(engine.ctx.handle, engine.handle, self.S, _lib.ptr(ids), C.byref(fp), flags, C.byref(h)),
+                           engine.ctx.handle)
+        else:
+            _lib.raise_for(self._lib.ww_stream_create(engine.ctx.handle, engine.handle, self.S, C.byref(fp), flags, C.byref(h)),
+                           engine.ctx.handle)
         self._h = h
         _lib.register("streams", self)
         self._post = np.zeros((self.S, 2), np.float32)
@@ -421,6 +573,18 @@ class StreamBank:
         else:
             a = np.ascontiguousarray(ids, dtype=np.int32)
             _lib.raise_for(self._lib.ww_stream_reset(self._h, _lib.ptr(a), a.size), self.engine.ctx.handle)
+
+    def set_model(self, ids: Optional[Sequence[int]], model: int) -> None:
+        """Move the listed streams (``None``: all) to member ``model`` of the bank's :class:`ModelSet` and reset them
+        (``ww_stream_set_model``: a stream's cached activations belong to the model that made them)."""
+        if not isinstance(self.engine, ModelSet):
+            raise ValueError("set_model: this bank was not built on a ModelSet")
+        if not 0 <= int(model) < self.engine.n_models:
+            raise ValueError(f"model must be in [0, {self.engine.n_models})")
+        a = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        if a is not None and a.size and (a.min() < 0 or a.max() >= self.S):
+            raise ValueError("stream id out of range")
+        _lib.raise_for(self._lib.ww_stream_set_model(self._h, _lib.ptr(a), 0 if a is None else a.size, int(model)), self.engine.ctx.handle)
 
     def window(self, stream: int) -> np.ndarray:
         """Stream ``stream``'s newest ``[window, n_mel]`` mel window, the block the model reads (``ww_stream_window``: a
