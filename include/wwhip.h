@@ -431,6 +431,32 @@ int ww_stream_window(ww_streams *st, int32_t stream, float *out);
 int ww_stream_feed_rows(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs);
 int ww_stream_feed(ww_streams *st, const int32_t *ids, int32_t n, const int16_t *pcm, const int64_t *sample_offs, int64_t cap_rows,
                    int64_t *row_offs, float *post, float *mel);
+/* ---- a stream bank at another input rate than 16 kHz ----------------------------------------------------------------------------
+ * ww_stream_attach_resampler makes `st` a bank at r's input rate: ww_stream_step, ww_stream_step_trigger and ww_pipeline_bank_step
+ * then read `frames` as [S][F] int16, F = rate_in / 50 (ww_stream_frame_samples: F, or 320 for a plain bank), and ww_stream_feed /
+ * ww_stream_feed_rows take packets at rate_in.  One kernel in front of a tick's own resamples the S frames into the [S][320] block
+ * the tick kernels read; no other kernel of the bank changes, so every form a bank has (ww_stream_create and ww_stream_create_set;
+ * incremental CRNN in one and two launches, both waits, WW_STREAM_FULL_RECOMPUTE, the Wavenet window bank in one and two launches,
+ * WW_STREAM_CAUSAL) works at rate_in.
+ * Definition.  r has (up, down, half) (ww_resampler_info).  Let x be the samples a stream has received since its last reset,
+ * LEAVING OUT the frames of ticks in which bit 1 of is_speech froze it (a frozen stream's frame is dropped whole, as its 16 kHz
+ * frame is, and its resampling state stands still), y = ww_resample's int16 output for x (out_format WW_SAMPLE_I16) continued as
+ * if x went on, and D = ceil(half / down).  The stream's 16 kHz signal is
+ *     z[n] = 0 for n < D,   z[n] = y[n - D] for n >= D
+ * and after N input samples the bank has consumed exactly floor(N * up / down) samples of z - 320 per tick, each determined by
+ * the N samples because half < down * (D + 1); the delay (D = 34 samples, 2.1 ms, for the default filter at every standard rate
+ * >= 16 kHz, 68 at 8 kHz) is what lets a tick deliver 320 samples from the first tick on.  A bank at rate_in yields, for every
+ * stream and every call, THE BITS OF THE SAME BANK AT 16 kHz GIVEN z.  A fed stream with N inputs and k new ones advances by
+ * floor((N + k) * up / down) - floor(N * up / down) samples of z, to which the tick's framing rule applies; however a stream's
+ * samples are cut into packets, calls and ticks, the bits are the same.  ww_stream_reset and ww_stream_set_model also clear the
+ * listed streams' resampling state (the next sample is x[0], z starts with D zeros again).  A stream keeps
+ * max(ceil((D * down + half) / up) + 1, ceil(((D + 1) * down + half) / up)) input samples between calls.
+ * Allowed only on a bank that has neither ticked nor been fed since its creation (else WW_ESTATE).  WW_EINVAL, ww_last_error
+ * naming the reason: r of another context, rate_out != 16000, rate_in == 16000 (a plain bank), rate_in % 50 != 0 (a fractional
+ * 20 ms frame - 11025 Hz has 220.5 samples -: not offered in the tick; resample such a stream in front of the bank), a second
+ * attach, a geometry whose history + frame exceed what a tick stages (12288 samples).  The resampler must outlive the bank. */
+int ww_stream_attach_resampler(ww_streams *st, const ww_resampler *r);
+int ww_stream_frame_samples(const ww_streams *st, int32_t *out);
 /* ---- the pipeline's host stages for S streams in lock step (BASELINE config 5 at the plugin surface) --------------------------
  * The reference drives three stage objects per stream and 20 ms frame (spokestack/pipeline.py:25-28, stage list of demo.py:29-36),
  * each a few comparisons on the shared SpeechContext.  For S streams each stage is ONE pass over plain arrays the caller owns

@@ -1,0 +1,147 @@
+"""Stream banks at another rate than 16 kHz, on the host: csrc/stream_rate.h under Address + UB sanitizer (a stand-alone program),
+the same formulas against ``wwhip.resample``'s range arithmetic, the ctypes binding of the two new entry points, and the errors
+``StreamBank(sample_rate=...)`` finds before it touches a device."""
+import math
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_CSRC = os.path.join(_ROOT, "wakeword-detection_amd", "csrc")
+NEW_SYMBOLS = ["ww_stream_attach_resampler", "ww_stream_frame_samples"]
+
+# rate_in: (up, down, half, F, D, taps per output) - DESIGN.md 7.4's table for the default filter
+TABLE = {8000: (2, 1, 68, 160, 68, 69), 22050: (320, 441, 14934, 441, 34, 94), 24000: (2, 3, 102, 480, 34, 103),
+         32000: (1, 2, 68, 640, 34, 137), 44100: (160, 441, 14934, 882, 34, 187), 48000: (1, 3, 102, 960, 34, 205)}
+
+
+def _no_sanitizer_runtime(output):
+    """Did a -fsanitize build fail because this clang ships no runtime for it?  (tests/test_host_logic.py's rule.)"""
+    return re.search(r"libclang_rt\.|unsupported (option|argument)[^\n]*-fsanitize", output) is not None
+
+
+@pytest.fixture(scope="module")
+def check_run(tmp_path_factory):
+    """tests/native/stream_rate_check.cpp compiled with Address + UB sanitizer and run once, as a child process (nothing is loaded
+    into this interpreter): the finished process, or a skip where there is no compiler or no sanitizer runtime."""
+    cxx = "/opt/rocm/lib/llvm/bin/clang++"
+    if not os.path.exists(cxx):
+        cxx = shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no clang++ in this image")
+    exe = tmp_path_factory.mktemp("stream_rate") / "stream_rate_check"
+    b = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-I" + _CSRC,
+                        os.path.join(_ROOT, "tests", "native", "stream_rate_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    if b.returncode != 0 and _no_sanitizer_runtime(b.stderr + b.stdout):
+        pytest.skip("this clang has no sanitizer runtime: " + b.stderr[-300:])
+    assert b.returncode == 0, b.stderr[-2000:]
+    return subprocess.run([str(exe)], capture_output=True, text=True, timeout=120,
+                          env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1"))
+
+
+def test_stream_rate_header_under_sanitizers(check_run):
+    """csrc/stream_rate.h - F, D, the history length, the per-call output counts over random packet cuts, that every emitted output
+    is determined and its inputs still held, where a tick's kernel places each output, and the refusals - compiled alone with
+    Address + UB sanitizer and checked on the CPU (tests/native/stream_rate_check.cpp lists the properties)."""
+    r = check_run
+    last = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
+    assert r.returncode == 0 and last.startswith("ok ") and not r.stderr.strip(), (r.returncode, r.stdout[-500:], r.stderr[-3000:])
+    assert int(last.split()[1]) > 100000
+
+
+def test_stream_rate_header_is_host_only():
+    """stream_rate.h includes no HIP header and calls no HIP function, like launch_plan.h (its one concession: the function the
+    kernel shares is marked for both sides where a HIP compiler reads it)."""
+    text = open(os.path.join(_CSRC, "stream_rate.h")).read()
+    code = re.sub(r"//[^\n]*", "", text)
+    assert "hip/" not in code and "common.h" not in code and not re.search(r"\bhip[A-Z]\w*\(", code)
+    assert "__global__" not in code and "__shared__" not in code
+
+
+@pytest.mark.parametrize("zeros", [32, 8])
+def test_header_geometry_against_the_resamplers_range_arithmetic(check_run, zeros):
+    """What csrc/stream_rate.h computes (the check program's "geom" lines: up, down, half, F, D and the history length per rate)
+    against ``wwhip.resample`` alone: the filter is ``design``'s, D = ceil(half / down); after N samples floor(N up / down) samples
+    of z are consumed and each is ``determined``; the first input of the next output lies within the HEADER's history, over ticks
+    and random packets."""
+    from wwhip import resample as rs
+    geom = {}
+    for line in check_run.stdout.splitlines():
+        f = line.split()
+        if f and f[0] == "geom" and int(f[1]) == zeros:
+            geom[int(f[2])] = tuple(int(v) for v in f[3:])
+    rng = np.random.default_rng(zeros)
+    for rate in (8000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000):
+        up, down, half, _ = rs.design(rate, 16000, zeros=zeros)
+        F, D = rate // 50, -(-half // down)
+        assert rate in geom, (zeros, rate)
+        assert geom[rate][:5] == (up, down, half, F, D), (rate, geom[rate])
+        hist = geom[rate][5]
+        assert rate % 50 == 0 and F * up == 320 * down and half < down * (D + 1)
+        if zeros == 32 and rate in TABLE:
+            assert (up, down, half, F, D, rs.taps_per_output(up, half)) == TABLE[rate]
+        if zeros == 32:
+            assert D == (68 if rate == 8000 else 34)
+        aligned = -(-(D * down + half) // up) + 1
+        assert aligned <= hist <= aligned + down
+        if zeros == 32:
+            assert aligned <= 816
+        n = 0
+        for k in [F] * 3 + [int(v) for v in rng.integers(1, 3001, 60)] + [F, 1, F]:
+            z0, z1 = n * up // down, (n + k) * up // down
+            if k == F:
+                assert z1 - z0 == 320
+            n += k
+            assert z1 - D <= rs.determined(n, up, down, half)           # y[z1 - D - 1] is the last one emitted
+            assert rs.first_needed(max(z1 - D, 0), up, down, half) >= n - hist  # what the next output reads is still held
+        assert math.gcd(up, down) == 1 and 320 % up == 0  # a lane's phase repeats every tick
+
+
+def test_binding_covers_the_new_entry_points():
+    from wwhip import _lib
+    header = open(os.path.join(_ROOT, "include", "wwhip.h")).read()
+    assert re.search(r"#define WW_ABI 4\b", header) and _lib.ABI == 4
+    for name in NEW_SYMBOLS:
+        m = re.search(r"\bint " + name + r"\(([^;]*)\);", header)
+        assert m, f"{name} is not declared in include/wwhip.h"
+        assert name in _lib.SYMBOLS, f"{name} is not bound in wwhip/_lib.py"
+        assert len(_lib.SYMBOLS[name][1]) == m.group(1).count(",") + 1, name
+    lib = _lib.load()
+    for name in NEW_SYMBOLS:
+        assert hasattr(lib, name), name
+
+
+def test_host_detectable_errors_raise_before_any_device_call(monkeypatch):
+    from wwhip import _lib, engine
+    from wwhip.engine import StreamBank
+
+    def no_native(*a, **k):
+        raise AssertionError("a host-detectable error reached the native library")
+    monkeypatch.setattr(_lib, "load", no_native)
+    monkeypatch.setattr(_lib, "default_context", no_native)
+
+    class _Eng:
+        n_models = 1
+
+    class _Rs:
+        rate_in = 48000
+
+    with pytest.raises(ValueError, match="fractional frame"):
+        StreamBank(_Eng(), 2, sample_rate=11025)
+    with pytest.raises(ValueError, match="whole number"):
+        StreamBank(_Eng(), 2, sample_rate=0)
+    with pytest.raises(ValueError, match="resampler reads 48000"):
+        StreamBank(_Eng(), 2, sample_rate=44100, resampler=_Rs())
+    _Rs.rate_in = 16000
+    with pytest.raises(ValueError, match="plain bank"):
+        StreamBank(_Eng(), 2, resampler=_Rs())
+    # the frames' shape follows the bank's rate
+    bank = StreamBank.__new__(StreamBank)
+    bank.S, bank._shape, bank._keep, bank._h = 3, (3, 960), None, None
+    with pytest.raises(ValueError, match=r"\[3, 960\] int16"):
+        bank._frames_address(np.zeros((3, 320), np.int16))
+    assert bank._frames_address(np.zeros((3, 960), np.int16)) != 0

@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""Stream banks at another rate than 16 kHz: what a tick and a feed cost (profiles/stream_rate/measured.txt).
+
+  tick   S streams, is_speech = 1, 20 ms per tick at --rate through StreamBank(sample_rate=rate): p50 / p99 of the per-tick latency
+         (tick submitted on the host -> posteriors visible on the host).  --rate 16000 is the plain bank (tools/stream_latency.py's
+         number for one model).
+  push   what a caller had to do without a rate bank: S StreamResampler objects in front of a 16 kHz bank - per tick S push() calls
+         (each its own upload, launch, synchronise and download), the 16 kHz samples queued per stream, a tick of the 16 kHz bank
+         once every stream holds 320.  The same p50 / p99, the pushes included.
+  feed   a causal Wavenet bank fed S streams x --seconds in ONE call at --rate (16000: the plain bank's feed): milliseconds per call.
+
+One JSON line.  The single-rate modes use nothing this tool's commit added, so the file also runs on its parent."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "wakeword-detection_amd")]
+import numpy as np  # noqa: E402
+from wwhip.engine import Engine, StreamBank  # noqa: E402
+
+ASSETS = os.path.join(ROOT, "wakeword-detection_amd/assets/tf_lite_models")
+
+
+def _pct(lat):
+    return {"p50_us": float(np.percentile(lat, 50) * 1e6), "p99_us": float(np.percentile(lat, 99) * 1e6), "mean_us": float(lat.mean() * 1e6)}
+
+
+def tick(args):
+    eng = Engine(os.path.join(ASSETS, args.model))
+    kw = {} if args.rate == 16000 else {"sample_rate": args.rate}
+    bank = StreamBank(eng, args.streams, **kw)
+    F = args.rate // 50
+    rng = np.random.default_rng(0)
+    frames = np.clip(rng.normal(0, 2500, (64, args.streams, F)), -32768, 32767).astype(np.int16)
+    speech = np.ones(args.streams, np.uint8)
+    for t in range(100):
+        bank.step(frames[t % 64], speech)
+    lat = np.empty(args.ticks)
+    n_post = 0
+    for t in range(args.ticks):
+        t0 = time.perf_counter()
+        p, n = bank.step(frames[t % 64], speech)
+        lat[t] = time.perf_counter() - t0
+        n_post += int(n.sum())
+    out = dict(mode="tick", model=args.model, rate=args.rate, streams=args.streams, ticks=args.ticks, posteriors_per_tick=n_post / args.ticks, **_pct(lat))
+    if hasattr(bank, "timeline"):
+        out["host_phases_us"] = {k: round(v, 2) for k, v in bank.timeline().items()}
+    bank.close()
+    eng.close()
+    return out
+
+
+def push(args):
+    from wwhip.resample import StreamResampler
+    eng = Engine(os.path.join(ASSETS, args.model))
+    S, F = args.streams, args.rate // 50
+    bank = StreamBank(eng, S)
+    rs = [StreamResampler(args.rate, 16000, eng.ctx, dtype=np.int16) for _ in range(S)]
+    rng = np.random.default_rng(0)
+    frames = np.clip(rng.normal(0, 2500, (64, S, F)), -32768, 32767).astype(np.int16)
+    speech = np.ones(S, np.uint8)
+    queue = np.zeros((S, 4096), np.int16)
+    held = np.zeros(S, int)
+    block = np.zeros((S, 320), np.int16)
+
+    def one(t):
+        for s in range(S):
+            y = rs[s].push(frames[t % 64, s])
+            queue[s, held[s]:held[s] + len(y)] = y
+            held[s] += len(y)
+        if held.min() < 320:
+            return 0
+        block[:] = queue[:, :320]
+        queue[:, :-320] = queue[:, 320:]
+        held[:] -= 320
+        return int(bank.step(block, speech)[1].sum())
+    for t in range(20):
+        one(t)
+    lat = np.empty(args.ticks)
+    n_post = 0
+    for t in range(args.ticks):
+        t0 = time.perf_counter()
+        n_post += one(t)
+        lat[t] = time.perf_counter() - t0
+    bank.close()
+    for r in rs:
+        r.close()
+    eng.close()
+    return dict(mode="push", model=args.model, rate=args.rate, streams=S, ticks=args.ticks, posteriors_per_tick=n_post / args.ticks, **_pct(lat))
+
+
+def feed(args):
+    eng = Engine(os.path.join(ASSETS, "Wavenet"))
+    kw = {} if args.rate == 16000 else {"sample_rate": args.rate}
+    S, n = args.streams, int(args.rate * args.seconds)
+    rng = np.random.default_rng(0)
+    pk = [np.clip(rng.normal(0, 2500, n), -32768, 32767).astype(np.int16) for _ in range(S)]
+    ms = []
+    rows = 0
+    bank = StreamBank(eng, S, causal=True, **kw)
+    for rep in range(args.repeats + 1):  # (the first call sizes the scratch: not counted)
+        bank.reset()
+        t0 = time.perf_counter()
+        posts, _ = bank.feed(list(range(S)), pk)
+        ms.append((time.perf_counter() - t0) * 1e3)
+        rows = sum(len(p) for p in posts)
+    bank.close()
+    eng.close()
+    return dict(mode="feed", rate=args.rate, streams=S, seconds=args.seconds, rows=rows, ms_per_call=[round(v, 2) for v in ms[1:]],
+                median_ms=float(np.median(ms[1:])))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("mode", choices=["tick", "push", "feed"])
+    ap.add_argument("--rate", type=int, default=48000, help="the streams' sample rate (a multiple of 50; 16000 = a plain bank)")
+    ap.add_argument("--streams", type=int, default=128)
+    ap.add_argument("--ticks", type=int, default=3000)
+    ap.add_argument("--model", default="CRNN", choices=["CRNN", "Wavenet"])
+    ap.add_argument("--seconds", type=float, default=10.0, help="feed: audio per stream and call")
+    ap.add_argument("--repeats", type=int, default=3, help="feed: timed calls")
+    a = ap.parse_args()
+    print(json.dumps({"tick": tick, "push": push, "feed": feed}[a.mode](a)))

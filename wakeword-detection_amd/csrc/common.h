@@ -16,6 +16,7 @@
 #include "../../include/wwhip.h"
 #include "launch_plan.h"
 #include "model_layout.h"
+#include "stream_rate.h"
 
 #define WW_WAVE 64
 
@@ -271,6 +272,21 @@ int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv
 int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, const int64_t *d_win_row, const int32_t *d_win_valid,
                           const int32_t *d_win_aux, int nw, float *d_state, float *d_zring, int32_t *d_zpos, float *d_out,
                           const ww_tick_tag *tag, const ww_set_ref *set = nullptr);
+// A stream bank at another rate than 16 kHz (resample.hip; geometry and bookkeeping: stream_rate.h).  The state object belongs to the
+// bank (streams.hip) and borrows the resampler's tap table.  _create: WW_EINVAL with the refusal's reason.  _tick: the S frames
+// [S][F] -> the [S][320] int16 device block *d_frames that the tick's kernels then read, ONE kernel on the context's stream in front
+// of them; flags = the tick's (bit 1: the stream is frozen), ctl_dev = the tick's control words as the device sees them.
+// _advance: the 16 kHz samples `stream` would consume on k more input samples (no state moves).  _feed: see resample.hip.
+struct ww_resampler;
+struct ww_stream_rate;
+int ww_k_rate_create(ww_ctx *ctx, const ww_resampler *r, int S, ww_stream_rate **out);
+void ww_k_rate_destroy(ww_stream_rate *rt);
+int ww_k_rate_frame_samples(const ww_stream_rate *rt);
+void ww_k_rate_reset(ww_stream_rate *rt, const int32_t *ids, int count);  // ids == nullptr: streams 0 .. count - 1
+int64_t ww_k_rate_advance(const ww_stream_rate *rt, int stream, int64_t k);
+int ww_k_rate_tick(ww_stream_rate *rt, const int16_t *frames, const uint8_t *flags, const int32_t *ctl_dev, const int16_t **d_frames);
+int ww_k_rate_feed(ww_stream_rate *rt, const int32_t *ids, int n, const int16_t *pcm, const int64_t *sample_offs, const int64_t *offs16,
+                   const int16_t **d_pcm16, bool *moved);
 int ww_k_far_frr(ww_ctx *ctx, const float *d_pos, int64_t n_pos, const float *d_neg, int64_t n_neg, int win,
                  const double *d_thr, int n_thr, double *d_smoothed, unsigned long long *d_pos_cnt,
                  unsigned long long *d_fa_cnt);

@@ -94,6 +94,22 @@ __global__ __launch_bounds__(RS_THREADS) void resample_decim_kernel(const TIn *_
     if (m0 + r < t.out_end) rs_store(out + t.out_off + (m0 + r - t.out_first), acc[r]);
 }
 
+// The phase form's chain, shared with the stream banks' tick (stream_rate_tick_kernel): tap 0 of phase p is h[p + jmax * up], the
+// largest index <= half of the phase, and the R outputs of one item, `down` staged samples apart, take tap tt (tp[tt * up], tp =
+// taps + p) over x0[r * down + tt] in ascending tt - ascending k.
+__device__ __forceinline__ int rs_jmax(int half, int p, int up) { return (half - p) / up; }
+template <int R>
+__device__ __forceinline__ void rs_chains(float (&acc)[R], const float *x0, const float *tp, int up, int down, int tpp) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r] = 0.0f;
+#pragma unroll 8
+  for (int tt = 0; tt < tpp; ++tt) {
+    const float h = tp[(size_t)tt * up];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = fmaf(h, x0[r * down + tt], acc[r]);
+  }
+}
+
 template <int R, typename TIn, typename TOut>
 __global__ __launch_bounds__(RS_THREADS) void resample_phase_kernel(const TIn *__restrict__ in, TOut *__restrict__ out,
                                                                     const rs_tile *__restrict__ tiles, const float *__restrict__ taps,
@@ -108,18 +124,10 @@ __global__ __launch_bounds__(RS_THREADS) void resample_phase_kernel(const TIn *_
   const int p = (int)(e - A * up);                     // phase: m * down mod up of every output of this item
   const int q = (int)(((int64_t)p * dinv) % up);       // m mod up
   const int cq = (int)(((int64_t)q * down) / up);      // floor(m * down / up) = (m / up) * down + cq
-  const int jmax = (half - p) / up;                    // tap 0 is h[p + jmax * up], the largest index <= half of the phase
+  const int jmax = rs_jmax(half, p, up);
   const float *x0 = xs + (int)(A * R * down + cq - jmax - t.k_lo);  // sample of tap 0 of output r = 0
-  const float *tp = taps + p;
   float acc[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) acc[r] = 0.0f;
-#pragma unroll 8
-  for (int tt = 0; tt < tpp; ++tt) {
-    const float h = tp[(size_t)tt * up];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = fmaf(h, x0[r * down + tt], acc[r]);
-  }
+  rs_chains<R>(acc, x0, taps + p, up, down, tpp);
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int64_t m = (A * R + r) * up + q;
@@ -372,3 +380,243 @@ int ww_resample(ww_resampler *r, const void *in, int32_t in_format, const int64_
 }
 
 }  // extern "C"
+
+// ---- a stream bank at another rate than 16 kHz (streams.hip: ww_stream_attach_resampler) ---------------------------
+// The bank's kernels are untouched: ONE kernel in front of a tick turns the S streams' frames at the bank's rate (F = rate / 50
+// samples each, page-locked) into the [S][320] int16 block the tick kernels read their samples from.  The geometry and the
+// bookkeeping are stream_rate.h's (host only); the arithmetic is this file's rule - rs_load, ONE chain per output over the
+// resampler's own tap table, rs_store -, so a stream's 16 kHz samples are the one-shot's bits behind D zeros.
+// One workgroup per stream, one lane per output.  A stream's state is the last `hist` input samples as fp32 (right-aligned; of a
+// young stream only the last `held` are its own, what lies in front reads as zero - a reset is the host's `held = 0`, no kernel):
+// read into LDS in front of the frame by the one workgroup that writes it back, no order between workgroups.
+struct ww_stream_rate {
+  ww_ctx *ctx = nullptr;
+  const ww_resampler *r = nullptr;
+  rate_geom g;
+  int S = 0;
+  float *d_hist = nullptr;    // [S][hist]
+  int16_t *d_out = nullptr;   // [S][320]: the tick's 16 kHz samples (640 bytes per stream: the tick kernels load them 16 at a time)
+  // the tick's page-locked input: [S] rate_ctl | [S][F] int16.  ONE copy: the kernel that reads it precedes the tick's kernel on
+  // the stream, so it has ended when a polled tick's first tag arrives
+  char *h_in = nullptr, *h_in_dev = nullptr;
+  std::vector<int64_t> n;     // input samples since the stream's last reset, frozen ticks left out
+  char *d_scratch = nullptr;  // a feed's [table | packets | segments | 16 kHz samples | tiles], grown on demand
+  size_t scratch_cap = 0;
+};
+
+struct rate_tick_args {
+  const int16_t *frames;  // page-locked [S][F], from a 16-byte boundary, padded to whole 16-byte pieces
+  const rate_ctl *rc;     // page-locked [S]
+  const int32_t *ctl;     // the tick's own control words [S][4] (page-locked): bit 1 of word 2 = the stream is frozen
+  const float *taps;
+  float *hist;
+  int16_t *out;
+  int up, down, half, tpp, F, D, H;
+};
+
+#define RATE_THREADS WW_RATE_FRAME_OUT
+
+__global__ __launch_bounds__(RATE_THREADS) void stream_rate_tick_kernel(rate_tick_args a) {
+  extern __shared__ float xs[];  // [H history | F frame | WW_RATE_PAD zeros]
+  const int s = blockIdx.x, tid = threadIdx.x;
+  // The frame crosses the bus 16 bytes per lane, whatever F is: the aligned 16-byte pieces that cover its 2 F bytes (the first and
+  // the last may hold a neighbour's samples, which are dropped; the block is padded to whole pieces).  The first RATE_THREADS
+  // pieces are requested BEFORE the control words are looked at - one trip over the bus instead of two in a row.
+  const size_t b0 = (size_t)s * a.F * 2, a0 = b0 & ~(size_t)15;
+  const int n16 = (int)((b0 + (size_t)a.F * 2 - a0 + 15) >> 4), lead = (int)(b0 - a0) >> 1;
+  const uint4 *src = (const uint4 *)((const char *)a.frames + a0);
+  uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+  if (tid < n16) raw = src[tid];
+  const int flags = a.ctl[s * 4 + 2];
+  const int4 cw = ((const int4 *)a.rc)[s];  // res, zeros, held
+  if (flags & 2) return;  // frozen: the frame is dropped whole, history and output block stay
+  float *hist = a.hist + (size_t)s * a.H;
+  auto put = [&](int q, const uint4 &v) {  // piece q: samples 8 q - lead .. 8 q - lead + 7 of the frame
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int i = q * 8 + e - lead;
+      if (i >= 0 && i < a.F) xs[a.H + i] = rs_load((int16_t)(w[e >> 1] >> ((e & 1) * 16)));
+    }
+  };
+  if (tid < n16) put(tid, raw);
+  for (int q = tid + RATE_THREADS; q < n16; q += RATE_THREADS) put(q, src[q]);
+  for (int i = tid; i < a.H; i += RATE_THREADS) xs[i] = i >= a.H - cw.z ? hist[i] : 0.0f;
+  if (tid < WW_RATE_PAD) xs[a.H + a.F + tid] = 0.0f;
+  __syncthreads();
+  const rate_out_pos o = rate_position(a.up, a.down, a.D, tid, cw.x);
+  float acc[1];
+  rs_chains<1>(acc, xs + a.H + o.c - rs_jmax(a.half, o.p, a.up), a.taps + o.p, a.up, a.down, a.tpp);
+  rs_store(a.out + (size_t)s * WW_RATE_FRAME_OUT + tid, tid < cw.y ? 0.0f : acc[0]);
+  for (int i = tid; i < a.H; i += RATE_THREADS) hist[i] = xs[a.F + i];  // (every read of the row went through LDS above)
+}
+
+// A feed's splice: stream d.sid's segment = [the `held` samples it holds | its packet of k] as fp32 for the resample kernels, and its
+// new history behind their reads.  Workgroup (i, c) copies samples [c * RATE_SPLICE, +RATE_SPLICE) of the segment; history rows
+// are shorter than that, so workgroup (i, 0) is the row's one reader, and it is its one writer.
+#define RATE_SPLICE 16384
+struct rate_feed_str {
+  int64_t pk_off;   // the packet's first sample in the call's packet buffer
+  int64_t k;        // its samples (> 0)
+  int64_t seg_off;  // the segment's first sample in the call's segment buffer
+  int32_t sid, held;
+};
+__global__ __launch_bounds__(256) void stream_rate_splice_kernel(const int16_t *pk, const rate_feed_str *str, float *seg, float *hist, int H) {
+  extern __shared__ float nh[];  // [H]
+  const rate_feed_str d = str[blockIdx.x];
+  float *h = hist + (size_t)d.sid * H;
+  const int64_t tot = d.held + d.k, v0 = (int64_t)blockIdx.y * RATE_SPLICE;
+  if (v0 >= tot) return;
+  auto sample = [&](int64_t v) -> float { return v < d.held ? h[H - d.held + v] : rs_load(pk[d.pk_off + (v - d.held)]); };
+  const int64_t v1 = v0 + RATE_SPLICE < tot ? v0 + RATE_SPLICE : tot;
+  for (int64_t v = v0 + threadIdx.x; v < v1; v += 256) seg[d.seg_off + v] = sample(v);
+  if (blockIdx.y) return;
+  const int keep = (int)(tot < H ? tot : H);
+  for (int i = threadIdx.x; i < keep; i += 256) nh[i] = sample(tot - keep + i);
+  __syncthreads();  // the row has been read
+  for (int i = threadIdx.x; i < keep; i += 256) h[H - keep + i] = nh[i];
+}
+
+void ww_k_rate_destroy(ww_stream_rate *rt) {
+  if (!rt) return;
+  if (rt->d_hist) hipFree(rt->d_hist);
+  if (rt->d_out) hipFree(rt->d_out);
+  if (rt->d_scratch) hipFree(rt->d_scratch);
+  if (rt->h_in) hipHostFree(rt->h_in);
+  delete rt;
+}
+
+static int rate_destroy_(ww_stream_rate *rt) {
+  ww_k_rate_destroy(rt);
+  return WW_OK;
+}
+
+int ww_k_rate_create(ww_ctx *ctx, const ww_resampler *r, int S, ww_stream_rate **out) {
+  *out = nullptr;
+  if (r->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: the resampler belongs to another context");
+  char why[256];
+  rate_geom g;
+  if (rate_make_geom(r->rate_in, r->rate_out, r->up, r->down, r->half, r->tpp, g, why, sizeof why))
+    return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: %s", why);
+  ww_stream_rate *rt = new ww_stream_rate();
+  ww_scoped<ww_stream_rate, rate_destroy_> own(rt);
+  rt->ctx = ctx; rt->r = r; rt->g = g; rt->S = S;
+  rt->n.assign((size_t)S, 0);
+  // (the frames start on a 16-byte boundary and end in whole 16-byte pieces: the kernel loads them as uint4)
+  const size_t b_hist = (size_t)S * g.hist * 4, b_out = (size_t)S * WW_RATE_FRAME_OUT * 2,
+               b_in = (size_t)S * sizeof(rate_ctl) + (((size_t)S * g.F * 2 + 15) & ~(size_t)15) + 16;
+  if (hipMalloc((void **)&rt->d_hist, b_hist) != hipSuccess || hipMalloc((void **)&rt->d_out, b_out) != hipSuccess ||
+      hipHostMalloc((void **)&rt->h_in, b_in) != hipSuccess)
+    return ww_fail(ctx, WW_ENOMEM, "cannot allocate the resampling state of %d streams at %d Hz", S, g.rate_in);
+  if (((uintptr_t)rt->d_out & 15) != 0) return ww_fail(ctx, WW_EINTERNAL, "the tick's sample block is not 16-byte aligned");
+  memset(rt->h_in, 0, b_in);
+  WW_HIP(ctx, hipHostGetDevicePointer((void **)&rt->h_in_dev, rt->h_in, 0));
+  WW_HIP(ctx, hipMemsetAsync(rt->d_hist, 0, b_hist, ctx->stream));
+  WW_HIP(ctx, hipMemsetAsync(rt->d_out, 0, b_out, ctx->stream));
+  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *out = own.release();
+  return WW_OK;
+}
+
+int ww_k_rate_frame_samples(const ww_stream_rate *rt) { return rt->g.F; }
+
+void ww_k_rate_reset(ww_stream_rate *rt, const int32_t *ids, int count) {
+  for (int i = 0; i < count; ++i) rt->n[(size_t)(ids ? ids[i] : i)] = 0;
+}
+
+int64_t ww_k_rate_advance(const ww_stream_rate *rt, int stream, int64_t k) { return rate_advance(rt->g, rt->n[(size_t)stream], k).count; }
+
+int ww_k_rate_tick(ww_stream_rate *rt, const int16_t *frames, const uint8_t *flags, const int32_t *ctl_dev, const int16_t **d_frames) {
+  ww_ctx *ctx = rt->ctx;
+  const rate_geom &g = rt->g;
+  const int S = rt->S;
+  rate_ctl *rc = (rate_ctl *)rt->h_in;
+  for (int s = 0; s < S; ++s) {
+    if (flags[s] & 2) continue;
+    const rate_step st = rate_advance(g, rt->n[(size_t)s], g.F);
+    rc[s] = {st.res, (int32_t)st.zeros, st.held, 0};
+    rt->n[(size_t)s] += g.F;
+  }
+  memcpy(rt->h_in + (size_t)S * sizeof(rate_ctl), frames, (size_t)S * g.F * 2);
+  rate_tick_args a = {};
+  a.rc = (const rate_ctl *)rt->h_in_dev;
+  a.frames = (const int16_t *)(rt->h_in_dev + (size_t)S * sizeof(rate_ctl));
+  a.ctl = ctl_dev;
+  a.taps = rt->r->d_taps;
+  a.hist = rt->d_hist;
+  a.out = rt->d_out;
+  a.up = (int)g.up; a.down = (int)g.down; a.half = (int)g.half; a.tpp = (int)g.tpp; a.F = g.F; a.D = g.D; a.H = g.hist;
+  {
+    ww_launch_scope scope(ctx, "stream_rate_tick_kernel");
+    hipLaunchKernelGGL(stream_rate_tick_kernel, dim3((unsigned)S), dim3(RATE_THREADS), (size_t)(g.hist + g.F + WW_RATE_PAD) * 4, ctx->stream, a);
+  }
+  WW_HIP(ctx, hipGetLastError());
+  *d_frames = rt->d_out;
+  return WW_OK;
+}
+
+// A feed's packets at the bank's rate -> its 16 kHz samples on the device: stream ids[i]'s lie at (*d_pcm16)[offs16[i] .. offs16[i + 1]),
+// offs16 as ww_k_rate_advance counts them.  *moved: the streams' sample counts have advanced (a failure behind that point leaves the
+// bank's host mirrors and its device state out of step).
+int ww_k_rate_feed(ww_stream_rate *rt, const int32_t *ids, int n, const int16_t *pcm, const int64_t *sample_offs, const int64_t *offs16,
+                   const int16_t **d_pcm16, bool *moved) {
+  ww_ctx *ctx = rt->ctx;
+  const rate_geom &g = rt->g;
+  std::vector<rate_feed_str> str;
+  rs_plan pl;
+  int64_t seg_total = 0, k_max = 0;
+  const int64_t s0 = sample_offs[0], samples = sample_offs[n] - s0;
+  for (int i = 0; i < n; ++i) {
+    const int64_t k = sample_offs[i + 1] - sample_offs[i];
+    if (k == 0) continue;
+    const int s = ids[i];
+    const rate_step st = rate_advance(g, rt->n[(size_t)s], k);
+    str.push_back({sample_offs[i] - s0, k, seg_total, s, st.held});
+    if (st.count > st.zeros) {
+      // the segment's first sample is input n - held of the stream; its outputs land behind the zeros of the stream's 16 kHz run
+      const int64_t so[2] = {seg_total, seg_total + st.held + k}, in_first[1] = {rt->n[(size_t)s] - st.held}, out_first[1] = {st.y0},
+                    oo[2] = {offs16[i] + st.zeros, offs16[i + 1]};
+      rs_make_plan(rt->r, so, in_first, out_first, oo, 1, pl);
+    }
+    seg_total += st.held + k;
+    k_max = std::max(k_max, st.held + k);
+  }
+  if (str.size() > 0x7fffffffu || pl.count() > 0x7fffffffu || (k_max + RATE_SPLICE - 1) / RATE_SPLICE > 65535)
+    return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: too much work for one call");
+  ww_tables tb;
+  tb.add(str);
+  const size_t b_tab = tb.bytes(), b_pk = ww_bump::need((size_t)samples, 2), b_seg = ww_bump::need((size_t)seg_total, 4),
+               b_z = ww_bump::need((size_t)offs16[n], 2), b_tiles = ww_bump::need(pl.count(), sizeof(rs_tile));
+  const size_t need = b_tab + b_pk + b_seg + b_z + b_tiles + 1024;
+  if (need > rt->scratch_cap) {
+    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rt->d_scratch) WW_HIP(ctx, hipFree(rt->d_scratch));
+    rt->d_scratch = nullptr;
+    rt->scratch_cap = 0;
+    if (hipMalloc((void **)&rt->d_scratch, need) != hipSuccess)
+      return ww_fail(ctx, WW_ENOMEM, "ww_stream_feed: cannot allocate %zu bytes for the call's samples at %d Hz", need, g.rate_in);
+    rt->scratch_cap = need;
+  }
+  ww_bump db(rt->d_scratch, rt->scratch_cap);
+  rate_feed_str *d_str = (rate_feed_str *)db.take<char>(b_tab);
+  int16_t *d_pk = db.take<int16_t>((size_t)samples);
+  float *d_seg = db.take<float>((size_t)seg_total);
+  int16_t *d_z = db.take<int16_t>((size_t)offs16[n]);
+  rs_tile *d_tiles = db.take<rs_tile>(pl.count());
+  *moved = true;
+  for (const rate_feed_str &d : str) rt->n[(size_t)d.sid] += d.k;
+  *d_pcm16 = d_z;
+  if (str.empty()) return WW_OK;
+  if (int rc = tb.send(ctx, d_str)) return rc;
+  WW_HIP(ctx, hipMemcpyAsync(d_pk, pcm + s0, (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
+  {
+    ww_launch_scope scope(ctx, "stream_rate_splice_kernel");
+    hipLaunchKernelGGL(stream_rate_splice_kernel, dim3((unsigned)str.size(), (unsigned)((k_max + RATE_SPLICE - 1) / RATE_SPLICE)), dim3(256),
+                       (size_t)g.hist * 4, ctx->stream, (const int16_t *)d_pk, (const rate_feed_str *)d_str, d_seg, rt->d_hist, (int)g.hist);
+  }
+  WW_HIP(ctx, hipGetLastError());
+  if (offs16[n] > 0) WW_HIP(ctx, hipMemsetAsync(d_z, 0, (size_t)offs16[n] * 2, ctx->stream));  // z's leading zeros
+  if (pl.count() > 0)
+    if (int rc = rs_run(rt->r, pl, d_tiles, d_seg, WW_SAMPLE_F32, d_z, WW_SAMPLE_I16)) return rc;
+  return WW_OK;
+}

@@ -99,6 +99,10 @@ struct ww_streams {
   std::vector<int32_t> stream_model;
   int32_t *d_stream_model = nullptr;  // [S]
   ww_set_ref set_ref;                 // {d_stream_model, nullptr, the set's stride}
+  // a bank at another rate than 16 kHz (ww_stream_attach_resampler): frames are [S][frame samples of that rate], and one kernel of
+  // resample.hip in front of a tick's own turns them into the [S][320] block the tick kernels read
+  ww_stream_rate *rate = nullptr;
+  bool used = false;                  // ticked or fed since creation
   // the kernels' extra argument: nullptr for a bank of one model
   const ww_set_ref *ref() const { return set ? &set_ref : nullptr; }
   int send_stream_model() {  // the host's copy -> the device table, in stream order (ww_tables::send, the one upload path)
@@ -338,6 +342,7 @@ int ww_stream_destroy(ww_streams *st) {
   void *host[] = {st->h_pack, st->h_out, st->h_tag};
   for (void *p : host)
     if (p) hipHostFree(p);
+  ww_k_rate_destroy(st->rate);
   delete st;
   return WW_OK;
   WW_GUARD_END(nullptr)
@@ -508,6 +513,30 @@ int ww_stream_create_set(ww_ctx *ctx, const ww_model_set *set, int32_t S, const 
   WW_GUARD_END(ctx)
 }
 
+// The bank becomes one at the resampler's input rate (include/wwhip.h).  The refusals that depend on the rates and the state object
+// are ww_k_rate_create's (resample.hip; stream_rate.h); no kernel of the bank changes, a tick only reads its samples elsewhere.
+int ww_stream_attach_resampler(ww_streams *st, const ww_resampler *r) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  ww_ctx *ctx = st->ctx;
+  if (!r) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: NULL resampler");
+  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
+  if (st->rate) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: this bank already has a resampler (%d Hz frames)", ww_k_rate_frame_samples(st->rate) * 50);
+  if (st->used) return ww_fail(ctx, WW_ESTATE, "ww_stream_attach_resampler: the bank has ticked or been fed: a resampler is attached to a new bank");
+  WW_ON_DEVICE(ctx, dev_scope);
+  return ww_k_rate_create(ctx, r, st->S, &st->rate);
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+int ww_stream_frame_samples(const ww_streams *st, int32_t *out) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  if (!out) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_samples: NULL argument");
+  *out = st->rate ? ww_k_rate_frame_samples(st->rate) : WW_CHUNK;
+  return WW_OK;
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
 // The listed streams move to another member of the bank's set and start afresh: the table first, then ww_stream_reset's kernels
 // behind it on the stream (they read the new member's gx_zero row).
 int ww_stream_set_model(ww_streams *st, const int32_t *ids, int32_t n, int32_t model) {
@@ -572,6 +601,7 @@ int ww_stream_reset(ww_streams *st, const int32_t *ids, int32_t n) {
     st->pos[s] = 0;
     st->rowq[s] = 0;
   }
+  if (st->rate) ww_k_rate_reset(st->rate, ids, count);  // the next sample is x[0] of a new signal: D zeros lead again
   return WW_OK;
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
@@ -641,6 +671,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   if (!frames || !is_speech || !post || !n_post) return ww_fail(ctx, WW_EINVAL, "NULL argument");
   WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
   *mutated = true;  // from here on the host's mirrors of the streams' state advance
+  st->used = true;
   const int S = st->S, hop = st->fp.hop, R = st->T + 1;
   uint64_t tl[WW_STREAM_TL_PHASES + 1];
   tl[0] = st_now_ns();
@@ -697,7 +728,13 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     st->rowq[s] = (st->rowq[s] + np) % WW_STREAM_GXC;
   }
   tl[1] = st_now_ns();
-  memcpy(h_frames, frames, (size_t)S * WW_CHUNK * 2);
+  // a bank at another rate: its frames go through ww_k_rate_tick's kernel into a device block, and the tick reads that
+  const int16_t *rate_frames = nullptr;
+  if (st->rate) {
+    if (int rc = ww_k_rate_tick(st->rate, frames, is_speech, (const int32_t *)(st->h_pack_dev + ((char *)h_ctl - st->h_pack)), &rate_frames)) return rc;
+  } else {
+    memcpy(h_frames, frames, (size_t)S * WW_CHUNK * 2);
+  }
   tl[2] = st_now_ns();
   const ww_model *m = st->model;
   // posterior element: width-1 head -> [0]; width-2 head -> [1]  
@@ -707,7 +744,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   if (st->one_launch) {
     // ---- ONE launch: front end + model, workgroup 2 s + k = window k of stream s (crnn.hip: crnn_stream_kernel<FE>; wavenet.hip)
     ww_tick_fe fe = {};
-    fe.frames = (const int16_t *)(st->h_pack_dev + ((char *)h_frames - st->h_pack));
+    fe.frames = rate_frames ? rate_frames : (const int16_t *)(st->h_pack_dev + ((char *)h_frames - st->h_pack));
     fe.ctl = (const int32_t *)(st->h_pack_dev + ((char *)h_ctl - st->h_pack));
     fe.ring = st->ring; fe.prev = st->prev; fe.hist = st->hist;
     fe.S = S; fe.HR = st->HR;
@@ -719,7 +756,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   } else {
     stream_fe_args a = {};
     // no copy engine on the tick's path: the kernel reads the pinned staging block itself
-    a.frames = (const int16_t *)(st->h_pack_dev + ((char *)st->h_frames - st->h_pack));
+    a.frames = rate_frames ? rate_frames : (const int16_t *)(st->h_pack_dev + ((char *)st->h_frames - st->h_pack));
     a.ctl = (const int32_t *)(st->h_pack_dev + ((char *)st->h_ctl - st->h_pack));
     a.h_row = (const int64_t *)(st->h_pack_dev + ((char *)st->h_win_row - st->h_pack));
     a.h_valid = (const int32_t *)(st->h_pack_dev + ((char *)st->h_win_valid - st->h_pack));
@@ -823,7 +860,10 @@ int ww_stream_step(ww_streams *st, const int16_t *frames, const uint8_t *is_spee
 // ---- ww_stream_feed: a causal bank advanced by any subset of its streams and any number of samples for each --------------------
 // The framing is the tick's rule for k samples instead of 320: tot = fill + k, rows = tot >= 512 ? (tot - 512) / 160 + 1 : 0,
 // fill' = tot - 160 rows.  Everything a refusal can depend on is looked at here, before any state moves.
-static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs, const char *what) {
+// A bank at another rate: k is what the packet's samples come to at 16 kHz (ww_k_rate_advance), and offs16 (n + 1 entries, from 0)
+// receives the sample_offs the rest of the feed then works with.
+static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs, const char *what,
+                      std::vector<int64_t> *offs16 = nullptr) {
   ww_ctx *ctx = st->ctx;
   if (!st->causal) return ww_fail(ctx, WW_EINVAL, "%s: only a bank created with WW_STREAM_CAUSAL can be fed (a window bank recomputes a window per row)", what);
   if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
@@ -832,13 +872,16 @@ static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64
   std::vector<uint8_t> seen((size_t)st->S, 0);
   int64_t rows = 0;
   row_offs[0] = 0;
+  if (offs16) offs16->assign((size_t)n + 1, 0);
   for (int i = 0; i < n; ++i) {
     const int s = ids[i];
     if (s < 0 || s >= st->S) return ww_fail(ctx, WW_EINVAL, "%s: stream id %d out of range", what, s);
     if (seen[s]) return ww_fail(ctx, WW_EINVAL, "%s: stream %d is named twice", what, s);
     seen[s] = 1;
-    const int64_t k = sample_offs[i + 1] - sample_offs[i];
+    int64_t k = sample_offs[i + 1] - sample_offs[i];
     if (k < 0) return ww_fail(ctx, WW_EINVAL, "%s: sample_offs descend at entry %d", what, i);
+    if (st->rate) k = ww_k_rate_advance(st->rate, s, k);
+    if (offs16) (*offs16)[(size_t)i + 1] = (*offs16)[(size_t)i] + k;
     const int64_t r = ww_fe_frames(st->fill[s] + k, st->fp.hop);
     if (r > 0x3fffffff || rows + r > 0x3fffffff) return ww_fail(ctx, WW_EINVAL, "%s: more than 2^30 rows in one call", what);
     rows += r;
@@ -850,19 +893,26 @@ static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64
 int ww_stream_feed_rows(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
-  return feed_check(st, ids, n, sample_offs, row_offs, "ww_stream_feed_rows");
+  std::vector<int64_t> offs16;
+  return feed_check(st, ids, n, sample_offs, row_offs, "ww_stream_feed_rows", &offs16);
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
 static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const int16_t *pcm, const int64_t *sample_offs, int64_t cap_rows,
                             int64_t *row_offs, float *post, float *mel, bool *mutated) {
   ww_ctx *ctx = st->ctx;
-  if (int rc = feed_check(st, ids, n, sample_offs, row_offs, "ww_stream_feed")) return rc;
-  const int64_t rows = row_offs[n], samples = n > 0 ? sample_offs[n] - sample_offs[0] : 0;
+  std::vector<int64_t> offs16;
+  if (int rc = feed_check(st, ids, n, sample_offs, row_offs, "ww_stream_feed", &offs16)) return rc;
+  const int64_t rows = row_offs[n], samples_in = n > 0 ? sample_offs[n] - sample_offs[0] : 0;
   if (cap_rows < rows) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: the call produces %lld rows, the buffers hold %lld", (long long)rows, (long long)cap_rows);
-  if (samples > 0 && !pcm) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: NULL sample buffer");
+  if (samples_in > 0 && !pcm) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: NULL sample buffer");
   if (rows > 0 && !post) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: NULL posterior buffer");
-  if (samples == 0) return WW_OK;  // nothing arrived: no stream moves
+  if (samples_in == 0) return WW_OK;  // nothing arrived: no stream moves
+  st->used = true;
+  // a bank at another rate: from here on the packets are their 16 kHz samples, which ww_k_rate_feed leaves on the device
+  const int64_t *in_offs = sample_offs;
+  if (st->rate) sample_offs = offs16.data();
+  const int64_t samples = sample_offs[n] - sample_offs[0];
   const ww_model *m = st->model;
   const int T = st->T, F = st->F, NO = st->NO, R = T + 1, hop = st->fp.hop, rf = ww_wave_receptive_field(m);
   if ((size_t)(WW_FEED_POOL_ROWS + T - 1) * 64 > 64 * 1024) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: windows of up to %d rows only", 1024 - WW_FEED_POOL_ROWS + 1);
@@ -891,6 +941,14 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
   float *d_z = large.empty() ? nullptr : db.take<float>((size_t)rows * NO);
   float *d_post = db.take<float>((size_t)rows);
   if (int rc = tb.send(ctx, d_tab)) return rc;
+  const int16_t *rate_pcm = nullptr;
+  if (st->rate) {
+    if (int rc = ww_k_rate_feed(st->rate, ids, n, pcm, in_offs, sample_offs, &rate_pcm, mutated)) return rc;
+    if (samples == 0) {  // the packets moved the streams' resampling state and completed no 16 kHz sample
+      WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      return WW_OK;
+    }
+  }
   // ---- from here on the host's mirrors of the streams' state advance
   *mutated = true;
   for (int i = 0; i < n; ++i) {
@@ -899,7 +957,11 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
     st->fill[s] = (int)(st->fill[s] + k - r * hop);
     st->pos[s] = (int)((st->pos[s] + r) % R);
   }
-  WW_HIP(ctx, hipMemcpyAsync(d_pcm, pcm + sample_offs[0], (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
+  if (rate_pcm) {
+    if (samples > 0) WW_HIP(ctx, hipMemcpyAsync(d_pcm, rate_pcm, (size_t)samples * 2, hipMemcpyDeviceToDevice, ctx->stream));
+  } else {
+    WW_HIP(ctx, hipMemcpyAsync(d_pcm, pcm + sample_offs[0], (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
+  }
   feed_fe_args a = {};
   a.pcm = d_pcm; a.str = d_str; a.grp = d_grp; a.rows = d_rows;
   a.ring = st->ring; a.hist = st->hist; a.prev = st->prev;

@@ -112,6 +112,8 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_stream_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ww_stream_reset": (C.c_int, [_vp, _vp, _i32]),
     "ww_stream_window": (C.c_int, [_vp, _i32, _vp]),
+    "ww_stream_attach_resampler": (C.c_int, [_vp, _vp]),
+    "ww_stream_frame_samples": (C.c_int, [_vp, _P(_i32)]),
     "ww_stream_feed_rows": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     "ww_stream_feed": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "ww_stream_timeline": (C.c_int, [_vp, _vp, _P(_i64), _i32]),

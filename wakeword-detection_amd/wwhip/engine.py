@@ -480,7 +480,7 @@ class StreamBank:
 
     def __init__(self, engine, n_streams: int, fp: Optional[_lib.FrontendParams] = None,
                  full_recompute: bool = False, two_launch: bool = False, sync_wait: bool = False, causal: bool = False,
-                 models: Optional[Sequence[int]] = None) -> None:
+                 models: Optional[Sequence[int]] = None, sample_rate: int = 16000, resampler=None) -> None:
         """``full_recompute``: every streaming CRNN window recomputed from its mel rows (``WW_STREAM_FULL_RECOMPUTE``)
         instead of the incremental kernel.  ``two_launch``: the incremental CRNN's tick as a front-end kernel + a model kernel
         (``WW_STREAM_TWO_LAUNCH``; default: ONE launch per tick).  ``sync_wait``: wait for a tick with ``hipStreamSynchronize``
@@ -489,9 +489,23 @@ class StreamBank:
         :meth:`Engine.sequence_forward` row by row from cached activations; a posterior is ``post_frames`` of the stream's rows
         since its last reset (every sampled row advances the state; rows that arrive while ``is_speech`` is set emit).
         ``engine`` may be a :class:`ModelSet`: stream ``s`` is then served by member ``models[s]`` (default: all by member 0;
-        ``ww_stream_create_set``) and :meth:`set_model` moves streams between members; ``full_recompute`` is refused."""
+        ``ww_stream_create_set``) and :meth:`set_model` moves streams between members; ``full_recompute`` is refused.
+        ``sample_rate`` other than 16000: the bank runs at that rate (``ww_stream_attach_resampler``) - :meth:`step` takes
+        ``[S, frame_samples]`` frames, ``frame_samples = sample_rate / 50``, :meth:`feed` packets at that rate, and every stream
+        yields the bits of the 16 kHz bank given its resampled signal behind ``D`` zeros (``include/wwhip.h``).  The bank creates
+        and owns a ``Resampler(sample_rate, 16000, ctx)``, or takes ``resampler`` (which must outlive it)."""
         self.engine = engine
         self.S = int(n_streams)
+        self.sample_rate = int(sample_rate if resampler is None else resampler.rate_in)
+        if resampler is not None and int(sample_rate) not in (16000, self.sample_rate):
+            raise ValueError(f"sample_rate = {sample_rate}, but the resampler reads {self.sample_rate} Hz")
+        if self.sample_rate <= 0 or self.sample_rate % 50:
+            raise ValueError(f"sample_rate {self.sample_rate}: a 20 ms frame must be a whole number of samples "
+                             "(rates with a fractional frame are not offered in the tick)")
+        if resampler is not None and self.sample_rate == 16000:
+            raise ValueError("a resampler from 16000 Hz: that is a plain bank")
+        self.frame_samples = self.sample_rate // 50
+        self._resampler, self._own_resampler = resampler, False
         is_set = isinstance(engine, ModelSet)
         if models is not None and not is_set:
             raise ValueError("models= names the members of a ModelSet: this bank is built on one Engine")
@@ -512,13 +526,21 @@ class StreamBank:
                            engine.ctx.handle)
         self._h = h
         _lib.register("streams", self)
+        if self.sample_rate != 16000:
+            if self._resampler is None:
+                from .resample import Resampler
+                self._resampler, self._own_resampler = Resampler(self.sample_rate, 16000, engine.ctx), True
+            _lib.raise_for(self._lib.ww_stream_attach_resampler(self._h, self._resampler._h), engine.ctx.handle)
+            n = C.c_int32(0)
+            _lib.raise_for(self._lib.ww_stream_frame_samples(self._h, C.byref(n)), engine.ctx.handle)
+            assert n.value == self.frame_samples
         self._post = np.zeros((self.S, 2), np.float32)
         self._n = np.zeros(self.S, np.int32)
         self._flags = np.zeros(self.S, np.uint8)
         # a tick is host-paced (spokestack/pipeline.py:25-28): the addresses of the bank's own arrays are taken once, not per call
         self._p_post, self._p_n, self._p_flags = (C.c_void_p(a.ctypes.data) for a in (self._post, self._n, self._flags))
         self._step = self._lib.ww_stream_step
-        self._shape = (self.S, 320)
+        self._shape = (self.S, self.frame_samples)
         self._keep = None
 
     def _frames_address(self, frames: np.ndarray) -> int:
@@ -526,7 +548,7 @@ class StreamBank:
         if not (type(f) is np.ndarray and f.dtype == np.int16 and f.flags.c_contiguous):
             f = self._keep = np.ascontiguousarray(frames, dtype=np.int16)  # (kept alive until the call has returned)
         if f.shape != self._shape:
-            raise ValueError(f"frames must be [{self.S}, 320] int16")
+            raise ValueError(f"frames must be [{self.S}, {self._shape[1]}] int16")
         try:
             return C.addressof(C.c_char.from_buffer(f))  # (a third of the cost of f.ctypes.data_as)
         except (TypeError, ValueError):                   # a read-only array
@@ -622,6 +644,9 @@ class StreamBank:
         if self._h and not _lib.is_shutdown():
             self._lib.ww_stream_destroy(self._h)
         self._h = None
+        if getattr(self, "_own_resampler", False):  # (behind the bank: it borrows the tap table)
+            self._resampler.close()
+            self._own_resampler = False
 
     def __del__(self):  # pragma: no cover
         try:

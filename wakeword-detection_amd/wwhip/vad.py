@@ -96,7 +96,9 @@ class VadBank:
     (spokestack/vad/webrtc.py:59-77 per stream).  Two forms: ``step(raw[S]) -> is_speech[S]`` on the bank's own ``is_speech``
     array, and the pipeline-stage form ``bank(contexts, frames)`` where ``contexts`` is a :class:`~wwhip.context.ContextBank`
     whose ``is_speech`` array IS the state (as the context is in the reference) and the raw decisions come from a batch
-    classifier ``classifier(frames[S, 320]) -> bool[S]`` (or are passed as ``raw=``)."""
+    classifier ``classifier(frames[S, F]) -> bool[S]`` (or are passed as ``raw=``); F is the frame length of the bank the
+    frames are for - 320, or ``sample_rate / 50`` in front of a ``StreamBank(sample_rate=...)``: the classifier sees the frames at
+    the bank's rate, as webrtcvad would."""
 
     def __init__(self, n_streams: int, frame_width: int = 20, vad_rise_delay: int = 0, vad_fall_delay: int = 0,
                  classifier: Optional[Callable[[np.ndarray], Sequence[bool]]] = None) -> None:
@@ -135,7 +137,7 @@ class VadBank:
             self._bound = (contexts, _lib.addr(contexts.is_speech))
         if raw is None:
             if self._classify is None:
-                raise ValueError("VadBank needs classifier=callable(frames[S, 320]) -> bool[S], or raw= per call")
+                raise ValueError("VadBank needs classifier=callable(frames[S, frame samples]) -> bool[S], or raw= per call")
             raw = self._classify(frames)
         if self._run(raw, self._bound[1]) and _LOG.isEnabledFor(logging.INFO):
             _LOG.info("vad: %d streams speaking", int(contexts.is_speech.sum()))
