@@ -352,7 +352,12 @@ int ww_wave_sequence(ww_ctx *ctx, const ww_model *model, const float *mel, int64
 
 /* Whole hot path for a batch of equal-length clips resident in HBM (BASELINE configs 2/3):
  * PCM [n_clips][samples_per_clip] -> log-mel -> one zero-padded window per clip ->
- * encode + detect -> d_out [n_clips][n_out].  d_mel_scratch may be NULL (ctx workspace). */
+ * encode + detect -> d_out [n_clips][n_out].  d_mel_scratch may be NULL (ctx workspace).
+ * A clip has (samples_per_clip - 512) / hop + 1 frames.  A clip of fewer than 512 samples has none and yields the model's row
+ * for the all-zero window; a clip of more than `window` frames is judged by its first `window` frames, the rest is not read by
+ * the model.  The result for a clip does not depend on the batch it is in (tests/test_gpu_clips64.py pins all of this).
+ * d_pcm is 16-byte aligned; WW_EINVAL for more than 65535 clips, a negative size, a hop outside 1..512, a pcm_divisor that is
+ * not positive or a NULL buffer; n_clips = 0 is a no-op. */
 int ww_clips_forward_dev(ww_ctx *ctx, const ww_model *model, const int16_t *d_pcm, int32_t n_clips,
                          int32_t samples_per_clip, const ww_frontend_params *fp, float *d_out);
 

@@ -113,7 +113,9 @@ def _batches():
     odd = [_clip(rng, n) for n in (2001, 1777, 3333, 515, 999, 1231)]
     return {
         "a ragged": (ragged, (32767.0, True, 0.0, 160)),       # 50 rows: boundaries inside tiles and between them, a last tile of 2 rows
-        "b equal": (equal, (32767.0, True, 0.0, 160)),         # 3 x 147 rows = 441: the one-multiply row -> clip path
+        # 3 x 147 rows = 441, equal clips through ww_logmel's offset tables (the equal-clips arithmetic, magic multiply included, is
+        # ww_clips_forward_dev's alone: tests/test_gpu_clips64.py, test_logmel_equal_clips_arithmetic_lookup_equals_offset_tables)
+        "b equal": (equal, (32767.0, True, 0.0, 160)),
         "c odd": (odd, (32768.0, True, 0.0, 160)),             # clips start at odd sample offsets
         "d generic": (ragged + odd, (32768.0, False, 0.97, 160)),  # pre-emphasis: generic staging
     }
