@@ -323,6 +323,35 @@ int ww_set_forward_windows_dev(ww_ctx *ctx, const ww_model_set *set, const float
 int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
                             const int32_t *seg_nw, int32_t n_seg, int32_t hop, float *d_out);
 
+/* The same over a model set - the evaluator's form (windows SLIDING over clips, utils/evaluate_models.py:66-88) for a list of
+ * checkpoints: every sequence is slid over by every member the call names.  members: a HOST array of n_members member ids, each a
+ * "slot" of the call; duplicates are allowed; NULL = every member of the set in order (n_members is then not looked at, but for its
+ * sign).  d_out is [slots][W][n_out], W = the sum of seg_nw, windows numbered sequence by sequence as in ww_forward_segments_dev:
+ * plane k holds member members[k]'s detect rows, with the bits that member gives alone in the same form (below).
+ * CRNN, hop 1..8, the sliding form enabled (WW_OPT_CRNN_SLIDE_MIN != 0) and W >= WW_OPT_CRNN_SLIDE_MIN: per group of sequences ONE
+ * crnn_rows_kernel launch and ONE tail launch over a (tiles | windows) x slots grid - a slot's projected rows, tail scratch and
+ * detect rows are planes of member-major buffers, the tile and first-field tables are built and uploaded once for all slots.  Groups
+ * are whole sequences with slots x windows <= 32,768 (a single larger sequence is a group of its own): the workspace bound of
+ * ww_forward_segments_dev.  CRNN otherwise, and every Wavenet: slots x W explicit windows naming the same rows, through the one-launch
+ * form of ww_set_forward_windows_dev.
+ * WW_EINVAL, with nothing enqueued and nothing written: a NULL ctx / set / d_mel / d_out (seg_row0 / seg_nw where n_seg > 0); a set
+ * of another context; hop <= 0; n_seg < 0; n_members < 0; a negative seg_nw; windows that leave the mel buffer; a member id outside
+ * [0, n_models) (ww_last_error names its index).  n_seg = 0, W = 0 and n_members = 0 (members != NULL) are WW_OK and write nothing.
+ * The host arrays are read before the call returns; the call enqueues and waits for no kernel unless a buffer of the context has to
+ * grow.
+ * ww_set_slide_forward: host pointers, ONE sequence of `rows` rows, synchronous - ww_slide_forward for every slot over one upload:
+ * out is [slots][n_windows][n_out], *n_windows the count PER MEMBER ((rows - window) / hop + 1, 0 if rows < window).
+ * ww_set_option: WW_OPT_CRNN_SLIDE_MIN and WW_OPT_CRNN_TAIL_MFMA (ww_model_set_option's meanings and ranges) for the set's launches -
+ * the two options that decide the form above; a set starts from the library's defaults whatever its members' options are.  Any other
+ * key: WW_EINVAL.  The two tails give the same bits; the rows form and the explicit-window form differ as they do for one model
+ * (three of a window's nineteen projected rows are summed in another order: posteriors within 2e-6).  A single model's
+ * ww_forward_segments_dev takes the rows form whatever W is: WW_OPT_CRNN_SLIDE_MIN = 1 gives a set exactly those bits. */
+int ww_set_forward_segments_dev(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
+                                const int32_t *seg_nw, int32_t n_seg, int32_t hop, const int32_t *members, int32_t n_members, float *d_out);
+int ww_set_slide_forward(ww_ctx *ctx, const ww_model_set *set, const float *mel, int64_t rows, int32_t hop, const int32_t *members,
+                         int32_t n_members, float *out, int64_t *n_windows);
+int ww_set_option(ww_model_set *set, int key, int64_t value);
+
 /* ---- Wavenet on whole sequences (fp32) ----------------------------------------------------
  * The reference Wavenet is causal and fully convolutional: its trainer builds it with timesteps=None "for variable length"
  * (wwdetect/wavenet/train_wavenet.py:75, wavenet_model.py:165-172) and only the TFLite export freezes 182 rows.  This is that

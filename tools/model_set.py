@@ -1,20 +1,26 @@
 #!/usr/bin/env python3
 """Development: what a model set (wwhip.ModelSet) costs and buys - the figures of profiles/model_set/measured.txt.
 
-  model_set.py codeobj A.so B.so   no GPU: per kernel of crnn_fused_kernel / crnn_stream_kernel / wavenet_kernel / wavenet_seq_kernel
-                                   the registers, LDS, scratch and instruction count in both libraries, and whether the
-                                   instruction streams are the same text (addresses and symbol offsets aside)
+  model_set.py codeobj A.so B.so   no GPU: per kernel of crnn_fused_kernel / crnn_stream_kernel / crnn_rows_kernel / gru_tail_kernel /
+                                   gru_tail16_kernel / wavenet_kernel / wavenet_seq_kernel the registers, LDS, scratch and instruction
+                                   count in both libraries, and whether the instruction streams are the same text (addresses and
+                                   symbol offsets aside)
   model_set.py tick [ticks=3000]   128-stream CRNN tick, p50 / p90 us: one model | a set of three dealt round-robin | three banks of
                                    128 ticked one after the other; run it under WWHIP_LIB=<other build> for the other side
   model_set.py tick_wave [ticks=3000]  the fp32 Wavenet's 128-stream window tick: one model against a set of two, one launch and two
   model_set.py batch [reps=200]    forward_all of three CRNNs on 256 windows against three Engine.forward calls, ms per call
+  model_set.py slide [reps=25]     three CRNNs sliding over 256 clips of 1.5 s padded as the evaluator pads them (hop 2, 49 windows per
+                                   clip, 12,544 per member), device-resident PCM: A = per member logmel_dev + forward_windows_dev +
+                                   forward_segments_dev, B = one logmel_dev + the set's two calls; A and B alternate, medians and spread
+                                   of each (profiles/model_set/slide_measured.txt)
 """
 import os, re, shutil, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "wakeword-detection_amd")]
 ASSETS = os.path.join(ROOT, "wakeword-detection_amd/assets/tf_lite_models")
 CRNNS = ["CRNN_nosilence", "CRNN_nosilence_enhanced", "CRNN_softmax"]
-KERNELS = ("crnn_fused_kernel", "crnn_stream_kernel", "wavenet_kernel", "wavenet_seq_kernel")
+KERNELS = ("crnn_fused_kernel", "crnn_stream_kernel", "crnn_rows_kernel", "gru_tail_kernel", "gru_tail16_kernel", "wavenet_kernel",
+           "wavenet_seq_kernel")
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
@@ -54,14 +60,17 @@ def kernels_of(lib):
             for n, p in zip(names, plain):
                 p = re.sub(r"^void ", "", p)
                 p = re.sub(r"\(.*$", "", p)
-                out[p] = dict(meta[n], insts=len(body.get(n, [])), text="\n".join(body.get(n, [])))
+                lines = body.get(n, [])
+                ends = [i for i, l in enumerate(lines) if l.startswith("s_endpgm")]
+                lines = lines[:ends[-1] + 1] if ends else lines  # (behind the last s_endpgm: padding up to the next symbol's alignment)
+                out[p] = dict(meta[n], insts=len(lines), text="\n".join(lines))
     return out
 
 
 def codeobj(a, b):
     ka, kb = kernels_of(a), kernels_of(b)
     for k in list(kb):  # B's instantiations that spell out a template parameter A does not have yet (SET = false)
-        short = k[:-len(", false>")] + ">" if k.endswith(", false>") else None
+        short = k[:-len(", false>")] + ">" if k.endswith(", false>") else k[:-len("<false>")] if k.endswith("<false>") else None
         if short and short in ka and short not in kb:
             kb[short] = kb.pop(k)
     cols = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "insts")
@@ -200,6 +209,74 @@ def batch(reps):
     print(f"device side: one set launch of 768 windows {one:.1f} us   three launches of 256 {three:.1f} us")
 
 
+def slide(reps):
+    """The evaluator's pass over a test set for three checkpoints: per member (A) against through the set (B), the clips' PCM on the
+    device.  Each side ends with one synchronise; wall clock around it."""
+    import numpy as np
+    import torch
+    from wwhip.engine import Engine, ModelSet, frontend_params
+    from wwhip.evaluate import CLIP_PAD
+    engines = [Engine(os.path.join(ASSETS, m)) for m in CRNNS]
+    ms = ModelSet(engines)
+    K, T, NO = len(engines), ms.window, ms.n_out
+    n, L, hop = 256, 24000, 2
+    rng = np.random.default_rng(7)
+    pcm = np.zeros((n, L + 2 * CLIP_PAD), np.int16)
+    pcm[:, CLIP_PAD:CLIP_PAD + L] = np.clip(rng.normal(0, 2500, (n, L)), -32768, 32767)
+    nf = (L + 2 * CLIP_PAD - 512) // 160 + 1
+    nf_bare = (L - 512) // 160 + 1
+    nw = (nf - T) // hop + 1
+    soffs = np.arange(n + 1, dtype=np.int64) * (L + 2 * CLIP_PAD)
+    foffs = np.arange(n + 1, dtype=np.int64) * nf
+    seg_nw = np.full(n, nw, np.int32)
+    print(f"{n} clips of {L} samples (+ 2 x {CLIP_PAD} of padding): {nf} rows and {nw} windows per clip, {n * nw} per member, {K} members")
+    d_pcm = torch.from_numpy(np.concatenate((pcm.ravel(), np.zeros(16, np.int16)))).cuda()
+    d_so, d_fo = torch.from_numpy(soffs).cuda(), torch.from_numpy(foffs).cuda()
+    d_mel = torch.empty((n * nf, 40), dtype=torch.float32, device="cuda")
+    row = (foffs[:-1] + CLIP_PAD // 160).astype(np.int64)
+    valid = np.full(n, min(nf_bare, T), np.int32)
+    d_row, d_valid = torch.from_numpy(row).cuda(), torch.from_numpy(valid).cuda()
+    d_rowK, d_validK = torch.from_numpy(np.tile(row, K)).cuda(), torch.from_numpy(np.tile(valid, K)).cuda()
+    ids = np.repeat(np.arange(K, dtype=np.int32), n)
+    out_a = torch.empty((K, n + n * nw, NO), dtype=torch.float32, device="cuda")
+    one_b = torch.empty((K, n, NO), dtype=torch.float32, device="cuda")
+    slide_b = torch.empty((K, n * nw, NO), dtype=torch.float32, device="cuda")
+    fp = frontend_params()
+    torch.cuda.synchronize()
+
+    def side_a():
+        for k, e in enumerate(engines):
+            e.logmel_dev(d_pcm.data_ptr(), d_so.data_ptr(), d_fo.data_ptr(), n, n * nf, nf, d_mel.data_ptr(), fp)
+            e.forward_windows_dev(d_mel.data_ptr(), n * nf, d_row.data_ptr(), d_valid.data_ptr(), n, out_a[k].data_ptr())
+            e.forward_segments_dev(d_mel.data_ptr(), n * nf, foffs[:-1], seg_nw, hop, out_a[k, n:].data_ptr())
+        ms.ctx.synchronize()
+
+    def side_b():
+        engines[0].logmel_dev(d_pcm.data_ptr(), d_so.data_ptr(), d_fo.data_ptr(), n, n * nf, nf, d_mel.data_ptr(), fp)
+        ms.forward_windows_dev(d_mel.data_ptr(), n * nf, d_rowK.data_ptr(), d_validK.data_ptr(), ids, K * n, one_b.data_ptr())
+        ms.forward_segments_dev(d_mel.data_ptr(), n * nf, foffs[:-1], seg_nw, hop, slide_b.data_ptr())
+        ms.ctx.synchronize()
+
+    for _ in range(5):
+        side_a()
+        side_b()
+    a, b = out_a.cpu().numpy(), np.concatenate((one_b.cpu().numpy(), slide_b.cpu().numpy()), axis=1)
+    print("B equals A bit for bit:", bool((a == b).all()))
+    ta, tb = np.empty(reps), np.empty(reps)
+    for r in range(reps):  # A and B alternate
+        t0 = time.perf_counter()
+        side_a()
+        t1 = time.perf_counter()
+        side_b()
+        ta[r], tb[r] = t1 - t0, time.perf_counter() - t1
+    for name, t in (("A: per member (3 x logmel_dev + forward_windows_dev + forward_segments_dev)", ta), ("B: one logmel_dev + the set's two calls", tb)):
+        q = np.percentile(t * 1e3, [0, 25, 50, 75, 100])
+        print(f"{name}: median {q[2]:.3f} ms  quartiles {q[1]:.3f} .. {q[3]:.3f}  min {q[0]:.3f}  max {q[4]:.3f}  ({reps} repeats)")
+    # A against itself: the medians of its even and odd repeats
+    print(f"A against itself: median of even repeats {np.median(ta[0::2]) * 1e3:.3f} ms, of odd repeats {np.median(ta[1::2]) * 1e3:.3f} ms")
+    print(f"B / A (medians): {np.median(tb) / np.median(ta):.3f}")
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else ""
     if what == "codeobj" and len(sys.argv) == 4:
@@ -210,5 +287,7 @@ if __name__ == "__main__":
         tick_wave(int(sys.argv[2]) if len(sys.argv) > 2 else 3000)
     elif what == "batch":
         batch(int(sys.argv[2]) if len(sys.argv) > 2 else 200)
+    elif what == "slide":
+        slide(int(sys.argv[2]) if len(sys.argv) > 2 else 25)
     else:
         sys.exit(__doc__)

@@ -424,7 +424,7 @@ int ww_model_set_create(ww_ctx *ctx, const ww_model *const *models, int32_t n_mo
     WW_HIP(ctx, hipMemcpyAsync((char *)set->block + (size_t)k * set->stride, models[k]->block, bytes, hipMemcpyDeviceToDevice, ctx->stream));
   WW_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the members may be freed as soon as the call returns
   // member 0 as the launchers see it: its geometry, its pointers inside the set's block; the dispatch options are the library's
-  // defaults, whatever member 0's are (a set has no ww_model_set_option)
+  // defaults, whatever member 0's are (ww_set_option moves the two that decide the sliding form)
   set->view = *models[0];
   set->view.block = set->block;
   {
@@ -440,6 +440,22 @@ int ww_model_set_create(ww_ctx *ctx, const ww_model *const *models, int32_t n_mo
   *out = own.release();
   return WW_OK;
   WW_GUARD_END(ctx)
+}
+
+// The two options that decide the sliding form's launches (the view starts from the library's defaults)
+int ww_set_option(ww_model_set *set, int key, int64_t value) {
+  WW_GUARD_BEGIN
+  if (!set) return WW_EINVAL;
+  if (value < 0 || value > 0x7fffffff) return ww_fail(set->ctx, WW_EINVAL, "option value %lld out of range", (long long)value);
+  switch (key) {
+    case WW_OPT_CRNN_SLIDE_MIN: set->view.opt_slide_min = (int)value; return WW_OK;
+    case WW_OPT_CRNN_TAIL_MFMA:
+      if (value > 2) return ww_fail(set->ctx, WW_EINVAL, "WW_OPT_CRNN_TAIL_MFMA takes 0 (never), 1 (from 9,216 windows per launch) or 2 (always)");
+      set->view.opt_tail_mfma = (int)value;
+      return WW_OK;
+    default: return ww_fail(set->ctx, WW_EINVAL, "a model set takes WW_OPT_CRNN_SLIDE_MIN and WW_OPT_CRNN_TAIL_MFMA, not option %d", key);
+  }
+  WW_GUARD_END(set ? set->ctx : nullptr)
 }
 
 int ww_model_set_info(const ww_model_set *set, ww_model_info *info, int32_t *n_models) {
@@ -804,6 +820,155 @@ int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, 
   void *ws = bump.take<char>(b_ws);
   if ((rc = tb.send(ctx, d_tab))) return rc;
   return forward_chunks(ctx, m, d_mel, mel_rows, d_rows, d_valid, 0, 0, nw, ws, d_out, nullptr, no_enc);
+  WW_GUARD_END(ctx)
+}
+
+}  // extern "C"
+
+// ---- a model set's sliding evaluation ------------------------------------------------------------------------------------------
+#define WW_SET_SLOT_CHUNK 1024  // member slots per launch of the sliding form (duplicates are allowed: a call may bring any number)
+
+// Everything ww_set_forward_segments_dev refuses, before anything is enqueued.  *W_out: windows per member, *n_slots: the call's
+// member slots; WW_OK with *W_out = 0: nothing to do.
+static int set_segments_check(ww_ctx *ctx, const ww_model_set *set, const void *d_mel, int64_t mel_rows, const int64_t *seg_row0,
+                              const int32_t *seg_nw, int32_t n_seg, int32_t hop, const int32_t *members, int32_t n_members, const void *d_out,
+                              int32_t *n_slots, int64_t *W_out) {
+  *W_out = 0;
+  *n_slots = 0;
+  if (!ctx || !set) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (set->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "the model set belongs to another context");
+  if (!d_mel || !d_out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (hop <= 0) return ww_fail(ctx, WW_EINVAL, "hop must be positive");
+  if (n_seg < 0) return ww_fail(ctx, WW_EINVAL, "negative sequence count");
+  if (n_members < 0) return ww_fail(ctx, WW_EINVAL, "negative member count");
+  if (n_seg > 0 && (!seg_row0 || !seg_nw)) return ww_fail(ctx, WW_EINVAL, "sequence descriptors are NULL");
+  const int T = set->view.info.window;
+  int64_t W = 0;
+  for (int s = 0; s < n_seg; ++s) {
+    if (seg_nw[s] < 0) return ww_fail(ctx, WW_EINVAL, "negative window count in sequence %d", s);
+    if (seg_nw[s] && (seg_row0[s] < 0 || seg_row0[s] + (int64_t)(seg_nw[s] - 1) * hop + T > mel_rows))
+      return ww_fail(ctx, WW_EINVAL, "sequence %d: windows leave the mel buffer", s);
+    W += seg_nw[s];
+  }
+  char why[160];
+  if (int rc = ww_set_check_ids(members, n_members, set->n, "members", why, sizeof why)) return ww_fail(ctx, rc, "ww_set_forward_segments_dev: %s", why);
+  const int32_t slots = members ? n_members : set->n;
+  if (slots == 0 || W == 0) return WW_OK;
+  if (W * slots > 0x7fffffff) return ww_fail(ctx, WW_EINVAL, "too many windows in one call");
+  *n_slots = slots;
+  *W_out = W;
+  return WW_OK;
+}
+
+// the checked call (the context's device is current)
+static int set_segments_run(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
+                            const int32_t *seg_nw, int32_t n_seg, int32_t hop, const int32_t *members, int32_t n_slots, int64_t W, float *d_out) {
+  const ww_model *m = &set->view;
+  const int NO = m->info.n_out, T = m->info.window;
+  std::vector<int32_t> all;
+  if (!members) {
+    all.resize((size_t)n_slots);
+    for (int k = 0; k < n_slots; ++k) all[k] = k;
+    members = all.data();
+  }
+  if (ww_crnn_set_segments_rows_form(m, hop, W)) {
+    for (int32_t k0 = 0; k0 < n_slots; k0 += WW_SET_SLOT_CHUNK) {
+      const int n = n_slots - k0 < WW_SET_SLOT_CHUNK ? n_slots - k0 : WW_SET_SLOT_CHUNK;
+      if (int rc = ww_k_crnn_set_segments_forward(ctx, m, (long long)set->stride, members + k0, n, d_mel, mel_rows, seg_row0, seg_nw, n_seg, hop, W,
+                                                  d_out + (size_t)k0 * W * NO))
+        return rc;
+    }
+    return WW_OK;
+  }
+  // every other model / form: the same windows as an explicit list of n_slots x W descriptors naming the same rows, member-major -
+  // descriptor k * W + w is window w by member members[k], and its detect row is row k * W + w of d_out
+  const size_t nw = (size_t)n_slots * (size_t)W;
+  std::vector<int64_t> rows(nw);
+  std::vector<int32_t> ids(nw);
+  {
+    size_t w = 0;
+    for (int s = 0; s < n_seg; ++s)
+      for (int k = 0; k < seg_nw[s]; ++k) rows[w++] = seg_row0[s] + (int64_t)k * hop;
+    for (int k = 1; k < n_slots; ++k) std::copy(rows.begin(), rows.begin() + W, rows.begin() + (size_t)k * W);
+    for (int k = 0; k < n_slots; ++k) std::fill(ids.begin() + (size_t)k * W, ids.begin() + (size_t)(k + 1) * W, members[k]);
+  }
+  const std::vector<int32_t> valid(nw, T);
+  ww_tables tb;
+  const size_t o_rows = tb.add(rows), o_valid = tb.add(valid), o_ids = tb.add(ids), b_ws = model_ws(m, 1);
+  if (int rc = ww_ensure(ctx, ctx->dev, tb.bytes() + b_ws + 1024, false)) return rc;
+  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
+  char *d_tab = bump.take<char>(tb.bytes());
+  void *ws = bump.take<char>(b_ws);
+  if (int rc = tb.send(ctx, d_tab)) return rc;
+  ww_set_ref ref;
+  ref.ids = (const int32_t *)(d_tab + o_ids);
+  ref.stride = (long long)set->stride;
+  const int64_t *d_rows = (const int64_t *)(d_tab + o_rows);
+  const int32_t *d_valid = (const int32_t *)(d_tab + o_valid);
+  if (m->kind == WW_KIND_CRNN) return ww_k_crnn_set_forward(ctx, m, ref, d_mel, mel_rows, d_rows, d_valid, (int)nw, d_out, nullptr);
+  return ww_k_wave_forward(ctx, m, d_mel, mel_rows, d_rows, d_valid, 0, 0, 0, (int)nw, ws, b_ws, d_out, nullptr, nullptr, &ref);
+}
+
+extern "C" {
+
+int ww_set_forward_segments_dev(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
+                                const int32_t *seg_nw, int32_t n_seg, int32_t hop, const int32_t *members, int32_t n_members, float *d_out) {
+  WW_GUARD_BEGIN
+  int32_t n_slots;
+  int64_t W;
+  if (int rc = set_segments_check(ctx, set, d_mel, mel_rows, seg_row0, seg_nw, n_seg, hop, members, n_members, d_out, &n_slots, &W)) return rc;
+  if (W == 0) return WW_OK;
+  WW_ON_DEVICE(ctx, dev);
+  return set_segments_run(ctx, set, d_mel, mel_rows, seg_row0, seg_nw, n_seg, hop, members, n_slots, W, d_out);
+  WW_GUARD_END(ctx)
+}
+
+int ww_set_slide_forward(ww_ctx *ctx, const ww_model_set *set, const float *mel, int64_t rows, int32_t hop, const int32_t *members,
+                         int32_t n_members, float *out, int64_t *n_windows) {
+  WW_GUARD_BEGIN
+  if (!ctx || !set || !n_windows) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (hop <= 0) return ww_fail(ctx, WW_EINVAL, "hop must be positive");
+  if (rows < 0) return ww_fail(ctx, WW_EINVAL, "negative row count");
+  const int T = set->view.info.window, F = set->view.info.n_mel, NO = set->view.info.n_out;
+  const int64_t nw = rows >= T ? (rows - T) / hop + 1 : 0;
+  if (nw > 0x7fffffff) return ww_fail(ctx, WW_EINVAL, "too many windows in one call");
+  *n_windows = nw;
+  if (nw > 0 && (!mel || !out)) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
+  const int64_t row0 = 0;
+  const int32_t seg_nw = (int32_t)nw;
+  int32_t n_slots;
+  int64_t W;
+  // (the same checks on the caller's own pointers: what is refused is refused before a byte moves; without a window there is no buffer
+  // to name)
+  if (int rc = set_segments_check(ctx, set, nw ? (const void *)mel : (const void *)&row0, rows, &row0, &seg_nw, 1, hop, members, n_members,
+                                  nw ? (const void *)out : (const void *)&row0, &n_slots, &W))
+    return rc;
+  if (W == 0) return WW_OK;
+  WW_ON_DEVICE(ctx, dev);
+  // the sequence and the detect rows in one allocation of the call's own (the launchers carve the context's arena from its start)
+  const size_t b_mel = ww_bump::need((size_t)rows * F, 4), b_out = ww_bump::need((size_t)n_slots * W * NO, 4);
+  struct dev_block {
+    void *p = nullptr;
+    ~dev_block() {
+      if (p) (void)hipFree(p);
+    }
+  } blk;
+  if (hipMalloc(&blk.p, b_mel + b_out) != hipSuccess) {
+    blk.p = nullptr;
+    return ww_fail(ctx, WW_ENOMEM, "ww_set_slide_forward: cannot allocate %zu bytes of device memory", b_mel + b_out);
+  }
+  float *d_mel = (float *)blk.p, *d_out = (float *)((char *)blk.p + b_mel);
+  int rc = WW_OK;
+  hipError_t e = hipMemcpyAsync(d_mel, mel, (size_t)rows * F * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    rc = set_segments_run(ctx, set, d_mel, rows, &row0, &seg_nw, 1, hop, members, n_slots, W, d_out);
+    if (rc == WW_OK) e = hipMemcpyAsync(out, d_out, (size_t)n_slots * W * NO * 4, hipMemcpyDeviceToHost, ctx->stream);
+  }
+  // the block is freed behind this wait, whatever the status
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (rc == WW_OK && (e != hipSuccess || es != hipSuccess))
+    rc = ww_fail(ctx, WW_EHIP, "ww_set_slide_forward: %s", hipGetErrorString(e != hipSuccess ? e : es));
+  return rc;
   WW_GUARD_END(ctx)
 }
 

@@ -93,6 +93,8 @@ struct ww_model_set {
 // table-driven tick: the stream in its window's aux word (aux != nullptr: a Wavenet window bank's kernel has no other use for that
 // table); a feed: its segment's stream - and every weight pointer of the kernel's arguments moves on by member * stride bytes.
 // The SET = false instantiations take the same (empty) argument and never look at it.
+// The sliding form's kernels (crnn_rows_kernel, gru_tail_kernel, gru_tail16_kernel with SET = true) index ids by blockIdx.y - the
+// call's member slot, a grid dimension - and read the sizes of their member-major planes from aux (crnn.hip: WW_SLIDE_AUX_*).
 struct ww_set_ref {
   const int32_t *ids = nullptr;
   const int32_t *aux = nullptr;
@@ -239,6 +241,11 @@ int ww_k_crnn_set_forward(ww_ctx *ctx, const ww_model *m, const ww_set_ref &set,
 bool ww_crnn_segments_capable(const ww_model *m, int hop);
 int ww_k_crnn_segments_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
                                const int32_t *seg_nw, int n_seg, int hop, float *d_out);
+// a set's sliding form (m: the set's view; ids: the call's member slots, a HOST array of n_ids checked ids; W: windows per member
+// of the call; d_out: [n_ids][W][n_out]): per group of sequences ONE crnn_rows_kernel<SET> and ONE tail launch over all slots
+bool ww_crnn_set_segments_rows_form(const ww_model *m, int hop, int64_t W);
+int ww_k_crnn_set_segments_forward(ww_ctx *ctx, const ww_model *m, long long set_stride, const int32_t *ids, int n_ids, const float *d_mel,
+                                   int64_t mel_rows, const int64_t *seg_row0, const int32_t *seg_nw, int n_seg, int hop, int64_t W, float *d_out);
 bool ww_crnn_stream_capable(const ww_model *m);
 int ww_k_crnn_stream_forward(ww_ctx *ctx, const ww_model *m, const float *d_hist, int64_t hist_rows, const int64_t *d_win_row,
                              const int32_t *d_win_valid, const int32_t *d_win_aux, float *d_gxc, int n_windows, float *d_out,

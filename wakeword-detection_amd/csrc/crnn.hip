@@ -1159,7 +1159,16 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
 // A workgroup stages the union of its 16 fields (15 stride + 20 <= 140 rows) once, runs the conv as 20 m-tiles
 // (position, frequency) and the projection as ONE full 16-row MFMA tile per n-tile - no 3-row remainder, and W_x1 is
 // streamed once per 16 rows that are then used by 16 x 17 / 3 windows.  gru_tail_kernel gathers a window's 19 rows.
+// SET (a model set's sliding form, ww_k_crnn_set_segments_forward): a two-dimensional grid - blockIdx.x is the tile as ever,
+// blockIdx.y the call's member slot, whose member is set.ids[blockIdx.y].  The weight pointers move on to that member's block,
+// and the slot writes plane blockIdx.y of the three lists (planes of set.aux[0] interior fields / set.aux[1] edge rows).  The
+// tile table is the geometry's and the hop's: one table for every slot.  From there on it is the single-model kernel.
 // ------------------------------------------------------------------------------------------
+// A set's sliding launches: what the planes hold, read as scalars through ww_set_ref::aux
+#define WW_SLIDE_AUX_NI 0  // interior fields per plane of gI
+#define WW_SLIDE_AUX_NW 1  // windows of the group per member: rows per plane of gL / gR, and what the tail16 scratch is sized by
+#define WW_SLIDE_AUX_W 2   // windows of the CALL per member: rows per plane of the output
+#define WW_SLIDE_AUX_N 4
 struct rows_args {
   const float *mel;
   int64_t mel_rows;
@@ -1171,7 +1180,18 @@ struct rows_args {
   const rows_tile *desc;  // or: one descriptor per workgroup (launch_plan.h; several sequences in one buffer: ww_k_crnn_segments_forward)
 };
 
-__global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
+template <bool SET = false>
+__global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a, ww_set_ref set) {
+  // (the moved pointers are names of their own, read where the single-model kernel reads its arguments - RK_ARG: a.w4 / a.out are
+  // chosen by kind where the kernel arguments lie, and a written-to copy of `a` would have to be indexed in registers or scratch)
+  const float *m_cbias = nullptr, *m_wx1s = nullptr, *m_bx1 = nullptr;
+  long long set_off = 0;
+  if constexpr (SET) {
+    set_off = ww_set_offset(set, blockIdx.y);
+    m_cbias = a.cbias; m_wx1s = a.wx1s; m_bx1 = a.bx1;
+    ww_set_move(m_cbias, set_off); ww_set_move(m_wx1s, set_off); ww_set_move(m_bx1, set_off);
+  }
+#define RK_ARG(name_) (SET ? m_##name_ : a.name_)
   extern __shared__ __align__(16) float cf_smem[];
   float *img = cf_smem, *feat = cf_smem + CF_IMG_FLOATS;  // feat: [16][CF_FLD]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1192,10 +1212,11 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
     out_row = p0;
   }
   const float *w4 = a.w4[kind];
+  if constexpr (SET) ww_set_move(w4, set_off);  // (behind the choice by kind: the three pointers stay where the kernel arguments are)
 
   float4 wreg[CV_KB][2];
   float wlast[2], cb0, cb1;
-  CV_LOAD_W(wreg, wlast, cb0, cb1, w4, a.cbias)
+  CV_LOAD_W(wreg, wlast, cb0, cb1, w4, RK_ARG(cbias))
 
   // ---- stage the union of the 16 fields: image[(mel + PF)][row - field0]
   int a_off[5], o_off[5][4];
@@ -1251,7 +1272,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
     CV_TILE_LOOP(5, if (i > 0) store_tile(i - 1, prev0, prev1);)
     store_tile(4, prev0, prev1);
   }
-  PJ_W_LANE(a.wx1s)
+  PJ_W_LANE(RK_ARG(wx1s))
   float4 bq[4][3];
   PJ_RING_PROLOGUE(4)
   __syncthreads();  // feat complete
@@ -1262,9 +1283,10 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
     float4 avq[2];
     avq[0] = *(const float4 *)(a0p);
     float bv1[3];
-    PJ_LOAD_BIAS(bv1, a.bx1)
+    PJ_LOAD_BIAS(bv1, RK_ARG(bx1))
     PJ_KLOOP(4, PJ_ROWS16, PJ_NO_ROWS, avq[(ks + 1) & 1] = *(const float4 *)(a0p + (ks + 1) * 16);)
     float *out = a.out[kind] + (size_t)out_row * 192;
+    if constexpr (SET) out += (size_t)blockIdx.y * (size_t)set.aux[kind == 0 ? WW_SLIDE_AUX_NI : WW_SLIDE_AUX_NW] * 192;
 #pragma unroll
     for (int n = 0; n < 3; ++n) {
       const int col = wave * 48 + n * 16 + j;
@@ -1274,6 +1296,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a) {
         if (kk * 4 + r < np) out[(size_t)(kk * 4 + r) * 192 + col] = acc[n][r] + bv;
     }
   }
+#undef RK_ARG
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1535,7 +1558,24 @@ struct tail_args {
 #define GT_HID (GT_ENC + 2 * GR_H)
 #define GT_SMEM_FLOATS (GT_HID + 2 * GR_H)
 
-__global__ __launch_bounds__(128, 4) void gru_tail_kernel(tail_args a) {
+// SET (both tails; the grid's y is the call's member slot as in crnn_rows_kernel<SET>): the weights of member set.ids[blockIdx.y],
+// plane blockIdx.y of the three projected-row lists and of the output; blockIdx.x stays the window (tail16: the group of sixteen -
+// a group never mixes members), and iI0, a function of the geometry and the hop, serves every slot.
+__device__ __forceinline__ void gt_set_move(tail_args &a, const ww_set_ref &set, int slot) {
+  const long long off = ww_set_offset(set, slot);
+  ww_set_move(a.wh1, off); ww_set_move(a.bh1, off); ww_set_move(a.wx2s, off); ww_set_move(a.wx2, off); ww_set_move(a.bx2, off);
+  ww_set_move(a.wh2, off); ww_set_move(a.bh2, off); ww_set_move(a.w1, off); ww_set_move(a.b1, off); ww_set_move(a.w2, off);
+  ww_set_move(a.b2, off);
+  const size_t nI = (size_t)set.aux[WW_SLIDE_AUX_NI], nW = (size_t)set.aux[WW_SLIDE_AUX_NW], W = (size_t)set.aux[WW_SLIDE_AUX_W];
+  a.gxI += (size_t)slot * nI * 6 * GR_H;
+  a.gxL += (size_t)slot * nW * 6 * GR_H;
+  a.gxR += (size_t)slot * nW * 6 * GR_H;
+  a.out += (size_t)slot * W * a.NOUT;
+}
+
+template <bool SET = false>
+__global__ __launch_bounds__(128, 4) void gru_tail_kernel(tail_args a, ww_set_ref set) {
+  if constexpr (SET) gt_set_move(a, set, blockIdx.y);
   constexpr int H = GR_H, OT = CV_OT;
   __shared__ __align__(16) float sm[GT_SMEM_FLOATS];
   float *gxs = sm, *seq1 = sm + GT_SEQ, *hb = sm + GT_HB, *encs = sm + GT_ENC, *hid = sm + GT_HID;
@@ -1640,7 +1680,12 @@ struct tail16_args {
   int nw;      // windows in this launch (the last workgroup may be partial)
 };
 
-__global__ __launch_bounds__(128, 2) void gru_tail16_kernel(tail16_args aa) {
+template <bool SET = false>
+__global__ __launch_bounds__(128, 2) void gru_tail16_kernel(tail16_args aa, ww_set_ref set) {
+  if constexpr (SET) {
+    gt_set_move(aa.t, set, blockIdx.y);
+    aa.seq += (size_t)blockIdx.y * (size_t)((aa.nw + 15) / 16) * CV_OT * 16 * 2 * GR_H;  // the slot's plane of the layer-1 outputs
+  }
   constexpr int H = GR_H, OT = CV_OT;
   const tail_args &a = aa.t;
   // LDS: the h exchange (9.2 KB) + each wave's recurrent weights as B-operand pages [tile 6][half 2][lane 64] x 16 bytes
@@ -2091,7 +2136,8 @@ int ww_k_crnn_init_device(ww_ctx *ctx) {
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
-  WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
+  WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
+  WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_FUSED_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_FUSED_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_FUSED_SMEM_BYTES));
@@ -2185,14 +2231,18 @@ static tail_args crnn_tail_args(const ww_crnn_dev &c) {
   t.NOUT = c.NOUT; t.HEAD = c.HEAD;
   return t;
 }
-static void launch_tail(ww_ctx *ctx, const ww_model *m, const tail_args &t, int nw, float *seq) {
+// set / slots: a model set's launch (the SET kernels, `slots` planes of nw windows each: seq holds slots x tail_seq_bytes(nw))
+static void launch_tail(ww_ctx *ctx, const ww_model *m, const tail_args &t, int nw, float *seq, const ww_set_ref *set = nullptr, int slots = 1) {
   if (m->opt_tail_mfma >= 2 || (m->opt_tail_mfma == 1 && nw >= WW_TAIL16_MIN)) {
     tail16_args a16 = {t, seq, nw};
-    ww_launch_scope scope(ctx, "gru_tail16_kernel");
-    hipLaunchKernelGGL(gru_tail16_kernel, dim3((unsigned)((nw + 15) / 16)), dim3(128), GT16_SMEM_BYTES, ctx->stream, a16);
+    ww_launch_scope scope(ctx, set ? "gru_tail16_kernel<set>" : "gru_tail16_kernel");
+    const unsigned groups = (unsigned)((nw + 15) / 16);
+    if (set) hipLaunchKernelGGL(gru_tail16_kernel<true>, dim3(groups, (unsigned)slots), dim3(128), GT16_SMEM_BYTES, ctx->stream, a16, *set);
+    else hipLaunchKernelGGL(gru_tail16_kernel<false>, dim3(groups), dim3(128), GT16_SMEM_BYTES, ctx->stream, a16, ww_set_ref{});
   } else {
-    ww_launch_scope scope(ctx, "gru_tail_kernel");
-    hipLaunchKernelGGL(gru_tail_kernel, dim3((unsigned)nw), dim3(128), 0, ctx->stream, t);
+    ww_launch_scope scope(ctx, set ? "gru_tail_kernel<set>" : "gru_tail_kernel");
+    if (set) hipLaunchKernelGGL(gru_tail_kernel<true>, dim3((unsigned)nw, (unsigned)slots), dim3(128), 0, ctx->stream, t, *set);
+    else hipLaunchKernelGGL(gru_tail_kernel<false>, dim3((unsigned)nw), dim3(128), 0, ctx->stream, t, ww_set_ref{});
   }
 }
 
@@ -2254,13 +2304,66 @@ int ww_k_crnn_segments_forward(ww_ctx *ctx, const ww_model *m, const float *d_me
       r.desc = d_tiles;
       {
         ww_launch_scope scope(ctx, "crnn_rows_kernel");
-        hipLaunchKernelGGL(crnn_rows_kernel, dim3((unsigned)gp.tiles.size()), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r);
+        hipLaunchKernelGGL(crnn_rows_kernel<false>, dim3((unsigned)gp.tiles.size()), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r, ww_set_ref{});
       }
       tail_args t = crnn_tail_args(c);
       t.gxI = gI; t.gxL = gL; t.gxR = gR;
       t.hop_g = hop / g; t.eight_g = 8 / g; t.iI0 = d_i0;
       t.out = d_out + (size_t)w_done * c.NOUT;
       launch_tail(ctx, m, t, (int)nW, seq);
+      WW_HIP(ctx, hipGetLastError());
+      w_done += nW;
+    }
+  }
+  return WW_OK;
+}
+
+// The same for a model set (ww_set_forward_segments_dev; m is the set's view, ids the call's member slots on the HOST, already
+// checked): every group is ONE crnn_rows_kernel<SET> launch and ONE tail launch over a (tiles | windows | groups of sixteen) x
+// n_ids grid.  A group's tile table and i0 are built and uploaded once and serve every slot; the projected-row lists, the tail16
+// scratch and the output are member-major planes.  Groups stay whole sequences with n_ids x nW <= WW_SEG_GROUP (a single larger
+// sequence is a group of its own), so the workspace bound is ww_k_crnn_segments_forward's.  d_out: [n_ids][W][NOUT], W = the call's
+// windows per member.
+bool ww_crnn_set_segments_rows_form(const ww_model *m, int hop, int64_t W) { return ww_crnn_segments_capable(m, hop) && W >= crnn_slide_min(m); }
+
+int ww_k_crnn_set_segments_forward(ww_ctx *ctx, const ww_model *m, long long set_stride, const int32_t *ids, int n_ids, const float *d_mel,
+                                   int64_t mel_rows, const int64_t *seg_row0, const int32_t *seg_nw, int n_seg, int hop, int64_t W, float *d_out) {
+  const ww_crnn_dev &c = m->crnn;
+  const int g = crnn_gcd8(hop);
+  const int64_t cap = std::max<int64_t>(WW_SEG_GROUP / n_ids, 1);
+  crnn_seg_group gp;
+  int64_t w_done = 0;
+  for (int s0 = 0; s0 < n_seg; s0 = gp.next) {
+    if (int rc = crnn_plan_group(seg_row0, seg_nw, n_seg, hop, c.T, c.PT, c.OT, c.ST, mel_rows, s0, gp, cap)) return ww_fail(ctx, rc, "%s", gp.err);
+    const int64_t nI = gp.nI, nW = gp.nW;
+    if (nW > 0) {
+      const int32_t aux[WW_SLIDE_AUX_N] = {(int32_t)nI, (int32_t)nW, (int32_t)W, 0};
+      ww_tables tb;
+      const size_t o_tiles = tb.add(gp.tiles), o_i0 = tb.add(gp.i0), o_ids = tb.add(ids, (size_t)n_ids), o_aux = tb.add(aux, (size_t)WW_SLIDE_AUX_N);
+      const size_t b_seq = tail_seq_bytes((int)nW) * (size_t)n_ids;
+      int rc = ww_ensure(ctx, ctx->dev, tb.bytes() + 3 * 256 + (size_t)n_ids * (size_t)(nI + 2 * nW) * 6 * c.H * 4 + b_seq + 8192, false);
+      if (rc) return rc;
+      ww_bump b(ctx->dev.ptr, ctx->dev.cap);
+      char *d_tab = b.take<char>(tb.bytes());
+      float *gI = b.take<float>((size_t)n_ids * nI * 6 * c.H), *gL = b.take<float>((size_t)n_ids * nW * 6 * c.H);
+      float *gR = b.take<float>((size_t)n_ids * nW * 6 * c.H);
+      float *seq = (float *)b.take<char>(b_seq);
+      if ((rc = tb.send(ctx, d_tab))) return rc;
+      ww_set_ref ref;
+      ref.ids = (const int32_t *)(d_tab + o_ids);
+      ref.aux = (const int32_t *)(d_tab + o_aux);
+      ref.stride = set_stride;
+      rows_args r = rows_args_of(c, d_mel, mel_rows, gI, gL, gR);
+      r.desc = (const rows_tile *)(d_tab + o_tiles);
+      {
+        ww_launch_scope scope(ctx, "crnn_rows_kernel<set>");
+        hipLaunchKernelGGL(crnn_rows_kernel<true>, dim3((unsigned)gp.tiles.size(), (unsigned)n_ids), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r, ref);
+      }
+      tail_args t = crnn_tail_args(c);
+      t.gxI = gI; t.gxL = gL; t.gxR = gR;
+      t.hop_g = hop / g; t.eight_g = 8 / g; t.iI0 = (const int64_t *)(d_tab + o_i0);
+      t.out = d_out + (size_t)w_done * c.NOUT;
+      launch_tail(ctx, m, t, (int)nW, seq, &ref, n_ids);
       WW_HIP(ctx, hipGetLastError());
       w_done += nW;
     }
@@ -2321,7 +2424,7 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
     for (int k = 0; k < 3; ++k) r.tiles[k] = (r.count[k] + 15) / 16;
     {
       ww_launch_scope scope(ctx, "crnn_rows_kernel");
-      hipLaunchKernelGGL(crnn_rows_kernel, dim3(r.tiles[0] + r.tiles[1] + r.tiles[2]), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r);
+      hipLaunchKernelGGL(crnn_rows_kernel<false>, dim3(r.tiles[0] + r.tiles[1] + r.tiles[2]), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r, ww_set_ref{});
     }
     tail_args t = crnn_tail_args(c);
     t.gxI = gI; t.gxL = gL; t.gxR = gR;

@@ -79,11 +79,14 @@ struct rows_tile {
 static inline int crnn_gcd8(int hop) { return hop % 8 == 0 ? 8 : hop % 4 == 0 ? 4 : hop % 2 == 0 ? 2 : 1; }
 static inline int64_t crnn_n_int(int64_t nw, int hop) { return ((nw - 1) * hop + 128) / crnn_gcd8(hop) + 1; }
 
-// groups of whole sequences of at most ~WW_SEG_GROUP windows bound the workspace
+// groups of whole sequences of at most ~WW_SEG_GROUP windows bound the workspace (a model set's call: windows x members of the call,
+// ww_k_crnn_set_segments_forward - its cap per member is WW_SEG_GROUP / members)
 #define WW_SEG_GROUP 32768
 
 // One group of ww_k_crnn_segments_forward: sequences [s0, next) of the call, nW windows numbered sequence by sequence and nI
-// interior fields; crnn_rows_kernel's tiles (no tile straddles two sequences) and each window's first interior field.
+// interior fields; crnn_rows_kernel's tiles (no tile straddles two sequences) and each window's first interior field.  `cap`: the
+// group takes sequences while its windows stay at or below it (its first sequence whatever its size).  Tiles and i0 are functions
+// of the sequences alone: where the cap cuts only moves the group's bases (nI, nW so far) under them.
 struct crnn_seg_group {
   std::vector<rows_tile> tiles;
   std::vector<int64_t> i0;
@@ -92,13 +95,13 @@ struct crnn_seg_group {
   char err[96] = {0};  // why planning stopped (status != WW_OK), for ww_fail
 };
 static inline int crnn_plan_group(const int64_t *seg_row0, const int32_t *seg_nw, int n_seg, int hop, int T, int PT, int OT, int ST,
-                                  int64_t mel_rows, int s0, crnn_seg_group &gp) {
+                                  int64_t mel_rows, int s0, crnn_seg_group &gp, int64_t cap = WW_SEG_GROUP) {
   const int g = crnn_gcd8(hop);
   gp.tiles.clear();
   gp.i0.clear();
   int64_t nI = 0, nW = 0;
   int s1 = s0;
-  for (; s1 < n_seg && (s1 == s0 || nW + seg_nw[s1] <= WW_SEG_GROUP); ++s1) {
+  for (; s1 < n_seg && (s1 == s0 || nW + seg_nw[s1] <= cap); ++s1) {
     const int nw = seg_nw[s1];
     if (nw < 0) {
       snprintf(gp.err, sizeof gp.err, "negative window count in sequence %d", s1);

@@ -102,6 +102,9 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_forward_windows_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
     "ww_set_forward_windows_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp]),
     "ww_forward_segments_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
+    "ww_set_forward_segments_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
+    "ww_set_slide_forward": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _P(_i64)]),
+    "ww_set_option": (C.c_int, [_vp, C.c_int, _i64]),
     "ww_wave_sequence_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ww_wave_sequence": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ww_clips_forward_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _P(FrontendParams), _vp]),

@@ -460,6 +460,54 @@ class ModelSet:
             return got[0].reshape(K, B, self.n_out), got[1].reshape((K, B) + self.enc_shape)
         return got.reshape(K, B, self.n_out)
 
+    def _slots(self, members) -> Optional[np.ndarray]:
+        """``members`` as the call's slot table (``None`` = every member in order): any number of ids, duplicates allowed."""
+        if members is None:
+            return None
+        a = np.asarray(members)
+        return _member_ids(a, a.size if a.ndim == 1 else -1, self.n_models, "members")
+
+    def set_option(self, key: str, value: int) -> None:
+        """``ww_set_option``: ``"crnn_slide_min"`` / ``"crnn_tail_mfma"`` (:meth:`Engine.set_option`'s meanings) for the set's
+        sliding launches.  They move the launch form, never the bits."""
+        keys = {"crnn_slide_min": _lib.OPT_CRNN_SLIDE_MIN, "crnn_tail_mfma": _lib.OPT_CRNN_TAIL_MFMA}
+        if key not in keys:
+            raise ValueError(f"a model set takes the options {sorted(keys)}, not {key!r}")
+        _lib.raise_for(self._lib.ww_set_option(self._set, keys[key], int(value)), self.ctx.handle)
+
+    def forward_segments_dev(self, d_mel_ptr: int, mel_rows: int, seg_row0: np.ndarray, seg_nw: np.ndarray, hop: int, d_out_ptr: int,
+                             members=None) -> None:
+        """``ww_set_forward_segments_dev``: :meth:`Engine.forward_segments_dev` by every member of ``members`` (``None``: all, in
+        order) in one call - ``d_out`` is ``[len(members), sum(seg_nw), n_out]``, plane ``k`` what member ``members[k]`` gives on
+        its own.  A CRNN set slides with ONE rows-kernel launch and ONE tail launch per group of sequences, whatever the number
+        of members.  The descriptor arrays are host arrays.  Enqueued on the context's stream, not waited for."""
+        r0 = np.ascontiguousarray(seg_row0, dtype=np.int64)
+        nw = np.ascontiguousarray(seg_nw, dtype=np.int32)
+        if r0.shape != nw.shape or r0.ndim != 1:
+            raise ValueError("seg_row0 and seg_nw must be 1-D arrays of the same length")
+        ids = self._slots(members)
+        _lib.raise_for(self._lib.ww_set_forward_segments_dev(self.ctx.handle, self._set, C.c_void_p(d_mel_ptr), int(mel_rows), _lib.ptr(r0),
+                                                             _lib.ptr(nw), int(r0.size), int(hop), _lib.ptr(ids) if ids is not None else None,
+                                                             int(ids.size) if ids is not None else 0, C.c_void_p(d_out_ptr)), self.ctx.handle)
+
+    def slide_forward_all(self, mel: np.ndarray, hop: int = 2, members=None) -> np.ndarray:
+        """``[rows, 40]`` -> ``[K', n_windows, n_out]``: :meth:`Engine.slide_forward` by every member of ``members`` (``None``: all)
+        over ONE upload of the sequence (``ww_set_slide_forward``)."""
+        mel = np.ascontiguousarray(mel, dtype=np.float32)
+        if mel.ndim != 2 or mel.shape[1] != self.n_mel:
+            raise ValueError(f"mel must be [rows, {self.n_mel}], got {mel.shape}")
+        ids = self._slots(members)
+        k = self.n_models if ids is None else int(ids.size)
+        rows = mel.shape[0]
+        nw = max(0, (rows - self.window) // hop + 1) if rows >= self.window and hop > 0 else 0
+        out = np.empty((k, nw, self.n_out), np.float32)
+        n = C.c_int64(0)
+        _lib.raise_for(self._lib.ww_set_slide_forward(self.ctx.handle, self._set, _lib.ptr(mel), rows, int(hop),
+                                                      _lib.ptr(ids) if ids is not None else None, int(ids.size) if ids is not None else 0,
+                                                      _lib.ptr(out), C.byref(n)), self.ctx.handle)
+        assert n.value == nw, (n.value, nw)
+        return out
+
     def close(self) -> None:
         if self._set and not _lib.is_shutdown():
             self._lib.ww_model_set_destroy(self._set)

@@ -1231,6 +1231,83 @@ def evaluate_testset(engine: Engine, clips: Sequence[np.ndarray], labels: Sequen
             "positives": pos, "negatives": neg, "hours": hours}
 
 
+def clip_posteriors_set(model_set, clips: Sequence[np.ndarray], hop: int = 2, fp=None):
+    """:func:`clip_posteriors` for every member of a :class:`wwhip.ModelSet` over ONE pass of the clips: one upload, ONE front-end
+    launch (the set's members share their filter), the ``n`` single windows of all ``K`` members in one launch
+    (``ModelSet.forward_windows_dev``: ``K n`` windows naming the same rows) and the sliding windows of all members in one call
+    (``ModelSet.forward_segments_dev``: for a CRNN set one rows-kernel launch and one tail launch per group of clips).
+    Returns ``(one_window [K, N], sliding)`` with ``sliding[k]`` the list :func:`clip_posteriors` returns for member ``k`` -
+    the same bits.  (A CRNN set whose clips hold fewer sliding windows in all than its ``crnn_slide_min`` - 64 - evaluates them as
+    explicit windows, where a single engine's ``forward_segments_dev`` still takes the rows form: those few posteriors then differ
+    as the two forms do for one model, by less than 2e-6; ``model_set.set_option("crnn_slide_min", 1)`` gives the engine's bits.)"""
+    import torch  # only to hold the device buffers of the batched launch
+
+    fp = fp or frontend_params()
+    K = model_set.n_models
+    front = model_set.engines[0]  # the set's one front end
+    pidx = [e.posterior_index for e in model_set.engines]
+    T, hop_s, PAD = model_set.window, int(fp.hop), CLIP_PAD
+    n = len(clips)
+    if n == 0:
+        return np.zeros((K, 0), np.float32), [[] for _ in range(K)]
+    if PAD % hop_s:
+        raise ValueError(f"front-end hop {hop_s} does not divide the 0.5 s padding")
+    lens = np.array([len(c) for c in clips], np.int64)
+    soffs = np.concatenate(([0], np.cumsum(lens + 2 * PAD)))
+    need = int(soffs[-1]) + 16
+    pin = torch.zeros(need, dtype=torch.int16, pin_memory=True)  # (a buffer of the call's own: clip_posteriors keeps its _PIN to itself)
+    pcm = pin.numpy()
+    for i, c in enumerate(clips):
+        a = int(soffs[i]) + PAD
+        pcm[a: a + len(c)] = c
+    nf_pad = np.where(lens + 2 * PAD >= 512, (lens + 2 * PAD - 512) // hop_s + 1, 0)
+    nf_bare = np.where(lens >= 512, (lens - 512) // hop_s + 1, 0)
+    foffs = np.concatenate(([0], np.cumsum(nf_pad)))
+    total_f = int(foffs[-1])
+    nw = np.where(nf_pad >= T, (nf_pad - T) // hop + 1, 0)
+    woffs = np.concatenate(([0], np.cumsum(nw)))
+    win_row = (foffs[:-1] + PAD // hop_s).astype(np.int64)
+    win_valid = np.minimum(nf_bare, T).astype(np.int32)
+    n_slide = int(woffs[-1])
+    dev = torch.device("cuda", model_set.ctx.device)
+    d_pcm = pin.to(dev, non_blocking=True)
+    d_so, d_fo = torch.from_numpy(soffs).to(dev), torch.from_numpy(foffs).to(dev)
+    d_mel = torch.empty((max(total_f, 1), model_set.n_mel), dtype=torch.float32, device=dev)
+    # window k * n + i: the single window of clip i by member k
+    d_row, d_valid = torch.from_numpy(np.tile(win_row, K)).to(dev), torch.from_numpy(np.tile(win_valid, K)).to(dev)
+    d_one = torch.empty((K * n, model_set.n_out), dtype=torch.float32, device=dev)
+    d_slide = torch.empty((K, max(n_slide, 1), model_set.n_out), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)
+    front.logmel_dev(d_pcm.data_ptr(), d_so.data_ptr(), d_fo.data_ptr(), n, total_f, int(nf_pad.max()), d_mel.data_ptr(), fp)
+    model_set.forward_windows_dev(d_mel.data_ptr(), total_f, d_row.data_ptr(), d_valid.data_ptr(), np.repeat(np.arange(K, dtype=np.int32), n),
+                                  K * n, d_one.data_ptr())
+    if n_slide:
+        model_set.forward_segments_dev(d_mel.data_ptr(), total_f, foffs[:-1], nw, hop, d_slide.data_ptr())
+    model_set.ctx.synchronize()
+    one = d_one.cpu().numpy().reshape(K, n, model_set.n_out)
+    slide = d_slide.cpu().numpy()[:, :n_slide]
+    p_one = np.stack([one[k, :, pidx[k]] for k in range(K)])
+    return p_one, [[slide[k, woffs[i]:woffs[i + 1], pidx[k]] for i in range(n)] for k in range(K)]
+
+
+def evaluate_testset_set(model_set, clips: Sequence[np.ndarray], labels: Sequence[int], thresholds=None, windowsize: int = 30, fp=None):
+    """:func:`evaluate_testset` for every member of a :class:`wwhip.ModelSet` over one pass of the clips
+    (:func:`clip_posteriors_set`): a list of ``K`` result dicts, dict ``k`` what ``evaluate_testset(Engine(member k), ...)`` returns."""
+    labels = np.asarray(labels).astype(bool)
+    p_one, sliding = clip_posteriors_set(model_set, clips, fp=fp)
+    hours = sum((len(c) + 16000) for c, l in zip(clips, labels) if not l) / 16000.0 / 3600.0
+    results = []
+    for k in range(model_set.n_models):
+        pos = np.array([s.max() if len(s) else 0.0 for s, l in zip(sliding[k], labels) if l], np.float32)
+        neg = np.concatenate([s for s, l in zip(sliding[k], labels) if not l]) if (~labels).any() else np.zeros(0, np.float32)
+        thr, frr, fa, cnt = far_frr(pos, neg, max(int(labels.sum()), 1), hours, thresholds, windowsize, engine=model_set.engines[k])
+        preds = (p_one[k] >= 0.5)
+        results.append({"thresholds": thr, "frr": frr, "fa_per_hour": fa, "fa_count": cnt, "frr_at_0.5_fa_per_hour": frr_at_fa(frr, fa, 0.5),
+                        "one_window_posteriors": p_one[k], "one_window_accuracy": float((preds == labels).mean()),
+                        "positives": pos, "negatives": neg, "hours": hours})
+    return results
+
+
 def evaluate_testset_sharded(engine: Engine, clips: Sequence[np.ndarray], labels: Sequence[int], rank: int = 0,
                              world: int = 1, comm_device: Optional[str] = None, thresholds=None, windowsize: int = 30,
                              fp=None):
