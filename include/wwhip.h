@@ -491,6 +491,37 @@ int ww_stream_feed(ww_streams *st, const int32_t *ids, int32_t n, const int16_t 
  * attach, a geometry whose history + frame exceed what a tick stages (12288 samples).  The resampler must outlive the bank. */
 int ww_stream_attach_resampler(ww_streams *st, const ww_resampler *r);
 int ww_stream_frame_samples(const ww_streams *st, int32_t *out);
+/* ---- a stream bank whose streams each run at their own sample rate ---------------------------------------------------------------
+ * ww_stream_attach_rates makes `st` a bank whose stream s runs at the input rate of rate class stream_rate[s]: 8 kHz telephony legs,
+ * 16 kHz app audio and 44.1 / 48 kHz capture streams in ONE bank and ONE tick.  rs[k] is class k (up to WW_STREAM_MAX_RATES);
+ * rs[k] == NULL is the 16 kHz class, a pass-through with no delay and no history.  stream_rate [n_streams] is a HOST array, read and
+ * checked before the call returns; NULL = every stream in class 0.  One kernel launch in front of a tick's own serves all classes;
+ * no other kernel of the bank changes, so every form a bank has works (as ww_stream_attach_resampler lists them).
+ * Contract.  Stream s yields, for every call (tick, trigger step, pipeline step, feed, window read-out), THE BITS STREAM s YIELDS
+ * IN A BANK THAT RUNS AT ITS RATE ALONE: for the 16 kHz class the plain bank, for any other class the bank
+ * ww_stream_attach_resampler(rs[k]) makes - z is the resampled signal behind D zeros, as defined above.
+ * Frames.  `frames` of ww_stream_step, ww_stream_step_trigger and ww_pipeline_bank_step is ONE contiguous ragged int16 block:
+ * stream s's rate / 50 samples start at sample frame_offs[s], no padding between streams.  ww_stream_frame_layout writes
+ * frame_samples [n_streams] and frame_offs [n_streams + 1] (frame_offs[n_streams] = the block's samples); it works on every bank (a
+ * plain or single-rate bank: the uniform layout).  ww_stream_frame_samples on a bank with per-stream rates is WW_EINVAL.
+ * ww_stream_feed / ww_stream_feed_rows on a WW_STREAM_CAUSAL bank: stream ids[i]'s packet is at that stream's rate, the rows follow
+ * from floor((N + k) * up / down) - floor(N * up / down) with the stream's own class (the 16 kHz class: the plain rule); however a
+ * stream's samples are cut into packets, calls and ticks, the bits are the same.  A feed's launches and copies are per class present
+ * in the call, whatever the number of streams.
+ * ww_stream_set_rate moves the listed streams (ids NULL -> all) to class rate_class AND resets them as ww_stream_reset does - the
+ * resampling count included: the next sample is x[0] of a new signal -, in stream order with the ticks, as ww_stream_set_model.
+ * The layout changes with it: read ww_stream_frame_layout again.  WW_EINVAL: a bank without rates, an id or a class out of range.
+ * A failure after the bank's table has changed marks the bank broken.  ww_stream_reset and ww_stream_set_model clear the listed
+ * streams' resampling state, as on a single-rate bank.
+ * ww_stream_attach_rates is allowed only on a bank that has neither ticked nor been fed (else WW_ESTATE); the resamplers must outlive
+ * the bank.  WW_EINVAL, ww_last_error naming the class and the reason: n_rates outside 1..WW_STREAM_MAX_RATES, a class that
+ * ww_stream_attach_resampler would refuse (rate_out != 16000, a resampler from 16000 - that class is NULL -, a fractional 20 ms
+ * frame, a geometry too long to stage), two classes of the same input rate, more than one NULL class, stream_rate[s] outside
+ * [0, n_rates) (its index named), a bank that already has a resampler or rates, a resampler of another context. */
+#define WW_STREAM_MAX_RATES 8
+int ww_stream_attach_rates(ww_streams *st, const ww_resampler *const *rs, int32_t n_rates, const int32_t *stream_rate);
+int ww_stream_frame_layout(const ww_streams *st, int32_t *frame_samples, int64_t *frame_offs);
+int ww_stream_set_rate(ww_streams *st, const int32_t *ids, int32_t n, int32_t rate_class);
 /* ---- the pipeline's host stages for S streams in lock step (BASELINE config 5 at the plugin surface) --------------------------
  * The reference drives three stage objects per stream and 20 ms frame (spokestack/pipeline.py:25-28, stage list of demo.py:29-36),
  * each a few comparisons on the shared SpeechContext.  For S streams each stage is ONE pass over plain arrays the caller owns

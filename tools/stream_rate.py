@@ -8,6 +8,12 @@
          (each its own upload, launch, synchronise and download), the 16 kHz samples queued per stream, a tick of the 16 kHz bank
          once every stream holds 320.  The same p50 / p99, the pushes included.
   feed   a causal Wavenet bank fed S streams x --seconds in ONE call at --rate (16000: the plain bank's feed): milliseconds per call.
+  mixed  per-stream rates (profiles/stream_rate/mixed_measured.txt), four sides alternated within this process over
+         --rounds rounds of --ticks ticks each, p50 / p99 per side and round:
+           a  ONE bank of S streams, half at 8000 and half at 48000 (StreamBank(sample_rate=[...]))
+           b  what it takes without: a bank of S / 2 streams at 8000 and one of S / 2 at 48000, ticked one after the other
+           c  a bank with per-stream rates whose S streams are all at 48000
+           d  the single-rate bank of S streams at 48000 (c - d: the price of the per-stream descriptor)
 
 One JSON line.  The single-rate modes use nothing this tool's commit added, so the file also runs on its parent."""
 import argparse
@@ -113,14 +119,59 @@ def feed(args):
                 median_ms=float(np.median(ms[1:])))
 
 
+def mixed(args):
+    eng = Engine(os.path.join(ASSETS, args.model))
+    S, H = args.streams, args.streams // 2
+    rng = np.random.default_rng(0)
+
+    def noise(*shape):
+        return np.clip(rng.normal(0, 2500, shape), -32768, 32767).astype(np.int16)
+    f8, f48, f48all = noise(64, H, 160), noise(64, H, 960), noise(64, S, 960)
+    flat = [np.concatenate((f8[t].ravel(), f48[t].ravel())) for t in range(64)]  # streams 0 .. H - 1 at 8000, the rest at 48000
+    sp_s, sp_h = np.ones(S, np.uint8), np.ones(H, np.uint8)
+    a = StreamBank(eng, S, sample_rate=[8000] * H + [48000] * (S - H))
+    b8, b48 = StreamBank(eng, H, sample_rate=8000), StreamBank(eng, S - H, sample_rate=48000)
+    c = StreamBank(eng, S, sample_rate=[48000] * S)
+    d = StreamBank(eng, S, sample_rate=48000)
+
+    def tick_b(t):
+        n = b8.step(f8[t], sp_h)[1].sum()
+        return n + b48.step(f48[t], sp_h)[1].sum()
+    sides = {"a": lambda t: a.step(flat[t], sp_s)[1].sum(), "b": tick_b, "c": lambda t: c.step(f48all[t].ravel(), sp_s)[1].sum(),
+             "d": lambda t: d.step(f48all[t], sp_s)[1].sum()}
+    for fn in sides.values():
+        for t in range(100):
+            fn(t % 64)
+    rounds = {k: [] for k in sides}
+    posts = {k: 0 for k in sides}
+    for r in range(args.rounds):
+        for k, fn in sides.items():
+            lat = np.empty(args.ticks)
+            for t in range(args.ticks):
+                t0 = time.perf_counter()
+                posts[k] += int(fn(t % 64))
+                lat[t] = time.perf_counter() - t0
+            rounds[k].append({q: round(v, 2) for q, v in _pct(lat).items()})
+    for bank in (a, b8, b48, c, d):
+        bank.close()
+    eng.close()
+    p50 = {k: [r["p50_us"] for r in v] for k, v in rounds.items()}
+    return dict(mode="mixed", model=args.model, streams=S, ticks=args.ticks, rounds=rounds,
+                posteriors_per_tick={k: v / (args.ticks * args.rounds) for k, v in posts.items()},
+                p50_range_us={k: [min(v), max(v)] for k, v in p50.items()},
+                a_below_b_beyond_spread=max(p50["a"]) < min(p50["b"]),
+                c_minus_d_p50_us=[round(x - y, 2) for x, y in zip(p50["c"], p50["d"])])
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("mode", choices=["tick", "push", "feed"])
+    ap.add_argument("mode", choices=["tick", "push", "feed", "mixed"])
     ap.add_argument("--rate", type=int, default=48000, help="the streams' sample rate (a multiple of 50; 16000 = a plain bank)")
     ap.add_argument("--streams", type=int, default=128)
     ap.add_argument("--ticks", type=int, default=3000)
     ap.add_argument("--model", default="CRNN", choices=["CRNN", "Wavenet"])
     ap.add_argument("--seconds", type=float, default=10.0, help="feed: audio per stream and call")
     ap.add_argument("--repeats", type=int, default=3, help="feed: timed calls")
+    ap.add_argument("--rounds", type=int, default=3, help="mixed: rounds the sides alternate over")
     a = ap.parse_args()
-    print(json.dumps({"tick": tick, "push": push, "feed": feed}[a.mode](a)))
+    print(json.dumps({"tick": tick, "push": push, "feed": feed, "mixed": mixed}[a.mode](a)))

@@ -17,6 +17,7 @@
 #include "launch_plan.h"
 #include "model_layout.h"
 #include "stream_rate.h"
+#include "stream_rates.h"
 
 #define WW_WAVE 64
 
@@ -294,6 +295,21 @@ int64_t ww_k_rate_advance(const ww_stream_rate *rt, int stream, int64_t k);
 int ww_k_rate_tick(ww_stream_rate *rt, const int16_t *frames, const uint8_t *flags, const int32_t *ctl_dev, const int16_t **d_frames);
 int ww_k_rate_feed(ww_stream_rate *rt, const int32_t *ids, int n, const int16_t *pcm, const int64_t *sample_offs, const int64_t *offs16,
                    const int16_t **d_pcm16, bool *moved);
+// A stream bank whose streams each run at their own rate (resample.hip; geometry and bookkeeping: stream_rates.h): rs[k] = rate class
+// k (nullptr: the 16 kHz class), stream_rate[s] = the class of stream s (nullptr: all 0).  _tick: the ragged frames -> the [S][320]
+// block, ONE kernel for every class.  _move: the listed streams (nullptr: 0 .. count - 1) to class c with their counts at 0, the
+// device table behind it in stream order.  _feed: the call's 16 kHz samples into d_dst (see resample.hip).  The rest as above.
+struct ww_stream_rates;
+int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, const int32_t *stream_rate, int S, ww_stream_rates **out);
+void ww_k_rates_destroy(ww_stream_rates *rt);
+int ww_k_rates_classes(const ww_stream_rates *rt);
+void ww_k_rates_layout(const ww_stream_rates *rt, int32_t *frame_samples, int64_t *frame_offs);  // [S], [S + 1]; either may be nullptr
+void ww_k_rates_reset(ww_stream_rates *rt, const int32_t *ids, int count);
+int ww_k_rates_move(ww_stream_rates *rt, const int32_t *ids, int count, int c);
+int64_t ww_k_rates_advance(const ww_stream_rates *rt, int stream, int64_t k);
+int ww_k_rates_tick(ww_stream_rates *rt, const int16_t *frames, const uint8_t *flags, const int32_t *ctl_dev, const int16_t **d_frames);
+int ww_k_rates_feed(ww_stream_rates *rt, const int32_t *ids, int n, const int16_t *pcm, const int64_t *sample_offs, const int64_t *offs16,
+                    int16_t *d_dst, bool *moved);
 int ww_k_far_frr(ww_ctx *ctx, const float *d_pos, int64_t n_pos, const float *d_neg, int64_t n_neg, int win,
                  const double *d_thr, int n_thr, double *d_smoothed, unsigned long long *d_pos_cnt,
                  unsigned long long *d_fa_cnt);

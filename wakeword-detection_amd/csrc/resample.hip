@@ -558,15 +558,18 @@ int ww_k_rate_tick(ww_stream_rate *rt, const int16_t *frames, const uint8_t *fla
 // A feed's packets at the bank's rate -> its 16 kHz samples on the device: stream ids[i]'s lie at (*d_pcm16)[offs16[i] .. offs16[i + 1]),
 // offs16 as ww_k_rate_advance counts them.  *moved: the streams' sample counts have advanced (a failure behind that point leaves the
 // bank's host mirrors and its device state out of step).
-int ww_k_rate_feed(ww_stream_rate *rt, const int32_t *ids, int n, const int16_t *pcm, const int64_t *sample_offs, const int64_t *offs16,
-                   const int16_t **d_pcm16, bool *moved) {
+// (`pick`: the n_pick packets of the call that are this object's - a class of a mixed-rate bank, ww_k_rates_feed further down, which
+// has the call's packets on the device already, d_pk, and names the buffer the 16 kHz samples go to, d_dst, zeroed by then)
+static int rate_feed_run(ww_stream_rate *rt, const int32_t *ids, int n, const int32_t *pick, int n_pick, const int16_t *pcm, const int16_t *d_pk_all,
+                         const int64_t *sample_offs, const int64_t *offs16, int16_t *d_dst, const int16_t **d_pcm16, bool *moved) {
   ww_ctx *ctx = rt->ctx;
   const rate_geom &g = rt->g;
   std::vector<rate_feed_str> str;
   rs_plan pl;
   int64_t seg_total = 0, k_max = 0;
   const int64_t s0 = sample_offs[0], samples = sample_offs[n] - s0;
-  for (int i = 0; i < n; ++i) {
+  for (int j = 0; j < (pick ? n_pick : n); ++j) {
+    const int i = pick ? pick[j] : j;
     const int64_t k = sample_offs[i + 1] - sample_offs[i];
     if (k == 0) continue;
     const int s = ids[i];
@@ -585,8 +588,8 @@ int ww_k_rate_feed(ww_stream_rate *rt, const int32_t *ids, int n, const int16_t 
     return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: too much work for one call");
   ww_tables tb;
   tb.add(str);
-  const size_t b_tab = tb.bytes(), b_pk = ww_bump::need((size_t)samples, 2), b_seg = ww_bump::need((size_t)seg_total, 4),
-               b_z = ww_bump::need((size_t)offs16[n], 2), b_tiles = ww_bump::need(pl.count(), sizeof(rs_tile));
+  const size_t b_tab = tb.bytes(), b_pk = d_pk_all ? 0 : ww_bump::need((size_t)samples, 2), b_seg = ww_bump::need((size_t)seg_total, 4),
+               b_z = d_dst ? 0 : ww_bump::need((size_t)offs16[n], 2), b_tiles = ww_bump::need(pl.count(), sizeof(rs_tile));
   const size_t need = b_tab + b_pk + b_seg + b_z + b_tiles + 1024;
   if (need > rt->scratch_cap) {
     WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -599,24 +602,311 @@ int ww_k_rate_feed(ww_stream_rate *rt, const int32_t *ids, int n, const int16_t 
   }
   ww_bump db(rt->d_scratch, rt->scratch_cap);
   rate_feed_str *d_str = (rate_feed_str *)db.take<char>(b_tab);
-  int16_t *d_pk = db.take<int16_t>((size_t)samples);
+  const int16_t *d_pk = d_pk_all ? d_pk_all : db.take<int16_t>((size_t)samples);
   float *d_seg = db.take<float>((size_t)seg_total);
-  int16_t *d_z = db.take<int16_t>((size_t)offs16[n]);
+  int16_t *d_z = d_dst ? d_dst : db.take<int16_t>((size_t)offs16[n]);
   rs_tile *d_tiles = db.take<rs_tile>(pl.count());
   *moved = true;
   for (const rate_feed_str &d : str) rt->n[(size_t)d.sid] += d.k;
-  *d_pcm16 = d_z;
+  if (d_pcm16) *d_pcm16 = d_z;
   if (str.empty()) return WW_OK;
   if (int rc = tb.send(ctx, d_str)) return rc;
-  WW_HIP(ctx, hipMemcpyAsync(d_pk, pcm + s0, (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
+  if (!d_pk_all) WW_HIP(ctx, hipMemcpyAsync((void *)d_pk, pcm + s0, (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
   {
     ww_launch_scope scope(ctx, "stream_rate_splice_kernel");
     hipLaunchKernelGGL(stream_rate_splice_kernel, dim3((unsigned)str.size(), (unsigned)((k_max + RATE_SPLICE - 1) / RATE_SPLICE)), dim3(256),
                        (size_t)g.hist * 4, ctx->stream, (const int16_t *)d_pk, (const rate_feed_str *)d_str, d_seg, rt->d_hist, (int)g.hist);
   }
   WW_HIP(ctx, hipGetLastError());
-  if (offs16[n] > 0) WW_HIP(ctx, hipMemsetAsync(d_z, 0, (size_t)offs16[n] * 2, ctx->stream));  // z's leading zeros
+  if (!d_dst && offs16[n] > 0) WW_HIP(ctx, hipMemsetAsync(d_z, 0, (size_t)offs16[n] * 2, ctx->stream));  // z's leading zeros
   if (pl.count() > 0)
     if (int rc = rs_run(rt->r, pl, d_tiles, d_seg, WW_SAMPLE_F32, d_z, WW_SAMPLE_I16)) return rc;
+  return WW_OK;
+}
+
+int ww_k_rate_feed(ww_stream_rate *rt, const int32_t *ids, int n, const int16_t *pcm, const int64_t *sample_offs, const int64_t *offs16,
+                   const int16_t **d_pcm16, bool *moved) {
+  return rate_feed_run(rt, ids, n, nullptr, 0, pcm, nullptr, sample_offs, offs16, nullptr, d_pcm16, moved);
+}
+
+// ---- a stream bank whose streams each run at their own rate (streams.hip: ww_stream_attach_rates) ------------------
+// Up to WW_STREAM_MAX_RATES rate classes, stream s in class cls[s]; the geometry and the bookkeeping are stream_rates.h's (host
+// only).  A resampling class IS the single-rate bank's state object above - its history rows [S][hist of the class], its counts, its
+// feed - of which a stream uses its own class's row only: a stream's bits are those of the single-rate bank of its class because
+// they are that bank's state, control words and arithmetic.  The 16 kHz class has no object: its samples pass through.
+// ONE kernel in front of a tick's own serves every class.  The tick's frames are one ragged int16 block (page-locked, stream s's
+// frame from sample desc[s].off); the per-stream descriptor {class, offset} is a DEVICE table (resent when a stream moves), so the
+// frame's first 320 16-byte pieces are requested before anything that crossed the bus is looked at, as in stream_rate_tick_kernel;
+// the class geometries travel as kernel arguments, picked by a wave-uniform index.  A stream that moves or is reset starts with
+// held = 0: whatever an earlier use left in the row reads as zero, no kernel clears it.
+struct ww_stream_rates {
+  ww_ctx *ctx = nullptr;
+  int S = 0;
+  rates_table tab;
+  ww_stream_rate *cls_rt[WW_STREAM_MAX_RATES] = {};  // nullptr: the 16 kHz class
+  std::vector<int32_t> cls;                          // [S] the stream's class
+  std::vector<rates_desc> desc;                      // [S] what d_desc was last sent
+  rates_desc *d_desc = nullptr;
+  int16_t *d_out = nullptr;  // [S][320]
+  char *h_in = nullptr, *h_in_dev = nullptr;  // page-locked [S] rate_ctl | the ragged frames (room for S frames of the longest class)
+  size_t lds_bytes = 0;
+  ww_resampler pass_r;        // the 16 kHz class of a feed: the identity form's tiles (resample_copy_kernel), no table
+  char *d_scratch = nullptr;  // a feed's [packets | the 16 kHz class's tiles], grown on demand
+  size_t scratch_cap = 0;
+  void layout() {
+    int64_t at = 0;
+    for (int s = 0; s < S; ++s) {
+      desc[(size_t)s] = {at, cls[(size_t)s], 0};
+      at += tab.g[cls[(size_t)s]].F;
+    }
+  }
+  int send() {
+    ww_tables tb;
+    tb.add(desc);
+    return tb.send(ctx, d_desc);
+  }
+};
+
+struct rates_class_dev {
+  const float *taps;
+  float *hist;  // [S][H]
+  int up, down, half, tpp, F, D, H, pass;
+};
+struct rates_tick_args {
+  const int16_t *frames;    // page-locked, ragged, from a 16-byte boundary, padded to whole 16-byte pieces
+  const rate_ctl *rc;       // page-locked [S]
+  const int32_t *ctl;       // the tick's own control words [S][4] (page-locked): bit 1 of word 2 = the stream is frozen
+  const rates_desc *desc;   // device [S]
+  int16_t *out;
+  rates_class_dev c[WW_STREAM_MAX_RATES];
+};
+
+__global__ __launch_bounds__(RATE_THREADS) void stream_rates_tick_kernel(rates_tick_args a) {
+  extern __shared__ float xs[];  // [H history | F frame | WW_RATE_PAD zeros] of the stream's class
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const rates_desc d = a.desc[s];
+  const rates_class_dev &g = a.c[__builtin_amdgcn_readfirstlane(d.cls) & (WW_STREAM_MAX_RATES - 1)];  // (scalar loads of the arguments)
+  const int F = g.F, H = g.H;
+  // the aligned 16-byte pieces that cover the frame's 2 F bytes, as in stream_rate_tick_kernel: a frame starts at any even byte
+  const size_t b0 = (size_t)d.off * 2, a0 = b0 & ~(size_t)15;
+  const int n16 = (int)((b0 + (size_t)F * 2 - a0 + 15) >> 4), lead = (int)(b0 - a0) >> 1;
+  const uint4 *src = (const uint4 *)((const char *)a.frames + a0);
+  uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+  if (tid < n16) raw = src[tid];
+  const int flags = a.ctl[s * 4 + 2];
+  const int4 cw = ((const int4 *)a.rc)[s];  // res, zeros, held
+  if (flags & 2) return;  // frozen: the frame is dropped whole, history and output block stay
+  if (g.pass) {  // the 16 kHz class: the frame is the stream's row of the block (41 pieces at most: one per lane)
+    int16_t *o = a.out + (size_t)s * WW_RATE_FRAME_OUT;
+    const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int i = tid * 8 + e - lead;
+      if (tid < n16 && i >= 0 && i < WW_RATE_FRAME_OUT) o[i] = (int16_t)(w[e >> 1] >> ((e & 1) * 16));
+    }
+    return;
+  }
+  float *hist = g.hist + (size_t)s * H;
+  auto put = [&](int q, const uint4 &v) {  // piece q: samples 8 q - lead .. 8 q - lead + 7 of the frame
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int i = q * 8 + e - lead;
+      if (i >= 0 && i < F) xs[H + i] = rs_load((int16_t)(w[e >> 1] >> ((e & 1) * 16)));
+    }
+  };
+  if (tid < n16) put(tid, raw);
+  for (int q = tid + RATE_THREADS; q < n16; q += RATE_THREADS) put(q, src[q]);
+  for (int i = tid; i < H; i += RATE_THREADS) xs[i] = i >= H - cw.z ? hist[i] : 0.0f;
+  if (tid < WW_RATE_PAD) xs[H + F + tid] = 0.0f;
+  __syncthreads();
+  const int up = g.up, down = g.down;
+  const rate_out_pos o = rate_position(up, down, g.D, tid, cw.x);
+  float acc[1];
+  rs_chains<1>(acc, xs + H + o.c - rs_jmax(g.half, o.p, up), g.taps + o.p, up, down, g.tpp);
+  rs_store(a.out + (size_t)s * WW_RATE_FRAME_OUT + tid, tid < cw.y ? 0.0f : acc[0]);
+  for (int i = tid; i < H; i += RATE_THREADS) hist[i] = xs[F + i];  // (every read of the row went through LDS above)
+}
+
+void ww_k_rates_destroy(ww_stream_rates *rt) {
+  if (!rt) return;
+  for (ww_stream_rate *c : rt->cls_rt) ww_k_rate_destroy(c);
+  if (rt->d_desc) hipFree(rt->d_desc);
+  if (rt->d_out) hipFree(rt->d_out);
+  if (rt->d_scratch) hipFree(rt->d_scratch);
+  if (rt->h_in) hipHostFree(rt->h_in);
+  delete rt;
+}
+
+static int rates_destroy_(ww_stream_rates *rt) {
+  ww_k_rates_destroy(rt);
+  return WW_OK;
+}
+
+int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, const int32_t *stream_rate, int S, ww_stream_rates **out) {
+  *out = nullptr;
+  char why[320];
+  ww_stream_rates *rt = new ww_stream_rates();
+  ww_scoped<ww_stream_rates, rates_destroy_> own(rt);
+  rt->ctx = ctx; rt->S = S;
+  rt->pass_r.ctx = ctx;
+  rt->pass_r.identity = true;
+  rt->pass_r.rate_in = rt->pass_r.rate_out = WW_RATE_OUT;
+  for (int k = 0; k < n_rates; ++k) {
+    const ww_resampler *r = rs[k];
+    if (r && r->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: class %d: the resampler belongs to another context", k);
+    if (r ? rates_add_class(rt->tab, false, r->rate_in, r->rate_out, r->up, r->down, r->half, r->tpp, why, sizeof why)
+          : rates_add_class(rt->tab, true, 0, 0, 0, 0, 0, 0, why, sizeof why))
+      return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %s", why);
+  }
+  if (rates_check_ids(rt->tab, stream_rate, S, "stream_rate", why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %s", why);
+  int64_t stage = 0;
+  if (rates_stage(rt->tab, &stage, why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %s", why);
+  rt->lds_bytes = (size_t)stage * 4;
+  for (int k = 0; k < n_rates; ++k)
+    if (rs[k])
+      if (int rc = ww_k_rate_create(ctx, rs[k], S, &rt->cls_rt[k])) return rc;
+  if (stream_rate) rt->cls.assign(stream_rate, stream_rate + S);
+  else rt->cls.assign((size_t)S, 0);
+  rt->desc.resize((size_t)S);
+  rt->layout();
+  ww_tables tb;
+  tb.add(rt->desc);
+  // (the frames start on a 16-byte boundary and end in whole 16-byte pieces: the kernel loads them as uint4)
+  const size_t b_out = (size_t)S * WW_RATE_FRAME_OUT * 2,
+               b_in = (size_t)S * sizeof(rate_ctl) + (((size_t)rates_layout_max(rt->tab, S) * 2 + 15) & ~(size_t)15) + 16;
+  if (hipMalloc((void **)&rt->d_desc, tb.bytes()) != hipSuccess || hipMalloc((void **)&rt->d_out, b_out) != hipSuccess ||
+      hipHostMalloc((void **)&rt->h_in, b_in) != hipSuccess)
+    return ww_fail(ctx, WW_ENOMEM, "cannot allocate the rate tables of %d streams in %d classes", S, n_rates);
+  if (((uintptr_t)rt->d_out & 15) != 0) return ww_fail(ctx, WW_EINTERNAL, "the tick's sample block is not 16-byte aligned");
+  memset(rt->h_in, 0, b_in);
+  WW_HIP(ctx, hipHostGetDevicePointer((void **)&rt->h_in_dev, rt->h_in, 0));
+  WW_HIP(ctx, hipMemsetAsync(rt->d_out, 0, b_out, ctx->stream));
+  if (int rc = rt->send()) return rc;
+  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *out = own.release();
+  return WW_OK;
+}
+
+int ww_k_rates_classes(const ww_stream_rates *rt) { return rt->tab.K; }
+
+void ww_k_rates_layout(const ww_stream_rates *rt, int32_t *frame_samples, int64_t *frame_offs) {
+  rates_layout(rt->tab, rt->cls.data(), rt->S, frame_samples, frame_offs);
+}
+
+// the count a stream's class keeps for it (the 16 kHz class keeps none)
+static int64_t &rates_count(ww_stream_rates *rt, int s, int64_t &none) {
+  ww_stream_rate *c = rt->cls_rt[rt->cls[(size_t)s]];
+  none = 0;
+  return c ? c->n[(size_t)s] : none;
+}
+
+void ww_k_rates_reset(ww_stream_rates *rt, const int32_t *ids, int count) {
+  int64_t none;
+  for (int i = 0; i < count; ++i) {
+    const int s = ids ? ids[i] : i;
+    rates_move(rt->cls[(size_t)s], rates_count(rt, s, none), rt->cls[(size_t)s]);
+  }
+}
+
+// The listed streams move to class c (checked by the caller) with their counts at 0, and the table goes up in stream order.  A
+// failure leaves the host's table as the device's was last sent; the caller marks the bank broken (the copy may have been enqueued).
+int ww_k_rates_move(ww_stream_rates *rt, const int32_t *ids, int count, int c) {
+  const std::vector<int32_t> before = rt->cls;
+  int64_t none;
+  for (int i = 0; i < count; ++i) {
+    const int s = ids ? ids[i] : i;
+    rt->cls[(size_t)s] = c;
+    rates_move(rt->cls[(size_t)s], rates_count(rt, s, none), c);
+  }
+  rt->layout();
+  if (int rc = rt->send()) {
+    rt->cls = before;
+    rt->layout();
+    return rc;
+  }
+  return WW_OK;
+}
+
+int64_t ww_k_rates_advance(const ww_stream_rates *rt, int stream, int64_t k) {
+  const int c = rt->cls[(size_t)stream];
+  return rates_advance(rt->tab, c, rt->cls_rt[c] ? rt->cls_rt[c]->n[(size_t)stream] : 0, k);
+}
+
+int ww_k_rates_tick(ww_stream_rates *rt, const int16_t *frames, const uint8_t *flags, const int32_t *ctl_dev, const int16_t **d_frames) {
+  ww_ctx *ctx = rt->ctx;
+  const int S = rt->S;
+  rate_ctl *rc = (rate_ctl *)rt->h_in;
+  int64_t none;
+  for (int s = 0; s < S; ++s) {
+    if (flags[s] & 2) continue;
+    rc[s] = rates_tick(rt->tab, rt->cls[(size_t)s], rates_count(rt, s, none));
+  }
+  const int64_t total = rt->desc[(size_t)S - 1].off + rt->tab.g[rt->cls[(size_t)S - 1]].F;
+  memcpy(rt->h_in + (size_t)S * sizeof(rate_ctl), frames, (size_t)total * 2);
+  rates_tick_args a = {};
+  a.rc = (const rate_ctl *)rt->h_in_dev;
+  a.frames = (const int16_t *)(rt->h_in_dev + (size_t)S * sizeof(rate_ctl));
+  a.ctl = ctl_dev;
+  a.desc = rt->d_desc;
+  a.out = rt->d_out;
+  for (int k = 0; k < rt->tab.K; ++k) {
+    const rate_geom &g = rt->tab.g[k];
+    const ww_stream_rate *c = rt->cls_rt[k];
+    a.c[k] = {c ? c->r->d_taps : nullptr, c ? c->d_hist : nullptr, (int)g.up, (int)g.down, (int)g.half, (int)g.tpp, g.F, g.D, g.hist, c ? 0 : 1};
+  }
+  for (int k = rt->tab.K; k < WW_STREAM_MAX_RATES; ++k) a.c[k] = a.c[0];  // (never picked: a class id is below K)
+  {
+    ww_launch_scope scope(ctx, "stream_rates_tick_kernel");
+    hipLaunchKernelGGL(stream_rates_tick_kernel, dim3((unsigned)S), dim3(RATE_THREADS), rt->lds_bytes, ctx->stream, a);
+  }
+  WW_HIP(ctx, hipGetLastError());
+  *d_frames = rt->d_out;
+  return WW_OK;
+}
+
+// A feed's packets, stream ids[i]'s at its own rate -> the call's 16 kHz samples at d_dst[offs16[i] .. offs16[i + 1]), offs16 as
+// ww_k_rates_advance counts them.  The packets go up once and are grouped by class (stream_rates.h): the 16 kHz class's go to their
+// place through the identity form's tiles, every other class's through the single-rate feed of that class with its subset of the
+// call - launches and copies per class present, whatever the number of streams.  *moved: as ww_k_rate_feed's.
+int ww_k_rates_feed(ww_stream_rates *rt, const int32_t *ids, int n, const int16_t *pcm, const int64_t *sample_offs, const int64_t *offs16,
+                    int16_t *d_dst, bool *moved) {
+  ww_ctx *ctx = rt->ctx;
+  std::vector<int32_t> pc((size_t)n);
+  for (int i = 0; i < n; ++i) pc[(size_t)i] = rt->cls[(size_t)ids[i]];
+  rates_groups grp;
+  rates_group(pc.data(), n, grp);
+  const int64_t s0 = sample_offs[0], samples = sample_offs[n] - s0;
+  rs_plan pl;
+  for (int c = 0; c < rt->tab.K; ++c) {
+    if (rt->cls_rt[c]) continue;
+    for (int j = grp.start[c]; j < grp.start[c + 1]; ++j) {
+      const int i = grp.order[(size_t)j];
+      const int64_t so[2] = {sample_offs[i] - s0, sample_offs[i + 1] - s0}, first[1] = {0}, oo[2] = {offs16[i], offs16[i + 1]};
+      rs_make_plan(&rt->pass_r, so, first, first, oo, 1, pl);
+    }
+  }
+  if (pl.count() > 0x7fffffffu) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: too much work for one call");
+  const size_t need = ww_bump::need((size_t)samples, 2) + ww_bump::need(pl.count(), sizeof(rs_tile)) + 1024;
+  if (need > rt->scratch_cap) {
+    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rt->d_scratch) WW_HIP(ctx, hipFree(rt->d_scratch));
+    rt->d_scratch = nullptr;
+    rt->scratch_cap = 0;
+    if (hipMalloc((void **)&rt->d_scratch, need) != hipSuccess) return ww_fail(ctx, WW_ENOMEM, "ww_stream_feed: cannot allocate %zu bytes for the call's samples", need);
+    rt->scratch_cap = need;
+  }
+  ww_bump db(rt->d_scratch, rt->scratch_cap);
+  int16_t *d_pk = db.take<int16_t>((size_t)samples);
+  rs_tile *d_tiles = db.take<rs_tile>(pl.count());
+  WW_HIP(ctx, hipMemcpyAsync(d_pk, pcm + s0, (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
+  if (offs16[n] > 0) WW_HIP(ctx, hipMemsetAsync(d_dst, 0, (size_t)offs16[n] * 2, ctx->stream));  // z's leading zeros
+  if (pl.count() > 0)
+    if (int rc = rs_run(&rt->pass_r, pl, d_tiles, d_pk, WW_SAMPLE_I16, d_dst, WW_SAMPLE_I16)) return rc;
+  for (int c = 0; c < rt->tab.K; ++c)
+    if (rt->cls_rt[c] && grp.start[c + 1] > grp.start[c])
+      if (int rc = rate_feed_run(rt->cls_rt[c], ids, n, grp.order.data() + grp.start[c], grp.start[c + 1] - grp.start[c], pcm, d_pk, sample_offs, offs16,
+                                 d_dst, nullptr, moved))
+        return rc;
   return WW_OK;
 }

@@ -102,6 +102,9 @@ struct ww_streams {
   // a bank at another rate than 16 kHz (ww_stream_attach_resampler): frames are [S][frame samples of that rate], and one kernel of
   // resample.hip in front of a tick's own turns them into the [S][320] block the tick kernels read
   ww_stream_rate *rate = nullptr;
+  // a bank whose streams each run at their own rate (ww_stream_attach_rates): frames are one ragged block, stream s's frame at its
+  // own rate, and ONE kernel of resample.hip in front of a tick's own serves every rate
+  ww_stream_rates *rates = nullptr;
   bool used = false;                  // ticked or fed since creation
   // the kernels' extra argument: nullptr for a bank of one model
   const ww_set_ref *ref() const { return set ? &set_ref : nullptr; }
@@ -343,6 +346,7 @@ int ww_stream_destroy(ww_streams *st) {
   for (void *p : host)
     if (p) hipHostFree(p);
   ww_k_rate_destroy(st->rate);
+  ww_k_rates_destroy(st->rates);
   delete st;
   return WW_OK;
   WW_GUARD_END(nullptr)
@@ -522,9 +526,72 @@ int ww_stream_attach_resampler(ww_streams *st, const ww_resampler *r) {
   if (!r) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: NULL resampler");
   if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
   if (st->rate) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: this bank already has a resampler (%d Hz frames)", ww_k_rate_frame_samples(st->rate) * 50);
+  if (st->rates) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: this bank already has per-stream rates (ww_stream_attach_rates)");
   if (st->used) return ww_fail(ctx, WW_ESTATE, "ww_stream_attach_resampler: the bank has ticked or been fed: a resampler is attached to a new bank");
   WW_ON_DEVICE(ctx, dev_scope);
   return ww_k_rate_create(ctx, r, st->S, &st->rate);
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+// A bank whose stream s runs at the input rate of class stream_rate[s] (include/wwhip.h).  What depends on the classes and the state
+// object are ww_k_rates_create's (resample.hip; stream_rates.h); no kernel of the bank changes, a tick only reads its samples elsewhere.
+int ww_stream_attach_rates(ww_streams *st, const ww_resampler *const *rs, int32_t n_rates, const int32_t *stream_rate) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  ww_ctx *ctx = st->ctx;
+  if (!rs) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: NULL class table");
+  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
+  if (n_rates < 1 || n_rates > WW_STREAM_MAX_RATES)
+    return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %d rate classes: a bank has 1..%d", (int)n_rates, WW_STREAM_MAX_RATES);
+  if (st->rate) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: this bank already has a resampler (%d Hz frames)", ww_k_rate_frame_samples(st->rate) * 50);
+  if (st->rates) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: this bank already has its rates (%d classes)", ww_k_rates_classes(st->rates));
+  if (st->used) return ww_fail(ctx, WW_ESTATE, "ww_stream_attach_rates: the bank has ticked or been fed: rates are attached to a new bank");
+  WW_ON_DEVICE(ctx, dev_scope);
+  return ww_k_rates_create(ctx, rs, n_rates, stream_rate, st->S, &st->rates);
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+int ww_stream_frame_layout(const ww_streams *st, int32_t *frame_samples, int64_t *frame_offs) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  if (!frame_samples || !frame_offs) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_layout: NULL argument");
+  if (st->rates) {
+    ww_k_rates_layout(st->rates, frame_samples, frame_offs);
+    return WW_OK;
+  }
+  const int F = st->rate ? ww_k_rate_frame_samples(st->rate) : WW_CHUNK;
+  for (int s = 0; s <= st->S; ++s) {
+    if (s < st->S) frame_samples[s] = F;
+    frame_offs[s] = (int64_t)s * F;
+  }
+  return WW_OK;
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+// The listed streams move to another rate class of the bank and start afresh: the table first, then ww_stream_reset's kernels behind
+// it on the stream, exactly as ww_stream_set_model does.
+int ww_stream_set_rate(ww_streams *st, const int32_t *ids, int32_t n, int32_t rate_class) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  ww_ctx *ctx = st->ctx;
+  if (!st->rates) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_rate: this bank has no per-stream rates (ww_stream_attach_rates)");
+  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
+  const int K = ww_k_rates_classes(st->rates);
+  if (rate_class < 0 || rate_class >= K) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_rate: class %d: the bank has rate classes 0..%d", (int)rate_class, K - 1);
+  if (ids && n < 0) return ww_fail(ctx, WW_EINVAL, "negative id count");
+  if (ids && n > 2 * st->S) return ww_fail(ctx, WW_EINVAL, "more ids than streams");
+  const int count = ids ? n : st->S;
+  for (int i = 0; ids && i < n; ++i)
+    if (ids[i] < 0 || ids[i] >= st->S) return ww_fail(ctx, WW_EINVAL, "stream id %d out of range", ids[i]);
+  if (count == 0) return WW_OK;
+  WW_ON_DEVICE(ctx, dev_scope);
+  if (int rc = ww_k_rates_move(st->rates, ids, count, rate_class)) {
+    st->broken = true;  // (the copy may or may not have been enqueued: which table the device holds is not known)
+    return rc;
+  }
+  const int rc = ww_stream_reset(st, ids, n);
+  if (rc != WW_OK) st->broken = true;
+  return rc;
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
@@ -532,6 +599,7 @@ int ww_stream_frame_samples(const ww_streams *st, int32_t *out) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
   if (!out) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_samples: NULL argument");
+  if (st->rates) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_samples: the streams of this bank have frames of their own: ww_stream_frame_layout");
   *out = st->rate ? ww_k_rate_frame_samples(st->rate) : WW_CHUNK;
   return WW_OK;
   WW_GUARD_END(st ? st->ctx : nullptr)
@@ -602,6 +670,7 @@ int ww_stream_reset(ww_streams *st, const int32_t *ids, int32_t n) {
     st->rowq[s] = 0;
   }
   if (st->rate) ww_k_rate_reset(st->rate, ids, count);  // the next sample is x[0] of a new signal: D zeros lead again
+  if (st->rates) ww_k_rates_reset(st->rates, ids, count);
   return WW_OK;
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
@@ -732,6 +801,8 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   const int16_t *rate_frames = nullptr;
   if (st->rate) {
     if (int rc = ww_k_rate_tick(st->rate, frames, is_speech, (const int32_t *)(st->h_pack_dev + ((char *)h_ctl - st->h_pack)), &rate_frames)) return rc;
+  } else if (st->rates) {
+    if (int rc = ww_k_rates_tick(st->rates, frames, is_speech, (const int32_t *)(st->h_pack_dev + ((char *)h_ctl - st->h_pack)), &rate_frames)) return rc;
   } else {
     memcpy(h_frames, frames, (size_t)S * WW_CHUNK * 2);
   }
@@ -881,6 +952,7 @@ static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64
     int64_t k = sample_offs[i + 1] - sample_offs[i];
     if (k < 0) return ww_fail(ctx, WW_EINVAL, "%s: sample_offs descend at entry %d", what, i);
     if (st->rate) k = ww_k_rate_advance(st->rate, s, k);
+    if (st->rates) k = ww_k_rates_advance(st->rates, s, k);
     if (offs16) (*offs16)[(size_t)i + 1] = (*offs16)[(size_t)i] + k;
     const int64_t r = ww_fe_frames(st->fill[s] + k, st->fp.hop);
     if (r > 0x3fffffff || rows + r > 0x3fffffff) return ww_fail(ctx, WW_EINVAL, "%s: more than 2^30 rows in one call", what);
@@ -911,7 +983,7 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
   st->used = true;
   // a bank at another rate: from here on the packets are their 16 kHz samples, which ww_k_rate_feed leaves on the device
   const int64_t *in_offs = sample_offs;
-  if (st->rate) sample_offs = offs16.data();
+  if (st->rate || st->rates) sample_offs = offs16.data();
   const int64_t samples = sample_offs[n] - sample_offs[0];
   const ww_model *m = st->model;
   const int T = st->T, F = st->F, NO = st->NO, R = T + 1, hop = st->fp.hop, rf = ww_wave_receptive_field(m);
@@ -949,6 +1021,13 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
       return WW_OK;
     }
   }
+  if (st->rates) {  // (a mixed-rate bank's 16 kHz samples land in d_pcm itself)
+    if (int rc = ww_k_rates_feed(st->rates, ids, n, pcm, in_offs, sample_offs, d_pcm, mutated)) return rc;
+    if (samples == 0) {
+      WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      return WW_OK;
+    }
+  }
   // ---- from here on the host's mirrors of the streams' state advance
   *mutated = true;
   for (int i = 0; i < n; ++i) {
@@ -959,7 +1038,7 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
   }
   if (rate_pcm) {
     if (samples > 0) WW_HIP(ctx, hipMemcpyAsync(d_pcm, rate_pcm, (size_t)samples * 2, hipMemcpyDeviceToDevice, ctx->stream));
-  } else {
+  } else if (!st->rates) {
     WW_HIP(ctx, hipMemcpyAsync(d_pcm, pcm + sample_offs[0], (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
   }
   feed_fe_args a = {};

@@ -117,6 +117,9 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_stream_window": (C.c_int, [_vp, _i32, _vp]),
     "ww_stream_attach_resampler": (C.c_int, [_vp, _vp]),
     "ww_stream_frame_samples": (C.c_int, [_vp, _P(_i32)]),
+    "ww_stream_attach_rates": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "ww_stream_frame_layout": (C.c_int, [_vp, _vp, _vp]),
+    "ww_stream_set_rate": (C.c_int, [_vp, _vp, _i32, _i32]),
     "ww_stream_feed_rows": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     "ww_stream_feed": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "ww_stream_timeline": (C.c_int, [_vp, _vp, _P(_i64), _i32]),

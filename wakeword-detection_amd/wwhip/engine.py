@@ -523,8 +523,33 @@ class ModelSet:
             pass
 
 
+MAX_RATES = 8  # WW_STREAM_MAX_RATES
+
+
+def _stream_rates(sample_rate, n_streams: int, resampler) -> Tuple[np.ndarray, List[int]]:
+    """``sample_rate`` given per stream -> (``int32[S]`` rates, the distinct rates in order of first appearance: the bank's rate
+    classes).  Everything that can be refused without a device is refused here."""
+    if resampler is not None:
+        raise ValueError("resampler= belongs to a bank at ONE rate: a bank with per-stream rates creates and owns its resamplers")
+    rates = np.asarray(sample_rate)
+    if rates.ndim != 1 or rates.size != n_streams:
+        raise ValueError(f"sample_rate must name one rate per stream ({n_streams}), got {rates.size if rates.ndim == 1 else rates.shape}")
+    if rates.dtype.kind not in "iu":
+        raise ValueError("sample_rate must be whole numbers of Hz")
+    rates = rates.astype(np.int64)
+    for r in rates.tolist():
+        if r <= 0 or r % 50:
+            raise ValueError(f"sample_rate {r}: a 20 ms frame must be a whole number of samples "
+                             "(rates with a fractional frame are not offered in the tick)")
+    classes = list(dict.fromkeys(rates.tolist()))
+    if len(classes) > MAX_RATES:
+        raise ValueError(f"{len(classes)} distinct sample rates: a bank has at most {MAX_RATES} rate classes")
+    return rates.astype(np.int32), classes
+
+
 class StreamBank:
     """S device-resident streams advanced 20 ms per :meth:`step` (``ww_stream_*``)."""
+    _mixed = False  # per-stream rates (sample_rate given as a sequence)
 
     def __init__(self, engine, n_streams: int, fp: Optional[_lib.FrontendParams] = None,
                  full_recompute: bool = False, two_launch: bool = False, sync_wait: bool = False, causal: bool = False,
@@ -541,9 +566,22 @@ class StreamBank:
         ``sample_rate`` other than 16000: the bank runs at that rate (``ww_stream_attach_resampler``) - :meth:`step` takes
         ``[S, frame_samples]`` frames, ``frame_samples = sample_rate / 50``, :meth:`feed` packets at that rate, and every stream
         yields the bits of the 16 kHz bank given its resampled signal behind ``D`` zeros (``include/wwhip.h``).  The bank creates
-        and owns a ``Resampler(sample_rate, 16000, ctx)``, or takes ``resampler`` (which must outlive it)."""
+        and owns a ``Resampler(sample_rate, 16000, ctx)``, or takes ``resampler`` (which must outlive it).
+        ``sample_rate`` as a SEQUENCE of S rates (up to 8 distinct ones; always this form, even with one distinct rate): stream
+        ``s`` runs at ``sample_rate[s]`` (``ww_stream_attach_rates``) and yields the bits it yields in a bank at that rate alone.
+        :attr:`sample_rates`, :attr:`frame_samples` (``int32[S]``) and :attr:`frame_offs` (``int64[S + 1]``) describe a tick's
+        frames: ONE flat int16 block of ``frame_offs[S]`` samples, stream ``s``'s ``sample_rate[s] / 50`` samples from
+        ``frame_offs[s]`` - or a sequence of S per-stream arrays, which is concatenated.  :meth:`feed` takes each stream's packet
+        at that stream's rate, :meth:`set_rate` moves streams to another of the bank's rates.  The bank creates and owns one
+        ``Resampler(r, 16000, ctx)`` per distinct rate other than 16000."""
         self.engine = engine
         self.S = int(n_streams)
+        if not isinstance(sample_rate, (int, np.integer)):
+            rates, classes = _stream_rates(sample_rate, self.S, resampler)
+            self._create(engine, fp, full_recompute, two_launch, sync_wait, causal, models)
+            self._attach_rates(rates, classes)
+            self._tick_arrays()
+            return
         self.sample_rate = int(sample_rate if resampler is None else resampler.rate_in)
         if resampler is not None and int(sample_rate) not in (16000, self.sample_rate):
             raise ValueError(f"sample_rate = {sample_rate}, but the resampler reads {self.sample_rate} Hz")
@@ -554,6 +592,19 @@ class StreamBank:
             raise ValueError("a resampler from 16000 Hz: that is a plain bank")
         self.frame_samples = self.sample_rate // 50
         self._resampler, self._own_resampler = resampler, False
+        self._create(engine, fp, full_recompute, two_launch, sync_wait, causal, models)
+        if self.sample_rate != 16000:
+            if self._resampler is None:
+                from .resample import Resampler
+                self._resampler, self._own_resampler = Resampler(self.sample_rate, 16000, engine.ctx), True
+            _lib.raise_for(self._lib.ww_stream_attach_resampler(self._h, self._resampler._h), engine.ctx.handle)
+            n = C.c_int32(0)
+            _lib.raise_for(self._lib.ww_stream_frame_samples(self._h, C.byref(n)), engine.ctx.handle)
+            assert n.value == self.frame_samples
+        self._shape = (self.S, self.frame_samples)
+        self._tick_arrays()
+
+    def _create(self, engine, fp, full_recompute, two_launch, sync_wait, causal, models) -> None:
         is_set = isinstance(engine, ModelSet)
         if models is not None and not is_set:
             raise ValueError("models= names the members of a ModelSet: this bank is built on one Engine")
@@ -574,24 +625,61 @@ class StreamBank:
                            engine.ctx.handle)
         self._h = h
         _lib.register("streams", self)
-        if self.sample_rate != 16000:
-            if self._resampler is None:
-                from .resample import Resampler
-                self._resampler, self._own_resampler = Resampler(self.sample_rate, 16000, engine.ctx), True
-            _lib.raise_for(self._lib.ww_stream_attach_resampler(self._h, self._resampler._h), engine.ctx.handle)
-            n = C.c_int32(0)
-            _lib.raise_for(self._lib.ww_stream_frame_samples(self._h, C.byref(n)), engine.ctx.handle)
-            assert n.value == self.frame_samples
+
+    def _attach_rates(self, rates: np.ndarray, classes: List[int]) -> None:
+        from .resample import Resampler
+        self._mixed, self.sample_rate = True, None
+        self._classes, self._resampler, self._own_resampler = classes, None, False
+        self._class_rs = []
+        try:
+            for r in classes:
+                self._class_rs.append(None if r == 16000 else Resampler(r, 16000, self.engine.ctx))
+            table = (C.c_void_p * len(classes))(*[None if r is None else r._h for r in self._class_rs])
+            cls = np.array([classes.index(int(r)) for r in rates], np.int32)
+            _lib.raise_for(self._lib.ww_stream_attach_rates(self._h, table, len(classes), _lib.ptr(cls)), self.engine.ctx.handle)
+            self._read_layout()
+            assert np.array_equal(self.frame_samples, rates // 50)
+        except Exception:
+            self.close()
+            raise
+
+    def _read_layout(self) -> None:
+        """``frame_samples``, ``frame_offs`` and ``sample_rates`` as the library states them (``ww_stream_frame_layout``)."""
+        fs, fo = np.zeros(self.S, np.int32), np.zeros(self.S + 1, np.int64)
+        _lib.raise_for(self._lib.ww_stream_frame_layout(self._h, _lib.ptr(fs), _lib.ptr(fo)), self.engine.ctx.handle)
+        self.frame_samples, self.frame_offs, self.sample_rates = fs, fo, fs * 50
+
+    def _tick_arrays(self) -> None:
         self._post = np.zeros((self.S, 2), np.float32)
         self._n = np.zeros(self.S, np.int32)
         self._flags = np.zeros(self.S, np.uint8)
         # a tick is host-paced (spokestack/pipeline.py:25-28): the addresses of the bank's own arrays are taken once, not per call
         self._p_post, self._p_n, self._p_flags = (C.c_void_p(a.ctypes.data) for a in (self._post, self._n, self._flags))
         self._step = self._lib.ww_stream_step
-        self._shape = (self.S, self.frame_samples)
         self._keep = None
+        if not self._mixed:
+            self.sample_rates = np.full(self.S, self.sample_rate, np.int32)
+            self.frame_offs = np.arange(self.S + 1, dtype=np.int64) * self.frame_samples
+
+    def _ragged_address(self, frames) -> int:
+        """A bank with per-stream rates: the flat int16 block of ``frame_offs[S]`` samples, or S per-stream arrays."""
+        f = frames
+        if not (type(f) is np.ndarray and f.dtype == np.int16 and f.ndim == 1 and f.flags.c_contiguous):
+            if type(f) is np.ndarray and f.ndim == 1 and f.dtype != object:
+                f = np.ascontiguousarray(f, dtype=np.int16)
+            else:
+                if len(f) != self.S:
+                    raise ValueError(f"frames must be one array per stream ({self.S}) or the flat block of {int(self.frame_offs[self.S])} int16 samples")
+                f = np.concatenate([np.asarray(a, dtype=np.int16).ravel() for a in f]) if self.S else np.zeros(0, np.int16)
+            self._keep = f  # (kept alive until the call has returned)
+        if f.size != int(self.frame_offs[self.S]):
+            raise ValueError(f"frames must hold {int(self.frame_offs[self.S])} int16 samples (ww_stream_frame_layout: stream s's "
+                             f"{'/'.join(str(int(v)) for v in sorted(set(self.frame_samples.tolist())))} samples from frame_offs[s]), got {f.size}")
+        return f.ctypes.data
 
     def _frames_address(self, frames: np.ndarray) -> int:
+        if self._mixed:
+            return self._ragged_address(frames)
         f = frames
         if not (type(f) is np.ndarray and f.dtype == np.int16 and f.flags.c_contiguous):
             f = self._keep = np.ascontiguousarray(frames, dtype=np.int16)  # (kept alive until the call has returned)
@@ -656,6 +744,21 @@ class StreamBank:
             raise ValueError("stream id out of range")
         _lib.raise_for(self._lib.ww_stream_set_model(self._h, _lib.ptr(a), 0 if a is None else a.size, int(model)), self.engine.ctx.handle)
 
+    def set_rate(self, ids: Optional[Sequence[int]], rate: int) -> None:
+        """Move the listed streams (``None``: all) to ``rate`` Hz, one of the rates the bank was built with, and reset them
+        (``ww_stream_set_rate``: the next sample is the first of a new signal).  ``frame_samples``, ``frame_offs`` and
+        ``sample_rates`` are read again: the layout of a tick's frames changes with the move."""
+        if not self._mixed:
+            raise ValueError("set_rate: this bank runs at one rate (sample_rate was not given per stream)")
+        if int(rate) not in self._classes:
+            raise ValueError(f"set_rate: {rate} Hz is not among the bank's rates {self._classes}")
+        a = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        if a is not None and a.size and (a.min() < 0 or a.max() >= self.S):
+            raise ValueError("stream id out of range")
+        _lib.raise_for(self._lib.ww_stream_set_rate(self._h, _lib.ptr(a), 0 if a is None else a.size, self._classes.index(int(rate))),
+                       self.engine.ctx.handle)
+        self._read_layout()
+
     def window(self, stream: int) -> np.ndarray:
         """Stream ``stream``'s newest ``[window, n_mel]`` mel window, the block the model reads (``ww_stream_window``: a
         read-out; the bank's state is left as it is)."""
@@ -667,7 +770,8 @@ class StreamBank:
         """A causal bank advanced by any subset of its streams and any number of samples for each (``ww_stream_feed``):
         stream ``ids[i]`` receives the int16 samples ``packets[i]``.  Returns ``(posts, mels)``: per listed stream the posteriors
         of its new mel rows ``[rows]`` and, with ``want_mel``, the rows themselves ``[rows, n_mel]`` (``mels`` is ``None``
-        otherwise).  However the samples are cut into packets, calls and :meth:`step` ticks, the results are the same bits."""
+        otherwise).  However the samples are cut into packets, calls and :meth:`step` ticks, the results are the same bits.
+        A bank at another rate, or with per-stream rates: each packet is at its stream's own rate."""
         a_ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
         n = int(a_ids.size)
         if len(packets) != n:
@@ -695,6 +799,10 @@ class StreamBank:
         if getattr(self, "_own_resampler", False):  # (behind the bank: it borrows the tap table)
             self._resampler.close()
             self._own_resampler = False
+        for r in getattr(self, "_class_rs", []):
+            if r is not None:
+                r.close()
+        self._class_rs = []
 
     def __del__(self):  # pragma: no cover
         try:

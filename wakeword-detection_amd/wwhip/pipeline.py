@@ -84,7 +84,8 @@ class SpeechPipeline:
 
 class SpeechPipelineBank(SpeechPipeline):
     """The same loop for S streams in lock step (BASELINE config 5): ``input_source.read()`` returns one 20 ms frame per stream
-    (``int16[S, 320]``, or ``int16[S, sample_rate / 50]`` where the wake-word stage's bank runs at another rate), the context is a :class:`~wwhip.context.ContextBank`, the stages are the banked ones -
+    (``int16[S, 320]``, or ``int16[S, sample_rate / 50]`` where the wake-word stage's bank runs at another rate; the flat ragged
+    block or S per-stream arrays where it has per-stream rates: passed through to the bank as they are), the context is a :class:`~wwhip.context.ContextBank`, the stages are the banked ones -
     ``VadBank``, ``WakewordBank``, ``ActivationTimeoutBank`` - called as ``stage(contexts, frames)`` in list order, one call per
     stage and tick whatever S is.  ``pipeline.context[s]`` is stream ``s``'s ``SpeechContext``; ``pipeline.event`` registers a
     handler for every stream (it receives the stream's context)."""

@@ -98,7 +98,8 @@ class VadBank:
     whose ``is_speech`` array IS the state (as the context is in the reference) and the raw decisions come from a batch
     classifier ``classifier(frames[S, F]) -> bool[S]`` (or are passed as ``raw=``); F is the frame length of the bank the
     frames are for - 320, or ``sample_rate / 50`` in front of a ``StreamBank(sample_rate=...)``: the classifier sees the frames at
-    the bank's rate, as webrtcvad would."""
+    the bank's rate, as webrtcvad would.  In front of a bank with per-stream rates (``StreamBank(sample_rate=[...])``) the
+    classifier receives what the source delivers - the flat ragged block or the S per-stream arrays - as it is."""
 
     def __init__(self, n_streams: int, frame_width: int = 20, vad_rise_delay: int = 0, vad_fall_delay: int = 0,
                  classifier: Optional[Callable[[np.ndarray], Sequence[bool]]] = None) -> None:

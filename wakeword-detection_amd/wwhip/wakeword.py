@@ -100,7 +100,9 @@ class WakewordBank:
 
     ``contexts`` is a :class:`~wwhip.context.ContextBank` - the stage then reads and writes the bank's flag arrays in place and
     raises ``activate`` events for the streams that fired, no per-stream Python otherwise - or, as before, a sequence of S
-    ``SpeechContext`` objects (their flags are gathered and written back one by one: the slow form)."""
+    ``SpeechContext`` objects (their flags are gathered and written back one by one: the slow form).  ``frames`` is what the
+    bank's :meth:`~wwhip.engine.StreamBank.step` takes and is passed through unchanged: ``[S, frame_samples]``, or for a bank with
+    per-stream rates the flat ragged block (or the S per-stream arrays)."""
 
     def __init__(self, n_streams: int, model_dir: str = "", posterior_threshold: float = 0.5, pre_emphasis: float = 0.0,
                  device: int = 0, on_wake: Optional[Callable[[np.ndarray], None]] = None, bank=None, causal: bool = False) -> None:
