@@ -280,29 +280,23 @@ int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv
 int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, const int64_t *d_win_row, const int32_t *d_win_valid,
                           const int32_t *d_win_aux, int nw, float *d_state, float *d_zring, int32_t *d_zpos, float *d_out,
                           const ww_tick_tag *tag, const ww_set_ref *set = nullptr);
-// A stream bank at another rate than 16 kHz (resample.hip; geometry and bookkeeping: stream_rate.h).  The state object belongs to the
-// bank (streams.hip) and borrows the resampler's tap table.  _create: WW_EINVAL with the refusal's reason.  _tick: the S frames
-// [S][F] -> the [S][320] int16 device block *d_frames that the tick's kernels then read, ONE kernel on the context's stream in front
-// of them; flags = the tick's (bit 1: the stream is frozen), ctl_dev = the tick's control words as the device sees them.
-// _advance: the 16 kHz samples `stream` would consume on k more input samples (no state moves).  _feed: see resample.hip.
+// A stream bank at other rates than 16 kHz (resample.hip; geometry and bookkeeping: stream_rate.h, stream_rates.h).  ONE state
+// object, which belongs to the bank (streams.hip) and borrows the resamplers' tap tables: rs[k] = rate class k (nullptr: the 16 kHz
+// class), stream_rate[s] = the class of stream s (nullptr: all 0).  `uniform` (ww_stream_attach_resampler): the one class rs[0], every
+// stream in it for good, frames [S][F] - _frame_samples gives F there and 0 on a per-stream bank, whose frames are one ragged block
+// (_layout).  _create: WW_EINVAL with the refusal's reason.  _tick: the frames -> the [S][320] int16 device block *d_frames that the
+// tick's kernels then read, ONE kernel for every class on the context's stream in front of them; flags = the tick's (bit 1: the
+// stream is frozen), ctl_dev = the tick's control words as the device sees them.  _reset: the listed streams' counts to 0 (ids ==
+// nullptr: streams 0 .. count - 1).  _move: the listed streams to class c with their counts at 0, the device table behind it in
+// stream order.  _advance: the 16 kHz samples `stream` would consume on k more input samples (no state moves).  _feed: the call's
+// 16 kHz samples into d_dst (see resample.hip).
 struct ww_resampler;
-struct ww_stream_rate;
-int ww_k_rate_create(ww_ctx *ctx, const ww_resampler *r, int S, ww_stream_rate **out);
-void ww_k_rate_destroy(ww_stream_rate *rt);
-int ww_k_rate_frame_samples(const ww_stream_rate *rt);
-void ww_k_rate_reset(ww_stream_rate *rt, const int32_t *ids, int count);  // ids == nullptr: streams 0 .. count - 1
-int64_t ww_k_rate_advance(const ww_stream_rate *rt, int stream, int64_t k);
-int ww_k_rate_tick(ww_stream_rate *rt, const int16_t *frames, const uint8_t *flags, const int32_t *ctl_dev, const int16_t **d_frames);
-int ww_k_rate_feed(ww_stream_rate *rt, const int32_t *ids, int n, const int16_t *pcm, const int64_t *sample_offs, const int64_t *offs16,
-                   const int16_t **d_pcm16, bool *moved);
-// A stream bank whose streams each run at their own rate (resample.hip; geometry and bookkeeping: stream_rates.h): rs[k] = rate class
-// k (nullptr: the 16 kHz class), stream_rate[s] = the class of stream s (nullptr: all 0).  _tick: the ragged frames -> the [S][320]
-// block, ONE kernel for every class.  _move: the listed streams (nullptr: 0 .. count - 1) to class c with their counts at 0, the
-// device table behind it in stream order.  _feed: the call's 16 kHz samples into d_dst (see resample.hip).  The rest as above.
 struct ww_stream_rates;
-int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, const int32_t *stream_rate, int S, ww_stream_rates **out);
+int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, const int32_t *stream_rate, int S, bool uniform,
+                      ww_stream_rates **out);
 void ww_k_rates_destroy(ww_stream_rates *rt);
 int ww_k_rates_classes(const ww_stream_rates *rt);
+int ww_k_rates_frame_samples(const ww_stream_rates *rt);
 void ww_k_rates_layout(const ww_stream_rates *rt, int32_t *frame_samples, int64_t *frame_offs);  // [S], [S + 1]; either may be nullptr
 void ww_k_rates_reset(ww_stream_rates *rt, const int32_t *ids, int count);
 int ww_k_rates_move(ww_stream_rates *rt, const int32_t *ids, int count, int c);

@@ -381,283 +381,46 @@ int ww_resample(ww_resampler *r, const void *in, int32_t in_format, const int64_
 
 }  // extern "C"
 
-// ---- a stream bank at another rate than 16 kHz (streams.hip: ww_stream_attach_resampler) ---------------------------
-// The bank's kernels are untouched: ONE kernel in front of a tick turns the S streams' frames at the bank's rate (F = rate / 50
-// samples each, page-locked) into the [S][320] int16 block the tick kernels read their samples from.  The geometry and the
-// bookkeeping are stream_rate.h's (host only); the arithmetic is this file's rule - rs_load, ONE chain per output over the
-// resampler's own tap table, rs_store -, so a stream's 16 kHz samples are the one-shot's bits behind D zeros.
-// One workgroup per stream, one lane per output.  A stream's state is the last `hist` input samples as fp32 (right-aligned; of a
-// young stream only the last `held` are its own, what lies in front reads as zero - a reset is the host's `held = 0`, no kernel):
-// read into LDS in front of the frame by the one workgroup that writes it back, no order between workgroups.
-struct ww_stream_rate {
-  ww_ctx *ctx = nullptr;
-  const ww_resampler *r = nullptr;
-  rate_geom g;
-  int S = 0;
-  float *d_hist = nullptr;    // [S][hist]
-  int16_t *d_out = nullptr;   // [S][320]: the tick's 16 kHz samples (640 bytes per stream: the tick kernels load them 16 at a time)
-  // the tick's page-locked input: [S] rate_ctl | [S][F] int16.  ONE copy: the kernel that reads it precedes the tick's kernel on
-  // the stream, so it has ended when a polled tick's first tag arrives
-  char *h_in = nullptr, *h_in_dev = nullptr;
-  std::vector<int64_t> n;     // input samples since the stream's last reset, frozen ticks left out
-  char *d_scratch = nullptr;  // a feed's [table | packets | segments | 16 kHz samples | tiles], grown on demand
-  size_t scratch_cap = 0;
-};
-
-struct rate_tick_args {
-  const int16_t *frames;  // page-locked [S][F], from a 16-byte boundary, padded to whole 16-byte pieces
-  const rate_ctl *rc;     // page-locked [S]
-  const int32_t *ctl;     // the tick's own control words [S][4] (page-locked): bit 1 of word 2 = the stream is frozen
-  const float *taps;
-  float *hist;
-  int16_t *out;
-  int up, down, half, tpp, F, D, H;
-};
-
-#define RATE_THREADS WW_RATE_FRAME_OUT
-
-__global__ __launch_bounds__(RATE_THREADS) void stream_rate_tick_kernel(rate_tick_args a) {
-  extern __shared__ float xs[];  // [H history | F frame | WW_RATE_PAD zeros]
-  const int s = blockIdx.x, tid = threadIdx.x;
-  // The frame crosses the bus 16 bytes per lane, whatever F is: the aligned 16-byte pieces that cover its 2 F bytes (the first and
-  // the last may hold a neighbour's samples, which are dropped; the block is padded to whole pieces).  The first RATE_THREADS
-  // pieces are requested BEFORE the control words are looked at - one trip over the bus instead of two in a row.
-  const size_t b0 = (size_t)s * a.F * 2, a0 = b0 & ~(size_t)15;
-  const int n16 = (int)((b0 + (size_t)a.F * 2 - a0 + 15) >> 4), lead = (int)(b0 - a0) >> 1;
-  const uint4 *src = (const uint4 *)((const char *)a.frames + a0);
-  uint4 raw = make_uint4(0u, 0u, 0u, 0u);
-  if (tid < n16) raw = src[tid];
-  const int flags = a.ctl[s * 4 + 2];
-  const int4 cw = ((const int4 *)a.rc)[s];  // res, zeros, held
-  if (flags & 2) return;  // frozen: the frame is dropped whole, history and output block stay
-  float *hist = a.hist + (size_t)s * a.H;
-  auto put = [&](int q, const uint4 &v) {  // piece q: samples 8 q - lead .. 8 q - lead + 7 of the frame
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int i = q * 8 + e - lead;
-      if (i >= 0 && i < a.F) xs[a.H + i] = rs_load((int16_t)(w[e >> 1] >> ((e & 1) * 16)));
-    }
-  };
-  if (tid < n16) put(tid, raw);
-  for (int q = tid + RATE_THREADS; q < n16; q += RATE_THREADS) put(q, src[q]);
-  for (int i = tid; i < a.H; i += RATE_THREADS) xs[i] = i >= a.H - cw.z ? hist[i] : 0.0f;
-  if (tid < WW_RATE_PAD) xs[a.H + a.F + tid] = 0.0f;
-  __syncthreads();
-  const rate_out_pos o = rate_position(a.up, a.down, a.D, tid, cw.x);
-  float acc[1];
-  rs_chains<1>(acc, xs + a.H + o.c - rs_jmax(a.half, o.p, a.up), a.taps + o.p, a.up, a.down, a.tpp);
-  rs_store(a.out + (size_t)s * WW_RATE_FRAME_OUT + tid, tid < cw.y ? 0.0f : acc[0]);
-  for (int i = tid; i < a.H; i += RATE_THREADS) hist[i] = xs[a.F + i];  // (every read of the row went through LDS above)
-}
-
-// A feed's splice: stream d.sid's segment = [the `held` samples it holds | its packet of k] as fp32 for the resample kernels, and its
-// new history behind their reads.  Workgroup (i, c) copies samples [c * RATE_SPLICE, +RATE_SPLICE) of the segment; history rows
-// are shorter than that, so workgroup (i, 0) is the row's one reader, and it is its one writer.
-#define RATE_SPLICE 16384
-struct rate_feed_str {
-  int64_t pk_off;   // the packet's first sample in the call's packet buffer
-  int64_t k;        // its samples (> 0)
-  int64_t seg_off;  // the segment's first sample in the call's segment buffer
-  int32_t sid, held;
-};
-__global__ __launch_bounds__(256) void stream_rate_splice_kernel(const int16_t *pk, const rate_feed_str *str, float *seg, float *hist, int H) {
-  extern __shared__ float nh[];  // [H]
-  const rate_feed_str d = str[blockIdx.x];
-  float *h = hist + (size_t)d.sid * H;
-  const int64_t tot = d.held + d.k, v0 = (int64_t)blockIdx.y * RATE_SPLICE;
-  if (v0 >= tot) return;
-  auto sample = [&](int64_t v) -> float { return v < d.held ? h[H - d.held + v] : rs_load(pk[d.pk_off + (v - d.held)]); };
-  const int64_t v1 = v0 + RATE_SPLICE < tot ? v0 + RATE_SPLICE : tot;
-  for (int64_t v = v0 + threadIdx.x; v < v1; v += 256) seg[d.seg_off + v] = sample(v);
-  if (blockIdx.y) return;
-  const int keep = (int)(tot < H ? tot : H);
-  for (int i = threadIdx.x; i < keep; i += 256) nh[i] = sample(tot - keep + i);
-  __syncthreads();  // the row has been read
-  for (int i = threadIdx.x; i < keep; i += 256) h[H - keep + i] = nh[i];
-}
-
-void ww_k_rate_destroy(ww_stream_rate *rt) {
-  if (!rt) return;
-  if (rt->d_hist) hipFree(rt->d_hist);
-  if (rt->d_out) hipFree(rt->d_out);
-  if (rt->d_scratch) hipFree(rt->d_scratch);
-  if (rt->h_in) hipHostFree(rt->h_in);
-  delete rt;
-}
-
-static int rate_destroy_(ww_stream_rate *rt) {
-  ww_k_rate_destroy(rt);
-  return WW_OK;
-}
-
-int ww_k_rate_create(ww_ctx *ctx, const ww_resampler *r, int S, ww_stream_rate **out) {
-  *out = nullptr;
-  if (r->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: the resampler belongs to another context");
-  char why[256];
-  rate_geom g;
-  if (rate_make_geom(r->rate_in, r->rate_out, r->up, r->down, r->half, r->tpp, g, why, sizeof why))
-    return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: %s", why);
-  ww_stream_rate *rt = new ww_stream_rate();
-  ww_scoped<ww_stream_rate, rate_destroy_> own(rt);
-  rt->ctx = ctx; rt->r = r; rt->g = g; rt->S = S;
-  rt->n.assign((size_t)S, 0);
-  // (the frames start on a 16-byte boundary and end in whole 16-byte pieces: the kernel loads them as uint4)
-  const size_t b_hist = (size_t)S * g.hist * 4, b_out = (size_t)S * WW_RATE_FRAME_OUT * 2,
-               b_in = (size_t)S * sizeof(rate_ctl) + (((size_t)S * g.F * 2 + 15) & ~(size_t)15) + 16;
-  if (hipMalloc((void **)&rt->d_hist, b_hist) != hipSuccess || hipMalloc((void **)&rt->d_out, b_out) != hipSuccess ||
-      hipHostMalloc((void **)&rt->h_in, b_in) != hipSuccess)
-    return ww_fail(ctx, WW_ENOMEM, "cannot allocate the resampling state of %d streams at %d Hz", S, g.rate_in);
-  if (((uintptr_t)rt->d_out & 15) != 0) return ww_fail(ctx, WW_EINTERNAL, "the tick's sample block is not 16-byte aligned");
-  memset(rt->h_in, 0, b_in);
-  WW_HIP(ctx, hipHostGetDevicePointer((void **)&rt->h_in_dev, rt->h_in, 0));
-  WW_HIP(ctx, hipMemsetAsync(rt->d_hist, 0, b_hist, ctx->stream));
-  WW_HIP(ctx, hipMemsetAsync(rt->d_out, 0, b_out, ctx->stream));
-  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *out = own.release();
-  return WW_OK;
-}
-
-int ww_k_rate_frame_samples(const ww_stream_rate *rt) { return rt->g.F; }
-
-void ww_k_rate_reset(ww_stream_rate *rt, const int32_t *ids, int count) {
-  for (int i = 0; i < count; ++i) rt->n[(size_t)(ids ? ids[i] : i)] = 0;
-}
-
-int64_t ww_k_rate_advance(const ww_stream_rate *rt, int stream, int64_t k) { return rate_advance(rt->g, rt->n[(size_t)stream], k).count; }
-
-int ww_k_rate_tick(ww_stream_rate *rt, const int16_t *frames, const uint8_t *flags, const int32_t *ctl_dev, const int16_t **d_frames) {
-  ww_ctx *ctx = rt->ctx;
-  const rate_geom &g = rt->g;
-  const int S = rt->S;
-  rate_ctl *rc = (rate_ctl *)rt->h_in;
-  for (int s = 0; s < S; ++s) {
-    if (flags[s] & 2) continue;
-    const rate_step st = rate_advance(g, rt->n[(size_t)s], g.F);
-    rc[s] = {st.res, (int32_t)st.zeros, st.held, 0};
-    rt->n[(size_t)s] += g.F;
-  }
-  memcpy(rt->h_in + (size_t)S * sizeof(rate_ctl), frames, (size_t)S * g.F * 2);
-  rate_tick_args a = {};
-  a.rc = (const rate_ctl *)rt->h_in_dev;
-  a.frames = (const int16_t *)(rt->h_in_dev + (size_t)S * sizeof(rate_ctl));
-  a.ctl = ctl_dev;
-  a.taps = rt->r->d_taps;
-  a.hist = rt->d_hist;
-  a.out = rt->d_out;
-  a.up = (int)g.up; a.down = (int)g.down; a.half = (int)g.half; a.tpp = (int)g.tpp; a.F = g.F; a.D = g.D; a.H = g.hist;
-  {
-    ww_launch_scope scope(ctx, "stream_rate_tick_kernel");
-    hipLaunchKernelGGL(stream_rate_tick_kernel, dim3((unsigned)S), dim3(RATE_THREADS), (size_t)(g.hist + g.F + WW_RATE_PAD) * 4, ctx->stream, a);
-  }
-  WW_HIP(ctx, hipGetLastError());
-  *d_frames = rt->d_out;
-  return WW_OK;
-}
-
-// A feed's packets at the bank's rate -> its 16 kHz samples on the device: stream ids[i]'s lie at (*d_pcm16)[offs16[i] .. offs16[i + 1]),
-// offs16 as ww_k_rate_advance counts them.  *moved: the streams' sample counts have advanced (a failure behind that point leaves the
-// bank's host mirrors and its device state out of step).
-// (`pick`: the n_pick packets of the call that are this object's - a class of a mixed-rate bank, ww_k_rates_feed further down, which
-// has the call's packets on the device already, d_pk, and names the buffer the 16 kHz samples go to, d_dst, zeroed by then)
-static int rate_feed_run(ww_stream_rate *rt, const int32_t *ids, int n, const int32_t *pick, int n_pick, const int16_t *pcm, const int16_t *d_pk_all,
-                         const int64_t *sample_offs, const int64_t *offs16, int16_t *d_dst, const int16_t **d_pcm16, bool *moved) {
-  ww_ctx *ctx = rt->ctx;
-  const rate_geom &g = rt->g;
-  std::vector<rate_feed_str> str;
-  rs_plan pl;
-  int64_t seg_total = 0, k_max = 0;
-  const int64_t s0 = sample_offs[0], samples = sample_offs[n] - s0;
-  for (int j = 0; j < (pick ? n_pick : n); ++j) {
-    const int i = pick ? pick[j] : j;
-    const int64_t k = sample_offs[i + 1] - sample_offs[i];
-    if (k == 0) continue;
-    const int s = ids[i];
-    const rate_step st = rate_advance(g, rt->n[(size_t)s], k);
-    str.push_back({sample_offs[i] - s0, k, seg_total, s, st.held});
-    if (st.count > st.zeros) {
-      // the segment's first sample is input n - held of the stream; its outputs land behind the zeros of the stream's 16 kHz run
-      const int64_t so[2] = {seg_total, seg_total + st.held + k}, in_first[1] = {rt->n[(size_t)s] - st.held}, out_first[1] = {st.y0},
-                    oo[2] = {offs16[i] + st.zeros, offs16[i + 1]};
-      rs_make_plan(rt->r, so, in_first, out_first, oo, 1, pl);
-    }
-    seg_total += st.held + k;
-    k_max = std::max(k_max, st.held + k);
-  }
-  if (str.size() > 0x7fffffffu || pl.count() > 0x7fffffffu || (k_max + RATE_SPLICE - 1) / RATE_SPLICE > 65535)
-    return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: too much work for one call");
-  ww_tables tb;
-  tb.add(str);
-  const size_t b_tab = tb.bytes(), b_pk = d_pk_all ? 0 : ww_bump::need((size_t)samples, 2), b_seg = ww_bump::need((size_t)seg_total, 4),
-               b_z = d_dst ? 0 : ww_bump::need((size_t)offs16[n], 2), b_tiles = ww_bump::need(pl.count(), sizeof(rs_tile));
-  const size_t need = b_tab + b_pk + b_seg + b_z + b_tiles + 1024;
-  if (need > rt->scratch_cap) {
-    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (rt->d_scratch) WW_HIP(ctx, hipFree(rt->d_scratch));
-    rt->d_scratch = nullptr;
-    rt->scratch_cap = 0;
-    if (hipMalloc((void **)&rt->d_scratch, need) != hipSuccess)
-      return ww_fail(ctx, WW_ENOMEM, "ww_stream_feed: cannot allocate %zu bytes for the call's samples at %d Hz", need, g.rate_in);
-    rt->scratch_cap = need;
-  }
-  ww_bump db(rt->d_scratch, rt->scratch_cap);
-  rate_feed_str *d_str = (rate_feed_str *)db.take<char>(b_tab);
-  const int16_t *d_pk = d_pk_all ? d_pk_all : db.take<int16_t>((size_t)samples);
-  float *d_seg = db.take<float>((size_t)seg_total);
-  int16_t *d_z = d_dst ? d_dst : db.take<int16_t>((size_t)offs16[n]);
-  rs_tile *d_tiles = db.take<rs_tile>(pl.count());
-  *moved = true;
-  for (const rate_feed_str &d : str) rt->n[(size_t)d.sid] += d.k;
-  if (d_pcm16) *d_pcm16 = d_z;
-  if (str.empty()) return WW_OK;
-  if (int rc = tb.send(ctx, d_str)) return rc;
-  if (!d_pk_all) WW_HIP(ctx, hipMemcpyAsync((void *)d_pk, pcm + s0, (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
-  {
-    ww_launch_scope scope(ctx, "stream_rate_splice_kernel");
-    hipLaunchKernelGGL(stream_rate_splice_kernel, dim3((unsigned)str.size(), (unsigned)((k_max + RATE_SPLICE - 1) / RATE_SPLICE)), dim3(256),
-                       (size_t)g.hist * 4, ctx->stream, (const int16_t *)d_pk, (const rate_feed_str *)d_str, d_seg, rt->d_hist, (int)g.hist);
-  }
-  WW_HIP(ctx, hipGetLastError());
-  if (!d_dst && offs16[n] > 0) WW_HIP(ctx, hipMemsetAsync(d_z, 0, (size_t)offs16[n] * 2, ctx->stream));  // z's leading zeros
-  if (pl.count() > 0)
-    if (int rc = rs_run(rt->r, pl, d_tiles, d_seg, WW_SAMPLE_F32, d_z, WW_SAMPLE_I16)) return rc;
-  return WW_OK;
-}
-
-int ww_k_rate_feed(ww_stream_rate *rt, const int32_t *ids, int n, const int16_t *pcm, const int64_t *sample_offs, const int64_t *offs16,
-                   const int16_t **d_pcm16, bool *moved) {
-  return rate_feed_run(rt, ids, n, nullptr, 0, pcm, nullptr, sample_offs, offs16, nullptr, d_pcm16, moved);
-}
-
-// ---- a stream bank whose streams each run at their own rate (streams.hip: ww_stream_attach_rates) ------------------
-// Up to WW_STREAM_MAX_RATES rate classes, stream s in class cls[s]; the geometry and the bookkeeping are stream_rates.h's (host
-// only).  A resampling class IS the single-rate bank's state object above - its history rows [S][hist of the class], its counts, its
-// feed - of which a stream uses its own class's row only: a stream's bits are those of the single-rate bank of its class because
-// they are that bank's state, control words and arithmetic.  The 16 kHz class has no object: its samples pass through.
-// ONE kernel in front of a tick's own serves every class.  The tick's frames are one ragged int16 block (page-locked, stream s's
-// frame from sample desc[s].off); the per-stream descriptor {class, offset} is a DEVICE table (resent when a stream moves), so the
-// frame's first 320 16-byte pieces are requested before anything that crossed the bus is looked at, as in stream_rate_tick_kernel;
-// the class geometries travel as kernel arguments, picked by a wave-uniform index.  A stream that moves or is reset starts with
-// held = 0: whatever an earlier use left in the row reads as zero, no kernel clears it.
+// ---- stream banks at other rates than 16 kHz (streams.hip: ww_stream_attach_resampler, ww_stream_attach_rates) --
+// The bank's kernels are untouched: ONE kernel in front of a tick turns the S streams' frames, each at its stream's rate (F = rate /
+// 50 samples, page-locked), into the [S][320] int16 block the tick kernels read their samples from.  Up to WW_STREAM_MAX_RATES rate
+// classes, stream s in class cls[s]; the geometry and the bookkeeping are stream_rate.h's and stream_rates.h's (host only); the
+// arithmetic is this file's rule - rs_load, ONE chain per output over the class's own tap table, rs_store -, so a stream's 16 kHz
+// samples are the one-shot's bits behind D zeros.  The 16 kHz class has no resampler: its samples pass through.
+// ONE state object serves both kinds of bank.  A `uniform` bank (ww_stream_attach_resampler) is the bank of one resampling class
+// with every stream in it for good: its frames are [S][F], and no per-stream descriptor is sent or read.  A per-stream bank's
+// frames are one ragged block (stream s's frame from sample desc[s].off); the descriptor {class, offset} is a DEVICE table (resent
+// when a stream moves), so the frame's first 320 16-byte pieces are requested before anything that crossed the bus is looked at.
+// One workgroup per stream, one lane per output.  A stream's state is the last `hist` input samples of its class as fp32
+// (right-aligned; of a young stream only the last `held` are its own, what lies in front reads as zero - a reset or a move is the
+// host's count = 0, no kernel): read into LDS in front of the frame by the one workgroup that writes it back, no order between
+// workgroups.  The history rows are per class, [S][hist of the class], and a stream uses its current class's row only: whatever an
+// earlier use left in a row reads as zero behind held = 0, so a move clears nothing.
 struct ww_stream_rates {
   ww_ctx *ctx = nullptr;
   int S = 0;
+  bool uniform = false;  // made by ww_stream_attach_resampler (NOT: K happens to be 1 - a per-stream bank of one class may still be moved)
   rates_table tab;
-  ww_stream_rate *cls_rt[WW_STREAM_MAX_RATES] = {};  // nullptr: the 16 kHz class
-  std::vector<int32_t> cls;                          // [S] the stream's class
-  std::vector<rates_desc> desc;                      // [S] what d_desc was last sent
-  rates_desc *d_desc = nullptr;
-  int16_t *d_out = nullptr;  // [S][320]
-  char *h_in = nullptr, *h_in_dev = nullptr;  // page-locked [S] rate_ctl | the ragged frames (room for S frames of the longest class)
+  const ww_resampler *r[WW_STREAM_MAX_RATES] = {};  // the class's resampler, whose tap table the kernels borrow; nullptr: the 16 kHz class
+  float *d_hist[WW_STREAM_MAX_RATES] = {};          // [S][hist of the class]
+  std::vector<int32_t> cls;                         // [S] the stream's class
+  std::vector<int64_t> n;  // [S] input samples since the stream's last reset or move, frozen ticks left out (a 16 kHz stream's stays 0)
+  std::vector<rates_desc> desc;                     // [S] what d_desc was last sent
+  int64_t total = 0;                                // samples of a tick's frames
+  rates_desc *d_desc = nullptr;                     // (a uniform bank has none)
+  int16_t *d_out = nullptr;  // [S][320]: the tick's 16 kHz samples (640 bytes per stream: the tick kernels load them 16 at a time)
+  // the tick's page-locked input: [S] rate_ctl | the frames (room for S frames of the longest class).  ONE copy: the kernel that
+  // reads it precedes the tick's kernel on the stream, so it has ended when a polled tick's first tag arrives
+  char *h_in = nullptr, *h_in_dev = nullptr;
   size_t lds_bytes = 0;
   ww_resampler pass_r;        // the 16 kHz class of a feed: the identity form's tiles (resample_copy_kernel), no table
-  char *d_scratch = nullptr;  // a feed's [packets | the 16 kHz class's tiles], grown on demand
+  char *d_scratch = nullptr;  // a feed's [packets | per class present: splice table | segments | tiles], grown on demand
   size_t scratch_cap = 0;
   void layout() {
-    int64_t at = 0;
+    total = 0;
     for (int s = 0; s < S; ++s) {
-      desc[(size_t)s] = {at, cls[(size_t)s], 0};
-      at += tab.g[cls[(size_t)s]].F;
+      desc[(size_t)s] = {total, cls[(size_t)s], 0};
+      total += tab.g[cls[(size_t)s]].F;
     }
   }
   int send() {
@@ -667,28 +430,46 @@ struct ww_stream_rates {
   }
 };
 
-struct rates_class_dev {
+struct rate_class_dev {
   const float *taps;
   float *hist;  // [S][H]
   int up, down, half, tpp, F, D, H, pass;
 };
-struct rates_tick_args {
-  const int16_t *frames;    // page-locked, ragged, from a 16-byte boundary, padded to whole 16-byte pieces
-  const rate_ctl *rc;       // page-locked [S]
-  const int32_t *ctl;       // the tick's own control words [S][4] (page-locked): bit 1 of word 2 = the stream is frozen
-  const rates_desc *desc;   // device [S]
+template <int K>
+struct rate_tick_args {
+  const int16_t *frames;   // page-locked, from a 16-byte boundary, padded to whole 16-byte pieces
+  const rate_ctl *rc;      // page-locked [S]
+  const int32_t *ctl;      // the tick's own control words [S][4] (page-locked): bit 1 of word 2 = the stream is frozen
   int16_t *out;
-  rates_class_dev c[WW_STREAM_MAX_RATES];
+  rate_class_dev c[K];
+  const rates_desc *desc;  // device [S]; a uniform bank: not read (last, so that K = 1 loads its arguments as flat ones would be)
 };
 
-__global__ __launch_bounds__(RATE_THREADS) void stream_rates_tick_kernel(rates_tick_args a) {
+#define RATE_THREADS WW_RATE_FRAME_OUT
+
+// PerStream = false, a uniform bank: frame s lies at s * F and the one class's geometry is read from fixed argument slots - nothing
+// is loaded in front of the frame.  PerStream = true: the descriptor comes from the device table and picks the class's geometry
+// with a wave-uniform index (scalar loads of the arguments); the 16 kHz class copies its frame.
+template <bool PerStream>
+__global__ __launch_bounds__(RATE_THREADS) void stream_rate_tick_kernel(rate_tick_args<PerStream ? WW_STREAM_MAX_RATES : 1> a) {
   extern __shared__ float xs[];  // [H history | F frame | WW_RATE_PAD zeros] of the stream's class
   const int s = blockIdx.x, tid = threadIdx.x;
-  const rates_desc d = a.desc[s];
-  const rates_class_dev &g = a.c[__builtin_amdgcn_readfirstlane(d.cls) & (WW_STREAM_MAX_RATES - 1)];  // (scalar loads of the arguments)
+  const rate_class_dev *cp = &a.c[0];
+  size_t b0;  // the frame's first byte
+  if constexpr (PerStream) {
+    const rates_desc d = a.desc[s];
+    cp = &a.c[__builtin_amdgcn_readfirstlane(d.cls) & (WW_STREAM_MAX_RATES - 1)];
+    b0 = (size_t)d.off * 2;
+  } else {
+    b0 = (size_t)s * a.c[0].F * 2;
+  }
+  const rate_class_dev &g = *cp;
   const int F = g.F, H = g.H;
-  // the aligned 16-byte pieces that cover the frame's 2 F bytes, as in stream_rate_tick_kernel: a frame starts at any even byte
-  const size_t b0 = (size_t)d.off * 2, a0 = b0 & ~(size_t)15;
+  // The frame crosses the bus 16 bytes per lane, whatever F is: the aligned 16-byte pieces that cover its 2 F bytes (a frame starts
+  // at any even byte; the first and the last piece may hold a neighbour's samples, which are dropped; the block is padded to whole
+  // pieces).  The first RATE_THREADS pieces are requested BEFORE the control words are looked at - one trip over the bus instead of
+  // two in a row.
+  const size_t a0 = b0 & ~(size_t)15;
   const int n16 = (int)((b0 + (size_t)F * 2 - a0 + 15) >> 4), lead = (int)(b0 - a0) >> 1;
   const uint4 *src = (const uint4 *)((const char *)a.frames + a0);
   uint4 raw = make_uint4(0u, 0u, 0u, 0u);
@@ -696,15 +477,17 @@ __global__ __launch_bounds__(RATE_THREADS) void stream_rates_tick_kernel(rates_t
   const int flags = a.ctl[s * 4 + 2];
   const int4 cw = ((const int4 *)a.rc)[s];  // res, zeros, held
   if (flags & 2) return;  // frozen: the frame is dropped whole, history and output block stay
-  if (g.pass) {  // the 16 kHz class: the frame is the stream's row of the block (41 pieces at most: one per lane)
-    int16_t *o = a.out + (size_t)s * WW_RATE_FRAME_OUT;
-    const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+  if constexpr (PerStream) {
+    if (g.pass) {  // the 16 kHz class: the frame is the stream's row of the block (41 pieces at most: one per lane)
+      int16_t *o = a.out + (size_t)s * WW_RATE_FRAME_OUT;
+      const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int i = tid * 8 + e - lead;
-      if (tid < n16 && i >= 0 && i < WW_RATE_FRAME_OUT) o[i] = (int16_t)(w[e >> 1] >> ((e & 1) * 16));
+      for (int e = 0; e < 8; ++e) {
+        const int i = tid * 8 + e - lead;
+        if (tid < n16 && i >= 0 && i < WW_RATE_FRAME_OUT) o[i] = (int16_t)(w[e >> 1] >> ((e & 1) * 16));
+      }
+      return;
     }
-    return;
   }
   float *hist = g.hist + (size_t)s * H;
   auto put = [&](int q, const uint4 &v) {  // piece q: samples 8 q - lead .. 8 q - lead + 7 of the frame
@@ -728,9 +511,36 @@ __global__ __launch_bounds__(RATE_THREADS) void stream_rates_tick_kernel(rates_t
   for (int i = tid; i < H; i += RATE_THREADS) hist[i] = xs[F + i];  // (every read of the row went through LDS above)
 }
 
+// A feed's splice: stream d.sid's segment = [the `held` samples it holds | its packet of k] as fp32 for the resample kernels, and its
+// new history behind their reads.  Workgroup (i, c) copies samples [c * RATE_SPLICE, +RATE_SPLICE) of the segment; history rows
+// are shorter than that, so workgroup (i, 0) is the row's one reader, and it is its one writer.
+#define RATE_SPLICE 16384
+struct rate_feed_str {
+  int64_t pk_off;   // the packet's first sample in the call's packet buffer
+  int64_t k;        // its samples (> 0)
+  int64_t seg_off;  // the segment's first sample in the class's segment buffer
+  int32_t sid, held;
+};
+__global__ __launch_bounds__(256) void stream_rate_splice_kernel(const int16_t *pk, const rate_feed_str *str, float *seg, float *hist, int H) {
+  extern __shared__ float nh[];  // [H]
+  const rate_feed_str d = str[blockIdx.x];
+  float *h = hist + (size_t)d.sid * H;
+  const int64_t tot = d.held + d.k, v0 = (int64_t)blockIdx.y * RATE_SPLICE;
+  if (v0 >= tot) return;
+  auto sample = [&](int64_t v) -> float { return v < d.held ? h[H - d.held + v] : rs_load(pk[d.pk_off + (v - d.held)]); };
+  const int64_t v1 = v0 + RATE_SPLICE < tot ? v0 + RATE_SPLICE : tot;
+  for (int64_t v = v0 + threadIdx.x; v < v1; v += 256) seg[d.seg_off + v] = sample(v);
+  if (blockIdx.y) return;
+  const int keep = (int)(tot < H ? tot : H);
+  for (int i = threadIdx.x; i < keep; i += 256) nh[i] = sample(tot - keep + i);
+  __syncthreads();  // the row has been read
+  for (int i = threadIdx.x; i < keep; i += 256) h[H - keep + i] = nh[i];
+}
+
 void ww_k_rates_destroy(ww_stream_rates *rt) {
   if (!rt) return;
-  for (ww_stream_rate *c : rt->cls_rt) ww_k_rate_destroy(c);
+  for (float *h : rt->d_hist)
+    if (h) hipFree(h);
   if (rt->d_desc) hipFree(rt->d_desc);
   if (rt->d_out) hipFree(rt->d_out);
   if (rt->d_scratch) hipFree(rt->d_scratch);
@@ -743,46 +553,60 @@ static int rates_destroy_(ww_stream_rates *rt) {
   return WW_OK;
 }
 
-int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, const int32_t *stream_rate, int S, ww_stream_rates **out) {
+int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, const int32_t *stream_rate, int S, bool uniform,
+                      ww_stream_rates **out) {
   *out = nullptr;
   char why[320];
   ww_stream_rates *rt = new ww_stream_rates();
   ww_scoped<ww_stream_rates, rates_destroy_> own(rt);
-  rt->ctx = ctx; rt->S = S;
+  rt->ctx = ctx; rt->S = S; rt->uniform = uniform;
   rt->pass_r.ctx = ctx;
   rt->pass_r.identity = true;
   rt->pass_r.rate_in = rt->pass_r.rate_out = WW_RATE_OUT;
-  for (int k = 0; k < n_rates; ++k) {
-    const ww_resampler *r = rs[k];
-    if (r && r->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: class %d: the resampler belongs to another context", k);
-    if (r ? rates_add_class(rt->tab, false, r->rate_in, r->rate_out, r->up, r->down, r->half, r->tpp, why, sizeof why)
-          : rates_add_class(rt->tab, true, 0, 0, 0, 0, 0, 0, why, sizeof why))
-      return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %s", why);
+  if (uniform) {  // the one class on its own: rate_make_geom's refusals, no class named
+    const ww_resampler *r = rs[0];
+    if (r->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: the resampler belongs to another context");
+    if (rate_make_geom(r->rate_in, r->rate_out, r->up, r->down, r->half, r->tpp, rt->tab.g[0], why, sizeof why))
+      return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: %s", why);
+    rt->tab.K = 1;
+  } else {
+    for (int k = 0; k < n_rates; ++k) {
+      const ww_resampler *r = rs[k];
+      if (r && r->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: class %d: the resampler belongs to another context", k);
+      if (r ? rates_add_class(rt->tab, false, r->rate_in, r->rate_out, r->up, r->down, r->half, r->tpp, why, sizeof why)
+            : rates_add_class(rt->tab, true, 0, 0, 0, 0, 0, 0, why, sizeof why))
+        return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %s", why);
+    }
   }
   if (rates_check_ids(rt->tab, stream_rate, S, "stream_rate", why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %s", why);
   int64_t stage = 0;
   if (rates_stage(rt->tab, &stage, why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %s", why);
   rt->lds_bytes = (size_t)stage * 4;
-  for (int k = 0; k < n_rates; ++k)
-    if (rs[k])
-      if (int rc = ww_k_rate_create(ctx, rs[k], S, &rt->cls_rt[k])) return rc;
   if (stream_rate) rt->cls.assign(stream_rate, stream_rate + S);
   else rt->cls.assign((size_t)S, 0);
+  rt->n.assign((size_t)S, 0);
   rt->desc.resize((size_t)S);
   rt->layout();
-  ww_tables tb;
-  tb.add(rt->desc);
   // (the frames start on a 16-byte boundary and end in whole 16-byte pieces: the kernel loads them as uint4)
-  const size_t b_out = (size_t)S * WW_RATE_FRAME_OUT * 2,
+  const size_t b_desc = ww_bump::need((size_t)S, sizeof(rates_desc)), b_out = (size_t)S * WW_RATE_FRAME_OUT * 2,
                b_in = (size_t)S * sizeof(rate_ctl) + (((size_t)rates_layout_max(rt->tab, S) * 2 + 15) & ~(size_t)15) + 16;
-  if (hipMalloc((void **)&rt->d_desc, tb.bytes()) != hipSuccess || hipMalloc((void **)&rt->d_out, b_out) != hipSuccess ||
-      hipHostMalloc((void **)&rt->h_in, b_in) != hipSuccess)
-    return ww_fail(ctx, WW_ENOMEM, "cannot allocate the rate tables of %d streams in %d classes", S, n_rates);
+  bool ok = hipMalloc((void **)&rt->d_out, b_out) == hipSuccess && hipHostMalloc((void **)&rt->h_in, b_in) == hipSuccess &&
+            (uniform || hipMalloc((void **)&rt->d_desc, b_desc) == hipSuccess);
+  for (int k = 0; k < n_rates && ok; ++k) {
+    rt->r[k] = rs[k];
+    if (rs[k]) ok = hipMalloc((void **)&rt->d_hist[k], (size_t)S * rt->tab.g[k].hist * 4) == hipSuccess;
+  }
+  if (!ok)
+    return uniform ? ww_fail(ctx, WW_ENOMEM, "cannot allocate the resampling state of %d streams at %d Hz", S, rt->tab.g[0].rate_in)
+                   : ww_fail(ctx, WW_ENOMEM, "cannot allocate the rate tables of %d streams in %d classes", S, n_rates);
   if (((uintptr_t)rt->d_out & 15) != 0) return ww_fail(ctx, WW_EINTERNAL, "the tick's sample block is not 16-byte aligned");
   memset(rt->h_in, 0, b_in);
   WW_HIP(ctx, hipHostGetDevicePointer((void **)&rt->h_in_dev, rt->h_in, 0));
+  for (int k = 0; k < n_rates; ++k)
+    if (rs[k]) WW_HIP(ctx, hipMemsetAsync(rt->d_hist[k], 0, (size_t)S * rt->tab.g[k].hist * 4, ctx->stream));
   WW_HIP(ctx, hipMemsetAsync(rt->d_out, 0, b_out, ctx->stream));
-  if (int rc = rt->send()) return rc;
+  if (!uniform)
+    if (int rc = rt->send()) return rc;
   WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
   *out = own.release();
   return WW_OK;
@@ -790,22 +614,16 @@ int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, c
 
 int ww_k_rates_classes(const ww_stream_rates *rt) { return rt->tab.K; }
 
+int ww_k_rates_frame_samples(const ww_stream_rates *rt) { return rt->uniform ? rt->tab.g[0].F : 0; }
+
 void ww_k_rates_layout(const ww_stream_rates *rt, int32_t *frame_samples, int64_t *frame_offs) {
   rates_layout(rt->tab, rt->cls.data(), rt->S, frame_samples, frame_offs);
 }
 
-// the count a stream's class keeps for it (the 16 kHz class keeps none)
-static int64_t &rates_count(ww_stream_rates *rt, int s, int64_t &none) {
-  ww_stream_rate *c = rt->cls_rt[rt->cls[(size_t)s]];
-  none = 0;
-  return c ? c->n[(size_t)s] : none;
-}
-
 void ww_k_rates_reset(ww_stream_rates *rt, const int32_t *ids, int count) {
-  int64_t none;
   for (int i = 0; i < count; ++i) {
     const int s = ids ? ids[i] : i;
-    rates_move(rt->cls[(size_t)s], rates_count(rt, s, none), rt->cls[(size_t)s]);
+    rates_move(rt->cls[(size_t)s], rt->n[(size_t)s], rt->cls[(size_t)s]);  // the next sample is x[0] of a new signal: D zeros lead again
   }
 }
 
@@ -813,11 +631,9 @@ void ww_k_rates_reset(ww_stream_rates *rt, const int32_t *ids, int count) {
 // failure leaves the host's table as the device's was last sent; the caller marks the bank broken (the copy may have been enqueued).
 int ww_k_rates_move(ww_stream_rates *rt, const int32_t *ids, int count, int c) {
   const std::vector<int32_t> before = rt->cls;
-  int64_t none;
   for (int i = 0; i < count; ++i) {
     const int s = ids ? ids[i] : i;
-    rt->cls[(size_t)s] = c;
-    rates_move(rt->cls[(size_t)s], rates_count(rt, s, none), c);
+    rates_move(rt->cls[(size_t)s], rt->n[(size_t)s], c);
   }
   rt->layout();
   if (int rc = rt->send()) {
@@ -829,84 +645,133 @@ int ww_k_rates_move(ww_stream_rates *rt, const int32_t *ids, int count, int c) {
 }
 
 int64_t ww_k_rates_advance(const ww_stream_rates *rt, int stream, int64_t k) {
-  const int c = rt->cls[(size_t)stream];
-  return rates_advance(rt->tab, c, rt->cls_rt[c] ? rt->cls_rt[c]->n[(size_t)stream] : 0, k);
+  return rates_advance(rt->tab, rt->cls[(size_t)stream], rt->n[(size_t)stream], k);
+}
+
+template <int K>
+static void rates_tick_launch(const ww_stream_rates *rt, const int32_t *ctl_dev) {
+  rate_tick_args<K> a = {};
+  a.rc = (const rate_ctl *)rt->h_in_dev;
+  a.frames = (const int16_t *)(rt->h_in_dev + (size_t)rt->S * sizeof(rate_ctl));
+  a.ctl = ctl_dev;
+  a.desc = rt->d_desc;
+  a.out = rt->d_out;
+  for (int k = 0; k < K; ++k) {
+    const int j = k < rt->tab.K ? k : 0;  // (a slot above the bank's classes is never picked: a class id is below tab.K)
+    const rate_geom &g = rt->tab.g[j];
+    a.c[k] = {rt->r[j] ? rt->r[j]->d_taps : nullptr, rt->d_hist[j], (int)g.up, (int)g.down, (int)g.half, (int)g.tpp, g.F, g.D, g.hist, rt->tab.pass[j] ? 1 : 0};
+  }
+  ww_launch_scope scope(rt->ctx, K == 1 ? "stream_rate_tick_kernel" : "stream_rates_tick_kernel");
+  hipLaunchKernelGGL((stream_rate_tick_kernel<(K > 1)>), dim3((unsigned)rt->S), dim3(RATE_THREADS), rt->lds_bytes, rt->ctx->stream, a);
 }
 
 int ww_k_rates_tick(ww_stream_rates *rt, const int16_t *frames, const uint8_t *flags, const int32_t *ctl_dev, const int16_t **d_frames) {
   ww_ctx *ctx = rt->ctx;
   const int S = rt->S;
   rate_ctl *rc = (rate_ctl *)rt->h_in;
-  int64_t none;
   for (int s = 0; s < S; ++s) {
     if (flags[s] & 2) continue;
-    rc[s] = rates_tick(rt->tab, rt->cls[(size_t)s], rates_count(rt, s, none));
+    rc[s] = rates_tick(rt->tab, rt->cls[(size_t)s], rt->n[(size_t)s]);
   }
-  const int64_t total = rt->desc[(size_t)S - 1].off + rt->tab.g[rt->cls[(size_t)S - 1]].F;
-  memcpy(rt->h_in + (size_t)S * sizeof(rate_ctl), frames, (size_t)total * 2);
-  rates_tick_args a = {};
-  a.rc = (const rate_ctl *)rt->h_in_dev;
-  a.frames = (const int16_t *)(rt->h_in_dev + (size_t)S * sizeof(rate_ctl));
-  a.ctl = ctl_dev;
-  a.desc = rt->d_desc;
-  a.out = rt->d_out;
-  for (int k = 0; k < rt->tab.K; ++k) {
-    const rate_geom &g = rt->tab.g[k];
-    const ww_stream_rate *c = rt->cls_rt[k];
-    a.c[k] = {c ? c->r->d_taps : nullptr, c ? c->d_hist : nullptr, (int)g.up, (int)g.down, (int)g.half, (int)g.tpp, g.F, g.D, g.hist, c ? 0 : 1};
-  }
-  for (int k = rt->tab.K; k < WW_STREAM_MAX_RATES; ++k) a.c[k] = a.c[0];  // (never picked: a class id is below K)
-  {
-    ww_launch_scope scope(ctx, "stream_rates_tick_kernel");
-    hipLaunchKernelGGL(stream_rates_tick_kernel, dim3((unsigned)S), dim3(RATE_THREADS), rt->lds_bytes, ctx->stream, a);
-  }
+  memcpy(rt->h_in + (size_t)S * sizeof(rate_ctl), frames, (size_t)rt->total * 2);
+  if (rt->uniform) rates_tick_launch<1>(rt, ctl_dev);
+  else rates_tick_launch<WW_STREAM_MAX_RATES>(rt, ctl_dev);
   WW_HIP(ctx, hipGetLastError());
   *d_frames = rt->d_out;
   return WW_OK;
 }
 
 // A feed's packets, stream ids[i]'s at its own rate -> the call's 16 kHz samples at d_dst[offs16[i] .. offs16[i + 1]), offs16 as
-// ww_k_rates_advance counts them.  The packets go up once and are grouped by class (stream_rates.h): the 16 kHz class's go to their
-// place through the identity form's tiles, every other class's through the single-rate feed of that class with its subset of the
-// call - launches and copies per class present, whatever the number of streams.  *moved: as ww_k_rate_feed's.
+// ww_k_rates_advance counts them.  The packets go up once and are grouped by class (stream_rates.h; a uniform bank has one group
+// that holds every packet): the 16 kHz class's go to their place through the identity form's tiles, every other class's through
+// the splice and the class's own resample kernels - launches and copies per class present, whatever the number of streams.
+// Everything a refusal depends on is planned before any state moves.  *moved: sample counts have advanced (a failure behind that
+// point leaves the bank's host mirrors and its device state out of step).
+struct rate_feed_class {
+  std::vector<rate_feed_str> str;  // the splice's packets (a resampling class)
+  rs_plan pl;
+  int64_t seg_total = 0, k_max = 0;
+};
+
 int ww_k_rates_feed(ww_stream_rates *rt, const int32_t *ids, int n, const int16_t *pcm, const int64_t *sample_offs, const int64_t *offs16,
                     int16_t *d_dst, bool *moved) {
   ww_ctx *ctx = rt->ctx;
+  const int K = rt->tab.K;
   std::vector<int32_t> pc((size_t)n);
   for (int i = 0; i < n; ++i) pc[(size_t)i] = rt->cls[(size_t)ids[i]];
   rates_groups grp;
   rates_group(pc.data(), n, grp);
   const int64_t s0 = sample_offs[0], samples = sample_offs[n] - s0;
-  rs_plan pl;
-  for (int c = 0; c < rt->tab.K; ++c) {
-    if (rt->cls_rt[c]) continue;
+  rate_feed_class work[WW_STREAM_MAX_RATES];
+  size_t need = ww_bump::need((size_t)samples, 2) + 1024;
+  for (int c = 0; c < K; ++c) {
+    rate_feed_class &w = work[c];
     for (int j = grp.start[c]; j < grp.start[c + 1]; ++j) {
-      const int i = grp.order[(size_t)j];
-      const int64_t so[2] = {sample_offs[i] - s0, sample_offs[i + 1] - s0}, first[1] = {0}, oo[2] = {offs16[i], offs16[i + 1]};
-      rs_make_plan(&rt->pass_r, so, first, first, oo, 1, pl);
+      const int i = grp.order[(size_t)j], s = ids[i];
+      const int64_t k = sample_offs[i + 1] - sample_offs[i];
+      if (k == 0) continue;
+      if (!rt->r[c]) {
+        const int64_t so[2] = {sample_offs[i] - s0, sample_offs[i + 1] - s0}, first[1] = {0}, oo[2] = {offs16[i], offs16[i + 1]};
+        rs_make_plan(&rt->pass_r, so, first, first, oo, 1, w.pl);
+        continue;
+      }
+      const rate_step st = rate_advance(rt->tab.g[c], rt->n[(size_t)s], k);
+      w.str.push_back({sample_offs[i] - s0, k, w.seg_total, s, st.held});
+      if (st.count > st.zeros) {
+        // the segment's first sample is input n - held of the stream; its outputs land behind the zeros of the stream's 16 kHz run
+        const int64_t so[2] = {w.seg_total, w.seg_total + st.held + k}, in_first[1] = {rt->n[(size_t)s] - st.held}, out_first[1] = {st.y0},
+                      oo[2] = {offs16[i] + st.zeros, offs16[i + 1]};
+        rs_make_plan(rt->r[c], so, in_first, out_first, oo, 1, w.pl);
+      }
+      w.seg_total += st.held + k;
+      w.k_max = std::max(w.k_max, st.held + k);
     }
+    if (w.str.size() > 0x7fffffffu || w.pl.count() > 0x7fffffffu || (w.k_max + RATE_SPLICE - 1) / RATE_SPLICE > 65535)
+      return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: too much work for one call");
+    need += ww_bump::need(w.str.size(), sizeof(rate_feed_str)) + ww_bump::need((size_t)w.seg_total, 4) + ww_bump::need(w.pl.count(), sizeof(rs_tile));
   }
-  if (pl.count() > 0x7fffffffu) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: too much work for one call");
-  const size_t need = ww_bump::need((size_t)samples, 2) + ww_bump::need(pl.count(), sizeof(rs_tile)) + 1024;
   if (need > rt->scratch_cap) {
     WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (rt->d_scratch) WW_HIP(ctx, hipFree(rt->d_scratch));
     rt->d_scratch = nullptr;
     rt->scratch_cap = 0;
-    if (hipMalloc((void **)&rt->d_scratch, need) != hipSuccess) return ww_fail(ctx, WW_ENOMEM, "ww_stream_feed: cannot allocate %zu bytes for the call's samples", need);
+    if (hipMalloc((void **)&rt->d_scratch, need) != hipSuccess)
+      return rt->uniform ? ww_fail(ctx, WW_ENOMEM, "ww_stream_feed: cannot allocate %zu bytes for the call's samples at %d Hz", need, rt->tab.g[0].rate_in)
+                         : ww_fail(ctx, WW_ENOMEM, "ww_stream_feed: cannot allocate %zu bytes for the call's samples", need);
     rt->scratch_cap = need;
   }
   ww_bump db(rt->d_scratch, rt->scratch_cap);
   int16_t *d_pk = db.take<int16_t>((size_t)samples);
-  rs_tile *d_tiles = db.take<rs_tile>(pl.count());
   WW_HIP(ctx, hipMemcpyAsync(d_pk, pcm + s0, (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
   if (offs16[n] > 0) WW_HIP(ctx, hipMemsetAsync(d_dst, 0, (size_t)offs16[n] * 2, ctx->stream));  // z's leading zeros
-  if (pl.count() > 0)
-    if (int rc = rs_run(&rt->pass_r, pl, d_tiles, d_pk, WW_SAMPLE_I16, d_dst, WW_SAMPLE_I16)) return rc;
-  for (int c = 0; c < rt->tab.K; ++c)
-    if (rt->cls_rt[c] && grp.start[c + 1] > grp.start[c])
-      if (int rc = rate_feed_run(rt->cls_rt[c], ids, n, grp.order.data() + grp.start[c], grp.start[c + 1] - grp.start[c], pcm, d_pk, sample_offs, offs16,
-                                 d_dst, nullptr, moved))
-        return rc;
+  // (each class has its own region of the scratch: a class's table goes up now, its kernels run later on the stream)
+  for (int c = 0; c < K; ++c) {
+    const rate_feed_class &w = work[c];
+    if (grp.start[c + 1] == grp.start[c]) continue;
+    rate_feed_str *d_str = db.take<rate_feed_str>(w.str.size());
+    float *d_seg = db.take<float>((size_t)w.seg_total);
+    rs_tile *d_tiles = db.take<rs_tile>(w.pl.count());
+    if (!rt->r[c]) {
+      if (w.pl.count() > 0)
+        if (int rc = rs_run(&rt->pass_r, w.pl, d_tiles, d_pk, WW_SAMPLE_I16, d_dst, WW_SAMPLE_I16)) return rc;
+      continue;
+    }
+    *moved = true;
+    for (const rate_feed_str &d : w.str) rt->n[(size_t)d.sid] += d.k;
+    if (w.str.empty()) continue;
+    ww_tables tb;
+    tb.add(w.str);
+    if (int rc = tb.send(ctx, d_str)) return rc;
+    {
+      ww_launch_scope scope(ctx, "stream_rate_splice_kernel");
+      hipLaunchKernelGGL(stream_rate_splice_kernel, dim3((unsigned)w.str.size(), (unsigned)((w.k_max + RATE_SPLICE - 1) / RATE_SPLICE)), dim3(256),
+                         (size_t)rt->tab.g[c].hist * 4, ctx->stream, (const int16_t *)d_pk, (const rate_feed_str *)d_str, d_seg, rt->d_hist[c],
+                         (int)rt->tab.g[c].hist);
+    }
+    WW_HIP(ctx, hipGetLastError());
+    if (w.pl.count() > 0)
+      if (int rc = rs_run(rt->r[c], w.pl, d_tiles, d_seg, WW_SAMPLE_F32, d_dst, WW_SAMPLE_I16)) return rc;
+  }
   return WW_OK;
 }
+

@@ -99,12 +99,11 @@ struct ww_streams {
   std::vector<int32_t> stream_model;
   int32_t *d_stream_model = nullptr;  // [S]
   ww_set_ref set_ref;                 // {d_stream_model, nullptr, the set's stride}
-  // a bank at another rate than 16 kHz (ww_stream_attach_resampler): frames are [S][frame samples of that rate], and one kernel of
-  // resample.hip in front of a tick's own turns them into the [S][320] block the tick kernels read
-  ww_stream_rate *rate = nullptr;
-  // a bank whose streams each run at their own rate (ww_stream_attach_rates): frames are one ragged block, stream s's frame at its
-  // own rate, and ONE kernel of resample.hip in front of a tick's own serves every rate
+  // a bank at other rates than 16 kHz: ONE kernel of resample.hip in front of a tick's own turns the frames into the [S][320] block
+  // the tick kernels read.  ww_stream_attach_resampler: frames are [S][frame samples of that rate] (a uniform bank);
+  // ww_stream_attach_rates: one ragged block, stream s's frame at its own rate
   ww_stream_rates *rates = nullptr;
+  int uniform_frame() const { return rates ? ww_k_rates_frame_samples(rates) : 0; }  // a uniform bank's frame samples; 0: not one
   bool used = false;                  // ticked or fed since creation
   // the kernels' extra argument: nullptr for a bank of one model
   const ww_set_ref *ref() const { return set ? &set_ref : nullptr; }
@@ -345,7 +344,6 @@ int ww_stream_destroy(ww_streams *st) {
   void *host[] = {st->h_pack, st->h_out, st->h_tag};
   for (void *p : host)
     if (p) hipHostFree(p);
-  ww_k_rate_destroy(st->rate);
   ww_k_rates_destroy(st->rates);
   delete st;
   return WW_OK;
@@ -518,18 +516,19 @@ int ww_stream_create_set(ww_ctx *ctx, const ww_model_set *set, int32_t S, const 
 }
 
 // The bank becomes one at the resampler's input rate (include/wwhip.h).  The refusals that depend on the rates and the state object
-// are ww_k_rate_create's (resample.hip; stream_rate.h); no kernel of the bank changes, a tick only reads its samples elsewhere.
+// are ww_k_rates_create's (resample.hip; stream_rate.h): the bank of ONE resampling class with every stream in it for good (a uniform
+// bank); no kernel of the bank changes, a tick only reads its samples elsewhere.
 int ww_stream_attach_resampler(ww_streams *st, const ww_resampler *r) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
   ww_ctx *ctx = st->ctx;
   if (!r) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: NULL resampler");
   if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
-  if (st->rate) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: this bank already has a resampler (%d Hz frames)", ww_k_rate_frame_samples(st->rate) * 50);
+  if (st->uniform_frame()) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: this bank already has a resampler (%d Hz frames)", st->uniform_frame() * 50);
   if (st->rates) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: this bank already has per-stream rates (ww_stream_attach_rates)");
   if (st->used) return ww_fail(ctx, WW_ESTATE, "ww_stream_attach_resampler: the bank has ticked or been fed: a resampler is attached to a new bank");
   WW_ON_DEVICE(ctx, dev_scope);
-  return ww_k_rate_create(ctx, r, st->S, &st->rate);
+  return ww_k_rates_create(ctx, &r, 1, nullptr, st->S, true, &st->rates);
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
@@ -543,11 +542,11 @@ int ww_stream_attach_rates(ww_streams *st, const ww_resampler *const *rs, int32_
   if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
   if (n_rates < 1 || n_rates > WW_STREAM_MAX_RATES)
     return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %d rate classes: a bank has 1..%d", (int)n_rates, WW_STREAM_MAX_RATES);
-  if (st->rate) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: this bank already has a resampler (%d Hz frames)", ww_k_rate_frame_samples(st->rate) * 50);
+  if (st->uniform_frame()) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: this bank already has a resampler (%d Hz frames)", st->uniform_frame() * 50);
   if (st->rates) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: this bank already has its rates (%d classes)", ww_k_rates_classes(st->rates));
   if (st->used) return ww_fail(ctx, WW_ESTATE, "ww_stream_attach_rates: the bank has ticked or been fed: rates are attached to a new bank");
   WW_ON_DEVICE(ctx, dev_scope);
-  return ww_k_rates_create(ctx, rs, n_rates, stream_rate, st->S, &st->rates);
+  return ww_k_rates_create(ctx, rs, n_rates, stream_rate, st->S, false, &st->rates);
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
@@ -559,10 +558,9 @@ int ww_stream_frame_layout(const ww_streams *st, int32_t *frame_samples, int64_t
     ww_k_rates_layout(st->rates, frame_samples, frame_offs);
     return WW_OK;
   }
-  const int F = st->rate ? ww_k_rate_frame_samples(st->rate) : WW_CHUNK;
   for (int s = 0; s <= st->S; ++s) {
-    if (s < st->S) frame_samples[s] = F;
-    frame_offs[s] = (int64_t)s * F;
+    if (s < st->S) frame_samples[s] = WW_CHUNK;
+    frame_offs[s] = (int64_t)s * WW_CHUNK;
   }
   return WW_OK;
   WW_GUARD_END(st ? st->ctx : nullptr)
@@ -574,7 +572,7 @@ int ww_stream_set_rate(ww_streams *st, const int32_t *ids, int32_t n, int32_t ra
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
   ww_ctx *ctx = st->ctx;
-  if (!st->rates) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_rate: this bank has no per-stream rates (ww_stream_attach_rates)");
+  if (!st->rates || st->uniform_frame()) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_rate: this bank has no per-stream rates (ww_stream_attach_rates)");
   if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
   const int K = ww_k_rates_classes(st->rates);
   if (rate_class < 0 || rate_class >= K) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_rate: class %d: the bank has rate classes 0..%d", (int)rate_class, K - 1);
@@ -599,8 +597,9 @@ int ww_stream_frame_samples(const ww_streams *st, int32_t *out) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
   if (!out) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_samples: NULL argument");
-  if (st->rates) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_samples: the streams of this bank have frames of their own: ww_stream_frame_layout");
-  *out = st->rate ? ww_k_rate_frame_samples(st->rate) : WW_CHUNK;
+  if (st->rates && !st->uniform_frame())
+    return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_samples: the streams of this bank have frames of their own: ww_stream_frame_layout");
+  *out = st->rates ? st->uniform_frame() : WW_CHUNK;
   return WW_OK;
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
@@ -669,8 +668,7 @@ int ww_stream_reset(ww_streams *st, const int32_t *ids, int32_t n) {
     st->pos[s] = 0;
     st->rowq[s] = 0;
   }
-  if (st->rate) ww_k_rate_reset(st->rate, ids, count);  // the next sample is x[0] of a new signal: D zeros lead again
-  if (st->rates) ww_k_rates_reset(st->rates, ids, count);
+  if (st->rates) ww_k_rates_reset(st->rates, ids, count);  // the next sample is x[0] of a new signal: D zeros lead again
   return WW_OK;
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
@@ -797,11 +795,9 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     st->rowq[s] = (st->rowq[s] + np) % WW_STREAM_GXC;
   }
   tl[1] = st_now_ns();
-  // a bank at another rate: its frames go through ww_k_rate_tick's kernel into a device block, and the tick reads that
+  // a bank at other rates: its frames go through ww_k_rates_tick's kernel into a device block, and the tick reads that
   const int16_t *rate_frames = nullptr;
-  if (st->rate) {
-    if (int rc = ww_k_rate_tick(st->rate, frames, is_speech, (const int32_t *)(st->h_pack_dev + ((char *)h_ctl - st->h_pack)), &rate_frames)) return rc;
-  } else if (st->rates) {
+  if (st->rates) {
     if (int rc = ww_k_rates_tick(st->rates, frames, is_speech, (const int32_t *)(st->h_pack_dev + ((char *)h_ctl - st->h_pack)), &rate_frames)) return rc;
   } else {
     memcpy(h_frames, frames, (size_t)S * WW_CHUNK * 2);
@@ -931,7 +927,7 @@ int ww_stream_step(ww_streams *st, const int16_t *frames, const uint8_t *is_spee
 // ---- ww_stream_feed: a causal bank advanced by any subset of its streams and any number of samples for each --------------------
 // The framing is the tick's rule for k samples instead of 320: tot = fill + k, rows = tot >= 512 ? (tot - 512) / 160 + 1 : 0,
 // fill' = tot - 160 rows.  Everything a refusal can depend on is looked at here, before any state moves.
-// A bank at another rate: k is what the packet's samples come to at 16 kHz (ww_k_rate_advance), and offs16 (n + 1 entries, from 0)
+// A bank at other rates: k is what the packet's samples come to at 16 kHz (ww_k_rates_advance), and offs16 (n + 1 entries, from 0)
 // receives the sample_offs the rest of the feed then works with.
 static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs, const char *what,
                       std::vector<int64_t> *offs16 = nullptr) {
@@ -951,7 +947,6 @@ static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64
     seen[s] = 1;
     int64_t k = sample_offs[i + 1] - sample_offs[i];
     if (k < 0) return ww_fail(ctx, WW_EINVAL, "%s: sample_offs descend at entry %d", what, i);
-    if (st->rate) k = ww_k_rate_advance(st->rate, s, k);
     if (st->rates) k = ww_k_rates_advance(st->rates, s, k);
     if (offs16) (*offs16)[(size_t)i + 1] = (*offs16)[(size_t)i] + k;
     const int64_t r = ww_fe_frames(st->fill[s] + k, st->fp.hop);
@@ -981,9 +976,9 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
   if (rows > 0 && !post) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: NULL posterior buffer");
   if (samples_in == 0) return WW_OK;  // nothing arrived: no stream moves
   st->used = true;
-  // a bank at another rate: from here on the packets are their 16 kHz samples, which ww_k_rate_feed leaves on the device
+  // a bank at other rates: from here on the packets are their 16 kHz samples, which ww_k_rates_feed leaves on the device
   const int64_t *in_offs = sample_offs;
-  if (st->rate || st->rates) sample_offs = offs16.data();
+  if (st->rates) sample_offs = offs16.data();
   const int64_t samples = sample_offs[n] - sample_offs[0];
   const ww_model *m = st->model;
   const int T = st->T, F = st->F, NO = st->NO, R = T + 1, hop = st->fp.hop, rf = ww_wave_receptive_field(m);
@@ -1013,17 +1008,9 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
   float *d_z = large.empty() ? nullptr : db.take<float>((size_t)rows * NO);
   float *d_post = db.take<float>((size_t)rows);
   if (int rc = tb.send(ctx, d_tab)) return rc;
-  const int16_t *rate_pcm = nullptr;
-  if (st->rate) {
-    if (int rc = ww_k_rate_feed(st->rate, ids, n, pcm, in_offs, sample_offs, &rate_pcm, mutated)) return rc;
-    if (samples == 0) {  // the packets moved the streams' resampling state and completed no 16 kHz sample
-      WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      return WW_OK;
-    }
-  }
-  if (st->rates) {  // (a mixed-rate bank's 16 kHz samples land in d_pcm itself)
+  if (st->rates) {  // (the bank's 16 kHz samples land in d_pcm itself)
     if (int rc = ww_k_rates_feed(st->rates, ids, n, pcm, in_offs, sample_offs, d_pcm, mutated)) return rc;
-    if (samples == 0) {
+    if (samples == 0) {  // the packets moved the streams' resampling state and completed no 16 kHz sample
       WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
       return WW_OK;
     }
@@ -1036,11 +1023,7 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
     st->fill[s] = (int)(st->fill[s] + k - r * hop);
     st->pos[s] = (int)((st->pos[s] + r) % R);
   }
-  if (rate_pcm) {
-    if (samples > 0) WW_HIP(ctx, hipMemcpyAsync(d_pcm, rate_pcm, (size_t)samples * 2, hipMemcpyDeviceToDevice, ctx->stream));
-  } else if (!st->rates) {
-    WW_HIP(ctx, hipMemcpyAsync(d_pcm, pcm + sample_offs[0], (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
-  }
+  if (!st->rates) WW_HIP(ctx, hipMemcpyAsync(d_pcm, pcm + sample_offs[0], (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
   feed_fe_args a = {};
   a.pcm = d_pcm; a.str = d_str; a.grp = d_grp; a.rows = d_rows;
   a.ring = st->ring; a.hist = st->hist; a.prev = st->prev;
