@@ -205,6 +205,40 @@ static void check_crnn() {
   CHECK(crnn_plan_group(rneg, fit, 1, 2, C_T, C_PT, C_OT, C_ST, 1000, 0, gp) == WW_EINVAL && !strcmp(gp.err, "sequence 0: windows leave the mel buffer"));
 }
 
+// ---- a segments call's descriptors: the whole-call walk and the explicit row list -------------------------------------------------
+static void check_seg_walk() {
+  const int hop = 2;
+  const int64_t r0[3] = {7, 1000, 400};
+  const int32_t nw[3] = {3, 0, 2};
+  const int64_t mel_rows = 400 + (2 - 1) * hop + C_T;  // sequence 2's last window ends on the buffer's last row
+  char err[WW_SEG_ERR];
+  int64_t W = -1;
+  CHECK(seg_walk(r0, nw, 3, hop, C_T, mel_rows, &W, err) == WW_OK && W == 5);  // (an empty sequence's row0 is never looked at)
+  std::vector<int64_t> rows(1, -5), want(1, -5);  // appended: what the list held stays
+  for (int s = 0; s < 3; ++s)
+    for (int k = 0; k < nw[s]; ++k) want.push_back(r0[s] + (int64_t)k * hop);
+  seg_rows(r0, nw, 3, hop, rows);
+  CHECK(rows == want && (int64_t)rows.size() == 1 + W);
+  // every fault: the walk's status and text, and crnn_plan_group's for the same call
+  crnn_seg_group gp;
+  auto refused = [&](const int64_t *row0, const int32_t *cnt, int64_t rows_in_buffer, const char *text) {
+    memset(err, 0x55, sizeof err);
+    CHECK(seg_walk(row0, cnt, 3, hop, C_T, rows_in_buffer, &W, err) == WW_EINVAL && !strcmp(err, text));
+    CHECK(crnn_plan_group(row0, cnt, 3, hop, C_T, C_PT, C_OT, C_ST, rows_in_buffer, 0, gp) == WW_EINVAL && !strcmp(gp.err, text));
+  };
+  const int32_t neg[3] = {3, -1, 2};
+  refused(r0, neg, mel_rows, "negative window count in sequence 1");
+  refused(r0, nw, mel_rows - 1, "sequence 2: windows leave the mel buffer");  // its last window one row past the buffer
+  const int64_t rneg[3] = {-1, 1000, 400};
+  refused(rneg, nw, mel_rows, "sequence 0: windows leave the mel buffer");
+  // no sequence: no window, no pointer read, nothing appended
+  W = -1;
+  rows.clear();
+  CHECK(seg_walk(nullptr, nullptr, 0, hop, C_T, 0, &W, err) == WW_OK && W == 0);
+  seg_rows(nullptr, nullptr, 0, hop, rows);
+  CHECK(rows.empty());
+}
+
 // ---- the Wavenet's cuts ------------------------------------------------------------------------------------------------------------
 static void check_wave() {
   for (int it = 0; it < 400; ++it) {
@@ -415,6 +449,7 @@ static void check_resample() {
 int main() {
   check_tables();
   check_crnn();
+  check_seg_walk();
   check_wave();
   check_feed();
   check_resample();

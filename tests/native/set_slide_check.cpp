@@ -93,7 +93,7 @@ static void check_case(const std::vector<int32_t> &nws, int hop, int64_t first_r
   one_owner(ref);
   for (int64_t budget : {(int64_t)40, (int64_t)48, (int64_t)WW_SEG_GROUP})
     for (int n_members : {1, 2, 3}) {
-      const int64_t cap = std::max<int64_t>(budget / n_members, 1);  // ww_k_crnn_set_segments_forward's
+      const int64_t cap = std::max<int64_t>(budget / n_members, 1);  // ww_k_crnn_segments_forward's for a set's call
       const flat_plan f = plan_all(row0, nws, hop, mel_rows, cap, n_members, budget);
       CHECK(f.nI == ref.nI && f.nW == ref.nW && f.tiles.size() == ref.tiles.size() && f.i0 == ref.i0);
       for (size_t i = 0; i < f.tiles.size(); ++i) CHECK(same_tile(f.tiles[i], ref.tiles[i]));

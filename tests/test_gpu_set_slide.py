@@ -324,6 +324,65 @@ def test_refusals(crnn_set, engines):
         other.close()
 
 
+def _engine_segments_rc(e, d_mel, mel_rows, row0, seg_nw, hop, out):
+    """``ww_forward_segments_dev`` by its status, a context synchronise behind it."""
+    from wwhip import _lib
+    r0, nw = np.ascontiguousarray(row0, np.int64), np.ascontiguousarray(seg_nw, np.int32)
+    rc = _lib.load().ww_forward_segments_dev(e.ctx.handle, e.handle, C.c_void_p(d_mel.data_ptr()), mel_rows, _lib.ptr(r0), _lib.ptr(nw), len(nw), hop,
+                                             C.c_void_p(out.data_ptr()))
+    e.ctx.synchronize()
+    return rc
+
+
+@pytest.mark.parametrize("name", [CRNNS[0], WAVES[0]])
+def test_single_model_refusals(engines, name):
+    """``ww_forward_segments_dev`` of one model (the CRNN's rows form, the Wavenet's explicit-window list) on test_refusals' sequences
+    [3, 0, 70] at hop 2: a negative seg_nw, windows that leave the mel buffer and a negative seg_row0 are WW_EINVAL, name their
+    sequence in ``ww_last_error`` and leave d_out all -7; a valid call afterwards has the bits of the one before them."""
+    import torch
+    from wwhip import _lib
+    e = engines[name]
+    T = e.window
+    mel, row0, seg_nw = _segments_buffer(51, [3, 0, 70], 2, T)
+    d_mel = torch.from_numpy(mel).cuda()
+    before = _engine_segments(e, d_mel, len(mel), row0, seg_nw, 2)
+    assert np.isfinite(before).all() and (before != -7.0).all()
+    out = torch.full((int(seg_nw.sum()) + 1, e.n_out), -7.0, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    for word, kw in (("sequence 1", {"seg_nw": [3, -1, 70]}),
+                     ("sequence 2", {"mel_rows": int(row0[2]) + 69 * 2 + T - 1}),  # one row short of the last window's last row
+                     ("sequence 0", {"row0": [-1, 0, int(row0[2])]})):
+        rc = _engine_segments_rc(e, d_mel, kw.get("mel_rows", len(mel)), kw.get("row0", row0), kw.get("seg_nw", seg_nw), 2, out)
+        text = _lib.load().ww_last_error(e.ctx.handle).decode()
+        assert rc == _lib.WW_EINVAL and word in text, (rc, text)
+        assert (out.cpu().numpy() == -7.0).all(), text
+    np.testing.assert_array_equal(_engine_segments(e, d_mel, len(mel), row0, seg_nw, 2), before)
+
+
+def test_refusal_above_a_group_enqueues_nothing(engines):
+    """The CRNN's rows form over three sequences of 16,385 windows at hop 2 (tests/test_gpu_launch_tables.py's: any two exceed a group
+    of 32,768 windows, so the call is three groups), the third moved one row down so that its last window ends one row past the
+    mel buffer: WW_EINVAL naming sequence 2, and none of the 3 x 16,385 rows of d_out written - the first two groups are not
+    launched either."""
+    import torch
+    from wwhip import _lib
+    e = engines[CRNNS[0]]
+    T, hop, nw = e.window, 2, 16385
+    span = (nw - 1) * hop + T
+    row0 = np.array([1, 1 + span + 3, 1 + span + 3 + span], np.int64)
+    rows = int(row0[2]) + span
+    mel = np.random.default_rng(78).uniform(0, 6.5, (rows, 40)).astype(np.float32)
+    assert mel.nbytes < 17 << 20
+    d_mel = torch.from_numpy(mel).cuda()
+    out = torch.full((3 * nw, e.n_out), -7.0, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    row0[2] += 1
+    rc = _engine_segments_rc(e, d_mel, rows, row0, [nw] * 3, hop, out)
+    text = _lib.load().ww_last_error(e.ctx.handle).decode()
+    assert rc == _lib.WW_EINVAL and "sequence 2" in text, (rc, text)
+    assert (out.cpu().numpy() == -7.0).all()
+
+
 def _clips():
     """12 seeded synthetic clips of 0.02 to 1.2 s: one under 512 samples (no frame of its own), one shorter than either model's
     window after the 2 x 0.5 s of padding (no sliding window), mixed labels."""
@@ -335,15 +394,20 @@ def _clips():
     return clips, labels
 
 
-@pytest.mark.parametrize("kind", ["crnn", "wavenet"])
+@pytest.mark.parametrize("kind", ["crnn", "wavenet", "crnn_alone"])
 def test_evaluator(crnn_set, wave_set, engines, kind):
     """``evaluate_testset_set(ms, clips, labels)[k]`` is ``evaluate_testset(Engine k, clips, labels)``: every array with
-    assert_array_equal, every scalar with ==."""
+    assert_array_equal, every scalar with == - for the three CRNNs, the two Wavenets and a set of a single CRNN member."""
+    from wwhip.engine import ModelSet
     from wwhip.evaluate import evaluate_testset, evaluate_testset_set
-    ms, names = (crnn_set, CRNNS) if kind == "crnn" else (wave_set, WAVES)
+    ms, names = {"crnn": (crnn_set, CRNNS), "wavenet": (wave_set, WAVES)}.get(kind) or (ModelSet([engines[CRNNS[0]]]), CRNNS[:1])
     clips, labels = _clips()
     assert min(len(c) for c in clips) < 512 and len(clips) == 12 and 0 < sum(labels) < 12
-    got = evaluate_testset_set(ms, clips, labels)
+    try:
+        got = evaluate_testset_set(ms, clips, labels)
+    finally:
+        if kind == "crnn_alone":
+            ms.close()
     assert len(got) == len(names)
     for k, name in enumerate(names):
         want = evaluate_testset(engines[name], clips, labels)

@@ -1,10 +1,9 @@
 #!/usr/bin/env python3
 """Development: what a model set (wwhip.ModelSet) costs and buys - the figures of profiles/model_set/measured.txt.
 
-  model_set.py codeobj A.so B.so   no GPU: per kernel of crnn_fused_kernel / crnn_stream_kernel / crnn_rows_kernel / gru_tail_kernel /
-                                   gru_tail16_kernel / wavenet_kernel / wavenet_seq_kernel the registers, LDS, scratch and instruction
-                                   count in both libraries, and whether the instruction streams are the same text (addresses and
-                                   symbol offsets aside)
+  model_set.py codeobj A.so B.so   no GPU: per instantiation of every kernel of the library (KERNELS) the registers, LDS, scratch and
+                                   instruction count in both libraries, and whether the instruction streams are the same text
+                                   (addresses and symbol offsets aside)
   model_set.py tick [ticks=3000]   128-stream CRNN tick, p50 / p90 us: one model | a set of three dealt round-robin | three banks of
                                    128 ticked one after the other; run it under WWHIP_LIB=<other build> for the other side
   model_set.py tick_wave [ticks=3000]  the fp32 Wavenet's 128-stream window tick: one model against a set of two, one launch and two
@@ -20,7 +19,14 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "wakeword-detection_amd")]
 ASSETS = os.path.join(ROOT, "wakeword-detection_amd/assets/tf_lite_models")
 CRNNS = ["CRNN_nosilence", "CRNN_nosilence_enhanced", "CRNN_softmax"]
 KERNELS = ("crnn_fused_kernel", "crnn_stream_kernel", "crnn_rows_kernel", "gru_tail_kernel", "gru_tail16_kernel", "wavenet_kernel",
-           "wavenet_seq_kernel")
+           "wavenet_seq_kernel",
+           # the rest of the library: the kernels a model set does not reach
+           "crnn_fused_bf16_kernel", "gemm_nt_kernel", "crnn_detect_kernel", "conv_generic_kernel", "gru_generic_kernel",
+           "wave_feed_pool_kernel", "wave_feed_ring_kernel", "wave_pool_step_kernel", "wave_pool_final_kernel", "wave_seq_post_kernel",
+           "iota_offs_kernel", "logmel_kernel", "logmel_rows_kernel", "stft_mag_kernel", "mel_only_kernel", "smooth_kernel", "sweep_kernel",
+           "pick_kernel", "viterbi2_kernel", "stream_frontend_kernel", "stream_feed_frontend_kernel", "stream_causal_reset_kernel",
+           "stream_reset_kernel", "resample_copy_kernel", "resample_decim_kernel", "resample_phase_kernel", "stream_rate_tick_kernel",
+           "stream_rate_splice_kernel")
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 

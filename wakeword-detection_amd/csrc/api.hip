@@ -638,15 +638,15 @@ static size_t model_ws(const ww_model *m, int nw) {
 }
 
 // ws: model scratch inside the context's device arena (ww_ensure'd by the caller for model_ws(m, nw) or more): its capacity is
-// what is left of the arena behind it
+// what is left of the arena behind it.  set: a model set's explicit windows (m: the set's view, window w by member set->ids[w])
 static int model_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_row,
                          const int32_t *d_valid, int64_t row0, int hop, int valid_const, int nw, void *ws, float *d_out,
-                         float *d_enc) {
+                         float *d_enc, const ww_set_ref *set = nullptr) {
   const char *lo = (const char *)ctx->dev.ptr, *p = (const char *)ws;
   const size_t cap = (p >= lo && p <= lo + ctx->dev.cap) ? (size_t)(lo + ctx->dev.cap - p) : 0;
   return m->kind == WW_KIND_CRNN
-             ? ww_k_crnn_forward(ctx, m, d_mel, mel_rows, d_row, d_valid, row0, hop, valid_const, nw, ws, cap, d_out, d_enc)
-             : ww_k_wave_forward(ctx, m, d_mel, mel_rows, d_row, d_valid, row0, hop, valid_const, nw, ws, cap, d_out, d_enc);
+             ? ww_k_crnn_forward(ctx, m, d_mel, mel_rows, d_row, d_valid, row0, hop, valid_const, nw, ws, cap, d_out, d_enc, nullptr, set)
+             : ww_k_wave_forward(ctx, m, d_mel, mel_rows, d_row, d_valid, row0, hop, valid_const, nw, ws, cap, d_out, d_enc, nullptr, set);
 }
 
 // windows are processed in chunks so that the workspace stays bounded
@@ -781,8 +781,7 @@ int ww_set_forward_windows_dev(ww_ctx *ctx, const ww_model_set *set, const float
   ww_set_ref ref;
   ref.ids = (const int32_t *)(d_tab + o_ids);
   ref.stride = (long long)set->stride;
-  if (m->kind == WW_KIND_CRNN) return ww_k_crnn_set_forward(ctx, m, ref, d_mel, mel_rows, d_win_row, d_win_valid, nw, d_out, d_enc);
-  return ww_k_wave_forward(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, 0, nw, ws, b_ws, d_out, d_enc, nullptr, &ref);
+  return model_forward(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, 0, nw, ws, d_out, d_enc, &ref);
   WW_GUARD_END(ctx)
 }
 
@@ -795,19 +794,17 @@ int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, 
   if (n_seg == 0) return WW_OK;
   if (!seg_row0 || !seg_nw) return ww_fail(ctx, WW_EINVAL, "sequence descriptors are NULL");
   WW_ON_DEVICE(ctx, dev);
+  // a bad descriptor is refused before anything is enqueued, whichever form the call takes
+  const int T = m->info.window;
+  int64_t nw;
+  char why[WW_SEG_ERR];
+  if (int rc = seg_walk(seg_row0, seg_nw, n_seg, hop, T, mel_rows, &nw, why)) return ww_fail(ctx, rc, "%s", why);
   if (ww_crnn_segments_capable(m, hop)) return ww_k_crnn_segments_forward(ctx, m, d_mel, mel_rows, seg_row0, seg_nw, n_seg, hop, d_out);
   // every other model / mode: the same windows as an explicit list through the per-window kernels
-  const int T = m->info.window;
-  std::vector<int64_t> rows;
-  for (int s = 0; s < n_seg; ++s) {
-    if (seg_nw[s] < 0) return ww_fail(ctx, WW_EINVAL, "negative window count in sequence %d", s);
-    if (seg_nw[s] && (seg_row0[s] < 0 || seg_row0[s] + (int64_t)(seg_nw[s] - 1) * hop + T > mel_rows))
-      return ww_fail(ctx, WW_EINVAL, "sequence %d: windows leave the mel buffer", s);
-    for (int k = 0; k < seg_nw[s]; ++k) rows.push_back(seg_row0[s] + (int64_t)k * hop);
-  }
-  const int64_t nw = (int64_t)rows.size();
   if (nw == 0) return WW_OK;
   if (nw > 0x7fffffff) return ww_fail(ctx, WW_EINVAL, "too many windows in one call");
+  std::vector<int64_t> rows;
+  seg_rows(seg_row0, seg_nw, n_seg, hop, rows);
   std::vector<int32_t> valid((size_t)nw, T);
   ww_tables tb;
   const size_t o_rows = tb.add(rows), o_valid = tb.add(valid), b_ws = model_ws(m, chunk_of(nw));
@@ -842,15 +839,9 @@ static int set_segments_check(ww_ctx *ctx, const ww_model_set *set, const void *
   if (n_seg < 0) return ww_fail(ctx, WW_EINVAL, "negative sequence count");
   if (n_members < 0) return ww_fail(ctx, WW_EINVAL, "negative member count");
   if (n_seg > 0 && (!seg_row0 || !seg_nw)) return ww_fail(ctx, WW_EINVAL, "sequence descriptors are NULL");
-  const int T = set->view.info.window;
-  int64_t W = 0;
-  for (int s = 0; s < n_seg; ++s) {
-    if (seg_nw[s] < 0) return ww_fail(ctx, WW_EINVAL, "negative window count in sequence %d", s);
-    if (seg_nw[s] && (seg_row0[s] < 0 || seg_row0[s] + (int64_t)(seg_nw[s] - 1) * hop + T > mel_rows))
-      return ww_fail(ctx, WW_EINVAL, "sequence %d: windows leave the mel buffer", s);
-    W += seg_nw[s];
-  }
+  int64_t W;
   char why[160];
+  if (int rc = seg_walk(seg_row0, seg_nw, n_seg, hop, set->view.info.window, mel_rows, &W, why)) return ww_fail(ctx, rc, "%s", why);
   if (int rc = ww_set_check_ids(members, n_members, set->n, "members", why, sizeof why)) return ww_fail(ctx, rc, "ww_set_forward_segments_dev: %s", why);
   const int32_t slots = members ? n_members : set->n;
   if (slots == 0 || W == 0) return WW_OK;
@@ -874,24 +865,21 @@ static int set_segments_run(ww_ctx *ctx, const ww_model_set *set, const float *d
   if (ww_crnn_set_segments_rows_form(m, hop, W)) {
     for (int32_t k0 = 0; k0 < n_slots; k0 += WW_SET_SLOT_CHUNK) {
       const int n = n_slots - k0 < WW_SET_SLOT_CHUNK ? n_slots - k0 : WW_SET_SLOT_CHUNK;
-      if (int rc = ww_k_crnn_set_segments_forward(ctx, m, (long long)set->stride, members + k0, n, d_mel, mel_rows, seg_row0, seg_nw, n_seg, hop, W,
-                                                  d_out + (size_t)k0 * W * NO))
-        return rc;
+      const ww_crnn_set_call sc = {(long long)set->stride, members + k0, n, W};
+      if (int rc = ww_k_crnn_segments_forward(ctx, m, d_mel, mel_rows, seg_row0, seg_nw, n_seg, hop, d_out + (size_t)k0 * W * NO, &sc)) return rc;
     }
     return WW_OK;
   }
   // every other model / form: the same windows as an explicit list of n_slots x W descriptors naming the same rows, member-major -
   // descriptor k * W + w is window w by member members[k], and its detect row is row k * W + w of d_out
   const size_t nw = (size_t)n_slots * (size_t)W;
-  std::vector<int64_t> rows(nw);
+  std::vector<int64_t> rows;
   std::vector<int32_t> ids(nw);
-  {
-    size_t w = 0;
-    for (int s = 0; s < n_seg; ++s)
-      for (int k = 0; k < seg_nw[s]; ++k) rows[w++] = seg_row0[s] + (int64_t)k * hop;
-    for (int k = 1; k < n_slots; ++k) std::copy(rows.begin(), rows.begin() + W, rows.begin() + (size_t)k * W);
-    for (int k = 0; k < n_slots; ++k) std::fill(ids.begin() + (size_t)k * W, ids.begin() + (size_t)(k + 1) * W, members[k]);
-  }
+  rows.reserve(nw);
+  seg_rows(seg_row0, seg_nw, n_seg, hop, rows);
+  rows.resize(nw);
+  for (int k = 1; k < n_slots; ++k) std::copy(rows.begin(), rows.begin() + W, rows.begin() + (size_t)k * W);
+  for (int k = 0; k < n_slots; ++k) std::fill(ids.begin() + (size_t)k * W, ids.begin() + (size_t)(k + 1) * W, members[k]);
   const std::vector<int32_t> valid(nw, T);
   ww_tables tb;
   const size_t o_rows = tb.add(rows), o_valid = tb.add(valid), o_ids = tb.add(ids), b_ws = model_ws(m, 1);
@@ -905,8 +893,7 @@ static int set_segments_run(ww_ctx *ctx, const ww_model_set *set, const float *d
   ref.stride = (long long)set->stride;
   const int64_t *d_rows = (const int64_t *)(d_tab + o_rows);
   const int32_t *d_valid = (const int32_t *)(d_tab + o_valid);
-  if (m->kind == WW_KIND_CRNN) return ww_k_crnn_set_forward(ctx, m, ref, d_mel, mel_rows, d_rows, d_valid, (int)nw, d_out, nullptr);
-  return ww_k_wave_forward(ctx, m, d_mel, mel_rows, d_rows, d_valid, 0, 0, 0, (int)nw, ws, b_ws, d_out, nullptr, nullptr, &ref);
+  return model_forward(ctx, m, d_mel, mel_rows, d_rows, d_valid, 0, 0, 0, (int)nw, ws, d_out, nullptr, &ref);
 }
 
 extern "C" {

@@ -235,18 +235,19 @@ int ww_k_crnn_init_device(ww_ctx *ctx);  // per-device kernel attributes (dynami
 // WW_EINVAL instead of writing past it
 int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
                       const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int n_windows, void *ws, size_t ws_bytes,
-                      float *d_out, float *d_enc, const ww_tick_tag *tag = nullptr);
-// a set's explicit windows, window w by member set->ids[w]: ONE crnn_fused_kernel launch whatever nw is (m: the set's view)
-int ww_k_crnn_set_forward(ww_ctx *ctx, const ww_model *m, const ww_set_ref &set, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
-                          const int32_t *d_win_valid, int nw, float *d_out, float *d_enc);
+                      float *d_out, float *d_enc, const ww_tick_tag *tag = nullptr, const ww_set_ref *set = nullptr);
 bool ww_crnn_segments_capable(const ww_model *m, int hop);
-int ww_k_crnn_segments_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
-                               const int32_t *seg_nw, int n_seg, int hop, float *d_out);
-// a set's sliding form (m: the set's view; ids: the call's member slots, a HOST array of n_ids checked ids; W: windows per member
-// of the call; d_out: [n_ids][W][n_out]): per group of sequences ONE crnn_rows_kernel<SET> and ONE tail launch over all slots
+// a set's call of the sliding form (m: the set's view): ids: the call's member slots, a HOST array of n_ids checked ids; W: windows
+// per member of the call; d_out: [n_ids][W][n_out].  Per group of sequences ONE crnn_rows_kernel<SET> and ONE tail launch over all slots
+struct ww_crnn_set_call {
+  long long stride;
+  const int32_t *ids;
+  int n_ids;
+  int64_t W;
+};
 bool ww_crnn_set_segments_rows_form(const ww_model *m, int hop, int64_t W);
-int ww_k_crnn_set_segments_forward(ww_ctx *ctx, const ww_model *m, long long set_stride, const int32_t *ids, int n_ids, const float *d_mel,
-                                   int64_t mel_rows, const int64_t *seg_row0, const int32_t *seg_nw, int n_seg, int hop, int64_t W, float *d_out);
+int ww_k_crnn_segments_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
+                               const int32_t *seg_nw, int n_seg, int hop, float *d_out, const ww_crnn_set_call *set = nullptr);
 bool ww_crnn_stream_capable(const ww_model *m);
 int ww_k_crnn_stream_forward(ww_ctx *ctx, const ww_model *m, const float *d_hist, int64_t hist_rows, const int64_t *d_win_row,
                              const int32_t *d_win_valid, const int32_t *d_win_aux, float *d_gxc, int n_windows, float *d_out,

@@ -720,7 +720,7 @@ __device__ __forceinline__ void cf_phases_d_to_g(const fused_args &a, float *img
 // per launch (the other forms lost theirs at no cost; profiles/EXPERIMENTS.md 9.5)
 #define CF_STAMP(i_) \
   if (FRONT_ONLY && a.stamps && lane == 0) a.stamps[((size_t)blockIdx.x * 4 + wave) * 10 + (i_)] = __builtin_amdgcn_s_memtime();
-// SET (a model set's batch, ww_k_crnn_set_forward): window blockIdx.x is evaluated by member set.ids[blockIdx.x] - the weight
+// SET (a model set's batch, ww_k_crnn_forward with a set): window blockIdx.x is evaluated by member set.ids[blockIdx.x] - the weight
 // pointers move on to that member's block before anything is read through them, and from there on the kernel is the
 // single-model kernel, instruction for instruction.
 __device__ __forceinline__ void cf_set_move(fused_args &a, long long off) {
@@ -1159,7 +1159,7 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
 // A workgroup stages the union of its 16 fields (15 stride + 20 <= 140 rows) once, runs the conv as 20 m-tiles
 // (position, frequency) and the projection as ONE full 16-row MFMA tile per n-tile - no 3-row remainder, and W_x1 is
 // streamed once per 16 rows that are then used by 16 x 17 / 3 windows.  gru_tail_kernel gathers a window's 19 rows.
-// SET (a model set's sliding form, ww_k_crnn_set_segments_forward): a two-dimensional grid - blockIdx.x is the tile as ever,
+// SET (a model set's sliding form, ww_k_crnn_segments_forward with a set's call): a two-dimensional grid - blockIdx.x is the tile as ever,
 // blockIdx.y the call's member slot, whose member is set.ids[blockIdx.y].  The weight pointers move on to that member's block,
 // and the slot writes plane blockIdx.y of the three lists (planes of set.aux[0] interior fields / set.aux[1] edge rows).  The
 // tile table is the geometry's and the hop's: one table for every slot.  From there on it is the single-model kernel.
@@ -2260,6 +2260,12 @@ static rows_args rows_args_of(const ww_crnn_dev &c, const float *mel, int64_t me
   r.out[0] = gI; r.out[1] = gL; r.out[2] = gR;
   return r;
 }
+// set / slots: as launch_tail's (the three output lists hold `slots` planes each)
+static void launch_rows(ww_ctx *ctx, const rows_args &r, unsigned tiles, const ww_set_ref *set = nullptr, int slots = 1) {
+  ww_launch_scope scope(ctx, set ? "crnn_rows_kernel<set>" : "crnn_rows_kernel");
+  if (set) hipLaunchKernelGGL(crnn_rows_kernel<true>, dim3(tiles, (unsigned)slots), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r, *set);
+  else hipLaunchKernelGGL(crnn_rows_kernel<false>, dim3(tiles), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r, ww_set_ref{});
+}
 
 // Scratch of a launch of nw windows, for sizing a buffer (ww_crnn_workspace) and for checking the one handed in
 // (ww_k_crnn_forward).  Sliding form: (fields + 2 edge rows per window) x 192 floats; fields <= 7 nw + 130 (hop 7), i.e. never
@@ -2272,74 +2278,32 @@ static size_t crnn_split_scratch(const ww_crnn_dev &c, int nw) {
 // Several mel sequences in one buffer (the clips of a test set, wwhip/evaluate.py), each slid over with the same hop:
 // crnn_rows_kernel by tile descriptors (no tile straddles two sequences), gru_tail_kernel with each window's first
 // interior field given explicitly.  seg_row0 / seg_nw are HOST arrays; windows are numbered sequence by sequence.
+// sc: a model set's call (ww_set_forward_segments_dev; m is the set's view, sc->ids the call's member slots on the HOST, already
+// checked).  Every group is then ONE crnn_rows_kernel<SET> launch and ONE tail launch over a (tiles | windows | groups of sixteen) x
+// n_ids grid.  A group's tile table and i0 are built and uploaded once and serve every slot; the projected-row lists, the tail16
+// scratch and the output are member-major planes: d_out is [n_ids][W][NOUT], W = the call's windows per member.  Groups stay whole
+// sequences with n_ids x nW <= WW_SEG_GROUP (a single larger sequence is a group of its own), so the workspace bound is one model's.
 bool ww_crnn_segments_capable(const ww_model *m, int hop) {
   return m->kind == WW_KIND_CRNN && !m->crnn.generic && hop >= 1 && hop <= 8 &&
          crnn_slide_min(m) != 0x7fffffff;
 }
-
-int ww_k_crnn_segments_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
-                               const int32_t *seg_nw, int n_seg, int hop, float *d_out) {
-  const ww_crnn_dev &c = m->crnn;
-  const int g = crnn_gcd8(hop);
-  crnn_seg_group gp;  // launch_plan.h: groups of whole sequences of at most ~WW_SEG_GROUP windows bound the workspace
-  int64_t w_done = 0;
-  for (int s0 = 0; s0 < n_seg; s0 = gp.next) {
-    if (int rc = crnn_plan_group(seg_row0, seg_nw, n_seg, hop, c.T, c.PT, c.OT, c.ST, mel_rows, s0, gp)) return ww_fail(ctx, rc, "%s", gp.err);
-    const int64_t nI = gp.nI, nW = gp.nW;
-    if (nW > 0) {
-      ww_tables tb;
-      const size_t o_tiles = tb.add(gp.tiles), o_i0 = tb.add(gp.i0);
-      const size_t b_rows = ww_bump::need((size_t)(nI + 2 * nW) * 6 * c.H, 4);
-      int rc = ww_ensure(ctx, ctx->dev, tb.bytes() + b_rows + tail_seq_bytes((int)nW) + 8192, false);
-      if (rc) return rc;
-      ww_bump b(ctx->dev.ptr, ctx->dev.cap);
-      char *d_tab = b.take<char>(tb.bytes());
-      const rows_tile *d_tiles = (const rows_tile *)(d_tab + o_tiles);
-      const int64_t *d_i0 = (const int64_t *)(d_tab + o_i0);
-      float *gI = b.take<float>((size_t)nI * 6 * c.H), *gL = b.take<float>((size_t)nW * 6 * c.H), *gR = b.take<float>((size_t)nW * 6 * c.H);
-      float *seq = (float *)b.take<char>(tail_seq_bytes((int)nW));
-      // the call goes on to build the next group (or returns) while this group's kernels run
-      if ((rc = tb.send(ctx, d_tab))) return rc;
-      rows_args r = rows_args_of(c, d_mel, mel_rows, gI, gL, gR);
-      r.desc = d_tiles;
-      {
-        ww_launch_scope scope(ctx, "crnn_rows_kernel");
-        hipLaunchKernelGGL(crnn_rows_kernel<false>, dim3((unsigned)gp.tiles.size()), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r, ww_set_ref{});
-      }
-      tail_args t = crnn_tail_args(c);
-      t.gxI = gI; t.gxL = gL; t.gxR = gR;
-      t.hop_g = hop / g; t.eight_g = 8 / g; t.iI0 = d_i0;
-      t.out = d_out + (size_t)w_done * c.NOUT;
-      launch_tail(ctx, m, t, (int)nW, seq);
-      WW_HIP(ctx, hipGetLastError());
-      w_done += nW;
-    }
-  }
-  return WW_OK;
-}
-
-// The same for a model set (ww_set_forward_segments_dev; m is the set's view, ids the call's member slots on the HOST, already
-// checked): every group is ONE crnn_rows_kernel<SET> launch and ONE tail launch over a (tiles | windows | groups of sixteen) x
-// n_ids grid.  A group's tile table and i0 are built and uploaded once and serve every slot; the projected-row lists, the tail16
-// scratch and the output are member-major planes.  Groups stay whole sequences with n_ids x nW <= WW_SEG_GROUP (a single larger
-// sequence is a group of its own), so the workspace bound is ww_k_crnn_segments_forward's.  d_out: [n_ids][W][NOUT], W = the call's
-// windows per member.
 bool ww_crnn_set_segments_rows_form(const ww_model *m, int hop, int64_t W) { return ww_crnn_segments_capable(m, hop) && W >= crnn_slide_min(m); }
 
-int ww_k_crnn_set_segments_forward(ww_ctx *ctx, const ww_model *m, long long set_stride, const int32_t *ids, int n_ids, const float *d_mel,
-                                   int64_t mel_rows, const int64_t *seg_row0, const int32_t *seg_nw, int n_seg, int hop, int64_t W, float *d_out) {
+int ww_k_crnn_segments_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
+                               const int32_t *seg_nw, int n_seg, int hop, float *d_out, const ww_crnn_set_call *sc) {
   const ww_crnn_dev &c = m->crnn;
-  const int g = crnn_gcd8(hop);
-  const int64_t cap = std::max<int64_t>(WW_SEG_GROUP / n_ids, 1);
-  crnn_seg_group gp;
+  const int g = crnn_gcd8(hop), n_ids = sc ? sc->n_ids : 1;
+  const int64_t cap = sc ? std::max<int64_t>(WW_SEG_GROUP / n_ids, 1) : WW_SEG_GROUP;
+  crnn_seg_group gp;  // launch_plan.h: groups of whole sequences of at most ~WW_SEG_GROUP windows x slots bound the workspace
   int64_t w_done = 0;
   for (int s0 = 0; s0 < n_seg; s0 = gp.next) {
     if (int rc = crnn_plan_group(seg_row0, seg_nw, n_seg, hop, c.T, c.PT, c.OT, c.ST, mel_rows, s0, gp, cap)) return ww_fail(ctx, rc, "%s", gp.err);
     const int64_t nI = gp.nI, nW = gp.nW;
     if (nW > 0) {
-      const int32_t aux[WW_SLIDE_AUX_N] = {(int32_t)nI, (int32_t)nW, (int32_t)W, 0};
+      const int32_t aux[WW_SLIDE_AUX_N] = {(int32_t)nI, (int32_t)nW, (int32_t)(sc ? sc->W : 0), 0};
       ww_tables tb;
-      const size_t o_tiles = tb.add(gp.tiles), o_i0 = tb.add(gp.i0), o_ids = tb.add(ids, (size_t)n_ids), o_aux = tb.add(aux, (size_t)WW_SLIDE_AUX_N);
+      const size_t o_tiles = tb.add(gp.tiles), o_i0 = tb.add(gp.i0);
+      const size_t o_ids = sc ? tb.add(sc->ids, (size_t)n_ids) : 0, o_aux = sc ? tb.add(aux, (size_t)WW_SLIDE_AUX_N) : 0;
       const size_t b_seq = tail_seq_bytes((int)nW) * (size_t)n_ids;
       int rc = ww_ensure(ctx, ctx->dev, tb.bytes() + 3 * 256 + (size_t)n_ids * (size_t)(nI + 2 * nW) * 6 * c.H * 4 + b_seq + 8192, false);
       if (rc) return rc;
@@ -2348,22 +2312,23 @@ int ww_k_crnn_set_segments_forward(ww_ctx *ctx, const ww_model *m, long long set
       float *gI = b.take<float>((size_t)n_ids * nI * 6 * c.H), *gL = b.take<float>((size_t)n_ids * nW * 6 * c.H);
       float *gR = b.take<float>((size_t)n_ids * nW * 6 * c.H);
       float *seq = (float *)b.take<char>(b_seq);
+      // the call goes on to build the next group (or returns) while this group's kernels run
       if ((rc = tb.send(ctx, d_tab))) return rc;
       ww_set_ref ref;
-      ref.ids = (const int32_t *)(d_tab + o_ids);
-      ref.aux = (const int32_t *)(d_tab + o_aux);
-      ref.stride = set_stride;
+      if (sc) {
+        ref.ids = (const int32_t *)(d_tab + o_ids);
+        ref.aux = (const int32_t *)(d_tab + o_aux);
+        ref.stride = sc->stride;
+      }
+      const ww_set_ref *set = sc ? &ref : nullptr;
       rows_args r = rows_args_of(c, d_mel, mel_rows, gI, gL, gR);
       r.desc = (const rows_tile *)(d_tab + o_tiles);
-      {
-        ww_launch_scope scope(ctx, "crnn_rows_kernel<set>");
-        hipLaunchKernelGGL(crnn_rows_kernel<true>, dim3((unsigned)gp.tiles.size(), (unsigned)n_ids), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r, ref);
-      }
+      launch_rows(ctx, r, (unsigned)gp.tiles.size(), set, n_ids);
       tail_args t = crnn_tail_args(c);
       t.gxI = gI; t.gxL = gL; t.gxR = gR;
       t.hop_g = hop / g; t.eight_g = 8 / g; t.iI0 = (const int64_t *)(d_tab + o_i0);
       t.out = d_out + (size_t)w_done * c.NOUT;
-      launch_tail(ctx, m, t, (int)nW, seq, &ref, n_ids);
+      launch_tail(ctx, m, t, (int)nW, seq, set, n_ids);
       WW_HIP(ctx, hipGetLastError());
       w_done += nW;
     }
@@ -2388,10 +2353,22 @@ bool ww_crnn_forward_tags(const ww_model *m, int nw) {
 
 int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
                       const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int nw, void *ws, size_t ws_bytes,
-                      float *d_out, float *d_enc, const ww_tick_tag *tag) {
+                      float *d_out, float *d_enc, const ww_tick_tag *tag, const ww_set_ref *set) {
   if (nw <= 0) return WW_OK;
   const ww_crnn_dev &c = m->crnn;
   win_addr wa = {d_win_row, d_win_valid, row0, hop, valid_const, mel_rows};
+  if (set) {
+    // a model set's explicit windows (m is the set's view: member 0's arguments, which each workgroup moves on to its own member):
+    // crnn_fused_kernel<false, SET> in ONE launch whatever nw is - no scratch, no sliding form, no front + tail split, no bf16
+    if (c.generic) return ww_fail(ctx, WW_EINVAL, "model set: standard conv geometry only");
+    const fused_args a = crnn_fused_args(c, d_mel, wa, d_enc, d_out);
+    {
+      ww_launch_scope scope(ctx, "crnn_fused_kernel<set>");
+      hipLaunchKernelGGL((crnn_fused_kernel<false, true>), dim3(nw), dim3(CF_THREADS), CF_FUSED_SMEM_BYTES, ctx->stream, a, *set);
+    }
+    WW_HIP(ctx, hipGetLastError());
+    return WW_OK;
+  }
   // the scratch this launch takes under the model's CURRENT options (ww_model_set_option may have moved the thresholds
   // since the caller sized ws): never past the end of what was handed in
   const bool slide_form = !c.generic && !d_win_row && !d_win_valid && valid_const >= c.T && hop >= 1 && hop <= 8 && nw >= crnn_slide_min(m) &&
@@ -2422,10 +2399,7 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
     r.stride[0] = g; r.stride[1] = hop; r.stride[2] = hop;
     r.count[0] = (int)n_int; r.count[1] = nw; r.count[2] = nw;
     for (int k = 0; k < 3; ++k) r.tiles[k] = (r.count[k] + 15) / 16;
-    {
-      ww_launch_scope scope(ctx, "crnn_rows_kernel");
-      hipLaunchKernelGGL(crnn_rows_kernel<false>, dim3(r.tiles[0] + r.tiles[1] + r.tiles[2]), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, r, ww_set_ref{});
-    }
+    launch_rows(ctx, r, (unsigned)(r.tiles[0] + r.tiles[1] + r.tiles[2]));
     tail_args t = crnn_tail_args(c);
     t.gxI = gI; t.gxL = gL; t.gxR = gR;
     t.hop_g = hop / g; t.eight_g = 8 / g;
@@ -2459,22 +2433,6 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
     ww_launch_scope scope(ctx, bf16 ? "crnn_fused_kernel<bf16x3>" : "crnn_fused_kernel");
     if (bf16) hipLaunchKernelGGL(crnn_fused_bf16_kernel<false>, dim3(nw), dim3(CF_THREADS), CFB_SMEM_BYTES, ctx->stream, a);
     else hipLaunchKernelGGL(crnn_fused_kernel<false>, dim3(nw), dim3(CF_THREADS), CF_FUSED_SMEM_BYTES, ctx->stream, a, ww_set_ref{});
-  }
-  WW_HIP(ctx, hipGetLastError());
-  return WW_OK;
-}
-
-// A model set's explicit windows (ww_set_forward_windows_dev): crnn_fused_kernel<false, SET> in ONE launch whatever nw is - no
-// front + tail split, no scratch.  m is the set's view: member 0's arguments, which each workgroup moves on to its own member.
-int ww_k_crnn_set_forward(ww_ctx *ctx, const ww_model *m, const ww_set_ref &set, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
-                          const int32_t *d_win_valid, int nw, float *d_out, float *d_enc) {
-  if (nw <= 0) return WW_OK;
-  const ww_crnn_dev &c = m->crnn;
-  if (c.generic) return ww_fail(ctx, WW_EINVAL, "model set: standard conv geometry only");
-  const fused_args a = crnn_fused_args(c, d_mel, {d_win_row, d_win_valid, 0, 0, 0, mel_rows}, d_enc, d_out);
-  {
-    ww_launch_scope scope(ctx, "crnn_fused_kernel<set>");
-    hipLaunchKernelGGL((crnn_fused_kernel<false, true>), dim3(nw), dim3(CF_THREADS), CF_FUSED_SMEM_BYTES, ctx->stream, a, set);
   }
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;

@@ -79,8 +79,39 @@ struct rows_tile {
 static inline int crnn_gcd8(int hop) { return hop % 8 == 0 ? 8 : hop % 4 == 0 ? 4 : hop % 2 == 0 ? 2 : 1; }
 static inline int64_t crnn_n_int(int64_t nw, int hop) { return ((nw - 1) * hop + 128) / crnn_gcd8(hop) + 1; }
 
+// ---- a segments call's descriptors (ww_forward_segments_dev, ww_set_forward_segments_dev): sequence s is seg_nw[s] windows of T
+// rows at seg_row0[s] + k * hop, all inside the mel buffer ------------------------------------------------------------------------
+#define WW_SEG_ERR 96  // room for the text of a refusal
+// sequence s alone: WW_OK, or WW_EINVAL with the reason in err
+static inline int seg_check(const int64_t *seg_row0, const int32_t *seg_nw, int s, int hop, int T, int64_t mel_rows, char *err) {
+  const int nw = seg_nw[s];
+  if (nw < 0) {
+    snprintf(err, WW_SEG_ERR, "negative window count in sequence %d", s);
+    return WW_EINVAL;
+  }
+  if (nw && (seg_row0[s] < 0 || seg_row0[s] + (int64_t)(nw - 1) * hop + T > mel_rows)) {
+    snprintf(err, WW_SEG_ERR, "sequence %d: windows leave the mel buffer", s);
+    return WW_EINVAL;
+  }
+  return WW_OK;
+}
+// the whole call, before anything is enqueued: *W = its windows, or the first fault
+static inline int seg_walk(const int64_t *seg_row0, const int32_t *seg_nw, int n_seg, int hop, int T, int64_t mel_rows, int64_t *W, char *err) {
+  *W = 0;
+  for (int s = 0; s < n_seg; ++s) {
+    if (int rc = seg_check(seg_row0, seg_nw, s, hop, T, mel_rows, err)) return rc;
+    *W += seg_nw[s];
+  }
+  return WW_OK;
+}
+// a checked call's windows as an explicit list of start rows, appended sequence by sequence
+static inline void seg_rows(const int64_t *seg_row0, const int32_t *seg_nw, int n_seg, int hop, std::vector<int64_t> &rows) {
+  for (int s = 0; s < n_seg; ++s)
+    for (int k = 0; k < seg_nw[s]; ++k) rows.push_back(seg_row0[s] + (int64_t)k * hop);
+}
+
 // groups of whole sequences of at most ~WW_SEG_GROUP windows bound the workspace (a model set's call: windows x members of the call,
-// ww_k_crnn_set_segments_forward - its cap per member is WW_SEG_GROUP / members)
+// its cap per member is WW_SEG_GROUP / members)
 #define WW_SEG_GROUP 32768
 
 // One group of ww_k_crnn_segments_forward: sequences [s0, next) of the call, nW windows numbered sequence by sequence and nI
@@ -92,7 +123,7 @@ struct crnn_seg_group {
   std::vector<int64_t> i0;
   int64_t nI = 0, nW = 0;
   int next = 0;
-  char err[96] = {0};  // why planning stopped (status != WW_OK), for ww_fail
+  char err[WW_SEG_ERR] = {0};  // why planning stopped (status != WW_OK), for ww_fail
 };
 static inline int crnn_plan_group(const int64_t *seg_row0, const int32_t *seg_nw, int n_seg, int hop, int T, int PT, int OT, int ST,
                                   int64_t mel_rows, int s0, crnn_seg_group &gp, int64_t cap = WW_SEG_GROUP) {
@@ -102,17 +133,10 @@ static inline int crnn_plan_group(const int64_t *seg_row0, const int32_t *seg_nw
   int64_t nI = 0, nW = 0;
   int s1 = s0;
   for (; s1 < n_seg && (s1 == s0 || nW + seg_nw[s1] <= cap); ++s1) {
+    if (int rc = seg_check(seg_row0, seg_nw, s1, hop, T, mel_rows, gp.err)) return rc;
     const int nw = seg_nw[s1];
-    if (nw < 0) {
-      snprintf(gp.err, sizeof gp.err, "negative window count in sequence %d", s1);
-      return WW_EINVAL;
-    }
     if (nw == 0) continue;
     const int64_t r0 = seg_row0[s1];
-    if (r0 < 0 || r0 + (int64_t)(nw - 1) * hop + T > mel_rows) {
-      snprintf(gp.err, sizeof gp.err, "sequence %d: windows leave the mel buffer", s1);
-      return WW_EINVAL;
-    }
     const int64_t n_int = crnn_n_int(nw, hop);
     for (int64_t p0 = 0; p0 < n_int; p0 += 16)
       gp.tiles.push_back({r0 + 2 + (int64_t)g * p0, nI + p0, g, (int32_t)(n_int - p0 < 16 ? n_int - p0 : 16), 0, 0});

@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import os
 import wave
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -28,7 +28,7 @@ from .models import engine_for
 WINDOW = 512
 CLIP_PAD = 8000  # 0.5 s of zeros each side of a clip (evaluate_models.py:52-53)
 CLIP_HOP = 2     # mel rows between windows (evaluate_models.py:42)
-_PIN = None  # page-locked staging buffer of clip_posteriors (torch tensor, grown on demand)
+_PIN = None  # page-locked staging buffer of the clip passes (_stage_clips: a torch tensor, grown on demand)
 _COPY_THREADS = 8  # copy threads of the uploader that assembles a rank's samples in page-locked memory
 
 
@@ -1150,29 +1150,37 @@ def synth_testset_scaled(n_wake: int = 2529, n_other: int = 2529, seed: int = 43
     return clips, labels
 
 
-def clip_posteriors(engine: Engine, clips: Sequence[np.ndarray], hop: int = 2, fp=None):
-    """Per clip: posterior of the single end-padded window (a17) and the sliding posteriors
-    (hop 2) of the clip padded by 0.5 s of zeros on both sides (evaluate_models.py:52-53), ring
-    reset per clip.  Returns (one_window [N], sliding list of arrays).
+class _ClipLayout(NamedTuple):
+    """Where the clips of one pass lie (:func:`_clip_layout`): offsets into the padded PCM batch, the log-mel rows and the
+    sliding windows, and the single window of every clip."""
+    soffs: np.ndarray      # [n + 1] first sample of every padded clip
+    nf_pad: np.ndarray     # [n] mel rows of the padded clip
+    foffs: np.ndarray      # [n + 1] its first row
+    nw: np.ndarray         # [n] sliding windows of the padded clip
+    woffs: np.ndarray      # [n + 1] its first sliding window
+    win_row: np.ndarray    # [n] first row of the bare clip: its single window
+    win_valid: np.ndarray  # [n] rows of that window that the bare clip fills (the rest are zeros)
 
-    One pass on the device: the padded clips go up once, one front-end launch makes their log-mel rows, and one
-    model launch evaluates every window.  The 0.5 s of leading zeros are exactly 50 hops, so frame k of the bare
-    clip is row k + 50 of the padded one: the single window of a17 is rows [50, 50 + min(frames, T)) of the same
-    buffer (``valid`` < T zero-pads it), no second front-end pass and no mel round trip through the host."""
-    import torch  # only to hold the device buffers of the batched launch
 
-    fp = fp or frontend_params()
-    pidx = engine.posterior_index
-    T, hop_s, PAD = engine.window, int(fp.hop), CLIP_PAD
-    n = len(clips)
-    if n == 0:
-        return np.zeros(0, np.float32), []
-    if PAD % hop_s:
-        raise ValueError(f"front-end hop {hop_s} does not divide the 0.5 s padding")
-    lens = np.array([len(c) for c in clips], np.int64)
-    soffs = np.concatenate(([0], np.cumsum(lens + 2 * PAD)))
-    # staged in page-locked memory (kept for the next call): the upload of the padded batch is the largest single
-    # cost of this function, and from pageable memory it runs at a fraction of the bus rate
+def _clip_layout(lens, T: int, hop: int, hop_s: int) -> _ClipLayout:
+    """Pure arithmetic on the clips' lengths - identical on every rank: each clip padded by 0.5 s of zeros on both sides
+    (evaluate_models.py:52-53), front-end hop ``hop_s`` samples, windows of ``T`` rows every ``hop`` rows.  The 0.5 s of leading
+    zeros are ``CLIP_PAD // hop_s`` whole hops, so frame k of the bare clip is row k + that of the padded one."""
+    lens = np.asarray(lens, np.int64)
+    padded = lens + 2 * CLIP_PAD
+    nf_pad = np.where(padded >= WINDOW, (padded - WINDOW) // hop_s + 1, 0)
+    nf_bare = np.where(lens >= WINDOW, (lens - WINDOW) // hop_s + 1, 0)
+    foffs = np.concatenate(([0], np.cumsum(nf_pad)))
+    nw = np.where(nf_pad >= T, (nf_pad - T) // hop + 1, 0)
+    return _ClipLayout(np.concatenate(([0], np.cumsum(padded))), nf_pad, foffs, nw, np.concatenate(([0], np.cumsum(nw))),
+                       (foffs[:-1] + CLIP_PAD // hop_s).astype(np.int64), np.minimum(nf_bare, T).astype(np.int32))
+
+
+def _stage_clips(clips: Sequence[np.ndarray], soffs: np.ndarray):
+    """The padded PCM batch in page-locked memory (kept for the next call): the upload of the padded batch is the largest
+    single cost of a clip pass, and from pageable memory it runs at a fraction of the bus rate.  A pass has waited for its
+    results when it returns, so the buffer is free again by then."""
+    import torch
     global _PIN
     need = int(soffs[-1]) + 16
     if _PIN is None or _PIN.numel() < need:
@@ -1182,38 +1190,75 @@ def clip_posteriors(engine: Engine, clips: Sequence[np.ndarray], hop: int = 2, f
     pcm[need - 16:] = 0
     for i, c in enumerate(clips):
         a = int(soffs[i])
-        pcm[a: a + PAD] = 0
-        pcm[a + PAD: a + PAD + len(c)] = c
-        pcm[a + PAD + len(c): a + 2 * PAD + len(c)] = 0
-    nf_pad = np.where(lens + 2 * PAD >= 512, (lens + 2 * PAD - 512) // hop_s + 1, 0)
-    nf_bare = np.where(lens >= 512, (lens - 512) // hop_s + 1, 0)
-    foffs = np.concatenate(([0], np.cumsum(nf_pad)))
-    total_f = int(foffs[-1])
-    # windows: one per clip (rows of the bare clip), then the sliding ones of the padded clip
-    nw = np.where(nf_pad >= T, (nf_pad - T) // hop + 1, 0)
-    woffs = np.concatenate(([0], np.cumsum(nw)))
-    # the n single windows (ragged: valid < T) as an explicit list; the sliding ones as n sequences of one buffer, which
-    # lets the CRNN compute every time position once per clip instead of once per window (ww_forward_segments_dev)
-    win_row = (foffs[:-1] + PAD // hop_s).astype(np.int64)
-    win_valid = np.minimum(nf_bare, T).astype(np.int32)
-    n_slide = int(woffs[-1])
-    dev = torch.device("cuda", engine.ctx.device)  # the engine's GPU, whatever torch's current device is
-    d_pcm = pin.to(dev, non_blocking=True)
-    d_so, d_fo = torch.from_numpy(soffs).to(dev), torch.from_numpy(foffs).to(dev)
-    d_mel = torch.empty((max(total_f, 1), engine.n_mel), dtype=torch.float32, device=dev)
-    d_row, d_valid = torch.from_numpy(win_row).to(dev), torch.from_numpy(win_valid).to(dev)
-    d_out = torch.empty((n + n_slide, engine.n_out), dtype=torch.float32, device=dev)
+        pcm[a: a + CLIP_PAD] = 0
+        pcm[a + CLIP_PAD: a + CLIP_PAD + len(c)] = c
+        pcm[a + CLIP_PAD + len(c): a + 2 * CLIP_PAD + len(c)] = 0
+    return pin
+
+
+def _clip_pass(runner, clips: Sequence[np.ndarray], hop: int, fp):
+    """One pass of the (at least one) clips on the device by a runner of ``K`` members - an :class:`Engine` (``K`` = 1, through the
+    engine's own entry points: its precision mode and launch forms live there) or a :class:`wwhip.ModelSet`: the padded clips go
+    up once, ONE front-end launch makes their log-mel rows, one launch evaluates the ``n`` single windows of all members (ragged:
+    ``valid`` < T zero-pads them; no second front-end pass, no mel round trip through the host) and one call the sliding windows
+    of all members (the clips as ``n`` sequences of one buffer, which lets a CRNN compute every time position once per clip
+    instead of once per window: ``ww_forward_segments_dev``).  Returns the layout and the detect rows ``[K, n, n_out]`` and
+    ``[K, sliding windows, n_out]``."""
+    import torch  # only to hold the device buffers of the batched launch
+
+    fp = fp or frontend_params()
+    hop_s = int(fp.hop)
+    if CLIP_PAD % hop_s:
+        raise ValueError(f"front-end hop {hop_s} does not divide the 0.5 s padding")
+    is_set = not isinstance(runner, Engine)
+    K = runner.n_models if is_set else 1
+    front = runner.engines[0] if is_set else runner  # (a set's members share their filter)
+    n = len(clips)
+    lay = _clip_layout([len(c) for c in clips], runner.window, hop, hop_s)
+    total_f, n_slide = int(lay.foffs[-1]), int(lay.woffs[-1])
+    dev = torch.device("cuda", runner.ctx.device)  # the runner's GPU, whatever torch's current device is
+    d_pcm = _stage_clips(clips, lay.soffs).to(dev, non_blocking=True)
+    d_so, d_fo = torch.from_numpy(lay.soffs).to(dev), torch.from_numpy(lay.foffs).to(dev)
+    d_mel = torch.empty((max(total_f, 1), runner.n_mel), dtype=torch.float32, device=dev)
+    # window k * n + i: the single window of clip i by member k
+    d_row, d_valid = torch.from_numpy(np.tile(lay.win_row, K)).to(dev), torch.from_numpy(np.tile(lay.win_valid, K)).to(dev)
+    d_one = torch.empty((K * n, runner.n_out), dtype=torch.float32, device=dev)
+    d_slide = torch.empty((K, max(n_slide, 1), runner.n_out), dtype=torch.float32, device=dev)
     torch.cuda.synchronize(dev)
-    engine.logmel_dev(d_pcm.data_ptr(), d_so.data_ptr(), d_fo.data_ptr(), n, total_f, int(nf_pad.max()), d_mel.data_ptr(), fp)
-    # the n single windows: one fused kernel or front + tail kernels by n - the same bits either way (one association of every
-    # sum in all forms of the CRNN), so the sharded evaluation does not differ between world sizes
-    engine.forward_windows_dev(d_mel.data_ptr(), total_f, d_row.data_ptr(), d_valid.data_ptr(), n, d_out.data_ptr())
+    front.logmel_dev(d_pcm.data_ptr(), d_so.data_ptr(), d_fo.data_ptr(), n, total_f, int(lay.nf_pad.max()), d_mel.data_ptr(), fp)
+    # an engine's n single windows: one fused kernel or front + tail kernels by n - the same bits either way (one association of
+    # every sum in all forms of the CRNN), so the sharded evaluation does not differ between world sizes
+    ids = (np.repeat(np.arange(K, dtype=np.int32), n),) if is_set else ()
+    runner.forward_windows_dev(d_mel.data_ptr(), total_f, d_row.data_ptr(), d_valid.data_ptr(), *ids, K * n, d_one.data_ptr())
     if n_slide:
-        engine.forward_segments_dev(d_mel.data_ptr(), total_f, foffs[:-1], nw, hop, d_out[n:].data_ptr())
-    engine.ctx.synchronize()
-    post = d_out.cpu().numpy()[:, pidx]
-    p_one, slide = post[:n], post[n:]
-    return p_one, [slide[woffs[i]:woffs[i + 1]] for i in range(n)]
+        runner.forward_segments_dev(d_mel.data_ptr(), total_f, lay.foffs[:-1], lay.nw, hop, d_slide.data_ptr())
+    runner.ctx.synchronize()
+    return lay, d_one.cpu().numpy().reshape(K, n, runner.n_out), d_slide.cpu().numpy()[:, :n_slide]
+
+
+def clip_posteriors(engine: Engine, clips: Sequence[np.ndarray], hop: int = 2, fp=None):
+    """Per clip: posterior of the single end-padded window (a17) and the sliding posteriors
+    (hop 2) of the clip padded by 0.5 s of zeros on both sides (evaluate_models.py:52-53), ring
+    reset per clip.  Returns (one_window [N], sliding list of arrays).  One pass on the device (:func:`_clip_pass`)."""
+    if len(clips) == 0:
+        return np.zeros(0, np.float32), []
+    lay, one, slide = _clip_pass(engine, clips, hop, fp)
+    pidx = engine.posterior_index
+    return one[0, :, pidx], [slide[0, lay.woffs[i]:lay.woffs[i + 1], pidx] for i in range(len(clips))]
+
+
+def _testset_result(engine: Engine, p_one: np.ndarray, sliding: Sequence[np.ndarray], labels: np.ndarray, clips: Sequence[np.ndarray],
+                    thresholds, windowsize: int) -> dict:
+    """FRR / FA-per-hour curves + FRR@0.5FA/h + one-window accuracy from one model's posteriors of the labelled clips: the
+    wake-word clips' maxima (a clip shorter than the window yields no posterior - the reference's np.max would raise: 0), the
+    others as one stream of their padded lengths."""
+    pos = np.array([s.max() if len(s) else 0.0 for s, l in zip(sliding, labels) if l], np.float32)
+    neg = np.concatenate([s for s, l in zip(sliding, labels) if not l]) if (~labels).any() else np.zeros(0, np.float32)
+    hours = sum(len(c) + 2 * CLIP_PAD for c, l in zip(clips, labels) if not l) / 16000.0 / 3600.0
+    thr, frr, fa, cnt = far_frr(pos, neg, max(int(labels.sum()), 1), hours, thresholds, windowsize, engine=engine)
+    return {"thresholds": thr, "frr": frr, "fa_per_hour": fa, "fa_count": cnt, "frr_at_0.5_fa_per_hour": frr_at_fa(frr, fa, 0.5),
+            "one_window_posteriors": p_one, "one_window_accuracy": float(((p_one >= 0.5) == labels).mean()),
+            "positives": pos, "negatives": neg, "hours": hours}
 
 
 def evaluate_testset(engine: Engine, clips: Sequence[np.ndarray], labels: Sequence[int], thresholds=None,
@@ -1221,14 +1266,7 @@ def evaluate_testset(engine: Engine, clips: Sequence[np.ndarray], labels: Sequen
     """FRR / FA-per-hour curves + FRR@0.5FA/h + one-window accuracy for a labelled clip set."""
     labels = np.asarray(labels).astype(bool)
     p_one, sliding = clip_posteriors(engine, clips, fp=fp)
-    pos = np.array([s.max() if len(s) else 0.0 for s, l in zip(sliding, labels) if l], np.float32)
-    neg = np.concatenate([s for s, l in zip(sliding, labels) if not l]) if (~labels).any() else np.zeros(0, np.float32)
-    hours = sum((len(c) + 16000) for c, l in zip(clips, labels) if not l) / 16000.0 / 3600.0
-    thr, frr, fa, cnt = far_frr(pos, neg, max(int(labels.sum()), 1), hours, thresholds, windowsize, engine=engine)
-    preds = (p_one >= 0.5)
-    return {"thresholds": thr, "frr": frr, "fa_per_hour": fa, "fa_count": cnt, "frr_at_0.5_fa_per_hour": frr_at_fa(frr, fa, 0.5),
-            "one_window_posteriors": p_one, "one_window_accuracy": float((preds == labels).mean()),
-            "positives": pos, "negatives": neg, "hours": hours}
+    return _testset_result(engine, p_one, sliding, labels, clips, thresholds, windowsize)
 
 
 def clip_posteriors_set(model_set, clips: Sequence[np.ndarray], hop: int = 2, fp=None):
@@ -1240,54 +1278,13 @@ def clip_posteriors_set(model_set, clips: Sequence[np.ndarray], hop: int = 2, fp
     the same bits.  (A CRNN set whose clips hold fewer sliding windows in all than its ``crnn_slide_min`` - 64 - evaluates them as
     explicit windows, where a single engine's ``forward_segments_dev`` still takes the rows form: those few posteriors then differ
     as the two forms do for one model, by less than 2e-6; ``model_set.set_option("crnn_slide_min", 1)`` gives the engine's bits.)"""
-    import torch  # only to hold the device buffers of the batched launch
-
-    fp = fp or frontend_params()
     K = model_set.n_models
-    front = model_set.engines[0]  # the set's one front end
-    pidx = [e.posterior_index for e in model_set.engines]
-    T, hop_s, PAD = model_set.window, int(fp.hop), CLIP_PAD
-    n = len(clips)
-    if n == 0:
+    if len(clips) == 0:
         return np.zeros((K, 0), np.float32), [[] for _ in range(K)]
-    if PAD % hop_s:
-        raise ValueError(f"front-end hop {hop_s} does not divide the 0.5 s padding")
-    lens = np.array([len(c) for c in clips], np.int64)
-    soffs = np.concatenate(([0], np.cumsum(lens + 2 * PAD)))
-    need = int(soffs[-1]) + 16
-    pin = torch.zeros(need, dtype=torch.int16, pin_memory=True)  # (a buffer of the call's own: clip_posteriors keeps its _PIN to itself)
-    pcm = pin.numpy()
-    for i, c in enumerate(clips):
-        a = int(soffs[i]) + PAD
-        pcm[a: a + len(c)] = c
-    nf_pad = np.where(lens + 2 * PAD >= 512, (lens + 2 * PAD - 512) // hop_s + 1, 0)
-    nf_bare = np.where(lens >= 512, (lens - 512) // hop_s + 1, 0)
-    foffs = np.concatenate(([0], np.cumsum(nf_pad)))
-    total_f = int(foffs[-1])
-    nw = np.where(nf_pad >= T, (nf_pad - T) // hop + 1, 0)
-    woffs = np.concatenate(([0], np.cumsum(nw)))
-    win_row = (foffs[:-1] + PAD // hop_s).astype(np.int64)
-    win_valid = np.minimum(nf_bare, T).astype(np.int32)
-    n_slide = int(woffs[-1])
-    dev = torch.device("cuda", model_set.ctx.device)
-    d_pcm = pin.to(dev, non_blocking=True)
-    d_so, d_fo = torch.from_numpy(soffs).to(dev), torch.from_numpy(foffs).to(dev)
-    d_mel = torch.empty((max(total_f, 1), model_set.n_mel), dtype=torch.float32, device=dev)
-    # window k * n + i: the single window of clip i by member k
-    d_row, d_valid = torch.from_numpy(np.tile(win_row, K)).to(dev), torch.from_numpy(np.tile(win_valid, K)).to(dev)
-    d_one = torch.empty((K * n, model_set.n_out), dtype=torch.float32, device=dev)
-    d_slide = torch.empty((K, max(n_slide, 1), model_set.n_out), dtype=torch.float32, device=dev)
-    torch.cuda.synchronize(dev)
-    front.logmel_dev(d_pcm.data_ptr(), d_so.data_ptr(), d_fo.data_ptr(), n, total_f, int(nf_pad.max()), d_mel.data_ptr(), fp)
-    model_set.forward_windows_dev(d_mel.data_ptr(), total_f, d_row.data_ptr(), d_valid.data_ptr(), np.repeat(np.arange(K, dtype=np.int32), n),
-                                  K * n, d_one.data_ptr())
-    if n_slide:
-        model_set.forward_segments_dev(d_mel.data_ptr(), total_f, foffs[:-1], nw, hop, d_slide.data_ptr())
-    model_set.ctx.synchronize()
-    one = d_one.cpu().numpy().reshape(K, n, model_set.n_out)
-    slide = d_slide.cpu().numpy()[:, :n_slide]
+    lay, one, slide = _clip_pass(model_set, clips, hop, fp)
+    pidx = [e.posterior_index for e in model_set.engines]
     p_one = np.stack([one[k, :, pidx[k]] for k in range(K)])
-    return p_one, [[slide[k, woffs[i]:woffs[i + 1], pidx[k]] for i in range(n)] for k in range(K)]
+    return p_one, [[slide[k, lay.woffs[i]:lay.woffs[i + 1], pidx[k]] for i in range(len(clips))] for k in range(K)]
 
 
 def evaluate_testset_set(model_set, clips: Sequence[np.ndarray], labels: Sequence[int], thresholds=None, windowsize: int = 30, fp=None):
@@ -1295,17 +1292,8 @@ def evaluate_testset_set(model_set, clips: Sequence[np.ndarray], labels: Sequenc
     (:func:`clip_posteriors_set`): a list of ``K`` result dicts, dict ``k`` what ``evaluate_testset(Engine(member k), ...)`` returns."""
     labels = np.asarray(labels).astype(bool)
     p_one, sliding = clip_posteriors_set(model_set, clips, fp=fp)
-    hours = sum((len(c) + 16000) for c, l in zip(clips, labels) if not l) / 16000.0 / 3600.0
-    results = []
-    for k in range(model_set.n_models):
-        pos = np.array([s.max() if len(s) else 0.0 for s, l in zip(sliding[k], labels) if l], np.float32)
-        neg = np.concatenate([s for s, l in zip(sliding[k], labels) if not l]) if (~labels).any() else np.zeros(0, np.float32)
-        thr, frr, fa, cnt = far_frr(pos, neg, max(int(labels.sum()), 1), hours, thresholds, windowsize, engine=model_set.engines[k])
-        preds = (p_one[k] >= 0.5)
-        results.append({"thresholds": thr, "frr": frr, "fa_per_hour": fa, "fa_count": cnt, "frr_at_0.5_fa_per_hour": frr_at_fa(frr, fa, 0.5),
-                        "one_window_posteriors": p_one[k], "one_window_accuracy": float((preds == labels).mean()),
-                        "positives": pos, "negatives": neg, "hours": hours})
-    return results
+    return [_testset_result(model_set.engines[k], p_one[k], sliding[k], labels, clips, thresholds, windowsize)
+            for k in range(model_set.n_models)]
 
 
 def evaluate_testset_sharded(engine: Engine, clips: Sequence[np.ndarray], labels: Sequence[int], rank: int = 0,
@@ -1320,13 +1308,11 @@ def evaluate_testset_sharded(engine: Engine, clips: Sequence[np.ndarray], labels
     Returns the result dict on rank 0 and ``None`` elsewhere."""
     from . import dist as D
     labels = np.asarray(labels).astype(bool)
-    T, n = engine.window, len(clips)
-    hop_s = int(fp.hop) if fp is not None else 160
-    # global layout of the sliding posteriors: pure arithmetic, identical on every rank (the same PAD / front-end hop / window
-    # hop clip_posteriors uses; asserted per clip below)
-    n_frames = np.array([(((len(c) + 2 * CLIP_PAD) - WINDOW) // hop_s + 1 if len(c) + 2 * CLIP_PAD >= WINDOW else 0) for c in clips], np.int64)
-    n_win = np.where(n_frames >= T, (n_frames - T) // CLIP_HOP + 1, 0)
-    offs = np.concatenate(([0], np.cumsum(n_win)))
+    n = len(clips)
+    # global layout of the sliding posteriors: the clip pass's own arithmetic over ALL clips, identical on every rank; what the
+    # pass returned for this rank's clips is held against it clip by clip below (it guards the gather's slots)
+    lay = _clip_layout([len(c) for c in clips], engine.window, CLIP_HOP, int(fp.hop) if fp is not None else 160)
+    n_win, offs = lay.nw, lay.woffs
     mine = D.shard_by_length([len(c) for c in clips], world)[rank]
     p_one, sliding = clip_posteriors(engine, [clips[i] for i in mine], CLIP_HOP, fp)
     for j, i in enumerate(mine):
@@ -1344,17 +1330,10 @@ def evaluate_testset_sharded(engine: Engine, clips: Sequence[np.ndarray], labels
         all_one[mine] = p_one
     if rank != 0:
         return None
-    # a clip shorter than the window yields no posterior (the reference's np.max would raise): 0
-    pos = np.array([all_slide[offs[i]:offs[i + 1]].max() if offs[i + 1] > offs[i] else 0.0
-                    for i in range(n) if labels[i]], np.float32)
-    neg = (np.concatenate([all_slide[offs[i]:offs[i + 1]] for i in range(n) if not labels[i]])
-           if (~labels).any() else np.zeros(0, np.float32))
-    hours = sum(len(clips[i]) + 2 * CLIP_PAD for i in range(n) if not labels[i]) / 16000.0 / 3600.0
-    thr, frr, fa, cnt = far_frr(pos, neg, max(int(labels.sum()), 1), hours, thresholds, windowsize, engine=engine)
-    return {"thresholds": thr, "frr": frr, "fa_per_hour": fa, "fa_count": cnt, "frr_at_0.5_fa_per_hour": frr_at_fa(frr, fa, 0.5),
-            "one_window_posteriors": all_one, "one_window_accuracy": float(((all_one >= 0.5) == labels).mean()),
-            "positives": pos, "negatives": neg, "hours": hours, "sliding": all_slide, "sliding_offsets": offs,
-            "windows": int(offs[-1]) + n, "posterior_checksum": float(all_slide.sum(dtype=np.float64))}
+    res = _testset_result(engine, all_one, [all_slide[offs[i]:offs[i + 1]] for i in range(n)], labels, clips, thresholds, windowsize)
+    res.update({"sliding": all_slide, "sliding_offsets": offs, "windows": int(offs[-1]) + n,
+                "posterior_checksum": float(all_slide.sum(dtype=np.float64))})
+    return res
 
 
 # ----------------------------------------------------------------------------------------------
