@@ -308,6 +308,10 @@ __device__ __forceinline__ float gru_step(const gru_w &g, const float *hin, int 
   return gru_blend(z, h_own, gru_candidate(r, sc, gc));
 }
 
+// The wave's number within its workgroup, in a scalar register: tid >> 6 is the same in all 64 lanes, which the compiler
+// cannot know - what is derived from it (a direction, a time position, `wave < 2`) would be vector work and exec-mask forks.
+__device__ __forceinline__ int wave_index(int tid) { return __builtin_amdgcn_readfirstlane(tid >> 6); }
+
 // Between the h write of one step and the h reads of the next: LDS instructions of ONE wave are
 // executed in issue order, so no s_waitcnt is needed - only the compiler must not reorder them.
 __device__ __forceinline__ void wsync_h() {
@@ -573,29 +577,53 @@ struct fused_args {
   ww_tick_tag tag;             // streaming ticks: the posterior as a {value, tick number} pair instead of the row of `out` (common.h)
 };
 
-// one direction of one GRU layer over the OT steps held in LDS (gx rows incl. b_x), h ping-pong in hd
+// one direction of one GRU layer over the OT steps held in LDS (gx rows incl. b_x), h ping-pong in hd.
+// dir is WAVE-UNIFORM and the caller hands it over in a scalar register (wave_index()): the time position is then scalar too,
+// and a step's LDS addresses are per-lane pointers formed here, in front of the loop, that move on by a scalar stride (gx row,
+// seq1 row) or take the ping-pong slot as an immediate offset (h) - no multiply, no select and no 64-bit arithmetic in a step.
+// The loop runs over the two-step period of the h ping-pong, so that the slot is a constant of each copy of the step and the
+// values carried from step to step (h_own, the prefetched inputs) change names instead of registers; OT is odd, its last step
+// is the tail and has nothing left to fetch ahead.
 template <bool SEQ>
 __device__ __forceinline__ float cf_recurrence(const gru_w &g, const float *gxs, float *hd, float *seq1, int dir, int unit, int half) {
   constexpr int H = GR_H, OT = CV_OT;
-  const float *gxl = gxs + dir * 3 * H + unit;
+  static_assert(OT % 2 == 1, "the step loop is pairs of steps plus one");
+  const int t0 = dir ? OT - 1 : 0;
+  const int gx_step = dir ? -GR_GX_LD : GR_GX_LD, seq_step = dir ? -GR_SEQ_LD : GR_SEQ_LD;
+  const float *gxp = gxs + t0 * GR_GX_LD + dir * 3 * H + unit;        // this step's projected inputs
+  float *sqp = SEQ ? seq1 + t0 * GR_SEQ_LD + dir * H + unit : nullptr; // this step's row of seq1
+  float *hw = hd + unit;
   float h_own = 0.f;
-  int t = dir ? OT - 1 : 0;
   // a step's projected inputs start two of its chains, so they are fetched a step ahead (behind the h reads, which are the
   // ones the step waits for)
-  float gz = gxl[t * GR_GX_LD], gr = gxl[t * GR_GX_LD + H], gc = gxl[t * GR_GX_LD + 2 * H];
-  for (int s = 0; s < OT; ++s) {
-    const int cur = s & 1;
-    const int tn = dir ? (t > 0 ? t - 1 : 0) : (t + 1 < OT ? t + 1 : OT - 1);
+  float gz = gxp[0], gr = gxp[H], gc = gxp[2 * H];
+#pragma unroll 1
+  for (int s = 0; s < OT / 2; ++s) {
     float nz, nr, nc;
-    h_own = gru_step<true>(g, hd + cur * H, half, gz, gr, gc, h_own, gxl + tn * GR_GX_LD, nz, nr, nc);
+    gxp += gx_step;
+    h_own = gru_step<true>(g, hd, half, gz, gr, gc, h_own, gxp, nz, nr, nc);
     if (half == 0) {
-      hd[(cur ^ 1) * H + unit] = h_own;
-      if (SEQ) seq1[t * GR_SEQ_LD + dir * H + unit] = h_own;
+      hw[H] = h_own;
+      if (SEQ) *sqp = h_own;
     }
+    if (SEQ) sqp += seq_step;
     wsync_h();
-    gz = nz; gr = nr; gc = nc;
-    t = tn;
+    gxp += gx_step;
+    h_own = gru_step<true>(g, hd + H, half, nz, nr, nc, h_own, gxp, gz, gr, gc);
+    if (half == 0) {
+      hw[0] = h_own;
+      if (SEQ) *sqp = h_own;
+    }
+    if (SEQ) sqp += seq_step;
+    wsync_h();
   }
+  float nz, nr, nc;  // (not fetched)
+  h_own = gru_step<false>(g, hd, half, gz, gr, gc, h_own, nullptr, nz, nr, nc);
+  if (half == 0) {
+    hw[H] = h_own;
+    if (SEQ) *sqp = h_own;
+  }
+  wsync_h();
   return h_own;
 }
 
@@ -652,7 +680,7 @@ __device__ __forceinline__ float cf_recurrence(const gru_w &g, const float *gxs,
 // recurrent weights (waves 0, 1: layer 1; waves 2, 3: layer 2).
 __device__ __forceinline__ void cf_phases_d_to_g(const fused_args &a, float *img, float *feat, const gru_w &g, int w) {
   constexpr int H = GR_H;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = wave_index(tid);  // (scalar: so are dir and the forks on wave below)
   const int j = lane & 15, kk = lane >> 4;
   const int unit = lane >> 1, half = lane & 1, dir = wave & 1;
   float *gxs = img + CF_GX, *seq1 = img + CF_SEQ, *hb = img + CF_HB, *encs = img + CF_ENC, *hid = img + CF_HID, *w2s = img + CF_W2S;
@@ -1579,7 +1607,7 @@ __global__ __launch_bounds__(128, 4) void gru_tail_kernel(tail_args a, ww_set_re
   constexpr int H = GR_H, OT = CV_OT;
   __shared__ __align__(16) float sm[GT_SMEM_FLOATS];
   float *gxs = sm, *seq1 = sm + GT_SEQ, *hb = sm + GT_HB, *encs = sm + GT_ENC, *hid = sm + GT_HID;
-  const int tid = threadIdx.x, lane = tid & 63, dir = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, dir = wave_index(tid);  // (scalar)
   const int j = lane & 15, kk = lane >> 4, unit = lane >> 1, half = lane & 1;
   const int w = blockIdx.x;
   gru_w g;
