@@ -342,8 +342,9 @@ int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *model, const float *d_m
  * ww_set_slide_forward: host pointers, ONE sequence of `rows` rows, synchronous - ww_slide_forward for every slot over one upload:
  * out is [slots][n_windows][n_out], *n_windows the count PER MEMBER ((rows - window) / hop + 1, 0 if rows < window).
  * ww_set_option: WW_OPT_CRNN_SLIDE_MIN and WW_OPT_CRNN_TAIL_MFMA (ww_model_set_option's meanings and ranges) for the set's launches -
- * the two options that decide the form above; a set starts from the library's defaults whatever its members' options are.  Any other
- * key: WW_EINVAL.  The two tails give the same bits; the rows form and the explicit-window form differ as they do for one model
+ * the two options that decide the form above - and WW_OPT_WAVE_SEQ_SEGMENT (likewise) for the cuts of ww_set_wave_sequence*; a set
+ * starts from the library's defaults whatever its members' options are.  Every other key (WW_OPT_CRNN_SPLIT_AT and
+ * WW_OPT_WAVENET_ROWMAJOR among them): WW_EINVAL.  The two tails give the same bits; the rows form and the explicit-window form differ as they do for one model
  * (three of a window's nineteen projected rows are summed in another order: posteriors within 2e-6).  A single model's
  * ww_forward_segments_dev takes the rows form whatever W is: WW_OPT_CRNN_SLIDE_MIN = 1 gives a set exactly those bits. */
 int ww_set_forward_segments_dev(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
@@ -378,6 +379,40 @@ int ww_wave_sequence_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel,
                          int32_t n_seq, int32_t pool_rows, float *d_enc, float *d_logits, float *d_post_frames, float *d_post);
 int ww_wave_sequence(ww_ctx *ctx, const ww_model *model, const float *mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
                      int32_t pool_rows, float *enc, float *logits, float *post_frames, float *post);
+
+/* The same over a model set of Wavenets, in ONE call over ONE mel buffer: the checkpoint loop of
+ * wwdetect/wavenet/evaluate_wavenet.py: eval_models over whole recordings (_all), and a service whose recordings each belong to a
+ * tenant's member (by sequence).  Sequences, row_offs, pool_rows and the outputs' meaning are ww_wave_sequence's.
+ *   ww_set_wave_sequence[_dev]: sequence s is evaluated by member seq_model[s] (a HOST array of n_seq ids; NULL = every sequence by
+ *     member 0); the outputs are laid out as ww_wave_sequence's - one plane.
+ *   ww_set_wave_sequence_all[_dev]: every sequence by every slot.  members / n_members as in ww_set_forward_segments_dev: a HOST array
+ *     of member ids, each a slot of the call, duplicates allowed, NULL = every member of the set in order (n_members is then looked at
+ *     for its sign only).  Plane k is member members[k]: enc [slots][total_rows][32], logits and post_frames
+ *     [slots][total_rows][n_out], post [slots][n_seq][n_out].
+ * Every output of sequence s in plane k carries the bits ww_wave_sequence gives for that sequence with that member alone, wherever the
+ * cuts fall (ww_set_option: WW_OPT_WAVE_SEQ_SEGMENT) and whatever the neighbouring sequences, the other slots and the size of the call
+ * are.  Rows of the buffers outside every sequence are neither read nor written, in every plane; an empty sequence's post rows are
+ * left as they are.  Every output may be NULL.
+ * The model kernel runs ONCE for all planes (a segments x slots grid, 1,024 slots per launch; the segment table is the single
+ * model's, the members travel beside it) and so does each pooling kernel: the launch count does not grow with the slots.
+ * WW_EINVAL, with nothing enqueued and nothing written: a NULL ctx or set; a set of another context; a set of CRNNs (a CRNN's
+ * bidirectional GRUs have no causal reading); n_seq < 0, pool_rows < 0, n_members < 0; offsets that descend or leave the buffer; a
+ * member id outside [0, n_models) (ww_last_error names its index); a NULL mel buffer where there are rows to compute.  WW_OK with
+ * nothing written: n_seq = 0, all sequences empty, n_members = 0 with members != NULL, every output NULL.
+ * The _dev forms enqueue on the context's stream and wait for nothing unless a buffer of the context has to grow; their host arrays
+ * are read before the call returns.  The host forms upload the mel once, whatever the number of slots, and are synchronous. */
+int ww_set_wave_sequence_dev(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t total_rows, const int64_t *row_offs,
+                             int32_t n_seq, const int32_t *seq_model, int32_t pool_rows, float *d_enc, float *d_logits,
+                             float *d_post_frames, float *d_post);
+int ww_set_wave_sequence(ww_ctx *ctx, const ww_model_set *set, const float *mel, int64_t total_rows, const int64_t *row_offs,
+                         int32_t n_seq, const int32_t *seq_model, int32_t pool_rows, float *enc, float *logits, float *post_frames,
+                         float *post);
+int ww_set_wave_sequence_all_dev(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t total_rows, const int64_t *row_offs,
+                                 int32_t n_seq, int32_t pool_rows, const int32_t *members, int32_t n_members, float *d_enc,
+                                 float *d_logits, float *d_post_frames, float *d_post);
+int ww_set_wave_sequence_all(ww_ctx *ctx, const ww_model_set *set, const float *mel, int64_t total_rows, const int64_t *row_offs,
+                             int32_t n_seq, int32_t pool_rows, const int32_t *members, int32_t n_members, float *enc, float *logits,
+                             float *post_frames, float *post);
 
 /* Whole hot path for a batch of equal-length clips resident in HBM (BASELINE configs 2/3):
  * PCM [n_clips][samples_per_clip] -> log-mel -> one zero-padded window per clip ->

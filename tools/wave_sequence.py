@@ -14,7 +14,13 @@
               alternated in blocks) and one stream's hour in one packet against Engine.logmel + sequence_forward, with the library's
               per-kernel times.  --part catchup | lockstep | hour | once (one untimed 1 h feed, for a kernel trace) | all.
 
-usage: wave_sequence.py feed [--part all] [--streams 128] [--seconds 10] [--reps 5] [--ticks 4000] |
+  set         a model set's sequence form: ONE ww_set_wave_sequence_all_dev call for K slots (the two shipped Wavenets, repeated)
+              against K ww_wave_sequence_dev calls of the members' engines over the same resident mel, post_frames of every row,
+              alternated; at two shapes - --seqs sequences of --rows rows (clips) and one sequence of --long-rows rows (a recording) -
+              and K = 1, 2, 4, 8.  The outputs of the two sides are compared bit for bit.
+
+usage: wave_sequence.py set [--seqs 256] [--rows 300] [--long-rows 360000] [--reps 9] |
+       wave_sequence.py feed [--part all] [--streams 128] [--seconds 10] [--reps 5] [--ticks 4000] |
        wave_sequence.py throughput [--model Wavenet] [--reps 5] [--once] | latency [--streams 128] [--ticks 4000] |
        distance [--clips 256]"""
 import argparse, json, os, sys, time
@@ -188,6 +194,52 @@ def feed(args):
     print(json.dumps(out))
 
 
+def set_form(args):
+    import torch
+    from wwhip.engine import ModelSet
+    names = ["Wavenet", "Wavenet_alt"]
+    engines = [_engine(n) for n in names]
+    ms = ModelSet(engines)
+    NO = ms.n_out
+    rng = np.random.default_rng(0)
+    out = {"members": names, "reps": args.reps, "shapes": []}
+
+    def timed(f):
+        ms.ctx.synchronize()
+        t0 = time.perf_counter(); f(); ms.ctx.synchronize()
+        return time.perf_counter() - t0
+    for label, n_seq, rows_each in (("clips", args.seqs, args.rows), ("recording", 1, args.long_rows)):
+        rows = n_seq * rows_each
+        d_mel = torch.from_numpy(rng.uniform(0.0, 6.0, (rows, 40)).astype(np.float32)).cuda()
+        offs = np.arange(n_seq + 1, dtype=np.int64) * rows_each
+        shape = {"shape": label, "sequences": n_seq, "rows_each": rows_each, "by_slots": []}
+        for K in (1, 2, 4, 8):
+            slots = [k % len(engines) for k in range(K)]
+            d_one = torch.empty((K, rows, NO), dtype=torch.float32, device="cuda")
+            d_many = torch.empty((K, rows, NO), dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()
+            one = lambda: ms.wave_sequence_all_dev(d_mel.data_ptr(), rows, offs, slots, d_post_frames_ptr=d_one.data_ptr())
+
+            def many():
+                for k, m in enumerate(slots):
+                    engines[m].wave_sequence_dev(d_mel.data_ptr(), rows, offs, d_post_frames_ptr=d_many[k].data_ptr())
+            for f in (one, many, one, many):  # warm-up: code objects, the context's workspace at its final size
+                timed(f)
+            t_one, t_many = [], []
+            for _ in range(args.reps):        # the two sides alternated
+                t_one.append(timed(one)); t_many.append(timed(many))
+            ms.ctx.profile(True); one(); prof = ms.ctx.profile_read(); ms.ctx.profile(False)
+            shape["by_slots"].append({"slots": K, "one_call_ms": _spread(np.array(t_one) * 1e3), "k_calls_ms": _spread(np.array(t_many) * 1e3),
+                                      "k_calls_over_one_call_median": float(np.median(t_many) / np.median(t_one)),
+                                      "spreads_overlap": bool(max(t_one) >= min(t_many) and max(t_many) >= min(t_one)),
+                                      "one_call_kernels_ms": {k: round(v["total_ms"], 3) for k, v in prof.items()},
+                                      "one_call_kernel_scopes": {k: int(v["calls"]) for k, v in prof.items()},
+                                      "same_bits": bool(torch.equal(d_one, d_many))})
+        out["shapes"].append(shape)
+    ms.close()
+    print(json.dumps(out))
+
+
 def distance(args):
     from wwhip.evaluate import synth_testset
     eng = _engine(args.model)
@@ -209,7 +261,7 @@ def distance(args):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["throughput", "latency", "distance", "feed"])
+    ap.add_argument("what", choices=["throughput", "latency", "distance", "feed", "set"])
     ap.add_argument("--model", default="Wavenet")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--wake", type=int, default=2529)
@@ -218,6 +270,9 @@ if __name__ == "__main__":
     ap.add_argument("--ticks", type=int, default=4000)
     ap.add_argument("--clips", type=int, default=256)
     ap.add_argument("--seconds", type=int, default=10)
+    ap.add_argument("--seqs", type=int, default=256)
+    ap.add_argument("--rows", type=int, default=300)
+    ap.add_argument("--long-rows", type=int, default=360000)
     ap.add_argument("--part", default="all", choices=["all", "catchup", "lockstep", "hour", "once"])
     a = ap.parse_args()
-    {"throughput": throughput, "latency": latency, "distance": distance, "feed": feed}[a.what](a)
+    {"throughput": throughput, "latency": latency, "distance": distance, "feed": feed, "set": set_form}[a.what](a)

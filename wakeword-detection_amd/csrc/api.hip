@@ -442,7 +442,8 @@ int ww_model_set_create(ww_ctx *ctx, const ww_model *const *models, int32_t n_mo
   WW_GUARD_END(ctx)
 }
 
-// The two options that decide the sliding form's launches (the view starts from the library's defaults)
+// The two options that decide the sliding form's launches and the segment length of the sequence form (the view starts from the
+// library's defaults)
 int ww_set_option(ww_model_set *set, int key, int64_t value) {
   WW_GUARD_BEGIN
   if (!set) return WW_EINVAL;
@@ -453,7 +454,9 @@ int ww_set_option(ww_model_set *set, int key, int64_t value) {
       if (value > 2) return ww_fail(set->ctx, WW_EINVAL, "WW_OPT_CRNN_TAIL_MFMA takes 0 (never), 1 (from 9,216 windows per launch) or 2 (always)");
       set->view.opt_tail_mfma = (int)value;
       return WW_OK;
-    default: return ww_fail(set->ctx, WW_EINVAL, "a model set takes WW_OPT_CRNN_SLIDE_MIN and WW_OPT_CRNN_TAIL_MFMA, not option %d", key);
+    case WW_OPT_WAVE_SEQ_SEGMENT: set->view.opt_wave_seq_segment = (int)value; return WW_OK;
+    default:
+      return ww_fail(set->ctx, WW_EINVAL, "a model set takes WW_OPT_CRNN_SLIDE_MIN, WW_OPT_CRNN_TAIL_MFMA and WW_OPT_WAVE_SEQ_SEGMENT, not option %d", key);
   }
   WW_GUARD_END(set ? set->ctx : nullptr)
 }
@@ -975,24 +978,43 @@ static int wave_seq_validate(ww_ctx *ctx, const ww_model *m, int64_t total_rows,
   return WW_OK;
 }
 
+// A model set's side of a call (m is then the set's view): `planes` output planes of total_rows rows each, plane k by member ids[k]
+// - or by_seq: ONE plane, sequence s by member ids[s].  ids: a HOST array of checked ids, planes (by_seq: n_seq) of them.
+struct wave_seq_set_call {
+  long long stride;
+  const int32_t *ids;
+  int planes;
+  bool by_seq;
+};
+
 static int wave_seq_run(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t total_rows, const int64_t *row_offs, int n_seq,
-                        int pool_rows, float *d_enc, float *d_logits, float *d_pf, float *d_post, const wave_seq_plan &pl, ww_bump &bump) {
+                        int pool_rows, float *d_enc, float *d_logits, float *d_pf, float *d_post, const wave_seq_plan &pl, ww_bump &bump,
+                        const wave_seq_set_call *sc = nullptr) {
   if (pl.segs.empty()) return WW_OK;
   if (pl.segs.size() > 0x7fffffffu) return ww_fail(ctx, WW_EINVAL, "too many segments in one call");
-  const int NO = m->info.n_out;
+  const int NO = m->info.n_out, planes = sc ? sc->planes : 1;
   ww_tables tb;
   const size_t o_segs = tb.add(pl.segs), o_offs = tb.add(row_offs, (size_t)n_seq + 1);
-  if (tb.bytes() != pl.b_segs + pl.b_offs) return ww_fail(ctx, WW_EINTERNAL, "wave_seq_run: the tables are not the size the plan reserved");
+  const size_t o_ids = sc ? tb.add(sc->ids, sc->by_seq ? (size_t)n_seq : (size_t)planes) : 0, o_aux = sc && sc->by_seq ? tb.add(pl.seg_seq) : 0;
+  if (tb.bytes() != pl.b_segs + pl.b_offs + pl.b_ids + pl.b_aux) return ww_fail(ctx, WW_EINTERNAL, "wave_seq_run: the tables are not the size the plan reserved");
   char *d_tab = bump.take<char>(tb.bytes());
   const wv_seg *d_segs = (const wv_seg *)(d_tab + o_segs);
   const int64_t *d_offs = (const int64_t *)(d_tab + o_offs);
+  const size_t plane = (size_t)total_rows * NO;
   float *d_z = d_logits;
-  if (!d_z && (d_pf || d_post)) d_z = bump.take<float>((size_t)total_rows * NO);
-  float *d_a = d_pf ? bump.take<float>((size_t)total_rows * NO) : nullptr, *d_b = d_pf ? bump.take<float>((size_t)total_rows * NO) : nullptr;
+  if (!d_z && (d_pf || d_post)) d_z = bump.take<float>(planes * plane);
+  float *d_a = d_pf ? bump.take<float>(planes * plane) : nullptr, *d_b = d_pf ? bump.take<float>(planes * plane) : nullptr;
   if (int rc = tb.send(ctx, d_tab)) return rc;
-  int rc = ww_k_wave_sequence(ctx, m, d_mel, d_segs, (int)pl.segs.size(), d_enc, d_z);
+  ww_set_ref ref;
+  if (sc) {
+    ref.ids = (const int32_t *)(d_tab + o_ids);
+    ref.aux = sc->by_seq ? (const int32_t *)(d_tab + o_aux) : nullptr;
+    ref.stride = sc->stride;
+  }
+  int rc = ww_k_wave_sequence(ctx, m, d_mel, d_segs, (int)pl.segs.size(), d_enc, d_z, sc ? &ref : nullptr, planes, total_rows);
   if (rc) return rc;
-  if (d_pf || d_post) rc = ww_k_wave_pool(ctx, d_z, row_offs[n_seq] - row_offs[0], row_offs[n_seq], NO, d_offs, n_seq, pool_rows, pl.max_len, d_a, d_b, d_pf, d_post);
+  if (d_pf || d_post)
+    rc = ww_k_wave_pool(ctx, d_z, row_offs[n_seq] - row_offs[0], row_offs[n_seq], NO, d_offs, n_seq, pool_rows, pl.max_len, d_a, d_b, d_pf, d_post, planes, total_rows);
   return rc;
 }
 
@@ -1048,6 +1070,159 @@ int ww_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t t
   if (post) WW_HIP(ctx, hipMemcpyAsync(post, d_post, (size_t)n_seq * NO * 4, hipMemcpyDeviceToHost, ctx->stream));
   WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return WW_OK;
+  WW_GUARD_END(ctx)
+}
+
+}  // extern "C"
+
+// ---- the sequence form over a model set (ww_set_wave_sequence*): validation, cuts, pooling and tables are the single model's
+//      (wave_seq_validate, wave_seq_run); a call adds its member ids and its planes ---------------------------------------------------
+// One shape for the four entry points.  by_seq: ONE plane, sequence s by member ids[s] (n_ids = n_seq; ids == NULL: member 0).
+// Otherwise plane k by member ids[k] (ids == NULL: every member in order, n_ids only checked for its sign).
+struct set_seq_request {
+  const float *mel;  // host or device, as the entry point's outputs
+  int64_t total_rows;
+  const int64_t *row_offs;
+  int32_t n_seq, pool_rows;
+  const int32_t *ids;
+  int32_t n_ids;
+  bool by_seq;
+  float *enc, *logits, *pf, *post;
+};
+
+// Everything the four refuse, before anything is enqueued or written.  *slots: the call's planes (by_seq: 1); 0 with WW_OK: a no-op
+static int set_wave_seq_check(ww_ctx *ctx, const ww_model_set *set, const set_seq_request &c, const char *what, int32_t *slots) {
+  *slots = 0;
+  if (!ctx || !set) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (set->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "the model set belongs to another context");
+  if (int rc = wave_seq_validate(ctx, &set->view, c.total_rows, c.row_offs, c.n_seq, c.pool_rows)) return rc;
+  if (c.n_ids < 0) return ww_fail(ctx, WW_EINVAL, "negative member count");
+  char why[160];
+  if (int rc = ww_set_check_ids(c.ids, c.n_ids, set->n, c.by_seq ? "seq_model" : "members", why, sizeof why)) return ww_fail(ctx, rc, "%s: %s", what, why);
+  const int32_t n = c.by_seq ? 1 : c.ids ? c.n_ids : set->n;
+  if (c.n_seq == 0 || c.row_offs[c.n_seq] == c.row_offs[0] || n == 0) return WW_OK;
+  if (!c.mel) return ww_fail(ctx, WW_EINVAL, "NULL mel buffer");
+  if (!c.enc && !c.logits && !c.pf && !c.post) return WW_OK;
+  *slots = n;
+  return WW_OK;
+}
+
+// The plan of a launch of `planes` planes: the set's view gives the receptive field, the width of a logit row and the segment option
+static void set_wave_seq_plan(const ww_model_set *set, const set_seq_request &c, int planes, wave_seq_plan &pl) {
+  wave_seq_set_make_plan(ww_wave_receptive_field(&set->view), set->view.info.n_out, set->view.opt_wave_seq_segment, c.total_rows, c.row_offs,
+                         c.n_seq, planes, c.by_seq, !c.logits && (c.pf || c.post), c.pf != nullptr, pl);
+}
+static int set_wave_seq_planes(int32_t slots) { return slots < WW_SET_SLOT_CHUNK ? slots : WW_SET_SLOT_CHUNK; }
+
+// The checked call on DEVICE buffers (the context's device is current): one launch of the model kernel per WW_SET_SLOT_CHUNK slots
+// - the plane is a 16-bit grid dimension, and the scratch of a call with many duplicates stays bounded.  `bump`: the arena behind
+// what the caller took from it; the caller has reserved the first launch's plan there (the largest).
+static int set_wave_seq_run(ww_ctx *ctx, const ww_model_set *set, const set_seq_request &c, int32_t slots, const wave_seq_plan &first, ww_bump bump) {
+  const ww_model *m = &set->view;
+  const int NO = m->info.n_out, S = m->info.enc_width;
+  std::vector<int32_t> own;
+  const int32_t *ids = c.ids;
+  if (!ids) {
+    own.assign(c.by_seq ? (size_t)c.n_seq : (size_t)slots, 0);  // (every sequence by member 0)
+    if (!c.by_seq)
+      for (int32_t k = 0; k < slots; ++k) own[k] = k;
+    ids = own.data();
+  }
+  for (int32_t k0 = 0; k0 < slots; k0 += WW_SET_SLOT_CHUNK) {
+    const int planes = set_wave_seq_planes(slots - k0);
+    wave_seq_plan later;
+    if (k0) set_wave_seq_plan(set, c, planes, later);
+    const wave_seq_set_call sc = {(long long)set->stride, c.by_seq ? ids : ids + k0, planes, c.by_seq};
+    const size_t at = (size_t)k0 * (size_t)c.total_rows;  // the launch's first plane, in rows
+    ww_bump scratch = bump;  // (the launches of a call follow each other on one stream: they share the scratch)
+    if (int rc = wave_seq_run(ctx, m, c.mel, c.total_rows, c.row_offs, c.n_seq, c.pool_rows, c.enc ? c.enc + at * S : nullptr,
+                              c.logits ? c.logits + at * NO : nullptr, c.pf ? c.pf + at * NO : nullptr,
+                              c.post ? c.post + (size_t)k0 * c.n_seq * NO : nullptr, k0 ? later : first, scratch, &sc))
+      return rc;
+  }
+  return WW_OK;
+}
+
+static int set_wave_seq_dev(ww_ctx *ctx, const ww_model_set *set, const set_seq_request &c, const char *what) {
+  int32_t slots;
+  if (int rc = set_wave_seq_check(ctx, set, c, what, &slots)) return rc;
+  if (slots == 0) return WW_OK;
+  WW_ON_DEVICE(ctx, dev);
+  wave_seq_plan pl;
+  set_wave_seq_plan(set, c, set_wave_seq_planes(slots), pl);
+  if (int rc = ww_ensure(ctx, ctx->dev, pl.bytes() + 1024, false)) return rc;
+  return set_wave_seq_run(ctx, set, c, slots, pl, ww_bump(ctx->dev.ptr, ctx->dev.cap));
+}
+
+// HOST buffers: one upload of the mel, the outputs' planes on the device, every plane's sequence rows back.  Synchronous.
+static int set_wave_seq_host(ww_ctx *ctx, const ww_model_set *set, const set_seq_request &c, const char *what) {
+  int32_t slots;
+  if (int rc = set_wave_seq_check(ctx, set, c, what, &slots)) return rc;
+  if (slots == 0) return WW_OK;
+  WW_ON_DEVICE(ctx, dev);
+  const int F = set->view.info.n_mel, NO = set->view.info.n_out, S = set->view.info.enc_width;
+  const size_t rows = (size_t)c.total_rows, K = (size_t)slots;
+  wave_seq_plan pl;
+  set_wave_seq_plan(set, c, set_wave_seq_planes(slots), pl);  // (which outputs exist decides the plan's scratch, not where they are)
+  set_seq_request d = c;
+  const size_t b_mel = ww_bump::need(rows * F, 4), b_enc = c.enc ? ww_bump::need(K * rows * S, 4) : 0, b_rows = ww_bump::need(K * rows * NO, 4);
+  const size_t b_post = ww_bump::need(K * c.n_seq * NO, 4);
+  if (int rc = ww_ensure(ctx, ctx->dev, b_mel + b_enc + 2 * b_rows + b_post + pl.bytes() + 1024, false)) return rc;
+  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
+  float *d_mel = bump.take<float>(rows * F);
+  d.mel = d_mel;
+  d.enc = c.enc ? bump.take<float>(K * rows * S) : nullptr;
+  d.logits = c.logits ? bump.take<float>(K * rows * NO) : nullptr;
+  d.pf = c.pf ? bump.take<float>(K * rows * NO) : nullptr;
+  d.post = c.post ? bump.take<float>(K * c.n_seq * NO) : nullptr;
+  // rows outside every sequence are neither read nor written, in any plane: only [r0, r1) travels, each way
+  const int64_t r0 = c.row_offs[0], r1 = c.row_offs[c.n_seq];
+  WW_HIP(ctx, hipMemcpyAsync(d_mel + r0 * F, c.mel + r0 * F, (size_t)(r1 - r0) * F * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (d.post) WW_HIP(ctx, hipMemcpyAsync(d.post, c.post, K * c.n_seq * NO * 4, hipMemcpyHostToDevice, ctx->stream));  // (empty sequences keep theirs)
+  if (int rc = set_wave_seq_run(ctx, set, d, slots, pl, bump)) return rc;
+  for (size_t k = 0; k < K; ++k) {
+    const size_t p = k * rows;
+    if (c.enc) WW_HIP(ctx, hipMemcpyAsync(c.enc + (p + r0) * S, d.enc + (p + r0) * S, (size_t)(r1 - r0) * S * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (c.logits) WW_HIP(ctx, hipMemcpyAsync(c.logits + (p + r0) * NO, d.logits + (p + r0) * NO, (size_t)(r1 - r0) * NO * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (c.pf) WW_HIP(ctx, hipMemcpyAsync(c.pf + (p + r0) * NO, d.pf + (p + r0) * NO, (size_t)(r1 - r0) * NO * 4, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (c.post) WW_HIP(ctx, hipMemcpyAsync(c.post, d.post, K * c.n_seq * NO * 4, hipMemcpyDeviceToHost, ctx->stream));
+  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return WW_OK;
+}
+
+extern "C" {
+
+int ww_set_wave_sequence_dev(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
+                             const int32_t *seq_model, int32_t pool_rows, float *d_enc, float *d_logits, float *d_post_frames, float *d_post) {
+  WW_GUARD_BEGIN
+  const set_seq_request c = {d_mel, total_rows, row_offs, n_seq, pool_rows, seq_model, n_seq < 0 ? 0 : n_seq, true, d_enc, d_logits, d_post_frames, d_post};
+  return set_wave_seq_dev(ctx, set, c, "ww_set_wave_sequence_dev");
+  WW_GUARD_END(ctx)
+}
+
+int ww_set_wave_sequence(ww_ctx *ctx, const ww_model_set *set, const float *mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
+                         const int32_t *seq_model, int32_t pool_rows, float *enc, float *logits, float *post_frames, float *post) {
+  WW_GUARD_BEGIN
+  const set_seq_request c = {mel, total_rows, row_offs, n_seq, pool_rows, seq_model, n_seq < 0 ? 0 : n_seq, true, enc, logits, post_frames, post};
+  return set_wave_seq_host(ctx, set, c, "ww_set_wave_sequence");
+  WW_GUARD_END(ctx)
+}
+
+int ww_set_wave_sequence_all_dev(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
+                                 int32_t pool_rows, const int32_t *members, int32_t n_members, float *d_enc, float *d_logits, float *d_post_frames,
+                                 float *d_post) {
+  WW_GUARD_BEGIN
+  const set_seq_request c = {d_mel, total_rows, row_offs, n_seq, pool_rows, members, n_members, false, d_enc, d_logits, d_post_frames, d_post};
+  return set_wave_seq_dev(ctx, set, c, "ww_set_wave_sequence_all_dev");
+  WW_GUARD_END(ctx)
+}
+
+int ww_set_wave_sequence_all(ww_ctx *ctx, const ww_model_set *set, const float *mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
+                             int32_t pool_rows, const int32_t *members, int32_t n_members, float *enc, float *logits, float *post_frames, float *post) {
+  WW_GUARD_BEGIN
+  const set_seq_request c = {mel, total_rows, row_offs, n_seq, pool_rows, members, n_members, false, enc, logits, post_frames, post};
+  return set_wave_seq_host(ctx, set, c, "ww_set_wave_sequence_all");
   WW_GUARD_END(ctx)
 }
 

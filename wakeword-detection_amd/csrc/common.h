@@ -96,6 +96,8 @@ struct ww_model_set {
 // The SET = false instantiations take the same (empty) argument and never look at it.
 // The sliding form's kernels (crnn_rows_kernel, gru_tail_kernel, gru_tail16_kernel with SET = true) index ids by blockIdx.y - the
 // call's member slot, a grid dimension - and read the sizes of their member-major planes from aux (crnn.hip: WW_SLIDE_AUX_*).
+// The Wavenet's whole-sequence form (wavenet_seq_kernel<12, false, false, true>) indexes ids by blockIdx.y as well - the slot is the
+// output plane - unless aux is given: then aux[blockIdx.x] is the segment's sequence and ids holds one member per sequence.
 struct ww_set_ref {
   const int32_t *ids = nullptr;
   const int32_t *aux = nullptr;
@@ -267,10 +269,13 @@ bool ww_wave_tick_capable(const ww_model *m, int n_streams);
 int ww_k_wave_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, const ww_tick_tag &tag, const ww_set_ref *set = nullptr);
 // The fp32 Wavenet's sequence form (wavenet.hip: wavenet_seq_kernel) over launch_plan.h's segments (wv_seg).
 int ww_wave_receptive_field(const ww_model *m);  // 1 + 2 * sum of the dilations
-int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const wv_seg *d_segs, int n_segs, float *d_enc, float *d_logits);
-// rows = offs[n_seq] - offs[0] (the rows that belong to a sequence), row_end = offs[n_seq]
+// set (m: the set's view): segments x planes workgroups in ONE launch, enc / logits [planes][plane_rows][...]; the member of plane y is
+// set->ids[y], or - set->aux given, one plane - the member of segment x is set->ids[set->aux[x]] (launch_plan.h: seg_seq)
+int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const wv_seg *d_segs, int n_segs, float *d_enc, float *d_logits,
+                       const ww_set_ref *set = nullptr, int planes = 1, int64_t plane_rows = 0);
+// rows = offs[n_seq] - offs[0] (the rows that belong to a sequence), row_end = offs[n_seq]; planes of plane_rows rows: as above
 int ww_k_wave_pool(ww_ctx *ctx, const float *d_z, int64_t rows, int64_t row_end, int n_out, const int64_t *d_offs, int n_seq, int64_t pool_rows,
-                   int64_t max_len, float *d_a, float *d_b, float *d_pf, float *d_post);
+                   int64_t max_len, float *d_a, float *d_b, float *d_pf, float *d_post, int planes = 1, int64_t plane_rows = 0);
 #define WW_WAVE_STATE_BLOCK 256  // floats of carried state per block and stream: [4 channel groups][16 rows][4]
 // A causal bank's feed (streams.hip: ww_stream_feed) over launch_plan.h's tables (wv_feed_seg, wv_feed_pool):
 // segs[0, n_small): one-wave form (posteriors, ring and state inside the kernel); segs[n_small, n_segs): twelve-wave form, logits to

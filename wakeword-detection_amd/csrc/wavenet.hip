@@ -1060,6 +1060,7 @@ struct wave_seq_args {
   // FEED
   const wv_feed_seg *fsegs;     // [workgroups]
   float *post;                  // [rows of the call]: the posterior column of every new row (the one-wave form's tail)
+  // (SET, whole sequences - ww_set_wave_sequence*: enc / logits are [planes][a.wa.mel_rows][...], workgroup (x, y) writes plane y)
 };
 
 // A stream's ring of its last P logit rows [P][16] and zpos = {the slot of the next row, rows held (<= P)}: the slot of the row
@@ -1110,11 +1111,21 @@ __device__ __forceinline__ void wv_zpos_advance(int32_t *zpos, int sid, int pos,
   } while (0)
 
 // SET (a causal bank created from a model set): the member of the workgroup's stream, set.ids[sid].
+// SET, whole sequences (a set's ww_set_wave_sequence*): workgroup (x, y) is segment x into output plane y.  Its member is
+// set.ids[y] - every sequence by the call's slot y - or, where set.aux is given (one plane, gridDim.y = 1), set.ids[set.aux[x]]:
+// aux[x] is the sequence of segment x and ids holds one member per sequence.  The segment table is the single model's.
 template <int NW, bool STREAM, bool FEED = false, bool SET = false>
 __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(wave_args a, wave_seq_args q, ww_set_ref set) {
-  static_assert(!SET || STREAM || FEED, "the batch sequence form takes one model");
+  static_assert(!SET || STREAM || FEED || NW == 12, "whole sequences run the twelve-wave form");
   if constexpr (SET) {
-    const long long off = ww_set_offset(set, FEED ? q.fsegs[blockIdx.x].sid : q.win_aux[blockIdx.x] & 0xffff);
+    [[maybe_unused]] int slot = 0;
+    if constexpr (!STREAM && !FEED) {
+      const int plane = blockIdx.y;
+      slot = set.aux ? __builtin_amdgcn_readfirstlane(set.aux[blockIdx.x]) : plane;
+      if (q.enc) q.enc += (size_t)plane * a.wa.mel_rows * WV_S;  // (a plane has a row per row of the mel buffer)
+      if (q.logits) q.logits += (size_t)plane * a.wa.mel_rows * a.NOUT;
+    }
+    const long long off = ww_set_offset(set, FEED ? q.fsegs[blockIdx.x].sid : STREAM ? q.win_aux[blockIdx.x] & 0xffff : slot);
     wv_set_move_front(a, off);
     wv_set_move_blocks(a, off);
     wv_set_move_head(a, off);
@@ -1299,11 +1310,14 @@ __device__ __forceinline__ int64_t wv_row_in_seq(const int64_t *offs, int n_seq,
   return row - offs[lo];
 }
 
+// (blockIdx.y: the plane of a model set's call - `plane` floats each, the same sequences in every one; a single model's call has one)
 __global__ __launch_bounds__(256) void wave_pool_step_kernel(const float *in, float *out, int64_t rows, int NOUT, const int64_t *offs, int n_seq,
-                                                             int64_t step) {
+                                                             int64_t step, int64_t plane) {
   // (rows = [offs[0], offs[n_seq]): rows of the buffers in front of or behind the sequences are neither read nor written)
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= rows * NOUT) return;
+  in += blockIdx.y * plane;
+  out += blockIdx.y * plane;
   i += offs[0] * NOUT;
   const int64_t row = i / NOUT;
   float v = in[i];
@@ -1313,7 +1327,9 @@ __global__ __launch_bounds__(256) void wave_pool_step_kernel(const float *in, fl
 
 // sixteen lanes per row (lane c = column c): the last step of the pooled maximum and wavenet_kernel's softmax
 __global__ __launch_bounds__(256) void wave_pool_final_kernel(const float *M, int64_t rows, int NOUT, const int64_t *offs, int n_seq, int64_t back,
-                                                              float *pf) {
+                                                              float *pf, int64_t plane) {
+  M += blockIdx.y * plane;
+  pf += blockIdx.y * plane;
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t row = offs[0] + (g >> 4), rc = row < rows ? row : rows - 1;
   const int c = (int)(g & 15);
@@ -1323,9 +1339,11 @@ __global__ __launch_bounds__(256) void wave_pool_final_kernel(const float *M, in
   if (row < rows && c < NOUT) pf[row * NOUT + c] = p;
 }
 
-// one workgroup per sequence: softmax(max over all its rows) - what model(X) returns with timesteps=None
-__global__ __launch_bounds__(256) void wave_seq_post_kernel(const float *z, const int64_t *offs, int NOUT, float *post) {
+// one workgroup per sequence and plane: softmax(max over all its rows) - what model(X) returns with timesteps=None
+__global__ __launch_bounds__(256) void wave_seq_post_kernel(const float *z, const int64_t *offs, int NOUT, float *post, int64_t plane) {
   __shared__ float red[16][16];
+  z += blockIdx.y * plane;
+  post += (size_t)blockIdx.y * gridDim.x * NOUT;  // [planes][n_seq][NOUT]
   const int s = blockIdx.x, tid = threadIdx.x, c = tid & 15, g = tid >> 4;
   const int64_t r0 = offs[s], r1 = offs[s + 1];
   if (r1 <= r0) return;  // an empty sequence has no posterior: its row of `post` is left as it is
@@ -1427,13 +1445,22 @@ int ww_wave_receptive_field(const ww_model *m) {
   return rf;
 }
 
-int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const wv_seg *d_segs, int n_segs, float *d_enc, float *d_logits) {
-  if (n_segs <= 0) return WW_OK;
+int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const wv_seg *d_segs, int n_segs, float *d_enc, float *d_logits,
+                       const ww_set_ref *set, int planes, int64_t plane_rows) {
+  if (n_segs <= 0 || planes <= 0) return WW_OK;
   if (int rc = wave_seq_check(ctx, m, "ww_wave_sequence")) return rc;
   wave_args a;
   if (int rc = wave_model_args(ctx, m->wave, d_mel, a)) return rc;
   wave_seq_args q = {};
   q.segs = d_segs; q.enc = d_enc; q.logits = d_logits;
+  if (set) {  // m: the set's view.  ONE launch over segments x planes
+    if (planes > 65535 || (set->aux && planes != 1)) return ww_fail(ctx, WW_EINTERNAL, "ww_k_wave_sequence: %d planes in one launch", planes);
+    a.wa.mel_rows = plane_rows;
+    ww_launch_scope scope(ctx, "wavenet_seq_kernel<set>");
+    hipLaunchKernelGGL((wavenet_seq_kernel<12, false, false, true>), dim3(n_segs, planes), dim3(12 * 64), 0, ctx->stream, a, q, *set);
+    WW_HIP(ctx, hipGetLastError());
+    return WW_OK;
+  }
   ww_launch_scope scope(ctx, "wavenet_seq_kernel");
   hipLaunchKernelGGL((wavenet_seq_kernel<12, false>), dim3(n_segs), dim3(12 * 64), 0, ctx->stream, a, q, ww_set_ref{});
   WW_HIP(ctx, hipGetLastError());
@@ -1441,12 +1468,16 @@ int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const
 }
 
 // pool_rows: 0 = from row 0 of each sequence.  max_len: the longest sequence.  d_a / d_b: [rows][NOUT] floats of scratch each.
+// planes > 1 (a model set's call): d_z, d_a, d_b and d_pf are [planes][plane_rows][NOUT], d_post [planes][n_seq][NOUT] - the plane is
+// the grid's second dimension, so the launches are those of one plane.
 int ww_k_wave_pool(ww_ctx *ctx, const float *d_z, int64_t rows, int64_t row_end, int NOUT, const int64_t *d_offs, int n_seq, int64_t pool_rows,
-                   int64_t max_len, float *d_a, float *d_b, float *d_pf, float *d_post) {
-  if (rows <= 0 || n_seq <= 0) return WW_OK;  // rows: offs[n_seq] - offs[0], the rows that belong to a sequence
+                   int64_t max_len, float *d_a, float *d_b, float *d_pf, float *d_post, int planes, int64_t plane_rows) {
+  if (rows <= 0 || n_seq <= 0 || planes <= 0) return WW_OK;  // rows: offs[n_seq] - offs[0], the rows that belong to a sequence
+  if (planes > 65535) return ww_fail(ctx, WW_EINTERNAL, "ww_k_wave_pool: %d planes in one launch", planes);
+  const int64_t plane = plane_rows * NOUT;
   if (d_post) {
     ww_launch_scope scope(ctx, "wave_seq_post_kernel");
-    hipLaunchKernelGGL(wave_seq_post_kernel, dim3(n_seq), dim3(256), 0, ctx->stream, d_z, d_offs, NOUT, d_post);
+    hipLaunchKernelGGL(wave_seq_post_kernel, dim3(n_seq, planes), dim3(256), 0, ctx->stream, d_z, d_offs, NOUT, d_post, plane);
     WW_HIP(ctx, hipGetLastError());
   }
   if (!d_pf) return WW_OK;
@@ -1457,11 +1488,11 @@ int ww_k_wave_pool(ww_ctx *ctx, const float *d_z, int64_t rows, int64_t row_end,
   const unsigned g1 = (unsigned)((rows * NOUT + 255) / 256);
   while (span * 2 <= P) {
     float *nxt = cur == d_a ? d_b : d_a;
-    hipLaunchKernelGGL(wave_pool_step_kernel, dim3(g1), dim3(256), 0, ctx->stream, cur, nxt, rows, NOUT, d_offs, n_seq, span);
+    hipLaunchKernelGGL(wave_pool_step_kernel, dim3(g1, planes), dim3(256), 0, ctx->stream, cur, nxt, rows, NOUT, d_offs, n_seq, span, plane);
     cur = nxt;
     span *= 2;
   }
-  hipLaunchKernelGGL(wave_pool_final_kernel, dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, ctx->stream, cur, row_end, NOUT, d_offs, n_seq, P - span, d_pf);
+  hipLaunchKernelGGL(wave_pool_final_kernel, dim3((unsigned)((rows * 16 + 255) / 256), planes), dim3(256), 0, ctx->stream, cur, row_end, NOUT, d_offs, n_seq, P - span, d_pf, plane);
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
 }

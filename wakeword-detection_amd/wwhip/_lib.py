@@ -107,6 +107,10 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_set_option": (C.c_int, [_vp, C.c_int, _i64]),
     "ww_wave_sequence_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ww_wave_sequence": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ww_set_wave_sequence_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "ww_set_wave_sequence": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "ww_set_wave_sequence_all_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "ww_set_wave_sequence_all": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "ww_clips_forward_dev": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _P(FrontendParams), _vp]),
     "ww_stream_create": (C.c_int, [_vp, _vp, _i32, _P(FrontendParams), C.c_uint32, _P(_vp)]),
     "ww_stream_create_set": (C.c_int, [_vp, _vp, _i32, _vp, _P(FrontendParams), C.c_uint32, _P(_vp)]),

@@ -231,21 +231,8 @@ class Engine:
         maximum over the last ``pool`` rows; ``pool=None``: the model's window, ``0``: from row 0) and ``"post"`` (``[n_out]``:
         softmax of the maximum over the whole sequence).  Returns ``{name: list of arrays, one per sequence}``; an empty
         sequence's ``post`` is NaN."""
-        if isinstance(mels, np.ndarray) and mels.ndim == 2:
-            mels = [mels]
-        want = tuple(want)
-        bad = [k for k in want if k not in self.SEQUENCE_OUTPUTS]
-        if bad:
-            raise ValueError(f"want must be drawn from {self.SEQUENCE_OUTPUTS}, got {bad}")
-        seqs = [np.ascontiguousarray(m, dtype=np.float32).reshape(-1, self.n_mel) if np.size(m) == 0 else np.ascontiguousarray(m, dtype=np.float32)
-                for m in mels]
-        for m in seqs:
-            if m.ndim != 2 or m.shape[1] != self.n_mel:
-                raise ValueError(f"every sequence must be [rows, {self.n_mel}]")
-        offs = np.zeros(len(seqs) + 1, np.int64)
-        np.cumsum([m.shape[0] for m in seqs], out=offs[1:])
+        want, seqs, offs, mel = _sequence_batch(mels, self.n_mel, want)
         total = int(offs[-1])
-        mel = np.concatenate(seqs) if seqs else np.zeros((0, self.n_mel), np.float32)
         pool = self.window if pool is None else int(pool)
         bufs = {"enc": np.empty((total, 32), np.float32) if "enc" in want else None,
                 "logits": np.empty((total, self.n_out), np.float32) if "logits" in want else None,
@@ -337,12 +324,32 @@ class Engine:
                                                     _lib.ptr(r0), _lib.ptr(nw), int(r0.size), int(hop), C.c_void_p(d_out_ptr)))
 
 
+def _sequence_batch(mels, n_mel: int, want):
+    """The arguments of a ``sequence_forward`` call, checked: ``(want, sequences, row offsets, the sequences back to back)``."""
+    if isinstance(mels, np.ndarray) and mels.ndim == 2:
+        mels = [mels]
+    want = tuple(want)
+    bad = [k for k in want if k not in Engine.SEQUENCE_OUTPUTS]
+    if bad:
+        raise ValueError(f"want must be drawn from {Engine.SEQUENCE_OUTPUTS}, got {bad}")
+    seqs = [np.ascontiguousarray(m, dtype=np.float32).reshape(-1, n_mel) if np.size(m) == 0 else np.ascontiguousarray(m, dtype=np.float32)
+            for m in mels]
+    for m in seqs:
+        if m.ndim != 2 or m.shape[1] != n_mel:
+            raise ValueError(f"every sequence must be [rows, {n_mel}]")
+    offs = np.zeros(len(seqs) + 1, np.int64)
+    np.cumsum([m.shape[0] for m in seqs], out=offs[1:])
+    mel = np.concatenate(seqs) if seqs else np.zeros((0, n_mel), np.float32)
+    return want, seqs, offs, mel
+
+
 def _member_ids(ids, n: int, n_models: int, what: str) -> np.ndarray:
     """``ids`` as the int32 table the library takes: ``n`` entries, each a member of a set of ``n_models`` (``ValueError`` otherwise:
     the library would refuse them too - ``WW_EINVAL`` - but a list of the wrong length it cannot see)."""
     a = np.asarray(ids)
     if a.ndim != 1 or a.size != n:
-        raise ValueError(f"{what} must have one entry per {'stream' if what == 'models' else 'window'} ({n}), got shape {a.shape}")
+        per = {"models": "stream", "seq_model": "sequence"}.get(what, "window")
+        raise ValueError(f"{what} must have one entry per {per} ({n}), got shape {a.shape}")
     if a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() >= n_models):
         raise ValueError(f"{what} must be integers in [0, {n_models}): the set's members")
     return np.ascontiguousarray(a, dtype=np.int32)
@@ -469,8 +476,10 @@ class ModelSet:
 
     def set_option(self, key: str, value: int) -> None:
         """``ww_set_option``: ``"crnn_slide_min"`` / ``"crnn_tail_mfma"`` (:meth:`Engine.set_option`'s meanings) for the set's
-        sliding launches.  They move the launch form, never the bits."""
-        keys = {"crnn_slide_min": _lib.OPT_CRNN_SLIDE_MIN, "crnn_tail_mfma": _lib.OPT_CRNN_TAIL_MFMA}
+        sliding launches, ``"wave_seq_segment"`` (likewise) for the cuts of :meth:`sequence_forward` /
+        :meth:`sequence_forward_all`.  They move the launch form, never the bits."""
+        keys = {"crnn_slide_min": _lib.OPT_CRNN_SLIDE_MIN, "crnn_tail_mfma": _lib.OPT_CRNN_TAIL_MFMA,
+                "wave_seq_segment": _lib.OPT_WAVE_SEQ_SEGMENT}
         if key not in keys:
             raise ValueError(f"a model set takes the options {sorted(keys)}, not {key!r}")
         _lib.raise_for(self._lib.ww_set_option(self._set, keys[key], int(value)), self.ctx.handle)
@@ -507,6 +516,80 @@ class ModelSet:
                                                       _lib.ptr(out), C.byref(n)), self.ctx.handle)
         assert n.value == nw, (n.value, nw)
         return out
+
+    def _sequence_buffers(self, want, planes: Optional[int], total: int, n_seq: int) -> dict:
+        """Host outputs of a sequence call (``planes=None``: the one plane of the by-sequence form); ``post`` starts as NaN."""
+        lead = () if planes is None else (planes,)
+        shapes = {"enc": (total, 32), "logits": (total, self.n_out), "post_frames": (total, self.n_out), "post": (n_seq, self.n_out)}
+        return {k: (np.full(lead + shapes[k], np.nan, np.float32) if k == "post" else np.empty(lead + shapes[k], np.float32)) if k in want
+                else None for k in Engine.SEQUENCE_OUTPUTS}
+
+    @staticmethod
+    def _per_sequence(bufs: dict, want, offs: np.ndarray) -> dict:
+        n = offs.size - 1
+        return {k: [bufs[k][i] for i in range(n)] if k == "post" else [bufs[k][offs[i]:offs[i + 1]] for i in range(n)] for k in want}
+
+    def sequence_forward(self, mels, model_ids, pool: Optional[int] = None, want: Sequence[str] = ("post",)) -> dict:
+        """:meth:`Engine.sequence_forward` with sequence ``s`` evaluated by member ``model_ids[s]`` (``ww_set_wave_sequence``): one
+        upload, one launch of the model kernel over all sequences, whoever their members are.  Same arguments otherwise, the
+        same return shape, and for every sequence the bits its member's engine gives on it alone.  Wavenet sets only."""
+        want, seqs, offs, mel = _sequence_batch(mels, self.n_mel, want)
+        ids = _member_ids(model_ids, len(seqs), self.n_models, "seq_model")
+        total = int(offs[-1])
+        bufs = self._sequence_buffers(want, None, total, len(seqs))
+        _lib.raise_for(self._lib.ww_set_wave_sequence(self.ctx.handle, self._set, _lib.ptr(mel), total, _lib.ptr(offs), len(seqs), _lib.ptr(ids),
+                                                      self.window if pool is None else int(pool), _lib.ptr(bufs["enc"]),
+                                                      _lib.ptr(bufs["logits"]), _lib.ptr(bufs["post_frames"]), _lib.ptr(bufs["post"])),
+                       self.ctx.handle)
+        return self._per_sequence(bufs, want, offs)
+
+    def sequence_forward_all(self, mels, members=None, pool: Optional[int] = None, want: Sequence[str] = ("post",)) -> dict:
+        """Every sequence by every member of ``members`` (``None``: all, in order; any number of ids, duplicates allowed) over ONE
+        upload of the mel (``ww_set_wave_sequence_all``) - the checkpoint loop of the reference's ``eval_models`` on whole
+        recordings.  Returns ``{name: [per slot][per sequence]}``: entry ``[k]`` is what ``Engine(member members[k])
+        .sequence_forward(mels, pool, want)[name]`` returns, bit for bit."""
+        want, seqs, offs, mel = _sequence_batch(mels, self.n_mel, want)
+        ids = self._slots(members)
+        k = self.n_models if ids is None else int(ids.size)
+        total = int(offs[-1])
+        bufs = self._sequence_buffers(want, k, total, len(seqs))
+        _lib.raise_for(self._lib.ww_set_wave_sequence_all(self.ctx.handle, self._set, _lib.ptr(mel), total, _lib.ptr(offs), len(seqs),
+                                                          self.window if pool is None else int(pool), _lib.ptr(ids) if ids is not None else None,
+                                                          k if ids is not None else 0, _lib.ptr(bufs["enc"]), _lib.ptr(bufs["logits"]),
+                                                          _lib.ptr(bufs["post_frames"]), _lib.ptr(bufs["post"])), self.ctx.handle)
+        return {name: [self._per_sequence({name: bufs[name][j]}, (name,), offs)[name] for j in range(k)] for name in want}
+
+    @staticmethod
+    def _row_offs(row_offs) -> np.ndarray:
+        offs = np.ascontiguousarray(row_offs, dtype=np.int64)
+        if offs.ndim != 1 or offs.size < 1:
+            raise ValueError("row_offs must be a 1-D array of n_seq + 1 offsets")
+        return offs
+
+    def wave_sequence_dev(self, d_mel_ptr: int, total_rows: int, row_offs: np.ndarray, model_ids, pool: Optional[int] = None,
+                          d_enc_ptr: int = 0, d_logits_ptr: int = 0, d_post_frames_ptr: int = 0, d_post_ptr: int = 0) -> None:
+        """:meth:`sequence_forward` on device buffers (``ww_set_wave_sequence_dev``): :meth:`Engine.wave_sequence_dev` with
+        sequence ``s`` by member ``model_ids[s]`` (a host array).  Enqueued on the context's stream, not waited for."""
+        offs = self._row_offs(row_offs)
+        ids = _member_ids(model_ids, int(offs.size - 1), self.n_models, "seq_model")
+        vp = lambda p: C.c_void_p(p) if p else None
+        _lib.raise_for(self._lib.ww_set_wave_sequence_dev(self.ctx.handle, self._set, vp(d_mel_ptr), int(total_rows), _lib.ptr(offs),
+                                                          int(offs.size - 1), _lib.ptr(ids), self.window if pool is None else int(pool),
+                                                          vp(d_enc_ptr), vp(d_logits_ptr), vp(d_post_frames_ptr), vp(d_post_ptr)), self.ctx.handle)
+
+    def wave_sequence_all_dev(self, d_mel_ptr: int, total_rows: int, row_offs: np.ndarray, members=None, pool: Optional[int] = None,
+                              d_enc_ptr: int = 0, d_logits_ptr: int = 0, d_post_frames_ptr: int = 0, d_post_ptr: int = 0) -> None:
+        """:meth:`sequence_forward_all` on device buffers (``ww_set_wave_sequence_all_dev``): plane ``k`` of every output -
+        ``[len(members), total_rows, ...]``, ``post`` ``[len(members), n_seq, n_out]`` - is member ``members[k]``'s.  Enqueued on
+        the context's stream, not waited for."""
+        offs = self._row_offs(row_offs)
+        ids = self._slots(members)
+        vp = lambda p: C.c_void_p(p) if p else None
+        _lib.raise_for(self._lib.ww_set_wave_sequence_all_dev(self.ctx.handle, self._set, vp(d_mel_ptr), int(total_rows), _lib.ptr(offs),
+                                                              int(offs.size - 1), self.window if pool is None else int(pool),
+                                                              _lib.ptr(ids) if ids is not None else None, int(ids.size) if ids is not None else 0,
+                                                              vp(d_enc_ptr), vp(d_logits_ptr), vp(d_post_frames_ptr), vp(d_post_ptr)),
+                       self.ctx.handle)
 
     def close(self) -> None:
         if self._set and not _lib.is_shutdown():
