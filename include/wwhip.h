@@ -470,6 +470,26 @@ int ww_stream_create(ww_ctx *ctx, const ww_model *model, int32_t n_streams, cons
 int ww_stream_create_set(ww_ctx *ctx, const ww_model_set *set, int32_t n_streams, const int32_t *stream_model,
                          const ww_frontend_params *fp, uint32_t flags, ww_streams **out);
 int ww_stream_set_model(ww_streams *st, const int32_t *ids, int32_t n, int32_t model);
+/* A bank that runs EVERY listed member of a set on EVERY stream (a device that listens for several wake words at once: one audio
+ * stream, K posteriors per 20 ms).  `members` is a HOST array of K = n_members member slots, 1 <= K <= 64, each checked as
+ * ww_stream_create_set's ids are; a member may be named more than once; NULL = every member of the set in order (n_members is then
+ * ignored).  Flags: 0, WW_STREAM_TWO_LAUNCH, WW_STREAM_SYNC_WAIT, and WW_STREAM_CAUSAL for a Wavenet set; WW_STREAM_FULL_RECOMPUTE
+ * and n_streams * K > 65535 are WW_EINVAL.  One front end per stream serves all K slots: a tick takes the frames of S streams once,
+ * and the bank keeps one sample ring and one mel history per stream and one model state per stream and slot.
+ * ww_stream_step_all is the bank's tick: frames, is_speech and n_post [S] exactly as ww_stream_step's; post is [S][K][2],
+ * post[s][j][k] = the posterior of member slot j for the tick's new row k (0 for k >= n_post[s]) - the bits a bank of that member
+ * alone yields on the same frames, flags and resets.  Forms: the incremental CRNN in one launch (default) and two, both waits; the
+ * Wavenet window bank (always two launches); WW_STREAM_CAUSAL by tick.
+ * ww_stream_members reads the list back: members (K entries; may be NULL) and *n_members = K; an ordinary bank: *n_members = 0.
+ * On such a bank ww_stream_reset (a stream's front end and all K model states), ww_stream_window, ww_stream_attach_resampler,
+ * ww_stream_attach_rates, ww_stream_set_rate, ww_stream_frame_samples, ww_stream_frame_layout, ww_stream_timeline and
+ * ww_stream_destroy work unchanged.  WW_EINVAL with the reason in ww_last_error, before any state moves: ww_stream_step,
+ * ww_stream_step_trigger, ww_pipeline_bank_step, ww_stream_set_model, ww_stream_feed and ww_stream_feed_rows on an every-member
+ * bank; ww_stream_step_all on any other bank. */
+int ww_stream_create_set_all(ww_ctx *ctx, const ww_model_set *set, int32_t n_streams, const int32_t *members, int32_t n_members,
+                             const ww_frontend_params *fp, uint32_t flags, ww_streams **out);
+int ww_stream_step_all(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post);
+int ww_stream_members(const ww_streams *st, int32_t *members, int32_t *n_members);
 int ww_stream_destroy(ww_streams *st);
 int ww_stream_step(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post);
 /* WakewordTrigger.reset (tflite.py:241-246) for the listed streams (ids NULL -> all). */

@@ -12,6 +12,11 @@
                                    clip, 12,544 per member), device-resident PCM: A = per member logmel_dev + forward_windows_dev +
                                    forward_segments_dev, B = one logmel_dev + the set's two calls; A and B alternate, medians and spread
                                    of each (profiles/model_set/slide_measured.txt)
+  model_set.py all [ticks=3000] [rounds=4] [rate=16000]
+                                   three CRNNs on each of 128 streams, polled one-launch tick, p50 / p99 us: A = the every-member bank
+                                   (StreamBank(set, 128, members="all")), B = the 384-stream bank with one member per stream and every
+                                   frame written three times (the workaround), C = three single-model banks ticked in turn; the sides
+                                   alternate inside the process, `rounds` rounds of `ticks` ticks (profiles/model_set/all_measured.txt)
 """
 import os, re, shutil, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -283,6 +288,60 @@ def slide(reps):
     print(f"B / A (medians): {np.median(tb) / np.median(ta):.3f}")
 
 
+def every(ticks, rounds, rate):
+    """A, B and C as the module's text says; B's timed region includes writing every frame three times, which is what its caller
+    has to do.  First the three sides' posteriors are compared once (same frames: same bits)."""
+    import numpy as np
+    from wwhip.engine import Engine, ModelSet, StreamBank
+    S, K, F = 128, len(CRNNS), rate // 50
+    rng = np.random.default_rng(5)
+    frames = np.clip(rng.normal(0, 2500, (16, S, F)), -32768, 32767).astype(np.int16)
+    speech, speech3 = np.ones(S, np.uint8), np.ones(S * K, np.uint8)
+    engines = [Engine(os.path.join(ASSETS, m)) for m in CRNNS]
+    ms = ModelSet(engines)
+    a = StreamBank(ms, S, members="all", sample_rate=rate)
+    b = StreamBank(ms, S * K, models=[v % K for v in range(S * K)], sample_rate=rate)
+    c = [StreamBank(e, S, sample_rate=rate) for e in engines]
+    thrice = np.empty((S, K, F), np.int16)
+
+    def step_a(f):
+        return a.step(f, speech)[0]
+
+    def step_b(f):
+        thrice[:] = f[:, None, :]  # stream s's frame to the three streams 3 s .. 3 s + 2
+        return b.step(thrice.reshape(S * K, F), speech3)[0].reshape(S, K, 2)
+
+    def step_c(f):
+        return np.stack([bank.step(f, speech)[0] for bank in c], axis=1)
+    sides = (("A every-member bank, 128 streams x 3", step_a), ("B 384-stream bank, frames x 3     ", step_b), ("C three banks of 128 in turn      ", step_c))
+    same = True
+    for t in range(200):
+        pa, pb, pc = (fn(frames[t % 16]) for _, fn in sides)
+        same = same and np.array_equal(pa, pb) and np.array_equal(pa, pc)
+    print(f"{rate} Hz, {S} streams, {K} CRNNs, one launch, polled; A, B and C give the same bits over 200 ticks: {same}", flush=True)
+    lat = {name: [] for name, _ in sides}
+    for r in range(rounds):
+        for name, fn in sides:  # the sides alternate inside the round
+            l = np.empty(ticks)
+            for t in range(ticks):
+                f = frames[t % 16]
+                t0 = time.perf_counter()
+                fn(f)
+                l[t] = time.perf_counter() - t0
+            lat[name].append(l)
+            print(f"round {r}  {name}  p50 {np.percentile(l, 50) * 1e6:6.1f} us  p99 {np.percentile(l, 99) * 1e6:6.1f} us", flush=True)
+    for name, _ in sides:
+        p50 = [np.percentile(l, 50) * 1e6 for l in lat[name]]
+        p99 = [np.percentile(l, 99) * 1e6 for l in lat[name]]
+        print(f"{name}  p50 median {np.median(p50):6.1f} us (range {min(p50):.1f} .. {max(p50):.1f})   p99 median {np.median(p99):6.1f} us "
+              f"(range {min(p99):.1f} .. {max(p99):.1f})   over {rounds} rounds of {ticks} ticks")
+    for bank in [a, b] + c:
+        tl = bank.timeline()
+        print("  timeline, mean us per phase:", " ".join(f"{k} {v:.1f}" for k, v in tl.items()), flush=True)
+        bank.close()
+    ms.close()
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else ""
     if what == "codeobj" and len(sys.argv) == 4:
@@ -295,5 +354,8 @@ if __name__ == "__main__":
         batch(int(sys.argv[2]) if len(sys.argv) > 2 else 200)
     elif what == "slide":
         slide(int(sys.argv[2]) if len(sys.argv) > 2 else 25)
+    elif what == "all":
+        arg = [int(v) for v in sys.argv[2:]] + [3000, 4, 16000][len(sys.argv) - 2:]
+        every(arg[0], max(arg[1], 4), arg[2])
     else:
         sys.exit(__doc__)

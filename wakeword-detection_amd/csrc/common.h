@@ -254,9 +254,10 @@ bool ww_crnn_stream_capable(const ww_model *m);
 int ww_k_crnn_stream_forward(ww_ctx *ctx, const ww_model *m, const float *d_hist, int64_t hist_rows, const int64_t *d_win_row,
                              const int32_t *d_win_valid, const int32_t *d_win_aux, float *d_gxc, int n_windows, float *d_out,
                              const ww_tick_tag *tag = nullptr, const ww_set_ref *set = nullptr);
-// one launch per tick: front end + incremental CRNN of all S streams (2 S workgroups); posteriors as tags only
+// one launch per tick: front end + incremental CRNN of all S streams (2 S workgroups); posteriors as tags only.  every_k > 0: every
+// stream runs every_k member slots (stream_all.h): 2 S every_k workgroups, set->ids and d_gxc by virtual stream, fe by physical
 int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, float *d_gxc, const ww_tick_tag &tag,
-                   const ww_set_ref *set = nullptr);
+                   const ww_set_ref *set = nullptr, int every_k = 0);
 // does a ww_k_crnn_forward launch of n explicit windows write the tags (the one-kernel forms do)?
 bool ww_crnn_forward_tags(const ww_model *m, int n_windows);
 size_t ww_wave_workspace(const ww_model *m, int n_windows);

@@ -957,8 +957,28 @@ static_assert(CT_BASE % 4 == 0 && CT_BASE + FE_TL_FLOATS <= CF_FEAT_FLOATS, "tic
 // posteriors go out as {value, tick number} pairs (ww_tick_tag) that the host polls.
 // SET (a bank created from a model set): the workgroup's member is set.ids[its stream] - FE != 0: stream blockIdx.x / 2; FE = 0: the
 // stream in the window's aux word.
-template <int FE, bool SET = false>
-__global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args sa, ww_set_ref set) {
+// ALL (FE != 0, SET: a bank that runs K member slots on every stream, stream_all.h): the grid is 2 S K, workgroup w is window
+// k = w & 1 of VIRTUAL stream v = w >> 1 = s K + slot.  The model side stays a function of v - the member set.ids[v], v's cache of
+// projected rows, tag slot w - and the front-end side reads PHYSICAL stream s = v / K (K: set.K, a kernel argument; s and slot are
+// scalars): the frames, the control words, ring[par], prev[par], the mel rows.  A stream now has 2 K workgroups and still exactly
+// ONE writer: the newest window's workgroup of slot 0 (fe_tick_decode).  Why the other 2 K - 1 need no order with it, whichever of
+// them runs first - a grid above what is resident at once starts siblings after their stream's writer has long finished:
+//   * every workgroup reads ring[par] and prev[par], last tick's copies; the writer stores ring[par ^ 1] and prev[par ^ 1] only.
+//     The copy a tick reads is written next by the NEXT tick's kernel, which the stream orders behind every workgroup of this one;
+//   * window k reads mel slots pos + k + 2 .. pos - 1 (mod T + 1) of the mirrored ring, T - k - 1 rows, and takes the tick's new
+//     rows from its own transforms.  The writer stores slots pos and pos + 1 (and their mirrors, T + 1 rows on): never a slot in
+//     that range, for k = 0 and k = 1 alike - the one spare slot of the ring;
+//   * the control words and frames are host memory that nobody writes during the tick;
+//   * what a workgroup writes besides is v's own: cache slot q0 + 128 (read by neither window of v this tick: they read q0 .. q0 +
+//     120 of a ring of 144) and tag slot w.
+// So no workgroup reads a word that another workgroup of the launch writes, and a sibling that starts late transforms the same
+// samples from the same copies: the same instructions on the same values as slot 0's, the same bits as a bank of that member alone.
+struct ww_set_all_ref : ww_set_ref {
+  int K = 1;  // member slots per stream
+};
+template <int FE, bool SET = false, bool ALL = false>
+__global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args sa, typename std::conditional<ALL, ww_set_all_ref, ww_set_ref>::type set) {
+  static_assert(!ALL || (SET && FE != 0), "the every-member form is a one-launch tick of a set bank");
   if constexpr (SET && FE != 0) cf_set_move(sa.f, ww_set_offset(set, blockIdx.x >> 1));
   const fused_args &a = sa.f;
   extern __shared__ __align__(16) float cf_smem[];
@@ -1043,7 +1063,12 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
   } else {
     typedef typename std::conditional<FE == 2, double, float>::type R;
     const ww_tick_fe &fe = sa.fe;
-    const int s = w >> 1, k = w & 1;
+    const int v = w >> 1, k = w & 1;  // the virtual stream (stream_all.h); an ordinary bank: the stream itself
+    int s = v, slot = 0;
+    if constexpr (ALL) {
+      s = __builtin_amdgcn_readfirstlane((int)((unsigned)v / (unsigned)set.K));
+      slot = v - s * set.K;
+    }
     // ---- over the bus, together: the tick's 320 samples (40 x 16 bytes) and the stream's control words
     uint4 raw = make_uint4(0u, 0u, 0u, 0u);
     if (tid < 40) raw = ((const uint4 *)(fe.frames + (size_t)s * WW_CHUNK))[tid];
@@ -1066,14 +1091,14 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
     load_conv_w();
     // ---- what this workgroup is (uniform over it)
     const int slots = a.T + 1;
-    const fe_tick_ctl c = fe_tick_decode(cw, k, slots);
+    const fe_tick_ctl c = fe_tick_decode(cw, k, slots, slot);
     if (c.idle) return;
     float4 stage[2];
     int sidx[2] = {-1, -1};
     if (c.window) {
       q0 = c.rowq + k + 1;  // rows since the reset incl. this window's newest, mod the cache ring
       q0 = q0 >= RA ? q0 - RA : q0;
-      cache = sa.gxc + (size_t)s * RA * (6 * H);
+      cache = sa.gxc + (size_t)v * RA * (6 * H);
       crow0 = cached(0); crow1 = cached(1); crow2 = cached(2);
       const float *src = a.mel + ((size_t)s * fe.HR + c.b) * CV_NMEL;
 #pragma unroll
@@ -2172,6 +2197,8 @@ int ww_k_crnn_init_device(ww_ctx *ctx) {
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
+  WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
+  WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CFB_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, CFB_SMEM_BYTES));
   return WW_OK;
@@ -2195,9 +2222,10 @@ static fused_args crnn_fused_args(const ww_crnn_dev &c, const float *mel, const 
 // streaming form (crnn_stream_kernel): standard geometry, fp32 contractions
 bool ww_crnn_stream_capable(const ww_model *m) { return m->kind == WW_KIND_CRNN && !m->crnn.generic; }
 
-// ONE launch per tick (crnn_stream_kernel<1 | 2>): 2 S workgroups, the posteriors as tags only
+// ONE launch per tick (crnn_stream_kernel<1 | 2>): 2 S workgroups, the posteriors as tags only.  every_k > 0 (a set bank that runs
+// every_k member slots on every stream): 2 S every_k workgroups of the ALL form, set->ids a table of S every_k members
 int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, float *d_gxc, const ww_tick_tag &tag,
-                   const ww_set_ref *set) {
+                   const ww_set_ref *set, int every_k) {
   const ww_crnn_dev &c = m->crnn;
   const ww_filter_dev &f = m->filt;
   if (c.generic || f.n_mel != CV_NMEL || fe.hop != 160)
@@ -2209,10 +2237,17 @@ int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int pre
   sa.gxc = d_gxc;
   sa.fe = fe;
   sa.fb = ww_fe_filt_of(f);
-  const int nwg = 2 * fe.S;
+  if (every_k < 0 || (every_k && !set) || (int64_t)fe.S * (every_k ? every_k : 1) > 65535)
+    return ww_fail(ctx, WW_EINVAL, "one-launch streaming tick: %d member slots on %d streams", every_k, fe.S);
+  const int nwg = 2 * fe.S * (every_k ? every_k : 1);
   {
     ww_launch_scope scope(ctx, "crnn_stream_kernel<tick>");
-    if (set && precise) hipLaunchKernelGGL((crnn_stream_kernel<2, true>), dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, *set);
+    if (every_k) {
+      ww_set_all_ref all;
+      all.ids = set->ids; all.aux = set->aux; all.stride = set->stride; all.K = every_k;
+      if (precise) hipLaunchKernelGGL((crnn_stream_kernel<2, true, true>), dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, all);
+      else hipLaunchKernelGGL((crnn_stream_kernel<1, true, true>), dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, all);
+    } else if (set && precise) hipLaunchKernelGGL((crnn_stream_kernel<2, true>), dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, *set);
     else if (set) hipLaunchKernelGGL((crnn_stream_kernel<1, true>), dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, *set);
     else if (precise) hipLaunchKernelGGL(crnn_stream_kernel<2>, dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, ww_set_ref{});
     else hipLaunchKernelGGL(crnn_stream_kernel<1>, dim3(nwg), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, ww_set_ref{});

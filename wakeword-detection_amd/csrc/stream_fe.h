@@ -92,22 +92,25 @@ __device__ __forceinline__ void fe_ring_store(float *hist, size_t row0, int p, i
 }
 
 // ---- the one-launch tick: what workgroup 2 s + k is (uniform over it) ----------------------------------------------------------------
+// A bank that runs K member slots on every stream (stream_all.h): workgroup 2 v + k, v = s K + slot, is window k of member slot `slot`
+// on stream s.  The 2 K workgroups of a stream read the same control words; the stream's state is written by slot 0's writer alone,
+// and a slot other than 0 that has no window has nothing to do at all.
 struct fe_tick_ctl {
   int fill, nf, pos, rowq;  // rowq: the CRNN's (rows since the reset, mod its cache ring)
   int par, np;
   bool idle;                // an active stream is not sampled at all (tflite.py:139-140) | the tick has no second window
-  bool window, writer;      // this workgroup evaluates a window | writes the stream's state (the tick's newest window, or none at all)
+  bool window, writer;      // this workgroup evaluates a window | writes the stream's state (the tick's newest window, or none at all; slot 0)
   int nfk;                  // window k ends at new frame k: it needs frames 0..k
   int b;                    // the T rows that end at new row k are the contiguous block from slot (pos + k + 2) % slots
 };
-__device__ __forceinline__ fe_tick_ctl fe_tick_decode(int4 cw, int k, int slots) {
+__device__ __forceinline__ fe_tick_ctl fe_tick_decode(int4 cw, int k, int slots, int slot = 0) {
   fe_tick_ctl c;
   c.fill = cw.x; c.nf = cw.y; c.pos = cw.w & 0xffff; c.rowq = cw.w >> 16;
   const int flags = cw.z;
   c.par = (flags >> 2) & 1;
   c.np = (flags & 1) ? c.nf : 0;  // frames are analysed only while the VAD says speech (tflite.py:166)
-  c.idle = (flags & 2) || k >= (c.np > 1 ? c.np : 1);
-  c.window = k < c.np; c.writer = k + 1 >= c.np;
+  c.idle = (flags & 2) || k >= (c.np > 1 || slot != 0 ? c.np : 1);
+  c.window = k < c.np; c.writer = k + 1 >= c.np && slot == 0;
   c.nfk = c.window ? k + 1 : 0;
   c.b = c.pos + k + 2;
   c.b = c.b >= slots ? c.b - slots : c.b;

@@ -26,6 +26,7 @@
 //   stream_feed_frontend_kernel  a causal bank fed any number of samples per stream (ww_stream_feed, further down): one workgroup
 //                           per 16 new frames of a stream, the same conversion and the same per-frame functions as above.
 #include "model_set.h"  // (in front of fft_device.h's macros)
+#include "stream_all.h"
 #include "stream_fe.h"
 
 #include <algorithm>
@@ -105,6 +106,19 @@ struct ww_streams {
   ww_stream_rates *rates = nullptr;
   int uniform_frame() const { return rates ? ww_k_rates_frame_samples(rates) : 0; }  // a uniform bank's frame samples; 0: not one
   bool used = false;                  // ticked or fed since creation
+  // a bank that runs K member slots on every stream (ww_stream_create_set_all; stream_all.h): the model side - stream_model and its
+  // device table, gxc, wstate, zring, zpos, h_tag, h_out, the window tables - is sized and indexed by VIRTUAL stream v = s K + slot,
+  // the front-end side - ring, prev, hist, the control words, the frames - by physical stream.  Every other bank: K = 1, v = s
+  int K = 1;
+  bool every = false;
+  std::vector<int32_t> members;       // [K] the member of each slot (an every-member bank)
+  int V() const { return S * K; }
+  // the reason this bank refuses `call` (stream_all.h: sa_check_call), where ww_last_error finds it; WW_OK: it does not
+  int check_call(const char *call, bool wants_every) const {
+    char why[320];
+    const int rc = sa_check_call(every, call, wants_every, why, sizeof why);
+    return rc ? ww_fail(ctx, rc, "%s", why) : WW_OK;
+  }
   // the kernels' extra argument: nullptr for a bank of one model
   const ww_set_ref *ref() const { return set ? &set_ref : nullptr; }
   int send_stream_model() {  // the host's copy -> the device table, in stream order (ww_tables::send, the one upload path)
@@ -331,6 +345,27 @@ __global__ void stream_reset_kernel(float *hist, const int32_t *ids, int S, int 
   }
 }
 
+// The reset's kernels for `count` streams (d_ids == nullptr: streams 0 .. count - 1).  A bank of K member slots per stream resets a
+// stream's front end once and its K model states: the mel history by physical id, then the caches by virtual id (d_vids: the count K
+// virtual streams of d_ids; nullptr with d_ids: all) - stream_reset_kernel with zero history rows touches the caches alone.
+static void stream_reset_launch(ww_streams *st, const int32_t *d_ids, const int32_t *d_vids, int count) {
+  ww_ctx *ctx = st->ctx;
+  const int K = st->K;
+  if (K == 1) {
+    hipLaunchKernelGGL(stream_reset_kernel, dim3(count), dim3(256), 0, ctx->stream, st->hist, d_ids, st->S, st->HR, st->F, st->gxc,
+                       (const float *)st->gx_zero, (const int32_t *)st->d_stream_model);
+  } else {
+    hipLaunchKernelGGL(stream_reset_kernel, dim3(count), dim3(256), 0, ctx->stream, st->hist, d_ids, st->S, st->HR, st->F, (float *)nullptr,
+                       (const float *)nullptr, (const int32_t *)nullptr);
+    if (st->gxc)
+      hipLaunchKernelGGL(stream_reset_kernel, dim3(count * K), dim3(256), 0, ctx->stream, st->hist, d_vids, st->V(), 0, st->F, st->gxc,
+                         (const float *)st->gx_zero, (const int32_t *)st->d_stream_model);
+  }
+  if (st->causal)
+    hipLaunchKernelGGL(stream_causal_reset_kernel, dim3(count * K), dim3(256), 0, ctx->stream, st->wstate, st->zpos, K == 1 ? d_ids : d_vids,
+                       st->V(), (int)st->model->wave.dil.size() * WW_WAVE_STATE_BLOCK);
+}
+
 extern "C" {
 
 int ww_stream_destroy(ww_streams *st) {
@@ -352,9 +387,10 @@ int ww_stream_destroy(ww_streams *st) {
 
 }  // extern "C"
 
-// ww_stream_create (set == nullptr) and ww_stream_create_set (model = the set's view; stream_model: checked by the caller, or nullptr)
+// ww_stream_create (set == nullptr), ww_stream_create_set (model = the set's view; stream_model: checked by the caller, or nullptr) and
+// ww_stream_create_set_all (every_k > 0: stream_model = the every_k member slots, checked by the caller, or nullptr)
 static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model_set *set, const int32_t *stream_model, int32_t S,
-                              const ww_frontend_params *fp, uint32_t flags, ww_streams **out) {
+                              const ww_frontend_params *fp, uint32_t flags, ww_streams **out, int every_k = 0) {
   if (flags & ~(uint32_t)(WW_STREAM_FULL_RECOMPUTE | WW_STREAM_TWO_LAUNCH | WW_STREAM_SYNC_WAIT | WW_STREAM_CAUSAL))
     return ww_fail(ctx, WW_EINVAL, "unknown stream flags 0x%x", flags);
   const bool causal = (flags & WW_STREAM_CAUSAL) != 0;
@@ -369,12 +405,19 @@ static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model
   ww_streams *st = new ww_streams();
   ww_scoped<ww_streams, ww_stream_destroy> own(st);  // (freed on every early return below)
   st->ctx = ctx; st->model = model; st->S = S; st->fp = *fp;
+  if (every_k) {
+    st->every = true;
+    st->K = every_k;
+    sa_member_table(stream_model, every_k, 1, st->members);
+  }
+  const int V = st->V();
   if (set) {
     st->set = set;
-    if (stream_model) st->stream_model.assign(stream_model, stream_model + S);
+    if (every_k) sa_member_table(stream_model, every_k, S, st->stream_model);
+    else if (stream_model) st->stream_model.assign(stream_model, stream_model + S);
     else st->stream_model.assign((size_t)S, 0);
-    if (hipMalloc((void **)&st->d_stream_model, ww_bump::need((size_t)S, 4)) != hipSuccess)
-      return ww_fail(ctx, WW_ENOMEM, "cannot allocate the model table of %d streams", S);
+    if (hipMalloc((void **)&st->d_stream_model, ww_bump::need((size_t)V, 4)) != hipSuccess)
+      return ww_fail(ctx, WW_ENOMEM, "cannot allocate the model table of %d streams", V);
     st->set_ref.ids = st->d_stream_model;
     st->set_ref.stride = (long long)set->stride;
   }
@@ -387,23 +430,24 @@ static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model
   // ONE launch per tick: the incremental CRNN at any size (tools/stream_forms.py: 7 % faster from 128 to 1,024 streams), the
   // Wavenet while a tick's windows stay within its twelve-wave form (ww_wave_tick_capable: up to 128 streams)
   st->causal = causal;  // (always the front-end kernel + one model kernel)
+  // (an every-member Wavenet bank always runs in two launches)
   st->one_launch = !causal && !(flags & WW_STREAM_TWO_LAUNCH) &&
-                   ((st->incremental && model->filt.n_mel == 40) || ww_wave_tick_capable(model, S));
+                   ((st->incremental && model->filt.n_mel == 40) || (!every_k && ww_wave_tick_capable(model, S)));
   // a borrowed stream is the caller's: when the call returns everything enqueued on it has completed, as before
   st->poll = ctx->own_stream && !(flags & WW_STREAM_SYNC_WAIT);
   // model scratch of the per-window kernels (explicit window rows: never the sliding form); the incremental CRNN needs none
   size_t ws_bytes = st->incremental ? 256
-                    : (model->kind == WW_KIND_CRNN ? ww_crnn_workspace(model, 2 * S, false) : ww_wave_workspace(model, 2 * S));
+                    : (model->kind == WW_KIND_CRNN ? ww_crnn_workspace(model, 2 * V, false) : ww_wave_workspace(model, 2 * V));
   bool ok = hipMalloc((void **)&st->ring, (size_t)2 * S * ST_RING * 4) == hipSuccess &&
             hipMalloc((void **)&st->hist, hist_elems * 4) == hipSuccess &&
             hipMalloc((void **)&st->prev, (size_t)2 * S * 4) == hipSuccess &&
             hipMalloc(&st->ws, ws_bytes) == hipSuccess && ((st->ws_bytes = ws_bytes), true) &&
-            hipHostMalloc((void **)&st->h_out, (size_t)2 * S * st->NO * 4) == hipSuccess &&
-            hipHostMalloc((void **)&st->h_tag, (size_t)2 * S * 8) == hipSuccess;
+            hipHostMalloc((void **)&st->h_out, (size_t)2 * V * st->NO * 4) == hipSuccess &&
+            hipHostMalloc((void **)&st->h_tag, (size_t)2 * V * 8) == hipSuccess;
   {
-    const size_t o_frames = 0, o_row = o_frames + (size_t)S * WW_CHUNK * 2, o_ctl = o_row + (size_t)2 * S * 8,
-                 o_valid = o_ctl + (size_t)S * 16, o_aux = o_valid + (size_t)2 * S * 4;
-    st->pack_bytes = o_aux + (size_t)2 * S * 4;
+    const size_t o_frames = 0, o_row = o_frames + (size_t)S * WW_CHUNK * 2, o_ctl = o_row + (size_t)2 * V * 8,
+                 o_valid = o_ctl + (size_t)S * 16, o_aux = o_valid + (size_t)2 * V * 4;
+    st->pack_bytes = o_aux + (size_t)2 * V * 4;
     st->pack_bytes = (st->pack_bytes + 255) & ~(size_t)255;
     ok = ok && hipMalloc((void **)&st->d_pack, st->pack_bytes) == hipSuccess &&
          hipHostMalloc((void **)&st->h_pack, 2 * st->pack_bytes) == hipSuccess;
@@ -418,7 +462,7 @@ static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model
   if (!ok) {
     return ww_fail(ctx, WW_ENOMEM, "cannot allocate state for %d streams", S);
   }
-  memset(st->h_tag, 0, (size_t)2 * S * 8);
+  memset(st->h_tag, 0, (size_t)2 * V * 8);
   if (hipHostGetDevicePointer((void **)&st->h_out_dev, st->h_out, 0) != hipSuccess ||
       hipHostGetDevicePointer((void **)&st->h_tag_dev, st->h_tag, 0) != hipSuccess ||
       hipHostGetDevicePointer((void **)&st->h_pack_dev, st->h_pack, 0) != hipSuccess) {
@@ -434,12 +478,12 @@ static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model
   st->pos.assign(S, 0);
   st->rowq.assign(S, 0);
   st->par.assign(S, 0);
-  st->expect.reserve((size_t)2 * S);
+  st->expect.reserve((size_t)2 * V);
   if (st->incremental) {
     const int K = set ? set->n : 1;  // gx_zero is a function of the weights: one row per member
-    if (hipMalloc((void **)&st->gxc, (size_t)S * WW_STREAM_GXC * 192 * 4) != hipSuccess ||
+    if (hipMalloc((void **)&st->gxc, (size_t)V * WW_STREAM_GXC * 192 * 4) != hipSuccess ||
         hipMalloc((void **)&st->gx_zero, (size_t)K * 192 * 4) != hipSuccess) {
-      return ww_fail(ctx, WW_ENOMEM, "cannot allocate the projected-row cache of %d streams", S);
+      return ww_fail(ctx, WW_ENOMEM, "cannot allocate the projected-row cache of %d streams", V);
     }
     // the row of an all-zero field: position 17 of one window over the (all-zero) history of stream 0, which the kernel
     // stores into slot (0 + 128) % ring of stream 0's cache.  A set: once per member, stream 0 lent to each in turn
@@ -447,7 +491,7 @@ static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model
     if (set) real.swap(st->stream_model);
     for (int k = 0; k < K; ++k) {
       if (set) {
-        st->stream_model.assign((size_t)S, k);
+        st->stream_model.assign((size_t)V, k);
         if (int rc = st->send_stream_model()) return rc;
       }
       hipMemsetAsync(st->gxc, 0, (size_t)WW_STREAM_GXC * 192 * 4, ctx->stream);
@@ -462,20 +506,19 @@ static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model
       st->stream_model.swap(real);
       if (int rc = st->send_stream_model()) return rc;
     }
-    hipLaunchKernelGGL(stream_reset_kernel, dim3(S), dim3(256), 0, ctx->stream, st->hist, (const int32_t *)nullptr, S, st->HR, st->F,
-                       st->gxc, (const float *)st->gx_zero, (const int32_t *)st->d_stream_model);
+    stream_reset_launch(st, nullptr, nullptr, S);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
       return ww_fail(ctx, WW_EHIP, "streaming CRNN set-up failed");
     }
   }
   if (causal) {
-    const size_t b_state = (size_t)S * (int)model->wave.dil.size() * WW_WAVE_STATE_BLOCK * 4, b_ring = (size_t)S * st->T * 16 * 4;
+    const size_t b_state = (size_t)V * (int)model->wave.dil.size() * WW_WAVE_STATE_BLOCK * 4, b_ring = (size_t)V * st->T * 16 * 4;
     if (hipMalloc((void **)&st->wstate, b_state) != hipSuccess || hipMalloc((void **)&st->zring, b_ring) != hipSuccess ||
-        hipMalloc((void **)&st->zpos, (size_t)S * 2 * 4) != hipSuccess)
-      return ww_fail(ctx, WW_ENOMEM, "cannot allocate the causal state of %d streams", S);
+        hipMalloc((void **)&st->zpos, (size_t)V * 2 * 4) != hipSuccess)
+      return ww_fail(ctx, WW_ENOMEM, "cannot allocate the causal state of %d streams", V);
     hipMemsetAsync(st->wstate, 0, b_state, ctx->stream);
     hipMemsetAsync(st->zring, 0, b_ring, ctx->stream);
-    hipMemsetAsync(st->zpos, 0, (size_t)S * 2 * 4, ctx->stream);
+    hipMemsetAsync(st->zpos, 0, (size_t)V * 2 * 4, ctx->stream);
     WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   if (set && !st->incremental) {  // (the incremental bank sent it above, behind its members' turns)
@@ -512,6 +555,23 @@ int ww_stream_create_set(ww_ctx *ctx, const ww_model_set *set, int32_t S, const 
     if (int rc = ww_set_check_ids(stream_model, S, set->n, "stream_model", why, sizeof why)) return ww_fail(ctx, rc, "ww_stream_create_set: %s", why);
   }
   return stream_create_impl(ctx, &set->view, set, stream_model, S, fp, flags, out);
+  WW_GUARD_END(ctx)
+}
+
+// Every listed member on every stream (include/wwhip.h; stream_all.h): the set bank of n_streams x n_members virtual streams
+int ww_stream_create_set_all(ww_ctx *ctx, const ww_model_set *set, int32_t S, const int32_t *members, int32_t n_members,
+                             const ww_frontend_params *fp, uint32_t flags, ww_streams **out) {
+  WW_GUARD_BEGIN
+  if (!ctx || !set || !fp || !out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (set->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "the model set belongs to another context");
+  if (!members) n_members = set->n;
+  char why[320];
+  if (int rc = sa_check_create(S, n_members, flags, why, sizeof why)) return ww_fail(ctx, rc, "ww_stream_create_set_all: %s", why);
+  if (set->view.kind == WW_KIND_CRNN && !ww_crnn_stream_capable(&set->view))
+    return ww_fail(ctx, WW_EINVAL, "a CRNN set streams through the incremental kernel: standard conv geometry only");
+  if (int rc = ww_set_check_ids(members, n_members, set->n, "members", why, sizeof why)) return ww_fail(ctx, rc, "ww_stream_create_set_all: %s", why);
+  return stream_create_impl(ctx, &set->view, set, members, S, fp, flags, out, n_members);
   WW_GUARD_END(ctx)
 }
 
@@ -611,6 +671,7 @@ int ww_stream_set_model(ww_streams *st, const int32_t *ids, int32_t n, int32_t m
   if (!st) return WW_EINVAL;
   ww_ctx *ctx = st->ctx;
   if (!st->set) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_model: this bank was not created from a model set");
+  if (int rc = st->check_call("ww_stream_set_model", false)) return rc;
   if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
   if (model < 0 || model >= st->set->n) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_model: model %d: the set has members 0..%d", (int)model, st->set->n - 1);
   if (ids && n < 0) return ww_fail(ctx, WW_EINVAL, "negative id count");
@@ -643,7 +704,7 @@ int ww_stream_reset(ww_streams *st, const int32_t *ids, int32_t n) {
   const int count = ids ? n : st->S;
   if (count == 0) return WW_OK;
   WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
-  int32_t *d_ids = nullptr;
+  int32_t *d_ids = nullptr, *d_vids = nullptr;
   if (ids) {
     for (int i = 0; i < n; ++i)
       if (ids[i] < 0 || ids[i] >= st->S) return ww_fail(ctx, WW_EINVAL, "stream id %d out of range", ids[i]);
@@ -652,12 +713,15 @@ int ww_stream_reset(ww_streams *st, const int32_t *ids, int32_t n) {
     memcpy(st->h_win_valid, ids, (size_t)n * 4);
     WW_HIP(ctx, hipMemcpyAsync(st->d_win_valid, st->h_win_valid, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     d_ids = st->d_win_valid;
+    if (st->K > 1) {  // the K virtual streams of each: staged in the aux table (2 S K ints as well)
+      std::vector<int32_t> vids;
+      sa_virtual_ids(ids, n, st->K, vids);
+      memcpy(st->h_win_aux, vids.data(), vids.size() * 4);
+      WW_HIP(ctx, hipMemcpyAsync(st->d_win_aux, st->h_win_aux, vids.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+      d_vids = st->d_win_aux;
+    }
   }
-  hipLaunchKernelGGL(stream_reset_kernel, dim3(count), dim3(256), 0, ctx->stream, st->hist, (const int32_t *)d_ids, st->S, st->HR, st->F,
-                     st->gxc, (const float *)st->gx_zero, (const int32_t *)st->d_stream_model);
-  if (st->causal)
-    hipLaunchKernelGGL(stream_causal_reset_kernel, dim3(count), dim3(256), 0, ctx->stream, st->wstate, st->zpos, (const int32_t *)d_ids, st->S,
-                       (int)st->model->wave.dil.size() * WW_WAVE_STATE_BLOCK);
+  stream_reset_launch(st, d_ids, d_vids, count);
   WW_HIP(ctx, hipGetLastError());
   WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // WakewordTrigger.reset (tflite.py:241-246): sample window emptied, frame window zeroed;
@@ -739,7 +803,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
   *mutated = true;  // from here on the host's mirrors of the streams' state advance
   st->used = true;
-  const int S = st->S, hop = st->fp.hop, R = st->T + 1;
+  const int S = st->S, hop = st->fp.hop;
   uint64_t tl[WW_STREAM_TL_PHASES + 1];
   tl[0] = st_now_ns();
   if (++st->seq == 0) st->seq = 1;  // (a tag of tick 0 is "never written")
@@ -749,51 +813,16 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   int16_t *h_frames = (int16_t *)((char *)st->h_frames + cp);
   int32_t *h_ctl = (int32_t *)((char *)st->h_ctl + cp);
   st->expect.clear();
-  int nw = 0, nw_c = 0;  // windows of the tick | causal: streams with new rows
-  for (int s = 0; s < S; ++s) {
-    const int flags = is_speech[s] & 3;
-    int nf = 0;
-    if (!(flags & 2)) {
-      nf = (int)ww_fe_frames(st->fill[s] + WW_CHUNK, hop);
-    }
-    const int np = (flags & 1) && !(flags & 2) ? nf : 0;
-    n_post[s] = np;
-    h_ctl[s * 4 + 0] = st->fill[s];
-    h_ctl[s * 4 + 1] = nf;
-    if (st->one_launch) {
-      // workgroup 2 s + k of the tick's one kernel finds everything else out by itself
-      h_ctl[s * 4 + 2] = flags | (st->par[s] << 2);
-      h_ctl[s * 4 + 3] = st->pos[s] | (st->rowq[s] << 16);
-      for (int k = 0; k < np; ++k) st->expect.push_back(2 * s + k);
-      if (!(flags & 2)) st->par[s] ^= 1;
-    } else if (st->causal) {
-      // every sampled row is analysed and advances the stream's state; bit 0 only decides whether its posterior is emitted.  One
-      // descriptor per stream with new rows: they are rows pos, pos + 1 of its mirrored ring (contiguous: pos + 1 <= R)
-      h_ctl[s * 4 + 2] = flags | 1;
-      h_ctl[s * 4 + 3] = st->pos[s];
-      if (nf) {
-        st->h_win_row[nw_c] = (int64_t)s * st->HR + st->pos[s];
-        st->h_win_valid[nw_c] = nf;
-        st->h_win_aux[nw_c] = s | ((np ? 1 : 0) << 16);
-        ++nw_c;
-      }
-      for (int k = 0; k < np; ++k) st->expect.push_back(2 * s + k);
-    } else {
-      h_ctl[s * 4 + 2] = flags;
-      h_ctl[s * 4 + 3] = st->pos[s];
-      for (int k = 0; k < np; ++k) {
-        // the T rows that end at this tick's new row k are the contiguous block that starts at (pos + k + 2) % R
-        st->h_win_row[nw + k] = (int64_t)s * st->HR + (st->pos[s] + k + 2) % R;
-        st->h_win_valid[nw + k] = st->T;
-        st->h_win_aux[nw + k] = s * WW_STREAM_GXC + (st->rowq[s] + k + 1) % WW_STREAM_GXC;  // rows since the reset incl. this window's newest
-        st->expect.push_back(nw + k);
-      }
-    }
-    nw += np;
-    if (!(flags & 2)) st->fill[s] = st->fill[s] + WW_CHUNK - nf * hop;
-    st->pos[s] = (st->pos[s] + (st->causal ? nf : np)) % R;
-    st->rowq[s] = (st->rowq[s] + np) % WW_STREAM_GXC;
-  }
+  // the tick's bookkeeping, control words, descriptors and tag slots: stream_all.h, per physical stream for its K virtual ones
+  sa_tick tk;
+  tk.S = S; tk.K = st->K; tk.T = st->T; tk.HR = st->HR;
+  tk.hop = hop; tk.chunk = WW_CHUNK; tk.window = WW_FFT_WINDOW; tk.gxc = WW_STREAM_GXC;
+  tk.form = st->one_launch ? SA_ONE_LAUNCH : st->causal ? SA_CAUSAL : SA_TABLE;
+  tk.fill = st->fill.data(); tk.pos = st->pos.data(); tk.rowq = st->rowq.data(); tk.par = st->par.data();
+  tk.ctl = h_ctl; tk.row = st->h_win_row; tk.valid = st->h_win_valid; tk.aux = st->h_win_aux;
+  tk.expect = &st->expect;
+  for (int s = 0; s < S; ++s) n_post[s] = sa_tick_stream(tk, s, is_speech[s]);
+  const int nw = tk.nw, nw_c = tk.nd;  // windows of the tick | causal: virtual streams with new rows
   tl[1] = st_now_ns();
   // a bank at other rates: its frames go through ww_k_rates_tick's kernel into a device block, and the tick reads that
   const int16_t *rate_frames = nullptr;
@@ -808,15 +837,16 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   const int pidx = st->NO == 1 ? 0 : 1;
   ww_tick_tag tag = {st->h_tag_dev, st->seq, pidx};
   bool tagged = false;
+  bool second = false;  // a second kernel was launched behind the tick's first
   if (st->one_launch) {
-    // ---- ONE launch: front end + model, workgroup 2 s + k = window k of stream s (crnn.hip: crnn_stream_kernel<FE>; wavenet.hip)
+    // ---- ONE launch: front end + model, workgroup 2 v + k = window k of (virtual) stream v (crnn.hip: crnn_stream_kernel<FE>; wavenet.hip)
     ww_tick_fe fe = {};
     fe.frames = rate_frames ? rate_frames : (const int16_t *)(st->h_pack_dev + ((char *)h_frames - st->h_pack));
     fe.ctl = (const int32_t *)(st->h_pack_dev + ((char *)h_ctl - st->h_pack));
     fe.ring = st->ring; fe.prev = st->prev; fe.hist = st->hist;
     fe.S = S; fe.HR = st->HR;
     fe.cv = ww_fe_pcm_of(st->fp); fe.hop = hop;
-    int rc = m->kind == WW_KIND_CRNN ? ww_k_crnn_tick(ctx, m, fe, st->fp.precise, st->gxc, tag, st->ref()) : ww_k_wave_tick(ctx, m, fe, st->fp.precise, tag, st->ref());
+    int rc = m->kind == WW_KIND_CRNN ? ww_k_crnn_tick(ctx, m, fe, st->fp.precise, st->gxc, tag, st->ref(), st->every ? st->K : 0) : ww_k_wave_tick(ctx, m, fe, st->fp.precise, tag, st->ref());
     if (rc) return rc;
     tagged = true;
     tl[3] = st_now_ns();
@@ -851,6 +881,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
       int rc = ww_k_wave_stream_tick(ctx, m, st->hist, st->d_win_row, st->d_win_valid, st->d_win_aux, nw_c, st->wstate, st->zring, st->zpos,
                                      st->h_out_dev, tagged ? &tag : nullptr, st->ref());
       if (rc) return rc;
+      second = nw_c > 0;
     } else if (nw && !st->incremental) {
       // the per-window kernels' scratch under the model's options of THIS tick (ww_model_set_option may have lowered the
       // front/tail threshold since the bank was created: the split form then wants nw x 19 x 192 floats)
@@ -860,7 +891,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
         WW_HIP(ctx, hipFree(st->ws));
         st->ws = nullptr;
         st->ws_bytes = 0;
-        const size_t want = m->kind == WW_KIND_CRNN ? ww_crnn_workspace(m, 2 * S, false) : ww_wave_workspace(m, 2 * S);
+        const size_t want = m->kind == WW_KIND_CRNN ? ww_crnn_workspace(m, 2 * st->V(), false) : ww_wave_workspace(m, 2 * st->V());
         if (hipMalloc(&st->ws, want > need ? want : need) != hipSuccess) return ww_fail(ctx, WW_ENOMEM, "cannot grow the model scratch of %d streams", S);
         st->ws_bytes = want > need ? want : need;
       }
@@ -882,9 +913,12 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
                    ? ww_k_crnn_forward(ctx, m, d_hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, 0, 0, 0, nw, st->ws, st->ws_bytes, st->h_out_dev, nullptr, tg)
                    : ww_k_wave_forward(ctx, m, d_hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, 0, 0, 0, nw, st->ws, st->ws_bytes, st->h_out_dev, nullptr, tg, wset);
       if (rc) return rc;
+      second = true;
     }
   }
-  tl[4] = st_now_ns();
+  // (include/wwhip.h: phase [3] is 0 where a tick is one launch - the one-launch forms, and a two-launch bank's tick without a window:
+  // no clock read of its own, which on a tick's first pass through this code measured the branches above, not a launch)
+  tl[4] = second ? st_now_ns() : tl[3];
   if (tagged && st->poll && nw) {
     int rc = st_poll_tags(st);
     if (rc) return rc;
@@ -892,28 +926,24 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   tl[5] = st_now_ns();
-  int w = 0;
-  for (int s = 0; s < S; ++s) {
-    post[s * 2] = 0.f;
-    post[s * 2 + 1] = 0.f;
-    for (int k = 0; k < n_post[s]; ++k, ++w) {
-      if (tagged) {
-        const unsigned bits = (unsigned)st->h_tag[st->one_launch || st->causal ? 2 * s + k : w];
-        memcpy(&post[s * 2 + k], &bits, 4);
-      } else {
-        post[s * 2 + k] = st->h_out[(size_t)(st->causal ? 2 * s + k : w) * st->NO + pidx];
-      }
-    }
-  }
+  // post[s][slot][k] from where it arrived (stream_all.h): a tag's low word, or the posterior column of a row of h_out
+  sa_scatter(tk.form, S, st->K, n_post, [&](int slot) -> float {
+    if (!tagged) return st->h_out[(size_t)slot * st->NO + pidx];
+    const unsigned bits = (unsigned)st->h_tag[slot];
+    float p;
+    memcpy(&p, &bits, 4);
+    return p;
+  }, post);
   tl[6] = st_now_ns();
   for (int i = 0; i < WW_STREAM_TL_PHASES; ++i) st->tl_ns[i] += tl[i + 1] - tl[i];
   ++st->tl_ticks;
   return WW_OK;
 }
 
-int ww_stream_step(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post) {
-  WW_GUARD_BEGIN
-  if (!st) return WW_EINVAL;
+// ww_stream_step and ww_stream_step_all: the refusals, then the one tick
+static int stream_step_entry(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post, const char *call,
+                             bool wants_every) {
+  if (int rc = st->check_call(call, wants_every)) return rc;
   // a tick that failed after the host's mirrors (fill, ring positions, state parity) had advanced leaves them out of step with
   // the device: the bank refuses further ticks instead of producing posteriors of a state that never existed
   if (st->broken) return ww_fail(st->ctx, WW_ESTATE, "this stream bank failed in an earlier tick: destroy it and create a new one");
@@ -921,6 +951,31 @@ int ww_stream_step(ww_streams *st, const int16_t *frames, const uint8_t *is_spee
   const int rc = stream_step_impl(st, frames, is_speech, post, n_post, &mutated);
   if (rc != WW_OK && mutated) st->broken = true;
   return rc;
+}
+
+int ww_stream_step(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  return stream_step_entry(st, frames, is_speech, post, n_post, "ww_stream_step", false);
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+// The tick of an every-member bank (include/wwhip.h): ww_stream_step's body, post [S][K][2]
+int ww_stream_step_all(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  return stream_step_entry(st, frames, is_speech, post, n_post, "ww_stream_step_all", true);
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+int ww_stream_members(const ww_streams *st, int32_t *members, int32_t *n_members) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  if (!n_members) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_members: NULL argument");
+  *n_members = st->every ? st->K : 0;
+  if (members)
+    for (int j = 0; st->every && j < st->K; ++j) members[j] = st->members[(size_t)j];
+  return WW_OK;
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
@@ -932,6 +987,7 @@ int ww_stream_step(ww_streams *st, const int16_t *frames, const uint8_t *is_spee
 static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs, const char *what,
                       std::vector<int64_t> *offs16 = nullptr) {
   ww_ctx *ctx = st->ctx;
+  if (int rc = st->check_call(what, false)) return rc;
   if (!st->causal) return ww_fail(ctx, WW_EINVAL, "%s: only a bank created with WW_STREAM_CAUSAL can be fed (a window bank recomputes a window per row)", what);
   if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
   if (n < 0) return ww_fail(ctx, WW_EINVAL, "%s: negative stream count", what);
@@ -1168,6 +1224,7 @@ int ww_stream_step_trigger(ww_streams *st, const int16_t *frames, const uint8_t 
   if (!st) return WW_EINVAL;
   if (!is_speech || !is_active || !was_speech || !posterior_max || !fired_ids || !n_fired || !fall_ids || !n_fall)
     return ww_fail(st->ctx, WW_EINVAL, "NULL argument");
+  if (int rc = st->check_call("ww_stream_step_trigger", false)) return rc;
   *n_fired = *n_fall = 0;
   st->stage_flags.resize((size_t)st->S);
   for (int s = 0; s < st->S; ++s) st->stage_flags[s] = (uint8_t)((is_speech[s] != 0) | ((is_active[s] != 0) << 1));
@@ -1184,6 +1241,7 @@ int ww_pipeline_bank_step(ww_streams *st, const int16_t *frames, ww_pipeline_sta
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
   if (!ps) return ww_fail(st->ctx, WW_EINVAL, "NULL state block");
+  if (int rc = st->check_call("ww_pipeline_bank_step", false)) return rc;  // (before the VAD stage moves)
   ps->n_vad_changed = ps->n_fired = ps->n_fall = ps->n_deact = 0;
   int rc = ww_vad_bank_step(st->S, ps->raw, ps->rise_frames, ps->fall_frames, ps->run_value, ps->run_length, ps->is_speech, &ps->n_vad_changed);
   if (rc) return ww_fail(st->ctx, rc, "ww_pipeline_bank_step: the VAD stage's arrays");

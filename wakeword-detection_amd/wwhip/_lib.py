@@ -115,6 +115,9 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_stream_create": (C.c_int, [_vp, _vp, _i32, _P(FrontendParams), C.c_uint32, _P(_vp)]),
     "ww_stream_create_set": (C.c_int, [_vp, _vp, _i32, _vp, _P(FrontendParams), C.c_uint32, _P(_vp)]),
     "ww_stream_set_model": (C.c_int, [_vp, _vp, _i32, _i32]),
+    "ww_stream_create_set_all": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(FrontendParams), C.c_uint32, _P(_vp)]),
+    "ww_stream_step_all": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ww_stream_members": (C.c_int, [_vp, _vp, _P(_i32)]),
     "ww_stream_destroy": (C.c_int, [_vp]),
     "ww_stream_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ww_stream_reset": (C.c_int, [_vp, _vp, _i32]),

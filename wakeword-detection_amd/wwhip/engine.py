@@ -607,6 +607,32 @@ class ModelSet:
 
 
 MAX_RATES = 8  # WW_STREAM_MAX_RATES
+MAX_MEMBER_SLOTS = 64  # WW_ALL_MAX_MEMBERS (csrc/stream_all.h)
+
+
+def _member_slots(members, engine, n_streams: int, models, full_recompute: bool) -> np.ndarray:
+    """``members=`` of a :class:`StreamBank` -> the ``int32[K]`` member slots.  Everything that can be refused without a device is
+    refused here."""
+    if not isinstance(engine, ModelSet):
+        raise ValueError("members= names members of a ModelSet: this bank is built on one Engine")
+    if models is not None:
+        raise ValueError("members= (every listed member on every stream) and models= (one member per stream) are mutually exclusive")
+    if full_recompute:
+        raise ValueError("full_recompute is not offered on a ModelSet")
+    if isinstance(members, str):
+        if members != "all":
+            raise ValueError(f"members must be \"all\" or a list of member ids, got {members!r}")
+        a = np.arange(engine.n_models, dtype=np.int32)
+    else:
+        a = np.asarray(members)
+        if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() >= engine.n_models:
+            raise ValueError(f"members must be a non-empty list of integers in [0, {engine.n_models}): the set's members")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+    if a.size > MAX_MEMBER_SLOTS:
+        raise ValueError(f"{a.size} member slots: a bank runs at most {MAX_MEMBER_SLOTS} on every stream")
+    if n_streams * a.size > 65535:
+        raise ValueError(f"{n_streams} streams x {a.size} member slots: a bank has at most 65535 of them")
+    return a
 
 
 def _stream_rates(sample_rate, n_streams: int, resampler) -> Tuple[np.ndarray, List[int]]:
@@ -633,10 +659,16 @@ def _stream_rates(sample_rate, n_streams: int, resampler) -> Tuple[np.ndarray, L
 class StreamBank:
     """S device-resident streams advanced 20 ms per :meth:`step` (``ww_stream_*``)."""
     _mixed = False  # per-stream rates (sample_rate given as a sequence)
+    members, n_members = None, 0  # the member slots of a bank that runs every listed member on every stream (members=)
+
+    def _no_every(self, what: str) -> None:
+        if self.n_members:
+            raise ValueError(f"{what}: this bank runs every listed member on every stream (members=): it has step, reset, window "
+                             "and set_rate only")
 
     def __init__(self, engine, n_streams: int, fp: Optional[_lib.FrontendParams] = None,
                  full_recompute: bool = False, two_launch: bool = False, sync_wait: bool = False, causal: bool = False,
-                 models: Optional[Sequence[int]] = None, sample_rate: int = 16000, resampler=None) -> None:
+                 models: Optional[Sequence[int]] = None, sample_rate: int = 16000, resampler=None, members=None) -> None:
         """``full_recompute``: every streaming CRNN window recomputed from its mel rows (``WW_STREAM_FULL_RECOMPUTE``)
         instead of the incremental kernel.  ``two_launch``: the incremental CRNN's tick as a front-end kernel + a model kernel
         (``WW_STREAM_TWO_LAUNCH``; default: ONE launch per tick).  ``sync_wait``: wait for a tick with ``hipStreamSynchronize``
@@ -656,9 +688,16 @@ class StreamBank:
         frames: ONE flat int16 block of ``frame_offs[S]`` samples, stream ``s``'s ``sample_rate[s] / 50`` samples from
         ``frame_offs[s]`` - or a sequence of S per-stream arrays, which is concatenated.  :meth:`feed` takes each stream's packet
         at that stream's rate, :meth:`set_rate` moves streams to another of the bank's rates.  The bank creates and owns one
-        ``Resampler(r, 16000, ctx)`` per distinct rate other than 16000."""
+        ``Resampler(r, 16000, ctx)`` per distinct rate other than 16000.
+        ``members="all"`` or a list of member ids of a :class:`ModelSet` (up to 64, repeats allowed; not together with ``models``):
+        EVERY listed member runs on EVERY stream (``ww_stream_create_set_all``) - one front end per stream, K = ``n_members`` model
+        states.  :meth:`step` takes the frames of S streams as always and returns ``(post[S, K, 2], n[S])``: ``post[s, j]`` is the
+        bits a bank of member ``members[j]`` alone yields.  :meth:`reset`, :meth:`window`, :meth:`set_rate` and ``sample_rate`` work
+        as before; :meth:`feed`, :meth:`set_model` and :meth:`step_trigger` raise ``ValueError``."""
         self.engine = engine
         self.S = int(n_streams)
+        self.members = None if members is None else _member_slots(members, engine, self.S, models, full_recompute)
+        self.n_members = 0 if self.members is None else int(self.members.size)
         if not isinstance(sample_rate, (int, np.integer)):
             rates, classes = _stream_rates(sample_rate, self.S, resampler)
             self._create(engine, fp, full_recompute, two_launch, sync_wait, causal, models)
@@ -700,7 +739,10 @@ class StreamBank:
         flags = ((_lib.STREAM_FULL_RECOMPUTE if full_recompute else 0) | (_lib.STREAM_TWO_LAUNCH if two_launch else 0)
                  | (_lib.STREAM_SYNC_WAIT if sync_wait else 0) | (_lib.STREAM_CAUSAL if causal else 0))
         self.causal = bool(causal)
-        if is_set:
+        if self.n_members:
+            _lib.raise_for(self._lib.ww_stream_create_set_all(engine.ctx.handle, engine.handle, self.S, _lib.ptr(self.members), self.n_members,
+                                                              C.byref(fp), flags, C.byref(h)), engine.ctx.handle)
+        elif is_set:
             _lib.raise_for(self._lib.ww_stream_create_set(engine.ctx.handle, engine.handle, self.S, _lib.ptr(ids), C.byref(fp), flags, C.byref(h)),
                            engine.ctx.handle)
         else:
@@ -733,12 +775,12 @@ class StreamBank:
         self.frame_samples, self.frame_offs, self.sample_rates = fs, fo, fs * 50
 
     def _tick_arrays(self) -> None:
-        self._post = np.zeros((self.S, 2), np.float32)
+        self._post = np.zeros((self.S, self.n_members, 2) if self.n_members else (self.S, 2), np.float32)
         self._n = np.zeros(self.S, np.int32)
         self._flags = np.zeros(self.S, np.uint8)
         # a tick is host-paced (spokestack/pipeline.py:25-28): the addresses of the bank's own arrays are taken once, not per call
         self._p_post, self._p_n, self._p_flags = (C.c_void_p(a.ctypes.data) for a in (self._post, self._n, self._flags))
-        self._step = self._lib.ww_stream_step
+        self._step = self._lib.ww_stream_step_all if self.n_members else self._lib.ww_stream_step
         self._keep = None
         if not self._mixed:
             self.sample_rates = np.full(self.S, self.sample_rate, np.int32)
@@ -778,6 +820,7 @@ class StreamBank:
         ``WakewordTrigger.__call__`` over its posteriors and the reset of the streams whose VAD bit fell.  Every argument but
         ``frames`` is an address taken once with ``_lib.addr`` (``WakewordBank`` owns the arrays): ``p_state`` =
         (was_speech, posterior_max, post, n_post, fired_ids, n_fired, fall_ids, n_fall)."""
+        self._no_every("step_trigger")
         rc = self._lib.ww_stream_step_trigger(self._h, self._frames_address(frames), p_is_speech, p_is_active, threshold, *p_state)
         if rc:
             _lib.raise_for(rc, self.engine.ctx.handle)
@@ -818,6 +861,7 @@ class StreamBank:
     def set_model(self, ids: Optional[Sequence[int]], model: int) -> None:
         """Move the listed streams (``None``: all) to member ``model`` of the bank's :class:`ModelSet` and reset them
         (``ww_stream_set_model``: a stream's cached activations belong to the model that made them)."""
+        self._no_every("set_model")
         if not isinstance(self.engine, ModelSet):
             raise ValueError("set_model: this bank was not built on a ModelSet")
         if not 0 <= int(model) < self.engine.n_models:
@@ -855,6 +899,7 @@ class StreamBank:
         of its new mel rows ``[rows]`` and, with ``want_mel``, the rows themselves ``[rows, n_mel]`` (``mels`` is ``None``
         otherwise).  However the samples are cut into packets, calls and :meth:`step` ticks, the results are the same bits.
         A bank at another rate, or with per-stream rates: each packet is at its stream's own rate."""
+        self._no_every("feed")
         a_ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
         n = int(a_ids.size)
         if len(packets) != n:

@@ -95,6 +95,10 @@ class SpeechPipelineBank(SpeechPipeline):
         reference's ``demo.py``), a tick is ONE library call (``ww_pipeline_bank_step``: the three stages' passes in stage order on
         the stages' own arrays) instead of three - the same flags, events and posteriors; ``False`` keeps the stage-by-stage loop."""
         from .context import ContextBank
+        for st in stages:
+            if getattr(st, "n_members", 0) or getattr(getattr(st, "_bank", None), "n_members", 0):
+                raise ValueError("SpeechPipelineBank: a bank that runs every listed member on every stream (members=) has no trigger "
+                                 "stage: step it directly")
         super().__init__(input_source, stages)
         self._context = ContextBank(n_streams)
         self._fused = self._bind_fused() if fused else None

@@ -114,6 +114,9 @@ class WakewordBank:
                 raise ValueError("WakewordBank needs model_dir (or bank=: a StreamBank built on an Engine of the caller's)")
             self._engine = engine_for(model_dir, device)
             bank = StreamBank(self._engine, self.S, frontend_params(32767.0, True, pre_emphasis, 160, True), causal=causal)
+        elif getattr(bank, "n_members", 0):
+            raise ValueError("WakewordBank: this bank runs every listed member on every stream (members=): the trigger stage has one "
+                             "posterior per stream and cannot say which wake word fired")
         self._bank = bank  # (anything with StreamBank's step_trigger / reset / close: the host-only tests pass a stub)
         self.threshold = float(posterior_threshold)
         self._on_wake = on_wake  # called with the ids of the streams that woke up this tick
