@@ -483,9 +483,11 @@ int ww_stream_set_model(ww_streams *st, const int32_t *ids, int32_t n, int32_t m
  * ww_stream_members reads the list back: members (K entries; may be NULL) and *n_members = K; an ordinary bank: *n_members = 0.
  * On such a bank ww_stream_reset (a stream's front end and all K model states), ww_stream_window, ww_stream_attach_resampler,
  * ww_stream_attach_rates, ww_stream_set_rate, ww_stream_frame_samples, ww_stream_frame_layout, ww_stream_timeline and
- * ww_stream_destroy work unchanged.  WW_EINVAL with the reason in ww_last_error, before any state moves: ww_stream_step,
- * ww_stream_step_trigger, ww_pipeline_bank_step, ww_stream_set_model, ww_stream_feed and ww_stream_feed_rows on an every-member
- * bank; ww_stream_step_all on any other bank. */
+ * ww_stream_destroy work unchanged; ww_stream_feed_all / ww_stream_feed_rows_all feed a WW_STREAM_CAUSAL bank of this kind in
+ * packets, and ww_stream_step_trigger_all is its wake-word stage (both further down).  WW_EINVAL with the reason in ww_last_error,
+ * before any state moves: ww_stream_step, ww_stream_step_trigger, ww_pipeline_bank_step, ww_stream_set_model, ww_stream_feed and
+ * ww_stream_feed_rows on an every-member bank; ww_stream_step_all, ww_stream_feed_all, ww_stream_feed_rows_all and
+ * ww_stream_step_trigger_all on any other bank. */
 int ww_stream_create_set_all(ww_ctx *ctx, const ww_model_set *set, int32_t n_streams, const int32_t *members, int32_t n_members,
                              const ww_frontend_params *fp, uint32_t flags, ww_streams **out);
 int ww_stream_step_all(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post);
@@ -520,6 +522,21 @@ int ww_stream_window(ww_streams *st, int32_t stream, float *out);
 int ww_stream_feed_rows(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs);
 int ww_stream_feed(ww_streams *st, const int32_t *ids, int32_t n, const int16_t *pcm, const int64_t *sample_offs, int64_t cap_rows,
                    int64_t *row_offs, float *post, float *mel);
+/* ww_stream_feed_all - ww_stream_feed on a bank created by ww_stream_create_set_all with WW_STREAM_CAUSAL (K member slots per
+ * stream): the same arguments and the same semantics, with
+ *   row_offs [n + 1]            counts MEL rows (not rows x K): stream ids[i]'s new rows are [row_offs[i], row_offs[i + 1])
+ *   post [row_offs[n]][K]       post[r][j] = the posterior of member slot j for new mel row r
+ *   mel  [row_offs[n]][n_mel]   written once per physical stream; may be NULL
+ * Slot j of stream s yields, bit for bit, what ww_stream_feed yields on an ordinary causal bank of member members[j] alone given the
+ * same packets, resets and ticks: a stream's samples may be cut into ww_stream_feed_all packets, calls and ww_stream_step_all ticks
+ * in any way.  The samples are uploaded and the front end runs once per stream whatever K is; each model segment runs once per slot.
+ * WW_EINVAL - before any state changes - for everything ww_stream_feed refuses, a bank that was not created by
+ * ww_stream_create_set_all, an every-member bank without WW_STREAM_CAUSAL, and a call of more than 2^30 posteriors (rows x K);
+ * WW_ESTATE, WW_ENOMEM and the broken-bank rule as ww_stream_feed's.  On any refusal row_offs, post and mel are left as they were.
+ * ww_stream_feed_rows_all writes the row_offs the same call would produce and touches no state. */
+int ww_stream_feed_rows_all(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs);
+int ww_stream_feed_all(ww_streams *st, const int32_t *ids, int32_t n, const int16_t *pcm, const int64_t *sample_offs, int64_t cap_rows,
+                       int64_t *row_offs, float *post, float *mel);
 /* ---- a stream bank at another input rate than 16 kHz ----------------------------------------------------------------------------
  * ww_stream_attach_resampler makes `st` a bank at r's input rate: ww_stream_step, ww_stream_step_trigger and ww_pipeline_bank_step
  * then read `frames` as [S][F] int16, F = rate_in / 50 (ww_stream_frame_samples: F, or 320 for a plain bank), and ww_stream_feed /
@@ -609,6 +626,30 @@ int ww_timeout_bank_step(int32_t n_streams, const uint8_t *is_speech, uint8_t *i
 int ww_stream_step_trigger(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, uint8_t *is_active, double threshold,
                            uint8_t *was_speech, float *posterior_max, float *post, int32_t *n_post, int32_t *fired_ids,
                            int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall);
+/* ww_trigger_bank_step_all - the trigger stage that says WHICH wake word fired: ww_trigger_bank_step's rule per stream with
+ * K = n_members member slots (1..64), over post[S][K][2] / n_post[S] as ww_stream_step_all delivers them.  thresholds [K]: slot j
+ * EXCEEDS on a row when (double)posterior > thresholds[j].  posterior_max [S][K] is the running maximum per slot, cleared for all K
+ * slots on the VAD falling edge.  A stream that is not active FIRES when any slot exceeds on any of the tick's rows: is_active[s] is
+ * set - once: a context has one flag - and entry i of three parallel lists of up to S entries is written:
+ *   fired_ids[i]   the stream
+ *   fired_mask[i]  bit j set when slot j exceeded on any row of the tick
+ *   fired_slot[i]  the winner: on the earliest row on which any slot exceeded, the exceeding slot with the greatest posterior; on
+ *                  equal posteriors the lowest slot
+ * A stream that is already active does not fire again (it is not listed; its maxima still move).  fall_ids as
+ * ww_trigger_bank_step's.  With K = 1 and thresholds[0] = t the call IS ww_trigger_bank_step(..., t, ...), bit for bit, with
+ * fired_slot all 0 and fired_mask all 1.  WW_EINVAL: NULL arguments, n_post outside 0..2, n_members outside 1..64.
+ * ww_stream_step_trigger_all - the wake-word stage of an every-member bank as ONE call: ww_stream_step_all with bit 0 =
+ * is_speech[s], bit 1 = is_active[s] as they stand before the tick, the rule above over its posteriors, ww_stream_reset of the
+ * streams whose VAD bit fell.  WW_EINVAL with the reason in ww_last_error on a bank that was not created by
+ * ww_stream_create_set_all. */
+int ww_trigger_bank_step_all(int32_t n_streams, int32_t n_members, const uint8_t *is_speech, uint8_t *is_active, const float *post,
+                             const int32_t *n_post, const double *thresholds, uint8_t *was_speech, float *posterior_max,
+                             int32_t *fired_ids, int32_t *fired_slot, uint64_t *fired_mask, int32_t *n_fired, int32_t *fall_ids,
+                             int32_t *n_fall);
+int ww_stream_step_trigger_all(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, uint8_t *is_active,
+                               const double *thresholds, uint8_t *was_speech, float *posterior_max, float *post, int32_t *n_post,
+                               int32_t *fired_ids, int32_t *fired_slot, uint64_t *fired_mask, int32_t *n_fired, int32_t *fall_ids,
+                               int32_t *n_fall);
 /* ww_pipeline_bank_step - ONE tick of the whole stage list of demo.py:29-36 for S streams (spokestack/pipeline.py:25-28: for stage in
  * stages: stage(context, frame)) as one call: ww_vad_bank_step, ww_stream_step_trigger, ww_timeout_bank_step in this order on the
  * arrays the state block points to (the caller owns them all; the block itself may be reused from tick to tick).  Equivalent to

@@ -17,9 +17,20 @@
                                    (StreamBank(set, 128, members="all")), B = the 384-stream bank with one member per stream and every
                                    frame written three times (the workaround), C = three single-model banks ticked in turn; the sides
                                    alternate inside the process, `rounds` rounds of `ticks` ticks (profiles/model_set/all_measured.txt)
+  model_set.py feed_all [rounds=4] [out=profiles/model_set/feed_all_measured.txt] [parent=build_variants/parent]
+                                   the feed of an every-member causal bank, written to `out` as well: (1) 128 streams x K in {2, 3}
+                                   Wavenet slots, a 10 s catch-up per stream and 20 ms packets, A = one feed_all against C = K
+                                   single-member causal banks fed in turn, alternated inside the process, p50 / p99 per round, and
+                                   where a call's device time goes (the context's profile); (2) `paths` below for this tree and for
+                                   the parent's tree under `parent` (its own build and Python package), alternated, a process each;
+                                   (3) the new instantiations' resources and the kernels whose text differs from the parent's
+  model_set.py paths [ticks=2000] [reps=12]
+                                   the paths that were there before: the 128-stream causal Wavenet tick (p50 / p99 us) and the
+                                   single-model feed of 128 x 10 s (p50 / p99 ms).  WWHIP_TREE=<another checkout> measures that tree
 """
 import os, re, shutil, subprocess, sys, tempfile, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.abspath(os.environ.get("WWHIP_TREE") or HERE)  # (WWHIP_TREE: `paths` on another checkout, built in place)
 sys.path[:0] = [ROOT, os.path.join(ROOT, "wakeword-detection_amd")]
 ASSETS = os.path.join(ROOT, "wakeword-detection_amd/assets/tf_lite_models")
 CRNNS = ["CRNN_nosilence", "CRNN_nosilence_enhanced", "CRNN_softmax"]
@@ -27,7 +38,7 @@ KERNELS = ("crnn_fused_kernel", "crnn_stream_kernel", "crnn_rows_kernel", "gru_t
            "wavenet_seq_kernel",
            # the rest of the library: the kernels a model set does not reach
            "crnn_fused_bf16_kernel", "gemm_nt_kernel", "crnn_detect_kernel", "conv_generic_kernel", "gru_generic_kernel",
-           "wave_feed_pool_kernel", "wave_feed_ring_kernel", "wave_pool_step_kernel", "wave_pool_final_kernel", "wave_seq_post_kernel",
+           "wave_feed_pool_kernel", "wave_feed_ring_kernel", "wave_feed_post_rows_kernel", "wave_pool_step_kernel", "wave_pool_final_kernel", "wave_seq_post_kernel",
            "iota_offs_kernel", "logmel_kernel", "logmel_rows_kernel", "stft_mag_kernel", "mel_only_kernel", "smooth_kernel", "sweep_kernel",
            "pick_kernel", "viterbi2_kernel", "stream_frontend_kernel", "stream_feed_frontend_kernel", "stream_causal_reset_kernel",
            "stream_reset_kernel", "resample_copy_kernel", "resample_decim_kernel", "resample_phase_kernel", "stream_rate_tick_kernel",
@@ -342,6 +353,158 @@ def every(ticks, rounds, rate):
     ms.close()
 
 
+WAVES = ["Wavenet", "Wavenet_alt"]
+
+
+def _noise(rng, n):
+    import numpy as np
+    return np.clip(rng.normal(0, 2500, n), -32768, 32767).astype(np.int16)
+
+
+def _spread(name, per_round, unit):
+    import numpy as np
+    p50 = [np.percentile(l, 50) for l in per_round]
+    p99 = [np.percentile(l, 99) for l in per_round]
+    return (f"{name}  p50 median {np.median(p50):9.3f} {unit} (range {min(p50):.3f} .. {max(p50):.3f})   p99 median {np.median(p99):9.3f} {unit} "
+            f"(range {min(p99):.3f} .. {max(p99):.3f})   over {len(per_round)} rounds of {len(per_round[0])} calls")
+
+
+def paths(ticks, reps, say=print):
+    """The causal paths the parent has as well: the 128-stream tick and the single-model feed of 128 x 10 s."""
+    import numpy as np
+    from wwhip.engine import Engine, StreamBank
+    S = 128
+    rng = np.random.default_rng(5)
+    eng = Engine(os.path.join(ASSETS, "Wavenet"))
+    frames = np.stack([_noise(rng, (S, 320)) for _ in range(16)])
+    speech = np.ones(S, np.uint8)
+    bank = StreamBank(eng, S, causal=True)
+    for t in range(200):
+        bank.step(frames[t % 16], speech)
+    lat = np.empty(ticks)
+    for t in range(ticks):
+        t0 = time.perf_counter()
+        bank.step(frames[t % 16], speech)
+        lat[t] = time.perf_counter() - t0
+    bank.close()
+    bank = StreamBank(eng, S, causal=True)
+    pk = [_noise(rng, 160000) for _ in range(S)]
+    ids = list(range(S))
+    for _ in range(2):
+        bank.feed(ids, pk)
+    fl = np.empty(reps)
+    for r in range(reps):
+        t0 = time.perf_counter()
+        bank.feed(ids, pk)
+        fl[r] = time.perf_counter() - t0
+    bank.close()
+    say(f"{os.path.relpath(ROOT, HERE)}: causal tick, 128 streams  p50 {np.percentile(lat, 50) * 1e6:6.1f} us  p99 {np.percentile(lat, 99) * 1e6:6.1f} us ({ticks} ticks)   "
+        f"feed 128 x 10 s  p50 {np.percentile(fl, 50) * 1e3:7.2f} ms  p99 {np.percentile(fl, 99) * 1e3:7.2f} ms ({reps} calls)")
+
+
+def feed_all(rounds, out_path, parent):
+    import numpy as np
+    from wwhip.engine import Engine, ModelSet, StreamBank
+    lines = []
+
+    def say(text=""):
+        print(text, flush=True)
+        lines.append(text)
+    S = 128
+    ids = list(range(S))
+    rng = np.random.default_rng(5)
+    engines = [Engine(os.path.join(ASSETS, m)) for m in WAVES]
+    ms = ModelSet(engines)
+    ctx = ms.ctx
+    work = (("10 s catch-up per stream (160,000 samples, 997 rows)", [_noise(rng, 160000) for _ in range(S)], 6, "ms", 1e3),
+            ("20 ms packets (320 samples, 2 rows)               ", [_noise(rng, 320) for _ in range(S)], 400, "us", 1e6))
+    say("== 1. one feed_all on the every-member causal bank (A) against K single-member causal banks fed in turn (C) ==")
+    say(f"{S} streams, fp32 Wavenet slots (members {WAVES}; K = 3 names member 0 twice), wall clock around StreamBank.feed_all / .feed as the "
+        "caller sees them (packing the packets into one block included, on both sides), the sides alternated inside one process")
+    for K in (2, 3):
+        members = [0, 1, 0][:K]
+        a = StreamBank(ms, S, causal=True, members=members)
+        c = [StreamBank(engines[m], S, causal=True) for m in members]
+        for name, pk, reps, unit, scale in work:
+            def side_a():
+                return a.feed_all(ids, pk)[0]
+
+            def side_c():
+                return [b.feed(ids, pk)[0] for b in c]
+            same = True
+            for _ in range(2):
+                pa, pc = side_a(), side_c()
+                same = same and all(np.array_equal(pa[i][:, j], pc[j][i]) for i in range(S) for j in range(K))
+            say(f"-- K = {K}, {name}: A and C give the same bits: {same}")
+            lat = {"A": [], "C": []}
+            for r in range(rounds):
+                for side, fn in (("A", side_a), ("C", side_c)):
+                    l = np.empty(reps)
+                    for i in range(reps):
+                        t0 = time.perf_counter()
+                        fn()
+                        l[i] = (time.perf_counter() - t0) * scale
+                    lat[side].append(l)
+                    say(f"round {r}  {side}  p50 {np.percentile(l, 50):9.3f} {unit}  p99 {np.percentile(l, 99):9.3f} {unit}")
+            for side in ("A", "C"):
+                say(_spread(side, lat[side], unit))
+            say(f"A / C (medians of the rounds' p50): {np.median([np.percentile(l, 50) for l in lat['A']]) / np.median([np.percentile(l, 50) for l in lat['C']]):.3f}")
+            # where a call's device time goes: event pairs around every launch (the context's profile), wall clock around the call
+            for side, fn in (("A", side_a), ("C", side_c)):
+                ctx.profile(True)
+                n = 3
+                t0 = time.perf_counter()
+                for _ in range(n):
+                    fn()
+                wall = (time.perf_counter() - t0) / n
+                prof = ctx.profile_read()
+                ctx.profile(False)
+                dev = sum(v["total_ms"] for v in prof.values()) / n
+                parts = "  ".join(f"{k} {v['total_ms'] / n * 1e3:.1f} us x{v['calls'] // n}" for k, v in sorted(prof.items()))
+                say(f"   {side} per call, profiled: wall {wall * 1e3:.3f} ms, kernels {dev:.3f} ms, rest (packing, tables, upload, copies back, host) "
+                    f"{wall * 1e3 - dev:.3f} ms | {parts}")
+        for b in [a] + c:
+            b.close()
+    ms.close()
+    for e in engines:
+        e.close()
+    say()
+    say("== 2. the parent's paths: this tree against the parent's, alternated, a process each (tools/model_set.py paths) ==")
+    tool = os.path.join(HERE, "tools", "model_set.py")
+    if os.path.isdir(os.path.join(parent, "wakeword-detection_amd", "wwhip")):
+        for pair in range(3):
+            for side, tree in (("parent", parent), ("new   ", HERE)):
+                env = dict(os.environ, WWHIP_TREE=tree)
+                env.pop("WWHIP_LIB", None)
+                r = subprocess.run([sys.executable, tool, "paths"], env=env, capture_output=True, text=True, timeout=300)
+                say(f"pair {pair} {side} " + (r.stdout.strip().splitlines()[-1] if r.returncode == 0 and r.stdout.strip() else f"FAILED ({r.returncode}): {r.stderr[-300:]}"))
+    else:
+        say(f"(no parent tree under {parent}: not measured)")
+    say()
+    say("== 3. code objects: the parent's library (A) against this tree's (B) ==")
+    plib = os.path.join(parent, "wakeword-detection_amd", "wwhip", "libwwhip.so")
+    kb = kernels_of(os.path.join(HERE, "wakeword-detection_amd", "wwhip", "libwwhip.so"))
+    ka = kernels_of(plib) if os.path.isfile(plib) else {}
+    for k in list(kb):
+        short = k[:-len(", false>")] + ">" if k.endswith(", false>") else None
+        if short and short in ka and short not in kb:
+            kb[short] = kb.pop(k)
+    new = sorted(k for k in kb if k not in ka)
+    differ = sorted(k for k in kb if k in ka and kb[k]["text"] != ka[k]["text"])
+    gone = sorted(k for k in ka if k not in kb)
+    say(f"{len(ka)} instantiations in A, {len(kb)} in B; in both with the same instruction text: {sum(1 for k in kb if k in ka) - len(differ)}; "
+        f"DIFFERENT text: {differ or 'none'}; only in A: {gone or 'none'}")
+    say("only in B (vgpr / agpr / sgpr / LDS bytes / scratch bytes / instructions; waves per SIMD by registers = 512 // (vgpr rounded up to 8; the count includes the agprs)):")
+    for k in new:
+        m = kb[k]
+        regs = -(-m.get("vgpr_count", 0) // 8) * 8
+        say(f"  {k}: {m.get('vgpr_count', 0)} / {m.get('agpr_count', 0)} / {m.get('sgpr_count', 0)} / {m.get('group_segment_fixed_size', 0)} / "
+            f"{m.get('private_segment_fixed_size', 0)} / {m['insts']}   -> {min(8, 512 // max(regs, 1))} waves per SIMD by registers")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else ""
     if what == "codeobj" and len(sys.argv) == 4:
@@ -354,6 +517,11 @@ if __name__ == "__main__":
         batch(int(sys.argv[2]) if len(sys.argv) > 2 else 200)
     elif what == "slide":
         slide(int(sys.argv[2]) if len(sys.argv) > 2 else 25)
+    elif what == "paths":
+        paths(int(sys.argv[2]) if len(sys.argv) > 2 else 2000, int(sys.argv[3]) if len(sys.argv) > 3 else 12)
+    elif what == "feed_all":
+        feed_all(max(int(sys.argv[2]) if len(sys.argv) > 2 else 4, 3), sys.argv[3] if len(sys.argv) > 3 else os.path.join(HERE, "profiles/model_set/feed_all_measured.txt"),
+                 sys.argv[4] if len(sys.argv) > 4 else os.path.join(HERE, "build_variants/parent"))
     elif what == "all":
         arg = [int(v) for v in sys.argv[2:]] + [3000, 4, 16000][len(sys.argv) - 2:]
         every(arg[0], max(arg[1], 4), arg[2])

@@ -283,7 +283,8 @@ int ww_k_wave_pool(ww_ctx *ctx, const float *d_z, int64_t rows, int64_t row_end,
 // d_z, then pool[n_pool] -> d_post and ring[n_ring] (one entry per such stream) -> the logit rings
 int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv_feed_seg *d_segs, int n_small, int n_segs,
                    const wv_feed_pool *d_pool, int n_pool, const wv_feed_pool *d_ring, int n_ring, float *d_z, float *d_state,
-                   float *d_zring, int32_t *d_zpos, int pidx, float *d_post, const ww_set_ref *set = nullptr);
+                   float *d_zring, int32_t *d_zpos, int pidx, float *d_post, const ww_set_ref *set = nullptr, int slots = 0,
+                   int64_t plane_rows = 0, float *d_post_rows = nullptr);
 int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, const int64_t *d_win_row, const int32_t *d_win_valid,
                           const int32_t *d_win_aux, int nw, float *d_state, float *d_zring, int32_t *d_zpos, float *d_out,
                           const ww_tick_tag *tag, const ww_set_ref *set = nullptr);

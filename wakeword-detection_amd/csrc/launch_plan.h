@@ -307,6 +307,22 @@ static inline void feed_make_plan(const int32_t *ids, int n, const int64_t *samp
   }
 }
 
+// The same plan for a bank of K member slots per stream (ww_stream_feed_all): streams, groups and segments stay the physical streams'
+// - the sequence kernel's every-member form runs a segment once per slot and finds the virtual stream itself.  The tail's kernels are
+// the single bank's, so their tables are written out per slot: slot j's entry names virtual stream sid K + j, and rows of plane j of
+// the logits and posteriors ([K][rows] rows: row0 + j rows), entry by entry in slot order.
+static inline void feed_plan_all(feed_plan &pl, int K, int64_t rows) {
+  auto per_slot = [&](std::vector<wv_feed_pool> &t) {
+    std::vector<wv_feed_pool> out;
+    out.reserve(t.size() * (size_t)K);
+    for (const wv_feed_pool &d : t)
+      for (int j = 0; j < K; ++j) out.push_back({d.row0 + (int64_t)j * rows, d.n, d.sid * K + j, d.k0, 0});
+    t.swap(out);
+  };
+  per_slot(pl.pool);
+  per_slot(pl.ringt);
+}
+
 // ---- the resampler (resample.hip) ------------------------------------------------------------------------------------------------
 #define RS_XCAP WW_RESAMPLE_MAX_SPAN  // floats of staged input per tile (48 KB: three workgroups per CU)
 #define RS_R 8                        // outputs per item, phase form

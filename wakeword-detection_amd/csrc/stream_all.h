@@ -68,12 +68,13 @@ static inline void sa_member_table(const int32_t *members, int K, int S, std::ve
 }
 
 // Which calls an every-member bank takes and which an ordinary bank takes.  `every` = the bank was created by
-// ww_stream_create_set_all; `call` = the entry point's name; `wants_every` = the call is ww_stream_step_all.  WW_OK, or WW_EINVAL
+// ww_stream_create_set_all; `call` = the entry point's name; `wants_every` = the call is one of that bank's own (ww_stream_step_all,
+// ww_stream_feed_all, ww_stream_feed_rows_all, ww_stream_step_trigger_all).  WW_OK, or WW_EINVAL
 // with the reason in err - looked at before any state moves.
 static inline int sa_check_call(bool every, const char *call, bool wants_every, char *err, size_t cap) {
   if (every && !wants_every)
     return sa_refuse(err, cap, "%s: this bank runs every listed member on every stream (ww_stream_create_set_all): its tick is ww_stream_step_all, "
-                     "and it has no feed, trigger stage or per-stream member", call);
+                     "its feed ww_stream_feed_all, its trigger stage ww_stream_step_trigger_all, and it has no per-stream member", call);
   if (!every && wants_every) return sa_refuse(err, cap, "%s: this bank was not created by ww_stream_create_set_all: its tick is ww_stream_step", call);
   return WW_OK;
 }
@@ -171,4 +172,72 @@ static inline void sa_virtual_ids(const int32_t *ids, int count, int K, std::vec
   out.resize((size_t)count * K);
   for (int i = 0; i < count; ++i)
     for (int j = 0; j < K; ++j) out[(size_t)i * K + j] = sa_virtual(ids ? ids[i] : i, K, j);
+}
+
+// ---- the trigger stage --------------------------------------------------------------------------------------------------------------
+// spokestack/wakeword/tflite.py:134-146 (VAD edge, reset on the fall) and :232-239 (running maximum, threshold, activation) over the
+// posteriors a tick delivered, per stream, with K member slots - the ONE statement of the rule: ww_trigger_bank_step and
+// ww_stream_step_trigger are its K = 1 case (one threshold, fired_slot and fired_mask not asked for).
+//   post [S][K][2], n_post [S] (0..2 rows of the tick), thresholds [K], posterior_max [S][K]
+//   - posterior_max[s][j] is slot j's running maximum; all K are cleared on the VAD falling edge (behind this tick's rows)
+//   - slot j EXCEEDS on a row when (double)p > thresholds[j]: the reference's float32 posterior against a Python float
+//   - a stream that is not active FIRES when any slot exceeds on any row: is_active[s] = 1, once, and entry i of the three lists:
+//     fired_ids[i] = s; fired_mask[i] bit j = slot j exceeded on some row of the tick; fired_slot[i] = the winner - on the earliest
+//     row on which any slot exceeded, the exceeding slot with the greatest posterior, the lowest slot among equals
+//   - a stream that is already active does not fire again (no entry); its maxima still move
+//   - fall_ids: the streams whose VAD bit fell (the caller resets them)
+// fired_slot / fired_mask may be nullptr (K = 1: they would be 0 and 1).  Arguments are the caller's to check.
+static inline void sa_trigger_update(int S, int K, const uint8_t *is_speech, uint8_t *is_active, const float *post, const int32_t *n_post,
+                                     const double *thresholds, uint8_t *was_speech, float *posterior_max, int32_t *fired_ids,
+                                     int32_t *fired_slot, uint64_t *fired_mask, int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall) {
+  int nf = 0, nl = 0;
+  for (int s = 0; s < S; ++s) {
+    const uint8_t sp = is_speech[s] != 0;
+    const bool fall = was_speech[s] && !sp;
+    was_speech[s] = sp;
+    const float *ps = post + (size_t)s * K * 2;
+    float *pm = posterior_max + (size_t)s * K;
+    uint64_t mask = 0;
+    int win = -1;
+    for (int k = 0; k < n_post[s]; ++k) {
+      int best = -1;
+      for (int j = 0; j < K; ++j) {
+        const float p = ps[j * 2 + k];
+        if (p > pm[j]) pm[j] = p;
+        if ((double)p > thresholds[j]) {
+          mask |= (uint64_t)1 << j;
+          if (best < 0 || p > ps[best * 2 + k]) best = j;
+        }
+      }
+      if (win < 0) win = best;
+    }
+    if (win >= 0 && !is_active[s]) {
+      is_active[s] = 1;
+      fired_ids[nf] = s;
+      if (fired_slot) fired_slot[nf] = win;
+      if (fired_mask) fired_mask[nf] = mask;
+      ++nf;
+    }
+    if (fall) {
+      for (int j = 0; j < K; ++j) pm[j] = 0.f;
+      fall_ids[nl++] = s;
+    }
+  }
+  *n_fired = nf;
+  *n_fall = nl;
+}
+
+// The arguments of ww_trigger_bank_step_all (include/wwhip.h): WW_OK, or WW_EINVAL with the reason in err
+static inline int sa_check_trigger(int64_t S, int64_t K, const void *is_speech, const void *is_active, const void *post, const int32_t *n_post,
+                                   const void *thresholds, const void *was_speech, const void *posterior_max, const void *fired_ids,
+                                   const void *fired_slot, const void *fired_mask, const void *n_fired, const void *fall_ids, const void *n_fall,
+                                   char *err, size_t cap) {
+  if (S < 0) return sa_refuse(err, cap, "stream count %lld out of range", (long long)S);
+  if (K < 1 || K > WW_ALL_MAX_MEMBERS) return sa_refuse(err, cap, "%lld member slots: the trigger stage takes 1..%d", (long long)K, WW_ALL_MAX_MEMBERS);
+  if (!n_fired || !n_fall || !thresholds) return sa_refuse(err, cap, "NULL argument");
+  if (S > 0 && (!is_speech || !is_active || !post || !n_post || !was_speech || !posterior_max || !fired_ids || !fired_slot || !fired_mask || !fall_ids))
+    return sa_refuse(err, cap, "NULL argument");
+  for (int64_t s = 0; s < S; ++s)
+    if (n_post[s] < 0 || n_post[s] > 2) return sa_refuse(err, cap, "n_post[%lld] = %d: a tick delivers 0..2 rows", (long long)s, (int)n_post[s]);
+  return WW_OK;
 }

@@ -984,17 +984,19 @@ int ww_stream_members(const ww_streams *st, int32_t *members, int32_t *n_members
 // fill' = tot - 160 rows.  Everything a refusal can depend on is looked at here, before any state moves.
 // A bank at other rates: k is what the packet's samples come to at 16 kHz (ww_k_rates_advance), and offs16 (n + 1 entries, from 0)
 // receives the sample_offs the rest of the feed then works with.
+// all: the call is an every-member bank's (ww_stream_feed_all, ww_stream_feed_rows_all) - row_offs counts mel rows all the same, and
+// a call's rows x K posteriors have the bound a call's rows have.
 static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs, const char *what,
-                      std::vector<int64_t> *offs16 = nullptr) {
+                      std::vector<int64_t> *offs16 = nullptr, bool all = false) {
   ww_ctx *ctx = st->ctx;
-  if (int rc = st->check_call(what, false)) return rc;
+  if (int rc = st->check_call(what, all)) return rc;
   if (!st->causal) return ww_fail(ctx, WW_EINVAL, "%s: only a bank created with WW_STREAM_CAUSAL can be fed (a window bank recomputes a window per row)", what);
   if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
   if (n < 0) return ww_fail(ctx, WW_EINVAL, "%s: negative stream count", what);
   if (!sample_offs || !row_offs || (n > 0 && !ids)) return ww_fail(ctx, WW_EINVAL, "%s: NULL argument", what);
   std::vector<uint8_t> seen((size_t)st->S, 0);
+  std::vector<int64_t> offs((size_t)n + 1, 0);  // row_offs is written once nothing can refuse the call any more
   int64_t rows = 0;
-  row_offs[0] = 0;
   if (offs16) offs16->assign((size_t)n + 1, 0);
   for (int i = 0; i < n; ++i) {
     const int s = ids[i];
@@ -1008,8 +1010,11 @@ static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64
     const int64_t r = ww_fe_frames(st->fill[s] + k, st->fp.hop);
     if (r > 0x3fffffff || rows + r > 0x3fffffff) return ww_fail(ctx, WW_EINVAL, "%s: more than 2^30 rows in one call", what);
     rows += r;
-    row_offs[i + 1] = rows;
+    if (all && rows * st->K > 0x3fffffff)
+      return ww_fail(ctx, WW_EINVAL, "%s: more than 2^30 posteriors (rows x %d member slots) in one call", what, st->K);
+    offs[(size_t)i + 1] = rows;
   }
+  memcpy(row_offs, offs.data(), offs.size() * 8);
   return WW_OK;
 }
 
@@ -1021,15 +1026,21 @@ int ww_stream_feed_rows(ww_streams *st, const int32_t *ids, int32_t n, const int
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
+// ww_stream_feed, and ww_stream_feed_all (all: a bank of K member slots per stream, stream_all.h).  The plan, the uploaded samples, the
+// front end and the host's mirrors are the PHYSICAL streams' and run once whatever K is; the model side - the sequence kernel's
+// every-member form, the tail's tables, the logits and posteriors - is the virtual streams' v = s K + slot.
 static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const int16_t *pcm, const int64_t *sample_offs, int64_t cap_rows,
-                            int64_t *row_offs, float *post, float *mel, bool *mutated) {
+                            int64_t *row_offs, float *post, float *mel, bool *mutated, bool all = false) {
   ww_ctx *ctx = st->ctx;
-  std::vector<int64_t> offs16;
-  if (int rc = feed_check(st, ids, n, sample_offs, row_offs, "ww_stream_feed", &offs16)) return rc;
-  const int64_t rows = row_offs[n], samples_in = n > 0 ? sample_offs[n] - sample_offs[0] : 0;
-  if (cap_rows < rows) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: the call produces %lld rows, the buffers hold %lld", (long long)rows, (long long)cap_rows);
-  if (samples_in > 0 && !pcm) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: NULL sample buffer");
-  if (rows > 0 && !post) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: NULL posterior buffer");
+  const char *what = all ? "ww_stream_feed_all" : "ww_stream_feed";
+  std::vector<int64_t> offs16, offs_out((size_t)(n > 0 ? n : 0) + 1, 0);
+  // (the caller's row_offs is written when no refusal is left)
+  if (int rc = feed_check(st, ids, n, sample_offs, sample_offs && row_offs ? offs_out.data() : nullptr, what, &offs16, all)) return rc;
+  const int64_t rows = offs_out[(size_t)n], samples_in = n > 0 ? sample_offs[n] - sample_offs[0] : 0;
+  if (cap_rows < rows) return ww_fail(ctx, WW_EINVAL, "%s: the call produces %lld rows, the buffers hold %lld", what, (long long)rows, (long long)cap_rows);
+  if (samples_in > 0 && !pcm) return ww_fail(ctx, WW_EINVAL, "%s: NULL sample buffer", what);
+  if (rows > 0 && !post) return ww_fail(ctx, WW_EINVAL, "%s: NULL posterior buffer", what);
+  memcpy(row_offs, offs_out.data(), offs_out.size() * 8);
   if (samples_in == 0) return WW_OK;  // nothing arrived: no stream moves
   st->used = true;
   // a bank at other rates: from here on the packets are their 16 kHz samples, which ww_k_rates_feed leaves on the device
@@ -1038,21 +1049,25 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
   const int64_t samples = sample_offs[n] - sample_offs[0];
   const ww_model *m = st->model;
   const int T = st->T, F = st->F, NO = st->NO, R = T + 1, hop = st->fp.hop, rf = ww_wave_receptive_field(m);
-  if ((size_t)(WW_FEED_POOL_ROWS + T - 1) * 64 > 64 * 1024) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: windows of up to %d rows only", 1024 - WW_FEED_POOL_ROWS + 1);
+  const int K = st->K;  // (1 unless `all`)
+  if ((size_t)(WW_FEED_POOL_ROWS + T - 1) * 64 > 64 * 1024) return ww_fail(ctx, WW_EINVAL, "%s: windows of up to %d rows only", what, 1024 - WW_FEED_POOL_ROWS + 1);
   WW_ON_DEVICE(ctx, dev_scope);
   feed_plan pl;  // launch_plan.h
   feed_make_plan(ids, n, sample_offs, row_offs, st->fill.data(), st->pos.data(), T, rf, m->opt_wave_seq_segment, pl);
+  if (all) feed_plan_all(pl, K, rows);
   const std::vector<feed_grp> &grp = pl.grp;
   const std::vector<wv_feed_seg> &small = pl.small, &large = pl.large;
-  if (grp.size() > 0x7fffffffu || small.size() + large.size() > 0x7fffffffu) return ww_fail(ctx, WW_EINVAL, "ww_stream_feed: too much work for one call");
+  if (grp.size() > 0x7fffffffu || small.size() + large.size() > 0x7fffffffu || pl.pool.size() > 0x7fffffffu)
+    return ww_fail(ctx, WW_EINVAL, "%s: too much work for one call", what);
   // ---- the call's scratch: [tables | samples | mel rows | logits | posteriors] in the context's workspace
   ww_tables tb;
   const size_t o_str = tb.add(pl.str), o_grp = tb.add(grp), o_seg = tb.add(small);
   tb.join(large);  // one table: the one-wave form's segments, then the twelve-wave form's
   const size_t o_pool = tb.add(pl.pool), o_ring = tb.add(pl.ringt);
-  const size_t b_pcm = ww_bump::need((size_t)samples, 2), b_rows = ww_bump::need((size_t)rows * F, 4), b_z = ww_bump::need((size_t)rows * NO, 4),
-               b_post = ww_bump::need((size_t)rows, 4);
-  if (int rc = ww_ensure(ctx, ctx->dev, tb.bytes() + b_pcm + b_rows + (large.empty() ? 0 : b_z) + b_post + 1024, false)) return rc;
+  // (logits and posteriors: K planes of `rows` rows; an every-member call's posteriors once more as the caller's [rows][K])
+  const size_t b_pcm = ww_bump::need((size_t)samples, 2), b_rows = ww_bump::need((size_t)rows * F, 4), b_z = ww_bump::need((size_t)rows * K * NO, 4),
+               b_post = ww_bump::need((size_t)rows * K, 4);
+  if (int rc = ww_ensure(ctx, ctx->dev, tb.bytes() + b_pcm + b_rows + (large.empty() ? 0 : b_z) + (all ? 2 : 1) * b_post + 1024, false)) return rc;
   ww_bump db(ctx->dev.ptr, ctx->dev.cap);
   char *d_tab = db.take<char>(tb.bytes());
   const feed_str *d_str = (const feed_str *)(d_tab + o_str);
@@ -1061,8 +1076,9 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
   const wv_feed_pool *d_pool = (const wv_feed_pool *)(d_tab + o_pool), *d_ringt = (const wv_feed_pool *)(d_tab + o_ring);
   int16_t *d_pcm = db.take<int16_t>((size_t)samples);
   float *d_rows = db.take<float>((size_t)rows * F);
-  float *d_z = large.empty() ? nullptr : db.take<float>((size_t)rows * NO);
-  float *d_post = db.take<float>((size_t)rows);
+  float *d_z = large.empty() ? nullptr : db.take<float>((size_t)rows * K * NO);
+  float *d_post = db.take<float>((size_t)rows * K);
+  float *d_post_rows = all ? db.take<float>((size_t)rows * K) : d_post;
   if (int rc = tb.send(ctx, d_tab)) return rc;
   if (st->rates) {  // (the bank's 16 kHz samples land in d_pcm itself)
     if (int rc = ww_k_rates_feed(st->rates, ids, n, pcm, in_offs, sample_offs, d_pcm, mutated)) return rc;
@@ -1096,9 +1112,9 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
   }
   const int pidx = NO == 1 ? 0 : 1;  // posterior element, as a tick's
   if (int rc = ww_k_wave_feed(ctx, m, d_rows, d_seg, (int)small.size(), (int)(small.size() + large.size()), d_pool, (int)pl.pool.size(), d_ringt,
-                              (int)pl.ringt.size(), d_z, st->wstate, st->zring, st->zpos, pidx, d_post, st->ref()))
+                              (int)pl.ringt.size(), d_z, st->wstate, st->zring, st->zpos, pidx, d_post, st->ref(), all ? K : 0, rows, all ? d_post_rows : nullptr))
     return rc;
-  if (rows > 0) WW_HIP(ctx, hipMemcpyAsync(post, d_post, (size_t)rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (rows > 0) WW_HIP(ctx, hipMemcpyAsync(post, d_post_rows, (size_t)rows * K * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (rows > 0 && mel) WW_HIP(ctx, hipMemcpyAsync(mel, d_rows, (size_t)rows * F * 4, hipMemcpyDeviceToHost, ctx->stream));
   WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return WW_OK;
@@ -1110,6 +1126,26 @@ int ww_stream_feed(ww_streams *st, const int32_t *ids, int32_t n, const int16_t 
   if (!st) return WW_EINVAL;
   bool mutated = false;
   const int rc = stream_feed_impl(st, ids, n, pcm, sample_offs, cap_rows, row_offs, post, mel, &mutated);
+  if (rc != WW_OK && mutated) st->broken = true;
+  return rc;
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+// The feed of an every-member causal bank (include/wwhip.h): ww_stream_feed_rows / ww_stream_feed with post [rows][K]
+int ww_stream_feed_rows_all(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  std::vector<int64_t> offs16;
+  return feed_check(st, ids, n, sample_offs, row_offs, "ww_stream_feed_rows_all", &offs16, true);
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+int ww_stream_feed_all(ww_streams *st, const int32_t *ids, int32_t n, const int16_t *pcm, const int64_t *sample_offs, int64_t cap_rows,
+                       int64_t *row_offs, float *post, float *mel) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  bool mutated = false;
+  const int rc = stream_feed_impl(st, ids, n, pcm, sample_offs, cap_rows, row_offs, post, mel, &mutated, true);
   if (rc != WW_OK && mutated) st->broken = true;
   return rc;
   WW_GUARD_END(st ? st->ctx : nullptr)
@@ -1147,33 +1183,12 @@ int ww_vad_bank_step(int32_t S, const uint8_t *raw, int32_t rise_frames, int32_t
 }
 
 // spokestack/wakeword/tflite.py:134-146 (VAD edge, reset on the fall) and :232-239 (running maximum, threshold, activation)
-// over the posteriors a tick delivered.  The comparison with the threshold is the reference's: a float32 posterior against a
-// Python float, i.e. in double.
+// over the posteriors a tick delivered: the one-slot case of stream_all.h's rule (sa_trigger_update), where it is stated.
 static void trigger_update(int S, const uint8_t *is_speech, uint8_t *is_active, const float *post, const int32_t *n_post,
                            double threshold, uint8_t *was_speech, float *posterior_max, int32_t *fired_ids, int32_t *n_fired,
                            int32_t *fall_ids, int32_t *n_fall) {
-  int nf = 0, nl = 0;
-  for (int s = 0; s < S; ++s) {
-    const uint8_t sp = is_speech[s] != 0;
-    const bool fall = was_speech[s] && !sp;
-    was_speech[s] = sp;
-    bool fire = false;
-    for (int k = 0; k < n_post[s]; ++k) {
-      const float p = post[s * 2 + k];
-      if (p > posterior_max[s]) posterior_max[s] = p;
-      if ((double)p > threshold) fire = true;
-    }
-    if (fire && !is_active[s]) {
-      is_active[s] = 1;
-      fired_ids[nf++] = s;
-    }
-    if (fall) {
-      posterior_max[s] = 0.f;
-      fall_ids[nl++] = s;
-    }
-  }
-  *n_fired = nf;
-  *n_fall = nl;
+  sa_trigger_update(S, 1, is_speech, is_active, post, n_post, &threshold, was_speech, posterior_max, fired_ids, nullptr, nullptr, n_fired,
+                    fall_ids, n_fall);
 }
 
 int ww_trigger_bank_step(int32_t S, const uint8_t *is_speech, uint8_t *is_active, const float *post, const int32_t *n_post,
@@ -1186,6 +1201,20 @@ int ww_trigger_bank_step(int32_t S, const uint8_t *is_speech, uint8_t *is_active
   for (int s = 0; s < S; ++s)
     if (n_post[s] < 0 || n_post[s] > 2) return WW_EINVAL;
   trigger_update(S, is_speech, is_active, post, n_post, threshold, was_speech, posterior_max, fired_ids, n_fired, fall_ids, n_fall);
+  return WW_OK;
+  WW_GUARD_END(nullptr)
+}
+
+// The trigger stage over K member slots per stream (include/wwhip.h; the rule: stream_all.h, sa_trigger_update)
+int ww_trigger_bank_step_all(int32_t S, int32_t K, const uint8_t *is_speech, uint8_t *is_active, const float *post, const int32_t *n_post,
+                             const double *thresholds, uint8_t *was_speech, float *posterior_max, int32_t *fired_ids, int32_t *fired_slot,
+                             uint64_t *fired_mask, int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall) {
+  WW_GUARD_BEGIN
+  if (sa_check_trigger(S, K, is_speech, is_active, post, n_post, thresholds, was_speech, posterior_max, fired_ids, fired_slot, fired_mask, n_fired,
+                       fall_ids, n_fall, nullptr, 0))
+    return WW_EINVAL;
+  sa_trigger_update(S, K, is_speech, is_active, post, n_post, thresholds, was_speech, posterior_max, fired_ids, fired_slot, fired_mask, n_fired,
+                    fall_ids, n_fall);
   return WW_OK;
   WW_GUARD_END(nullptr)
 }
@@ -1231,6 +1260,29 @@ int ww_stream_step_trigger(ww_streams *st, const int16_t *frames, const uint8_t 
   int rc = ww_stream_step(st, frames, st->stage_flags.data(), post, n_post);
   if (rc) return rc;
   trigger_update(st->S, is_speech, is_active, post, n_post, threshold, was_speech, posterior_max, fired_ids, n_fired, fall_ids, n_fall);
+  if (*n_fall) rc = ww_stream_reset(st, fall_ids, *n_fall);
+  return rc;
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+// The wake-word stage of an every-member bank as ONE call (include/wwhip.h): ww_stream_step_all with bit 0 = is_speech, bit 1 =
+// is_active as they stand BEFORE the tick, the K-slot rule over its posteriors, then ww_stream_reset of the streams whose VAD bit fell.
+int ww_stream_step_trigger_all(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, uint8_t *is_active, const double *thresholds,
+                               uint8_t *was_speech, float *posterior_max, float *post, int32_t *n_post, int32_t *fired_ids,
+                               int32_t *fired_slot, uint64_t *fired_mask, int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  if (!is_speech || !is_active || !thresholds || !was_speech || !posterior_max || !fired_ids || !fired_slot || !fired_mask || !n_fired || !fall_ids ||
+      !n_fall)
+    return ww_fail(st->ctx, WW_EINVAL, "NULL argument");
+  if (int rc = st->check_call("ww_stream_step_trigger_all", true)) return rc;
+  *n_fired = *n_fall = 0;
+  st->stage_flags.resize((size_t)st->S);
+  for (int s = 0; s < st->S; ++s) st->stage_flags[s] = (uint8_t)((is_speech[s] != 0) | ((is_active[s] != 0) << 1));
+  int rc = ww_stream_step_all(st, frames, st->stage_flags.data(), post, n_post);
+  if (rc) return rc;
+  sa_trigger_update(st->S, st->K, is_speech, is_active, post, n_post, thresholds, was_speech, posterior_max, fired_ids, fired_slot, fired_mask,
+                    n_fired, fall_ids, n_fall);
   if (*n_fall) rc = ww_stream_reset(st, fall_ids, *n_fall);
   return rc;
   WW_GUARD_END(st ? st->ctx : nullptr)

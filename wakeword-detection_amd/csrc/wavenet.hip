@@ -1114,10 +1114,24 @@ __device__ __forceinline__ void wv_zpos_advance(int32_t *zpos, int sid, int pos,
 // SET, whole sequences (a set's ww_set_wave_sequence*): workgroup (x, y) is segment x into output plane y.  Its member is
 // set.ids[y] - every sequence by the call's slot y - or, where set.aux is given (one plane, gridDim.y = 1), set.ids[set.aux[x]]:
 // aux[x] is the sequence of segment x and ids holds one member per sequence.  The segment table is the single model's.
-template <int NW, bool STREAM, bool FEED = false, bool SET = false>
+// ALL (a feed of an every-member bank, ww_stream_feed_all): workgroup (x, y) is segment x run by member slot y of gridDim.y.  The
+// segment table and the row buffer are the physical streams'; the workgroup's weights, history, logit ring and position are those of
+// VIRTUAL stream sid K + y, and its logits and posteriors go to plane y of q.logits / q.post ([K][a.wa.mel_rows][...]).  Slot and K
+// are the grid's, i.e. scalars: nothing is added to a lane's registers.
+template <int NW, bool STREAM, bool FEED = false, bool SET = false, bool ALL = false>
 __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(wave_args a, wave_seq_args q, ww_set_ref set) {
   static_assert(!SET || STREAM || FEED || NW == 12, "whole sequences run the twelve-wave form");
-  if constexpr (SET) {
+  static_assert(!ALL || (SET && FEED), "every member slot on a segment: the feed of a bank created from a model set");
+  if constexpr (ALL) {
+    const int slot = blockIdx.y, K = gridDim.y;
+    const int v = __builtin_amdgcn_readfirstlane(q.fsegs[blockIdx.x].sid) * K + slot;
+    if (q.logits) q.logits += (size_t)slot * a.wa.mel_rows * a.NOUT;
+    q.post += (size_t)slot * a.wa.mel_rows;
+    const long long off = ww_set_offset(set, v);
+    wv_set_move_front(a, off);
+    wv_set_move_blocks(a, off);
+    wv_set_move_head(a, off);
+  } else if constexpr (SET) {
     [[maybe_unused]] int slot = 0;
     if constexpr (!STREAM && !FEED) {
       const int plane = blockIdx.y;
@@ -1147,6 +1161,7 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 3 : 1) void wavenet_seq_kernel(
   if (FEED) {
     const wv_feed_seg sg = q.fsegs[w];
     row0 = sg.row0; n = sg.n; skipn = sg.skip; sid = sg.sid; fflags = sg.flags;
+    if constexpr (ALL) sid = __builtin_amdgcn_readfirstlane(sid) * (int)gridDim.y + (int)blockIdx.y;  // the virtual stream
   } else if (STREAM) {
     row0 = q.win_row[w];
     n = q.win_valid[w];
@@ -1516,22 +1531,39 @@ int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, c
   return WW_OK;
 }
 
+// [slots][rows] posteriors of a feed's every-member form -> the caller's [rows][slots]
+__global__ __launch_bounds__(256) void wave_feed_post_rows_kernel(const float *planes, int64_t rows, int slots, float *out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // element of out
+  if (i >= rows * slots) return;
+  const int64_t r = i / slots;
+  const int j = (int)(i - r * slots);
+  out[i] = planes[(int64_t)j * rows + r];
+}
+
 // A causal bank's feed (streams.hip: ww_stream_feed).  The forms by the rows a stream brought: up to WW_FEED_TILE_ROWS the one-wave
 // form, above the twelve-wave form with its tail as two small kernels; a call may launch both.
+// slots > 0 (ww_stream_feed_all; `set` given): every segment is run by `slots` workgroups, one per member slot - the segment table is
+// the physical streams', d_state / d_zring / d_zpos are the virtual streams', d_z and d_post hold `slots` planes of plane_rows rows
+// and the tail's tables name virtual streams and rows of those planes (launch_plan.h: feed_plan_all).  d_post_rows receives the
+// posteriors as [plane_rows][slots].
 int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv_feed_seg *d_segs, int n_small, int n_segs,
                    const wv_feed_pool *d_pool, int n_pool, const wv_feed_pool *d_ring, int n_ring, float *d_z, float *d_state,
-                   float *d_zring, int32_t *d_zpos, int pidx, float *d_post, const ww_set_ref *set) {
+                   float *d_zring, int32_t *d_zpos, int pidx, float *d_post, const ww_set_ref *set, int slots,
+                   int64_t plane_rows, float *d_post_rows) {
   if (n_segs <= 0) return WW_OK;
   if (int rc = wave_seq_check(ctx, m, "ww_stream_feed")) return rc;
+  if (slots && (!set || slots > 65535 || plane_rows <= 0 || !d_post_rows)) return ww_fail(ctx, WW_EINTERNAL, "ww_k_wave_feed: %d member slots", slots);
   wave_args a;
   if (int rc = wave_model_args(ctx, m->wave, d_rows, a)) return rc;
   a.tag = {nullptr, 0, pidx};
   wave_seq_args q = {};
   q.state = d_state; q.zring = d_zring; q.zpos = d_zpos; q.P = m->wave.T; q.post = d_post;
+  if (slots) a.wa.mel_rows = plane_rows;  // (the rows of a plane of d_z / d_post)
   if (n_small > 0) {
     q.fsegs = d_segs;
     ww_launch_scope scope(ctx, "wavenet_seq_kernel<feed,1>");
-    if (set) hipLaunchKernelGGL((wavenet_seq_kernel<1, false, true, true>), dim3(n_small), dim3(64), 0, ctx->stream, a, q, *set);
+    if (slots) hipLaunchKernelGGL((wavenet_seq_kernel<1, false, true, true, true>), dim3(n_small, slots), dim3(64), 0, ctx->stream, a, q, *set);
+    else if (set) hipLaunchKernelGGL((wavenet_seq_kernel<1, false, true, true>), dim3(n_small), dim3(64), 0, ctx->stream, a, q, *set);
     else hipLaunchKernelGGL((wavenet_seq_kernel<1, false, true>), dim3(n_small), dim3(64), 0, ctx->stream, a, q, ww_set_ref{});
     WW_HIP(ctx, hipGetLastError());
   }
@@ -1540,7 +1572,8 @@ int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv
     q.logits = d_z;
     {
       ww_launch_scope scope(ctx, "wavenet_seq_kernel<feed,12>");
-      if (set) hipLaunchKernelGGL((wavenet_seq_kernel<12, false, true, true>), dim3(n_segs - n_small), dim3(12 * 64), 0, ctx->stream, a, q, *set);
+      if (slots) hipLaunchKernelGGL((wavenet_seq_kernel<12, false, true, true, true>), dim3(n_segs - n_small, slots), dim3(12 * 64), 0, ctx->stream, a, q, *set);
+      else if (set) hipLaunchKernelGGL((wavenet_seq_kernel<12, false, true, true>), dim3(n_segs - n_small), dim3(12 * 64), 0, ctx->stream, a, q, *set);
       else hipLaunchKernelGGL((wavenet_seq_kernel<12, false, true>), dim3(n_segs - n_small), dim3(12 * 64), 0, ctx->stream, a, q, ww_set_ref{});
       WW_HIP(ctx, hipGetLastError());
     }
@@ -1550,6 +1583,12 @@ int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv
     hipLaunchKernelGGL(wave_feed_pool_kernel, dim3(n_pool), dim3(256), sm, ctx->stream, (const float *)d_z, d_pool, a.NOUT, q.P, pidx,
                        (const float *)d_zring, (const int32_t *)d_zpos, d_post);
     hipLaunchKernelGGL(wave_feed_ring_kernel, dim3(n_ring), dim3(256), 0, ctx->stream, (const float *)d_z, d_ring, a.NOUT, q.P, d_zring, d_zpos);
+    WW_HIP(ctx, hipGetLastError());
+  }
+  if (slots) {
+    ww_launch_scope scope(ctx, "wave_feed_post_rows_kernel");
+    hipLaunchKernelGGL(wave_feed_post_rows_kernel, dim3((unsigned)((plane_rows * slots + 255) / 256)), dim3(256), 0, ctx->stream, (const float *)d_post,
+                       plane_rows, slots, d_post_rows);
     WW_HIP(ctx, hipGetLastError());
   }
   return WW_OK;

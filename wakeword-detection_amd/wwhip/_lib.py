@@ -129,11 +129,15 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_stream_set_rate": (C.c_int, [_vp, _vp, _i32, _i32]),
     "ww_stream_feed_rows": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     "ww_stream_feed": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ww_stream_feed_rows_all": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    "ww_stream_feed_all": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "ww_stream_timeline": (C.c_int, [_vp, _vp, _P(_i64), _i32]),
     "ww_vad_bank_step": (C.c_int, [_i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ww_trigger_bank_step": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ww_timeout_bank_step": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp]),
     "ww_stream_step_trigger": (C.c_int, [_vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ww_trigger_bank_step_all": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ww_stream_step_trigger_all": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ww_pipeline_bank_step": (C.c_int, [_vp, _vp, _P(PipelineState)]),
     "ww_superframe_smooth": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp]),
     "ww_far_frr": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),

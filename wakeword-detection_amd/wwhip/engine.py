@@ -663,8 +663,8 @@ class StreamBank:
 
     def _no_every(self, what: str) -> None:
         if self.n_members:
-            raise ValueError(f"{what}: this bank runs every listed member on every stream (members=): it has step, reset, window "
-                             "and set_rate only")
+            raise ValueError(f"{what}: this bank runs every listed member on every stream (members=): it has step, feed_all, "
+                             "step_trigger_all, reset, window and set_rate")
 
     def __init__(self, engine, n_streams: int, fp: Optional[_lib.FrontendParams] = None,
                  full_recompute: bool = False, two_launch: bool = False, sync_wait: bool = False, causal: bool = False,
@@ -693,7 +693,8 @@ class StreamBank:
         EVERY listed member runs on EVERY stream (``ww_stream_create_set_all``) - one front end per stream, K = ``n_members`` model
         states.  :meth:`step` takes the frames of S streams as always and returns ``(post[S, K, 2], n[S])``: ``post[s, j]`` is the
         bits a bank of member ``members[j]`` alone yields.  :meth:`reset`, :meth:`window`, :meth:`set_rate` and ``sample_rate`` work
-        as before; :meth:`feed`, :meth:`set_model` and :meth:`step_trigger` raise ``ValueError``."""
+        as before; a causal bank of this kind is fed in packets by :meth:`feed_all`, and :meth:`step_trigger_all` is its wake-word
+        stage (``wwhip.wakeword.WakewordSetBank``); :meth:`feed`, :meth:`set_model` and :meth:`step_trigger` raise ``ValueError``."""
         self.engine = engine
         self.S = int(n_streams)
         self.members = None if members is None else _member_slots(members, engine, self.S, models, full_recompute)
@@ -919,6 +920,43 @@ class StreamBank:
         posts = [post[row_offs[i]:row_offs[i + 1]].copy() for i in range(n)]
         mels = [mel[row_offs[i]:row_offs[i + 1]].copy() for i in range(n)] if want_mel else None
         return posts, mels
+
+    def feed_all(self, ids: Sequence[int], packets: Sequence[np.ndarray], want_mel: bool = False):
+        """:meth:`feed` on a causal bank that runs every listed member on every stream (``members=``; ``ww_stream_feed_all``):
+        the same arguments; ``posts[i]`` is ``[rows_i, K]`` - column ``j`` is the bits :meth:`feed` yields on a causal bank of member
+        ``members[j]`` alone -, ``mels`` as :meth:`feed`'s (one set of rows per stream, whatever K is).  The samples of a stream may
+        be cut into ``feed_all`` packets, calls and :meth:`step` ticks in any way."""
+        if not self.n_members:
+            raise ValueError("feed_all: this bank was not built with members=: an ordinary causal bank takes feed")
+        a_ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        n = int(a_ids.size)
+        if len(packets) != n:
+            raise ValueError("one packet per listed stream")
+        pk = [np.ascontiguousarray(p, dtype=np.int16).ravel() for p in packets]
+        offs = np.zeros(n + 1, np.int64)
+        np.cumsum([p.size for p in pk], out=offs[1:])
+        pcm = np.concatenate(pk) if n and offs[n] else np.zeros(1, np.int16)
+        row_offs = np.zeros(n + 1, np.int64)
+        h, K = self.engine.ctx.handle, self.n_members
+        _lib.raise_for(self._lib.ww_stream_feed_rows_all(self._h, _lib.ptr(a_ids), n, _lib.ptr(offs), _lib.ptr(row_offs)), h)
+        rows = int(row_offs[n])
+        post = np.empty((max(rows, 1), K), np.float32)
+        mel = np.empty((max(rows, 1), self.engine.n_mel), np.float32) if want_mel else None
+        _lib.raise_for(self._lib.ww_stream_feed_all(self._h, _lib.ptr(a_ids), n, _lib.ptr(pcm), _lib.ptr(offs), rows, _lib.ptr(row_offs),
+                                                    _lib.ptr(post), _lib.ptr(mel) if want_mel else None), h)
+        posts = [post[row_offs[i]:row_offs[i + 1]].copy() for i in range(n)]
+        mels = [mel[row_offs[i]:row_offs[i + 1]].copy() for i in range(n)] if want_mel else None
+        return posts, mels
+
+    def step_trigger_all(self, frames: np.ndarray, p_is_speech, p_is_active, p_thresholds, p_state) -> None:
+        """The wake-word stage of an every-member bank as ONE library call (``ww_stream_step_trigger_all``); every argument but
+        ``frames`` is an address taken once (``WakewordSetBank`` owns the arrays): ``p_state`` = (was_speech, posterior_max, post,
+        n_post, fired_ids, fired_slot, fired_mask, n_fired, fall_ids, n_fall)."""
+        if not self.n_members:
+            raise ValueError("step_trigger_all: this bank was not built with members=: an ordinary bank takes step_trigger")
+        rc = self._lib.ww_stream_step_trigger_all(self._h, self._frames_address(frames), p_is_speech, p_is_active, p_thresholds, *p_state)
+        if rc:
+            _lib.raise_for(rc, self.engine.ctx.handle)
 
     def close(self) -> None:
         if self._h and not _lib.is_shutdown():

@@ -86,7 +86,7 @@ class SpeechPipelineBank(SpeechPipeline):
     """The same loop for S streams in lock step (BASELINE config 5): ``input_source.read()`` returns one 20 ms frame per stream
     (``int16[S, 320]``, or ``int16[S, sample_rate / 50]`` where the wake-word stage's bank runs at another rate; the flat ragged
     block or S per-stream arrays where it has per-stream rates: passed through to the bank as they are), the context is a :class:`~wwhip.context.ContextBank`, the stages are the banked ones -
-    ``VadBank``, ``WakewordBank``, ``ActivationTimeoutBank`` - called as ``stage(contexts, frames)`` in list order, one call per
+    ``VadBank``, ``WakewordBank`` (or ``WakewordSetBank``: several wake words per stream), ``ActivationTimeoutBank`` - called as ``stage(contexts, frames)`` in list order, one call per
     stage and tick whatever S is.  ``pipeline.context[s]`` is stream ``s``'s ``SpeechContext``; ``pipeline.event`` registers a
     handler for every stream (it receives the stream's context)."""
 
@@ -95,10 +95,12 @@ class SpeechPipelineBank(SpeechPipeline):
         reference's ``demo.py``), a tick is ONE library call (``ww_pipeline_bank_step``: the three stages' passes in stage order on
         the stages' own arrays) instead of three - the same flags, events and posteriors; ``False`` keeps the stage-by-stage loop."""
         from .context import ContextBank
+        from .wakeword import WakewordSetBank
         for st in stages:
-            if getattr(st, "n_members", 0) or getattr(getattr(st, "_bank", None), "n_members", 0):
+            # (WakewordSetBank is the one stage around such a bank; it runs in the stage-by-stage loop: _bind_fused wants a WakewordBank)
+            if type(st) is not WakewordSetBank and (getattr(st, "n_members", 0) or getattr(getattr(st, "_bank", None), "n_members", 0)):
                 raise ValueError("SpeechPipelineBank: a bank that runs every listed member on every stream (members=) has no trigger "
-                                 "stage: step it directly")
+                                 "stage but WakewordSetBank: wrap it in one, or step it directly")
         super().__init__(input_source, stages)
         self._context = ContextBank(n_streams)
         self._fused = self._bind_fused() if fused else None

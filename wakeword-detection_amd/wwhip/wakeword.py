@@ -180,3 +180,138 @@ class WakewordBank:
 
     def close(self) -> None:
         self._bank.close()
+
+
+class WakewordSetBank:
+    """The wake-word stage of S streams that listen for SEVERAL wake words at once: an every-member
+    :class:`~wwhip.engine.StreamBank` (``StreamBank(model_set, S, members=...)``: one front end per stream, K member slots) and
+    :class:`WakewordBank`'s host logic with K slots per stream, inside one library call per tick
+    (``ww_stream_step_trigger_all``).  The rule (tflite.py:134-146,232-239 per stream): a running maximum per slot, cleared for all
+    slots on the VAD falling edge; slot ``j`` exceeds when its posterior is above ``thresholds[j]``; a stream that is not active fires
+    when any slot exceeds - ``activate`` is raised once per stream, as the reference's context has one flag - and the stage says which
+    wake word it was: :attr:`wake_slot` ``[S]`` (int32; -1 until a stream first fires, then its last winner: on the earliest row on
+    which any slot exceeded, the exceeding slot with the greatest posterior, the lowest among equals), :attr:`wake_mask` ``[S]``
+    (uint64; bit ``j``: slot ``j`` exceeded in the tick of the stream's last fire) and :attr:`posterior_max` ``[S, K]``.
+
+    ``thresholds``: one value for every slot, or one per slot.  ``names``: one name per slot, for :meth:`wake_word`.  ``bank=``: an
+    every-member bank of the caller's (``model_set`` / ``members`` / ``pre_emphasis`` / ``causal`` are then not looked at).
+    ``on_wake(ids, slots)`` is called with the streams that fired this tick and their winning slots.  ``contexts`` and ``frames``
+    of :meth:`step` are :meth:`WakewordBank.step`'s; it returns the tick's posteriors ``[S, K, 2]``."""
+
+    def __init__(self, n_streams: int, model_set=None, members="all", thresholds=0.5, names: Optional[Sequence[str]] = None, bank=None,
+                 pre_emphasis: float = 0.0, causal: bool = False, on_wake: Optional[Callable[[np.ndarray, np.ndarray], None]] = None) -> None:
+        self.S = int(n_streams)
+        if bank is None:
+            if model_set is None:
+                raise ValueError("WakewordSetBank needs model_set (a ModelSet), or bank=: a StreamBank built with members=")
+            bank = StreamBank(model_set, self.S, frontend_params(32767.0, True, pre_emphasis, 160, True), causal=causal, members=members)
+            owned = True
+        else:
+            owned = False
+            if not getattr(bank, "n_members", 0):
+                raise ValueError("WakewordSetBank: this bank was not built with members= (one model per stream): its stage is WakewordBank")
+            if getattr(bank, "S", self.S) != self.S:
+                raise ValueError(f"WakewordSetBank: the bank has {bank.S} streams, the stage {self.S}")
+        self._bank = bank  # (anything with StreamBank's n_members / step_trigger_all / reset / close: the host-only tests pass a stub)
+        self.K = K = int(bank.n_members)
+        try:
+            th = np.asarray(thresholds, np.float64)
+            if th.ndim == 0:
+                th = np.full(K, float(th))
+            if th.ndim != 1 or th.size != K:
+                raise ValueError(f"thresholds: one value, or one per member slot ({K}), got {np.shape(thresholds)}")
+            if names is not None and len(names) != K:
+                raise ValueError(f"names: one per member slot ({K}), got {len(names)}")
+        except ValueError:
+            if owned:
+                bank.close()
+            raise
+        from . import _lib
+        self.thresholds = np.ascontiguousarray(th)
+        self.names = None if names is None else [str(x) for x in names]
+        self._on_wake = on_wake
+        self.posterior_max = np.zeros((self.S, K), np.float32)
+        self.wake_slot = np.full(self.S, -1, np.int32)
+        self.wake_mask = np.zeros(self.S, np.uint64)
+        self._was_speech = np.zeros(self.S, np.uint8)
+        self._post = np.zeros((self.S, K, 2), np.float32)
+        self._n = np.zeros(self.S, np.int32)
+        self._fired = np.zeros(self.S, np.int32)
+        self._fired_slot = np.zeros(self.S, np.int32)
+        self._fired_mask = np.zeros(self.S, np.uint64)
+        self._fall = np.zeros(self.S, np.int32)
+        self._counts = np.zeros(2, np.int32)
+        a = _lib.addr
+        self._p_thresholds = a(self.thresholds)
+        self._p_state = (a(self._was_speech), a(self.posterior_max), a(self._post), a(self._n), a(self._fired), a(self._fired_slot),
+                         a(self._fired_mask), a(self._counts[0:1]), a(self._fall), a(self._counts[1:2]))
+        self._bound = None     # (the ContextBank, the addresses of its two flag arrays)
+        self._scratch = None   # flag arrays for the sequence-of-contexts form
+
+    @property
+    def n_members(self) -> int:
+        return self.K
+
+    @property
+    def n_post(self) -> np.ndarray:
+        """Posteriors per stream and slot delivered by the last tick (0, 1 or 2)."""
+        return self._n
+
+    @property
+    def fall_ids(self) -> np.ndarray:
+        """The streams whose VAD bit fell in the last tick (they were reset)."""
+        return self._fall[:self._counts[1]].copy()
+
+    def wake_word(self, stream: int) -> Optional[str]:
+        """The name of the wake word stream ``stream`` last woke to; ``None`` before its first fire."""
+        if self.names is None:
+            raise ValueError("wake_word: the stage was built without names=")
+        j = int(self.wake_slot[int(stream)])
+        return None if j < 0 else self.names[j]
+
+    def _fires(self):
+        nf = self._counts[0]
+        if not nf:
+            return None
+        ids, slots = self._fired[:nf].copy(), self._fired_slot[:nf].copy()
+        self.wake_slot[ids] = slots
+        self.wake_mask[ids] = self._fired_mask[:nf]
+        if self._on_wake is not None:
+            self._on_wake(ids, slots)
+        return ids
+
+    def step(self, contexts, frames: np.ndarray) -> np.ndarray:
+        from . import _lib
+        if len(contexts) != self.S:
+            raise ValueError("one context per stream")
+        if hasattr(contexts, "emit"):  # a ContextBank: its arrays are the state
+            b = self._bound
+            if b is None or b[0] is not contexts:
+                b = self._bound = (contexts, _lib.addr(contexts.is_speech), _lib.addr(contexts.is_active))
+            self._bank.step_trigger_all(frames, b[1], b[2], self._p_thresholds, self._p_state)
+            ids = self._fires()
+            if ids is not None:
+                contexts.emit("activate", ids)
+            return self._post.copy()
+        # a sequence of SpeechContext objects
+        sc = self._scratch
+        if sc is None:
+            speech, active = np.zeros(self.S, np.uint8), np.zeros(self.S, np.uint8)
+            sc = self._scratch = (speech, active, _lib.addr(speech), _lib.addr(active))
+        sc[0][:] = [c.is_speech for c in contexts]
+        sc[1][:] = [c.is_active for c in contexts]
+        self._bank.step_trigger_all(frames, sc[2], sc[3], self._p_thresholds, self._p_state)
+        ids = self._fires()
+        if ids is not None:
+            for s in ids:
+                contexts[int(s)].is_active = True  # (the setter raises the activate event)
+        return self._post.copy()
+
+    __call__ = step  # the stage form: bank(contexts, frames)
+
+    def reset(self) -> None:
+        self._bank.reset()
+        self.posterior_max[:] = 0.0
+
+    def close(self) -> None:
+        self._bank.close()
