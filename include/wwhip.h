@@ -257,11 +257,25 @@ typedef struct ww_resample_info {
 #define WW_RESAMPLE_MAX_SPAN 12288
 #define WW_SAMPLE_I16 0
 #define WW_SAMPLE_F32 1
+/* G.711 (ITU-T), one byte per sample, as a telephony leg carries it: an INPUT format of ww_resample / ww_resample_dev (and of the
+ * stream banks' formats below).  A code decodes to the 16-bit sample audioop.ulaw2lin(b, 2) / audioop.alaw2lin(b, 2) give:
+ *   mu-law:  v = ~code & 0xFF;  t = (((v & 0x0F) << 3) + 0x84) << ((v & 0x70) >> 4);  x = (v & 0x80) ? 0x84 - t : t - 0x84
+ *   A-law:   v = code ^ 0x55;   t = (v & 0x0F) << 4;  seg = (v & 0x70) >> 4;
+ *            seg == 0 ? t += 8 : (t += 0x108, t <<= seg - 1);  x = (v & 0x80) ? t : -t
+ * (mu-law: +-32124, 255 distinct values; A-law: +-32256, 256 distinct values.)  The codes are decoded in the kernels that read the
+ * samples, and A G.711 INPUT YIELDS THE BITS THE SAME CALL YIELDS ON THE DECODED int16 SAMPLES - no tolerance.  Samples are one byte
+ * each: sample_offs counts samples as ever, and a segment may start at any byte.  As out_format they are WW_EINVAL.  rate_in ==
+ * rate_out: the output is the decoded signal (WW_SAMPLE_I16: exactly; WW_SAMPLE_F32: times 2^-15).  (Value 2 is no format.)
+ * ww_g711_table writes the 256 decoded values of WW_SAMPLE_MULAW or WW_SAMPLE_ALAW; host only, no context; another format, or a NULL
+ * table, is WW_EINVAL. */
+#define WW_SAMPLE_MULAW 8
+#define WW_SAMPLE_ALAW 9
+int ww_g711_table(int32_t format, int16_t table[256]);
 int ww_resampler_create(ww_ctx *ctx, int32_t rate_in, int32_t rate_out, const ww_resampler_params *params, ww_resampler **out);
 int ww_resampler_destroy(ww_resampler *r);
 int ww_resampler_info(const ww_resampler *r, ww_resample_info *out);
 /* Output ranges of n_seg segments in one launch.  Segment u holds samples [sample_offs[u], sample_offs[u + 1]) of `in`
- * (WW_SAMPLE_I16 or WW_SAMPLE_F32), which are samples in_first[u] .. of its own signal; outputs out_first[u] .. of that signal,
+ * (WW_SAMPLE_I16, WW_SAMPLE_F32, WW_SAMPLE_MULAW or WW_SAMPLE_ALAW), which are samples in_first[u] .. of its own signal; outputs out_first[u] .. of that signal,
  * out_offs[u + 1] - out_offs[u] of them, go to out[out_offs[u] .. out_offs[u + 1]) as WW_SAMPLE_F32, or as WW_SAMPLE_I16 =
  * clip(rint(y * 32768), -32768, 32767).  Samples outside a segment read as zero.  in_first / out_first == NULL: all zero (a
  * one-shot clip: count = ceil(n * up / down)).  A long signal in pieces, or a stream in packets: give each piece
@@ -594,6 +608,39 @@ int ww_stream_frame_samples(const ww_streams *st, int32_t *out);
 int ww_stream_attach_rates(ww_streams *st, const ww_resampler *const *rs, int32_t n_rates, const int32_t *stream_rate);
 int ww_stream_frame_layout(const ww_streams *st, int32_t *frame_samples, int64_t *frame_offs);
 int ww_stream_set_rate(ww_streams *st, const int32_t *ids, int32_t n, int32_t rate_class);
+/* ---- stream banks that read G.711 ------------------------------------------------------------------------------------------------
+ * A telephony leg arrives as G.711, one byte per sample (WW_SAMPLE_MULAW, WW_SAMPLE_ALAW above).  A bank takes it as it is: the one
+ * kernel in front of a tick, and a feed's splice and pass-through copy, decode the bytes where they unpack them.  Contract, as
+ * everywhere: A G.711 STREAM YIELDS THE BITS THE SAME CALL YIELDS ON ITS DECODED int16 SAMPLES, no tolerance.  Nothing behind the rate
+ * kernel knows the format, so every bank form, model-set banks, every-member banks, ww_stream_set_rate, ww_stream_reset and
+ * ww_stream_set_model work on such a bank.
+ * ww_stream_attach_rates_fmt is ww_stream_attach_rates where class k reads its frames and packets as formats[k]: WW_SAMPLE_I16,
+ * WW_SAMPLE_MULAW or WW_SAMPLE_ALAW (WW_SAMPLE_F32 or anything else: WW_EINVAL).  A class is a (rate, format) pair: the same rate may
+ * come in two formats, two classes of the same pair are WW_EINVAL.  rs[k] == NULL with a G.711 format is 16 kHz G.711: it decodes
+ * only, no delay and no history (and may stand beside the int16 NULL class).  formats == NULL: all WW_SAMPLE_I16 - the call then IS
+ * ww_stream_attach_rates, which keeps every refusal it has.
+ * ww_stream_attach_resampler_fmt is the uniform bank of ww_stream_attach_resampler (no per-stream descriptor) whose frames are
+ * [S][F] of in_format and whose packets are of in_format.
+ * Frames.  On a bank that has a G.711 class, `frames` of ww_stream_step, _step_all, _step_trigger, _step_trigger_all and
+ * ww_pipeline_bank_step is read as ONE BYTE block: a G.711 frame (rate / 50 bytes) starts at the next byte, an int16 frame (rate / 25
+ * bytes) at the next even byte, with one pad byte in front of it where needed.  ww_stream_frame_layout_bytes writes frame_bytes
+ * [n_streams], byte_offs [n_streams + 1] (byte_offs[n_streams] = the end of the last frame: the block's bytes) and formats
+ * [n_streams]; it works on every bank (a plain bank: 640-byte WW_SAMPLE_I16 frames; any bank without G.711: twice
+ * ww_stream_frame_layout's figures).  The layout changes with ww_stream_set_rate.  On a bank with a G.711 class the calls that count
+ * int16 samples - ww_stream_frame_layout, ww_stream_frame_samples, ww_stream_feed, ww_stream_feed_all - are WW_EINVAL;
+ * ww_stream_feed_rows / _rows_all count samples, whatever their format, and stay as they are.
+ * ww_stream_feed_bytes / ww_stream_feed_bytes_all are ww_stream_feed / ww_stream_feed_all with packets given in bytes: packet i is
+ * bytes [byte_offs[i], byte_offs[i + 1]) of data, in its stream's format.  An int16 packet with an odd offset or an odd length is
+ * WW_EINVAL.  On a bank without G.711 classes they are ww_stream_feed / _all with sample_offs = byte_offs / 2.  Everything those calls
+ * promise carries over: the same bits however the samples are cut into packets, calls and ticks, every refusal before any state
+ * moves (row_offs, post and mel untouched), the broken-bank rule.  A call's packets go up once. */
+int ww_stream_attach_rates_fmt(ww_streams *st, const ww_resampler *const *rs, const int32_t *formats, int32_t n_rates, const int32_t *stream_rate);
+int ww_stream_attach_resampler_fmt(ww_streams *st, const ww_resampler *r, int32_t in_format);
+int ww_stream_frame_layout_bytes(const ww_streams *st, int32_t *frame_bytes, int64_t *byte_offs, int32_t *formats);
+int ww_stream_feed_bytes(ww_streams *st, const int32_t *ids, int32_t n, const void *data, const int64_t *byte_offs, int64_t cap_rows,
+                         int64_t *row_offs, float *post, float *mel);
+int ww_stream_feed_bytes_all(ww_streams *st, const int32_t *ids, int32_t n, const void *data, const int64_t *byte_offs, int64_t cap_rows,
+                             int64_t *row_offs, float *post, float *mel);
 /* ---- the pipeline's host stages for S streams in lock step (BASELINE config 5 at the plugin surface) --------------------------
  * The reference drives three stage objects per stream and 20 ms frame (spokestack/pipeline.py:25-28, stage list of demo.py:29-36),
  * each a few comparisons on the shared SpeechContext.  For S streams each stage is ONE pass over plain arrays the caller owns

@@ -14,6 +14,13 @@
            b  what it takes without: a bank of S / 2 streams at 8000 and one of S / 2 at 48000, ticked one after the other
            c  a bank with per-stream rates whose S streams are all at 48000
            d  the single-rate bank of S streams at 48000 (c - d: the price of the per-stream descriptor)
+  g711   G.711 input (profiles/stream_rate/g711_measured.txt), three sides alternated within this process over --rounds
+         rounds of --ticks ticks each, S streams at 8000 Hz, p50 / p99 per side and round:
+           a  the uniform mu-law bank (StreamBank(sample_rate=8000, sample_format="mulaw")) given the bytes
+           b  the uniform int16 bank at 8000 given frames that were decoded beforehand (the decode is not timed)
+           c  the bank of b with the host decode a caller needed without a: table[frames] in numpy inside the timed region
+         and a catch-up: S streams x --seconds of mu-law in ONE feed of a causal Wavenet bank through ww_stream_feed_bytes against
+         the host decode (table[packet] per stream) plus ww_stream_feed of the int16 bank, milliseconds per call.
 
 One JSON line.  The single-rate modes use nothing this tool's commit added, so the file also runs on its parent."""
 import argparse
@@ -163,9 +170,74 @@ def mixed(args):
                 c_minus_d_p50_us=[round(x - y, 2) for x, y in zip(p50["c"], p50["d"])])
 
 
+def g711(args):
+    from wwhip import g711 as g
+    eng = Engine(os.path.join(ASSETS, args.model))
+    S, F = args.streams, 160
+    rng = np.random.default_rng(0)
+    table = g.table("mulaw")
+    codes = rng.integers(0, 256, (64, S, F), dtype=np.uint8)
+    decoded = table[codes]
+    sp = np.ones(S, np.uint8)
+    a = StreamBank(eng, S, sample_rate=8000, sample_format="mulaw")
+    b = StreamBank(eng, S, sample_rate=8000)
+    sides = {"a": lambda t: a.step(codes[t], sp)[1].sum(), "b": lambda t: b.step(decoded[t], sp)[1].sum(),
+             "c": lambda t: b.step(table[codes[t]], sp)[1].sum()}
+    for fn in sides.values():
+        for t in range(100):
+            fn(t % 64)
+    rounds = {k: [] for k in sides}
+    posts = {k: 0 for k in sides}
+    for r in range(args.rounds):
+        for k, fn in sides.items():
+            lat = np.empty(args.ticks)
+            for t in range(args.ticks):
+                t0 = time.perf_counter()
+                posts[k] += int(fn(t % 64))
+                lat[t] = time.perf_counter() - t0
+            rounds[k].append({q: round(v, 2) for q, v in _pct(lat).items()})
+    a.close()
+    b.close()
+    eng.close()
+    # the catch-up feed
+    wave = Engine(os.path.join(ASSETS, "Wavenet"))
+    n = int(8000 * args.seconds)
+    pk = [rng.integers(0, 256, n, dtype=np.uint8) for _ in range(S)]
+    fa = StreamBank(wave, S, causal=True, sample_rate=8000, sample_format="mulaw")
+    fb = StreamBank(wave, S, causal=True, sample_rate=8000)
+    ids = list(range(S))
+    ms = {"feed_bytes": [], "decode_then_feed": [], "decode_alone": []}
+    rows = {}
+    for rep_ in range(args.repeats + 1):  # (the first call sizes the scratch: not counted)
+        fa.reset()
+        t0 = time.perf_counter()
+        posts_a, _ = fa.feed(ids, pk)
+        ms["feed_bytes"].append((time.perf_counter() - t0) * 1e3)
+        fb.reset()
+        t0 = time.perf_counter()
+        dec = [table[p] for p in pk]
+        t1 = time.perf_counter()
+        posts_b, _ = fb.feed(ids, dec)
+        ms["decode_then_feed"].append((time.perf_counter() - t0) * 1e3)
+        ms["decode_alone"].append((t1 - t0) * 1e3)
+        rows = {"feed_bytes": sum(len(p) for p in posts_a), "decode_then_feed": sum(len(p) for p in posts_b)}
+    same = all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(posts_a, posts_b))
+    fa.close()
+    fb.close()
+    wave.close()
+    p50 = {k: [r["p50_us"] for r in v] for k, v in rounds.items()}
+    return dict(mode="g711", model=args.model, streams=S, ticks=args.ticks, rounds=rounds,
+                posteriors_per_tick={k: v / (args.ticks * args.rounds) for k, v in posts.items()},
+                p50_range_us={k: [min(v), max(v)] for k, v in p50.items()},
+                a_minus_b_p50_us=[round(x - y, 2) for x, y in zip(p50["a"], p50["b"])],
+                c_minus_a_p50_us=[round(x - y, 2) for x, y in zip(p50["c"], p50["a"])],
+                feed=dict(seconds=args.seconds, rows=rows, same_bits=bool(same), ms_per_call={k: [round(v, 2) for v in x[1:]] for k, x in ms.items()},
+                          median_ms={k: float(np.median(x[1:])) for k, x in ms.items()}))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("mode", choices=["tick", "push", "feed", "mixed"])
+    ap.add_argument("mode", choices=["tick", "push", "feed", "mixed", "g711"])
     ap.add_argument("--rate", type=int, default=48000, help="the streams' sample rate (a multiple of 50; 16000 = a plain bank)")
     ap.add_argument("--streams", type=int, default=128)
     ap.add_argument("--ticks", type=int, default=3000)
@@ -174,4 +246,4 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=3, help="feed: timed calls")
     ap.add_argument("--rounds", type=int, default=3, help="mixed: rounds the sides alternate over")
     a = ap.parse_args()
-    print(json.dumps({"tick": tick, "push": push, "feed": feed, "mixed": mixed}[a.mode](a)))
+    print(json.dumps({"tick": tick, "push": push, "feed": feed, "mixed": mixed, "g711": g711}[a.mode](a)))

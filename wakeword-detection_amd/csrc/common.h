@@ -18,6 +18,7 @@
 #include "model_layout.h"
 #include "stream_rate.h"
 #include "stream_rates.h"
+#include "stream_formats.h"
 
 #define WW_WAVE 64
 
@@ -300,8 +301,14 @@ int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, c
 // 16 kHz samples into d_dst (see resample.hip).
 struct ww_resampler;
 struct ww_stream_rates;
-int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, const int32_t *stream_rate, int S, bool uniform,
-                      ww_stream_rates **out);
+// formats[k] (nullptr: all int16) = the sample format class k reads its frames and packets in (stream_formats.h): with a G.711 class
+// in the bank (_g711) a tick's frames are one BYTE block (_layout_bytes; a uniform bank: [S][F] of the format) and a feed's packets
+// are counted in bytes.  `what`: the entry point's name, for the refusals.
+int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, const int32_t *formats, int n_rates, const int32_t *stream_rate, int S, bool uniform,
+                      const char *what, ww_stream_rates **out);
+bool ww_k_rates_g711(const ww_stream_rates *rt);
+int ww_k_rates_stream_format(const ww_stream_rates *rt, int stream);
+void ww_k_rates_layout_bytes(const ww_stream_rates *rt, int32_t *frame_bytes, int64_t *byte_offs, int32_t *formats);  // [S], [S + 1], [S]; each may be nullptr
 void ww_k_rates_destroy(ww_stream_rates *rt);
 int ww_k_rates_classes(const ww_stream_rates *rt);
 int ww_k_rates_frame_samples(const ww_stream_rates *rt);
@@ -310,7 +317,7 @@ void ww_k_rates_reset(ww_stream_rates *rt, const int32_t *ids, int count);
 int ww_k_rates_move(ww_stream_rates *rt, const int32_t *ids, int count, int c);
 int64_t ww_k_rates_advance(const ww_stream_rates *rt, int stream, int64_t k);
 int ww_k_rates_tick(ww_stream_rates *rt, const int16_t *frames, const uint8_t *flags, const int32_t *ctl_dev, const int16_t **d_frames);
-int ww_k_rates_feed(ww_stream_rates *rt, const int32_t *ids, int n, const int16_t *pcm, const int64_t *sample_offs, const int64_t *offs16,
+int ww_k_rates_feed(ww_stream_rates *rt, const int32_t *ids, int n, const void *data, const int64_t *byte_offs, const int64_t *offs16,
                     int16_t *d_dst, bool *moved);
 int ww_k_far_frr(ww_ctx *ctx, const float *d_pos, int64_t n_pos, const float *d_neg, int64_t n_neg, int win,
                  const double *d_thr, int n_thr, double *d_smoothed, unsigned long long *d_pos_cnt,

@@ -35,6 +35,24 @@ struct ww_resampler : rs_geom {
 
 __device__ __forceinline__ float rs_load(int16_t v) { return (float)v * (1.0f / 32768.0f); }  // exact: a power of two
 __device__ __forceinline__ float rs_load(float v) { return v; }
+// G.711 (ITU-T, 16-bit output: audioop.ulaw2lin / alaw2lin at width 2): a code decodes in registers to the int16 sample, which goes the
+// int16 sample's way from there on - the chains see the same fp32 values, so a G.711 input yields the decoded int16 input's bits.
+struct rs_mulaw { uint8_t code; };
+struct rs_alaw { uint8_t code; };
+__host__ __device__ __forceinline__ int g711_mulaw(unsigned code) {
+  const unsigned v = ~code & 0xFFu;
+  const int t = (int)((((v & 0x0Fu) << 3) + 0x84u) << ((v & 0x70u) >> 4));
+  return (v & 0x80u) ? 0x84 - t : t - 0x84;
+}
+__host__ __device__ __forceinline__ int g711_alaw(unsigned code) {
+  const unsigned v = (code ^ 0x55u) & 0xFFu, seg = (v & 0x70u) >> 4;
+  int t = (int)((v & 0x0Fu) << 4);
+  t = seg == 0 ? t + 8 : (t + 0x108) << (seg - 1);
+  return (v & 0x80u) ? t : -t;
+}
+__host__ __device__ __forceinline__ int g711_decode(int law, unsigned code) { return law == WW_SAMPLE_MULAW ? g711_mulaw(code) : g711_alaw(code); }
+__device__ __forceinline__ float rs_load(rs_mulaw v) { return rs_load((int16_t)g711_mulaw(v.code)); }
+__device__ __forceinline__ float rs_load(rs_alaw v) { return rs_load((int16_t)g711_alaw(v.code)); }
 __device__ __forceinline__ void rs_store(float *p, float v) { *p = v; }
 __device__ __forceinline__ void rs_store(int16_t *p, float v) {
   v = rintf(v * 32768.0f);
@@ -171,13 +189,19 @@ static void rs_launch(ww_ctx *ctx, const char *name, K kernel, size_t n_tiles, A
   hipLaunchKernelGGL(kernel, dim3((unsigned)n_tiles), dim3(RS_THREADS), 0, ctx->stream, args...);
 }
 
+static size_t rs_sample_bytes(int fmt) {  // 0: not a sample format
+  return fmt == WW_SAMPLE_I16 ? 2 : fmt == WW_SAMPLE_F32 ? 4 : (fmt == WW_SAMPLE_MULAW || fmt == WW_SAMPLE_ALAW) ? 1 : 0;
+}
+
 static int rs_validate(const ww_resampler *r, const void *in, int in_fmt, const int64_t *so, const int64_t *in_first, const int64_t *out_first,
                        const int64_t *oo, int n_seg, const void *out, int out_fmt, int64_t *n_out_total) {
   ww_ctx *ctx = r->ctx;
   *n_out_total = 0;
   if (n_seg < 0) return ww_fail(ctx, WW_EINVAL, "ww_resample: n_seg = %d", n_seg);
-  if ((in_fmt != WW_SAMPLE_I16 && in_fmt != WW_SAMPLE_F32) || (out_fmt != WW_SAMPLE_I16 && out_fmt != WW_SAMPLE_F32))
-    return ww_fail(ctx, WW_EINVAL, "ww_resample: sample formats are WW_SAMPLE_I16 and WW_SAMPLE_F32");
+  if (out_fmt == WW_SAMPLE_MULAW || out_fmt == WW_SAMPLE_ALAW)
+    return ww_fail(ctx, WW_EINVAL, "ww_resample: G.711 is an input format only: out_format is WW_SAMPLE_I16 or WW_SAMPLE_F32");
+  if (rs_sample_bytes(in_fmt) == 0 || (out_fmt != WW_SAMPLE_I16 && out_fmt != WW_SAMPLE_F32))
+    return ww_fail(ctx, WW_EINVAL, "ww_resample: sample formats are WW_SAMPLE_I16 and WW_SAMPLE_F32 (in_format: also WW_SAMPLE_MULAW and WW_SAMPLE_ALAW)");
   if (n_seg == 0) return WW_OK;
   if (!so || !oo) return ww_fail(ctx, WW_EINVAL, "ww_resample: NULL offset table");
   if (so[0] < 0 || oo[0] < 0) return ww_fail(ctx, WW_EINVAL, "ww_resample: negative offset");
@@ -224,10 +248,14 @@ static int rs_run(const ww_resampler *r, const rs_plan &pl, rs_tile *d_tiles, co
   tb.join(pl.ph8);
   tb.join(pl.ph1);
   if (int rc = tb.send(ctx, d_tiles)) return rc;
-  if (in_fmt == WW_SAMPLE_I16 && out_fmt == WW_SAMPLE_F32) rs_launch_all(r, pl, d_tiles, (const int16_t *)d_in, (float *)d_out);
-  else if (in_fmt == WW_SAMPLE_F32 && out_fmt == WW_SAMPLE_F32) rs_launch_all(r, pl, d_tiles, (const float *)d_in, (float *)d_out);
-  else if (in_fmt == WW_SAMPLE_I16) rs_launch_all(r, pl, d_tiles, (const int16_t *)d_in, (int16_t *)d_out);
-  else rs_launch_all(r, pl, d_tiles, (const float *)d_in, (int16_t *)d_out);
+  auto to = [&](auto *in) {
+    if (out_fmt == WW_SAMPLE_F32) rs_launch_all(r, pl, d_tiles, in, (float *)d_out);
+    else rs_launch_all(r, pl, d_tiles, in, (int16_t *)d_out);
+  };
+  if (in_fmt == WW_SAMPLE_I16) to((const int16_t *)d_in);
+  else if (in_fmt == WW_SAMPLE_F32) to((const float *)d_in);
+  else if (in_fmt == WW_SAMPLE_MULAW) to((const rs_mulaw *)d_in);
+  else to((const rs_alaw *)d_in);
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;
 }
@@ -335,6 +363,16 @@ int ww_resampler_info(const ww_resampler *r, ww_resample_info *out) {
   WW_GUARD_END(r ? r->ctx : nullptr)
 }
 
+int ww_g711_table(int32_t format, int16_t table[256]) {
+  WW_GUARD_BEGIN
+  if (!table) return ww_fail(nullptr, WW_EINVAL, "ww_g711_table: NULL table");
+  if (format != WW_SAMPLE_MULAW && format != WW_SAMPLE_ALAW)
+    return ww_fail(nullptr, WW_EINVAL, "ww_g711_table: format %d: WW_SAMPLE_MULAW or WW_SAMPLE_ALAW", (int)format);
+  for (unsigned c = 0; c < 256; ++c) table[c] = (int16_t)(format == WW_SAMPLE_MULAW ? g711_mulaw(c) : g711_alaw(c));
+  return WW_OK;
+  WW_GUARD_END(nullptr)
+}
+
 int ww_resample_dev(ww_resampler *r, const void *d_in, int32_t in_format, const int64_t *sample_offs, const int64_t *in_first,
                     const int64_t *out_first, const int64_t *out_offs, int32_t n_seg, void *d_out, int32_t out_format) {
   WW_GUARD_BEGIN
@@ -363,7 +401,7 @@ int ww_resample(ww_resampler *r, const void *in, int32_t in_format, const int64_
   WW_ON_DEVICE(ctx, dev);
   rs_plan pl;
   rs_make_plan(r, sample_offs, in_first, out_first, out_offs, n_seg, pl);
-  const size_t ie = in_format == WW_SAMPLE_I16 ? 2 : 4, oe = out_format == WW_SAMPLE_I16 ? 2 : 4;
+  const size_t ie = rs_sample_bytes(in_format), oe = rs_sample_bytes(out_format);
   const int64_t s0 = sample_offs[0], n_in = sample_offs[n_seg] - s0, o0 = out_offs[0];
   if (int rc = ww_ensure(ctx, ctx->dev, ww_bump::need((size_t)n_in, ie) + ww_bump::need((size_t)n_out, oe) + ww_bump::need(pl.count(), sizeof(rs_tile)) + 1024, false))
     return rc;
@@ -396,17 +434,23 @@ int ww_resample(ww_resampler *r, const void *in, int32_t in_format, const int64_
 // host's count = 0, no kernel): read into LDS in front of the frame by the one workgroup that writes it back, no order between
 // workgroups.  The history rows are per class, [S][hist of the class], and a stream uses its current class's row only: whatever an
 // earlier use left in a row reads as zero behind held = 0, so a move clears nothing.
+// Formats (stream_formats.h): a class reads its frames and packets as int16 or as G.711 mu-law / A-law, one byte per
+// sample.  Only the unpacking knows: the tick's kernel takes a frame as F x bytes-per-sample bytes from any byte (an int16 frame: any
+// even byte) and decodes a G.711 piece's 16 samples where it unpacks an int16 piece's 8, the feed's splice and pass-through copy take
+// byte offsets and the class's format.  What is staged is rs_load of the decoded int16 value, so everything behind - chains,
+// history, outputs - has the decoded int16 input's bits.
 struct ww_stream_rates {
   ww_ctx *ctx = nullptr;
   int S = 0;
   bool uniform = false;  // made by ww_stream_attach_resampler (NOT: K happens to be 1 - a per-stream bank of one class may still be moved)
   rates_table tab;
+  formats_table fmt;  // the classes' sample formats (stream_formats.h); all int16 unless the bank was attached with formats
   const ww_resampler *r[WW_STREAM_MAX_RATES] = {};  // the class's resampler, whose tap table the kernels borrow; nullptr: the 16 kHz class
   float *d_hist[WW_STREAM_MAX_RATES] = {};          // [S][hist of the class]
   std::vector<int32_t> cls;                         // [S] the stream's class
   std::vector<int64_t> n;  // [S] input samples since the stream's last reset or move, frozen ticks left out (a 16 kHz stream's stays 0)
   std::vector<rates_desc> desc;                     // [S] what d_desc was last sent
-  int64_t total = 0;                                // samples of a tick's frames
+  int64_t total = 0;                                // bytes of a tick's frames
   rates_desc *d_desc = nullptr;                     // (a uniform bank has none)
   int16_t *d_out = nullptr;  // [S][320]: the tick's 16 kHz samples (640 bytes per stream: the tick kernels load them 16 at a time)
   // the tick's page-locked input: [S] rate_ctl | the frames (room for S frames of the longest class).  ONE copy: the kernel that
@@ -416,11 +460,13 @@ struct ww_stream_rates {
   ww_resampler pass_r;        // the 16 kHz class of a feed: the identity form's tiles (resample_copy_kernel), no table
   char *d_scratch = nullptr;  // a feed's [packets | per class present: splice table | segments | tiles], grown on demand
   size_t scratch_cap = 0;
-  void layout() {
+  void layout() {  // (stream_formats.h: formats_layout)
     total = 0;
     for (int s = 0; s < S; ++s) {
-      desc[(size_t)s] = {total, cls[(size_t)s], 0};
-      total += tab.g[cls[(size_t)s]].F;
+      const int c = cls[(size_t)s], b = format_bytes(fmt.fmt[c]);
+      total = formats_frame_start(total, b);
+      desc[(size_t)s] = {total, c, 0};
+      total += (int64_t)tab.g[c].F * b;
     }
   }
   int send() {
@@ -434,10 +480,11 @@ struct rate_class_dev {
   const float *taps;
   float *hist;  // [S][H]
   int up, down, half, tpp, F, D, H, pass;
+  int law;  // 0: int16 samples; WW_SAMPLE_MULAW / WW_SAMPLE_ALAW: one byte per sample, decoded as it is unpacked
 };
 template <int K>
 struct rate_tick_args {
-  const int16_t *frames;   // page-locked, from a 16-byte boundary, padded to whole 16-byte pieces
+  const int16_t *frames;   // page-locked, from a 16-byte boundary, padded to whole 16-byte pieces (a byte block: int16 and G.711 frames)
   const rate_ctl *rc;      // page-locked [S]
   const int32_t *ctl;      // the tick's own control words [S][4] (page-locked): bit 1 of word 2 = the stream is frozen
   int16_t *out;
@@ -459,18 +506,26 @@ __global__ __launch_bounds__(RATE_THREADS) void stream_rate_tick_kernel(rate_tic
   if constexpr (PerStream) {
     const rates_desc d = a.desc[s];
     cp = &a.c[__builtin_amdgcn_readfirstlane(d.cls) & (WW_STREAM_MAX_RATES - 1)];
-    b0 = (size_t)d.off * 2;
+    b0 = (size_t)d.off;  // (the table holds byte offsets: an int16 frame's is even)
   } else {
-    b0 = (size_t)s * a.c[0].F * 2;
+    b0 = (size_t)s * a.c[0].F * (a.c[0].law ? 1 : 2);
   }
   const rate_class_dev &g = *cp;
-  const int F = g.F, H = g.H;
-  // The frame crosses the bus 16 bytes per lane, whatever F is: the aligned 16-byte pieces that cover its 2 F bytes (a frame starts
-  // at any even byte; the first and the last piece may hold a neighbour's samples, which are dropped; the block is padded to whole
-  // pieces).  The first RATE_THREADS pieces are requested BEFORE the control words are looked at - one trip over the bus instead of
-  // two in a row.
+  const int F = g.F, H = g.H, law = g.law;  // (law: wave-uniform, like every field of the class)
+  // A G.711 class decodes through a 256-entry table in LDS, filled here by 256 lanes with one code each: the few lanes that hold the
+  // frame's pieces would else run 16 decodes in a row each (measured: a few tenths of a microsecond per tick at 128 streams).  The entries
+  // are rs_load of the decoded int16 values - what the int16 path stages.
+  __shared__ float g711_tab[256];
+  if (law) {
+    if (tid < 256) g711_tab[tid] = rs_load((int16_t)g711_decode(law, (unsigned)tid));
+    __syncthreads();  // (the class is the workgroup's: every lane comes here or none does)
+  }
+  // The frame crosses the bus 16 bytes per lane, whatever F is: the aligned 16-byte pieces that cover its bytes - 2 F of an int16
+  // frame, which starts at any even byte, F of a G.711 frame, which starts at any byte (the first and the last piece may hold a
+  // neighbour's samples, which are dropped; the block is padded to whole pieces).  The first RATE_THREADS pieces are requested BEFORE
+  // the control words are looked at - one trip over the bus instead of two in a row.
   const size_t a0 = b0 & ~(size_t)15;
-  const int n16 = (int)((b0 + (size_t)F * 2 - a0 + 15) >> 4), lead = (int)(b0 - a0) >> 1;
+  const int n16 = (int)((b0 + (size_t)F * (law ? 1 : 2) - a0 + 15) >> 4), lead = law ? (int)(b0 - a0) : (int)(b0 - a0) >> 1;  // lead: samples
   const uint4 *src = (const uint4 *)((const char *)a.frames + a0);
   uint4 raw = make_uint4(0u, 0u, 0u, 0u);
   if (tid < n16) raw = src[tid];
@@ -481,6 +536,14 @@ __global__ __launch_bounds__(RATE_THREADS) void stream_rate_tick_kernel(rate_tic
     if (g.pass) {  // the 16 kHz class: the frame is the stream's row of the block (41 pieces at most: one per lane)
       int16_t *o = a.out + (size_t)s * WW_RATE_FRAME_OUT;
       const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+      if (law) {  // 16 kHz G.711: the decoded frame is the row (21 pieces at most)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int i = tid * 16 + e - lead;
+          if (tid < n16 && i >= 0 && i < WW_RATE_FRAME_OUT) o[i] = (int16_t)(g711_tab[(w[e >> 2] >> ((e & 3) * 8)) & 0xFFu] * 32768.0f);  // (exact: the entry is the value / 2^15)
+        }
+        return;
+      }
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const int i = tid * 8 + e - lead;
@@ -490,8 +553,16 @@ __global__ __launch_bounds__(RATE_THREADS) void stream_rate_tick_kernel(rate_tic
     }
   }
   float *hist = g.hist + (size_t)s * H;
-  auto put = [&](int q, const uint4 &v) {  // piece q: samples 8 q - lead .. 8 q - lead + 7 of the frame
+  auto put = [&](int q, const uint4 &v) {  // piece q: samples 8 q - lead .. 8 q - lead + 7 of the frame (G.711: 16 q - lead .. + 15)
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
+    if (law) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int i = q * 16 + e - lead;
+        if (i >= 0 && i < F) xs[H + i] = g711_tab[(w[e >> 2] >> ((e & 3) * 8)) & 0xFFu];
+      }
+      return;
+    }
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int i = q * 8 + e - lead;
@@ -516,18 +587,22 @@ __global__ __launch_bounds__(RATE_THREADS) void stream_rate_tick_kernel(rate_tic
 // are shorter than that, so workgroup (i, 0) is the row's one reader, and it is its one writer.
 #define RATE_SPLICE 16384
 struct rate_feed_str {
-  int64_t pk_off;   // the packet's first sample in the call's packet buffer
+  int64_t pk_off;   // the packet's first BYTE in the call's packet buffer (an int16 packet's is even)
   int64_t k;        // its samples (> 0)
   int64_t seg_off;  // the segment's first sample in the class's segment buffer
   int32_t sid, held;
 };
-__global__ __launch_bounds__(256) void stream_rate_splice_kernel(const int16_t *pk, const rate_feed_str *str, float *seg, float *hist, int H) {
+__global__ __launch_bounds__(256) void stream_rate_splice_kernel(const char *pk, const rate_feed_str *str, float *seg, float *hist, int H, int law) {
   extern __shared__ float nh[];  // [H]
   const rate_feed_str d = str[blockIdx.x];
   float *h = hist + (size_t)d.sid * H;
   const int64_t tot = d.held + d.k, v0 = (int64_t)blockIdx.y * RATE_SPLICE;
   if (v0 >= tot) return;
-  auto sample = [&](int64_t v) -> float { return v < d.held ? h[H - d.held + v] : rs_load(pk[d.pk_off + (v - d.held)]); };
+  auto sample = [&](int64_t v) -> float {  // (law: the class's format, the same for every packet of the launch)
+    if (v < d.held) return h[H - d.held + v];
+    if (law) return rs_load((int16_t)g711_decode(law, (unsigned char)pk[d.pk_off + (v - d.held)]));
+    return rs_load(((const int16_t *)(pk + d.pk_off))[v - d.held]);
+  };
   const int64_t v1 = v0 + RATE_SPLICE < tot ? v0 + RATE_SPLICE : tot;
   for (int64_t v = v0 + threadIdx.x; v < v1; v += 256) seg[d.seg_off + v] = sample(v);
   if (blockIdx.y) return;
@@ -553,8 +628,8 @@ static int rates_destroy_(ww_stream_rates *rt) {
   return WW_OK;
 }
 
-int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, const int32_t *stream_rate, int S, bool uniform,
-                      ww_stream_rates **out) {
+int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, const int32_t *formats, int n_rates, const int32_t *stream_rate, int S, bool uniform,
+                      const char *what, ww_stream_rates **out) {
   *out = nullptr;
   char why[320];
   ww_stream_rates *rt = new ww_stream_rates();
@@ -565,10 +640,25 @@ int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, c
   rt->pass_r.rate_in = rt->pass_r.rate_out = WW_RATE_OUT;
   if (uniform) {  // the one class on its own: rate_make_geom's refusals, no class named
     const ww_resampler *r = rs[0];
-    if (r->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: the resampler belongs to another context");
+    if (r->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "%s: the resampler belongs to another context", what);
+    if (formats && !format_bytes(formats[0]))
+      return ww_fail(ctx, WW_EINVAL, "%s: format %d: a bank reads WW_SAMPLE_I16, WW_SAMPLE_MULAW or WW_SAMPLE_ALAW (float32 streams are not offered)", what,
+                     (int)formats[0]);
     if (rate_make_geom(r->rate_in, r->rate_out, r->up, r->down, r->half, r->tpp, rt->tab.g[0], why, sizeof why))
-      return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: %s", why);
+      return ww_fail(ctx, WW_EINVAL, "%s: %s", what, why);
     rt->tab.K = 1;
+    if (formats) {
+      rt->fmt.fmt[0] = formats[0];
+      rt->fmt.g711 = format_bytes(formats[0]) == 1;
+    }
+  } else if (formats) {  // classes are (rate, format) pairs (stream_formats.h)
+    for (int k = 0; k < n_rates; ++k) {
+      const ww_resampler *r = rs[k];
+      if (r && r->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "%s: class %d: the resampler belongs to another context", what, k);
+      if (r ? formats_add_class(rt->tab, rt->fmt, formats[k], false, r->rate_in, r->rate_out, r->up, r->down, r->half, r->tpp, why, sizeof why)
+            : formats_add_class(rt->tab, rt->fmt, formats[k], true, 0, 0, 0, 0, 0, 0, why, sizeof why))
+        return ww_fail(ctx, WW_EINVAL, "%s: %s", what, why);
+    }
   } else {
     for (int k = 0; k < n_rates; ++k) {
       const ww_resampler *r = rs[k];
@@ -578,9 +668,9 @@ int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, c
         return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %s", why);
     }
   }
-  if (rates_check_ids(rt->tab, stream_rate, S, "stream_rate", why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %s", why);
+  if (rates_check_ids(rt->tab, stream_rate, S, "stream_rate", why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "%s: %s", what, why);
   int64_t stage = 0;
-  if (rates_stage(rt->tab, &stage, why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %s", why);
+  if (rates_stage(rt->tab, &stage, why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "%s: %s", what, why);
   rt->lds_bytes = (size_t)stage * 4;
   if (stream_rate) rt->cls.assign(stream_rate, stream_rate + S);
   else rt->cls.assign((size_t)S, 0);
@@ -589,7 +679,7 @@ int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, c
   rt->layout();
   // (the frames start on a 16-byte boundary and end in whole 16-byte pieces: the kernel loads them as uint4)
   const size_t b_desc = ww_bump::need((size_t)S, sizeof(rates_desc)), b_out = (size_t)S * WW_RATE_FRAME_OUT * 2,
-               b_in = (size_t)S * sizeof(rate_ctl) + (((size_t)rates_layout_max(rt->tab, S) * 2 + 15) & ~(size_t)15) + 16;
+               b_in = (size_t)S * sizeof(rate_ctl) + (((size_t)formats_layout_max(rt->tab, rt->fmt, S) + 15) & ~(size_t)15) + 16;
   bool ok = hipMalloc((void **)&rt->d_out, b_out) == hipSuccess && hipHostMalloc((void **)&rt->h_in, b_in) == hipSuccess &&
             (uniform || hipMalloc((void **)&rt->d_desc, b_desc) == hipSuccess);
   for (int k = 0; k < n_rates && ok; ++k) {
@@ -615,6 +705,14 @@ int ww_k_rates_create(ww_ctx *ctx, const ww_resampler *const *rs, int n_rates, c
 int ww_k_rates_classes(const ww_stream_rates *rt) { return rt->tab.K; }
 
 int ww_k_rates_frame_samples(const ww_stream_rates *rt) { return rt->uniform ? rt->tab.g[0].F : 0; }
+
+bool ww_k_rates_g711(const ww_stream_rates *rt) { return rt->fmt.g711; }
+
+int ww_k_rates_stream_format(const ww_stream_rates *rt, int stream) { return rt->fmt.fmt[rt->cls[(size_t)stream]]; }
+
+void ww_k_rates_layout_bytes(const ww_stream_rates *rt, int32_t *frame_bytes, int64_t *byte_offs, int32_t *formats) {
+  formats_layout(rt->tab, rt->fmt, rt->cls.data(), rt->S, frame_bytes, byte_offs, formats);
+}
 
 void ww_k_rates_layout(const ww_stream_rates *rt, int32_t *frame_samples, int64_t *frame_offs) {
   rates_layout(rt->tab, rt->cls.data(), rt->S, frame_samples, frame_offs);
@@ -659,7 +757,8 @@ static void rates_tick_launch(const ww_stream_rates *rt, const int32_t *ctl_dev)
   for (int k = 0; k < K; ++k) {
     const int j = k < rt->tab.K ? k : 0;  // (a slot above the bank's classes is never picked: a class id is below tab.K)
     const rate_geom &g = rt->tab.g[j];
-    a.c[k] = {rt->r[j] ? rt->r[j]->d_taps : nullptr, rt->d_hist[j], (int)g.up, (int)g.down, (int)g.half, (int)g.tpp, g.F, g.D, g.hist, rt->tab.pass[j] ? 1 : 0};
+    a.c[k] = {rt->r[j] ? rt->r[j]->d_taps : nullptr, rt->d_hist[j], (int)g.up, (int)g.down, (int)g.half, (int)g.tpp, g.F, g.D, g.hist, rt->tab.pass[j] ? 1 : 0,
+              format_bytes(rt->fmt.fmt[j]) == 1 ? rt->fmt.fmt[j] : 0};
   }
   ww_launch_scope scope(rt->ctx, K == 1 ? "stream_rate_tick_kernel" : "stream_rates_tick_kernel");
   hipLaunchKernelGGL((stream_rate_tick_kernel<(K > 1)>), dim3((unsigned)rt->S), dim3(RATE_THREADS), rt->lds_bytes, rt->ctx->stream, a);
@@ -673,7 +772,7 @@ int ww_k_rates_tick(ww_stream_rates *rt, const int16_t *frames, const uint8_t *f
     if (flags[s] & 2) continue;
     rc[s] = rates_tick(rt->tab, rt->cls[(size_t)s], rt->n[(size_t)s]);
   }
-  memcpy(rt->h_in + (size_t)S * sizeof(rate_ctl), frames, (size_t)rt->total * 2);
+  memcpy(rt->h_in + (size_t)S * sizeof(rate_ctl), frames, (size_t)rt->total);
   if (rt->uniform) rates_tick_launch<1>(rt, ctl_dev);
   else rates_tick_launch<WW_STREAM_MAX_RATES>(rt, ctl_dev);
   WW_HIP(ctx, hipGetLastError());
@@ -693,7 +792,7 @@ struct rate_feed_class {
   int64_t seg_total = 0, k_max = 0;
 };
 
-int ww_k_rates_feed(ww_stream_rates *rt, const int32_t *ids, int n, const int16_t *pcm, const int64_t *sample_offs, const int64_t *offs16,
+int ww_k_rates_feed(ww_stream_rates *rt, const int32_t *ids, int n, const void *data, const int64_t *byte_offs, const int64_t *offs16,
                     int16_t *d_dst, bool *moved) {
   ww_ctx *ctx = rt->ctx;
   const int K = rt->tab.K;
@@ -701,22 +800,25 @@ int ww_k_rates_feed(ww_stream_rates *rt, const int32_t *ids, int n, const int16_
   for (int i = 0; i < n; ++i) pc[(size_t)i] = rt->cls[(size_t)ids[i]];
   rates_groups grp;
   rates_group(pc.data(), n, grp);
-  const int64_t s0 = sample_offs[0], samples = sample_offs[n] - s0;
+  // packet i is bytes [byte_offs[i], byte_offs[i + 1]) of `data` in its class's format (the caller has checked int16 packets for
+  // even offsets and lengths); the upload starts at an even byte, so an int16 packet is as aligned on the device as on the host
+  const int64_t s0 = byte_offs[0] & ~(int64_t)1, bytes = byte_offs[n] - s0;
   rate_feed_class work[WW_STREAM_MAX_RATES];
-  size_t need = ww_bump::need((size_t)samples, 2) + 1024;
+  size_t need = ww_bump::need((size_t)bytes, 1) + 1024;
   for (int c = 0; c < K; ++c) {
     rate_feed_class &w = work[c];
+    const int bps = format_bytes(rt->fmt.fmt[c]);
     for (int j = grp.start[c]; j < grp.start[c + 1]; ++j) {
       const int i = grp.order[(size_t)j], s = ids[i];
-      const int64_t k = sample_offs[i + 1] - sample_offs[i];
+      const int64_t k = (byte_offs[i + 1] - byte_offs[i]) / bps, p0 = byte_offs[i] - s0;  // the packet's samples | its first byte of the upload
       if (k == 0) continue;
-      if (!rt->r[c]) {
-        const int64_t so[2] = {sample_offs[i] - s0, sample_offs[i + 1] - s0}, first[1] = {0}, oo[2] = {offs16[i], offs16[i + 1]};
+      if (!rt->r[c]) {  // (the identity form's tiles count samples of the class's format from the upload's start)
+        const int64_t so[2] = {p0 / bps, p0 / bps + k}, first[1] = {0}, oo[2] = {offs16[i], offs16[i + 1]};
         rs_make_plan(&rt->pass_r, so, first, first, oo, 1, w.pl);
         continue;
       }
       const rate_step st = rate_advance(rt->tab.g[c], rt->n[(size_t)s], k);
-      w.str.push_back({sample_offs[i] - s0, k, w.seg_total, s, st.held});
+      w.str.push_back({p0, k, w.seg_total, s, st.held});
       if (st.count > st.zeros) {
         // the segment's first sample is input n - held of the stream; its outputs land behind the zeros of the stream's 16 kHz run
         const int64_t so[2] = {w.seg_total, w.seg_total + st.held + k}, in_first[1] = {rt->n[(size_t)s] - st.held}, out_first[1] = {st.y0},
@@ -741,8 +843,8 @@ int ww_k_rates_feed(ww_stream_rates *rt, const int32_t *ids, int n, const int16_
     rt->scratch_cap = need;
   }
   ww_bump db(rt->d_scratch, rt->scratch_cap);
-  int16_t *d_pk = db.take<int16_t>((size_t)samples);
-  WW_HIP(ctx, hipMemcpyAsync(d_pk, pcm + s0, (size_t)samples * 2, hipMemcpyHostToDevice, ctx->stream));
+  char *d_pk = db.take<char>((size_t)bytes);
+  WW_HIP(ctx, hipMemcpyAsync(d_pk, (const char *)data + s0, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
   if (offs16[n] > 0) WW_HIP(ctx, hipMemsetAsync(d_dst, 0, (size_t)offs16[n] * 2, ctx->stream));  // z's leading zeros
   // (each class has its own region of the scratch: a class's table goes up now, its kernels run later on the stream)
   for (int c = 0; c < K; ++c) {
@@ -753,7 +855,7 @@ int ww_k_rates_feed(ww_stream_rates *rt, const int32_t *ids, int n, const int16_
     rs_tile *d_tiles = db.take<rs_tile>(w.pl.count());
     if (!rt->r[c]) {
       if (w.pl.count() > 0)
-        if (int rc = rs_run(&rt->pass_r, w.pl, d_tiles, d_pk, WW_SAMPLE_I16, d_dst, WW_SAMPLE_I16)) return rc;
+        if (int rc = rs_run(&rt->pass_r, w.pl, d_tiles, d_pk, rt->fmt.fmt[c], d_dst, WW_SAMPLE_I16)) return rc;
       continue;
     }
     *moved = true;
@@ -765,8 +867,8 @@ int ww_k_rates_feed(ww_stream_rates *rt, const int32_t *ids, int n, const int16_
     {
       ww_launch_scope scope(ctx, "stream_rate_splice_kernel");
       hipLaunchKernelGGL(stream_rate_splice_kernel, dim3((unsigned)w.str.size(), (unsigned)((w.k_max + RATE_SPLICE - 1) / RATE_SPLICE)), dim3(256),
-                         (size_t)rt->tab.g[c].hist * 4, ctx->stream, (const int16_t *)d_pk, (const rate_feed_str *)d_str, d_seg, rt->d_hist[c],
-                         (int)rt->tab.g[c].hist);
+                         (size_t)rt->tab.g[c].hist * 4, ctx->stream, (const char *)d_pk, (const rate_feed_str *)d_str, d_seg, rt->d_hist[c],
+                         (int)rt->tab.g[c].hist, format_bytes(rt->fmt.fmt[c]) == 1 ? (int)rt->fmt.fmt[c] : 0);
     }
     WW_HIP(ctx, hipGetLastError());
     if (w.pl.count() > 0)

@@ -141,7 +141,7 @@ static inline void rates_move(int32_t &cls, int64_t &n, int c) {
 
 // The tick's per-stream descriptor (a DEVICE table the bank resends when a stream moves)
 struct rates_desc {
-  int64_t off;  // the frame's first sample in the ragged block
+  int64_t off;  // the frame's first BYTE in the tick's block (2 x its first sample in a bank of int16 frames; stream_formats.h)
   int32_t cls, pad;
 };
 

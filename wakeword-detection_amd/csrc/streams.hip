@@ -105,6 +105,7 @@ struct ww_streams {
   // ww_stream_attach_rates: one ragged block, stream s's frame at its own rate
   ww_stream_rates *rates = nullptr;
   int uniform_frame() const { return rates ? ww_k_rates_frame_samples(rates) : 0; }  // a uniform bank's frame samples; 0: not one
+  bool g711() const { return rates && ww_k_rates_g711(rates); }  // some rate class reads G.711: frames and packets are counted in bytes
   bool used = false;                  // ticked or fed since creation
   // a bank that runs K member slots on every stream (ww_stream_create_set_all; stream_all.h): the model side - stream_model and its
   // device table, gxc, wstate, zring, zpos, h_tag, h_out, the window tables - is sized and indexed by VIRTUAL stream v = s K + slot,
@@ -578,35 +579,61 @@ int ww_stream_create_set_all(ww_ctx *ctx, const ww_model_set *set, int32_t S, co
 // The bank becomes one at the resampler's input rate (include/wwhip.h).  The refusals that depend on the rates and the state object
 // are ww_k_rates_create's (resample.hip; stream_rate.h): the bank of ONE resampling class with every stream in it for good (a uniform
 // bank); no kernel of the bank changes, a tick only reads its samples elsewhere.
+static int attach_resampler_impl(ww_streams *st, const ww_resampler *r, const int32_t *format, const char *what) {
+  ww_ctx *ctx = st->ctx;
+  if (!r) return ww_fail(ctx, WW_EINVAL, "%s: NULL resampler", what);
+  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
+  if (st->uniform_frame()) return ww_fail(ctx, WW_EINVAL, "%s: this bank already has a resampler (%d Hz frames)", what, st->uniform_frame() * 50);
+  if (st->rates) return ww_fail(ctx, WW_EINVAL, "%s: this bank already has per-stream rates (ww_stream_attach_rates)", what);
+  if (st->used) return ww_fail(ctx, WW_ESTATE, "%s: the bank has ticked or been fed: a resampler is attached to a new bank", what);
+  WW_ON_DEVICE(ctx, dev_scope);
+  return ww_k_rates_create(ctx, &r, format, 1, nullptr, st->S, true, what, &st->rates);
+}
+
 int ww_stream_attach_resampler(ww_streams *st, const ww_resampler *r) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
-  ww_ctx *ctx = st->ctx;
-  if (!r) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: NULL resampler");
-  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
-  if (st->uniform_frame()) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: this bank already has a resampler (%d Hz frames)", st->uniform_frame() * 50);
-  if (st->rates) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_resampler: this bank already has per-stream rates (ww_stream_attach_rates)");
-  if (st->used) return ww_fail(ctx, WW_ESTATE, "ww_stream_attach_resampler: the bank has ticked or been fed: a resampler is attached to a new bank");
-  WW_ON_DEVICE(ctx, dev_scope);
-  return ww_k_rates_create(ctx, &r, 1, nullptr, st->S, true, &st->rates);
+  return attach_resampler_impl(st, r, nullptr, "ww_stream_attach_resampler");
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+// ww_stream_attach_resampler for frames and packets of in_format (include/wwhip.h): the uniform bank, [S][F] of the format
+int ww_stream_attach_resampler_fmt(ww_streams *st, const ww_resampler *r, int32_t in_format) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  return attach_resampler_impl(st, r, &in_format, "ww_stream_attach_resampler_fmt");
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
 // A bank whose stream s runs at the input rate of class stream_rate[s] (include/wwhip.h).  What depends on the classes and the state
 // object are ww_k_rates_create's (resample.hip; stream_rates.h); no kernel of the bank changes, a tick only reads its samples elsewhere.
+static int attach_rates_impl(ww_streams *st, const ww_resampler *const *rs, const int32_t *formats, int32_t n_rates, const int32_t *stream_rate,
+                             const char *what) {
+  ww_ctx *ctx = st->ctx;
+  if (!rs) return ww_fail(ctx, WW_EINVAL, "%s: NULL class table", what);
+  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
+  if (n_rates < 1 || n_rates > WW_STREAM_MAX_RATES) return ww_fail(ctx, WW_EINVAL, "%s: %d rate classes: a bank has 1..%d", what, (int)n_rates, WW_STREAM_MAX_RATES);
+  if (st->uniform_frame()) return ww_fail(ctx, WW_EINVAL, "%s: this bank already has a resampler (%d Hz frames)", what, st->uniform_frame() * 50);
+  if (st->rates) return ww_fail(ctx, WW_EINVAL, "%s: this bank already has its rates (%d classes)", what, ww_k_rates_classes(st->rates));
+  if (st->used) return ww_fail(ctx, WW_ESTATE, "%s: the bank has ticked or been fed: rates are attached to a new bank", what);
+  WW_ON_DEVICE(ctx, dev_scope);
+  return ww_k_rates_create(ctx, rs, formats, n_rates, stream_rate, st->S, false, what, &st->rates);
+}
+
 int ww_stream_attach_rates(ww_streams *st, const ww_resampler *const *rs, int32_t n_rates, const int32_t *stream_rate) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
-  ww_ctx *ctx = st->ctx;
-  if (!rs) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: NULL class table");
-  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
-  if (n_rates < 1 || n_rates > WW_STREAM_MAX_RATES)
-    return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: %d rate classes: a bank has 1..%d", (int)n_rates, WW_STREAM_MAX_RATES);
-  if (st->uniform_frame()) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: this bank already has a resampler (%d Hz frames)", st->uniform_frame() * 50);
-  if (st->rates) return ww_fail(ctx, WW_EINVAL, "ww_stream_attach_rates: this bank already has its rates (%d classes)", ww_k_rates_classes(st->rates));
-  if (st->used) return ww_fail(ctx, WW_ESTATE, "ww_stream_attach_rates: the bank has ticked or been fed: rates are attached to a new bank");
-  WW_ON_DEVICE(ctx, dev_scope);
-  return ww_k_rates_create(ctx, rs, n_rates, stream_rate, st->S, false, &st->rates);
+  return attach_rates_impl(st, rs, nullptr, n_rates, stream_rate, "ww_stream_attach_rates");
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+// ww_stream_attach_rates where class k reads its frames and packets as formats[k] (include/wwhip.h): a class is a (rate, format) pair
+// (stream_formats.h).  formats == NULL: ww_stream_attach_rates itself.
+int ww_stream_attach_rates_fmt(ww_streams *st, const ww_resampler *const *rs, const int32_t *formats, int32_t n_rates, const int32_t *stream_rate) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  if (!formats) return attach_rates_impl(st, rs, nullptr, n_rates, stream_rate, "ww_stream_attach_rates");
+  return attach_rates_impl(st, rs, formats, n_rates, stream_rate, "ww_stream_attach_rates_fmt");
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
@@ -614,6 +641,8 @@ int ww_stream_frame_layout(const ww_streams *st, int32_t *frame_samples, int64_t
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
   if (!frame_samples || !frame_offs) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_layout: NULL argument");
+  if (st->g711())
+    return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_layout: this bank has G.711 streams, its frames are counted in bytes: ww_stream_frame_layout_bytes");
   if (st->rates) {
     ww_k_rates_layout(st->rates, frame_samples, frame_offs);
     return WW_OK;
@@ -653,10 +682,29 @@ int ww_stream_set_rate(ww_streams *st, const int32_t *ids, int32_t n, int32_t ra
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
+// The byte layout of a tick's frames on any bank (include/wwhip.h; stream_formats.h: formats_layout)
+int ww_stream_frame_layout_bytes(const ww_streams *st, int32_t *frame_bytes, int64_t *byte_offs, int32_t *formats) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  if (!frame_bytes || !byte_offs || !formats) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_layout_bytes: NULL argument");
+  if (st->rates) {
+    ww_k_rates_layout_bytes(st->rates, frame_bytes, byte_offs, formats);
+    return WW_OK;
+  }
+  for (int s = 0; s <= st->S; ++s) {
+    if (s < st->S) frame_bytes[s] = WW_CHUNK * 2, formats[s] = WW_SAMPLE_I16;
+    byte_offs[s] = (int64_t)s * WW_CHUNK * 2;
+  }
+  return WW_OK;
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
 int ww_stream_frame_samples(const ww_streams *st, int32_t *out) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
   if (!out) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_samples: NULL argument");
+  if (st->g711())
+    return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_samples: this bank has G.711 streams, its frames are counted in bytes: ww_stream_frame_layout_bytes");
   if (st->rates && !st->uniform_frame())
     return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_samples: the streams of this bank have frames of their own: ww_stream_frame_layout");
   *out = st->rates ? st->uniform_frame() : WW_CHUNK;
@@ -1029,10 +1077,13 @@ int ww_stream_feed_rows(ww_streams *st, const int32_t *ids, int32_t n, const int
 // ww_stream_feed, and ww_stream_feed_all (all: a bank of K member slots per stream, stream_all.h).  The plan, the uploaded samples, the
 // front end and the host's mirrors are the PHYSICAL streams' and run once whatever K is; the model side - the sequence kernel's
 // every-member form, the tail's tables, the logits and posteriors - is the virtual streams' v = s K + slot.
+// byte_offs (ww_stream_feed_bytes on a bank with G.711 streams): packet i is bytes [byte_offs[i], byte_offs[i + 1]) of pcm in its
+// stream's format, and sample_offs counts its samples; nullptr: pcm is int16 and packet i is its samples [sample_offs[i], sample_offs[i + 1]).
 static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const int16_t *pcm, const int64_t *sample_offs, int64_t cap_rows,
-                            int64_t *row_offs, float *post, float *mel, bool *mutated, bool all = false) {
+                            int64_t *row_offs, float *post, float *mel, bool *mutated, bool all = false, const int64_t *byte_offs = nullptr,
+                            const char *what = nullptr) {
   ww_ctx *ctx = st->ctx;
-  const char *what = all ? "ww_stream_feed_all" : "ww_stream_feed";
+  if (!what) what = all ? "ww_stream_feed_all" : "ww_stream_feed";
   std::vector<int64_t> offs16, offs_out((size_t)(n > 0 ? n : 0) + 1, 0);
   // (the caller's row_offs is written when no refusal is left)
   if (int rc = feed_check(st, ids, n, sample_offs, sample_offs && row_offs ? offs_out.data() : nullptr, what, &offs16, all)) return rc;
@@ -1081,7 +1132,13 @@ static int stream_feed_impl(ww_streams *st, const int32_t *ids, int32_t n, const
   float *d_post_rows = all ? db.take<float>((size_t)rows * K) : d_post;
   if (int rc = tb.send(ctx, d_tab)) return rc;
   if (st->rates) {  // (the bank's 16 kHz samples land in d_pcm itself)
-    if (int rc = ww_k_rates_feed(st->rates, ids, n, pcm, in_offs, sample_offs, d_pcm, mutated)) return rc;
+    std::vector<int64_t> twice;
+    if (!byte_offs) {
+      twice.resize((size_t)n + 1);
+      for (int i = 0; i <= n; ++i) twice[(size_t)i] = 2 * in_offs[i];
+      byte_offs = twice.data();
+    }
+    if (int rc = ww_k_rates_feed(st->rates, ids, n, pcm, byte_offs, sample_offs, d_pcm, mutated)) return rc;
     if (samples == 0) {  // the packets moved the streams' resampling state and completed no 16 kHz sample
       WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
       return WW_OK;
@@ -1124,6 +1181,7 @@ int ww_stream_feed(ww_streams *st, const int32_t *ids, int32_t n, const int16_t 
                    int64_t *row_offs, float *post, float *mel) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
+  if (st->g711()) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_feed: this bank has G.711 streams, its packets are counted in bytes: ww_stream_feed_bytes");
   bool mutated = false;
   const int rc = stream_feed_impl(st, ids, n, pcm, sample_offs, cap_rows, row_offs, post, mel, &mutated);
   if (rc != WW_OK && mutated) st->broken = true;
@@ -1144,10 +1202,54 @@ int ww_stream_feed_all(ww_streams *st, const int32_t *ids, int32_t n, const int1
                        int64_t *row_offs, float *post, float *mel) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
+  if (st->g711()) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_feed_all: this bank has G.711 streams, its packets are counted in bytes: ww_stream_feed_bytes_all");
   bool mutated = false;
   const int rc = stream_feed_impl(st, ids, n, pcm, sample_offs, cap_rows, row_offs, post, mel, &mutated, true);
   if (rc != WW_OK && mutated) st->broken = true;
   return rc;
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+// ww_stream_feed_bytes / _all (include/wwhip.h): the packets' samples are counted per stream format (stream_formats.h: formats_packet)
+// - a refusal there, like every other, comes before any state moves -, then the call is ww_stream_feed's: on a bank without G.711
+// streams with sample_offs = byte_offs / 2, on a bank with them with the byte offsets beside the sample counts.
+static int stream_feed_bytes(ww_streams *st, const int32_t *ids, int32_t n, const void *data, const int64_t *byte_offs, int64_t cap_rows, int64_t *row_offs,
+                             float *post, float *mel, bool all) {
+  const char *what = all ? "ww_stream_feed_bytes_all" : "ww_stream_feed_bytes";
+  bool mutated = false;
+  std::vector<int64_t> so;
+  const bool g711 = st->g711();
+  if (n > 0 && ids && byte_offs) {  // (anything else is feed_check's refusal)
+    so.assign((size_t)n + 1, g711 ? 0 : byte_offs[0] / 2);
+    if (!g711 && (byte_offs[0] & 1)) return ww_fail(st->ctx, WW_EINVAL, "%s: packet 0: an int16 packet starts at byte %lld: an odd offset", what, (long long)byte_offs[0]);
+    char why[200];
+    for (int i = 0; i < n; ++i) {
+      const int s = ids[i];
+      const int32_t fmt = g711 && s >= 0 && s < st->S ? ww_k_rates_stream_format(st->rates, s) : WW_SAMPLE_I16;  // (an id out of range: feed_check's refusal)
+      int64_t k = 0;
+      if (formats_packet(fmt, i, byte_offs[i], byte_offs[i + 1], &k, why, sizeof why)) return ww_fail(st->ctx, WW_EINVAL, "%s: %s", what, why);
+      so[(size_t)i + 1] = so[(size_t)i] + k;
+    }
+  }
+  const int64_t *sample_offs = so.empty() ? byte_offs : so.data();
+  const int rc = stream_feed_impl(st, ids, n, (const int16_t *)data, sample_offs, cap_rows, row_offs, post, mel, &mutated, all, g711 && !so.empty() ? byte_offs : nullptr, what);
+  if (rc != WW_OK && mutated) st->broken = true;
+  return rc;
+}
+
+int ww_stream_feed_bytes(ww_streams *st, const int32_t *ids, int32_t n, const void *data, const int64_t *byte_offs, int64_t cap_rows, int64_t *row_offs,
+                         float *post, float *mel) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  return stream_feed_bytes(st, ids, n, data, byte_offs, cap_rows, row_offs, post, mel, false);
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+int ww_stream_feed_bytes_all(ww_streams *st, const int32_t *ids, int32_t n, const void *data, const int64_t *byte_offs, int64_t cap_rows, int64_t *row_offs,
+                             float *post, float *mel) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  return stream_feed_bytes(st, ids, n, data, byte_offs, cap_rows, row_offs, post, mel, true);
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 

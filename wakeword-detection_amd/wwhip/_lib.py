@@ -25,6 +25,7 @@ PRECISION_FP32, PRECISION_BF16X3 = 0, 1
 OPT_CRNN_SPLIT_AT, OPT_CRNN_SLIDE_MIN, OPT_CRNN_TAIL_MFMA, OPT_WAVENET_ROWMAJOR, OPT_WAVE_SEQ_SEGMENT = 1, 2, 3, 4, 5
 STREAM_FULL_RECOMPUTE, STREAM_TWO_LAUNCH, STREAM_SYNC_WAIT, STREAM_CAUSAL = 1, 2, 4, 8
 SAMPLE_I16, SAMPLE_F32 = 0, 1
+SAMPLE_MULAW, SAMPLE_ALAW = 8, 9  # G.711, one byte per sample: input formats
 SET_MAX_MODELS = 64  # include/wwhip.h: WW_SET_MAX_MODELS
 ABI = 4  # include/wwhip.h: WW_ABI - the signatures this binding was written against
 
@@ -91,6 +92,7 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_filter_apply": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "ww_detect": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
     "ww_logmel_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _P(FrontendParams), _vp]),
+    "ww_g711_table": (C.c_int, [_i32, _vp]),
     "ww_resampler_create": (C.c_int, [_vp, _i32, _i32, _vp, _P(_vp)]),
     "ww_resampler_destroy": (C.c_int, [_vp]),
     "ww_resampler_info": (C.c_int, [_vp, _vp]),
@@ -127,6 +129,11 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_stream_attach_rates": (C.c_int, [_vp, _vp, _i32, _vp]),
     "ww_stream_frame_layout": (C.c_int, [_vp, _vp, _vp]),
     "ww_stream_set_rate": (C.c_int, [_vp, _vp, _i32, _i32]),
+    "ww_stream_attach_rates_fmt": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
+    "ww_stream_attach_resampler_fmt": (C.c_int, [_vp, _vp, _i32]),
+    "ww_stream_frame_layout_bytes": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ww_stream_feed_bytes": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ww_stream_feed_bytes_all": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "ww_stream_feed_rows": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     "ww_stream_feed": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "ww_stream_feed_rows_all": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),

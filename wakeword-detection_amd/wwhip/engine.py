@@ -656,9 +656,36 @@ def _stream_rates(sample_rate, n_streams: int, resampler) -> Tuple[np.ndarray, L
     return rates.astype(np.int32), classes
 
 
+SAMPLE_FORMATS = {"pcm16": _lib.SAMPLE_I16, "mulaw": _lib.SAMPLE_MULAW, "alaw": _lib.SAMPLE_ALAW}  # a stream's format -> WW_SAMPLE_*
+_FORMAT_NAMES = {v: k for k, v in SAMPLE_FORMATS.items()}
+_FORMAT_DTYPE = {"pcm16": np.dtype(np.int16), "mulaw": np.dtype(np.uint8), "alaw": np.dtype(np.uint8)}
+
+
+def _stream_formats(sample_format, n_streams: int) -> Optional[List[str]]:
+    """``sample_format`` -> one format name per stream, or None when every stream reads pcm16 (a bank without formats).  Everything
+    that can be refused without a device is refused here."""
+    names = [sample_format] * n_streams if isinstance(sample_format, str) else list(sample_format)
+    if len(names) != n_streams:
+        raise ValueError(f"sample_format must name one format per stream ({n_streams}), got {len(names)}")
+    for f in names:
+        if not isinstance(f, str) or f not in SAMPLE_FORMATS:
+            raise ValueError(f"unknown sample format {f!r}: one of {', '.join(SAMPLE_FORMATS)}")
+    return None if all(f == "pcm16" for f in names) else names
+
+
+def _checked_samples(a, fmt: str, what: str) -> np.ndarray:
+    """``a`` as a flat contiguous array of the dtype ``fmt`` is carried in - int16 for pcm16, uint8 codes for mulaw / alaw; an array
+    of the other kind is refused, not converted."""
+    a = np.asarray(a)
+    if a.dtype != _FORMAT_DTYPE[fmt]:
+        raise ValueError(f"{what} reads {fmt}: its samples are {_FORMAT_DTYPE[fmt]}, not {a.dtype}")
+    return np.ascontiguousarray(a).ravel()
+
+
 class StreamBank:
     """S device-resident streams advanced 20 ms per :meth:`step` (``ww_stream_*``)."""
     _mixed = False  # per-stream rates (sample_rate given as a sequence)
+    _g711 = False  # some stream reads G.711 (sample_format=): frames and packets are byte blocks
     members, n_members = None, 0  # the member slots of a bank that runs every listed member on every stream (members=)
 
     def _no_every(self, what: str) -> None:
@@ -668,7 +695,8 @@ class StreamBank:
 
     def __init__(self, engine, n_streams: int, fp: Optional[_lib.FrontendParams] = None,
                  full_recompute: bool = False, two_launch: bool = False, sync_wait: bool = False, causal: bool = False,
-                 models: Optional[Sequence[int]] = None, sample_rate: int = 16000, resampler=None, members=None) -> None:
+                 models: Optional[Sequence[int]] = None, sample_rate: int = 16000, resampler=None, members=None,
+                 sample_format="pcm16") -> None:
         """``full_recompute``: every streaming CRNN window recomputed from its mel rows (``WW_STREAM_FULL_RECOMPUTE``)
         instead of the incremental kernel.  ``two_launch``: the incremental CRNN's tick as a front-end kernel + a model kernel
         (``WW_STREAM_TWO_LAUNCH``; default: ONE launch per tick).  ``sync_wait``: wait for a tick with ``hipStreamSynchronize``
@@ -694,12 +722,33 @@ class StreamBank:
         states.  :meth:`step` takes the frames of S streams as always and returns ``(post[S, K, 2], n[S])``: ``post[s, j]`` is the
         bits a bank of member ``members[j]`` alone yields.  :meth:`reset`, :meth:`window`, :meth:`set_rate` and ``sample_rate`` work
         as before; a causal bank of this kind is fed in packets by :meth:`feed_all`, and :meth:`step_trigger_all` is its wake-word
-        stage (``wwhip.wakeword.WakewordSetBank``); :meth:`feed`, :meth:`set_model` and :meth:`step_trigger` raise ``ValueError``."""
+        stage (``wwhip.wakeword.WakewordSetBank``); :meth:`feed`, :meth:`set_model` and :meth:`step_trigger` raise ``ValueError``.
+        ``sample_format``: ``"pcm16"`` (the default), ``"mulaw"`` or ``"alaw"`` - G.711, one byte per sample, as a telephony leg
+        carries it, decoded in the kernels that read the samples -, or a sequence of S of them.  A G.711 stream yields the bits it
+        yields given its decoded int16 samples.  A scalar rate other than 16000 with a scalar format is the uniform bank
+        (``ww_stream_attach_resampler_fmt``): :meth:`step` takes ``[S, frame_samples]`` uint8.  Anything else is the per-stream form
+        (``ww_stream_attach_rates_fmt``; a class is a (rate, format) pair, up to 8): :meth:`step` takes the flat uint8 block of
+        ``frame_byte_offs[S]`` bytes - stream ``s``'s ``frame_bytes[s]`` bytes from ``frame_byte_offs[s]``; an int16 frame starts on
+        an even byte, behind one pad byte where needed - or S per-stream arrays, int16 for a pcm16 stream and uint8 for a G.711
+        one (an array of the other kind is refused).  :meth:`feed` / :meth:`feed_all` take per-stream packets the same way, and
+        :meth:`set_rate` takes the format beside the rate.  :attr:`sample_formats`, :attr:`frame_bytes` and
+        :attr:`frame_byte_offs` are there on every bank."""
         self.engine = engine
         self.S = int(n_streams)
+        formats = _stream_formats(sample_format, self.S)
         self.members = None if members is None else _member_slots(members, engine, self.S, models, full_recompute)
         self.n_members = 0 if self.members is None else int(self.members.size)
-        if not isinstance(sample_rate, (int, np.integer)):
+        scalar_rate = isinstance(sample_rate, (int, np.integer))
+        if formats is not None and not (scalar_rate and isinstance(sample_format, str) and int(sample_rate) != 16000):
+            rates, _ = _stream_rates([int(sample_rate)] * self.S if scalar_rate else sample_rate, self.S, resampler)
+            pairs = list(dict.fromkeys(zip(rates.tolist(), formats)))
+            if len(pairs) > MAX_RATES:
+                raise ValueError(f"{len(pairs)} distinct (rate, format) pairs: a bank has at most {MAX_RATES} classes")
+            self._create(engine, fp, full_recompute, two_launch, sync_wait, causal, models)
+            self._attach_rates(rates, pairs, formats)
+            self._tick_arrays()
+            return
+        if not scalar_rate:
             rates, classes = _stream_rates(sample_rate, self.S, resampler)
             self._create(engine, fp, full_recompute, two_launch, sync_wait, causal, models)
             self._attach_rates(rates, classes)
@@ -720,10 +769,14 @@ class StreamBank:
             if self._resampler is None:
                 from .resample import Resampler
                 self._resampler, self._own_resampler = Resampler(self.sample_rate, 16000, engine.ctx), True
-            _lib.raise_for(self._lib.ww_stream_attach_resampler(self._h, self._resampler._h), engine.ctx.handle)
-            n = C.c_int32(0)
-            _lib.raise_for(self._lib.ww_stream_frame_samples(self._h, C.byref(n)), engine.ctx.handle)
-            assert n.value == self.frame_samples
+            if formats is not None:  # the uniform bank of one G.711 format
+                self._g711, self._uniform_format = True, formats[0]
+                _lib.raise_for(self._lib.ww_stream_attach_resampler_fmt(self._h, self._resampler._h, SAMPLE_FORMATS[formats[0]]), engine.ctx.handle)
+            else:
+                _lib.raise_for(self._lib.ww_stream_attach_resampler(self._h, self._resampler._h), engine.ctx.handle)
+                n = C.c_int32(0)
+                _lib.raise_for(self._lib.ww_stream_frame_samples(self._h, C.byref(n)), engine.ctx.handle)
+                assert n.value == self.frame_samples
         self._shape = (self.S, self.frame_samples)
         self._tick_arrays()
 
@@ -752,17 +805,28 @@ class StreamBank:
         self._h = h
         _lib.register("streams", self)
 
-    def _attach_rates(self, rates: np.ndarray, classes: List[int]) -> None:
+    def _attach_rates(self, rates: np.ndarray, classes: List, formats: Optional[List[str]] = None) -> None:
+        """``classes``: the bank's rates - or, with ``formats`` (one name per stream), its (rate, format) pairs - in class order."""
         from .resample import Resampler
         self._mixed, self.sample_rate = True, None
         self._classes, self._resampler, self._own_resampler = classes, None, False
         self._class_rs = []
+        self._g711 = formats is not None
         try:
-            for r in classes:
-                self._class_rs.append(None if r == 16000 else Resampler(r, 16000, self.engine.ctx))
-            table = (C.c_void_p * len(classes))(*[None if r is None else r._h for r in self._class_rs])
-            cls = np.array([classes.index(int(r)) for r in rates], np.int32)
-            _lib.raise_for(self._lib.ww_stream_attach_rates(self._h, table, len(classes), _lib.ptr(cls)), self.engine.ctx.handle)
+            by_rate = {}  # (two formats of one rate share the rate's resampler)
+            for c in classes:
+                r = c[0] if self._g711 else c
+                if r != 16000 and r not in by_rate:
+                    by_rate[r] = Resampler(r, 16000, self.engine.ctx)
+                    self._class_rs.append(by_rate[r])
+            table = (C.c_void_p * len(classes))(*[None if (c[0] if self._g711 else c) == 16000 else by_rate[c[0] if self._g711 else c]._h for c in classes])
+            if self._g711:
+                cls = np.array([classes.index((int(r), f)) for r, f in zip(rates, formats)], np.int32)
+                fm = np.array([SAMPLE_FORMATS[c[1]] for c in classes], np.int32)
+                _lib.raise_for(self._lib.ww_stream_attach_rates_fmt(self._h, table, _lib.ptr(fm), len(classes), _lib.ptr(cls)), self.engine.ctx.handle)
+            else:
+                cls = np.array([classes.index(int(r)) for r in rates], np.int32)
+                _lib.raise_for(self._lib.ww_stream_attach_rates(self._h, table, len(classes), _lib.ptr(cls)), self.engine.ctx.handle)
             self._read_layout()
             assert np.array_equal(self.frame_samples, rates // 50)
         except Exception:
@@ -771,6 +835,13 @@ class StreamBank:
 
     def _read_layout(self) -> None:
         """``frame_samples``, ``frame_offs`` and ``sample_rates`` as the library states them (``ww_stream_frame_layout``)."""
+        fb, bo, fm = np.zeros(self.S, np.int32), np.zeros(self.S + 1, np.int64), np.zeros(self.S, np.int32)
+        _lib.raise_for(self._lib.ww_stream_frame_layout_bytes(self._h, _lib.ptr(fb), _lib.ptr(bo), _lib.ptr(fm)), self.engine.ctx.handle)
+        self.frame_bytes, self.frame_byte_offs, self.sample_formats = fb, bo, [_FORMAT_NAMES[int(v)] for v in fm]
+        if self._g711:  # (frame_offs counts int16 samples: such a bank has none)
+            fs = fb // np.where(fm == _lib.SAMPLE_I16, 2, 1).astype(np.int32)
+            self.frame_samples, self.frame_offs, self.sample_rates = fs, None, fs * 50
+            return
         fs, fo = np.zeros(self.S, np.int32), np.zeros(self.S + 1, np.int64)
         _lib.raise_for(self._lib.ww_stream_frame_layout(self._h, _lib.ptr(fs), _lib.ptr(fo)), self.engine.ctx.handle)
         self.frame_samples, self.frame_offs, self.sample_rates = fs, fo, fs * 50
@@ -785,7 +856,10 @@ class StreamBank:
         self._keep = None
         if not self._mixed:
             self.sample_rates = np.full(self.S, self.sample_rate, np.int32)
-            self.frame_offs = np.arange(self.S + 1, dtype=np.int64) * self.frame_samples
+            self.frame_offs = None if self._g711 else np.arange(self.S + 1, dtype=np.int64) * self.frame_samples
+            self.sample_formats = [self._uniform_format if self._g711 else "pcm16"] * self.S
+            self.frame_bytes = np.full(self.S, self.frame_samples * (1 if self._g711 else 2), np.int32)
+            self.frame_byte_offs = np.arange(self.S + 1, dtype=np.int64) * int(self.frame_samples * (1 if self._g711 else 2))
 
     def _ragged_address(self, frames) -> int:
         """A bank with per-stream rates: the flat int16 block of ``frame_offs[S]`` samples, or S per-stream arrays."""
@@ -803,7 +877,39 @@ class StreamBank:
                              f"{'/'.join(str(int(v)) for v in sorted(set(self.frame_samples.tolist())))} samples from frame_offs[s]), got {f.size}")
         return f.ctypes.data
 
+    def _byte_address(self, frames) -> int:
+        """A bank with G.711 streams: the uniform bank's ``[S, frame_samples]`` uint8, or a per-stream bank's flat uint8 block of
+        ``frame_byte_offs[S]`` bytes or S per-stream arrays, each of its stream's dtype (they are laid out with the pad bytes)."""
+        f = frames
+        total = int(self.frame_byte_offs[self.S])
+        if not self._mixed:
+            if not (type(f) is np.ndarray and f.dtype == np.uint8 and f.flags.c_contiguous):
+                f = self._keep = _checked_samples(frames, self.sample_formats[0] if self.S else "mulaw", "this bank").reshape(np.shape(frames))
+            if f.shape != self._shape:
+                raise ValueError(f"frames must be [{self.S}, {self._shape[1]}] uint8")
+            return f.ctypes.data
+        if type(f) is np.ndarray and f.ndim == 1 and f.dtype != object:
+            if f.dtype != np.uint8:
+                raise ValueError(f"the flat block of a bank with G.711 streams is uint8 ({total} bytes: ww_stream_frame_layout_bytes), not {f.dtype}")
+            if not f.flags.c_contiguous:
+                f = self._keep = np.ascontiguousarray(f)
+        else:
+            if len(f) != self.S:
+                raise ValueError(f"frames must be one array per stream ({self.S}) or the flat block of {total} bytes")
+            block = np.zeros(total, np.uint8)
+            for s, a in enumerate(f):
+                a = _checked_samples(a, self.sample_formats[s], f"stream {s}")
+                if a.nbytes != int(self.frame_bytes[s]):
+                    raise ValueError(f"stream {s}'s frame has {int(self.frame_samples[s])} samples, got {a.size}")
+                block[int(self.frame_byte_offs[s]):int(self.frame_byte_offs[s]) + a.nbytes] = a.view(np.uint8)
+            f = self._keep = block
+        if f.size != total:
+            raise ValueError(f"frames must hold {total} bytes (ww_stream_frame_layout_bytes), got {f.size}")
+        return f.ctypes.data
+
     def _frames_address(self, frames: np.ndarray) -> int:
+        if self._g711:
+            return self._byte_address(frames)
         if self._mixed:
             return self._ragged_address(frames)
         f = frames
@@ -872,18 +978,29 @@ class StreamBank:
             raise ValueError("stream id out of range")
         _lib.raise_for(self._lib.ww_stream_set_model(self._h, _lib.ptr(a), 0 if a is None else a.size, int(model)), self.engine.ctx.handle)
 
-    def set_rate(self, ids: Optional[Sequence[int]], rate: int) -> None:
+    def set_rate(self, ids: Optional[Sequence[int]], rate: int, sample_format: Optional[str] = None) -> None:
         """Move the listed streams (``None``: all) to ``rate`` Hz, one of the rates the bank was built with, and reset them
         (``ww_stream_set_rate``: the next sample is the first of a new signal).  ``frame_samples``, ``frame_offs`` and
-        ``sample_rates`` are read again: the layout of a tick's frames changes with the move."""
+        ``sample_rates`` are read again: the layout of a tick's frames changes with the move.  A bank built with ``sample_format``:
+        the streams move to the class (``rate``, ``sample_format``); the format may be left out where the bank has the rate in one
+        format only."""
         if not self._mixed:
             raise ValueError("set_rate: this bank runs at one rate (sample_rate was not given per stream)")
-        if int(rate) not in self._classes:
+        if self._g711:
+            if sample_format is not None and sample_format not in SAMPLE_FORMATS:
+                raise ValueError(f"unknown sample format {sample_format!r}: one of {', '.join(SAMPLE_FORMATS)}")
+            hits = [c for c in self._classes if c[0] == int(rate) and sample_format in (None, c[1])]
+            if len(hits) != 1:
+                raise ValueError(f"set_rate: ({rate} Hz, {sample_format}) names {len(hits)} of the bank's classes {self._classes}")
+            rate = hits[0]
+        elif sample_format not in (None, "pcm16"):
+            raise ValueError(f"set_rate: this bank's streams all read pcm16, not {sample_format}")
+        if (rate if self._g711 else int(rate)) not in self._classes:
             raise ValueError(f"set_rate: {rate} Hz is not among the bank's rates {self._classes}")
         a = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
         if a is not None and a.size and (a.min() < 0 or a.max() >= self.S):
             raise ValueError("stream id out of range")
-        _lib.raise_for(self._lib.ww_stream_set_rate(self._h, _lib.ptr(a), 0 if a is None else a.size, self._classes.index(int(rate))),
+        _lib.raise_for(self._lib.ww_stream_set_rate(self._h, _lib.ptr(a), 0 if a is None else a.size, self._classes.index(rate if self._g711 else int(rate))),
                        self.engine.ctx.handle)
         self._read_layout()
 
@@ -901,6 +1018,8 @@ class StreamBank:
         otherwise).  However the samples are cut into packets, calls and :meth:`step` ticks, the results are the same bits.
         A bank at another rate, or with per-stream rates: each packet is at its stream's own rate."""
         self._no_every("feed")
+        if self._g711:
+            return self._feed_bytes(ids, packets, want_mel, False)
         a_ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
         n = int(a_ids.size)
         if len(packets) != n:
@@ -928,6 +1047,8 @@ class StreamBank:
         be cut into ``feed_all`` packets, calls and :meth:`step` ticks in any way."""
         if not self.n_members:
             raise ValueError("feed_all: this bank was not built with members=: an ordinary causal bank takes feed")
+        if self._g711:
+            return self._feed_bytes(ids, packets, want_mel, True)
         a_ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
         n = int(a_ids.size)
         if len(packets) != n:
@@ -946,6 +1067,40 @@ class StreamBank:
                                                     _lib.ptr(post), _lib.ptr(mel) if want_mel else None), h)
         posts = [post[row_offs[i]:row_offs[i + 1]].copy() for i in range(n)]
         mels = [mel[row_offs[i]:row_offs[i + 1]].copy() for i in range(n)] if want_mel else None
+        return posts, mels
+
+    def _feed_bytes(self, ids: Sequence[int], packets: Sequence[np.ndarray], want_mel: bool, every: bool):
+        """:meth:`feed` / :meth:`feed_all` of a bank with G.711 streams (``ww_stream_feed_bytes`` / ``_all``): ``packets[i]`` is int16
+        for a pcm16 stream and uint8 for a G.711 one.  A call's packets are one byte buffer without gaps, and an int16 packet starts
+        on an even byte: the int16 packets go first, the results come back in the caller's order."""
+        a_ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        n = int(a_ids.size)
+        if len(packets) != n:
+            raise ValueError("one packet per listed stream")
+        if n and (a_ids.min() < 0 or a_ids.max() >= self.S):
+            raise ValueError("stream id out of range")
+        pk = [_checked_samples(p, self.sample_formats[int(s)], f"stream {int(s)}") for s, p in zip(a_ids, packets)]
+        order = sorted(range(n), key=lambda i: pk[i].dtype != np.int16)  # (stable: int16 packets first)
+        a_ids = np.ascontiguousarray(a_ids[order]) if n else a_ids
+        pk = [pk[i].view(np.uint8) for i in order]
+        offs = np.zeros(n + 1, np.int64)
+        np.cumsum([p.size for p in pk], out=offs[1:])
+        counts = np.zeros(n + 1, np.int64)  # the packets' samples, for ww_stream_feed_rows
+        np.cumsum([p.size // (2 if self.sample_formats[int(s)] == "pcm16" else 1) for s, p in zip(a_ids, pk)], out=counts[1:])
+        data = np.concatenate(pk) if n and offs[n] else np.zeros(2, np.uint8)
+        row_offs = np.zeros(n + 1, np.int64)
+        h, K = self.engine.ctx.handle, self.n_members
+        rows_fn, feed_fn = ((self._lib.ww_stream_feed_rows_all, self._lib.ww_stream_feed_bytes_all) if every
+                            else (self._lib.ww_stream_feed_rows, self._lib.ww_stream_feed_bytes))
+        _lib.raise_for(rows_fn(self._h, _lib.ptr(a_ids), n, _lib.ptr(counts), _lib.ptr(row_offs)), h)
+        rows = int(row_offs[n])
+        post = np.empty((max(rows, 1), K) if every else max(rows, 1), np.float32)
+        mel = np.empty((max(rows, 1), self.engine.n_mel), np.float32) if want_mel else None
+        _lib.raise_for(feed_fn(self._h, _lib.ptr(a_ids), n, _lib.ptr(data), _lib.ptr(offs), rows, _lib.ptr(row_offs), _lib.ptr(post),
+                               _lib.ptr(mel) if want_mel else None), h)
+        back = np.argsort(order) if n else []
+        posts = [post[row_offs[j]:row_offs[j + 1]].copy() for j in back]
+        mels = [mel[row_offs[j]:row_offs[j + 1]].copy() for j in back] if want_mel else None
         return posts, mels
 
     def step_trigger_all(self, frames: np.ndarray, p_is_speech, p_is_active, p_thresholds, p_state) -> None:

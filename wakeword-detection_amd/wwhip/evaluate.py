@@ -59,7 +59,12 @@ class _Phases:
 def read_wav(path: str, sample_rate: int = 16000, resample: bool = False) -> np.ndarray:
     """PCM16 mono wav -> float32 in [-1, 1) exactly as ``librosa.load(path, sr=sample_rate)``
     returns it when no resampling is needed (int16 / 32768).  ``resample=True``: a file at another rate is converted on the
-    GPU (:func:`wwhip.resample.load` - this project's filter, not librosa's) instead of refused."""
+    GPU (:func:`wwhip.resample.load` - this project's filter, not librosa's) instead of refused.  A G.711 wav (mu-law, A-law;
+    ``resample=True``) is decoded, and resampled where its rate asks for it, in one device pass."""
+    g = _g711_header(path, sample_rate, resample)
+    if g is not None:
+        from .resample import load
+        return load(path, sr=sample_rate)
     with wave.open(path, "rb") as w:
         if w.getsampwidth() != 2:
             raise ValueError(f"{path}: only 16-bit PCM is supported")
@@ -73,6 +78,20 @@ def read_wav(path: str, sample_rate: int = 16000, resample: bool = False) -> np.
             raw = raw.reshape(-1, w.getnchannels()).astype(np.float32).mean(axis=1) / np.float32(32768.0)
             return raw.astype(np.float32)
     return raw.astype(np.float32) / np.float32(32768.0)
+
+
+def _g711_header(path: str, sample_rate: int, resample: bool):
+    """The header of a G.711 wav (``wave`` cannot open one), None for any other file.  G.711 is decoded on the device, by the
+    resampler's kernels: such a file is opened with ``resample=True``."""
+    from .resample import _g711_wav
+    g = _g711_wav(str(path), header_only=True)
+    if g is None:
+        return None
+    if not resample and g.rate != sample_rate:
+        raise ValueError(f"{path}: sample rate {g.rate} != {sample_rate} (no resampler here)")
+    if not resample:
+        raise ValueError(f"{path}: a G.711 ({g.law}) wav is decoded by the resampler: open it with resample=True")
+    return g
 
 
 def frame_schedule(n_padded_per_file: Sequence[int], hop: int = 160, chunk: int = 320,
@@ -148,6 +167,10 @@ def get_posterior(models_dir, model_type, eval_type, test_files, frame_width, sa
 def wav_length(path: str, sample_rate: int = 16000, resample: bool = False) -> int:
     """Samples ``read_wav(path)`` would return, from the header alone (``resample=True``: ``ceil(n * up / down)`` for a file
     at another rate)."""
+    g = _g711_header(path, sample_rate, resample)
+    if g is not None:
+        from .resample import out_len, ratio
+        return out_len(g.frames, *ratio(g.rate, sample_rate))
     with wave.open(path, "rb") as w:
         if w.getframerate() != sample_rate and resample:
             from .resample import out_len, ratio
@@ -159,6 +182,8 @@ def wav_length(path: str, sample_rate: int = 16000, resample: bool = False) -> i
 
 def read_wav_pcm(path: str, sample_rate: int = 16000, resample: bool = False) -> np.ndarray:
     """Mono PCM16 wav as int16 (``librosa.load`` = these / 32768); anything else as :func:`read_wav`'s float32."""
+    if _g711_header(path, sample_rate, resample) is not None:
+        return read_wav(path, sample_rate, resample)
     with wave.open(path, "rb") as w:
         if w.getsampwidth() == 2 and w.getnchannels() == 1 and w.getframerate() == sample_rate:
             return np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16)

@@ -82,7 +82,14 @@ def first_needed(m: int, up: int, down: int, half: int) -> int:
 _SAMPLE = {np.dtype(np.int16): 0, np.dtype(np.float32): 1}
 
 
-def _sample_format(dtype) -> int:
+def _sample_format(dtype, law: Optional[str] = None) -> int:
+    """The library's format of samples of ``dtype``; with ``law`` ("mulaw" / "alaw"): of G.711 codes, which are uint8."""
+    if law is not None:
+        from .g711 import sample_format
+        fmt = sample_format(law)
+        if np.dtype(dtype) != np.uint8:
+            raise ValueError(f"{law} samples are uint8 codes, not {np.dtype(dtype)}")
+        return fmt
     try:
         return _SAMPLE[np.dtype(dtype)]
     except KeyError:
@@ -116,9 +123,10 @@ class Resampler:
         return history(self.up, self.half)
 
     def ranges(self, segments: Sequence[np.ndarray], in_first: Optional[Sequence[int]], out_first: Optional[Sequence[int]],
-               counts: Sequence[int], dtype=np.float32) -> List[np.ndarray]:
+               counts: Sequence[int], dtype=np.float32, law: Optional[str] = None) -> List[np.ndarray]:
         """Outputs ``[out_first[u], out_first[u] + counts[u])`` of the signals whose samples ``in_first[u] ..`` are
-        ``segments[u]`` (all int16 or all float32), in ONE launch; samples outside a segment read as zero."""
+        ``segments[u]`` (all int16 or all float32; with ``law``: all uint8 G.711 codes, decoded in the kernels), in ONE launch;
+        samples outside a segment read as zero."""
         lib = self._lib
         out_fmt = _sample_format(dtype)
         if len(segments) == 0:
@@ -126,7 +134,7 @@ class Resampler:
         kinds = {np.asarray(s).dtype for s in segments}
         if len(kinds) != 1:
             raise ValueError("the segments of one call are all int16 or all float32")
-        in_fmt = _sample_format(kinds.pop())
+        in_fmt = _sample_format(kinds.pop(), law)
         segs = [np.ascontiguousarray(s).reshape(-1) for s in segments]
         so = np.zeros(len(segs) + 1, np.int64)
         np.cumsum([len(s) for s in segs], out=so[1:])
@@ -141,27 +149,28 @@ class Resampler:
         lib.raise_for(rc, self.ctx.handle)
         return [y[oo[u]:oo[u + 1]] for u in range(len(segs))]
 
-    def range(self, x: np.ndarray, in_first: int, out_first: int, count: int, dtype=np.float32) -> np.ndarray:
-        return self.ranges([x], [in_first], [out_first], [count], dtype)[0]
+    def range(self, x: np.ndarray, in_first: int, out_first: int, count: int, dtype=np.float32, law: Optional[str] = None) -> np.ndarray:
+        return self.ranges([x], [in_first], [out_first], [count], dtype, law)[0]
 
-    def __call__(self, clips: Union[np.ndarray, Sequence[np.ndarray]], dtype=np.float32):
-        """Whole clips (int16 or float32): a list in, a list of ``dtype`` arrays out; one array in, one out."""
+    def __call__(self, clips: Union[np.ndarray, Sequence[np.ndarray]], dtype=np.float32, law: Optional[str] = None):
+        """Whole clips (int16 or float32; ``law="mulaw"`` / ``"alaw"``: uint8 G.711 codes): a list in, a list of ``dtype`` arrays
+        out; one array in, one out.  G.711 clips give the bits their decoded int16 samples give."""
         single = isinstance(clips, np.ndarray)
         segs = [clips] if single else list(clips)
-        out = self.ranges(segs, None, None, [self.out_len(np.asarray(s).size) for s in segs], dtype)
+        out = self.ranges(segs, None, None, [self.out_len(np.asarray(s).size) for s in segs], dtype, law)
         return out[0] if single else out
 
     def resample_dev(self, d_in: int, in_dtype, sample_offs: np.ndarray, out_offs: np.ndarray, d_out: int, out_dtype=np.float32,
-                     in_first: Optional[np.ndarray] = None, out_first: Optional[np.ndarray] = None) -> None:
+                     in_first: Optional[np.ndarray] = None, out_first: Optional[np.ndarray] = None, law: Optional[str] = None) -> None:
         """``ww_resample_dev``: device addresses (``tensor.data_ptr()``), host offset tables (int64, ``n_seg + 1`` entries);
-        enqueued on the context's stream, no synchronisation."""
+        enqueued on the context's stream, no synchronisation.  ``law``: the input is uint8 G.711 codes (``in_dtype`` uint8)."""
         lib = self._lib
         so, oo = np.ascontiguousarray(sample_offs, np.int64), np.ascontiguousarray(out_offs, np.int64)
         if len(so) != len(oo) or len(so) < 1:
             raise ValueError("sample_offs and out_offs have n_seg + 1 entries each")
         i0 = None if in_first is None else np.ascontiguousarray(in_first, np.int64)
         o0 = None if out_first is None else np.ascontiguousarray(out_first, np.int64)
-        rc = lib.load().ww_resample_dev(self._h, C.c_void_p(d_in), _sample_format(in_dtype), lib.ptr(so), lib.ptr(i0), lib.ptr(o0), lib.ptr(oo),
+        rc = lib.load().ww_resample_dev(self._h, C.c_void_p(d_in), _sample_format(in_dtype, law), lib.ptr(so), lib.ptr(i0), lib.ptr(o0), lib.ptr(oo),
                                         len(so) - 1, C.c_void_p(d_out), _sample_format(out_dtype))
         lib.raise_for(rc, self.ctx.handle)
 
@@ -184,16 +193,22 @@ class StreamResampler:
     Between calls the object keeps the samples the next output can still reach: from ``first_needed(next output)`` on, which is
     at most ``2 * ceil(half / up) + ceil(down / up)`` samples - ``ceil(half / up)`` behind the centre of the next output, and as
     many ahead of it that have arrived but do not yet determine it.  During a push the packet is appended to them.  The arithmetic
-    is the kernel's: ``backend(samples, in_first, out_first, count) -> outputs`` defaults to :meth:`Resampler.range`."""
+    is the kernel's: ``backend(samples, in_first, out_first, count) -> outputs`` defaults to :meth:`Resampler.range`.
+    ``law="mulaw"`` / ``"alaw"``: the packets are uint8 G.711 codes (kept as codes between calls, decoded in the kernels)."""
 
     def __init__(self, rate_in: int, rate_out: int = 16000, ctx=None, backend: Optional[Callable] = None, dtype=np.float32,
-                 zeros: int = ZEROS, rolloff: float = ROLLOFF, beta: float = BETA) -> None:
+                 zeros: int = ZEROS, rolloff: float = ROLLOFF, beta: float = BETA, law: Optional[str] = None) -> None:
         self.up, self.down = ratio(rate_in, rate_out)
         self.dtype = np.dtype(dtype)
+        self.law = law
+        if law is not None:
+            _sample_format(np.uint8, law)
+            if backend is not None:
+                raise ValueError("a G.711 stream is decoded by the library's kernels: no backend")
         if backend is None:
             self._rs = Resampler(rate_in, rate_out, ctx, zeros, rolloff, beta)
             self.half = self._rs.half
-            backend = lambda x, i0, o0, n: self._rs.range(x, i0, o0, n, self.dtype)  # noqa: E731
+            backend = lambda x, i0, o0, n: self._rs.range(x, i0, o0, n, self.dtype, self.law)  # noqa: E731
         else:
             self._rs = None
             self.half = design(rate_in, rate_out, zeros, rolloff, beta)[2] if (self.up, self.down) != (1, 1) else 0
@@ -216,7 +231,7 @@ class StreamResampler:
 
     def push(self, packet: np.ndarray) -> np.ndarray:
         packet = np.ascontiguousarray(packet).reshape(-1)
-        _sample_format(packet.dtype)
+        _sample_format(packet.dtype, self.law)
         if self._hist is None:
             self._hist = packet[:0].copy()
         elif packet.dtype != self._hist.dtype:
@@ -233,7 +248,7 @@ class StreamResampler:
 
     def flush(self) -> np.ndarray:
         """The outputs that were waiting for samples, computed against zeros: ``ceil(n * up / down)`` in all."""
-        buf = self._hist if self._hist is not None else np.zeros(0, np.float32)
+        buf = self._hist if self._hist is not None else np.zeros(0, np.uint8 if self.law else np.float32)
         return self._emit(buf, out_len(self.n_in, self.up, self.down))
 
     def close(self) -> None:
@@ -255,6 +270,17 @@ def _cached(rate_in: int, rate_out: int, device: int = 0) -> Resampler:
     return r
 
 
+def _g711_wav(path: str, header_only: bool = False):
+    """The file as :class:`wwhip.g711.G711Wav` when it is a G.711 wav; None for everything else (which ``wave`` then judges)."""
+    from .g711 import read_wav
+    try:
+        return read_wav(path, header_only)
+    except ValueError as e:
+        if "not a RIFF/WAVE" in str(e):
+            return None
+        raise
+
+
 def read_pcm16(path: str) -> Tuple[np.ndarray, int]:
     """A PCM16 wav as ``(int16 [frames, channels], rate)``."""
     with wave.open(path, "rb") as w:
@@ -267,8 +293,19 @@ def read_pcm16(path: str) -> Tuple[np.ndarray, int]:
 def load(path: str, sr: int = 16000, mono: bool = True, device: int = 0) -> np.ndarray:
     """The reference's ``librosa.load(path, sr=16000)`` call shape for PCM16 wavs at ANY rate: float32 in [-1, 1) at ``sr``,
     channels averaged as :func:`wwhip.evaluate.read_wav` does (``mono=False``: ``[channels, n]``).  The filter is this module's,
-    not librosa's.  Plugs into the ``loader=`` hook of ``get_posterior`` / ``get_posterior_sharded`` / ``DatasetFilter``."""
-    pcm, rate = read_pcm16(str(path))
+    not librosa's.  Plugs into the ``loader=`` hook of ``get_posterior`` / ``get_posterior_sharded`` / ``DatasetFilter``.
+    A G.711 wav (mu-law or A-law) is read too: a mono file's (and with ``mono=False`` every channel's) bytes go up once and are
+    decoded and resampled in one device pass - also when the file is at ``sr`` already, where the pass is the decode alone."""
+    g = _g711_wav(str(path))
+    if g is not None:
+        if g.channels == 1 or not mono:
+            codes = [np.ascontiguousarray(g.codes[:, c]) for c in range(g.channels)]
+            out = _cached(g.rate, int(sr), device)(codes, np.float32, law=g.law)
+            return out[0] if mono else np.stack(out)
+        from .g711 import decode
+        pcm, rate = decode(g.codes, g.law), g.rate  # channels are averaged as decoded samples: a host pass, as for PCM16
+    else:
+        pcm, rate = read_pcm16(str(path))
     ch = pcm.shape[1]
     if mono and ch > 1:
         clips: List[np.ndarray] = [(pcm.astype(np.float32).mean(axis=1) / np.float32(32768.0)).astype(np.float32)]
