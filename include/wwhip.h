@@ -753,6 +753,45 @@ int ww_far_frr_dev(ww_ctx *ctx, const float *d_pos, int64_t n_pos, const float *
 int ww_posterior_pick_dev(ww_ctx *ctx, const float *d_rows, int64_t n, int32_t n_out, int32_t pidx, const int64_t *d_seg_offs,
                           int64_t n_seg, float *d_out);
 
+/* ---- detection events: WHERE the smoothed posterior is above the threshold -------------------
+ * ww_far_frr counts the rising edges of (smoothed > threshold); these two calls say where they are - the library's counterpart of
+ * the reference's examine_audio / plot_wav_and_posterior (utils/evaluate_models.py), for many recordings and many wake words at once.
+ * Input
+ *   post [planes][n] fp32, 1 <= planes <= 64 (one plane per wake word: ww_posterior_pick_dev makes them from detect rows)
+ *   seg_offs [n_seg + 1]   ascending row offsets within [0, n], shared by all planes (HOST array); NULL = one segment [0, n).
+ *                          Rows outside every segment belong to no event.
+ *   win                    the smoothing window
+ *   thr [planes] fp64      one threshold per plane (HOST array)
+ * The rule, per plane k and segment u, p = the segment's m rows:
+ *   sm[i]   the value ww_far_frr writes to smoothed[i] when given that segment alone as neg, bit for bit: the centre of the full
+ *           convolution, sm[i] = sum over j = i + (win-1)/2 - (win-1) .. i + (win-1)/2, ascending, clipped to [0, m), of
+ *           (double)p[j] * (1.0 / win), in fp64 (for m < win too, where ww_far_frr itself refuses the call); win <= 0: sm[i] =
+ *           (double)p[i].  Smoothing never reads across a segment boundary.
+ *   above   row i is above when sm[i] > thr[k], an fp64 compare: a NaN is not above (sweep_kernel's rule)
+ *   event   a maximal run [start, end) of above rows inside the segment.  A run that reaches a segment's end ends there; a run that
+ *           begins at the first row of the next segment is a new event.
+ *   fields  start, end and peak are relative to the segment's first row; peak is the smallest i in the run at which sm is greatest,
+ *           peak_value = sm[peak].
+ * Order: by plane, then segment, then start; the output is identical from run to run (no atomics decide a position).
+ * With one segment the number of events of plane k equals fa_count of ww_far_frr_dev on that plane at thr[k].
+ * *n_events receives the total found; only the first min(total, cap) events in that order are written to `events`, nothing behind
+ * them; events == NULL with cap == 0 counts only.  plane_counts (may be NULL) receives the total per plane.
+ * WW_EINVAL with the reason in ww_last_error and no output written: planes outside 1..64; negative n, n_seg or cap; descending offsets
+ * or offsets outside [0, n]; NULL thr or n_events; NULL events with cap > 0; NULL post with n > 0; more rows than one launch takes
+ * (n > 2^39).  Both calls return with the events in the caller's array: ww_posterior_events_dev reads device posteriors where they
+ * are - offsets and thresholds go up, the plane totals and the written events come back, nothing else crosses the bus -,
+ * ww_posterior_events uploads host posteriors first.  Five kernel launches per call whatever n, n_seg, planes and the number of
+ * events are (detection events). */
+typedef struct ww_event {
+  int32_t plane, seg;
+  int64_t start, end, peak; /* segment-relative rows; the run is [start, end) */
+  double peak_value;
+} ww_event; /* 40 bytes */
+int ww_posterior_events_dev(ww_ctx *ctx, const float *d_post, int64_t n, int32_t planes, const int64_t *seg_offs, int64_t n_seg,
+                            int32_t win, const double *thr, ww_event *events, int64_t cap, int64_t *n_events, int64_t *plane_counts);
+int ww_posterior_events(ww_ctx *ctx, const float *post, int64_t n, int32_t planes, const int64_t *seg_offs, int64_t n_seg, int32_t win,
+                        const double *thr, ww_event *events, int64_t cap, int64_t *n_events, int64_t *plane_counts);
+
 /* ---- superframe shortest-path smoothing -------------------------------------------------
  * Replaces wwdetect/wfst.py:17-71 `smooth()` (pynini 2-state x T lattice, tropical shortest path) as
  * wired in utils/CRNN_files/tflite.py:252-263 (superframe of 10 posteriors; trigger if the best path

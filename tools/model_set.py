@@ -40,7 +40,7 @@ KERNELS = ("crnn_fused_kernel", "crnn_stream_kernel", "crnn_rows_kernel", "gru_t
            "crnn_fused_bf16_kernel", "gemm_nt_kernel", "crnn_detect_kernel", "conv_generic_kernel", "gru_generic_kernel",
            "wave_feed_pool_kernel", "wave_feed_ring_kernel", "wave_feed_post_rows_kernel", "wave_pool_step_kernel", "wave_pool_final_kernel", "wave_seq_post_kernel",
            "iota_offs_kernel", "logmel_kernel", "logmel_rows_kernel", "stft_mag_kernel", "mel_only_kernel", "smooth_kernel", "sweep_kernel",
-           "pick_kernel", "viterbi2_kernel", "stream_frontend_kernel", "stream_feed_frontend_kernel", "stream_causal_reset_kernel",
+           "pick_kernel", "ev_smooth_kernel", "ev_count_kernel", "ev_scan_kernel", "ev_write_kernel", "ev_peak_kernel", "viterbi2_kernel", "stream_frontend_kernel", "stream_feed_frontend_kernel", "stream_causal_reset_kernel",
            "stream_reset_kernel", "resample_copy_kernel", "resample_decim_kernel", "resample_phase_kernel", "stream_rate_tick_kernel",
            "stream_rate_splice_kernel")
 LLVM = "/opt/rocm/lib/llvm/bin"

@@ -1352,6 +1352,66 @@ int ww_posterior_pick_dev(ww_ctx *ctx, const float *d_rows, int64_t n, int32_t n
   WW_GUARD_END(ctx)
 }
 
+// ------------------------------------------------------------------------------------------
+// detection events (events_plan.h: checks, geometry, scratch; posterior.hip: the five passes)
+// ------------------------------------------------------------------------------------------
+// post: a host pointer (uploaded here) or, with on_device, a device pointer the kernels read where it is
+static int posterior_events_impl(ww_ctx *ctx, bool on_device, const float *post, int64_t n, int32_t planes, const int64_t *seg_offs,
+                                 int64_t n_seg, int32_t win, const double *thr, ww_event *events, int64_t cap, int64_t *n_events,
+                                 int64_t *plane_counts) {
+  if (!ctx) return ww_fail(ctx, WW_EINVAL, "posterior events: NULL context");
+  char why[256] = {0};
+  if (ev_check(post, n, planes, seg_offs, n_seg, thr, events, cap, n_events, why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "posterior events: %s", why);
+  ev_plan p;
+  if (ev_make_plan(n, planes, seg_offs != nullptr, n_seg, cap, p, why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "posterior events: %s", why);
+  WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
+  const size_t rows = (size_t)planes * (size_t)n;
+  const size_t b_up = on_device ? 0 : ww_bump::need(rows + 1, 4);
+  int rc = ww_ensure(ctx, ctx->dev, b_up + p.bytes + 1024, false);
+  if (rc) return rc;
+  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
+  const float *d_post = post;
+  if (!on_device) {
+    float *up = bump.take<float>(rows + 1);
+    if (rows) WW_HIP(ctx, hipMemcpyAsync(up, post, rows * 4, hipMemcpyHostToDevice, ctx->stream));
+    d_post = up;
+  }
+  char *ws = bump.take<char>(p.bytes);
+  const int64_t whole[2] = {0, n};  // (read by the copy below; the call ends in a synchronise)
+  WW_HIP(ctx, hipMemcpyAsync(ws + p.o_offs, seg_offs ? seg_offs : whole, (size_t)p.n_offs * 8, hipMemcpyHostToDevice, ctx->stream));
+  WW_HIP(ctx, hipMemcpyAsync(ws + p.o_thr, thr, (size_t)planes * 8, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = ww_k_posterior_events(ctx, d_post, p, win, ws))) return rc;
+  int64_t totals[WW_EVENTS_MAX_PLANES];
+  WW_HIP(ctx, hipMemcpyAsync(totals, ws + p.o_totals, (size_t)planes * 8, hipMemcpyDeviceToHost, ctx->stream));
+  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int64_t total = 0;
+  for (int k = 0; k < planes; ++k) total += totals[k];
+  const int64_t written = ev_written(total, cap);
+  if (total < 0 || written > p.dev_cap) return ww_fail(ctx, WW_EINTERNAL, "posterior events: %lld events do not fit the plan's %lld", (long long)written, (long long)p.dev_cap);
+  if (written > 0) {  // only the events themselves cross the bus
+    WW_HIP(ctx, hipMemcpyAsync(events, ws + p.o_events, (size_t)written * sizeof(ww_event), hipMemcpyDeviceToHost, ctx->stream));
+    WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  *n_events = total;
+  if (plane_counts)
+    for (int k = 0; k < planes; ++k) plane_counts[k] = totals[k];
+  return WW_OK;
+}
+
+int ww_posterior_events_dev(ww_ctx *ctx, const float *d_post, int64_t n, int32_t planes, const int64_t *seg_offs, int64_t n_seg,
+                            int32_t win, const double *thr, ww_event *events, int64_t cap, int64_t *n_events, int64_t *plane_counts) {
+  WW_GUARD_BEGIN
+  return posterior_events_impl(ctx, true, d_post, n, planes, seg_offs, n_seg, win, thr, events, cap, n_events, plane_counts);
+  WW_GUARD_END(ctx)
+}
+
+int ww_posterior_events(ww_ctx *ctx, const float *post, int64_t n, int32_t planes, const int64_t *seg_offs, int64_t n_seg, int32_t win,
+                        const double *thr, ww_event *events, int64_t cap, int64_t *n_events, int64_t *plane_counts) {
+  WW_GUARD_BEGIN
+  return posterior_events_impl(ctx, false, post, n, planes, seg_offs, n_seg, win, thr, events, cap, n_events, plane_counts);
+  WW_GUARD_END(ctx)
+}
+
 int ww_superframe_smooth(ww_ctx *ctx, const float *in, int64_t n, int32_t T, float stay_bonus, int32_t in_is_cost,
                          uint8_t *path, uint8_t *wake) {
   WW_GUARD_BEGIN

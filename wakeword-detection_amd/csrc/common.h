@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/wwhip.h"
+#include "events_plan.h"
 #include "launch_plan.h"
 #include "model_layout.h"
 #include "stream_rate.h"
@@ -265,6 +266,8 @@ size_t ww_wave_workspace(const ww_model *m, int n_windows);
 int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
                       const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int n_windows, void *ws, size_t ws_bytes,
                       float *d_out, float *d_enc, const ww_tick_tag *tag = nullptr, const ww_set_ref *set = nullptr);
+// the five passes of ww_posterior_events over device posteriors; ws: p.bytes of device scratch with offsets and thresholds in place
+int ww_k_posterior_events(ww_ctx *ctx, const float *d_post, const ev_plan &p, int win, char *ws);
 int ww_k_posterior_pick(ww_ctx *ctx, const float *d_rows, int64_t n, int n_out, int pidx, const int64_t *d_seg_offs, int64_t n_seg,
                         float *d_out);
 bool ww_wave_tick_capable(const ww_model *m, int n_streams);

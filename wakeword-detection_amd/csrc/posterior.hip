@@ -127,6 +127,215 @@ int ww_k_posterior_pick(ww_ctx *ctx, const float *d_rows, int64_t n, int n_out, 
   return WW_OK;
 }
 
+// ---- detection events (include/wwhip.h: ww_posterior_events; events_plan.h: geometry and scratch): where each plane's smoothed
+// posterior is above its threshold, as (plane, segment, start, end, peak, peak value) records in (plane, segment, start) order.
+// Five launches, each its own pass - no workgroup ever waits for another one, every loop is bounded by its data:
+//   ev_smooth_kernel  sm[plane][i]: smooth_kernel's sum over the row's own segment (found by binary search in the offsets); rows
+//                     outside every segment become NaN, which is above nothing.  Plane 0's workgroups also write the row flags.
+//   ev_count_kernel   rises (above, and the segment's first row or the row before is not above) per tile of WW_EVENTS_TILE rows
+//   ev_scan_kernel    one workgroup per plane: exclusive scan of the plane's tile counts, and the plane's total
+//   ev_write_kernel   the rank of a rise = rises of the planes in front + rises of the plane's tiles in front + rises of the tile up
+//                     to the row - 1: the rise writes plane and start of that event; a fall (above, and the segment's last row or the
+//                     next row is not above) has the same expression for its rank and writes end.  Rises and falls alternate, so
+//                     every event gets one of each; ranks >= the device buffer's capacity are not written.
+//   ev_peak_kernel    one wave per written event: the first greatest sm of [start, end), the segment, and the three rows made
+//                     relative to it
+#define EV_FIRST 1
+#define EV_LAST 2
+
+// the segment of row i: the last u with offs[u] <= i (-1: none); a row of a segment has 0 <= u < n_offs - 1
+__device__ __forceinline__ int64_t ev_segment(const int64_t *__restrict__ offs, int64_t n_offs, int64_t i) {
+  int64_t lo = 0, hi = n_offs;  // the first u with offs[u] > i lies in [lo, hi]
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (offs[mid] <= i) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo - 1;
+}
+
+__global__ __launch_bounds__(WW_EVENTS_TILE) void ev_smooth_kernel(const float *__restrict__ post, int64_t n, int win,
+                                                                   const int64_t *__restrict__ offs, int64_t n_offs,
+                                                                   double *__restrict__ sm, unsigned char *__restrict__ flags) {
+  const int64_t i = (int64_t)blockIdx.x * WW_EVENTS_TILE + threadIdx.x;
+  if (i >= n) return;
+  const float *p = post + (int64_t)blockIdx.y * n;
+  double *out = sm + (int64_t)blockIdx.y * n;
+  const int64_t u = ev_segment(offs, n_offs, i);
+  if (u < 0 || u >= n_offs - 1) {
+    out[i] = __longlong_as_double(0x7ff8000000000000LL);
+    if (blockIdx.y == 0) flags[i] = 0;
+    return;
+  }
+  const int64_t s0 = offs[u], s1 = offs[u + 1];
+  if (blockIdx.y == 0) flags[i] = (unsigned char)((i == s0 ? EV_FIRST : 0) | (i + 1 == s1 ? EV_LAST : 0));
+  if (win <= 0) {
+    out[i] = (double)p[i];
+    return;
+  }
+  // smooth_kernel's sum, term for term, with the segment in place of the whole stream
+  const double v = 1.0 / (double)win;
+  const int64_t shift = (win - 1) / 2;
+  const int64_t hi = i + shift, lo = hi - (win - 1);
+  double acc = 0.0;
+  for (int64_t j = lo; j <= hi; ++j)
+    if (j >= s0 && j < s1) acc += (double)p[j] * v;
+  out[i] = acc;
+}
+
+__global__ __launch_bounds__(WW_EVENTS_TILE) void ev_count_kernel(const double *__restrict__ sm, const unsigned char *__restrict__ flags,
+                                                                  int64_t n, const double *__restrict__ thr, int64_t tiles,
+                                                                  unsigned int *__restrict__ counts) {
+  __shared__ unsigned int s_w[WW_EVENTS_TILE / 64];
+  const int64_t i = (int64_t)blockIdx.x * WW_EVENTS_TILE + threadIdx.x;
+  const double *s = sm + (int64_t)blockIdx.y * n;
+  const double t = thr[blockIdx.y];
+  const bool above = i < n && s[i] > t;
+  const bool rise = above && (i == 0 || (flags[i] & EV_FIRST) || !(s[i - 1] > t));
+  const unsigned long long b = __ballot(rise);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = (unsigned int)__popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned int c = 0;
+    for (int w = 0; w < WW_EVENTS_TILE / 64; ++w) c += s_w[w];
+    counts[(int64_t)blockIdx.y * tiles + blockIdx.x] = c;
+  }
+}
+
+__global__ __launch_bounds__(256) void ev_scan_kernel(const unsigned int *__restrict__ counts, int64_t tiles, long long *__restrict__ bases,
+                                                      long long *__restrict__ totals) {
+  __shared__ long long s_w[4];
+  const unsigned int *c = counts + (int64_t)blockIdx.x * tiles;
+  long long *b = bases + (int64_t)blockIdx.x * tiles;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  long long carry = 0;  // the same in every thread
+  for (int64_t t0 = 0; t0 < tiles; t0 += 256) {
+    const int64_t t = t0 + threadIdx.x;
+    const long long x = t < tiles ? (long long)c[t] : 0;
+    long long inc = x;
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long y = __shfl_up(inc, o);
+      if (lane >= o) inc += y;
+    }
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    long long wbase = 0, chunk = 0;
+    for (int w = 0; w < 4; ++w) {
+      if (w < wave) wbase += s_w[w];
+      chunk += s_w[w];
+    }
+    if (t < tiles) b[t] = carry + wbase + inc - x;
+    carry += chunk;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) totals[blockIdx.x] = carry;
+}
+
+__global__ __launch_bounds__(WW_EVENTS_TILE) void ev_write_kernel(const double *__restrict__ sm, const unsigned char *__restrict__ flags,
+                                                                  int64_t n, const double *__restrict__ thr, int64_t tiles,
+                                                                  const long long *__restrict__ bases, const long long *__restrict__ totals,
+                                                                  ww_event *__restrict__ ev, long long dev_cap) {
+  __shared__ unsigned int s_w[WW_EVENTS_TILE / 64];
+  const int plane = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  long long pb = lane < plane ? totals[lane] : 0;  // (plane <= 63)
+  for (int o = 32; o > 0; o >>= 1) pb += __shfl_xor(pb, o);
+  const int64_t i = (int64_t)blockIdx.x * WW_EVENTS_TILE + threadIdx.x;
+  const double *s = sm + (int64_t)plane * n;
+  const double t = thr[plane];
+  const bool above = i < n && s[i] > t;
+  const bool rise = above && (i == 0 || (flags[i] & EV_FIRST) || !(s[i - 1] > t));
+  const bool fall = above && (i == n - 1 || (flags[i] & EV_LAST) || !(s[i + 1] > t));
+  const unsigned long long b = __ballot(rise);
+  if (lane == 0) s_w[wave] = (unsigned int)__popcll(b);
+  __syncthreads();
+  unsigned int upto = (unsigned int)__popcll(b & ((2ull << lane) - 1ull));  // rises of the wave up to this lane, itself included
+  for (int w = 0; w < wave; ++w) upto += s_w[w];
+  const long long r = pb + bases[(int64_t)plane * tiles + blockIdx.x] + (long long)upto - 1;
+  if (rise && r >= 0 && r < dev_cap) {
+    ev[r].plane = plane;
+    ev[r].start = i;
+  }
+  if (fall && r >= 0 && r < dev_cap) ev[r].end = i + 1;
+}
+
+__global__ __launch_bounds__(256) void ev_peak_kernel(const double *__restrict__ sm, int64_t n, const int64_t *__restrict__ offs,
+                                                      int64_t n_offs, const long long *__restrict__ totals, int planes, ww_event *ev,
+                                                      long long dev_cap) {
+  const int lane = threadIdx.x & 63;
+  long long total = lane < planes ? totals[lane] : 0;
+  for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
+  const long long limit = total < dev_cap ? total : dev_cap;
+  const long long waves = (long long)gridDim.x * (blockDim.x >> 6);
+  for (long long e = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); e < limit; e += waves) {
+    ww_event *x = ev + e;
+    const int plane = x->plane;
+    int64_t start = x->start, end = x->end;  // rows of the plane, as the write pass left them
+    if (plane < 0 || plane >= planes) continue;
+    start = start < 0 ? 0 : (start > n ? n : start);  // (what the write pass wrote is in range: nothing is read outside the plane)
+    end = end < start ? start : (end > n ? n : end);
+    const double *s = sm + (int64_t)plane * n;
+    double best = -INFINITY;
+    long long at = 0x7fffffffffffffffLL;
+    for (int64_t i = start + lane; i < end; i += 64) {
+      const double v = s[i];
+      if (v > best) {
+        best = v;
+        at = i;
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const double ov = __shfl_xor(best, o);
+      const long long oa = __shfl_xor(at, o);
+      if (ov > best || (ov == best && oa < at)) {
+        best = ov;
+        at = oa;
+      }
+    }
+    if (lane == 0) {
+      const int64_t u = ev_segment(offs, n_offs, start);
+      const int64_t s0 = u >= 0 ? offs[u] : 0;
+      x->seg = (int32_t)u;
+      x->start = start - s0;
+      x->end = end - s0;
+      x->peak = at - s0;
+      x->peak_value = best;
+    }
+  }
+}
+
+int ww_k_posterior_events(ww_ctx *ctx, const float *d_post, const ev_plan &p, int win, char *ws) {
+  double *sm = (double *)(ws + p.o_sm), *thr = (double *)(ws + p.o_thr);
+  unsigned char *flags = (unsigned char *)(ws + p.o_flags);
+  const int64_t *offs = (const int64_t *)(ws + p.o_offs);
+  unsigned int *counts = (unsigned int *)(ws + p.o_counts);
+  long long *bases = (long long *)(ws + p.o_bases), *totals = (long long *)(ws + p.o_totals);
+  ww_event *ev = (ww_event *)(ws + p.o_events);
+  const dim3 grid((unsigned)p.tiles, (unsigned)p.planes), block(WW_EVENTS_TILE);
+  {
+    ww_launch_scope scope(ctx, "ev_smooth_kernel");
+    hipLaunchKernelGGL(ev_smooth_kernel, grid, block, 0, ctx->stream, d_post, p.n, win, offs, p.n_offs, sm, flags);
+  }
+  {
+    ww_launch_scope scope(ctx, "ev_count_kernel");
+    hipLaunchKernelGGL(ev_count_kernel, grid, block, 0, ctx->stream, sm, flags, p.n, thr, p.tiles, counts);
+  }
+  {
+    ww_launch_scope scope(ctx, "ev_scan_kernel");
+    hipLaunchKernelGGL(ev_scan_kernel, dim3((unsigned)p.planes), dim3(256), 0, ctx->stream, counts, p.tiles, bases, totals);
+  }
+  {
+    ww_launch_scope scope(ctx, "ev_write_kernel");
+    hipLaunchKernelGGL(ev_write_kernel, grid, block, 0, ctx->stream, sm, flags, p.n, thr, p.tiles, bases, totals, ev, (long long)p.dev_cap);
+  }
+  {
+    ww_launch_scope scope(ctx, "ev_peak_kernel");
+    hipLaunchKernelGGL(ev_peak_kernel, dim3((unsigned)p.peak_blocks), dim3(64 * WW_EVENTS_PEAK_WAVES), 0, ctx->stream, sm, p.n, offs, p.n_offs,
+                       totals, (int)p.planes, ev, (long long)p.dev_cap);
+  }
+  WW_HIP(ctx, hipGetLastError());
+  return WW_OK;
+}
+
 // ---- superframe shortest-path smoothing (wwdetect/wfst.py:17-71; wiring utils/CRNN_files/tflite.py:252-263)
 // The reference builds a 2-state x T lattice with pynini and takes the single shortest path in the
 // tropical semiring (float32 weights): start arcs cost ln 2 + c[0][p]; an arc into state p at time t

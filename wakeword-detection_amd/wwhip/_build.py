@@ -45,7 +45,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                os.path.join(CSRC, "model_set.h"),
                os.path.join(CSRC, "launch_plan.h"), os.path.join(CSRC, "stream_rate.h"), os.path.join(CSRC, "stream_rates.h"),
                os.path.join(CSRC, "stream_formats.h"),
-               os.path.join(CSRC, "stream_all.h"),
+               os.path.join(CSRC, "stream_all.h"), os.path.join(CSRC, "events_plan.h"),
                os.path.join(os.path.dirname(ROOT), "include", "wwhip.h")]
     jobs = []
     objs = []

@@ -150,7 +150,14 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_far_frr": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),
     "ww_far_frr_dev": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),
     "ww_posterior_pick_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
+    "ww_posterior_events_dev": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "ww_posterior_events": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp]),
 }
+
+# ``ww_event`` (include/wwhip.h): one detection event, 40 bytes - what ww_posterior_events[_dev] write
+EVENT_DTYPE = np.dtype({"names": ["plane", "seg", "start", "end", "peak", "peak_value"],
+                        "formats": [np.int32, np.int32, np.int64, np.int64, np.int64, np.float64],
+                        "offsets": [0, 4, 8, 16, 24, 32], "itemsize": 40})
 
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()

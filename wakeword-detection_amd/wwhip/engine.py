@@ -21,6 +21,56 @@ def frontend_params(pcm_divisor: float = 32767.0, clip: bool = True, pre_emphasi
     return _lib.FrontendParams(float(pcm_divisor), int(bool(clip)), float(pre_emphasis), int(hop), int(bool(precise)))
 
 
+def _events_args(planes: int, n: int, threshold, seg_offs):
+    """The host arrays of a detection-event call, checked: one fp64 threshold per plane (a scalar serves all) and the int64 segment
+    offsets (``None``: one segment)."""
+    thr = np.asarray(threshold, np.float64)
+    if thr.ndim == 0:
+        thr = np.full(planes, float(thr))
+    thr = np.ascontiguousarray(thr.ravel())
+    if thr.size != planes:
+        raise ValueError(f"threshold: one value, or one per plane ({planes}), got {thr.size}")
+    offs = None
+    if seg_offs is not None:
+        offs = np.ascontiguousarray(seg_offs, dtype=np.int64)
+        if offs.ndim != 1 or offs.size < 1:
+            raise ValueError("seg_offs must be a 1-D array of n_seg + 1 row offsets")
+    return thr, offs
+
+
+def _events_call(fn, ctx, post_arg, n: int, planes: int, threshold, seg_offs, window: int, cap: Optional[int], want_counts: bool):
+    """``ww_posterior_events`` / ``ww_posterior_events_dev`` into an array of :data:`wwhip._lib.EVENT_DTYPE`.  ``cap`` = ``None``: room
+    for 4,096 events first, and where the call reports more, once more with room for all of them; a number: that many at the most
+    (the first ``cap`` in plane, segment, start order)."""
+    thr, offs = _events_args(planes, n, threshold, seg_offs)
+    counts = np.zeros(planes, np.int64)
+    total = C.c_int64(0)
+    room = 4096 if cap is None else int(cap)
+    while True:
+        ev = np.zeros(max(room, 0), _lib.EVENT_DTYPE)
+        _lib.raise_for(fn(ctx.handle, post_arg, int(n), int(planes), _lib.ptr(offs), 0 if offs is None else int(offs.size - 1), int(window),
+                          _lib.ptr(thr), _lib.ptr(ev) if room > 0 else None, room, C.addressof(total), _lib.ptr(counts)), ctx.handle)
+        if cap is not None or total.value <= room:
+            break
+        room = int(total.value)
+    ev = ev[:min(int(total.value), max(room, 0))]
+    return (ev, counts, int(total.value)) if want_counts else ev
+
+
+def _events_host(ctx, post, threshold, seg_offs, window, cap, want_counts):
+    p = np.ascontiguousarray(post, dtype=np.float32)
+    if p.ndim == 1:
+        p = p[None]
+    if p.ndim != 2:
+        raise ValueError("post must be 1-D, or [planes, n]")
+    return _events_call(_lib.load().ww_posterior_events, ctx, _lib.ptr(p), p.shape[1], p.shape[0], threshold, seg_offs, window, cap, want_counts)
+
+
+def _events_dev(ctx, d_post_ptr, n, planes, threshold, seg_offs, window, cap, want_counts):
+    return _events_call(_lib.load().ww_posterior_events_dev, ctx, C.c_void_p(d_post_ptr) if d_post_ptr else None, n, planes, threshold, seg_offs,
+                        window, cap, want_counts)
+
+
 class Engine:
     """A model directory (filter/encode/detect ``.tflite``) resident on one MI355X."""
 
@@ -291,6 +341,20 @@ class Engine:
                                                   C.c_void_p(d_seg_offs_ptr) if d_seg_offs_ptr else None, int(n_seg),
                                                   C.c_void_p(d_out_ptr)))
 
+    def posterior_events(self, post, threshold, seg_offs=None, window: int = 30, cap: Optional[int] = None, want_counts: bool = False):
+        """Where the smoothed posterior is above the threshold (``ww_posterior_events``, include/wwhip.h states the rule): ``post`` is
+        1-D or ``[planes, n]`` float32, ``threshold`` one value or one per plane, ``seg_offs`` ``n_seg + 1`` ascending row offsets
+        (``None``: one segment; smoothing and runs never cross a boundary).  Returns the events as an array of
+        ``wwhip._lib.EVENT_DTYPE`` (``plane, seg, start, end, peak, peak_value``; rows relative to the segment) in plane, segment, start
+        order; with ``want_counts`` also the totals per plane and overall.  ``cap`` limits how many are returned."""
+        return _events_host(self.ctx, post, threshold, seg_offs, window, cap, want_counts)
+
+    def posterior_events_dev(self, d_post_ptr: int, n: int, threshold, seg_offs=None, window: int = 30, planes: int = 1,
+                             cap: Optional[int] = None, want_counts: bool = False):
+        """:meth:`posterior_events` over ``[planes, n]`` float32 posteriors that are already on the device
+        (``ww_posterior_events_dev``): offsets and thresholds go up, only the events come back."""
+        return _events_dev(self.ctx, d_post_ptr, n, planes, threshold, seg_offs, window, cap, want_counts)
+
     # ------------------------------------------------------------------ device-resident paths (torch plumbing)
     def clips_forward_dev(self, d_pcm_ptr: int, n_clips: int, samples_per_clip: int, d_out_ptr: int,
                           fp: Optional[_lib.FrontendParams] = None) -> None:
@@ -473,6 +537,18 @@ class ModelSet:
             return None
         a = np.asarray(members)
         return _member_ids(a, a.size if a.ndim == 1 else -1, self.n_models, "members")
+
+    def posterior_events(self, post, thresholds, seg_offs=None, window: int = 30, cap: Optional[int] = None, want_counts: bool = False):
+        """:meth:`Engine.posterior_events` with one plane and one threshold per member: ``post`` is ``[n_models, n]``."""
+        p = np.asarray(post)
+        if p.ndim != 2 or p.shape[0] != self.n_models:
+            raise ValueError(f"post must be [{self.n_models}, n]: one plane per member, got shape {p.shape}")
+        return _events_host(self.ctx, p, thresholds, seg_offs, window, cap, want_counts)
+
+    def posterior_events_dev(self, d_post_ptr: int, n: int, thresholds, seg_offs=None, window: int = 30, cap: Optional[int] = None,
+                             want_counts: bool = False):
+        """:meth:`Engine.posterior_events_dev` over ``[n_models, n]`` device posteriors, one threshold per member."""
+        return _events_dev(self.ctx, d_post_ptr, n, self.n_models, thresholds, seg_offs, window, cap, want_counts)
 
     def set_option(self, key: str, value: int) -> None:
         """``ww_set_option``: ``"crnn_slide_min"`` / ``"crnn_tail_mfma"`` (:meth:`Engine.set_option`'s meanings) for the set's

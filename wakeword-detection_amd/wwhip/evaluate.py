@@ -1187,21 +1187,22 @@ class _ClipLayout(NamedTuple):
     win_valid: np.ndarray  # [n] rows of that window that the bare clip fills (the rest are zeros)
 
 
-def _clip_layout(lens, T: int, hop: int, hop_s: int) -> _ClipLayout:
+def _clip_layout(lens, T: int, hop: int, hop_s: int, pad: int = CLIP_PAD) -> _ClipLayout:
     """Pure arithmetic on the clips' lengths - identical on every rank: each clip padded by 0.5 s of zeros on both sides
     (evaluate_models.py:52-53), front-end hop ``hop_s`` samples, windows of ``T`` rows every ``hop`` rows.  The 0.5 s of leading
-    zeros are ``CLIP_PAD // hop_s`` whole hops, so frame k of the bare clip is row k + that of the padded one."""
+    zeros are ``CLIP_PAD // hop_s`` whole hops, so frame k of the bare clip is row k + that of the padded one.  (``pad``: the zeros
+    each side, in samples; :func:`find_wakewords` can do without them.)"""
     lens = np.asarray(lens, np.int64)
-    padded = lens + 2 * CLIP_PAD
+    padded = lens + 2 * pad
     nf_pad = np.where(padded >= WINDOW, (padded - WINDOW) // hop_s + 1, 0)
     nf_bare = np.where(lens >= WINDOW, (lens - WINDOW) // hop_s + 1, 0)
     foffs = np.concatenate(([0], np.cumsum(nf_pad)))
     nw = np.where(nf_pad >= T, (nf_pad - T) // hop + 1, 0)
     return _ClipLayout(np.concatenate(([0], np.cumsum(padded))), nf_pad, foffs, nw, np.concatenate(([0], np.cumsum(nw))),
-                       (foffs[:-1] + CLIP_PAD // hop_s).astype(np.int64), np.minimum(nf_bare, T).astype(np.int32))
+                       (foffs[:-1] + pad // hop_s).astype(np.int64), np.minimum(nf_bare, T).astype(np.int32))
 
 
-def _stage_clips(clips: Sequence[np.ndarray], soffs: np.ndarray):
+def _stage_clips(clips: Sequence[np.ndarray], soffs: np.ndarray, pad: int = CLIP_PAD):
     """The padded PCM batch in page-locked memory (kept for the next call): the upload of the padded batch is the largest
     single cost of a clip pass, and from pageable memory it runs at a fraction of the bus rate.  A pass has waited for its
     results when it returns, so the buffer is free again by then."""
@@ -1215,50 +1216,59 @@ def _stage_clips(clips: Sequence[np.ndarray], soffs: np.ndarray):
     pcm[need - 16:] = 0
     for i, c in enumerate(clips):
         a = int(soffs[i])
-        pcm[a: a + CLIP_PAD] = 0
-        pcm[a + CLIP_PAD: a + CLIP_PAD + len(c)] = c
-        pcm[a + CLIP_PAD + len(c): a + 2 * CLIP_PAD + len(c)] = 0
+        pcm[a: a + pad] = 0
+        pcm[a + pad: a + pad + len(c)] = c
+        pcm[a + pad + len(c): a + 2 * pad + len(c)] = 0
     return pin
 
 
 def _clip_pass(runner, clips: Sequence[np.ndarray], hop: int, fp):
+    """:func:`_clip_pass_dev` with the detect rows brought to the host: the layout and ``[K, n, n_out]``, ``[K, sliding windows, n_out]``."""
+    lay, d_one, d_slide, n_slide = _clip_pass_dev(runner, clips, hop, fp)
+    K, n = d_slide.shape[0], len(clips)
+    return lay, d_one.cpu().numpy().reshape(K, n, runner.n_out), d_slide.cpu().numpy()[:, :n_slide]
+
+
+def _clip_pass_dev(runner, clips: Sequence[np.ndarray], hop: int, fp, single: bool = True, pad: int = CLIP_PAD):
     """One pass of the (at least one) clips on the device by a runner of ``K`` members - an :class:`Engine` (``K`` = 1, through the
     engine's own entry points: its precision mode and launch forms live there) or a :class:`wwhip.ModelSet`: the padded clips go
     up once, ONE front-end launch makes their log-mel rows, one launch evaluates the ``n`` single windows of all members (ragged:
     ``valid`` < T zero-pads them; no second front-end pass, no mel round trip through the host) and one call the sliding windows
     of all members (the clips as ``n`` sequences of one buffer, which lets a CRNN compute every time position once per clip
     instead of once per window: ``ww_forward_segments_dev``).  Returns the layout and the detect rows ``[K, n, n_out]`` and
-    ``[K, sliding windows, n_out]``."""
+    ``[K, sliding windows, n_out]`` - as device tensors, waited for: ``(layout, single rows, sliding rows, sliding windows per
+    member)``.  ``single = False`` leaves the single windows out (``None``); ``pad``: the zeros each side of a clip, in samples."""
     import torch  # only to hold the device buffers of the batched launch
 
     fp = fp or frontend_params()
     hop_s = int(fp.hop)
-    if CLIP_PAD % hop_s:
+    if pad % hop_s:
         raise ValueError(f"front-end hop {hop_s} does not divide the 0.5 s padding")
     is_set = not isinstance(runner, Engine)
     K = runner.n_models if is_set else 1
     front = runner.engines[0] if is_set else runner  # (a set's members share their filter)
     n = len(clips)
-    lay = _clip_layout([len(c) for c in clips], runner.window, hop, hop_s)
+    lay = _clip_layout([len(c) for c in clips], runner.window, hop, hop_s, pad)
     total_f, n_slide = int(lay.foffs[-1]), int(lay.woffs[-1])
     dev = torch.device("cuda", runner.ctx.device)  # the runner's GPU, whatever torch's current device is
-    d_pcm = _stage_clips(clips, lay.soffs).to(dev, non_blocking=True)
+    d_pcm = _stage_clips(clips, lay.soffs, pad).to(dev, non_blocking=True)
     d_so, d_fo = torch.from_numpy(lay.soffs).to(dev), torch.from_numpy(lay.foffs).to(dev)
     d_mel = torch.empty((max(total_f, 1), runner.n_mel), dtype=torch.float32, device=dev)
     # window k * n + i: the single window of clip i by member k
     d_row, d_valid = torch.from_numpy(np.tile(lay.win_row, K)).to(dev), torch.from_numpy(np.tile(lay.win_valid, K)).to(dev)
-    d_one = torch.empty((K * n, runner.n_out), dtype=torch.float32, device=dev)
+    d_one = torch.empty((K * n, runner.n_out), dtype=torch.float32, device=dev) if single else None
     d_slide = torch.empty((K, max(n_slide, 1), runner.n_out), dtype=torch.float32, device=dev)
     torch.cuda.synchronize(dev)
     front.logmel_dev(d_pcm.data_ptr(), d_so.data_ptr(), d_fo.data_ptr(), n, total_f, int(lay.nf_pad.max()), d_mel.data_ptr(), fp)
     # an engine's n single windows: one fused kernel or front + tail kernels by n - the same bits either way (one association of
     # every sum in all forms of the CRNN), so the sharded evaluation does not differ between world sizes
     ids = (np.repeat(np.arange(K, dtype=np.int32), n),) if is_set else ()
-    runner.forward_windows_dev(d_mel.data_ptr(), total_f, d_row.data_ptr(), d_valid.data_ptr(), *ids, K * n, d_one.data_ptr())
+    if single:
+        runner.forward_windows_dev(d_mel.data_ptr(), total_f, d_row.data_ptr(), d_valid.data_ptr(), *ids, K * n, d_one.data_ptr())
     if n_slide:
         runner.forward_segments_dev(d_mel.data_ptr(), total_f, lay.foffs[:-1], lay.nw, hop, d_slide.data_ptr())
     runner.ctx.synchronize()
-    return lay, d_one.cpu().numpy().reshape(K, n, runner.n_out), d_slide.cpu().numpy()[:, :n_slide]
+    return lay, d_one, d_slide, n_slide
 
 
 def clip_posteriors(engine: Engine, clips: Sequence[np.ndarray], hop: int = 2, fp=None):
@@ -1319,6 +1329,82 @@ def evaluate_testset_set(model_set, clips: Sequence[np.ndarray], labels: Sequenc
     p_one, sliding = clip_posteriors_set(model_set, clips, fp=fp)
     return [_testset_result(model_set.engines[k], p_one[k], sliding[k], labels, clips, thresholds, windowsize)
             for k in range(model_set.n_models)]
+
+
+class Detection(NamedTuple):
+    """One event of :func:`find_wakewords`: the windows ``[start, end)`` of clip ``clip`` on which member ``member``'s smoothed
+    posterior is above its threshold, the window ``peak`` at which it is greatest (the first of equals) and its value there; the
+    three times are seconds from the bare clip's first sample."""
+    clip: int
+    member: int
+    name: Optional[str]
+    start: int
+    end: int
+    peak: int
+    start_s: float
+    end_s: float
+    peak_s: float
+    peak_value: float
+
+
+def detection_times(start: int, end: int, peak: int, n_samples: int, T: int, hop: int, hop_s: int = 160, pad: int = CLIP_PAD,
+                    sample_rate: int = 16000) -> Tuple[float, float, float]:
+    """The times :func:`find_wakewords` reports (its docstring states the definition), for a clip of ``n_samples`` samples."""
+    first = lambda w: w * hop * hop_s                        # window w covers samples [first(w), last1(w)) of the padded clip
+    last1 = lambda w: (w * hop + T - 1) * hop_s + WINDOW
+    clamp = lambda x: min(max((x - pad) / sample_rate, 0.0), n_samples / sample_rate)
+    return clamp(first(start)), clamp(last1(end - 1)), clamp((first(peak) + last1(peak)) / 2)
+
+
+def find_wakewords(runner, clips: Sequence[np.ndarray], thresholds, hop: int = 2, windowsize: int = 30, pad: bool = True, fp=None,
+                   names: Optional[Sequence[str]] = None) -> List[Detection]:
+    """Scan recordings for wake words: which member of ``runner`` (an :class:`Engine`, or a :class:`wwhip.ModelSet` - every member
+    over ONE front-end pass) fires in which clip, and when.  The clips go through the pass :func:`clip_posteriors` /
+    :func:`clip_posteriors_set` run (one upload, one front-end launch, the sliding windows of all members in one call); the detect
+    rows stay on the device, each member's posterior column is picked into a plane of ``[K, windows]`` and ONE
+    ``posterior_events_dev`` call over the clips' window offsets returns the events (include/wwhip.h: the smoothed posterior of a clip
+    - ``windowsize`` taps, never across a clip boundary - above ``thresholds[member]``; one value serves all members).  Only events
+    cross the bus.  A clip shorter than the model's window has no windows and no detections.
+
+    Returns :class:`Detection` tuples ordered by member, then clip, then start.  ``start``, ``end``, ``peak`` count the clip's own
+    windows.  Times: with ``T`` the model's window in rows, ``hop_s`` the front end's hop in samples and ``hop`` the windows' hop in
+    rows, window ``w`` covers samples ``[w * hop * hop_s, (w * hop + T - 1) * hop_s + 512)`` of the padded clip (``pad``: 0.5 s of
+    zeros each side, as the reference's evaluator pads; ``pad=False``: none).  ``start_s`` is the first sample of window ``start``,
+    ``end_s`` one past the last sample of window ``end - 1``, ``peak_s`` the centre of window ``peak`` (the mean of its first sample
+    and one past its last); each minus the leading pad, divided by 16000 and clamped to ``[0, clip length in seconds]``.
+    ``names``: one per member (a set's directory names by default)."""
+    import torch
+
+    is_set = not isinstance(runner, Engine)
+    K = runner.n_models if is_set else 1
+    members = runner.engines if is_set else [runner]
+    if names is None:
+        names = runner.names if is_set else [os.path.basename(os.path.normpath(runner.model_dir))]
+    if len(names) != K:
+        raise ValueError(f"names: one per member ({K}), got {len(names)}")
+    thr = np.asarray(thresholds, np.float64)
+    thr = np.full(K, float(thr)) if thr.ndim == 0 else thr.ravel()
+    if thr.size != K:
+        raise ValueError(f"thresholds: one value, or one per member ({K}), got {thr.size}")
+    if len(clips) == 0:
+        return []
+    fp = fp or frontend_params()
+    pad_s = CLIP_PAD if pad else 0
+    lay, _, d_slide, n_slide = _clip_pass_dev(runner, clips, hop, fp, single=False, pad=pad_s)
+    if n_slide == 0:
+        return []
+    dev = d_slide.device
+    d_plane = torch.empty((K, n_slide), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)  # (torch's stream is not the context's)
+    for k, e in enumerate(members):
+        e.posterior_pick_dev(d_slide[k].data_ptr(), n_slide, d_plane[k].data_ptr())
+    ev = runner.posterior_events_dev(d_plane.data_ptr(), n_slide, thr, seg_offs=lay.woffs, window=windowsize, **({} if is_set else {"planes": 1}))
+    out = []
+    for x in ev:
+        c, a, b, p = int(x["seg"]), int(x["start"]), int(x["end"]), int(x["peak"])
+        ts = detection_times(a, b, p, len(clips[c]), runner.window, hop, int(fp.hop), pad_s)
+        out.append(Detection(c, int(x["plane"]), names[int(x["plane"])], a, b, p, ts[0], ts[1], ts[2], float(x["peak_value"])))
+    return out
 
 
 def evaluate_testset_sharded(engine: Engine, clips: Sequence[np.ndarray], labels: Sequence[int], rank: int = 0,
