@@ -732,7 +732,15 @@ int ww_stream_timeline(ww_streams *st, double *mean_ns, int64_t *ticks, int32_t 
  *   neg' = np.convolve(neg, ones(win)/win, 'same')   (fp64)
  *   frr[k] = (num_wakewords - #(pos > thr[k])) / num_wakewords
  *   fa_count[k] = #rising edges of (neg' > thr[k]);  fa_per_h[k] = fa_count[k] / hours
- * smoothed (may be NULL) receives neg' ([N] fp64).  win <= 0 skips the smoothing. */
+ * smoothed (may be NULL) receives neg' ([N] fp64).  win <= 0 skips the smoothing: neg' = (double)neg.
+ *   positives   pos > thr[k] is a float32 comparison, pos[i] > (float)thr[k]: the reference pins numpy==1.19.5, where a float32
+ *               array against a float64 scalar compares in float32.  A positive between thr[k] and (float)thr[k] is therefore
+ *               judged by the rounded threshold.  The negatives' neg' > thr[k] is an fp64 comparison.
+ *   thresholds  1 <= n_thr <= 1024, in any order, repeats allowed: entry k is counted against thr[k] alone.  n_thr > 1024 is
+ *               WW_EINVAL and no output is written.
+ *   NaN         a NaN is above nothing: a NaN positive is not accepted; a NaN row of neg makes the rows of neg' whose window holds it
+ *               NaN, those rows are not above, and a run may begin on the row after them.
+ * A negative stream shorter than win > 0 is refused (np.convolve 'same' would change its length). */
 int ww_far_frr(ww_ctx *ctx, const float *pos, int64_t n_pos, const float *neg, int64_t n_neg, int32_t win,
                const double *thr, int32_t n_thr, double num_wakewords, double hours, double *frr,
                double *fa_per_h, int64_t *fa_count, double *smoothed);
@@ -749,7 +757,9 @@ int ww_far_frr_dev(ww_ctx *ctx, const float *d_pos, int64_t n_pos, const float *
  * SURVEY quirk C1 -; :98-99: the max over a wake-word clip's windows).  d_rows: [n][n_out] detect rows as the model entry points
  * leave them.  d_seg_offs == NULL: d_out[i] = d_rows[i][pidx] for all n rows (:105-106, the negative stream: every window
  * counts); otherwise d_seg_offs is a device table of n_seg + 1 ascending row offsets and d_out[s] = max over rows
- * [d_seg_offs[s], d_seg_offs[s + 1]).  Enqueues on the context's stream, no synchronisation. */
+ * [d_seg_offs[s], d_seg_offs[s + 1]).  Offsets are clamped to [0, n]; a run without rows yields -inf (the reference never asks
+ * for one: np.max of nothing raises).  The maximum is np.max's: a run that holds a NaN yields NaN - such a clip is above no
+ * threshold, as in the reference.  Enqueues on the context's stream, no synchronisation. */
 int ww_posterior_pick_dev(ww_ctx *ctx, const float *d_rows, int64_t n, int32_t n_out, int32_t pidx, const int64_t *d_seg_offs,
                           int64_t n_seg, float *d_out);
 

@@ -139,13 +139,16 @@ def sliding_posteriors(filt: RefFilter, samples: np.ndarray, encoder_len: int,
 
 def far_frr(keyword_post: np.ndarray, no_keyword_post: np.ndarray, num_wakewords: int, hours: float,
             thresholds: Optional[np.ndarray] = None, windowsize: int = 30):
-    """Reference ``utils/evaluate_models.py:183-218`` (numbers only, no plots)."""
+    """Reference ``utils/evaluate_models.py:183-218`` (numbers only, no plots).  The positives are compared in their own dtype: the
+    reference pins ``numpy==1.19.5``, where a float32 array against a float64 scalar compares in float32 - a later NumPy would
+    compare ``keyword_post > threshold`` in float64 and accept a positive that lies between ``threshold`` and ``float32(threshold)``."""
+    keyword_post = np.asarray(keyword_post)
     if thresholds is None:
         thresholds = np.arange(0.5, 0.99999, 0.005)  # :185
     neg = np.convolve(no_keyword_post, np.ones((windowsize,)) / windowsize, mode="same")  # :188-189
     frr, far, cnt = [], [], []
     for threshold in thresholds:
-        accepts = (keyword_post > threshold).sum()  # :201
+        accepts = (keyword_post > keyword_post.dtype.type(threshold)).sum()  # :201, as NumPy 1.19.5 promotes it
         frr.append((num_wakewords - accepts) / num_wakewords)  # :202-204
         prev = False
         fa = 0

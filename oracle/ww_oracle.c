@@ -591,7 +591,9 @@ int wwo_far_frr(const double *pos, int64_t P, const double *neg_smoothed, int64_
   for (int k = 0; k < nthr; ++k) {
     double t = thr[k];
     int64_t acc = 0;
-    for (int64_t i = 0; i < P; ++i) acc += pos[i] > t;
+    /* the positives are float32 posteriors and the reference's NumPy (1.19.5) compares a float32 array with a float64 scalar in
+     * float32; the smoothed negatives below are float64 and compare in double */
+    for (int64_t i = 0; i < P; ++i) acc += (float)pos[i] > (float)t;
     frr[k] = (num_wakewords - (double)acc) / num_wakewords;
     int64_t fa = 0;
     int prev = 0;

@@ -23,6 +23,7 @@ TAU_E = 1.2e-5      # fp32 encoder output, relative to max(1, max|row|) (measure
 TAU_BF16 = 6.5e-4   # precision="bf16x3" posteriors (measured 1.6e-4)
 TAU_E_BF16 = 1.5e-4  # precision="bf16x3" encoder output (measured 3.7e-5)
 TAU_STREAM = 3e-4   # streaming, after the front end (measured 7.6e-5)
+TAU_STREAM_BF16 = 2.1e-4  # precision="bf16x3" stream banks (measured 5.15e-5)
 TOL_FILTER = 3e-6   # filter.tflite alone: absolute log-mel (measured 7.8e-7)
 
 
@@ -300,43 +301,114 @@ def test_slide_forward_hop_1_at_64_and_65_windows(engines, ref, name):
 
 
 # ---------------------------------------------------------------- g. streaming
+STREAM_S = 8
+
+
+@pytest.fixture(scope="module")
+def stream_ref(engines, oracles, ref):
+    """name -> (pcm, want, want64), computed once per module: 8 streams offset in time by 2 ticks each on a PCM stream whose
+    posteriors cross the decision range; ``want[s]``: the C oracle's log-mel rows, Ref64 on the hop-1 windows (as
+    test_stream_bank_matches_batch_path builds them); ``want64[s]`` for two of the streams: the float64 front end's rows
+    (Ref64.logmel) instead of the C oracle's."""
+    cache = {}
+
+    def get(name):
+        if name in cache:
+            return cache[name]
+        e, ora = engines[name], oracles[name]
+        r = ref(name)[0]
+        S, n = STREAM_S, STREAM_TICKS * 320
+        src = R.decision_stream(ora, n, STREAM_SEED)
+        pcm = np.stack([np.concatenate([np.zeros(2 * s * 320, np.int16), src])[:n] for s in range(S)])
+        memo, want = {}, []
+        for s in range(S):
+            want.append(_ref_windows(r, R.stream_windows(ora.logmel(pcm[s]), e.window), memo)[:, e.posterior_index])
+        assert len(memo) <= len(want[0]) + 1    # the delayed streams share stream 0's windows
+        # the same streams with the float64 front end's rows (Ref64.logmel: its silence rows are not exactly 0, so the delayed streams
+        # do not share windows with stream 0 - streams 0 and S - 1 stand for them)
+        memo64, want64 = {}, {}
+        for s in (0, S - 1):
+            mel64 = r.logmel(pcm[s]).y.astype(np.float32)
+            want64[s] = _ref_windows(r, R.stream_windows(mel64, e.window), memo64)[:, e.posterior_index]
+        cache[name] = (pcm, want, want64)
+        return cache[name]
+    return get
+
+
+def _run_bank(e, pcm, **flags):
+    """The posteriors of every stream of a StreamBank over STREAM_TICKS ticks of 20 ms."""
+    from wwhip.engine import StreamBank
+    S = len(pcm)
+    bank = StreamBank(e, S, **flags)
+    posts = [[] for _ in range(S)]
+    try:
+        for t in range(STREAM_TICKS):
+            p, k = bank.step(pcm[:, t * 320:(t + 1) * 320], np.ones(S, np.uint8))
+            for s in range(S):
+                posts[s] += [float(p[s, j]) for j in range(k[s])]
+    finally:
+        bank.close()
+    return posts
+
+
+def _stream_post(case, posts, want, want64, tau):
+    S = len(posts)
+    for s in range(S):
+        assert len(posts[s]) == len(want[s])
+    _post(f"{case}, {S} streams", np.concatenate(posts)[:, None], np.concatenate(want)[:, None], tau)
+    _post(f"{case}, streams 0 and {S - 1} against Ref64.logmel rows",
+          np.concatenate([posts[s] for s in want64])[:, None], np.concatenate(list(want64.values()))[:, None], tau)
+
+
 @pytest.mark.parametrize("name", ["CRNN", "Wavenet"])
-def test_stream_bank_vs_float64(engines, oracles, ref, name):
+def test_stream_bank_vs_float64(engines, stream_ref, name):
     """StreamBank's default one-launch tick and a full_recompute bank, 8 streams offset in time by 2 ticks each, on a PCM
     stream whose posteriors cross the decision range; reference: the C oracle's log-mel rows, Ref64 on the hop-1 windows
     (as test_stream_bank_matches_batch_path builds them), and for two of the streams the float64 front end's rows
     (Ref64.logmel) instead of the C oracle's.  Measured: tau 7.6e-5 (CRNN: the GPU front end's log-mel rows are
     not the oracle's to the last bit), 4.5e-6 (Wavenet); against Ref64.logmel rows 6.2e-5 (CRNN), 4.1e-6 (Wavenet) - the CRNN's
     tau is its sensitivity to fp32 log-mel rows, not a front-end error, so TAU_STREAM stays."""
-    from wwhip.engine import StreamBank
-    e, ora = engines[name], oracles[name]
-    r = ref(name)[0]
-    S, n = 8, STREAM_TICKS * 320
-    src = R.decision_stream(ora, n, STREAM_SEED)
-    pcm = np.stack([np.concatenate([np.zeros(2 * s * 320, np.int16), src])[:n] for s in range(S)])
-    memo, want = {}, []
-    for s in range(S):
-        want.append(_ref_windows(r, R.stream_windows(ora.logmel(pcm[s]), e.window), memo)[:, e.posterior_index])
-    assert len(memo) <= len(want[0]) + 1    # the delayed streams share stream 0's windows
-    # the same streams with the float64 front end's rows (Ref64.logmel: its silence rows are not exactly 0, so the delayed streams
-    # do not share windows with stream 0 - streams 0 and S - 1 stand for them)
-    memo64, want64 = {}, {}
-    for s in (0, S - 1):
-        mel64 = r.logmel(pcm[s]).y.astype(np.float32)
-        want64[s] = _ref_windows(r, R.stream_windows(mel64, e.window), memo64)[:, e.posterior_index]
+    pcm, want, want64 = stream_ref(name)
     for full in (False, True):
-        bank = StreamBank(e, S, full_recompute=full)
-        posts = [[] for _ in range(S)]
-        try:
-            for t in range(STREAM_TICKS):
-                p, k = bank.step(pcm[:, t * 320:(t + 1) * 320], np.ones(S, np.uint8))
-                for s in range(S):
-                    posts[s] += [float(p[s, j]) for j in range(k[s])]
-        finally:
-            bank.close()
-        for s in range(S):
-            assert len(posts[s]) == len(want[s])
-        _post(f"{name} stream bank full_recompute={full}, {S} streams", np.concatenate(posts)[:, None],
-              np.concatenate(want)[:, None], TAU_STREAM)
-        _post(f"{name} stream bank full_recompute={full}, streams 0 and {S - 1} against Ref64.logmel rows",
-              np.concatenate([posts[s] for s in want64])[:, None], np.concatenate(list(want64.values()))[:, None], TAU_STREAM)
+        posts = _run_bank(engines[name], pcm, full_recompute=full)
+        _stream_post(f"{name} stream bank full_recompute={full}", posts, want, want64, TAU_STREAM)
+
+
+BF16_BANKS = {"Wavenet": [("one launch", {}), ("two launches, waited", dict(two_launch=True, sync_wait=True)),
+                          ("full_recompute", dict(full_recompute=True))],
+              "CRNN": [("default", {}), ("full_recompute", dict(full_recompute=True))]}
+
+
+@pytest.mark.parametrize("name", ["CRNN", "Wavenet"])
+def test_stream_bank_bf16x3_vs_float64(assets, engines, stream_ref, name):
+    """The stream banks of a precision="bf16x3" engine on test_stream_bank_vs_float64's streams and references.  Wavenet: the default
+    one-launch tick (the bf16x3 tick kernel), the two-launch form waited for, and a full_recompute bank.  CRNN: the default bank -
+    its incremental kernel is fp32 by design, so it is held to the fp32 banks' TAU_STREAM - and a full_recompute bank (the fused
+    bf16 kernel).  Every figure is printed before anything is asserted.  Measured, against the C oracle's rows / against
+    Ref64.logmel rows: Wavenet tau 3.61e-5 / 3.57e-5 in all three forms (max|dp| 7.7e-7); CRNN full_recompute 5.15e-5 / 4.94e-5
+    (max|dp| 1.6e-5); CRNN default 7.56e-5 / 6.14e-5 - the fp32 banks' figures, as it is their kernel.  TAU_STREAM_BF16 is four times
+    the worst of the bf16 kernels' figures.
+    Without a tolerance: the Wavenet's one-launch and two-launch banks give the same bits on this input, and the CRNN's default
+    bank gives the bits of the fp32 engine's default bank."""
+    from wwhip.engine import Engine
+    pcm, want, want64 = stream_ref(name)
+    e = Engine(os.path.join(assets, name), precision="bf16x3")
+    try:
+        posts = {form: _run_bank(e, pcm, **flags) for form, flags in BF16_BANKS[name]}
+    finally:
+        e.close()
+    flat = lambda ps, which: np.concatenate([ps[s] for s in which])
+    for form, ps in posts.items():
+        for s in range(STREAM_S):
+            assert len(ps[s]) == len(want[s]), (form, s)
+        for what, which, w in (("the C oracle's rows", range(STREAM_S), want), ("Ref64.logmel rows", list(want64), want64)):
+            g, w64 = flat(ps, which), flat(w, which)
+            print(f"\nREF64 {name} bf16x3 stream bank, {form}, against {what}: needs tau {R.needed_tau(g[:, None], w64[:, None]):.2e}, "
+                  f"max|dp| {np.abs(g - w64).max():.2e}", end="")
+    for form, ps in posts.items():
+        tau = TAU_STREAM if (name, form) == ("CRNN", "default") else TAU_STREAM_BF16
+        _stream_post(f"{name} bf16x3 stream bank, {form}", ps, want, want64, tau)
+    if name == "Wavenet":
+        assert posts["one launch"] == posts["two launches, waited"]
+    else:
+        assert posts["default"] == _run_bank(engines[name], pcm)

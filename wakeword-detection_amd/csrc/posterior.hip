@@ -109,9 +109,17 @@ __global__ __launch_bounds__(256) void pick_kernel(const float *__restrict__ row
   int64_t lo = seg_offs[s], hi = seg_offs[s + 1];
   lo = lo < 0 ? 0 : lo;
   hi = hi > n ? n : hi;
-  float m = -INFINITY;  // (an empty run: the caller never asks for one - np.max of an empty list raises in the reference)
-  for (int64_t w = lo + lane; w < hi; w += 64) m = fmaxf(m, rows[w * n_out + pidx]);
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  // np.max's maximum: a NaN in the run makes the run NaN (fmaxf would drop it), and such a clip is above no threshold.  Once m is
+  // a NaN both tests are false and it stays.  (-inf for an empty run: np.max of an empty list raises in the reference.)
+  float m = -INFINITY;
+  for (int64_t w = lo + lane; w < hi; w += 64) {
+    const float v = rows[w * n_out + pidx];
+    m = (v > m || v != v) ? v : m;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v = __shfl_xor(m, o);
+    m = (v > m || v != v) ? v : m;
+  }
   if (lane == 0) out[s] = m;
 }
 
