@@ -12,7 +12,9 @@
 //   * K = 1 gives v = s: an every-member bank of one slot plans what an ordinary bank plans;
 //   * resets in the middle (mirrors zeroed as ww_stream_reset does) and the virtual ids of a reset;
 //   * the member table [S K], and every refusal: of a creation (slots outside 1..64, full recompute, unknown flags, no streams,
-//     S K > 65535 with 65535 itself allowed) and of a call on the wrong kind of bank, each with its reason.
+//     S K > 65535 with 65535 itself allowed) and of a call on the wrong kind of bank, each with its reason;
+//   * the id list of a reset or a move (sa_check_ids): no list, an empty one and 2 S ids pass; a negative count, more than 2 S ids and
+//     an id out of range are refused, each alone with its reason, and in that order where two apply.
 // Prints "ok <checks>" and exits 0; or says what failed and exits 1.
 #include <cstdio>
 #include <cstdlib>
@@ -213,6 +215,27 @@ int main() {
   CHECK(sa_check_call(true, "ww_stream_step_all", true, why, sizeof why) == WW_OK);
   char tiny[8];
   CHECK(sa_check_call(true, "ww_stream_step", false, tiny, sizeof tiny) == WW_EINVAL && strlen(tiny) == 7);  // cut, not overrun
+
+  // ---- the id list of a reset or a move on a bank of 4 streams: each refusal alone, then two at once in the fixed order
+  {
+    const int S = 4;
+    const int32_t good[8] = {0, 3, 3, 1, 2, 0, 3, 3}, low[3] = {0, -1, 2}, high[3] = {0, 1, 4}, nine[9] = {0, 1, 2, 3, 0, 1, 2, 3, 0};
+    CHECK(sa_check_ids(nullptr, 0, S, why, sizeof why) == WW_OK);
+    CHECK(sa_check_ids(nullptr, -5, S, why, sizeof why) == WW_OK && sa_check_ids(nullptr, 1000, S, why, sizeof why) == WW_OK);  // every stream: n is not looked at
+    CHECK(sa_check_ids(good, 0, S, why, sizeof why) == WW_OK);
+    CHECK(sa_check_ids(good, 3, S, why, sizeof why) == WW_OK);
+    CHECK(sa_check_ids(good, 2 * S, S, why, sizeof why) == WW_OK);  // a stream may be named again: up to 2 S ids
+    why[0] = 0;
+    CHECK(sa_check_ids(good, -1, S, why, sizeof why) == WW_EINVAL && strcmp(why, "negative id count") == 0);
+    CHECK(sa_check_ids(nine, 2 * S + 1, S, why, sizeof why) == WW_EINVAL && strcmp(why, "more ids than streams") == 0);
+    CHECK(sa_check_ids(low, 3, S, why, sizeof why) == WW_EINVAL && strcmp(why, "stream id -1 out of range") == 0);
+    CHECK(sa_check_ids(high, 3, S, why, sizeof why) == WW_EINVAL && strcmp(why, "stream id 4 out of range") == 0);
+    CHECK(sa_check_ids(high, 2, S, why, sizeof why) == WW_OK);  // (the bad id lies behind the count)
+    const int32_t nine_bad[9] = {7, 1, 2, 3, 0, 1, 2, 3, 0};
+    CHECK(sa_check_ids(nine_bad, 9, S, why, sizeof why) == WW_EINVAL && strstr(why, "more ids"));  // the count is looked at before the ids
+    CHECK(sa_check_ids(good, 1, 0, why, sizeof why) == WW_EINVAL && strstr(why, "more ids"));
+    CHECK(sa_check_ids(low, 3, S, nullptr, 0) == WW_EINVAL);
+  }
 
   printf("ok %ld\n", n_checks);
   return 0;

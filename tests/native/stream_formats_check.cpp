@@ -6,7 +6,8 @@
 //     met), a gap between two frames is one pad byte and lies in front of an int16 frame only, offsets ascend, the total is the end of
 //     the last frame = the frames' bytes + the pad bytes;
 //   * the reserved size: formats_layout_max bounds the layout after every step of random move scripts;
-//   * a bank of int16 classes only: the layout is 2 x stream_rates.h's sample layout, its maximum 2 x rates_layout_max;
+//   * a bank of int16 classes only: the layout is 2 x stream_rates.h's sample layout, its maximum 2 x rates_layout_max, and it has no
+//     pad byte (the sample offsets of such a bank are its byte offsets halved);
 //   * the packet checks: an int16 packet with an odd offset or an odd length is refused with the packet named, a G.711 packet starts
 //     and ends anywhere, the sample counts are bytes / bytes per sample.
 // Prints "layout <S> <frame bytes...> | <byte offsets...>" for the mix of tests/test_gpu_g711_streams.py, then "ok <checks>", and exits 0;
@@ -169,6 +170,11 @@ int main() {
       CHECK(nb == 2 * ns && formats_layout_max(a, g, S) == 2 * rates_layout_max(b, S));
       for (int s = 0; s <= S; ++s) CHECK(bo[(size_t)s] == 2 * so[(size_t)s]);
       for (int s = 0; s < S; ++s) CHECK(fb[(size_t)s] == 2 * fs[(size_t)s] && fm[(size_t)s] == WW_FMT_I16);
+      // no pad byte anywhere in a table without G.711: a frame starts where the one before ends, so the sample offsets are bo / 2
+      bool odd16 = false, padded16 = false;
+      check_layout(a, g, cls, &odd16, &padded16);
+      CHECK(!padded16 && !odd16);
+      for (int s = 0; s < S; ++s) CHECK(bo[(size_t)s + 1] == bo[(size_t)s] + fb[(size_t)s]);
     }
   }
 

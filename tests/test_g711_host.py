@@ -174,6 +174,7 @@ def test_host_detectable_errors_raise_before_any_device_call(monkeypatch):
     # a per-stream bank's frames: the flat uint8 block, or one array per stream of the stream's own dtype
     bank = StreamBank.__new__(StreamBank)
     bank.S, bank._mixed, bank._g711, bank._keep, bank._h = 3, True, True, None, None
+    bank._dtype, bank._shape = np.dtype(np.uint8), (962,)
     bank.sample_formats = ["mulaw", "pcm16", "alaw"]
     bank.frame_samples = np.array([161, 320, 160], np.int32)
     bank.frame_bytes = np.array([161, 640, 160], np.int32)
@@ -213,7 +214,7 @@ def test_host_detectable_errors_raise_before_any_device_call(monkeypatch):
         bank.set_rate([0], 8000, "g722")
     # the uniform bank: [S, F] uint8
     uni = StreamBank.__new__(StreamBank)
-    uni.S, uni._mixed, uni._g711, uni._keep, uni._shape = 2, False, True, None, (2, 160)
+    uni.S, uni._mixed, uni._g711, uni._keep, uni._shape, uni._dtype = 2, False, True, None, (2, 160), np.dtype(np.uint8)
     uni.sample_formats, uni.frame_byte_offs = ["mulaw", "mulaw"], np.array([0, 160, 320], np.int64)
     assert uni._frames_address(np.zeros((2, 160), np.uint8)) != 0
     with pytest.raises(ValueError, match="not int16"):

@@ -142,6 +142,7 @@ def test_host_detectable_errors_raise_before_any_device_call(monkeypatch):
     # the frames' shape follows the bank's rate
     bank = StreamBank.__new__(StreamBank)
     bank.S, bank._shape, bank._keep, bank._h = 3, (3, 960), None, None
+    bank._dtype, bank.frame_byte_offs = np.dtype(np.int16), np.arange(4, dtype=np.int64) * 1920
     with pytest.raises(ValueError, match=r"\[3, 960\] int16"):
         bank._frames_address(np.zeros((3, 320), np.int16))
     assert bank._frames_address(np.zeros((3, 960), np.int16)) != 0

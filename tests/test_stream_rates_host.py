@@ -140,6 +140,8 @@ def test_host_detectable_errors_raise_before_any_device_call(monkeypatch):
     bank.S, bank._mixed, bank._keep, bank._h = 3, True, None, None
     bank.frame_samples = np.array([960, 320, 160], np.int32)
     bank.frame_offs = np.array([0, 960, 1280, 1440], np.int64)
+    bank.frame_bytes, bank.frame_byte_offs = 2 * bank.frame_samples, 2 * bank.frame_offs
+    bank._dtype, bank._shape = np.dtype(np.int16), (1440,)
     with pytest.raises(ValueError, match="1440 int16 samples"):
         bank._frames_address(np.zeros(1441, np.int16))
     with pytest.raises(ValueError, match="1440 int16 samples"):
@@ -149,7 +151,7 @@ def test_host_detectable_errors_raise_before_any_device_call(monkeypatch):
     assert bank._frames_address(np.zeros(1440, np.int16)) != 0
     assert bank._frames_address([np.zeros(960, np.int16), np.zeros(320, np.int16), np.zeros(160, np.int16)]) != 0
     with pytest.raises(ValueError, match="not among the bank's rates"):
-        bank._classes = [48000, 16000, 8000]
+        bank._classes = [(48000, "pcm16"), (16000, "pcm16"), (8000, "pcm16")]
         bank.set_rate([0], 44100)
     uniform = StreamBank.__new__(StreamBank)
     with pytest.raises(ValueError, match="runs at one rate"):

@@ -79,6 +79,18 @@ static inline int sa_check_call(bool every, const char *call, bool wants_every, 
   return WW_OK;
 }
 
+// The id list of ww_stream_reset, ww_stream_set_model and ww_stream_set_rate on a bank of S streams: ids == nullptr names every stream
+// (n is not looked at); else n ids, a stream as often as the caller likes, up to the 2 S entries the list is staged in.  WW_OK, or
+// WW_EINVAL with the reason in err, looked for in this order: a negative count, more ids than that, an id out of range.
+static inline int sa_check_ids(const int32_t *ids, int64_t n, int S, char *err, size_t cap) {
+  if (!ids) return WW_OK;
+  if (n < 0) return sa_refuse(err, cap, "negative id count");
+  if (n > 2 * (int64_t)S) return sa_refuse(err, cap, "more ids than streams");
+  for (int64_t i = 0; i < n; ++i)
+    if (ids[i] < 0 || ids[i] >= S) return sa_refuse(err, cap, "stream id %d out of range", (int)ids[i]);
+  return WW_OK;
+}
+
 // ---- one tick ---------------------------------------------------------------------------------------------------------------------
 // frames that `tot` buffered samples complete (one whenever `window` are buffered, then the oldest `hop` are dropped): the rule of
 // stream_fe.h's ww_fe_frames, which the feed uses, stated where no HIP header is in reach (the check program holds it against the

@@ -120,6 +120,28 @@ struct ww_streams {
     const int rc = sa_check_call(every, call, wants_every, why, sizeof why);
     return rc ? ww_fail(ctx, rc, "%s", why) : WW_OK;
   }
+  // likewise the id list of a reset or a move (stream_all.h: sa_check_ids)
+  int check_ids(const int32_t *ids, int32_t n) const {
+    char why[64];
+    const int rc = sa_check_ids(ids, n, S, why, sizeof why);
+    return rc ? ww_fail(ctx, rc, "%s", why) : WW_OK;
+  }
+  // a call that failed after the host's mirrors (fill, ring positions, state parity, the member and rate tables) had moved leaves them
+  // out of step with the device: `guarded` marks the bank, and `check_sound` refuses every later call that would build on them
+  // instead of producing posteriors of a state that never existed
+  int check_sound() const {
+    return broken ? ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one") : WW_OK;
+  }
+  template <typename Body>
+  int guarded(Body &&body) {  // body(bool *mutated): sets *mutated once the mirrors move
+    bool mutated = false;
+    const int rc = body(&mutated);
+    if (rc != WW_OK && mutated) broken = true;
+    return rc;
+  }
+  // the device's address of a place in the page-locked input block
+  template <typename P>
+  const P *dev_of(const P *host) const { return (const P *)(h_pack_dev + ((const char *)host - h_pack)); }
   // the kernels' extra argument: nullptr for a bank of one model
   const ww_set_ref *ref() const { return set ? &set_ref : nullptr; }
   int send_stream_model() {  // the host's copy -> the device table, in stream order (ww_tables::send, the one upload path)
@@ -133,6 +155,11 @@ static inline uint64_t st_now_ns() {
   timespec ts;
   clock_gettime(CLOCK_MONOTONIC, &ts);
   return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
+}
+
+// scratch of the per-window kernels for nw windows (explicit window rows: never the sliding form)
+static size_t model_scratch_bytes(const ww_model *m, int nw) {
+  return m->kind == WW_KIND_CRNN ? ww_crnn_workspace(m, nw, false) : ww_wave_workspace(m, nw);
 }
 
 struct stream_fe_args {
@@ -436,9 +463,8 @@ static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model
                    ((st->incremental && model->filt.n_mel == 40) || (!every_k && ww_wave_tick_capable(model, S)));
   // a borrowed stream is the caller's: when the call returns everything enqueued on it has completed, as before
   st->poll = ctx->own_stream && !(flags & WW_STREAM_SYNC_WAIT);
-  // model scratch of the per-window kernels (explicit window rows: never the sliding form); the incremental CRNN needs none
-  size_t ws_bytes = st->incremental ? 256
-                    : (model->kind == WW_KIND_CRNN ? ww_crnn_workspace(model, 2 * V, false) : ww_wave_workspace(model, 2 * V));
+  // model scratch of the per-window kernels; the incremental CRNN needs none
+  size_t ws_bytes = st->incremental ? 256 : model_scratch_bytes(model, 2 * V);
   bool ok = hipMalloc((void **)&st->ring, (size_t)2 * S * ST_RING * 4) == hipSuccess &&
             hipMalloc((void **)&st->hist, hist_elems * 4) == hipSuccess &&
             hipMalloc((void **)&st->prev, (size_t)2 * S * 4) == hipSuccess &&
@@ -582,7 +608,7 @@ int ww_stream_create_set_all(ww_ctx *ctx, const ww_model_set *set, int32_t S, co
 static int attach_resampler_impl(ww_streams *st, const ww_resampler *r, const int32_t *format, const char *what) {
   ww_ctx *ctx = st->ctx;
   if (!r) return ww_fail(ctx, WW_EINVAL, "%s: NULL resampler", what);
-  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
+  if (int rc = st->check_sound()) return rc;
   if (st->uniform_frame()) return ww_fail(ctx, WW_EINVAL, "%s: this bank already has a resampler (%d Hz frames)", what, st->uniform_frame() * 50);
   if (st->rates) return ww_fail(ctx, WW_EINVAL, "%s: this bank already has per-stream rates (ww_stream_attach_rates)", what);
   if (st->used) return ww_fail(ctx, WW_ESTATE, "%s: the bank has ticked or been fed: a resampler is attached to a new bank", what);
@@ -611,7 +637,7 @@ static int attach_rates_impl(ww_streams *st, const ww_resampler *const *rs, cons
                              const char *what) {
   ww_ctx *ctx = st->ctx;
   if (!rs) return ww_fail(ctx, WW_EINVAL, "%s: NULL class table", what);
-  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
+  if (int rc = st->check_sound()) return rc;
   if (n_rates < 1 || n_rates > WW_STREAM_MAX_RATES) return ww_fail(ctx, WW_EINVAL, "%s: %d rate classes: a bank has 1..%d", what, (int)n_rates, WW_STREAM_MAX_RATES);
   if (st->uniform_frame()) return ww_fail(ctx, WW_EINVAL, "%s: this bank already has a resampler (%d Hz frames)", what, st->uniform_frame() * 50);
   if (st->rates) return ww_fail(ctx, WW_EINVAL, "%s: this bank already has its rates (%d classes)", what, ww_k_rates_classes(st->rates));
@@ -637,20 +663,22 @@ int ww_stream_attach_rates_fmt(ww_streams *st, const ww_resampler *const *rs, co
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
+// A plain bank's frames (no rates attached): WW_CHUNK int16 samples per stream, back to back.  `unit`: 1 counts samples, 2 bytes.
+static void plain_layout(int S, int unit, int32_t *frame, int64_t *offs) {
+  for (int s = 0; s <= S; ++s) {
+    if (s < S) frame[s] = WW_CHUNK * unit;
+    offs[s] = (int64_t)s * WW_CHUNK * unit;
+  }
+}
+
 int ww_stream_frame_layout(const ww_streams *st, int32_t *frame_samples, int64_t *frame_offs) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
   if (!frame_samples || !frame_offs) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_layout: NULL argument");
   if (st->g711())
     return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_layout: this bank has G.711 streams, its frames are counted in bytes: ww_stream_frame_layout_bytes");
-  if (st->rates) {
-    ww_k_rates_layout(st->rates, frame_samples, frame_offs);
-    return WW_OK;
-  }
-  for (int s = 0; s <= st->S; ++s) {
-    if (s < st->S) frame_samples[s] = WW_CHUNK;
-    frame_offs[s] = (int64_t)s * WW_CHUNK;
-  }
+  if (st->rates) ww_k_rates_layout(st->rates, frame_samples, frame_offs);
+  else plain_layout(st->S, 1, frame_samples, frame_offs);
   return WW_OK;
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
@@ -662,23 +690,18 @@ int ww_stream_set_rate(ww_streams *st, const int32_t *ids, int32_t n, int32_t ra
   if (!st) return WW_EINVAL;
   ww_ctx *ctx = st->ctx;
   if (!st->rates || st->uniform_frame()) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_rate: this bank has no per-stream rates (ww_stream_attach_rates)");
-  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
+  if (int rc = st->check_sound()) return rc;
   const int K = ww_k_rates_classes(st->rates);
   if (rate_class < 0 || rate_class >= K) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_rate: class %d: the bank has rate classes 0..%d", (int)rate_class, K - 1);
-  if (ids && n < 0) return ww_fail(ctx, WW_EINVAL, "negative id count");
-  if (ids && n > 2 * st->S) return ww_fail(ctx, WW_EINVAL, "more ids than streams");
+  if (int rc = st->check_ids(ids, n)) return rc;
   const int count = ids ? n : st->S;
-  for (int i = 0; ids && i < n; ++i)
-    if (ids[i] < 0 || ids[i] >= st->S) return ww_fail(ctx, WW_EINVAL, "stream id %d out of range", ids[i]);
   if (count == 0) return WW_OK;
   WW_ON_DEVICE(ctx, dev_scope);
-  if (int rc = ww_k_rates_move(st->rates, ids, count, rate_class)) {
-    st->broken = true;  // (the copy may or may not have been enqueued: which table the device holds is not known)
-    return rc;
-  }
-  const int rc = ww_stream_reset(st, ids, n);
-  if (rc != WW_OK) st->broken = true;
-  return rc;
+  return st->guarded([&](bool *mutated) {
+    *mutated = true;  // (a failed upload may or may not have been enqueued: which table the device holds is not known)
+    if (int rc = ww_k_rates_move(st->rates, ids, count, rate_class)) return rc;
+    return ww_stream_reset(st, ids, n);
+  });
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
@@ -689,11 +712,9 @@ int ww_stream_frame_layout_bytes(const ww_streams *st, int32_t *frame_bytes, int
   if (!frame_bytes || !byte_offs || !formats) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_frame_layout_bytes: NULL argument");
   if (st->rates) {
     ww_k_rates_layout_bytes(st->rates, frame_bytes, byte_offs, formats);
-    return WW_OK;
-  }
-  for (int s = 0; s <= st->S; ++s) {
-    if (s < st->S) frame_bytes[s] = WW_CHUNK * 2, formats[s] = WW_SAMPLE_I16;
-    byte_offs[s] = (int64_t)s * WW_CHUNK * 2;
+  } else {
+    plain_layout(st->S, 2, frame_bytes, byte_offs);
+    std::fill(formats, formats + st->S, (int32_t)WW_SAMPLE_I16);
   }
   return WW_OK;
   WW_GUARD_END(st ? st->ctx : nullptr)
@@ -720,27 +741,25 @@ int ww_stream_set_model(ww_streams *st, const int32_t *ids, int32_t n, int32_t m
   ww_ctx *ctx = st->ctx;
   if (!st->set) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_model: this bank was not created from a model set");
   if (int rc = st->check_call("ww_stream_set_model", false)) return rc;
-  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
+  if (int rc = st->check_sound()) return rc;
   if (model < 0 || model >= st->set->n) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_model: model %d: the set has members 0..%d", (int)model, st->set->n - 1);
-  if (ids && n < 0) return ww_fail(ctx, WW_EINVAL, "negative id count");
-  if (ids && n > 2 * st->S) return ww_fail(ctx, WW_EINVAL, "more ids than streams");
+  if (int rc = st->check_ids(ids, n)) return rc;
   const int count = ids ? n : st->S;
-  for (int i = 0; ids && i < n; ++i)
-    if (ids[i] < 0 || ids[i] >= st->S) return ww_fail(ctx, WW_EINVAL, "stream id %d out of range", ids[i]);
   if (count == 0) return WW_OK;
   WW_ON_DEVICE(ctx, dev_scope);
-  // the host's table is what the device's was last sent: it changes only with an upload that was enqueued, and a failure behind
-  // that point (the reset's kernels) leaves streams on their new member with their old caches: no further ticks
-  const std::vector<int32_t> before = st->stream_model;
-  for (int i = 0; i < count; ++i) st->stream_model[ids ? ids[i] : i] = model;
-  if (int rc = st->send_stream_model()) {
-    st->stream_model = before;
-    st->broken = true;  // (the copy may or may not have been enqueued: which table the device holds is not known)
-    return rc;
-  }
-  const int rc = ww_stream_reset(st, ids, n);
-  if (rc != WW_OK) st->broken = true;
-  return rc;
+  // the host's table is what the device's was last sent: it changes only with an upload that was enqueued (a failed one may or may
+  // not have been: which table the device holds is not known), and a failure behind that point (the reset's kernels) leaves streams
+  // on their new member with their old caches: no further ticks
+  return st->guarded([&](bool *mutated) {
+    *mutated = true;
+    const std::vector<int32_t> before = st->stream_model;
+    for (int i = 0; i < count; ++i) st->stream_model[ids ? ids[i] : i] = model;
+    if (int rc = st->send_stream_model()) {
+      st->stream_model = before;
+      return rc;
+    }
+    return ww_stream_reset(st, ids, n);
+  });
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
@@ -748,16 +767,13 @@ int ww_stream_reset(ww_streams *st, const int32_t *ids, int32_t n) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
   ww_ctx *ctx = st->ctx;
-  if (ids && n < 0) return ww_fail(ctx, WW_EINVAL, "negative id count");
+  if (int rc = st->check_ids(ids, n)) return rc;
   const int count = ids ? n : st->S;
   if (count == 0) return WW_OK;
   WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
   int32_t *d_ids = nullptr, *d_vids = nullptr;
   if (ids) {
-    for (int i = 0; i < n; ++i)
-      if (ids[i] < 0 || ids[i] >= st->S) return ww_fail(ctx, WW_EINVAL, "stream id %d out of range", ids[i]);
-    // reuse the window-valid buffer (2S ints) as id staging
-    if (n > 2 * st->S) return ww_fail(ctx, WW_EINVAL, "more ids than streams");
+    // reuse the window-valid buffer (2 S ints: sa_check_ids's bound) as id staging
     memcpy(st->h_win_valid, ids, (size_t)n * 4);
     WW_HIP(ctx, hipMemcpyAsync(st->d_win_valid, st->h_win_valid, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     d_ids = st->d_win_valid;
@@ -875,7 +891,7 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   // a bank at other rates: its frames go through ww_k_rates_tick's kernel into a device block, and the tick reads that
   const int16_t *rate_frames = nullptr;
   if (st->rates) {
-    if (int rc = ww_k_rates_tick(st->rates, frames, is_speech, (const int32_t *)(st->h_pack_dev + ((char *)h_ctl - st->h_pack)), &rate_frames)) return rc;
+    if (int rc = ww_k_rates_tick(st->rates, frames, is_speech, st->dev_of(h_ctl), &rate_frames)) return rc;
   } else {
     memcpy(h_frames, frames, (size_t)S * WW_CHUNK * 2);
   }
@@ -889,8 +905,8 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   if (st->one_launch) {
     // ---- ONE launch: front end + model, workgroup 2 v + k = window k of (virtual) stream v (crnn.hip: crnn_stream_kernel<FE>; wavenet.hip)
     ww_tick_fe fe = {};
-    fe.frames = rate_frames ? rate_frames : (const int16_t *)(st->h_pack_dev + ((char *)h_frames - st->h_pack));
-    fe.ctl = (const int32_t *)(st->h_pack_dev + ((char *)h_ctl - st->h_pack));
+    fe.frames = rate_frames ? rate_frames : st->dev_of(h_frames);
+    fe.ctl = st->dev_of(h_ctl);
     fe.ring = st->ring; fe.prev = st->prev; fe.hist = st->hist;
     fe.S = S; fe.HR = st->HR;
     fe.cv = ww_fe_pcm_of(st->fp); fe.hop = hop;
@@ -901,11 +917,11 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   } else {
     stream_fe_args a = {};
     // no copy engine on the tick's path: the kernel reads the pinned staging block itself
-    a.frames = rate_frames ? rate_frames : (const int16_t *)(st->h_pack_dev + ((char *)st->h_frames - st->h_pack));
-    a.ctl = (const int32_t *)(st->h_pack_dev + ((char *)st->h_ctl - st->h_pack));
-    a.h_row = (const int64_t *)(st->h_pack_dev + ((char *)st->h_win_row - st->h_pack));
-    a.h_valid = (const int32_t *)(st->h_pack_dev + ((char *)st->h_win_valid - st->h_pack));
-    a.h_aux = (const int32_t *)(st->h_pack_dev + ((char *)st->h_win_aux - st->h_pack));
+    a.frames = rate_frames ? rate_frames : st->dev_of(st->h_frames);
+    a.ctl = st->dev_of(st->h_ctl);
+    a.h_row = st->dev_of(st->h_win_row);
+    a.h_valid = st->dev_of(st->h_win_valid);
+    a.h_aux = st->dev_of(st->h_win_aux);
     a.d_row = st->d_win_row; a.d_valid = st->d_win_valid; a.d_aux = st->d_win_aux; a.nw = st->causal ? nw_c : nw; a.S = S;
     a.ring = st->ring;
     a.hist = st->hist; a.prev = st->prev;
@@ -933,13 +949,13 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     } else if (nw && !st->incremental) {
       // the per-window kernels' scratch under the model's options of THIS tick (ww_model_set_option may have lowered the
       // front/tail threshold since the bank was created: the split form then wants nw x 19 x 192 floats)
-      const size_t need = m->kind == WW_KIND_CRNN ? ww_crnn_workspace(m, nw, false) : ww_wave_workspace(m, nw);
+      const size_t need = model_scratch_bytes(m, nw);
       if (need > st->ws_bytes) {
         WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
         WW_HIP(ctx, hipFree(st->ws));
         st->ws = nullptr;
         st->ws_bytes = 0;
-        const size_t want = m->kind == WW_KIND_CRNN ? ww_crnn_workspace(m, 2 * st->V(), false) : ww_wave_workspace(m, 2 * st->V());
+        const size_t want = model_scratch_bytes(m, 2 * st->V());
         if (hipMalloc(&st->ws, want > need ? want : need) != hipSuccess) return ww_fail(ctx, WW_ENOMEM, "cannot grow the model scratch of %d streams", S);
         st->ws_bytes = want > need ? want : need;
       }
@@ -992,13 +1008,8 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
 static int stream_step_entry(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post, const char *call,
                              bool wants_every) {
   if (int rc = st->check_call(call, wants_every)) return rc;
-  // a tick that failed after the host's mirrors (fill, ring positions, state parity) had advanced leaves them out of step with
-  // the device: the bank refuses further ticks instead of producing posteriors of a state that never existed
-  if (st->broken) return ww_fail(st->ctx, WW_ESTATE, "this stream bank failed in an earlier tick: destroy it and create a new one");
-  bool mutated = false;
-  const int rc = stream_step_impl(st, frames, is_speech, post, n_post, &mutated);
-  if (rc != WW_OK && mutated) st->broken = true;
-  return rc;
+  if (int rc = st->check_sound()) return rc;
+  return st->guarded([&](bool *mutated) { return stream_step_impl(st, frames, is_speech, post, n_post, mutated); });
 }
 
 int ww_stream_step(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post) {
@@ -1039,7 +1050,7 @@ static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64
   ww_ctx *ctx = st->ctx;
   if (int rc = st->check_call(what, all)) return rc;
   if (!st->causal) return ww_fail(ctx, WW_EINVAL, "%s: only a bank created with WW_STREAM_CAUSAL can be fed (a window bank recomputes a window per row)", what);
-  if (st->broken) return ww_fail(ctx, WW_ESTATE, "this stream bank failed in an earlier call: destroy it and create a new one");
+  if (int rc = st->check_sound()) return rc;
   if (n < 0) return ww_fail(ctx, WW_EINVAL, "%s: negative stream count", what);
   if (!sample_offs || !row_offs || (n > 0 && !ids)) return ww_fail(ctx, WW_EINVAL, "%s: NULL argument", what);
   std::vector<uint8_t> seen((size_t)st->S, 0);
@@ -1069,8 +1080,7 @@ static int feed_check(ww_streams *st, const int32_t *ids, int32_t n, const int64
 int ww_stream_feed_rows(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
-  std::vector<int64_t> offs16;
-  return feed_check(st, ids, n, sample_offs, row_offs, "ww_stream_feed_rows", &offs16);
+  return feed_check(st, ids, n, sample_offs, row_offs, "ww_stream_feed_rows");
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
@@ -1182,10 +1192,7 @@ int ww_stream_feed(ww_streams *st, const int32_t *ids, int32_t n, const int16_t 
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
   if (st->g711()) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_feed: this bank has G.711 streams, its packets are counted in bytes: ww_stream_feed_bytes");
-  bool mutated = false;
-  const int rc = stream_feed_impl(st, ids, n, pcm, sample_offs, cap_rows, row_offs, post, mel, &mutated);
-  if (rc != WW_OK && mutated) st->broken = true;
-  return rc;
+  return st->guarded([&](bool *mutated) { return stream_feed_impl(st, ids, n, pcm, sample_offs, cap_rows, row_offs, post, mel, mutated); });
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
@@ -1193,8 +1200,7 @@ int ww_stream_feed(ww_streams *st, const int32_t *ids, int32_t n, const int16_t 
 int ww_stream_feed_rows_all(ww_streams *st, const int32_t *ids, int32_t n, const int64_t *sample_offs, int64_t *row_offs) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
-  std::vector<int64_t> offs16;
-  return feed_check(st, ids, n, sample_offs, row_offs, "ww_stream_feed_rows_all", &offs16, true);
+  return feed_check(st, ids, n, sample_offs, row_offs, "ww_stream_feed_rows_all", nullptr, true);
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
@@ -1203,10 +1209,7 @@ int ww_stream_feed_all(ww_streams *st, const int32_t *ids, int32_t n, const int1
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
   if (st->g711()) return ww_fail(st->ctx, WW_EINVAL, "ww_stream_feed_all: this bank has G.711 streams, its packets are counted in bytes: ww_stream_feed_bytes_all");
-  bool mutated = false;
-  const int rc = stream_feed_impl(st, ids, n, pcm, sample_offs, cap_rows, row_offs, post, mel, &mutated, true);
-  if (rc != WW_OK && mutated) st->broken = true;
-  return rc;
+  return st->guarded([&](bool *mutated) { return stream_feed_impl(st, ids, n, pcm, sample_offs, cap_rows, row_offs, post, mel, mutated, true); });
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
@@ -1216,7 +1219,6 @@ int ww_stream_feed_all(ww_streams *st, const int32_t *ids, int32_t n, const int1
 static int stream_feed_bytes(ww_streams *st, const int32_t *ids, int32_t n, const void *data, const int64_t *byte_offs, int64_t cap_rows, int64_t *row_offs,
                              float *post, float *mel, bool all) {
   const char *what = all ? "ww_stream_feed_bytes_all" : "ww_stream_feed_bytes";
-  bool mutated = false;
   std::vector<int64_t> so;
   const bool g711 = st->g711();
   if (n > 0 && ids && byte_offs) {  // (anything else is feed_check's refusal)
@@ -1232,9 +1234,9 @@ static int stream_feed_bytes(ww_streams *st, const int32_t *ids, int32_t n, cons
     }
   }
   const int64_t *sample_offs = so.empty() ? byte_offs : so.data();
-  const int rc = stream_feed_impl(st, ids, n, (const int16_t *)data, sample_offs, cap_rows, row_offs, post, mel, &mutated, all, g711 && !so.empty() ? byte_offs : nullptr, what);
-  if (rc != WW_OK && mutated) st->broken = true;
-  return rc;
+  return st->guarded([&](bool *mutated) {
+    return stream_feed_impl(st, ids, n, (const int16_t *)data, sample_offs, cap_rows, row_offs, post, mel, mutated, all, g711 && !so.empty() ? byte_offs : nullptr, what);
+  });
 }
 
 int ww_stream_feed_bytes(ww_streams *st, const int32_t *ids, int32_t n, const void *data, const int64_t *byte_offs, int64_t cap_rows, int64_t *row_offs,
@@ -1286,13 +1288,6 @@ int ww_vad_bank_step(int32_t S, const uint8_t *raw, int32_t rise_frames, int32_t
 
 // spokestack/wakeword/tflite.py:134-146 (VAD edge, reset on the fall) and :232-239 (running maximum, threshold, activation)
 // over the posteriors a tick delivered: the one-slot case of stream_all.h's rule (sa_trigger_update), where it is stated.
-static void trigger_update(int S, const uint8_t *is_speech, uint8_t *is_active, const float *post, const int32_t *n_post,
-                           double threshold, uint8_t *was_speech, float *posterior_max, int32_t *fired_ids, int32_t *n_fired,
-                           int32_t *fall_ids, int32_t *n_fall) {
-  sa_trigger_update(S, 1, is_speech, is_active, post, n_post, &threshold, was_speech, posterior_max, fired_ids, nullptr, nullptr, n_fired,
-                    fall_ids, n_fall);
-}
-
 int ww_trigger_bank_step(int32_t S, const uint8_t *is_speech, uint8_t *is_active, const float *post, const int32_t *n_post,
                          double threshold, uint8_t *was_speech, float *posterior_max, int32_t *fired_ids, int32_t *n_fired,
                          int32_t *fall_ids, int32_t *n_fall) {
@@ -1302,7 +1297,8 @@ int ww_trigger_bank_step(int32_t S, const uint8_t *is_speech, uint8_t *is_active
     return WW_EINVAL;
   for (int s = 0; s < S; ++s)
     if (n_post[s] < 0 || n_post[s] > 2) return WW_EINVAL;
-  trigger_update(S, is_speech, is_active, post, n_post, threshold, was_speech, posterior_max, fired_ids, n_fired, fall_ids, n_fall);
+  sa_trigger_update(S, 1, is_speech, is_active, post, n_post, &threshold, was_speech, posterior_max, fired_ids, nullptr, nullptr, n_fired,
+                    fall_ids, n_fall);
   return WW_OK;
   WW_GUARD_END(nullptr)
 }
@@ -1345,48 +1341,52 @@ int ww_timeout_bank_step(int32_t S, const uint8_t *is_speech, uint8_t *is_active
   WW_GUARD_END(nullptr)
 }
 
+}  // extern "C"
+
 // WakewordTrigger.__call__ for S streams as ONE call: the tick (ww_stream_step with bit 0 = is_speech, bit 1 = is_active as they
 // stand BEFORE the tick), then ww_trigger_bank_step over its posteriors, then WakewordTrigger.reset for the streams whose VAD bit
 // fell (tflite.py:143-146).  is_active is updated in place.
+// Every: the stage of an every-member bank (K slots per stream, the tick ww_stream_step_all); else K = 1 - one threshold, the slot and
+// mask lists not asked for (nullptr, as sa_trigger_update permits) -, known where the rule's loops are compiled.
+template <bool Every>
+static int stream_step_trigger(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, uint8_t *is_active, const double *thresholds,
+                               uint8_t *was_speech, float *posterior_max, float *post, int32_t *n_post, int32_t *fired_ids,
+                               int32_t *fired_slot, uint64_t *fired_mask, int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall) {
+  if (!is_speech || !is_active || !thresholds || !was_speech || !posterior_max || !fired_ids || !n_fired || !fall_ids || !n_fall ||
+      (Every && (!fired_slot || !fired_mask)))
+    return ww_fail(st->ctx, WW_EINVAL, "NULL argument");
+  if (int rc = st->check_call(Every ? "ww_stream_step_trigger_all" : "ww_stream_step_trigger", Every)) return rc;
+  *n_fired = *n_fall = 0;
+  st->stage_flags.resize((size_t)st->S);
+  for (int s = 0; s < st->S; ++s) st->stage_flags[s] = (uint8_t)((is_speech[s] != 0) | ((is_active[s] != 0) << 1));
+  int rc = stream_step_entry(st, frames, st->stage_flags.data(), post, n_post, Every ? "ww_stream_step_all" : "ww_stream_step", Every);
+  if (rc) return rc;
+  sa_trigger_update(st->S, Every ? st->K : 1, is_speech, is_active, post, n_post, thresholds, was_speech, posterior_max, fired_ids, fired_slot,
+                    fired_mask, n_fired, fall_ids, n_fall);
+  if (*n_fall) rc = ww_stream_reset(st, fall_ids, *n_fall);
+  return rc;
+}
+
+extern "C" {
+
 int ww_stream_step_trigger(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, uint8_t *is_active, double threshold,
                            uint8_t *was_speech, float *posterior_max, float *post, int32_t *n_post, int32_t *fired_ids,
                            int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
-  if (!is_speech || !is_active || !was_speech || !posterior_max || !fired_ids || !n_fired || !fall_ids || !n_fall)
-    return ww_fail(st->ctx, WW_EINVAL, "NULL argument");
-  if (int rc = st->check_call("ww_stream_step_trigger", false)) return rc;
-  *n_fired = *n_fall = 0;
-  st->stage_flags.resize((size_t)st->S);
-  for (int s = 0; s < st->S; ++s) st->stage_flags[s] = (uint8_t)((is_speech[s] != 0) | ((is_active[s] != 0) << 1));
-  int rc = ww_stream_step(st, frames, st->stage_flags.data(), post, n_post);
-  if (rc) return rc;
-  trigger_update(st->S, is_speech, is_active, post, n_post, threshold, was_speech, posterior_max, fired_ids, n_fired, fall_ids, n_fall);
-  if (*n_fall) rc = ww_stream_reset(st, fall_ids, *n_fall);
-  return rc;
+  return stream_step_trigger<false>(st, frames, is_speech, is_active, &threshold, was_speech, posterior_max, post, n_post, fired_ids, nullptr, nullptr,
+                                    n_fired, fall_ids, n_fall);
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 
-// The wake-word stage of an every-member bank as ONE call (include/wwhip.h): ww_stream_step_all with bit 0 = is_speech, bit 1 =
-// is_active as they stand BEFORE the tick, the K-slot rule over its posteriors, then ww_stream_reset of the streams whose VAD bit fell.
+// The wake-word stage of an every-member bank as ONE call (include/wwhip.h): the K-slot rule, and which slot it was
 int ww_stream_step_trigger_all(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, uint8_t *is_active, const double *thresholds,
                                uint8_t *was_speech, float *posterior_max, float *post, int32_t *n_post, int32_t *fired_ids,
                                int32_t *fired_slot, uint64_t *fired_mask, int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall) {
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
-  if (!is_speech || !is_active || !thresholds || !was_speech || !posterior_max || !fired_ids || !fired_slot || !fired_mask || !n_fired || !fall_ids ||
-      !n_fall)
-    return ww_fail(st->ctx, WW_EINVAL, "NULL argument");
-  if (int rc = st->check_call("ww_stream_step_trigger_all", true)) return rc;
-  *n_fired = *n_fall = 0;
-  st->stage_flags.resize((size_t)st->S);
-  for (int s = 0; s < st->S; ++s) st->stage_flags[s] = (uint8_t)((is_speech[s] != 0) | ((is_active[s] != 0) << 1));
-  int rc = ww_stream_step_all(st, frames, st->stage_flags.data(), post, n_post);
-  if (rc) return rc;
-  sa_trigger_update(st->S, st->K, is_speech, is_active, post, n_post, thresholds, was_speech, posterior_max, fired_ids, fired_slot, fired_mask,
-                    n_fired, fall_ids, n_fall);
-  if (*n_fall) rc = ww_stream_reset(st, fall_ids, *n_fall);
-  return rc;
+  return stream_step_trigger<true>(st, frames, is_speech, is_active, thresholds, was_speech, posterior_max, post, n_post, fired_ids, fired_slot,
+                                   fired_mask, n_fired, fall_ids, n_fall);
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 

@@ -711,9 +711,8 @@ def _member_slots(members, engine, n_streams: int, models, full_recompute: bool)
     return a
 
 
-def _stream_rates(sample_rate, n_streams: int, resampler) -> Tuple[np.ndarray, List[int]]:
-    """``sample_rate`` given per stream -> (``int32[S]`` rates, the distinct rates in order of first appearance: the bank's rate
-    classes).  Everything that can be refused without a device is refused here."""
+def _stream_rates(sample_rate, n_streams: int, resampler) -> np.ndarray:
+    """``sample_rate`` given per stream -> the ``int32[S]`` rates.  Everything that can be refused without a device is refused here."""
     if resampler is not None:
         raise ValueError("resampler= belongs to a bank at ONE rate: a bank with per-stream rates creates and owns its resamplers")
     rates = np.asarray(sample_rate)
@@ -726,10 +725,9 @@ def _stream_rates(sample_rate, n_streams: int, resampler) -> Tuple[np.ndarray, L
         if r <= 0 or r % 50:
             raise ValueError(f"sample_rate {r}: a 20 ms frame must be a whole number of samples "
                              "(rates with a fractional frame are not offered in the tick)")
-    classes = list(dict.fromkeys(rates.tolist()))
-    if len(classes) > MAX_RATES:
-        raise ValueError(f"{len(classes)} distinct sample rates: a bank has at most {MAX_RATES} rate classes")
-    return rates.astype(np.int32), classes
+    if len(set(rates.tolist())) > MAX_RATES:
+        raise ValueError(f"{len(set(rates.tolist()))} distinct sample rates: a bank has at most {MAX_RATES} rate classes")
+    return rates.astype(np.int32)
 
 
 SAMPLE_FORMATS = {"pcm16": _lib.SAMPLE_I16, "mulaw": _lib.SAMPLE_MULAW, "alaw": _lib.SAMPLE_ALAW}  # a stream's format -> WW_SAMPLE_*
@@ -737,16 +735,40 @@ _FORMAT_NAMES = {v: k for k, v in SAMPLE_FORMATS.items()}
 _FORMAT_DTYPE = {"pcm16": np.dtype(np.int16), "mulaw": np.dtype(np.uint8), "alaw": np.dtype(np.uint8)}
 
 
-def _stream_formats(sample_format, n_streams: int) -> Optional[List[str]]:
-    """``sample_format`` -> one format name per stream, or None when every stream reads pcm16 (a bank without formats).  Everything
-    that can be refused without a device is refused here."""
+def _stream_formats(sample_format, n_streams: int) -> List[str]:
+    """``sample_format`` -> one format name per stream.  Everything that can be refused without a device is refused here."""
     names = [sample_format] * n_streams if isinstance(sample_format, str) else list(sample_format)
     if len(names) != n_streams:
         raise ValueError(f"sample_format must name one format per stream ({n_streams}), got {len(names)}")
     for f in names:
         if not isinstance(f, str) or f not in SAMPLE_FORMATS:
             raise ValueError(f"unknown sample format {f!r}: one of {', '.join(SAMPLE_FORMATS)}")
-    return None if all(f == "pcm16" for f in names) else names
+    return names
+
+
+def _stream_classes(sample_rate, sample_format, resampler, n_streams: int):
+    """What ``StreamBank`` was asked for -> (rates, one format name per stream, per-stream form?).  A scalar rate with pcm16 streams,
+    or a scalar rate other than 16000 with a scalar format, is the bank at ONE rate - plain at 16000, else uniform; ``rates`` is that
+    rate, ``resampler``'s input rate where one is given.  Anything else is the per-stream form, even with one distinct rate:
+    ``rates`` is ``int32[S]``.  Everything that can be refused without a device is refused here."""
+    names = _stream_formats(sample_format, n_streams)
+    scalar = isinstance(sample_rate, (int, np.integer))
+    g711 = any(f != "pcm16" for f in names)
+    if not scalar or (g711 and not (isinstance(sample_format, str) and int(sample_rate) != 16000)):
+        rates = _stream_rates([int(sample_rate)] * n_streams if scalar else sample_rate, n_streams, resampler)
+        pairs = set(zip(rates.tolist(), names))
+        if len(pairs) > MAX_RATES:
+            raise ValueError(f"{len(pairs)} distinct (rate, format) pairs: a bank has at most {MAX_RATES} classes")
+        return rates, names, True
+    rate = int(sample_rate if resampler is None else resampler.rate_in)
+    if resampler is not None and int(sample_rate) not in (16000, rate):
+        raise ValueError(f"sample_rate = {sample_rate}, but the resampler reads {rate} Hz")
+    if rate <= 0 or rate % 50:
+        raise ValueError(f"sample_rate {rate}: a 20 ms frame must be a whole number of samples "
+                         "(rates with a fractional frame are not offered in the tick)")
+    if resampler is not None and rate == 16000:
+        raise ValueError("a resampler from 16000 Hz: that is a plain bank")
+    return rate, names, False
 
 
 def _checked_samples(a, fmt: str, what: str) -> np.ndarray:
@@ -760,8 +782,8 @@ def _checked_samples(a, fmt: str, what: str) -> np.ndarray:
 
 class StreamBank:
     """S device-resident streams advanced 20 ms per :meth:`step` (``ww_stream_*``)."""
-    _mixed = False  # per-stream rates (sample_rate given as a sequence)
-    _g711 = False  # some stream reads G.711 (sample_format=): frames and packets are byte blocks
+    _mixed = False  # the per-stream form (ww_stream_attach_rates[_fmt]): every stream in a (rate, format) class of its own choosing
+    _g711 = False  # some class reads G.711 (sample_format=): frames and packets are byte blocks
     members, n_members = None, 0  # the member slots of a bank that runs every listed member on every stream (members=)
 
     def _no_every(self, what: str) -> None:
@@ -811,58 +833,33 @@ class StreamBank:
         :attr:`frame_byte_offs` are there on every bank."""
         self.engine = engine
         self.S = int(n_streams)
-        formats = _stream_formats(sample_format, self.S)
+        # ---- what was asked for, and every refusal that needs no device
+        rates, names, self._mixed = _stream_classes(sample_rate, sample_format, resampler, self.S)
+        self._g711 = any(f != "pcm16" for f in names)
+        self.sample_rate = None if self._mixed else rates
+        self._classes = list(dict.fromkeys(zip(rates.tolist(), names))) if self._mixed else None  # (rate, format) pairs in class order
         self.members = None if members is None else _member_slots(members, engine, self.S, models, full_recompute)
         self.n_members = 0 if self.members is None else int(self.members.size)
-        scalar_rate = isinstance(sample_rate, (int, np.integer))
-        if formats is not None and not (scalar_rate and isinstance(sample_format, str) and int(sample_rate) != 16000):
-            rates, _ = _stream_rates([int(sample_rate)] * self.S if scalar_rate else sample_rate, self.S, resampler)
-            pairs = list(dict.fromkeys(zip(rates.tolist(), formats)))
-            if len(pairs) > MAX_RATES:
-                raise ValueError(f"{len(pairs)} distinct (rate, format) pairs: a bank has at most {MAX_RATES} classes")
-            self._create(engine, fp, full_recompute, two_launch, sync_wait, causal, models)
-            self._attach_rates(rates, pairs, formats)
-            self._tick_arrays()
-            return
-        if not scalar_rate:
-            rates, classes = _stream_rates(sample_rate, self.S, resampler)
-            self._create(engine, fp, full_recompute, two_launch, sync_wait, causal, models)
-            self._attach_rates(rates, classes)
-            self._tick_arrays()
-            return
-        self.sample_rate = int(sample_rate if resampler is None else resampler.rate_in)
-        if resampler is not None and int(sample_rate) not in (16000, self.sample_rate):
-            raise ValueError(f"sample_rate = {sample_rate}, but the resampler reads {self.sample_rate} Hz")
-        if self.sample_rate <= 0 or self.sample_rate % 50:
-            raise ValueError(f"sample_rate {self.sample_rate}: a 20 ms frame must be a whole number of samples "
-                             "(rates with a fractional frame are not offered in the tick)")
-        if resampler is not None and self.sample_rate == 16000:
-            raise ValueError("a resampler from 16000 Hz: that is a plain bank")
-        self.frame_samples = self.sample_rate // 50
-        self._resampler, self._own_resampler = resampler, False
-        self._create(engine, fp, full_recompute, two_launch, sync_wait, causal, models)
-        if self.sample_rate != 16000:
-            if self._resampler is None:
-                from .resample import Resampler
-                self._resampler, self._own_resampler = Resampler(self.sample_rate, 16000, engine.ctx), True
-            if formats is not None:  # the uniform bank of one G.711 format
-                self._g711, self._uniform_format = True, formats[0]
-                _lib.raise_for(self._lib.ww_stream_attach_resampler_fmt(self._h, self._resampler._h, SAMPLE_FORMATS[formats[0]]), engine.ctx.handle)
-            else:
-                _lib.raise_for(self._lib.ww_stream_attach_resampler(self._h, self._resampler._h), engine.ctx.handle)
-                n = C.c_int32(0)
-                _lib.raise_for(self._lib.ww_stream_frame_samples(self._h, C.byref(n)), engine.ctx.handle)
-                assert n.value == self.frame_samples
-        self._shape = (self.S, self.frame_samples)
-        self._tick_arrays()
-
-    def _create(self, engine, fp, full_recompute, two_launch, sync_wait, causal, models) -> None:
         is_set = isinstance(engine, ModelSet)
         if models is not None and not is_set:
             raise ValueError("models= names the members of a ModelSet: this bank is built on one Engine")
         if is_set and full_recompute:
             raise ValueError("full_recompute is not offered on a ModelSet")
         ids = _member_ids(models, self.S, engine.n_models, "models") if models is not None else None
+        # ---- the bank, its one attach call, its layout
+        self._resampler, self._own_resampler, self._class_rs = resampler, False, []
+        self._create(fp, full_recompute, two_launch, sync_wait, causal, ids)
+        try:
+            self._attach(rates, names)
+            self._read_layout()
+            assert (self.sample_rates == rates).all(), (self.sample_rates, rates)
+        except Exception:
+            self.close()
+            raise
+        self._tick_arrays()
+
+    def _create(self, fp, full_recompute, two_launch, sync_wait, causal, ids) -> None:
+        engine = self.engine
         self._lib = _lib.load()
         fp = fp or frontend_params()
         h = C.c_void_p()
@@ -872,7 +869,7 @@ class StreamBank:
         if self.n_members:
             _lib.raise_for(self._lib.ww_stream_create_set_all(engine.ctx.handle, engine.handle, self.S, _lib.ptr(self.members), self.n_members,
                                                               C.byref(fp), flags, C.byref(h)), engine.ctx.handle)
-        elif is_set:
+        elif isinstance(engine, ModelSet):
             _lib.raise_for(self._lib.ww_stream_create_set(engine.ctx.handle, engine.handle, self.S, _lib.ptr(ids), C.byref(fp), flags, C.byref(h)),
                            engine.ctx.handle)
         else:
@@ -881,46 +878,47 @@ class StreamBank:
         self._h = h
         _lib.register("streams", self)
 
-    def _attach_rates(self, rates: np.ndarray, classes: List, formats: Optional[List[str]] = None) -> None:
-        """``classes``: the bank's rates - or, with ``formats`` (one name per stream), its (rate, format) pairs - in class order."""
+    def _attach(self, rates, names: List[str]) -> None:
+        """The bank's one attach call: none (a plain bank), ``ww_stream_attach_resampler[_fmt]`` (the uniform bank: ``rates`` is its one
+        rate) or ``ww_stream_attach_rates[_fmt]`` (the per-stream form: ``rates[s]``, ``names[s]`` name stream ``s``'s class)."""
+        if not self._mixed and rates == 16000:
+            return
         from .resample import Resampler
-        self._mixed, self.sample_rate = True, None
-        self._classes, self._resampler, self._own_resampler = classes, None, False
-        self._class_rs = []
-        self._g711 = formats is not None
-        try:
-            by_rate = {}  # (two formats of one rate share the rate's resampler)
-            for c in classes:
-                r = c[0] if self._g711 else c
+        lib, ctx = self._lib, self.engine.ctx
+        if not self._mixed:
+            if self._resampler is None:
+                self._resampler, self._own_resampler = Resampler(rates, 16000, ctx), True
+            rc = (lib.ww_stream_attach_resampler_fmt(self._h, self._resampler._h, SAMPLE_FORMATS[names[0]]) if self._g711
+                  else lib.ww_stream_attach_resampler(self._h, self._resampler._h))
+        else:
+            classes, by_rate = self._classes, {}  # (two formats of one rate share the rate's resampler)
+            for r, _ in classes:
                 if r != 16000 and r not in by_rate:
-                    by_rate[r] = Resampler(r, 16000, self.engine.ctx)
+                    by_rate[r] = Resampler(r, 16000, ctx)
                     self._class_rs.append(by_rate[r])
-            table = (C.c_void_p * len(classes))(*[None if (c[0] if self._g711 else c) == 16000 else by_rate[c[0] if self._g711 else c]._h for c in classes])
+            table = (C.c_void_p * len(classes))(*[None if r == 16000 else by_rate[r]._h for r, _ in classes])
+            cls = np.array([classes.index(c) for c in zip(rates.tolist(), names)], np.int32)
             if self._g711:
-                cls = np.array([classes.index((int(r), f)) for r, f in zip(rates, formats)], np.int32)
-                fm = np.array([SAMPLE_FORMATS[c[1]] for c in classes], np.int32)
-                _lib.raise_for(self._lib.ww_stream_attach_rates_fmt(self._h, table, _lib.ptr(fm), len(classes), _lib.ptr(cls)), self.engine.ctx.handle)
+                fm = np.array([SAMPLE_FORMATS[f] for _, f in classes], np.int32)
+                rc = lib.ww_stream_attach_rates_fmt(self._h, table, _lib.ptr(fm), len(classes), _lib.ptr(cls))
             else:
-                cls = np.array([classes.index(int(r)) for r in rates], np.int32)
-                _lib.raise_for(self._lib.ww_stream_attach_rates(self._h, table, len(classes), _lib.ptr(cls)), self.engine.ctx.handle)
-            self._read_layout()
-            assert np.array_equal(self.frame_samples, rates // 50)
-        except Exception:
-            self.close()
-            raise
+                rc = lib.ww_stream_attach_rates(self._h, table, len(classes), _lib.ptr(cls))
+        _lib.raise_for(rc, ctx.handle)
 
     def _read_layout(self) -> None:
-        """``frame_samples``, ``frame_offs`` and ``sample_rates`` as the library states them (``ww_stream_frame_layout``)."""
-        fb, bo, fm = np.zeros(self.S, np.int32), np.zeros(self.S + 1, np.int64), np.zeros(self.S, np.int32)
+        """A tick's frames as the library states them (``ww_stream_frame_layout_bytes``, which answers on every bank): the six public
+        layout attributes, and the dtype and shape :meth:`_frames_address` passes without a second look.  Read again after a
+        :meth:`set_rate`.  ``frame_offs`` counts int16 samples: a bank with G.711 streams has none, and a bank without them has no pad
+        bytes, so its sample offsets are the byte offsets halved."""
+        S = self.S
+        fb, bo, fm = np.zeros(S, np.int32), np.zeros(S + 1, np.int64), np.zeros(S, np.int32)
         _lib.raise_for(self._lib.ww_stream_frame_layout_bytes(self._h, _lib.ptr(fb), _lib.ptr(bo), _lib.ptr(fm)), self.engine.ctx.handle)
+        fs = fb // np.where(fm == _lib.SAMPLE_I16, 2, 1).astype(np.int32)
         self.frame_bytes, self.frame_byte_offs, self.sample_formats = fb, bo, [_FORMAT_NAMES[int(v)] for v in fm]
-        if self._g711:  # (frame_offs counts int16 samples: such a bank has none)
-            fs = fb // np.where(fm == _lib.SAMPLE_I16, 2, 1).astype(np.int32)
-            self.frame_samples, self.frame_offs, self.sample_rates = fs, None, fs * 50
-            return
-        fs, fo = np.zeros(self.S, np.int32), np.zeros(self.S + 1, np.int64)
-        _lib.raise_for(self._lib.ww_stream_frame_layout(self._h, _lib.ptr(fs), _lib.ptr(fo)), self.engine.ctx.handle)
-        self.frame_samples, self.frame_offs, self.sample_rates = fs, fo, fs * 50
+        self.frame_samples, self.sample_rates = (fs if self._mixed else int(fs[0])), fs * 50
+        self.frame_offs = None if self._g711 else bo // 2
+        self._dtype = np.dtype(np.uint8 if self._g711 else np.int16)
+        self._shape = (int(bo[S]) // self._dtype.itemsize,) if self._mixed else (S, int(fs[0]))
 
     def _tick_arrays(self) -> None:
         self._post = np.zeros((self.S, self.n_members, 2) if self.n_members else (self.S, 2), np.float32)
@@ -930,69 +928,41 @@ class StreamBank:
         self._p_post, self._p_n, self._p_flags = (C.c_void_p(a.ctypes.data) for a in (self._post, self._n, self._flags))
         self._step = self._lib.ww_stream_step_all if self.n_members else self._lib.ww_stream_step
         self._keep = None
-        if not self._mixed:
-            self.sample_rates = np.full(self.S, self.sample_rate, np.int32)
-            self.frame_offs = None if self._g711 else np.arange(self.S + 1, dtype=np.int64) * self.frame_samples
-            self.sample_formats = [self._uniform_format if self._g711 else "pcm16"] * self.S
-            self.frame_bytes = np.full(self.S, self.frame_samples * (1 if self._g711 else 2), np.int32)
-            self.frame_byte_offs = np.arange(self.S + 1, dtype=np.int64) * int(self.frame_samples * (1 if self._g711 else 2))
 
-    def _ragged_address(self, frames) -> int:
-        """A bank with per-stream rates: the flat int16 block of ``frame_offs[S]`` samples, or S per-stream arrays."""
-        f = frames
-        if not (type(f) is np.ndarray and f.dtype == np.int16 and f.ndim == 1 and f.flags.c_contiguous):
-            if type(f) is np.ndarray and f.ndim == 1 and f.dtype != object:
-                f = np.ascontiguousarray(f, dtype=np.int16)
+    def _stage_frames(self, frames) -> np.ndarray:
+        """A tick's frames in any accepted form -> the block the library reads, placed and checked by the layout.  A whole block -
+        the flat one of ``frame_byte_offs[S]`` bytes, on a bank at one rate also ``[S, frame_samples]`` or anything numpy stacks to
+        it - is passed on; S per-stream arrays (the per-stream form) go to ``frame_byte_offs[s]`` each, pad bytes zero.  A bank
+        without G.711 streams converts to int16; one with them refuses an array of the other kind."""
+        S, total = self.S, int(self.frame_byte_offs[self.S])
+        holds = f"{total} bytes" if self._g711 else f"{total // 2} int16 samples"
+        which = "ww_stream_frame_layout_bytes" if self._g711 else "ww_stream_frame_layout"
+        if not self._mixed or (type(frames) is np.ndarray and frames.ndim == 1 and frames.dtype != object):
+            if not self._g711:
+                f = np.ascontiguousarray(frames, dtype=np.int16)
+            elif np.asarray(frames).dtype != np.uint8:
+                raise ValueError(f"the block of a bank with G.711 streams is uint8 ({holds}: {which}), not {np.asarray(frames).dtype}")
             else:
-                if len(f) != self.S:
-                    raise ValueError(f"frames must be one array per stream ({self.S}) or the flat block of {int(self.frame_offs[self.S])} int16 samples")
-                f = np.concatenate([np.asarray(a, dtype=np.int16).ravel() for a in f]) if self.S else np.zeros(0, np.int16)
-            self._keep = f  # (kept alive until the call has returned)
-        if f.size != int(self.frame_offs[self.S]):
-            raise ValueError(f"frames must hold {int(self.frame_offs[self.S])} int16 samples (ww_stream_frame_layout: stream s's "
-                             f"{'/'.join(str(int(v)) for v in sorted(set(self.frame_samples.tolist())))} samples from frame_offs[s]), got {f.size}")
-        return f.ctypes.data
-
-    def _byte_address(self, frames) -> int:
-        """A bank with G.711 streams: the uniform bank's ``[S, frame_samples]`` uint8, or a per-stream bank's flat uint8 block of
-        ``frame_byte_offs[S]`` bytes or S per-stream arrays, each of its stream's dtype (they are laid out with the pad bytes)."""
-        f = frames
-        total = int(self.frame_byte_offs[self.S])
-        if not self._mixed:
-            if not (type(f) is np.ndarray and f.dtype == np.uint8 and f.flags.c_contiguous):
-                f = self._keep = _checked_samples(frames, self.sample_formats[0] if self.S else "mulaw", "this bank").reshape(np.shape(frames))
-            if f.shape != self._shape:
-                raise ValueError(f"frames must be [{self.S}, {self._shape[1]}] uint8")
-            return f.ctypes.data
-        if type(f) is np.ndarray and f.ndim == 1 and f.dtype != object:
-            if f.dtype != np.uint8:
-                raise ValueError(f"the flat block of a bank with G.711 streams is uint8 ({total} bytes: ww_stream_frame_layout_bytes), not {f.dtype}")
-            if not f.flags.c_contiguous:
-                f = self._keep = np.ascontiguousarray(f)
-        else:
-            if len(f) != self.S:
-                raise ValueError(f"frames must be one array per stream ({self.S}) or the flat block of {total} bytes")
-            block = np.zeros(total, np.uint8)
-            for s, a in enumerate(f):
-                a = _checked_samples(a, self.sample_formats[s], f"stream {s}")
-                if a.nbytes != int(self.frame_bytes[s]):
-                    raise ValueError(f"stream {s}'s frame has {int(self.frame_samples[s])} samples, got {a.size}")
-                block[int(self.frame_byte_offs[s]):int(self.frame_byte_offs[s]) + a.nbytes] = a.view(np.uint8)
-            f = self._keep = block
-        if f.size != total:
-            raise ValueError(f"frames must hold {total} bytes (ww_stream_frame_layout_bytes), got {f.size}")
-        return f.ctypes.data
+                f = np.ascontiguousarray(frames)
+            if f.shape != self._shape and f.shape != (total // self._dtype.itemsize,):
+                raise ValueError(f"frames must hold {holds} ({which}), got {f.size}" if self._mixed
+                                 else f"frames must be [{S}, {self._shape[1]}] {self._dtype}")
+            return f
+        if len(frames) != S:
+            raise ValueError(f"frames must be one array per stream ({S}) or the flat block of {holds}")
+        block = np.zeros(total, np.uint8)
+        for s, a in enumerate(frames):
+            a = (_checked_samples(a, self.sample_formats[s], f"stream {s}") if self._g711 else np.ascontiguousarray(a, dtype=np.int16).ravel())
+            at = int(self.frame_byte_offs[s])
+            if a.nbytes != self.frame_bytes[s]:
+                raise ValueError(f"stream {s}'s frame has {int(self.frame_bytes[s]) // a.itemsize} samples, got {a.size} (frames must hold {holds})")
+            block[at:at + a.nbytes] = a.view(np.uint8)
+        return block
 
     def _frames_address(self, frames: np.ndarray) -> int:
-        if self._g711:
-            return self._byte_address(frames)
-        if self._mixed:
-            return self._ragged_address(frames)
         f = frames
-        if not (type(f) is np.ndarray and f.dtype == np.int16 and f.flags.c_contiguous):
-            f = self._keep = np.ascontiguousarray(frames, dtype=np.int16)  # (kept alive until the call has returned)
-        if f.shape != self._shape:
-            raise ValueError(f"frames must be [{self.S}, {self._shape[1]}] int16")
+        if not (type(f) is np.ndarray and f.dtype == self._dtype and f.flags.c_contiguous and f.shape == self._shape):
+            f = self._keep = self._stage_frames(frames)  # (kept alive until the call has returned)
         try:
             return C.addressof(C.c_char.from_buffer(f))  # (a third of the cost of f.ctypes.data_as)
         except (TypeError, ValueError):                   # a read-only array
@@ -1062,22 +1032,18 @@ class StreamBank:
         format only."""
         if not self._mixed:
             raise ValueError("set_rate: this bank runs at one rate (sample_rate was not given per stream)")
-        if self._g711:
-            if sample_format is not None and sample_format not in SAMPLE_FORMATS:
-                raise ValueError(f"unknown sample format {sample_format!r}: one of {', '.join(SAMPLE_FORMATS)}")
-            hits = [c for c in self._classes if c[0] == int(rate) and sample_format in (None, c[1])]
-            if len(hits) != 1:
-                raise ValueError(f"set_rate: ({rate} Hz, {sample_format}) names {len(hits)} of the bank's classes {self._classes}")
-            rate = hits[0]
-        elif sample_format not in (None, "pcm16"):
+        if not self._g711 and sample_format not in (None, "pcm16"):
             raise ValueError(f"set_rate: this bank's streams all read pcm16, not {sample_format}")
-        if (rate if self._g711 else int(rate)) not in self._classes:
-            raise ValueError(f"set_rate: {rate} Hz is not among the bank's rates {self._classes}")
+        if sample_format is not None and sample_format not in SAMPLE_FORMATS:
+            raise ValueError(f"unknown sample format {sample_format!r}: one of {', '.join(SAMPLE_FORMATS)}")
+        hits = [k for k, c in enumerate(self._classes) if c[0] == int(rate) and sample_format in (None, c[1])]
+        if len(hits) != 1:
+            raise ValueError(f"set_rate: ({rate} Hz, {sample_format}) names {len(hits)} of the bank's classes {self._classes}" if self._g711
+                             else f"set_rate: {rate} Hz is not among the bank's rates {[c[0] for c in self._classes]}")
         a = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
         if a is not None and a.size and (a.min() < 0 or a.max() >= self.S):
             raise ValueError("stream id out of range")
-        _lib.raise_for(self._lib.ww_stream_set_rate(self._h, _lib.ptr(a), 0 if a is None else a.size, self._classes.index(rate if self._g711 else int(rate))),
-                       self.engine.ctx.handle)
+        _lib.raise_for(self._lib.ww_stream_set_rate(self._h, _lib.ptr(a), 0 if a is None else a.size, hits[0]), self.engine.ctx.handle)
         self._read_layout()
 
     def window(self, stream: int) -> np.ndarray:
@@ -1094,26 +1060,50 @@ class StreamBank:
         otherwise).  However the samples are cut into packets, calls and :meth:`step` ticks, the results are the same bits.
         A bank at another rate, or with per-stream rates: each packet is at its stream's own rate."""
         self._no_every("feed")
-        if self._g711:
-            return self._feed_bytes(ids, packets, want_mel, False)
+        return self._feed(ids, packets, want_mel, False)
+
+    def _feed(self, ids: Sequence[int], packets: Sequence[np.ndarray], want_mel: bool, every: bool):
+        """:meth:`feed` (``every`` false) and :meth:`feed_all`: the call's ids and packets staged as one buffer, the library asked for
+        the rows the call will produce (``ww_stream_feed_rows[_all]``), then fed (``ww_stream_feed[_all]``), and the results cut per
+        listed stream.  A bank with G.711 streams feeds bytes (``ww_stream_feed_bytes[_all]``): ``packets[i]`` is int16 for a pcm16
+        stream and uint8 for a G.711 one, and as an int16 packet starts on an even byte of the gapless buffer the int16 packets go
+        first; the results come back in the caller's order."""
         a_ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
         n = int(a_ids.size)
         if len(packets) != n:
             raise ValueError("one packet per listed stream")
-        pk = [np.ascontiguousarray(p, dtype=np.int16).ravel() for p in packets]
-        offs = np.zeros(n + 1, np.int64)
-        np.cumsum([p.size for p in pk], out=offs[1:])
-        pcm = np.concatenate(pk) if n and offs[n] else np.zeros(1, np.int16)
+        back = range(n)
+        if self._g711:
+            if n and (a_ids.min() < 0 or a_ids.max() >= self.S):
+                raise ValueError("stream id out of range")
+            pk = [_checked_samples(p, self.sample_formats[int(s)], f"stream {int(s)}") for s, p in zip(a_ids, packets)]
+            order = sorted(range(n), key=lambda i: pk[i].dtype != np.int16)  # (stable: int16 packets first)
+            a_ids = np.ascontiguousarray(a_ids[order]) if n else a_ids
+            pk, back = [pk[i] for i in order], np.argsort(order) if n else []
+        else:
+            pk = [np.ascontiguousarray(p, dtype=np.int16).ravel() for p in packets]
+        counts = np.zeros(n + 1, np.int64)  # the packets' samples: ww_stream_feed_rows counts these on every bank
+        np.cumsum([p.size for p in pk], out=counts[1:])
+        offs = counts  # where packet i lies in the buffer: in samples, or on a bank with G.711 streams in bytes
+        if self._g711:
+            offs = np.zeros(n + 1, np.int64)
+            np.cumsum([p.nbytes for p in pk], out=offs[1:])
+            pk = [p.view(np.uint8) for p in pk]
+        data = np.concatenate(pk) if n and offs[n] else np.zeros(2, np.uint8)
         row_offs = np.zeros(n + 1, np.int64)
-        h = self.engine.ctx.handle
-        _lib.raise_for(self._lib.ww_stream_feed_rows(self._h, _lib.ptr(a_ids), n, _lib.ptr(offs), _lib.ptr(row_offs)), h)
+        lib, h = self._lib, self.engine.ctx.handle
+        rows_fn, feed_fn = {(False, False): (lib.ww_stream_feed_rows, lib.ww_stream_feed),
+                            (False, True): (lib.ww_stream_feed_rows_all, lib.ww_stream_feed_all),
+                            (True, False): (lib.ww_stream_feed_rows, lib.ww_stream_feed_bytes),
+                            (True, True): (lib.ww_stream_feed_rows_all, lib.ww_stream_feed_bytes_all)}[self._g711, every]
+        _lib.raise_for(rows_fn(self._h, _lib.ptr(a_ids), n, _lib.ptr(counts), _lib.ptr(row_offs)), h)
         rows = int(row_offs[n])
-        post = np.empty(max(rows, 1), np.float32)
+        post = np.empty((max(rows, 1), self.n_members) if every else max(rows, 1), np.float32)
         mel = np.empty((max(rows, 1), self.engine.n_mel), np.float32) if want_mel else None
-        _lib.raise_for(self._lib.ww_stream_feed(self._h, _lib.ptr(a_ids), n, _lib.ptr(pcm), _lib.ptr(offs), rows, _lib.ptr(row_offs),
-                                                _lib.ptr(post), _lib.ptr(mel) if want_mel else None), h)
-        posts = [post[row_offs[i]:row_offs[i + 1]].copy() for i in range(n)]
-        mels = [mel[row_offs[i]:row_offs[i + 1]].copy() for i in range(n)] if want_mel else None
+        _lib.raise_for(feed_fn(self._h, _lib.ptr(a_ids), n, _lib.ptr(data), _lib.ptr(offs), rows, _lib.ptr(row_offs), _lib.ptr(post),
+                               _lib.ptr(mel) if want_mel else None), h)
+        posts = [post[row_offs[j]:row_offs[j + 1]].copy() for j in back]
+        mels = [mel[row_offs[j]:row_offs[j + 1]].copy() for j in back] if want_mel else None
         return posts, mels
 
     def feed_all(self, ids: Sequence[int], packets: Sequence[np.ndarray], want_mel: bool = False):
@@ -1123,61 +1113,7 @@ class StreamBank:
         be cut into ``feed_all`` packets, calls and :meth:`step` ticks in any way."""
         if not self.n_members:
             raise ValueError("feed_all: this bank was not built with members=: an ordinary causal bank takes feed")
-        if self._g711:
-            return self._feed_bytes(ids, packets, want_mel, True)
-        a_ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
-        n = int(a_ids.size)
-        if len(packets) != n:
-            raise ValueError("one packet per listed stream")
-        pk = [np.ascontiguousarray(p, dtype=np.int16).ravel() for p in packets]
-        offs = np.zeros(n + 1, np.int64)
-        np.cumsum([p.size for p in pk], out=offs[1:])
-        pcm = np.concatenate(pk) if n and offs[n] else np.zeros(1, np.int16)
-        row_offs = np.zeros(n + 1, np.int64)
-        h, K = self.engine.ctx.handle, self.n_members
-        _lib.raise_for(self._lib.ww_stream_feed_rows_all(self._h, _lib.ptr(a_ids), n, _lib.ptr(offs), _lib.ptr(row_offs)), h)
-        rows = int(row_offs[n])
-        post = np.empty((max(rows, 1), K), np.float32)
-        mel = np.empty((max(rows, 1), self.engine.n_mel), np.float32) if want_mel else None
-        _lib.raise_for(self._lib.ww_stream_feed_all(self._h, _lib.ptr(a_ids), n, _lib.ptr(pcm), _lib.ptr(offs), rows, _lib.ptr(row_offs),
-                                                    _lib.ptr(post), _lib.ptr(mel) if want_mel else None), h)
-        posts = [post[row_offs[i]:row_offs[i + 1]].copy() for i in range(n)]
-        mels = [mel[row_offs[i]:row_offs[i + 1]].copy() for i in range(n)] if want_mel else None
-        return posts, mels
-
-    def _feed_bytes(self, ids: Sequence[int], packets: Sequence[np.ndarray], want_mel: bool, every: bool):
-        """:meth:`feed` / :meth:`feed_all` of a bank with G.711 streams (``ww_stream_feed_bytes`` / ``_all``): ``packets[i]`` is int16
-        for a pcm16 stream and uint8 for a G.711 one.  A call's packets are one byte buffer without gaps, and an int16 packet starts
-        on an even byte: the int16 packets go first, the results come back in the caller's order."""
-        a_ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
-        n = int(a_ids.size)
-        if len(packets) != n:
-            raise ValueError("one packet per listed stream")
-        if n and (a_ids.min() < 0 or a_ids.max() >= self.S):
-            raise ValueError("stream id out of range")
-        pk = [_checked_samples(p, self.sample_formats[int(s)], f"stream {int(s)}") for s, p in zip(a_ids, packets)]
-        order = sorted(range(n), key=lambda i: pk[i].dtype != np.int16)  # (stable: int16 packets first)
-        a_ids = np.ascontiguousarray(a_ids[order]) if n else a_ids
-        pk = [pk[i].view(np.uint8) for i in order]
-        offs = np.zeros(n + 1, np.int64)
-        np.cumsum([p.size for p in pk], out=offs[1:])
-        counts = np.zeros(n + 1, np.int64)  # the packets' samples, for ww_stream_feed_rows
-        np.cumsum([p.size // (2 if self.sample_formats[int(s)] == "pcm16" else 1) for s, p in zip(a_ids, pk)], out=counts[1:])
-        data = np.concatenate(pk) if n and offs[n] else np.zeros(2, np.uint8)
-        row_offs = np.zeros(n + 1, np.int64)
-        h, K = self.engine.ctx.handle, self.n_members
-        rows_fn, feed_fn = ((self._lib.ww_stream_feed_rows_all, self._lib.ww_stream_feed_bytes_all) if every
-                            else (self._lib.ww_stream_feed_rows, self._lib.ww_stream_feed_bytes))
-        _lib.raise_for(rows_fn(self._h, _lib.ptr(a_ids), n, _lib.ptr(counts), _lib.ptr(row_offs)), h)
-        rows = int(row_offs[n])
-        post = np.empty((max(rows, 1), K) if every else max(rows, 1), np.float32)
-        mel = np.empty((max(rows, 1), self.engine.n_mel), np.float32) if want_mel else None
-        _lib.raise_for(feed_fn(self._h, _lib.ptr(a_ids), n, _lib.ptr(data), _lib.ptr(offs), rows, _lib.ptr(row_offs), _lib.ptr(post),
-                               _lib.ptr(mel) if want_mel else None), h)
-        back = np.argsort(order) if n else []
-        posts = [post[row_offs[j]:row_offs[j + 1]].copy() for j in back]
-        mels = [mel[row_offs[j]:row_offs[j + 1]].copy() for j in back] if want_mel else None
-        return posts, mels
+        return self._feed(ids, packets, want_mel, True)
 
     def step_trigger_all(self, frames: np.ndarray, p_is_speech, p_is_active, p_thresholds, p_state) -> None:
         """The wake-word stage of an every-member bank as ONE library call (``ww_stream_step_trigger_all``); every argument but

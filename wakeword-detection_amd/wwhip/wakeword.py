@@ -93,6 +93,38 @@ class WakewordTrigger:
         self.reset()
 
 
+def _flag_addresses(stage, contexts):
+    """The addresses of the ``is_speech`` and ``is_active`` arrays a banked stage's tick reads and writes: a ``ContextBank``'s own
+    (taken once per bank: its arrays are the state), or the stage's scratch arrays filled from a sequence of S ``SpeechContext``
+    objects (the slow form)."""
+    from . import _lib
+    if hasattr(contexts, "emit"):
+        b = stage._bound
+        if b is None or b[0] is not contexts:
+            if len(contexts) != stage.S:
+                raise ValueError("one context per stream")
+            b = stage._bound = (contexts, _lib.addr(contexts.is_speech), _lib.addr(contexts.is_active))
+        return b[1], b[2]
+    if len(contexts) != stage.S:
+        raise ValueError("one context per stream")
+    sc = stage._scratch
+    if sc is None:
+        speech, active = np.zeros(stage.S, np.uint8), np.zeros(stage.S, np.uint8)
+        sc = stage._scratch = (speech, active, _lib.addr(speech), _lib.addr(active))
+    sc[0][:] = [c.is_speech for c in contexts]
+    sc[1][:] = [c.is_active for c in contexts]
+    return sc[2], sc[3]
+
+
+def _activate(contexts, ids) -> None:
+    """The streams that fired: one ``activate`` event on a ``ContextBank`` (the tick has set its flags), else each context's flag."""
+    if hasattr(contexts, "emit"):
+        contexts.emit("activate", ids)
+    else:
+        for s in ids:
+            contexts[int(s)].is_active = True  # (the setter raises the activate event)
+
+
 class WakewordBank:
     """S streams in lock step: the batched form of :class:`WakewordTrigger` - one kernel launch per 20 ms tick for all streams,
     and the trigger's host logic (VAD-edge reset, running maximum, threshold, activation; tflite.py:134-146,232-239) as one pass
@@ -138,38 +170,14 @@ class WakewordBank:
         return self._n
 
     def step(self, contexts, frames: np.ndarray) -> np.ndarray:
-        from . import _lib
-        if hasattr(contexts, "emit"):  # a ContextBank: its arrays are the state
-            b = self._bound
-            if b is None or b[0] is not contexts:
-                if len(contexts) != self.S:
-                    raise ValueError("one context per stream")
-                b = self._bound = (contexts, _lib.addr(contexts.is_speech), _lib.addr(contexts.is_active))
-            self._bank.step_trigger(frames, b[1], b[2], self.threshold, self._p_state)
-            nf = self._counts[0]
-            if nf:
-                ids = self._fired[:nf].copy()
-                if self._on_wake is not None:
-                    self._on_wake(ids)
-                contexts.emit("activate", ids)
-            return self._post.copy()
-        # a sequence of SpeechContext objects
-        if len(contexts) != self.S:
-            raise ValueError("one context per stream")
-        sc = self._scratch
-        if sc is None:
-            speech, active = np.zeros(self.S, np.uint8), np.zeros(self.S, np.uint8)
-            sc = self._scratch = (speech, active, _lib.addr(speech), _lib.addr(active))
-        sc[0][:] = [c.is_speech for c in contexts]
-        sc[1][:] = [c.is_active for c in contexts]
-        self._bank.step_trigger(frames, sc[2], sc[3], self.threshold, self._p_state)
+        p_speech, p_active = _flag_addresses(self, contexts)
+        self._bank.step_trigger(frames, p_speech, p_active, self.threshold, self._p_state)
         nf = self._counts[0]
         if nf:
             ids = self._fired[:nf].copy()
             if self._on_wake is not None:
                 self._on_wake(ids)
-            for s in ids:
-                contexts[int(s)].is_active = True  # (the setter raises the activate event)
+            _activate(contexts, ids)
         return self._post.copy()
 
     __call__ = step  # the stage form: bank(contexts, frames)
@@ -281,30 +289,11 @@ class WakewordSetBank:
         return ids
 
     def step(self, contexts, frames: np.ndarray) -> np.ndarray:
-        from . import _lib
-        if len(contexts) != self.S:
-            raise ValueError("one context per stream")
-        if hasattr(contexts, "emit"):  # a ContextBank: its arrays are the state
-            b = self._bound
-            if b is None or b[0] is not contexts:
-                b = self._bound = (contexts, _lib.addr(contexts.is_speech), _lib.addr(contexts.is_active))
-            self._bank.step_trigger_all(frames, b[1], b[2], self._p_thresholds, self._p_state)
-            ids = self._fires()
-            if ids is not None:
-                contexts.emit("activate", ids)
-            return self._post.copy()
-        # a sequence of SpeechContext objects
-        sc = self._scratch
-        if sc is None:
-            speech, active = np.zeros(self.S, np.uint8), np.zeros(self.S, np.uint8)
-            sc = self._scratch = (speech, active, _lib.addr(speech), _lib.addr(active))
-        sc[0][:] = [c.is_speech for c in contexts]
-        sc[1][:] = [c.is_active for c in contexts]
-        self._bank.step_trigger_all(frames, sc[2], sc[3], self._p_thresholds, self._p_state)
+        p_speech, p_active = _flag_addresses(self, contexts)
+        self._bank.step_trigger_all(frames, p_speech, p_active, self._p_thresholds, self._p_state)
         ids = self._fires()
         if ids is not None:
-            for s in ids:
-                contexts[int(s)].is_active = True  # (the setter raises the activate event)
+            _activate(contexts, ids)
         return self._post.copy()
 
     __call__ = step  # the stage form: bank(contexts, frames)
