@@ -253,7 +253,7 @@ static void check_wave() {
     }
     const int64_t total_rows = offs.back() + rnd(0, 9);
     wave_seq_plan pl;
-    wave_seq_make_plan(rf, n_out, seg_opt, total_rows, offs.data(), n_seq, it % 3 == 0, it % 4 == 0, pl);
+    wave_seq_make_plan(rf, n_out, seg_opt, total_rows, offs.data(), n_seq, 1, WAVE_SEQ_IDS_NONE, it % 3 == 0, it % 4 == 0, pl);
     size_t at = 0;
     int64_t max_len = 0;
     for (int s = 0; s < n_seq; ++s) {

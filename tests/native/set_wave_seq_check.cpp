@@ -1,5 +1,5 @@
 // set_wave_seq_check - the host half of the Wavenet's sequence form over a model set on the CPU, under Address + UB sanitizer
-// (tests/test_set_sequence_host.py): csrc/launch_plan.h's wave_seq_set_make_plan over random offset lists and slot lists, and
+// (tests/test_set_sequence_host.py): csrc/launch_plan.h's wave_seq_make_plan in its three id forms over random offset lists and slot lists, and
 // csrc/model_set.h's check of the ids a call brings.  Prints "ok <checks>" and exits 0, or the failed condition and exits 1.
 //
 // A set's launch is segments x planes workgroups: workgroup (x, y) keeps rows [row0 + skip, row0 + n) of segment x and writes them
@@ -39,13 +39,14 @@ static void check_case(int it) {
   const int64_t total_rows = offs.back() + rnd(0, 9);
   const bool need_z = it % 3 == 0, need_pool = it % 4 == 0;
   wave_seq_plan one;
-  wave_seq_make_plan(rf, n_out, seg_opt, total_rows, offs.data(), n_seq, need_z, need_pool, one);
+  wave_seq_make_plan(rf, n_out, seg_opt, total_rows, offs.data(), n_seq, 1, WAVE_SEQ_IDS_NONE, need_z, need_pool, one);
+  CHECK(one.b_ids == 0 && one.b_aux == 0 && one.seg_seq.empty());  // (no ids: the single model's plan)
 
   for (int form = 0; form < 2; ++form) {
     const bool by_seq = form == 1;
     const int planes = by_seq ? 1 : pick<int>({1, 1, 2, 3, 64, 65, 1024});  // (a slot list of that many ids, duplicates or not)
     wave_seq_plan pl;
-    wave_seq_set_make_plan(rf, n_out, seg_opt, total_rows, offs.data(), n_seq, planes, by_seq, need_z, need_pool, pl);
+    wave_seq_make_plan(rf, n_out, seg_opt, total_rows, offs.data(), n_seq, planes, by_seq ? WAVE_SEQ_IDS_BY_SEQ : WAVE_SEQ_IDS_BY_PLANE, need_z, need_pool, pl);
     // the cuts are the single model's, segment for segment: a member is weights, not geometry
     CHECK(pl.segs.size() == one.segs.size() && pl.max_len == one.max_len);
     for (size_t i = 0; i < pl.segs.size(); ++i) CHECK(same_seg(pl.segs[i], one.segs[i]));

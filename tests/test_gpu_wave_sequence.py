@@ -320,3 +320,175 @@ def test_refusals_and_degenerate_sizes(engines, assets):
     assert lib.ww_stream_create(eng.ctx.handle, eng.handle, 4, C.byref(fp), _lib.STREAM_CAUSAL | _lib.STREAM_FULL_RECOMPUTE,
                                 C.byref(h)) == _lib.WW_EINVAL
     assert not h.value
+
+
+# ------------------------------------------------- one path for a model and a model set: outputs asked for, rows outside, bad calls
+EDGE_LENGTHS = [0, 1, 180, 181, 193, 400]   # around the receptive field (181) and a chunk (192); 400 rows at 256: two segments
+EDGE_FRONT, EDGE_BEHIND = 7, 5              # rows of the buffers in front of the first sequence and behind the last
+EDGE_SEGMENT = 256                          # test_the_cuts_do_not_show's: the 400-row sequence is cut
+EDGE_EMPTY = EDGE_LENGTHS.index(0)
+SENTINEL = -7.0
+
+
+@pytest.fixture(scope="module")
+def edge(engines):
+    """The small batch of the tests below, per model: its sequences, all four outputs of ONE ``sequence_forward`` call (computed
+    once, never written to) and a one-member ``ModelSet`` on the same engine, both cutting at EDGE_SEGMENT."""
+    from wwhip.engine import ModelSet
+    rng = np.random.default_rng(20261020)
+    seqs = [_random_mel(rng, n) if n else np.zeros((0, 40), np.float32) for n in EDGE_LENGTHS]
+    out, sets = {}, []
+    for name, eng in engines.items():
+        ms = ModelSet([eng])
+        ms.set_option("wave_seq_segment", EDGE_SEGMENT)
+        sets.append(ms)
+        with eng.options(wave_seq_segment=EDGE_SEGMENT):
+            ref = eng.sequence_forward(seqs, want=ALL)
+        for k in ALL:
+            for a in ref[k]:
+                a.setflags(write=False)
+        out[name] = (seqs, ref, ms)
+    yield out
+    for ms in sets:
+        ms.close()
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_every_subset_of_the_outputs_carries_the_same_bits(engines, edge, model):
+    """Every non-empty subset of the four outputs, through ``Engine.sequence_forward`` and through a one-member set's
+    ``sequence_forward_all``: what comes back is what was asked for, and each array equals the all-four call's, bit for bit -
+    whether the logits and the pooling buffers are the caller's or the plan's scratch."""
+    import itertools
+    eng = engines[model]
+    seqs, ref, ms = edge[model]
+    for r in range(1, len(ALL) + 1):
+        for want in itertools.combinations(ALL, r):
+            with eng.options(wave_seq_segment=EDGE_SEGMENT):
+                one = eng.sequence_forward(seqs, want=want)
+            every = ms.sequence_forward_all(seqs, want=want)
+            assert tuple(one) == want and tuple(every) == want
+            for k in want:
+                assert len(one[k]) == len(every[k][0]) == len(seqs) and len(every[k]) == 1
+                for i in range(len(seqs)):
+                    if k == "post" and i == EDGE_EMPTY:
+                        assert np.isnan(one[k][i]).all() and np.isnan(every[k][0][i]).all()
+                        continue
+                    np.testing.assert_array_equal(one[k][i], ref[k][i], err_msg=f"model, want {want}: {k} of sequence {i}")
+                    np.testing.assert_array_equal(every[k][0][i], ref[k][i], err_msg=f"set, want {want}: {k} of sequence {i}")
+
+
+def _edge_buffers(seqs, n_out):
+    """The batch in one buffer with EDGE_FRONT rows of NaN in front and EDGE_BEHIND behind, its offsets, and outputs full of SENTINEL."""
+    mel = np.concatenate([np.full((EDGE_FRONT, 40), np.nan, np.float32)] + seqs + [np.full((EDGE_BEHIND, 40), np.nan, np.float32)])
+    offs = (EDGE_FRONT + np.concatenate([[0], np.cumsum(EDGE_LENGTHS)])).astype(np.int64)
+    total = len(mel)
+    shape = {"enc": (total, 32), "logits": (total, n_out), "post_frames": (total, n_out), "post": (len(seqs), n_out)}
+    return mel, offs, {k: np.full(shape[k], SENTINEL, np.float32) for k in ALL}
+
+
+def _check_edge(got, offs, ref, what):
+    """Rows of sequence i are the reference's; every other row, and the empty sequence's ``post``, is still SENTINEL."""
+    for i in range(len(EDGE_LENGTHS)):
+        a, b = int(offs[i]), int(offs[i + 1])
+        for k in ("enc", "logits", "post_frames"):
+            np.testing.assert_array_equal(got[k][a:b], ref[k][i], err_msg=f"{what}: {k} of sequence {i}")
+        if i != EDGE_EMPTY:
+            np.testing.assert_array_equal(got["post"][i], ref["post"][i], err_msg=f"{what}: post of sequence {i}")
+    for k in ("enc", "logits", "post_frames"):
+        assert (got[k][:int(offs[0])] == SENTINEL).all() and (got[k][int(offs[-1]):] == SENTINEL).all(), (what, k)
+        assert len(got[k][:int(offs[0])]) == EDGE_FRONT and len(got[k][int(offs[-1]):]) == EDGE_BEHIND
+    assert (got["post"][EDGE_EMPTY] == SENTINEL).all(), what
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_rows_outside_the_sequences_are_neither_read_nor_written(engines, edge, model):
+    """``ww_wave_sequence`` and ``ww_wave_sequence_dev`` on buffers with rows in front of the first sequence and behind the last:
+    those mel rows hold NaN and the results are the unpoisoned run's, bit for bit; those output rows, and the empty sequence's
+    ``post``, keep the bytes they had."""
+    import torch
+    from wwhip import _lib
+    lib = _lib.load()
+    eng = engines[model]
+    seqs, ref, _ = edge[model]
+    mel, offs, host = _edge_buffers(seqs, eng.n_out)
+    with eng.options(wave_seq_segment=EDGE_SEGMENT):
+        rc = lib.ww_wave_sequence(eng.ctx.handle, eng.handle, _lib.ptr(mel), len(mel), _lib.ptr(offs), len(seqs), eng.window,
+                                  *[_lib.ptr(host[k]) for k in ALL])
+        assert rc == _lib.WW_OK, lib.ww_last_error(eng.ctx.handle)
+        _check_edge(host, offs, ref, "host")
+        d_mel = torch.from_numpy(mel).cuda()
+        dev = {k: torch.full(v.shape, SENTINEL, dtype=torch.float32, device="cuda") for k, v in host.items()}
+        torch.cuda.synchronize()
+        eng.wave_sequence_dev(d_mel.data_ptr(), len(mel), offs, None, *[dev[k].data_ptr() for k in ALL])
+        eng.ctx.synchronize()
+        _check_edge({k: v.cpu().numpy() for k, v in dev.items()}, offs, ref, "dev")
+
+
+def test_one_table_of_bad_calls_for_the_six_entry_points(engines, edge, assets):
+    """Negative ``n_seq``, pool and rows, descending offsets, offsets past ``total_rows``, NULL mel with a non-empty sequence, a
+    CRNN model / set and - single model - a split-bf16 model: WW_EINVAL from each of the six entry points, with outputs full of
+    SENTINEL untouched.  ``n_seq == 0``, only empty sequences and no output pointer: WW_OK, outputs untouched."""
+    import torch
+    from wwhip import _lib
+    from wwhip.engine import Engine, ModelSet
+    lib = _lib.load()
+    eng = engines["Wavenet"]
+    seqs, _, ms = edge["Wavenet"]
+    ctx = eng.ctx.handle
+    mel, offs, host = _edge_buffers(seqs, eng.n_out)
+    total, n_seq = len(mel), len(seqs)
+    d_mel = torch.from_numpy(mel).cuda()
+    dev = {k: torch.full(v.shape, SENTINEL, dtype=torch.float32, device="cuda") for k, v in host.items()}
+    torch.cuda.synchronize()
+    crnn = Engine(os.path.join(assets, "CRNN_nosilence"), ctx=eng.ctx)
+    crnn_set = ModelSet([crnn])
+    bf16 = Engine(os.path.join(assets, "Wavenet"), precision="bf16x3", ctx=eng.ctx)
+    member0 = np.zeros(1, np.int32)
+    route0 = np.zeros(n_seq, np.int32)
+    OMIT = object()
+
+    def entry(name):
+        """-> call(**changes) for the entry point, and the models it refuses"""
+        on_dev = name.endswith("_dev")
+        single = not name.startswith("ww_set_")
+        good = eng.handle if single else ms.handle
+        the_mel = C.c_void_p(d_mel.data_ptr()) if on_dev else _lib.ptr(mel)
+        outs = [C.c_void_p(dev[k].data_ptr()) for k in ALL] if on_dev else [_lib.ptr(host[k]) for k in ALL]
+
+        def call(model=good, m=OMIT, rows=total, ro=offs, n=n_seq, pool=50, o=OMIT):
+            ro = np.ascontiguousarray(ro, np.int64)
+            args = [ctx, model, the_mel if m is OMIT else m, rows, _lib.ptr(ro), n]
+            if single:
+                args += [pool]
+            elif "_all" in name:
+                args += [pool, _lib.ptr(member0), 1]
+            else:
+                args += [_lib.ptr(route0), pool]
+            rc = getattr(lib, name)(*args, *(outs if o is OMIT else [None] * 4))
+            eng.ctx.synchronize()
+            return rc
+        return call, ([crnn.handle, bf16.handle] if single else [crnn_set.handle])
+
+    def untouched():
+        return all((v == SENTINEL).all() for v in host.values()) and all(bool((v == SENTINEL).all()) for v in dev.values())
+
+    down = offs.copy()
+    down[4] = down[3] - 1
+    empty = np.full(n_seq + 1, 9, np.int64)
+    try:
+        for name in ("ww_wave_sequence", "ww_wave_sequence_dev", "ww_set_wave_sequence", "ww_set_wave_sequence_dev",
+                     "ww_set_wave_sequence_all", "ww_set_wave_sequence_all_dev"):
+            call, refused_models = entry(name)
+            bad = [dict(n=-1), dict(pool=-1), dict(rows=-1), dict(ro=down), dict(rows=total - EDGE_BEHIND - 1), dict(m=None)]
+            bad += [dict(model=h) for h in refused_models]
+            for kw in bad:
+                assert call(**kw) == _lib.WW_EINVAL, (name, kw)
+                assert len(lib.ww_last_error(ctx)) > 8, (name, kw)
+                assert untouched(), (name, kw)
+            for kw in (dict(n=0), dict(ro=empty), dict(o=None)):
+                assert call(**kw) == _lib.WW_OK, (name, kw, lib.ww_last_error(ctx))
+                assert untouched(), (name, kw)
+    finally:
+        crnn_set.close()
+        crnn.close()
+        bf16.close()

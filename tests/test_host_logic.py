@@ -1123,16 +1123,16 @@ def test_launch_plan_is_host_only_and_its_structs_and_constants_have_one_definit
 
 def test_dev_entry_points_do_not_synchronise_for_their_tables():
     """include/wwhip.h: the _dev entry points enqueue on the context's stream and return without synchronising.  The two that
-    build tables from host arrays - and wave_seq_run, which both forms of ww_wave_sequence share - hold no hipStreamSynchronize;
-    the slot protocol is spelled out once, in ww_tables::send."""
+    build tables from host arrays - and wave_seq_dev and wave_seq_run, through which ww_wave_sequence_dev goes and which every
+    form of the sequence call shares - hold no hipStreamSynchronize; the slot protocol is spelled out once, in ww_tables::send."""
     import re
     text = {f: open(os.path.join(_CSRC, f)).read() for f in sorted(os.listdir(_CSRC)) if f.endswith(".hip")}
     api = text["api.hip"]
-    for name in ("ww_forward_segments_dev", "ww_wave_sequence_dev", "wave_seq_run"):
+    for name in ("ww_forward_segments_dev", "ww_wave_sequence_dev", "wave_seq_dev", "wave_seq_run"):
         m, = re.finditer(r"^[A-Za-z_][A-Za-z0-9_ \*]*\b" + name + r"\(", api, flags=re.M)
         open_brace = api.index("{", m.end())
         body = api[open_brace:api.index("\n}\n", open_brace)]
-        assert "tb.send(" in body or "wave_seq_run(" in body or "ww_k_crnn_segments_forward(" in body, name
+        assert "tb.send(" in body or "wave_seq_run(" in body or "wave_seq_dev(" in body or "ww_k_crnn_segments_forward(" in body, name
         assert "hipStreamSynchronize" not in body and "hipDeviceSynchronize" not in body and "hipEventSynchronize" not in body, name
     users = {f: t.count("desc_busy") for f, t in text.items()}
     assert users.pop("api.hip") > 0 and not any(users.values()), users

@@ -21,11 +21,12 @@ def _no_sanitizer_runtime(output):
 
 
 def test_set_planner_under_sanitizers(tmp_path):
-    """csrc/launch_plan.h's wave_seq_set_make_plan over 600 random offset lists (empty sequences, lengths around the chunk and
+    """csrc/launch_plan.h's wave_seq_make_plan over 600 random offset lists (empty sequences, lengths around the chunk and
     the receptive field, rows in front of and behind the sequences), explicit and library-chosen segment lengths, slot counts 1,
-    2, 3, 64, 65, 1024 and the by-sequence form: the cuts are wave_seq_make_plan's segment for segment; every (sequence row,
-    plane) has exactly one owner segment and no other row has one; the warm-up is min(s0, rf - 1); seg_seq names each segment's
-    sequence; the table sizes are what the plan reserved; one plane reproduces the single model's plan.  csrc/model_set.h's
+    2, 3, 64, 65, 1024 with an id per plane, and the by-sequence form: the cuts are those of the plan without ids (the single
+    model's) segment for segment; every (sequence row, plane) has exactly one owner segment and no other row has one; the warm-up
+    is min(s0, rf - 1); seg_seq names each segment's sequence; the table sizes are what the plan reserved; one plane reproduces
+    the single model's plan, which reserves neither ids nor seg_seq.  csrc/model_set.h's
     ww_set_check_ids on ``seq_model`` and ``members``.  (tests/native/set_wave_seq_check.cpp; a child process, nothing is loaded
     into this interpreter.)"""
     cxx = "/opt/rocm/lib/llvm/bin/clang++"
@@ -124,21 +125,22 @@ def _body(api, name):
 
 
 def test_the_dev_entry_points_synchronise_nothing():
-    """The bodies of ww_set_wave_sequence_dev and ww_set_wave_sequence_all_dev - and of every function between them and
-    wave_seq_run, which they share with the single model's path - hold no hipStreamSynchronize, hipDeviceSynchronize or
-    hipEventSynchronize; the tables go through wave_seq_run's one tb.send."""
+    """The bodies of ww_wave_sequence_dev, ww_set_wave_sequence_dev and ww_set_wave_sequence_all_dev - and of every function
+    between them and wave_seq_run, the one path of a model and a model set - hold no hipStreamSynchronize, hipDeviceSynchronize
+    or hipEventSynchronize; the tables go through wave_seq_run's one tb.send."""
     api = open(os.path.join(_CSRC, "api.hip")).read()
-    for name in ("ww_set_wave_sequence_dev", "ww_set_wave_sequence_all_dev"):
+    for name in ("ww_wave_sequence_dev", "ww_set_wave_sequence_dev", "ww_set_wave_sequence_all_dev"):
         body = _body(api, name)
-        assert "set_wave_seq_dev(" in body, name
+        assert "wave_seq_dev(" in body, name
         for sync in ("hipStreamSynchronize", "hipDeviceSynchronize", "hipEventSynchronize"):
             assert sync not in body, (name, sync)
-    chain = {"set_wave_seq_dev": "set_wave_seq_run(", "set_wave_seq_run": "wave_seq_run(", "set_wave_seq_check": "wave_seq_validate(",
+    chain = {"wave_seq_dev": "wave_seq_run(", "wave_seq_check": "wave_seq_validate(", "wave_seq_plan_of": "wave_seq_make_plan(",
              "wave_seq_run": "tb.send("}
     for name, callee in chain.items():
         body = _body(api, name)
         assert callee in body, (name, callee)
         for sync in ("hipStreamSynchronize", "hipDeviceSynchronize", "hipEventSynchronize"):
             assert sync not in body, (name, sync)
+    assert "wave_seq_check(" in _body(api, "wave_seq_dev") and "wave_seq_plan_of(" in _body(api, "wave_seq_dev")
     # one definition each of what the set shares with the single model
     assert len(re.findall(r"^static int wave_seq_run\(", api, re.M)) == 1 and len(re.findall(r"^static int wave_seq_validate\(", api, re.M)) == 1

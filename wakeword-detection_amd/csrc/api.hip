@@ -962,11 +962,26 @@ int ww_set_slide_forward(ww_ctx *ctx, const ww_model_set *set, const float *mel,
   WW_GUARD_END(ctx)
 }
 
-// ---- the Wavenet's sequence form (wavenet.hip: wavenet_seq_kernel) -----------------------------------------------------------
-static int wave_seq_validate(ww_ctx *ctx, const ww_model *m, int64_t total_rows, const int64_t *row_offs, int32_t n_seq, int32_t pool_rows) {
-  if (m->kind != WW_KIND_WAVENET)
-    return ww_fail(ctx, WW_EINVAL, "ww_wave_sequence: Wavenet models only (a CRNN's bidirectional GRUs have no causal reading)");
-  if (m->precision != WW_PRECISION_FP32) return ww_fail(ctx, WW_EINVAL, "ww_wave_sequence: fp32 only; this model is in split-bf16 mode");
+}  // extern "C"
+
+// ---- the Wavenet's sequence form (wavenet.hip: wavenet_seq_kernel), for a model and for a model set --------------------------------
+// One shape for the six entry points.  set == NULL: a single model - one plane, no ids.  Otherwise m is the set's view and, by_seq:
+// ONE plane, sequence s by member ids[s] (n_ids = n_seq; ids == NULL: member 0); else plane k by member ids[k] (ids == NULL: every
+// member in order, n_ids only checked for its sign).
+struct wave_seq_request {
+  const ww_model *m;
+  const ww_model_set *set;
+  const float *mel;  // host or device, as the entry point's outputs
+  int64_t total_rows;
+  const int64_t *row_offs;
+  int32_t n_seq, pool_rows;
+  const int32_t *ids;
+  int32_t n_ids;
+  bool by_seq;
+  float *enc, *logits, *pf, *post;
+};
+
+static int wave_seq_validate(ww_ctx *ctx, int64_t total_rows, const int64_t *row_offs, int32_t n_seq, int32_t pool_rows) {
   if (n_seq < 0) return ww_fail(ctx, WW_EINVAL, "negative sequence count");
   if (pool_rows < 0) return ww_fail(ctx, WW_EINVAL, "negative pool length");
   if (total_rows < 0) return ww_fail(ctx, WW_EINVAL, "negative row count");
@@ -978,128 +993,19 @@ static int wave_seq_validate(ww_ctx *ctx, const ww_model *m, int64_t total_rows,
   return WW_OK;
 }
 
-// A model set's side of a call (m is then the set's view): `planes` output planes of total_rows rows each, plane k by member ids[k]
-// - or by_seq: ONE plane, sequence s by member ids[s].  ids: a HOST array of checked ids, planes (by_seq: n_seq) of them.
-struct wave_seq_set_call {
-  long long stride;
-  const int32_t *ids;
-  int planes;
-  bool by_seq;
-};
-
-static int wave_seq_run(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t total_rows, const int64_t *row_offs, int n_seq,
-                        int pool_rows, float *d_enc, float *d_logits, float *d_pf, float *d_post, const wave_seq_plan &pl, ww_bump &bump,
-                        const wave_seq_set_call *sc = nullptr) {
-  if (pl.segs.empty()) return WW_OK;
-  if (pl.segs.size() > 0x7fffffffu) return ww_fail(ctx, WW_EINVAL, "too many segments in one call");
-  const int NO = m->info.n_out, planes = sc ? sc->planes : 1;
-  ww_tables tb;
-  const size_t o_segs = tb.add(pl.segs), o_offs = tb.add(row_offs, (size_t)n_seq + 1);
-  const size_t o_ids = sc ? tb.add(sc->ids, sc->by_seq ? (size_t)n_seq : (size_t)planes) : 0, o_aux = sc && sc->by_seq ? tb.add(pl.seg_seq) : 0;
-  if (tb.bytes() != pl.b_segs + pl.b_offs + pl.b_ids + pl.b_aux) return ww_fail(ctx, WW_EINTERNAL, "wave_seq_run: the tables are not the size the plan reserved");
-  char *d_tab = bump.take<char>(tb.bytes());
-  const wv_seg *d_segs = (const wv_seg *)(d_tab + o_segs);
-  const int64_t *d_offs = (const int64_t *)(d_tab + o_offs);
-  const size_t plane = (size_t)total_rows * NO;
-  float *d_z = d_logits;
-  if (!d_z && (d_pf || d_post)) d_z = bump.take<float>(planes * plane);
-  float *d_a = d_pf ? bump.take<float>(planes * plane) : nullptr, *d_b = d_pf ? bump.take<float>(planes * plane) : nullptr;
-  if (int rc = tb.send(ctx, d_tab)) return rc;
-  ww_set_ref ref;
-  if (sc) {
-    ref.ids = (const int32_t *)(d_tab + o_ids);
-    ref.aux = sc->by_seq ? (const int32_t *)(d_tab + o_aux) : nullptr;
-    ref.stride = sc->stride;
-  }
-  int rc = ww_k_wave_sequence(ctx, m, d_mel, d_segs, (int)pl.segs.size(), d_enc, d_z, sc ? &ref : nullptr, planes, total_rows);
-  if (rc) return rc;
-  if (d_pf || d_post)
-    rc = ww_k_wave_pool(ctx, d_z, row_offs[n_seq] - row_offs[0], row_offs[n_seq], NO, d_offs, n_seq, pool_rows, pl.max_len, d_a, d_b, d_pf, d_post, planes, total_rows);
-  return rc;
-}
-
-int ww_wave_sequence_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
-                         int32_t pool_rows, float *d_enc, float *d_logits, float *d_post_frames, float *d_post) {
-  WW_GUARD_BEGIN
-  if (!ctx || !m) return ww_fail(ctx, WW_EINVAL, "NULL argument");
-  if (int rc = wave_seq_validate(ctx, m, total_rows, row_offs, n_seq, pool_rows)) return rc;
-  if (n_seq == 0 || row_offs[n_seq] == row_offs[0]) return WW_OK;
-  if (!d_mel) return ww_fail(ctx, WW_EINVAL, "NULL mel buffer");
-  if (!d_enc && !d_logits && !d_post_frames && !d_post) return WW_OK;
-  WW_ON_DEVICE(ctx, dev);
-  wave_seq_plan pl;
-  wave_seq_make_plan(ww_wave_receptive_field(m), m->info.n_out, m->opt_wave_seq_segment, total_rows, row_offs, n_seq,
-                     !d_logits && (d_post_frames || d_post), d_post_frames != nullptr, pl);
-  if (int rc = ww_ensure(ctx, ctx->dev, pl.bytes() + 1024, false)) return rc;
-  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
-  return wave_seq_run(ctx, m, d_mel, total_rows, row_offs, n_seq, pool_rows, d_enc, d_logits, d_post_frames, d_post, pl, bump);
-  WW_GUARD_END(ctx)
-}
-
-int ww_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
-                     int32_t pool_rows, float *enc, float *logits, float *post_frames, float *post) {
-  WW_GUARD_BEGIN
-  if (!ctx || !m) return ww_fail(ctx, WW_EINVAL, "NULL argument");
-  if (int rc = wave_seq_validate(ctx, m, total_rows, row_offs, n_seq, pool_rows)) return rc;
-  if (n_seq == 0 || row_offs[n_seq] == row_offs[0]) return WW_OK;
-  if (!mel) return ww_fail(ctx, WW_EINVAL, "NULL mel buffer");
-  if (!enc && !logits && !post_frames && !post) return WW_OK;
-  WW_ON_DEVICE(ctx, dev);
-  const int F = m->info.n_mel, NO = m->info.n_out, S = m->info.enc_width;
-  wave_seq_plan pl;
-  wave_seq_make_plan(ww_wave_receptive_field(m), m->info.n_out, m->opt_wave_seq_segment, total_rows, row_offs, n_seq,
-                     !logits && (post_frames || post), post_frames != nullptr, pl);
-  const size_t b_mel = ww_bump::need((size_t)total_rows * F, 4), b_enc = enc ? ww_bump::need((size_t)total_rows * S, 4) : 0;
-  const size_t b_rows = ww_bump::need((size_t)total_rows * NO, 4), b_post = ww_bump::need((size_t)n_seq * NO, 4);
-  if (int rc = ww_ensure(ctx, ctx->dev, b_mel + b_enc + 2 * b_rows + b_post + pl.bytes() + 1024, false)) return rc;
-  ww_bump bump(ctx->dev.ptr, ctx->dev.cap);
-  float *d_mel = bump.take<float>((size_t)total_rows * F);
-  float *d_enc = enc ? bump.take<float>((size_t)total_rows * S) : nullptr;
-  float *d_z = logits ? bump.take<float>((size_t)total_rows * NO) : nullptr;
-  float *d_pf = post_frames ? bump.take<float>((size_t)total_rows * NO) : nullptr;
-  float *d_post = post ? bump.take<float>((size_t)n_seq * NO) : nullptr;
-  // rows of the mel buffer outside every sequence are never read; rows of the outputs outside every sequence are never written:
-  // the caller's bytes there stay as they are
-  const int64_t r0 = row_offs[0], r1 = row_offs[n_seq];
-  WW_HIP(ctx, hipMemcpyAsync(d_mel + r0 * F, mel + r0 * F, (size_t)(r1 - r0) * F * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (d_post) WW_HIP(ctx, hipMemcpyAsync(d_post, post, (size_t)n_seq * NO * 4, hipMemcpyHostToDevice, ctx->stream));  // (empty sequences keep theirs)
-  if (int rc = wave_seq_run(ctx, m, d_mel, total_rows, row_offs, n_seq, pool_rows, d_enc, d_z, d_pf, d_post, pl, bump)) return rc;
-  if (enc) WW_HIP(ctx, hipMemcpyAsync(enc + r0 * S, d_enc + r0 * S, (size_t)(r1 - r0) * S * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (logits) WW_HIP(ctx, hipMemcpyAsync(logits + r0 * NO, d_z + r0 * NO, (size_t)(r1 - r0) * NO * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (post_frames) WW_HIP(ctx, hipMemcpyAsync(post_frames + r0 * NO, d_pf + r0 * NO, (size_t)(r1 - r0) * NO * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (post) WW_HIP(ctx, hipMemcpyAsync(post, d_post, (size_t)n_seq * NO * 4, hipMemcpyDeviceToHost, ctx->stream));
-  WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return WW_OK;
-  WW_GUARD_END(ctx)
-}
-
-}  // extern "C"
-
-// ---- the sequence form over a model set (ww_set_wave_sequence*): validation, cuts, pooling and tables are the single model's
-//      (wave_seq_validate, wave_seq_run); a call adds its member ids and its planes ---------------------------------------------------
-// One shape for the four entry points.  by_seq: ONE plane, sequence s by member ids[s] (n_ids = n_seq; ids == NULL: member 0).
-// Otherwise plane k by member ids[k] (ids == NULL: every member in order, n_ids only checked for its sign).
-struct set_seq_request {
-  const float *mel;  // host or device, as the entry point's outputs
-  int64_t total_rows;
-  const int64_t *row_offs;
-  int32_t n_seq, pool_rows;
-  const int32_t *ids;
-  int32_t n_ids;
-  bool by_seq;
-  float *enc, *logits, *pf, *post;
-};
-
-// Everything the four refuse, before anything is enqueued or written.  *slots: the call's planes (by_seq: 1); 0 with WW_OK: a no-op
-static int set_wave_seq_check(ww_ctx *ctx, const ww_model_set *set, const set_seq_request &c, const char *what, int32_t *slots) {
+// Everything the six refuse, before anything is enqueued or written.  *slots: the call's planes (no set, by_seq: 1); 0 with WW_OK: a no-op
+static int wave_seq_check(ww_ctx *ctx, const wave_seq_request &c, const char *what, int32_t *slots) {
   *slots = 0;
-  if (!ctx || !set) return ww_fail(ctx, WW_EINVAL, "NULL argument");
-  if (set->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "the model set belongs to another context");
-  if (int rc = wave_seq_validate(ctx, &set->view, c.total_rows, c.row_offs, c.n_seq, c.pool_rows)) return rc;
-  if (c.n_ids < 0) return ww_fail(ctx, WW_EINVAL, "negative member count");
-  char why[160];
-  if (int rc = ww_set_check_ids(c.ids, c.n_ids, set->n, c.by_seq ? "seq_model" : "members", why, sizeof why)) return ww_fail(ctx, rc, "%s: %s", what, why);
-  const int32_t n = c.by_seq ? 1 : c.ids ? c.n_ids : set->n;
+  if (!ctx || !c.m) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (c.set && c.set->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "the model set belongs to another context");
+  if (int rc = ww_wave_seq_check(ctx, c.m, what)) return rc;
+  if (int rc = wave_seq_validate(ctx, c.total_rows, c.row_offs, c.n_seq, c.pool_rows)) return rc;
+  if (c.set) {
+    if (c.n_ids < 0) return ww_fail(ctx, WW_EINVAL, "negative member count");
+    char why[160];
+    if (int rc = ww_set_check_ids(c.ids, c.n_ids, c.set->n, c.by_seq ? "seq_model" : "members", why, sizeof why)) return ww_fail(ctx, rc, "%s: %s", what, why);
+  }
+  const int32_t n = !c.set || c.by_seq ? 1 : c.ids ? c.n_ids : c.set->n;
   if (c.n_seq == 0 || c.row_offs[c.n_seq] == c.row_offs[0] || n == 0) return WW_OK;
   if (!c.mel) return ww_fail(ctx, WW_EINVAL, "NULL mel buffer");
   if (!c.enc && !c.logits && !c.pf && !c.post) return WW_OK;
@@ -1107,64 +1013,85 @@ static int set_wave_seq_check(ww_ctx *ctx, const ww_model_set *set, const set_se
   return WW_OK;
 }
 
-// The plan of a launch of `planes` planes: the set's view gives the receptive field, the width of a logit row and the segment option
-static void set_wave_seq_plan(const ww_model_set *set, const set_seq_request &c, int planes, wave_seq_plan &pl) {
-  wave_seq_set_make_plan(ww_wave_receptive_field(&set->view), set->view.info.n_out, set->view.opt_wave_seq_segment, c.total_rows, c.row_offs,
-                         c.n_seq, planes, c.by_seq, !c.logits && (c.pf || c.post), c.pf != nullptr, pl);
+// The plan of a launch of `planes` planes: the model gives the receptive field, the width of a logit row and the segment option
+// (which outputs exist decides the plan's scratch, not where they are)
+static void wave_seq_plan_of(const wave_seq_request &c, int planes, wave_seq_plan &pl) {
+  wave_seq_make_plan(ww_wave_receptive_field(c.m), c.m->info.n_out, c.m->opt_wave_seq_segment, c.total_rows, c.row_offs, c.n_seq, planes,
+                     !c.set ? WAVE_SEQ_IDS_NONE : c.by_seq ? WAVE_SEQ_IDS_BY_SEQ : WAVE_SEQ_IDS_BY_PLANE, !c.logits && (c.pf || c.post),
+                     c.pf != nullptr, pl);
 }
-static int set_wave_seq_planes(int32_t slots) { return slots < WW_SET_SLOT_CHUNK ? slots : WW_SET_SLOT_CHUNK; }
+static int wave_seq_planes(int32_t slots) { return slots < WW_SET_SLOT_CHUNK ? slots : WW_SET_SLOT_CHUNK; }
 
 // The checked call on DEVICE buffers (the context's device is current): one launch of the model kernel per WW_SET_SLOT_CHUNK slots
 // - the plane is a 16-bit grid dimension, and the scratch of a call with many duplicates stays bounded.  `bump`: the arena behind
-// what the caller took from it; the caller has reserved the first launch's plan there (the largest).
-static int set_wave_seq_run(ww_ctx *ctx, const ww_model_set *set, const set_seq_request &c, int32_t slots, const wave_seq_plan &first, ww_bump bump) {
-  const ww_model *m = &set->view;
-  const int NO = m->info.n_out, S = m->info.enc_width;
+// what the caller took from it; the caller has reserved the first launch's plan there (the largest).  Each launch's tables are ONE
+// block: segments, row_offs and, of a set, the launch's ids and (by_seq) the sequence of each segment.
+static int wave_seq_run(ww_ctx *ctx, const wave_seq_request &c, int32_t slots, const wave_seq_plan &first, ww_bump bump) {
+  const int NO = c.m->info.n_out, S = c.m->info.enc_width;
+  const size_t rows = (size_t)c.total_rows;
   std::vector<int32_t> own;
   const int32_t *ids = c.ids;
-  if (!ids) {
+  if (c.set && !ids) {
     own.assign(c.by_seq ? (size_t)c.n_seq : (size_t)slots, 0);  // (every sequence by member 0)
     if (!c.by_seq)
       for (int32_t k = 0; k < slots; ++k) own[k] = k;
     ids = own.data();
   }
   for (int32_t k0 = 0; k0 < slots; k0 += WW_SET_SLOT_CHUNK) {
-    const int planes = set_wave_seq_planes(slots - k0);
+    const int planes = wave_seq_planes(slots - k0);
     wave_seq_plan later;
-    if (k0) set_wave_seq_plan(set, c, planes, later);
-    const wave_seq_set_call sc = {(long long)set->stride, c.by_seq ? ids : ids + k0, planes, c.by_seq};
-    const size_t at = (size_t)k0 * (size_t)c.total_rows;  // the launch's first plane, in rows
+    if (k0) wave_seq_plan_of(c, planes, later);
+    const wave_seq_plan &pl = k0 ? later : first;
+    if (pl.segs.empty()) return WW_OK;
+    if (pl.segs.size() > 0x7fffffffu) return ww_fail(ctx, WW_EINVAL, "too many segments in one call");
+    ww_tables tb;
+    const size_t o_segs = tb.add(pl.segs), o_offs = tb.add(c.row_offs, (size_t)c.n_seq + 1);
+    const size_t o_ids = c.set ? tb.add(c.by_seq ? ids : ids + k0, c.by_seq ? (size_t)c.n_seq : (size_t)planes) : 0;
+    const size_t o_aux = c.set && c.by_seq ? tb.add(pl.seg_seq) : 0;
+    if (tb.bytes() != pl.b_segs + pl.b_offs + pl.b_ids + pl.b_aux) return ww_fail(ctx, WW_EINTERNAL, "wave_seq_run: the tables are not the size the plan reserved");
     ww_bump scratch = bump;  // (the launches of a call follow each other on one stream: they share the scratch)
-    if (int rc = wave_seq_run(ctx, m, c.mel, c.total_rows, c.row_offs, c.n_seq, c.pool_rows, c.enc ? c.enc + at * S : nullptr,
-                              c.logits ? c.logits + at * NO : nullptr, c.pf ? c.pf + at * NO : nullptr,
-                              c.post ? c.post + (size_t)k0 * c.n_seq * NO : nullptr, k0 ? later : first, scratch, &sc))
+    char *d_tab = scratch.take<char>(tb.bytes());
+    const size_t at = (size_t)k0 * rows;  // the launch's first plane, in rows
+    float *d_pf = c.pf ? c.pf + at * NO : nullptr, *d_post = c.post ? c.post + (size_t)k0 * c.n_seq * NO : nullptr;
+    float *d_z = c.logits ? c.logits + at * NO : nullptr;
+    if (!d_z && (d_pf || d_post)) d_z = scratch.take<float>(planes * rows * NO);
+    float *d_a = d_pf ? scratch.take<float>(planes * rows * NO) : nullptr, *d_b = d_pf ? scratch.take<float>(planes * rows * NO) : nullptr;
+    if (int rc = tb.send(ctx, d_tab)) return rc;
+    ww_set_ref ref;
+    if (c.set) ref = {(const int32_t *)(d_tab + o_ids), c.by_seq ? (const int32_t *)(d_tab + o_aux) : nullptr, (long long)c.set->stride};
+    if (int rc = ww_k_wave_sequence(ctx, c.m, c.mel, (const wv_seg *)(d_tab + o_segs), (int)pl.segs.size(), c.enc ? c.enc + at * S : nullptr, d_z,
+                                    c.set ? &ref : nullptr, planes, c.total_rows))
       return rc;
+    if (d_pf || d_post)
+      if (int rc = ww_k_wave_pool(ctx, d_z, c.row_offs[c.n_seq] - c.row_offs[0], c.row_offs[c.n_seq], NO, (const int64_t *)(d_tab + o_offs), c.n_seq,
+                                  c.pool_rows, pl.max_len, d_a, d_b, d_pf, d_post, planes, c.total_rows))
+        return rc;
   }
   return WW_OK;
 }
 
-static int set_wave_seq_dev(ww_ctx *ctx, const ww_model_set *set, const set_seq_request &c, const char *what) {
+static int wave_seq_dev(ww_ctx *ctx, const wave_seq_request &c, const char *what) {
   int32_t slots;
-  if (int rc = set_wave_seq_check(ctx, set, c, what, &slots)) return rc;
+  if (int rc = wave_seq_check(ctx, c, what, &slots)) return rc;
   if (slots == 0) return WW_OK;
   WW_ON_DEVICE(ctx, dev);
   wave_seq_plan pl;
-  set_wave_seq_plan(set, c, set_wave_seq_planes(slots), pl);
+  wave_seq_plan_of(c, wave_seq_planes(slots), pl);
   if (int rc = ww_ensure(ctx, ctx->dev, pl.bytes() + 1024, false)) return rc;
-  return set_wave_seq_run(ctx, set, c, slots, pl, ww_bump(ctx->dev.ptr, ctx->dev.cap));
+  return wave_seq_run(ctx, c, slots, pl, ww_bump(ctx->dev.ptr, ctx->dev.cap));
 }
 
 // HOST buffers: one upload of the mel, the outputs' planes on the device, every plane's sequence rows back.  Synchronous.
-static int set_wave_seq_host(ww_ctx *ctx, const ww_model_set *set, const set_seq_request &c, const char *what) {
+static int wave_seq_host(ww_ctx *ctx, const wave_seq_request &c, const char *what) {
   int32_t slots;
-  if (int rc = set_wave_seq_check(ctx, set, c, what, &slots)) return rc;
+  if (int rc = wave_seq_check(ctx, c, what, &slots)) return rc;
   if (slots == 0) return WW_OK;
   WW_ON_DEVICE(ctx, dev);
-  const int F = set->view.info.n_mel, NO = set->view.info.n_out, S = set->view.info.enc_width;
+  const int F = c.m->info.n_mel, NO = c.m->info.n_out, S = c.m->info.enc_width;
   const size_t rows = (size_t)c.total_rows, K = (size_t)slots;
   wave_seq_plan pl;
-  set_wave_seq_plan(set, c, set_wave_seq_planes(slots), pl);  // (which outputs exist decides the plan's scratch, not where they are)
-  set_seq_request d = c;
+  wave_seq_plan_of(c, wave_seq_planes(slots), pl);
+  wave_seq_request d = c;
   const size_t b_mel = ww_bump::need(rows * F, 4), b_enc = c.enc ? ww_bump::need(K * rows * S, 4) : 0, b_rows = ww_bump::need(K * rows * NO, 4);
   const size_t b_post = ww_bump::need(K * c.n_seq * NO, 4);
   if (int rc = ww_ensure(ctx, ctx->dev, b_mel + b_enc + 2 * b_rows + b_post + pl.bytes() + 1024, false)) return rc;
@@ -1175,11 +1102,12 @@ static int set_wave_seq_host(ww_ctx *ctx, const ww_model_set *set, const set_seq
   d.logits = c.logits ? bump.take<float>(K * rows * NO) : nullptr;
   d.pf = c.pf ? bump.take<float>(K * rows * NO) : nullptr;
   d.post = c.post ? bump.take<float>(K * c.n_seq * NO) : nullptr;
-  // rows outside every sequence are neither read nor written, in any plane: only [r0, r1) travels, each way
+  // rows of the mel buffer outside every sequence are never read, rows of the outputs outside every sequence never written, in any
+  // plane: only [r0, r1) travels, each way, and the caller's bytes elsewhere stay as they are
   const int64_t r0 = c.row_offs[0], r1 = c.row_offs[c.n_seq];
   WW_HIP(ctx, hipMemcpyAsync(d_mel + r0 * F, c.mel + r0 * F, (size_t)(r1 - r0) * F * 4, hipMemcpyHostToDevice, ctx->stream));
   if (d.post) WW_HIP(ctx, hipMemcpyAsync(d.post, c.post, K * c.n_seq * NO * 4, hipMemcpyHostToDevice, ctx->stream));  // (empty sequences keep theirs)
-  if (int rc = set_wave_seq_run(ctx, set, d, slots, pl, bump)) return rc;
+  if (int rc = wave_seq_run(ctx, d, slots, pl, bump)) return rc;
   for (size_t k = 0; k < K; ++k) {
     const size_t p = k * rows;
     if (c.enc) WW_HIP(ctx, hipMemcpyAsync(c.enc + (p + r0) * S, d.enc + (p + r0) * S, (size_t)(r1 - r0) * S * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1193,19 +1121,35 @@ static int set_wave_seq_host(ww_ctx *ctx, const ww_model_set *set, const set_seq
 
 extern "C" {
 
+int ww_wave_sequence_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
+                         int32_t pool_rows, float *d_enc, float *d_logits, float *d_post_frames, float *d_post) {
+  WW_GUARD_BEGIN
+  const wave_seq_request c = {m, nullptr, d_mel, total_rows, row_offs, n_seq, pool_rows, nullptr, 0, false, d_enc, d_logits, d_post_frames, d_post};
+  return wave_seq_dev(ctx, c, "ww_wave_sequence_dev");
+  WW_GUARD_END(ctx)
+}
+
+int ww_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
+                     int32_t pool_rows, float *enc, float *logits, float *post_frames, float *post) {
+  WW_GUARD_BEGIN
+  const wave_seq_request c = {m, nullptr, mel, total_rows, row_offs, n_seq, pool_rows, nullptr, 0, false, enc, logits, post_frames, post};
+  return wave_seq_host(ctx, c, "ww_wave_sequence");
+  WW_GUARD_END(ctx)
+}
+
 int ww_set_wave_sequence_dev(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
                              const int32_t *seq_model, int32_t pool_rows, float *d_enc, float *d_logits, float *d_post_frames, float *d_post) {
   WW_GUARD_BEGIN
-  const set_seq_request c = {d_mel, total_rows, row_offs, n_seq, pool_rows, seq_model, n_seq < 0 ? 0 : n_seq, true, d_enc, d_logits, d_post_frames, d_post};
-  return set_wave_seq_dev(ctx, set, c, "ww_set_wave_sequence_dev");
+  const wave_seq_request c = {set ? &set->view : nullptr, set, d_mel, total_rows, row_offs, n_seq, pool_rows, seq_model, n_seq < 0 ? 0 : n_seq, true, d_enc, d_logits, d_post_frames, d_post};
+  return wave_seq_dev(ctx, c, "ww_set_wave_sequence_dev");
   WW_GUARD_END(ctx)
 }
 
 int ww_set_wave_sequence(ww_ctx *ctx, const ww_model_set *set, const float *mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
                          const int32_t *seq_model, int32_t pool_rows, float *enc, float *logits, float *post_frames, float *post) {
   WW_GUARD_BEGIN
-  const set_seq_request c = {mel, total_rows, row_offs, n_seq, pool_rows, seq_model, n_seq < 0 ? 0 : n_seq, true, enc, logits, post_frames, post};
-  return set_wave_seq_host(ctx, set, c, "ww_set_wave_sequence");
+  const wave_seq_request c = {set ? &set->view : nullptr, set, mel, total_rows, row_offs, n_seq, pool_rows, seq_model, n_seq < 0 ? 0 : n_seq, true, enc, logits, post_frames, post};
+  return wave_seq_host(ctx, c, "ww_set_wave_sequence");
   WW_GUARD_END(ctx)
 }
 
@@ -1213,16 +1157,16 @@ int ww_set_wave_sequence_all_dev(ww_ctx *ctx, const ww_model_set *set, const flo
                                  int32_t pool_rows, const int32_t *members, int32_t n_members, float *d_enc, float *d_logits, float *d_post_frames,
                                  float *d_post) {
   WW_GUARD_BEGIN
-  const set_seq_request c = {d_mel, total_rows, row_offs, n_seq, pool_rows, members, n_members, false, d_enc, d_logits, d_post_frames, d_post};
-  return set_wave_seq_dev(ctx, set, c, "ww_set_wave_sequence_all_dev");
+  const wave_seq_request c = {set ? &set->view : nullptr, set, d_mel, total_rows, row_offs, n_seq, pool_rows, members, n_members, false, d_enc, d_logits, d_post_frames, d_post};
+  return wave_seq_dev(ctx, c, "ww_set_wave_sequence_all_dev");
   WW_GUARD_END(ctx)
 }
 
 int ww_set_wave_sequence_all(ww_ctx *ctx, const ww_model_set *set, const float *mel, int64_t total_rows, const int64_t *row_offs, int32_t n_seq,
                              int32_t pool_rows, const int32_t *members, int32_t n_members, float *enc, float *logits, float *post_frames, float *post) {
   WW_GUARD_BEGIN
-  const set_seq_request c = {mel, total_rows, row_offs, n_seq, pool_rows, members, n_members, false, enc, logits, post_frames, post};
-  return set_wave_seq_host(ctx, set, c, "ww_set_wave_sequence_all");
+  const wave_seq_request c = {set ? &set->view : nullptr, set, mel, total_rows, row_offs, n_seq, pool_rows, members, n_members, false, enc, logits, post_frames, post};
+  return wave_seq_host(ctx, c, "ww_set_wave_sequence_all");
   WW_GUARD_END(ctx)
 }
 

@@ -274,6 +274,8 @@ bool ww_wave_tick_capable(const ww_model *m, int n_streams);
 int ww_k_wave_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, const ww_tick_tag &tag, const ww_set_ref *set = nullptr);
 // The fp32 Wavenet's sequence form (wavenet.hip: wavenet_seq_kernel) over launch_plan.h's segments (wv_seg).
 int ww_wave_receptive_field(const ww_model *m);  // 1 + 2 * sum of the dilations
+// the form's reach, for the entry point or launcher `what`: WW_EINVAL for a CRNN and for a model in split-bf16 mode
+int ww_wave_seq_check(ww_ctx *ctx, const ww_model *m, const char *what);
 // set (m: the set's view): segments x planes workgroups in ONE launch, enc / logits [planes][plane_rows][...]; the member of plane y is
 // set->ids[y], or - set->aux given, one plane - the member of segment x is set->ids[set->aux[x]] (launch_plan.h: seg_seq)
 int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const wv_seg *d_segs, int n_segs, float *d_enc, float *d_logits,

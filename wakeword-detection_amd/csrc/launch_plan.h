@@ -172,8 +172,8 @@ static inline int64_t ww_wave_segment_rows(int64_t rows, int rf) {
 }
 
 // Device scratch of one call: the segment table, the device copy of row_offs, logits where the caller wants none, and the two
-// buffers of the pooled maximum.  A model set's call (wave_seq_set_make_plan) adds its member ids and, where each sequence has a
-// member of its own, seg_seq: the sequence of segment i - a table BESIDE the segments, wv_seg stays as it is.
+// buffers of the pooled maximum - `planes` planes of total_rows rows each.  A model set's call adds its member ids and, where each
+// sequence has a member of its own, seg_seq: the sequence of segment i - a table BESIDE the segments, wv_seg stays as it is.
 struct wave_seq_plan {
   std::vector<wv_seg> segs;
   std::vector<int32_t> seg_seq;
@@ -181,11 +181,15 @@ struct wave_seq_plan {
   size_t b_segs = 0, b_offs = 0, b_z = 0, b_pool = 0, b_ids = 0, b_aux = 0;
   size_t bytes() const { return b_segs + b_offs + b_ids + b_aux + b_z + 2 * b_pool; }
 };
+// How a call names its members.  NONE: a single model (one plane, no table).  BY_PLANE: plane k by member ids[k], `planes` ids - the
+// plane is a grid dimension and there is no second table.  BY_SEQ: one plane, sequence s by member ids[s], n_seq ids - a segment
+// finds its member through seg_seq, written as the cuts are made (empty sequences have no segment).
+enum wave_seq_ids { WAVE_SEQ_IDS_NONE, WAVE_SEQ_IDS_BY_PLANE, WAVE_SEQ_IDS_BY_SEQ };
 // Cuts: a sequence is computed in segments of G rows; every segment but a sequence's first starts RF - 1 rows early and drops them.
-// G = seg_opt (WW_OPT_WAVE_SEQ_SEGMENT), or if that is 0 the library's: ww_wave_segment_rows', at least one chunk.
-static inline void wave_seq_make_plan(int rf, int n_out, int64_t seg_opt, int64_t total_rows, const int64_t *row_offs, int n_seq, bool need_z,
-                                      bool need_pool, wave_seq_plan &pl) {
-  const int NO = n_out;
+// G = seg_opt (WW_OPT_WAVE_SEQ_SEGMENT), or if that is 0 the library's: ww_wave_segment_rows', at least one chunk.  The cuts are the
+// same for every plane and every id form: a member is weights, not geometry.
+static inline void wave_seq_make_plan(int rf, int n_out, int64_t seg_opt, int64_t total_rows, const int64_t *row_offs, int n_seq, int planes,
+                                      wave_seq_ids ids, bool need_z, bool need_pool, wave_seq_plan &pl) {
   int64_t span = 0;
   for (int s = 0; s < n_seq; ++s) {
     span += row_offs[s + 1] - row_offs[s];
@@ -198,33 +202,16 @@ static inline void wave_seq_make_plan(int rf, int n_out, int64_t seg_opt, int64_
     for (int64_t s0 = 0; s0 < len; s0 += G) {
       const int64_t warm = std::min<int64_t>(s0, rf - 1), rows = std::min<int64_t>(G, len - s0);
       pl.segs.push_back({o + s0 - warm, (int32_t)(warm + rows), (int32_t)warm});
+      if (ids == WAVE_SEQ_IDS_BY_SEQ) pl.seg_seq.push_back(s);
     }
   }
+  const size_t rows = (size_t)planes * (size_t)total_rows * n_out;
   pl.b_segs = ww_bump::need(pl.segs.size(), sizeof(wv_seg));
   pl.b_offs = ww_bump::need((size_t)n_seq + 1, 8);
-  pl.b_z = need_z ? ww_bump::need((size_t)total_rows * NO, 4) : 0;
-  pl.b_pool = need_pool ? ww_bump::need((size_t)total_rows * NO, 4) : 0;
-}
-// The same call over a model set (ww_set_wave_sequence*): the cuts are wave_seq_make_plan's - a member is weights, not geometry -
-// and every output and scratch buffer has `planes` planes of total_rows rows.  by_seq (one plane; sequence s by member ids[s], n_seq
-// ids): a segment finds its member through seg_seq, read off the finished cuts (a segment's first kept row lies in its sequence).
-// Otherwise (plane k by member ids[k], `planes` ids): the plane is a grid dimension and there is no second table.
-static inline void wave_seq_set_make_plan(int rf, int n_out, int64_t seg_opt, int64_t total_rows, const int64_t *row_offs, int n_seq, int planes,
-                                          bool by_seq, bool need_z, bool need_pool, wave_seq_plan &pl) {
-  wave_seq_make_plan(rf, n_out, seg_opt, total_rows, row_offs, n_seq, need_z, need_pool, pl);
-  const size_t plane = (size_t)total_rows * n_out;
-  pl.b_z = need_z ? ww_bump::need((size_t)planes * plane, 4) : 0;
-  pl.b_pool = need_pool ? ww_bump::need((size_t)planes * plane, 4) : 0;
-  pl.b_ids = ww_bump::need(by_seq ? (size_t)n_seq : (size_t)planes, 4);
-  if (by_seq) {
-    pl.seg_seq.reserve(pl.segs.size());
-    int s = 0;
-    for (const wv_seg &sg : pl.segs) {
-      while (row_offs[s + 1] <= sg.row0 + sg.skip) ++s;  // (empty sequences have no segment)
-      pl.seg_seq.push_back(s);
-    }
-    pl.b_aux = ww_bump::need(pl.seg_seq.size(), 4);
-  }
+  pl.b_z = need_z ? ww_bump::need(rows, 4) : 0;
+  pl.b_pool = need_pool ? ww_bump::need(rows, 4) : 0;
+  pl.b_ids = ids == WAVE_SEQ_IDS_NONE ? 0 : ww_bump::need(ids == WAVE_SEQ_IDS_BY_SEQ ? (size_t)n_seq : (size_t)planes, 4);
+  pl.b_aux = ww_bump::need(pl.seg_seq.size(), 4);
 }
 
 // ---- a causal bank's feed (streams.hip: ww_stream_feed) ---------------------------------------------------------------------------

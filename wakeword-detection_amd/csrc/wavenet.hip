@@ -1448,7 +1448,7 @@ int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
 }
 
 // The sequence form's reach: the fp32 transposed block loop only
-static int wave_seq_check(ww_ctx *ctx, const ww_model *m, const char *what) {
+int ww_wave_seq_check(ww_ctx *ctx, const ww_model *m, const char *what) {
   if (m->kind != WW_KIND_WAVENET) return ww_fail(ctx, WW_EINVAL, "%s: the sequence form exists for Wavenet models only (a CRNN's bidirectional GRUs have no causal reading)", what);
   if (m->precision != WW_PRECISION_FP32) return ww_fail(ctx, WW_EINVAL, "%s: the sequence form is fp32 only; this model is in split-bf16 mode", what);
   return WW_OK;
@@ -1463,7 +1463,7 @@ int ww_wave_receptive_field(const ww_model *m) {
 int ww_k_wave_sequence(ww_ctx *ctx, const ww_model *m, const float *d_mel, const wv_seg *d_segs, int n_segs, float *d_enc, float *d_logits,
                        const ww_set_ref *set, int planes, int64_t plane_rows) {
   if (n_segs <= 0 || planes <= 0) return WW_OK;
-  if (int rc = wave_seq_check(ctx, m, "ww_wave_sequence")) return rc;
+  if (int rc = ww_wave_seq_check(ctx, m, "ww_wave_sequence")) return rc;
   wave_args a;
   if (int rc = wave_model_args(ctx, m->wave, d_mel, a)) return rc;
   wave_seq_args q = {};
@@ -1517,7 +1517,7 @@ int ww_k_wave_stream_tick(ww_ctx *ctx, const ww_model *m, const float *d_hist, c
                           const int32_t *d_win_aux, int nw, float *d_state, float *d_zring, int32_t *d_zpos, float *d_out,
                           const ww_tick_tag *tag, const ww_set_ref *set) {
   if (nw <= 0) return WW_OK;
-  if (int rc = wave_seq_check(ctx, m, "causal streaming tick")) return rc;
+  if (int rc = ww_wave_seq_check(ctx, m, "causal streaming tick")) return rc;
   wave_args a;
   if (int rc = wave_model_args(ctx, m->wave, d_hist, a)) return rc;
   if (tag) a.tag = *tag;
@@ -1551,7 +1551,7 @@ int ww_k_wave_feed(ww_ctx *ctx, const ww_model *m, const float *d_rows, const wv
                    float *d_zring, int32_t *d_zpos, int pidx, float *d_post, const ww_set_ref *set, int slots,
                    int64_t plane_rows, float *d_post_rows) {
   if (n_segs <= 0) return WW_OK;
-  if (int rc = wave_seq_check(ctx, m, "ww_stream_feed")) return rc;
+  if (int rc = ww_wave_seq_check(ctx, m, "ww_stream_feed")) return rc;
   if (slots && (!set || slots > 65535 || plane_rows <= 0 || !d_post_rows)) return ww_fail(ctx, WW_EINTERNAL, "ww_k_wave_feed: %d member slots", slots);
   wave_args a;
   if (int rc = wave_model_args(ctx, m->wave, d_rows, a)) return rc;

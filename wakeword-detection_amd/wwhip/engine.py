@@ -284,30 +284,21 @@ class Engine:
         want, seqs, offs, mel = _sequence_batch(mels, self.n_mel, want)
         total = int(offs[-1])
         pool = self.window if pool is None else int(pool)
-        bufs = {"enc": np.empty((total, 32), np.float32) if "enc" in want else None,
-                "logits": np.empty((total, self.n_out), np.float32) if "logits" in want else None,
-                "post_frames": np.empty((total, self.n_out), np.float32) if "post_frames" in want else None,
-                "post": np.full((len(seqs), self.n_out), np.nan, np.float32) if "post" in want else None}
+        bufs = _sequence_buffers(self.n_out, self.enc_shape[1], want, None, total, len(seqs))
         self._chk(self._lib.ww_wave_sequence(self.ctx.handle, self._model, _lib.ptr(mel), total, _lib.ptr(offs), len(seqs), pool,
                                              _lib.ptr(bufs["enc"]), _lib.ptr(bufs["logits"]), _lib.ptr(bufs["post_frames"]),
                                              _lib.ptr(bufs["post"])))
-        out = {}
-        for k in want:
-            out[k] = [bufs[k][i] for i in range(len(seqs))] if k == "post" else [bufs[k][offs[i]:offs[i + 1]] for i in range(len(seqs))]
-        return out
+        return _per_sequence(bufs, want, offs)
 
     def wave_sequence_dev(self, d_mel_ptr: int, total_rows: int, row_offs: np.ndarray, pool: Optional[int] = None, d_enc_ptr: int = 0,
                           d_logits_ptr: int = 0, d_post_frames_ptr: int = 0, d_post_ptr: int = 0) -> None:
         """:meth:`sequence_forward` on device buffers (``ww_wave_sequence_dev``): sequence ``s`` is rows ``[row_offs[s],
         row_offs[s + 1])`` of the mel buffer (``row_offs``: a host array); the per-row outputs are indexed by mel row, ``post`` by
         sequence; a pointer of 0 leaves that output out.  Enqueued on the context's stream, not waited for."""
-        offs = np.ascontiguousarray(row_offs, dtype=np.int64)
-        if offs.ndim != 1 or offs.size < 1:
-            raise ValueError("row_offs must be a 1-D array of n_seq + 1 offsets")
-        vp = lambda p: C.c_void_p(p) if p else None
-        self._chk(self._lib.ww_wave_sequence_dev(self.ctx.handle, self._model, vp(d_mel_ptr), int(total_rows), _lib.ptr(offs), int(offs.size - 1),
-                                                 self.window if pool is None else int(pool), vp(d_enc_ptr), vp(d_logits_ptr),
-                                                 vp(d_post_frames_ptr), vp(d_post_ptr)))
+        offs = _row_offs(row_offs)
+        self._chk(self._lib.ww_wave_sequence_dev(self.ctx.handle, self._model, _vp(d_mel_ptr), int(total_rows), _lib.ptr(offs), int(offs.size - 1),
+                                                 self.window if pool is None else int(pool), _vp(d_enc_ptr), _vp(d_logits_ptr),
+                                                 _vp(d_post_frames_ptr), _vp(d_post_ptr)))
 
     # ------------------------------------------------------------------ evaluator
     def far_frr(self, pos: np.ndarray, neg: np.ndarray, thresholds: np.ndarray, num_wakewords: float, hours: float,
@@ -405,6 +396,33 @@ def _sequence_batch(mels, n_mel: int, want):
     np.cumsum([m.shape[0] for m in seqs], out=offs[1:])
     mel = np.concatenate(seqs) if seqs else np.zeros((0, n_mel), np.float32)
     return want, seqs, offs, mel
+
+
+def _sequence_buffers(n_out: int, enc_width: int, want, planes: Optional[int], total: int, n_seq: int) -> dict:
+    """Host outputs of a sequence call (``planes=None``: the one plane of a single model or of the by-sequence form); ``post``
+    starts as NaN."""
+    lead = () if planes is None else (planes,)
+    shapes = {"enc": (total, enc_width), "logits": (total, n_out), "post_frames": (total, n_out), "post": (n_seq, n_out)}
+    return {k: (np.full(lead + shapes[k], np.nan, np.float32) if k == "post" else np.empty(lead + shapes[k], np.float32)) if k in want
+            else None for k in Engine.SEQUENCE_OUTPUTS}
+
+
+def _per_sequence(bufs: dict, want, offs: np.ndarray) -> dict:
+    """One plane's buffers as ``{name: list of arrays, one per sequence}``."""
+    n = offs.size - 1
+    return {k: [bufs[k][i] for i in range(n)] if k == "post" else [bufs[k][offs[i]:offs[i + 1]] for i in range(n)] for k in want}
+
+
+def _row_offs(row_offs) -> np.ndarray:
+    offs = np.ascontiguousarray(row_offs, dtype=np.int64)
+    if offs.ndim != 1 or offs.size < 1:
+        raise ValueError("row_offs must be a 1-D array of n_seq + 1 offsets")
+    return offs
+
+
+def _vp(p: int):
+    """A device address as a ``void *`` argument; 0 is NULL."""
+    return C.c_void_p(p) if p else None
 
 
 def _member_ids(ids, n: int, n_models: int, what: str) -> np.ndarray:
@@ -593,18 +611,6 @@ class ModelSet:
         assert n.value == nw, (n.value, nw)
         return out
 
-    def _sequence_buffers(self, want, planes: Optional[int], total: int, n_seq: int) -> dict:
-        """Host outputs of a sequence call (``planes=None``: the one plane of the by-sequence form); ``post`` starts as NaN."""
-        lead = () if planes is None else (planes,)
-        shapes = {"enc": (total, 32), "logits": (total, self.n_out), "post_frames": (total, self.n_out), "post": (n_seq, self.n_out)}
-        return {k: (np.full(lead + shapes[k], np.nan, np.float32) if k == "post" else np.empty(lead + shapes[k], np.float32)) if k in want
-                else None for k in Engine.SEQUENCE_OUTPUTS}
-
-    @staticmethod
-    def _per_sequence(bufs: dict, want, offs: np.ndarray) -> dict:
-        n = offs.size - 1
-        return {k: [bufs[k][i] for i in range(n)] if k == "post" else [bufs[k][offs[i]:offs[i + 1]] for i in range(n)] for k in want}
-
     def sequence_forward(self, mels, model_ids, pool: Optional[int] = None, want: Sequence[str] = ("post",)) -> dict:
         """:meth:`Engine.sequence_forward` with sequence ``s`` evaluated by member ``model_ids[s]`` (``ww_set_wave_sequence``): one
         upload, one launch of the model kernel over all sequences, whoever their members are.  Same arguments otherwise, the
@@ -612,12 +618,12 @@ class ModelSet:
         want, seqs, offs, mel = _sequence_batch(mels, self.n_mel, want)
         ids = _member_ids(model_ids, len(seqs), self.n_models, "seq_model")
         total = int(offs[-1])
-        bufs = self._sequence_buffers(want, None, total, len(seqs))
+        bufs = _sequence_buffers(self.n_out, self.enc_shape[1], want, None, total, len(seqs))
         _lib.raise_for(self._lib.ww_set_wave_sequence(self.ctx.handle, self._set, _lib.ptr(mel), total, _lib.ptr(offs), len(seqs), _lib.ptr(ids),
                                                       self.window if pool is None else int(pool), _lib.ptr(bufs["enc"]),
                                                       _lib.ptr(bufs["logits"]), _lib.ptr(bufs["post_frames"]), _lib.ptr(bufs["post"])),
                        self.ctx.handle)
-        return self._per_sequence(bufs, want, offs)
+        return _per_sequence(bufs, want, offs)
 
     def sequence_forward_all(self, mels, members=None, pool: Optional[int] = None, want: Sequence[str] = ("post",)) -> dict:
         """Every sequence by every member of ``members`` (``None``: all, in order; any number of ids, duplicates allowed) over ONE
@@ -628,43 +634,34 @@ class ModelSet:
         ids = self._slots(members)
         k = self.n_models if ids is None else int(ids.size)
         total = int(offs[-1])
-        bufs = self._sequence_buffers(want, k, total, len(seqs))
+        bufs = _sequence_buffers(self.n_out, self.enc_shape[1], want, k, total, len(seqs))
         _lib.raise_for(self._lib.ww_set_wave_sequence_all(self.ctx.handle, self._set, _lib.ptr(mel), total, _lib.ptr(offs), len(seqs),
                                                           self.window if pool is None else int(pool), _lib.ptr(ids) if ids is not None else None,
                                                           k if ids is not None else 0, _lib.ptr(bufs["enc"]), _lib.ptr(bufs["logits"]),
                                                           _lib.ptr(bufs["post_frames"]), _lib.ptr(bufs["post"])), self.ctx.handle)
-        return {name: [self._per_sequence({name: bufs[name][j]}, (name,), offs)[name] for j in range(k)] for name in want}
-
-    @staticmethod
-    def _row_offs(row_offs) -> np.ndarray:
-        offs = np.ascontiguousarray(row_offs, dtype=np.int64)
-        if offs.ndim != 1 or offs.size < 1:
-            raise ValueError("row_offs must be a 1-D array of n_seq + 1 offsets")
-        return offs
+        return {name: [_per_sequence({name: bufs[name][j]}, (name,), offs)[name] for j in range(k)] for name in want}
 
     def wave_sequence_dev(self, d_mel_ptr: int, total_rows: int, row_offs: np.ndarray, model_ids, pool: Optional[int] = None,
                           d_enc_ptr: int = 0, d_logits_ptr: int = 0, d_post_frames_ptr: int = 0, d_post_ptr: int = 0) -> None:
         """:meth:`sequence_forward` on device buffers (``ww_set_wave_sequence_dev``): :meth:`Engine.wave_sequence_dev` with
         sequence ``s`` by member ``model_ids[s]`` (a host array).  Enqueued on the context's stream, not waited for."""
-        offs = self._row_offs(row_offs)
+        offs = _row_offs(row_offs)
         ids = _member_ids(model_ids, int(offs.size - 1), self.n_models, "seq_model")
-        vp = lambda p: C.c_void_p(p) if p else None
-        _lib.raise_for(self._lib.ww_set_wave_sequence_dev(self.ctx.handle, self._set, vp(d_mel_ptr), int(total_rows), _lib.ptr(offs),
+        _lib.raise_for(self._lib.ww_set_wave_sequence_dev(self.ctx.handle, self._set, _vp(d_mel_ptr), int(total_rows), _lib.ptr(offs),
                                                           int(offs.size - 1), _lib.ptr(ids), self.window if pool is None else int(pool),
-                                                          vp(d_enc_ptr), vp(d_logits_ptr), vp(d_post_frames_ptr), vp(d_post_ptr)), self.ctx.handle)
+                                                          _vp(d_enc_ptr), _vp(d_logits_ptr), _vp(d_post_frames_ptr), _vp(d_post_ptr)), self.ctx.handle)
 
     def wave_sequence_all_dev(self, d_mel_ptr: int, total_rows: int, row_offs: np.ndarray, members=None, pool: Optional[int] = None,
                               d_enc_ptr: int = 0, d_logits_ptr: int = 0, d_post_frames_ptr: int = 0, d_post_ptr: int = 0) -> None:
         """:meth:`sequence_forward_all` on device buffers (``ww_set_wave_sequence_all_dev``): plane ``k`` of every output -
         ``[len(members), total_rows, ...]``, ``post`` ``[len(members), n_seq, n_out]`` - is member ``members[k]``'s.  Enqueued on
         the context's stream, not waited for."""
-        offs = self._row_offs(row_offs)
+        offs = _row_offs(row_offs)
         ids = self._slots(members)
-        vp = lambda p: C.c_void_p(p) if p else None
-        _lib.raise_for(self._lib.ww_set_wave_sequence_all_dev(self.ctx.handle, self._set, vp(d_mel_ptr), int(total_rows), _lib.ptr(offs),
+        _lib.raise_for(self._lib.ww_set_wave_sequence_all_dev(self.ctx.handle, self._set, _vp(d_mel_ptr), int(total_rows), _lib.ptr(offs),
                                                               int(offs.size - 1), self.window if pool is None else int(pool),
                                                               _lib.ptr(ids) if ids is not None else None, int(ids.size) if ids is not None else 0,
-                                                              vp(d_enc_ptr), vp(d_logits_ptr), vp(d_post_frames_ptr), vp(d_post_ptr)),
+                                                              _vp(d_enc_ptr), _vp(d_logits_ptr), _vp(d_post_frames_ptr), _vp(d_post_ptr)),
                        self.ctx.handle)
 
     def close(self) -> None:
