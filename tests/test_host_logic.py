@@ -1052,6 +1052,83 @@ def test_model_pack_hostile_blobs(pack_check, pack_blobs, name):
         assert status in (0, WW_EBLOB), (case, status, msg)
 
 
+def _geom_words(other, tag):
+    """The ``geom <tag> k=v ...`` line model_pack_check prints, as a dict (lists for the per-block words)."""
+    line = next(x for x in other if x.startswith(f"geom {tag} "))
+    out = {}
+    for kv in line.split()[2:]:
+        k, v = kv.split("=")
+        out[k] = [int(x) for x in v.split(",") if x] if "," in v else int(v)
+    return out
+
+
+def test_model_pack_takes_every_geometry_of_the_table(pack_check):
+    """Every blob of tests/geometry64.py's GEOMETRIES - the edges of what the loader accepts: NB 32, T 192, NOUT 16, C 64, CRNN NOUT 8,
+    T n_mel 16384, a 13-, 32- and 39-band filter - packs with status 0 under Address + UB sanitizer, and the geometry the packer
+    prints is the bundle's."""
+    import geometry64 as G
+    from wwhip import weights as W
+    for name, g in G.GEOMETRIES.items():
+        b = g.bundle()
+        (status, msg, arrays, other), = pack_check(G.blob_of(b))
+        assert status == 0 and arrays, (name, status, msg)
+        want = G.expected_geometry(b)
+        got = _geom_words(other, "crnn" if g.kind == "crnn" else "wave")
+        assert {k: got[k] for k in want} == want, (name, got, want)
+        info = _geom_words(other, "info")
+        assert (info["window"], info["n_mel"], info["n_out"]) == (g.T, g.n_mel, g.n_out), (name, info)
+        if g.kind == "crnn":
+            assert got["generic"] == int(not g.standard) and got["FEATP"] == -(-got["OF"] * got["C"] // 64) * 64, (name, got)
+
+
+def _beyond_bounds():
+    """name -> blob: one step past each bound the kernels rely on (the step inside is a row of GEOMETRIES)."""
+    import dataclasses
+    import geometry64 as G
+    from wwhip import weights as W
+    wave = lambda **kw: G.synthetic_wavenet(**dict(dict(seed=1, T=20, n_mel=40, dilations=[1, 2], has_res=[True, False], n_out=2), **kw))
+    crnn = lambda **kw: G.synthetic_crnn(**dict(dict(seed=2, T=40, n_mel=40, C=4, KF=8, KT=5, SF=8, ST=3, same=False, n_out=2, head=1), **kw))
+    out = {
+        "NB = 33": wave(dilations=[1] * 33, has_res=[True] * 33),
+        "a dilation of 9": wave(dilations=[1, 9]),
+        "T = 193": wave(T=193),
+        "NOUT = 17": wave(n_out=17),
+        "CRNN C = 65": crnn(C=65),
+        "CRNN NOUT = 9": crnn(n_out=9),
+        "T n_mel = 16385": crnn(T=3277, n_mel=5, KF=3, KT=3, SF=1, ST=64),
+        "CRNN n_mel differing from the filter's": dataclasses.replace(crnn(), filt=G.cut_filter(39)),
+        "Wavenet n_mel differing from the filter's": dataclasses.replace(wave(), filt=G.cut_filter(39)),
+    }
+    assert out["T n_mel = 16385"].crnn.n_frames * out["T n_mel = 16385"].crnn.n_mel == 16385
+    blobs = {k: W.pack_blob(v) for k, v in out.items()}
+    # NB = 0: no bundle has no blocks - the block count of wave.meta (word 4) of a two-block blob set to 0
+    two = W.pack_blob(wave())
+    off = next(o for n, _, o, _ in _blob_sections(two) if n == "wave.meta")
+    blobs["NB = 0"] = two[:off + 16] + (0).to_bytes(4, "little") + two[off + 20:]
+    return blobs
+
+
+BEYOND = ["NB = 33", "NB = 0", "a dilation of 9", "T = 193", "NOUT = 17", "CRNN C = 65", "CRNN NOUT = 9", "T n_mel = 16385",
+          "CRNN n_mel differing from the filter's", "Wavenet n_mel differing from the filter's"]
+
+
+@pytest.fixture(scope="module")
+def beyond_blobs():
+    blobs = _beyond_bounds()
+    assert sorted(blobs) == sorted(BEYOND)
+    return blobs
+
+
+@pytest.mark.parametrize("name", BEYOND, ids=[n.replace(" ", "-").replace("'", "") for n in BEYOND])
+def test_model_pack_refuses_what_the_kernels_cannot_hold(pack_check, beyond_blobs, name):
+    """One step past each bound a kernel relies on is refused by the loader with WW_EBLOB and a message - no sanitizer report, and
+    never a loaded model that a launch would have to refuse (NB = 33 was one until pack_wave bounded NB: wave_args::dil4[2], the
+    residual mask and the LDS vector table hold 32 blocks): 33 blocks, no block, a dilation of 9, T = 193, NOUT = 17, a CRNN of 65
+    channels, of 9 outputs, of 16,385 window values, and a model whose n_mel is not its filter's."""
+    (status, msg, arrays, _), = pack_check(beyond_blobs[name])
+    assert status == WW_EBLOB and msg.strip() and not arrays, (name, status, msg)
+
+
 def test_model_pack_is_host_only_and_layout_constants_have_one_definition():
     """model_pack.h and model_layout.h include no HIP header and call no HIP function (so they build and run without a GPU);
     every constant model_layout.h defines is defined nowhere else under csrc/, and api.hip carries none of the literals the

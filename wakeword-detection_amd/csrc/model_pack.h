@@ -282,7 +282,8 @@ inline int pack_crnn(ww_packed_model &pm, const blob_view &bv) {
   c.PF = meta[7]; c.PT = meta[8]; c.OF = meta[9]; c.OT = meta[10]; c.H = meta[11]; c.NOUT = meta[12]; c.HEAD = meta[13];
   // Every word is bounded before any arithmetic on it.  A window holds at most 16,384 values (T * n_mel, n_mel >= 1), so no
   // kernel extent, stride, padding or output count of a conv over it can exceed 16,384 either: with these bounds every product
-  // below (K = KF * KT, OF * C, (OT - 1) * ST, C * K, ...) stays under 2^31.
+  // below (K = KF * KT, OF * C, (OT - 1) * ST, C * K, ...) stays under 2^31.  It is also conv_generic_kernel's bound: the kernel
+  // stages a window in 4 * T * n_mel <= 65,536 bytes of dynamic LDS, the most a launch is given without hipFuncSetAttribute.
   const int LIM = 16384;
   auto in = [](int x, int lo, int hi) { return x >= lo && x <= hi; };
   if (c.H != 32 || !in(c.C, 1, 64) || !in(c.NOUT, 1, 8) || c.n_mel != pm.filt.n_mel || !in(c.T, 1, LIM) ||
@@ -398,9 +399,11 @@ inline int pack_wave(ww_packed_model &pm, const blob_view &bv) {
   if (!bv.ints("wave.meta", 6, meta)) return pm.fail(WW_EBLOB, "blob lacks wave.meta");
   ww_wave_geom &v = pm.wave;
   v.T = meta[0]; v.n_mel = meta[1]; v.C = meta[2]; v.S = meta[3]; v.NB = meta[4]; v.NOUT = meta[5];
-  if (v.C != 16 || v.S != 32 || v.T > 192 || v.T < 1 || v.n_mel > 48 || v.NOUT < 1 || v.NOUT > 16 || v.NB < 1 ||
+  // NB <= 32: the kernels carry a block's dilation in 4 bits of wave_args::dil4[2] and its residual flag in a bit of a 32-bit mask,
+  // and size their LDS vector table (WV_VT_F), BatchNorm table and the sequence form's history for 32 blocks (wavenet.hip).
+  if (v.C != 16 || v.S != 32 || v.T > 192 || v.T < 1 || v.n_mel > 48 || v.NOUT < 1 || v.NOUT > 16 || v.NB < 1 || v.NB > 32 ||
       v.n_mel != pm.filt.n_mel)
-    return pm.fail(WW_EBLOB, "unsupported Wavenet geometry (T=%d C=%d S=%d)", v.T, v.C, v.S);
+    return pm.fail(WW_EBLOB, "unsupported Wavenet geometry (T=%d C=%d S=%d NB=%d NOUT=%d n_mel=%d)", v.T, v.C, v.S, v.NB, v.NOUT, v.n_mel);
   const int NB = v.NB, C = v.C, S = v.S;
   std::vector<int32_t> dil, order, has_res;
   if (!bv.ints("wave.dilations", NB, dil)) return pm.fail(WW_EBLOB, "blob lacks wave.dilations");
