@@ -141,6 +141,16 @@ int ww_timer_stop(ww_ctx *ctx, float *elapsed_ms); /* synchronises on the stop e
 int ww_model_load(ww_ctx *ctx, const void *blob, size_t len, ww_model **out);
 int ww_model_free(ww_model *model);
 int ww_model_get_info(const ww_model *model, ww_model_info *out);
+/* The detect head of a CRNN (crnn.meta[13] of the blob); a Wavenet answers WW_HEAD_SOFTMAX, which is what its detect graph ends in.
+ *   WW_HEAD_SIGMOID / WW_HEAD_SOFTMAX  Arik_CRNN (wwdetect/CRNN/model.py:21-56): Dense(64, relu) -> Dense(n_out) on the last states
+ *   WW_HEAD_CTC                        Arik_CRNN_CTC (model.py:82-145): one Dense(n_out, softmax) on every step of layer 2, n_out =
+ *                                      labels + blank.  Loaded only at the standard conv geometry, H = 32, 2 <= n_out <= 8; it
+ *                                      runs through the ww_ctc_* family below and through nothing else (every other entry point
+ *                                      that takes a model answers it with WW_EINVAL). */
+#define WW_HEAD_SIGMOID 0
+#define WW_HEAD_SOFTMAX 1
+#define WW_HEAD_CTC 2
+int ww_model_head_kind(const ww_model *model, int32_t *out);
 
 /* Arithmetic of the model contractions.  The reference runs fp32 TFLite kernels; SURVEY 8(d) cfg 3 asks
  * for the Wavenet convs on bf16 MFMA with fp32 accumulate next to an fp32 parity mode.
@@ -315,6 +325,36 @@ int ww_slide_forward(ww_ctx *ctx, const ww_model *model, const float *mel, int64
  * zero padded at the end up to `window` rows (evaluate_tf_lite_opts.py:43-45). */
 int ww_forward_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows,
                            const int64_t *d_win_row, const int32_t *d_win_valid, int32_t n_windows, float *d_out);
+
+/* ---- CTC-trained CRNNs (WW_HEAD_CTC): per-step label posteriors and their greedy decode --------------------------------------
+ * What wwdetect/CRNN/evaluate.py:100-150 (eval_CTC) does with model.predict + K.ctc_decode(greedy=True): a window gives
+ * T' = 19 rows of L posteriors (L = n_out = labels + blank, the blank is class L - 1; dataloader.py:54-62), and its decoded string is,
+ * step by step, the argmax over the classes (lowest index on a tie), kept when it is not the blank and differs from the previous
+ * step's argmax (the blank counts as a previous value: a, blank, a reads "a a").
+ *   labels  [n][max_labels] int32: the first max_labels decoded labels, padded with -1;  1 <= max_labels <= 19
+ *   lengths [n] int32: the whole decoded length (it may exceed max_labels)
+ *   steps   [n][19][L] the posteriors, optional (NULL);  enc [n][19][64] layer 2's step outputs [h_fwd(t) | h_bwd(t)], optional
+ * The decode reads the float32 posteriors as written to `steps`.  (Keras' ctc_decode takes log(y + 1e-7) first: monotone, so it can
+ * only turn a strict order of two posteriors into a tie where they round together; the library decodes the posteriors themselves.)
+ * fp32, standard conv geometry, one model: WW_EINVAL (before anything is written) for a model whose head is not WW_HEAD_CTC, a CTC
+ * model in WW_PRECISION_BF16X3, a NULL required pointer, max_labels outside 1..19.  n = 0: WW_OK, nothing written.
+ * Always crnn_fused_kernel<front>, then gru_tail_ctc_kernel (csrc/crnn.hip). */
+int ww_ctc_forward(ww_ctx *ctx, const ww_model *model, const float *windows, int32_t n, int32_t max_labels, int32_t *labels,
+                   int32_t *lengths, float *steps, float *enc);
+/* Device form with ww_forward_windows_dev's windows: window w reads d_win_valid[w] rows from row d_win_row[w] and is zero padded at
+ * the end - the dataloader's truncate-and-pad of a clip (wwdetect/CRNN/dataloader.py:90-92). */
+int ww_ctc_forward_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                               const int32_t *d_win_valid, int32_t n, int32_t max_labels, int32_t *d_labels, int32_t *d_lengths,
+                               float *d_steps, float *d_enc);
+/* Windows sliding over one mel sequence as in ww_slide_forward (*n_windows of them; labels / lengths / steps sized for that many).
+ * WW_OPT_CRNN_SLIDE_MIN does not apply: crnn_rows_kernel's projected rows differ from the front kernel's in their last bits, and a
+ * window's outputs here are the same bits whether it arrives under a hop or cut out and handed to ww_ctc_forward. */
+int ww_ctc_slide_forward(ww_ctx *ctx, const ww_model *model, const float *mel, int64_t rows, int32_t hop, int32_t max_labels,
+                         int32_t *labels, int32_t *lengths, float *steps, int64_t *n_windows);
+/* The decode alone, on any device posteriors [n][T][L], 1 <= T <= 4096, 2 <= L <= 64 (csrc/ctc_decode.h's function, one thread per
+ * row of the batch); labels / lengths as above with 1 <= max_labels <= T. */
+int ww_ctc_greedy_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, int32_t L, int32_t max_labels, int32_t *d_labels,
+                      int32_t *d_lengths);
 
 /* ww_forward_windows_dev over a model set: window w is evaluated by member win_model[w], all windows in ONE launch (K checkpoints
  * over the same mel - the loop over eval_models of wwdetect/wavenet/evaluate_wavenet.py - are K x n windows that name the same rows).

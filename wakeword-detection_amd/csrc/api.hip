@@ -353,6 +353,14 @@ int ww_model_get_info(const ww_model *m, ww_model_info *out) {
   WW_GUARD_END(m ? m->ctx : nullptr)
 }
 
+int ww_model_head_kind(const ww_model *m, int32_t *out) {
+  WW_GUARD_BEGIN
+  if (!m || !out) return WW_EINVAL;
+  *out = m->kind == WW_KIND_CRNN ? m->crnn.HEAD : WW_HEAD_SOFTMAX;
+  return WW_OK;
+  WW_GUARD_END(m ? m->ctx : nullptr)
+}
+
 int ww_model_set_precision(ww_model *m, int precision) {
   WW_GUARD_BEGIN
   if (!m) return WW_EINVAL;
@@ -612,6 +620,7 @@ int ww_filter_apply(ww_ctx *ctx, const ww_model *m, const float *mag, int64_t n,
 int ww_detect(ww_ctx *ctx, const ww_model *m, const float *enc, int32_t n, float *out) {
   WW_GUARD_BEGIN
   if (!ctx || !m) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (int rc_ctc = ww_crnn_refuse_ctc(ctx, m, "ww_detect")) return rc_ctc;
   if (n < 0) return ww_fail(ctx, WW_EINVAL, "negative row count");
   if (n == 0) return WW_OK;
   if (!enc || !out) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
@@ -705,6 +714,61 @@ static int forward_host(ww_ctx *ctx, const ww_model *m, const float *mel, int64_
   return io.finish();
 }
 
+// ---- CTC-trained CRNNs (include/wwhip.h: ww_ctc_*) ------------------------------------------------------------------------------
+#define WW_CTC_STEPS 19  // the standard geometry's conv positions: a CTC model loads at no other (model_pack.h)
+
+// what the three model entry points of the family refuse, before anything is written
+static int ctc_check(ww_ctx *ctx, const ww_model *m, int32_t max_labels, const void *labels, const void *lengths, const char *what) {
+  if (!ctx || !m) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (int rc = ww_crnn_ctc_check(ctx, m, what)) return rc;
+  if (max_labels < 1 || max_labels > WW_CTC_STEPS) return ww_fail(ctx, WW_EINVAL, "%s: max_labels %d outside 1..%d", what, (int)max_labels, WW_CTC_STEPS);
+  if (!labels || !lengths) return ww_fail(ctx, WW_EINVAL, "%s: labels / lengths are NULL", what);
+  return WW_OK;
+}
+
+// ww_k_crnn_ctc_forward over nw windows, chunk_of(nw) at a time, as forward_chunks: sliding windows (d_row == nullptr) or an explicit
+// list; every output moves on with the windows.  ws: scratch inside the context's device arena, sized for one chunk.
+static int ctc_chunks(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_row, const int32_t *d_valid,
+                      int hop, int valid_const, int64_t nw, void *ws, int max_labels, int32_t *d_labels, int32_t *d_lengths, float *d_steps,
+                      float *d_enc) {
+  const char *lo = (const char *)ctx->dev.ptr, *p = (const char *)ws;
+  const size_t cap = (p >= lo && p <= lo + ctx->dev.cap) ? (size_t)(lo + ctx->dev.cap - p) : 0;
+  const int chunk = chunk_of(nw), L = m->info.n_out;
+  const size_t per_enc = (size_t)m->info.enc_rows * m->info.enc_width;
+  for (int64_t w0 = 0; w0 < nw; w0 += chunk) {
+    const int n = (int)((nw - w0) < chunk ? (nw - w0) : chunk);
+    if (int rc = ww_k_crnn_ctc_forward(ctx, m, d_mel, mel_rows, d_row ? d_row + w0 : nullptr, d_row ? d_valid + w0 : nullptr, d_row ? 0 : w0 * hop,
+                                       hop, valid_const, n, ws, cap, max_labels, d_labels + (size_t)w0 * max_labels, d_lengths + w0,
+                                       d_steps ? d_steps + (size_t)w0 * WW_CTC_STEPS * L : nullptr, d_enc ? d_enc + (size_t)w0 * per_enc : nullptr))
+      return rc;
+  }
+  return WW_OK;
+}
+
+// the host forms: the sequence in, every output the caller asked for out, staged like forward_host's
+static int ctc_host(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t rows, int hop, int64_t nw, int max_labels, int32_t *labels,
+                    int32_t *lengths, float *steps, float *enc) {
+  const int T = m->info.window, F = m->info.n_mel, L = m->info.n_out;
+  const size_t per_enc = (size_t)m->info.enc_rows * m->info.enc_width, n_lab = (size_t)nw * max_labels, n_steps = (size_t)nw * WW_CTC_STEPS * L;
+  WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
+  const size_t b_io = ww_bump::need((size_t)rows * F, 4) + ww_bump::need(n_lab, 4) + ww_bump::need((size_t)nw, 4) +
+                      (steps ? ww_bump::need(n_steps, 4) : 0) + (enc ? ww_bump::need((size_t)nw * per_enc, 4) : 0);
+  const size_t b_ws = ww_crnn_ctc_workspace(m, chunk_of(nw));
+  ww_staged_io io(ctx);
+  int rc = io.init(b_io, b_ws + 1024, nw <= 64);
+  if (rc) return rc;
+  const float *d_mel = io.in(mel, (size_t)rows * F);
+  int32_t *d_lab = io.out<int32_t>(n_lab), *d_len = io.out<int32_t>((size_t)nw);
+  float *d_steps = steps ? io.out<float>(n_steps) : nullptr, *d_enc = enc ? io.out<float>((size_t)nw * per_enc) : nullptr;
+  void *ws = io.scratch(b_ws);
+  if (io.rc) return io.rc;
+  if ((rc = ctc_chunks(ctx, m, d_mel, rows, nullptr, nullptr, hop, T, nw, ws, max_labels, d_lab, d_len, d_steps, d_enc))) return rc;
+  if ((rc = io.fetch(labels, d_lab, n_lab * 4)) || (rc = io.fetch(lengths, d_len, (size_t)nw * 4))) return rc;
+  if (steps && (rc = io.fetch(steps, d_steps, n_steps * 4))) return rc;
+  if (enc && (rc = io.fetch(enc, d_enc, (size_t)nw * per_enc * 4))) return rc;
+  return io.finish();
+}
+
 __global__ void iota_offs_kernel(int64_t *sample_offs, int64_t *frame_offs, int n, int64_t samples, int64_t frames) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i <= n) {
@@ -718,6 +782,7 @@ extern "C" {
 int ww_forward_enc(ww_ctx *ctx, const ww_model *m, const float *windows, int32_t nw, float *out, float *enc) {
   WW_GUARD_BEGIN
   if (!ctx || !m) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (int rc_ctc = ww_crnn_refuse_ctc(ctx, m, "ww_forward")) return rc_ctc;
   if (nw < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
   if (nw == 0) return WW_OK;
   if (!windows || !out) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
@@ -736,6 +801,7 @@ int ww_slide_forward(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t r
                      int64_t *n_windows) {
   WW_GUARD_BEGIN
   if (!ctx || !m || !n_windows) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (int rc_ctc = ww_crnn_refuse_ctc(ctx, m, "ww_slide_forward")) return rc_ctc;
   if (hop <= 0) return ww_fail(ctx, WW_EINVAL, "hop must be positive");
   if (rows < 0) return ww_fail(ctx, WW_EINVAL, "negative row count");
   const int T = m->info.window;
@@ -751,6 +817,7 @@ int ww_forward_windows_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, i
                            const int32_t *d_win_valid, int32_t nw, float *d_out) {
   WW_GUARD_BEGIN
   if (!ctx || !m || !d_mel || !d_out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (int rc_ctc = ww_crnn_refuse_ctc(ctx, m, "ww_forward_windows_dev")) return rc_ctc;
   if (nw < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
   if (nw == 0) return WW_OK;
   if (!d_win_row || !d_win_valid) return ww_fail(ctx, WW_EINVAL, "window descriptors are NULL");
@@ -758,6 +825,63 @@ int ww_forward_windows_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, i
   int rc = ww_ensure(ctx, ctx->dev, model_ws(m, chunk_of(nw)) + 1024, false);
   if (rc) return rc;
   return forward_chunks(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, nw, ctx->dev.ptr, d_out, nullptr, no_enc);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_forward(ww_ctx *ctx, const ww_model *m, const float *windows, int32_t n, int32_t max_labels, int32_t *labels, int32_t *lengths,
+                   float *steps, float *enc) {
+  WW_GUARD_BEGIN
+  if (int rc = ctc_check(ctx, m, max_labels, labels, lengths, "ww_ctc_forward")) return rc;
+  if (n < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
+  if (n == 0) return WW_OK;
+  if (!windows) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
+  // n stacked windows are one mel sequence of n * T rows read with hop = T
+  return ctc_host(ctx, m, windows, (int64_t)n * m->info.window, m->info.window, n, max_labels, labels, lengths, steps, enc);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_slide_forward(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t rows, int32_t hop, int32_t max_labels, int32_t *labels,
+                         int32_t *lengths, float *steps, int64_t *n_windows) {
+  WW_GUARD_BEGIN
+  if (int rc = ctc_check(ctx, m, max_labels, labels, lengths, "ww_ctc_slide_forward")) return rc;
+  if (!n_windows) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (hop <= 0) return ww_fail(ctx, WW_EINVAL, "hop must be positive");
+  if (rows < 0) return ww_fail(ctx, WW_EINVAL, "negative row count");
+  const int T = m->info.window;
+  const int64_t nw = rows >= T ? (rows - T) / hop + 1 : 0;
+  if (nw > 0 && !mel) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
+  *n_windows = nw;
+  if (nw == 0) return WW_OK;
+  return ctc_host(ctx, m, mel, rows, hop, nw, max_labels, labels, lengths, steps, nullptr);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_forward_windows_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                               const int32_t *d_win_valid, int32_t n, int32_t max_labels, int32_t *d_labels, int32_t *d_lengths,
+                               float *d_steps, float *d_enc) {
+  WW_GUARD_BEGIN
+  if (int rc = ctc_check(ctx, m, max_labels, d_labels, d_lengths, "ww_ctc_forward_windows_dev")) return rc;
+  if (n < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
+  if (n == 0) return WW_OK;
+  if (!d_mel) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (!d_win_row || !d_win_valid) return ww_fail(ctx, WW_EINVAL, "window descriptors are NULL");
+  WW_ON_DEVICE(ctx, dev);
+  if (int rc = ww_ensure(ctx, ctx->dev, ww_crnn_ctc_workspace(m, chunk_of(n)) + 1024, false)) return rc;
+  return ctc_chunks(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, n, ctx->dev.ptr, max_labels, d_labels, d_lengths, d_steps, d_enc);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_greedy_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, int32_t L, int32_t max_labels, int32_t *d_labels,
+                      int32_t *d_lengths) {
+  WW_GUARD_BEGIN
+  if (!ctx) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (T < 1 || T > 4096 || L < 2 || L > 64) return ww_fail(ctx, WW_EINVAL, "ww_ctc_greedy_dev: T = %d (1..4096), L = %d (2..64)", (int)T, (int)L);
+  if (max_labels < 1 || max_labels > T) return ww_fail(ctx, WW_EINVAL, "ww_ctc_greedy_dev: max_labels %d outside 1..%d", (int)max_labels, (int)T);
+  if (n < 0 || n > 0x7fffffff) return ww_fail(ctx, WW_EINVAL, "ww_ctc_greedy_dev: sequence count out of range");
+  if (n == 0) return WW_OK;
+  if (!d_steps || !d_labels || !d_lengths) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  WW_ON_DEVICE(ctx, dev);
+  return ww_k_ctc_greedy(ctx, d_steps, n, T, L, max_labels, d_labels, d_lengths);
   WW_GUARD_END(ctx)
 }
 
@@ -792,6 +916,7 @@ int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, 
                             const int32_t *seg_nw, int32_t n_seg, int32_t hop, float *d_out) {
   WW_GUARD_BEGIN
   if (!ctx || !m || !d_mel || !d_out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (int rc_ctc = ww_crnn_refuse_ctc(ctx, m, "ww_forward_segments_dev")) return rc_ctc;
   if (n_seg < 0) return ww_fail(ctx, WW_EINVAL, "negative sequence count");
   if (hop <= 0) return ww_fail(ctx, WW_EINVAL, "hop must be positive");
   if (n_seg == 0) return WW_OK;
@@ -998,6 +1123,7 @@ static int wave_seq_check(ww_ctx *ctx, const wave_seq_request &c, const char *wh
   *slots = 0;
   if (!ctx || !c.m) return ww_fail(ctx, WW_EINVAL, "NULL argument");
   if (c.set && c.set->ctx != ctx) return ww_fail(ctx, WW_EINVAL, "the model set belongs to another context");
+  if (int rc = ww_crnn_refuse_ctc(ctx, c.m, what)) return rc;
   if (int rc = ww_wave_seq_check(ctx, c.m, what)) return rc;
   if (int rc = wave_seq_validate(ctx, c.total_rows, c.row_offs, c.n_seq, c.pool_rows)) return rc;
   if (c.set) {
@@ -1174,6 +1300,7 @@ int ww_clips_forward_dev(ww_ctx *ctx, const ww_model *m, const int16_t *d_pcm, i
                          const ww_frontend_params *fp, float *d_out) {
   WW_GUARD_BEGIN
   if (!ctx || !m || !d_pcm || !d_out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (int rc_ctc = ww_crnn_refuse_ctc(ctx, m, "ww_clips_forward_dev")) return rc_ctc;
   if (n_clips < 0 || samples < 0) return ww_fail(ctx, WW_EINVAL, "negative size");
   if (n_clips == 0) return WW_OK;
   if (n_clips > 65535) return ww_fail(ctx, WW_EINVAL, "at most 65535 clips per call");

@@ -262,6 +262,18 @@ int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int pre
                    const ww_set_ref *set = nullptr, int every_k = 0);
 // does a ww_k_crnn_forward launch of n explicit windows write the tags (the one-kernel forms do)?
 bool ww_crnn_forward_tags(const ww_model *m, int n_windows);
+// CTC-trained CRNNs (WW_HEAD_CTC; crnn.hip).  ww_crnn_refuse_ctc: WW_EINVAL naming the ww_ctc_* family if m is one, WW_OK otherwise -
+// the first statement of every launcher above and of the entry points that would do other work before they reach one.
+// ww_crnn_ctc_check: the other way round (not a CTC CRNN, or one in split-bf16 mode: WW_EINVAL).
+int ww_crnn_refuse_ctc(ww_ctx *ctx, const ww_model *m, const char *what);
+int ww_crnn_ctc_check(ww_ctx *ctx, const ww_model *m, const char *what);
+size_t ww_crnn_ctc_workspace(const ww_model *m, int n_windows);  // n_windows >= 1
+// crnn_fused_kernel<front> + gru_tail_ctc_kernel, for explicit and for sliding windows;
+// d_steps [n][19][L] and d_enc [n][19][64] may be nullptr
+int ww_k_crnn_ctc_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                          const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int n_windows, void *ws, size_t ws_bytes,
+                          int max_labels, int32_t *d_labels, int32_t *d_lengths, float *d_steps, float *d_enc);
+int ww_k_ctc_greedy(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, int max_labels, int32_t *d_labels, int32_t *d_lengths);
 size_t ww_wave_workspace(const ww_model *m, int n_windows);
 int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
                       const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int n_windows, void *ws, size_t ws_bytes,

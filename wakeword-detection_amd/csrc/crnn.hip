@@ -14,6 +14,7 @@
 // Round 1's three-kernel chain (conv5x20_kernel -> gemm_nt_kernel -> gru_head_kernel, 52 us per 256 windows against
 // 34 us fused) and its bf16x6 projection GEMM are gone; their measurements are in DESIGN.md 7.1.
 #include "stream_fe.h"
+#include "ctc_decode.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -1709,6 +1710,130 @@ __global__ __launch_bounds__(128, 4) void gru_tail_kernel(tail_args a, ww_set_re
 }
 
 // ------------------------------------------------------------------------------------------
+// gru_tail_ctc_kernel: gru_tail_kernel for a CTC-trained CRNN (Arik_CRNN_CTC, wwdetect/CRNN/model.py:82-145; WW_HEAD_CTC).  The same
+// two-wave workgroup per window, the same sourcing of the 19 projected rows (its launcher hands it gx1: ww_k_crnn_ctc_forward), layer 1 and layer 2's input projection through the same
+// macros - every step of layer 2 carries the bits the other tails give it.  What differs is behind them:
+//   layer 2 keeps its step outputs (cf_recurrence<true>) in a second sequence buffer seq2[19][GR_SEQ_LD]: row t = [h_fwd(t) | h_bwd(t)],
+//     the backward state at t being the one after steps 18..t (Keras' Bidirectional(return_sequences=True)); optional store enc [n][19][64]
+//   the head is ONE dense layer on every row, z[t][c] = b2[c] + sum_k w2[c][k] seq2[t][k], then the softmax over the L classes of a
+//     row; the 19 x 8 (row, class slot) pairs are dealt over the 128 threads in two passes, eight adjacent lanes per row, which is
+//     the arrangement head_activation's softmax exchanges in; optional store steps [n][19][L]
+//   thread 0 decodes the 19 rows of posteriors as written (ctc_decode.h): labels [n][max_labels], lengths [n]
+// LDS (floats): gx [19][196] | seq1 [20][68] | seq2 [19][68] | h [2][2][2][32] | posteriors [19][8] = 27.1 KB: five workgroups per CU
+// (the head's weights [8][68] take gx's place once layer 2 is done).
+// ------------------------------------------------------------------------------------------
+struct tail_ctc_args {
+  tail_args t;        // t.enc: optional [Nw][OT][2H]; t.out is not used; t.NOUT = L (2..8), the blank is class L - 1
+  float *steps;       // optional [Nw][OT][L]
+  int32_t *labels;    // [Nw][max_labels]
+  int32_t *lengths;   // [Nw]
+  int max_labels;     // 1..OT
+};
+#define GTC_SEQ2 (GT_SEQ + 20 * GR_SEQ_LD)
+#define GTC_HB (GTC_SEQ2 + 19 * GR_SEQ_LD)
+#define GTC_POST (GTC_HB + 2 * 2 * 2 * GR_H)
+#define GTC_SMEM_FLOATS (GTC_POST + 19 * 8)
+static_assert(CV_OT == 19 && GTC_SEQ2 % 4 == 0 && GTC_HB % 4 == 0, "gru_tail_ctc_kernel's LDS layout is written for 19 steps, 16-byte aligned rows");
+
+__global__ __launch_bounds__(128, 4) void gru_tail_ctc_kernel(tail_ctc_args ca) {
+  const tail_args &a = ca.t;
+  constexpr int H = GR_H, OT = CV_OT;
+  __shared__ __align__(16) float sm[GTC_SMEM_FLOATS];
+  float *gxs = sm, *seq1 = sm + GT_SEQ, *seq2 = sm + GTC_SEQ2, *hb = sm + GTC_HB, *post = sm + GTC_POST;
+  const int tid = threadIdx.x, lane = tid & 63, dir = wave_index(tid);  // (scalar)
+  const int j = lane & 15, kk = lane >> 4, unit = lane >> 1, half = lane & 1;
+  const int w = blockIdx.x;
+  gru_w g;
+  gru_load_w(g, a.wh1, a.bh1, dir, unit, half);
+  {
+    // the window's 19 projected rows -> LDS, as gru_tail_kernel stages them
+    constexpr int NQ = OT * 6 * H / 4, NS = (NQ + 127) / 128;
+    int64_t i0w = (int64_t)w * a.hop_g;
+    if (!a.gx1 && a.iI0) i0w = a.iI0[w];
+    f32x4 st[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const int q = min(tid + 128 * s, NQ - 1), t = q / 48, c4 = q - t * 48;
+      const float *row = a.gx1 ? a.gx1 + ((size_t)w * OT + t) * 6 * H
+                       : t == 0 ? a.gxL + (size_t)w * 6 * H
+                       : t == OT - 1 ? a.gxR + (size_t)w * 6 * H
+                                     : a.gxI + ((size_t)i0w + (size_t)(t - 1) * a.eight_g) * 6 * H;
+      st[s] = *(const f32x4 *)(row + c4 * 4);
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const int q = tid + 128 * s, t = q / 48, c4 = q - t * 48;
+      if (q < NQ) *(f32x4 *)(&gxs[t * GR_GX_LD + c4 * 4]) = st[s];
+    }
+  }
+  CLEAR_SEQ_H(seq1, 20, hb, 128)
+  __syncthreads();
+  cf_recurrence<true>(g, gxs, hb + dir * 2 * H, seq1, dir, unit, half);
+  __syncthreads();
+  // layer-2 input projection: wave d owns n-tiles 6 d .. 6 d + 5, in two passes of three (gru_tail_kernel's)
+#pragma unroll 1
+  for (int pass = 0; pass < 2; ++pass) {
+    const int nt0 = dir * 6 + pass * 3;
+    float4 bq[4][3];
+    L2_LOAD_W(bq, a.wx2s, nt0)
+    float bb2[3];
+    L2_LOAD_BIAS(bb2, a.bx2, nt0)
+    L2_PROJECT(bq, bb2, j < 3 ? 16 + j : 19 /* row 19 is zero */, nt0, __syncthreads();)
+  }
+  gru_w g2;
+  gru_load_w(g2, a.wh2, a.bh2, dir, unit, half);
+  __syncthreads();
+  // the head's weights [L <= 8][64]: one 16-byte load per thread, on its way during the recurrence (thread tid: row tid / 16)
+  const float4 w2q = tid * 4 < a.NOUT * 2 * H ? ((const float4 *)a.w2)[tid] : make_float4(0.f, 0.f, 0.f, 0.f);
+  // layer 2, every step kept: each (row, direction half) of seq2 is written exactly once, so seq2 needs no clearing
+  cf_recurrence<true>(g2, gxs, hb + (2 + dir) * 2 * H, seq2, dir, unit, half);
+  __syncthreads();
+  // gx is dead: the head's weights take its place, rows GR_SEQ_LD apart (eight rows 64 apart would share their banks)
+  float *w2s = gxs;
+  *(float4 *)(&w2s[(tid >> 4) * GR_SEQ_LD + (tid & 15) * 4]) = w2q;
+  if (a.enc)
+    for (int i = tid; i < OT * 2 * H; i += 128) a.enc[(size_t)w * OT * 2 * H + i] = seq2[(i >> 6) * GR_SEQ_LD + (i & 63)];
+  __syncthreads();
+  // head: slot p = tid + 128 pass is (row p / 8, class p % 8); slots past row 18 recompute row 18 and store nothing (every lane of a
+  // wave takes part in the softmax's exchanges).  One fmaf chain in k order from zero, the bias added last - the association of the
+  // other heads' last layer (cf_phases_d_to_g, gru_tail_kernel, crnn_detect_kernel) - then head_activation's softmax: one definition.
+  {
+    const int L = a.NOUT, o = tid & 7;
+    const float4 *wr = (const float4 *)(w2s + o * GR_SEQ_LD);  // (rows L..7 are zeros)
+    const float b2v = a.b2[o < L ? o : 0];
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+      const int p = tid + 128 * pass, t = min(p >> 3, OT - 1);
+      float y = 0.f;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const float4 wv = wr[q];
+        const float4 sv = *(const float4 *)(&seq2[t * GR_SEQ_LD + q * 4]);
+        y = fmaf(wv.x, sv.x, y); y = fmaf(wv.y, sv.y, y);
+        y = fmaf(wv.z, sv.z, y); y = fmaf(wv.w, sv.w, y);
+      }
+      y += b2v;
+      const float pr = head_activation(y, o, L, 1 /* softmax */);
+      if (o < L && (p >> 3) < OT) {
+        post[t * 8 + o] = pr;
+        if (ca.steps) ca.steps[((size_t)w * OT + t) * L + o] = pr;
+      }
+    }
+  }
+  __syncthreads();
+  // greedy decode of the posteriors as written
+  if (tid == 0)
+    ca.lengths[w] = ww_ctc_greedy_row(post, OT, a.NOUT, 8, ca.labels + (size_t)w * ca.max_labels, ca.max_labels);
+}
+
+// the decode alone over [n][T][L] posteriors in global memory: one thread per sequence
+__global__ __launch_bounds__(64) void ctc_greedy_kernel(const float *steps, long long n, int T, int L, int max_labels, int32_t *labels,
+                                                        int32_t *lengths) {
+  const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (i < n) lengths[i] = ww_ctc_greedy_row(steps + (size_t)i * T * L, T, L, L, labels + (size_t)i * max_labels, max_labels);
+}
+
+// ------------------------------------------------------------------------------------------
 // gru_tail16_kernel: the same work as gru_tail_kernel for SIXTEEN windows per two-wave workgroup (wave 0 forward, wave 1
 // backward), with the recurrent mat-vec of the sixteen windows as one matrix product per step on v_mfma_f32_16x16x4_f32:
 //   [16 windows x 32 units] x W_h^T [32 x 96]  =  6 n-tiles (z, r, c  x  unit half) x 8 k-steps = 48 MFMAs.
@@ -2032,7 +2157,18 @@ __global__ __launch_bounds__(64) void crnn_detect_kernel(const float *enc, const
   if (lane < NOUT) out[(size_t)w * NOUT + lane] = p;
 }
 
+// A CTC-trained CRNN (WW_HEAD_CTC) has no Dense(64, relu) -> Dense(n_out) head on its last states: every launcher of this file that
+// evaluates that head answers it here, before anything is enqueued (ww_k_crnn_ctc_forward below is its way in).  The zero-filled w1 / b1
+// of its device block (model_pack.h) are the second line of defence, not the first.
+int ww_crnn_refuse_ctc(ww_ctx *ctx, const ww_model *m, const char *what) {
+  if (m && m->kind == WW_KIND_CRNN && m->crnn.HEAD == WW_HEAD_CTC)
+    return ww_fail(ctx, WW_EINVAL, "%s: the model is a CTC-trained CRNN (per-step label posteriors, no wake-word posterior): it runs through "
+                   "ww_ctc_forward, ww_ctc_forward_windows_dev and ww_ctc_slide_forward only", what);
+  return WW_OK;
+}
+
 int ww_k_crnn_detect(ww_ctx *ctx, const ww_model *m, const float *d_enc, int nw, float *d_out) {
+  if (int rc = ww_crnn_refuse_ctc(ctx, m, "ww_k_crnn_detect")) return rc;
   if (nw <= 0) return WW_OK;
   const ww_crnn_dev &c = m->crnn;
   ww_launch_scope scope(ctx, "crnn_detect_kernel");
@@ -2226,6 +2362,7 @@ bool ww_crnn_stream_capable(const ww_model *m) { return m->kind == WW_KIND_CRNN 
 // every_k member slots on every stream): 2 S every_k workgroups of the ALL form, set->ids a table of S every_k members
 int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, float *d_gxc, const ww_tick_tag &tag,
                    const ww_set_ref *set, int every_k) {
+  if (int rc = ww_crnn_refuse_ctc(ctx, m, "ww_k_crnn_tick")) return rc;
   const ww_crnn_dev &c = m->crnn;
   const ww_filter_dev &f = m->filt;
   if (c.generic || f.n_mel != CV_NMEL || fe.hop != 160)
@@ -2259,6 +2396,7 @@ int ww_k_crnn_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int pre
 int ww_k_crnn_stream_forward(ww_ctx *ctx, const ww_model *m, const float *d_hist, int64_t hist_rows, const int64_t *d_win_row,
                              const int32_t *d_win_valid, const int32_t *d_win_aux, float *d_gxc, int nw, float *d_out,
                              const ww_tick_tag *tag, const ww_set_ref *set) {
+  if (int rc = ww_crnn_refuse_ctc(ctx, m, "ww_k_crnn_stream_forward")) return rc;
   if (nw <= 0) return WW_OK;
   const ww_crnn_dev &c = m->crnn;
   if (c.generic) return ww_fail(ctx, WW_EINVAL, "streaming CRNN kernel: standard conv geometry only");
@@ -2354,6 +2492,7 @@ bool ww_crnn_set_segments_rows_form(const ww_model *m, int hop, int64_t W) { ret
 
 int ww_k_crnn_segments_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
                                const int32_t *seg_nw, int n_seg, int hop, float *d_out, const ww_crnn_set_call *sc) {
+  if (int rc = ww_crnn_refuse_ctc(ctx, m, "ww_k_crnn_segments_forward")) return rc;
   const ww_crnn_dev &c = m->crnn;
   const int g = crnn_gcd8(hop), n_ids = sc ? sc->n_ids : 1;
   const int64_t cap = sc ? std::max<int64_t>(WW_SEG_GROUP / n_ids, 1) : WW_SEG_GROUP;
@@ -2417,6 +2556,7 @@ bool ww_crnn_forward_tags(const ww_model *m, int nw) {
 int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
                       const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int nw, void *ws, size_t ws_bytes,
                       float *d_out, float *d_enc, const ww_tick_tag *tag, const ww_set_ref *set) {
+  if (int rc = ww_crnn_refuse_ctc(ctx, m, "ww_k_crnn_forward")) return rc;
   if (nw <= 0) return WW_OK;
   const ww_crnn_dev &c = m->crnn;
   win_addr wa = {d_win_row, d_win_valid, row0, hop, valid_const, mel_rows};
@@ -2496,6 +2636,66 @@ int ww_k_crnn_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_
     ww_launch_scope scope(ctx, bf16 ? "crnn_fused_kernel<bf16x3>" : "crnn_fused_kernel");
     if (bf16) hipLaunchKernelGGL(crnn_fused_bf16_kernel<false>, dim3(nw), dim3(CF_THREADS), CFB_SMEM_BYTES, ctx->stream, a);
     else hipLaunchKernelGGL(crnn_fused_kernel<false>, dim3(nw), dim3(CF_THREADS), CF_FUSED_SMEM_BYTES, ctx->stream, a, ww_set_ref{});
+  }
+  WW_HIP(ctx, hipGetLastError());
+  return WW_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// A CTC-trained CRNN's launches: always crnn_fused_kernel<front> (fp32), then gru_tail_ctc_kernel - for sliding windows too, whatever
+// WW_OPT_CRNN_SLIDE_MIN says.  crnn_rows_kernel's projected rows are not the front kernel's bits (it deals every position to a
+// 16-row MFMA tile, the front kernel rows 16..18 of a window to 4x4x1 blocks whose partial sums meet at the end: the posteriors of
+// the two forms differ by up to 4e-7, and tests/test_gpu_parity.py allows the other heads 2e-6 there).  A decoded label is an argmax:
+// a window must read the same whether it arrives in a list or under a hop, so there is ONE front.
+// ------------------------------------------------------------------------------------------
+int ww_crnn_ctc_check(ww_ctx *ctx, const ww_model *m, const char *what) {
+  if (m->kind != WW_KIND_CRNN || m->crnn.HEAD != WW_HEAD_CTC)
+    return ww_fail(ctx, WW_EINVAL, "%s: the model is not a CTC-trained CRNN (WW_HEAD_CTC); ww_forward and its family run it", what);
+  if (m->crnn.generic || m->crnn.H != GR_H || m->crnn.OT != CV_OT || m->crnn.NOUT < 2 || m->crnn.NOUT > 8)
+    return ww_fail(ctx, WW_EINTERNAL, "%s: a CTC model of a geometry the loader should have refused", what);
+  if (m->precision != WW_PRECISION_FP32) return ww_fail(ctx, WW_EINVAL, "%s: a CTC-trained CRNN runs in WW_PRECISION_FP32 only", what);
+  return WW_OK;
+}
+
+// scratch of a launch of nw >= 1 windows (the projected rows; the model's options do not move it)
+size_t ww_crnn_ctc_workspace(const ww_model *m, int nw) { return ww_bump::need((size_t)nw * m->crnn.OT * 6 * m->crnn.H, 4) + 2048; }
+
+int ww_k_crnn_ctc_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                          const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int nw, void *ws, size_t ws_bytes,
+                          int max_labels, int32_t *d_labels, int32_t *d_lengths, float *d_steps, float *d_enc) {
+  if (int rc = ww_crnn_ctc_check(ctx, m, "ww_k_crnn_ctc_forward")) return rc;
+  if (max_labels < 1 || max_labels > CV_OT || !d_labels || !d_lengths) return ww_fail(ctx, WW_EINVAL, "CTC launch: max_labels %d / NULL output", max_labels);
+  if (nw <= 0) return WW_OK;
+  const ww_crnn_dev &c = m->crnn;
+  const size_t need = ww_crnn_ctc_workspace(m, nw);
+  if (need > ws_bytes) return ww_fail(ctx, WW_EINVAL, "CTC launch of %d windows needs %zu bytes of scratch, the caller reserved %zu", nw, need, ws_bytes);
+  const win_addr wa = {d_win_row, d_win_valid, row0, hop, valid_const, mel_rows};
+  fused_args a = crnn_fused_args(c, d_mel, wa, nullptr, nullptr);
+  ww_bump b(ws, ws_bytes);
+  a.gx_out = b.take<float>((size_t)nw * c.OT * 6 * c.H);
+  {
+    ww_launch_scope scope(ctx, "crnn_fused_kernel<front>");
+    hipLaunchKernelGGL(crnn_fused_kernel<true>, dim3(nw), dim3(CF_THREADS), CF_FUSED_SMEM_BYTES, ctx->stream, a, ww_set_ref{});
+  }
+  tail_ctc_args ca = {};
+  ca.t = crnn_tail_args(c);
+  ca.t.gx1 = a.gx_out;
+  ca.t.enc = d_enc;
+  ca.steps = d_steps; ca.labels = d_labels; ca.lengths = d_lengths; ca.max_labels = max_labels;
+  {
+    ww_launch_scope scope(ctx, "gru_tail_ctc_kernel");
+    hipLaunchKernelGGL(gru_tail_ctc_kernel, dim3((unsigned)nw), dim3(128), 0, ctx->stream, ca);
+  }
+  WW_HIP(ctx, hipGetLastError());
+  return WW_OK;
+}
+
+int ww_k_ctc_greedy(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, int max_labels, int32_t *d_labels, int32_t *d_lengths) {
+  if (n <= 0) return WW_OK;
+  {
+    ww_launch_scope scope(ctx, "ctc_greedy_kernel");
+    hipLaunchKernelGGL(ctc_greedy_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_steps, (long long)n, T, L, max_labels,
+                       d_labels, d_lengths);
   }
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;

@@ -295,6 +295,16 @@ inline int pack_crnn(ww_packed_model &pm, const blob_view &bv) {
   c.generic = !(c.C == 32 && c.n_mel == 40 && c.T == 151 && c.KF == 5 && c.KT == 20 && c.SF == 2 && c.ST == 8 && c.PF == 1 &&
                 c.PT == 6 && c.OF == 20 && c.OT == 19);
   c.FEATP = (c.OF * c.C + 63) / 64 * 64;
+  if (!in(c.HEAD, WW_HEAD_SIGMOID, WW_HEAD_CTC)) return pm.fail(WW_EBLOB, "unknown CRNN head kind %d (0 sigmoid, 1 softmax, 2 CTC)", c.HEAD);
+  if (c.HEAD == WW_HEAD_CTC) {
+    // gru_tail_ctc_kernel (crnn.hip) is built for the 19 steps of the standard geometry and deals its softmax rows to groups of eight
+    // lanes; a CTC output needs a label and the blank.  Whatever loads, ww_ctc_* can launch.
+    std::vector<float> none;
+    if (c.generic) return pm.fail(WW_EBLOB, "a CTC head (HEAD = 2) takes the standard conv geometry only (19 steps of 640 features)");
+    if (!in(c.NOUT, 2, 8)) return pm.fail(WW_EBLOB, "a CTC head (HEAD = 2) has 2..8 classes (labels + blank), not %d", c.NOUT);
+    if (bv.words("crnn.head_w1", none) || bv.words("crnn.head_b1", none))
+      return pm.fail(WW_EBLOB, "a CTC head (HEAD = 2) has one dense layer: the blob carries crnn.head_w1 / crnn.head_b1");
+  }
   NEED_F(cw, "crnn.conv_w", (size_t)c.C * K);
   NEED_F(cb, "crnn.conv_b", c.C);
   if (!c.generic) {
@@ -385,12 +395,17 @@ inline int pack_crnn(ww_packed_model &pm, const blob_view &bv) {
   if ((rc = cat2("crnn.g2f.bx", "crnn.g2b.bx", G, v))) return rc; pm.add("crnn.bx2", v);
   if ((rc = cat2("crnn.g2f.wh", "crnn.g2b.wh", (size_t)G * c.H, v))) return rc; pm.add("crnn.wh2", v);
   if ((rc = cat2("crnn.g2f.bh", "crnn.g2b.bh", G, v))) return rc; pm.add("crnn.bh2", v);
-  NEED_F(w1, "crnn.head_w1", in2 * in2);
-  NEED_F(b1, "crnn.head_b1", in2);
+  // a CTC head has no first layer: its w1 / b1 are zeros of the same size, so that no kernel argument of any form is a null pointer
+  // (the launchers refuse a CTC model long before: crnn.hip, ww_crnn_refuse_ctc)
+  std::vector<float> w1(in2 * in2, 0.f), b1(in2, 0.f);
+  if (c.HEAD != WW_HEAD_CTC) {
+    if ((rc = bv.floats(pm, "crnn.head_w1", in2 * in2, w1)) || (rc = bv.floats(pm, "crnn.head_b1", in2, b1))) return rc;
+  }
   NEED_F(w2, "crnn.head_w2", (size_t)c.NOUT * in2);
   NEED_F(b2, "crnn.head_b2", c.NOUT);
   pm.add("crnn.w1", w1); pm.add("crnn.b1", b1); pm.add("crnn.w2", w2); pm.add("crnn.b2", b2);
-  pm.info.window = c.T; pm.info.n_out = c.NOUT; pm.info.enc_rows = 1; pm.info.enc_width = 2 * c.H;
+  pm.info.window = c.T; pm.info.n_out = c.NOUT; pm.info.enc_width = 2 * c.H;
+  pm.info.enc_rows = c.HEAD == WW_HEAD_CTC ? c.OT : 1;  // (a CTC encoder returns the whole sequence)
   return WW_OK;
 }
 

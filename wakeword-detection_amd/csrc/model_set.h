@@ -100,6 +100,9 @@ static inline int ww_set_check(const ww_set_member *mem, int32_t n, const void *
     if (m.kind == WW_KIND_CRNN ? !ww_set_same_crnn(*m.crnn, *m0.crnn) : !ww_set_same_wave(*m.wave, *m0.wave))
       return ww_set_refuse(err, cap, "member %d's geometry differs from member 0's%s", k,
                            m.kind == WW_KIND_WAVENET ? " (sizes, dilations, block order or residual convs)" : "");
+    // (behind the comparison: a member whose head alone differs from member 0's is a geometry mismatch like any other)
+    if (m.kind == WW_KIND_CRNN && m.crnn->HEAD == WW_HEAD_CTC)
+      return ww_set_refuse(err, cap, "member %d is a CTC-trained CRNN: it runs alone, through ww_ctc_forward and its family, not in a model set", k);
     if (m.block_bytes != m0.block_bytes)
       return ww_set_refuse(err, cap, "member %d's device block has %zu bytes, member 0's %zu", k, m.block_bytes, m0.block_bytes);
     if (!ww_set_same_filter(*m.filt, *m0.filt) || *m.filt_image != *m0.filt_image)

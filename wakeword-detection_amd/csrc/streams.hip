@@ -419,6 +419,7 @@ int ww_stream_destroy(ww_streams *st) {
 // ww_stream_create_set_all (every_k > 0: stream_model = the every_k member slots, checked by the caller, or nullptr)
 static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model_set *set, const int32_t *stream_model, int32_t S,
                               const ww_frontend_params *fp, uint32_t flags, ww_streams **out, int every_k = 0) {
+  if (int rc = ww_crnn_refuse_ctc(ctx, model, "ww_stream_create")) return rc;
   if (flags & ~(uint32_t)(WW_STREAM_FULL_RECOMPUTE | WW_STREAM_TWO_LAUNCH | WW_STREAM_SYNC_WAIT | WW_STREAM_CAUSAL))
     return ww_fail(ctx, WW_EINVAL, "unknown stream flags 0x%x", flags);
   const bool causal = (flags & WW_STREAM_CAUSAL) != 0;

@@ -75,9 +75,12 @@ class Engine:
     """A model directory (filter/encode/detect ``.tflite``) resident on one MI355X."""
 
     def __init__(self, model_dir: str, device: int = 0, ctx: Optional[_lib.Context] = None,
-                 precision: str = "fp32", weights_fp16: bool = False) -> None:
+                 precision: str = "fp32", weights_fp16: bool = False, bundle: Optional["W.ModelBundle"] = None) -> None:
+        """``bundle``: the model as a :class:`wwhip.weights.ModelBundle` instead of a directory to read (``model_dir`` is then only a
+        name) - how a CTC-trained CRNN arrives (``weights.crnn_ctc_params``)."""
         self._weights_fp16 = bool(weights_fp16)
-        self.bundle = W.load_model_dir(model_dir)
+        self._given_bundle = bundle
+        self.bundle = bundle if bundle is not None else W.load_model_dir(model_dir)
         if weights_fp16:  # the reference's float16-quantised model variant (weights.quantize_fp16)
             self.bundle = W.quantize_fp16(self.bundle)
         self.blob = W.pack_blob(self.bundle)
@@ -95,6 +98,9 @@ class Engine:
         self.n_bins = info.n_bins
         self.n_out = info.n_out
         self.enc_shape = (info.enc_rows, info.enc_width)
+        hk = C.c_int32(0)
+        _lib.raise_for(self._lib.ww_model_head_kind(h, C.byref(hk)), self.ctx.handle)
+        self.head_kind = int(hk.value)  # _lib.HEAD_SIGMOID | HEAD_SOFTMAX | HEAD_CTC
         self.model_dir = model_dir
         _lib.register("models", self)
         self._options = {"crnn_split_at": 1024, "crnn_slide_min": 64, "crnn_tail_mfma": 1, "wavenet_rowmajor": 0, "wave_seq_segment": 0}  # the library's defaults
@@ -154,7 +160,7 @@ class Engine:
         e = lanes.get(k)
         if e is None or e.handle is None:
             e = lanes[k] = Engine(self.model_dir, device=self.ctx.device, ctx=_lib.Context(self.ctx.device), precision=self.precision,
-                                  weights_fp16=self._weights_fp16)
+                                  weights_fp16=self._weights_fp16, bundle=self._given_bundle)
         if e.precision != self.precision:
             e.set_precision(self.precision)
         for key, v in self._options.items():
@@ -267,6 +273,72 @@ class Engine:
         self._chk(self._lib.ww_slide_forward(self.ctx.handle, self._model, _lib.ptr(m), rows, int(hop), _lib.ptr(out), C.byref(got)))
         assert got.value == nw
         return out
+
+    # ------------------------------------------------------------------ CTC-trained CRNNs (include/wwhip.h: ww_ctc_*)
+    @property
+    def is_ctc(self) -> bool:
+        return self.head_kind == _lib.HEAD_CTC
+
+    CTC_STEPS = 19  # rows of posteriors per window: the standard geometry's conv positions
+    CTC_OUTPUTS = ("labels", "steps", "enc")
+
+    def _ctc_want(self, want, max_labels: int, allowed) -> None:
+        bad = [k for k in want if k not in allowed]
+        if bad:
+            raise ValueError(f"want takes {allowed}, not {bad}")
+        if not 1 <= int(max_labels) <= self.CTC_STEPS:
+            raise ValueError(f"max_labels {max_labels} outside 1..{self.CTC_STEPS}")
+
+    def ctc_forward(self, windows: np.ndarray, max_labels: int = 2, want: Sequence[str] = ("labels",)):
+        """``[B, window, 40]`` -> :class:`wwhip.ctc.CtcResult`: the greedy-CTC-decoded labels of every window (``labels [B, max_labels]``
+        padded with -1, ``lengths [B]`` the whole decoded length), and on request (``want``) the posteriors ``steps [B, 19, n_out]``
+        and layer 2's step outputs ``enc [B, 19, 64]`` (``ww_ctc_forward``; wwdetect/CRNN/evaluate.py:100-150)."""
+        from .ctc import CtcResult
+        self._ctc_want(want, max_labels, self.CTC_OUTPUTS)
+        w = np.ascontiguousarray(windows, dtype=np.float32)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.shape[1] != self.window or w.shape[2] != self.n_mel:
+            raise ValueError(f"Cannot set tensor: Dimension mismatch. Got {tuple(w.shape[1:])} but expected "
+                             f"{(self.window, self.n_mel)} per window")
+        n = w.shape[0]
+        labels, lengths = np.full((n, int(max_labels)), -1, np.int32), np.zeros(n, np.int32)
+        steps = np.empty((n, self.CTC_STEPS, self.n_out), np.float32) if "steps" in want else None
+        enc = np.empty((n, self.CTC_STEPS, self.enc_shape[1]), np.float32) if "enc" in want else None
+        self._chk(self._lib.ww_ctc_forward(self.ctx.handle, self._model, _lib.ptr(w), n, int(max_labels), _lib.ptr(labels), _lib.ptr(lengths),
+                                           _lib.ptr(steps), _lib.ptr(enc)))
+        return CtcResult(labels, lengths, steps, enc)
+
+    def ctc_slide_forward(self, mel: np.ndarray, hop: int = 2, max_labels: int = 2, want: Sequence[str] = ("labels",)):
+        """Windows sliding over one ``[rows, 40]`` sequence (``ww_ctc_slide_forward``); ``want``: ``"labels"``, ``"steps"``."""
+        from .ctc import CtcResult
+        self._ctc_want(want, max_labels, ("labels", "steps"))
+        m = np.ascontiguousarray(mel, dtype=np.float32)
+        if m.ndim != 2 or m.shape[1] != self.n_mel:
+            raise ValueError(f"mel must be [rows, {self.n_mel}]")
+        if hop < 1:
+            raise ValueError("hop must be positive")
+        rows = m.shape[0]
+        nw = (rows - self.window) // hop + 1 if rows >= self.window else 0
+        labels, lengths = np.full((nw, int(max_labels)), -1, np.int32), np.zeros(nw, np.int32)
+        steps = np.empty((nw, self.CTC_STEPS, self.n_out), np.float32) if "steps" in want else None
+        got = C.c_int64(0)
+        self._chk(self._lib.ww_ctc_slide_forward(self.ctx.handle, self._model, _lib.ptr(m), rows, int(hop), int(max_labels), _lib.ptr(labels),
+                                                 _lib.ptr(lengths), _lib.ptr(steps), C.byref(got)))
+        assert got.value == nw
+        return CtcResult(labels, lengths, steps, None)
+
+    def ctc_forward_windows_dev(self, d_mel_ptr: int, mel_rows: int, d_win_row_ptr: int, d_win_valid_ptr: int, n_windows: int,
+                                max_labels: int, d_labels_ptr: int, d_lengths_ptr: int, d_steps_ptr: int = 0, d_enc_ptr: int = 0) -> None:
+        """``ww_ctc_forward_windows_dev`` on device addresses (enqueued on the context's stream; 0 = no such output)."""
+        self._chk(self._lib.ww_ctc_forward_windows_dev(self.ctx.handle, self._model, _vp(d_mel_ptr), int(mel_rows), _vp(d_win_row_ptr),
+                                                       _vp(d_win_valid_ptr), int(n_windows), int(max_labels), _vp(d_labels_ptr),
+                                                       _vp(d_lengths_ptr), _vp(d_steps_ptr), _vp(d_enc_ptr)))
+
+    def ctc_greedy_dev(self, d_steps_ptr: int, n: int, T: int, L: int, max_labels: int, d_labels_ptr: int, d_lengths_ptr: int) -> None:
+        """``ww_ctc_greedy_dev``: the decode alone on device posteriors ``[n, T, L]`` (any model; the context is this engine's)."""
+        self._chk(self._lib.ww_ctc_greedy_dev(self.ctx.handle, _vp(d_steps_ptr), int(n), int(T), int(L), int(max_labels), _vp(d_labels_ptr),
+                                              _vp(d_lengths_ptr)))
 
     SEQUENCE_OUTPUTS = ("enc", "logits", "post_frames", "post")
 

@@ -1130,6 +1130,64 @@ def models_predict(engine: Engine, X: np.ndarray, threshold: float = 0.5) -> Tup
     return [1 if p >= threshold else 0 for p in post], post
 
 
+def ctc_statistics(y_true, y_pred) -> dict:
+    """The counts and ratios ``eval_CTC`` prints (``wwdetect/CRNN/evaluate.py:140-150``: tp, fp, tn, fn, precision, recall, and
+    sklearn's balanced accuracy - the mean of the recalls of the classes that occur) for 0 / 1 classes.  A ratio whose denominator
+    is zero is 0.0, as Keras' metrics give it."""
+    t, p = np.asarray(y_true).astype(bool), np.asarray(y_pred).astype(bool)
+    if t.shape != p.shape or t.ndim != 1:
+        raise ValueError("y_true and y_pred must be two vectors of one length")
+    tp, fp = int(np.sum(t & p)), int(np.sum(~t & p))
+    tn, fn = int(np.sum(~t & ~p)), int(np.sum(t & ~p))
+    ratio = lambda a, b: float(a) / float(b) if b else 0.0
+    recalls = [ratio(hit, n) for hit, n in ((tp, tp + fn), (tn, tn + fp)) if n]
+    return {"tp": tp, "fp": fp, "tn": tn, "fn": fn, "precision": ratio(tp, tp + fp), "recall": ratio(tp, tp + fn),
+            "balanced accuracy": float(np.mean(recalls)) if recalls else 0.0}
+
+
+def evaluate_ctc(engine: Engine, features: Sequence[np.ndarray], is_hotword: Sequence[int], target: Sequence[int] = (1, 2)) -> dict:
+    """``eval_CTC`` (``wwdetect/CRNN/evaluate.py:100-150``) for a CTC-trained CRNN over the records of an H5 feature file:
+    ``features`` is a list of ``[frames_i, n_mel]`` arrays (what ``DatasetFilter`` writes), ``is_hotword`` their attribute.  One
+    upload of all rows, ONE ``ww_ctc_forward_windows_dev`` over descriptors - one window per clip, truncated to the model's window
+    and zero-padded at the end on the device (``dataloader.py:90-92``) - and one download of the decoded labels.  A clip is a wake
+    word iff its first ``len(target)`` decoded labels are ``target`` ([HEY][SNIPS]).  Returns :func:`ctc_statistics` plus
+    ``"decoded"`` (the per-clip strings), ``"predicted"``, ``"labels"`` and ``"lengths"``."""
+    import torch
+
+    from . import ctc
+    if not getattr(engine, "is_ctc", False):
+        raise ValueError("evaluate_ctc takes a CTC-trained CRNN (Engine.is_ctc); evaluate_testset and models_predict run the others")
+    n, T, F = len(features), engine.window, engine.n_mel
+    if len(is_hotword) != n:
+        raise ValueError("one is_hotword per record")
+    k = max(len(target), 1)
+    feats = [np.ascontiguousarray(f, dtype=np.float32) for f in features]
+    for f in feats:
+        if f.ndim != 2 or f.shape[1] != F:
+            raise ValueError(f"every record must be [frames, {F}], got {f.shape}")
+    rows = np.array([f.shape[0] for f in feats], np.int64)
+    win_row = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64) if n else np.zeros(0, np.int64)
+    win_valid = np.minimum(rows, T).astype(np.int32)
+    labels, lengths = np.full((n, k), -1, np.int32), np.zeros(n, np.int32)
+    if n:
+        total = int(rows.sum())
+        dev = torch.device("cuda", engine.ctx.device)
+        mel = np.concatenate(feats) if total else np.zeros((0, F), np.float32)
+        d_mel = torch.empty((max(total, 1), F), dtype=torch.float32, device=dev)
+        d_mel[:total] = torch.from_numpy(mel).to(dev)
+        d_row, d_valid = torch.from_numpy(win_row).to(dev), torch.from_numpy(win_valid).to(dev)
+        d_lab = torch.empty((n, k), dtype=torch.int32, device=dev)
+        d_len = torch.empty(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # (torch's stream is not the context's)
+        engine.ctc_forward_windows_dev(d_mel.data_ptr(), total, d_row.data_ptr(), d_valid.data_ptr(), n, k, d_lab.data_ptr(), d_len.data_ptr())
+        engine.ctx.synchronize()
+        labels, lengths = d_lab.cpu().numpy(), d_len.cpu().numpy()
+    pred = ctc.is_wakeword(labels, lengths, target)
+    out = ctc_statistics(np.asarray(is_hotword).astype(bool), pred)
+    out.update(decoded=[ctc.label_string(labels[i], lengths[i]) for i in range(n)], predicted=pred, labels=labels, lengths=lengths)
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # Whole-test-set evaluation on in-memory clips (SURVEY 8d cfg 1 / cfg 4): the a17 flow (one window
 # per clip) and the a14-a16 flow (sliding hop 2, max per positive clip, negatives as one stream,

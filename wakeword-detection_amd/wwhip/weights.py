@@ -34,6 +34,7 @@ BLOB_VERSION = 1
 
 HEAD_SIGMOID = 0
 HEAD_SOFTMAX = 1
+HEAD_CTC = 2  # Arik_CRNN_CTC (wwdetect/CRNN/model.py:82-145): one TimeDistributed(Dense(labels + blank, softmax)) over layer 2's steps
 
 
 class GraphPatternError(ValueError):
@@ -162,11 +163,11 @@ class CrnnParams:
     out_t: int
     gru1: Tuple[GruDir, GruDir]  # (forward, backward)
     gru2: Tuple[GruDir, GruDir]
-    head_w1: np.ndarray  # [64, 64]
-    head_b1: np.ndarray
-    head_w2: np.ndarray  # [n_out, 64]
+    head_w1: Optional[np.ndarray]  # [64, 64]; None for HEAD_CTC
+    head_b1: Optional[np.ndarray]
+    head_w2: np.ndarray  # [n_out, 64]; HEAD_CTC: [L, 2H], L = labels + blank (the blank is the last class)
     head_b2: np.ndarray
-    head_kind: int  # HEAD_SIGMOID | HEAD_SOFTMAX
+    head_kind: int  # HEAD_SIGMOID | HEAD_SOFTMAX | HEAD_CTC
 
     @property
     def n_out(self) -> int:
@@ -175,6 +176,18 @@ class CrnnParams:
     @property
     def units(self) -> int:
         return int(self.gru1[0].w_h.shape[1])
+
+
+def crnn_ctc_params(base: CrnnParams, w, b) -> CrnnParams:
+    """``base`` with its detect head swapped for the CTC head of ``Arik_CRNN_CTC``: ``w`` [L, 2H] and ``b`` [L] of the
+    per-step dense layer, L = labels + blank.  How a caller with weights in hand makes a CTC bundle (no reader of a CTC
+    ``.tflite`` / ``.h5`` exists: DESIGN.md 8)."""
+    import dataclasses
+    w = np.ascontiguousarray(w, np.float32)
+    b = np.ascontiguousarray(b, np.float32)
+    if w.ndim != 2 or w.shape[1] != 2 * base.units or b.shape != (w.shape[0],):
+        raise ValueError(f"CTC head must be w [L, {2 * base.units}] and b [L], got {w.shape} and {b.shape}")
+    return dataclasses.replace(base, head_w1=None, head_b1=None, head_w2=w, head_b2=b, head_kind=HEAD_CTC)
 
 
 def _same_pad(n_in: int, k: int, s: int) -> Tuple[int, Tuple[int, int]]:
@@ -544,6 +557,8 @@ class ModelBundle:
     def posterior_index(self) -> int:
         """Quirk C1 of SURVEY: width-1 head -> element 0, width-2 head -> element 1
         (reference wakeword/tflite.py:228-231 vs evaluate_models.py:80,86)."""
+        if self.kind == KIND_CRNN and self.crnn.head_kind == HEAD_CTC:
+            raise ValueError("a CTC-trained CRNN has per-step label posteriors, no wake-word posterior: decode them (wwhip.ctc)")
         return 0 if self.n_out == 1 else 1
 
 
@@ -617,8 +632,9 @@ def _sections(bundle: ModelBundle) -> List[Tuple[str, np.ndarray]]:
             for dn, g in zip(("f", "b"), layer):
                 sec += [(f"crnn.g{li}{dn}.wx", g.w_x), (f"crnn.g{li}{dn}.bx", g.b_x),
                         (f"crnn.g{li}{dn}.wh", g.w_h), (f"crnn.g{li}{dn}.bh", g.b_h)]
-        sec += [("crnn.head_w1", c.head_w1), ("crnn.head_b1", c.head_b1),
-                ("crnn.head_w2", c.head_w2), ("crnn.head_b2", c.head_b2)]
+        if c.head_kind != HEAD_CTC:
+            sec += [("crnn.head_w1", c.head_w1), ("crnn.head_b1", c.head_b1)]
+        sec += [("crnn.head_w2", c.head_w2), ("crnn.head_b2", c.head_b2)]
     else:
         w = bundle.wavenet
         nb = len(w.blocks)
