@@ -234,6 +234,9 @@ int ww_stft_mag(ww_ctx *ctx, const ww_model *model, const float *frames, int64_t
  * spokestack/wakeword/tflite.py:183-184; utils/tf_lite/filter.py:72-73). */
 int ww_filter_apply(ww_ctx *ctx, const ww_model *model, const float *mag, int64_t n, float *mel);
 
+/* Device form of ww_logmel: the row of frame j of utterance u is the bits of the host form's.  Extent: samples outside
+ * [d_sample_offs[0], d_sample_offs[n_utt]) never reach a row, a frame reads its own utterance only, and rows [0, total_frames) of
+ * d_mel are written and nothing else. */
 int ww_logmel_dev(ww_ctx *ctx, const ww_model *model, const int16_t *d_pcm, const int64_t *d_sample_offs,
                   const int64_t *d_frame_offs, int32_t n_utt, int64_t total_frames, int64_t max_frames_per_utt,
                   const ww_frontend_params *fp, float *d_mel);
@@ -322,7 +325,10 @@ int ww_slide_forward(ww_ctx *ctx, const ww_model *model, const float *mel, int64
                      int64_t *n_windows);
 
 /* Device form.  Window w reads mel rows [d_win_row[w], d_win_row[w] + d_win_valid[w]) and is
- * zero padded at the end up to `window` rows (evaluate_tf_lite_opts.py:43-45). */
+ * zero padded at the end up to `window` rows (evaluate_tf_lite_opts.py:43-45).
+ * Extent: rows that no window names - the rows from d_win_valid[w] on, the rows between the windows - never reach a result, whatever
+ * they hold (NaN and Inf included); d_out[0 .. n_windows) is written and nothing else; a non-finite value in a window's own rows
+ * affects that window's row alone (tests/test_gpu_extents.py holds this for every _dev entry point that says "Extent"). */
 int ww_forward_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows,
                            const int64_t *d_win_row, const int32_t *d_win_valid, int32_t n_windows, float *d_out);
 
@@ -342,7 +348,8 @@ int ww_forward_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_me
 int ww_ctc_forward(ww_ctx *ctx, const ww_model *model, const float *windows, int32_t n, int32_t max_labels, int32_t *labels,
                    int32_t *lengths, float *steps, float *enc);
 /* Device form with ww_forward_windows_dev's windows: window w reads d_win_valid[w] rows from row d_win_row[w] and is zero padded at
- * the end - the dataloader's truncate-and-pad of a clip (wwdetect/CRNN/dataloader.py:90-92). */
+ * the end - the dataloader's truncate-and-pad of a clip (wwdetect/CRNN/dataloader.py:90-92).  Extent: as ww_forward_windows_dev, for
+ * each of the four outputs - rows [0, n) of each are written, and a window's non-finite rows reach that window's rows alone. */
 int ww_ctc_forward_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
                                const int32_t *d_win_valid, int32_t n, int32_t max_labels, int32_t *d_labels, int32_t *d_lengths,
                                float *d_steps, float *d_enc);
@@ -362,7 +369,8 @@ int ww_ctc_greedy_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, i
  * sent to the device with the call's other tables.  d_enc (may be NULL) receives the encoder rows [n_windows][enc_rows][enc_width].
  * CRNN: one crnn_fused_kernel launch whatever n_windows is (no front + tail split); Wavenet: the fp32 transposed form, twelve waves
  * up to 256 windows and four above, as for one model.  Row w carries the bits of ww_forward_windows_dev with member win_model[w] on
- * the same launch size.  n_windows = 0: WW_OK, nothing written. */
+ * the same launch size.  n_windows = 0: WW_OK, nothing written.  Extent: as ww_forward_windows_dev, for d_out and for d_enc
+ * ([0, n_windows) rows each). */
 int ww_set_forward_windows_dev(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
                                const int32_t *d_win_valid, const int32_t *win_model, int32_t n_windows, float *d_out, float *d_enc);
 
@@ -373,7 +381,11 @@ int ww_set_forward_windows_dev(ww_ctx *ctx, const ww_model_set *set, const float
  * position are computed once per sequence instead of once per window that contains it.  The host arrays are read before the
  * call returns, for every model: the caller may free or overwrite them at once.  The kernels are enqueued like every _dev entry
  * point's and the call waits for none of them unless a buffer of the context has to grow for it (its launch tables travel
- * through two page-locked buffers of the context, so a caller can stage its next batch while this one computes). */
+ * through two page-locked buffers of the context, so a caller can stage its next batch while this one computes).
+ * Extent: rows of the buffer outside every sequence - the gaps, what lies in front of the first and behind the last - never reach
+ * a result (a sequence's edge positions are computed from ITS rows and zeros, whatever its neighbours hold: NaN and Inf included);
+ * d_out[0 .. sum of seg_nw) is written and nothing else; a non-finite row affects the windows of its own sequence that name it,
+ * and no other sequence.  A sequence gives the bits it gives in a call of its own. */
 int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
                             const int32_t *seg_nw, int32_t n_seg, int32_t hop, float *d_out);
 
@@ -400,7 +412,8 @@ int ww_forward_segments_dev(ww_ctx *ctx, const ww_model *model, const float *d_m
  * starts from the library's defaults whatever its members' options are.  Every other key (WW_OPT_CRNN_SPLIT_AT and
  * WW_OPT_WAVENET_ROWMAJOR among them): WW_EINVAL.  The two tails give the same bits; the rows form and the explicit-window form differ as they do for one model
  * (three of a window's nineteen projected rows are summed in another order: posteriors within 2e-6).  A single model's
- * ww_forward_segments_dev takes the rows form whatever W is: WW_OPT_CRNN_SLIDE_MIN = 1 gives a set exactly those bits. */
+ * ww_forward_segments_dev takes the rows form whatever W is: WW_OPT_CRNN_SLIDE_MIN = 1 gives a set exactly those bits.
+ * Extent: as ww_forward_segments_dev in every plane; the slots x W rows of d_out are written and nothing behind the last plane. */
 int ww_set_forward_segments_dev(ww_ctx *ctx, const ww_model_set *set, const float *d_mel, int64_t mel_rows, const int64_t *seg_row0,
                                 const int32_t *seg_nw, int32_t n_seg, int32_t hop, const int32_t *members, int32_t n_members, float *d_out);
 int ww_set_slide_forward(ww_ctx *ctx, const ww_model_set *set, const float *mel, int64_t rows, int32_t hop, const int32_t *members,
@@ -475,7 +488,9 @@ int ww_set_wave_sequence_all(ww_ctx *ctx, const ww_model_set *set, const float *
  * for the all-zero window; a clip of more than `window` frames is judged by its first `window` frames, the rest is not read by
  * the model.  The result for a clip does not depend on the batch it is in (tests/test_gpu_clips64.py pins all of this).
  * d_pcm is 16-byte aligned; WW_EINVAL for more than 65535 clips, a negative size, a hop outside 1..512, a pcm_divisor that is
- * not positive or a NULL buffer; n_clips = 0 is a no-op. */
+ * not positive or a NULL buffer; n_clips = 0 is a no-op.
+ * Extent: samples in front of d_pcm and behind its n_clips x samples_per_clip never reach a result; d_out[0 .. n_clips) is written
+ * and nothing else. */
 int ww_clips_forward_dev(ww_ctx *ctx, const ww_model *model, const int16_t *d_pcm, int32_t n_clips,
                          int32_t samples_per_clip, const ww_frontend_params *fp, float *d_out);
 
@@ -788,7 +803,8 @@ int ww_far_frr(ww_ctx *ctx, const float *pos, int64_t n_pos, const float *neg, i
 /* The same sweep over posteriors that are already on the context's device (the sharded evaluators: the values a rank's
  * kernels produced, or what the posterior gather delivered) - d_pos / d_neg are device pointers, nothing but the thresholds goes
  * up and nothing but the n_thr counters comes back; d_smoothed (device, [n_neg] fp64) may be NULL.  Returns after the
- * counters are on the host. */
+ * counters are on the host.  Extent: nothing in front of or behind d_pos[0 .. n_pos) and d_neg[0 .. n_neg) reaches a counter or a
+ * smoothed value (the window is clipped to the stream), and d_smoothed[0 .. n_neg) is written and nothing else. */
 int ww_far_frr_dev(ww_ctx *ctx, const float *d_pos, int64_t n_pos, const float *d_neg, int64_t n_neg, int32_t win,
                    const double *thr, int32_t n_thr, double num_wakewords, double hours, double *frr, double *fa_per_h,
                    int64_t *fa_count, double *d_smoothed);
@@ -799,7 +815,9 @@ int ww_far_frr_dev(ww_ctx *ctx, const float *d_pos, int64_t n_pos, const float *
  * counts); otherwise d_seg_offs is a device table of n_seg + 1 ascending row offsets and d_out[s] = max over rows
  * [d_seg_offs[s], d_seg_offs[s + 1]).  Offsets are clamped to [0, n]; a run without rows yields -inf (the reference never asks
  * for one: np.max of nothing raises).  The maximum is np.max's: a run that holds a NaN yields NaN - such a clip is above no
- * threshold, as in the reference.  Enqueues on the context's stream, no synchronisation. */
+ * threshold, as in the reference.  Enqueues on the context's stream, no synchronisation.
+ * Extent: only element pidx of the rows of a run (of all n rows without a table) reaches d_out - not the other columns, not the
+ * rows no run names, nothing around d_rows; d_out[0 .. n_seg) (or [0 .. n)) is written and nothing else. */
 int ww_posterior_pick_dev(ww_ctx *ctx, const float *d_rows, int64_t n, int32_t n_out, int32_t pidx, const int64_t *d_seg_offs,
                           int64_t n_seg, float *d_out);
 
@@ -831,7 +849,9 @@ int ww_posterior_pick_dev(ww_ctx *ctx, const float *d_rows, int64_t n, int32_t n
  * (n > 2^39).  Both calls return with the events in the caller's array: ww_posterior_events_dev reads device posteriors where they
  * are - offsets and thresholds go up, the plane totals and the written events come back, nothing else crosses the bus -,
  * ww_posterior_events uploads host posteriors first.  Five kernel launches per call whatever n, n_seg, planes and the number of
- * events are (detection events). */
+ * events are (detection events).
+ * Extent: the rows of a plane that no segment names, and what lies around d_post, reach no event, no peak value and no count; a
+ * non-finite row affects the events of its own segment and plane alone. */
 typedef struct ww_event {
   int32_t plane, seg;
   int64_t start, end, peak; /* segment-relative rows; the run is [start, end) */

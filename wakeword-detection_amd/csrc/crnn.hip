@@ -1314,7 +1314,26 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_rows_kernel(rows_args a, w
   __syncthreads();
   // ---- conv: five m-tiles per wave (CV_TILE_LOOP)
   {
-    auto load_a = [&](cv_a &av, int i) { CV_LOAD_A(av, img + a_off[i]) };
+    // An edge position's cleared taps (conv_wL: frames kt < PT, conv_wR: the last 7, model_pack.h) lie over rows of the buffer that
+    // are NOT the window's - the sequence's own rows in front of it or behind it, a gap, the next sequence.  0 * x is 0 for a finite
+    // x only, so the operands under those taps are cleared as well, by a select: a NaN or an Inf in a row the window does not name
+    // stays out of it.  (Finite rows: the same +-0 products as before.)  `kind` is uniform: the interior tiles skip all of it.
+    auto load_a = [&](cv_a &av, int i) {
+      CV_LOAD_A(av, img + a_off[i])
+      if (kind != 0) {
+        const int lo = kind == 1 ? 0 : CV_KT - 7, hi = kind == 1 ? CV_PT : CV_KT;  // the cleared frames [lo, hi)
+#pragma unroll
+        for (int kb = 0; kb < CV_KB; ++kb) {
+          const int kt = (kb * 16 + kk * 4) % CV_KT;
+          av.q[kb].x = (kt + 0 >= lo && kt + 0 < hi) ? 0.f : av.q[kb].x;
+          av.q[kb].y = (kt + 1 >= lo && kt + 1 < hi) ? 0.f : av.q[kb].y;
+          av.q[kb].z = (kt + 2 >= lo && kt + 2 < hi) ? 0.f : av.q[kb].z;
+          av.q[kb].w = (kt + 3 >= lo && kt + 3 < hi) ? 0.f : av.q[kb].w;
+        }
+        const int ktl = CV_QL * 4 % CV_KT + kk;  // the last quad's frames 16..19
+        av.last = (ktl >= lo && ktl < hi) ? 0.f : av.last;
+      }
+    };
     auto store_tile = [&](int i, const f32x4 &r0, const f32x4 &r1) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
