@@ -264,8 +264,9 @@ typedef struct ww_resample_info {
 } ww_resample_info;
 /* A filter whose table (up * taps per output) exceeds WW_RESAMPLE_MAX_TAPS, or whose tile (2 * down + taps per output + 2
  * staged samples) exceeds WW_RESAMPLE_MAX_SPAN, is refused with WW_EINVAL: every pair of the standard rates 8, 11.025, 16,
- * 22.05, 24, 32, 44.1, 48, 88.2, 96, 176.4, 192 kHz passes (largest: 192 kHz <-> 11.025 kHz, 174,080 taps), 44101 -> 16000
- * (2.99 M taps) does not.  Rates <= 0: WW_EINVAL. */
+ * 22.05, 24, 32, 44.1, 48, 88.2, 96, 176.4, 192 kHz passes (largest table: 11.025 kHz -> 192 kHz, 174,080 taps; 192 kHz ->
+ * 11.025 kHz has 173,460 and the longest tile, 2 * 2560 + 1180 + 2 staged samples), 44101 <-> 16000 (2.99 M taps) does not.
+ * Rates <= 0: WW_EINVAL. */
 #define WW_RESAMPLE_MAX_TAPS (1 << 20)
 #define WW_RESAMPLE_MAX_SPAN 12288
 #define WW_SAMPLE_I16 0

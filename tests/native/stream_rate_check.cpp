@@ -7,7 +7,8 @@
 //     still in the stream's history;
 //   * for every residue a stream can be at and every output of a tick: rate_position's (c, p) are the output's first input and
 //     phase as the absolute indices give them, and the chain's reads stay inside [history | frame | pad];
-//   * the refusals: 11025 Hz, 16000 Hz, an output rate other than 16000 Hz, a geometry too long for a tick's staging.
+//   * the refusals: 11025 Hz, 16000 Hz, an output rate other than 16000 Hz, a geometry too long for a tick's staging;
+//   * the staging cap from both sides: all of the above at 500000 Hz (12,156 of 12,288 staged floats), and 510000 Hz refused.
 // Prints one "geom <zeros> <rate> <up> <down> <half> <F> <D> <history>" line per geometry and then "ok <checks>" and exits 0, or says
 // what failed and exits 1.
 #include <cmath>
@@ -65,7 +66,7 @@ static void check_rate(int rate_in, int zeros, const int *table /* up, down, hal
   CHECK(g.D == (half + down - 1) / down && half < down * (g.D + 1));
   const int64_t aligned = (g.D * down + half + up - 1) / up + 1;
   CHECK(g.hist >= aligned && g.hist >= ((g.D + 1) * down + half + up - 1) / up && g.hist <= aligned + down);
-  if (zeros == 32) CHECK(aligned <= 816 && g.hist <= 828);
+  if (zeros == 32 && rate_in <= 192000) CHECK(aligned <= 816 && g.hist <= 828);  // (the standard rates' histories)
   CHECK(g.hist + g.F + WW_RATE_PAD <= WW_RATE_STAGE_MAX);
 
   // ---- random cuts: packets of 1 .. 3000 samples, empty packets and ticks of F, from a reset
@@ -131,6 +132,21 @@ int main() {
     CHECK(rate_make_geom(rate, 16000, up, down, half, tpp, g, why, sizeof why) == 0 && g.D == 34 && tpp >= 374 && tpp <= 815);
   }
   for (int rate : {8000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000, 12000, 16050}) check_rate(rate, 8, nullptr);
+  {  // the staging cap decides what a bank accepts: 500000 Hz fills 12,156 of the 12,288 staged floats, 510000 Hz would need 12,399
+    static const int near_cap[6] = {4, 125, 4233, 10000, 34, 2117};
+    check_rate(500000, 32, near_cap);
+    int64_t up, down, half, tpp;
+    design(500000, 32, 0.945, up, down, half, tpp);
+    rate_geom g;
+    char why[256] = {0};
+    CHECK(rate_make_geom(500000, 16000, up, down, half, tpp, g, why, sizeof why) == 0 && g.hist == 2152);
+    CHECK(g.hist + g.F + WW_RATE_PAD == 12156 && WW_RATE_STAGE_MAX == 12288);
+    CHECK((2 * g.F + 15) / 16 == 1250);  // 16-byte pieces of an aligned int16 frame: four trips of the tick's piece loop (320 lanes)
+    design(510000, 32, 0.945, up, down, half, tpp);
+    cur_rate = 510000;
+    CHECK(up == 8 && down == 255 && rate_refusal(510000, 16000, why, sizeof why) == 0);
+    CHECK(rate_make_geom(510000, 16000, up, down, half, tpp, g, why, sizeof why) == 1 && strstr(why, "12399 staged") && strstr(why, "12288"));
+  }
 
   // ---- the refusals, each with its reason
   cur_rate = 0;

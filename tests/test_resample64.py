@@ -21,12 +21,21 @@ def designs():
     return {r: R64.design(r) for r in RATES}
 
 
+@pytest.fixture(scope="module")
+def rep_designs(designs):
+    """The seven rates to 16 kHz as before, and the representatives of every class of the tile planner."""
+    out = {(r, 16000): designs[r] for r in RATES}
+    out.update({p: R64.design(*p) for p in R64.CLASS_REPS})
+    return out
+
+
 def test_design_agrees_with_the_reference_statement(designs):
-    for r in RATES:
-        up, down, half, h = RS.design(r, 16000)
-        u2, d2, h2, want = designs[r]
+    assert len(R64.PAIRS) == 132 and len(set(R64.PAIRS)) == 132
+    for ri, ro in R64.PAIRS:
+        up, down, half, h = RS.design(ri, ro)
+        u2, d2, h2, want = designs[ri] if ro == 16000 and ri in designs else R64.design(ri, ro)
         assert (up, down, half) == (u2, d2, h2) and h.dtype == np.float64 and h.shape == want.shape == (2 * half + 1,)
-        assert np.abs(h - want).max() <= 1e-15 * np.abs(want).max(), r
+        assert np.abs(h - want).max() <= 1e-15 * np.abs(want).max(), (ri, ro)
         assert RS.taps_per_output(up, half) == R64.tpp(up, half)
     table = {48000: (1, 3, 102, 205), 44100: (160, 441, 14934, 187), 8000: (2, 1, 68, 69)}
     for r, want in table.items():
@@ -37,10 +46,28 @@ def test_design_agrees_with_the_reference_statement(designs):
         RS.design(0, 16000)
 
 
-def test_direct_sum_is_scipy_resample_poly(designs):
+def test_class_representatives_are_of_the_classes_they_stand_for(rep_designs):
+    """(form, ne8, ne1, lanes1) of every pair of CLASS_REPS by the tests' own statement of the planner's arithmetic
+    (tests/native/launch_plan_check.cpp holds the library's against the same table, for all 132 pairs)."""
+    want = {(192000, 8000): ("decim", 0, 256, 63), (176400, 11025): ("decim", 64, 256, 100), (192000, 16000): ("decim", 64, 256, 136),
+            (192000, 24000): ("decim", 128, 256, 209), (96000, 16000): ("decim", 128, 256, 256),
+            (192000, 11025): ("phase", 0, 256, 0), (32000, 11025): ("phase", 0, 256, 0), (176400, 8000): ("phase", 0, 256, 0),
+            (176400, 16000): ("phase", 64, 256, 0), (88200, 16000): ("phase", 128, 256, 0), (48000, 11025): ("phase", 128, 256, 0),
+            (11025, 192000): ("phase", 256, 256, 0), (8000, 192000): ("phase", 256, 256, 0), (16000, 48000): ("phase", 256, 256, 0),
+            (16000, 44100): ("phase", 256, 256, 0), (500000, 16000): ("phase", 0, 256, 0)}
+    assert set(want) == set(R64.CLASS_REPS)
+    for p in R64.CLASS_REPS:
+        up, down, half, _ = rep_designs[p]
+        assert R64.plan_class(up, down, half) == want[p], p
+    assert rep_designs[(11025, 192000)][0] == 2560 and R64.tpp(2560, rep_designs[(11025, 192000)][2]) * 2560 == 174080
+    assert rep_designs[(192000, 11025)][1] == 2560 and R64.tpp(147, rep_designs[(192000, 11025)][2]) * 147 == 173460
+    assert (rep_designs[(32000, 11025)][0], rep_designs[(8000, 192000)][:2]) == (441, (24, 1))
+    assert R64.tpp(4, rep_designs[(500000, 16000)][2]) == 2117
+
+
+def test_direct_sum_is_scipy_resample_poly(rep_designs):
     rng = np.random.default_rng(5)
-    for r in RATES:
-        up, down, half, h = designs[r]
+    for r, (up, down, half, h) in rep_designs.items():
         x = rng.uniform(-1, 1, 3001)
         a, b = R64.direct(x, up, down, half, h), R64.poly(x, up, down, h)
         assert a.shape == b.shape == (R64.out_len(len(x), up, down),)
@@ -49,9 +76,8 @@ def test_direct_sum_is_scipy_resample_poly(designs):
         assert err <= 1e-13, (r, err)
 
 
-def test_every_phase_has_unit_dc_gain(designs):
-    for r in RATES:
-        up, down, half, h = designs[r]
+def test_every_phase_has_unit_dc_gain(rep_designs):
+    for r, (up, down, half, h) in rep_designs.items():
         gains = np.array([h[(half + p) % up::up].sum() for p in range(up)])
         err = float(np.abs(gains - 1.0).max())
         print(f"{r}: max|DC gain - 1| = {err:.2e}")
