@@ -775,6 +775,45 @@ typedef struct ww_pipeline_state {
   int32_t n_vad_changed, n_fired, n_fall, n_deact; /* out */
 } ww_pipeline_state;
 int ww_pipeline_bank_step(ww_streams *st, const int16_t *frames, ww_pipeline_state *ps);
+/* ---- CTC stream banks: a CTC-trained CRNN (WW_HEAD_CTC) behind the streaming tick ---------------------------------------------
+ * ww_stream_create, ww_stream_create_set[_all] and ww_model_set_create refuse a CTC model; this is its own way in.
+ * ww_stream_create_ctc - S streams in lock step on ONE fp32 CTC-trained CRNN.  flags: 0, WW_STREAM_TWO_LAUNCH, WW_STREAM_SYNC_WAIT,
+ * WW_STREAM_FULL_RECOMPUTE (as ww_stream_create's) and WW_STREAM_CTC_STEPS; WW_STREAM_CAUSAL, an unknown flag, and a model that is
+ * not an fp32 WW_HEAD_CTC CRNN are WW_EINVAL.  The default form is the incremental kernel in one launch per tick (3 new time
+ * positions per window, the rest from the per-stream cache) with layer 2's nineteen steps, the per-row softmax head and the greedy
+ * decode inside the workgroup; a window's decode travels to the host as one 32-bit word (bits 27..31 the whole decoded length 0..19,
+ * bits 3i..3i+2 label i for i < WW_STREAM_CTC_MAX_LABELS; a label is < L - 1 <= 7).  With WW_STREAM_FULL_RECOMPUTE a tick's windows
+ * go through the offline path's kernels (ww_ctc_forward's: front + CTC tail) over the ring's descriptors, and carry ITS bits; the
+ * incremental forms agree with one another bit for bit and with the offline path within the bound the incremental CRNN bank has
+ * against ww_forward.  WW_STREAM_CTC_STEPS: the bank also returns every window's [19][L] posteriors; such a bank always waits with
+ * hipStreamSynchronize (no order is built between the posteriors' stores and a polled tag).
+ * ww_stream_step_ctc - the tick.  frames, is_speech (bit 0 = speech, bit 1 = active) and n_post [S] exactly as ww_stream_step's; for
+ * each of the 0, 1 or 2 new windows k of stream s: labels [S][2][max_labels] the first decoded labels padded with -1, lengths [S][2]
+ * the WHOLE decoded length (it may exceed max_labels), steps [S][2][19][L] the posteriors (may be NULL; non-NULL on a bank without
+ * WW_STREAM_CTC_STEPS is WW_EINVAL).  1 <= max_labels <= WW_STREAM_CTC_MAX_LABELS.  Entries at or past n_post[s] are left as they were.
+ * ww_ctc_trigger_bank_step / ww_stream_step_ctc_trigger - the wake-word stage: ww_trigger_bank_step and ww_stream_step_trigger with
+ * another firing rule - the same VAD-edge bookkeeping against was_speech, the same fired and fall lists, the same reset of the
+ * streams whose speech bit fell.  A stream that is not active fires on the first window of the tick whose decode STARTS WITH
+ * target[0 .. n_target): its whole length reaches n_target and its first n_target labels equal it (wwdetect/CRNN/evaluate.py:100-150
+ * with [HEY][SNIPS]); 1 <= n_target <= max_labels.
+ * On a CTC bank ww_stream_reset, _window, _attach_resampler[_fmt], _attach_rates[_fmt], _set_rate, the frame-layout calls, _timeline
+ * and _destroy work unchanged.  WW_EINVAL before any state moves, ww_last_error naming the family to use instead: ww_stream_step,
+ * _step_all, _step_trigger[_all], ww_pipeline_bank_step, ww_stream_feed* and ww_stream_set_model on a CTC bank; the three ww_*_ctc*
+ * stream calls on any other bank.  Not offered: CTC members of model sets and every-member banks, feed, split-bf16, a fused
+ * ww_pipeline_bank_step with this stage, more than WW_STREAM_CTC_MAX_LABELS labels per streamed window. */
+#define WW_STREAM_CTC_STEPS 16u
+#define WW_STREAM_CTC_MAX_LABELS 9
+int ww_stream_create_ctc(ww_ctx *ctx, const ww_model *model, int32_t n_streams, const ww_frontend_params *fp, uint32_t flags,
+                         ww_streams **out);
+int ww_stream_step_ctc(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels,
+                       int32_t *lengths, float *steps, int32_t *n_post);
+int ww_ctc_trigger_bank_step(int32_t n_streams, const uint8_t *is_speech, uint8_t *is_active, const int32_t *labels,
+                             const int32_t *lengths, const int32_t *n_post, int32_t max_labels, const int32_t *target,
+                             int32_t n_target, uint8_t *was_speech, int32_t *fired_ids, int32_t *n_fired, int32_t *fall_ids,
+                             int32_t *n_fall);
+int ww_stream_step_ctc_trigger(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, uint8_t *is_active, int32_t max_labels,
+                               const int32_t *target, int32_t n_target, uint8_t *was_speech, int32_t *labels, int32_t *lengths,
+                               float *steps, int32_t *n_post, int32_t *fired_ids, int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall);
 /* Where a tick's time goes on the HOST side of ww_stream_step (the loop of spokestack/pipeline.py:25-28 is host-paced, so
  * BASELINE config 5's per-tick latency is this call): mean nanoseconds per phase over the ticks since the last reset -
  * [0] plan (control words and window descriptors of the tick), [1] the caller's frames into the page-locked block,

@@ -6,7 +6,12 @@ Two sides on the same resident windows, alternated within one process for severa
   softmax  ``forward_windows_dev`` of the shipped CRNN_softmax forced into front + vector tail (``crnn_split_at=1,
            crnn_tail_mfma=0``): the same work minus 18 head rows and the decode
 Per side and size: p50 / p90 of the per-call time (context timer around ``calls`` back-to-back calls, one sample per round), then
-the per-kernel split under ``ww_profile``.  Usage: python tools/ctc_bench.py [rounds] [calls] > profiles/ctc/measured.txt"""
+the per-kernel split under ``ww_profile``.  Usage: python tools/ctc_bench.py [rounds] [calls] > profiles/ctc/measured.txt
+
+``stream``: what a CTC stream bank's tick costs (``wwhip.engine.CtcStreamBank``, S = 128, L = 4), per form, beside the shipped
+``CRNN_softmax`` ``StreamBank`` tick on the same frames - one process, the sides alternated over several rounds, per side the p50 /
+p99 of the host's time per ``step`` (``time.perf_counter`` around the call: what the 20 ms loop pays), and the mean host timeline.
+Usage: python tools/ctc_bench.py stream [rounds] [ticks] > profiles/ctc/stream_measured.txt"""
 import os
 import sys
 
@@ -20,48 +25,91 @@ from wwhip.engine import Engine  # noqa: E402
 
 import ctc64  # noqa: E402
 
-rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 9
-calls = int(sys.argv[2]) if len(sys.argv) > 2 else 200
-ctx = _lib.Context(0)
-ctc = Engine("synthetic-ctc-4", ctx=ctx, bundle=ctc64.model(4))
-smx = Engine(os.path.join(ROOT, "wakeword-detection_amd/assets/tf_lite_models/CRNN_softmax"), ctx=ctx)
-smx.set_option("crnn_split_at", 1)
-smx.set_option("crnn_tail_mfma", 0)
 
-for n in (256, 4096):
-    wins = ctc64.G.windows(7, min(n, 512), 151, 40)
-    d_mel = torch.from_numpy(np.ascontiguousarray(wins).reshape(-1, 40)).cuda()
-    d_row = (torch.arange(n, dtype=torch.int64, device="cuda") % len(wins)) * 151
-    d_valid = torch.full((n,), 151, dtype=torch.int32, device="cuda")
-    d_lab = torch.empty((n, 2), dtype=torch.int32, device="cuda")
-    d_len = torch.empty(n, dtype=torch.int32, device="cuda")
-    d_out = torch.empty((n, smx.n_out), dtype=torch.float32, device="cuda")
-    torch.cuda.synchronize()
-    sides = {
-        "ctc": lambda: ctc.ctc_forward_windows_dev(d_mel.data_ptr(), d_mel.shape[0], d_row.data_ptr(), d_valid.data_ptr(), n, 2,
-                                                   d_lab.data_ptr(), d_len.data_ptr()),
-        "softmax": lambda: smx.forward_windows_dev(d_mel.data_ptr(), d_mel.shape[0], d_row.data_ptr(), d_valid.data_ptr(), n, d_out.data_ptr()),
-    }
-    for fn in sides.values():
-        for _ in range(5):
-            fn()
-    ctx.synchronize()
-    times = {k: [] for k in sides}
-    for _ in range(rounds):
+
+def windows_mode(rounds: int, calls: int) -> None:
+    ctx = _lib.Context(0)
+    ctc = Engine("synthetic-ctc-4", ctx=ctx, bundle=ctc64.model(4))
+    smx = Engine(os.path.join(ROOT, "wakeword-detection_amd/assets/tf_lite_models/CRNN_softmax"), ctx=ctx)
+    smx.set_option("crnn_split_at", 1)
+    smx.set_option("crnn_tail_mfma", 0)
+
+    for n in (256, 4096):
+        wins = ctc64.G.windows(7, min(n, 512), 151, 40)
+        d_mel = torch.from_numpy(np.ascontiguousarray(wins).reshape(-1, 40)).cuda()
+        d_row = (torch.arange(n, dtype=torch.int64, device="cuda") % len(wins)) * 151
+        d_valid = torch.full((n,), 151, dtype=torch.int32, device="cuda")
+        d_lab = torch.empty((n, 2), dtype=torch.int32, device="cuda")
+        d_len = torch.empty(n, dtype=torch.int32, device="cuda")
+        d_out = torch.empty((n, smx.n_out), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        sides = {
+            "ctc": lambda: ctc.ctc_forward_windows_dev(d_mel.data_ptr(), d_mel.shape[0], d_row.data_ptr(), d_valid.data_ptr(), n, 2,
+                                                       d_lab.data_ptr(), d_len.data_ptr()),
+            "softmax": lambda: smx.forward_windows_dev(d_mel.data_ptr(), d_mel.shape[0], d_row.data_ptr(), d_valid.data_ptr(), n, d_out.data_ptr()),
+        }
+        for fn in sides.values():
+            for _ in range(5):
+                fn()
+        ctx.synchronize()
+        times = {k: [] for k in sides}
+        for _ in range(rounds):
+            for k, fn in sides.items():
+                ctx.timer_start()
+                for _ in range(calls):
+                    fn()
+                times[k].append(ctx.timer_stop() / calls * 1e3)
+        for k, t in times.items():
+            print(f"{n} windows, {k}: p50 {np.percentile(t, 50):.1f} us, p90 {np.percentile(t, 90):.1f} us per call "
+                  f"({rounds} rounds of {calls} calls, sides alternated)")
         for k, fn in sides.items():
-            ctx.timer_start()
+            ctx.profile(True)
             for _ in range(calls):
                 fn()
-            times[k].append(ctx.timer_stop() / calls * 1e3)
+            p = ctx.profile_read()
+            ctx.profile(False)
+            print(f"{n} windows, {k}, per kernel (us):", {name: round(v["total_ms"] / v["calls"] * 1e3, 1) for name, v in p.items()})
+    ctc.close()
+    smx.close()
+
+
+def stream_mode(rounds: int, ticks: int, S: int = 128) -> None:
+    import time
+    from wwhip.engine import CtcStreamBank, StreamBank
+    ctx = _lib.Context(0)
+    ctc = Engine("synthetic-ctc-4", ctx=ctx, bundle=ctc64.model(4))
+    smx = Engine(os.path.join(ROOT, "wakeword-detection_amd/assets/tf_lite_models/CRNN_softmax"), ctx=ctx)
+    banks = {"ctc, one launch (default)": CtcStreamBank(ctc, S), "ctc, two launches": CtcStreamBank(ctc, S, two_launch=True),
+             "ctc, full_recompute": CtcStreamBank(ctc, S, full_recompute=True), "ctc, one launch, want_steps": CtcStreamBank(ctc, S, want_steps=True),
+             "CRNN_softmax StreamBank (yardstick)": StreamBank(smx, S)}
+    rng = np.random.default_rng(3)
+    frames = np.clip(rng.normal(0, 2500, (ticks, S, 320)), -32768, 32767).astype(np.int16)
+    speech = np.ones(S, np.uint8)
+    for b in banks.values():   # past the 151-row fill, every later tick two windows per stream
+        for t in range(100):
+            b.step(frames[t % ticks], speech)
+        b.timeline(reset=True)
+    times = {k: [] for k in banks}
+    for _ in range(rounds):
+        for k, b in banks.items():
+            for t in range(ticks):
+                t0 = time.perf_counter()
+                b.step(frames[t], speech)
+                times[k].append((time.perf_counter() - t0) * 1e6)
+    print(f"S = {S} streams, L = 4, 2 windows per stream and tick; {rounds} rounds of {ticks} ticks per side, sides alternated; host time per step()")
     for k, t in times.items():
-        print(f"{n} windows, {k}: p50 {np.percentile(t, 50):.1f} us, p90 {np.percentile(t, 90):.1f} us per call "
-              f"({rounds} rounds of {calls} calls, sides alternated)")
-    for k, fn in sides.items():
-        ctx.profile(True)
-        for _ in range(calls):
-            fn()
-        p = ctx.profile_read()
-        ctx.profile(False)
-        print(f"{n} windows, {k}, per kernel (us):", {name: round(v["total_ms"] / v["calls"] * 1e3, 1) for name, v in p.items()})
-ctc.close()
-smx.close()
+        tl = banks[k].timeline()
+        print(f"{k}: p50 {np.percentile(t, 50):.1f} us, p99 {np.percentile(t, 99):.1f} us, min {min(t):.1f} us per tick; "
+              f"timeline (mean us): " + ", ".join(f"{n} {tl[n]:.1f}" for n in StreamBank.TIMELINE_PHASES))
+    for b in banks.values():
+        b.close()
+    ctc.close()
+    smx.close()
+
+
+if __name__ == "__main__":
+    args = sys.argv[1:]
+    if args and args[0] == "stream":
+        stream_mode(int(args[1]) if len(args) > 1 else 7, int(args[2]) if len(args) > 2 else 300)
+    else:
+        windows_mode(int(args[0]) if len(args) > 0 else 9, int(args[1]) if len(args) > 1 else 200)

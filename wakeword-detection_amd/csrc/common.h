@@ -216,6 +216,11 @@ __device__ __forceinline__ void tick_tag_store(const ww_tick_tag &t, int w, floa
   const unsigned long long word = (unsigned long long)__float_as_uint(v) | ((unsigned long long)t.seq << 32);
   __hip_atomic_store(t.slots + w + k, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+// The same store for a value that is 32 bits of its own (stream_ctc.h: a streamed window's decode), not a float's
+__device__ __forceinline__ void tick_tag_store(const ww_tick_tag &t, int w, unsigned bits) {
+  const unsigned long long word = (unsigned long long)bits | ((unsigned long long)t.seq << 32);
+  __hip_atomic_store(t.slots + w, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 #endif
 
 struct ww_tick_fe;  // the streaming front end's side of a one-launch tick (stream_fe.h)
@@ -274,6 +279,13 @@ int ww_k_crnn_ctc_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, in
                           const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int n_windows, void *ws, size_t ws_bytes,
                           int max_labels, int32_t *d_labels, int32_t *d_lengths, float *d_steps, float *d_enc);
 int ww_k_ctc_greedy(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, int max_labels, int32_t *d_labels, int32_t *d_lengths);
+// A CTC stream bank's incremental ticks (crnn_stream_kernel<FE, false, false, CTC>): ww_k_crnn_tick's and ww_k_crnn_stream_forward's
+// arguments; a window's decode goes out as one 32-bit word (stream_ctc.h) - the value half of its tag where tag slots are given, else
+// row w of d_words -, and with d_steps (page-locked, [windows of the launch][19][L]; nullptr: off) its posteriors beside it
+int ww_k_crnn_ctc_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, float *d_gxc, const ww_tick_tag &tag, float *d_steps);
+int ww_k_crnn_ctc_stream_forward(ww_ctx *ctx, const ww_model *m, const float *d_hist, int64_t hist_rows, const int64_t *d_win_row,
+                                 const int32_t *d_win_valid, const int32_t *d_win_aux, float *d_gxc, int n_windows, uint32_t *d_words,
+                                 float *d_steps, const ww_tick_tag *tag = nullptr);
 size_t ww_wave_workspace(const ww_model *m, int n_windows);
 int ww_k_wave_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
                       const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int n_windows, void *ws, size_t ws_bytes,

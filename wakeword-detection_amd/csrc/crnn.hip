@@ -15,6 +15,7 @@
 // 34 us fused) and its bf16x6 projection GEMM are gone; their measurements are in DESIGN.md 7.1.
 #include "stream_fe.h"
 #include "ctc_decode.h"
+#include "stream_ctc.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -745,6 +746,110 @@ __device__ __forceinline__ void cf_phases_d_to_g(const fused_args &a, float *img
   }
 }
 
+// ---- the CTC head (WW_HEAD_CTC): ONE definition for gru_tail_ctc_kernel and cf_phases_d_to_g_ctc --------------------------------
+// One dense layer on every row of layer 2's step outputs, z[t][c] = b2[c] + sum_k w2[c][k] seq2[t][k], then the softmax over the L
+// classes of a row.  The 19 x 8 (row, class slot) pairs are dealt over the threads that are free, eight adjacent lanes per row - the
+// arrangement head_activation's softmax exchanges in.
+// The head's weights [L <= 8][64] as 128 x 16 bytes: thread tid < 128 loads row tid / 16 (rows L..7: zeros) ...
+__device__ __forceinline__ float4 ctc_head_w_load(const float *w2, int tid, int L) {
+  return tid * 4 < L * 2 * GR_H ? ((const float4 *)w2)[tid] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// ... and parks it in LDS, rows GR_SEQ_LD apart (eight rows 64 apart would share their banks)
+__device__ __forceinline__ void ctc_head_w_park(float *w2s, int tid, const float4 w2q) {
+  *(float4 *)(&w2s[(tid >> 4) * GR_SEQ_LD + (tid & 15) * 4]) = w2q;
+}
+// Slot p is (row p / 8, class p % 8); slots past row 18 recompute row 18 and store nothing (every lane of a wave takes part in the
+// softmax's exchanges).  One fmaf chain in k order from zero, the bias added last - the association of the other heads' last layer
+// (cf_phases_d_to_g, gru_tail_kernel, crnn_detect_kernel) - then head_activation's softmax.  The posterior goes to post[row][8] (LDS)
+// and, where steps_w is given, to the window's [19][L] block of the caller's posteriors.
+__device__ __forceinline__ void ctc_head_slot(const float *w2s, const float *seq2, float b2v, int p, int L, float *post, float *steps_w) {
+  constexpr int OT = CV_OT;
+  const int o = p & 7, t = min(p >> 3, OT - 1);
+  const float4 *wr = (const float4 *)(w2s + o * GR_SEQ_LD);  // (rows L..7 are zeros)
+  float y = 0.f;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const float4 wv = wr[q];
+    const float4 sv = *(const float4 *)(&seq2[t * GR_SEQ_LD + q * 4]);
+    y = fmaf(wv.x, sv.x, y); y = fmaf(wv.y, sv.y, y);
+    y = fmaf(wv.z, sv.z, y); y = fmaf(wv.w, sv.w, y);
+  }
+  y += b2v;
+  const float pr = head_activation(y, o, L, 1 /* softmax */);
+  if (o < L && (p >> 3) < OT) {
+    post[t * 8 + o] = pr;
+    if (steps_w) steps_w[t * L + o] = pr;
+  }
+}
+
+// Phases D..G of the streaming kernel for a CTC-trained CRNN (crnn_stream_kernel<FE, false, false, CTC>): cf_phases_d_to_g with
+// gru_tail_ctc_kernel's back end.  Layer 1 and phase E run through the same macros on the same wave split; layer 2 keeps every step
+// (cf_recurrence<true>) in seq2, the head is the shared one above on the three waves it needs, and thread 0 decodes the rows as
+// written (ctc_decode.h) and sends the decode out as ONE 32-bit word (stream_ctc.h): the value half of the window's tag where the
+// launch has tag slots, else row w of the launch's output block.
+// No LDS of its own: seq2, the posterior rows and the head's weights live in the feat region, which is dead behind "gx complete" -
+// where the other heads keep w1s, and a CTC model has no w1.
+#define CFC_SEQ2 0                                 // floats from `feat`: [19][GR_SEQ_LD], row t = [h_fwd(t) | h_bwd(t)]
+#define CFC_POST (CFC_SEQ2 + CV_OT * GR_SEQ_LD)    // [19][8] posteriors
+#define CFC_W2S (CFC_POST + CV_OT * 8)             // [8][GR_SEQ_LD] the head's weights
+#define CFC_FLOATS (CFC_W2S + 8 * GR_SEQ_LD)
+static_assert(CV_OT == WW_SC_STEPS && CFC_SEQ2 % 4 == 0 && CFC_POST % 4 == 0 && CFC_W2S % 4 == 0,
+              "cf_phases_d_to_g_ctc's LDS layout is written for 19 steps, 16-byte aligned rows");
+static_assert(CFC_FLOATS <= CF_FEAT_FLOATS, "the CTC back end does not fit the feat region");
+static_assert(CV_OT * 8 <= 3 * 64, "the head's (row, class slot) pairs are one pass of three waves");
+__device__ __forceinline__ void cf_phases_d_to_g_ctc(const fused_args &a, float *img, float *feat, const gru_w &g, int w, float *steps) {
+  constexpr int H = GR_H, OT = CV_OT;
+  const int tid = threadIdx.x, lane = tid & 63, wave = wave_index(tid);  // (scalar: so are dir and the forks on wave below)
+  const int j = lane & 15, kk = lane >> 4;
+  const int unit = lane >> 1, half = lane & 1, dir = wave & 1;
+  float *gxs = img + CF_GX, *seq1 = img + CF_SEQ, *hb = img + CF_HB;
+  float *seq2 = feat + CFC_SEQ2, *post = feat + CFC_POST, *w2s = feat + CFC_W2S;
+  // ---- D: layer-1 recurrence (waves 0, 1), every wave's W_x2 operands on their way (as cf_phases_d_to_g)
+  float4 bq2[4][3];
+  L2_LOAD_W(bq2, a.wx2s, wave * 3)
+  if (wave < 2) {
+    __builtin_amdgcn_s_setprio(3);
+    cf_recurrence<true>(g, gxs, hb + dir * 2 * H, seq1, dir, unit, half);
+    __builtin_amdgcn_s_setprio(0);
+  }
+  __syncthreads();
+
+  // ---- E: layer-2 input projection (L2_PROJECT), 3 n-tiles per wave; rows 19..31 of seq1 are zeros
+  {
+    float bb2[3];
+    L2_LOAD_BIAS(bb2, a.bx2, wave * 3)
+    __builtin_amdgcn_sched_barrier(0);
+    L2_PROJECT(bq2, bb2, 16 + j, wave * 3, )
+  }
+  __syncthreads();
+
+  // ---- F: layer-2 recurrence (waves 2, 3), every step kept: each (row, direction half) of seq2 is written exactly once, so seq2
+  //      needs no clearing | waves 0, 1: the head's weights -> LDS
+  const float b2v = a.b2[(tid & 7) < a.NOUT ? (tid & 7) : 0];  // (on its way during the recurrence)
+  if (wave >= 2) {
+    __builtin_amdgcn_s_setprio(3);
+    cf_recurrence<true>(g, gxs, hb + (2 + dir) * 2 * H, seq2, dir, unit, half);
+    __builtin_amdgcn_s_setprio(0);
+  } else {
+    ctc_head_w_park(w2s, tid, ctc_head_w_load(a.w2, tid, a.NOUT));
+  }
+  __syncthreads();
+
+  // ---- G: the head: 19 x 8 slots on waves 0..2, one pass
+  if (wave < 3) {
+    ctc_head_slot(w2s, seq2, b2v, tid, a.NOUT, post, steps ? steps + (size_t)w * OT * a.NOUT : nullptr);
+  }
+  __syncthreads();
+  // greedy decode of the posteriors as written, packed
+  if (tid == 0) {
+    int32_t *lab = (int32_t *)w2s;  // (the head is through with its weights)
+    const int32_t len = ww_ctc_greedy_row(post, OT, a.NOUT, 8, lab, WW_STREAM_CTC_MAX_LABELS);
+    const unsigned word = ww_sc_pack(lab, len);
+    if (a.tag.slots) tick_tag_store(a.tag, w, word);
+    else ((unsigned *)a.out)[w] = word;  // (the launch's output block holds words, not floats)
+  }
+}
+
 // crnn_fused_kernel<front> alone keeps its stamp sites: without them its compiled form ran ~1 % slower at 16,384 windows
 // per launch (the other forms lost theirs at no cost; profiles/EXPERIMENTS.md 9.5)
 #define CF_STAMP(i_) \
@@ -977,9 +1082,19 @@ static_assert(CT_BASE % 4 == 0 && CT_BASE + FE_TL_FLOATS <= CF_FEAT_FLOATS, "tic
 struct ww_set_all_ref : ww_set_ref {
   int K = 1;  // member slots per stream
 };
-template <int FE, bool SET = false, bool ALL = false>
-__global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args sa, typename std::conditional<ALL, ww_set_all_ref, ww_set_ref>::type set) {
+// CTC: a CTC bank runs one model, so the kernel's second argument is not a set's tables but the launch's posteriors
+// [windows][19][L] in page-locked memory (nullptr: not asked for) - stream_args and the other forms' arguments stay as they are
+struct ww_ctc_ref {
+  float *steps;
+};
+template <bool ALL, bool CTC>
+using cs_second_arg = typename std::conditional<CTC, ww_ctc_ref, typename std::conditional<ALL, ww_set_all_ref, ww_set_ref>::type>::type;
+// CTC (a CTC stream bank, streams.hip: ww_stream_create_ctc): everything up to "gx complete" is the kernel as it is; behind it
+// cf_phases_d_to_g_ctc keeps layer 2's nineteen steps, runs the per-row softmax head and decodes on the device.
+template <int FE, bool SET = false, bool ALL = false, bool CTC = false>
+__global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args sa, cs_second_arg<ALL, CTC> set) {
   static_assert(!ALL || (SET && FE != 0), "the every-member form is a one-launch tick of a set bank");
+  static_assert(!CTC || (!SET && !ALL), "a CTC bank runs one model: CTC members of model sets are not offered");
   if constexpr (SET && FE != 0) cf_set_move(sa.f, ww_set_offset(set, blockIdx.x >> 1));
   const fused_args &a = sa.f;
   extern __shared__ __align__(16) float cf_smem[];
@@ -1199,7 +1314,8 @@ __global__ __launch_bounds__(CF_THREADS, 2) void crnn_stream_kernel(stream_args 
     }
   }
   __syncthreads();  // gx complete; nobody reads feat any more
-  cf_phases_d_to_g(a, img, feat, g, w);
+  if constexpr (CTC) cf_phases_d_to_g_ctc(a, img, feat, g, w, set.steps);
+  else cf_phases_d_to_g(a, img, feat, g, w);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1802,42 +1918,24 @@ __global__ __launch_bounds__(128, 4) void gru_tail_ctc_kernel(tail_ctc_args ca) 
   gru_w g2;
   gru_load_w(g2, a.wh2, a.bh2, dir, unit, half);
   __syncthreads();
-  // the head's weights [L <= 8][64]: one 16-byte load per thread, on its way during the recurrence (thread tid: row tid / 16)
-  const float4 w2q = tid * 4 < a.NOUT * 2 * H ? ((const float4 *)a.w2)[tid] : make_float4(0.f, 0.f, 0.f, 0.f);
+  // the head's weights: on their way during the recurrence (ctc_head_w_load)
+  const float4 w2q = ctc_head_w_load(a.w2, tid, a.NOUT);
   // layer 2, every step kept: each (row, direction half) of seq2 is written exactly once, so seq2 needs no clearing
   cf_recurrence<true>(g2, gxs, hb + (2 + dir) * 2 * H, seq2, dir, unit, half);
   __syncthreads();
-  // gx is dead: the head's weights take its place, rows GR_SEQ_LD apart (eight rows 64 apart would share their banks)
+  // gx is dead: the head's weights take its place
   float *w2s = gxs;
-  *(float4 *)(&w2s[(tid >> 4) * GR_SEQ_LD + (tid & 15) * 4]) = w2q;
+  ctc_head_w_park(w2s, tid, w2q);
   if (a.enc)
     for (int i = tid; i < OT * 2 * H; i += 128) a.enc[(size_t)w * OT * 2 * H + i] = seq2[(i >> 6) * GR_SEQ_LD + (i & 63)];
   __syncthreads();
-  // head: slot p = tid + 128 pass is (row p / 8, class p % 8); slots past row 18 recompute row 18 and store nothing (every lane of a
-  // wave takes part in the softmax's exchanges).  One fmaf chain in k order from zero, the bias added last - the association of the
-  // other heads' last layer (cf_phases_d_to_g, gru_tail_kernel, crnn_detect_kernel) - then head_activation's softmax: one definition.
+  // the shared head (ctc_head_slot): slot p = tid + 128 pass, two passes
   {
     const int L = a.NOUT, o = tid & 7;
-    const float4 *wr = (const float4 *)(w2s + o * GR_SEQ_LD);  // (rows L..7 are zeros)
     const float b2v = a.b2[o < L ? o : 0];
+    float *steps_w = ca.steps ? ca.steps + (size_t)w * OT * L : nullptr;
 #pragma unroll 1
-    for (int pass = 0; pass < 2; ++pass) {
-      const int p = tid + 128 * pass, t = min(p >> 3, OT - 1);
-      float y = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const float4 wv = wr[q];
-        const float4 sv = *(const float4 *)(&seq2[t * GR_SEQ_LD + q * 4]);
-        y = fmaf(wv.x, sv.x, y); y = fmaf(wv.y, sv.y, y);
-        y = fmaf(wv.z, sv.z, y); y = fmaf(wv.w, sv.w, y);
-      }
-      y += b2v;
-      const float pr = head_activation(y, o, L, 1 /* softmax */);
-      if (o < L && (p >> 3) < OT) {
-        post[t * 8 + o] = pr;
-        if (ca.steps) ca.steps[((size_t)w * OT + t) * L + o] = pr;
-      }
-    }
+    for (int pass = 0; pass < 2; ++pass) ctc_head_slot(w2s, seq2, b2v, tid + 128 * pass, L, post, steps_w);
   }
   __syncthreads();
   // greedy decode of the posteriors as written
@@ -2354,6 +2452,9 @@ int ww_k_crnn_init_device(ww_ctx *ctx) {
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
+  WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<0, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
+  WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<1, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
+  WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_stream_kernel<2, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CF_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CFB_SMEM_BYTES));
   WW_HIP(ctx, hipFuncSetAttribute((const void *)crnn_fused_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, CFB_SMEM_BYTES));
   return WW_OK;
@@ -2715,6 +2816,50 @@ int ww_k_ctc_greedy(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, 
     ww_launch_scope scope(ctx, "ctc_greedy_kernel");
     hipLaunchKernelGGL(ctc_greedy_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_steps, (long long)n, T, L, max_labels,
                        d_labels, d_lengths);
+  }
+  WW_HIP(ctx, hipGetLastError());
+  return WW_OK;
+}
+
+// A CTC stream bank's incremental ticks: ww_k_crnn_tick and ww_k_crnn_stream_forward for crnn_stream_kernel's CTC form.  The same
+// launch geometry and arguments; a window's decode leaves as one word (stream_ctc.h), its posteriors on request to d_steps.
+int ww_k_crnn_ctc_tick(ww_ctx *ctx, const ww_model *m, const ww_tick_fe &fe, int precise, float *d_gxc, const ww_tick_tag &tag, float *d_steps) {
+  if (int rc = ww_crnn_ctc_check(ctx, m, "ww_k_crnn_ctc_tick")) return rc;
+  const ww_crnn_dev &c = m->crnn;
+  const ww_filter_dev &f = m->filt;
+  if (f.n_mel != CV_NMEL || fe.hop != 160) return ww_fail(ctx, WW_EINVAL, "one-launch streaming tick: standard conv geometry, 40 mel bands and hop 160 only");
+  if (!tag.slots || fe.S <= 0 || fe.S > 65535) return ww_fail(ctx, WW_EINVAL, "one-launch streaming tick: no tag slots / %d streams", fe.S);
+  stream_args sa = {};
+  sa.f = crnn_fused_args(c, fe.hist, {nullptr, nullptr, 0, 0, 0, (int64_t)fe.S * fe.HR}, nullptr, nullptr);
+  sa.f.tag = tag;
+  sa.gxc = d_gxc;
+  sa.fe = fe;
+  sa.fb = ww_fe_filt_of(f);
+  {
+    ww_launch_scope scope(ctx, "crnn_stream_kernel<tick,ctc>");
+    if (precise) hipLaunchKernelGGL((crnn_stream_kernel<2, false, false, true>), dim3(2 * fe.S), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, ww_ctc_ref{d_steps});
+    else hipLaunchKernelGGL((crnn_stream_kernel<1, false, false, true>), dim3(2 * fe.S), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, ww_ctc_ref{d_steps});
+  }
+  WW_HIP(ctx, hipGetLastError());
+  return WW_OK;
+}
+
+int ww_k_crnn_ctc_stream_forward(ww_ctx *ctx, const ww_model *m, const float *d_hist, int64_t hist_rows, const int64_t *d_win_row,
+                                 const int32_t *d_win_valid, const int32_t *d_win_aux, float *d_gxc, int nw, uint32_t *d_words, float *d_steps,
+                                 const ww_tick_tag *tag) {
+  if (int rc = ww_crnn_ctc_check(ctx, m, "ww_k_crnn_ctc_stream_forward")) return rc;
+  if (nw <= 0) return WW_OK;
+  const ww_crnn_dev &c = m->crnn;
+  if (!d_win_row || !d_win_valid || !d_win_aux) return ww_fail(ctx, WW_EINVAL, "streaming CRNN kernel: NULL window table");
+  if (!d_words && !(tag && tag->slots)) return ww_fail(ctx, WW_EINVAL, "streaming CTC kernel: neither an output block nor tag slots");
+  stream_args sa = {};
+  sa.f = crnn_fused_args(c, d_hist, {d_win_row, d_win_valid, 0, 0, 0, hist_rows}, nullptr, (float *)d_words);  // (words: cf_phases_d_to_g_ctc)
+  sa.aux = d_win_aux;
+  sa.gxc = d_gxc;
+  if (tag) sa.f.tag = *tag;
+  {
+    ww_launch_scope scope(ctx, "crnn_stream_kernel<ctc>");
+    hipLaunchKernelGGL((crnn_stream_kernel<0, false, false, true>), dim3(nw), dim3(CF_THREADS), CF_SMEM_BYTES, ctx->stream, sa, ww_ctc_ref{d_steps});
   }
   WW_HIP(ctx, hipGetLastError());
   return WW_OK;

@@ -27,6 +27,7 @@
 //                           per 16 new frames of a stream, the same conversion and the same per-frame functions as above.
 #include "model_set.h"  // (in front of fft_device.h's macros)
 #include "stream_all.h"
+#include "stream_ctc.h"
 #include "stream_fe.h"
 
 #include <algorithm>
@@ -114,8 +115,21 @@ struct ww_streams {
   bool every = false;
   std::vector<int32_t> members;       // [K] the member of each slot (an every-member bank)
   int V() const { return S * K; }
-  // the reason this bank refuses `call` (stream_all.h: sa_check_call), where ww_last_error finds it; WW_OK: it does not
-  int check_call(const char *call, bool wants_every) const {
+  // a CTC stream bank (ww_stream_create_ctc; stream_ctc.h): `model` is a CTC-trained CRNN, a tick's windows come back as decoded
+  // labels - one 32-bit word per window in the tags or in h_out, which then holds words - and, on a WW_STREAM_CTC_STEPS bank, as
+  // posteriors in h_steps [2 S][19][L].  The WW_STREAM_FULL_RECOMPUTE form runs ww_k_crnn_ctc_forward, whose labels [2 S][9] and
+  // lengths [2 S] arrive in h_lab.  Everything else of the bank - rings, caches, tables, rates - is the ordinary bank's
+  bool ctc = false, ctc_steps = false;
+  float *h_steps = nullptr, *h_steps_dev = nullptr;
+  int32_t *h_lab = nullptr, *h_lab_dev = nullptr;
+  // the reason this bank refuses `call` (CTC or not: here; every-member or not: stream_all.h, sa_check_call), where ww_last_error
+  // finds it; WW_OK: it does not
+  int check_call(const char *call, bool wants_every, bool wants_ctc = false) const {
+    if (ctc && !wants_ctc)
+      return ww_fail(ctx, WW_EINVAL, "%s: this bank runs a CTC-trained CRNN (ww_stream_create_ctc), whose windows decode to labels: its tick is "
+                     "ww_stream_step_ctc, its trigger stage ww_stream_step_ctc_trigger, and it has no posterior, no feed, no member and no fused pipeline step", call);
+    if (!ctc && wants_ctc)
+      return ww_fail(ctx, WW_EINVAL, "%s: this bank was not created by ww_stream_create_ctc: its tick is ww_stream_step and its family", call);
     char why[320];
     const int rc = sa_check_call(every, call, wants_every, why, sizeof why);
     return rc ? ww_fail(ctx, rc, "%s", why) : WW_OK;
@@ -159,6 +173,7 @@ static inline uint64_t st_now_ns() {
 
 // scratch of the per-window kernels for nw windows (explicit window rows: never the sliding form)
 static size_t model_scratch_bytes(const ww_model *m, int nw) {
+  if (m->kind == WW_KIND_CRNN && m->crnn.HEAD == WW_HEAD_CTC) return ww_crnn_ctc_workspace(m, nw);
   return m->kind == WW_KIND_CRNN ? ww_crnn_workspace(m, nw, false) : ww_wave_workspace(m, nw);
 }
 
@@ -404,7 +419,7 @@ int ww_stream_destroy(ww_streams *st) {
   void *dev[] = {st->ring, st->hist, st->prev, st->d_pack, st->ws, st->gxc, st->gx_zero, st->wstate, st->zring, st->zpos, st->d_stream_model};
   for (void *p : dev)
     if (p) hipFree(p);
-  void *host[] = {st->h_pack, st->h_out, st->h_tag};
+  void *host[] = {st->h_pack, st->h_out, st->h_tag, st->h_steps, st->h_lab};
   for (void *p : host)
     if (p) hipHostFree(p);
   ww_k_rates_destroy(st->rates);
@@ -416,10 +431,14 @@ int ww_stream_destroy(ww_streams *st) {
 }  // extern "C"
 
 // ww_stream_create (set == nullptr), ww_stream_create_set (model = the set's view; stream_model: checked by the caller, or nullptr) and
-// ww_stream_create_set_all (every_k > 0: stream_model = the every_k member slots, checked by the caller, or nullptr)
+// ww_stream_create_set_all (every_k > 0: stream_model = the every_k member slots, checked by the caller, or nullptr);
+// ww_stream_create_ctc (ctc: the model is a CTC-trained CRNN, checked by the caller; flags may carry WW_STREAM_CTC_STEPS)
 static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model_set *set, const int32_t *stream_model, int32_t S,
-                              const ww_frontend_params *fp, uint32_t flags, ww_streams **out, int every_k = 0) {
-  if (int rc = ww_crnn_refuse_ctc(ctx, model, "ww_stream_create")) return rc;
+                              const ww_frontend_params *fp, uint32_t flags, ww_streams **out, int every_k = 0, bool ctc = false) {
+  if (!ctc)
+    if (int rc = ww_crnn_refuse_ctc(ctx, model, "ww_stream_create")) return rc;
+  const bool ctc_steps = ctc && (flags & WW_STREAM_CTC_STEPS);
+  if (ctc) flags &= ~(uint32_t)WW_STREAM_CTC_STEPS;
   if (flags & ~(uint32_t)(WW_STREAM_FULL_RECOMPUTE | WW_STREAM_TWO_LAUNCH | WW_STREAM_SYNC_WAIT | WW_STREAM_CAUSAL))
     return ww_fail(ctx, WW_EINVAL, "unknown stream flags 0x%x", flags);
   const bool causal = (flags & WW_STREAM_CAUSAL) != 0;
@@ -434,6 +453,7 @@ static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model
   ww_streams *st = new ww_streams();
   ww_scoped<ww_streams, ww_stream_destroy> own(st);  // (freed on every early return below)
   st->ctx = ctx; st->model = model; st->S = S; st->fp = *fp;
+  st->ctc = ctc; st->ctc_steps = ctc_steps;
   if (every_k) {
     st->every = true;
     st->K = every_k;
@@ -464,6 +484,8 @@ static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model
                    ((st->incremental && model->filt.n_mel == 40) || (!every_k && ww_wave_tick_capable(model, S)));
   // a borrowed stream is the caller's: when the call returns everything enqueued on it has completed, as before
   st->poll = ctx->own_stream && !(flags & WW_STREAM_SYNC_WAIT);
+  // (stream_ctc.h: no order is built between a window's posteriors and its tag, so a bank that returns posteriors waits for the stream)
+  if (ctc_steps) st->poll = false;
   // model scratch of the per-window kernels; the incremental CRNN needs none
   size_t ws_bytes = st->incremental ? 256 : model_scratch_bytes(model, 2 * V);
   bool ok = hipMalloc((void **)&st->ring, (size_t)2 * S * ST_RING * 4) == hipSuccess &&
@@ -486,6 +508,12 @@ static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model
       st->h_win_valid = (int32_t *)(st->h_pack + o_valid); st->d_win_valid = (int32_t *)(st->d_pack + o_valid);
       st->h_win_aux = (int32_t *)(st->h_pack + o_aux);     st->d_win_aux = (int32_t *)(st->d_pack + o_aux);
     }
+  }
+  if (ctc) {
+    ok = ok && (!ctc_steps || hipHostMalloc((void **)&st->h_steps, (size_t)2 * S * WW_SC_STEPS * st->NO * 4) == hipSuccess) &&
+         (st->incremental || hipHostMalloc((void **)&st->h_lab, (size_t)2 * S * (WW_STREAM_CTC_MAX_LABELS + 1) * 4) == hipSuccess);
+    if (ok && st->h_steps && hipHostGetDevicePointer((void **)&st->h_steps_dev, st->h_steps, 0) != hipSuccess) ok = false;
+    if (ok && st->h_lab && hipHostGetDevicePointer((void **)&st->h_lab_dev, st->h_lab, 0) != hipSuccess) ok = false;
   }
   if (!ok) {
     return ww_fail(ctx, WW_ENOMEM, "cannot allocate state for %d streams", S);
@@ -523,8 +551,11 @@ static int stream_create_impl(ww_ctx *ctx, const ww_model *model, const ww_model
         if (int rc = st->send_stream_model()) return rc;
       }
       hipMemsetAsync(st->gxc, 0, (size_t)WW_STREAM_GXC * 192 * 4, ctx->stream);
-      int rc = ww_k_crnn_stream_forward(ctx, model, st->hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, st->d_win_aux,
-                                        st->gxc, 1, st->h_out_dev, nullptr, st->ref());  // d_pack is zeroed: window row 0, aux 0 (valid 0 = all-zero window)
+      // d_pack is zeroed: window row 0, aux 0 (valid 0 = all-zero window)
+      int rc = ctc ? ww_k_crnn_ctc_stream_forward(ctx, model, st->hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, st->d_win_aux, st->gxc, 1,
+                                                  (uint32_t *)st->h_out_dev, nullptr)
+                   : ww_k_crnn_stream_forward(ctx, model, st->hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, st->d_win_aux,
+                                              st->gxc, 1, st->h_out_dev, nullptr, st->ref());
       if (rc) {
         return rc;
       }
@@ -740,8 +771,8 @@ int ww_stream_set_model(ww_streams *st, const int32_t *ids, int32_t n, int32_t m
   WW_GUARD_BEGIN
   if (!st) return WW_EINVAL;
   ww_ctx *ctx = st->ctx;
+  if (int rc = st->check_call("ww_stream_set_model", false)) return rc;  // (an every-member bank has a set: no refusal changes places)
   if (!st->set) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_model: this bank was not created from a model set");
-  if (int rc = st->check_call("ww_stream_set_model", false)) return rc;
   if (int rc = st->check_sound()) return rc;
   if (model < 0 || model >= st->set->n) return ww_fail(ctx, WW_EINVAL, "ww_stream_set_model: model %d: the set has members 0..%d", (int)model, st->set->n - 1);
   if (int rc = st->check_ids(ids, n)) return rc;
@@ -862,9 +893,19 @@ static int st_poll_tags(ww_streams *st) {
   return WW_OK;
 }
 
-static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post, bool *mutated) {
+// where a CTC bank's tick puts what it decoded (ww_stream_step_ctc's arguments, checked there)
+struct st_ctc_out {
+  int max_labels;
+  int32_t *labels, *lengths;  // [S][2][max_labels], [S][2]
+  float *steps;               // [S][2][19][L] or nullptr
+};
+
+// The one tick of every bank.  co (a CTC bank, stream_ctc.h): the same bookkeeping, frames, front end and wait; the model launches
+// are the CTC forms', and what arrives is scattered as labels, lengths and posteriors instead of `post` (nullptr then).
+static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post, bool *mutated,
+                            const st_ctc_out *co = nullptr) {
   ww_ctx *ctx = st->ctx;
-  if (!frames || !is_speech || !post || !n_post) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (!frames || !is_speech || (!post && !co) || !n_post) return ww_fail(ctx, WW_EINVAL, "NULL argument");
   WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
   *mutated = true;  // from here on the host's mirrors of the streams' state advance
   st->used = true;
@@ -911,7 +952,8 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     fe.ring = st->ring; fe.prev = st->prev; fe.hist = st->hist;
     fe.S = S; fe.HR = st->HR;
     fe.cv = ww_fe_pcm_of(st->fp); fe.hop = hop;
-    int rc = m->kind == WW_KIND_CRNN ? ww_k_crnn_tick(ctx, m, fe, st->fp.precise, st->gxc, tag, st->ref(), st->every ? st->K : 0) : ww_k_wave_tick(ctx, m, fe, st->fp.precise, tag, st->ref());
+    int rc = co ? ww_k_crnn_ctc_tick(ctx, m, fe, st->fp.precise, st->gxc, tag, st->h_steps_dev)
+             : m->kind == WW_KIND_CRNN ? ww_k_crnn_tick(ctx, m, fe, st->fp.precise, st->gxc, tag, st->ref(), st->every ? st->K : 0) : ww_k_wave_tick(ctx, m, fe, st->fp.precise, tag, st->ref());
     if (rc) return rc;
     tagged = true;
     tl[3] = st_now_ns();
@@ -965,14 +1007,21 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
       // the heads store a tick's few posteriors straight into pinned host memory - as {value, tick number} pairs where the
       // launch form writes them (every one-kernel form), else as rows of h_out: no device-to-host copy (a DMA operation of
       // its own) between the last kernel and the host's wake-up
-      tagged = st->poll && (st->incremental || m->kind == WW_KIND_WAVENET || ww_crnn_forward_tags(m, nw));
+      // (a CTC bank: the incremental kernel writes tags; the full-recompute form's tail writes labels and lengths, never tags)
+      tagged = st->poll && (st->incremental || (!co && (m->kind == WW_KIND_WAVENET || ww_crnn_forward_tags(m, nw))));
       const ww_tick_tag *tg = tagged ? &tag : nullptr;
       const float *d_hist = st->hist;
       // (a set's two-launch Wavenet tick: the kernel finds its stream in the window's aux word, which it has no other use for)
       ww_set_ref wref = st->set_ref;
       wref.aux = st->d_win_aux;
       const ww_set_ref *wset = st->set ? &wref : nullptr;
-      int rc = st->incremental
+      int rc = co ? (st->incremental
+                         ? ww_k_crnn_ctc_stream_forward(ctx, m, d_hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, st->d_win_aux, st->gxc, nw,
+                                                        (uint32_t *)st->h_out_dev, st->h_steps_dev, tg)
+                         : ww_k_crnn_ctc_forward(ctx, m, d_hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, 0, 0, 0, nw, st->ws, st->ws_bytes,
+                                                 WW_STREAM_CTC_MAX_LABELS, st->h_lab_dev, st->h_lab_dev + (size_t)2 * S * WW_STREAM_CTC_MAX_LABELS,
+                                                 st->h_steps_dev, nullptr))
+               : st->incremental
                    ? ww_k_crnn_stream_forward(ctx, m, d_hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, st->d_win_aux, st->gxc, nw, st->h_out_dev, tg, st->ref())
                : m->kind == WW_KIND_CRNN
                    ? ww_k_crnn_forward(ctx, m, d_hist, (int64_t)S * st->HR, st->d_win_row, st->d_win_valid, 0, 0, 0, nw, st->ws, st->ws_bytes, st->h_out_dev, nullptr, tg)
@@ -991,6 +1040,23 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     WW_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   tl[5] = st_now_ns();
+  if (co) {
+    // labels / lengths [s][k] from where the window's word arrived (stream_ctc.h): a tag's low word, a word of h_out, or - the
+    // full-recompute form - the tail's own labels and length; the posteriors from the same slot of h_steps
+    const bool table = tk.form == SA_TABLE;
+    sc_scatter(table, S, n_post, [&](int slot) -> uint32_t {
+      if (!st->incremental)
+        return ww_sc_pack(st->h_lab + (size_t)slot * WW_STREAM_CTC_MAX_LABELS, st->h_lab[(size_t)2 * S * WW_STREAM_CTC_MAX_LABELS + slot]);
+      return tagged ? (uint32_t)st->h_tag[slot] : ((const uint32_t *)st->h_out)[slot];
+    }, co->max_labels, co->labels, co->lengths);
+    if (co->steps) {
+      const size_t row = (size_t)WW_SC_STEPS * st->NO;
+      int w = 0;
+      for (int s = 0; s < S; ++s)
+        for (int k = 0; k < n_post[s]; ++k, ++w)
+          memcpy(co->steps + ((size_t)s * 2 + k) * row, st->h_steps + (size_t)(table ? w : 2 * s + k) * row, row * sizeof(float));
+    }
+  } else
   // post[s][slot][k] from where it arrived (stream_all.h): a tag's low word, or the posterior column of a row of h_out
   sa_scatter(tk.form, S, st->K, n_post, [&](int slot) -> float {
     if (!tagged) return st->h_out[(size_t)slot * st->NO + pidx];
@@ -1005,12 +1071,12 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   return WW_OK;
 }
 
-// ww_stream_step and ww_stream_step_all: the refusals, then the one tick
+// ww_stream_step, ww_stream_step_all and (co: a CTC bank's outputs) ww_stream_step_ctc: the refusals, then the one tick
 static int stream_step_entry(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post, const char *call,
-                             bool wants_every) {
-  if (int rc = st->check_call(call, wants_every)) return rc;
+                             bool wants_every, const st_ctc_out *co = nullptr) {
+  if (int rc = st->check_call(call, wants_every, co != nullptr)) return rc;
   if (int rc = st->check_sound()) return rc;
-  return st->guarded([&](bool *mutated) { return stream_step_impl(st, frames, is_speech, post, n_post, mutated); });
+  return st->guarded([&](bool *mutated) { return stream_step_impl(st, frames, is_speech, post, n_post, mutated, co); });
 }
 
 int ww_stream_step(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, float *post, int32_t *n_post) {
@@ -1421,6 +1487,82 @@ int ww_stream_timeline(ww_streams *st, double *mean_ns, int64_t *ticks, int32_t 
     st->tl_ticks = 0;
   }
   return WW_OK;
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+}  // extern "C"
+
+// ---- a CTC stream bank (include/wwhip.h; stream_ctc.h) ----------------------------------------------------------------------------------
+// ww_stream_step_ctc's refusals - all before any state moves -, then the one tick
+static int stream_step_ctc_entry(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels,
+                                 int32_t *lengths, float *steps, int32_t *n_post, const char *call) {
+  ww_ctx *ctx = st->ctx;
+  if (int rc = st->check_call(call, false, true)) return rc;
+  if (int rc = st->check_sound()) return rc;
+  if (max_labels < 1 || max_labels > WW_STREAM_CTC_MAX_LABELS)
+    return ww_fail(ctx, WW_EINVAL, "%s: max_labels %d: a streamed window carries 1..%d labels", call, (int)max_labels, WW_STREAM_CTC_MAX_LABELS);
+  if (!labels || !lengths) return ww_fail(ctx, WW_EINVAL, "%s: NULL argument", call);
+  if (steps && !st->ctc_steps) return ww_fail(ctx, WW_EINVAL, "%s: posteriors are returned by a bank created with WW_STREAM_CTC_STEPS", call);
+  const st_ctc_out co = {max_labels, labels, lengths, steps};
+  return stream_step_entry(st, frames, is_speech, nullptr, n_post, call, false, &co);
+}
+
+extern "C" {
+
+int ww_stream_create_ctc(ww_ctx *ctx, const ww_model *model, int32_t S, const ww_frontend_params *fp, uint32_t flags, ww_streams **out) {
+  WW_GUARD_BEGIN
+  if (!ctx || !model || !fp || !out) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (int rc = ww_crnn_ctc_check(ctx, model, "ww_stream_create_ctc")) return rc;
+  if (flags & WW_STREAM_CAUSAL) return ww_fail(ctx, WW_EINVAL, "ww_stream_create_ctc: WW_STREAM_CAUSAL is the fp32 Wavenet's sequence form, not a CRNN's");
+  if (flags & ~(uint32_t)(WW_STREAM_FULL_RECOMPUTE | WW_STREAM_TWO_LAUNCH | WW_STREAM_SYNC_WAIT | WW_STREAM_CTC_STEPS))
+    return ww_fail(ctx, WW_EINVAL, "ww_stream_create_ctc: unknown stream flags 0x%x", flags);
+  return stream_create_impl(ctx, model, nullptr, nullptr, S, fp, flags, out, 0, true);
+  WW_GUARD_END(ctx)
+}
+
+int ww_stream_step_ctc(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels, int32_t *lengths,
+                       float *steps, int32_t *n_post) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  return stream_step_ctc_entry(st, frames, is_speech, max_labels, labels, lengths, steps, n_post, "ww_stream_step_ctc");
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+// ww_trigger_bank_step with the label rule in place of the threshold (stream_ctc.h: sc_trigger_update, where the rule is stated)
+int ww_ctc_trigger_bank_step(int32_t S, const uint8_t *is_speech, uint8_t *is_active, const int32_t *labels, const int32_t *lengths,
+                             const int32_t *n_post, int32_t max_labels, const int32_t *target, int32_t n_target, uint8_t *was_speech,
+                             int32_t *fired_ids, int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall) {
+  WW_GUARD_BEGIN
+  if (sc_check_trigger(S, is_speech, is_active, labels, lengths, n_post, max_labels, target, n_target, was_speech, fired_ids, n_fired, fall_ids, n_fall))
+    return WW_EINVAL;
+  sc_trigger_update(S, is_speech, is_active, labels, lengths, n_post, max_labels, target, n_target, was_speech, fired_ids, n_fired, fall_ids, n_fall);
+  return WW_OK;
+  WW_GUARD_END(nullptr)
+}
+
+// ww_stream_step_trigger for a CTC bank: the tick (bit 0 = is_speech, bit 1 = is_active as they stand BEFORE the tick), the label
+// rule over its decodes, then the reset of the streams whose VAD bit fell.  is_active is updated in place.
+int ww_stream_step_ctc_trigger(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, uint8_t *is_active, int32_t max_labels,
+                               const int32_t *target, int32_t n_target, uint8_t *was_speech, int32_t *labels, int32_t *lengths, float *steps,
+                               int32_t *n_post, int32_t *fired_ids, int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  const char *call = "ww_stream_step_ctc_trigger";
+  if (int rc = st->check_call(call, false, true)) return rc;
+  if (!is_speech || !is_active || !target || !was_speech || !n_post || !fired_ids || !n_fired || !fall_ids || !n_fall)
+    return ww_fail(st->ctx, WW_EINVAL, "%s: NULL argument", call);
+  if (max_labels < 1 || max_labels > WW_STREAM_CTC_MAX_LABELS || n_target < 1 || n_target > max_labels)
+    return ww_fail(st->ctx, WW_EINVAL, "%s: max_labels %d (1..%d), a target of %d labels (1..max_labels)", call, (int)max_labels,
+                   WW_STREAM_CTC_MAX_LABELS, (int)n_target);
+  *n_fired = *n_fall = 0;
+  st->stage_flags.resize((size_t)st->S);
+  for (int s = 0; s < st->S; ++s) st->stage_flags[s] = (uint8_t)((is_speech[s] != 0) | ((is_active[s] != 0) << 1));
+  int rc = stream_step_ctc_entry(st, frames, st->stage_flags.data(), max_labels, labels, lengths, steps, n_post, call);
+  if (rc) return rc;
+  sc_trigger_update(st->S, is_speech, is_active, labels, lengths, n_post, max_labels, target, n_target, was_speech, fired_ids, n_fired, fall_ids, n_fall);
+  if (*n_fall) rc = ww_stream_reset(st, fall_ids, *n_fall);
+  return rc;
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 

@@ -42,7 +42,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "fft_device.h"), os.path.join(CSRC, "stream_fe.h"),
                os.path.join(CSRC, "host_stage.h"), os.path.join(CSRC, "model_layout.h"), os.path.join(CSRC, "model_pack.h"),
-               os.path.join(CSRC, "model_set.h"), os.path.join(CSRC, "ctc_decode.h"),
+               os.path.join(CSRC, "model_set.h"), os.path.join(CSRC, "ctc_decode.h"), os.path.join(CSRC, "stream_ctc.h"),
                os.path.join(CSRC, "launch_plan.h"), os.path.join(CSRC, "stream_rate.h"), os.path.join(CSRC, "stream_rates.h"),
                os.path.join(CSRC, "stream_formats.h"),
                os.path.join(CSRC, "stream_all.h"), os.path.join(CSRC, "events_plan.h"),

@@ -25,6 +25,8 @@ HEAD_SIGMOID, HEAD_SOFTMAX, HEAD_CTC = 0, 1, 2  # include/wwhip.h: WW_HEAD_*
 PRECISION_FP32, PRECISION_BF16X3 = 0, 1
 OPT_CRNN_SPLIT_AT, OPT_CRNN_SLIDE_MIN, OPT_CRNN_TAIL_MFMA, OPT_WAVENET_ROWMAJOR, OPT_WAVE_SEQ_SEGMENT = 1, 2, 3, 4, 5
 STREAM_FULL_RECOMPUTE, STREAM_TWO_LAUNCH, STREAM_SYNC_WAIT, STREAM_CAUSAL = 1, 2, 4, 8
+STREAM_CTC_STEPS = 16       # a CTC stream bank that also returns per-step posteriors (ww_stream_create_ctc)
+STREAM_CTC_MAX_LABELS = 9   # include/wwhip.h: WW_STREAM_CTC_MAX_LABELS
 SAMPLE_I16, SAMPLE_F32 = 0, 1
 SAMPLE_MULAW, SAMPLE_ALAW = 8, 9  # G.711, one byte per sample: input formats
 SET_MAX_MODELS = 64  # include/wwhip.h: WW_SET_MAX_MODELS
@@ -152,6 +154,10 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_trigger_bank_step_all": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ww_stream_step_trigger_all": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ww_pipeline_bank_step": (C.c_int, [_vp, _vp, _P(PipelineState)]),
+    "ww_stream_create_ctc": (C.c_int, [_vp, _vp, _i32, _P(FrontendParams), C.c_uint32, _P(_vp)]),
+    "ww_stream_step_ctc": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "ww_ctc_trigger_bank_step": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ww_stream_step_ctc_trigger": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ww_superframe_smooth": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp]),
     "ww_far_frr": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),
     "ww_far_frr_dev": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),

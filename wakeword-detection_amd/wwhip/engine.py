@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -1211,3 +1211,116 @@ class StreamBank:
             self.close()
         except Exception:
             pass
+
+
+class CtcTick(NamedTuple):
+    """What :meth:`CtcStreamBank.step` returns: ``labels [S, 2, max_labels]`` int32 padded with -1, ``lengths [S, 2]`` int32 (the whole
+    decoded length, which may exceed ``max_labels``), ``n [S]`` the windows each stream delivered this tick (0, 1 or 2; entries at
+    or past ``n[s]`` are -1 / 0 / 0), and on a ``want_steps`` bank ``steps [S, 2, 19, L]``."""
+    labels: np.ndarray
+    lengths: np.ndarray
+    n: np.ndarray
+    steps: Optional[np.ndarray] = None
+
+
+class CtcStreamBank(StreamBank):
+    """S device-resident streams on one CTC-trained CRNN, advanced 20 ms per :meth:`step` (``ww_stream_create_ctc``,
+    ``ww_stream_step_ctc``): per tick and stream the greedy-decoded labels of its 0, 1 or 2 new windows.
+
+    ``max_labels`` (1..9): labels kept per window.  ``want_steps``: the bank also returns every window's ``[19, L]`` posteriors
+    (``WW_STREAM_CTC_STEPS``; it then always waits for the stream).  ``two_launch`` / ``sync_wait``: :class:`StreamBank`'s, same bits in
+    every form.  ``full_recompute``: a tick's windows through the offline path's kernels - the bits of :meth:`Engine.ctc_forward` on
+    :meth:`window`; the incremental forms agree with it within the float32 bound of the recurrences.  ``sample_rate``,
+    ``sample_format`` and ``resampler`` are :class:`StreamBank`'s.  :meth:`reset`, :meth:`window`, :meth:`set_rate`,
+    :meth:`timeline`, :meth:`close` and the frame-layout attributes work as there; :meth:`feed`, :meth:`set_model` and the other
+    banks' trigger stages are refused."""
+    MAX_LABELS = _lib.STREAM_CTC_MAX_LABELS
+
+    def __init__(self, engine, n_streams: int, fp: Optional[_lib.FrontendParams] = None, max_labels: int = 2, want_steps: bool = False,
+                 two_launch: bool = False, sync_wait: bool = False, full_recompute: bool = False, sample_rate=16000,
+                 sample_format="pcm16", resampler=None) -> None:
+        if isinstance(engine, ModelSet) or not getattr(engine, "is_ctc", False):
+            raise ValueError("CtcStreamBank runs one CTC-trained CRNN (an Engine whose is_ctc is true); StreamBank runs the other models")
+        if not 1 <= int(max_labels) <= self.MAX_LABELS:
+            raise ValueError(f"max_labels {max_labels} outside 1..{self.MAX_LABELS}: a streamed window carries at most {self.MAX_LABELS} labels")
+        self.max_labels, self.want_steps = int(max_labels), bool(want_steps)
+        super().__init__(engine, n_streams, fp, full_recompute=full_recompute, two_launch=two_launch, sync_wait=sync_wait,
+                         sample_rate=sample_rate, resampler=resampler, sample_format=sample_format)
+
+    def _create(self, fp, full_recompute, two_launch, sync_wait, causal, ids) -> None:
+        engine = self.engine
+        self._lib = _lib.load()
+        fp = fp or frontend_params()
+        h = C.c_void_p()
+        flags = ((_lib.STREAM_FULL_RECOMPUTE if full_recompute else 0) | (_lib.STREAM_TWO_LAUNCH if two_launch else 0)
+                 | (_lib.STREAM_SYNC_WAIT if sync_wait else 0) | (_lib.STREAM_CTC_STEPS if self.want_steps else 0))
+        self.causal = False
+        _lib.raise_for(self._lib.ww_stream_create_ctc(engine.ctx.handle, engine.handle, self.S, C.byref(fp), flags, C.byref(h)), engine.ctx.handle)
+        self._h = h
+        _lib.register("streams", self)
+
+    def _tick_arrays(self) -> None:
+        S, M = self.S, self.max_labels
+        self._labels = np.full((S, 2, M), -1, np.int32)
+        self._lengths = np.zeros((S, 2), np.int32)
+        self._steps = np.zeros((S, 2, Engine.CTC_STEPS, self.engine.n_out), np.float32) if self.want_steps else None
+        self._n = np.zeros(S, np.int32)
+        self._flags = np.zeros(S, np.uint8)
+        self._p_labels, self._p_lengths, self._p_n, self._p_flags = (C.c_void_p(a.ctypes.data) for a in (self._labels, self._lengths, self._n, self._flags))
+        self._p_steps = C.c_void_p(self._steps.ctypes.data) if self.want_steps else None
+        self._keep = None
+
+    def step(self, frames: np.ndarray, is_speech: np.ndarray, is_active: Optional[np.ndarray] = None) -> CtcTick:
+        pf = self._frames_address(frames)
+        sp = np.ascontiguousarray(is_speech, dtype=np.uint8).ravel()
+        if sp.size != self.S:
+            raise ValueError("is_speech must have one entry per stream")
+        np.bitwise_and(sp, 1, out=self._flags)
+        if is_active is not None:
+            self._flags |= (np.ascontiguousarray(is_active, dtype=np.uint8).ravel() & 1) << 1
+        self._clear()
+        rc = self._lib.ww_stream_step_ctc(self._h, pf, self._p_flags, self.max_labels, self._p_labels, self._p_lengths, self._p_steps, self._p_n)
+        if rc:
+            _lib.raise_for(rc, self.engine.ctx.handle)
+        return self._tick()
+
+    def _clear(self) -> None:
+        # (the library leaves entries at or past n[s] as they were: what the caller gets there is -1 / 0 / 0, not the last tick's)
+        self._labels[:] = -1
+        self._lengths[:] = 0
+        if self._steps is not None:
+            self._steps[:] = 0.0
+
+    def _tick(self) -> CtcTick:
+        return CtcTick(self._labels.copy(), self._lengths.copy(), self._n.copy(), None if self._steps is None else self._steps.copy())
+
+    def step_ctc_trigger(self, frames: np.ndarray, p_is_speech, p_is_active, p_target, n_target: int, p_state) -> CtcTick:
+        """The wake-word stage of all streams as ONE library call (``ww_stream_step_ctc_trigger``): the tick, the label rule over
+        its decodes and the reset of the streams whose VAD bit fell.  ``p_state`` = (was_speech, fired_ids, n_fired, fall_ids,
+        n_fall), addresses taken once (``CtcWakewordBank`` owns the arrays)."""
+        was_speech, fired, n_fired, fall, n_fall = p_state
+        self._clear()
+        rc = self._lib.ww_stream_step_ctc_trigger(self._h, self._frames_address(frames), p_is_speech, p_is_active, self.max_labels, p_target,
+                                                  int(n_target), was_speech, self._p_labels, self._p_lengths, self._p_steps, self._p_n,
+                                                  fired, n_fired, fall, n_fall)
+        if rc:
+            _lib.raise_for(rc, self.engine.ctx.handle)
+        return self._tick()
+
+    def _refuse(self, what: str):
+        raise ValueError(f"{what}: this bank runs a CTC-trained CRNN: it has step, step_ctc_trigger, reset, window, set_rate and timeline")
+
+    def step_trigger(self, *a, **k):
+        self._refuse("step_trigger")
+
+    def step_trigger_all(self, *a, **k):
+        self._refuse("step_trigger_all")
+
+    def feed(self, *a, **k):
+        self._refuse("feed")
+
+    def feed_all(self, *a, **k):
+        self._refuse("feed_all")
+
+    def set_model(self, *a, **k):
+        self._refuse("set_model")

@@ -14,6 +14,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
+from . import ctc
 from .context import SpeechContext
 from .engine import StreamBank, frontend_params
 from .models import engine_for
@@ -301,6 +302,89 @@ class WakewordSetBank:
     def reset(self) -> None:
         self._bank.reset()
         self.posterior_max[:] = 0.0
+
+    def close(self) -> None:
+        self._bank.close()
+
+
+class CtcWakewordBank:
+    """The wake-word stage of S streams on a CTC-trained CRNN: a :class:`~wwhip.engine.CtcStreamBank` and the trigger's host logic
+    inside one library call per tick (``ww_stream_step_ctc_trigger``).  :class:`WakewordBank`'s bookkeeping - the VAD edge, the
+    reset of the streams whose speech bit fell, ``activate`` once per stream - with another firing rule: a stream that is not active
+    fires on the first window of the tick whose decode starts with ``target`` (``wwhip.ctc.is_wakeword``; the reference's
+    ``eval_CTC`` with ``[HEY][SNIPS]``).
+
+    ``engine``: an :class:`~wwhip.engine.Engine` on a CTC-trained CRNN, from which the stage builds its bank; or ``bank=``: a
+    ``CtcStreamBank`` of the caller's (``engine`` / ``pre_emphasis`` are then not looked at), whose ``max_labels`` must reach
+    ``len(target)``.  ``on_wake(ids)`` is called with the streams that fired this tick.  ``contexts`` and ``frames`` of :meth:`step`
+    are :meth:`WakewordBank.step`'s; it returns the tick (:class:`~wwhip.engine.CtcTick`)."""
+
+    def __init__(self, n_streams: int, engine=None, target: Sequence[int] = ctc.WAKEWORD, bank=None, pre_emphasis: float = 0.0,
+                 on_wake: Optional[Callable[[np.ndarray], None]] = None) -> None:
+        from . import _lib
+        from .engine import CtcStreamBank
+        self.S = int(n_streams)
+        t = np.asarray(target)
+        if t.ndim != 1 or t.size < 1 or t.dtype.kind not in "iu" or t.min() < 0 or t.max() > 7:
+            raise ValueError("target must be a non-empty sequence of labels 0..7")
+        if t.size > _lib.STREAM_CTC_MAX_LABELS:
+            raise ValueError(f"target has {t.size} labels: a streamed window carries at most {_lib.STREAM_CTC_MAX_LABELS}")
+        if bank is None:
+            if engine is None:
+                raise ValueError("CtcWakewordBank needs engine (an Engine on a CTC-trained CRNN), or bank=: a CtcStreamBank")
+            bank = CtcStreamBank(engine, self.S, frontend_params(32767.0, True, pre_emphasis, 160, True), max_labels=max(2, int(t.size)))
+        else:
+            if not hasattr(bank, "step_ctc_trigger"):
+                raise ValueError("CtcWakewordBank: this bank does not decode labels (a StreamBank): its stage is WakewordBank")
+            if getattr(bank, "S", self.S) != self.S:
+                raise ValueError(f"CtcWakewordBank: the bank has {bank.S} streams, the stage {self.S}")
+            if int(bank.max_labels) < t.size:
+                raise ValueError(f"CtcWakewordBank: the bank keeps {bank.max_labels} labels per window, the target has {t.size}")
+        self._bank = bank  # (anything with CtcStreamBank's max_labels / step_ctc_trigger / reset / close: the host-only tests pass a stub)
+        self.target = np.ascontiguousarray(t, np.int32)
+        self._on_wake = on_wake
+        self._was_speech = np.zeros(self.S, np.uint8)
+        self._fired = np.zeros(self.S, np.int32)
+        self._fall = np.zeros(self.S, np.int32)
+        self._counts = np.zeros(2, np.int32)
+        self._n = np.zeros(self.S, np.int32)
+        a = _lib.addr
+        self._p_target = a(self.target)
+        self._p_state = (a(self._was_speech), a(self._fired), a(self._counts[0:1]), a(self._fall), a(self._counts[1:2]))
+        self._bound = None     # (the ContextBank, the addresses of its two flag arrays)
+        self._scratch = None   # flag arrays for the sequence-of-contexts form
+
+    @property
+    def n_post(self) -> np.ndarray:
+        """Windows per stream delivered by the last tick (0, 1 or 2)."""
+        return self._n
+
+    @property
+    def fired_ids(self) -> np.ndarray:
+        """The streams that fired in the last tick."""
+        return self._fired[:self._counts[0]].copy()
+
+    @property
+    def fall_ids(self) -> np.ndarray:
+        """The streams whose VAD bit fell in the last tick (they were reset)."""
+        return self._fall[:self._counts[1]].copy()
+
+    def step(self, contexts, frames: np.ndarray):
+        p_speech, p_active = _flag_addresses(self, contexts)
+        tick = self._bank.step_ctc_trigger(frames, p_speech, p_active, self._p_target, int(self.target.size), self._p_state)
+        self._n = tick.n
+        nf = self._counts[0]
+        if nf:
+            ids = self._fired[:nf].copy()
+            if self._on_wake is not None:
+                self._on_wake(ids)
+            _activate(contexts, ids)
+        return tick
+
+    __call__ = step  # the stage form: bank(contexts, frames)
+
+    def reset(self) -> None:
+        self._bank.reset()
 
     def close(self) -> None:
         self._bank.close()
