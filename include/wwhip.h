@@ -137,7 +137,22 @@ int ww_timer_stop(ww_ctx *ctx, float *elapsed_ms); /* synchronises on the stop e
  * wwhip.weights.pack_blob from the reference's .tflite files:
  *   u32 magic 'WWHB' | u32 version 1 | u32 kind | u32 n_sections
  *   n_sections x { char name[24]; u32 offset_bytes; u32 count }   then 16-byte aligned payload
- * Weights are uploaded once and stay resident in HBM. */
+ * Weights are uploaded once and stay resident in HBM.
+ * Sections of a CRNN (float32 unless said otherwise; G = 3 gate blocks z, r, h for a reset-after GRU, G = 4 blocks i, f, c, o for an
+ * LSTM; H units, F the width of the head's first layer):
+ *   crnn.meta      int32[14]  n_mel, T, C, KF, KT, SF, ST, PF, PT, OF, OT, H, NOUT, HEAD
+ *   crnn.cell      int32[2]   cell (WW_CELL_GRU | WW_CELL_LSTM), F.  OPTIONAL: absent means GRU and F = 2H, and pack_blob writes it
+ *                             only for another cell or another F, so a blob of the shipped combination keeps its bytes.
+ *   crnn.conv_w [C][KF][KT], crnn.conv_b [C]
+ *   crnn.g{1,2}{f,b}.wx [G H][in], .bx [G H], .wh [G H][H], .bh [G H]   layer 1 | 2, forward | backward; in = OF C | 2H.
+ *                             A GRU carries all four; an LSTM has ONE bias, .bx, and carries NO .bh section.
+ *   crnn.head_w1 [F][2H], crnn.head_b1 [F]    (absent for WW_HEAD_CTC), crnn.head_w2 [NOUT][F], crnn.head_b2 [NOUT]
+ * Accepted: H in {16, 32, 48, 64}, F in 1..64, either cell; refused with WW_EBLOB and a text naming the rule: an unknown cell, another
+ * H or F, an LSTM blob with .bh, a GRU blob without, WW_HEAD_CTC on anything but GRU / H = 32.  Everything except (GRU, H = 32,
+ * F = 64, the standard conv) runs the layered path of csrc/crnn.hip (conv_generic_kernel, gemm_nt_kernel, rnn_layer_kernel,
+ * crnn_head_kernel). */
+#define WW_CELL_GRU 0
+#define WW_CELL_LSTM 1
 int ww_model_load(ww_ctx *ctx, const void *blob, size_t len, ww_model **out);
 int ww_model_free(ww_model *model);
 int ww_model_get_info(const ww_model *model, ww_model_info *out);
@@ -151,6 +166,9 @@ int ww_model_get_info(const ww_model *model, ww_model_info *out);
 #define WW_HEAD_SOFTMAX 1
 #define WW_HEAD_CTC 2
 int ww_model_head_kind(const ww_model *model, int32_t *out);
+/* The recurrent layers of a CRNN: cell (WW_CELL_GRU | WW_CELL_LSTM), units H per direction (the encoding is 2H wide) and head_units F
+ * of the head's first dense layer.  WW_EINVAL for a Wavenet or a NULL pointer. */
+int ww_model_rnn_kind(const ww_model *model, int32_t *cell, int32_t *units, int32_t *head_units);
 
 /* Arithmetic of the model contractions.  The reference runs fp32 TFLite kernels; SURVEY 8(d) cfg 3 asks
  * for the Wavenet convs on bf16 MFMA with fp32 accumulate next to an fp32 parity mode.

@@ -361,6 +361,17 @@ int ww_model_head_kind(const ww_model *m, int32_t *out) {
   WW_GUARD_END(m ? m->ctx : nullptr)
 }
 
+int ww_model_rnn_kind(const ww_model *m, int32_t *cell, int32_t *units, int32_t *head_units) {
+  WW_GUARD_BEGIN
+  if (!m || !cell || !units || !head_units) return WW_EINVAL;
+  if (m->kind != WW_KIND_CRNN) return ww_fail(m->ctx, WW_EINVAL, "ww_model_rnn_kind: the model is not a CRNN");
+  *cell = m->crnn.CELL;
+  *units = m->crnn.H;
+  *head_units = m->crnn.F;
+  return WW_OK;
+  WW_GUARD_END(m ? m->ctx : nullptr)
+}
+
 int ww_model_set_precision(ww_model *m, int precision) {
   WW_GUARD_BEGIN
   if (!m) return WW_EINVAL;

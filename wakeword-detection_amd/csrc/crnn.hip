@@ -11,6 +11,9 @@
 //   generic path       any other conv geometry (utils/CRNN_files/*_old.tflite): conv_generic_kernel, gemm_nt_kernel
 //                      (C = A W^T + b, 64x64x64 tiles, fp32 MFMA, XCD-aware tile order), gru_generic_kernel,
 //                      crnn_detect_kernel.
+//   other cells        an LSTM, a GRU of 16, 48 or 64 units, a head of another width than 64 (what the trainer's tuner can pick):
+//                      the generic path with rnn_layer_kernel<CELL, H> for the recurrences and crnn_head_kernel for the head,
+//                      whatever the conv geometry.
 // Round 1's three-kernel chain (conv5x20_kernel -> gemm_nt_kernel -> gru_head_kernel, 52 us per 256 windows against
 // 34 us fused) and its bf16x6 projection GEMM are gone; their measurements are in DESIGN.md 7.1.
 #include "stream_fe.h"
@@ -2274,6 +2277,32 @@ __global__ __launch_bounds__(64) void crnn_detect_kernel(const float *enc, const
   if (lane < NOUT) out[(size_t)w * NOUT + lane] = p;
 }
 
+// The detect head at any width: enc [Nw][E] (E = 2H <= 128) -> Dense(F <= 64, relu) -> Dense(NOUT <= 8) -> sigmoid | softmax, one wave
+// per row.  crnn_detect_kernel's association: one fmaf chain in k order from zero, the bias last, then head_activation.
+__global__ __launch_bounds__(64) void crnn_head_kernel(const float *enc, const float *w1, const float *b1, const float *w2, const float *b2,
+                                                       float *out, int E, int F, int NOUT, int HEAD) {
+  __shared__ float e[128], hid[64];
+  const int lane = threadIdx.x, w = blockIdx.x;
+  for (int k = lane; k < E; k += 64) e[k] = enc[(size_t)w * E + k];
+  __syncthreads();
+  if (lane < F) {
+    float acc = 0.f;
+    for (int k = 0; k < E; ++k) acc = fmaf(w1[lane * E + k], e[k], acc);
+    hid[lane] = fmaxf(acc + b1[lane], 0.f);
+  }
+  __syncthreads();
+  float y = 0.f;
+  if (lane < NOUT) {
+    for (int k = 0; k < F; ++k) y = fmaf(w2[lane * F + k], hid[k], y);
+    y += b2[lane];
+  }
+  const float p = head_activation(y, lane, NOUT, HEAD);
+  if (lane < NOUT) out[(size_t)w * NOUT + lane] = p;
+}
+
+// the cell every kernel above rnn_layer_kernel is written for
+static bool crnn_std_cell(const ww_crnn_dev &c) { return c.CELL == WW_CELL_GRU && c.H == GR_H && c.F == 2 * GR_H; }
+
 // A CTC-trained CRNN (WW_HEAD_CTC) has no Dense(64, relu) -> Dense(n_out) head on its last states: every launcher of this file that
 // evaluates that head answers it here, before anything is enqueued (ww_k_crnn_ctc_forward below is its way in).  The zero-filled w1 / b1
 // of its device block (model_pack.h) are the second line of defence, not the first.
@@ -2288,6 +2317,12 @@ int ww_k_crnn_detect(ww_ctx *ctx, const ww_model *m, const float *d_enc, int nw,
   if (int rc = ww_crnn_refuse_ctc(ctx, m, "ww_k_crnn_detect")) return rc;
   if (nw <= 0) return WW_OK;
   const ww_crnn_dev &c = m->crnn;
+  if (!crnn_std_cell(c)) {
+    ww_launch_scope scope(ctx, "crnn_head_kernel");
+    hipLaunchKernelGGL(crnn_head_kernel, dim3(nw), dim3(64), 0, ctx->stream, d_enc, c.w1, c.b1, c.w2, c.b2, d_out, 2 * c.H, c.F, c.NOUT, c.HEAD);
+    WW_HIP(ctx, hipGetLastError());
+    return WW_OK;
+  }
   ww_launch_scope scope(ctx, "crnn_detect_kernel");
   hipLaunchKernelGGL(crnn_detect_kernel, dim3(nw), dim3(64), 0, ctx->stream, d_enc, c.w1, c.b1, c.w2, c.b2, d_out, c.NOUT, c.HEAD);
   WW_HIP(ctx, hipGetLastError());
@@ -2385,9 +2420,181 @@ __global__ __launch_bounds__(128) void gru_generic_kernel(grug_args a) {
   if (a.last && half == 0) a.last[(size_t)w * 2 * H + dir * H + unit] = h_own;
 }
 
+// ------------------------------------------------------------------------------------------
+// The cells the trainer's tuner can pick besides the shipped one (wwdetect/CRNN/train.py:112-125): a reset-after GRU or an LSTM of
+// H = 16, 32, 48 or 64 units.  rnn_layer_kernel<CELL, H> is gru_generic_kernel's place in the layered path for them: one workgroup
+// per window, both directions, gx [Nw][OT][2 G H] from the GEMM (G = 3 gate blocks z, r, h | 4 blocks i, f, c, o), the states to
+// seq [Nw][OT][seq_ld] (forward | backward, then zeros up to seq_ld) and / or the last ones to last [Nw][2H].
+//
+// Lane map.  A direction is TPD threads, unit u = LPU lanes ("slices"), slice s holds the KS = H / LPU columns [s KS, (s + 1) KS) of
+// the unit's G rows of W_h in registers (G KS floats: at most 128, LSTM of 64 units):
+//     H    LPU  TPD  KS   waves per direction
+//     16    4    64   4   1
+//     32    2    64  16   1
+//     48    2   128  24   2  (lanes 96..127 of a direction hold no unit: zero weights, no load, no store; their DPP partners are idle too)
+//     64    2   128  32   2
+// h ping-pongs through LDS.  A one-wave direction orders it with wsync_h (LDS traffic of one wave is served in issue order); a
+// two-wave direction meets at lds_barrier() once per step - both directions run the same OT steps and no lane leaves the loop, so
+// the workgroup barrier is uniform.  The next step's G projected inputs are in flight while this step computes.
+//
+// ONE association of a gate's pre-activation (gru_step's, extended to LPU slices): per slice s an even-k and an odd-k fmaf chain over
+// the slice's columns, k ascending (the two halves of a packed fp32 FMA),
+//     E_s: k = s KS, s KS + 2, ..      O_s: k = s KS + 1, s KS + 3, ..
+// E_0 starts from the projected input x (from 0 for the GRU's candidate gate, whose x joins as tanh(x_c + r * hc)), O_0 from b_h (0
+// for an LSTM, whose one bias is in x), every other chain from 0; a slice's value is E_s + O_s and the slices are joined by a fixed
+// DPP tree: v += v[lane ^ 1], then for LPU = 4 v += v[lane ^ 2].  At (GRU, 32) this is (E0 + O0) + (E1 + O1), gru_step's bits.
+// LSTM (Keras order i, f, c, o): c' = f c + i g, h' = o tanh(c') with g = tanh(pre_c), spelled out as gru_blend is.
+// ------------------------------------------------------------------------------------------
+template <int CELL, int H>
+struct rnn_cfg {
+  static_assert((CELL == WW_CELL_GRU || CELL == WW_CELL_LSTM) && (H == 16 || H == 32 || H == 48 || H == 64), "cells of 16, 32, 48, 64 units");
+  static constexpr int G = CELL == WW_CELL_LSTM ? 4 : 3;
+  static constexpr int LPU = H == 16 ? 4 : 2;
+  static constexpr int TPD = H * LPU <= 64 ? 64 : 128;
+  static constexpr int KS = H / LPU;
+  static_assert(KS % 4 == 0 && H * LPU <= TPD && TPD % 64 == 0, "a slice is whole float4s; a direction is whole waves");
+};
+
+struct rnn_args {
+  const float *gx;   // [Nw][OT][2*G*H] input projections incl. b_x
+  const float *wh;   // [2][G*H][H]
+  const float *bh;   // [2][G*H] (zeros for an LSTM)
+  float *seq;        // [Nw][OT][seq_ld] (fwd | bwd | zeros) or nullptr
+  float *last;       // [Nw][2H] (fwd_last | bwd_last) or nullptr
+  int OT, seq_ld;
+};
+
+__device__ __forceinline__ float swap_quad2(float v) {
+  // value of lane ^ 2: DPP quad_perm [2,3,0,1]
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true));
+}
+
+__device__ __forceinline__ float lstm_cell(float i, float f, float g, float c) { return __fmaf_rn(f, c, __fmul_rn(i, g)); }
+__device__ __forceinline__ float lstm_out(float o, float c) { return __fmul_rn(o, fast_tanh(c)); }
+
+template <int CELL, int H>
+__global__ __launch_bounds__((2 * rnn_cfg<CELL, H>::TPD)) void rnn_layer_kernel(rnn_args a) {
+  using cfg = rnn_cfg<CELL, H>;
+  constexpr int G = cfg::G, LPU = cfg::LPU, TPD = cfg::TPD, KS = cfg::KS, NQ = KS / 4, GX = 2 * G * H;
+  __shared__ __align__(16) float hbuf[2][2][H];
+  const int tid = threadIdx.x;
+  const int dir = __builtin_amdgcn_readfirstlane(tid / TPD);  // (whole waves per direction)
+  const int lt = tid - dir * TPD, unit = lt / LPU, slice = lt % LPU;
+  const bool live = unit < H, own = live && slice == 0;  // own: the lane that carries the unit's state and stores it
+  const int w = blockIdx.x, OT = a.OT;
+
+  f32x2 wv[G][2 * NQ];
+  float bh[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const float *row = a.wh + ((size_t)dir * G * H + (size_t)g * H + (live ? unit : 0)) * H + slice * KS;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (live) v = *(const float4 *)(row + 4 * q);
+      wv[g][2 * q] = (f32x2){v.x, v.y};
+      wv[g][2 * q + 1] = (f32x2){v.z, v.w};
+    }
+    bh[g] = own ? a.bh[dir * G * H + g * H + unit] : 0.f;  // slice 0's odd-k chain starts from b_h, every other one from zero
+  }
+  for (int i = tid; i < 2 * 2 * H; i += 2 * TPD) (&hbuf[0][0][0])[i] = 0.f;
+  // the pad columns [2H, seq_ld) of every row, on every call: the next GEMM multiplies them by zero weights, and the workspace is
+  // reused - 0 * NaN is NaN
+  if (a.seq && a.seq_ld > 2 * H) {
+    const int pad = a.seq_ld - 2 * H;
+    for (int i = tid; i < OT * pad; i += 2 * TPD) {
+      const int t = i / pad, col = i - t * pad;
+      a.seq[((size_t)w * OT + t) * a.seq_ld + 2 * H + col] = 0.f;
+    }
+  }
+  __syncthreads();
+
+  const float *gxl = a.gx + (size_t)w * OT * GX + dir * G * H + (live ? unit : 0);
+  int t = dir ? OT - 1 : 0;
+  float x[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) x[g] = own ? gxl[(size_t)t * GX + g * H] : 0.f;
+  float h_own = 0.f, c_own = 0.f;
+  for (int s = 0; s < OT; ++s) {
+    const int cur = s & 1;
+    const int tn = dir ? t - 1 : t + 1;
+    float nx[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) nx[g] = 0.f;
+    if (own && s + 1 < OT) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) nx[g] = gxl[(size_t)tn * GX + g * H];
+    }
+    const float4 *hp = (const float4 *)(&hbuf[dir][cur][slice * KS]);
+    float4 hv[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) hv[q] = hp[q];
+    f32x2 acc[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) acc[g] = (f32x2){(CELL == WW_CELL_GRU && g == 2) ? 0.f : x[g], bh[g]};  // (x and bh are 0 off slice 0)
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const f32x2 h0 = {hv[q].x, hv[q].y}, h1 = {hv[q].z, hv[q].w};
+#pragma unroll
+      for (int g = 0; g < G; ++g) acc[g] = __builtin_elementwise_fma(wv[g][2 * q], h0, acc[g]);
+#pragma unroll
+      for (int g = 0; g < G; ++g) acc[g] = __builtin_elementwise_fma(wv[g][2 * q + 1], h1, acc[g]);
+    }
+    float pre[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      float v = acc[g].x + acc[g].y;
+      v += swap_pair(v);
+      if (LPU == 4) v += swap_quad2(v);
+      pre[g] = v;
+    }
+    if (CELL == WW_CELL_GRU) {
+      const float z = fast_sigmoid(pre[0]), r = fast_sigmoid(pre[1]);
+      h_own = gru_blend(z, h_own, gru_candidate(r, pre[2], x[2]));
+    } else {
+      const float ig = fast_sigmoid(pre[0]), fg = fast_sigmoid(pre[1]), gg = fast_tanh(pre[2]), og = fast_sigmoid(pre[G - 1]);
+      c_own = lstm_cell(ig, fg, gg, c_own);
+      h_own = lstm_out(og, c_own);
+    }
+    if (own) {
+      hbuf[dir][cur ^ 1][unit] = h_own;
+      if (a.seq) a.seq[((size_t)w * OT + t) * a.seq_ld + dir * H + unit] = h_own;
+    }
+    if (TPD == 64) wsync_h();
+    else lds_barrier();
+#pragma unroll
+    for (int g = 0; g < G; ++g) x[g] = nx[g];
+    t = tn;
+  }
+  if (a.last && own) a.last[(size_t)w * 2 * H + dir * H + unit] = h_own;
+}
+
+static int crnn_gates(const ww_crnn_dev &c) { return c.CELL == WW_CELL_LSTM ? 4 : 3; }
+
+template <int CELL, int H>
+static void launch_rnn_layer_as(ww_ctx *ctx, const rnn_args &a, int nw) {
+  hipLaunchKernelGGL((rnn_layer_kernel<CELL, H>), dim3(nw), dim3(2 * rnn_cfg<CELL, H>::TPD), 0, ctx->stream, a);
+}
+
+static int launch_rnn_layer(ww_ctx *ctx, const ww_crnn_dev &c, const char *name, const rnn_args &a, int nw) {
+  ww_launch_scope scope(ctx, name);
+  switch (c.CELL * 100 + c.H) {
+    case 16: launch_rnn_layer_as<WW_CELL_GRU, 16>(ctx, a, nw); break;
+    case 32: launch_rnn_layer_as<WW_CELL_GRU, 32>(ctx, a, nw); break;
+    case 48: launch_rnn_layer_as<WW_CELL_GRU, 48>(ctx, a, nw); break;
+    case 64: launch_rnn_layer_as<WW_CELL_GRU, 64>(ctx, a, nw); break;
+    case 116: launch_rnn_layer_as<WW_CELL_LSTM, 16>(ctx, a, nw); break;
+    case 132: launch_rnn_layer_as<WW_CELL_LSTM, 32>(ctx, a, nw); break;
+    case 148: launch_rnn_layer_as<WW_CELL_LSTM, 48>(ctx, a, nw); break;
+    case 164: launch_rnn_layer_as<WW_CELL_LSTM, 64>(ctx, a, nw); break;
+    default: return ww_fail(ctx, WW_EINTERNAL, "no recurrence kernel for cell %d of %d units (the loader should have refused it)", c.CELL, c.H);
+  }
+  return WW_OK;
+}
+
 static size_t crnn_generic_workspace(const ww_crnn_dev &c, int nw) {
   const size_t rows = (size_t)nw * c.OT;
-  return ww_bump::need(rows * c.FEATP, 4) + ww_bump::need(rows * 6 * c.H, 4) + ww_bump::need(rows * 2 * c.H, 4) +
+  return ww_bump::need(rows * c.FEATP, 4) + ww_bump::need(rows * 2 * crnn_gates(c) * c.H, 4) + ww_bump::need(rows * c.SEQP, 4) +
          ww_bump::need((size_t)nw * 2 * c.H, 4) + 1024;
 }
 
@@ -2404,7 +2611,8 @@ static int crnn_forward_generic(ww_ctx *ctx, const ww_model *m, const win_addr &
   const ww_crnn_dev &c = m->crnn;
   const size_t rows = (size_t)nw * c.OT;
   ww_bump b(ws, ~size_t(0));
-  float *feat = b.take<float>(rows * c.FEATP), *gx = b.take<float>(rows * 6 * c.H), *seq = b.take<float>(rows * 2 * c.H);
+  const int GX = 2 * crnn_gates(c) * c.H;  // gate rows of both directions (6 H for a GRU)
+  float *feat = b.take<float>(rows * c.FEATP), *gx = b.take<float>(rows * GX), *seq = b.take<float>(rows * c.SEQP);
   float *enc = b.take<float>((size_t)nw * 2 * c.H);
   if (d_enc) enc = d_enc;
   {
@@ -2412,7 +2620,17 @@ static int crnn_forward_generic(ww_ctx *ctx, const ww_model *m, const win_addr &
     ww_launch_scope scope(ctx, "conv_generic_kernel");
     hipLaunchKernelGGL(conv_generic_kernel, dim3(nw), dim3(256), (size_t)c.T * c.n_mel * sizeof(float), ctx->stream, a);
   }
-  launch_gemm(ctx, "gemm_nt_kernel<gru1,generic>", feat, c.wx1p, c.bx1, gx, (int)rows, 6 * c.H, c.FEATP);
+  launch_gemm(ctx, "gemm_nt_kernel<gru1,generic>", feat, c.wx1p, c.bx1, gx, (int)rows, GX, c.FEATP);
+  if (!crnn_std_cell(c)) {
+    // any cell but the shipped one: rnn_layer_kernel; layer 1's sequence has rows of SEQP (wx2 is packed to match: model_pack.h)
+    const rnn_args a1 = {gx, c.wh1, c.bh1, seq, nullptr, c.OT, c.SEQP};
+    if (int rc = launch_rnn_layer(ctx, c, "rnn_layer_kernel<seq>", a1, nw)) return rc;
+    launch_gemm(ctx, "gemm_nt_kernel<gru2,generic>", seq, c.wx2, c.bx2, gx, (int)rows, GX, c.SEQP);
+    const rnn_args a2 = {gx, c.wh2, c.bh2, nullptr, enc, c.OT, c.SEQP};
+    if (int rc = launch_rnn_layer(ctx, c, "rnn_layer_kernel<last>", a2, nw)) return rc;
+    WW_HIP(ctx, hipGetLastError());
+    return ww_k_crnn_detect(ctx, m, enc, nw, d_out);
+  }
   {
     grug_args a = {gx, c.wh1, c.bh1, seq, nullptr, c.OT};
     ww_launch_scope scope(ctx, "gru_generic_kernel<seq>");

@@ -40,8 +40,13 @@ struct ww_crnn_geom {
   int n_mel = 0, T = 0, C = 0, KF = 0, KT = 0, SF = 0, ST = 0, PF = 0, PT = 0, OF = 0, OT = 0, H = 0, NOUT = 0, HEAD = 0;
   // Any other conv geometry (utils/CRNN_files/*_old.tflite: 20x5 kernel, stride 8x2, VALID, 74 steps of 96 features)
   // takes the generic kernels of crnn.hip: direct conv, the same MFMA GEMM on K padded to FEATP, step-wise GRUs.
+  // So does every recurrent cell but the shipped one (a reset-after GRU of 32 units under a 64-wide head): an LSTM, H = 16, 48, 64 or a
+  // head of another width runs rnn_layer_kernel / crnn_head_kernel behind the same conv and GEMM, whatever its conv geometry.
   bool generic = false;
   int FEATP = 0;  // OF*C rounded up to the GEMM's K tile (64)
+  int CELL = 0;   // WW_CELL_GRU | WW_CELL_LSTM: G = 3 (z, r, h) or 4 (i, f, c, o) gate blocks of H rows
+  int F = 0;      // width of the head's first dense layer, 1..64
+  int SEQP = 0;   // 2H rounded up to the GEMM's K tile: row stride of the layer-1 sequence and of wx2 on the layered path
 };
 
 struct ww_wave_geom {
@@ -72,17 +77,18 @@ struct ww_crnn_dev : ww_crnn_geom {
   float *conv_w = nullptr;   // [CV_KPAD/4][32][4] (MFMA B-operand order); generic: conv_wt
   float *conv_b = nullptr;   // [C]
   float *wx1s = nullptr;     // W_x1 [2*3H][OF*C] (rows: fwd z,r,h then bwd z,r,h) in MFMA B-operand order [OF*C/4][2*3H][4] (crnn_fused_kernel)
+  // (G = 3 gate blocks z, r, h of a GRU, 4 blocks i, f, c, o of an LSTM, wherever 3H stands below)
   float *bx1 = nullptr;      // [2*3H]
   float *wh1 = nullptr;      // [2][3H][H]
-  float *bh1 = nullptr;      // [2][3H]
-  float *wx2 = nullptr;      // [2*3H][2H]
+  float *bh1 = nullptr;      // [2][3H]; zeros for an LSTM (its one bias is bx)
+  float *wx2 = nullptr;      // [2*3H][SEQP]: [2*3H][2H] where 2H is a multiple of 64, zero padded behind column 2H otherwise
   float *wx2s = nullptr;     // the same in MFMA B-operand order [2H/4][2*3H][4]
   unsigned short *cwb = nullptr;   // split-bf16 mode: conv weights hi/lo planes in A-operand order (crnn_fused_bf16_kernel)
   unsigned short *wx1b = nullptr;  // split-bf16 mode: W_x1 hi/lo planes in B-operand order
   float *bx2 = nullptr;
   float *wh2 = nullptr;
   float *bh2 = nullptr;
-  float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;
+  float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;  // head: w1 [F][2H], b1 [F], w2 [NOUT][F], b2 [NOUT]
   // generic geometry (ww_crnn_geom::generic)
   float *conv_wt = nullptr;    // [KF*KT][C]  (k-major for the implicit GEMM)
   float *conv_wL = nullptr, *conv_wR = nullptr;  // conv_w with the taps that meet a window's zero padding cleared (first 6 / last 7 frames): crnn_rows_kernel

@@ -94,6 +94,12 @@ struct blob_view {
       return pm.fail(WW_EBLOB, "blob section %s missing or has %u elements (expected %zu)", name, cnt, expect);
     return WW_OK;
   }
+  // whether the section table names `name` at all (its extent may still lie outside the blob)
+  bool has(const char *name) const {
+    for (uint32_t i = 0; i < n; ++i)
+      if (strncmp((const char *)(base + 16 + 32 * (size_t)i), name, 24) == 0) return true;
+    return false;
+  }
   // an int32 section of exactly `expect` words
   bool ints(const char *name, size_t expect, std::vector<int32_t> &out) const { return words(name, out) && out.size() == expect; }
 };
@@ -286,20 +292,44 @@ inline int pack_crnn(ww_packed_model &pm, const blob_view &bv) {
   // stages a window in 4 * T * n_mel <= 65,536 bytes of dynamic LDS, the most a launch is given without hipFuncSetAttribute.
   const int LIM = 16384;
   auto in = [](int x, int lo, int hi) { return x >= lo && x <= hi; };
-  if (c.H != 32 || !in(c.C, 1, 64) || !in(c.NOUT, 1, 8) || c.n_mel != pm.filt.n_mel || !in(c.T, 1, LIM) ||
+  // the optional crnn.cell = [cell, F] (wwhip/weights.py writes it only for what crnn.meta cannot say): absent, a GRU under a 2H-wide
+  // head.  Each word is tested before anything is computed from it - F = 2 * H below only once H is one of four values.
+  if (c.H != 16 && c.H != 32 && c.H != 48 && c.H != 64)
+    return pm.fail(WW_EBLOB, "unsupported CRNN recurrent width H = %d (the cells are built for 16, 32, 48 and 64 units)", c.H);
+  c.CELL = WW_CELL_GRU;
+  c.F = 2 * c.H;
+  if (bv.has("crnn.cell")) {
+    std::vector<int32_t> cell;
+    if (!bv.ints("crnn.cell", 2, cell)) return pm.fail(WW_EBLOB, "blob section crnn.cell is not two words [cell, F] inside the blob");
+    if (cell[0] != WW_CELL_GRU && cell[0] != WW_CELL_LSTM)
+      return pm.fail(WW_EBLOB, "unknown CRNN recurrent cell %d (0 GRU, 1 LSTM)", cell[0]);
+    if (!in(cell[1], 1, 64)) return pm.fail(WW_EBLOB, "unsupported CRNN head width F = %d (the head takes 1..64)", cell[1]);
+    c.CELL = cell[0];
+    c.F = cell[1];
+  }
+  // (a CTC head has no first layer, so no F of its own: its blob is refused by the CTC rule below, which names the cell it takes)
+  if (c.F > 64 && c.HEAD != WW_HEAD_CTC) return pm.fail(WW_EBLOB, "unsupported CRNN head width F = %d (2H without crnn.cell; the head takes 1..64)", c.F);
+  if (!in(c.C, 1, 64) || !in(c.NOUT, 1, 8) || c.n_mel != pm.filt.n_mel || !in(c.T, 1, LIM) ||
       (int64_t)c.T * c.n_mel > LIM || !in(c.KF, 1, LIM) || !in(c.KT, 1, LIM) || !in(c.SF, 1, LIM) || !in(c.ST, 1, LIM) ||
       !in(c.OF, 1, LIM) || !in(c.OT, 1, LIM) || !in(c.PF, 0, LIM) || !in(c.PT, 0, LIM))
     return pm.fail(WW_EBLOB, "unsupported CRNN geometry (C=%d H=%d K=%dx%d stride %dx%d)", c.C, c.H, c.KF, c.KT, c.SF, c.ST);
   const int K = c.KF * c.KT;
   // the geometry of wwdetect/CRNN/train.py:27-49 (every current export) runs on the kernels built for it
-  c.generic = !(c.C == 32 && c.n_mel == 40 && c.T == 151 && c.KF == 5 && c.KT == 20 && c.SF == 2 && c.ST == 8 && c.PF == 1 &&
-                c.PT == 6 && c.OF == 20 && c.OT == 19);
+  const bool std_conv = c.C == 32 && c.n_mel == 40 && c.T == 151 && c.KF == 5 && c.KT == 20 && c.SF == 2 && c.ST == 8 && c.PF == 1 &&
+                        c.PT == 6 && c.OF == 20 && c.OT == 19;
+  // ... and so does the cell they are built for: a reset-after GRU of 32 units under a 64-wide head
+  const bool std_cell = c.CELL == WW_CELL_GRU && c.H == 32 && c.F == 64;
+  c.generic = !(std_conv && std_cell);
   c.FEATP = (c.OF * c.C + 63) / 64 * 64;
+  c.SEQP = (2 * c.H + 63) / 64 * 64;
   if (!in(c.HEAD, WW_HEAD_SIGMOID, WW_HEAD_CTC)) return pm.fail(WW_EBLOB, "unknown CRNN head kind %d (0 sigmoid, 1 softmax, 2 CTC)", c.HEAD);
   if (c.HEAD == WW_HEAD_CTC) {
     // gru_tail_ctc_kernel (crnn.hip) is built for the 19 steps of the standard geometry and deals its softmax rows to groups of eight
     // lanes; a CTC output needs a label and the blank.  Whatever loads, ww_ctc_* can launch.
     std::vector<float> none;
+    if (!(c.CELL == WW_CELL_GRU && c.H == 32))
+      return pm.fail(WW_EBLOB, "a CTC head (HEAD = 2) takes a GRU of 32 units only, not cell %d of %d units", c.CELL, c.H);
+    if (!std_cell) return pm.fail(WW_EBLOB, "a CTC head (HEAD = 2) has no first dense layer: crnn.cell gives F = %d", c.F);
     if (c.generic) return pm.fail(WW_EBLOB, "a CTC head (HEAD = 2) takes the standard conv geometry only (19 steps of 640 features)");
     if (!in(c.NOUT, 2, 8)) return pm.fail(WW_EBLOB, "a CTC head (HEAD = 2) has 2..8 classes (labels + blank), not %d", c.NOUT);
     if (bv.words("crnn.head_w1", none) || bv.words("crnn.head_b1", none))
@@ -332,7 +362,14 @@ inline int pack_crnn(ww_packed_model &pm, const blob_view &bv) {
     pm.add("crnn.conv_wt", wt);  // (ww_model_load: conv_w is this array too)
   }
   pm.add("crnn.conv_b", cb);
-  const int G = 3 * c.H;
+  const int G = (c.CELL == WW_CELL_LSTM ? 4 : 3) * c.H;  // gate rows of one direction
+  {  // a Keras LSTM has ONE bias (it travels as bx); a reset-after GRU has two
+    static const char *const bhs[4] = {"crnn.g1f.bh", "crnn.g1b.bh", "crnn.g2f.bh", "crnn.g2b.bh"};
+    for (const char *name : bhs) {
+      if (c.CELL == WW_CELL_LSTM && bv.has(name)) return pm.fail(WW_EBLOB, "an LSTM blob carries %s: an LSTM has one bias, bx", name);
+      if (c.CELL == WW_CELL_GRU && !bv.has(name)) return pm.fail(WW_EBLOB, "a GRU blob lacks %s: a reset-after GRU has a recurrent bias", name);
+    }
+  }
   auto cat2 = [&](const char *a, const char *b, size_t each, std::vector<float> &out) -> int {
     std::vector<float> vb;
     if (!bv.words(a, out) || !bv.words(b, vb) || out.size() != each || vb.size() != each)
@@ -343,7 +380,15 @@ inline int pack_crnn(ww_packed_model &pm, const blob_view &bv) {
   std::vector<float> v;
   int rc;
   const size_t in1 = (size_t)c.OF * c.C, in2 = 2 * (size_t)c.H;
-  if ((rc = cat2("crnn.g1f.wx", "crnn.g1b.wx", G * in1, v))) return rc;  // W_x1 [2*3H][OF*C], rows: fwd z,r,h then bwd z,r,h
+  // for an LSTM the device block holds a zero bh of the usual size: no kernel argument is ever null
+  auto bh2 = [&](const char *a, const char *b, std::vector<float> &out) -> int {
+    if (c.CELL == WW_CELL_LSTM) {
+      out.assign(2 * (size_t)G, 0.f);
+      return WW_OK;
+    }
+    return cat2(a, b, G, out);
+  };
+  if ((rc = cat2("crnn.g1f.wx", "crnn.g1b.wx", G * in1, v))) return rc;  // W_x1 [2*G][OF*C], rows: fwd gates then bwd gates
   if (!c.generic) {
     pm.add("crnn.wx1s", pack_k4(v, 2 * G, in1));
     {  // W_x1 [192][640] -> [plane][k-step 20][n-tile 12][lane = g*16 + j][8]: element e is W[nt*16 + j][ks*32 + 8 g + e]
@@ -389,19 +434,28 @@ inline int pack_crnn(ww_packed_model &pm, const blob_view &bv) {
   }
   if ((rc = cat2("crnn.g1f.bx", "crnn.g1b.bx", G, v))) return rc; pm.add("crnn.bx1", v);
   if ((rc = cat2("crnn.g1f.wh", "crnn.g1b.wh", (size_t)G * c.H, v))) return rc; pm.add("crnn.wh1", v);
-  if ((rc = cat2("crnn.g1f.bh", "crnn.g1b.bh", G, v))) return rc; pm.add("crnn.bh1", v);
-  if ((rc = cat2("crnn.g2f.wx", "crnn.g2b.wx", G * in2, v))) return rc; pm.add("crnn.wx2", v);
+  if ((rc = bh2("crnn.g1f.bh", "crnn.g1b.bh", v))) return rc; pm.add("crnn.bh1", v);
+  if ((rc = cat2("crnn.g2f.wx", "crnn.g2b.wx", G * in2, v))) return rc;
+  if ((size_t)c.SEQP == in2) {
+    pm.add("crnn.wx2", v);
+  } else {
+    // gemm_nt_kernel walks K in whole blocks of 64: at 2H = 32 or 96 layer 2's operand rows are SEQP wide, zero padded, as wx1p's
+    // are FEATP wide (the layer-1 sequence has the same row stride, its pad columns written as zeros by rnn_layer_kernel)
+    std::vector<float> wp((size_t)2 * G * c.SEQP, 0.f);
+    for (int r = 0; r < 2 * G; ++r) memcpy(&wp[(size_t)r * c.SEQP], &v[(size_t)r * in2], in2 * sizeof(float));
+    pm.add("crnn.wx2", wp);
+  }
   pm.add("crnn.wx2s", pack_k4(v, 2 * G, in2));
   if ((rc = cat2("crnn.g2f.bx", "crnn.g2b.bx", G, v))) return rc; pm.add("crnn.bx2", v);
   if ((rc = cat2("crnn.g2f.wh", "crnn.g2b.wh", (size_t)G * c.H, v))) return rc; pm.add("crnn.wh2", v);
-  if ((rc = cat2("crnn.g2f.bh", "crnn.g2b.bh", G, v))) return rc; pm.add("crnn.bh2", v);
+  if ((rc = bh2("crnn.g2f.bh", "crnn.g2b.bh", v))) return rc; pm.add("crnn.bh2", v);
   // a CTC head has no first layer: its w1 / b1 are zeros of the same size, so that no kernel argument of any form is a null pointer
   // (the launchers refuse a CTC model long before: crnn.hip, ww_crnn_refuse_ctc)
-  std::vector<float> w1(in2 * in2, 0.f), b1(in2, 0.f);
+  std::vector<float> w1((size_t)c.F * in2, 0.f), b1((size_t)c.F, 0.f);  // w1 [F][2H]
   if (c.HEAD != WW_HEAD_CTC) {
-    if ((rc = bv.floats(pm, "crnn.head_w1", in2 * in2, w1)) || (rc = bv.floats(pm, "crnn.head_b1", in2, b1))) return rc;
+    if ((rc = bv.floats(pm, "crnn.head_w1", (size_t)c.F * in2, w1)) || (rc = bv.floats(pm, "crnn.head_b1", (size_t)c.F, b1))) return rc;
   }
-  NEED_F(w2, "crnn.head_w2", (size_t)c.NOUT * in2);
+  NEED_F(w2, "crnn.head_w2", (size_t)c.NOUT * (c.HEAD == WW_HEAD_CTC ? in2 : (size_t)c.F));
   NEED_F(b2, "crnn.head_b2", c.NOUT);
   pm.add("crnn.w1", w1); pm.add("crnn.b1", b1); pm.add("crnn.w2", w2); pm.add("crnn.b2", b2);
   pm.info.window = c.T; pm.info.n_out = c.NOUT; pm.info.enc_width = 2 * c.H;

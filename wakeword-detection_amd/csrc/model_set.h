@@ -72,7 +72,7 @@ static inline bool ww_set_same_filter(const ww_filter_geom &a, const ww_filter_g
 static inline bool ww_set_same_crnn(const ww_crnn_geom &a, const ww_crnn_geom &b) {
   return a.n_mel == b.n_mel && a.T == b.T && a.C == b.C && a.KF == b.KF && a.KT == b.KT && a.SF == b.SF && a.ST == b.ST && a.PF == b.PF &&
          a.PT == b.PT && a.OF == b.OF && a.OT == b.OT && a.H == b.H && a.NOUT == b.NOUT && a.HEAD == b.HEAD && a.generic == b.generic &&
-         a.FEATP == b.FEATP;
+         a.FEATP == b.FEATP && a.CELL == b.CELL && a.F == b.F && a.SEQP == b.SEQP;
 }
 static inline bool ww_set_same_wave(const ww_wave_geom &a, const ww_wave_geom &b) {
   return a.T == b.T && a.n_mel == b.n_mel && a.C == b.C && a.S == b.S && a.NB == b.NB && a.NOUT == b.NOUT && a.dil == b.dil &&
@@ -90,6 +90,9 @@ static inline int ww_set_check(const ww_set_member *mem, int32_t n, const void *
     if (m.kind != WW_KIND_CRNN && m.kind != WW_KIND_WAVENET) return ww_set_refuse(err, cap, "member %d is of unknown kind %d", k, m.kind);
     if (m.precision != WW_PRECISION_FP32)
       return ww_set_refuse(err, cap, "member %d is in split-bf16 mode: model sets are fp32 only", k);
+    if (m.kind == WW_KIND_CRNN && m.crnn->generic && !(m.crnn->CELL == WW_CELL_GRU && m.crnn->H == 32 && m.crnn->F == 64))
+      return ww_set_refuse(err, cap, "member %d is a CRNN of cell %d (0 GRU, 1 LSTM), %d units and a %d-wide head, which runs the generic layered path: model sets "
+                           "take a GRU of 32 units under a 64-wide head at the standard conv geometry only", k, m.crnn->CELL, m.crnn->H, m.crnn->F);
     if (m.kind == WW_KIND_CRNN && m.crnn->generic)
       return ww_set_refuse(err, cap, "member %d is a CRNN of generic conv geometry: model sets take the standard geometry only", k);
     if (m.kind != m0.kind) return ww_set_refuse(err, cap, "member %d is of kind %d, member 0 of kind %d: one set, one kind", k, m.kind, m0.kind);

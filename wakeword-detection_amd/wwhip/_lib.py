@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("WWHIP_LIB") or os.path.join(_PKG, "libwwhip.so")
 WW_OK, WW_EINVAL, WW_EBLOB, WW_EHIP, WW_ENOMEM, WW_ESTATE, WW_ENODEVICE, WW_EINTERNAL = 0, -1, -2, -3, -4, -5, -6, -7
 KIND_CRNN, KIND_WAVENET = 1, 2
 HEAD_SIGMOID, HEAD_SOFTMAX, HEAD_CTC = 0, 1, 2  # include/wwhip.h: WW_HEAD_*
+CELL_GRU, CELL_LSTM = 0, 1  # include/wwhip.h: WW_CELL_*
 PRECISION_FP32, PRECISION_BF16X3 = 0, 1
 OPT_CRNN_SPLIT_AT, OPT_CRNN_SLIDE_MIN, OPT_CRNN_TAIL_MFMA, OPT_WAVENET_ROWMAJOR, OPT_WAVE_SEQ_SEGMENT = 1, 2, 3, 4, 5
 STREAM_FULL_RECOMPUTE, STREAM_TWO_LAUNCH, STREAM_SYNC_WAIT, STREAM_CAUSAL = 1, 2, 4, 8
@@ -84,6 +85,7 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_model_free": (C.c_int, [_vp]),
     "ww_model_get_info": (C.c_int, [_vp, _P(ModelInfo)]),
     "ww_model_head_kind": (C.c_int, [_vp, _P(_i32)]),
+    "ww_model_rnn_kind": (C.c_int, [_vp, _P(_i32), _P(_i32), _P(_i32)]),
     "ww_ctc_forward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ww_ctc_forward_windows_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ww_ctc_slide_forward": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _P(_i64)]),

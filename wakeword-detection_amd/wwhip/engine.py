@@ -101,6 +101,12 @@ class Engine:
         hk = C.c_int32(0)
         _lib.raise_for(self._lib.ww_model_head_kind(h, C.byref(hk)), self.ctx.handle)
         self.head_kind = int(hk.value)  # _lib.HEAD_SIGMOID | HEAD_SOFTMAX | HEAD_CTC
+        # a CRNN's recurrent layers: cell (_lib.CELL_GRU | CELL_LSTM), units per direction, width of the head's first layer
+        self.cell = self.units = self.head_units = None
+        if self.kind == _lib.KIND_CRNN:
+            rk = [C.c_int32(0) for _ in range(3)]
+            _lib.raise_for(self._lib.ww_model_rnn_kind(h, *(C.byref(v) for v in rk)), self.ctx.handle)
+            self.cell, self.units, self.head_units = (int(v.value) for v in rk)
         self.model_dir = model_dir
         _lib.register("models", self)
         self._options = {"crnn_split_at": 1024, "crnn_slide_min": 64, "crnn_tail_mfma": 1, "wavenet_rowmajor": 0, "wave_seq_segment": 0}  # the library's defaults

@@ -36,6 +36,11 @@ HEAD_SIGMOID = 0
 HEAD_SOFTMAX = 1
 HEAD_CTC = 2  # Arik_CRNN_CTC (wwdetect/CRNN/model.py:82-145): one TimeDistributed(Dense(labels + blank, softmax)) over layer 2's steps
 
+# the recurrent cell of a CRNN (wwdetect/CRNN/train.py:112-125 lets the tuner pick either, 16 .. 64 units wide)
+CELL_GRU = 0
+CELL_LSTM = 1
+CELL_GATES = {CELL_GRU: 3, CELL_LSTM: 4}
+
 
 class GraphPatternError(ValueError):
     """The graph does not have the structure of a reference CRNN/Wavenet export."""
@@ -143,10 +148,16 @@ def extract_filter(model: R.Model) -> FilterParams:
 # --------------------------------------------------------------------------
 @dataclass
 class GruDir:
-    w_x: np.ndarray  # [3H, in]  gate order z, r, h
-    b_x: np.ndarray  # [3H]
-    w_h: np.ndarray  # [3H, H]
-    b_h: np.ndarray  # [3H]
+    """One direction of a recurrent layer of either cell, G gate blocks of H rows each: G = 3 in the order z, r, h for a
+    reset-after GRU, G = 4 in Keras' order i, f, c, o for an LSTM.  A Keras LSTM has ONE bias: it travels as ``b_x`` and ``b_h`` is
+    ``None``."""
+    w_x: np.ndarray  # [G H, in]
+    b_x: np.ndarray  # [G H]
+    w_h: np.ndarray  # [G H, H]
+    b_h: Optional[np.ndarray]  # [G H]; None for an LSTM
+
+
+RnnDir = GruDir
 
 
 @dataclass
@@ -163,11 +174,12 @@ class CrnnParams:
     out_t: int
     gru1: Tuple[GruDir, GruDir]  # (forward, backward)
     gru2: Tuple[GruDir, GruDir]
-    head_w1: Optional[np.ndarray]  # [64, 64]; None for HEAD_CTC
+    head_w1: Optional[np.ndarray]  # [F, 2H] (the trainer's F = 64); None for HEAD_CTC
     head_b1: Optional[np.ndarray]
-    head_w2: np.ndarray  # [n_out, 64]; HEAD_CTC: [L, 2H], L = labels + blank (the blank is the last class)
+    head_w2: np.ndarray  # [n_out, F]; HEAD_CTC: [L, 2H], L = labels + blank (the blank is the last class)
     head_b2: np.ndarray
     head_kind: int  # HEAD_SIGMOID | HEAD_SOFTMAX | HEAD_CTC
+    cell: int = CELL_GRU  # CELL_GRU | CELL_LSTM
 
     @property
     def n_out(self) -> int:
@@ -176,6 +188,11 @@ class CrnnParams:
     @property
     def units(self) -> int:
         return int(self.gru1[0].w_h.shape[1])
+
+    @property
+    def head_units(self) -> int:
+        """F, the width of the head's first dense layer (2H where there is none: a CTC head)."""
+        return int(self.head_w1.shape[0]) if self.head_w1 is not None else 2 * self.units
 
 
 def crnn_ctc_params(base: CrnnParams, w, b) -> CrnnParams:
@@ -628,10 +645,14 @@ def _sections(bundle: ModelBundle) -> List[Tuple[str, np.ndarray]]:
                                     c.out_f, c.out_t, c.units, c.n_out, c.head_kind], np.int32)),
             ("crnn.conv_w", c.conv_w), ("crnn.conv_b", c.conv_b),
         ]
+        # only where it says something crnn.meta does not: a blob of a GRU with a 2H-wide head keeps the bytes it always had
+        if c.cell != CELL_GRU or c.head_units != 2 * c.units:
+            sec.insert(len(sec) - 2, ("crnn.cell", np.array([c.cell, c.head_units], np.int32)))
         for li, layer in ((1, c.gru1), (2, c.gru2)):
             for dn, g in zip(("f", "b"), layer):
-                sec += [(f"crnn.g{li}{dn}.wx", g.w_x), (f"crnn.g{li}{dn}.bx", g.b_x),
-                        (f"crnn.g{li}{dn}.wh", g.w_h), (f"crnn.g{li}{dn}.bh", g.b_h)]
+                sec += [(f"crnn.g{li}{dn}.wx", g.w_x), (f"crnn.g{li}{dn}.bx", g.b_x), (f"crnn.g{li}{dn}.wh", g.w_h)]
+                if g.b_h is not None:  # (an LSTM direction has one bias, b_x)
+                    sec += [(f"crnn.g{li}{dn}.bh", g.b_h)]
         if c.head_kind != HEAD_CTC:
             sec += [("crnn.head_w1", c.head_w1), ("crnn.head_b1", c.head_b1)]
         sec += [("crnn.head_w2", c.head_w2), ("crnn.head_b2", c.head_b2)]
@@ -689,12 +710,12 @@ def pack_blob(bundle: ModelBundle) -> bytes:
 
 def unpack_blob(blob: bytes) -> Dict[str, np.ndarray]:
     """Inverse of :func:`pack_blob` for tests and the CPU oracle (sections come back
-    flat; int sections are those named ``*.meta`` / dilations / order / has_res)."""
+    flat; int sections are those named ``*.meta`` / ``*.cell`` / dilations / order / has_res)."""
     magic, ver, kind, n = struct.unpack_from("<IIII", blob, 0)
     if magic != BLOB_MAGIC or ver != BLOB_VERSION:
         raise ValueError("bad blob header")
     out: Dict[str, np.ndarray] = {"__kind__": np.array([kind], np.int32)}
-    int_names = ("meta", "dilations", "skip_order", "has_res")
+    int_names = ("meta", "dilations", "skip_order", "has_res", "cell")
     for i in range(n):
         base = 16 + 32 * i
         name = blob[base : base + 24].split(b"\0", 1)[0].decode("ascii")
@@ -702,3 +723,150 @@ def unpack_blob(blob: bytes) -> Dict[str, np.ndarray]:
         dt = np.int32 if name.rsplit(".", 1)[-1] in int_names else np.float32
         out[name] = np.frombuffer(blob, dtype=dt, count=cnt, offset=off)
     return out
+
+
+# --------------------------------------------------------------------------
+# Keras checkpoints (wwdetect/CRNN/model.py:64-66 save_separate: encode.h5 + detect.h5) -> CrnnParams
+# --------------------------------------------------------------------------
+def crnn_from_keras(n_mel: int, n_frames: int, conv, rnn1, rnn2, dense1, dense2, *, cell: int = CELL_GRU,
+                    strides: Tuple[int, int] = (2, 8), padding: str = "same", head_kind: int = HEAD_SOFTMAX) -> CrnnParams:
+    """``CrnnParams`` from arrays in the layout ``layer.get_weights()`` returns.
+
+    ``conv``: ``(kernel [l_f, l_t, 1, C], bias [C])``.  ``rnn1`` / ``rnn2``: ``(forward, backward)``, each
+    ``(kernel [in, G H], recurrent_kernel [H, G H], bias)`` with ``bias [2, 3H]`` (input, recurrent) for a reset-after GRU and
+    ``bias [4H]`` for an LSTM (tanh / sigmoid, gate order i, f, c, o).  ``dense1`` / ``dense2``: ``(kernel [in, out], bias [out])``.
+    ``strides`` (frequency, time) and ``padding`` ("same" | "valid") are the Conv2D's; ``head_kind`` is the last activation."""
+    if cell not in CELL_GATES:
+        raise GraphPatternError(f"unknown recurrent cell {cell}")
+    if head_kind not in (HEAD_SIGMOID, HEAD_SOFTMAX):
+        raise GraphPatternError(f"head kind {head_kind}: a Keras detect model ends in sigmoid or softmax")
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)
+    G = CELL_GATES[cell]
+    ck, cb = (np.asarray(a, np.float32) for a in conv)
+    if ck.ndim != 4 or ck.shape[2] != 1 or cb.shape != (ck.shape[3],):
+        raise GraphPatternError(f"conv kernel must be [l_f, l_t, 1, C] with a bias [C], got {ck.shape} and {cb.shape}")
+    kf, kt, _, C = ck.shape
+    sf, st = (int(v) for v in strides)
+    if padding.lower() == "same":
+        out_f, pad_f = _same_pad(n_mel, kf, sf)
+        out_t, pad_t = _same_pad(n_frames, kt, st)
+    elif padding.lower() == "valid":
+        out_f, pad_f = (n_mel - kf) // sf + 1, (0, 0)
+        out_t, pad_t = (n_frames - kt) // st + 1, (0, 0)
+    else:
+        raise GraphPatternError(f"conv padding {padding!r} is neither same nor valid")
+    units = int(np.shape(rnn1[0][1])[0])
+
+    def direction(w, n_in: int) -> GruDir:
+        k, r, b = (np.asarray(a, np.float32) for a in w)
+        if k.shape != (n_in, G * units) or r.shape != (units, G * units):
+            raise GraphPatternError(f"recurrent kernels must be [{n_in}, {G * units}] and [{units}, {G * units}], got {k.shape} and {r.shape}")
+        if cell == CELL_GRU:
+            if b.shape != (2, G * units):
+                raise GraphPatternError(f"a reset-after GRU's bias is [2, {G * units}], got {b.shape}")
+            return GruDir(f32(k.T), f32(b[0]), f32(r.T), f32(b[1]))
+        if b.shape != (G * units,):
+            raise GraphPatternError(f"an LSTM's bias is [{G * units}], got {b.shape}")
+        return GruDir(f32(k.T), f32(b), f32(r.T), None)
+
+    if len(rnn1) != 2 or len(rnn2) != 2:
+        raise GraphPatternError("a recurrent layer is (forward, backward)")
+    g1 = tuple(direction(w, out_f * C) for w in rnn1)
+    g2 = tuple(direction(w, 2 * units) for w in rnn2)
+    (k1, b1), (k2, b2) = ((np.asarray(a, np.float32) for a in d) for d in (dense1, dense2))
+    if k1.ndim != 2 or k1.shape[0] != 2 * units or b1.shape != (k1.shape[1],) or k2.ndim != 2 or k2.shape[0] != k1.shape[1] or \
+            b2.shape != (k2.shape[1],):
+        raise GraphPatternError(f"dense kernels must be [{2 * units}, F] and [F, n_out], got {k1.shape} and {k2.shape}")
+    return CrnnParams(int(n_mel), int(n_frames), f32(np.transpose(ck[:, :, 0, :], (2, 0, 1))), f32(cb), sf, st, pad_f, pad_t, out_f, out_t,
+                      g1, g2, f32(k1.T), f32(b1), f32(k2.T), f32(b2), int(head_kind), int(cell))
+
+
+def read_keras_h5(path: str) -> Tuple[dict, Dict[str, np.ndarray]]:
+    """A Keras ``.h5`` checkpoint -> (its ``model_config``, every weight by its Keras name), read with ``wwhip.h5min``."""
+    import json
+    from . import h5min
+    with h5min.File(path) as f:
+        config = json.loads(f.attrs["model_config"])
+        w: Dict[str, np.ndarray] = {}
+        mw = f["model_weights"]
+        for lname in mw.keys():
+            names = mw[lname].attrs.get("weight_names")
+            for n in ([] if names is None else names):
+                n = n.decode() if isinstance(n, bytes) else n
+                w[n] = np.asarray(mw[lname][n][()])
+    return config, w
+
+
+def crnn_from_keras_config(encode, detect) -> CrnnParams:
+    """``(model_config, weight dict)`` of the encoder and of the detector (``read_keras_h5``) -> ``CrnnParams``.  The layer list must
+    be the trainer's: Conv2D (relu), Permute, Reshape, two Bidirectional (concat) layers of GRU (reset_after) or LSTM cells, tanh /
+    sigmoid, the first returning sequences and the second not; Dense (relu), Dense (sigmoid | softmax).  ``GraphPatternError`` on
+    anything else."""
+    (ecfg, ew), (dcfg, dw) = encode, detect
+
+    def layers(cfg, what):
+        try:
+            return [L for L in cfg["config"]["layers"] if L["class_name"] not in ("InputLayer", "Dropout")]
+        except (KeyError, TypeError):
+            raise GraphPatternError(f"{what}: no layer list in the model config") from None
+
+    def weight(w, name):
+        if name not in w:
+            raise GraphPatternError(f"checkpoint lacks the weight {name}")
+        return w[name]
+
+    el, dl = layers(ecfg, "encoder"), layers(dcfg, "detector")
+    if [L["class_name"] for L in el] != ["Conv2D", "Permute", "Reshape", "Bidirectional", "Bidirectional"]:
+        raise GraphPatternError(f"encoder layers are {[L['class_name'] for L in el]}, not Conv2D, Permute, Reshape and two Bidirectional")
+    if [L["class_name"] for L in dl] != ["Dense", "Dense"]:
+        raise GraphPatternError(f"detector layers are {[L['class_name'] for L in dl]}, not two Dense")
+    conv = el[0]["config"]
+    shape = conv.get("batch_input_shape") or ecfg["config"]["layers"][0]["config"].get("batch_input_shape")
+    if not shape or len(shape) != 4 or shape[3] != 1:
+        raise GraphPatternError(f"encoder input shape {shape} is not [None, n_mel, frames, 1]")
+    if conv["activation"] != "relu" or list(conv.get("dilation_rate", [1, 1])) != [1, 1] or conv["padding"] not in ("same", "valid"):
+        raise GraphPatternError("the Conv2D must be undilated, same or valid, with relu")
+    if list(el[1]["config"]["dims"]) != [2, 1, 3]:
+        raise GraphPatternError("expected Permute((2, 1, 3)) after the conv")
+    cells, units, rnn = [], [], []
+    for L, want_seq in zip(el[3:], (True, False)):
+        c = L["config"]
+        inner, ic = c["layer"]["class_name"], c["layer"]["config"]
+        if c.get("merge_mode") != "concat":
+            raise GraphPatternError("Bidirectional layers must merge by concat")
+        if inner == "GRU":
+            if not ic.get("reset_after"):
+                raise GraphPatternError("a GRU must be reset_after (Keras v2)")
+            cells.append(CELL_GRU)
+        elif inner == "LSTM":
+            cells.append(CELL_LSTM)
+        else:
+            raise GraphPatternError(f"recurrent layer {inner} is neither GRU nor LSTM")
+        if ic["activation"] != "tanh" or ic["recurrent_activation"] != "sigmoid" or not ic["use_bias"] or ic.get("go_backwards"):
+            raise GraphPatternError("recurrent layers must be tanh / sigmoid with a bias, running forwards")
+        if bool(ic["return_sequences"]) != want_seq:
+            raise GraphPatternError("the first recurrent layer returns sequences, the second its last states")
+        units.append(int(ic["units"]))
+        pre = sorted({n.rsplit("/", 1)[0] for n in ew if n.startswith(c["name"] + "/")})
+        fwd, bwd = [p for p in pre if "/forward_" in p], [p for p in pre if "/backward_" in p]
+        if len(fwd) != 1 or len(bwd) != 1:
+            raise GraphPatternError(f"layer {c['name']} does not hold one forward and one backward cell")
+        rnn.append(tuple(tuple(weight(ew, f"{p}/{n}:0") for n in ("kernel", "recurrent_kernel", "bias")) for p in (fwd[0], bwd[0])))
+    if cells[0] != cells[1] or units[0] != units[1]:
+        raise GraphPatternError("the two recurrent layers differ in cell or width")
+    d1, d2 = dl[0]["config"], dl[1]["config"]
+    if d1["activation"] != "relu" or d2["activation"] not in ("sigmoid", "softmax"):
+        raise GraphPatternError("detector activations must be relu, then sigmoid or softmax")
+    dense = [(weight(dw, f"{d['name']}/kernel:0"), weight(dw, f"{d['name']}/bias:0")) for d in (d1, d2)]
+    p = crnn_from_keras(int(shape[1]), int(shape[2]), (weight(ew, conv["name"] + "/kernel:0"), weight(ew, conv["name"] + "/bias:0")),
+                        rnn[0], rnn[1], dense[0], dense[1], cell=cells[0], strides=tuple(conv["strides"]), padding=conv["padding"],
+                        head_kind=HEAD_SOFTMAX if d2["activation"] == "softmax" else HEAD_SIGMOID)
+    if p.units != units[0]:
+        raise GraphPatternError(f"the config says {units[0]} units, the kernels {p.units}")
+    return p
+
+
+def load_keras_pair(encode_h5: str, detect_h5: str, filt: FilterParams) -> ModelBundle:
+    """The two checkpoints ``save_separate`` writes, plus a filter (a Keras CRNN has none: ``extract_filter`` of any model
+    directory's ``filter.tflite``), as a bundle ``Engine(bundle=...)`` and ``pack_blob`` take."""
+    return ModelBundle(KIND_CRNN, filt, crnn=crnn_from_keras_config(read_keras_h5(encode_h5), read_keras_h5(detect_h5)))
