@@ -20,8 +20,9 @@
 // (This kernel's fp64 form, the default front end of rounds 1-3, is recorded in profiles/EXPERIMENTS.md.)
 // logmel_kernel and logmel_rows_kernel are built from one set of pieces, defined once in front of them: LM_STAGE_GENERIC,
 // pcm_quot_clip2 and LM_STAGE_SIMPLE_LOAD / LM_STAGE_SIMPLE_STORE (staging), hann_pair, hann_mul_pair and hann_mul_at (Hann
-// product), LM_PARTNERS, LM_UNTANGLE_K2 and untangle_tail (real-FFT untangling), LM_MEL_TILE (mel filter and the park of the
-// output tile); logmel_lds is logmel_kernel's LDS layout, logmel_instance the host's choice of instantiation.
+// product), LM_PARTNERS, LM_UNTANGLE_K2 and untangle_tail (real-FFT untangling), LM_MEL_REQ_* and LM_MEL_COMPUTE (the table
+// fetches of the mel filter; the filter and the park of the output tile); logmel_lds is logmel_kernel's LDS layout,
+// logmel_instance the host's choice of instantiation.
 // (stft_mag_kernel and the streaming kernel keep the earlier one-wave-per-frame radix-4 Stockham
 // FFT of fft_device.h: they are not on the batched path.)
 //
@@ -365,35 +366,63 @@ __device__ __forceinline__ void untangle_tail(const cplx<R> z, float *mrow, int 
 //   a group start on different slots mod 4 - conflict-free.  (The fp32 MFMA form of this contraction kept
 //   the SIMD's vector ALU idle for 32 cycles per instruction - fp32 MFMA and VALU share a datapath on gfx950
 //   - and needed three workgroup barriers for the partial sums; this form needs none.)
-// Each group's weight chunks are fetched when its turn comes (the 64 weight registers must not be live across the FFT, and one
-// group's magnitudes and weights are in flight at a time); without melv_aligned the magnitudes are read a float at a time.
-// Empty slots write to a spare word each so that the code stays straight-line.
+// The tail comes in two halves.  What the request half fetches - a lane's three meta words, its three biases (addressed by
+// meta) and the weight chunks of its slot - depends on (lane_ >> 2) and the model alone, on nothing the wave computes, so a
+// kernel may ask for it as early as it has registers to receive it: LM_MEL_REQ_META, LM_MEL_REQ_BIAS (waits for meta) and
+// LM_MEL_REQ_W per group, in that order.  Registers are the one constraint: the weights must not be live across the FFT, whose
+// data fills the file, and while group 0 runs its 36 weights sit beside its 36 magnitudes, which leaves room for the 16 of
+// group 1 in a 104-register wave and for neither group 1's nor the 12 of group 2 in a 92-register one.  So the caller
+// requests the groups below ahead_ and the compute half the others: group 0, if it is among them, where its turn comes, the
+// rest behind group 0's FMAs, where they have the log tail of group 0 and the whole of group 1 to arrive in.  The compute half reads q_ from registers, group 0 first: loads return in
+// order, so each group waits with a counted vmcnt for its own chunks only.  Without melv_aligned the magnitudes are read a
+// float at a time.  Empty slots write to a spare word each so that the code stays straight-line.
+struct lm_mel_fetch {
+  int meta[WW_MELV_GROUPS];  // first bin | band << 16 of this lane's slot in each group
+  float bias[WW_MELV_GROUPS];
+  float4 wq[WW_MELV_CHUNKS];
+};
 #define LM_MEL_LOGTAIL(a_, acc_, bias_) ((logf(fmaxf((acc_) + (bias_), (a_).floor_v)) + (a_).log_off) * (a_).scale)
-#define LM_MEL_TILE(a_, mg_, lane_)                                                                                    \
+#define LM_MEL_REQ_META(a_, lane_, q_)                                                                                 \
   do {                                                                                                                 \
-    const int j_ = (lane_) >> 2, sub_ = (lane_) & 3; /* (slot, frame) of this lane */                                  \
-    constexpr int CAPQ_[WW_MELV_GROUPS] = WW_MELV_CAPQ, C0_[WW_MELV_GROUPS] = WW_MELV_CHUNK0;                          \
-    const float4 *wv_ = (const float4 *)(a_).melV + j_;                                                                \
-    const float *mrow_ = (mg_) + sub_ * MAG_LD;                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                                 \
-    int meta_[3];                                                                                                      \
-    _Pragma("unroll") for (int g_ = 0; g_ < 3; ++g_) meta_[g_] = (a_).melVmeta[g_ * 16 + j_];                          \
-    float4 wq_[WW_MELV_CHUNKS];                                                                                        \
-    int band_[3];                                                                                                      \
-    float bias_[3];                                                                                                    \
-    _Pragma("unroll") for (int g_ = 0; g_ < 3; ++g_) {                                                                 \
-      band_[g_] = (int)((unsigned)meta_[g_] >> 16); /* 0xffff: empty slot */                                           \
-      bias_[g_] = (a_).bias[band_[g_] < (a_).n_mel ? band_[g_] : 0];                                                   \
+    const unsigned j_ = (unsigned)(lane_) >> 2; /* slot of this lane */                                                \
+    _Pragma("unroll") for (int g_ = 0; g_ < WW_MELV_GROUPS; ++g_) (q_).meta[g_] = (a_).melVmeta[g_ * 16 + j_];         \
+  } while (0)
+#define LM_MEL_REQ_BIAS(a_, q_)                                                                                        \
+  do {                                                                                                                 \
+    _Pragma("unroll") for (int g_ = 0; g_ < WW_MELV_GROUPS; ++g_) {                                                    \
+      const int band_ = (int)((unsigned)(q_).meta[g_] >> 16); /* 0xffff: empty slot */                                 \
+      (q_).bias[g_] = (a_).bias[band_ < (a_).n_mel ? band_ : 0];                                                       \
     }                                                                                                                  \
+  } while (0)
+#define LM_MEL_REQ_W(a_, lane_, q_, g_)                                                                                \
+  do {                                                                                                                 \
+    constexpr int RCAPQ_[WW_MELV_GROUPS] = WW_MELV_CAPQ, RC0_[WW_MELV_GROUPS] = WW_MELV_CHUNK0;                        \
+    const float4 *wv_ = (const float4 *)(a_).melV + ((unsigned)(lane_) >> 2);                                          \
+    _Pragma("unroll") for (int c_ = 0; c_ < RCAPQ_[g_]; ++c_) (q_).wq[RC0_[g_] + c_] = wv_[(RC0_[g_] + c_) * 16];      \
+  } while (0)
+#define LM_MEL_REQ_REST(a_, lane_, q_, g_, ahead_)                                                                     \
+  do {                                                                                                                 \
+    if ((g_) == 0 && (ahead_) < WW_MELV_GROUPS) {                                                                      \
+      __builtin_amdgcn_sched_barrier(0);                                                                               \
+      _Pragma("unroll") for (int h_ = (ahead_) > 1 ? (ahead_) : 1; h_ < WW_MELV_GROUPS; ++h_)                          \
+        LM_MEL_REQ_W(a_, lane_, q_, h_);                                                                               \
+      __builtin_amdgcn_sched_barrier(0);                                                                               \
+    }                                                                                                                  \
+  } while (0)
+#define LM_MEL_COMPUTE(a_, mg_, lane_, q_, ahead_)                                                                     \
+  do {                                                                                                                 \
+    const int sub_ = (lane_) & 3; /* frame of this lane (its slot: lane_ >> 2) */                                      \
+    constexpr int CAPQ_[WW_MELV_GROUPS] = WW_MELV_CAPQ, C0_[WW_MELV_GROUPS] = WW_MELV_CHUNK0;                          \
+    const float *mrow_ = (mg_) + sub_ * MAG_LD;                                                                        \
     float res_[3];                                                                                                     \
     if ((a_).melv_aligned) {                                                                                           \
       _Pragma("unroll") for (int g_ = 0; g_ < 3; ++g_) {                                                               \
         __builtin_amdgcn_sched_barrier(0);                                                                             \
-        _Pragma("unroll") for (int c_ = 0; c_ < CAPQ_[g_]; ++c_) wq_[C0_[g_] + c_] = wv_[(C0_[g_] + c_) * 16];         \
-        lds_cfloat4 *mb_ = (lds_cfloat4 *)lds_opaque(mrow_ + (meta_[g_] & 0xffff));                                    \
+        if (g_ == 0 && (ahead_) == 0) LM_MEL_REQ_W(a_, lane_, q_, 0);                                                  \
+        lds_cfloat4 *mb_ = (lds_cfloat4 *)lds_opaque(mrow_ + ((q_).meta[g_] & 0xffff));                                \
         float acc_ = 0.f, acc1_ = 0.f; /* two chains: a dependent fp32 FMA does not issue back to back */              \
         _Pragma("unroll") for (int c_ = 0; c_ < CAPQ_[g_]; ++c_) {                                                     \
-          const float4 w4_ = wq_[C0_[g_] + c_];                                                                        \
+          const float4 w4_ = (q_).wq[C0_[g_] + c_];                                                                    \
           const f32x4 m4_ = mb_[c_];                                                                                   \
           acc_ = fmaf(m4_[0], w4_.x, acc_);                                                                            \
           acc1_ = fmaf(m4_[1], w4_.y, acc1_);                                                                          \
@@ -401,27 +430,31 @@ __device__ __forceinline__ void untangle_tail(const cplx<R> z, float *mrow, int 
           acc1_ = fmaf(m4_[3], w4_.w, acc1_);                                                                          \
         }                                                                                                              \
         acc_ += acc1_;                                                                                                 \
-        res_[g_] = LM_MEL_LOGTAIL(a_, acc_, bias_[g_]);                                                                \
+        LM_MEL_REQ_REST(a_, lane_, q_, g_, ahead_);                                                                    \
+        res_[g_] = LM_MEL_LOGTAIL(a_, acc_, (q_).bias[g_]);                                                            \
       }                                                                                                                \
     } else {                                                                                                           \
       _Pragma("unroll") for (int g_ = 0; g_ < 3; ++g_) {                                                               \
         __builtin_amdgcn_sched_barrier(0);                                                                             \
-        _Pragma("unroll") for (int c_ = 0; c_ < CAPQ_[g_]; ++c_) wq_[C0_[g_] + c_] = wv_[(C0_[g_] + c_) * 16];         \
-        lds_cfloat *mb_ = lds_opaque(mrow_ + (meta_[g_] & 0xffff));                                                    \
+        if (g_ == 0 && (ahead_) == 0) LM_MEL_REQ_W(a_, lane_, q_, 0);                                                  \
+        lds_cfloat *mb_ = lds_opaque(mrow_ + ((q_).meta[g_] & 0xffff));                                                \
         float acc_ = 0.f;                                                                                              \
         _Pragma("unroll") for (int c_ = 0; c_ < CAPQ_[g_]; ++c_) {                                                     \
-          const float4 w4_ = wq_[C0_[g_] + c_];                                                                        \
+          const float4 w4_ = (q_).wq[C0_[g_] + c_];                                                                    \
           acc_ = fmaf(mb_[4 * c_ + 0], w4_.x, acc_);                                                                   \
           acc_ = fmaf(mb_[4 * c_ + 1], w4_.y, acc_);                                                                   \
           acc_ = fmaf(mb_[4 * c_ + 2], w4_.z, acc_);                                                                   \
           acc_ = fmaf(mb_[4 * c_ + 3], w4_.w, acc_);                                                                   \
         }                                                                                                              \
-        res_[g_] = LM_MEL_LOGTAIL(a_, acc_, bias_[g_]);                                                                \
+        LM_MEL_REQ_REST(a_, lane_, q_, g_, ahead_);                                                                    \
+        res_[g_] = LM_MEL_LOGTAIL(a_, acc_, (q_).bias[g_]);                                                            \
       }                                                                                                                \
     }                                                                                                                  \
     lds_fence(); /* the magnitudes are dead */                                                                         \
-    _Pragma("unroll") for (int g_ = 0; g_ < 3; ++g_)                                                                   \
-      (mg_)[band_[g_] < (a_).n_mel ? sub_ * (a_).n_mel + band_[g_] : 4 * (a_).n_mel + (lane_)] = res_[g_];             \
+    _Pragma("unroll") for (int g_ = 0; g_ < 3; ++g_) {                                                                 \
+      const int band_ = (int)((unsigned)(q_).meta[g_] >> 16);                                                          \
+      (mg_)[band_ < (a_).n_mel ? sub_ * (a_).n_mel + band_ : 4 * (a_).n_mel + (lane_)] = res_[g_];                     \
+    }                                                                                                                  \
     lds_fence();                                                                                                       \
   } while (0)
 
@@ -541,6 +574,7 @@ __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
   __syncthreads();  // the sample tile is dead now - wave 3's transposes and magnitudes move in
   // From here on the four waves never meet again: each one carries its own 4 frames to the output.
   if (!active) return;
+  lm_mel_fetch mq;
   {
     dft16<R>(v);
 #pragma unroll
@@ -562,9 +596,16 @@ __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
     lds_fence();
     // pass 2: lane j = k1 holds Y[n2][k1]; output w[pos] = Z[k1 + 16 k_of(pos)]
     dft16<R>(w);
+    // the mel tail's meta words and biases arrive under the untangling; its weights (92 registers) are left to LM_MEL_COMPUTE
+    __builtin_amdgcn_sched_barrier(0);
+    LM_MEL_REQ_META(a, lane, mq);
+    __builtin_amdgcn_sched_barrier(0);
     // untangle: the partners Z[256 - k] arrive through the (dead) transpose buffer, W512^k from the LDS table
     cplx<R> pz[8];
     LM_PARTNERS(R, w, trs, j, pz);
+    __builtin_amdgcn_sched_barrier(0);
+    LM_MEL_REQ_BIAS(a, mq);
+    __builtin_amdgcn_sched_barrier(0);
     float *mrow = mg + sub * MAG_LD;
 #pragma unroll
     for (int k2 = 0; k2 < 8; ++k2) LM_UNTANGLE_K2(R, w[pos_of(k2)], pz[k2], tb_un[j + 16 * k2], mrow, j + 16 * k2);
@@ -574,7 +615,7 @@ __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
   // ---- mel filterbank and the park of the wave's 4 x n_mel tile, which leaves as one contiguous store
   lds_fence();
   {
-    LM_MEL_TILE(a, mg, lane);
+    LM_MEL_COMPUTE(a, mg, lane, mq, 0);
     const int nv = (nfb - fb) < 4 ? (nfb - fb) : 4;
     float *dstf = a.mel + (a.frame_offs[u] + f0 + fb) * (int64_t)a.n_mel;
     if ((((uintptr_t)dstf) & 15) == 0 && (a.n_mel & 3) == 0) {
@@ -602,15 +643,17 @@ __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
 //   * Hann pairs and twiddles come from the L1-resident tables (4 + 4 + 4 KB, shared by every wave of the chip);
 //   * 104 registers (amdgpu_num_vgpr counts in units of two on gfx90a+): the Hann products, the inter-pass twiddles and the
 //     untangling twiddles are software-pipelined by hand in chunks of 4 / 3 / 2 instead of all at once, and the mel
-//     weights are fetched group by group: three of these waves sit on a SIMD beside a 184-register CRNN wave, four alone.
+//     weights are requested as the untangling retires registers: three of these waves sit on a SIMD beside a 184-register
+//     CRNN wave, four alone.
 // A wave whose four frames do not lie in one clip within 3 hops of each other (a clip boundary) stages them frame by frame
 // (generic path, <= 1 wave in 37 for 1.5 s clips).  The arithmetic is that of the fp64 tile kernel it replaced, instruction for
 // instruction, with bit-identical results (profiles/EXPERIMENTS.md, round 4).
 // What it has in common with logmel_kernel is the shared pieces above, instantiated for one wave and R = double: staging
 // (LM_STAGE_SIMPLE_LOAD / LM_STAGE_SIMPLE_STORE with NV vectors per lane and idx_t indices; stage_generic_wave = LM_STAGE_GENERIC at
 // stride 64), hann_pair on the global double2 table with hann_mul_pair / hann_mul_at per chunk of LW_HC, LM_PARTNERS,
-// LM_UNTANGLE_K2 on a register chunk of W512^k, untangle_tail and LM_MEL_TILE.  Its own: the row -> clip lookup, the chunked
-// table fetches, the fp64 transposes (lds_read16_b64) and the final store, whose rows are global (vm) instead of per clip.
+// LM_UNTANGLE_K2 on a register chunk of W512^k, untangle_tail, LM_MEL_REQ_* and LM_MEL_COMPUTE.  Its own: the row -> clip
+// lookup, the chunked table fetches, the fp64 transposes (lds_read16_b64) and the final store, whose rows are global (vm)
+// instead of per clip.
 // ---------------------------------------------------------------------------------------------------------------------
 #ifndef LW_WPB
 #define LW_WPB 2  // waves per workgroup (they share nothing).  Same box, rocprofv3, 256 / 4,096 clips: 4 waves 27.96 / 353.5 us,
@@ -747,6 +790,7 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
   R *tr = (R *)wb;          // [4][16][TR_LD]
   float *mg = (float *)wb;  // overlay: [4][MAG_LD]
   cplx<R> v[16];
+  lm_mel_fetch mq;  // the mel tail's tables, requested under the untangling
   const double2 *twp = (const double2 *)a.tw16 + j;  // [k1][16 j] = W256^(j k1)
   double2 tq[2][LW_TC];
   {
@@ -840,6 +884,14 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
     double2 uq[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) uq[0][i] = unp[16 * i];
+    // The mel tail's tables ride under the untangling: every request BEHIND the uq request of its chunk, so that the counted
+    // wait for a uq chunk never waits for mel data (loads return in order), and each as soon as the registers are there: three
+    // meta words now, the biases a chunk later, the weights of groups 0 and 1 (52 registers) behind the third chunk, when twelve
+    // of the sixteen w and pz pairs are retired (a chunk earlier they spill).  The generic-staging instances carry more across
+    // the transform and have no room for weights before untangle_tail (W_AT 4: requested there).
+    constexpr int W_AT = SIMPLE ? 3 : 4;
+    __builtin_amdgcn_sched_barrier(0);
+    LM_MEL_REQ_META(a, l2, mq);
     cplx<R> pz[8];
     LM_PARTNERS(R, w, trs, j, pz);
     float *mrow = mg + sub * MAG_LD;
@@ -848,6 +900,14 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
       if (c + 1 < 4) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) uq[(c + 1) & 1][i] = unp[16 * (2 * (c + 1) + i)];
+      }
+      if (c == 0 || c == W_AT) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (c == 0) LM_MEL_REQ_BIAS(a, mq);
+        if (c == W_AT) {
+          LM_MEL_REQ_W(a, l2, mq, 0);
+          LM_MEL_REQ_W(a, l2, mq, 1);
+        }
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -865,7 +925,13 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
   lds_fence();
   {
     const int lane = lw_lane();
-    LM_MEL_TILE(a, mg, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    if (!SIMPLE) {
+      LM_MEL_REQ_W(a, lane, mq, 0);
+      LM_MEL_REQ_W(a, lane, mq, 1);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    LM_MEL_COMPUTE(a, mg, lane, mq, 2);
     float *dstf = a.mel + g0 * (int64_t)a.n_mel;
     const bool prefix = (vm & (vm + 1)) == 0;  // valid rows are 0 .. r_last
     if (prefix && (((uintptr_t)dstf) & 15) == 0 && (a.n_mel & 3) == 0) {

@@ -9,7 +9,7 @@
 // ---- mel filter (fft_device.h, stream_fe.h, frontend.hip) --------------------------------------------------------------------
 #define WW_MEL_TAPS 36  // wpad [WW_MEL_TAPS][64]: longest band of the shipped filterbank (checked at model load)
 #define MAG_LD 272      // floats per frame of magnitudes in the batch front end: 257 + zero pad to 17 * 16
-// Lane form (frontend.hip: LM_MEL_TILE): the bands, widest first, in three groups of 16 slots; a slot of group g accumulates
+// Lane form (frontend.hip: LM_MEL_REQ_W, LM_MEL_COMPUTE): the bands, widest first, in three groups of 16 slots; a slot of group g accumulates
 // WW_MELV_CAPQ[g] float4 chunks of padded taps (36, 16 and 12 taps), the group's chunks start at chunk WW_MELV_CHUNK0[g].
 #define WW_MELV_GROUPS 3
 #define WW_MELV_CAPQ {9, 4, 3}
