@@ -382,6 +382,47 @@ int ww_ctc_slide_forward(ww_ctx *ctx, const ww_model *model, const float *mel, i
 int ww_ctc_greedy_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, int32_t L, int32_t max_labels, int32_t *d_labels,
                       int32_t *d_lengths);
 
+/* ---- CTC-trained CRNNs: a wake-word SCORE from the forward algorithm ---------------------------------------------------------------
+ * The reference trains these models with K.ctc_batch_cost against [HEY][SNIPS] (wwdetect/CRNN/train.py:184-200): -log of the
+ * probability that a window's label sequence collapses to the target.  Evaluated at inference that probability is a number to put a
+ * threshold on - what ww_far_frr[_dev], ww_posterior_events[_dev] and a stream bank's trigger need, and the greedy decode cannot give.
+ * The statement, its recurrence and its arithmetic: csrc/ctc_score.h (wwhip.ctc.score is the same in float64).
+ *   y [T][L] posteriors, the blank is class L - 1;  1 <= T <= 64 (the linear domain, no rescaling), 2 <= L <= 64
+ *   targets [K][WW_CTC_SCORE_MAX_TARGET] int32 on the HOST, target_lens [K]: 1 <= K <= WW_CTC_SCORE_MAX_TARGETS targets of
+ *     1 <= U <= WW_CTC_SCORE_MAX_TARGET labels in [0, L - 2], repeats allowed
+ *   mode  WW_CTC_SCORE_EXACT   P(decode == target), the loss's quantity
+ *         WW_CTC_SCORE_PREFIX  P(decode starts with target), the quantity of the trigger rule (ww_ctc_trigger_bank_step)
+ *   score [K][n] float32, plane-major: plane k is a posterior track that ww_far_frr_dev / ww_posterior_events_dev take as it is
+ * Every + and * is one float32 operation in the header's order, on the device and on the host: ww_ctc_score_dev gives the bits of
+ * ww_ctc_score_rows.  Against the float64 statement on the same float32 posteriors the relative error is at most (3T + 2) 2^-24, plus
+ * (2U + 1) T 2^-126 where values under FLT_MIN are flushed.  The posteriors themselves are read (Keras' loss renormalises
+ * log(y + 1e-7) with a second softmax; the library does not copy that).
+ * WW_EINVAL before anything is written, the text naming the rule: T outside 1..64, L outside 2..64, K or a target's length out of
+ * range, a label outside [0, L - 2], an unknown mode, a NULL required pointer; the model forms also for a model that is not
+ * WW_HEAD_CTC or is in WW_PRECISION_BF16X3, and for labels without lengths.  n = 0: WW_OK, nothing written.
+ * ww_ctc_score_dev - ctc_score_kernel alone (csrc/ctc_score.hip) on any device posteriors [n][T][L]; rows [0, n) of each of the K
+ *   planes are written, and a sequence's non-finite posteriors reach its own K scores alone.  Enqueued on the context's stream.
+ * ww_ctc_score_rows - host only, no context (its refusal's text: ww_last_error(NULL)): the header's function over host arrays.
+ * ww_ctc_score / _windows_dev / ww_ctc_slide_score - ww_ctc_forward / _windows_dev / ww_ctc_slide_forward with the score kernel behind
+ *   every chunk's model launch, on the posteriors that ww_ctc_forward would return as `steps` (T = 19, L = n_out; they stay in the
+ *   workspace).  labels [n][max_labels] and lengths [n] are optional, both or neither: the greedy decode beside the score. */
+#define WW_CTC_SCORE_MAX_TARGET 9
+#define WW_CTC_SCORE_MAX_TARGETS 8
+#define WW_CTC_SCORE_EXACT 0
+#define WW_CTC_SCORE_PREFIX 1
+int ww_ctc_score_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, int32_t L, const int32_t *targets, const int32_t *target_lens,
+                     int32_t K, int32_t mode, float *d_score);
+int ww_ctc_score_rows(const float *steps, int64_t n, int32_t T, int32_t L, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                      int32_t mode, float *score);
+int ww_ctc_score(ww_ctx *ctx, const ww_model *model, const float *windows, int32_t n, const int32_t *targets, const int32_t *target_lens,
+                 int32_t K, int32_t mode, float *score, int32_t max_labels, int32_t *labels, int32_t *lengths);
+int ww_ctc_score_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                             const int32_t *d_win_valid, int32_t n, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                             int32_t mode, float *d_score, int32_t max_labels, int32_t *d_labels, int32_t *d_lengths);
+int ww_ctc_slide_score(ww_ctx *ctx, const ww_model *model, const float *mel, int64_t rows, int32_t hop, const int32_t *targets,
+                       const int32_t *target_lens, int32_t K, int32_t mode, float *score, int32_t max_labels, int32_t *labels,
+                       int32_t *lengths, int64_t *n_windows);
+
 /* ww_forward_windows_dev over a model set: window w is evaluated by member win_model[w], all windows in ONE launch (K checkpoints
  * over the same mel - the loop over eval_models of wwdetect/wavenet/evaluate_wavenet.py - are K x n windows that name the same rows).
  * win_model is a HOST array: read and checked before the call returns (an id outside [0, n_models): WW_EINVAL, nothing is launched),
@@ -832,6 +873,24 @@ int ww_ctc_trigger_bank_step(int32_t n_streams, const uint8_t *is_speech, uint8_
 int ww_stream_step_ctc_trigger(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, uint8_t *is_active, int32_t max_labels,
                                const int32_t *target, int32_t n_target, uint8_t *was_speech, int32_t *labels, int32_t *lengths,
                                float *steps, int32_t *n_post, int32_t *fired_ids, int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall);
+/* ---- CTC stream banks: the forward-algorithm score per tick (ww_ctc_score_* above) ---------------------------------------------------
+ * ww_stream_ctc_set_targets - gives a WW_STREAM_CTC_STEPS bank its targets and mode (ww_ctc_score_dev's arguments, T = 19, L = n_out;
+ *   the same refusals); it may be called again between ticks.  WW_EINVAL on every other bank.
+ * ww_stream_step_ctc_score - ww_stream_step_ctc plus ONE ctc_score_kernel launch behind the tick's model launch, on the same stream,
+ *   over the bank's page-locked posterior block, into a page-locked [2 S][K]; scores [S][2][K] float32: window k of stream s, target j.
+ *   Entries at or past n_post[s] are left as they were.  In every form of the bank (one launch, two launches, full recompute) a
+ *   window's scores are the bits ww_ctc_score_dev gives on the posteriors the same tick returns in `steps` (which may be NULL).
+ *   WW_EINVAL before any state moves on a bank without targets.  ww_stream_step_ctc on a bank with targets is what it was.
+ * ww_ctc_score_trigger_bank_step - host only: ww_ctc_trigger_bank_step's VAD-edge bookkeeping, fired and fall lists with the score
+ *   rule.  A stream that is not active fires on the first window of the tick on which some slot j has (double)score > thresholds[j]
+ *   (ww_trigger_bank_step_all's comparison); fired_slot [n_fired] (may be NULL) names the exceeding slot with the greatest score on
+ *   that window, the lowest slot among equals.  1 <= K <= WW_CTC_SCORE_MAX_TARGETS; WW_EINVAL with nothing touched otherwise. */
+int ww_stream_ctc_set_targets(ww_streams *st, const int32_t *targets, const int32_t *target_lens, int32_t K, int32_t mode);
+int ww_stream_step_ctc_score(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels,
+                             int32_t *lengths, float *steps, float *scores, int32_t *n_post);
+int ww_ctc_score_trigger_bank_step(int32_t n_streams, int32_t K, const uint8_t *is_speech, uint8_t *is_active, const float *scores,
+                                   const int32_t *n_post, const double *thresholds, uint8_t *was_speech, int32_t *fired_ids,
+                                   int32_t *fired_slot, int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall);
 /* Where a tick's time goes on the HOST side of ww_stream_step (the loop of spokestack/pipeline.py:25-28 is host-paced, so
  * BASELINE config 5's per-tick latency is this call): mean nanoseconds per phase over the ticks since the last reset -
  * [0] plan (control words and window descriptors of the tick), [1] the caller's frames into the page-locked block,

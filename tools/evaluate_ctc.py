@@ -52,19 +52,30 @@ def parse_args():
     p.add_argument("--ctc_head", type=str, required=True, help=".npz with w [L, 64] and b [L] (the blank is the last class)")
     p.add_argument("--keras_kernel", action="store_true", help="w is stored as Keras keeps it, [64, L]")
     p.add_argument("--testset", type=str, default="test.h5")
+    p.add_argument("--thresholds", type=int, default=0, metavar="N",
+                   help="also score every clip with the CTC forward algorithm (P(decode == [HEY][SNIPS])) and print the FAR/FRR sweep over N "
+                        "thresholds evenly spaced in (0, 1)")
+    p.add_argument("--score_mode", type=str, default="exact", choices=("exact", "prefix"), help="exact: the decode IS the target; prefix: starts with it")
     return p.parse_args()
 
 
 def main(args):
     feats, labels, keys = read_records(os.path.join(args.data_dir, args.testset))
     eng = Engine(args.model_dir, bundle=ctc_bundle(args.model_dir, args.ctc_head, args.keras_kernel))
-    stats = evaluate_ctc(eng, feats, labels)
+    thr = np.linspace(0.0, 1.0, args.thresholds + 2)[1:-1] if args.thresholds > 0 else None
+    stats = evaluate_ctc(eng, feats, labels, thresholds=thr, mode=args.score_mode)
     eng.close()
     print("False accept files:", [k for k, p, t in zip(keys, stats["predicted"], labels) if p and not t])
     print("False reject files:", [k for k, p, t in zip(keys, stats["predicted"], labels) if t and not p])
     for name in ("tp", "fp", "tn", "fn", "precision", "recall"):
         print(f"{name}: {float(stats[name])}")
     print(f"balanced accuracy: {stats['balanced accuracy']}")
+    if thr is not None:
+        print(f"score ({args.score_mode}): wake-word clips median {np.median(stats['scores'][np.asarray(labels, bool)]) if any(labels) else float('nan'):.3g}, "
+              f"others median {np.median(stats['scores'][~np.asarray(labels, bool)]) if not all(labels) else float('nan'):.3g}")
+        print("threshold  FRR  FA/h  FA")
+        for t, frr, fa, cnt in zip(stats["thresholds"], stats["frr"], stats["fa_per_hour"], stats["fa_count"]):
+            print(f"{t:.4f}  {frr:.4f}  {fa:.3f}  {int(cnt)}")
     return stats
 
 

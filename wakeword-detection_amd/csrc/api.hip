@@ -1,5 +1,6 @@
 // C ABI of libwwhip.so: context, model upload, host/device entry points (see include/wwhip.h).
 #include "common.h"
+#include "ctc_score.h"
 #include "model_pack.h"
 #include "model_set.h"
 
@@ -780,6 +781,85 @@ static int ctc_host(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t ro
   return io.finish();
 }
 
+// ---- the forward-algorithm score (include/wwhip.h: ww_ctc_score_*; csrc/ctc_score.h) --------------------------------------------
+// the arguments every form shares -> the kernel's argument; WW_EINVAL naming the rule
+static int ctc_score_targets_of(ww_ctx *ctx, int T, int L, const int32_t *targets, const int32_t *target_lens, int K, int mode, const char *what,
+                                ww_ctc_score_targets &tg) {
+  char why[200];
+  if (!ww_ctc_score_args_ok(T, L, targets, target_lens, K, mode, why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "%s: %s", what, why);
+  memset(&tg, 0, sizeof tg);
+  tg.K = K;
+  tg.mode = mode;
+  for (int k = 0; k < K; ++k) {
+    tg.len[k] = (int8_t)target_lens[k];
+    for (int u = 0; u < target_lens[k]; ++u) tg.c[k][u] = (int8_t)targets[k * WW_CTC_SCORE_MAX_TARGET + u];
+  }
+  return WW_OK;
+}
+
+// what the three model forms refuse before anything is written: ctc_check's rules (labels and lengths are optional here, together)
+static int ctc_score_check(ww_ctx *ctx, const ww_model *m, const int32_t *targets, const int32_t *target_lens, int K, int mode, const void *score,
+                           int max_labels, const void *labels, const void *lengths, const char *what, ww_ctc_score_targets &tg) {
+  if (!ctx || !m) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (int rc = ww_crnn_ctc_check(ctx, m, what)) return rc;
+  if (int rc = ctc_score_targets_of(ctx, WW_CTC_STEPS, m->info.n_out, targets, target_lens, K, mode, what, tg)) return rc;
+  if ((labels == nullptr) != (lengths == nullptr)) return ww_fail(ctx, WW_EINVAL, "%s: labels and lengths go together", what);
+  if (labels && (max_labels < 1 || max_labels > WW_CTC_STEPS)) return ww_fail(ctx, WW_EINVAL, "%s: max_labels %d outside 1..%d", what, max_labels, WW_CTC_STEPS);
+  if (!score) return ww_fail(ctx, WW_EINVAL, "%s: score is NULL", what);
+  return WW_OK;
+}
+
+// device scratch of ctc_score_chunks for nw windows: a chunk's posteriors, its decode where the caller did not ask for one, the model's
+static size_t ctc_score_workspace(const ww_model *m, int64_t nw) {
+  const size_t chunk = (size_t)chunk_of(nw);
+  return ww_bump::need(chunk * WW_CTC_STEPS * m->info.n_out, 4) + 2 * ww_bump::need(chunk, 4) + ww_crnn_ctc_workspace(m, (int)chunk);
+}
+
+// ctc_chunks with the posteriors kept in the workspace and ctc_score_kernel behind every chunk's model launch: d_score [K][nw]
+// (d_labels / d_lengths: nullptr, or the decode beside the score).  ws: ctc_score_workspace(m, nw) bytes inside the device arena.
+static int ctc_score_chunks(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_row, const int32_t *d_valid,
+                            int hop, int valid_const, int64_t nw, void *ws, const ww_ctc_score_targets &tg, float *d_score, int max_labels,
+                            int32_t *d_labels, int32_t *d_lengths) {
+  const int chunk = chunk_of(nw), L = m->info.n_out;
+  ww_bump bump(ws, ctc_score_workspace(m, nw));
+  float *d_steps = bump.take<float>((size_t)chunk * WW_CTC_STEPS * L);
+  int32_t *own_lab = bump.take<int32_t>((size_t)chunk), *own_len = bump.take<int32_t>((size_t)chunk);
+  void *mws = bump.base + bump.off;
+  const char *lo = (const char *)ctx->dev.ptr, *p = (const char *)mws;
+  const size_t cap = (p >= lo && p <= lo + ctx->dev.cap) ? (size_t)(lo + ctx->dev.cap - p) : 0;
+  for (int64_t w0 = 0; w0 < nw; w0 += chunk) {
+    const int n = (int)((nw - w0) < chunk ? (nw - w0) : chunk);
+    if (int rc = ww_k_crnn_ctc_forward(ctx, m, d_mel, mel_rows, d_row ? d_row + w0 : nullptr, d_row ? d_valid + w0 : nullptr, d_row ? 0 : w0 * hop,
+                                       hop, valid_const, n, mws, cap, d_labels ? max_labels : 1, d_labels ? d_labels + (size_t)w0 * max_labels : own_lab,
+                                       d_labels ? d_lengths + w0 : own_len, d_steps, nullptr))
+      return rc;
+    if (int rc = ww_k_ctc_score(ctx, d_steps, n, WW_CTC_STEPS, L, tg, d_score + w0, nw, 1)) return rc;
+  }
+  return WW_OK;
+}
+
+// the host forms: the sequence in, the K planes (and the decode, where asked for) out, staged like ctc_host's
+static int ctc_score_host(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t rows, int hop, int64_t nw, const ww_ctc_score_targets &tg,
+                          float *score, int max_labels, int32_t *labels, int32_t *lengths) {
+  const int T = m->info.window, F = m->info.n_mel;
+  const size_t n_score = (size_t)nw * tg.K, n_lab = labels ? (size_t)nw * max_labels : 0;
+  WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
+  const size_t b_io = ww_bump::need((size_t)rows * F, 4) + ww_bump::need(n_score, 4) + (labels ? ww_bump::need(n_lab, 4) + ww_bump::need((size_t)nw, 4) : 0);
+  const size_t b_ws = ctc_score_workspace(m, nw);
+  ww_staged_io io(ctx);
+  int rc = io.init(b_io, b_ws + 1024, nw <= 64);
+  if (rc) return rc;
+  const float *d_mel = io.in(mel, (size_t)rows * F);
+  float *d_score = io.out<float>(n_score);
+  int32_t *d_lab = labels ? io.out<int32_t>(n_lab) : nullptr, *d_len = labels ? io.out<int32_t>((size_t)nw) : nullptr;
+  void *ws = io.scratch(b_ws);
+  if (io.rc) return io.rc;
+  if ((rc = ctc_score_chunks(ctx, m, d_mel, rows, nullptr, nullptr, hop, T, nw, ws, tg, d_score, max_labels, d_lab, d_len))) return rc;
+  if ((rc = io.fetch(score, d_score, n_score * 4))) return rc;
+  if (labels && ((rc = io.fetch(labels, d_lab, n_lab * 4)) || (rc = io.fetch(lengths, d_len, (size_t)nw * 4)))) return rc;
+  return io.finish();
+}
+
 __global__ void iota_offs_kernel(int64_t *sample_offs, int64_t *frame_offs, int n, int64_t samples, int64_t frames) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i <= n) {
@@ -893,6 +973,82 @@ int ww_ctc_greedy_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, i
   if (!d_steps || !d_labels || !d_lengths) return ww_fail(ctx, WW_EINVAL, "NULL argument");
   WW_ON_DEVICE(ctx, dev);
   return ww_k_ctc_greedy(ctx, d_steps, n, T, L, max_labels, d_labels, d_lengths);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_score_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, int32_t L, const int32_t *targets, const int32_t *target_lens,
+                     int32_t K, int32_t mode, float *d_score) {
+  WW_GUARD_BEGIN
+  if (!ctx) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  ww_ctc_score_targets tg;
+  if (int rc = ctc_score_targets_of(ctx, T, L, targets, target_lens, K, mode, "ww_ctc_score_dev", tg)) return rc;
+  if (n < 0 || n > 0x7fffffff) return ww_fail(ctx, WW_EINVAL, "ww_ctc_score_dev: sequence count out of range");
+  if (n == 0) return WW_OK;
+  if (!d_steps || !d_score) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  WW_ON_DEVICE(ctx, dev);
+  return ww_k_ctc_score(ctx, d_steps, n, T, L, tg, d_score, n, 1);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_score_rows(const float *steps, int64_t n, int32_t T, int32_t L, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                      int32_t mode, float *score) {
+  WW_GUARD_BEGIN
+  char why[200];
+  if (!ww_ctc_score_args_ok(T, L, targets, target_lens, K, mode, why, sizeof why)) return ww_fail(nullptr, WW_EINVAL, "ww_ctc_score_rows: %s", why);
+  if (n < 0) return ww_fail(nullptr, WW_EINVAL, "ww_ctc_score_rows: negative sequence count");
+  if (n == 0) return WW_OK;
+  if (!steps || !score) return ww_fail(nullptr, WW_EINVAL, "NULL argument");
+  for (int k = 0; k < K; ++k)
+    for (int64_t i = 0; i < n; ++i)
+      score[(size_t)k * n + i] = ww_ctc_score_row(steps + (size_t)i * T * L, T, L, L, targets + k * WW_CTC_SCORE_MAX_TARGET, target_lens[k], mode);
+  return WW_OK;
+  WW_GUARD_END(nullptr)
+}
+
+int ww_ctc_score(ww_ctx *ctx, const ww_model *m, const float *windows, int32_t n, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                 int32_t mode, float *score, int32_t max_labels, int32_t *labels, int32_t *lengths) {
+  WW_GUARD_BEGIN
+  ww_ctc_score_targets tg;
+  if (int rc = ctc_score_check(ctx, m, targets, target_lens, K, mode, score, max_labels, labels, lengths, "ww_ctc_score", tg)) return rc;
+  if (n < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
+  if (n == 0) return WW_OK;
+  if (!windows) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
+  // n stacked windows are one mel sequence of n * T rows read with hop = T
+  return ctc_score_host(ctx, m, windows, (int64_t)n * m->info.window, m->info.window, n, tg, score, max_labels, labels, lengths);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_slide_score(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t rows, int32_t hop, const int32_t *targets,
+                       const int32_t *target_lens, int32_t K, int32_t mode, float *score, int32_t max_labels, int32_t *labels, int32_t *lengths,
+                       int64_t *n_windows) {
+  WW_GUARD_BEGIN
+  ww_ctc_score_targets tg;
+  if (int rc = ctc_score_check(ctx, m, targets, target_lens, K, mode, score, max_labels, labels, lengths, "ww_ctc_slide_score", tg)) return rc;
+  if (!n_windows) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (hop <= 0) return ww_fail(ctx, WW_EINVAL, "hop must be positive");
+  if (rows < 0) return ww_fail(ctx, WW_EINVAL, "negative row count");
+  const int T = m->info.window;
+  const int64_t nw = rows >= T ? (rows - T) / hop + 1 : 0;
+  if (nw > 0 && !mel) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
+  *n_windows = nw;
+  if (nw == 0) return WW_OK;
+  return ctc_score_host(ctx, m, mel, rows, hop, nw, tg, score, max_labels, labels, lengths);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_score_windows_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                             const int32_t *d_win_valid, int32_t n, const int32_t *targets, const int32_t *target_lens, int32_t K, int32_t mode,
+                             float *d_score, int32_t max_labels, int32_t *d_labels, int32_t *d_lengths) {
+  WW_GUARD_BEGIN
+  ww_ctc_score_targets tg;
+  if (int rc = ctc_score_check(ctx, m, targets, target_lens, K, mode, d_score, max_labels, d_labels, d_lengths, "ww_ctc_score_windows_dev", tg)) return rc;
+  if (n < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
+  if (n == 0) return WW_OK;
+  if (!d_mel) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (!d_win_row || !d_win_valid) return ww_fail(ctx, WW_EINVAL, "window descriptors are NULL");
+  WW_ON_DEVICE(ctx, dev);
+  if (int rc = ww_ensure(ctx, ctx->dev, ctc_score_workspace(m, n) + 1024, false)) return rc;
+  return ctc_score_chunks(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, n, ctx->dev.ptr, tg, d_score, max_labels, d_labels, d_lengths);
   WW_GUARD_END(ctx)
 }
 

@@ -279,6 +279,16 @@ int ww_k_crnn_ctc_forward(ww_ctx *ctx, const ww_model *m, const float *d_mel, in
                           const int32_t *d_win_valid, int64_t row0, int hop, int valid_const, int n_windows, void *ws, size_t ws_bytes,
                           int max_labels, int32_t *d_labels, int32_t *d_lengths, float *d_steps, float *d_enc);
 int ww_k_ctc_greedy(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, int max_labels, int32_t *d_labels, int32_t *d_lengths);
+// ctc_score_kernel (ctc_score.hip; the statement: ctc_score.h): the forward-algorithm score of K targets over any device posteriors
+// [n][T][L], score[k * stride_k + i * stride_i] for sequence i and target k.  The targets travel as a kernel argument; a caller
+// fills the struct only from arguments that ww_ctc_score_args_ok has passed (labels < 63 fit its bytes).
+struct ww_ctc_score_targets {
+  int8_t c[8][9];  // [WW_CTC_SCORE_MAX_TARGETS][WW_CTC_SCORE_MAX_TARGET]
+  int8_t len[8];
+  int32_t K = 0, mode = 0;
+};
+int ww_k_ctc_score(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, const ww_ctc_score_targets &tg, float *d_score, int64_t stride_k,
+                   int64_t stride_i);
 // A CTC stream bank's incremental ticks (crnn_stream_kernel<FE, false, false, CTC>): ww_k_crnn_tick's and ww_k_crnn_stream_forward's
 // arguments; a window's decode goes out as one 32-bit word (stream_ctc.h) - the value half of its tag where tag slots are given, else
 // row w of d_words -, and with d_steps (page-locked, [windows of the launch][19][L]; nullptr: off) its posteriors beside it

@@ -103,3 +103,49 @@ static inline int sc_check_trigger(int64_t S, const void *is_speech, const void 
     if (n_post[s] < 0 || n_post[s] > 2) return -1;
   return 0;
 }
+
+// The same stage with the SCORE rule (ctc_score.h: a window's forward-algorithm scores for K targets, one per slot): the VAD-edge
+// bookkeeping above, and stream_all.h's comparison (sa_trigger_update: the float32 value against a Python float, (double)p > t).
+//   scores [S][2][K] (window k of the tick, slot j), n_post [S], thresholds [K]
+//   - a stream that is not active FIRES on the first window of the tick on which some slot j has (double)score > thresholds[j]:
+//     is_active[s] = 1, fired_ids gets s and fired_slot the exceeding slot with the greatest score on that window, the lowest slot
+//     among equals; a stream that is already active does not fire again
+//   - fall_ids: the streams whose VAD bit fell (the caller resets them)
+// fired_slot may be nullptr.  Arguments are the caller's to check (sc_check_score_trigger).
+static inline void sc_score_trigger_update(int S, int K, const uint8_t *is_speech, uint8_t *is_active, const float *scores, const int32_t *n_post,
+                                           const double *thresholds, uint8_t *was_speech, int32_t *fired_ids, int32_t *fired_slot,
+                                           int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall) {
+  int nf = 0, nl = 0;
+  for (int s = 0; s < S; ++s) {
+    const uint8_t sp = is_speech[s] != 0;
+    const bool fall = was_speech[s] && !sp;
+    was_speech[s] = sp;
+    int win = -1;
+    for (int k = 0; k < n_post[s] && win < 0; ++k) {
+      const float *p = scores + ((size_t)s * 2 + k) * K;
+      for (int j = 0; j < K; ++j)
+        if ((double)p[j] > thresholds[j] && (win < 0 || p[j] > p[win])) win = j;
+    }
+    if (win >= 0 && !is_active[s]) {
+      is_active[s] = 1;
+      fired_ids[nf] = s;
+      if (fired_slot) fired_slot[nf] = win;
+      ++nf;
+    }
+    if (fall) fall_ids[nl++] = s;
+  }
+  *n_fired = nf;
+  *n_fall = nl;
+}
+
+// The arguments of ww_ctc_score_trigger_bank_step (include/wwhip.h): 0, or -1 with nothing touched
+static inline int sc_check_score_trigger(int64_t S, int64_t K, const void *is_speech, const void *is_active, const void *scores, const int32_t *n_post,
+                                         const void *thresholds, const void *was_speech, const void *fired_ids, const void *fired_slot,
+                                         const void *n_fired, const void *fall_ids, const void *n_fall) {
+  (void)fired_slot;
+  if (S < 0 || K < 1 || K > 8 || !n_fired || !n_fall || !thresholds) return -1;
+  if (S > 0 && (!is_speech || !is_active || !scores || !n_post || !was_speech || !fired_ids || !fall_ids)) return -1;
+  for (int64_t s = 0; s < S; ++s)
+    if (n_post[s] < 0 || n_post[s] > 2) return -1;
+  return 0;
+}

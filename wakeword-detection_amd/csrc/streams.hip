@@ -28,6 +28,7 @@
 #include "model_set.h"  // (in front of fft_device.h's macros)
 #include "stream_all.h"
 #include "stream_ctc.h"
+#include "ctc_score.h"
 #include "stream_fe.h"
 
 #include <algorithm>
@@ -122,6 +123,11 @@ struct ww_streams {
   bool ctc = false, ctc_steps = false;
   float *h_steps = nullptr, *h_steps_dev = nullptr;
   int32_t *h_lab = nullptr, *h_lab_dev = nullptr;
+  // ww_stream_ctc_set_targets (a WW_STREAM_CTC_STEPS bank): ww_stream_step_ctc_score runs ctc_score_kernel over h_steps behind the
+  // tick's model launch, on the same stream; its scores arrive in h_score [2 S][K], slot for slot beside the posteriors
+  bool score_set = false;
+  ww_ctc_score_targets score_tg;
+  float *h_score = nullptr, *h_score_dev = nullptr;
   // the reason this bank refuses `call` (CTC or not: here; every-member or not: stream_all.h, sa_check_call), where ww_last_error
   // finds it; WW_OK: it does not
   int check_call(const char *call, bool wants_every, bool wants_ctc = false) const {
@@ -419,7 +425,7 @@ int ww_stream_destroy(ww_streams *st) {
   void *dev[] = {st->ring, st->hist, st->prev, st->d_pack, st->ws, st->gxc, st->gx_zero, st->wstate, st->zring, st->zpos, st->d_stream_model};
   for (void *p : dev)
     if (p) hipFree(p);
-  void *host[] = {st->h_pack, st->h_out, st->h_tag, st->h_steps, st->h_lab};
+  void *host[] = {st->h_pack, st->h_out, st->h_tag, st->h_steps, st->h_lab, st->h_score};
   for (void *p : host)
     if (p) hipHostFree(p);
   ww_k_rates_destroy(st->rates);
@@ -898,6 +904,7 @@ struct st_ctc_out {
   int max_labels;
   int32_t *labels, *lengths;  // [S][2][max_labels], [S][2]
   float *steps;               // [S][2][19][L] or nullptr
+  float *scores;              // [S][2][K] or nullptr (ww_stream_step_ctc_score: the bank's targets are set)
 };
 
 // The one tick of every bank.  co (a CTC bank, stream_ctc.h): the same bookkeeping, frames, front end and wait; the model launches
@@ -1030,6 +1037,12 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
       second = true;
     }
   }
+  // ww_stream_step_ctc_score: the forward-algorithm scores of the tick's windows, one more launch behind the model's, over the
+  // posterior block slot for slot (the table form fills slots 0 .. nw - 1, the one-launch form slot 2 s + k: all 2 S are scored, and a
+  // slot no window of this tick wrote is not read back)
+  if (co && co->scores && nw)
+    if (int rc = ww_k_ctc_score(ctx, st->h_steps_dev, tk.form == SA_TABLE ? nw : 2 * S, WW_SC_STEPS, st->NO, st->score_tg, st->h_score_dev, 1, st->score_tg.K))
+      return rc;
   // (include/wwhip.h: phase [3] is 0 where a tick is one launch - the one-launch forms, and a two-launch bank's tick without a window:
   // no clock read of its own, which on a tick's first pass through this code measured the branches above, not a launch)
   tl[4] = second ? st_now_ns() : tl[3];
@@ -1055,6 +1068,13 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
       for (int s = 0; s < S; ++s)
         for (int k = 0; k < n_post[s]; ++k, ++w)
           memcpy(co->steps + ((size_t)s * 2 + k) * row, st->h_steps + (size_t)(table ? w : 2 * s + k) * row, row * sizeof(float));
+    }
+    if (co->scores) {
+      const size_t row = (size_t)st->score_tg.K;
+      int w = 0;
+      for (int s = 0; s < S; ++s)
+        for (int k = 0; k < n_post[s]; ++k, ++w)
+          memcpy(co->scores + ((size_t)s * 2 + k) * row, st->h_score + (size_t)(table ? w : 2 * s + k) * row, row * sizeof(float));
     }
   } else
   // post[s][slot][k] from where it arrived (stream_all.h): a tag's low word, or the posterior column of a row of h_out
@@ -1495,7 +1515,7 @@ int ww_stream_timeline(ww_streams *st, double *mean_ns, int64_t *ticks, int32_t 
 // ---- a CTC stream bank (include/wwhip.h; stream_ctc.h) ----------------------------------------------------------------------------------
 // ww_stream_step_ctc's refusals - all before any state moves -, then the one tick
 static int stream_step_ctc_entry(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels,
-                                 int32_t *lengths, float *steps, int32_t *n_post, const char *call) {
+                                 int32_t *lengths, float *steps, int32_t *n_post, const char *call, float *scores = nullptr) {
   ww_ctx *ctx = st->ctx;
   if (int rc = st->check_call(call, false, true)) return rc;
   if (int rc = st->check_sound()) return rc;
@@ -1503,7 +1523,7 @@ static int stream_step_ctc_entry(ww_streams *st, const int16_t *frames, const ui
     return ww_fail(ctx, WW_EINVAL, "%s: max_labels %d: a streamed window carries 1..%d labels", call, (int)max_labels, WW_STREAM_CTC_MAX_LABELS);
   if (!labels || !lengths) return ww_fail(ctx, WW_EINVAL, "%s: NULL argument", call);
   if (steps && !st->ctc_steps) return ww_fail(ctx, WW_EINVAL, "%s: posteriors are returned by a bank created with WW_STREAM_CTC_STEPS", call);
-  const st_ctc_out co = {max_labels, labels, lengths, steps};
+  const st_ctc_out co = {max_labels, labels, lengths, steps, scores};
   return stream_step_entry(st, frames, is_speech, nullptr, n_post, call, false, &co);
 }
 
@@ -1527,6 +1547,60 @@ int ww_stream_step_ctc(ww_streams *st, const int16_t *frames, const uint8_t *is_
   if (!st) return WW_EINVAL;
   return stream_step_ctc_entry(st, frames, is_speech, max_labels, labels, lengths, steps, n_post, "ww_stream_step_ctc");
   WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+int ww_stream_ctc_set_targets(ww_streams *st, const int32_t *targets, const int32_t *target_lens, int32_t K, int32_t mode) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  const char *call = "ww_stream_ctc_set_targets";
+  ww_ctx *ctx = st->ctx;
+  if (int rc = st->check_call(call, false, true)) return rc;
+  if (!st->ctc_steps) return ww_fail(ctx, WW_EINVAL, "%s: the score is computed from a tick's posteriors: the bank must be created with WW_STREAM_CTC_STEPS", call);
+  char why[200];
+  if (!ww_ctc_score_args_ok(WW_SC_STEPS, st->NO, targets, target_lens, K, mode, why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "%s: %s", call, why);
+  if (!st->h_score) {
+    WW_ON_DEVICE(ctx, dev_scope);
+    if (hipHostMalloc((void **)&st->h_score, (size_t)2 * st->S * WW_CTC_SCORE_MAX_TARGETS * 4) != hipSuccess) {
+      st->h_score = nullptr;
+      return ww_fail(ctx, WW_ENOMEM, "%s: cannot allocate the score block of %d streams", call, st->S);
+    }
+    if (hipHostGetDevicePointer((void **)&st->h_score_dev, st->h_score, 0) != hipSuccess) return ww_fail(ctx, WW_EHIP, "%s: the score block is not visible to the device", call);
+  }
+  ww_ctc_score_targets &tg = st->score_tg;
+  memset(&tg, 0, sizeof tg);
+  tg.K = K;
+  tg.mode = mode;
+  for (int k = 0; k < K; ++k) {
+    tg.len[k] = (int8_t)target_lens[k];
+    for (int u = 0; u < target_lens[k]; ++u) tg.c[k][u] = (int8_t)targets[k * WW_CTC_SCORE_MAX_TARGET + u];
+  }
+  st->score_set = true;
+  return WW_OK;
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+int ww_stream_step_ctc_score(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels,
+                             int32_t *lengths, float *steps, float *scores, int32_t *n_post) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  const char *call = "ww_stream_step_ctc_score";
+  if (int rc = st->check_call(call, false, true)) return rc;
+  if (!st->score_set) return ww_fail(st->ctx, WW_EINVAL, "%s: the bank has no targets (ww_stream_ctc_set_targets)", call);
+  if (!scores) return ww_fail(st->ctx, WW_EINVAL, "%s: NULL argument", call);
+  return stream_step_ctc_entry(st, frames, is_speech, max_labels, labels, lengths, steps, n_post, call, scores);
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+// ww_ctc_trigger_bank_step with the score rule (stream_ctc.h: sc_score_trigger_update, where the rule is stated)
+int ww_ctc_score_trigger_bank_step(int32_t S, int32_t K, const uint8_t *is_speech, uint8_t *is_active, const float *scores, const int32_t *n_post,
+                                   const double *thresholds, uint8_t *was_speech, int32_t *fired_ids, int32_t *fired_slot, int32_t *n_fired,
+                                   int32_t *fall_ids, int32_t *n_fall) {
+  WW_GUARD_BEGIN
+  if (sc_check_score_trigger(S, K, is_speech, is_active, scores, n_post, thresholds, was_speech, fired_ids, fired_slot, n_fired, fall_ids, n_fall))
+    return WW_EINVAL;
+  sc_score_trigger_update(S, K, is_speech, is_active, scores, n_post, thresholds, was_speech, fired_ids, fired_slot, n_fired, fall_ids, n_fall);
+  return WW_OK;
+  WW_GUARD_END(nullptr)
 }
 
 // ww_trigger_bank_step with the label rule in place of the threshold (stream_ctc.h: sc_trigger_update, where the rule is stated)

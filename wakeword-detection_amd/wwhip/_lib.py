@@ -28,6 +28,8 @@ OPT_CRNN_SPLIT_AT, OPT_CRNN_SLIDE_MIN, OPT_CRNN_TAIL_MFMA, OPT_WAVENET_ROWMAJOR,
 STREAM_FULL_RECOMPUTE, STREAM_TWO_LAUNCH, STREAM_SYNC_WAIT, STREAM_CAUSAL = 1, 2, 4, 8
 STREAM_CTC_STEPS = 16       # a CTC stream bank that also returns per-step posteriors (ww_stream_create_ctc)
 STREAM_CTC_MAX_LABELS = 9   # include/wwhip.h: WW_STREAM_CTC_MAX_LABELS
+CTC_SCORE_MAX_TARGET, CTC_SCORE_MAX_TARGETS = 9, 8  # include/wwhip.h: WW_CTC_SCORE_MAX_TARGET[S]
+CTC_SCORE_EXACT, CTC_SCORE_PREFIX = 0, 1      # include/wwhip.h: WW_CTC_SCORE_*
 SAMPLE_I16, SAMPLE_F32 = 0, 1
 SAMPLE_MULAW, SAMPLE_ALAW = 8, 9  # G.711, one byte per sample: input formats
 SET_MAX_MODELS = 64  # include/wwhip.h: WW_SET_MAX_MODELS
@@ -90,6 +92,11 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_ctc_forward_windows_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ww_ctc_slide_forward": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _P(_i64)]),
     "ww_ctc_greedy_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "ww_ctc_score_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "ww_ctc_score_rows": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "ww_ctc_score": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "ww_ctc_score_windows_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "ww_ctc_slide_score": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _P(_i64)]),
     "ww_model_set_precision": (C.c_int, [_vp, C.c_int]),
     "ww_model_set_option": (C.c_int, [_vp, C.c_int, _i64]),
     "ww_model_set_create": (C.c_int, [_vp, _P(_vp), _i32, _P(_vp)]),
@@ -160,6 +167,9 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_stream_step_ctc": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "ww_ctc_trigger_bank_step": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ww_stream_step_ctc_trigger": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ww_stream_ctc_set_targets": (C.c_int, [_vp, _vp, _vp, _i32, _i32]),
+    "ww_stream_step_ctc_score": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ww_ctc_score_trigger_bank_step": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ww_superframe_smooth": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp]),
     "ww_far_frr": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),
     "ww_far_frr_dev": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),

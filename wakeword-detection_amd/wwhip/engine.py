@@ -346,6 +346,67 @@ class Engine:
         self._chk(self._lib.ww_ctc_greedy_dev(self.ctx.handle, _vp(d_steps_ptr), int(n), int(T), int(L), int(max_labels), _vp(d_labels_ptr),
                                               _vp(d_lengths_ptr)))
 
+    # the forward-algorithm score (include/wwhip.h: ww_ctc_score_*; wwhip.ctc.score is its float64 statement)
+    def _ctc_score_args(self, targets, mode, L: int):
+        from . import ctc
+        table, lens = ctc.pack_targets(targets, L)
+        return table, lens, len(lens), ctc.score_mode(mode)
+
+    def ctc_score(self, windows: np.ndarray, targets=((1, 2),), mode="exact", max_labels: int = 0):
+        """``[B, window, 40]`` -> ``scores [K, B]`` float32: per target (a tuple of labels; ``[HEY][SNIPS]`` by default) and window the
+        probability that the window's decode is (``mode="exact"``, the CTC loss's quantity) or starts with (``"prefix"``) the target,
+        from the posteriors :meth:`ctc_forward` returns as ``steps`` (``ww_ctc_score``).  Plane ``k`` is a posterior track for
+        :func:`wwhip.evaluate.far_frr` and the event calls.  With ``max_labels > 0`` the greedy decode comes with it:
+        ``(scores, CtcResult(labels, lengths))``."""
+        from .ctc import CtcResult
+        table, lens, K, md = self._ctc_score_args(targets, mode, self.n_out)
+        w = np.ascontiguousarray(windows, dtype=np.float32)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.shape[1] != self.window or w.shape[2] != self.n_mel:
+            raise ValueError(f"Cannot set tensor: Dimension mismatch. Got {tuple(w.shape[1:])} but expected "
+                             f"{(self.window, self.n_mel)} per window")
+        n, m = w.shape[0], int(max_labels)
+        scores = np.empty((K, n), np.float32)
+        labels, lengths = (np.full((n, m), -1, np.int32), np.zeros(n, np.int32)) if m else (None, None)
+        self._chk(self._lib.ww_ctc_score(self.ctx.handle, self._model, _lib.ptr(w), n, _lib.ptr(table), _lib.ptr(lens), K, md, _lib.ptr(scores),
+                                         m, _lib.ptr(labels), _lib.ptr(lengths)))
+        return (scores, CtcResult(labels, lengths)) if m else scores
+
+    def ctc_slide_score(self, mel: np.ndarray, hop: int = 2, targets=((1, 2),), mode="exact", max_labels: int = 0):
+        """:meth:`ctc_score` of the windows sliding over one ``[rows, 40]`` sequence (``ww_ctc_slide_score``): ``scores [K, n_windows]``."""
+        from .ctc import CtcResult
+        table, lens, K, md = self._ctc_score_args(targets, mode, self.n_out)
+        mm = np.ascontiguousarray(mel, dtype=np.float32)
+        if mm.ndim != 2 or mm.shape[1] != self.n_mel:
+            raise ValueError(f"mel must be [rows, {self.n_mel}]")
+        if hop < 1:
+            raise ValueError("hop must be positive")
+        rows, m = mm.shape[0], int(max_labels)
+        nw = (rows - self.window) // hop + 1 if rows >= self.window else 0
+        scores = np.empty((K, nw), np.float32)
+        labels, lengths = (np.full((nw, m), -1, np.int32), np.zeros(nw, np.int32)) if m else (None, None)
+        got = C.c_int64(0)
+        self._chk(self._lib.ww_ctc_slide_score(self.ctx.handle, self._model, _lib.ptr(mm), rows, int(hop), _lib.ptr(table), _lib.ptr(lens), K, md,
+                                               _lib.ptr(scores), m, _lib.ptr(labels), _lib.ptr(lengths), C.byref(got)))
+        assert got.value == nw
+        return (scores, CtcResult(labels, lengths)) if m else scores
+
+    def ctc_score_windows_dev(self, d_mel_ptr: int, mel_rows: int, d_win_row_ptr: int, d_win_valid_ptr: int, n_windows: int, targets, mode,
+                              d_score_ptr: int, max_labels: int = 0, d_labels_ptr: int = 0, d_lengths_ptr: int = 0) -> None:
+        """``ww_ctc_score_windows_dev`` on device addresses: ``d_score [K, n_windows]`` (enqueued on the context's stream)."""
+        table, lens, K, md = self._ctc_score_args(targets, mode, self.n_out)
+        self._chk(self._lib.ww_ctc_score_windows_dev(self.ctx.handle, self._model, _vp(d_mel_ptr), int(mel_rows), _vp(d_win_row_ptr),
+                                                     _vp(d_win_valid_ptr), int(n_windows), _lib.ptr(table), _lib.ptr(lens), K, md,
+                                                     _vp(d_score_ptr), int(max_labels), _vp(d_labels_ptr), _vp(d_lengths_ptr)))
+
+    def ctc_score_dev(self, d_steps_ptr: int, n: int, T: int, L: int, targets, mode, d_score_ptr: int) -> None:
+        """``ww_ctc_score_dev``: the score kernel alone on device posteriors ``[n, T, L]`` -> ``d_score [K, n]`` (any model; the
+        context is this engine's)."""
+        table, lens, K, md = self._ctc_score_args(targets, mode, int(L))
+        self._chk(self._lib.ww_ctc_score_dev(self.ctx.handle, _vp(d_steps_ptr), int(n), int(T), int(L), _lib.ptr(table), _lib.ptr(lens), K, md,
+                                             _vp(d_score_ptr)))
+
     SEQUENCE_OUTPUTS = ("enc", "logits", "post_frames", "post")
 
     def sequence_forward(self, mels, pool: Optional[int] = None, want: Sequence[str] = ("post",)) -> dict:
@@ -1222,11 +1283,13 @@ class StreamBank:
 class CtcTick(NamedTuple):
     """What :meth:`CtcStreamBank.step` returns: ``labels [S, 2, max_labels]`` int32 padded with -1, ``lengths [S, 2]`` int32 (the whole
     decoded length, which may exceed ``max_labels``), ``n [S]`` the windows each stream delivered this tick (0, 1 or 2; entries at
-    or past ``n[s]`` are -1 / 0 / 0), and on a ``want_steps`` bank ``steps [S, 2, 19, L]``."""
+    or past ``n[s]`` are -1 / 0 / 0), on a ``want_steps`` bank ``steps [S, 2, 19, L]``, and on a bank with ``targets``
+    ``scores [S, 2, K]`` float32: the forward-algorithm score of window k of stream s for target j (``wwhip.ctc.score``)."""
     labels: np.ndarray
     lengths: np.ndarray
     n: np.ndarray
     steps: Optional[np.ndarray] = None
+    scores: Optional[np.ndarray] = None
 
 
 class CtcStreamBank(StreamBank):
@@ -1239,19 +1302,41 @@ class CtcStreamBank(StreamBank):
     :meth:`window`; the incremental forms agree with it within the float32 bound of the recurrences.  ``sample_rate``,
     ``sample_format`` and ``resampler`` are :class:`StreamBank`'s.  :meth:`reset`, :meth:`window`, :meth:`set_rate`,
     :meth:`timeline`, :meth:`close` and the frame-layout attributes work as there; :meth:`feed`, :meth:`set_model` and the other
-    banks' trigger stages are refused."""
+    banks' trigger stages are refused.
+
+    ``targets`` (label tuples, at most 8 of at most 9 labels) and ``mode`` (``"exact"`` / ``"prefix"``): every tick also gives the
+    windows' forward-algorithm scores, ``CtcTick.scores`` - one more small launch behind the tick's, over the posteriors, so the
+    bank keeps them (``WW_STREAM_CTC_STEPS``) whether or not ``want_steps`` returns them.  :meth:`set_targets` changes them."""
     MAX_LABELS = _lib.STREAM_CTC_MAX_LABELS
 
     def __init__(self, engine, n_streams: int, fp: Optional[_lib.FrontendParams] = None, max_labels: int = 2, want_steps: bool = False,
                  two_launch: bool = False, sync_wait: bool = False, full_recompute: bool = False, sample_rate=16000,
-                 sample_format="pcm16", resampler=None) -> None:
+                 sample_format="pcm16", resampler=None, targets=None, mode="exact") -> None:
         if isinstance(engine, ModelSet) or not getattr(engine, "is_ctc", False):
             raise ValueError("CtcStreamBank runs one CTC-trained CRNN (an Engine whose is_ctc is true); StreamBank runs the other models")
         if not 1 <= int(max_labels) <= self.MAX_LABELS:
             raise ValueError(f"max_labels {max_labels} outside 1..{self.MAX_LABELS}: a streamed window carries at most {self.MAX_LABELS} labels")
         self.max_labels, self.want_steps = int(max_labels), bool(want_steps)
+        self.n_targets = 0
+        self._keep_steps = self.want_steps or targets is not None
+        if targets is not None:  # (refused here, before a bank exists)
+            from . import ctc
+            ctc.pack_targets(targets, engine.n_out), ctc.score_mode(mode)
         super().__init__(engine, n_streams, fp, full_recompute=full_recompute, two_launch=two_launch, sync_wait=sync_wait,
                          sample_rate=sample_rate, resampler=resampler, sample_format=sample_format)
+        if targets is not None:
+            self.set_targets(targets, mode)
+
+    def set_targets(self, targets, mode="exact") -> None:
+        """The targets and mode of :attr:`CtcTick.scores` from the next tick on (``ww_stream_ctc_set_targets``); the bank must have
+        been created with ``targets`` or ``want_steps``."""
+        from . import ctc
+        table, lens = ctc.pack_targets(targets, self.engine.n_out)
+        _lib.raise_for(self._lib.ww_stream_ctc_set_targets(self._h, _lib.ptr(table), _lib.ptr(lens), len(lens), ctc.score_mode(mode)),
+                       self.engine.ctx.handle)
+        self.n_targets = len(lens)
+        self._scores = np.zeros((self.S, 2, self.n_targets), np.float32)
+        self._p_scores = C.c_void_p(self._scores.ctypes.data)
 
     def _create(self, fp, full_recompute, two_launch, sync_wait, causal, ids) -> None:
         engine = self.engine
@@ -1259,7 +1344,7 @@ class CtcStreamBank(StreamBank):
         fp = fp or frontend_params()
         h = C.c_void_p()
         flags = ((_lib.STREAM_FULL_RECOMPUTE if full_recompute else 0) | (_lib.STREAM_TWO_LAUNCH if two_launch else 0)
-                 | (_lib.STREAM_SYNC_WAIT if sync_wait else 0) | (_lib.STREAM_CTC_STEPS if self.want_steps else 0))
+                 | (_lib.STREAM_SYNC_WAIT if sync_wait else 0) | (_lib.STREAM_CTC_STEPS if self._keep_steps else 0))
         self.causal = False
         _lib.raise_for(self._lib.ww_stream_create_ctc(engine.ctx.handle, engine.handle, self.S, C.byref(fp), flags, C.byref(h)), engine.ctx.handle)
         self._h = h
@@ -1285,7 +1370,11 @@ class CtcStreamBank(StreamBank):
         if is_active is not None:
             self._flags |= (np.ascontiguousarray(is_active, dtype=np.uint8).ravel() & 1) << 1
         self._clear()
-        rc = self._lib.ww_stream_step_ctc(self._h, pf, self._p_flags, self.max_labels, self._p_labels, self._p_lengths, self._p_steps, self._p_n)
+        if self.n_targets:
+            rc = self._lib.ww_stream_step_ctc_score(self._h, pf, self._p_flags, self.max_labels, self._p_labels, self._p_lengths, self._p_steps,
+                                                    self._p_scores, self._p_n)
+        else:
+            rc = self._lib.ww_stream_step_ctc(self._h, pf, self._p_flags, self.max_labels, self._p_labels, self._p_lengths, self._p_steps, self._p_n)
         if rc:
             _lib.raise_for(rc, self.engine.ctx.handle)
         return self._tick()
@@ -1296,9 +1385,12 @@ class CtcStreamBank(StreamBank):
         self._lengths[:] = 0
         if self._steps is not None:
             self._steps[:] = 0.0
+        if self.n_targets:
+            self._scores[:] = 0.0
 
     def _tick(self) -> CtcTick:
-        return CtcTick(self._labels.copy(), self._lengths.copy(), self._n.copy(), None if self._steps is None else self._steps.copy())
+        return CtcTick(self._labels.copy(), self._lengths.copy(), self._n.copy(), None if self._steps is None else self._steps.copy(),
+                       self._scores.copy() if self.n_targets else None)
 
     def step_ctc_trigger(self, frames: np.ndarray, p_is_speech, p_is_active, p_target, n_target: int, p_state) -> CtcTick:
         """The wake-word stage of all streams as ONE library call (``ww_stream_step_ctc_trigger``): the tick, the label rule over

@@ -1145,13 +1145,21 @@ def ctc_statistics(y_true, y_pred) -> dict:
             "balanced accuracy": float(np.mean(recalls)) if recalls else 0.0}
 
 
-def evaluate_ctc(engine: Engine, features: Sequence[np.ndarray], is_hotword: Sequence[int], target: Sequence[int] = (1, 2)) -> dict:
+def evaluate_ctc(engine: Engine, features: Sequence[np.ndarray], is_hotword: Sequence[int], target: Sequence[int] = (1, 2),
+                 thresholds=None, mode: str = "exact", windowsize: int = 1) -> dict:
     """``eval_CTC`` (``wwdetect/CRNN/evaluate.py:100-150``) for a CTC-trained CRNN over the records of an H5 feature file:
     ``features`` is a list of ``[frames_i, n_mel]`` arrays (what ``DatasetFilter`` writes), ``is_hotword`` their attribute.  One
     upload of all rows, ONE ``ww_ctc_forward_windows_dev`` over descriptors - one window per clip, truncated to the model's window
     and zero-padded at the end on the device (``dataloader.py:90-92``) - and one download of the decoded labels.  A clip is a wake
     word iff its first ``len(target)`` decoded labels are ``target`` ([HEY][SNIPS]).  Returns :func:`ctc_statistics` plus
-    ``"decoded"`` (the per-clip strings), ``"predicted"``, ``"labels"`` and ``"lengths"``."""
+    ``"decoded"`` (the per-clip strings), ``"predicted"``, ``"labels"`` and ``"lengths"``.
+
+    ``thresholds`` (an array, or ``True`` for :func:`default_thresholds`): the clips also get a SCORE - the forward-algorithm
+    probability that a clip's decode is (``mode="exact"``, the CTC loss's quantity) or starts with (``"prefix"``) ``target``
+    (``wwhip.ctc.score``; ``ww_ctc_score_windows_dev``, the decode coming out of the same call) - and the result gains ``"scores"``
+    ``[n]`` and the sweep of :func:`far_frr` over them: ``"thresholds"``, ``"frr"``, ``"fa_per_hour"``, ``"fa_count"`` - the wake-word
+    clips' scores against the others' in record order, the others' duration counted at 10 ms a frame.  ``windowsize`` is
+    :func:`far_frr`'s smoothing of the negative track (1: none - these are one score per clip, not per frame)."""
     import torch
 
     from . import ctc
@@ -1179,12 +1187,27 @@ def evaluate_ctc(engine: Engine, features: Sequence[np.ndarray], is_hotword: Seq
         d_lab = torch.empty((n, k), dtype=torch.int32, device=dev)
         d_len = torch.empty(n, dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)  # (torch's stream is not the context's)
-        engine.ctc_forward_windows_dev(d_mel.data_ptr(), total, d_row.data_ptr(), d_valid.data_ptr(), n, k, d_lab.data_ptr(), d_len.data_ptr())
+        if thresholds is None:
+            engine.ctc_forward_windows_dev(d_mel.data_ptr(), total, d_row.data_ptr(), d_valid.data_ptr(), n, k, d_lab.data_ptr(), d_len.data_ptr())
+        else:
+            d_score = torch.empty(n, dtype=torch.float32, device=dev)
+            engine.ctc_score_windows_dev(d_mel.data_ptr(), total, d_row.data_ptr(), d_valid.data_ptr(), n, [tuple(int(c) for c in target)], mode,
+                                         d_score.data_ptr(), k, d_lab.data_ptr(), d_len.data_ptr())
         engine.ctx.synchronize()
         labels, lengths = d_lab.cpu().numpy(), d_len.cpu().numpy()
+        if thresholds is not None:
+            scores = d_score.cpu().numpy()
     pred = ctc.is_wakeword(labels, lengths, target)
     out = ctc_statistics(np.asarray(is_hotword).astype(bool), pred)
     out.update(decoded=[ctc.label_string(labels[i], lengths[i]) for i in range(n)], predicted=pred, labels=labels, lengths=lengths)
+    if thresholds is not None:
+        truth = np.asarray(is_hotword).astype(bool)
+        if not n:
+            scores = np.zeros(0, np.float32)
+        thr = None if thresholds is True else thresholds
+        hours = float(rows[~truth].sum()) * 0.01 / 3600.0
+        thr, frr, fa, cnt = far_frr(scores[truth], scores[~truth], int(truth.sum()), hours, thr, windowsize=windowsize, engine=engine)
+        out.update(scores=scores, thresholds=thr, frr=frr, fa_per_hour=fa, fa_count=cnt)
     return out
 
 

@@ -317,13 +317,23 @@ class CtcWakewordBank:
     ``engine``: an :class:`~wwhip.engine.Engine` on a CTC-trained CRNN, from which the stage builds its bank; or ``bank=``: a
     ``CtcStreamBank`` of the caller's (``engine`` / ``pre_emphasis`` are then not looked at), whose ``max_labels`` must reach
     ``len(target)``.  ``on_wake(ids)`` is called with the streams that fired this tick.  ``contexts`` and ``frames`` of :meth:`step`
-    are :meth:`WakewordBank.step`'s; it returns the tick (:class:`~wwhip.engine.CtcTick`)."""
+    are :meth:`WakewordBank.step`'s; it returns the tick (:class:`~wwhip.engine.CtcTick`).
+
+    ``thresholds`` (one per target of the bank; a number for one target): the SCORE rule instead - a stream that is not active fires
+    on the first window of the tick whose forward-algorithm score (``wwhip.ctc.score``, ``CtcTick.scores``) for some target ``j``
+    exceeds ``thresholds[j]``, :class:`WakewordSetBank`'s comparison (``ww_ctc_score_trigger_bank_step``); :attr:`fired_slots` names
+    the target.  The stage's own bank then scores ``targets`` (default: ``target`` alone) in ``mode``; a ``bank=`` of the caller's
+    must have been created with targets, as many as there are thresholds."""
 
     def __init__(self, n_streams: int, engine=None, target: Sequence[int] = ctc.WAKEWORD, bank=None, pre_emphasis: float = 0.0,
-                 on_wake: Optional[Callable[[np.ndarray], None]] = None) -> None:
+                 on_wake: Optional[Callable[[np.ndarray], None]] = None, thresholds=None, targets=None, mode: str = "prefix") -> None:
         from . import _lib
         from .engine import CtcStreamBank
         self.S = int(n_streams)
+        self.thresholds = None
+        if thresholds is not None:
+            self._init_score_rule(engine, bank, pre_emphasis, on_wake, thresholds, targets if targets is not None else [tuple(target)], mode)
+            return
         t = np.asarray(target)
         if t.ndim != 1 or t.size < 1 or t.dtype.kind not in "iu" or t.min() < 0 or t.max() > 7:
             raise ValueError("target must be a non-empty sequence of labels 0..7")
@@ -354,6 +364,54 @@ class CtcWakewordBank:
         self._bound = None     # (the ContextBank, the addresses of its two flag arrays)
         self._scratch = None   # flag arrays for the sequence-of-contexts form
 
+    def _init_score_rule(self, engine, bank, pre_emphasis, on_wake, thresholds, targets, mode) -> None:
+        from . import _lib
+        from .engine import CtcStreamBank
+        thr = np.atleast_1d(np.asarray(thresholds, np.float64))
+        if thr.ndim != 1 or not np.all(np.isfinite(thr)):
+            raise ValueError("thresholds must be finite numbers, one per target")
+        if bank is None:
+            if engine is None:
+                raise ValueError("CtcWakewordBank needs engine (an Engine on a CTC-trained CRNN), or bank=: a CtcStreamBank")
+            if len(targets) != thr.size:
+                raise ValueError(f"CtcWakewordBank: {thr.size} thresholds for {len(targets)} targets")
+            bank = CtcStreamBank(engine, self.S, frontend_params(32767.0, True, pre_emphasis, 160, True), targets=targets, mode=mode)
+        else:
+            if getattr(bank, "S", self.S) != self.S:
+                raise ValueError(f"CtcWakewordBank: the bank has {bank.S} streams, the stage {self.S}")
+            if int(getattr(bank, "n_targets", 0)) != thr.size:
+                raise ValueError(f"CtcWakewordBank: {thr.size} thresholds, but the bank scores {getattr(bank, 'n_targets', 0)} targets "
+                                 "(CtcStreamBank(..., targets=))")
+        self._bank = bank
+        self.thresholds = np.ascontiguousarray(thr)
+        self._on_wake = on_wake
+        self._was_speech = np.zeros(self.S, np.uint8)
+        self._fired = np.zeros(self.S, np.int32)
+        self._fired_slot = np.zeros(self.S, np.int32)
+        self._fall = np.zeros(self.S, np.int32)
+        self._counts = np.zeros(2, np.int32)
+        self._n = np.zeros(self.S, np.int32)
+        self._lib = _lib.load()
+        self._bound = None
+        self._scratch = None
+
+    def _step_scores(self, contexts, frames):
+        from . import _lib
+        p_speech, p_active = _flag_addresses(self, contexts)
+        S = self.S
+        speech, active = (contexts.is_speech, contexts.is_active) if hasattr(contexts, "emit") else self._scratch[:2]
+        tick = self._bank.step(frames, speech, active)
+        n, scores = np.ascontiguousarray(tick.n, np.int32), np.ascontiguousarray(tick.scores, np.float32)
+        rc = self._lib.ww_ctc_score_trigger_bank_step(S, int(self.thresholds.size), p_speech, p_active, _lib.ptr(scores), _lib.ptr(n),
+                                                      _lib.ptr(self.thresholds), _lib.ptr(self._was_speech), _lib.ptr(self._fired),
+                                                      _lib.ptr(self._fired_slot), _lib.ptr(self._counts[0:1]), _lib.ptr(self._fall),
+                                                      _lib.ptr(self._counts[1:2]))
+        if rc:
+            raise ValueError("ww_ctc_score_trigger_bank_step refused its arguments")
+        if self._counts[1]:
+            self._bank.reset(self._fall[:self._counts[1]].copy())
+        return tick
+
     @property
     def n_post(self) -> np.ndarray:
         """Windows per stream delivered by the last tick (0, 1 or 2)."""
@@ -365,13 +423,23 @@ class CtcWakewordBank:
         return self._fired[:self._counts[0]].copy()
 
     @property
+    def fired_slots(self) -> np.ndarray:
+        """Score rule: for each of :attr:`fired_ids` the target whose threshold was exceeded (the greatest score among several)."""
+        if self.thresholds is None:
+            raise ValueError("fired_slots belongs to the score rule (thresholds=)")
+        return self._fired_slot[:self._counts[0]].copy()
+
+    @property
     def fall_ids(self) -> np.ndarray:
         """The streams whose VAD bit fell in the last tick (they were reset)."""
         return self._fall[:self._counts[1]].copy()
 
     def step(self, contexts, frames: np.ndarray):
-        p_speech, p_active = _flag_addresses(self, contexts)
-        tick = self._bank.step_ctc_trigger(frames, p_speech, p_active, self._p_target, int(self.target.size), self._p_state)
+        if self.thresholds is not None:
+            tick = self._step_scores(contexts, frames)
+        else:
+            p_speech, p_active = _flag_addresses(self, contexts)
+            tick = self._bank.step_ctc_trigger(frames, p_speech, p_active, self._p_target, int(self.target.size), self._p_state)
         self._n = tick.n
         nf = self._counts[0]
         if nf:
