@@ -423,6 +423,38 @@ int ww_ctc_slide_score(ww_ctx *ctx, const ww_model *model, const float *mel, int
                        const int32_t *target_lens, int32_t K, int32_t mode, float *score, int32_t max_labels, int32_t *labels,
                        int32_t *lengths, int64_t *n_windows);
 
+/* ---- CTC-trained CRNNs: WHERE in a window the target lies (Viterbi alignment) ---------------------------------------------------------
+ * The decode, the tick and the score say whether a window holds [HEY][SNIPS]; the stage behind the wake word (an activation timeout,
+ * a recogniser fed the audio after the word) needs where.  The most probable path through the target's CTC lattice - the max-product
+ * twin of the score's sum - and the steps at which it enters and leaves each label, to one conv step (80 ms at the standard
+ * geometry; wwhip.ctc.step_rows maps a step to mel rows).  The statement, its tie rules and its arithmetic: csrc/ctc_align.h
+ * (wwhip.ctc.align is the same in float64).  Arguments and limits are ww_ctc_score_*'s: y [T][L], targets [K][9], target_lens [K], mode
+ *   WW_CTC_SCORE_EXACT   the best path whose collapse IS the target; it ends at step T - 1
+ *   WW_CTC_SCORE_PREFIX  the best path up to the step t* at which it completes the target (what follows is free: the trigger's rule)
+ *   value [K][n] float32: the probability of that path (one float32 multiplication per step)
+ *   span  [K][n][WW_CTC_SCORE_MAX_TARGET][2] int8: {first step, last step} of label u on that path; in prefix mode the last label's
+ *     pair is {t*, t*}; rows u >= U are -1; value == 0 (T too short, a zero posterior on every path, underflow): every row is -1
+ * All K n values and all K n 18 span bytes are written.  On the device and on the host the same comparisons and multiplications in
+ * the same order: ww_ctc_align_dev gives the bits of ww_ctc_align_rows.  Against the float64 statement on the same float32
+ * posteriors the value is within (T - 1) 2^-24 relative (plus flushing under FLT_MIN), and the path is an optimal one up to twice that.
+ * WW_EINVAL before anything is written, the text naming the rule: ww_ctc_score_*'s rules, and a NULL value or span.  n = 0: WW_OK.
+ * ww_ctc_align_dev - ctc_align_kernel alone (csrc/ctc_align.hip) on any device posteriors [n][T][L], enqueued on the context's stream.
+ * ww_ctc_align_rows - host only, no context (its refusal's text: ww_last_error(NULL)).
+ * ww_ctc_align / _windows_dev / ww_ctc_slide_align - ww_ctc_score / _windows_dev / ww_ctc_slide_score with the align kernel in the
+ *   score kernel's place behind every chunk's model launch; labels / lengths are the optional decode, as there. */
+int ww_ctc_align_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, int32_t L, const int32_t *targets, const int32_t *target_lens,
+                     int32_t K, int32_t mode, float *d_value, int8_t *d_span);
+int ww_ctc_align_rows(const float *steps, int64_t n, int32_t T, int32_t L, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                      int32_t mode, float *value, int8_t *span);
+int ww_ctc_align(ww_ctx *ctx, const ww_model *model, const float *windows, int32_t n, const int32_t *targets, const int32_t *target_lens,
+                 int32_t K, int32_t mode, float *value, int8_t *span, int32_t max_labels, int32_t *labels, int32_t *lengths);
+int ww_ctc_align_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                             const int32_t *d_win_valid, int32_t n, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                             int32_t mode, float *d_value, int8_t *d_span, int32_t max_labels, int32_t *d_labels, int32_t *d_lengths);
+int ww_ctc_slide_align(ww_ctx *ctx, const ww_model *model, const float *mel, int64_t rows, int32_t hop, const int32_t *targets,
+                       const int32_t *target_lens, int32_t K, int32_t mode, float *value, int8_t *span, int32_t max_labels, int32_t *labels,
+                       int32_t *lengths, int64_t *n_windows);
+
 /* ww_forward_windows_dev over a model set: window w is evaluated by member win_model[w], all windows in ONE launch (K checkpoints
  * over the same mel - the loop over eval_models of wwdetect/wavenet/evaluate_wavenet.py - are K x n windows that name the same rows).
  * win_model is a HOST array: read and checked before the call returns (an id outside [0, n_models): WW_EINVAL, nothing is launched),
@@ -891,6 +923,14 @@ int ww_stream_step_ctc_score(ww_streams *st, const int16_t *frames, const uint8_
 int ww_ctc_score_trigger_bank_step(int32_t n_streams, int32_t K, const uint8_t *is_speech, uint8_t *is_active, const float *scores,
                                    const int32_t *n_post, const double *thresholds, uint8_t *was_speech, int32_t *fired_ids,
                                    int32_t *fired_slot, int32_t *n_fired, int32_t *fall_ids, int32_t *n_fall);
+/* ww_stream_step_ctc_align - ww_stream_step_ctc_score plus ONE ctc_align_kernel launch behind the score's, on the same posterior block:
+ *   align_value [S][2][K] float32 and align_span [S][2][K][WW_CTC_SCORE_MAX_TARGET][2] int8 beside the scores (ww_ctc_align_* above, the
+ *   bank's targets and mode), through a page-locked block the bank allocates on the first such call.  Entries at or past n_post[s] are
+ *   left as they were.  In every form of the bank a window's alignment is the bits ww_ctc_align_dev gives on the posteriors the same
+ *   tick returns in `steps`.  WW_EINVAL before any state moves: a bank without WW_STREAM_CTC_STEPS or without targets, a NULL output.
+ *   ww_stream_step_ctc and ww_stream_step_ctc_score keep their launches. */
+int ww_stream_step_ctc_align(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels,
+                             int32_t *lengths, float *steps, float *scores, float *align_value, int8_t *align_span, int32_t *n_post);
 /* Where a tick's time goes on the HOST side of ww_stream_step (the loop of spokestack/pipeline.py:25-28 is host-paced, so
  * BASELINE config 5's per-tick latency is this call): mean nanoseconds per phase over the ticks since the last reset -
  * [0] plan (control words and window descriptors of the tick), [1] the caller's frames into the page-locked block,

@@ -17,7 +17,13 @@ Usage: python tools/ctc_bench.py stream [rounds] [ticks] > profiles/ctc/stream_m
 targets) beside ``ctc_forward_windows_dev`` on 256 and 4,096 resident windows, the sides alternated as above, then the per-kernel
 split; and the S = 128 ``CtcStreamBank`` tick with targets beside the same bank without them (``want_steps`` on both sides: a
 scoring bank keeps its posteriors), host time per ``step``.
-Usage: python tools/ctc_bench.py score [rounds] [calls] [ticks] > profiles/ctc/score_measured.txt"""
+Usage: python tools/ctc_bench.py score [rounds] [calls] [ticks] > profiles/ctc/score_measured.txt
+
+``align``: what the Viterbi alignment costs.  ``ctc_align_windows_dev`` (front + CTC tail + ctc_align_kernel, K = 1 and K = 3) beside
+``ctc_score_windows_dev`` (the same model launches + ctc_score_kernel) and ``ctc_forward_windows_dev`` on 256 and 4,096 resident
+windows, the sides alternated, then the per-kernel split; and the S = 128 ``CtcStreamBank`` tick with scores and alignment beside the
+same bank with scores alone, host time per ``step``.
+Usage: python tools/ctc_bench.py align [rounds] [calls] [ticks] > profiles/ctc/align_measured.txt"""
 import os
 import sys
 
@@ -182,9 +188,81 @@ def score_mode(rounds: int, calls: int, ticks: int, S: int = 128) -> None:
     ctc.close()
 
 
+def align_mode(rounds: int, calls: int, ticks: int, S: int = 128) -> None:
+    import time
+    from wwhip.engine import CtcStreamBank
+    ctx = _lib.Context(0)
+    ctc = Engine("synthetic-ctc-4", ctx=ctx, bundle=ctc64.model(4))
+    one, three = [(1, 2)], [(1, 2), (0,), (1, 1)]
+    for n in (256, 4096):
+        wins = ctc64.G.windows(7, min(n, 512), 151, 40)
+        d_mel = torch.from_numpy(np.ascontiguousarray(wins).reshape(-1, 40)).cuda()
+        d_row = (torch.arange(n, dtype=torch.int64, device="cuda") % len(wins)) * 151
+        d_valid = torch.full((n,), 151, dtype=torch.int32, device="cuda")
+        d_lab = torch.empty((n, 2), dtype=torch.int32, device="cuda")
+        d_len = torch.empty(n, dtype=torch.int32, device="cuda")
+        d_score = torch.empty((3, n), dtype=torch.float32, device="cuda")
+        d_span = torch.empty((3, n, 9, 2), dtype=torch.int8, device="cuda")
+        torch.cuda.synchronize()
+        a = (d_mel.data_ptr(), d_mel.shape[0], d_row.data_ptr(), d_valid.data_ptr(), n)
+        sides = {
+            "ctc_forward (labels)": lambda: ctc.ctc_forward_windows_dev(*a, 2, d_lab.data_ptr(), d_len.data_ptr()),
+            "ctc_score K=1 exact": lambda: ctc.ctc_score_windows_dev(*a, one, "exact", d_score.data_ptr()),
+            "ctc_align K=1 exact": lambda: ctc.ctc_align_windows_dev(*a, one, "exact", d_score.data_ptr(), d_span.data_ptr()),
+            "ctc_score K=3 prefix": lambda: ctc.ctc_score_windows_dev(*a, three, "prefix", d_score.data_ptr()),
+            "ctc_align K=3 prefix": lambda: ctc.ctc_align_windows_dev(*a, three, "prefix", d_score.data_ptr(), d_span.data_ptr()),
+        }
+        for fn in sides.values():
+            for _ in range(5):
+                fn()
+        ctx.synchronize()
+        times = {k: [] for k in sides}
+        for _ in range(rounds):
+            for k, fn in sides.items():
+                ctx.timer_start()
+                for _ in range(calls):
+                    fn()
+                times[k].append(ctx.timer_stop() / calls * 1e3)
+        for k, t in times.items():
+            print(f"{n} windows, {k}: p50 {np.percentile(t, 50):.1f} us, p90 {np.percentile(t, 90):.1f} us per call "
+                  f"({rounds} rounds of {calls} calls, sides alternated)")
+        for k, fn in sides.items():
+            ctx.profile(True)
+            for _ in range(calls):
+                fn()
+            p = ctx.profile_read()
+            ctx.profile(False)
+            print(f"{n} windows, {k}, per kernel (us):", {name: round(v["total_ms"] / v["calls"] * 1e3, 1) for name, v in p.items()})
+    banks = {"steps + scores K=1, one launch": CtcStreamBank(ctc, S, want_steps=True, targets=one),
+             "steps + scores + alignment K=1, one launch": CtcStreamBank(ctc, S, want_steps=True, targets=one, align=True),
+             "steps + scores K=3 prefix, one launch": CtcStreamBank(ctc, S, want_steps=True, targets=three, mode="prefix"),
+             "steps + scores + alignment K=3 prefix, one launch": CtcStreamBank(ctc, S, want_steps=True, targets=three, mode="prefix", align=True)}
+    rng = np.random.default_rng(3)
+    frames = np.clip(rng.normal(0, 2500, (ticks, S, 320)), -32768, 32767).astype(np.int16)
+    speech = np.ones(S, np.uint8)
+    for b in banks.values():   # past the 151-row fill, every later tick two windows per stream
+        for t in range(100):
+            b.step(frames[t % ticks], speech)
+    times = {k: [] for k in banks}
+    for _ in range(rounds):
+        for k, b in banks.items():
+            for t in range(ticks):
+                t0 = time.perf_counter()
+                b.step(frames[t], speech)
+                times[k].append((time.perf_counter() - t0) * 1e6)
+    print(f"S = {S} streams, L = 4, 2 windows per stream and tick; {rounds} rounds of {ticks} ticks per side, sides alternated; host time per step()")
+    for k, t in times.items():
+        print(f"{k}: p50 {np.percentile(t, 50):.1f} us, p99 {np.percentile(t, 99):.1f} us, min {min(t):.1f} us per tick")
+    for b in banks.values():
+        b.close()
+    ctc.close()
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
-    if args and args[0] == "score":
+    if args and args[0] == "align":
+        align_mode(int(args[1]) if len(args) > 1 else 9, int(args[2]) if len(args) > 2 else 200, int(args[3]) if len(args) > 3 else 300)
+    elif args and args[0] == "score":
         score_mode(int(args[1]) if len(args) > 1 else 9, int(args[2]) if len(args) > 2 else 200, int(args[3]) if len(args) > 3 else 300)
     elif args and args[0] == "stream":
         stream_mode(int(args[1]) if len(args) > 1 else 7, int(args[2]) if len(args) > 2 else 300)

@@ -56,6 +56,8 @@ def parse_args():
                    help="also score every clip with the CTC forward algorithm (P(decode == [HEY][SNIPS])) and print the FAR/FRR sweep over N "
                         "thresholds evenly spaced in (0, 1)")
     p.add_argument("--score_mode", type=str, default="exact", choices=("exact", "prefix"), help="exact: the decode IS the target; prefix: starts with it")
+    p.add_argument("--align", action="store_true",
+                   help="also print, per clip, where the best [HEY][SNIPS] path (Viterbi, --score_mode) lies: each label's seconds into the clip")
     return p.parse_args()
 
 
@@ -63,7 +65,7 @@ def main(args):
     feats, labels, keys = read_records(os.path.join(args.data_dir, args.testset))
     eng = Engine(args.model_dir, bundle=ctc_bundle(args.model_dir, args.ctc_head, args.keras_kernel))
     thr = np.linspace(0.0, 1.0, args.thresholds + 2)[1:-1] if args.thresholds > 0 else None
-    stats = evaluate_ctc(eng, feats, labels, thresholds=thr, mode=args.score_mode)
+    stats = evaluate_ctc(eng, feats, labels, thresholds=thr, mode=args.score_mode, align=args.align)
     eng.close()
     print("False accept files:", [k for k, p, t in zip(keys, stats["predicted"], labels) if p and not t])
     print("False reject files:", [k for k, p, t in zip(keys, stats["predicted"], labels) if t and not p])
@@ -76,6 +78,10 @@ def main(args):
         print("threshold  FRR  FA/h  FA")
         for t, frr, fa, cnt in zip(stats["thresholds"], stats["frr"], stats["fa_per_hour"], stats["fa_count"]):
             print(f"{t:.4f}  {frr:.4f}  {fa:.3f}  {int(cnt)}")
+    if args.align:
+        print(f"clip  path probability ({args.score_mode})  [HEY] s  [SNIPS] s")
+        for key, val, sec in zip(keys, stats["align_value"], stats["span_seconds"]):
+            print(f"{key}  {val:.3g}  " + "  ".join("-" if np.isnan(a) else f"{a:.2f}-{b:.2f}" for a, b in sec))
     return stats
 
 

@@ -1,5 +1,6 @@
 // C ABI of libwwhip.so: context, model upload, host/device entry points (see include/wwhip.h).
 #include "common.h"
+#include "ctc_align.h"
 #include "ctc_score.h"
 #include "model_pack.h"
 #include "model_set.h"
@@ -816,10 +817,10 @@ static size_t ctc_score_workspace(const ww_model *m, int64_t nw) {
 }
 
 // ctc_chunks with the posteriors kept in the workspace and ctc_score_kernel behind every chunk's model launch: d_score [K][nw]
-// (d_labels / d_lengths: nullptr, or the decode beside the score).  ws: ctc_score_workspace(m, nw) bytes inside the device arena.
+// (d_labels / d_lengths: nullptr, or the decode beside the score; d_score may be nullptr where d_value / d_span are given).  ws: ctc_score_workspace(m, nw) bytes inside the device arena.
 static int ctc_score_chunks(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_row, const int32_t *d_valid,
                             int hop, int valid_const, int64_t nw, void *ws, const ww_ctc_score_targets &tg, float *d_score, int max_labels,
-                            int32_t *d_labels, int32_t *d_lengths) {
+                            int32_t *d_labels, int32_t *d_lengths, float *d_value = nullptr, int8_t *d_span = nullptr) {
   const int chunk = chunk_of(nw), L = m->info.n_out;
   ww_bump bump(ws, ctc_score_workspace(m, nw));
   float *d_steps = bump.take<float>((size_t)chunk * WW_CTC_STEPS * L);
@@ -833,29 +834,39 @@ static int ctc_score_chunks(ww_ctx *ctx, const ww_model *m, const float *d_mel, 
                                        hop, valid_const, n, mws, cap, d_labels ? max_labels : 1, d_labels ? d_labels + (size_t)w0 * max_labels : own_lab,
                                        d_labels ? d_lengths + w0 : own_len, d_steps, nullptr))
       return rc;
-    if (int rc = ww_k_ctc_score(ctx, d_steps, n, WW_CTC_STEPS, L, tg, d_score + w0, nw, 1)) return rc;
+    if (d_score)
+      if (int rc = ww_k_ctc_score(ctx, d_steps, n, WW_CTC_STEPS, L, tg, d_score + w0, nw, 1)) return rc;
+    // the align forms (ww_ctc_align_*): ctc_align_kernel in the score kernel's place, d_value [K][nw] and d_span [K][nw][9][2]
+    if (d_value)
+      if (int rc = ww_k_ctc_align(ctx, d_steps, n, WW_CTC_STEPS, L, tg, d_value + w0, d_span + w0 * (2 * WW_CTC_SCORE_MAX_TARGET), nw, 1)) return rc;
   }
   return WW_OK;
 }
 
 // the host forms: the sequence in, the K planes (and the decode, where asked for) out, staged like ctc_host's
+// (score, or value and span: the score forms and the align forms)
 static int ctc_score_host(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t rows, int hop, int64_t nw, const ww_ctc_score_targets &tg,
-                          float *score, int max_labels, int32_t *labels, int32_t *lengths) {
+                          float *score, int max_labels, int32_t *labels, int32_t *lengths, float *value = nullptr, int8_t *span = nullptr) {
   const int T = m->info.window, F = m->info.n_mel;
   const size_t n_score = (size_t)nw * tg.K, n_lab = labels ? (size_t)nw * max_labels : 0;
   WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
-  const size_t b_io = ww_bump::need((size_t)rows * F, 4) + ww_bump::need(n_score, 4) + (labels ? ww_bump::need(n_lab, 4) + ww_bump::need((size_t)nw, 4) : 0);
+  const size_t n_span = value ? n_score * 2 * WW_CTC_SCORE_MAX_TARGET : 0;
+  const size_t b_io = ww_bump::need((size_t)rows * F, 4) + ww_bump::need(n_score, 4) + ww_bump::need(n_span, 1) + (labels ? ww_bump::need(n_lab, 4) + ww_bump::need((size_t)nw, 4) : 0);
   const size_t b_ws = ctc_score_workspace(m, nw);
   ww_staged_io io(ctx);
   int rc = io.init(b_io, b_ws + 1024, nw <= 64);
   if (rc) return rc;
   const float *d_mel = io.in(mel, (size_t)rows * F);
-  float *d_score = io.out<float>(n_score);
+  float *d_score = io.out<float>(n_score);  // (the align forms: the values)
+  int8_t *d_span = value ? io.out<int8_t>(n_span) : nullptr;
   int32_t *d_lab = labels ? io.out<int32_t>(n_lab) : nullptr, *d_len = labels ? io.out<int32_t>((size_t)nw) : nullptr;
   void *ws = io.scratch(b_ws);
   if (io.rc) return io.rc;
-  if ((rc = ctc_score_chunks(ctx, m, d_mel, rows, nullptr, nullptr, hop, T, nw, ws, tg, d_score, max_labels, d_lab, d_len))) return rc;
-  if ((rc = io.fetch(score, d_score, n_score * 4))) return rc;
+  if ((rc = ctc_score_chunks(ctx, m, d_mel, rows, nullptr, nullptr, hop, T, nw, ws, tg, value ? nullptr : d_score, max_labels, d_lab, d_len,
+                             value ? d_score : nullptr, d_span)))
+    return rc;
+  if ((rc = io.fetch(value ? value : score, d_score, n_score * 4))) return rc;
+  if (value && (rc = io.fetch(span, d_span, n_span))) return rc;
   if (labels && ((rc = io.fetch(labels, d_lab, n_lab * 4)) || (rc = io.fetch(lengths, d_len, (size_t)nw * 4)))) return rc;
   return io.finish();
 }
@@ -1049,6 +1060,89 @@ int ww_ctc_score_windows_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel,
   WW_ON_DEVICE(ctx, dev);
   if (int rc = ww_ensure(ctx, ctx->dev, ctc_score_workspace(m, n) + 1024, false)) return rc;
   return ctc_score_chunks(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, n, ctx->dev.ptr, tg, d_score, max_labels, d_labels, d_lengths);
+  WW_GUARD_END(ctx)
+}
+
+// ---- the Viterbi alignment (include/wwhip.h: ww_ctc_align_*; csrc/ctc_align.h): the score family's forms, one to one -------------
+int ww_ctc_align_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, int32_t L, const int32_t *targets, const int32_t *target_lens,
+                     int32_t K, int32_t mode, float *d_value, int8_t *d_span) {
+  WW_GUARD_BEGIN
+  if (!ctx) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  ww_ctc_score_targets tg;
+  if (int rc = ctc_score_targets_of(ctx, T, L, targets, target_lens, K, mode, "ww_ctc_align_dev", tg)) return rc;
+  if (n < 0 || n > 0x7fffffff) return ww_fail(ctx, WW_EINVAL, "ww_ctc_align_dev: sequence count out of range");
+  if (!d_value || !d_span) return ww_fail(ctx, WW_EINVAL, "ww_ctc_align_dev: value / span are NULL");
+  if (n == 0) return WW_OK;
+  if (!d_steps) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  WW_ON_DEVICE(ctx, dev);
+  return ww_k_ctc_align(ctx, d_steps, n, T, L, tg, d_value, d_span, n, 1);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_align_rows(const float *steps, int64_t n, int32_t T, int32_t L, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                      int32_t mode, float *value, int8_t *span) {
+  WW_GUARD_BEGIN
+  char why[200];
+  if (!ww_ctc_score_args_ok(T, L, targets, target_lens, K, mode, why, sizeof why)) return ww_fail(nullptr, WW_EINVAL, "ww_ctc_align_rows: %s", why);
+  if (n < 0) return ww_fail(nullptr, WW_EINVAL, "ww_ctc_align_rows: negative sequence count");
+  if (!value || !span) return ww_fail(nullptr, WW_EINVAL, "ww_ctc_align_rows: value / span are NULL");
+  if (n == 0) return WW_OK;
+  if (!steps) return ww_fail(nullptr, WW_EINVAL, "NULL argument");
+  for (int k = 0; k < K; ++k)
+    for (int64_t i = 0; i < n; ++i)
+      ww_ctc_align_row(steps + (size_t)i * T * L, T, L, L, targets + k * WW_CTC_SCORE_MAX_TARGET, target_lens[k], mode, value + (size_t)k * n + i,
+                       span + ((size_t)k * n + i) * (2 * WW_CTC_SCORE_MAX_TARGET));
+  return WW_OK;
+  WW_GUARD_END(nullptr)
+}
+
+int ww_ctc_align(ww_ctx *ctx, const ww_model *m, const float *windows, int32_t n, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                 int32_t mode, float *value, int8_t *span, int32_t max_labels, int32_t *labels, int32_t *lengths) {
+  WW_GUARD_BEGIN
+  ww_ctc_score_targets tg;
+  if (int rc = ctc_score_check(ctx, m, targets, target_lens, K, mode, value, max_labels, labels, lengths, "ww_ctc_align", tg)) return rc;
+  if (!span) return ww_fail(ctx, WW_EINVAL, "ww_ctc_align: span is NULL");
+  if (n < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
+  if (n == 0) return WW_OK;
+  if (!windows) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
+  return ctc_score_host(ctx, m, windows, (int64_t)n * m->info.window, m->info.window, n, tg, nullptr, max_labels, labels, lengths, value, span);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_slide_align(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t rows, int32_t hop, const int32_t *targets,
+                       const int32_t *target_lens, int32_t K, int32_t mode, float *value, int8_t *span, int32_t max_labels, int32_t *labels,
+                       int32_t *lengths, int64_t *n_windows) {
+  WW_GUARD_BEGIN
+  ww_ctc_score_targets tg;
+  if (int rc = ctc_score_check(ctx, m, targets, target_lens, K, mode, value, max_labels, labels, lengths, "ww_ctc_slide_align", tg)) return rc;
+  if (!span) return ww_fail(ctx, WW_EINVAL, "ww_ctc_slide_align: span is NULL");
+  if (!n_windows) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (hop <= 0) return ww_fail(ctx, WW_EINVAL, "hop must be positive");
+  if (rows < 0) return ww_fail(ctx, WW_EINVAL, "negative row count");
+  const int T = m->info.window;
+  const int64_t nw = rows >= T ? (rows - T) / hop + 1 : 0;
+  if (nw > 0 && !mel) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
+  *n_windows = nw;
+  if (nw == 0) return WW_OK;
+  return ctc_score_host(ctx, m, mel, rows, hop, nw, tg, nullptr, max_labels, labels, lengths, value, span);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_align_windows_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                             const int32_t *d_win_valid, int32_t n, const int32_t *targets, const int32_t *target_lens, int32_t K, int32_t mode,
+                             float *d_value, int8_t *d_span, int32_t max_labels, int32_t *d_labels, int32_t *d_lengths) {
+  WW_GUARD_BEGIN
+  ww_ctc_score_targets tg;
+  if (int rc = ctc_score_check(ctx, m, targets, target_lens, K, mode, d_value, max_labels, d_labels, d_lengths, "ww_ctc_align_windows_dev", tg)) return rc;
+  if (!d_span) return ww_fail(ctx, WW_EINVAL, "ww_ctc_align_windows_dev: span is NULL");
+  if (n < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
+  if (n == 0) return WW_OK;
+  if (!d_mel) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (!d_win_row || !d_win_valid) return ww_fail(ctx, WW_EINVAL, "window descriptors are NULL");
+  WW_ON_DEVICE(ctx, dev);
+  if (int rc = ww_ensure(ctx, ctx->dev, ctc_score_workspace(m, n) + 1024, false)) return rc;
+  return ctc_score_chunks(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, n, ctx->dev.ptr, tg, nullptr, max_labels, d_labels, d_lengths, d_value,
+                          d_span);
   WW_GUARD_END(ctx)
 }
 

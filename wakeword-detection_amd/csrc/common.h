@@ -289,6 +289,10 @@ struct ww_ctc_score_targets {
 };
 int ww_k_ctc_score(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, const ww_ctc_score_targets &tg, float *d_score, int64_t stride_k,
                    int64_t stride_i);
+// ctc_align_kernel (ctc_align.hip; the statement: ctc_align.h): the Viterbi alignment of the same K targets over the same posteriors.
+// At o = k * stride_k + i * stride_i: d_value[o] and the 18 bytes d_span[18 o ..] ([WW_CTC_SCORE_MAX_TARGET][2] int8).
+int ww_k_ctc_align(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, const ww_ctc_score_targets &tg, float *d_value, int8_t *d_span,
+                   int64_t stride_k, int64_t stride_i);
 // A CTC stream bank's incremental ticks (crnn_stream_kernel<FE, false, false, CTC>): ww_k_crnn_tick's and ww_k_crnn_stream_forward's
 // arguments; a window's decode goes out as one 32-bit word (stream_ctc.h) - the value half of its tag where tag slots are given, else
 // row w of d_words -, and with d_steps (page-locked, [windows of the launch][19][L]; nullptr: off) its posteriors beside it

@@ -29,6 +29,7 @@
 #include "stream_all.h"
 #include "stream_ctc.h"
 #include "ctc_score.h"
+#include "ctc_align.h"
 #include "stream_fe.h"
 
 #include <algorithm>
@@ -128,6 +129,12 @@ struct ww_streams {
   bool score_set = false;
   ww_ctc_score_targets score_tg;
   float *h_score = nullptr, *h_score_dev = nullptr;
+  // ww_stream_step_ctc_align: ctc_align_kernel over the same block with the same targets; one page-locked block, allocated by the
+  // first such call: the values [2 S][WW_CTC_SCORE_MAX_TARGETS] float32, then the spans [2 S][WW_CTC_SCORE_MAX_TARGETS][9][2] int8
+  // (a tick uses the first 2 S K of each)
+  float *h_align = nullptr, *h_align_dev = nullptr;
+  int8_t *h_span() const { return (int8_t *)(h_align + (size_t)2 * S * WW_CTC_SCORE_MAX_TARGETS); }
+  int8_t *h_span_dev() const { return (int8_t *)(h_align_dev + (size_t)2 * S * WW_CTC_SCORE_MAX_TARGETS); }
   // the reason this bank refuses `call` (CTC or not: here; every-member or not: stream_all.h, sa_check_call), where ww_last_error
   // finds it; WW_OK: it does not
   int check_call(const char *call, bool wants_every, bool wants_ctc = false) const {
@@ -425,7 +432,7 @@ int ww_stream_destroy(ww_streams *st) {
   void *dev[] = {st->ring, st->hist, st->prev, st->d_pack, st->ws, st->gxc, st->gx_zero, st->wstate, st->zring, st->zpos, st->d_stream_model};
   for (void *p : dev)
     if (p) hipFree(p);
-  void *host[] = {st->h_pack, st->h_out, st->h_tag, st->h_steps, st->h_lab, st->h_score};
+  void *host[] = {st->h_pack, st->h_out, st->h_tag, st->h_steps, st->h_lab, st->h_score, st->h_align};
   for (void *p : host)
     if (p) hipHostFree(p);
   ww_k_rates_destroy(st->rates);
@@ -905,6 +912,8 @@ struct st_ctc_out {
   int32_t *labels, *lengths;  // [S][2][max_labels], [S][2]
   float *steps;               // [S][2][19][L] or nullptr
   float *scores;              // [S][2][K] or nullptr (ww_stream_step_ctc_score: the bank's targets are set)
+  float *align_value = nullptr;  // [S][2][K] and [S][2][K][9][2], or nullptr (ww_stream_step_ctc_align)
+  int8_t *align_span = nullptr;
 };
 
 // The one tick of every bank.  co (a CTC bank, stream_ctc.h): the same bookkeeping, frames, front end and wait; the model launches
@@ -1043,6 +1052,11 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
   if (co && co->scores && nw)
     if (int rc = ww_k_ctc_score(ctx, st->h_steps_dev, tk.form == SA_TABLE ? nw : 2 * S, WW_SC_STEPS, st->NO, st->score_tg, st->h_score_dev, 1, st->score_tg.K))
       return rc;
+  // ww_stream_step_ctc_align: and the alignment of the same slots, one launch more
+  if (co && co->align_value && nw)
+    if (int rc = ww_k_ctc_align(ctx, st->h_steps_dev, tk.form == SA_TABLE ? nw : 2 * S, WW_SC_STEPS, st->NO, st->score_tg, st->h_align_dev,
+                                st->h_span_dev(), 1, st->score_tg.K))
+      return rc;
   // (include/wwhip.h: phase [3] is 0 where a tick is one launch - the one-launch forms, and a two-launch bank's tick without a window:
   // no clock read of its own, which on a tick's first pass through this code measured the branches above, not a launch)
   tl[4] = second ? st_now_ns() : tl[3];
@@ -1075,6 +1089,16 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
       for (int s = 0; s < S; ++s)
         for (int k = 0; k < n_post[s]; ++k, ++w)
           memcpy(co->scores + ((size_t)s * 2 + k) * row, st->h_score + (size_t)(table ? w : 2 * s + k) * row, row * sizeof(float));
+    }
+    if (co->align_value) {
+      const size_t row = (size_t)st->score_tg.K, srow = row * 2 * WW_CTC_SCORE_MAX_TARGET;
+      int w = 0;
+      for (int s = 0; s < S; ++s)
+        for (int k = 0; k < n_post[s]; ++k, ++w) {
+          const size_t slot = (size_t)(table ? w : 2 * s + k);
+          memcpy(co->align_value + ((size_t)s * 2 + k) * row, st->h_align + slot * row, row * sizeof(float));
+          memcpy(co->align_span + ((size_t)s * 2 + k) * srow, st->h_span() + slot * srow, srow);
+        }
     }
   } else
   // post[s][slot][k] from where it arrived (stream_all.h): a tag's low word, or the posterior column of a row of h_out
@@ -1515,7 +1539,8 @@ int ww_stream_timeline(ww_streams *st, double *mean_ns, int64_t *ticks, int32_t 
 // ---- a CTC stream bank (include/wwhip.h; stream_ctc.h) ----------------------------------------------------------------------------------
 // ww_stream_step_ctc's refusals - all before any state moves -, then the one tick
 static int stream_step_ctc_entry(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels,
-                                 int32_t *lengths, float *steps, int32_t *n_post, const char *call, float *scores = nullptr) {
+                                 int32_t *lengths, float *steps, int32_t *n_post, const char *call, float *scores = nullptr,
+                                 float *align_value = nullptr, int8_t *align_span = nullptr) {
   ww_ctx *ctx = st->ctx;
   if (int rc = st->check_call(call, false, true)) return rc;
   if (int rc = st->check_sound()) return rc;
@@ -1523,7 +1548,7 @@ static int stream_step_ctc_entry(ww_streams *st, const int16_t *frames, const ui
     return ww_fail(ctx, WW_EINVAL, "%s: max_labels %d: a streamed window carries 1..%d labels", call, (int)max_labels, WW_STREAM_CTC_MAX_LABELS);
   if (!labels || !lengths) return ww_fail(ctx, WW_EINVAL, "%s: NULL argument", call);
   if (steps && !st->ctc_steps) return ww_fail(ctx, WW_EINVAL, "%s: posteriors are returned by a bank created with WW_STREAM_CTC_STEPS", call);
-  const st_ctc_out co = {max_labels, labels, lengths, steps, scores};
+  const st_ctc_out co = {max_labels, labels, lengths, steps, scores, align_value, align_span};
   return stream_step_entry(st, frames, is_speech, nullptr, n_post, call, false, &co);
 }
 
@@ -1588,6 +1613,33 @@ int ww_stream_step_ctc_score(ww_streams *st, const int16_t *frames, const uint8_
   if (!st->score_set) return ww_fail(st->ctx, WW_EINVAL, "%s: the bank has no targets (ww_stream_ctc_set_targets)", call);
   if (!scores) return ww_fail(st->ctx, WW_EINVAL, "%s: NULL argument", call);
   return stream_step_ctc_entry(st, frames, is_speech, max_labels, labels, lengths, steps, n_post, call, scores);
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+int ww_stream_step_ctc_align(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels,
+                             int32_t *lengths, float *steps, float *scores, float *align_value, int8_t *align_span, int32_t *n_post) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  const char *call = "ww_stream_step_ctc_align";
+  ww_ctx *ctx = st->ctx;
+  if (int rc = st->check_call(call, false, true)) return rc;
+  if (!st->ctc_steps) return ww_fail(ctx, WW_EINVAL, "%s: the alignment is computed from a tick's posteriors: the bank must be created with WW_STREAM_CTC_STEPS", call);
+  if (!st->score_set) return ww_fail(ctx, WW_EINVAL, "%s: the bank has no targets (ww_stream_ctc_set_targets)", call);
+  if (!scores || !align_value || !align_span) return ww_fail(ctx, WW_EINVAL, "%s: NULL argument", call);
+  if (!st->h_align) {
+    WW_ON_DEVICE(ctx, dev_scope);
+    const size_t slots = (size_t)2 * st->S * WW_CTC_SCORE_MAX_TARGETS;
+    if (hipHostMalloc((void **)&st->h_align, slots * (4 + 2 * WW_CTC_SCORE_MAX_TARGET)) != hipSuccess) {
+      st->h_align = nullptr;
+      return ww_fail(ctx, WW_ENOMEM, "%s: cannot allocate the alignment block of %d streams", call, st->S);
+    }
+    if (hipHostGetDevicePointer((void **)&st->h_align_dev, st->h_align, 0) != hipSuccess) {
+      hipHostFree(st->h_align);
+      st->h_align = nullptr;
+      return ww_fail(ctx, WW_EHIP, "%s: the alignment block is not visible to the device", call);
+    }
+  }
+  return stream_step_ctc_entry(st, frames, is_speech, max_labels, labels, lengths, steps, n_post, call, scores, align_value, align_span);
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 

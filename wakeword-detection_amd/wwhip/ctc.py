@@ -13,6 +13,10 @@ the posteriors themselves.
 ``score`` is the forward algorithm over the same posteriors: the probability that a window's label sequence collapses to a target -
 what ``K.ctc_batch_cost`` (``wwdetect/CRNN/train.py:184-200``) is minus the logarithm of -, the number a threshold can be put on.
 ``csrc/ctc_score.h`` states it; the function here is that statement in float64.
+
+``align`` is the max-product twin: the most probable path through the target's lattice and the steps at which it enters and leaves
+each label - where in the window the wake word lies, to one conv step (``csrc/ctc_align.h``; ``step_rows`` / ``span_rows`` /
+``span_seconds`` turn steps into mel rows and time).
 """
 from __future__ import annotations
 
@@ -143,6 +147,144 @@ def score_rows(steps, targets, mode="exact") -> np.ndarray:
     out = np.empty((len(lens), n), np.float32)
     _lib.raise_for(_lib.load().ww_ctc_score_rows(_lib.ptr(y), n, T, L, _lib.ptr(table), _lib.ptr(lens), len(lens), score_mode(mode),
                                                  _lib.ptr(out)), None)
+    return out
+
+
+class CtcAlignment(NamedTuple):
+    """``value [K, n]``: the probability of the best path of target ``k`` over window ``i`` (0: there is none);
+    ``span [K, n, U_max, 2]`` int32: the first and the last step at which that path is on label ``u`` (-1: no such label, or no
+    path); in prefix mode the last label's pair is ``{t*, t*}``, the step that completes the target.  ``paths`` (``wwhip.ctc.align``
+    only): ``paths[k][i]`` the path itself, a class per step - ``T`` steps in exact mode, ``t* + 1`` in prefix mode - or ``None``."""
+    value: np.ndarray
+    span: np.ndarray
+    paths: Optional[list] = None
+
+
+def align(steps, targets, mode="exact") -> CtcAlignment:
+    """``csrc/ctc_align.h`` in float64: ``steps [n, T, L]`` (or ``[T, L]``), ``targets`` a list of label tuples.
+
+    The lattice is :func:`score`'s with max in the place of the sum: ``v_0(0) = y_0[blank]``, ``v_0(1) = y_0[c_0]``; for ``t >= 1``
+    the candidates ``v(s)`` (shift 0), ``v(s - 1)`` (shift 1), ``v(s - 2)`` (shift 2, where ``skip(s)``), the best being the first
+    of the largest, and ``v_t(s) = best * y_t[cls(s)]``.  Exact: the path ends at ``T - 1`` in state ``2U - 1``, or ``2U`` if that is
+    strictly larger.  Prefix: ``q_t = max(v_{t-1}(2U - 2), skip(2U - 1) ? v_{t-1}(2U - 3)) * y_t[c_{U-1}]``,
+    ``q_0 = (U == 1 ? y_0[c_0] : 0)``; the path enters state ``2U - 1`` at the earliest step ``t*`` of the largest ``q_t`` and ends
+    there."""
+    y = np.asarray(steps, np.float64)
+    if y.ndim == 2:
+        y = y[None]
+    if y.ndim != 3 or y.shape[1] < 1 or y.shape[2] < 2:
+        raise ValueError(f"steps must be [n, T >= 1, L >= 2], got {y.shape}")
+    n, T, L = y.shape
+    table, lens = pack_targets(targets, L)
+    prefix = score_mode(mode) == SCORE_MODES["prefix"]
+    K, umax = len(lens), int(lens.max())
+    value, span = np.zeros((K, n), np.float64), np.full((K, n, umax, 2), -1, np.int32)
+    paths = [[None] * n for _ in range(K)]
+    for k, U in enumerate(lens):
+        c = table[k, :U]
+        S = 2 * U + 1
+        cls = [L - 1 if s % 2 == 0 else int(c[(s - 1) // 2]) for s in range(S)]
+        skip = [s % 2 == 1 and s >= 3 and c[(s - 1) // 2] != c[(s - 3) // 2] for s in range(S)]
+        for i in range(n):
+            v = [0.0] * S
+            v[0], v[1] = y[i, 0, L - 1], y[i, 0, c[0]]
+            bp = np.zeros((T, S), np.int64)
+            Q, t_star, q_shift = (y[i, 0, c[0]] if U == 1 else 0.0), 0, 0
+            for t in range(1, T):
+                if prefix:
+                    m, sh = v[S - 3], 1
+                    if skip[S - 2] and v[S - 4] > m:
+                        m, sh = v[S - 4], 2
+                    q = m * y[i, t, c[U - 1]]
+                    if q > Q:
+                        Q, t_star, q_shift = q, t, sh
+                nv = [0.0] * S
+                for s in range(S):
+                    best, sh = v[s], 0
+                    if s >= 1 and v[s - 1] > best:
+                        best, sh = v[s - 1], 1
+                    if skip[s] and v[s - 2] > best:
+                        best, sh = v[s - 2], 2
+                    bp[t, s] = sh
+                    nv[s] = best * y[i, t, cls[s]]
+                v = nv
+            if prefix:
+                value[k, i] = Q
+                if Q == 0.0:
+                    continue
+                states = [S - 2]
+                s, t = S - 2 - q_shift, t_star - 1
+            else:
+                s = S - 1 if v[S - 1] > v[S - 2] else S - 2
+                value[k, i] = v[s]
+                if v[s] == 0.0:
+                    continue
+                states, t = [], T - 1
+            while t >= 0:
+                states.append(s)
+                if t >= 1:
+                    s -= int(bp[t, s])
+                t -= 1
+            states.reverse()
+            paths[k][i] = np.array([cls[s] for s in states], np.int32)
+            for t, s in enumerate(states):
+                if s % 2:
+                    u = (s - 1) // 2
+                    if span[k, i, u, 0] < 0:
+                        span[k, i, u, 0] = t
+                    span[k, i, u, 1] = t
+    return CtcAlignment(value, span, paths)
+
+
+def align_rows(steps, targets, mode="exact") -> CtcAlignment:
+    """``csrc/ctc_align.h``'s float32 function over host arrays (``ww_ctc_align_rows``; no GPU): ``value [K, n]`` float32 and
+    ``span [K, n, U_max, 2]`` int32 - the bits the device kernel is held to."""
+    from . import _lib
+    y = np.ascontiguousarray(steps, np.float32)
+    if y.ndim == 2:
+        y = y[None]
+    if y.ndim != 3:
+        raise ValueError(f"steps must be [n, T, L], got {y.shape}")
+    n, T, L = y.shape
+    table, lens = pack_targets(targets, L)
+    value, span = np.empty((len(lens), n), np.float32), np.empty((len(lens), n, SCORE_MAX_TARGET, 2), np.int8)
+    _lib.raise_for(_lib.load().ww_ctc_align_rows(_lib.ptr(y), n, T, L, _lib.ptr(table), _lib.ptr(lens), len(lens), score_mode(mode),
+                                                 _lib.ptr(value), _lib.ptr(span)), None)
+    return CtcAlignment(value, span[:, :, :int(lens.max())].astype(np.int32))
+
+
+# the conv front of the standard geometry (a 151-row window -> 19 steps): kernel 20 rows, stride 8, 6 rows of padding in front
+CONV_KT, CONV_ST, CONV_PT, WINDOW_ROWS = 20, 8, 6, 151
+ROW_SECONDS = 0.01  # a mel row every 10 ms
+
+
+def step_rows(t) -> Tuple[np.ndarray, np.ndarray]:
+    """The mel rows of a window that conv step ``t`` reads at the standard geometry: ``(first, last)`` =
+    ``[8 t - 6, 8 t + 13]`` clipped to ``[0, 150]`` (scalars or arrays)."""
+    t = np.asarray(t)
+    first, last = CONV_ST * t - CONV_PT, CONV_ST * t - CONV_PT + CONV_KT - 1
+    return np.clip(first, 0, WINDOW_ROWS - 1), np.clip(last, 0, WINDOW_ROWS - 1)
+
+
+def span_rows(span, window_row0=0) -> np.ndarray:
+    """``span [..., 2]`` (first step, last step; -1: none) of windows that start at row ``window_row0`` (a number, or an array that
+    broadcasts against ``span[..., 0]``) -> ``[..., 2]`` int64: the first row the first step reads and the last row the last step
+    reads, counted on the sequence's rows; -1 where the span is -1."""
+    sp = np.asarray(span).astype(np.int64)
+    if sp.ndim < 1 or sp.shape[-1] != 2:
+        raise ValueError(f"span must be [..., 2], got {sp.shape}")
+    row0 = np.asarray(window_row0, np.int64)
+    out = np.stack([step_rows(sp[..., 0])[0] + row0, step_rows(sp[..., 1])[1] + row0], axis=-1)
+    out[(sp < 0).any(axis=-1)] = -1
+    return out
+
+
+def span_seconds(span, window_row0=0) -> np.ndarray:
+    """:func:`span_rows` in seconds, ``[..., 2]`` float64: the time at which the first row starts and the time at which the last
+    row ends (a row every 10 ms); NaN where the span is -1."""
+    rows = span_rows(span, window_row0)
+    out = np.stack([rows[..., 0] * ROW_SECONDS, (rows[..., 1] + 1) * ROW_SECONDS], axis=-1)
+    out[(rows < 0).any(axis=-1)] = np.nan
     return out
 
 

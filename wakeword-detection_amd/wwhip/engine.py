@@ -407,6 +407,71 @@ class Engine:
         self._chk(self._lib.ww_ctc_score_dev(self.ctx.handle, _vp(d_steps_ptr), int(n), int(T), int(L), _lib.ptr(table), _lib.ptr(lens), K, md,
                                              _vp(d_score_ptr)))
 
+    # the Viterbi alignment (include/wwhip.h: ww_ctc_align_*; wwhip.ctc.align is its float64 statement)
+    @staticmethod
+    def _ctc_alignment(value, span, lens):
+        from .ctc import CtcAlignment
+        return CtcAlignment(value, span[:, :, :int(lens.max())].astype(np.int32))
+
+    def ctc_align(self, windows: np.ndarray, targets=((1, 2),), mode="exact", max_labels: int = 0):
+        """``[B, window, 40]`` -> :class:`~wwhip.ctc.CtcAlignment` ``(value [K, B] float32, span [K, B, U_max, 2] int32)``: per target
+        and window the most probable path that reads (``mode="exact"``) or completes (``"prefix"``) the target, from the posteriors
+        :meth:`ctc_forward` returns as ``steps`` - its probability, and the first and last conv step it spends on each label
+        (``ww_ctc_align``; ``wwhip.ctc.span_rows`` / ``span_seconds`` turn steps into mel rows and time).  With ``max_labels > 0``
+        the greedy decode comes with it: ``(alignment, CtcResult(labels, lengths))``."""
+        from .ctc import CtcResult
+        table, lens, K, md = self._ctc_score_args(targets, mode, self.n_out)
+        w = np.ascontiguousarray(windows, dtype=np.float32)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.shape[1] != self.window or w.shape[2] != self.n_mel:
+            raise ValueError(f"Cannot set tensor: Dimension mismatch. Got {tuple(w.shape[1:])} but expected "
+                             f"{(self.window, self.n_mel)} per window")
+        n, m = w.shape[0], int(max_labels)
+        value, span = np.empty((K, n), np.float32), np.empty((K, n, _lib.CTC_SCORE_MAX_TARGET, 2), np.int8)
+        labels, lengths = (np.full((n, m), -1, np.int32), np.zeros(n, np.int32)) if m else (None, None)
+        self._chk(self._lib.ww_ctc_align(self.ctx.handle, self._model, _lib.ptr(w), n, _lib.ptr(table), _lib.ptr(lens), K, md, _lib.ptr(value),
+                                         _lib.ptr(span), m, _lib.ptr(labels), _lib.ptr(lengths)))
+        al = self._ctc_alignment(value, span, lens)
+        return (al, CtcResult(labels, lengths)) if m else al
+
+    def ctc_slide_align(self, mel: np.ndarray, hop: int = 2, targets=((1, 2),), mode="exact", max_labels: int = 0):
+        """:meth:`ctc_align` of the windows sliding over one ``[rows, 40]`` sequence (``ww_ctc_slide_align``): window ``i`` starts at
+        row ``i * hop`` (``wwhip.ctc.span_rows(al.span, np.arange(n) * hop)`` places the spans on the sequence)."""
+        from .ctc import CtcResult
+        table, lens, K, md = self._ctc_score_args(targets, mode, self.n_out)
+        mm = np.ascontiguousarray(mel, dtype=np.float32)
+        if mm.ndim != 2 or mm.shape[1] != self.n_mel:
+            raise ValueError(f"mel must be [rows, {self.n_mel}]")
+        if hop < 1:
+            raise ValueError("hop must be positive")
+        rows, m = mm.shape[0], int(max_labels)
+        nw = (rows - self.window) // hop + 1 if rows >= self.window else 0
+        value, span = np.empty((K, nw), np.float32), np.empty((K, nw, _lib.CTC_SCORE_MAX_TARGET, 2), np.int8)
+        labels, lengths = (np.full((nw, m), -1, np.int32), np.zeros(nw, np.int32)) if m else (None, None)
+        got = C.c_int64(0)
+        self._chk(self._lib.ww_ctc_slide_align(self.ctx.handle, self._model, _lib.ptr(mm), rows, int(hop), _lib.ptr(table), _lib.ptr(lens), K, md,
+                                               _lib.ptr(value), _lib.ptr(span), m, _lib.ptr(labels), _lib.ptr(lengths), C.byref(got)))
+        assert got.value == nw
+        al = self._ctc_alignment(value, span, lens)
+        return (al, CtcResult(labels, lengths)) if m else al
+
+    def ctc_align_windows_dev(self, d_mel_ptr: int, mel_rows: int, d_win_row_ptr: int, d_win_valid_ptr: int, n_windows: int, targets, mode,
+                              d_value_ptr: int, d_span_ptr: int, max_labels: int = 0, d_labels_ptr: int = 0, d_lengths_ptr: int = 0) -> None:
+        """``ww_ctc_align_windows_dev`` on device addresses: ``d_value [K, n_windows]`` float32 and ``d_span [K, n_windows, 9, 2]`` int8
+        (enqueued on the context's stream)."""
+        table, lens, K, md = self._ctc_score_args(targets, mode, self.n_out)
+        self._chk(self._lib.ww_ctc_align_windows_dev(self.ctx.handle, self._model, _vp(d_mel_ptr), int(mel_rows), _vp(d_win_row_ptr),
+                                                     _vp(d_win_valid_ptr), int(n_windows), _lib.ptr(table), _lib.ptr(lens), K, md,
+                                                     _vp(d_value_ptr), _vp(d_span_ptr), int(max_labels), _vp(d_labels_ptr), _vp(d_lengths_ptr)))
+
+    def ctc_align_dev(self, d_steps_ptr: int, n: int, T: int, L: int, targets, mode, d_value_ptr: int, d_span_ptr: int) -> None:
+        """``ww_ctc_align_dev``: the align kernel alone on device posteriors ``[n, T, L]`` -> ``d_value [K, n]`` float32 and
+        ``d_span [K, n, 9, 2]`` int8 (any model; the context is this engine's)."""
+        table, lens, K, md = self._ctc_score_args(targets, mode, int(L))
+        self._chk(self._lib.ww_ctc_align_dev(self.ctx.handle, _vp(d_steps_ptr), int(n), int(T), int(L), _lib.ptr(table), _lib.ptr(lens), K, md,
+                                             _vp(d_value_ptr), _vp(d_span_ptr)))
+
     SEQUENCE_OUTPUTS = ("enc", "logits", "post_frames", "post")
 
     def sequence_forward(self, mels, pool: Optional[int] = None, want: Sequence[str] = ("post",)) -> dict:
@@ -1290,6 +1355,8 @@ class CtcTick(NamedTuple):
     n: np.ndarray
     steps: Optional[np.ndarray] = None
     scores: Optional[np.ndarray] = None
+    align_values: Optional[np.ndarray] = None  # an ``align=True`` bank: [S, 2, K] float32, the best path's probability
+    spans: Optional[np.ndarray] = None         # and [S, 2, K, U_max, 2] int32, its first / last step per label (wwhip.ctc.align)
 
 
 class CtcStreamBank(StreamBank):
@@ -1306,12 +1373,17 @@ class CtcStreamBank(StreamBank):
 
     ``targets`` (label tuples, at most 8 of at most 9 labels) and ``mode`` (``"exact"`` / ``"prefix"``): every tick also gives the
     windows' forward-algorithm scores, ``CtcTick.scores`` - one more small launch behind the tick's, over the posteriors, so the
-    bank keeps them (``WW_STREAM_CTC_STEPS``) whether or not ``want_steps`` returns them.  :meth:`set_targets` changes them."""
+    bank keeps them (``WW_STREAM_CTC_STEPS``) whether or not ``want_steps`` returns them.  :meth:`set_targets` changes them.  With ``align=True`` a tick also gives the
+    windows' Viterbi alignment for the same targets and mode, ``CtcTick.align_values`` / ``CtcTick.spans`` (``wwhip.ctc.align``;
+    ``ww_stream_step_ctc_align``: one launch more)."""
     MAX_LABELS = _lib.STREAM_CTC_MAX_LABELS
 
     def __init__(self, engine, n_streams: int, fp: Optional[_lib.FrontendParams] = None, max_labels: int = 2, want_steps: bool = False,
                  two_launch: bool = False, sync_wait: bool = False, full_recompute: bool = False, sample_rate=16000,
-                 sample_format="pcm16", resampler=None, targets=None, mode="exact") -> None:
+                 sample_format="pcm16", resampler=None, targets=None, mode="exact", align: bool = False) -> None:
+        if align and targets is None:
+            raise ValueError("CtcStreamBank(align=True) aligns the bank's targets: give targets=")
+        self.align = bool(align)
         if isinstance(engine, ModelSet) or not getattr(engine, "is_ctc", False):
             raise ValueError("CtcStreamBank runs one CTC-trained CRNN (an Engine whose is_ctc is true); StreamBank runs the other models")
         if not 1 <= int(max_labels) <= self.MAX_LABELS:
@@ -1335,8 +1407,14 @@ class CtcStreamBank(StreamBank):
         _lib.raise_for(self._lib.ww_stream_ctc_set_targets(self._h, _lib.ptr(table), _lib.ptr(lens), len(lens), ctc.score_mode(mode)),
                        self.engine.ctx.handle)
         self.n_targets = len(lens)
+        self.target_lens = lens.copy()
         self._scores = np.zeros((self.S, 2, self.n_targets), np.float32)
         self._p_scores = C.c_void_p(self._scores.ctypes.data)
+        if self.align:
+            self._umax = int(lens.max())
+            self._align_values = np.zeros((self.S, 2, self.n_targets), np.float32)
+            self._spans = np.full((self.S, 2, self.n_targets, _lib.CTC_SCORE_MAX_TARGET, 2), -1, np.int8)
+            self._p_align_values, self._p_spans = C.c_void_p(self._align_values.ctypes.data), C.c_void_p(self._spans.ctypes.data)
 
     def _create(self, fp, full_recompute, two_launch, sync_wait, causal, ids) -> None:
         engine = self.engine
@@ -1370,7 +1448,10 @@ class CtcStreamBank(StreamBank):
         if is_active is not None:
             self._flags |= (np.ascontiguousarray(is_active, dtype=np.uint8).ravel() & 1) << 1
         self._clear()
-        if self.n_targets:
+        if self.n_targets and self.align:
+            rc = self._lib.ww_stream_step_ctc_align(self._h, pf, self._p_flags, self.max_labels, self._p_labels, self._p_lengths, self._p_steps,
+                                                    self._p_scores, self._p_align_values, self._p_spans, self._p_n)
+        elif self.n_targets:
             rc = self._lib.ww_stream_step_ctc_score(self._h, pf, self._p_flags, self.max_labels, self._p_labels, self._p_lengths, self._p_steps,
                                                     self._p_scores, self._p_n)
         else:
@@ -1387,10 +1468,15 @@ class CtcStreamBank(StreamBank):
             self._steps[:] = 0.0
         if self.n_targets:
             self._scores[:] = 0.0
+        if self.n_targets and self.align:
+            self._align_values[:] = 0.0
+            self._spans[:] = -1
 
     def _tick(self) -> CtcTick:
         return CtcTick(self._labels.copy(), self._lengths.copy(), self._n.copy(), None if self._steps is None else self._steps.copy(),
-                       self._scores.copy() if self.n_targets else None)
+                       self._scores.copy() if self.n_targets else None,
+                       self._align_values.copy() if self.n_targets and self.align else None,
+                       self._spans[:, :, :, :self._umax].astype(np.int32) if self.n_targets and self.align else None)
 
     def step_ctc_trigger(self, frames: np.ndarray, p_is_speech, p_is_active, p_target, n_target: int, p_state) -> CtcTick:
         """The wake-word stage of all streams as ONE library call (``ww_stream_step_ctc_trigger``): the tick, the label rule over

@@ -1146,7 +1146,7 @@ def ctc_statistics(y_true, y_pred) -> dict:
 
 
 def evaluate_ctc(engine: Engine, features: Sequence[np.ndarray], is_hotword: Sequence[int], target: Sequence[int] = (1, 2),
-                 thresholds=None, mode: str = "exact", windowsize: int = 1) -> dict:
+                 thresholds=None, mode: str = "exact", windowsize: int = 1, align: bool = False) -> dict:
     """``eval_CTC`` (``wwdetect/CRNN/evaluate.py:100-150``) for a CTC-trained CRNN over the records of an H5 feature file:
     ``features`` is a list of ``[frames_i, n_mel]`` arrays (what ``DatasetFilter`` writes), ``is_hotword`` their attribute.  One
     upload of all rows, ONE ``ww_ctc_forward_windows_dev`` over descriptors - one window per clip, truncated to the model's window
@@ -1159,7 +1159,12 @@ def evaluate_ctc(engine: Engine, features: Sequence[np.ndarray], is_hotword: Seq
     (``wwhip.ctc.score``; ``ww_ctc_score_windows_dev``, the decode coming out of the same call) - and the result gains ``"scores"``
     ``[n]`` and the sweep of :func:`far_frr` over them: ``"thresholds"``, ``"frr"``, ``"fa_per_hour"``, ``"fa_count"`` - the wake-word
     clips' scores against the others' in record order, the others' duration counted at 10 ms a frame.  ``windowsize`` is
-    :func:`far_frr`'s smoothing of the negative track (1: none - these are one score per clip, not per frame)."""
+    :func:`far_frr`'s smoothing of the negative track (1: none - these are one score per clip, not per frame).
+
+    ``align=True``: every clip also gets the Viterbi alignment of ``target`` in ``mode`` (``wwhip.ctc.align``; one
+    ``ww_ctc_align_windows_dev`` over the same descriptors) - ``"align_value"`` ``[n]``, ``"spans"`` ``[n, len(target), 2]`` int32 (the
+    first and last conv step of each label on the best path, -1 where there is none) and ``"span_seconds"`` (``wwhip.ctc.span_seconds``:
+    where in the clip each label lies)."""
     import torch
 
     from . import ctc
@@ -1193,10 +1198,18 @@ def evaluate_ctc(engine: Engine, features: Sequence[np.ndarray], is_hotword: Seq
             d_score = torch.empty(n, dtype=torch.float32, device=dev)
             engine.ctc_score_windows_dev(d_mel.data_ptr(), total, d_row.data_ptr(), d_valid.data_ptr(), n, [tuple(int(c) for c in target)], mode,
                                          d_score.data_ptr(), k, d_lab.data_ptr(), d_len.data_ptr())
+        if align:
+            d_value = torch.empty(n, dtype=torch.float32, device=dev)
+            d_span = torch.empty((n, ctc.SCORE_MAX_TARGET, 2), dtype=torch.int8, device=dev)
+            torch.cuda.synchronize(dev)
+            engine.ctc_align_windows_dev(d_mel.data_ptr(), total, d_row.data_ptr(), d_valid.data_ptr(), n, [tuple(int(c) for c in target)], mode,
+                                         d_value.data_ptr(), d_span.data_ptr())
         engine.ctx.synchronize()
         labels, lengths = d_lab.cpu().numpy(), d_len.cpu().numpy()
         if thresholds is not None:
             scores = d_score.cpu().numpy()
+        if align:
+            align_value, spans = d_value.cpu().numpy(), d_span.cpu().numpy()[:, :len(target)].astype(np.int32)
     pred = ctc.is_wakeword(labels, lengths, target)
     out = ctc_statistics(np.asarray(is_hotword).astype(bool), pred)
     out.update(decoded=[ctc.label_string(labels[i], lengths[i]) for i in range(n)], predicted=pred, labels=labels, lengths=lengths)
@@ -1208,6 +1221,10 @@ def evaluate_ctc(engine: Engine, features: Sequence[np.ndarray], is_hotword: Seq
         hours = float(rows[~truth].sum()) * 0.01 / 3600.0
         thr, frr, fa, cnt = far_frr(scores[truth], scores[~truth], int(truth.sum()), hours, thr, windowsize=windowsize, engine=engine)
         out.update(scores=scores, thresholds=thr, frr=frr, fa_per_hour=fa, fa_count=cnt)
+    if align:
+        if not n:
+            align_value, spans = np.zeros(0, np.float32), np.full((0, len(target), 2), -1, np.int32)
+        out.update(align_value=align_value, spans=spans, span_seconds=ctc.span_seconds(spans))
     return out
 
 

@@ -10,7 +10,7 @@ host logic: VAD-edge reset, activation, running maximum.
 from __future__ import annotations
 
 import logging
-from typing import Callable, Optional, Sequence
+from typing import Callable, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -323,14 +323,21 @@ class CtcWakewordBank:
     on the first window of the tick whose forward-algorithm score (``wwhip.ctc.score``, ``CtcTick.scores``) for some target ``j``
     exceeds ``thresholds[j]``, :class:`WakewordSetBank`'s comparison (``ww_ctc_score_trigger_bank_step``); :attr:`fired_slots` names
     the target.  The stage's own bank then scores ``targets`` (default: ``target`` alone) in ``mode``; a ``bank=`` of the caller's
-    must have been created with targets, as many as there are thresholds."""
+    must have been created with targets, as many as there are thresholds.
+
+    ``align=True`` (with the score rule): the bank also aligns its targets (``CtcStreamBank(align=True)``, ``CtcTick.spans``), and on
+    a fire the stage records WHERE the word lies: :meth:`wake_span_rows`."""
 
     def __init__(self, n_streams: int, engine=None, target: Sequence[int] = ctc.WAKEWORD, bank=None, pre_emphasis: float = 0.0,
-                 on_wake: Optional[Callable[[np.ndarray], None]] = None, thresholds=None, targets=None, mode: str = "prefix") -> None:
+                 on_wake: Optional[Callable[[np.ndarray], None]] = None, thresholds=None, targets=None, mode: str = "prefix",
+                 align: bool = False) -> None:
         from . import _lib
         from .engine import CtcStreamBank
         self.S = int(n_streams)
         self.thresholds = None
+        self.align = bool(align)
+        if self.align and thresholds is None:
+            raise ValueError("CtcWakewordBank(align=True) records the span of the target whose score fired: it needs thresholds=")
         if thresholds is not None:
             self._init_score_rule(engine, bank, pre_emphasis, on_wake, thresholds, targets if targets is not None else [tuple(target)], mode)
             return
@@ -375,10 +382,13 @@ class CtcWakewordBank:
                 raise ValueError("CtcWakewordBank needs engine (an Engine on a CTC-trained CRNN), or bank=: a CtcStreamBank")
             if len(targets) != thr.size:
                 raise ValueError(f"CtcWakewordBank: {thr.size} thresholds for {len(targets)} targets")
-            bank = CtcStreamBank(engine, self.S, frontend_params(32767.0, True, pre_emphasis, 160, True), targets=targets, mode=mode)
+            bank = CtcStreamBank(engine, self.S, frontend_params(32767.0, True, pre_emphasis, 160, True), targets=targets, mode=mode,
+                                 align=self.align)
         else:
             if getattr(bank, "S", self.S) != self.S:
                 raise ValueError(f"CtcWakewordBank: the bank has {bank.S} streams, the stage {self.S}")
+            if self.align and not getattr(bank, "align", False):
+                raise ValueError("CtcWakewordBank(align=True): the bank does not align its targets (CtcStreamBank(..., align=True))")
             if int(getattr(bank, "n_targets", 0)) != thr.size:
                 raise ValueError(f"CtcWakewordBank: {thr.size} thresholds, but the bank scores {getattr(bank, 'n_targets', 0)} targets "
                                  "(CtcStreamBank(..., targets=))")
@@ -394,6 +404,27 @@ class CtcWakewordBank:
         self._lib = _lib.load()
         self._bound = None
         self._scratch = None
+        # align=True: the windows a stream has delivered since its last reset, and the rows of the word on its last fire
+        self._seen = np.zeros(self.S, np.int64)
+        self._wake_rows = np.full((self.S, 2), -1, np.int64)
+
+    def _record_spans(self, tick) -> None:
+        """On a fire: the fired target's span on the window that fired, as rows of the stream (:meth:`wake_span_rows`)."""
+        for s, j in zip(self._fired[:self._counts[0]], self._fired_slot[:self._counts[0]]):
+            over = (tick.scores[s, :tick.n[s]].astype(np.float64) > self.thresholds).any(axis=1)
+            k = int(np.argmax(over))  # the first window of the tick on which a threshold was exceeded
+            sp, U = tick.spans[s, k, j], int(self._bank.target_lens[j])
+            self._wake_rows[s] = ctc.span_rows([sp[0, 0], sp[U - 1, 1]], int(self._seen[s]) + k - (ctc.WINDOW_ROWS - 1))
+
+    def wake_span_rows(self, s: int) -> Tuple[int, int]:
+        """``align=True``: where the word lay when stream ``s`` last fired - the first mel row of the fired target's first label and
+        the last row of its last label (``wwhip.ctc.span_rows`` over the fired window's span).  Rows are the stream's own: row ``r``
+        is the newest row of the ``r``-th window (0-based) the stream has delivered since its last reset, so the fired window covers
+        rows ``r - 150 .. r`` and a row below 0 lies in the silence in front of the stream.  ``(-1, -1)``: the stream has not fired,
+        or the fired target had no path in the bank's mode (its alignment value was 0)."""
+        if not self.align:
+            raise ValueError("wake_span_rows belongs to a stage created with align=True")
+        return int(self._wake_rows[s, 0]), int(self._wake_rows[s, 1])
 
     def _step_scores(self, contexts, frames):
         from . import _lib
@@ -408,6 +439,10 @@ class CtcWakewordBank:
                                                       _lib.ptr(self._counts[1:2]))
         if rc:
             raise ValueError("ww_ctc_score_trigger_bank_step refused its arguments")
+        if self.align:
+            self._record_spans(tick)
+            self._seen += n
+            self._seen[self._fall[:self._counts[1]]] = 0
         if self._counts[1]:
             self._bank.reset(self._fall[:self._counts[1]].copy())
         return tick
@@ -453,6 +488,8 @@ class CtcWakewordBank:
 
     def reset(self) -> None:
         self._bank.reset()
+        if self.thresholds is not None:
+            self._seen[:] = 0
 
     def close(self) -> None:
         self._bank.close()
