@@ -455,6 +455,47 @@ int ww_ctc_slide_align(ww_ctx *ctx, const ww_model *model, const float *mel, int
                        const int32_t *target_lens, int32_t K, int32_t mode, float *value, int8_t *span, int32_t max_labels, int32_t *labels,
                        int32_t *lengths, int64_t *n_windows);
 
+/* ---- CTC-trained CRNNs: prefix BEAM SEARCH, the n most probable label strings -----------------------------------------------------------
+ * The greedy decode collapses the most probable path; it does not find the most probable label STRING, and ww_ctc_score_* needs its
+ * targets named in advance.  The beam search gives the P most probable strings of a window with their probabilities - what
+ * K.ctc_decode(greedy=False, beam_width, top_paths) is asked for.  The statement, its order and its arithmetic: csrc/ctc_beam.h
+ * (wwhip.ctc.beam_search is the same in float64): the textbook prefix search on the posteriors themselves, in the linear domain.  It
+ * is not a bit copy of TensorFlow's decoder, which works on log(y + 1e-7) in the log domain; the parity target is the float64 statement.
+ *   y [T][L] posteriors, the blank is class L - 1;  1 <= T <= WW_CTC_BEAM_MAX_T, 2 <= L <= 8
+ *   1 <= beam_width <= WW_CTC_BEAM_MAX_WIDTH, 1 <= top_paths <= min(beam_width, WW_CTC_BEAM_MAX_PATHS), 1 <= max_labels <= T
+ *   labels  [n][top_paths][max_labels] int32: the first max_labels labels of path p, padded with -1
+ *   lengths [n][top_paths] int32: the WHOLE length of path p (it may exceed max_labels; 0 is the empty string)
+ *   prob    [n][top_paths] float32: P(decode == that string) as far as the beam saw it, descending (ties: shorter, then lexicographic)
+ *   a path whose probability is 0, or that the beam has no entry for, is absent: length -1, every label -1, prob 0
+ * Every + and * is one float32 operation in the header's order, every comparison the header's, on the device and on the host:
+ * ww_ctc_beam_dev gives the bits of ww_ctc_beam_rows.  Against the float64 statement on the same float32 posteriors with the same
+ * pruning decisions a probability is within (3T + 2) 2^-24 relative (derived in the header), plus 5 T (T + 1) 2^-126 where values
+ * under FLT_MIN are flushed.
+ * WW_EINVAL before anything is written, the text naming the rule: T, L, beam_width, top_paths or max_labels out of range, a NULL
+ * required pointer; the model forms also for a model that is not WW_HEAD_CTC or is in WW_PRECISION_BF16X3.  n = 0: WW_OK, nothing
+ * written.
+ * ww_ctc_beam_dev - ctc_beam_kernel alone (csrc/ctc_beam.hip: a wave per sequence, a beam slot per lane) on any device posteriors
+ *   [n][T][L]; rows [0, n) of each output are written and nothing else, and a sequence's non-finite posteriors reach its own outputs
+ *   alone.  Enqueued on the context's stream, no synchronisation.
+ * ww_ctc_beam_rows - host only, no context (its refusal's text: ww_last_error(NULL)): the header's function over host arrays.
+ * ww_ctc_beam / _windows_dev / ww_ctc_slide_beam - ww_ctc_forward / _windows_dev / ww_ctc_slide_forward with the beam kernel behind
+ *   every chunk's model launch, on the posteriors that ww_ctc_forward would return as `steps` (T = 19, L = n_out; they stay in the
+ *   workspace).  The greedy decode is not carried beside it. */
+#define WW_CTC_BEAM_MAX_T 19
+#define WW_CTC_BEAM_MAX_WIDTH 64
+#define WW_CTC_BEAM_MAX_PATHS 8
+int ww_ctc_beam_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, int32_t L, int32_t beam_width, int32_t top_paths,
+                    int32_t max_labels, int32_t *d_labels, int32_t *d_lengths, float *d_prob);
+int ww_ctc_beam_rows(const float *steps, int64_t n, int32_t T, int32_t L, int32_t beam_width, int32_t top_paths, int32_t max_labels,
+                     int32_t *labels, int32_t *lengths, float *prob);
+int ww_ctc_beam(ww_ctx *ctx, const ww_model *model, const float *windows, int32_t n, int32_t beam_width, int32_t top_paths,
+                int32_t max_labels, int32_t *labels, int32_t *lengths, float *prob);
+int ww_ctc_beam_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                            const int32_t *d_win_valid, int32_t n, int32_t beam_width, int32_t top_paths, int32_t max_labels,
+                            int32_t *d_labels, int32_t *d_lengths, float *d_prob);
+int ww_ctc_slide_beam(ww_ctx *ctx, const ww_model *model, const float *mel, int64_t rows, int32_t hop, int32_t beam_width,
+                      int32_t top_paths, int32_t max_labels, int32_t *labels, int32_t *lengths, float *prob, int64_t *n_windows);
+
 /* ww_forward_windows_dev over a model set: window w is evaluated by member win_model[w], all windows in ONE launch (K checkpoints
  * over the same mel - the loop over eval_models of wwdetect/wavenet/evaluate_wavenet.py - are K x n windows that name the same rows).
  * win_model is a HOST array: read and checked before the call returns (an id outside [0, n_models): WW_EINVAL, nothing is launched),
@@ -931,7 +972,17 @@ int ww_ctc_score_trigger_bank_step(int32_t n_streams, int32_t K, const uint8_t *
  *   ww_stream_step_ctc and ww_stream_step_ctc_score keep their launches. */
 int ww_stream_step_ctc_align(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels,
                              int32_t *lengths, float *steps, float *scores, float *align_value, int8_t *align_span, int32_t *n_post);
-/* Where a tick's time goes on the HOST side of ww_stream_step (the loop of spokestack/pipeline.py:25-28 is host-paced, so
+/* ww_stream_step_ctc_beam - ww_stream_step_ctc plus ONE ctc_beam_kernel launch behind the tick's model launch, over the bank's
+ *   page-locked posterior block (ww_ctc_beam_* above, T = 19, L = n_out): beam_labels [S][2][top_paths][beam_max_labels],
+ *   beam_lengths [S][2][top_paths] and beam_probs [S][2][top_paths], through a page-locked block the bank allocates on the first such
+ *   call.  Entries at or past n_post[s] are left as they were.  In every form of the bank a window's paths are the bits
+ *   ww_ctc_beam_dev gives on the posteriors the same tick returns in `steps` (which may be NULL).  WW_EINVAL before any state moves:
+ *   a bank without WW_STREAM_CTC_STEPS, beam_width / top_paths / beam_max_labels out of range, a NULL output.  The scores and the
+ *   alignment are not carried in the same call. */
+int ww_stream_step_ctc_beam(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels,
+                            int32_t *lengths, float *steps, int32_t beam_width, int32_t top_paths, int32_t beam_max_labels,
+                            int32_t *beam_labels, int32_t *beam_lengths, float *beam_probs, int32_t *n_post);
+/* Where a tick's time goes on the HOST side of ww_stream_step(the loop of spokestack/pipeline.py:25-28 is host-paced, so
  * BASELINE config 5's per-tick latency is this call): mean nanoseconds per phase over the ticks since the last reset -
  * [0] plan (control words and window descriptors of the tick), [1] the caller's frames into the page-locked block,
  * [2] first kernel launch, [3] second kernel launch (0 where a tick is one launch), [4] waiting for the posteriors,

@@ -58,6 +58,9 @@ def parse_args():
     p.add_argument("--score_mode", type=str, default="exact", choices=("exact", "prefix"), help="exact: the decode IS the target; prefix: starts with it")
     p.add_argument("--align", action="store_true",
                    help="also print, per clip, where the best [HEY][SNIPS] path (Viterbi, --score_mode) lies: each label's seconds into the clip")
+    p.add_argument("--beam", type=int, default=0, metavar="W",
+                   help="apply the [HEY][SNIPS] rule to the most probable label string found by prefix beam search of width W (1..64) instead "
+                        "of the greedy decode: eval_CTC with greedy=False")
     return p.parse_args()
 
 
@@ -65,8 +68,10 @@ def main(args):
     feats, labels, keys = read_records(os.path.join(args.data_dir, args.testset))
     eng = Engine(args.model_dir, bundle=ctc_bundle(args.model_dir, args.ctc_head, args.keras_kernel))
     thr = np.linspace(0.0, 1.0, args.thresholds + 2)[1:-1] if args.thresholds > 0 else None
-    stats = evaluate_ctc(eng, feats, labels, thresholds=thr, mode=args.score_mode, align=args.align)
+    stats = evaluate_ctc(eng, feats, labels, thresholds=thr, mode=args.score_mode, align=args.align, beam_width=args.beam or None)
     eng.close()
+    if args.beam:
+        print(f"beam search, width {args.beam}: top string's probability median {np.median(stats['beam_probs']) if len(feats) else float('nan'):.3g}")
     print("False accept files:", [k for k, p, t in zip(keys, stats["predicted"], labels) if p and not t])
     print("False reject files:", [k for k, p, t in zip(keys, stats["predicted"], labels) if t and not p])
     for name in ("tp", "fp", "tn", "fn", "precision", "recall"):

@@ -1,6 +1,7 @@
 // C ABI of libwwhip.so: context, model upload, host/device entry points (see include/wwhip.h).
 #include "common.h"
 #include "ctc_align.h"
+#include "ctc_beam.h"
 #include "ctc_score.h"
 #include "model_pack.h"
 #include "model_set.h"
@@ -871,6 +872,63 @@ static int ctc_score_host(ww_ctx *ctx, const ww_model *m, const float *mel, int6
   return io.finish();
 }
 
+// ---- the prefix beam search (include/wwhip.h: ww_ctc_beam_*; csrc/ctc_beam.h) --------------------------------------------------------
+// what the three model forms refuse before anything is written
+static int ctc_beam_check(ww_ctx *ctx, const ww_model *m, int W, int P, int max_labels, const void *labels, const void *lengths, const void *prob,
+                          const char *what) {
+  if (!ctx || !m) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (int rc = ww_crnn_ctc_check(ctx, m, what)) return rc;
+  char why[200];
+  if (!ww_ctc_beam_args_ok(WW_CTC_STEPS, m->info.n_out, W, P, max_labels, why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "%s: %s", what, why);
+  if (!labels || !lengths || !prob) return ww_fail(ctx, WW_EINVAL, "%s: labels / lengths / prob are NULL", what);
+  return WW_OK;
+}
+
+// ctc_score_chunks with ctc_beam_kernel behind every chunk's model launch: d_labels [nw][P][max_labels], d_lengths [nw][P], d_prob [nw][P]
+// (the greedy decode the model launch also makes stays in the workspace).  ws: ctc_score_workspace(m, nw) bytes inside the device arena.
+static int ctc_beam_chunks(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_row, const int32_t *d_valid,
+                           int hop, int valid_const, int64_t nw, void *ws, int W, int P, int max_labels, int32_t *d_labels, int32_t *d_lengths,
+                           float *d_prob) {
+  const int chunk = chunk_of(nw), L = m->info.n_out;
+  ww_bump bump(ws, ctc_score_workspace(m, nw));
+  float *d_steps = bump.take<float>((size_t)chunk * WW_CTC_STEPS * L);
+  int32_t *own_lab = bump.take<int32_t>((size_t)chunk), *own_len = bump.take<int32_t>((size_t)chunk);
+  void *mws = bump.base + bump.off;
+  const char *lo = (const char *)ctx->dev.ptr, *p = (const char *)mws;
+  const size_t cap = (p >= lo && p <= lo + ctx->dev.cap) ? (size_t)(lo + ctx->dev.cap - p) : 0;
+  for (int64_t w0 = 0; w0 < nw; w0 += chunk) {
+    const int n = (int)((nw - w0) < chunk ? (nw - w0) : chunk);
+    if (int rc = ww_k_crnn_ctc_forward(ctx, m, d_mel, mel_rows, d_row ? d_row + w0 : nullptr, d_row ? d_valid + w0 : nullptr, d_row ? 0 : w0 * hop,
+                                       hop, valid_const, n, mws, cap, 1, own_lab, own_len, d_steps, nullptr))
+      return rc;
+    if (int rc = ww_k_ctc_beam(ctx, d_steps, n, WW_CTC_STEPS, L, W, P, max_labels, d_labels + (size_t)w0 * P * max_labels, d_lengths + (size_t)w0 * P,
+                               d_prob + (size_t)w0 * P))
+      return rc;
+  }
+  return WW_OK;
+}
+
+// the host forms: the sequence in, the P paths of every window out, staged like ctc_score_host's
+static int ctc_beam_host(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t rows, int hop, int64_t nw, int W, int P, int max_labels,
+                         int32_t *labels, int32_t *lengths, float *prob) {
+  const int T = m->info.window, F = m->info.n_mel;
+  const size_t n_path = (size_t)nw * P, n_lab = n_path * max_labels;
+  WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
+  const size_t b_io = ww_bump::need((size_t)rows * F, 4) + ww_bump::need(n_lab, 4) + 2 * ww_bump::need(n_path, 4);
+  const size_t b_ws = ctc_score_workspace(m, nw);
+  ww_staged_io io(ctx);
+  int rc = io.init(b_io, b_ws + 1024, nw <= 64);
+  if (rc) return rc;
+  const float *d_mel = io.in(mel, (size_t)rows * F);
+  int32_t *d_lab = io.out<int32_t>(n_lab), *d_len = io.out<int32_t>(n_path);
+  float *d_prob = io.out<float>(n_path);
+  void *ws = io.scratch(b_ws);
+  if (io.rc) return io.rc;
+  if ((rc = ctc_beam_chunks(ctx, m, d_mel, rows, nullptr, nullptr, hop, T, nw, ws, W, P, max_labels, d_lab, d_len, d_prob))) return rc;
+  if ((rc = io.fetch(labels, d_lab, n_lab * 4)) || (rc = io.fetch(lengths, d_len, n_path * 4)) || (rc = io.fetch(prob, d_prob, n_path * 4))) return rc;
+  return io.finish();
+}
+
 __global__ void iota_offs_kernel(int64_t *sample_offs, int64_t *frame_offs, int n, int64_t samples, int64_t frames) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i <= n) {
@@ -1143,6 +1201,82 @@ int ww_ctc_align_windows_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel,
   if (int rc = ww_ensure(ctx, ctx->dev, ctc_score_workspace(m, n) + 1024, false)) return rc;
   return ctc_score_chunks(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, n, ctx->dev.ptr, tg, nullptr, max_labels, d_labels, d_lengths, d_value,
                           d_span);
+  WW_GUARD_END(ctx)
+}
+
+// ---- the prefix beam search (include/wwhip.h: ww_ctc_beam_*; csrc/ctc_beam.h) --------------------------------------------------------
+int ww_ctc_beam_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, int32_t L, int32_t beam_width, int32_t top_paths, int32_t max_labels,
+                    int32_t *d_labels, int32_t *d_lengths, float *d_prob) {
+  WW_GUARD_BEGIN
+  if (!ctx) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  char why[200];
+  if (!ww_ctc_beam_args_ok(T, L, beam_width, top_paths, max_labels, why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "ww_ctc_beam_dev: %s", why);
+  if (n < 0 || n > 0x7fffffff) return ww_fail(ctx, WW_EINVAL, "ww_ctc_beam_dev: sequence count out of range");
+  if (!d_labels || !d_lengths || !d_prob) return ww_fail(ctx, WW_EINVAL, "ww_ctc_beam_dev: labels / lengths / prob are NULL");
+  if (n == 0) return WW_OK;
+  if (!d_steps) return ww_fail(ctx, WW_EINVAL, "ww_ctc_beam_dev: steps is NULL");
+  WW_ON_DEVICE(ctx, dev);
+  return ww_k_ctc_beam(ctx, d_steps, n, T, L, beam_width, top_paths, max_labels, d_labels, d_lengths, d_prob);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_beam_rows(const float *steps, int64_t n, int32_t T, int32_t L, int32_t beam_width, int32_t top_paths, int32_t max_labels,
+                     int32_t *labels, int32_t *lengths, float *prob) {
+  WW_GUARD_BEGIN
+  char why[200];
+  if (!ww_ctc_beam_args_ok(T, L, beam_width, top_paths, max_labels, why, sizeof why)) return ww_fail(nullptr, WW_EINVAL, "ww_ctc_beam_rows: %s", why);
+  if (n < 0) return ww_fail(nullptr, WW_EINVAL, "ww_ctc_beam_rows: negative sequence count");
+  if (!labels || !lengths || !prob) return ww_fail(nullptr, WW_EINVAL, "ww_ctc_beam_rows: labels / lengths / prob are NULL");
+  if (n == 0) return WW_OK;
+  if (!steps) return ww_fail(nullptr, WW_EINVAL, "ww_ctc_beam_rows: steps is NULL");
+  for (int64_t i = 0; i < n; ++i)
+    ww_ctc_beam_row(steps + (size_t)i * T * L, T, L, L, beam_width, top_paths, max_labels, labels + (size_t)i * top_paths * max_labels,
+                    lengths + (size_t)i * top_paths, prob + (size_t)i * top_paths);
+  return WW_OK;
+  WW_GUARD_END(nullptr)
+}
+
+int ww_ctc_beam(ww_ctx *ctx, const ww_model *m, const float *windows, int32_t n, int32_t beam_width, int32_t top_paths, int32_t max_labels,
+                int32_t *labels, int32_t *lengths, float *prob) {
+  WW_GUARD_BEGIN
+  if (int rc = ctc_beam_check(ctx, m, beam_width, top_paths, max_labels, labels, lengths, prob, "ww_ctc_beam")) return rc;
+  if (n < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
+  if (n == 0) return WW_OK;
+  if (!windows) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
+  // n stacked windows are one mel sequence of n * T rows read with hop = T
+  return ctc_beam_host(ctx, m, windows, (int64_t)n * m->info.window, m->info.window, n, beam_width, top_paths, max_labels, labels, lengths, prob);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_slide_beam(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t rows, int32_t hop, int32_t beam_width, int32_t top_paths,
+                      int32_t max_labels, int32_t *labels, int32_t *lengths, float *prob, int64_t *n_windows) {
+  WW_GUARD_BEGIN
+  if (int rc = ctc_beam_check(ctx, m, beam_width, top_paths, max_labels, labels, lengths, prob, "ww_ctc_slide_beam")) return rc;
+  if (!n_windows) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (hop <= 0) return ww_fail(ctx, WW_EINVAL, "hop must be positive");
+  if (rows < 0) return ww_fail(ctx, WW_EINVAL, "negative row count");
+  const int T = m->info.window;
+  const int64_t nw = rows >= T ? (rows - T) / hop + 1 : 0;
+  if (nw > 0 && !mel) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
+  *n_windows = nw;
+  if (nw == 0) return WW_OK;
+  return ctc_beam_host(ctx, m, mel, rows, hop, nw, beam_width, top_paths, max_labels, labels, lengths, prob);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_beam_windows_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                            const int32_t *d_win_valid, int32_t n, int32_t beam_width, int32_t top_paths, int32_t max_labels, int32_t *d_labels,
+                            int32_t *d_lengths, float *d_prob) {
+  WW_GUARD_BEGIN
+  if (int rc = ctc_beam_check(ctx, m, beam_width, top_paths, max_labels, d_labels, d_lengths, d_prob, "ww_ctc_beam_windows_dev")) return rc;
+  if (n < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
+  if (n == 0) return WW_OK;
+  if (!d_mel) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (!d_win_row || !d_win_valid) return ww_fail(ctx, WW_EINVAL, "window descriptors are NULL");
+  WW_ON_DEVICE(ctx, dev);
+  if (int rc = ww_ensure(ctx, ctx->dev, ctc_score_workspace(m, n) + 1024, false)) return rc;
+  return ctc_beam_chunks(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, n, ctx->dev.ptr, beam_width, top_paths, max_labels, d_labels, d_lengths,
+                         d_prob);
   WW_GUARD_END(ctx)
 }
 

@@ -293,6 +293,10 @@ int ww_k_ctc_score(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, c
 // At o = k * stride_k + i * stride_i: d_value[o] and the 18 bytes d_span[18 o ..] ([WW_CTC_SCORE_MAX_TARGET][2] int8).
 int ww_k_ctc_align(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, const ww_ctc_score_targets &tg, float *d_value, int8_t *d_span,
                    int64_t stride_k, int64_t stride_i);
+// ctc_beam_kernel (ctc_beam.hip; the statement: ctc_beam.h): the prefix beam search over any device posteriors [n][T][L], a wave per
+// sequence: d_labels [n][P][max_labels], d_lengths [n][P], d_prob [n][P].  The arguments have passed ww_ctc_beam_args_ok.
+int ww_k_ctc_beam(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, int W, int P, int max_labels, int32_t *d_labels, int32_t *d_lengths,
+                  float *d_prob);
 // A CTC stream bank's incremental ticks (crnn_stream_kernel<FE, false, false, CTC>): ww_k_crnn_tick's and ww_k_crnn_stream_forward's
 // arguments; a window's decode goes out as one 32-bit word (stream_ctc.h) - the value half of its tag where tag slots are given, else
 // row w of d_words -, and with d_steps (page-locked, [windows of the launch][19][L]; nullptr: off) its posteriors beside it

@@ -30,6 +30,7 @@
 #include "stream_ctc.h"
 #include "ctc_score.h"
 #include "ctc_align.h"
+#include "ctc_beam.h"
 #include "stream_fe.h"
 
 #include <algorithm>
@@ -135,6 +136,13 @@ struct ww_streams {
   float *h_align = nullptr, *h_align_dev = nullptr;
   int8_t *h_span() const { return (int8_t *)(h_align + (size_t)2 * S * WW_CTC_SCORE_MAX_TARGETS); }
   int8_t *h_span_dev() const { return (int8_t *)(h_align_dev + (size_t)2 * S * WW_CTC_SCORE_MAX_TARGETS); }
+  // ww_stream_step_ctc_beam: ctc_beam_kernel over the same posterior block; one page-locked block of 32-bit words, allocated by the
+  // first such call for the widest call there is: labels [2 S][WW_CTC_BEAM_MAX_PATHS][19], then lengths and probabilities
+  // [2 S][WW_CTC_BEAM_MAX_PATHS] each (a tick with P paths of M labels uses the first 2 S P M, 2 S P and 2 S P of them)
+  int32_t *h_beam = nullptr, *h_beam_dev = nullptr;
+  size_t beam_len_off() const { return (size_t)2 * S * WW_CTC_BEAM_MAX_PATHS * WW_SC_STEPS; }
+  size_t beam_prob_off() const { return beam_len_off() + (size_t)2 * S * WW_CTC_BEAM_MAX_PATHS; }
+  size_t beam_words() const { return beam_prob_off() + (size_t)2 * S * WW_CTC_BEAM_MAX_PATHS; }
   // the reason this bank refuses `call` (CTC or not: here; every-member or not: stream_all.h, sa_check_call), where ww_last_error
   // finds it; WW_OK: it does not
   int check_call(const char *call, bool wants_every, bool wants_ctc = false) const {
@@ -432,7 +440,7 @@ int ww_stream_destroy(ww_streams *st) {
   void *dev[] = {st->ring, st->hist, st->prev, st->d_pack, st->ws, st->gxc, st->gx_zero, st->wstate, st->zring, st->zpos, st->d_stream_model};
   for (void *p : dev)
     if (p) hipFree(p);
-  void *host[] = {st->h_pack, st->h_out, st->h_tag, st->h_steps, st->h_lab, st->h_score, st->h_align};
+  void *host[] = {st->h_pack, st->h_out, st->h_tag, st->h_steps, st->h_lab, st->h_score, st->h_align, st->h_beam};
   for (void *p : host)
     if (p) hipHostFree(p);
   ww_k_rates_destroy(st->rates);
@@ -914,6 +922,10 @@ struct st_ctc_out {
   float *scores;              // [S][2][K] or nullptr (ww_stream_step_ctc_score: the bank's targets are set)
   float *align_value = nullptr;  // [S][2][K] and [S][2][K][9][2], or nullptr (ww_stream_step_ctc_align)
   int8_t *align_span = nullptr;
+  // ww_stream_step_ctc_beam: [S][2][P][M], [S][2][P], [S][2][P], or nullptr
+  int beam_width = 0, top_paths = 0, beam_max_labels = 0;
+  int32_t *beam_labels = nullptr, *beam_lengths = nullptr;
+  float *beam_probs = nullptr;
 };
 
 // The one tick of every bank.  co (a CTC bank, stream_ctc.h): the same bookkeeping, frames, front end and wait; the model launches
@@ -1057,6 +1069,11 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
     if (int rc = ww_k_ctc_align(ctx, st->h_steps_dev, tk.form == SA_TABLE ? nw : 2 * S, WW_SC_STEPS, st->NO, st->score_tg, st->h_align_dev,
                                 st->h_span_dev(), 1, st->score_tg.K))
       return rc;
+  // ww_stream_step_ctc_beam: the beam search over the same slots, one launch behind the model's
+  if (co && co->beam_labels && nw)
+    if (int rc = ww_k_ctc_beam(ctx, st->h_steps_dev, tk.form == SA_TABLE ? nw : 2 * S, WW_SC_STEPS, st->NO, co->beam_width, co->top_paths, co->beam_max_labels,
+                               st->h_beam_dev, st->h_beam_dev + st->beam_len_off(), (float *)(st->h_beam_dev + st->beam_prob_off())))
+      return rc;
   // (include/wwhip.h: phase [3] is 0 where a tick is one launch - the one-launch forms, and a two-launch bank's tick without a window:
   // no clock read of its own, which on a tick's first pass through this code measured the branches above, not a launch)
   tl[4] = second ? st_now_ns() : tl[3];
@@ -1098,6 +1115,17 @@ static int stream_step_impl(ww_streams *st, const int16_t *frames, const uint8_t
           const size_t slot = (size_t)(table ? w : 2 * s + k);
           memcpy(co->align_value + ((size_t)s * 2 + k) * row, st->h_align + slot * row, row * sizeof(float));
           memcpy(co->align_span + ((size_t)s * 2 + k) * srow, st->h_span() + slot * srow, srow);
+        }
+    }
+    if (co->beam_labels) {
+      const size_t P = (size_t)co->top_paths, lrow = P * co->beam_max_labels;
+      int w = 0;
+      for (int s = 0; s < S; ++s)
+        for (int k = 0; k < n_post[s]; ++k, ++w) {
+          const size_t slot = (size_t)(table ? w : 2 * s + k), o = (size_t)s * 2 + k;
+          memcpy(co->beam_labels + o * lrow, st->h_beam + slot * lrow, lrow * 4);
+          memcpy(co->beam_lengths + o * P, st->h_beam + st->beam_len_off() + slot * P, P * 4);
+          memcpy(co->beam_probs + o * P, st->h_beam + st->beam_prob_off() + slot * P, P * 4);
         }
     }
   } else
@@ -1540,7 +1568,7 @@ int ww_stream_timeline(ww_streams *st, double *mean_ns, int64_t *ticks, int32_t 
 // ww_stream_step_ctc's refusals - all before any state moves -, then the one tick
 static int stream_step_ctc_entry(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels,
                                  int32_t *lengths, float *steps, int32_t *n_post, const char *call, float *scores = nullptr,
-                                 float *align_value = nullptr, int8_t *align_span = nullptr) {
+                                 float *align_value = nullptr, int8_t *align_span = nullptr, const st_ctc_out *beam = nullptr) {
   ww_ctx *ctx = st->ctx;
   if (int rc = st->check_call(call, false, true)) return rc;
   if (int rc = st->check_sound()) return rc;
@@ -1548,7 +1576,11 @@ static int stream_step_ctc_entry(ww_streams *st, const int16_t *frames, const ui
     return ww_fail(ctx, WW_EINVAL, "%s: max_labels %d: a streamed window carries 1..%d labels", call, (int)max_labels, WW_STREAM_CTC_MAX_LABELS);
   if (!labels || !lengths) return ww_fail(ctx, WW_EINVAL, "%s: NULL argument", call);
   if (steps && !st->ctc_steps) return ww_fail(ctx, WW_EINVAL, "%s: posteriors are returned by a bank created with WW_STREAM_CTC_STEPS", call);
-  const st_ctc_out co = {max_labels, labels, lengths, steps, scores, align_value, align_span};
+  st_ctc_out co = {max_labels, labels, lengths, steps, scores, align_value, align_span};
+  if (beam) {
+    co.beam_width = beam->beam_width; co.top_paths = beam->top_paths; co.beam_max_labels = beam->beam_max_labels;
+    co.beam_labels = beam->beam_labels; co.beam_lengths = beam->beam_lengths; co.beam_probs = beam->beam_probs;
+  }
   return stream_step_entry(st, frames, is_speech, nullptr, n_post, call, false, &co);
 }
 
@@ -1640,6 +1672,37 @@ int ww_stream_step_ctc_align(ww_streams *st, const int16_t *frames, const uint8_
     }
   }
   return stream_step_ctc_entry(st, frames, is_speech, max_labels, labels, lengths, steps, n_post, call, scores, align_value, align_span);
+  WW_GUARD_END(st ? st->ctx : nullptr)
+}
+
+int ww_stream_step_ctc_beam(ww_streams *st, const int16_t *frames, const uint8_t *is_speech, int32_t max_labels, int32_t *labels,
+                            int32_t *lengths, float *steps, int32_t beam_width, int32_t top_paths, int32_t beam_max_labels, int32_t *beam_labels,
+                            int32_t *beam_lengths, float *beam_probs, int32_t *n_post) {
+  WW_GUARD_BEGIN
+  if (!st) return WW_EINVAL;
+  const char *call = "ww_stream_step_ctc_beam";
+  ww_ctx *ctx = st->ctx;
+  if (int rc = st->check_call(call, false, true)) return rc;
+  if (!st->ctc_steps) return ww_fail(ctx, WW_EINVAL, "%s: the beam search reads a tick's posteriors: the bank must be created with WW_STREAM_CTC_STEPS", call);
+  char why[200];
+  if (!ww_ctc_beam_args_ok(WW_SC_STEPS, st->NO, beam_width, top_paths, beam_max_labels, why, sizeof why)) return ww_fail(ctx, WW_EINVAL, "%s: %s", call, why);
+  if (!beam_labels || !beam_lengths || !beam_probs) return ww_fail(ctx, WW_EINVAL, "%s: beam_labels / beam_lengths / beam_probs are NULL", call);
+  if (!st->h_beam) {
+    WW_ON_DEVICE(ctx, dev_scope);
+    if (hipHostMalloc((void **)&st->h_beam, st->beam_words() * 4) != hipSuccess) {
+      st->h_beam = nullptr;
+      return ww_fail(ctx, WW_ENOMEM, "%s: cannot allocate the beam block of %d streams", call, st->S);
+    }
+    if (hipHostGetDevicePointer((void **)&st->h_beam_dev, st->h_beam, 0) != hipSuccess) {
+      hipHostFree(st->h_beam);
+      st->h_beam = nullptr;
+      return ww_fail(ctx, WW_EHIP, "%s: the beam block is not visible to the device", call);
+    }
+  }
+  st_ctc_out beam;
+  beam.beam_width = beam_width; beam.top_paths = top_paths; beam.beam_max_labels = beam_max_labels;
+  beam.beam_labels = beam_labels; beam.beam_lengths = beam_lengths; beam.beam_probs = beam_probs;
+  return stream_step_ctc_entry(st, frames, is_speech, max_labels, labels, lengths, steps, n_post, call, nullptr, nullptr, nullptr, &beam);
   WW_GUARD_END(st ? st->ctx : nullptr)
 }
 

@@ -102,6 +102,11 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_ctc_align": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ww_ctc_align_windows_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ww_ctc_slide_align": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _P(_i64)]),
+    "ww_ctc_beam_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ww_ctc_beam_rows": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ww_ctc_beam": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ww_ctc_beam_windows_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ww_ctc_slide_beam": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _P(_i64)]),
     "ww_model_set_precision": (C.c_int, [_vp, C.c_int]),
     "ww_model_set_option": (C.c_int, [_vp, C.c_int, _i64]),
     "ww_model_set_create": (C.c_int, [_vp, _P(_vp), _i32, _P(_vp)]),
@@ -175,6 +180,7 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_stream_ctc_set_targets": (C.c_int, [_vp, _vp, _vp, _i32, _i32]),
     "ww_stream_step_ctc_score": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ww_stream_step_ctc_align": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ww_stream_step_ctc_beam": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ww_ctc_score_trigger_bank_step": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ww_superframe_smooth": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp]),
     "ww_far_frr": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),

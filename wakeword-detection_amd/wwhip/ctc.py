@@ -17,6 +17,11 @@ what ``K.ctc_batch_cost`` (``wwdetect/CRNN/train.py:184-200``) is minus the loga
 ``align`` is the max-product twin: the most probable path through the target's lattice and the steps at which it enters and leaves
 each label - where in the window the wake word lies, to one conv step (``csrc/ctc_align.h``; ``step_rows`` / ``span_rows`` /
 ``span_seconds`` turn steps into mel rows and time).
+
+``beam_search`` is the prefix beam search: the most probable label STRINGS of a window and their probabilities, where the greedy
+decode collapses the most probable path - ``K.ctc_decode(greedy=False, beam_width, top_paths)``'s question.  ``csrc/ctc_beam.h``
+states it (the textbook search in the linear domain on the posteriors themselves; not TensorFlow's log-domain bits); the function
+here is that statement in float64, ``beam_rows`` the library's float32 function on the host.
 """
 from __future__ import annotations
 
@@ -251,6 +256,135 @@ def align_rows(steps, targets, mode="exact") -> CtcAlignment:
     _lib.raise_for(_lib.load().ww_ctc_align_rows(_lib.ptr(y), n, T, L, _lib.ptr(table), _lib.ptr(lens), len(lens), score_mode(mode),
                                                  _lib.ptr(value), _lib.ptr(span)), None)
     return CtcAlignment(value, span[:, :, :int(lens.max())].astype(np.int32))
+
+
+BEAM_MAX_T, BEAM_MAX_L, BEAM_MAX_WIDTH, BEAM_MAX_PATHS = 19, 8, 64, 8  # include/wwhip.h: WW_CTC_BEAM_*
+_KEY_LEN_SHIFT = 3 * BEAM_MAX_T  # a prefix key: the length above bit 57, the labels below at 3 bits each, the first label highest
+
+
+class CtcBeam(NamedTuple):
+    """``labels [n, P, max_labels]`` int32 padded with -1, ``lengths [n, P]`` int32 (the whole length; -1: the path is absent),
+    ``probs [n, P]``: the P most probable label strings of each window, descending.  ``log_probs`` is what Keras returns."""
+    labels: np.ndarray
+    lengths: np.ndarray
+    probs: np.ndarray
+
+    @property
+    def log_probs(self) -> np.ndarray:
+        with np.errstate(divide="ignore"):
+            return np.log(self.probs)
+
+
+def beam_rel_bound(T: int) -> float:
+    """``csrc/ctc_beam.h``'s derived bound: the relative error of a reported probability against the float64 statement on the same
+    float32 posteriors with the same pruning decisions, ``(3 T + 2) 2^-24``."""
+    return (3 * int(T) + 2) * 2.0 ** -24
+
+
+def _beam_args(T, L, beam_width, top_paths, max_labels):
+    W, P = int(beam_width), int(top_paths)
+    M = T if max_labels is None else int(max_labels)
+    if not 1 <= T <= BEAM_MAX_T:
+        raise ValueError(f"T = {T} outside 1..{BEAM_MAX_T}")
+    if not 2 <= L <= BEAM_MAX_L:
+        raise ValueError(f"L = {L} outside 2..{BEAM_MAX_L}")
+    if not 1 <= W <= BEAM_MAX_WIDTH:
+        raise ValueError(f"beam_width = {W} outside 1..{BEAM_MAX_WIDTH}")
+    if not 1 <= P <= min(W, BEAM_MAX_PATHS):
+        raise ValueError(f"top_paths = {P} outside 1..min(beam_width, {BEAM_MAX_PATHS})")
+    if not 1 <= M <= T:
+        raise ValueError(f"max_labels = {M} outside 1..T = 1..{T}")
+    return W, P, M
+
+
+def key_labels(key: int) -> Tuple[int, ...]:
+    """A prefix key -> its labels."""
+    key = int(key)
+    n = key >> _KEY_LEN_SHIFT
+    return tuple((key >> (_KEY_LEN_SHIFT - 3 * (i + 1))) & 7 for i in range(n))
+
+
+def beam_search(steps, beam_width: int, top_paths: int = 1, max_labels: Optional[int] = None, dtype=np.float64, trace: Optional[list] = None) -> CtcBeam:
+    """``csrc/ctc_beam.h`` in ``dtype``: CTC prefix beam search over ``steps [n, T, L]`` (or ``[T, L]``) posteriors, the blank being
+    class ``L - 1`` - the ``top_paths`` most probable label strings of each window and their probabilities.
+
+    The beam: at most ``beam_width`` entries ``(key, pb, pnb)``, from the empty prefix with ``(1, 0)``.  A step, for every entry
+    ``A`` with ``tot = pb + pnb``: stay ``pb' = tot * y[blank]``, ``pnb' = pnb * y[last(A)]`` (0 for the empty prefix); extend, for
+    every label ``c``, ``ext = (c == last(A) ? pb : tot) * y[c]`` - added to ``pnb'`` of ``A + c`` where that is a beam entry (its stay
+    term first, then one addition), else a new candidate ``(0, ext)``.  The next beam: the first ``beam_width`` candidates by
+    total ``pb' + pnb'`` descending (NaN ranks as -1), then key ascending (shorter first, then lexicographic).
+
+    float64 is the statement the library is tested against; with ``np.float32`` every operation is one float32 operation in the
+    header's order and the result carries ``ww_ctc_beam_rows``' bits.  ``trace`` (a list) receives per window a list of per-step
+    ``(ranks, keys)`` of ALL the step's candidates in the order - what a test needs to judge how close a pruning decision was."""
+    y = np.asarray(steps, dtype)
+    if y.ndim == 2:
+        y = y[None]
+    if y.ndim != 3:
+        raise ValueError(f"steps must be [n, T, L], got {y.shape}")
+    n, T, L = y.shape
+    W, P, M = _beam_args(T, L, beam_width, top_paths, max_labels)
+    dt = y.dtype.type
+    u = np.uint64
+    labels, lengths, probs = np.full((n, P, M), -1, np.int32), np.full((n, P), -1, np.int32), np.zeros((n, P), y.dtype)
+    cs = np.arange(L - 1)
+    for i in range(n):
+        key, pb, pnb = np.zeros(1, u), np.ones(1, y.dtype), np.zeros(1, y.dtype)
+        steps_trace = []
+        with np.errstate(all="ignore"):
+            for t in range(T):
+                row = y[i, t]
+                ln = (key >> u(_KEY_LEN_SHIFT)).astype(np.int64)
+                last = np.where(ln > 0, (key >> (_KEY_LEN_SHIFT - 3 * np.maximum(ln, 1)).astype(u)).astype(np.int64) & 7, -1)
+                tot = pb + pnb
+                st_pb = tot * row[L - 1]
+                st_pnb = np.where(last >= 0, pnb * row[np.maximum(last, 0)], dt(0))
+                ext = np.where(cs[None, :] == last[:, None], pb[:, None], tot[:, None]) * row[None, :L - 1]  # [nb, L - 1]
+                child = key[:, None] + (u(1) << u(_KEY_LEN_SHIFT)) + (cs[None, :].astype(u) << (_KEY_LEN_SHIFT - 3 * (ln[:, None] + 1)).astype(u))
+                # a child that is itself a beam entry takes the extension: its stay term first, then one addition
+                order = np.argsort(key)
+                pos = np.minimum(np.searchsorted(key[order], child), len(key) - 1)
+                found = key[order][pos] == child
+                st_pnb = st_pnb.copy()
+                tgt = order[pos[found]]
+                st_pnb[tgt] = st_pnb[tgt] + ext[found]
+                new = ~found
+                c_key = np.concatenate([key, child[new]])
+                c_pb = np.concatenate([st_pb, np.zeros(int(new.sum()), y.dtype)])
+                c_pnb = np.concatenate([st_pnb, ext[new]])
+                total = c_pb + c_pnb
+                rank = np.where(np.isnan(total), dt(-1), total)
+                sel = np.lexsort((c_key, -rank))
+                if trace is not None:
+                    steps_trace.append((rank[sel].copy(), c_key[sel].copy()))
+                sel = sel[:W]
+                key, pb, pnb = c_key[sel], c_pb[sel], c_pnb[sel]
+            total = pb + pnb
+        if trace is not None:
+            trace.append(steps_trace)
+        for p in range(min(P, len(key))):
+            if total[p] == 0:
+                continue
+            lab = key_labels(key[p])
+            lengths[i, p], probs[i, p] = len(lab), total[p]
+            labels[i, p, :min(M, len(lab))] = lab[:M]
+    return CtcBeam(labels, lengths, probs)
+
+
+def beam_rows(steps, beam_width: int, top_paths: int = 1, max_labels: Optional[int] = None) -> CtcBeam:
+    """``csrc/ctc_beam.h``'s float32 function over host arrays (``ww_ctc_beam_rows``; no GPU) - the bits the device kernel is held to."""
+    from . import _lib
+    y = np.ascontiguousarray(steps, np.float32)
+    if y.ndim == 2:
+        y = y[None]
+    if y.ndim != 3:
+        raise ValueError(f"steps must be [n, T, L], got {y.shape}")
+    n, T, L = y.shape
+    W, P = int(beam_width), int(top_paths)
+    M = T if max_labels is None else int(max_labels)
+    labels, lengths, probs = np.empty((n, max(P, 0), max(M, 0)), np.int32), np.empty((n, max(P, 0)), np.int32), np.empty((n, max(P, 0)), np.float32)
+    _lib.raise_for(_lib.load().ww_ctc_beam_rows(_lib.ptr(y), n, T, L, W, P, M, _lib.ptr(labels), _lib.ptr(lengths), _lib.ptr(probs)), None)
+    return CtcBeam(labels, lengths, probs)
 
 
 # the conv front of the standard geometry (a 151-row window -> 19 steps): kernel 20 rows, stride 8, 6 rows of padding in front

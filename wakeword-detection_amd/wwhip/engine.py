@@ -472,6 +472,61 @@ class Engine:
         self._chk(self._lib.ww_ctc_align_dev(self.ctx.handle, _vp(d_steps_ptr), int(n), int(T), int(L), _lib.ptr(table), _lib.ptr(lens), K, md,
                                              _vp(d_value_ptr), _vp(d_span_ptr)))
 
+    # the prefix beam search (include/wwhip.h: ww_ctc_beam_*; wwhip.ctc.beam_search is its float64 statement)
+    def _ctc_beam_out(self, n: int, beam_width: int, top_paths: int, max_labels):
+        W, P = int(beam_width), int(top_paths)
+        M = self.CTC_STEPS if max_labels is None else int(max_labels)
+        # (shapes only: the library names the rule a bad argument breaks)
+        return W, P, M, (np.full((n, max(P, 1), max(M, 1)), -1, np.int32), np.full((n, max(P, 1)), -1, np.int32), np.zeros((n, max(P, 1)), np.float32))
+
+    def ctc_beam(self, windows: np.ndarray, beam_width: int, top_paths: int = 1, max_labels: Optional[int] = None):
+        """``[B, window, 40]`` -> :class:`~wwhip.ctc.CtcBeam` ``(labels [B, P, max_labels], lengths [B, P], probs [B, P])``: the
+        ``top_paths`` most probable label strings of every window and their probabilities, by prefix beam search of width
+        ``beam_width`` over the posteriors :meth:`ctc_forward` returns as ``steps`` (``ww_ctc_beam``; ``K.ctc_decode(greedy=False)``'s
+        question, the statement in ``csrc/ctc_beam.h``).  An absent path has length -1 and probability 0."""
+        from .ctc import CtcBeam
+        w = np.ascontiguousarray(windows, dtype=np.float32)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.shape[1] != self.window or w.shape[2] != self.n_mel:
+            raise ValueError(f"Cannot set tensor: Dimension mismatch. Got {tuple(w.shape[1:])} but expected "
+                             f"{(self.window, self.n_mel)} per window")
+        n = w.shape[0]
+        W, P, M, (labels, lengths, probs) = self._ctc_beam_out(n, beam_width, top_paths, max_labels)
+        self._chk(self._lib.ww_ctc_beam(self.ctx.handle, self._model, _lib.ptr(w), n, W, P, M, _lib.ptr(labels), _lib.ptr(lengths), _lib.ptr(probs)))
+        return CtcBeam(labels, lengths, probs)
+
+    def ctc_slide_beam(self, mel: np.ndarray, hop: int = 2, beam_width: int = 8, top_paths: int = 1, max_labels: Optional[int] = None):
+        """:meth:`ctc_beam` of the windows sliding over one ``[rows, 40]`` sequence (``ww_ctc_slide_beam``)."""
+        from .ctc import CtcBeam
+        mm = np.ascontiguousarray(mel, dtype=np.float32)
+        if mm.ndim != 2 or mm.shape[1] != self.n_mel:
+            raise ValueError(f"mel must be [rows, {self.n_mel}]")
+        if hop < 1:
+            raise ValueError("hop must be positive")
+        rows = mm.shape[0]
+        nw = (rows - self.window) // hop + 1 if rows >= self.window else 0
+        W, P, M, (labels, lengths, probs) = self._ctc_beam_out(nw, beam_width, top_paths, max_labels)
+        got = C.c_int64(0)
+        self._chk(self._lib.ww_ctc_slide_beam(self.ctx.handle, self._model, _lib.ptr(mm), rows, int(hop), W, P, M, _lib.ptr(labels), _lib.ptr(lengths),
+                                              _lib.ptr(probs), C.byref(got)))
+        assert got.value == nw
+        return CtcBeam(labels, lengths, probs)
+
+    def ctc_beam_windows_dev(self, d_mel_ptr: int, mel_rows: int, d_win_row_ptr: int, d_win_valid_ptr: int, n_windows: int, beam_width: int,
+                             top_paths: int, max_labels: int, d_labels_ptr: int, d_lengths_ptr: int, d_prob_ptr: int) -> None:
+        """``ww_ctc_beam_windows_dev`` on device addresses: ``d_labels [n_windows, P, max_labels]`` int32, ``d_lengths`` and ``d_prob``
+        ``[n_windows, P]`` (enqueued on the context's stream)."""
+        self._chk(self._lib.ww_ctc_beam_windows_dev(self.ctx.handle, self._model, _vp(d_mel_ptr), int(mel_rows), _vp(d_win_row_ptr),
+                                                    _vp(d_win_valid_ptr), int(n_windows), int(beam_width), int(top_paths), int(max_labels),
+                                                    _vp(d_labels_ptr), _vp(d_lengths_ptr), _vp(d_prob_ptr)))
+
+    def ctc_beam_dev(self, d_steps_ptr: int, n: int, T: int, L: int, beam_width: int, top_paths: int, max_labels: int, d_labels_ptr: int,
+                     d_lengths_ptr: int, d_prob_ptr: int) -> None:
+        """``ww_ctc_beam_dev``: the beam kernel alone on device posteriors ``[n, T, L]`` (any model; the context is this engine's)."""
+        self._chk(self._lib.ww_ctc_beam_dev(self.ctx.handle, _vp(d_steps_ptr), int(n), int(T), int(L), int(beam_width), int(top_paths),
+                                            int(max_labels), _vp(d_labels_ptr), _vp(d_lengths_ptr), _vp(d_prob_ptr)))
+
     SEQUENCE_OUTPUTS = ("enc", "logits", "post_frames", "post")
 
     def sequence_forward(self, mels, pool: Optional[int] = None, want: Sequence[str] = ("post",)) -> dict:
@@ -1357,6 +1412,9 @@ class CtcTick(NamedTuple):
     scores: Optional[np.ndarray] = None
     align_values: Optional[np.ndarray] = None  # an ``align=True`` bank: [S, 2, K] float32, the best path's probability
     spans: Optional[np.ndarray] = None         # and [S, 2, K, U_max, 2] int32, its first / last step per label (wwhip.ctc.align)
+    beam_labels: Optional[np.ndarray] = None   # a ``beam_width=`` bank: [S, 2, P, M] int32 padded with -1 (wwhip.ctc.beam_search)
+    beam_lengths: Optional[np.ndarray] = None  # [S, 2, P] int32, -1: the path is absent
+    beam_probs: Optional[np.ndarray] = None    # [S, 2, P] float32, descending
 
 
 class CtcStreamBank(StreamBank):
@@ -1375,12 +1433,24 @@ class CtcStreamBank(StreamBank):
     windows' forward-algorithm scores, ``CtcTick.scores`` - one more small launch behind the tick's, over the posteriors, so the
     bank keeps them (``WW_STREAM_CTC_STEPS``) whether or not ``want_steps`` returns them.  :meth:`set_targets` changes them.  With ``align=True`` a tick also gives the
     windows' Viterbi alignment for the same targets and mode, ``CtcTick.align_values`` / ``CtcTick.spans`` (``wwhip.ctc.align``;
-    ``ww_stream_step_ctc_align``: one launch more)."""
+    ``ww_stream_step_ctc_align``: one launch more).
+
+    ``beam_width`` (1..64) with ``top_paths`` (1..min(beam_width, 8)) and ``beam_max_labels`` (1..19, all 19 by default): every tick
+    also gives the ``top_paths`` most probable label strings of its windows by prefix beam search, ``CtcTick.beam_labels`` /
+    ``beam_lengths`` / ``beam_probs`` (``wwhip.ctc.beam_search``; ``ww_stream_step_ctc_beam``: one more small launch over the
+    tick's posteriors, which the bank then keeps).  ``targets=`` together with ``beam_width=`` is not built: ``ValueError``."""
     MAX_LABELS = _lib.STREAM_CTC_MAX_LABELS
 
     def __init__(self, engine, n_streams: int, fp: Optional[_lib.FrontendParams] = None, max_labels: int = 2, want_steps: bool = False,
                  two_launch: bool = False, sync_wait: bool = False, full_recompute: bool = False, sample_rate=16000,
-                 sample_format="pcm16", resampler=None, targets=None, mode="exact", align: bool = False) -> None:
+                 sample_format="pcm16", resampler=None, targets=None, mode="exact", align: bool = False, beam_width: Optional[int] = None, top_paths: int = 1,
+                 beam_max_labels: Optional[int] = None) -> None:
+        if beam_width is not None and targets is not None:
+            raise ValueError("CtcStreamBank: targets= together with beam_width= is not built (a tick carries the scores or the beam)")
+        self.beam_width = None if beam_width is None else int(beam_width)
+        if self.beam_width is not None:  # (refused here, before a bank exists)
+            from . import ctc
+            _, self.top_paths, self.beam_max_labels = ctc._beam_args(Engine.CTC_STEPS, getattr(engine, "n_out", 2), self.beam_width, top_paths, beam_max_labels)
         if align and targets is None:
             raise ValueError("CtcStreamBank(align=True) aligns the bank's targets: give targets=")
         self.align = bool(align)
@@ -1390,7 +1460,7 @@ class CtcStreamBank(StreamBank):
             raise ValueError(f"max_labels {max_labels} outside 1..{self.MAX_LABELS}: a streamed window carries at most {self.MAX_LABELS} labels")
         self.max_labels, self.want_steps = int(max_labels), bool(want_steps)
         self.n_targets = 0
-        self._keep_steps = self.want_steps or targets is not None
+        self._keep_steps = self.want_steps or targets is not None or self.beam_width is not None
         if targets is not None:  # (refused here, before a bank exists)
             from . import ctc
             ctc.pack_targets(targets, engine.n_out), ctc.score_mode(mode)
@@ -1438,6 +1508,11 @@ class CtcStreamBank(StreamBank):
         self._p_labels, self._p_lengths, self._p_n, self._p_flags = (C.c_void_p(a.ctypes.data) for a in (self._labels, self._lengths, self._n, self._flags))
         self._p_steps = C.c_void_p(self._steps.ctypes.data) if self.want_steps else None
         self._keep = None
+        if self.beam_width is not None:
+            P, BM = self.top_paths, self.beam_max_labels
+            self._beam_labels, self._beam_lengths = np.full((S, 2, P, BM), -1, np.int32), np.full((S, 2, P), -1, np.int32)
+            self._beam_probs = np.zeros((S, 2, P), np.float32)
+            self._p_beam = tuple(C.c_void_p(a.ctypes.data) for a in (self._beam_labels, self._beam_lengths, self._beam_probs))
 
     def step(self, frames: np.ndarray, is_speech: np.ndarray, is_active: Optional[np.ndarray] = None) -> CtcTick:
         pf = self._frames_address(frames)
@@ -1448,7 +1523,10 @@ class CtcStreamBank(StreamBank):
         if is_active is not None:
             self._flags |= (np.ascontiguousarray(is_active, dtype=np.uint8).ravel() & 1) << 1
         self._clear()
-        if self.n_targets and self.align:
+        if self.beam_width is not None:
+            rc = self._lib.ww_stream_step_ctc_beam(self._h, pf, self._p_flags, self.max_labels, self._p_labels, self._p_lengths, self._p_steps,
+                                                   self.beam_width, self.top_paths, self.beam_max_labels, *self._p_beam, self._p_n)
+        elif self.n_targets and self.align:
             rc = self._lib.ww_stream_step_ctc_align(self._h, pf, self._p_flags, self.max_labels, self._p_labels, self._p_lengths, self._p_steps,
                                                     self._p_scores, self._p_align_values, self._p_spans, self._p_n)
         elif self.n_targets:
@@ -1471,12 +1549,17 @@ class CtcStreamBank(StreamBank):
         if self.n_targets and self.align:
             self._align_values[:] = 0.0
             self._spans[:] = -1
+        if self.beam_width is not None:
+            self._beam_labels[:] = -1
+            self._beam_lengths[:] = -1
+            self._beam_probs[:] = 0.0
 
     def _tick(self) -> CtcTick:
         return CtcTick(self._labels.copy(), self._lengths.copy(), self._n.copy(), None if self._steps is None else self._steps.copy(),
                        self._scores.copy() if self.n_targets else None,
                        self._align_values.copy() if self.n_targets and self.align else None,
-                       self._spans[:, :, :, :self._umax].astype(np.int32) if self.n_targets and self.align else None)
+                       self._spans[:, :, :, :self._umax].astype(np.int32) if self.n_targets and self.align else None,
+                       *((self._beam_labels.copy(), self._beam_lengths.copy(), self._beam_probs.copy()) if self.beam_width is not None else ()))
 
     def step_ctc_trigger(self, frames: np.ndarray, p_is_speech, p_is_active, p_target, n_target: int, p_state) -> CtcTick:
         """The wake-word stage of all streams as ONE library call (``ww_stream_step_ctc_trigger``): the tick, the label rule over

@@ -1146,7 +1146,7 @@ def ctc_statistics(y_true, y_pred) -> dict:
 
 
 def evaluate_ctc(engine: Engine, features: Sequence[np.ndarray], is_hotword: Sequence[int], target: Sequence[int] = (1, 2),
-                 thresholds=None, mode: str = "exact", windowsize: int = 1, align: bool = False) -> dict:
+                 thresholds=None, mode: str = "exact", windowsize: int = 1, align: bool = False, beam_width: Optional[int] = None) -> dict:
     """``eval_CTC`` (``wwdetect/CRNN/evaluate.py:100-150``) for a CTC-trained CRNN over the records of an H5 feature file:
     ``features`` is a list of ``[frames_i, n_mel]`` arrays (what ``DatasetFilter`` writes), ``is_hotword`` their attribute.  One
     upload of all rows, ONE ``ww_ctc_forward_windows_dev`` over descriptors - one window per clip, truncated to the model's window
@@ -1164,7 +1164,12 @@ def evaluate_ctc(engine: Engine, features: Sequence[np.ndarray], is_hotword: Seq
     ``align=True``: every clip also gets the Viterbi alignment of ``target`` in ``mode`` (``wwhip.ctc.align``; one
     ``ww_ctc_align_windows_dev`` over the same descriptors) - ``"align_value"`` ``[n]``, ``"spans"`` ``[n, len(target), 2]`` int32 (the
     first and last conv step of each label on the best path, -1 where there is none) and ``"span_seconds"`` (``wwhip.ctc.span_seconds``:
-    where in the clip each label lies)."""
+    where in the clip each label lies).
+
+    ``beam_width=W``: the rule is applied to the most probable label STRING of every clip, found by prefix beam search of width ``W``
+    (``wwhip.ctc.beam_search``; one ``ww_ctc_beam_windows_dev`` over the same descriptors), instead of the greedy decode - the
+    reference's ``eval_CTC`` with ``greedy=False``.  ``"labels"``, ``"lengths"``, ``"decoded"`` and ``"predicted"`` are then that
+    string's (length -1: no string has a probability above 0), and ``"beam_probs"`` ``[n]`` its probability."""
     import torch
 
     from . import ctc
@@ -1204,8 +1209,15 @@ def evaluate_ctc(engine: Engine, features: Sequence[np.ndarray], is_hotword: Seq
             torch.cuda.synchronize(dev)
             engine.ctc_align_windows_dev(d_mel.data_ptr(), total, d_row.data_ptr(), d_valid.data_ptr(), n, [tuple(int(c) for c in target)], mode,
                                          d_value.data_ptr(), d_span.data_ptr())
+        if beam_width is not None:
+            d_beam_prob = torch.empty(n, dtype=torch.float32, device=dev)
+            torch.cuda.synchronize(dev)
+            engine.ctc_beam_windows_dev(d_mel.data_ptr(), total, d_row.data_ptr(), d_valid.data_ptr(), n, int(beam_width), 1, k, d_lab.data_ptr(),
+                                        d_len.data_ptr(), d_beam_prob.data_ptr())
         engine.ctx.synchronize()
         labels, lengths = d_lab.cpu().numpy(), d_len.cpu().numpy()
+        if beam_width is not None:
+            beam_probs = d_beam_prob.cpu().numpy()
         if thresholds is not None:
             scores = d_score.cpu().numpy()
         if align:
@@ -1225,6 +1237,8 @@ def evaluate_ctc(engine: Engine, features: Sequence[np.ndarray], is_hotword: Seq
         if not n:
             align_value, spans = np.zeros(0, np.float32), np.full((0, len(target), 2), -1, np.int32)
         out.update(align_value=align_value, spans=spans, span_seconds=ctc.span_seconds(spans))
+    if beam_width is not None:
+        out.update(beam_probs=beam_probs if n else np.zeros(0, np.float32))
     return out
 
 
