@@ -496,6 +496,44 @@ int ww_ctc_beam_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_m
 int ww_ctc_slide_beam(ww_ctx *ctx, const ww_model *model, const float *mel, int64_t rows, int32_t hop, int32_t beam_width,
                       int32_t top_paths, int32_t max_labels, int32_t *labels, int32_t *lengths, float *prob, int64_t *n_windows);
 
+/* ---- CTC-trained CRNNs: HOW MUCH of each step belongs to each label (forward-backward occupancy) --------------------------------------
+ * The alignment gives the one best path; this is the posterior over ALL the paths that read the target: given that the window reads
+ * it, the share of step t that label u holds - the soft counterpart of the span, with the confidence of a boundary in it -, in
+ * prefix mode the distribution of the step that completes the wake word, and in exact mode the per-class share whose difference from
+ * the posteriors is the gradient of the CTC loss (-log of ww_ctc_score_*'s exact score) with respect to a step's logits.  The
+ * statement and its arithmetic: csrc/ctc_occupancy.h (wwhip.ctc.occupancy is the same in float64).  Arguments and limits are
+ * ww_ctc_score_*'s: y [T][L], targets [K][9], target_lens [K], mode
+ *   value [K][n] float32: Z, the bits of ww_ctc_score_* for the same mode
+ *   occ   [K][n][T][WW_CTC_SCORE_MAX_TARGET] float32: occ[t][u] = P(the path is on label u at step t | the target); in prefix mode
+ *     u = U - 1 holds P(the target is completed at step t | it is completed), which sums to 1 over t; rows u >= U are +0
+ *   cls   [K][n][T][L] float32, or NULL; exact mode only: the same posterior per CLASS (the blank included; a label that occurs twice
+ *     in the target gets both shares); every row sums to 1, and y - cls is d(-log Z)/d(logits)
+ *   Z == 0 (T too short, a zero posterior on every path, underflow): every occ and cls entry of the pair is +0
+ * Every byte of the K n entries of each output is written.  On the device and on the host the same float32 operations in the same
+ * order: ww_ctc_occupancy_dev gives the bits of ww_ctc_occupancy_rows.  Against the float64 statement on the same float32 posteriors
+ * an occ entry is within (6T + 4) 2^-24 relative, a cls entry within (6T + 4 + 2U) 2^-24, plus an absolute term for what lies under
+ * FLT_MIN (derived in tests/ctc_occupancy64.py).
+ * WW_EINVAL before anything is written, the text naming the rule: ww_ctc_score_*'s rules, a NULL value or occ, a cls in prefix mode.
+ * n = 0: WW_OK.
+ * ww_ctc_occupancy_dev - ctc_occupancy_kernel alone (csrc/ctc_occupancy.hip) on any device posteriors [n][T][L], enqueued on the
+ *   context's stream.
+ * ww_ctc_occupancy_rows - host only, no context (its refusal's text: ww_last_error(NULL)).
+ * ww_ctc_occupancy / _windows_dev / ww_ctc_slide_occupancy - ww_ctc_align / _windows_dev / ww_ctc_slide_align with this kernel in the
+ *   align kernel's place behind every chunk's model launch (T = 19, L = n_out); labels / lengths are the optional decode, as there. */
+int ww_ctc_occupancy_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, int32_t L, const int32_t *targets, const int32_t *target_lens,
+                         int32_t K, int32_t mode, float *d_value, float *d_occ, float *d_cls);
+int ww_ctc_occupancy_rows(const float *steps, int64_t n, int32_t T, int32_t L, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                          int32_t mode, float *value, float *occ, float *cls);
+int ww_ctc_occupancy(ww_ctx *ctx, const ww_model *model, const float *windows, int32_t n, const int32_t *targets, const int32_t *target_lens,
+                     int32_t K, int32_t mode, float *value, float *occ, float *cls, int32_t max_labels, int32_t *labels, int32_t *lengths);
+int ww_ctc_occupancy_windows_dev(ww_ctx *ctx, const ww_model *model, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                                 const int32_t *d_win_valid, int32_t n, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                                 int32_t mode, float *d_value, float *d_occ, float *d_cls, int32_t max_labels, int32_t *d_labels,
+                                 int32_t *d_lengths);
+int ww_ctc_slide_occupancy(ww_ctx *ctx, const ww_model *model, const float *mel, int64_t rows, int32_t hop, const int32_t *targets,
+                           const int32_t *target_lens, int32_t K, int32_t mode, float *value, float *occ, float *cls, int32_t max_labels,
+                           int32_t *labels, int32_t *lengths, int64_t *n_windows);
+
 /* ww_forward_windows_dev over a model set: window w is evaluated by member win_model[w], all windows in ONE launch (K checkpoints
  * over the same mel - the loop over eval_models of wwdetect/wavenet/evaluate_wavenet.py - are K x n windows that name the same rows).
  * win_model is a HOST array: read and checked before the call returns (an id outside [0, n_models): WW_EINVAL, nothing is launched),

@@ -29,7 +29,12 @@ Usage: python tools/ctc_bench.py align [rounds] [calls] [ticks] > profiles/ctc/a
 paths) beside ``ctc_score_windows_dev`` and ``ctc_forward_windows_dev`` on 256 and 4,096 resident windows, and ``ctc_beam_dev`` alone
 on the same posteriors, the sides alternated, then the per-kernel split; ``ww_ctc_beam_rows`` on the host for the same 4,096
 sequences; and the S = 128 ``CtcStreamBank`` tick with posteriors, with and without the beam, host time per ``step``.
-Usage: python tools/ctc_bench.py beam [rounds] [calls] [ticks] > profiles/ctc/beam_measured.txt"""
+Usage: python tools/ctc_bench.py beam [rounds] [calls] [ticks] > profiles/ctc/beam_measured.txt
+
+``occupancy``: what the forward-backward occupancy costs.  ``ctc_occupancy_dev`` (ctc_occupancy_kernel alone, two targets, exact mode,
+with and without ``cls``) beside ``ctc_score_dev`` and ``ctc_align_dev`` on the same 256 and 4,096 resident posteriors of the L = 4
+model, and the three ``_windows_dev`` forms (the model launches in front), the sides alternated, then the per-kernel split.
+Usage: python tools/ctc_bench.py occupancy [rounds] [calls] > profiles/ctc/occupancy_measured.txt"""
 import os
 import sys
 
@@ -349,9 +354,67 @@ def beam_mode(rounds: int, calls: int, ticks: int, S: int = 128) -> None:
     ctc.close()
 
 
+def occupancy_mode(rounds: int, calls: int) -> None:
+    ctx = _lib.Context(0)
+    ctc = Engine("synthetic-ctc-4", ctx=ctx, bundle=ctc64.model(4))
+    two = [(1, 2), (1, 1)]
+    for n in (256, 4096):
+        wins = ctc64.G.windows(7, min(n, 512), 151, 40)
+        d_mel = torch.from_numpy(np.ascontiguousarray(wins).reshape(-1, 40)).cuda()
+        d_row = (torch.arange(n, dtype=torch.int64, device="cuda") % len(wins)) * 151
+        d_valid = torch.full((n,), 151, dtype=torch.int32, device="cuda")
+        d_lab = torch.empty((n, 2), dtype=torch.int32, device="cuda")
+        d_len = torch.empty(n, dtype=torch.int32, device="cuda")
+        d_steps = torch.empty((n, 19, 4), dtype=torch.float32, device="cuda")
+        d_score = torch.empty((2, n), dtype=torch.float32, device="cuda")
+        d_span = torch.empty((2, n, 9, 2), dtype=torch.int8, device="cuda")
+        d_occ = torch.empty((2, n, 19, 9), dtype=torch.float32, device="cuda")
+        d_cls = torch.empty((2, n, 19, 4), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        a = (d_mel.data_ptr(), d_mel.shape[0], d_row.data_ptr(), d_valid.data_ptr(), n)
+        ctc.ctc_forward_windows_dev(*a, 2, d_lab.data_ptr(), d_len.data_ptr(), d_steps.data_ptr())
+        ctx.synchronize()
+        s = (d_steps.data_ptr(), n, 19, 4, two, "exact")
+        sides = {
+            "ctc_score_dev alone K=2 exact": lambda: ctc.ctc_score_dev(*s, d_score.data_ptr()),
+            "ctc_align_dev alone K=2 exact": lambda: ctc.ctc_align_dev(*s, d_score.data_ptr(), d_span.data_ptr()),
+            "ctc_occupancy_dev alone K=2 exact": lambda: ctc.ctc_occupancy_dev(*s, d_score.data_ptr(), d_occ.data_ptr()),
+            "ctc_occupancy_dev alone K=2 exact + cls": lambda: ctc.ctc_occupancy_dev(*s, d_score.data_ptr(), d_occ.data_ptr(), d_cls.data_ptr()),
+            "ctc_score_windows_dev K=2 exact": lambda: ctc.ctc_score_windows_dev(*a, two, "exact", d_score.data_ptr()),
+            "ctc_align_windows_dev K=2 exact": lambda: ctc.ctc_align_windows_dev(*a, two, "exact", d_score.data_ptr(), d_span.data_ptr()),
+            "ctc_occupancy_windows_dev K=2 exact": lambda: ctc.ctc_occupancy_windows_dev(*a, two, "exact", d_score.data_ptr(), d_occ.data_ptr()),
+            "ctc_occupancy_windows_dev K=2 exact + cls": lambda: ctc.ctc_occupancy_windows_dev(*a, two, "exact", d_score.data_ptr(), d_occ.data_ptr(),
+                                                                                               d_cls.data_ptr()),
+        }
+        for fn in sides.values():
+            for _ in range(5):
+                fn()
+        ctx.synchronize()
+        times = {k: [] for k in sides}
+        for _ in range(rounds):
+            for k, fn in sides.items():
+                ctx.timer_start()
+                for _ in range(calls):
+                    fn()
+                times[k].append(ctx.timer_stop() / calls * 1e3)
+        for k, t in times.items():
+            print(f"{n} windows, {k}: p50 {np.percentile(t, 50):.1f} us, p90 {np.percentile(t, 90):.1f} us per call "
+                  f"({rounds} rounds of {calls} calls, sides alternated)")
+        for k, fn in sides.items():
+            ctx.profile(True)
+            for _ in range(calls):
+                fn()
+            p = ctx.profile_read()
+            ctx.profile(False)
+            print(f"{n} windows, {k}, per kernel (us):", {name: round(v["total_ms"] / v["calls"] * 1e3, 1) for name, v in p.items()})
+    ctc.close()
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
-    if args and args[0] == "beam":
+    if args and args[0] == "occupancy":
+        occupancy_mode(int(args[1]) if len(args) > 1 else 9, int(args[2]) if len(args) > 2 else 200)
+    elif args and args[0] == "beam":
         beam_mode(int(args[1]) if len(args) > 1 else 9, int(args[2]) if len(args) > 2 else 200, int(args[3]) if len(args) > 3 else 300)
     elif args and args[0] == "align":
         align_mode(int(args[1]) if len(args) > 1 else 9, int(args[2]) if len(args) > 2 else 200, int(args[3]) if len(args) > 3 else 300)

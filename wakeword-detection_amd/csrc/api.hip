@@ -2,6 +2,7 @@
 #include "common.h"
 #include "ctc_align.h"
 #include "ctc_beam.h"
+#include "ctc_occupancy.h"
 #include "ctc_score.h"
 #include "model_pack.h"
 #include "model_set.h"
@@ -929,6 +930,73 @@ static int ctc_beam_host(ww_ctx *ctx, const ww_model *m, const float *mel, int64
   return io.finish();
 }
 
+// ---- the forward-backward occupancy (include/wwhip.h: ww_ctc_occupancy_*; csrc/ctc_occupancy.h) ---------------------------------------
+// what the three model forms refuse before anything is written: the score forms' rules, the occupancy's own (a NULL value or occ, a
+// cls in prefix mode)
+static int ctc_occupancy_check(ww_ctx *ctx, const ww_model *m, const int32_t *targets, const int32_t *target_lens, int K, int mode, const void *value,
+                               const void *occ, const void *cls, int max_labels, const void *labels, const void *lengths, const char *what,
+                               ww_ctc_score_targets &tg) {
+  if (!ctx || !m) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (int rc = ww_crnn_ctc_check(ctx, m, what)) return rc;
+  char why[200];
+  if (!ww_ctc_occupancy_args_ok(WW_CTC_STEPS, m->info.n_out, targets, target_lens, K, mode, value, occ, cls, why, sizeof why))
+    return ww_fail(ctx, WW_EINVAL, "%s: %s", what, why);
+  if ((labels == nullptr) != (lengths == nullptr)) return ww_fail(ctx, WW_EINVAL, "%s: labels and lengths go together", what);
+  if (labels && (max_labels < 1 || max_labels > WW_CTC_STEPS)) return ww_fail(ctx, WW_EINVAL, "%s: max_labels %d outside 1..%d", what, max_labels, WW_CTC_STEPS);
+  return ctc_score_targets_of(ctx, WW_CTC_STEPS, m->info.n_out, targets, target_lens, K, mode, what, tg);
+}
+
+// ctc_score_chunks with ctc_occupancy_kernel behind every chunk's model launch: d_value [K][nw], d_occ [K][nw][19][9] and, where not
+// nullptr, d_cls [K][nw][19][L] (d_labels / d_lengths: nullptr, or the decode beside them).  ws: ctc_score_workspace(m, nw) bytes
+// inside the device arena.
+static int ctc_occupancy_chunks(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_row, const int32_t *d_valid,
+                                int hop, int valid_const, int64_t nw, void *ws, const ww_ctc_score_targets &tg, float *d_value, float *d_occ,
+                                float *d_cls, int max_labels, int32_t *d_labels, int32_t *d_lengths) {
+  const int chunk = chunk_of(nw), L = m->info.n_out;
+  ww_bump bump(ws, ctc_score_workspace(m, nw));
+  float *d_steps = bump.take<float>((size_t)chunk * WW_CTC_STEPS * L);
+  int32_t *own_lab = bump.take<int32_t>((size_t)chunk), *own_len = bump.take<int32_t>((size_t)chunk);
+  void *mws = bump.base + bump.off;
+  const char *lo = (const char *)ctx->dev.ptr, *p = (const char *)mws;
+  const size_t cap = (p >= lo && p <= lo + ctx->dev.cap) ? (size_t)(lo + ctx->dev.cap - p) : 0;
+  for (int64_t w0 = 0; w0 < nw; w0 += chunk) {
+    const int n = (int)((nw - w0) < chunk ? (nw - w0) : chunk);
+    if (int rc = ww_k_crnn_ctc_forward(ctx, m, d_mel, mel_rows, d_row ? d_row + w0 : nullptr, d_row ? d_valid + w0 : nullptr, d_row ? 0 : w0 * hop,
+                                       hop, valid_const, n, mws, cap, d_labels ? max_labels : 1, d_labels ? d_labels + (size_t)w0 * max_labels : own_lab,
+                                       d_labels ? d_lengths + w0 : own_len, d_steps, nullptr))
+      return rc;
+    if (int rc = ww_k_ctc_occupancy(ctx, d_steps, n, WW_CTC_STEPS, L, tg, d_value + w0, d_occ + (size_t)w0 * WW_CTC_STEPS * WW_CTC_SCORE_MAX_TARGET,
+                                    d_cls ? d_cls + (size_t)w0 * WW_CTC_STEPS * L : nullptr, nw, 1))
+      return rc;
+  }
+  return WW_OK;
+}
+
+// the host forms: the sequence in, the K planes of value, occ and (where asked for) cls and the decode out, staged like ctc_score_host's
+static int ctc_occupancy_host(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t rows, int hop, int64_t nw, const ww_ctc_score_targets &tg,
+                              float *value, float *occ, float *cls, int max_labels, int32_t *labels, int32_t *lengths) {
+  const int T = m->info.window, F = m->info.n_mel, L = m->info.n_out;
+  const size_t n_val = (size_t)nw * tg.K, n_occ = n_val * WW_CTC_STEPS * WW_CTC_SCORE_MAX_TARGET, n_cls = cls ? n_val * WW_CTC_STEPS * L : 0;
+  const size_t n_lab = labels ? (size_t)nw * max_labels : 0;
+  WW_ON_DEVICE(ctx, dev_scope);  // the caller's current device is left as it was
+  const size_t b_io = ww_bump::need((size_t)rows * F, 4) + ww_bump::need(n_val, 4) + ww_bump::need(n_occ, 4) + (cls ? ww_bump::need(n_cls, 4) : 0) +
+                      (labels ? ww_bump::need(n_lab, 4) + ww_bump::need((size_t)nw, 4) : 0);
+  const size_t b_ws = ctc_score_workspace(m, nw);
+  ww_staged_io io(ctx);
+  int rc = io.init(b_io, b_ws + 1024, nw <= 64);
+  if (rc) return rc;
+  const float *d_mel = io.in(mel, (size_t)rows * F);
+  float *d_value = io.out<float>(n_val), *d_occ = io.out<float>(n_occ), *d_cls = cls ? io.out<float>(n_cls) : nullptr;
+  int32_t *d_lab = labels ? io.out<int32_t>(n_lab) : nullptr, *d_len = labels ? io.out<int32_t>((size_t)nw) : nullptr;
+  void *ws = io.scratch(b_ws);
+  if (io.rc) return io.rc;
+  if ((rc = ctc_occupancy_chunks(ctx, m, d_mel, rows, nullptr, nullptr, hop, T, nw, ws, tg, d_value, d_occ, d_cls, max_labels, d_lab, d_len))) return rc;
+  if ((rc = io.fetch(value, d_value, n_val * 4)) || (rc = io.fetch(occ, d_occ, n_occ * 4))) return rc;
+  if (cls && (rc = io.fetch(cls, d_cls, n_cls * 4))) return rc;
+  if (labels && ((rc = io.fetch(labels, d_lab, n_lab * 4)) || (rc = io.fetch(lengths, d_len, (size_t)nw * 4)))) return rc;
+  return io.finish();
+}
+
 __global__ void iota_offs_kernel(int64_t *sample_offs, int64_t *frame_offs, int n, int64_t samples, int64_t frames) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i <= n) {
@@ -1277,6 +1345,95 @@ int ww_ctc_beam_windows_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, 
   if (int rc = ww_ensure(ctx, ctx->dev, ctc_score_workspace(m, n) + 1024, false)) return rc;
   return ctc_beam_chunks(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, n, ctx->dev.ptr, beam_width, top_paths, max_labels, d_labels, d_lengths,
                          d_prob);
+  WW_GUARD_END(ctx)
+}
+
+// ---- the forward-backward occupancy (include/wwhip.h: ww_ctc_occupancy_*; csrc/ctc_occupancy.h): the align family's forms, one to one --
+int ww_ctc_occupancy_dev(ww_ctx *ctx, const float *d_steps, int64_t n, int32_t T, int32_t L, const int32_t *targets, const int32_t *target_lens,
+                         int32_t K, int32_t mode, float *d_value, float *d_occ, float *d_cls) {
+  WW_GUARD_BEGIN
+  if (!ctx) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  char why[200];
+  if (!ww_ctc_occupancy_args_ok(T, L, targets, target_lens, K, mode, d_value, d_occ, d_cls, why, sizeof why))
+    return ww_fail(ctx, WW_EINVAL, "ww_ctc_occupancy_dev: %s", why);
+  ww_ctc_score_targets tg;
+  if (int rc = ctc_score_targets_of(ctx, T, L, targets, target_lens, K, mode, "ww_ctc_occupancy_dev", tg)) return rc;
+  if (n < 0 || n > 0x7fffffff) return ww_fail(ctx, WW_EINVAL, "ww_ctc_occupancy_dev: sequence count out of range");
+  if (n == 0) return WW_OK;
+  if (!d_steps) return ww_fail(ctx, WW_EINVAL, "ww_ctc_occupancy_dev: steps is NULL");
+  WW_ON_DEVICE(ctx, dev);
+  return ww_k_ctc_occupancy(ctx, d_steps, n, T, L, tg, d_value, d_occ, d_cls, n, 1);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_occupancy_rows(const float *steps, int64_t n, int32_t T, int32_t L, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                          int32_t mode, float *value, float *occ, float *cls) {
+  WW_GUARD_BEGIN
+  char why[200];
+  if (!ww_ctc_occupancy_args_ok(T, L, targets, target_lens, K, mode, value, occ, cls, why, sizeof why))
+    return ww_fail(nullptr, WW_EINVAL, "ww_ctc_occupancy_rows: %s", why);
+  if (n < 0) return ww_fail(nullptr, WW_EINVAL, "ww_ctc_occupancy_rows: negative sequence count");
+  if (n == 0) return WW_OK;
+  if (!steps) return ww_fail(nullptr, WW_EINVAL, "ww_ctc_occupancy_rows: steps is NULL");
+  for (int k = 0; k < K; ++k)
+    for (int64_t i = 0; i < n; ++i) {
+      const size_t o = (size_t)k * n + i;
+      value[o] = ww_ctc_occupancy_row(steps + (size_t)i * T * L, T, L, L, targets + k * WW_CTC_SCORE_MAX_TARGET, target_lens[k], mode,
+                                      occ + o * T * WW_CTC_SCORE_MAX_TARGET, cls ? cls + o * T * L : nullptr);
+    }
+  return WW_OK;
+  WW_GUARD_END(nullptr)
+}
+
+int ww_ctc_occupancy(ww_ctx *ctx, const ww_model *m, const float *windows, int32_t n, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                     int32_t mode, float *value, float *occ, float *cls, int32_t max_labels, int32_t *labels, int32_t *lengths) {
+  WW_GUARD_BEGIN
+  ww_ctc_score_targets tg;
+  if (int rc = ctc_occupancy_check(ctx, m, targets, target_lens, K, mode, value, occ, cls, max_labels, labels, lengths, "ww_ctc_occupancy", tg)) return rc;
+  if (n < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
+  if (n == 0) return WW_OK;
+  if (!windows) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
+  // n stacked windows are one mel sequence of n * T rows read with hop = T
+  return ctc_occupancy_host(ctx, m, windows, (int64_t)n * m->info.window, m->info.window, n, tg, value, occ, cls, max_labels, labels, lengths);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_slide_occupancy(ww_ctx *ctx, const ww_model *m, const float *mel, int64_t rows, int32_t hop, const int32_t *targets,
+                           const int32_t *target_lens, int32_t K, int32_t mode, float *value, float *occ, float *cls, int32_t max_labels,
+                           int32_t *labels, int32_t *lengths, int64_t *n_windows) {
+  WW_GUARD_BEGIN
+  ww_ctc_score_targets tg;
+  if (int rc = ctc_occupancy_check(ctx, m, targets, target_lens, K, mode, value, occ, cls, max_labels, labels, lengths, "ww_ctc_slide_occupancy", tg))
+    return rc;
+  if (!n_windows) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (hop <= 0) return ww_fail(ctx, WW_EINVAL, "hop must be positive");
+  if (rows < 0) return ww_fail(ctx, WW_EINVAL, "negative row count");
+  const int T = m->info.window;
+  const int64_t nw = rows >= T ? (rows - T) / hop + 1 : 0;
+  if (nw > 0 && !mel) return ww_fail(ctx, WW_EINVAL, "NULL buffer");
+  *n_windows = nw;
+  if (nw == 0) return WW_OK;
+  return ctc_occupancy_host(ctx, m, mel, rows, hop, nw, tg, value, occ, cls, max_labels, labels, lengths);
+  WW_GUARD_END(ctx)
+}
+
+int ww_ctc_occupancy_windows_dev(ww_ctx *ctx, const ww_model *m, const float *d_mel, int64_t mel_rows, const int64_t *d_win_row,
+                                 const int32_t *d_win_valid, int32_t n, const int32_t *targets, const int32_t *target_lens, int32_t K,
+                                 int32_t mode, float *d_value, float *d_occ, float *d_cls, int32_t max_labels, int32_t *d_labels,
+                                 int32_t *d_lengths) {
+  WW_GUARD_BEGIN
+  ww_ctc_score_targets tg;
+  if (int rc = ctc_occupancy_check(ctx, m, targets, target_lens, K, mode, d_value, d_occ, d_cls, max_labels, d_labels, d_lengths,
+                                   "ww_ctc_occupancy_windows_dev", tg))
+    return rc;
+  if (n < 0) return ww_fail(ctx, WW_EINVAL, "negative window count");
+  if (n == 0) return WW_OK;
+  if (!d_mel) return ww_fail(ctx, WW_EINVAL, "NULL argument");
+  if (!d_win_row || !d_win_valid) return ww_fail(ctx, WW_EINVAL, "window descriptors are NULL");
+  WW_ON_DEVICE(ctx, dev);
+  if (int rc = ww_ensure(ctx, ctx->dev, ctc_score_workspace(m, n) + 1024, false)) return rc;
+  return ctc_occupancy_chunks(ctx, m, d_mel, mel_rows, d_win_row, d_win_valid, 0, 0, n, ctx->dev.ptr, tg, d_value, d_occ, d_cls, max_labels, d_labels,
+                              d_lengths);
   WW_GUARD_END(ctx)
 }
 

@@ -293,6 +293,11 @@ int ww_k_ctc_score(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, c
 // At o = k * stride_k + i * stride_i: d_value[o] and the 18 bytes d_span[18 o ..] ([WW_CTC_SCORE_MAX_TARGET][2] int8).
 int ww_k_ctc_align(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, const ww_ctc_score_targets &tg, float *d_value, int8_t *d_span,
                    int64_t stride_k, int64_t stride_i);
+// ctc_occupancy_kernel (ctc_occupancy.hip; the statement: ctc_occupancy.h): the forward-backward occupancy of the same K targets over
+// the same posteriors.  At o = k * stride_k + i * stride_i: d_value[o], d_occ[o][T][WW_CTC_SCORE_MAX_TARGET] and, where d_cls is not
+// nullptr (exact mode only), d_cls[o][T][L].  The arguments have passed ww_ctc_occupancy_args_ok.
+int ww_k_ctc_occupancy(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, const ww_ctc_score_targets &tg, float *d_value, float *d_occ,
+                       float *d_cls, int64_t stride_k, int64_t stride_i);
 // ctc_beam_kernel (ctc_beam.hip; the statement: ctc_beam.h): the prefix beam search over any device posteriors [n][T][L], a wave per
 // sequence: d_labels [n][P][max_labels], d_lengths [n][P], d_prob [n][P].  The arguments have passed ww_ctc_beam_args_ok.
 int ww_k_ctc_beam(ww_ctx *ctx, const float *d_steps, int64_t n, int T, int L, int W, int P, int max_labels, int32_t *d_labels, int32_t *d_lengths,

@@ -18,7 +18,7 @@ OBJ_DIR = os.path.join(CSRC, "build")
 LIB_PATH = os.path.join(PKG_DIR, "libwwhip.so")
 HOSTEXT_PATH = os.path.join(PKG_DIR, "_wwhostext.so")  # CPython extension: per-clip bookkeeping of the evaluators' staging (csrc/hostext.c)
 
-SOURCES = ["api.hip", "frontend.hip", "crnn.hip", "wavenet.hip", "posterior.hip", "streams.hip", "uploader.hip", "resample.hip", "ctc_score.hip", "ctc_align.hip", "ctc_beam.hip"]
+SOURCES = ["api.hip", "frontend.hip", "crnn.hip", "wavenet.hip", "posterior.hip", "streams.hip", "uploader.hip", "resample.hip", "ctc_score.hip", "ctc_align.hip", "ctc_beam.hip", "ctc_occupancy.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
 FLAGS += os.environ.get("WWHIP_DEFS", "").split()  # development only: e.g. WWHIP_DEFS="-DFPB=32"
 
@@ -42,7 +42,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "fft_device.h"), os.path.join(CSRC, "stream_fe.h"),
                os.path.join(CSRC, "host_stage.h"), os.path.join(CSRC, "model_layout.h"), os.path.join(CSRC, "model_pack.h"),
-               os.path.join(CSRC, "model_set.h"), os.path.join(CSRC, "ctc_decode.h"), os.path.join(CSRC, "ctc_score.h"), os.path.join(CSRC, "ctc_align.h"), os.path.join(CSRC, "ctc_beam.h"), os.path.join(CSRC, "stream_ctc.h"),
+               os.path.join(CSRC, "model_set.h"), os.path.join(CSRC, "ctc_decode.h"), os.path.join(CSRC, "ctc_score.h"), os.path.join(CSRC, "ctc_align.h"), os.path.join(CSRC, "ctc_beam.h"), os.path.join(CSRC, "ctc_occupancy.h"), os.path.join(CSRC, "stream_ctc.h"),
                os.path.join(CSRC, "launch_plan.h"), os.path.join(CSRC, "stream_rate.h"), os.path.join(CSRC, "stream_rates.h"),
                os.path.join(CSRC, "stream_formats.h"),
                os.path.join(CSRC, "stream_all.h"), os.path.join(CSRC, "events_plan.h"),

@@ -107,6 +107,11 @@ SYMBOLS: Dict[str, tuple] = {
     "ww_ctc_beam": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ww_ctc_beam_windows_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ww_ctc_slide_beam": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _P(_i64)]),
+    "ww_ctc_occupancy_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "ww_ctc_occupancy_rows": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "ww_ctc_occupancy": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "ww_ctc_occupancy_windows_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "ww_ctc_slide_occupancy": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _P(_i64)]),
     "ww_model_set_precision": (C.c_int, [_vp, C.c_int]),
     "ww_model_set_option": (C.c_int, [_vp, C.c_int, _i64]),
     "ww_model_set_create": (C.c_int, [_vp, _P(_vp), _i32, _P(_vp)]),

@@ -22,6 +22,11 @@ each label - where in the window the wake word lies, to one conv step (``csrc/ct
 decode collapses the most probable path - ``K.ctc_decode(greedy=False, beam_width, top_paths)``'s question.  ``csrc/ctc_beam.h``
 states it (the textbook search in the linear domain on the posteriors themselves; not TensorFlow's log-domain bits); the function
 here is that statement in float64, ``beam_rows`` the library's float32 function on the host.
+
+``occupancy`` is the forward-backward pass: given that a window reads a target, the share of each step that each label holds over
+ALL such paths, the completion step's distribution in prefix mode, and the per-class share whose difference from the posteriors is
+the gradient of the CTC loss with respect to a step's logits (``csrc/ctc_occupancy.h``; ``occupancy_rows`` is the library's float32
+function on the host, :class:`CtcOccupancy` carries ``blank``, ``loss``, ``grad`` and ``expected_step``).
 """
 from __future__ import annotations
 
@@ -256,6 +261,136 @@ def align_rows(steps, targets, mode="exact") -> CtcAlignment:
     _lib.raise_for(_lib.load().ww_ctc_align_rows(_lib.ptr(y), n, T, L, _lib.ptr(table), _lib.ptr(lens), len(lens), score_mode(mode),
                                                  _lib.ptr(value), _lib.ptr(span)), None)
     return CtcAlignment(value, span[:, :, :int(lens.max())].astype(np.int32))
+
+
+class CtcOccupancy(NamedTuple):
+    """``value [K, n]``: the score ``Z`` of target ``k`` over window ``i`` (:func:`score`'s, for the same mode);
+    ``occ [K, n, T, 9]``: given that the window reads the target, the probability that its path is on label ``u`` at step ``t``, over
+    all such paths (rows ``u >= U`` are 0); in prefix mode ``occ[..., U - 1]`` is the probability that step ``t`` COMPLETES the
+    target, which sums to 1 over ``t``.  ``cls [K, n, T, L]`` (exact mode, where asked for; else ``None``): the same posterior per
+    class, the blank included; every row sums to 1.  Where ``value == 0`` there is no such path and every entry is 0."""
+    value: np.ndarray
+    occ: np.ndarray
+    cls: Optional[np.ndarray] = None
+
+    @property
+    def blank(self) -> np.ndarray:
+        """``[K, n, T]``: ``1 - occ.sum(-1)``, in exact mode the blank's share of each step (it may be a rounding below 0)."""
+        return 1 - self.occ.sum(axis=-1)
+
+    @property
+    def loss(self) -> np.ndarray:
+        """``[K, n]``: ``-log(value)``, what ``K.ctc_batch_cost`` is on the posteriors themselves (``inf`` where ``value == 0``)."""
+        with np.errstate(divide="ignore"):
+            return -np.log(self.value)
+
+    def grad(self, steps) -> np.ndarray:
+        """``[K, n, T, L]``: ``steps - cls``, the gradient of :attr:`loss` with respect to the LOGITS of each step (the softmax's
+        inputs) of ``steps [n, T, L]``.  It is zeros where ``value == 0``: the loss is infinite there and has no gradient, and a
+        caller that sums these over clips must not take the posteriors themselves for an error signal.  Exact mode with ``cls``."""
+        if self.cls is None:
+            raise ValueError("grad needs cls: exact mode, want_classes=True")
+        y = np.asarray(steps, self.cls.dtype)
+        if y.ndim == 2:
+            y = y[None]
+        if y.shape != self.cls.shape[1:]:
+            raise ValueError(f"steps must be {self.cls.shape[1:]}, got {y.shape}")
+        return np.where((self.value == 0)[:, :, None, None], 0, y[None] - self.cls).astype(self.cls.dtype)
+
+    @property
+    def expected_step(self) -> np.ndarray:
+        """``[K, n, 9]``: per label ``sum_t t occ / sum_t occ``, the mean step of the label under the posterior over paths (in prefix
+        mode the last label's is the mean completion step); NaN where the label is absent or ``value == 0``."""
+        t = np.arange(self.occ.shape[2], dtype=np.float64)[None, None, :, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (t * self.occ).sum(axis=2) / self.occ.sum(axis=2, dtype=np.float64)
+
+
+def occupancy(steps, targets, mode="exact", dtype=np.float64) -> CtcOccupancy:
+    """``csrc/ctc_occupancy.h`` in ``dtype``: ``steps [n, T, L]`` (or ``[T, L]``) posteriors, ``targets`` a list of label tuples ->
+    :class:`CtcOccupancy` (``cls`` in exact mode, ``None`` in prefix mode).
+
+    :func:`score`'s lattice and forward variable ``a_t(s)``.  Exact: ``b_{T-1}(2U) = b_{T-1}(2U - 1) = 1``,
+    ``m_{t+1}(s) = b_{t+1}(s) y_{t+1}[cls(s)]``, ``b_t(s) = (m(s) + m(s + 1)) + (skip(s + 2) ? m(s + 2) : 0)`` - no ``y_t`` in ``b_t``,
+    so nothing is divided by a posterior -, ``Z = a_{T-1}(2U) + a_{T-1}(2U - 1)``, ``g_t(s) = a_t(s) b_t(s) / Z``;
+    ``occ[t, u] = g_t(2u + 1)`` and ``cls[t, k]`` the sum of ``g_t(s)`` over the states of class ``k`` in ascending ``s``.  Prefix: the
+    live states are ``0 .. 2U - 2``, ``b_{T-1} = 0``, the backward value of the completed state ``2U - 1`` is 1 at every step, ``Z`` is
+    the prefix score and ``occ[t, U - 1] = e_t / Z`` with ``e_t`` the score's completion term.  ``Z == 0``: everything is 0.
+
+    float64 is the statement the library is tested against; with ``np.float32`` every operation is one float32 operation in the
+    header's order and the result carries ``ww_ctc_occupancy_rows``' bits."""
+    y = np.asarray(steps, dtype)
+    if y.ndim == 2:
+        y = y[None]
+    if y.ndim != 3 or y.shape[1] < 1 or y.shape[2] < 2:
+        raise ValueError(f"steps must be [n, T >= 1, L >= 2], got {y.shape}")
+    n, T, L = y.shape
+    table, lens = pack_targets(targets, L)
+    prefix = score_mode(mode) == SCORE_MODES["prefix"]
+    K = len(lens)
+    value, occ = np.zeros((K, n), y.dtype), np.zeros((K, n, T, SCORE_MAX_TARGET), y.dtype)
+    cls_out = None if prefix else np.zeros((K, n, T, L), y.dtype)
+    zero, one = np.zeros(n, y.dtype), np.ones(n, y.dtype)
+    for k, U in enumerate(lens):
+        c = table[k, :U]
+        S = 2 * U + 1
+        cls = [L - 1 if s % 2 == 0 else int(c[(s - 1) // 2]) for s in range(S)]
+        skip = [s % 2 == 1 and s >= 3 and c[(s - 1) // 2] != c[(s - 3) // 2] for s in range(S)] + [False, False]
+        a = [[zero] * S for _ in range(T)]
+        a[0][0], a[0][1] = y[:, 0, L - 1], y[:, 0, c[0]]
+        e = [y[:, 0, c[0]] if U == 1 else zero]  # the completion terms, e_t
+        P = e[0]
+        for t in range(1, T):
+            p = a[t - 1]
+            e.append((p[S - 3] + (p[S - 4] if skip[S - 2] else zero)) * y[:, t, c[U - 1]])
+            P = P + e[t]
+            a[t] = [((p[s] + (p[s - 1] if s >= 1 else zero)) + (p[s - 2] if skip[s] else zero)) * y[:, t, cls[s]] for s in range(S)]
+        Z = P if prefix else a[T - 1][S - 1] + a[T - 1][S - 2]
+        if prefix:  # a_t(2U - 1) is not live: e_t sits there, under a backward value pinned to 1
+            for t in range(T):
+                a[t][S - 2] = e[t]
+        value[k] = Z
+        some = Z != 0
+        Zs = np.where(some, Z, 1)
+        b = [zero] * (S - 2) + [one, zero if prefix else one]
+        for t in range(T - 1, -1, -1):
+            g = [np.where(some, (a[t][s] * b[s]) / Zs, 0) for s in range(S)]
+            for u in range(U):
+                occ[k, :, t, u] = g[2 * u + 1]
+            if cls_out is not None:
+                seen = set()
+                for s in range(S):  # ascending s, from the first state of the class
+                    cls_out[k, :, t, cls[s]] = cls_out[k, :, t, cls[s]] + g[s] if cls[s] in seen else g[s]
+                    seen.add(cls[s])
+            if t == 0:
+                break
+            m = [b[s] * y[:, t, cls[s]] for s in range(S)] + [zero, zero]
+            b = [(m[s] + m[s + 1]) + (m[s + 2] if skip[s + 2] else zero) for s in range(S)]
+            if prefix:
+                b[S - 2], b[S - 1] = one, zero
+    return CtcOccupancy(value, occ, cls_out)
+
+
+def occupancy_rows(steps, targets, mode="exact", want_classes: Optional[bool] = None) -> CtcOccupancy:
+    """``csrc/ctc_occupancy.h``'s float32 function over host arrays (``ww_ctc_occupancy_rows``; no GPU) - the bits the device kernel
+    is held to.  ``want_classes``: ``cls`` too (the default in exact mode; the library refuses it in prefix mode)."""
+    from . import _lib
+    y = np.ascontiguousarray(steps, np.float32)
+    if y.ndim == 2:
+        y = y[None]
+    if y.ndim != 3:
+        raise ValueError(f"steps must be [n, T, L], got {y.shape}")
+    n, T, L = y.shape
+    table, lens = pack_targets(targets, L)
+    md = score_mode(mode)
+    if want_classes is None:
+        want_classes = md == SCORE_MODES["exact"]
+    K = len(lens)
+    value, occ = np.empty((K, n), np.float32), np.empty((K, n, max(T, 0), SCORE_MAX_TARGET), np.float32)
+    cls = np.empty((K, n, max(T, 0), max(L, 0)), np.float32) if want_classes else None
+    _lib.raise_for(_lib.load().ww_ctc_occupancy_rows(_lib.ptr(y), n, T, L, _lib.ptr(table), _lib.ptr(lens), K, md, _lib.ptr(value), _lib.ptr(occ),
+                                                     _lib.ptr(cls)), None)
+    return CtcOccupancy(value, occ, cls)
 
 
 BEAM_MAX_T, BEAM_MAX_L, BEAM_MAX_WIDTH, BEAM_MAX_PATHS = 19, 8, 64, 8  # include/wwhip.h: WW_CTC_BEAM_*

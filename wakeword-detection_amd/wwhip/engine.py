@@ -472,6 +472,75 @@ class Engine:
         self._chk(self._lib.ww_ctc_align_dev(self.ctx.handle, _vp(d_steps_ptr), int(n), int(T), int(L), _lib.ptr(table), _lib.ptr(lens), K, md,
                                              _vp(d_value_ptr), _vp(d_span_ptr)))
 
+    # the forward-backward occupancy (include/wwhip.h: ww_ctc_occupancy_*; wwhip.ctc.occupancy is its float64 statement)
+    def _ctc_occupancy_out(self, K: int, n: int, want_classes: bool):
+        value, occ = np.empty((K, n), np.float32), np.empty((K, n, self.CTC_STEPS, _lib.CTC_SCORE_MAX_TARGET), np.float32)
+        return value, occ, (np.empty((K, n, self.CTC_STEPS, self.n_out), np.float32) if want_classes else None)
+
+    def ctc_occupancy(self, windows: np.ndarray, targets=((1, 2),), mode="exact", want_classes: bool = False, max_labels: int = 0):
+        """``[B, window, 40]`` -> :class:`~wwhip.ctc.CtcOccupancy` ``(value [K, B], occ [K, B, 19, 9], cls [K, B, 19, n_out] | None)``:
+        per target and window, over ALL the paths that read (``mode="exact"``) or complete (``"prefix"``) the target, the share of
+        each conv step that each label holds - the soft counterpart of :meth:`ctc_align`'s span; in prefix mode the last label's
+        column is the distribution of the completion step (``ww_ctc_occupancy``).  ``value`` carries :meth:`ctc_score`'s bits.
+        ``want_classes`` (exact mode only) adds the per-class shares, whose difference from the posteriors is the CTC loss's
+        gradient (``CtcOccupancy.grad``).  With ``max_labels > 0`` the greedy decode comes with it:
+        ``(occupancy, CtcResult(labels, lengths))``."""
+        from .ctc import CtcOccupancy, CtcResult
+        table, lens, K, md = self._ctc_score_args(targets, mode, self.n_out)
+        w = np.ascontiguousarray(windows, dtype=np.float32)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.shape[1] != self.window or w.shape[2] != self.n_mel:
+            raise ValueError(f"Cannot set tensor: Dimension mismatch. Got {tuple(w.shape[1:])} but expected "
+                             f"{(self.window, self.n_mel)} per window")
+        n, m = w.shape[0], int(max_labels)
+        value, occ, cls = self._ctc_occupancy_out(K, n, want_classes)
+        labels, lengths = (np.full((n, m), -1, np.int32), np.zeros(n, np.int32)) if m else (None, None)
+        self._chk(self._lib.ww_ctc_occupancy(self.ctx.handle, self._model, _lib.ptr(w), n, _lib.ptr(table), _lib.ptr(lens), K, md, _lib.ptr(value),
+                                             _lib.ptr(occ), _lib.ptr(cls), m, _lib.ptr(labels), _lib.ptr(lengths)))
+        oc = CtcOccupancy(value, occ, cls)
+        return (oc, CtcResult(labels, lengths)) if m else oc
+
+    def ctc_slide_occupancy(self, mel: np.ndarray, hop: int = 2, targets=((1, 2),), mode="exact", want_classes: bool = False, max_labels: int = 0):
+        """:meth:`ctc_occupancy` of the windows sliding over one ``[rows, 40]`` sequence (``ww_ctc_slide_occupancy``): window ``i``
+        starts at row ``i * hop``."""
+        from .ctc import CtcOccupancy, CtcResult
+        table, lens, K, md = self._ctc_score_args(targets, mode, self.n_out)
+        mm = np.ascontiguousarray(mel, dtype=np.float32)
+        if mm.ndim != 2 or mm.shape[1] != self.n_mel:
+            raise ValueError(f"mel must be [rows, {self.n_mel}]")
+        if hop < 1:
+            raise ValueError("hop must be positive")
+        rows, m = mm.shape[0], int(max_labels)
+        nw = (rows - self.window) // hop + 1 if rows >= self.window else 0
+        value, occ, cls = self._ctc_occupancy_out(K, nw, want_classes)
+        labels, lengths = (np.full((nw, m), -1, np.int32), np.zeros(nw, np.int32)) if m else (None, None)
+        got = C.c_int64(0)
+        self._chk(self._lib.ww_ctc_slide_occupancy(self.ctx.handle, self._model, _lib.ptr(mm), rows, int(hop), _lib.ptr(table), _lib.ptr(lens), K, md,
+                                                   _lib.ptr(value), _lib.ptr(occ), _lib.ptr(cls), m, _lib.ptr(labels), _lib.ptr(lengths),
+                                                   C.byref(got)))
+        assert got.value == nw
+        oc = CtcOccupancy(value, occ, cls)
+        return (oc, CtcResult(labels, lengths)) if m else oc
+
+    def ctc_occupancy_windows_dev(self, d_mel_ptr: int, mel_rows: int, d_win_row_ptr: int, d_win_valid_ptr: int, n_windows: int, targets, mode,
+                                  d_value_ptr: int, d_occ_ptr: int, d_cls_ptr: int = 0, max_labels: int = 0, d_labels_ptr: int = 0,
+                                  d_lengths_ptr: int = 0) -> None:
+        """``ww_ctc_occupancy_windows_dev`` on device addresses: ``d_value [K, n_windows]``, ``d_occ [K, n_windows, 19, 9]`` and (0 = none)
+        ``d_cls [K, n_windows, 19, n_out]`` float32 (enqueued on the context's stream)."""
+        table, lens, K, md = self._ctc_score_args(targets, mode, self.n_out)
+        self._chk(self._lib.ww_ctc_occupancy_windows_dev(self.ctx.handle, self._model, _vp(d_mel_ptr), int(mel_rows), _vp(d_win_row_ptr),
+                                                         _vp(d_win_valid_ptr), int(n_windows), _lib.ptr(table), _lib.ptr(lens), K, md,
+                                                         _vp(d_value_ptr), _vp(d_occ_ptr), _vp(d_cls_ptr), int(max_labels), _vp(d_labels_ptr),
+                                                         _vp(d_lengths_ptr)))
+
+    def ctc_occupancy_dev(self, d_steps_ptr: int, n: int, T: int, L: int, targets, mode, d_value_ptr: int, d_occ_ptr: int, d_cls_ptr: int = 0) -> None:
+        """``ww_ctc_occupancy_dev``: the occupancy kernel alone on device posteriors ``[n, T, L]`` -> ``d_value [K, n]``,
+        ``d_occ [K, n, T, 9]`` and (0 = none) ``d_cls [K, n, T, L]`` float32 (any model; the context is this engine's)."""
+        table, lens, K, md = self._ctc_score_args(targets, mode, int(L))
+        self._chk(self._lib.ww_ctc_occupancy_dev(self.ctx.handle, _vp(d_steps_ptr), int(n), int(T), int(L), _lib.ptr(table), _lib.ptr(lens), K, md,
+                                                 _vp(d_value_ptr), _vp(d_occ_ptr), _vp(d_cls_ptr)))
+
     # the prefix beam search (include/wwhip.h: ww_ctc_beam_*; wwhip.ctc.beam_search is its float64 statement)
     def _ctc_beam_out(self, n: int, beam_width: int, top_paths: int, max_labels):
         W, P = int(beam_width), int(top_paths)
