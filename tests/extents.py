@@ -1,5 +1,6 @@
 """The extent of a call: which rows it may let into its result and which bytes it may write.  The harness of
-tests/test_extents.py (NumPy stand-ins: the harness must be able to fail) and tests/test_gpu_extents.py (the library's device calls).
+tests/test_extents.py (NumPy stand-ins: the harness must be able to fail), tests/test_gpu_extents.py and
+tests/test_gpu_extents_ctc.py (the library's device calls).
 
 A buffer handed to a call is a ``Guarded``: ONE allocation laid out as ``[front guard | body | back guard]``, of which the call gets
 the body's address and the body's extent.  Every address a test hands over therefore lies inside memory the test owns, and so does an
@@ -13,6 +14,9 @@ over-read or over-write of up to a guard's width; nothing here provokes a fault.
            spare row against zero weights, shows under the NaN alone: 0 * NaN is NaN, 0 * 1e30 is 0.  (tests/test_extents.py pins
            both cases.)
            int16 PCM has no NaN: its poisons are a full-scale +-32767 square wave and zeros.
+           A call whose every row is named (the CTC lattice calls read all of ``steps [n][T][L]``) gets a second kind of run: some
+           SEQUENCES of the body hold the poison (``poison_sequences``) and every other sequence's outputs must carry the clean
+           run's bits (``assert_others_same_bits``); what the poisoned sequences' own rows hold is reported, not asserted.
   outputs  the guards hold a sentinel (-7) and ``check_guards`` asserts that every guard byte is what it was.
 
 What the poison runs do NOT show: an over-read whose value is discarded (loaded and never used, or used only in lanes whose results
@@ -135,6 +139,51 @@ def poison_runs(run, poisons=tuple(POISONS), what: str = ""):
         for k in base:
             assert_same_bits(got[p][k], base[k], f"{what}: {k} under the {p} poison against the {poisons[-1]} baseline")
     return base
+
+
+def poison_sequences(steps: np.ndarray, which, poison) -> np.ndarray:
+    """A copy of ``steps`` (first axis: sequences) in which the sequences in ``which`` hold the poison in EVERY element.  For calls
+    whose every row is named (the CTC lattice calls take ``steps [n][T][L]`` and read all of it): the guards' poison says nothing
+    about a leak between two sequences of the body, a poisoned sequence beside a clean one does."""
+    out = np.array(steps, copy=True)
+    which = sorted(int(i) for i in which)
+    assert which and 0 <= which[0] and which[-1] < len(out), (which, len(out))
+    out[which] = fill_of(poison, out.dtype, 1)[0]
+    return out
+
+
+def assert_others_same_bits(got: dict, base: dict, which, axes: dict, what: str, show=None) -> None:
+    """The comparison of a poisoned-sequence run: every output of ``got`` carries the bits of ``base`` on every index of its sequence
+    axis (``axes[name]``) that is NOT in ``which``.  The poisoned sequences' own rows are not asserted - the reference does not define
+    them; ``show`` (a list) receives ``(name, own rows)`` for the caller to print."""
+    assert got.keys() == base.keys(), (what, sorted(got), sorted(base))
+    for k in base:
+        n = base[k].shape[axes[k]]
+        keep = np.ones(n, bool)
+        keep[sorted(int(i) for i in which)] = False
+        assert keep.any()
+        a, b = np.compress(keep, got[k], axis=axes[k]), np.compress(keep, base[k], axis=axes[k])
+        assert_same_bits(a, b, f"{what}: {k}, the sequences other than the poisoned {sorted(int(i) for i in which)}")
+        if show is not None:
+            show.append((k, np.compress(~keep, got[k], axis=axes[k])))
+
+
+def guarded_outputs(spec: dict, device: bool = False, rows: int = 2) -> dict:
+    """``{name: (shape, dtype)}`` -> ``{name: Guarded}``, each body and each guard full of the sentinel in the output's own dtype
+    (float32 value / occ / cls / prob, int8 span, int32 labels / lengths: -7 is a value of all of them).  A guard is ``rows`` rows of
+    the output (everything behind its first axis), at least 256 elements: a row or a plane stored behind the extent lands in it."""
+    out = {}
+    for name, (shape, dtype) in spec.items():
+        width = max(256, int(rows) * int(np.prod(shape[1:], dtype=np.int64)))
+        out[name] = Guarded(np.full(shape, SENTINEL, dtype), SENTINEL, width=width, device=device)
+    return out
+
+
+def read_outputs(outs: dict, what: str) -> dict:
+    """Every output's guards checked, then ``{name: host copy of the body}``."""
+    for name, g in outs.items():
+        g.check_guards(f"{what}: {name}")
+    return {name: g.read() for name, g in outs.items()}
 
 
 def window_layout(valid, gaps, T: int, tail_pair=None):

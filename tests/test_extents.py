@@ -5,12 +5,19 @@ The window op is the shape of the library's CRNN front: window ``w`` is ``valid[
 zero padded to ``T`` rows; a conv over time (``KT`` rows, stride 1), a ReLU, a mean and a sigmoid give one value per window.  The
 stand-ins index the ALLOCATION of a ``Guarded`` (guards included), as a kernel indexes memory: a mistaken index lands in a guard, not
 in a Python exception.  The ReLU comes in the two forms hardware offers - one that propagates a NaN (``np.maximum``) and the
-``v_max_f32`` form that returns the other operand (``np.fmax``) - because the second launders a NaN poison into the baseline's 0."""
+``v_max_f32`` form that returns the other operand (``np.fmax``) - because the second launders a NaN poison into the baseline's 0.
+
+Further down: a stand-in of the segmented CTC lattice (pairs packed P lanes apart, neighbours by a shift of the whole vector) in three
+variants - edge lanes that select 0 (passes), that multiply by a 0 mask (fails under the NaN alone), and a tail segment that stores
+(trips the output guard) - and the library's host functions ``ww_ctc_{score,align,beam,occupancy}_rows`` through every layout and
+assertion that tests/test_gpu_extents_ctc.py makes of the device kernels (tests/extents_ctc.py states them once for both)."""
 import numpy as np
 import pytest
 
+import ctc64
 import events64 as E
 import extents as X
+import extents_ctc as EC
 
 T, F, KT = 24, 8, 4
 VALID = [T, 0, T, 1, 9, T - 1, T, 9]
@@ -148,3 +155,152 @@ def test_clean_smoothing_passes_and_is_the_float64_statement():
 def test_smoothing_that_reads_one_element_before_its_segment_is_rejected():
     with pytest.raises(AssertionError, match="nan poison"):
         X.poison_runs(lambda p: run_smooth(p, mutant=True), poisons=("nan", "zero"), what="smoothing")
+
+
+# ---------------------------------------------------------------------------------------------------- the segmented CTC lattice
+# The shape of ctc_score_kernel (csrc/ctc_score.hip): the forward recursion of every (sequence, target) pair in ONE flat vector of
+# lanes, pair j in lanes [j P, (j + 1) P), a(s - 1) and a(s - 2) fetched by a shift of the WHOLE vector - so what lane 0 and lane 1 of
+# a segment receive is the neighbour pair's.  The grid is rounded up to whole workgroups of 256 / P segments; a segment past the last
+# pair repeats the last pair's work.  Scores go to ``out[pair]`` (the bank's [windows][K] layout).
+LAT_P, LAT_UMAX = 4, 1       # 2 U + 1 = P - 1: lane P - 2 of a segment is live, and a shift by 2 brings it to the next segment's lane 0
+
+
+def lattice_op(steps: X.Guarded, n, T, L, targets, out: X.Guarded, variant=None, P=LAT_P):
+    """``variant``: ``None`` - the edge lanes SELECT 0; ``"mask"`` - they multiply what the shift brought by a 0 mask; ``"tail"`` - a
+    segment past the last pair stores its repeat."""
+    k_n = len(targets)
+    total, per = n * k_n, 256 // P
+    segs = -(-total // per) * per
+    lane = np.arange(segs * P)
+    s, raw = lane % P, lane // P
+    pair = np.minimum(raw, total - 1)
+    i, k = pair // k_n, pair % k_n
+    tab = np.array([list(c) + [0] * (EC.NU - len(c)) for c in targets])
+    U = np.array([len(c) for c in targets])[k]
+    on, odd, u = s < 2 * U + 1, (s % 2 == 1), np.minimum(np.maximum(s - 1, 0) // 2, EC.NU - 1)
+    cls = np.where(on & odd, tab[k, u], L - 1)
+    skip = on & odd & (u >= 1) & (tab[k, u] != tab[k, np.maximum(u - 1, 0)])
+    dt = out.dtype                                # the arithmetic's type: float32 as the kernel's, or float64 (below)
+    m, o, zero = steps.buf.astype(dt), out.buf, dt.type(0)
+    col = steps.width + i * T * L + cls
+
+    def shr(v, d):
+        return np.concatenate([np.zeros(d, dt), v[:-d]])
+    a = np.where(on & (s <= 1), m[col], zero)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for t in range(1, T):
+            y, a1, a2 = m[col + t * L], shr(a, 1), shr(a, 2)
+            if variant == "mask":
+                a1, a2 = a1 * (s >= 1).astype(dt), a2 * skip.astype(dt)
+            else:
+                a1, a2 = np.where(s >= 1, a1, zero), np.where(skip, a2, zero)
+            a = np.where(on, ((a + a1) + a2) * y, zero)
+        exact = a + shr(a, 1)
+    store = (s == 2 * U) & ((raw < total) | (variant == "tail"))
+    o[out.width + raw[store]] = exact[store]
+
+
+def run_lattice(poison, variant=None, poisoned=None, T=4, L=4, dtype=np.float32, umax=LAT_UMAX):
+    n, targets = EC.N_SEQ, EC.targets_of(umax, L)
+    y = EC.tables(45, n, T, L)
+    body = y if poisoned is None else X.poison_sequences(y, poisoned, poison)
+    steps = X.Guarded(body, poison, width=EC.steps_guard(T, L))
+    outs = X.guarded_outputs({"score": ((n, EC.K), dtype)})
+    lattice_op(steps, n, T, L, targets, outs["score"], variant, EC.SEGMENT[umax])
+    steps.check_guards(f"steps ({poison})")
+    return X.read_outputs(outs, f"lattice stand-in ({poison}, {variant})")
+
+
+def lattice_standin_case(variant, poisons, T=4, dtype=np.float32, umax=LAT_UMAX):
+    poisoned = EC.check_edges(EC.SEGMENT[umax])
+    base = X.poison_runs(lambda p: run_lattice(p, variant, None, T, dtype=dtype, umax=umax), what=f"stand-in {variant}")
+    for p in poisons:
+        X.assert_others_same_bits(run_lattice(p, variant, poisoned, T, dtype=dtype, umax=umax), base, poisoned, {"score": 0},
+                                  f"stand-in {variant}, {p} poison")
+    return base
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("T", [1, 2, 4, 9, 19])
+def test_lattice_standin_that_selects_passes_and_is_the_statement(T, dtype):
+    from wwhip import ctc
+    got = lattice_standin_case(None, tuple(X.POISONS), T, dtype)["score"]
+    want = ctc.score(EC.tables(45, EC.N_SEQ, T, 4), EC.targets_of(LAT_UMAX, 4), "exact", dtype)
+    X.assert_same_bits(got, np.ascontiguousarray(want.T), f"the stand-in against wwhip.ctc.score in {np.dtype(dtype)}, T = {T}")
+    assert T < 2 or (got > 0).sum() > got.size // 2
+
+
+def test_lattice_standin_that_masks_fails_under_the_nan_alone():
+    """Lane 0 of a segment multiplies the neighbour's a(2U) by a 0 mask: 0 * NaN is NaN, 0 * 1e30 is 0.  The neighbour's a(2U) is
+    not 0 from step 1 on, leaks into lane 0 at step 2 and reaches the score's lanes at step 3: T = 4.  In float32 a sequence of 1e30
+    has overflowed by then (1e30 * 1e30), and 0 * Inf is NaN too - there both poisons show the mistake; the arithmetic in float64,
+    where 1e30^4 is finite, shows what the 1e30 poison alone is worth against this mistake: nothing."""
+    lattice_standin_case("mask", ("1e30", "zero"), dtype=np.float64)
+    with pytest.raises(AssertionError, match="nan poison"):
+        lattice_standin_case("mask", ("nan",), dtype=np.float64)
+    lattice_standin_case("mask", tuple(X.POISONS), T=3)      # (one step too few for the leak to reach a score)
+    for p in ("nan", "1e30"):
+        with pytest.raises(AssertionError, match=f"{p} poison"):
+            lattice_standin_case("mask", (p,))
+
+
+@pytest.mark.parametrize("umax", list(EC.SEGMENT))
+def test_lattice_standin_at_every_segment_width(umax):
+    """The stand-in at the widths and target lengths of section E, T = 19: the select passes and is the float32 statement; the 0 mask
+    is rejected wherever a shift can reach across two pairs at all - P = 4, 8, 16, where the longest target fills P - 1 lanes and is
+    the sequence's last.  At P = 32 the 13 idle lanes of a segment keep a shift by 2 to itself, and the mask goes unnoticed."""
+    from wwhip import ctc
+    got = lattice_standin_case(None, tuple(X.POISONS), 19, umax=umax)["score"]
+    want = ctc.score(EC.tables(45, EC.N_SEQ, 19, 4), EC.targets_of(umax, 4), "exact", np.float32)
+    X.assert_same_bits(got, np.ascontiguousarray(want.T), f"the stand-in against wwhip.ctc.score in float32, Umax = {umax}")
+    if EC.SEGMENT[umax] < 32:
+        with pytest.raises(AssertionError, match="nan poison"):
+            lattice_standin_case("mask", ("nan",), 19, umax=umax)
+    else:
+        lattice_standin_case("mask", tuple(X.POISONS), 19, umax=umax)
+
+
+def test_lattice_standin_whose_tail_segments_store_trips_the_output_guard():
+    """The repeat carries the last pair's value: in the body nothing would show.  Only the guard behind ``out`` does."""
+    with pytest.raises(AssertionError, match="back guard"):
+        run_lattice("zero", "tail")
+
+
+# ---------------------------------------------------------------------------------------------------- the host twins, section E's cases
+@pytest.fixture(scope="module")
+def host():
+    return EC.Backend()
+
+
+@pytest.mark.parametrize("umax", list(EC.SEGMENT))
+@pytest.mark.parametrize("name", ["score", "align", "occupancy"])
+def test_host_lattice_functions_pass_section_e(host, name, umax):
+    """``ww_ctc_{score,align,occupancy}_rows`` through every layout and assertion the device kernels get
+    (tests/test_gpu_extents_ctc.py): the cases are well formed, and the reference itself keeps every sequence to itself."""
+    for T in EC.TS:
+        for L in ctc64.LS:
+            for mode in EC.MODES:
+                base = EC.lattice_case(host, name, umax, T, L, mode)
+                assert np.isfinite(base["score" if name == "score" else "value"]).all()
+                if name == "occupancy" and mode == "exact":
+                    both = EC.lattice_case(host, name, umax, T, L, mode, want_cls=True)
+                    for k in base:
+                        X.assert_same_bits(both[k], base[k], f"occupancy {k} with and without cls")
+    live = EC.lattice_case(host, name, umax, 19, 4, "prefix")["score" if name == "score" else "value"]
+    assert (live > 0).sum() > live.size // 2     # (the cases are not all-zero scores)
+
+
+@pytest.mark.parametrize("W", [1, 8, 64])
+def test_host_beam_function_passes_section_e(host, W):
+    for T in EC.BEAM_TS:
+        for L in ctc64.LS:
+            for P in sorted({1, min(W, 8)}):     # top_paths is at most min(beam_width, WW_CTC_BEAM_MAX_PATHS = 8)
+                base = EC.beam_case(host, T, L, W, P)
+                assert (base["lengths"][:, 0] >= 0).all() and (base["prob"][:, 0] > 0).all()
+
+
+def test_greedy_statement_passes_section_e(host):
+    for T in EC.TS:
+        for L in ctc64.LS:
+            base = EC.greedy_case(host, T, L)
+            assert (base["lengths"] >= 0).all() and (base["lengths"] <= T).all()

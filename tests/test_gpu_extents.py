@@ -11,6 +11,7 @@ every other output row's bits alone; what its own row holds is printed, not asse
   B  sliding forms    ww_forward_segments_dev, ww_set_forward_segments_dev; Engine.slide_forward, ww_ctc_slide_forward
   C  clips, front end ww_clips_forward_dev, ww_logmel_dev
   D  evaluator tail   ww_far_frr_dev (with d_smoothed), ww_posterior_pick_dev, ww_posterior_events_dev
+  E, F                the CTC lattice calls; the host-pointer ticks and ww_resample_dev: tests/test_gpu_extents_ctc.py
 
 No address handed to the library lies outside an allocation of the test's, guards included; nothing here is expected to fault.
 tests/test_extents.py shows on NumPy stand-ins that this harness rejects the mistakes it is there for.
