@@ -5,7 +5,7 @@
 set -e
 cd "$(dirname "$0")/.."
 name=$1; defs=$2; shift 2 || true
-sources="api.hip frontend.hip crnn.hip wavenet.hip posterior.hip streams.hip uploader.hip resample.hip"  # = wwhip/_build.py: SOURCES
+sources="api.hip frontend.hip crnn.hip wavenet.hip posterior.hip streams.hip uploader.hip resample.hip ctc_score.hip ctc_align.hip ctc_beam.hip ctc_occupancy.hip"  # = wwhip/_build.py: SOURCES
 only=${@:-$sources}
 mkdir -p build_variants/obj_$name
 objs=""

@@ -527,8 +527,8 @@ __device__ __forceinline__ float4 pj_w_ld(pj_gptr4 p) {
 // 14.8k cycles over 9.6k cycles of MFMAs and its partner advanced only once it was alone).
 // LDS: the window image (28.9 KB; after B it holds the last six feat rows, then gx, seq1, h, the head's small vectors) + feat
 // rows 0..12 (33.7 KB; after C the head's first layer) = 62.6 KB (78.1 KB until the end of round 4: CF_FUSED_SMEM_BYTES below),
-// two workgroups per CU - one's recurrences and staging run beside the other's MFMA phases - with room for two front-end
-// workgroups beside them.
+// two workgroups per CU - one's recurrences and staging run beside the other's MFMA phases - with room for four front-end
+// waves beside them (one four-wave workgroup of logmel_rows_kernel, 36,864 B; two two-wave ones of 17 KB until EXPERIMENTS 24).
 // ------------------------------------------------------------------------------------------
 #define CF_THREADS 256
 #define CF_FLD 648  // feat row: 640 + 8; FLD/4 = 162 = 2 (mod 16): the 16-lane groups of the A-operand ds_read_b128 hit 16 distinct slots

@@ -627,20 +627,22 @@ __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// logmel_rows_kernel (round 4): the fp64 front end with NOTHING shared between the waves of a workgroup.
+// logmel_rows_kernel (round 4): the fp64 front end with next to nothing shared between the waves of a workgroup
+// (since section 24 of profiles/EXPERIMENTS.md: the Hann half table, behind one barrier at the top).
 //
 // Why.  In the pipelined step the front end of batch i+1 runs in the shadow of batch i's crnn_fused_kernel, whose one
 // wave per SIMD keeps the shared fp32-MFMA / vector datapath about half busy; how much of the other half the front end
 // picks up is set by how many of its waves fit beside a CRNN workgroup.  The fp64 tile kernel of rounds 1-3 cost 10 KB of LDS and
 // 128 registers per wave (40 KB per 4-wave workgroup: the 16-frame sample tile + Hann table + three transpose buffers), so two
-// workgroups = 8 waves fit.  This kernel costs 8.5 KB and 104 registers per wave and no workgroup barrier:
+// workgroups = 8 waves fit.  This kernel costs 8.5 KB and 104 registers per wave and one workgroup barrier, in front of the transform:
 //   * a wave owns the four consecutive GLOBAL frames 4 W .. 4 W + 3 of the launch (mel rows are numbered through all
 //     clips), so tiles run across clip boundaries: 37,632 frames = 9,408 full waves, none of the 256 three-frame tiles of
 //     the per-clip tiling, and ragged batches leave no partly filled workgroups behind;
 //   * it stages its own samples (<= 512 + 3 hop, two 16-byte loads per lane) into ITS transpose buffer, which is dead
 //     until the first DFT pass is over: LDS instructions of one wave execute in order, so neither the hand-over of the
 //     buffer from tile to transposes to magnitudes to the output tile nor the staging needs a barrier;
-//   * Hann pairs and twiddles come from the L1-resident tables (4 + 4 + 4 KB, shared by every wave of the chip);
+//   * Hann pairs come from the workgroup's Hann block in LDS (LW_HANN_N below), twiddles from the L1-resident tables (4 + 4 KB,
+//     shared by every wave of the chip);
 //   * 104 registers (amdgpu_num_vgpr counts in units of two on gfx90a+): the Hann products, the inter-pass twiddles and the
 //     untangling twiddles are software-pipelined by hand in chunks of 4 / 3 / 2 instead of all at once, and the mel
 //     weights are requested as the untangling retires registers: three of these waves sit on a SIMD beside a 184-register
@@ -650,17 +652,28 @@ __global__ __launch_bounds__(256, 5) void logmel_kernel(logmel_args a) {
 // instruction, with bit-identical results (profiles/EXPERIMENTS.md, round 4).
 // What it has in common with logmel_kernel is the shared pieces above, instantiated for one wave and R = double: staging
 // (LM_STAGE_SIMPLE_LOAD / LM_STAGE_SIMPLE_STORE with NV vectors per lane and idx_t indices; stage_generic_wave = LM_STAGE_GENERIC at
-// stride 64), hann_pair on the global double2 table with hann_mul_pair / hann_mul_at per chunk of LW_HC, LM_PARTNERS,
+// stride 64), lw_hann_pair on the Hann block with hann_mul_pair / hann_mul_at per chunk of LW_HC, LM_PARTNERS,
 // LM_UNTANGLE_K2 on a register chunk of W512^k, untangle_tail, LM_MEL_REQ_* and LM_MEL_COMPUTE.  Its own: the row -> clip
 // lookup, the chunked table fetches, the fp64 transposes (lds_read16_b64) and the final store, whose rows are global (vm)
 // instead of per clip.
 // ---------------------------------------------------------------------------------------------------------------------
 #ifndef LW_WPB
-#define LW_WPB 2  // waves per workgroup (they share nothing).  Same box, rocprofv3, 256 / 4,096 clips: 4 waves 27.96 / 353.5 us,
-#endif            // 2 waves 27.2-27.5 / 350.5-352.0, 1 wave 27.6 / 350.9; rounds 1-3's fp64 tile kernel 27.3-27.8 / 356.4-357.6
+#define LW_WPB 4  // waves per workgroup: they share the Hann block and nothing else.  Chosen on the PIPELINED step, where the
+#endif            // front end runs beside two CRNN workgroups: 40.83 us at 2 waves, 40.22 at 4 (nothing shared), 39.70 at 4 with
+// the Hann block (profiles/EXPERIMENTS.md, section 24; why 4 sits better there is not known).  The kernel ALONE is slower at 4: same
+// box, rocprofv3, 256 / 4,096 clips, nothing shared: 4 waves 27.96 / 353.5 us, 2 waves 27.2-27.5 / 350.5-352.0.
+// The Hann block behind the per-wave buffers: the half table of 128 pairs (h[2n], h[2n+1]) as the global table holds it, 2,048 B.
+// Thread t < 128 fetches pair t beside its wave's samples and parks it; ONE barrier, and every Hann pair of the transform is a
+// ds_read_b128 at an immediate offset from one of two per-lane addresses (a 16-lane row reads 256 contiguous bytes: no conflict).
+// 4 x 8,704 + 2,048 = 36,864 B per workgroup: four workgroups on a CU alone, one beside two crnn_fused_kernel workgroups at any
+// allocation granule up to 2 KB - the sixteen and the four waves that fitted before.  The W512 and W256 twiddles stay in L1: with
+// them the block no longer fits beside the CRNN, and the step gains nothing (section 24).
+#define LW_HANN_N 128
+static_assert(LW_HANN_N <= 64 * LW_WPB, "one 16-byte load per thread fills the Hann block");
 
 #ifndef LW_HC
-#define LW_HC 4    // Hann pairs fetched per chunk (16 / LW_HC chunks, double-buffered)
+#define LW_HC 4    // Hann pairs fetched per chunk (16 / LW_HC chunks, double-buffered; sized when the pairs came through L1 and kept for
+                   // the LDS block: chunks of 2 or 8 spill registers, section 24)
 #endif
 #ifndef LW_TC
 #define LW_TC 3    // inter-pass twiddles fetched per chunk (15 / LW_TC chunks, double-buffered)
@@ -687,6 +700,20 @@ __device__ __forceinline__ int64_t lw_readlane64(int64_t v, int src_lane) {
 }
 
 __device__ __forceinline__ int lw_readlane64(int v, int src_lane) { return __builtin_amdgcn_readlane(v, src_lane); }
+
+// Entry e of the Hann block as an LDS pointer the compiler knows nothing about (see lds_opaque), and hann_pair on the block:
+// pf = entry j, pr = entry 15 - j
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) const f64x2 lds_cf64x2;
+__device__ __forceinline__ lds_cf64x2 *lw_hann_entry(const unsigned char *blk, int e) {
+  unsigned p = (unsigned)(uintptr_t)blk + 16u * (unsigned)e;  // low 32 bits of a flat LDS pointer = the LDS byte address
+  asm volatile("" : "+v"(p));
+  return (lds_cf64x2 *)(uintptr_t)p;
+}
+__device__ __forceinline__ double2 lw_hann_pair(lds_cf64x2 *pf, lds_cf64x2 *pr, int n1) {
+  const f64x2 t = n1 < 8 ? pf[16 * n1] : pr[16 * (15 - n1)];
+  return n1 < 8 ? make_double2(t.x, t.y) : make_double2(t.y, t.x);
+}
 template <bool SMALL> struct lw_idx { typedef int64_t type; };
 template <> struct lw_idx<true> { typedef int type; };  // every sample index of the launch fits 31 bits (the host checked)
 
@@ -704,7 +731,11 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
   const int nper = gridDim.x >> 3;
   const int64_t W = ((int64_t)(blockIdx.x & 7) * nper + (blockIdx.x >> 3)) * LW_WPB + wave;
   const int64_t g0 = W * 4;
-  if (g0 >= a.total_frames) return;  // no barrier anywhere below: a wave may simply leave
+  // this thread's pair of the Hann block, requested in front of the wave's samples: the two round trips overlap.  A wave without
+  // rows (g0 past the launch's last row: rv below is false in every lane) parks its share, passes the one barrier and leaves
+  unsigned char *hblk = smem + (size_t)LW_WPB * LW_WBUF;
+  uint4 hv = make_uint4(0, 0, 0, 0);
+  if ((int)threadIdx.x < LW_HANN_N) hv = ((const uint4 *)a.hann)[threadIdx.x];
   unsigned char *wb = smem + (size_t)wave * LW_WBUF;
   float *tile = (float *)wb;
 
@@ -746,44 +777,50 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
     }
   }
   const unsigned long long vm = __ballot(rv);
-  if (vm == 0) return;
-  const int r_first = __builtin_ctzll(vm) >> 4, r_last = (63 - __builtin_clzll(vm)) >> 4;
-  const idx_t b0 = lw_readlane64(b, 16 * r_first), s0 = lw_readlane64(s_begin, 16 * r_first);
-  if (!rv) {  // surplus rows recompute the first valid frame (results unused)
-    b = b0;
-    s_begin = s0;
-  }
-  const idx_t total = (idx_t)a.sample_offs[a.n_utt];
-  // one contiguous tile serves the wave when every row starts within 3 hops of the first one, in the same clip
-  const bool contig = __all(s_begin == s0 && b >= b0 && b - b0 <= 3 * (idx_t)a.hop);
-  const float *src;
-  if (contig) {
-    const idx_t bmax = lw_readlane64(b, 16 * r_last);
-    const int shift = (int)(b0 % VEC);
-    const idx_t ga = b0 - shift;  // multiple of VEC, >= 0
-    const int n_vec = (shift + (int)(bmax - b0) + WIN + VEC - 1) / VEC;
-    if (SIMPLE) {
-      // No pre-emphasis, divisor 32767/32768, hop <= 168 (host checks): NV vectors per lane, straight-line: all loads in
-      // flight together
-      constexpr int NV = F32IN ? 4 : 2;
-      idx_t gq[NV];
-      uint4 raw[NV];
-      LM_STAGE_SIMPLE_LOAD(F32IN, NV, 64, idx_t, a, ga, n_vec, total, lane, gq, raw);
-      LM_STAGE_SIMPLE_STORE(F32IN, NV, 64, idx_t, a, tile, n_vec, total, lane, gq, raw);
+  const float *src = tile;
+  int r_last = 0;
+  if (vm != 0) {  // (a wave without rows has nothing to stage)
+    const int r_first = __builtin_ctzll(vm) >> 4;
+    r_last = (63 - __builtin_clzll(vm)) >> 4;
+    const idx_t b0 = lw_readlane64(b, 16 * r_first), s0 = lw_readlane64(s_begin, 16 * r_first);
+    if (!rv) {  // surplus rows recompute the first valid frame (results unused)
+      b = b0;
+      s_begin = s0;
+    }
+    const idx_t total = (idx_t)a.sample_offs[a.n_utt];
+    // one contiguous tile serves the wave when every row starts within 3 hops of the first one, in the same clip
+    const bool contig = __all(s_begin == s0 && b >= b0 && b - b0 <= 3 * (idx_t)a.hop);
+    if (contig) {
+      const idx_t bmax = lw_readlane64(b, 16 * r_last);
+      const int shift = (int)(b0 % VEC);
+      const idx_t ga = b0 - shift;  // multiple of VEC, >= 0
+      const int n_vec = (shift + (int)(bmax - b0) + WIN + VEC - 1) / VEC;
+      if (SIMPLE) {
+        // No pre-emphasis, divisor 32767/32768, hop <= 168 (host checks): NV vectors per lane, straight-line: all loads in
+        // flight together
+        constexpr int NV = F32IN ? 4 : 2;
+        idx_t gq[NV];
+        uint4 raw[NV];
+        LM_STAGE_SIMPLE_LOAD(F32IN, NV, 64, idx_t, a, ga, n_vec, total, lane, gq, raw);
+        LM_STAGE_SIMPLE_STORE(F32IN, NV, 64, idx_t, a, tile, n_vec, total, lane, gq, raw);
+      } else {
+        stage_generic_wave<F32IN>(a, tile, (int64_t)ga, n_vec, (int64_t)s0, (int64_t)total, lane);
+      }
+      src = tile + shift + (int)(b - b0);
     } else {
-      stage_generic_wave<F32IN>(a, tile, (int64_t)ga, n_vec, (int64_t)s0, (int64_t)total, lane);
+      // frames of two clips (or a very short one) in this wave: frame by frame
+      for (int r = 0; r < 4; ++r) {
+        if (!((vm >> (16 * r)) & 1)) continue;
+        const int64_t br = lw_readlane64(b, 16 * r), sr = lw_readlane64(s_begin, 16 * r);
+        const int sh = (int)(br % VEC);
+        stage_generic_wave<F32IN>(a, tile + r * LW_ROWF, br - sh, (sh + WIN + VEC - 1) / VEC, sr, (int64_t)total, lane);
+      }
+      src = tile + (rv ? sub : r_first) * LW_ROWF + (int)(b % VEC);
     }
-    src = tile + shift + (int)(b - b0);
-  } else {
-    // frames of two clips (or a very short one) in this wave: frame by frame
-    for (int r = 0; r < 4; ++r) {
-      if (!((vm >> (16 * r)) & 1)) continue;
-      const int64_t br = lw_readlane64(b, 16 * r), sr = lw_readlane64(s_begin, 16 * r);
-      const int sh = (int)(br % VEC);
-      stage_generic_wave<F32IN>(a, tile + r * LW_ROWF, br - sh, (sh + WIN + VEC - 1) / VEC, sr, (int64_t)total, lane);
-    }
-    src = tile + (rv ? sub : r_first) * LW_ROWF + (int)(b % VEC);
   }
+  if ((int)threadIdx.x < LW_HANN_N) ((uint4 *)hblk)[threadIdx.x] = hv;
+  __syncthreads();  // the only barrier: behind it the waves share nothing but the (constant) Hann block
+  if (vm == 0) return;
   lds_fence();
 
   // ---- FFT: every 16-lane row of the wave owns one frame
@@ -795,13 +832,13 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
   double2 tq[2][LW_TC];
   {
     // pass 1: lane j holds z[16 n1 + j], n1 = 0..15; Hann product in fp64 (tflite.py:175).  Hann pairs (h[2n], h[2n+1]),
-    // n = 16 n1 + j, from the half table of 128 pairs (h[m] = h[511 - m]) through the vector L1, four n1 at a time and one
+    // n = 16 n1 + j, from the half table of 128 pairs (h[m] = h[511 - m]) in the Hann block, four n1 at a time and one
     // chunk ahead: 16 + 16 registers instead of the 64 of the whole set
-    const double2 *hb = (const double2 *)a.hann;
+    lds_cf64x2 *pf = lw_hann_entry(hblk, j), *pr = lw_hann_entry(hblk, 15 - j);
     constexpr int HC = LW_HC, NHC = 16 / HC;  // Hann pairs per chunk; one chunk in flight ahead of the one being used
     double2 h[2][HC];
 #pragma unroll
-    for (int i = 0; i < HC; ++i) h[0][i] = hann_pair(hb, i, j);
+    for (int i = 0; i < HC; ++i) h[0][i] = lw_hann_pair(pf, pr, i);
     const bool pairs = __all((((int)(src - tile)) & 1) == 0);
     if (pairs) {
       // 8-byte aligned pairs: ds_read_b64 (with hop = 160 the four frames of a wave sit 32 banks apart: conflict-free)
@@ -811,7 +848,7 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
       for (int c = 0; c < NHC; ++c) {
         if (c + 1 < NHC) {
 #pragma unroll
-          for (int i = 0; i < HC; ++i) h[(c + 1) & 1][i] = hann_pair(hb, HC * (c + 1) + i, j);
+          for (int i = 0; i < HC; ++i) h[(c + 1) & 1][i] = lw_hann_pair(pf, pr, HC * (c + 1) + i);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (c == 0) lds_wait_all(xs);
@@ -824,7 +861,7 @@ __global__ __launch_bounds__(64 * LW_WPB) __attribute__((amdgpu_num_vgpr(LW_VGPR
       for (int c = 0; c < NHC; ++c) {
         if (c + 1 < NHC) {
 #pragma unroll
-          for (int i = 0; i < HC; ++i) h[(c + 1) & 1][i] = hann_pair(hb, HC * (c + 1) + i, j);
+          for (int i = 0; i < HC; ++i) h[(c + 1) & 1][i] = lw_hann_pair(pf, pr, HC * (c + 1) + i);
         }
 #pragma unroll
         for (int i = 0; i < HC; ++i) v[HC * c + i] = hann_mul_at<R>(src, 16 * (HC * c + i) + j, h[c & 1][i]);
@@ -1031,7 +1068,7 @@ int ww_k_logmel(ww_ctx *ctx, const ww_model *m, const int16_t *d_pcm, const floa
     const int64_t n_wg = 8 * ((((n_waves + LW_WPB - 1) / LW_WPB) + 7) / 8);
     if (n_wg > 0x7fffffff) return ww_fail(ctx, WW_EINVAL, "front-end launch too large (%lld workgroups): split the batch", (long long)n_wg);
     const dim3 grid_w((unsigned)n_wg), block_w(64 * LW_WPB);
-    const size_t sm = (size_t)LW_WPB * LW_WBUF;
+    const size_t sm = (size_t)LW_WPB * LW_WBUF + LW_HANN_N * 16;  // per-wave buffers, Hann block
     ww_launch_scope scope(ctx, "logmel_rows_kernel");
     hipLaunchKernelGGL(logmel_instance(true, f32in, simple_w, small_w), grid_w, block_w, sm, ctx->stream, a);
     WW_HIP(ctx, hipGetLastError());
